@@ -8,14 +8,16 @@ primus_ntt/src/dcrt/prime64.rs:106) over a batch of 4096 RNS polynomials = 12 28
 shard across GPUs with no collective: each rank owns its own batch of 4096
 ("weak" scaling); torch.distributed is used only for the timing barrier.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  Every rank also runs the RLWE external product (config 4; batch 1024
-per GPU, aggregated over ranks = config 5's scaling curve).  Extra legs on rank 0 at N = 1:
-per-kernel HIP-event timing for the roofline object, the fused NTT->mul->INTT rate (config 3), the
-u32 tables, and a bounded CPU run of the oracle (the C restatement of the reference's scalar path)
-for `cpu_baseline`.
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up and K timed steps, writes the
+last step's output with --dump-outputs, and prints the line.  With --full every rank also runs
+the RLWE external product (config 4; batch 1024 per GPU, aggregated over ranks = config 5's
+scaling curve), and rank 0 at N = 1 the extra legs: device-copy bandwidth, per-kernel HIP-event
+timing for the roofline object, the fused NTT->mul->INTT rate (config 3), the u32 tables, and a
+bounded CPU run of the oracle (the C restatement of the reference's scalar path) for
+`cpu_baseline`.
 """
 from __future__ import annotations
 
@@ -36,6 +38,7 @@ if ROOT not in sys.path:
 Q61 = [2305843009211596801, 2305843009210023937, 2305843009208713217]
 LOG_N = 16
 SEED_NTT, SEED_CONFIG5, SEED_GGSW = 0x5EED000000000003, 0x5EED000000000005, 99
+SEED_DUMP, DUMP_WORDS = 0x5EED0000000000D0, 1 << 20  # --dump-outputs: which words of the output are written
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is achievable
 
 
@@ -57,15 +60,22 @@ def parse_args():
                     "the visible GPUs first (a rank whose GPU is missing fails by itself and ends its peers)")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even with one rank (test aid: "
                     "exercises the RCCL barrier / max-reduce on a 1-GPU box)")
-    ap.add_argument("--dump-dir", default="", help="parity aid for tests/test_gpu_shard.py: every rank writes the HIP "
-                    "outputs of its shard (one forward NTT of its RNS polynomials, its config-5 products) as "
+    ap.add_argument("--dump-dir", default="", help="parity aid for tests/test_gpu_shard.py (with --full): every rank writes "
+                    "the HIP outputs of its shard (one forward NTT of its RNS polynomials, its config-5 products) as "
                     "rank<r>.npz into this directory; small --batch / --ext-total only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one "
+                    "computed as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--full", action="store_true", help="also run every other leg: device-copy bandwidth, external "
+                    "products (configs 4, 5, u32), per-kernel roofline objects, sustained rate, inverse / generic-prime / "
+                    "N=2^14 / polymul / u32 legs and the CPU baseline.  Without it a run times the headline step only")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when bench.py spawns the ranks itself")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     args = ap.parse_args()
     if args.gpus is None:  # `torchrun --nproc-per-node N bench.py` without --gpus
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_dir and not args.full:
+        ap.error("--dump-dir needs --full (its config-5 products come from a --full leg)")
     return args
 
 
@@ -413,6 +423,30 @@ def pmc_traffic(kernel: str, batch: int):
     return None
 
 
+def dump_outputs(out_dir: str, x, name: str) -> None:
+    """--dump-outputs: what the timed step leaves its caller — the batch of RNS polynomials after the forward transform,
+    canonical residues in bit-reversed order — as out_dir/<name>.npy.  A fixed sample of DUMP_WORDS words (positions drawn
+    with SEED_DUMP, sorted; every word when the batch is smaller) keeps the file at 16 MiB.  Each 64-bit word is stored
+    as its four 16-bit limbs, most significant first, in float32, which holds them exactly: shape (words, 4)."""
+    import torch
+    words = x.numel()
+    if words > DUMP_WORDS:
+        idx = np.sort(np.random.default_rng(SEED_DUMP).choice(words, DUMP_WORDS, replace=False))
+    else:
+        idx = np.arange(words)
+    w = x[torch.from_numpy(idx).to(x.device)].cpu().numpy().view(np.uint64)
+    limbs = (w[:, None] >> np.array([48, 32, 16, 0], np.uint64)) & np.uint64(0xFFFF)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), limbs.astype(np.float32))
+
+
+def finish(result: dict, rank: int, dist) -> None:
+    if rank == 0:
+        print(json.dumps(result))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
 def spawn_ranks(args) -> int:
     """`python bench.py --gpus N` outside a launcher: start N fresh rank processes (one per GPU, the
     environment torch.distributed.run would give them) and relay rank 0's JSON line.  The parent never execs and runs
@@ -509,7 +543,7 @@ def main():
     # element-wise copy kernel and by the library's 16-bytes-per-lane non-temporal copy kernel, HIP events on the launch
     # stream; the best one is `peak_measured`
     copy_bw = None
-    if rank == 0 and not args.dump_dir and words >= (1 << 24):
+    if args.full and rank == 0 and not args.dump_dir and words >= (1 << 24):
         half = (words // 2) & ~1
         src, dst = x[:half], x[half:2 * half]
         st = torch.cuda.current_stream()
@@ -546,6 +580,8 @@ def main():
 
     dt = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, dist,
                      "cuda" if args.dist_backend == "nccl" else "cpu")
+    if args.dump_outputs:  # before any --full leg reuses the buffer
+        dump_outputs(args.dump_outputs, x, "ntt_out" if world == 1 else "ntt_out_rank%d" % rank)
 
     limb_ntts = world * batch * L * args.steps
     value = limb_ntts / dt
@@ -571,6 +607,8 @@ def main():
     }
     if dist_seen is not None and dist_seen["world_size"] != world:
         raise SystemExit("bench.py: the process group has %d ranks, the launcher said %d" % (dist_seen["world_size"], world))
+    if not args.full:  # a plain run ends with the headline step; every leg below is --full
+        return finish(result, rank, dist)
 
     # ---- config 4 / 5: RNS gadget external product, k=1, logB=30 (ell=6), batch 1024 per GPU, one shared
     #      GGSW replicated per device; every rank runs it, the rate is aggregated over ranks (weak scaling,
@@ -925,11 +963,7 @@ def main():
         del k32, o32, ctx32
         if not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
-
-    if rank == 0:
-        print(json.dumps(result))
-    if dist is not None:
-        dist.destroy_process_group()
+    finish(result, rank, dist)
 
 
 if __name__ == "__main__":

@@ -63,7 +63,7 @@ def test_ranks_on_one_device_through_bench_entry(tmp_path, orc, world, batch, to
     # batch: per-rank RNS polynomials of the NTT leg; total: ciphertexts of the config-5 job
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--one-device", "--dist-backend", "gloo",
            "--batch", str(batch), "--ext-batch", "2", "--ext-total", str(total), "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--dump-dir", str(tmp_path)] + extra
+           "--no-cpu-baseline", "--full", "--dump-dir", str(tmp_path)] + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -166,7 +166,7 @@ def test_bench_under_the_launcher_with_rccl(tmp_path):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2",
-           "--warmup", "1", "--batch", "16", "--ext-batch", "4", "--ext-total", "8", "--no-cpu-baseline"]
+           "--warmup", "1", "--batch", "16", "--ext-batch", "4", "--ext-total", "8", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -174,3 +174,35 @@ def test_bench_under_the_launcher_with_rccl(tmp_path):
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["external_product_config5"]["batch_total"] == 8
     assert "roofline" in line
+
+
+def test_plain_bench_run_times_the_headline_step_and_dumps_its_output(tmp_path, orc):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the line carries the headline fields
+    and none of the --full legs, and DIR/ntt_out.npy is the fixed sample of what the last timed step left in the buffer —
+    the synthetic batch after W + K forward transforms, checked word for word against the oracle."""
+    import bench
+
+    steps, warmup, batch = 3, 1, 8
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--batch", str(batch), "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["unit"] == "NTT/s" and line["higher_is_better"] is True and line["dtype"] == "u64"
+    assert line["metric"].startswith("NTT/sec at N=2^16") and line["steps"] == steps and line["warmup"] == warmup
+    assert line["value"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 - batch * 3) < 1e-6 * batch * 3
+    assert not {"external_product", "external_product_config5", "roofline", "cpu_baseline", "sustained"} & set(line)
+    dumped = np.load(os.path.join(tmp_path, "ntt_out.npy"))
+    words = batch * 3 * N
+    assert dumped.dtype == np.float32 and dumped.shape == (bench.DUMP_WORDS, 4)
+    limbs = dumped.astype(np.uint64)
+    got = (limbs[:, 0] << 48) | (limbs[:, 1] << 32) | (limbs[:, 2] << 16) | limbs[:, 3]
+    exp = fill_uniform_words(bench.SEED_NTT, 0, words, bench.Q61, N)
+    o = orc.U64DcrtTable(LOG_N, bench.Q61)
+    for _ in range(warmup + steps):
+        o.transform_slice(exp)
+    idx = np.sort(np.random.default_rng(bench.SEED_DUMP).choice(words, bench.DUMP_WORDS, replace=False))
+    assert np.array_equal(got, exp[idx]), "dumped output != oracle after warmup + steps forward transforms"

@@ -289,3 +289,27 @@ def test_bench_line_fields_of_round_6():
     assert b["polymul_per_element"]["algorithmic_bytes_per_product"] == 72 * 65536
     assert b["polymul"]["algorithmic_bytes_per_product"] == 48 * 65536
     assert b["roofline_generic"]["frac"] < b["roofline"]["frac"]
+
+
+def test_bench_dump_outputs_sample_is_exact_and_fixed(tmp_path):
+    """--dump-outputs writes a fixed, seeded sample of the output words as float32 16-bit limbs: the words come back
+    exactly, the positions do not depend on the run, and the file stays far below 64 MB."""
+    import torch
+
+    import bench
+    words = 3 * bench.DUMP_WORDS
+    vals = np.random.default_rng(5).integers(0, bench.Q61[0], words, dtype=np.uint64)
+    x = torch.from_numpy(vals.view(np.int64))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), x, "ntt_out")
+    a, b = np.load(tmp_path / "a" / "ntt_out.npy"), np.load(tmp_path / "b" / "ntt_out.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_WORDS, 4) and np.array_equal(a, b)
+    assert os.path.getsize(tmp_path / "a" / "ntt_out.npy") < 64 << 20
+    limbs = a.astype(np.uint64)
+    got = (limbs[:, 0] << 48) | (limbs[:, 1] << 32) | (limbs[:, 2] << 16) | limbs[:, 3]
+    idx = np.sort(np.random.default_rng(bench.SEED_DUMP).choice(words, bench.DUMP_WORDS, replace=False))
+    assert np.array_equal(got, vals[idx])
+    small = torch.from_numpy(vals[:1000].view(np.int64))   # a batch below the sample size is written whole
+    bench.dump_outputs(str(tmp_path / "c"), small, "ntt_out")
+    limbs = np.load(tmp_path / "c" / "ntt_out.npy").astype(np.uint64)
+    assert np.array_equal((limbs[:, 0] << 48) | (limbs[:, 1] << 32) | (limbs[:, 2] << 16) | limbs[:, 3], vals[:1000])

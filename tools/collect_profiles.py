@@ -24,7 +24,7 @@ d = collections.defaultdict(list)
 for r in csv.DictReader(open(tr)):
     g = int(r.get("Grid_Size", r.get("Grid_Size_X", 0)))
     d[(short(r["Kernel_Name"]), g)].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
-lines = ["rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline   (grouped by kernel and grid size,",
+lines = ["rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline   (grouped by kernel and grid size,",
          "because the timed steps launch the two passes per 1/8-batch tile on two streams while the roofline leg launches full-size passes)",
          f"{'kernel':62s} {'grid':>10s} {'n':>4s} {'avg ms':>8s} {'min ms':>8s} {'max ms':>8s}"]
 out = []

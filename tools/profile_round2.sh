@@ -4,9 +4,9 @@
 set -x
 R=$GRAFT_REPO_ROOT; TAG=${1:-r03_a}; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-cd $R && python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
+cd $R && python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.err
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -- python3 $R/bench.py --no-cpu-baseline --ext-total 0 > $O/bench_prof.json 2> $O/bench_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_bench -- python3 $R/bench.py --full --no-cpu-baseline --ext-total 0 > $O/bench_prof.json 2> $O/bench_prof.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/tools/profile_ntt.py > $O/p1.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 $R/tools/profile_ntt.py > $O/p2.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- python3 $R/tools/profile_ntt.py > $O/p3.log 2>&1
