@@ -295,6 +295,12 @@ int pfhe_dcrt_add_mul_factor_assign_dev(const pfhe_dcrt *table, uint64_t *acc_de
 int pfhe_dcrt_mul_monomial_to_dev(const pfhe_dcrt *table, const uint64_t *a_dev, size_t r, uint64_t *out_dev,
                                   size_t len, void *stream);
 int pfhe_dcrt_mul_monomial_assign_dev(const pfhe_dcrt *table, uint64_t *data_dev, size_t r, size_t len, void *stream);
+/* CrtGlwe::mul_monic_monomial_assign (glwe/crt.rs:76-114) with one exponent per element: element e (polys_per_exp
+ * RNS polynomials, polys_per_exp x L x N words) of a_dev is multiplied by X^{exps_dev[e]} into out_dev.  Each exponent is
+ * taken modulo 2N (read on the device only, never by the host); len must be a whole number of elements; out_dev must not
+ * overlap a_dev.  exps_dev holds len / (polys_per_exp * L * N) uint32 exponents.  (The X^{-b_e} * TV of a bootstrap.) */
+int pfhe_dcrt_mul_monomial_each_to_dev(const pfhe_dcrt *table, const uint64_t *a_dev, size_t len, const uint32_t *exps_dev,
+                                       size_t polys_per_exp, uint64_t *out_dev, void *stream);
 /* Point-wise inverse.  The reference panics on a non-invertible element; this call synchronises the stream and
  * returns PFHE_ERR_NO_INVERSE (outputs unspecified).  Not capturable into a HIP graph. */
 int pfhe_dcrt_inv_to_dev(const pfhe_dcrt *table, const uint64_t *a_dev, uint64_t *out_dev, size_t len, void *stream);
@@ -465,6 +471,40 @@ int pfhe_extprod_glev_mul_big_uint_poly_to_dev(pfhe_extprod_plan *plan, const ui
                                                const uint64_t *big_uint_poly_dev, size_t len_poly, uint64_t *result_dev,
                                                size_t len_result, void *stream);
 
+/* =====================================================================================
+ * Batched blind rotation over the external product — the CMUX loop of a bootstrap
+ * ===================================================================================== */
+typedef struct pfhe_blindrot pfhe_blindrot;
+
+/* For every step i = 0 .. n_steps-1 in order, and every ciphertext e of the batch:
+ *   D     = X^{exps[e*n_steps+i]} * ACC_e - ACC_e    CrtGlwe::mul_monic_monomial_assign (glwe/crt.rs:76-114),
+ *                                                    sub_element_wise_assign (macros/mod.rs:438)
+ *   E     = coeff_form(D (x) BSK_i)                  CrtGlwe::mul_dcrt_ggsw_to (glwe/crt.rs:200-227),
+ *                                                    DcrtGlwe::write_coeff_form (macros/mod.rs:921)
+ *   ACC_e = ACC_e + E                                add_element_wise_assign (macros/mod.rs:410)
+ * acc: batch CrtGlwe in coefficient form ((k+1) x L x N words each), read and written in place; bsk: n_steps DcrtGgsw end
+ * to end ((k+1) x ell x (k+1) x L x N words each), shared by the batch; exps: batch x n_steps uint32, ciphertext-major.
+ * batch = len_acc / ((k+1)*L*N), n_steps = len_bsk / ggsw words; PFHE_ERR_BAD_LENGTH unless both divide evenly and
+ * len_exps == batch * n_steps; n_steps == 0 is a no-op.  Output canonical, bit-identical to that sequence.
+ * The handle borrows `table` (which must outlive it) and owns an external-product plan (pfhe_extprod_plan_create with the
+ * same arguments) plus three glue buffers of chunk ciphertexts, all allocated here; a batch larger than the chunk runs
+ * chunk by chunk, every step of a chunk before the next chunk.  One holder at a time, as the plan (PFHE_ERR_BUSY).
+ * N = 2^10 / 2^11 with k = 1 (where the external product takes its small-ring kernel: at least 1024 (ciphertext, limb)
+ * pairs per chunk, fused kernels enabled when the handle was created) runs two launches per step; every other shape runs
+ * the product and one glue launch per step. */
+int pfhe_blindrot_create(const pfhe_dcrt *table, const pfhe_rns *base, const pfhe_basis *basis, size_t glwe_dimension,
+                         size_t chunk, pfhe_blindrot **out);
+void pfhe_blindrot_destroy(pfhe_blindrot *h);
+int pfhe_blindrot_in_use(const pfhe_blindrot *h);  /* 1 while some thread is inside a pfhe_blindrot_* call on it */
+size_t pfhe_blindrot_scratch_bytes(const pfhe_blindrot *h);
+/* Device form: every exponent is taken modulo 2N on the device.  All work is queued on `stream`, with no host
+ * synchronisation and no allocation, so a whole rotation can be captured into a HIP graph. */
+int pfhe_blindrot_rotate_dev(pfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const uint64_t *bsk_dev, size_t len_bsk,
+                             const uint32_t *exps_dev, size_t len_exps, void *stream);
+/* Host form: PFHE_ERR_BAD_ARGUMENT for any exponent of 2N or more (the reference's debug_assert!(r < 2N)). */
+int pfhe_blindrot_rotate(pfhe_blindrot *h, uint64_t *acc, size_t len_acc, const uint64_t *bsk, size_t len_bsk,
+                         const uint32_t *exps, size_t len_exps);
+
 /* Profiling hooks (bench.py / rocprofv3): a transform is executed as a short sequence of kernel
  * passes (DESIGN.md "Kernels"); these run or name ONE pass so that each kernel can be timed with
  * HIP events in isolation.  The data is only meaningful after all passes have run in order. */
@@ -625,6 +665,7 @@ int pfhe_dcrt32_transform_pass_dev(const pfhe_dcrt32 *table, uint32_t *poly_dev,
 typedef struct pfhe_rns32 pfhe_rns32;
 typedef struct pfhe_basis32 pfhe_basis32;
 typedef struct pfhe_extprod32_plan pfhe_extprod32_plan;
+typedef struct pfhe_blindrot32 pfhe_blindrot32;
 
 /* RNSBase::new(moduli) — base.rs:79-117.  Errors: EMPTY_BASE (:47-49), COPRIME (:83-89),
  * UNREPRESENTABLE_MODULUS when a modulus is not in (1, 2^30) (BarrettModulus::<u32>::new,
@@ -775,6 +816,21 @@ int pfhe_extprod32_add_dcrt_glev_mul_big_uint_poly_assign_dev(pfhe_extprod32_pla
 int pfhe_extprod32_glev_mul_big_uint_poly_to_dev(pfhe_extprod32_plan *plan, const uint32_t *dcrt_glev_dev, size_t len_glev,
                                                  const uint32_t *big_uint_poly_dev, size_t len_poly, uint32_t *result_dev,
                                                  size_t len_result, void *stream);
+
+/* The per-element monomial product over U32DcrtTable (as pfhe_dcrt_mul_monomial_each_to_dev, uint32 words). */
+int pfhe_dcrt32_mul_monomial_each_to_dev(const pfhe_dcrt32 *table, const uint32_t *a_dev, size_t len,
+                                         const uint32_t *exps_dev, size_t polys_per_exp, uint32_t *out_dev, void *stream);
+/* The batched blind rotation over the u32 product (as pfhe_blindrot_*, uint32 words; every shape takes the u32 product
+ * and one glue launch per step). */
+int pfhe_blindrot32_create(const pfhe_dcrt32 *table, const pfhe_rns32 *base, const pfhe_basis32 *basis,
+                           size_t glwe_dimension, size_t chunk, pfhe_blindrot32 **out);
+void pfhe_blindrot32_destroy(pfhe_blindrot32 *h);
+int pfhe_blindrot32_in_use(const pfhe_blindrot32 *h);
+size_t pfhe_blindrot32_scratch_bytes(const pfhe_blindrot32 *h);
+int pfhe_blindrot32_rotate_dev(pfhe_blindrot32 *h, uint32_t *acc_dev, size_t len_acc, const uint32_t *bsk_dev,
+                               size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream);
+int pfhe_blindrot32_rotate(pfhe_blindrot32 *h, uint32_t *acc, size_t len_acc, const uint32_t *bsk, size_t len_bsk,
+                           const uint32_t *exps, size_t len_exps);
 
 #ifdef __cplusplus
 }

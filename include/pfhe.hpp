@@ -411,6 +411,37 @@ inline void mul_dcrt_ggsw_to_dev(const uint64_t *crt_glwe_dev, size_t len_glwe, 
                                             result_dev, len_result, into_coeff_form, stream));
 }
 
+// The batched blind rotation over the external product (pfhe_blindrot_*): for every step i and ciphertext e,
+// ACC_e += coeff_form(((X^{exps[e*n_steps+i]} - 1) * ACC_e) (x) BSK_i)  — CrtGlwe::mul_monic_monomial_assign
+// (glwe/crt.rs:76-114), sub_element_wise_assign, CrtGlwe::mul_dcrt_ggsw_to (glwe/crt.rs:200-227), write_coeff_form,
+// add_element_wise_assign.  Owns its product plan and glue buffers; one holder at a time, like DcrtGlevContext.
+class BlindRotate {
+  public:
+    BlindRotate(const U64DcrtTable &table, const RNSBase &base, const BigUintApproxSignedBasis &basis,
+                size_t glwe_dimension = 1, size_t chunk = 0) {
+        check(pfhe_blindrot_create(table.handle(), base.handle(), basis.handle(), glwe_dimension, chunk, &h_));
+    }
+    ~BlindRotate() { pfhe_blindrot_destroy(h_); }
+    BlindRotate(const BlindRotate &) = delete;
+    BlindRotate &operator=(const BlindRotate &) = delete;
+    pfhe_blindrot *handle() const { return h_; }
+    bool in_use() const { return pfhe_blindrot_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_blindrot_scratch_bytes(h_); }
+    // host slices; every exponent below 2N
+    void rotate(uint64_t *acc, size_t len_acc, const uint64_t *bsk, size_t len_bsk, const uint32_t *exps,
+                size_t len_exps) {
+        check(pfhe_blindrot_rotate(h_, acc, len_acc, bsk, len_bsk, exps, len_exps));
+    }
+    // device buffers, queued on `stream` (exponents taken modulo 2N)
+    void rotate_dev(uint64_t *acc_dev, size_t len_acc, const uint64_t *bsk_dev, size_t len_bsk, const uint32_t *exps_dev,
+                    size_t len_exps, void *stream = nullptr) {
+        check(pfhe_blindrot_rotate_dev(h_, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream));
+    }
+
+  private:
+    pfhe_blindrot *h_ = nullptr;
+};
+
 // ---- the <u32> instantiation of the same operators (RNSBase<u32>, BigUintApproxSignedBasis<u32> — the type the
 // reference's tests/big_uint.rs:13 runs — and CrtGlwe<u32>::mul_dcrt_ggsw_to over a U32DcrtTable).  Words are
 // uint32_t in memory (residues, digits, limbs of big integers); moduli below 2^30, log_basis below 32; up to 32 moduli.
@@ -537,6 +568,32 @@ class DcrtGlevContext32 {
 
   private:
     pfhe_extprod32_plan *h_ = nullptr;
+};
+
+// the batched blind rotation over the u32 product, as BlindRotate
+class BlindRotate32 {
+  public:
+    BlindRotate32(const U32DcrtTable &table, const RNSBase32 &base, const BigUintApproxSignedBasis32 &basis,
+                  size_t glwe_dimension = 1, size_t chunk = 0) {
+        check(pfhe_blindrot32_create(table.handle(), base.handle(), basis.handle(), glwe_dimension, chunk, &h_));
+    }
+    ~BlindRotate32() { pfhe_blindrot32_destroy(h_); }
+    BlindRotate32(const BlindRotate32 &) = delete;
+    BlindRotate32 &operator=(const BlindRotate32 &) = delete;
+    pfhe_blindrot32 *handle() const { return h_; }
+    bool in_use() const { return pfhe_blindrot32_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_blindrot32_scratch_bytes(h_); }
+    void rotate(uint32_t *acc, size_t len_acc, const uint32_t *bsk, size_t len_bsk, const uint32_t *exps,
+                size_t len_exps) {
+        check(pfhe_blindrot32_rotate(h_, acc, len_acc, bsk, len_bsk, exps, len_exps));
+    }
+    void rotate_dev(uint32_t *acc_dev, size_t len_acc, const uint32_t *bsk_dev, size_t len_bsk, const uint32_t *exps_dev,
+                    size_t len_exps, void *stream = nullptr) {
+        check(pfhe_blindrot32_rotate_dev(h_, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream));
+    }
+
+  private:
+    pfhe_blindrot32 *h_ = nullptr;
 };
 
 // CrtGlwe<u32>::mul_dcrt_ggsw_to (crates/primus_lattice/src/glwe/crt.rs:200-227)

@@ -460,3 +460,78 @@ impl Drop for HipExternalProduct32 {
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Batched blind rotation over the external product (the CMUX loop of a bootstrap): for every step i and ciphertext e,
+//   ACC_e += coeff_form(((X^{exps[e*n_steps+i]} - 1) * ACC_e) (x) BSK_i)
+// (CrtGlwe::mul_monic_monomial_assign, glwe/crt.rs:76-114; CrtGlwe::mul_dcrt_ggsw_to, glwe/crt.rs:200-227)
+// ------------------------------------------------------------------------------------------------
+/// Owns the basis, the RNS base and the rotation handle (its product plan and glue buffers): one per stream.
+pub struct HipBlindRotate {
+    rns: *mut ffi::pfhe_rns,
+    basis: *mut ffi::pfhe_basis,
+    h: *mut ffi::pfhe_blindrot,
+}
+impl HipBlindRotate {
+    pub fn new(table: &HipDcrtTable, moduli: &[u64], log_basis: u32, glwe_dimension: usize) -> Result<Self, c_int> {
+        let (mut rns, mut basis, mut h) = (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut());
+        unsafe {
+            let rc = ffi::pfhe_rns_create(moduli.as_ptr(), moduli.len(), device(), &mut rns);
+            if rc != ffi::PFHE_OK { return Err(rc); }
+            let rc = ffi::pfhe_basis_create(rns, log_basis, 0, &mut basis);
+            if rc != ffi::PFHE_OK { ffi::pfhe_rns_destroy(rns); return Err(rc); }
+            let rc = ffi::pfhe_blindrot_create(table.handle(), rns, basis, glwe_dimension, 0, &mut h);
+            if rc != ffi::PFHE_OK { ffi::pfhe_basis_destroy(basis); ffi::pfhe_rns_destroy(rns); return Err(rc); }
+        }
+        Ok(Self { rns, basis, h })
+    }
+    /// `acc_dev`: batch x (k+1) x L x N words (coefficient form, updated in place); `bsk_dev`: n_steps GGSWs end to end;
+    /// `exps_dev`: batch x n_steps exponents, ciphertext-major (taken modulo 2N).
+    pub unsafe fn rotate_dev(&mut self, acc_dev: *mut u64, len_acc: usize, bsk_dev: *const u64, len_bsk: usize,
+                             exps_dev: *const u32, len_exps: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        status(unsafe { ffi::pfhe_blindrot_rotate_dev(self.h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream) })
+    }
+}
+impl Drop for HipBlindRotate {
+    fn drop(&mut self) {
+        unsafe {
+            ffi::pfhe_blindrot_destroy(self.h);
+            ffi::pfhe_basis_destroy(self.basis);
+            ffi::pfhe_rns_destroy(self.rns);
+        }
+    }
+}
+
+/// The same over `U32DcrtTable` (u32 words on the device).
+pub struct HipBlindRotate32 {
+    rns: *mut ffi::pfhe_rns32,
+    basis: *mut ffi::pfhe_basis32,
+    h: *mut ffi::pfhe_blindrot32,
+}
+impl HipBlindRotate32 {
+    pub fn new(table: &HipU32DcrtTable, moduli: &[u32], log_basis: u32, glwe_dimension: usize) -> Result<Self, c_int> {
+        let (mut rns, mut basis, mut h) = (core::ptr::null_mut(), core::ptr::null_mut(), core::ptr::null_mut());
+        unsafe {
+            let rc = ffi::pfhe_rns32_create(moduli.as_ptr(), moduli.len(), device(), &mut rns);
+            if rc != ffi::PFHE_OK { return Err(rc); }
+            let rc = ffi::pfhe_basis32_create(rns, log_basis, 0, &mut basis);
+            if rc != ffi::PFHE_OK { ffi::pfhe_rns32_destroy(rns); return Err(rc); }
+            let rc = ffi::pfhe_blindrot32_create(table.handle(), rns, basis, glwe_dimension, 0, &mut h);
+            if rc != ffi::PFHE_OK { ffi::pfhe_basis32_destroy(basis); ffi::pfhe_rns32_destroy(rns); return Err(rc); }
+        }
+        Ok(Self { rns, basis, h })
+    }
+    pub unsafe fn rotate_dev(&mut self, acc_dev: *mut u32, len_acc: usize, bsk_dev: *const u32, len_bsk: usize,
+                             exps_dev: *const u32, len_exps: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        status(unsafe { ffi::pfhe_blindrot32_rotate_dev(self.h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream) })
+    }
+}
+impl Drop for HipBlindRotate32 {
+    fn drop(&mut self) {
+        unsafe {
+            ffi::pfhe_blindrot32_destroy(self.h);
+            ffi::pfhe_basis32_destroy(self.basis);
+            ffi::pfhe_rns32_destroy(self.rns);
+        }
+    }
+}

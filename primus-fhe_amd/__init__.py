@@ -7,7 +7,8 @@ primus_lattice) and delegate through the C ABI in include/pfhe.h to hand-written
 constructors raise.
 """
 from ._lib import PfheError, build, lib, library_path, status_string  # noqa: F401
-from .lattice import (DcrtGlevContext, DcrtGlevContext32, add_dcrt_glev_mul_big_uint_poly_assign_dev,  # noqa: F401
+from .lattice import (BlindRotateContext, BlindRotateContext32, blind_rotate, blind_rotate_dev,  # noqa: F401
+                      DcrtGlevContext, DcrtGlevContext32, add_dcrt_glev_mul_big_uint_poly_assign_dev,  # noqa: F401
                       add_dcrt_glev_mul_crt_poly_assign_dev, glev_mul_big_uint_poly_to_dev, glev_mul_crt_poly_to_dev,
                       mul_dcrt_ggsw_to, mul_dcrt_ggsw_to_dev, profile_mul_dcrt_ggsw_to_dev)
 from .ntt import NttError, U32DcrtTable, U32NttTable, U64DcrtTable, U64NttTable  # noqa: F401
@@ -18,4 +19,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "BigUintApproxSignedBasis", "BaseConverter", "BaseConverter32", "DcrtGlevContext", "RNSBase32", "BigUintApproxSignedBasis32",
            "DcrtGlevContext32", "mul_dcrt_ggsw_to", "mul_dcrt_ggsw_to_dev",
            "add_dcrt_glev_mul_crt_poly_assign_dev", "glev_mul_crt_poly_to_dev", "add_dcrt_glev_mul_big_uint_poly_assign_dev",
-           "glev_mul_big_uint_poly_to_dev", "build", "lib", "library_path", "status_string"]
+           "glev_mul_big_uint_poly_to_dev", "BlindRotateContext", "BlindRotateContext32", "blind_rotate", "blind_rotate_dev",
+           "build", "lib", "library_path", "status_string"]

@@ -160,6 +160,15 @@ def _declare(lib: C.CDLL) -> None:
         sig(ep + "glev_mul_crt_poly_to_dev", ci, vp, vp, sz, vp, sz, vp, sz, vp)
         sig(ep + "add_dcrt_glev_mul_big_uint_poly_assign_dev", ci, vp, vp, sz, vp, sz, vp, sz, vp)
         sig(ep + "glev_mul_big_uint_poly_to_dev", ci, vp, vp, sz, vp, sz, vp, sz, vp)
+    for br in ("pfhe_blindrot_", "pfhe_blindrot32_"):   # batched blind rotation over either product
+        sig(br + "create", ci, vp, vp, vp, sz, sz, C.POINTER(vp))
+        sig(br + "destroy", None, vp)
+        sig(br + "in_use", ci, vp)
+        sig(br + "scratch_bytes", sz, vp)
+        sig(br + "rotate_dev", ci, vp, vp, sz, vp, sz, vp, sz, vp)
+        sig(br + "rotate", ci, vp, vp, sz, vp, sz, vp, sz)
+    sig("pfhe_dcrt_mul_monomial_each_to_dev", ci, vp, vp, sz, vp, sz, vp, vp)
+    sig("pfhe_dcrt32_mul_monomial_each_to_dev", ci, vp, vp, sz, vp, sz, vp, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)
     sig("pfhe_dcrt_transform_num_passes", ci, vp)

@@ -1252,3 +1252,255 @@ int pfhe_extprod32_glev_mul_big_uint_poly_to_dev(pfhe_extprod32_plan *plan, cons
 }
 
 }  // extern "C"
+
+/* ------------------------------ batched blind rotation ------------------------------ */
+
+// The blind-rotation (CMUX) loop of a bootstrap over the external product: for every step i and ciphertext e,
+//   ACC_e <- ACC_e + coeff_form(((X^{exps[e*n_steps+i]} - 1) * ACC_e) (x) BSK_i)
+// (CrtGlwe::mul_monic_monomial_assign, glwe/crt.rs:76-114; sub_element_wise_assign, macros/mod.rs:438;
+// CrtGlwe::mul_dcrt_ggsw_to, glwe/crt.rs:200-227; DcrtGlwe::write_coeff_form, macros/mod.rs:921;
+// add_element_wise_assign, macros/mod.rs:410).  The handle owns an external-product plan and three glue buffers of
+// chunk ciphertexts (D, E and the second accumulator of the ping-pong), all allocated at creation; a call allocates
+// nothing and synchronises with nothing, so one whole rotation can be captured into a HIP graph.
+template <class Plan, class W>
+struct BlindRotCore {
+    Plan *plan = nullptr;  // owned
+    std::atomic<std::uintptr_t> owner{0};  // one holder at a time (PlanLease), as the plan
+    int depth = 0;
+    hipEvent_t last_done = nullptr;  // cross-stream ordering of successive calls, as run_product
+    bool last_valid = false;
+    W *d = nullptr, *e = nullptr, *ping = nullptr;  // chunk * glwe words each
+    size_t glwe = 0, ggsw = 0;
+    ~BlindRotCore() {
+        if (!plan) return;
+        {
+            DeviceGuard g(plan->table->device);
+            for (W *b : {d, e, ping})
+                if (b) (void)counted_free(b);
+            if (last_done) (void)hipEventDestroy(last_done);
+        }
+        delete plan;
+    }
+};
+struct pfhe_blindrot : BlindRotCore<pfhe_extprod_plan, u64> {};
+struct pfhe_blindrot32 : BlindRotCore<pfhe_extprod32_plan, u32> {};
+
+namespace {
+
+template <class H>
+int blindrot_finish_create(H *h) {
+    const TableSet &t = *h->plan->table;
+    h->glwe = (size_t)(h->plan->k + 1) * t.L * t.n;
+    h->ggsw = (size_t)(h->plan->k + 1) * h->plan->basis.ell * h->glwe;
+    DeviceGuard g(t.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    using W = typename std::remove_pointer<decltype(h->d)>::type;
+    for (W **b : {&h->d, &h->e, &h->ping}) {
+        void *p = nullptr;
+        PFHE_HIP(counted_malloc(&p, h->plan->chunk * h->glwe * sizeof(W)));
+        *b = (W *)p;
+    }
+    PFHE_HIP(hipEventCreateWithFlags(&h->last_done, hipEventDisableTiming));
+    return PFHE_OK;
+}
+
+// the product of one step: E = coeff_form(D (x) BSK_i) for `cur` ciphertexts
+int blindrot_product(pfhe_blindrot *h, const u64 *d, const u64 *key, u64 *e, u64 cur, hipStream_t s) {
+    return pfhe_extprod_mul_dcrt_ggsw_to_dev(h->plan, (const uint64_t *)d, cur * h->glwe, (const uint64_t *)key, h->ggsw,
+                                             (uint64_t *)e, cur * h->glwe, 1, s);
+}
+int blindrot_product(pfhe_blindrot32 *h, const u32 *d, const u32 *key, u32 *e, u64 cur, hipStream_t s) {
+    return pfhe_extprod32_mul_dcrt_ggsw_to_dev(h->plan, d, cur * h->glwe, key, h->ggsw, e, cur * h->glwe, 1, s);
+}
+
+// Fused small-ring step (u64 only): taken under exactly the condition run_product_impl takes extprod_small_kernel under.
+// Two launches per step, no D or E buffer: digits of X^r * ACC - ACC, then the product whose epilogue adds E to ACC.
+bool blindrot_small_fused(const pfhe_blindrot *h, u64 cur) {
+    const pfhe_extprod_plan *p = h->plan;
+    const TableSet &t = *p->table;
+    return p->sdigits != nullptr && extprod_small_supported(t.log_n, p->k, p->rns.dev.value_len, p->basis.log_basis) &&
+           cur * t.L >= 1024 && p->use_fused;
+}
+bool blindrot_small_fused(const pfhe_blindrot32 *, u64) { return false; }
+int blindrot_small_steps(pfhe_blindrot *h, u64 *acc, const u64 *bsk, const u32 *exps, u64 n_steps, u64 cur, hipStream_t s) {
+    const pfhe_extprod_plan *p = h->plan;
+    const TableSet &t = *p->table;
+    RnsParams rns = p->rns;
+    rns.dev.big_input = rns.wide_tab.big_input = 0u;
+    for (u64 i = 0; i < n_steps; ++i) {
+        PFHE_TRY(blindrot_small_digits_dev(rns, p->basis_par, t.log_n, acc, (int *)p->sdigits, cur, exps + i, (u32)n_steps, s));
+        PFHE_TRY(blindrot_small_product_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, p->basis.ell, (const int *)p->sdigits,
+                                            bsk + i * h->ggsw, acc, cur, s));
+    }
+    return PFHE_OK;
+}
+int blindrot_small_steps(pfhe_blindrot32 *, u32 *, const u32 *, const u32 *, u64, u64, hipStream_t) {
+    return PFHE_ERR_UNSUPPORTED;
+}
+
+template <class H, class W>
+int blindrot_rotate_dev(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
+                        hipStream_t s) {
+    if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h);
+    const TableSet &t = *h->plan->table;
+    if (len_acc % h->glwe != 0 || len_bsk % h->ggsw != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->ggsw)) {
+        set_last_error("blind rotation: acc must be batch*(k+1)*L*N words, bsk n_steps*(k+1)*ell*(k+1)*L*N and exps "
+                       "batch*n_steps exponents");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    const u64 batch = len_acc / h->glwe, n_steps = len_bsk / h->ggsw;
+    if (batch == 0 || n_steps == 0) return PFHE_OK;
+    if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(acc);
+    PFHE_REQUIRE_ALIGNED(bsk);
+    DeviceGuard g(t.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    const bool tracked = !stream_is_capturing(s);
+    if (tracked && h->last_valid) PFHE_HIP(hipStreamWaitEvent(s, h->last_done, 0));
+    const u32 rows = h->plan->k + 1;
+    int rc = PFHE_OK;
+    // chunk after chunk; every step of a chunk runs before the next chunk starts
+    for (u64 done = 0; done < batch && rc == PFHE_OK; done += h->plan->chunk) {
+        const u64 cur = std::min<u64>(h->plan->chunk, batch - done);
+        W *a0 = acc + done * h->glwe;
+        const uint32_t *ex = exps + done * n_steps;
+        if (blindrot_small_fused(h, cur)) {
+            rc = blindrot_small_steps(h, a0, bsk, ex, n_steps, cur, s);
+            continue;
+        }
+        // ping-pong between the caller's accumulator and the handle's: every step writes ACC' to the other one, so the
+        // gather of a rotated word never sees a word already updated; an odd step count starts in the handle's buffer
+        // so that the last step ends in the caller's
+        W *src = a0;
+        if (n_steps % 2) {
+            rc = blindrot_glue_dev<W>(t, BlindRotGlue::kFirstCopy, a0, nullptr, h->ping, h->d, ex, (u32)n_steps, rows, cur, s);
+            src = h->ping;
+        } else {
+            rc = blindrot_glue_dev<W>(t, BlindRotGlue::kFirst, a0, nullptr, nullptr, h->d, ex, (u32)n_steps, rows, cur, s);
+        }
+        for (u64 i = 0; i < n_steps && rc == PFHE_OK; ++i) {
+            rc = blindrot_product(h, h->d, bsk + i * h->ggsw, h->e, cur, s);
+            if (rc != PFHE_OK) break;
+            W *dst = src == a0 ? h->ping : a0;
+            rc = i + 1 < n_steps
+                     ? blindrot_glue_dev<W>(t, BlindRotGlue::kStep, src, h->e, dst, h->d, ex + i + 1, (u32)n_steps, rows, cur, s)
+                     : blindrot_glue_dev<W>(t, BlindRotGlue::kLast, src, h->e, dst, nullptr, ex, (u32)n_steps, rows, cur, s);
+            src = dst;
+        }
+    }
+    if (tracked) {  // also after a failed call: whatever it queued still uses the buffers
+        if (hipEventRecord(h->last_done, s) == hipSuccess) {
+            h->last_valid = true;
+        } else {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(s);
+            h->last_valid = false;
+        }
+    }
+    return rc;
+}
+
+// host form: every exponent must be below 2N (the reference's debug_assert!(r < 2N)); staged through the pooled context
+template <class H, class W, class DevFn>
+int blindrot_rotate_host(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
+                         DevFn dev) {
+    if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h);
+    if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
+    const size_t two_n = 2 * h->plan->table->n;
+    for (size_t i = 0; i < len_exps; ++i) {
+        if (exps[i] >= two_n) {
+            set_last_error("blind rotation: every exponent must be below 2N");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
+    }
+    if (len_acc % h->glwe != 0 || len_bsk % h->ggsw != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->ggsw)) {
+        set_last_error("blind rotation: acc must be batch*(k+1)*L*N words, bsk n_steps*(k+1)*ell*(k+1)*L*N and exps "
+                       "batch*n_steps exponents");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
+    DeviceGuard g(h->plan->table->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(h->plan->table->device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *a = nullptr, *k = nullptr, *x = nullptr;
+    PFHE_TRY(st.upload(acc, len_acc * sizeof(W), &a));
+    PFHE_TRY(st.upload(bsk, len_bsk * sizeof(W), &k));
+    PFHE_TRY(st.upload(exps, len_exps * sizeof(uint32_t), &x));
+    PFHE_TRY(dev(h, (W *)a, len_acc, (const W *)k, len_bsk, (const uint32_t *)x, len_exps, st.stream()));
+    PFHE_TRY(st.download(acc, a, len_acc * sizeof(W)));
+    return st.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfhe_blindrot_create(const pfhe_dcrt *table, const pfhe_rns *base, const pfhe_basis *basis, size_t glwe_dimension,
+                         size_t chunk, pfhe_blindrot **out) {
+    PFHE_GUARD_BEGIN
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    auto h = std::make_unique<pfhe_blindrot>();
+    PFHE_TRY(pfhe_extprod_plan_create(table, base, basis, glwe_dimension, chunk, &h->plan));
+    PFHE_TRY(blindrot_finish_create(h.get()));
+    *out = h.release();
+    return PFHE_OK;
+    PFHE_GUARD_END
+}
+void pfhe_blindrot_destroy(pfhe_blindrot *h) { delete h; }
+int pfhe_blindrot_in_use(const pfhe_blindrot *h) { return h && h->owner.load(std::memory_order_acquire) != 0 ? 1 : 0; }
+size_t pfhe_blindrot_scratch_bytes(const pfhe_blindrot *h) {
+    if (!h || !h->plan) return 0;
+    return pfhe_extprod_plan_scratch_bytes(h->plan) + 3 * h->plan->chunk * h->glwe * sizeof(u64);
+}
+int pfhe_blindrot_rotate_dev(pfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const uint64_t *bsk_dev, size_t len_bsk,
+                             const uint32_t *exps_dev, size_t len_exps, void *stream) {
+    PFHE_GUARD_BEGIN
+    return blindrot_rotate_dev<pfhe_blindrot, u64>(h, (u64 *)acc_dev, len_acc, (const u64 *)bsk_dev, len_bsk, exps_dev,
+                                                   len_exps, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_blindrot_rotate(pfhe_blindrot *h, uint64_t *acc, size_t len_acc, const uint64_t *bsk, size_t len_bsk,
+                         const uint32_t *exps, size_t len_exps) {
+    PFHE_GUARD_BEGIN
+    return blindrot_rotate_host(h, (u64 *)acc, len_acc, (const u64 *)bsk, len_bsk, exps, len_exps,
+                                blindrot_rotate_dev<pfhe_blindrot, u64>);
+    PFHE_GUARD_END
+}
+
+int pfhe_blindrot32_create(const pfhe_dcrt32 *table, const pfhe_rns32 *base, const pfhe_basis32 *basis,
+                           size_t glwe_dimension, size_t chunk, pfhe_blindrot32 **out) {
+    PFHE_GUARD_BEGIN
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    auto h = std::make_unique<pfhe_blindrot32>();
+    PFHE_TRY(pfhe_extprod32_plan_create(table, base, basis, glwe_dimension, chunk, &h->plan));
+    PFHE_TRY(blindrot_finish_create(h.get()));
+    *out = h.release();
+    return PFHE_OK;
+    PFHE_GUARD_END
+}
+void pfhe_blindrot32_destroy(pfhe_blindrot32 *h) { delete h; }
+int pfhe_blindrot32_in_use(const pfhe_blindrot32 *h) { return h && h->owner.load(std::memory_order_acquire) != 0 ? 1 : 0; }
+size_t pfhe_blindrot32_scratch_bytes(const pfhe_blindrot32 *h) {
+    if (!h || !h->plan) return 0;
+    return pfhe_extprod32_plan_scratch_bytes(h->plan) + 3 * h->plan->chunk * h->glwe * sizeof(u32);
+}
+int pfhe_blindrot32_rotate_dev(pfhe_blindrot32 *h, uint32_t *acc_dev, size_t len_acc, const uint32_t *bsk_dev,
+                               size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
+    PFHE_GUARD_BEGIN
+    return blindrot_rotate_dev<pfhe_blindrot32, u32>(h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps,
+                                                     (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_blindrot32_rotate(pfhe_blindrot32 *h, uint32_t *acc, size_t len_acc, const uint32_t *bsk, size_t len_bsk,
+                           const uint32_t *exps, size_t len_exps) {
+    PFHE_GUARD_BEGIN
+    return blindrot_rotate_host(h, acc, len_acc, bsk, len_bsk, exps, len_exps, blindrot_rotate_dev<pfhe_blindrot32, u32>);
+    PFHE_GUARD_END
+}
+
+}  // extern "C"

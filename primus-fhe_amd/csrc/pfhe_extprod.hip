@@ -218,10 +218,21 @@ __global__ __launch_bounds__(LOGE == 3 ? 512 : 256, LOGE == 3 ? kMulacc8MinWaves
 // CPT coefficients per thread.  Two adjacent ones for big integers of at most 4 limbs held by value (16-byte loads of
 // the residues, one store of the digit pair: every BASELINE config); one for longer integers and for the device-table
 // form of a wide base (RT = RnsWide, BT = BasisDev or BasisWide), whose residues are fetched as the lift consumes them.
-template <int LEN, class DT, class RT, class BT, int CPT, class WT = u64>
+// SRC: where the residues come from.  CrtLoad: the input polynomials as they are.  MonomialSubLoad (blind rotation,
+// by-value bases only): the residues of X^r * a - a (crt/mul.rs:102-127, then reduce_sub), r = exps[(poly / rows) * stride]
+// mod 2N — the rotated word of every limb is gathered and subtracted before the CRT compose.
+struct CrtLoad {
+    static constexpr bool kRotate = false;
+};
+struct MonomialSubLoad {
+    static constexpr bool kRotate = true;
+    const u32 *exps;
+    u32 stride, rows;
+};
+template <int LEN, class DT, class RT, class BT, int CPT, class WT = u64, class SRC = CrtLoad>
 __global__ __launch_bounds__(256) void gadget_signed_digits_kernel(RT R, BT B, u32 log_n,
                                                                   const WT *__restrict__ crt, DT *__restrict__ out,
-                                                                  u64 total_threads) {
+                                                                  u64 total_threads, SRC src) {
     const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total_threads) return;
     const u32 n = 1u << log_n;
@@ -235,7 +246,19 @@ __global__ __launch_bounds__(256) void gadget_signed_digits_kernel(RT R, BT B, u
     } else if constexpr (kByValue<RT>) {
         u64 r[CPT][kMaxLimbs];
         for (u32 i = 0; i < R.L; ++i) {
-            if constexpr (CPT == 2) {  // two adjacent residues in one load (16 bytes of u64 words, 8 bytes of u32 words), read once
+            if constexpr (SRC::kRotate) {
+                const u32 rr = src.exps[(poly / src.rows) * src.stride] & (2 * n - 1);
+                const bool high = rr >= n;
+                const u32 rot = high ? rr - n : rr;
+                const u64 q = R.modulus(i);
+                const WT *__restrict__ base = crt + (poly * R.L + i) * n;
+#pragma unroll
+                for (int e = 0; e < CPT; ++e) {
+                    const u32 j = t + e;
+                    const u64 a = base[j], x = base[(j - rot) & (n - 1)];
+                    r[e][i] = sub_mod(((j < rot) != high) ? (x ? q - x : 0) : x, a, q);
+                }
+            } else if constexpr (CPT == 2) {  // two adjacent residues in one load (16 bytes of u64 words, 8 bytes of u32 words), read once
                 typedef WT WT2 __attribute__((ext_vector_type(2)));
                 const WT2 w = __builtin_nontemporal_load(reinterpret_cast<const WT2 *>(crt + (poly * R.L + i) * n + t));
                 r[0][i] = w.x;
@@ -281,15 +304,15 @@ struct SignedDigitsLaunch {
             constexpr int CPT = LEN <= 4 ? 2 : 1;
             if (b.wide()) {
                 hipLaunchKernelGGL((gadget_signed_digits_kernel<LEN, DT, RnsWide, BasisWide, 1, WT>), dim3((u32)((coeffs + 255) / 256)), dim3(256), 0, s,
-                                   r.wide_tab, b.wide_tab, log_n, crt, sdigits, coeffs);
+                                   r.wide_tab, b.wide_tab, log_n, crt, sdigits, coeffs, CrtLoad{});
             } else if constexpr (LEN <= kMaxLimbs) {
                 if (r.wide()) {
                     hipLaunchKernelGGL((gadget_signed_digits_kernel<LEN, DT, RnsWide, BasisDev, 1, WT>), dim3((u32)((coeffs + 255) / 256)), dim3(256), 0, s,
-                                       r.wide_tab, b.dev, log_n, crt, sdigits, coeffs);
+                                       r.wide_tab, b.dev, log_n, crt, sdigits, coeffs, CrtLoad{});
                 } else {
                     const u64 threads = coeffs / CPT;
                     hipLaunchKernelGGL((gadget_signed_digits_kernel<LEN, DT, RnsDev, BasisDev, CPT, WT>), dim3((u32)((threads + 255) / 256)), dim3(256), 0, s,
-                                       r.dev, b.dev, log_n, crt, sdigits, threads);
+                                       r.dev, b.dev, log_n, crt, sdigits, threads, CrtLoad{});
                 }
             }
             return PFHE_OK;
@@ -522,7 +545,9 @@ __global__ __launch_bounds__(256, 4) void gadget_block_mulacc32_kernel(const u64
 // and their transforms never exist in HBM: traffic is 4*ell*N bytes of digits per input polynomial,
 // 8*N per output polynomial, and the key out of L2.
 // ------------------------------------------------------------------------------------------
-template <class A, int LOGB, int NC>
+// ADD_COEFF (blind rotation): the coefficient-form epilogue adds the word already in `result` and stores the sum in
+// place (ACC += E, add_element_wise_assign).  A workgroup reads and writes only its own (ciphertext, limb) words.
+template <class A, int LOGB, int NC, bool ADD_COEFF = false>
 __device__ __forceinline__ void extprod_small_body(
     const int *__restrict__ sdigits, const u64 *__restrict__ ggsw, u64 ggsw_stride, u64 *__restrict__ result,
     const NttPrime *__restrict__ primes, u32 L, u32 rows, u32 ell, u64 total, u32 accumulate, u32 into_coeff) {
@@ -602,8 +627,13 @@ __device__ __forceinline__ void extprod_small_body(
         if (into_coeff) {
             block_inverse_core<A, LOGB>(ar, y, lds, n, 0u, lte, /*final_block=*/true, /*lazy=*/false);
             u64 *__restrict__ o = out + (u64)c * W + lte;  // register layout <LOGB-4>: element lt + k * TPB
+            if constexpr (ADD_COEFF) {
 #pragma unroll
-            for (int k = 0; k < 16; ++k) o[(u32)k * Cfg::TPB] = y[k];
+                for (int k = 0; k < 16; ++k) o[(u32)k * Cfg::TPB] = add_mod(y[k], o[(u32)k * Cfg::TPB], P->q);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) o[(u32)k * Cfg::TPB] = y[k];
+            }
         } else {
             const GVec2Ptr o = (GVec2Ptr)(void *)(out + (u64)c * W + lte * 16);
 #pragma unroll
@@ -619,35 +649,35 @@ __device__ __forceinline__ void extprod_small_body(
 
 // (the body runs with the arithmetic's fold-inside form: at 256 registers this kernel has no room for the values the
 // 16-instruction butterfly keeps alive in front of its asm block — pfhe_ntt_device.hpp, PmArith::kFoldOutside)
-template <class A, int LOGB, int NC>
+template <class A, int LOGB, int NC, bool ADD_COEFF = false>
 __global__ __launch_bounds__(BlockCfg<LOGB>::THREADS) __attribute__((amdgpu_waves_per_eu(2, 3))) void extprod_small_kernel(
     const int *__restrict__ sdigits, const u64 *__restrict__ ggsw, u64 ggsw_stride, u64 *__restrict__ result,
     const NttPrime *__restrict__ primes, u32 L, u32 rows, u32 ell, u64 total, u32 accumulate, u32 into_coeff) {
-    extprod_small_body<typename FoldInsideOf<A>::type, LOGB, NC>(sdigits, ggsw, ggsw_stride, result, primes, L, rows, ell, total,
-                                                                  accumulate, into_coeff);
+    extprod_small_body<typename FoldInsideOf<A>::type, LOGB, NC, ADD_COEFF>(sdigits, ggsw, ggsw_stride, result, primes, L, rows,
+                                                                             ell, total, accumulate, into_coeff);
 }
 
-template <class A, int LOGB, int NC>
+template <class A, int LOGB, int NC, bool ADD_COEFF = false>
 int launch_extprod_small(const int *sdigits, const u64 *ggsw, u64 stride, u64 *result, const NttPrime *primes, u32 L,
                          u32 rows, u32 ell, u64 batch, bool accumulate, bool into_coeff, hipStream_t s) {
     const u64 total = batch * L;
     if (total == 0) return PFHE_OK;
     if (total > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
     constexpr size_t lds_bytes = (size_t)BlockCfg<LOGB>::LDS_WORDS * sizeof(u64);
-    hipLaunchKernelGGL((extprod_small_kernel<A, LOGB, NC>), dim3((u32)total), dim3(BlockCfg<LOGB>::THREADS), lds_bytes, s,
+    hipLaunchKernelGGL((extprod_small_kernel<A, LOGB, NC, ADD_COEFF>), dim3((u32)total), dim3(BlockCfg<LOGB>::THREADS), lds_bytes, s,
                        sdigits, ggsw, stride, result, primes, L, rows, ell, total, accumulate ? 1u : 0u,
                        into_coeff ? 1u : 0u);
     PFHE_HIP(hipGetLastError());
     return PFHE_OK;
 }
 
-template <class A, int NC>
+template <class A, int NC, bool ADD_COEFF = false>
 int dispatch_extprod_small(u32 log_n, const int *sdigits, const u64 *ggsw, u64 stride, u64 *result,
                            const NttPrime *primes, u32 L, u32 rows, u32 ell, u64 batch, bool accumulate, bool into_coeff,
                            hipStream_t s) {
     switch (log_n) {
-        case 10: return launch_extprod_small<A, 10, NC>(sdigits, ggsw, stride, result, primes, L, rows, ell, batch, accumulate, into_coeff, s);
-        case 11: return launch_extprod_small<A, 11, NC>(sdigits, ggsw, stride, result, primes, L, rows, ell, batch, accumulate, into_coeff, s);
+        case 10: return launch_extprod_small<A, 10, NC, ADD_COEFF>(sdigits, ggsw, stride, result, primes, L, rows, ell, batch, accumulate, into_coeff, s);
+        case 11: return launch_extprod_small<A, 11, NC, ADD_COEFF>(sdigits, ggsw, stride, result, primes, L, rows, ell, batch, accumulate, into_coeff, s);
     }
     return PFHE_ERR_UNSUPPORTED;
 }
@@ -794,6 +824,36 @@ int gadget_decompose_strided_dev(const RnsParams &r, const BasisParams &b, const
     }
     return k == 4 ? digits_strided_by_width<ShoupArith, 4>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s)
                   : digits_strided_by_width<ShoupArith, 3>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s);
+}
+
+// ---- batched blind rotation, fused small-ring step (the handle in pfhe_capi_rns.hip picks this path exactly where
+//      run_product_impl picks extprod_small_kernel) ----
+int blindrot_small_digits_dev(const RnsParams &r, const BasisParams &b, u32 log_n, const u64 *acc, int *sdigits, u64 batch,
+                              const u32 *exps, u32 exp_stride, hipStream_t s) {
+    if (b.wide() || r.wide() || r.dev.value_len > 4) return PFHE_ERR_UNSUPPORTED;
+    const u64 threads = ((batch * 2) << log_n) / 2;  // k = 1: two polynomials per ciphertext, two coefficients per thread
+    if (threads == 0) return PFHE_OK;
+    const MonomialSubLoad src{exps, exp_stride, 2};
+    const dim3 g((u32)((threads + 255) / 256)), th(256);
+    switch (r.dev.value_len) {
+        case 1: hipLaunchKernelGGL((gadget_signed_digits_kernel<1, int, RnsDev, BasisDev, 2, u64, MonomialSubLoad>), g, th, 0, s, r.dev, b.dev, log_n, acc, sdigits, threads, src); break;
+        case 2: hipLaunchKernelGGL((gadget_signed_digits_kernel<2, int, RnsDev, BasisDev, 2, u64, MonomialSubLoad>), g, th, 0, s, r.dev, b.dev, log_n, acc, sdigits, threads, src); break;
+        case 3: hipLaunchKernelGGL((gadget_signed_digits_kernel<3, int, RnsDev, BasisDev, 2, u64, MonomialSubLoad>), g, th, 0, s, r.dev, b.dev, log_n, acc, sdigits, threads, src); break;
+        case 4: hipLaunchKernelGGL((gadget_signed_digits_kernel<4, int, RnsDev, BasisDev, 2, u64, MonomialSubLoad>), g, th, 0, s, r.dev, b.dev, log_n, acc, sdigits, threads, src); break;
+        default: return PFHE_ERR_UNSUPPORTED;
+    }
+    PFHE_HIP(hipGetLastError());
+    return PFHE_OK;
+}
+
+int blindrot_small_product_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u32 ell, const int *sdigits,
+                               const u64 *ggsw, u64 *acc, u64 batch, hipStream_t s) {
+    // one shared key (stride 0), coefficient-form output added to ACC in place
+    if (arith == kArithMont)
+        return dispatch_extprod_small<MontArith, 2, true>(log_n, sdigits, ggsw, 0, acc, primes, L, 2, ell, batch, false, true, s);
+    return arith == kArithPm
+               ? dispatch_extprod_small<PmArith, 2, true>(log_n, sdigits, ggsw, 0, acc, primes, L, 2, ell, batch, false, true, s)
+               : dispatch_extprod_small<ShoupArith, 2, true>(log_n, sdigits, ggsw, 0, acc, primes, L, 2, ell, batch, false, true, s);
 }
 
 }  // namespace pfhe

@@ -212,6 +212,26 @@ int extprod_small_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u32 k
                       const u64 *ggsw, bool ggsw_shared, u64 *result, u64 batch, bool accumulate, bool into_coeff,
                       hipStream_t s);
 
+// ---- batched blind rotation (pfhe_blindrot.hip; the handles live in pfhe_capi_rns.hip) ----
+// Per element e (polys_per_exp RNS polynomials of L x N words) with exponent r = exps[e * exp_stride] mod 2N:
+//   kFirst:     d_out = X^r acc - acc
+//   kFirstCopy: d_out = X^r acc - acc, acc_out = acc
+//   kStep:      acc_out = acc + e_in, d_out = X^r acc_out - acc_out   (acc_out must not alias acc or e_in)
+//   kLast:      acc_out = acc + e_in
+//   kMonomial:  d_out = X^r acc
+struct TableSet;
+enum class BlindRotGlue { kFirst, kFirstCopy, kStep, kLast, kMonomial };
+template <class WT>
+int blindrot_glue_dev(const TableSet &t, BlindRotGlue mode, const WT *acc, const WT *e_in, WT *acc_out, WT *d_out,
+                      const u32 *exps, u32 exp_stride, u32 polys_per_exp, u64 elements, hipStream_t s);
+// The two launches of a fused small-ring step (extprod_small_supported shapes, k = 1): balanced int32 digits of
+// D = X^r * ACC - ACC formed as the residues are loaded (r = exps[e * exp_stride] mod 2N for ciphertext e), then
+// extprod_small_kernel with a coefficient-form epilogue that adds its result to ACC in place.
+int blindrot_small_digits_dev(const RnsParams &r, const BasisParams &b, u32 log_n, const u64 *acc, int *sdigits, u64 batch,
+                              const u32 *exps, u32 exp_stride, hipStream_t s);
+int blindrot_small_product_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u32 ell, const int *sdigits,
+                               const u64 *ggsw, u64 *acc, u64 batch, hipStream_t s);
+
 }  // namespace pfhe
 
 // handles behind the C ABI (shared by pfhe_capi_rns.hip and pfhe_convert.hip); the *32 ones are the <u32> instantiations

@@ -303,6 +303,16 @@ class U64DcrtTable:
         p, n = _dev(data)
         check(lib().pfhe_dcrt_mul_monomial_assign_dev(self._h, p, r, n, _stream(stream)))
 
+    def mul_monomial_each_to_dev(self, a, exps, polys_per_exp: int, out, stream=None):
+        """out = a * X^{exps[e]} per element e of polys_per_exp RNS polynomials (CrtGlwe::mul_monic_monomial_assign,
+        glwe/crt.rs:76-114, one exponent per element).  exps: int32/uint32 CUDA tensor or (ptr, count); each exponent is
+        taken modulo 2N on the device."""
+        (pa, n), (po, no) = _dev(a), _dev(out)
+        if n != no:
+            raise ValueError("a and out must have the same length")
+        pe, _ = _dev32(exps)
+        check(lib().pfhe_dcrt_mul_monomial_each_to_dev(self._h, pa, n, pe, polys_per_exp, po, _stream(stream)))
+
     def inv_to_dev(self, a, out, stream=None):
         """DcrtPolynomial::inv_to / inv_assign (dcrt/inv.rs:33-68): point-wise inverse; raises NoInverse where the
         reference panics."""
@@ -486,3 +496,11 @@ class U32DcrtTable(_U32Common):
     def transform_pass_dev(self, poly, inverse: bool, index: int, lazy: bool = False, stream=None):
         p, n = _dev32(poly)
         check(lib().pfhe_dcrt32_transform_pass_dev(self._h, p, n, int(inverse), index, int(lazy), _stream(stream)))
+
+    def mul_monomial_each_to_dev(self, a, exps, polys_per_exp: int, out, stream=None):
+        """out = a * X^{exps[e]} per element e of polys_per_exp RNS polynomials (uint32 words; as on U64DcrtTable)."""
+        (pa, n), (po, no) = _dev32(a), _dev32(out)
+        if n != no:
+            raise ValueError("a and out must have the same length")
+        pe, _ = _dev32(exps)
+        check(lib().pfhe_dcrt32_mul_monomial_each_to_dev(self._h, pa, n, pe, polys_per_exp, po, _stream(stream)))
