@@ -832,6 +832,75 @@ int pfhe_blindrot32_rotate_dev(pfhe_blindrot32 *h, uint32_t *acc_dev, size_t len
 int pfhe_blindrot32_rotate(pfhe_blindrot32 *h, uint32_t *acc, size_t len_acc, const uint32_t *bsk, size_t len_bsk,
                            const uint32_t *exps, size_t len_exps);
 
+/* ---- torus FFT (primus_fft) and the TFHE external product (primus_lattice::tfhe) ----
+ * FullComplex64FftTable — primus_fft/src/complex64/table.rs:47-130 (the FftTable trait, table.rs): negacyclic transforms of
+ * N = 2^log_n torus words.  Fourier values are complex f64 stored as interleaved (re, im) doubles, N per polynomial
+ * (fourier_length == poly_length, the reference's full layout); lengths below count complex values.  1 <= log_n <= 14
+ * (the N/2-point transform of a polynomial lives in LDS): 0 or more gives PFHE_ERR_UNSUPPORTED, before the device is
+ * touched.  u64 names carry no suffix, u32 names end in 32 (TorusFftValue for u64 / u32, primus_fft/src/torus.rs:32-58). */
+typedef struct pfhe_fft pfhe_fft;
+int pfhe_fft_create(uint32_t log_n, int device, pfhe_fft **out);
+void pfhe_fft_destroy(pfhe_fft *fft);
+size_t pfhe_fft_poly_length(const pfhe_fft *fft);
+size_t pfhe_fft_fourier_length(const pfhe_fft *fft);   /* N, as FullComplex64FftTable */
+/* FftTable::forward_torus_slice / inverse_torus_slice over count polynomials (len_input = count*N words -> count*N complex
+ * values, and back).  The inverse takes Re of the full inverse, rounds half away from zero and wraps as
+ * from_f64_wrapping_rounded (u32: saturate at +-2^63, then mod 2^32; u64: saturate at +-2^127, then exactly mod 2^64) on any
+ * spectrum, conjugate-symmetric or not. */
+int pfhe_fft_forward_torus_dev(const pfhe_fft *fft, const uint64_t *input_dev, size_t len_input, double *output_dev,
+                               size_t len_output, void *stream);
+int pfhe_fft_forward_torus32_dev(const pfhe_fft *fft, const uint32_t *input_dev, size_t len_input, double *output_dev,
+                                 size_t len_output, void *stream);
+int pfhe_fft_inverse_torus_dev(const pfhe_fft *fft, const double *input_dev, size_t len_input, uint64_t *output_dev,
+                               size_t len_output, void *stream);
+int pfhe_fft_inverse_torus32_dev(const pfhe_fft *fft, const double *input_dev, size_t len_input, uint32_t *output_dev,
+                                 size_t len_output, void *stream);
+/* host-slice forms of the same four (the trait's own signatures; staged, synchronous) */
+int pfhe_fft_forward_torus_slice(const pfhe_fft *fft, const uint64_t *input, size_t len_input, double *output,
+                                 size_t len_output);
+int pfhe_fft_forward_torus32_slice(const pfhe_fft *fft, const uint32_t *input, size_t len_input, double *output,
+                                   size_t len_output);
+int pfhe_fft_inverse_torus_slice(const pfhe_fft *fft, const double *input, size_t len_input, uint64_t *output,
+                                 size_t len_output);
+int pfhe_fft_inverse_torus32_slice(const pfhe_fft *fft, const double *input, size_t len_input, uint32_t *output,
+                                   size_t len_output);
+
+/* The plan of the TFHE product: ApproxSignedBasis<T>::new(None, log_basis, Some(decompose_length) or None)
+ * (primus_decompose/src/primitive/basis.rs:47-177; decompose_length 0 = the full BITS / log_basis) bundled with
+ * TfheFftContext<T> (primus_lattice/src/context/tfhe.rs).  The basis's assert!s (log_basis in 1..BITS-1, decompose_length
+ * at most BITS / log_basis) give PFHE_ERR_BAD_ARGUMENT before anything else is looked at; glwe_dimension (k) above 64 gives
+ * PFHE_ERR_UNSUPPORTED.  `fft` is borrowed and must outlive the plan.  k = 1 with N <= 2^11 runs one fused launch per
+ * chunk and owns no scratch; every other shape owns chunk*(k+1)*(ell+1)*N/2 + (k+1)*ell*(k+1)*N/2 complex values of device
+ * scratch (chunk 0 = about 256 MiB).  Everything is allocated here; a call only queues work, so it can be captured into a
+ * HIP graph.  One holder at a time (PFHE_ERR_BUSY), successive calls on different streams ordered by the plan, as
+ * pfhe_extprod_plan. */
+typedef struct pfhe_tfhe_plan pfhe_tfhe_plan;
+typedef struct pfhe_tfhe32_plan pfhe_tfhe32_plan;
+int pfhe_tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                          size_t chunk, pfhe_tfhe_plan **out);
+void pfhe_tfhe_plan_destroy(pfhe_tfhe_plan *plan);
+int pfhe_tfhe_plan_in_use(const pfhe_tfhe_plan *plan);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_plan_scratch_bytes(const pfhe_tfhe_plan *plan);
+/* external_product_to — primus_lattice/src/tfhe/external_product.rs:36-93: output = input (x) key for a batch of GLWE
+ * ciphertexts (len_input = len_output = batch*(k+1)*N torus words; the same buffer or disjoint) and ONE Fourier GGSW key
+ * in the reference's layout, (k+1) rows x ell levels x (k+1) components x N complex values (len_key counts them).  Results
+ * are deterministic and do not depend on the batch size or the chunk. */
+int pfhe_tfhe_external_product_to_dev(pfhe_tfhe_plan *plan, const uint64_t *input_dev, size_t len_input,
+                                      const double *key_dev, size_t len_key, uint64_t *output_dev, size_t len_output,
+                                      void *stream);
+int pfhe_tfhe_external_product_to(pfhe_tfhe_plan *plan, const uint64_t *input, size_t len_input, const double *key,
+                                  size_t len_key, uint64_t *output, size_t len_output);
+int pfhe_tfhe32_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                            size_t chunk, pfhe_tfhe32_plan **out);
+void pfhe_tfhe32_plan_destroy(pfhe_tfhe32_plan *plan);
+int pfhe_tfhe32_plan_in_use(const pfhe_tfhe32_plan *plan);
+size_t pfhe_tfhe32_plan_scratch_bytes(const pfhe_tfhe32_plan *plan);
+int pfhe_tfhe32_external_product_to_dev(pfhe_tfhe32_plan *plan, const uint32_t *input_dev, size_t len_input,
+                                        const double *key_dev, size_t len_key, uint32_t *output_dev, size_t len_output,
+                                        void *stream);
+int pfhe_tfhe32_external_product_to(pfhe_tfhe32_plan *plan, const uint32_t *input, size_t len_input, const double *key,
+                                    size_t len_key, uint32_t *output, size_t len_output);
+
 #ifdef __cplusplus
 }
 #endif

@@ -611,4 +611,103 @@ inline void mul_dcrt_ggsw_to_dev(const uint32_t *crt_glwe_dev, size_t len_glwe, 
                                               result_dev, len_result, into_coeff_form, stream));
 }
 
+// FullComplex64FftTable — primus_fft::FftTable (crates/primus_fft/src/table.rs, complex64/table.rs:47-130): Fourier
+// values as interleaved (re, im) doubles, N complex values per polynomial; lengths count complex values / torus words.
+class FullComplex64FftTable {
+  public:
+    explicit FullComplex64FftTable(uint32_t log_n, int device = 0) { check(pfhe_fft_create(log_n, device, &h_)); }
+    ~FullComplex64FftTable() { pfhe_fft_destroy(h_); }
+    FullComplex64FftTable(const FullComplex64FftTable &) = delete;
+    FullComplex64FftTable &operator=(const FullComplex64FftTable &) = delete;
+    pfhe_fft *handle() const { return h_; }
+    size_t poly_length() const { return pfhe_fft_poly_length(h_); }
+    size_t fourier_length() const { return pfhe_fft_fourier_length(h_); }
+    void forward_torus_slice(const uint64_t *in, size_t len_in, double *out, size_t len_out) const {
+        check(pfhe_fft_forward_torus_slice(h_, in, len_in, out, len_out));
+    }
+    void forward_torus_slice(const uint32_t *in, size_t len_in, double *out, size_t len_out) const {
+        check(pfhe_fft_forward_torus32_slice(h_, in, len_in, out, len_out));
+    }
+    void inverse_torus_slice(const double *in, size_t len_in, uint64_t *out, size_t len_out) const {
+        check(pfhe_fft_inverse_torus_slice(h_, in, len_in, out, len_out));
+    }
+    void inverse_torus_slice(const double *in, size_t len_in, uint32_t *out, size_t len_out) const {
+        check(pfhe_fft_inverse_torus32_slice(h_, in, len_in, out, len_out));
+    }
+    void forward_torus_dev(const uint64_t *in, size_t len_in, double *out, size_t len_out, void *stream = nullptr) const {
+        check(pfhe_fft_forward_torus_dev(h_, in, len_in, out, len_out, stream));
+    }
+    void forward_torus_dev(const uint32_t *in, size_t len_in, double *out, size_t len_out, void *stream = nullptr) const {
+        check(pfhe_fft_forward_torus32_dev(h_, in, len_in, out, len_out, stream));
+    }
+    void inverse_torus_dev(const double *in, size_t len_in, uint64_t *out, size_t len_out, void *stream = nullptr) const {
+        check(pfhe_fft_inverse_torus_dev(h_, in, len_in, out, len_out, stream));
+    }
+    void inverse_torus_dev(const double *in, size_t len_in, uint32_t *out, size_t len_out, void *stream = nullptr) const {
+        check(pfhe_fft_inverse_torus32_dev(h_, in, len_in, out, len_out, stream));
+    }
+
+  private:
+    pfhe_fft *h_ = nullptr;
+};
+
+// TfheFftContext<u64> with its power-of-two ApproxSignedBasis<u64> (primus_lattice/src/context/tfhe.rs,
+// primus_decompose/src/primitive/basis.rs:47-177); decompose_length 0 = the full 64 / log_basis.  One holder at a time.
+class TfheFftContext {
+  public:
+    TfheFftContext(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis,
+                   size_t decompose_length = 0, size_t chunk = 0) {
+        check(pfhe_tfhe_plan_create(fft.handle(), glwe_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfheFftContext() { pfhe_tfhe_plan_destroy(h_); }
+    TfheFftContext(const TfheFftContext &) = delete;
+    TfheFftContext &operator=(const TfheFftContext &) = delete;
+    pfhe_tfhe_plan *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_plan_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_plan_scratch_bytes(h_); }
+
+  private:
+    pfhe_tfhe_plan *h_ = nullptr;
+};
+
+// the u32 torus
+class TfheFftContext32 {
+  public:
+    TfheFftContext32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis,
+                     size_t decompose_length = 0, size_t chunk = 0) {
+        check(pfhe_tfhe32_plan_create(fft.handle(), glwe_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfheFftContext32() { pfhe_tfhe32_plan_destroy(h_); }
+    TfheFftContext32(const TfheFftContext32 &) = delete;
+    TfheFftContext32 &operator=(const TfheFftContext32 &) = delete;
+    pfhe_tfhe32_plan *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_plan_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_plan_scratch_bytes(h_); }
+
+  private:
+    pfhe_tfhe32_plan *h_ = nullptr;
+};
+
+// external_product_to (crates/primus_lattice/src/tfhe/external_product.rs:36-93): a batch of GLWE ciphertexts, one
+// Fourier GGSW key (len_key complex values)
+inline void external_product_to(const uint64_t *input, size_t len_input, const double *key, size_t len_key, uint64_t *output,
+                                size_t len_output, TfheFftContext &context) {
+    check(pfhe_tfhe_external_product_to(context.handle(), input, len_input, key, len_key, output, len_output));
+}
+inline void external_product_to(const uint32_t *input, size_t len_input, const double *key, size_t len_key, uint32_t *output,
+                                size_t len_output, TfheFftContext32 &context) {
+    check(pfhe_tfhe32_external_product_to(context.handle(), input, len_input, key, len_key, output, len_output));
+}
+inline void external_product_to_dev(const uint64_t *input_dev, size_t len_input, const double *key_dev, size_t len_key,
+                                    uint64_t *output_dev, size_t len_output, TfheFftContext &context, void *stream = nullptr) {
+    check(pfhe_tfhe_external_product_to_dev(context.handle(), input_dev, len_input, key_dev, len_key, output_dev, len_output,
+                                            stream));
+}
+inline void external_product_to_dev(const uint32_t *input_dev, size_t len_input, const double *key_dev, size_t len_key,
+                                    uint32_t *output_dev, size_t len_output, TfheFftContext32 &context,
+                                    void *stream = nullptr) {
+    check(pfhe_tfhe32_external_product_to_dev(context.handle(), input_dev, len_input, key_dev, len_key, output_dev,
+                                              len_output, stream));
+}
+
 }  // namespace pfhe

@@ -7,12 +7,16 @@
 //!   * `U32NttTable`  (crates/primus_ntt/src/ntt/prime32/table.rs:37)  -> [`HipU32NttTable`]
 //! so that every function of primus_lattice that is generic over `Table: NttTable` / `DcrtTable`
 //! runs on the GPU unchanged (one host->device->host round trip per `&mut [T]` call), and adds the
-//! batched, device-resident external product as [`HipExternalProduct`].
+//! batched, device-resident external product as [`HipExternalProduct`].  `FullComplex64FftTable`
+//! (crates/primus_fft/src/complex64/table.rs:47) -> [`HipFftTable`] behind `FftTable`, and the TFHE product in the
+//! Fourier domain as [`HipTfheExternalProduct`] / [`HipTfheExternalProduct32`].
 mod ffi;
 
 use core::ffi::{c_int, CStr};
 
+use num_complex::Complex64;
 use primus_data::{DataMut, RawData};
+use primus_fft::{FftError, FftTable, TorusFftValue};
 use primus_ntt::{DcrtTable, NttError, NttTable};
 use primus_poly::{CrtPolynomial, DcrtPolynomial, NttPolynomial, Polynomial};
 use primus_reduce::FieldContext;
@@ -533,5 +537,123 @@ impl Drop for HipBlindRotate32 {
             ffi::pfhe_basis32_destroy(self.basis);
             ffi::pfhe_rns32_destroy(self.rns);
         }
+    }
+}
+
+/// `FftTable` (crates/primus_fft/src/table.rs) over the host-slice forms of the torus FFT: the drop-in replacement of
+/// `FullComplex64FftTable` (complex64/table.rs:47-130; fourier_length == poly_length == N).  u32 and u64 torus values;
+/// 1 <= log_n <= 14 (the table's `new` refuses more with `FftError::InvalidLogN { max: 14 }`).  The batched,
+/// device-resident product is [`HipTfheExternalProduct`].
+pub struct HipFftTable {
+    fft: *mut ffi::pfhe_fft,
+    n: usize,
+}
+unsafe impl Send for HipFftTable {}
+unsafe impl Sync for HipFftTable {}
+impl Drop for HipFftTable {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_fft_destroy(self.fft) }
+    }
+}
+impl HipFftTable {
+    pub fn handle(&self) -> *mut ffi::pfhe_fft {
+        self.fft
+    }
+}
+impl FftTable for HipFftTable {
+    fn new(log_n: u32) -> Result<Self, FftError> {
+        let mut fft = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_fft_create(log_n, device(), &mut fft) } {
+            ffi::PFHE_OK => Ok(Self { fft, n: 1usize << log_n }),
+            ffi::PFHE_ERR_UNSUPPORTED => Err(FftError::InvalidLogN { log_n, max: 14 }),
+            e => panic!("pfhe_fft_create: status {e}: {}", last_error()),
+        }
+    }
+    fn poly_length(&self) -> usize {
+        self.n
+    }
+    fn fourier_length(&self) -> usize {
+        self.n
+    }
+    fn forward_torus_slice<T: TorusFftValue>(&self, input: &[T], output: &mut [Complex64]) {
+        // Complex64 is #[repr(C)] { re, im }: the interleaved layout of the C ABI
+        let out = output.as_mut_ptr() as *mut f64;
+        let rc = unsafe {
+            match core::mem::size_of::<T>() {
+                8 => ffi::pfhe_fft_forward_torus_slice(self.fft, input.as_ptr() as *const u64, input.len(), out, output.len()),
+                4 => ffi::pfhe_fft_forward_torus32_slice(self.fft, input.as_ptr() as *const u32, input.len(), out, output.len()),
+                _ => panic!("HipFftTable: u32 and u64 torus values only"),
+            }
+        };
+        assert_eq!(rc, ffi::PFHE_OK, "pfhe_fft_forward_torus_slice: {}", last_error());
+    }
+    fn inverse_torus_slice<T: TorusFftValue>(&self, input: &[Complex64], output: &mut [T]) {
+        let inp = input.as_ptr() as *const f64;
+        let rc = unsafe {
+            match core::mem::size_of::<T>() {
+                8 => ffi::pfhe_fft_inverse_torus_slice(self.fft, inp, input.len(), output.as_mut_ptr() as *mut u64, output.len()),
+                4 => ffi::pfhe_fft_inverse_torus32_slice(self.fft, inp, input.len(), output.as_mut_ptr() as *mut u32, output.len()),
+                _ => panic!("HipFftTable: u32 and u64 torus values only"),
+            }
+        };
+        assert_eq!(rc, ffi::PFHE_OK, "pfhe_fft_inverse_torus_slice: {}", last_error());
+    }
+}
+
+/// `external_product_to` (crates/primus_lattice/src/tfhe/external_product.rs:36-93) for a batch of u64-torus GLWE
+/// ciphertexts and one Fourier GGSW key, with its `ApproxSignedBasis::<u64>::new(None, log_basis, reverse_length)` and
+/// `TfheFftContext` in one plan (`decompose_length` 0 = the full length).  [`HipTfheExternalProduct32`]: the u32 torus.
+pub struct HipTfheExternalProduct {
+    plan: *mut ffi::pfhe_tfhe_plan,
+}
+impl HipTfheExternalProduct {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize) -> Result<Self, c_int> {
+        let mut plan = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe_plan_create(fft.handle(), glwe_dimension, log_basis, decompose_length, 0, &mut plan) } {
+            ffi::PFHE_OK => Ok(Self { plan }),
+            e => Err(e),
+        }
+    }
+    /// `input_dev` / `output_dev`: batch x (k+1) x N words; `key_dev`: (k+1) x ell x (k+1) x N complex values
+    pub unsafe fn external_product_to_dev(&mut self, input_dev: *const u64, len_input: usize, key_dev: *const f64,
+                                          len_key: usize, output_dev: *mut u64, stream: *mut core::ffi::c_void)
+                                          -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe_external_product_to_dev(self.plan, input_dev, len_input, key_dev, len_key, output_dev,
+                                                             len_input, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheExternalProduct {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe_plan_destroy(self.plan) }
+    }
+}
+
+pub struct HipTfheExternalProduct32 {
+    plan: *mut ffi::pfhe_tfhe32_plan,
+}
+impl HipTfheExternalProduct32 {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize) -> Result<Self, c_int> {
+        let mut plan = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe32_plan_create(fft.handle(), glwe_dimension, log_basis, decompose_length, 0, &mut plan) } {
+            ffi::PFHE_OK => Ok(Self { plan }),
+            e => Err(e),
+        }
+    }
+    pub unsafe fn external_product_to_dev(&mut self, input_dev: *const u32, len_input: usize, key_dev: *const f64,
+                                          len_key: usize, output_dev: *mut u32, stream: *mut core::ffi::c_void)
+                                          -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe32_external_product_to_dev(self.plan, input_dev, len_input, key_dev, len_key,
+                                                               output_dev, len_input, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheExternalProduct32 {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe32_plan_destroy(self.plan) }
     }
 }

@@ -12,6 +12,8 @@ from .lattice import (BlindRotateContext, BlindRotateContext32, blind_rotate, bl
                       add_dcrt_glev_mul_crt_poly_assign_dev, glev_mul_big_uint_poly_to_dev, glev_mul_crt_poly_to_dev,
                       mul_dcrt_ggsw_to, mul_dcrt_ggsw_to_dev, profile_mul_dcrt_ggsw_to_dev)
 from .ntt import NttError, U32DcrtTable, U32NttTable, U64DcrtTable, U64NttTable  # noqa: F401
+from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheFftContext, tfhe_external_product_to,  # noqa: F401
+                   tfhe_external_product_to_dev, write_fourier_form)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -20,4 +22,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "DcrtGlevContext32", "mul_dcrt_ggsw_to", "mul_dcrt_ggsw_to_dev",
            "add_dcrt_glev_mul_crt_poly_assign_dev", "glev_mul_crt_poly_to_dev", "add_dcrt_glev_mul_big_uint_poly_assign_dev",
            "glev_mul_big_uint_poly_to_dev", "BlindRotateContext", "BlindRotateContext32", "blind_rotate", "blind_rotate_dev",
-           "build", "lib", "library_path", "status_string"]
+           "FullComplex64FftTable", "ApproxSignedBasis", "TfheFftContext", "tfhe_external_product_to",
+           "tfhe_external_product_to_dev", "write_fourier_form", "build", "lib", "library_path", "status_string"]

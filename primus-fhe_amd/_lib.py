@@ -169,6 +169,24 @@ def _declare(lib: C.CDLL) -> None:
         sig(br + "rotate", ci, vp, vp, sz, vp, sz, vp, sz)
     sig("pfhe_dcrt_mul_monomial_each_to_dev", ci, vp, vp, sz, vp, sz, vp, vp)
     sig("pfhe_dcrt32_mul_monomial_each_to_dev", ci, vp, vp, sz, vp, sz, vp, vp)
+    # torus FFT tables and the TFHE external product (u64: no suffix, u32: 32)
+    f64p = C.POINTER(C.c_double)
+    sig("pfhe_fft_create", ci, u32, ci, C.POINTER(vp))
+    sig("pfhe_fft_destroy", None, vp)
+    sig("pfhe_fft_poly_length", sz, vp)
+    sig("pfhe_fft_fourier_length", sz, vp)
+    for w in ("", "32"):
+        sig("pfhe_fft_forward_torus" + w + "_dev", ci, vp, vp, sz, f64p, sz, vp)
+        sig("pfhe_fft_inverse_torus" + w + "_dev", ci, vp, f64p, sz, vp, sz, vp)
+        sig("pfhe_fft_forward_torus" + w + "_slice", ci, vp, vp, sz, f64p, sz)
+        sig("pfhe_fft_inverse_torus" + w + "_slice", ci, vp, f64p, sz, vp, sz)
+        tp = "pfhe_tfhe" + w + "_"
+        sig(tp + "plan_create", ci, vp, sz, u32, sz, sz, C.POINTER(vp))
+        sig(tp + "plan_destroy", None, vp)
+        sig(tp + "plan_in_use", ci, vp)
+        sig(tp + "plan_scratch_bytes", sz, vp)
+        sig(tp + "external_product_to_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
+        sig(tp + "external_product_to", ci, vp, vp, sz, f64p, sz, vp, sz)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)
     sig("pfhe_dcrt_transform_num_passes", ci, vp)

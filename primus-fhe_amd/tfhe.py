@@ -1,0 +1,195 @@
+"""Torus FFT tables and the TFHE external product — host-side mirror of primus_fft / primus_lattice::tfhe.
+
+Reference: FullComplex64FftTable (primus_fft/src/complex64/table.rs:47-130) behind the FftTable trait (table.rs),
+TorusFftValue (torus.rs:32-58), ApproxSignedBasis<T> with a power-of-two modulus (primus_decompose/src/primitive/basis.rs),
+TfheFftContext (primus_lattice/src/context/tfhe.rs), external_product_to (tfhe/external_product.rs:36-93) and the
+write_fourier_form conversions of GLWE / GLev / GGSW (tfhe/convert.rs).
+
+Layouts are the reference's: a torus polynomial is N words (uint32 or uint64), a Fourier polynomial N complex values
+(fourier_length == poly_length), a GLWE (k+1) polynomials, a Fourier GGSW (k+1) x ell x (k+1) Fourier polynomials.  Fourier
+values are complex128 arrays, or the interleaved float64 view of one (re, im, re, im, ...).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import PfheError, check, lib
+from .ntt import _stream
+
+_WORD = {np.dtype(np.uint64): "", np.dtype(np.uint32): "32"}
+
+
+def _host_words(a: np.ndarray):
+    if not isinstance(a, np.ndarray) or a.dtype not in _WORD or not a.flags.c_contiguous:
+        raise TypeError("expected a C-contiguous numpy uint32 or uint64 array")
+    return a.ctypes.data_as(C.c_void_p), a.size, _WORD[a.dtype]
+
+
+def _host_fourier(a: np.ndarray):
+    """(pointer, complex count) of a complex128 array or its interleaved float64 view"""
+    if not isinstance(a, np.ndarray) or not a.flags.c_contiguous:
+        raise TypeError("expected a C-contiguous numpy complex128 / float64 array")
+    if a.dtype == np.complex128:
+        return a.ctypes.data_as(C.POINTER(C.c_double)), a.size
+    if a.dtype == np.float64 and a.size % 2 == 0:
+        return a.ctypes.data_as(C.POINTER(C.c_double)), a.size // 2
+    raise TypeError("expected complex128 values or an interleaved float64 view")
+
+
+def _dev_words(t, suffix=None):
+    """(pointer, words, suffix) of a contiguous CUDA tensor of 32-bit (u32 torus) or 64-bit (u64 torus) elements"""
+    if isinstance(t, tuple):
+        ptr, words, sfx = t
+        return C.c_void_p(int(ptr)), int(words), sfx
+    if not hasattr(t, "data_ptr") or not t.is_cuda or not t.is_contiguous() or t.element_size() not in (4, 8) \
+            or t.is_floating_point() or t.is_complex():
+        raise TypeError("expected a contiguous 32- or 64-bit integer CUDA tensor")
+    return C.c_void_p(t.data_ptr()), t.numel(), "32" if t.element_size() == 4 else ""
+
+
+def _dev_fourier(t):
+    """(pointer, complex count) of a contiguous complex128 or float64 (interleaved) CUDA tensor"""
+    import torch
+    if isinstance(t, tuple):
+        return C.cast(C.c_void_p(int(t[0])), C.POINTER(C.c_double)), int(t[1])
+    if not t.is_cuda or not t.is_contiguous() or t.dtype not in (torch.complex128, torch.float64):
+        raise TypeError("expected a contiguous complex128 or float64 CUDA tensor")
+    n = t.numel() if t.dtype == torch.complex128 else t.numel() // 2
+    return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_double)), n
+
+
+class FullComplex64FftTable:
+    """primus_fft::FullComplex64FftTable — negacyclic torus FFT of N = 2^log_n (1 <= log_n <= 14), u32 and u64 words."""
+
+    def __init__(self, log_n: int, device: int = 0):
+        h = C.c_void_p()
+        check(lib().pfhe_fft_create(log_n, device, C.byref(h)))
+        self._h, self.log_n, self.device = h, log_n, device
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().pfhe_fft_destroy(h)
+            self._h = None
+
+    def poly_length(self) -> int:
+        return int(lib().pfhe_fft_poly_length(self._h))
+
+    def fourier_length(self) -> int:
+        return int(lib().pfhe_fft_fourier_length(self._h))
+
+    # ---- host slices (FftTable::forward_torus_slice / inverse_torus_slice, over one or more polynomials) ----
+    def forward_torus_slice(self, inp: np.ndarray, out: np.ndarray) -> None:
+        pi, ni, w = _host_words(inp)
+        po, no = _host_fourier(out)
+        check(getattr(lib(), "pfhe_fft_forward_torus" + w + "_slice")(self._h, pi, ni, po, no))
+
+    def inverse_torus_slice(self, inp: np.ndarray, out: np.ndarray) -> None:
+        pi, ni = _host_fourier(inp)
+        po, no, w = _host_words(out)
+        check(getattr(lib(), "pfhe_fft_inverse_torus" + w + "_slice")(self._h, pi, ni, po, no))
+
+    # ---- device tensors: int32 / uint32 words select the u32 torus, int64 / uint64 the u64 torus ----
+    def forward_torus_dev(self, inp, out, stream=None) -> None:
+        pi, ni, w = _dev_words(inp)
+        po, no = _dev_fourier(out)
+        check(getattr(lib(), "pfhe_fft_forward_torus" + w + "_dev")(self._h, pi, ni, po, no, _stream(stream)))
+
+    def inverse_torus_dev(self, inp, out, stream=None) -> None:
+        pi, ni = _dev_fourier(inp)
+        po, no, w = _dev_words(out)
+        check(getattr(lib(), "pfhe_fft_inverse_torus" + w + "_dev")(self._h, pi, ni, po, no, _stream(stream)))
+
+
+class ApproxSignedBasis:
+    """primus_decompose::ApproxSignedBasis<T> with modulus None (2^BITS): a host-side value object.  `bits` is 32 or 64
+    (the torus word); reverse_length limits the number of levels (basis.rs:47-177).  The reference's assert!s raise
+    PfheError BadArgument here."""
+
+    def __init__(self, bits: int, log_basis: int, reverse_length: int | None = None):
+        if bits not in (32, 64):
+            raise PfheError(33, "bits must be 32 or 64")
+        if not 0 < log_basis < bits:
+            raise PfheError(33, "log_basis must be in 1..BITS-1")
+        full = bits // log_basis
+        if reverse_length is not None and not 0 < reverse_length <= full:
+            raise PfheError(33, "reverse_length must be in 1..BITS/log_basis")
+        self.bits, self._log_basis = bits, log_basis
+        self._length = full if reverse_length is None else reverse_length
+
+    def log_basis(self) -> int:
+        return self._log_basis
+
+    def decompose_length(self) -> int:
+        return self._length
+
+    def drop_bits(self) -> int:
+        return self.bits - self._length * self._log_basis
+
+
+class TfheFftContext:
+    """TfheFftContext<T> bundled with its basis and table (context/tfhe.rs): owns the device scratch of the product.  One
+    holder at a time: a call from a second thread while one is inside raises PfheError (Busy)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1, chunk: int = 0):
+        self._w = "" if basis.bits == 64 else "32"
+        self._pre = "pfhe_tfhe" + self._w + "_"
+        h = C.c_void_p()
+        check(getattr(lib(), self._pre + "plan_create")(fft._h, glwe_dimension, basis.log_basis(),
+                                                         basis.decompose_length(), chunk, C.byref(h)))
+        self._h = h
+        self.fft, self.basis, self.glwe_dimension = fft, basis, glwe_dimension
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            getattr(lib(), self._pre + "plan_destroy")(h)
+            self._h = None
+
+    def dtype(self):
+        return np.uint64 if self.basis.bits == 64 else np.uint32
+
+    def scratch_bytes(self) -> int:
+        return int(getattr(lib(), self._pre + "plan_scratch_bytes")(self._h))
+
+    def in_use(self) -> bool:
+        return bool(getattr(lib(), self._pre + "plan_in_use")(self._h))
+
+    def glwe_len(self) -> int:
+        return (self.glwe_dimension + 1) * self.fft.poly_length()
+
+    def key_len(self) -> int:
+        """complex values of one Fourier GGSW key"""
+        return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
+
+
+def tfhe_external_product_to(inp: np.ndarray, key: np.ndarray, out: np.ndarray, ctx: TfheFftContext) -> None:
+    """external_product_to (tfhe/external_product.rs:36-93) on host arrays: out = inp (x) key for a batch of GLWE
+    ciphertexts (batch*(k+1)*N words of the context's width) and one Fourier GGSW key."""
+    pi, ni, wi = _host_words(inp)
+    po, no, wo = _host_words(out)
+    pk, nk = _host_fourier(key)
+    if wi != ctx._w or wo != ctx._w:
+        raise TypeError("input / output words must match the basis width")
+    check(getattr(lib(), ctx._pre + "external_product_to")(ctx._h, pi, ni, pk, nk, po, no))
+
+
+def tfhe_external_product_to_dev(inp, key, out, ctx: TfheFftContext, stream=None) -> None:
+    """the device form: inp / out 32- or 64-bit integer CUDA tensors (the context's width), key complex128 or float64"""
+    pi, ni, wi = _dev_words(inp)
+    po, no, wo = _dev_words(out)
+    pk, nk = _dev_fourier(key)
+    if wi != ctx._w or wo != ctx._w:
+        raise TypeError("input / output words must match the basis width")
+    check(getattr(lib(), ctx._pre + "external_product_to_dev")(ctx._h, pi, ni, pk, nk, po, no, _stream(stream)))
+
+
+def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) -> None:
+    """Glwe / Glev / Ggsw::write_fourier_form (tfhe/convert.rs): the Fourier containers are polynomial after polynomial,
+    so each is one batched forward transform.  numpy arrays take the host form, CUDA tensors the device form."""
+    if isinstance(coeff, np.ndarray):
+        fft.forward_torus_slice(coeff, fourier)
+    else:
+        fft.forward_torus_dev(coeff, fourier, stream)
