@@ -1,6 +1,5 @@
 // pfhe_capi_rns.hip — extern "C" boundary for RNSBase, BigUintApproxSignedBasis and the RNS gadget
 // external product (include/pfhe.h, second half).
-#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <memory>
@@ -11,24 +10,20 @@
 
 #include "pfhe_capi_internal.hpp"
 #include "pfhe_ntt_device.hpp"
+#include "pfhe_plan_guard.hpp"
 #include "pfhe_rns.hpp"
 #include "pfhe_staging.hpp"
 
 using namespace pfhe;
 
-struct pfhe_extprod_plan {
-    const TableSet *table = nullptr;  // borrowed from the pfhe_dcrt (must outlive the plan)
-    // Exclusivity.  The plan owns the product's scratch (digit buffers), like the reference's `&mut DcrtGlevContext`
-    // (primus_lattice/src/context/glev.rs:4-10), which the borrow checker lets ONE caller hold at a time.  Here the holder
-    // is a thread: every entry point that touches the scratch takes the plan for the duration of the call (PlanLease), and
-    // a second thread that arrives meanwhile is refused with PFHE_ERR_BUSY ("plan in use") instead of racing on the
-    // digit buffer.  owner = a per-thread token (0: free); depth counts nested entries of the owning thread (the host-pointer
-    // and profiling entry points call the device ones).
-    std::atomic<std::uintptr_t> owner{0};
-    int depth = 0;
-    // cross-stream ordering of successive calls (run_product): the event recorded behind the last call's kernels
-    hipEvent_t last_done = nullptr;
-    bool last_valid = false;
+// The RNS gadget external product's plan, for both word widths (W = u64: pfhe_extprod_plan over a U64DcrtTable;
+// W = u32: pfhe_extprod32_plan, CrtGlwe<u32>::mul_dcrt_ggsw_to over a U32DcrtTable, glwe/crt.rs:200-227,
+// dcrt/prime32.rs:11).  The plan owns the product's scratch (digit buffers); `guard` keeps it to one holder at a time.
+template <class W>
+struct ExtprodPlanCore {
+    using Word = W;
+    const TableSet *table = nullptr;  // borrowed from the pfhe_dcrt / pfhe_dcrt32 (must outlive the plan)
+    PlanGuard guard;
     RnsParams rns;
     BasisParams basis_par;
     BasisCore basis{};  // the scalar constants of basis_par
@@ -43,103 +38,35 @@ struct pfhe_extprod_plan {
     // workgroups a call must offer before the fused block + multiply-accumulate kernel is taken (N = 2^16, 3 limbs,
     // coefficient form: 1 / 2 / 4 / 5 ciphertexts take 97 / 121 / 165 / 190 us unfused and 141 / 144 / 158 / 164 us fused)
     static constexpr u64 fused_min_wgs = 160;
-    // measurement aid (pfhe_extprod_profile_dev): when non-null, run_product records an event before the
+    // measurement aid (pfhe_extprod_profile_dev, u64 only): when non-null, run_product records an event before the
     // decomposition, between the decomposition and the transform / multiply-accumulate, and after it, per chunk
     std::vector<hipEvent_t> *prof = nullptr;
-    u64 *digits = nullptr;
+    W *digits = nullptr;
     size_t digits_words = 0;
-    void *sdigits = nullptr;  // compact signed digits of one chunk (chunk * (k+1) * ell * N words of sdigit_bytes: int32 when log_basis <= 31, else int64), or null
+    // compact signed digits of one chunk (chunk * (k+1) * ell * N words of sdigit_bytes), or null.  u64: int32 when
+    // log_basis <= 31, else int64; u32: balanced int32 digits, for N = 2^16, k = 1 (the fused kernels)
+    void *sdigits = nullptr;
     size_t sdigit_bytes = 0;
-    ~pfhe_extprod_plan() {
+    ~ExtprodPlanCore() {
         if (!table) return;
         DeviceGuard g(table->device);
         if (digits) (void)counted_free(digits);
         if (sdigits) (void)counted_free(sdigits);
-        if (last_done) (void)hipEventDestroy(last_done);
     }
 };
-
-// The <u32> instantiation of the same product: CrtGlwe<u32>::mul_dcrt_ggsw_to over a U32DcrtTable (glwe/crt.rs:200-227,
-// dcrt/prime32.rs:11).  N = 2^16, k = 1 (the bench shape) takes the 64-bit plan's kernels on B32Arith: balanced int32
-// digits, lift + strided pass, block pass + multiply-accumulate (+ inverse block pass) with the transformed digits on chip.
-// Every other shape: steps (1)-(4) fused (gadget_decompose_kernel on u32 words), the table's forward transform over the
-// lifted digit polynomials, one multiply-accumulate kernel.  Chunk after chunk on the caller's stream.
-struct pfhe_extprod32_plan {
-    const TableSet *table = nullptr;  // borrowed from the pfhe_dcrt32 (must outlive the plan)
-    std::atomic<std::uintptr_t> owner{0};  // one holder at a time, as pfhe_extprod_plan
-    int depth = 0;
-    hipEvent_t last_done = nullptr;
-    bool last_valid = false;
-    RnsParams rns;
-    BasisParams basis_par;
-    BasisCore basis{};
-    u32 k = 1;
-    size_t chunk = 1;
-    u32 *digits = nullptr;  // chunk * (k+1) * ell * L * N words
-    size_t digits_words = 0;
-    int *sdigits = nullptr;  // N = 2^16, k = 1 (the fused kernels): chunk * (k+1) * ell * N balanced digits
-    bool use_fused = true;   // PFHE_DISABLE_FUSED_EXTPROD, read at plan creation
-    ~pfhe_extprod32_plan() {
-        if (!table) return;
-        DeviceGuard g(table->device);
-        if (digits) (void)counted_free(digits);
-        if (sdigits) (void)counted_free(sdigits);
-        if (last_done) (void)hipEventDestroy(last_done);
-    }
-};
+struct pfhe_extprod_plan : ExtprodPlanCore<u64> {};
+struct pfhe_extprod32_plan : ExtprodPlanCore<u32> {};
 
 namespace {
 
-int plan_check(const pfhe_extprod_plan *p) {
+constexpr const char *kPlanBusy =
+    "external-product plan in use by another thread (one plan per thread, like &mut DcrtGlevContext)";
+
+template <class Plan>
+int plan_check(const Plan *p) {
     if (!p || !p->table) return PFHE_ERR_BAD_ARGUMENT;
     return PFHE_OK;
 }
-
-// the calling thread's hold on a plan's scratch for one entry point (see pfhe_extprod_plan::owner)
-inline std::uintptr_t plan_thread_token() {
-    static thread_local char token;
-    return reinterpret_cast<std::uintptr_t>(&token);
-}
-// take (or re-enter) the plan for the calling thread; false: another thread holds it
-template <class Plan>
-bool plan_acquire(Plan *p) {
-    const std::uintptr_t me = plan_thread_token();
-    std::uintptr_t free_ = 0;
-    if (p->owner.load(std::memory_order_relaxed) == me) {
-        ++p->depth;  // nested entry of the thread that holds the plan
-        return true;
-    }
-    if (p->owner.compare_exchange_strong(free_, me, std::memory_order_acquire)) {
-        p->depth = 1;
-        return true;
-    }
-    return false;
-}
-template <class Plan>
-void plan_release(Plan *p) {
-    if (--p->depth == 0) p->owner.store(0, std::memory_order_release);
-}
-template <class Plan>
-class PlanLease {
-  public:
-    explicit PlanLease(Plan *p) : p_(p), held_(plan_acquire(p)) {}
-    ~PlanLease() {
-        if (held_) plan_release(p_);
-    }
-    PlanLease(const PlanLease &) = delete;
-    PlanLease &operator=(const PlanLease &) = delete;
-    bool held() const { return held_; }
-
-  private:
-    Plan *p_;
-    bool held_ = false;
-};
-#define PFHE_PLAN_LEASE(plan)                                                                                       \
-    PlanLease<typename std::remove_pointer<decltype(plan)>::type> lease_(plan);                                                                                          \
-    if (!lease_.held()) {                                                                                            \
-        set_last_error("external-product plan in use by another thread (one plan per thread, like &mut DcrtGlevContext)"); \
-        return PFHE_ERR_BUSY;                                                                                        \
-    }
 
 // one row of the product: acc[e] += glev[e or shared] (x) crt_poly[e]   (glwe/dcrt.rs:178-255)
 // rows == k+1 without `accumulate` gives CrtGlwe::mul_dcrt_ggsw_to (glwe/crt.rs:200-227).
@@ -148,106 +75,82 @@ class PlanLease {
 // transform this function already ran on the result: -1 = all of them (small-ring kernel), 1 = the block pass
 // (fused into the multiply-accumulate kernel; the caller runs the remaining strided pass), 0 = none.
 // `big_input`: the input polynomials are BigUintPolynomials (value_len limbs per coefficient) instead of CRT ones.
-int run_product_impl(pfhe_extprod_plan *p, const u64 *crt_polys, u32 rows, const u64 *keys, bool keys_shared, u64 *result,
-                     u64 batch, bool accumulate, hipStream_t s, bool into_coeff, int *coeff_passes, bool big_input) {
-    if (coeff_passes) *coeff_passes = 0;
-    const TableSet &t = *p->table;
-    const u64 W = (u64)t.L * t.n;
-    RnsParams rns = p->rns;
-    rns.dev.big_input = rns.wide_tab.big_input = big_input ? 1u : 0u;
-    const u64 in_words = big_input ? (u64)rns.dev.value_len * t.n : W;  // words per input polynomial
-    const u32 ell = p->basis.ell;
-    const u64 key_words = (u64)rows * ell * (p->k + 1) * W;
-    // Everything runs chunk after chunk on the caller's stream (also while the caller captures a HIP graph).
-    // small rings: digit extraction + ONE kernel for everything else
-    // (one workgroup per (ciphertext, limb) runs 12+ transforms back to back: it needs a batch that fills the chip)
-    if (p->sdigits != nullptr && extprod_small_supported(t.log_n, p->k, p->rns.dev.value_len, p->basis.log_basis) &&
-        batch * t.L >= 1024 && p->use_fused) {
+int run_product(pfhe_extprod_plan *p, const u64 *crt_polys, u32 rows, const u64 *keys, bool keys_shared, u64 *result,
+                u64 batch, bool accumulate, hipStream_t s, bool big_input, bool into_coeff = false,
+                int *coeff_passes = nullptr) {
+    return ordered_on(p->guard, s, [&]() -> int {
+        if (coeff_passes) *coeff_passes = 0;
+        const TableSet &t = *p->table;
+        const u64 W = (u64)t.L * t.n;
+        RnsParams rns = p->rns;
+        rns.dev.big_input = rns.wide_tab.big_input = big_input ? 1u : 0u;
+        const u64 in_words = big_input ? (u64)rns.dev.value_len * t.n : W;  // words per input polynomial
+        const u32 ell = p->basis.ell;
+        const u64 key_words = (u64)rows * ell * (p->k + 1) * W;
+        // Everything runs chunk after chunk on the caller's stream (also while the caller captures a HIP graph).
+        // small rings: digit extraction + ONE kernel for everything else
+        // (one workgroup per (ciphertext, limb) runs 12+ transforms back to back: it needs a batch that fills the chip)
+        if (p->sdigits != nullptr && extprod_small_supported(t.log_n, p->k, p->rns.dev.value_len, p->basis.log_basis) &&
+            batch * t.L >= 1024 && p->use_fused) {
+            for (u64 done = 0; done < batch; done += p->chunk) {
+                const u64 cur = std::min<u64>(p->chunk, batch - done);
+                PFHE_TRY(gadget_signed_digits_dev(rns, p->basis_par, t.log_n, crt_polys + done * rows * in_words, (int *)p->sdigits, cur * rows, s));
+                PFHE_TRY(extprod_small_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, p->k, rows, ell, (const int *)p->sdigits,
+                                           keys + (keys_shared ? 0 : done * key_words), keys_shared,
+                                           result + done * (p->k + 1) * W, cur, accumulate, into_coeff, s));
+            }
+            if (coeff_passes) *coeff_passes = into_coeff ? -1 : 0;
+            return PFHE_OK;
+        }
+        const bool fused = gadget_fused_supported(t.log_n, p->k) && p->use_fused &&
+                           ((std::min<u64>(batch, p->chunk) * t.L) << (t.log_n - 12)) >= p->fused_min_wgs;
+        const int passes = ntt_num_passes(t.log_n, t.ntt_arith, t.tune);
+        // One arithmetic for everything in here — the gadget kernels and the plain transform passes around them: the table's
+        // transform arithmetic t.ntt_arith (pseudo-Mersenne, Montgomery form for generic primes below 2^61, or the
+        // reference's Shoup form).
+        // coefficient-form output: the inverse transform's block pass runs inside the fused kernel, on the accumulators
+        const bool inv_tail = fused && into_coeff && !accumulate && coeff_passes != nullptr && passes == 2;
+        if (inv_tail) *coeff_passes = 1;
+        const bool fused_decompose = gadget_decompose_strided_supported(t.log_n, p->rns.dev.value_len) && p->sdigits != nullptr;
+        u64 *dg = p->digits;
         for (u64 done = 0; done < batch; done += p->chunk) {
             const u64 cur = std::min<u64>(p->chunk, batch - done);
-            PFHE_TRY(gadget_signed_digits_dev(rns, p->basis_par, t.log_n, crt_polys + done * rows * in_words, (int *)p->sdigits, cur * rows, s));
-            PFHE_TRY(extprod_small_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, p->k, rows, ell, (const int *)p->sdigits,
-                                       keys + (keys_shared ? 0 : done * key_words), keys_shared,
-                                       result + done * (p->k + 1) * W, cur, accumulate, into_coeff, s));
+            const u64 npolys = cur * rows * ell * t.L;
+            const auto stamp = [&]() -> int {
+                if (p->prof == nullptr) return PFHE_OK;
+                hipEvent_t ev = nullptr;
+                PFHE_HIP(hipEventCreate(&ev));
+                p->prof->push_back(ev);
+                PFHE_HIP(hipEventRecord(ev, s));
+                return PFHE_OK;
+            };
+            PFHE_TRY(stamp());
+            // ---- steps (1)-(4) + strided passes into the digit buffer ----
+            if (fused_decompose) {
+                PFHE_TRY(gadget_decompose_strided_dev(rns, p->basis_par, t.primes_dev, t.log_n, t.ntt_arith,
+                                                      crt_polys + done * rows * in_words, dg, cur * rows, s, p->sdigits));
+            } else {
+                PFHE_TRY(gadget_decompose_dev(rns, p->basis_par, t.log_n, crt_polys + done * rows * in_words, dg, cur * rows, s));
+                for (int i = 0; i < passes - 1; ++i)
+                    PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, i, false, s, nullptr, 0, t.tune));
+            }
+            PFHE_TRY(stamp());
+            // ---- block pass (last pass of the transform) + multiply-accumulate ----
+            if (fused) {
+                PFHE_TRY(gadget_block_mulacc_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, p->k, rows * ell, dg,
+                                                 keys + (keys_shared ? 0 : done * key_words), keys_shared,
+                                                 result + done * (p->k + 1) * W, cur, accumulate, s, inv_tail));
+            } else {
+                PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, passes - 1, false, s, nullptr, 0,
+                                      t.tune));
+                PFHE_TRY(gadget_mulacc_dev(t.primes_dev, t.L, t.log_n, p->k, rows, ell, dg,
+                                           keys + (keys_shared ? 0 : done * key_words), keys_shared,
+                                           result + done * (p->k + 1) * W, cur, accumulate, s));
+            }
+            PFHE_TRY(stamp());
         }
-        if (coeff_passes) *coeff_passes = into_coeff ? -1 : 0;
         return PFHE_OK;
-    }
-    const bool fused = gadget_fused_supported(t.log_n, p->k) && p->use_fused &&
-                       ((std::min<u64>(batch, p->chunk) * t.L) << (t.log_n - 12)) >= p->fused_min_wgs;
-    const int passes = ntt_num_passes(t.log_n, t.ntt_arith, t.tune);
-    // One arithmetic for everything in here — the gadget kernels and the plain transform passes around them: the table's
-    // transform arithmetic t.ntt_arith (pseudo-Mersenne, Montgomery form for generic primes below 2^61, or the
-    // reference's Shoup form).
-    // coefficient-form output: the inverse transform's block pass runs inside the fused kernel, on the accumulators
-    const bool inv_tail = fused && into_coeff && !accumulate && coeff_passes != nullptr && passes == 2;
-    if (inv_tail) *coeff_passes = 1;
-    const bool fused_decompose = gadget_decompose_strided_supported(t.log_n, p->rns.dev.value_len) && p->sdigits != nullptr;
-    u64 *dg = p->digits;
-    for (u64 done = 0; done < batch; done += p->chunk) {
-        const u64 cur = std::min<u64>(p->chunk, batch - done);
-        const u64 npolys = cur * rows * ell * t.L;
-        const auto stamp = [&]() -> int {
-            if (p->prof == nullptr) return PFHE_OK;
-            hipEvent_t ev = nullptr;
-            PFHE_HIP(hipEventCreate(&ev));
-            p->prof->push_back(ev);
-            PFHE_HIP(hipEventRecord(ev, s));
-            return PFHE_OK;
-        };
-        PFHE_TRY(stamp());
-        // ---- steps (1)-(4) + strided passes into the digit buffer ----
-        if (fused_decompose) {
-            PFHE_TRY(gadget_decompose_strided_dev(rns, p->basis_par, t.primes_dev, t.log_n, t.ntt_arith,
-                                                  crt_polys + done * rows * in_words, dg, cur * rows, s, p->sdigits));
-        } else {
-            PFHE_TRY(gadget_decompose_dev(rns, p->basis_par, t.log_n, crt_polys + done * rows * in_words, dg, cur * rows, s));
-            for (int i = 0; i < passes - 1; ++i)
-                PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, i, false, s, nullptr, 0, t.tune));
-        }
-        PFHE_TRY(stamp());
-        // ---- block pass (last pass of the transform) + multiply-accumulate ----
-        if (fused) {
-            PFHE_TRY(gadget_block_mulacc_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, p->k, rows * ell, dg,
-                                             keys + (keys_shared ? 0 : done * key_words), keys_shared,
-                                             result + done * (p->k + 1) * W, cur, accumulate, s, inv_tail));
-        } else {
-            PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, passes - 1, false, s, nullptr, 0,
-                                  t.tune));
-            PFHE_TRY(gadget_mulacc_dev(t.primes_dev, t.L, t.log_n, p->k, rows, ell, dg,
-                                       keys + (keys_shared ? 0 : done * key_words), keys_shared,
-                                       result + done * (p->k + 1) * W, cur, accumulate, s));
-        }
-        PFHE_TRY(stamp());
-    }
-    return PFHE_OK;
-}
-
-
-// The plan's digit buffers are touched by run_product_impl only.  Successive calls on DIFFERENT streams are ordered here:
-// every call records the plan's `last_done` event behind its last kernel, and a call on another stream first makes that
-// stream wait for it — so "one plan, used from one stream after another" needs no event handling by the caller (calls by
-// two THREADS at once are refused by the lease above; work captured into a HIP graph is outside this bookkeeping: a
-// capturing stream neither waits nor records, and a graph that uses a plan must not be replayed beside other users of it).
-int run_product(pfhe_extprod_plan *p, const u64 *crt_polys, u32 rows, const u64 *keys, bool keys_shared, u64 *result,
-                u64 batch, bool accumulate, hipStream_t s, bool into_coeff = false, int *coeff_passes = nullptr,
-                bool big_input = false) {
-    const bool tracked = p->last_done != nullptr && !stream_is_capturing(s);
-    // (always, also on the stream that recorded it: a handle comparison would miss a stream destroyed and re-created at
-    // the same address; waiting on one's own stream's event costs nothing)
-    if (tracked && p->last_valid) PFHE_HIP(hipStreamWaitEvent(s, p->last_done, 0));
-    const int rc = run_product_impl(p, crt_polys, rows, keys, keys_shared, result, batch, accumulate, s, into_coeff, coeff_passes,
-                                    big_input);
-    if (tracked) {  // also after a failed call: whatever it queued still uses the buffers
-        if (hipEventRecord(p->last_done, s) == hipSuccess) {
-            p->last_valid = true;
-        } else {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s);  // no event: fall back to draining the stream
-            p->last_valid = false;
-        }
-    }
-    return rc;
+    });
 }
 
 }  // namespace
@@ -746,14 +649,98 @@ extern "C" {
 PFHE_RNS_FAMILY(pfhe_rns, pfhe_basis, uint64_t)
 PFHE_RNS_FAMILY(pfhe_rns32, pfhe_basis32, uint32_t)
 
+}  // extern "C"
+
 /* ------------------------------ external product ------------------------------ */
 
-int pfhe_extprod_plan_create(const pfhe_dcrt *table, const pfhe_rns *rns, const pfhe_basis *basis,
-                             size_t glwe_dimension, size_t chunk, pfhe_extprod_plan **out) {
-    PFHE_GUARD_BEGIN
+namespace {
+
+// The <u32> product.  N = 2^16, k = 1 (the bench shape) takes the 64-bit plan's kernels on B32Arith: balanced int32
+// digits, lift + strided pass, block pass + multiply-accumulate (+ inverse block pass) with the transformed digits on chip.
+// Every other shape: steps (1)-(4) fused (gadget_decompose_kernel on u32 words), the table's forward transform over the
+// lifted digit polynomials, one multiply-accumulate kernel.  Chunk after chunk on the caller's stream.
+// *coeff_passes (when the caller wants coefficient form): 1 = the inverse transform's block pass ran inside the fused
+// kernel (the caller runs the strided pass), 0 = none
+int run_product(pfhe_extprod32_plan *p, const u32 *polys, u32 rows, const u32 *keys, bool keys_shared, u32 *result,
+                u64 batch, bool accumulate, hipStream_t s, bool big_input, bool into_coeff = false,
+                int *coeff_passes = nullptr) {
+    return ordered_on(p->guard, s, [&]() -> int {
+        if (coeff_passes) *coeff_passes = 0;
+        const TableSet &t = *p->table;
+        const u64 W = (u64)t.L * t.n;
+        RnsParams rns = p->rns;
+        rns.dev.big_input = rns.wide_tab.big_input = big_input ? 1u : 0u;
+        const u64 in_words = big_input ? (u64)rns.dev.value_words * t.n : W;
+        const u32 ell = p->basis.ell;
+        const u64 key_words = (u64)rows * ell * (p->k + 1) * W;
+        int *sdigits = (int *)p->sdigits;
+        // the fused kernels launch one workgroup per (ciphertext, limb, block): they pay once that fills the chip
+        const bool fused = sdigits != nullptr && p->use_fused && extprod32_fused_supported(t.log_n, p->k) &&
+                           ((std::min<u64>(batch, p->chunk) * t.L) << (t.log_n - 12)) >= p->fused_min_wgs;
+        const bool inv_tail = fused && into_coeff && !accumulate && coeff_passes != nullptr;
+        if (inv_tail) *coeff_passes = 1;
+        for (u64 done = 0; done < batch; done += p->chunk) {
+            const u64 cur = std::min<u64>(p->chunk, batch - done);
+            const u32 *kp = keys + (keys_shared ? 0 : done * key_words);
+            u32 *rp = result + done * (p->k + 1) * W;
+            if (fused) {
+                PFHE_TRY(gadget_signed_digits_dev<u32>(rns, p->basis_par, t.log_n, polys + done * rows * in_words, sdigits, cur * rows, s));
+                PFHE_TRY(digits_strided32_dev(t.primes_dev, t.L, t.log_n, ell, sdigits, p->digits, cur * rows, s));
+                PFHE_TRY(gadget_block_mulacc32_dev(t.primes_dev, t.L, t.log_n, rows * ell, p->digits, kp, keys_shared, rp, cur,
+                                                   accumulate, inv_tail, s));
+                continue;
+            }
+            PFHE_TRY(gadget_decompose_dev<u32>(rns, p->basis_par, t.log_n, polys + done * rows * in_words, p->digits, cur * rows, s));
+            PFHE_TRY(ntt32_transform_dev(t.primes_dev, t.L, t.log_n, p->digits, cur * rows * ell * t.L, false, false, s, t.tune));
+            PFHE_TRY(gadget_mulacc32_dev(t.primes_dev, t.L, t.log_n, p->k, rows, ell, p->digits, kp, keys_shared, rp, cur, accumulate, s));
+        }
+        return PFHE_OK;
+    });
+}
+
+// The rest of DcrtGlwe::into_coeff_form (macros/mod.rs:901-911) after a product that reported `coeff_passes`.
+// u64: nothing ran -> the whole inverse; the block pass ran -> the remaining passes
+int finish_coeff_form(const pfhe_extprod_plan *plan, u64 *result, u64 batch, int coeff_passes, hipStream_t s) {
+    const TableSet &t = *plan->table;
+    if (coeff_passes == 0)
+        PFHE_TRY(ntt_inverse_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, result, batch * (plan->k + 1) * t.L, false, s, t.tune));
+    for (int i = coeff_passes; i > 0 && i < ntt_num_passes(t.log_n, t.ntt_arith, t.tune); ++i)
+        PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, result, batch * (plan->k + 1) * t.L, true, i, false, s,
+                              nullptr, 0, t.tune));
+    return PFHE_OK;
+}
+// u32: nothing ran -> the table's inverse; the block pass ran inside the fused kernel -> the strided pass finishes
+int finish_coeff_form(const pfhe_extprod32_plan *plan, u32 *result, u64 batch, int coeff_passes, hipStream_t s) {
+    const TableSet &t = *plan->table;
+    if (coeff_passes == 0)
+        PFHE_TRY(ntt32_transform_dev(t.primes_dev, t.L, t.log_n, result, batch * (plan->k + 1) * t.L, true, false, s, t.tune));
+    if (coeff_passes == 1)
+        PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n - 1, kArithB32, reinterpret_cast<u64 *>(result),
+                              batch * (plan->k + 1) * t.L, true, 1, false, s, nullptr, 0, t.tune));
+    return PFHE_OK;
+}
+
+// bytes per compact signed digit when one of the width's kernels wants them for this shape, else 0 (no buffer)
+size_t sdigit_bytes_for(const pfhe_extprod_plan &p) {
+    const TableSet &t = *p.table;
+    return gadget_decompose_strided_supported(t.log_n, p.rns.dev.value_len) ||
+                   extprod_small_supported(t.log_n, p.k, p.rns.dev.value_len, p.basis.log_basis)
+               ? gadget_digit_bytes(p.basis.log_basis)
+               : 0;
+}
+size_t sdigit_bytes_for(const pfhe_extprod32_plan &p) {
+    return p.use_fused && extprod32_fused_supported(p.table->log_n, p.k) ? sizeof(int) : 0;
+}
+
+inline const TableSet *table_of(const pfhe_dcrt *t) { return capi_table_of(t); }
+inline const TableSet *table_of(const pfhe_dcrt32 *t) { return capi_table32_of(t); }
+
+template <class Plan, class Table, class Rns, class Basis>
+int plan_create(const Table *table, const Rns *rns, const Basis *basis, size_t glwe_dimension, size_t chunk, Plan **out) {
+    using W = typename Plan::Word;
     if (!out || !table || !rns || !basis || glwe_dimension == 0 || glwe_dimension > 64) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    const TableSet *t = capi_table_of(table);
+    const TableSet *t = table_of(table);
     if (t->L != rns->h.par.dev.L) {
         set_last_error("DCRT table and RNS base have different moduli counts");
         return PFHE_ERR_BAD_ARGUMENT;
@@ -771,18 +758,20 @@ int pfhe_extprod_plan_create(const pfhe_dcrt *table, const pfhe_rns *rns, const 
             return PFHE_ERR_BAD_ARGUMENT;
         }
     }
-    auto p = std::make_unique<pfhe_extprod_plan>();
+    auto p = std::make_unique<Plan>();
     p->table = t;
     p->rns = rns->h.par;
     p->basis_par = basis->h.par;
     p->basis = basis->h.par.dev;
     p->k = (u32)glwe_dimension;
-    // default: about 2 GiB of digit polynomials per buffer, at least 128 ciphertexts — measured at N = 2^16, 3 limbs
-    // with today's kernels (ms per 1024 products): 32: 21.7, 64: 21.2, 128: 20.8, 256: 20.9, 1024: 20.8 (round 1, slower
-    // kernels: 64 was the optimum); small rings need many more ciphertexts per launch to amortise the launches
+    // default: about 2 GiB (u64) / 1 GiB (u32) of digit polynomials per buffer, at least 128 ciphertexts — measured at
+    // N = 2^16, 3 limbs, u64, with today's kernels (ms per 1024 products): 32: 21.7, 64: 21.2, 128: 20.8, 256: 20.9,
+    // 1024: 20.8 (round 1, slower kernels: 64 was the optimum); small rings need many more ciphertexts per launch to
+    // amortise the launches
     if (chunk == 0) {
-        const size_t per_ct = (size_t)(glwe_dimension + 1) * p->basis.ell * t->L * t->n * sizeof(u64);
-        chunk = std::max<size_t>(128, std::min<size_t>(65536, ((size_t)2 << 30) / per_ct));
+        const size_t per_ct = (size_t)(glwe_dimension + 1) * p->basis.ell * t->L * t->n * sizeof(W);
+        const size_t budget = sizeof(W) == 8 ? (size_t)2 << 30 : (size_t)1 << 30;
+        chunk = std::max<size_t>(128, std::min<size_t>(65536, budget / per_ct));
     }
     p->chunk = chunk;
     p->digits_words = p->chunk * (p->k + 1) * p->basis.ell * t->L * t->n;
@@ -790,50 +779,31 @@ int pfhe_extprod_plan_create(const pfhe_dcrt *table, const pfhe_rns *rns, const 
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     // read here, once, and kept in the plan (nothing on the launch path calls getenv)
     p->use_fused = std::getenv("PFHE_DISABLE_FUSED_EXTPROD") == nullptr;
-    {
-        void *d = nullptr;
-        PFHE_HIP(counted_malloc(&d, p->digits_words * sizeof(u64)));
-        p->digits = (u64 *)d;
-    }
-    if (gadget_decompose_strided_supported(t->log_n, p->rns.dev.value_len) ||
-        extprod_small_supported(t->log_n, p->k, p->rns.dev.value_len, p->basis.log_basis)) {
-        void *d = nullptr;
-        p->sdigit_bytes = gadget_digit_bytes(p->basis.log_basis);
-        PFHE_HIP(counted_malloc(&d, p->chunk * (p->k + 1) * p->basis.ell * t->n * p->sdigit_bytes));
-        p->sdigits = d;
-    }
-    PFHE_HIP(hipEventCreateWithFlags(&p->last_done, hipEventDisableTiming));
+    void *d = nullptr;
+    PFHE_HIP(counted_malloc(&d, p->digits_words * sizeof(W)));
+    p->digits = (W *)d;
+    p->sdigit_bytes = sdigit_bytes_for(*p);
+    if (p->sdigit_bytes)
+        PFHE_HIP(counted_malloc(&p->sdigits, p->chunk * (p->k + 1) * p->basis.ell * t->n * p->sdigit_bytes));
+    PFHE_TRY(p->guard.init(t->device));
     *out = p.release();
     return PFHE_OK;
-    PFHE_GUARD_END
 }
 
-void pfhe_extprod_plan_destroy(pfhe_extprod_plan *p) { delete p; }
-int pfhe_extprod_plan_in_use(const pfhe_extprod_plan *p) {
-    return p && p->owner.load(std::memory_order_acquire) != 0 ? 1 : 0;
-}
-// test aid: hold != 0 takes the plan for the calling thread as an entry point would (PFHE_ERR_BUSY if another thread has
-// it) and keeps it until the same thread calls with hold == 0
-int pfhe_extprod_plan_debug_hold(pfhe_extprod_plan *p, int hold) {
-    if (plan_check(p) != PFHE_OK) return PFHE_ERR_BAD_ARGUMENT;
-    if (hold) return plan_acquire(p) ? PFHE_OK : PFHE_ERR_BUSY;
-    if (p->owner.load(std::memory_order_relaxed) != plan_thread_token()) return PFHE_ERR_BAD_ARGUMENT;
-    plan_release(p);
-    return PFHE_OK;
-}
-size_t pfhe_extprod_plan_scratch_bytes(const pfhe_extprod_plan *p) {
+template <class Plan>
+size_t plan_scratch_bytes(const Plan *p) {
     if (!p) return 0;
-    return p->digits_words * 8 + (p->sdigits ? p->chunk * (p->k + 1) * p->basis.ell * p->table->n * p->sdigit_bytes : 0);
+    return p->digits_words * sizeof(typename Plan::Word) +
+           (p->sdigits ? p->chunk * (p->k + 1) * p->basis.ell * p->table->n * p->sdigit_bytes : 0);
 }
 
-int pfhe_extprod_mul_dcrt_ggsw_to_dev(pfhe_extprod_plan *plan, const uint64_t *crt_glwe_dev, size_t len_glwe,
-                                      const uint64_t *dcrt_ggsw_dev, size_t len_ggsw, uint64_t *result_dev,
-                                      size_t len_result, int into_coeff_form, void *stream) {
-    PFHE_GUARD_BEGIN
+template <class Plan, class W>
+int mul_dcrt_ggsw_to_dev(Plan *plan, const W *crt_glwe_dev, size_t len_glwe, const W *dcrt_ggsw_dev, size_t len_ggsw,
+                         W *result_dev, size_t len_result, int into_coeff_form, hipStream_t stream) {
     PFHE_TRY(plan_check(plan));
-    PFHE_PLAN_LEASE(plan);
+    PFHE_PLAN_LEASE(plan->guard, kPlanBusy);
     const TableSet &t = *plan->table;
-    const size_t W = (size_t)t.L * t.n, glwe = (plan->k + 1) * W;
+    const size_t words = (size_t)t.L * t.n, glwe = (plan->k + 1) * words;
     const size_t ggsw = (size_t)(plan->k + 1) * plan->basis.ell * glwe;
     if (len_glwe % glwe != 0 || len_result != len_glwe || (len_ggsw != ggsw && len_ggsw != len_glwe / glwe * ggsw)) {
         set_last_error("external product: glwe/result must be batch*(k+1)*L*N words and the GGSW one or batch "
@@ -848,18 +818,93 @@ int pfhe_extprod_mul_dcrt_ggsw_to_dev(pfhe_extprod_plan *plan, const uint64_t *c
     PFHE_REQUIRE_ALIGNED(result_dev);
     DeviceGuard g(t.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const bool shared = len_ggsw == ggsw && batch > 1 ? true : (len_ggsw == ggsw);
     // result.set_zero() (glwe/crt.rs:217) is implied: the first accumulation overwrites
     int coeff_passes = 0;
-    PFHE_TRY(run_product(plan, (const u64 *)crt_glwe_dev, plan->k + 1, (const u64 *)dcrt_ggsw_dev, shared,
-                         (u64 *)result_dev, batch, false, (hipStream_t)stream, into_coeff_form != 0, &coeff_passes));
-    if (into_coeff_form && coeff_passes == 0)  // DcrtGlwe::into_coeff_form, macros/mod.rs:901-911
-        PFHE_TRY(ntt_inverse_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, (u64 *)result_dev, batch * (plan->k + 1) * t.L, false,
-                                 (hipStream_t)stream, t.tune));
-    for (int i = coeff_passes; into_coeff_form && i > 0 && i < ntt_num_passes(t.log_n, t.ntt_arith, t.tune); ++i)
-        PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, (u64 *)result_dev, batch * (plan->k + 1) * t.L, true, i,
-                              false, (hipStream_t)stream, nullptr, 0, t.tune));
+    PFHE_TRY(run_product(plan, crt_glwe_dev, plan->k + 1, dcrt_ggsw_dev, len_ggsw == ggsw, result_dev, batch, false, stream,
+                         false, into_coeff_form != 0, &coeff_passes));
+    if (into_coeff_form) PFHE_TRY(finish_coeff_form(plan, result_dev, batch, coeff_passes, stream));
     return PFHE_OK;
+}
+
+template <class Plan, class W>
+int mul_dcrt_ggsw_to(Plan *plan, const W *crt_glwe, size_t len_glwe, const W *dcrt_ggsw, size_t len_ggsw, W *result,
+                     size_t len_result, int into_coeff_form) {
+    PFHE_TRY(plan_check(plan));
+    PFHE_PLAN_LEASE(plan->guard, kPlanBusy);
+    if ((!crt_glwe || !dcrt_ggsw || !result) && len_glwe) return PFHE_ERR_BAD_ARGUMENT;
+    DeviceGuard g(plan->table->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(plan->table->device);  // pooled staging context: no allocation in steady state
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *a = nullptr, *k = nullptr, *r = nullptr;
+    PFHE_TRY(st.upload(crt_glwe, len_glwe * sizeof(W), &a));
+    PFHE_TRY(st.upload(dcrt_ggsw, len_ggsw * sizeof(W), &k));
+    PFHE_TRY(st.alloc(len_result * sizeof(W), &r));
+    PFHE_TRY(mul_dcrt_ggsw_to_dev(plan, (const W *)a, len_glwe, (const W *)k, len_ggsw, (W *)r, len_result, into_coeff_form,
+                                  st.stream()));
+    PFHE_TRY(st.download(result, r, len_result * sizeof(W)));
+    return st.finish();
+}
+
+// The GLev rows against `batch` polynomials, accumulating or overwriting (`out_name`: what the length message calls the output).  CRT residues: DcrtGlwe::
+// add_dcrt_glev_mul_crt_poly_assign (glwe/dcrt.rs:178-255); big integers modulo Q (`big_input`): DcrtGlwe::
+// add_dcrt_glev_mul_big_uint_poly_assign (glwe/dcrt.rs:258-338) / DcrtGlev::mul_big_uint_poly_to (glev/dcrt.rs:113-175)
+template <class Plan, class W>
+int glev_common(Plan *plan, W *out_dev, size_t len_out, const W *dcrt_glev_dev, size_t len_glev, const W *poly_dev,
+                size_t len_poly, bool accumulate, bool big_input, const char *out_name, void *stream) {
+    PFHE_TRY(plan_check(plan));
+    PFHE_PLAN_LEASE(plan->guard, kPlanBusy);
+    const TableSet &t = *plan->table;
+    const size_t words = (size_t)t.L * t.n, glwe = (plan->k + 1) * words, glev = plan->basis.ell * glwe;
+    const size_t value_words = sizeof(W) == 8 ? plan->rns.dev.value_len : plan->rns.dev.value_words;
+    const size_t in_words = big_input ? value_words * t.n : words;
+    if (len_poly % in_words != 0) return PFHE_ERR_BAD_LENGTH;  // glwe/dcrt.rs:277
+    const u64 batch = len_poly / in_words;
+    if (len_out != batch * glwe || (len_glev != glev && len_glev != batch * glev)) {
+        set_last_error(std::string("glev product: ") + out_name +
+                       " must be batch*(k+1)*L*N words and the GLev one or batch of ell*(k+1)*L*N");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (batch == 0) return PFHE_OK;
+    if (!out_dev || !dcrt_glev_dev || !poly_dev) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(out_dev);
+    PFHE_REQUIRE_ALIGNED(dcrt_glev_dev);
+    PFHE_REQUIRE_ALIGNED(poly_dev);
+    DeviceGuard g(t.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return run_product(plan, poly_dev, 1, dcrt_glev_dev, len_glev == glev, out_dev, batch, accumulate, (hipStream_t)stream,
+                       big_input);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfhe_extprod_plan_create(const pfhe_dcrt *table, const pfhe_rns *rns, const pfhe_basis *basis,
+                             size_t glwe_dimension, size_t chunk, pfhe_extprod_plan **out) {
+    PFHE_GUARD_BEGIN
+    return plan_create(table, rns, basis, glwe_dimension, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_extprod_plan_destroy(pfhe_extprod_plan *p) { delete p; }
+int pfhe_extprod_plan_in_use(const pfhe_extprod_plan *p) { return p ? p->guard.in_use() : 0; }
+// test aid: hold != 0 takes the plan for the calling thread as an entry point would (PFHE_ERR_BUSY if another thread has
+// it) and keeps it until the same thread calls with hold == 0
+int pfhe_extprod_plan_debug_hold(pfhe_extprod_plan *p, int hold) {
+    if (plan_check(p) != PFHE_OK) return PFHE_ERR_BAD_ARGUMENT;
+    if (hold) return p->guard.acquire() ? PFHE_OK : PFHE_ERR_BUSY;
+    if (!p->guard.held_by_caller()) return PFHE_ERR_BAD_ARGUMENT;
+    p->guard.release();
+    return PFHE_OK;
+}
+size_t pfhe_extprod_plan_scratch_bytes(const pfhe_extprod_plan *p) { return plan_scratch_bytes(p); }
+
+int pfhe_extprod_mul_dcrt_ggsw_to_dev(pfhe_extprod_plan *plan, const uint64_t *crt_glwe_dev, size_t len_glwe,
+                                      const uint64_t *dcrt_ggsw_dev, size_t len_ggsw, uint64_t *result_dev,
+                                      size_t len_result, int into_coeff_form, void *stream) {
+    PFHE_GUARD_BEGIN
+    return mul_dcrt_ggsw_to_dev(plan, (const u64 *)crt_glwe_dev, len_glwe, (const u64 *)dcrt_ggsw_dev, len_ggsw,
+                                (u64 *)result_dev, len_result, into_coeff_form, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 
@@ -868,7 +913,7 @@ int pfhe_extprod_profile_dev(pfhe_extprod_plan *plan, const uint64_t *crt_glwe_d
                              double *ms_out, size_t *launches_out, void *stream) {
     PFHE_GUARD_BEGIN
     PFHE_TRY(plan_check(plan));
-    PFHE_PLAN_LEASE(plan);
+    PFHE_PLAN_LEASE(plan->guard, kPlanBusy);
     if (!ms_out || !launches_out) return PFHE_ERR_BAD_ARGUMENT;
     std::vector<hipEvent_t> ev;
     plan->prof = &ev;
@@ -897,25 +942,8 @@ int pfhe_extprod_add_dcrt_glev_mul_crt_poly_assign_dev(pfhe_extprod_plan *plan, 
                                                        const uint64_t *dcrt_glev_dev, size_t len_glev,
                                                        const uint64_t *crt_poly_dev, size_t len_poly, void *stream) {
     PFHE_GUARD_BEGIN
-    PFHE_TRY(plan_check(plan));
-    PFHE_PLAN_LEASE(plan);
-    const TableSet &t = *plan->table;
-    const size_t W = (size_t)t.L * t.n, glwe = (plan->k + 1) * W, glev = plan->basis.ell * glwe;
-    if (len_poly % W != 0) return PFHE_ERR_BAD_LENGTH;
-    const u64 batch = len_poly / W;
-    if (len_acc != batch * glwe || (len_glev != glev && len_glev != batch * glev)) {
-        set_last_error("glev product: acc must be batch*(k+1)*L*N words and the GLev one or batch of ell*(k+1)*L*N");
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    if (batch == 0) return PFHE_OK;
-    if (!acc_dev || !dcrt_glev_dev || !crt_poly_dev) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(acc_dev);
-    PFHE_REQUIRE_ALIGNED(dcrt_glev_dev);
-    PFHE_REQUIRE_ALIGNED(crt_poly_dev);
-    DeviceGuard g(t.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return run_product(plan, (const u64 *)crt_poly_dev, 1, (const u64 *)dcrt_glev_dev, len_glev == glev,
-                       (u64 *)acc_dev, batch, true, (hipStream_t)stream);
+    return glev_common(plan, (u64 *)acc_dev, len_acc, (const u64 *)dcrt_glev_dev, len_glev, (const u64 *)crt_poly_dev,
+                       len_poly, true, false, "acc", stream);
     PFHE_GUARD_END
 }
 
@@ -923,53 +951,9 @@ int pfhe_extprod_glev_mul_crt_poly_to_dev(pfhe_extprod_plan *plan, const uint64_
                                           const uint64_t *crt_poly_dev, size_t len_poly, uint64_t *result_dev,
                                           size_t len_result, void *stream) {
     PFHE_GUARD_BEGIN
-    PFHE_TRY(plan_check(plan));
-    PFHE_PLAN_LEASE(plan);
-    const TableSet &t = *plan->table;
-    const size_t W = (size_t)t.L * t.n, glwe = (plan->k + 1) * W, glev = plan->basis.ell * glwe;
-    if (len_poly % W != 0) return PFHE_ERR_BAD_LENGTH;
-    const u64 batch = len_poly / W;
-    if (len_result != batch * glwe || (len_glev != glev && len_glev != batch * glev)) {
-        set_last_error("glev product: result must be batch*(k+1)*L*N words and the GLev one or batch of ell*(k+1)*L*N");
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    if (batch == 0) return PFHE_OK;
-    if (!result_dev || !dcrt_glev_dev || !crt_poly_dev) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(result_dev);
-    PFHE_REQUIRE_ALIGNED(dcrt_glev_dev);
-    PFHE_REQUIRE_ALIGNED(crt_poly_dev);
-    DeviceGuard g(t.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return run_product(plan, (const u64 *)crt_poly_dev, 1, (const u64 *)dcrt_glev_dev, len_glev == glev,
-                       (u64 *)result_dev, batch, false, (hipStream_t)stream);
+    return glev_common(plan, (u64 *)result_dev, len_result, (const u64 *)dcrt_glev_dev, len_glev,
+                       (const u64 *)crt_poly_dev, len_poly, false, false, "result", stream);
     PFHE_GUARD_END
-}
-
-// DcrtGlwe::add_dcrt_glev_mul_big_uint_poly_assign (glwe/dcrt.rs:258-338) / DcrtGlev::mul_big_uint_poly_to
-// (glev/dcrt.rs:113-175): the GLev rows against polynomials given as big integers modulo Q
-static int glev_big_uint_common(pfhe_extprod_plan *plan, uint64_t *out_dev, size_t len_out, const uint64_t *dcrt_glev_dev,
-                                size_t len_glev, const uint64_t *big_uint_poly_dev, size_t len_poly, bool accumulate,
-                                void *stream) {
-    PFHE_TRY(plan_check(plan));
-    PFHE_PLAN_LEASE(plan);
-    const TableSet &t = *plan->table;
-    const size_t W = (size_t)t.L * t.n, glwe = (plan->k + 1) * W, glev = plan->basis.ell * glwe;
-    const size_t in_words = (size_t)plan->rns.dev.value_len * t.n;
-    if (len_poly % in_words != 0) return PFHE_ERR_BAD_LENGTH;  // glwe/dcrt.rs:277
-    const u64 batch = len_poly / in_words;
-    if (len_out != batch * glwe || (len_glev != glev && len_glev != batch * glev)) {
-        set_last_error("glev product: acc/result must be batch*(k+1)*L*N words and the GLev one or batch of ell*(k+1)*L*N");
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    if (batch == 0) return PFHE_OK;
-    if (!out_dev || !dcrt_glev_dev || !big_uint_poly_dev) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(out_dev);
-    PFHE_REQUIRE_ALIGNED(dcrt_glev_dev);
-    PFHE_REQUIRE_ALIGNED(big_uint_poly_dev);
-    DeviceGuard g(t.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return run_product(plan, (const u64 *)big_uint_poly_dev, 1, (const u64 *)dcrt_glev_dev, len_glev == glev,
-                       (u64 *)out_dev, batch, accumulate, (hipStream_t)stream, false, nullptr, true);
 }
 
 int pfhe_extprod_add_dcrt_glev_mul_big_uint_poly_assign_dev(pfhe_extprod_plan *plan, uint64_t *acc_dev, size_t len_acc,
@@ -977,7 +961,8 @@ int pfhe_extprod_add_dcrt_glev_mul_big_uint_poly_assign_dev(pfhe_extprod_plan *p
                                                             const uint64_t *big_uint_poly_dev, size_t len_poly,
                                                             void *stream) {
     PFHE_GUARD_BEGIN
-    return glev_big_uint_common(plan, acc_dev, len_acc, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, true, stream);
+    return glev_common(plan, (u64 *)acc_dev, len_acc, (const u64 *)dcrt_glev_dev, len_glev,
+                       (const u64 *)big_uint_poly_dev, len_poly, true, true, "acc/result", stream);
     PFHE_GUARD_END
 }
 
@@ -985,8 +970,8 @@ int pfhe_extprod_glev_mul_big_uint_poly_to_dev(pfhe_extprod_plan *plan, const ui
                                                const uint64_t *big_uint_poly_dev, size_t len_poly, uint64_t *result_dev,
                                                size_t len_result, void *stream) {
     PFHE_GUARD_BEGIN
-    return glev_big_uint_common(plan, result_dev, len_result, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, false,
-                                stream);
+    return glev_common(plan, (u64 *)result_dev, len_result, (const u64 *)dcrt_glev_dev, len_glev,
+                       (const u64 *)big_uint_poly_dev, len_poly, false, true, "acc/result", stream);
     PFHE_GUARD_END
 }
 
@@ -994,204 +979,29 @@ int pfhe_extprod_mul_dcrt_ggsw_to(pfhe_extprod_plan *plan, const uint64_t *crt_g
                                   const uint64_t *dcrt_ggsw, size_t len_ggsw, uint64_t *result, size_t len_result,
                                   int into_coeff_form) {
     PFHE_GUARD_BEGIN
-    PFHE_TRY(plan_check(plan));
-    PFHE_PLAN_LEASE(plan);
-    if ((!crt_glwe || !dcrt_ggsw || !result) && len_glwe) return PFHE_ERR_BAD_ARGUMENT;
-    DeviceGuard g(plan->table->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(plan->table->device);  // pooled staging context: no allocation in steady state
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *r = nullptr;
-    PFHE_TRY(st.upload(crt_glwe, len_glwe * 8, &a));
-    PFHE_TRY(st.upload(dcrt_ggsw, len_ggsw * 8, &k));
-    PFHE_TRY(st.alloc(len_result * 8, &r));
-    PFHE_TRY(pfhe_extprod_mul_dcrt_ggsw_to_dev(plan, (const uint64_t *)a, len_glwe, (const uint64_t *)k, len_ggsw,
-                                               (uint64_t *)r, len_result, into_coeff_form, st.stream()));
-    PFHE_TRY(st.download(result, r, len_result * 8));
-    return st.finish();
+    return mul_dcrt_ggsw_to(plan, (const u64 *)crt_glwe, len_glwe, (const u64 *)dcrt_ggsw, len_ggsw, (u64 *)result,
+                            len_result, into_coeff_form);
     PFHE_GUARD_END
 }
 
 /* ------------------------------ external product over U32DcrtTable ------------------------------ */
 
-}  // extern "C"
-
-namespace {
-
-// *coeff_passes (when the caller wants coefficient form): 1 = the inverse transform's block pass ran inside the fused
-// kernel (the caller runs the strided pass), 0 = none
-int run_product32(pfhe_extprod32_plan *p, const u32 *polys, u32 rows, const u32 *keys, bool keys_shared, u32 *result,
-                  u64 batch, bool accumulate, hipStream_t s, bool big_input, bool into_coeff = false,
-                  int *coeff_passes = nullptr) {
-    if (coeff_passes) *coeff_passes = 0;
-    const TableSet &t = *p->table;
-    const bool tracked = p->last_done != nullptr && !stream_is_capturing(s);
-    if (tracked && p->last_valid) PFHE_HIP(hipStreamWaitEvent(s, p->last_done, 0));
-    const u64 W = (u64)t.L * t.n;
-    RnsParams rns = p->rns;
-    rns.dev.big_input = rns.wide_tab.big_input = big_input ? 1u : 0u;
-    const u64 in_words = big_input ? (u64)rns.dev.value_words * t.n : W;
-    const u32 ell = p->basis.ell;
-    const u64 key_words = (u64)rows * ell * (p->k + 1) * W;
-    // the fused kernels launch one workgroup per (ciphertext, limb, block): they pay once that fills the chip
-    const bool fused = p->sdigits != nullptr && p->use_fused && extprod32_fused_supported(t.log_n, p->k) &&
-                       ((std::min<u64>(batch, p->chunk) * t.L) << (t.log_n - 12)) >= 160;
-    const bool inv_tail = fused && into_coeff && !accumulate && coeff_passes != nullptr;
-    if (inv_tail) *coeff_passes = 1;
-    int rc = PFHE_OK;
-    for (u64 done = 0; done < batch && rc == PFHE_OK; done += p->chunk) {
-        const u64 cur = std::min<u64>(p->chunk, batch - done);
-        const u32 *kp = keys + (keys_shared ? 0 : done * key_words);
-        u32 *rp = result + done * (p->k + 1) * W;
-        if (fused) {
-            rc = gadget_signed_digits_dev<u32>(rns, p->basis_par, t.log_n, polys + done * rows * in_words, p->sdigits, cur * rows, s);
-            if (rc == PFHE_OK) rc = digits_strided32_dev(t.primes_dev, t.L, t.log_n, ell, p->sdigits, p->digits, cur * rows, s);
-            if (rc == PFHE_OK)
-                rc = gadget_block_mulacc32_dev(t.primes_dev, t.L, t.log_n, rows * ell, p->digits, kp, keys_shared, rp, cur,
-                                               accumulate, inv_tail, s);
-            continue;
-        }
-        rc = gadget_decompose_dev<u32>(rns, p->basis_par, t.log_n, polys + done * rows * in_words, p->digits, cur * rows, s);
-        if (rc == PFHE_OK)
-            rc = ntt32_transform_dev(t.primes_dev, t.L, t.log_n, p->digits, cur * rows * ell * t.L, false, false, s, t.tune);
-        if (rc == PFHE_OK)
-            rc = gadget_mulacc32_dev(t.primes_dev, t.L, t.log_n, p->k, rows, ell, p->digits, kp, keys_shared, rp, cur, accumulate, s);
-    }
-    if (tracked) {  // also after a failed call: whatever it queued still uses the buffers
-        if (hipEventRecord(p->last_done, s) == hipSuccess) {
-            p->last_valid = true;
-        } else {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s);
-            p->last_valid = false;
-        }
-    }
-    return rc;
-}
-
-int plan32_check(const pfhe_extprod32_plan *p) { return (!p || !p->table) ? PFHE_ERR_BAD_ARGUMENT : PFHE_OK; }
-
-// one GLev row against `batch` polynomials (CRT residues or big integers), accumulating or overwriting
-int glev32_common(pfhe_extprod32_plan *plan, uint32_t *out_dev, size_t len_out, const uint32_t *dcrt_glev_dev, size_t len_glev,
-                  const uint32_t *poly_dev, size_t len_poly, bool accumulate, bool big_input, void *stream) {
-    PFHE_TRY(plan32_check(plan));
-    PFHE_PLAN_LEASE(plan);
-    const TableSet &t = *plan->table;
-    const size_t W = (size_t)t.L * t.n, glwe = (plan->k + 1) * W, glev = plan->basis.ell * glwe;
-    const size_t in_words = big_input ? (size_t)plan->rns.dev.value_words * t.n : W;
-    if (len_poly % in_words != 0) return PFHE_ERR_BAD_LENGTH;
-    const u64 batch = len_poly / in_words;
-    if (len_out != batch * glwe || (len_glev != glev && len_glev != batch * glev)) {
-        set_last_error("glev product: acc/result must be batch*(k+1)*L*N words and the GLev one or batch of ell*(k+1)*L*N");
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    if (batch == 0) return PFHE_OK;
-    if (!out_dev || !dcrt_glev_dev || !poly_dev) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(out_dev);
-    PFHE_REQUIRE_ALIGNED(dcrt_glev_dev);
-    PFHE_REQUIRE_ALIGNED(poly_dev);
-    DeviceGuard g(t.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return run_product32(plan, poly_dev, 1, dcrt_glev_dev, len_glev == glev, out_dev, batch, accumulate, (hipStream_t)stream,
-                         big_input);
-}
-
-}  // namespace
-
-extern "C" {
-
 int pfhe_extprod32_plan_create(const pfhe_dcrt32 *table, const pfhe_rns32 *rns, const pfhe_basis32 *basis,
                                size_t glwe_dimension, size_t chunk, pfhe_extprod32_plan **out) {
     PFHE_GUARD_BEGIN
-    if (!out || !table || !rns || !basis || glwe_dimension == 0 || glwe_dimension > 64) return PFHE_ERR_BAD_ARGUMENT;
-    *out = nullptr;
-    const TableSet *t = capi_table32_of(table);
-    if (t->L != rns->h.par.dev.L) {
-        set_last_error("DCRT table and RNS base have different moduli counts");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    for (u32 i = 0; i < t->L; ++i) {
-        if (t->primes[i].q != rns->h.moduli[i]) {
-            set_last_error("DCRT table and RNS base must use the same moduli in the same order");
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
-        if (basis->h.par.dev.basis >= t->primes[i].q) {  // wrapping_decompose needs B < q_i (base.rs:288-292)
-            set_last_error("gadget basis must be smaller than every RNS modulus");
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
-    }
-    if (basis->h.rns.dev.L != rns->h.par.dev.L || basis->h.Q != rns->h.Q) return PFHE_ERR_BAD_ARGUMENT;  // basis.rs:52
-    auto p = std::make_unique<pfhe_extprod32_plan>();
-    p->table = t;
-    p->rns = rns->h.par;
-    p->basis_par = basis->h.par;
-    p->basis = basis->h.par.dev;
-    p->k = (u32)glwe_dimension;
-    if (chunk == 0) {  // about 1 GiB of digit polynomials, at least 128 ciphertexts
-        const size_t per_ct = (size_t)(glwe_dimension + 1) * p->basis.ell * t->L * t->n * sizeof(u32);
-        chunk = std::max<size_t>(128, std::min<size_t>(65536, ((size_t)1 << 30) / per_ct));
-    }
-    p->chunk = chunk;
-    p->digits_words = p->chunk * (p->k + 1) * p->basis.ell * t->L * t->n;
-    DeviceGuard g(t->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    p->use_fused = std::getenv("PFHE_DISABLE_FUSED_EXTPROD") == nullptr;
-    void *d = nullptr;
-    PFHE_HIP(counted_malloc(&d, p->digits_words * sizeof(u32)));
-    p->digits = (u32 *)d;
-    if (p->use_fused && extprod32_fused_supported(t->log_n, p->k)) {
-        void *sd = nullptr;
-        PFHE_HIP(counted_malloc(&sd, p->chunk * (p->k + 1) * p->basis.ell * t->n * sizeof(int)));
-        p->sdigits = (int *)sd;
-    }
-    PFHE_HIP(hipEventCreateWithFlags(&p->last_done, hipEventDisableTiming));
-    *out = p.release();
-    return PFHE_OK;
+    return plan_create(table, rns, basis, glwe_dimension, chunk, out);
     PFHE_GUARD_END
 }
-
 void pfhe_extprod32_plan_destroy(pfhe_extprod32_plan *p) { delete p; }
-int pfhe_extprod32_plan_in_use(const pfhe_extprod32_plan *p) {
-    return p && p->owner.load(std::memory_order_acquire) != 0 ? 1 : 0;
-}
-size_t pfhe_extprod32_plan_scratch_bytes(const pfhe_extprod32_plan *p) {
-    if (!p) return 0;
-    return p->digits_words * sizeof(u32) + (p->sdigits ? p->chunk * (p->k + 1) * p->basis.ell * p->table->n * sizeof(int) : 0);
-}
+int pfhe_extprod32_plan_in_use(const pfhe_extprod32_plan *p) { return p ? p->guard.in_use() : 0; }
+size_t pfhe_extprod32_plan_scratch_bytes(const pfhe_extprod32_plan *p) { return plan_scratch_bytes(p); }
 
 int pfhe_extprod32_mul_dcrt_ggsw_to_dev(pfhe_extprod32_plan *plan, const uint32_t *crt_glwe_dev, size_t len_glwe,
                                         const uint32_t *dcrt_ggsw_dev, size_t len_ggsw, uint32_t *result_dev,
                                         size_t len_result, int into_coeff_form, void *stream) {
     PFHE_GUARD_BEGIN
-    PFHE_TRY(plan32_check(plan));
-    PFHE_PLAN_LEASE(plan);
-    const TableSet &t = *plan->table;
-    const size_t W = (size_t)t.L * t.n, glwe = (plan->k + 1) * W;
-    const size_t ggsw = (size_t)(plan->k + 1) * plan->basis.ell * glwe;
-    if (len_glwe % glwe != 0 || len_result != len_glwe || (len_ggsw != ggsw && len_ggsw != len_glwe / glwe * ggsw)) {
-        set_last_error("external product: glwe/result must be batch*(k+1)*L*N words and the GGSW one or batch "
-                       "ciphertexts of (k+1)*ell*(k+1)*L*N words");
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    const u64 batch = len_glwe / glwe;
-    if (batch == 0) return PFHE_OK;
-    if (!crt_glwe_dev || !dcrt_ggsw_dev || !result_dev) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(crt_glwe_dev);
-    PFHE_REQUIRE_ALIGNED(dcrt_ggsw_dev);
-    PFHE_REQUIRE_ALIGNED(result_dev);
-    DeviceGuard g(t.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    // result.set_zero() (glwe/crt.rs:217) is implied: the multiply-accumulate overwrites
-    int coeff_passes = 0;
-    PFHE_TRY(run_product32(plan, crt_glwe_dev, plan->k + 1, dcrt_ggsw_dev, len_ggsw == ggsw, result_dev, batch, false,
-                           (hipStream_t)stream, false, into_coeff_form != 0, &coeff_passes));
-    if (into_coeff_form && coeff_passes == 0)  // DcrtGlwe::into_coeff_form, macros/mod.rs:901-911
-        PFHE_TRY(ntt32_transform_dev(t.primes_dev, t.L, t.log_n, result_dev, batch * (plan->k + 1) * t.L, true, false,
-                                     (hipStream_t)stream, t.tune));
-    if (into_coeff_form && coeff_passes == 1)  // the block pass ran inside the fused kernel: the strided pass finishes
-        PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n - 1, kArithB32, reinterpret_cast<u64 *>(result_dev),
-                              batch * (plan->k + 1) * t.L, true, 1, false, (hipStream_t)stream, nullptr, 0, t.tune));
-    return PFHE_OK;
+    return mul_dcrt_ggsw_to_dev(plan, crt_glwe_dev, len_glwe, dcrt_ggsw_dev, len_ggsw, result_dev, len_result,
+                                into_coeff_form, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 
@@ -1199,21 +1009,7 @@ int pfhe_extprod32_mul_dcrt_ggsw_to(pfhe_extprod32_plan *plan, const uint32_t *c
                                     const uint32_t *dcrt_ggsw, size_t len_ggsw, uint32_t *result, size_t len_result,
                                     int into_coeff_form) {
     PFHE_GUARD_BEGIN
-    PFHE_TRY(plan32_check(plan));
-    PFHE_PLAN_LEASE(plan);
-    if ((!crt_glwe || !dcrt_ggsw || !result) && len_glwe) return PFHE_ERR_BAD_ARGUMENT;
-    DeviceGuard g(plan->table->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(plan->table->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *r = nullptr;
-    PFHE_TRY(st.upload(crt_glwe, len_glwe * sizeof(u32), &a));
-    PFHE_TRY(st.upload(dcrt_ggsw, len_ggsw * sizeof(u32), &k));
-    PFHE_TRY(st.alloc(len_result * sizeof(u32), &r));
-    PFHE_TRY(pfhe_extprod32_mul_dcrt_ggsw_to_dev(plan, (const uint32_t *)a, len_glwe, (const uint32_t *)k, len_ggsw,
-                                                 (uint32_t *)r, len_result, into_coeff_form, st.stream()));
-    PFHE_TRY(st.download(result, r, len_result * sizeof(u32)));
-    return st.finish();
+    return mul_dcrt_ggsw_to(plan, crt_glwe, len_glwe, dcrt_ggsw, len_ggsw, result, len_result, into_coeff_form);
     PFHE_GUARD_END
 }
 
@@ -1221,7 +1017,8 @@ int pfhe_extprod32_add_dcrt_glev_mul_crt_poly_assign_dev(pfhe_extprod32_plan *pl
                                                          const uint32_t *dcrt_glev_dev, size_t len_glev,
                                                          const uint32_t *crt_poly_dev, size_t len_poly, void *stream) {
     PFHE_GUARD_BEGIN
-    return glev32_common(plan, acc_dev, len_acc, dcrt_glev_dev, len_glev, crt_poly_dev, len_poly, true, false, stream);
+    return glev_common(plan, acc_dev, len_acc, dcrt_glev_dev, len_glev, crt_poly_dev, len_poly, true, false, "acc/result",
+                       stream);
     PFHE_GUARD_END
 }
 
@@ -1229,7 +1026,8 @@ int pfhe_extprod32_glev_mul_crt_poly_to_dev(pfhe_extprod32_plan *plan, const uin
                                             const uint32_t *crt_poly_dev, size_t len_poly, uint32_t *result_dev,
                                             size_t len_result, void *stream) {
     PFHE_GUARD_BEGIN
-    return glev32_common(plan, result_dev, len_result, dcrt_glev_dev, len_glev, crt_poly_dev, len_poly, false, false, stream);
+    return glev_common(plan, result_dev, len_result, dcrt_glev_dev, len_glev, crt_poly_dev, len_poly, false, false,
+                       "acc/result", stream);
     PFHE_GUARD_END
 }
 
@@ -1238,7 +1036,8 @@ int pfhe_extprod32_add_dcrt_glev_mul_big_uint_poly_assign_dev(pfhe_extprod32_pla
                                                               const uint32_t *big_uint_poly_dev, size_t len_poly,
                                                               void *stream) {
     PFHE_GUARD_BEGIN
-    return glev32_common(plan, acc_dev, len_acc, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, true, true, stream);
+    return glev_common(plan, acc_dev, len_acc, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, true, true,
+                       "acc/result", stream);
     PFHE_GUARD_END
 }
 
@@ -1246,8 +1045,8 @@ int pfhe_extprod32_glev_mul_big_uint_poly_to_dev(pfhe_extprod32_plan *plan, cons
                                                  const uint32_t *big_uint_poly_dev, size_t len_poly, uint32_t *result_dev,
                                                  size_t len_result, void *stream) {
     PFHE_GUARD_BEGIN
-    return glev32_common(plan, result_dev, len_result, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, false, true,
-                         stream);
+    return glev_common(plan, result_dev, len_result, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, false, true,
+                       "acc/result", stream);
     PFHE_GUARD_END
 }
 
@@ -1265,10 +1064,7 @@ int pfhe_extprod32_glev_mul_big_uint_poly_to_dev(pfhe_extprod32_plan *plan, cons
 template <class Plan, class W>
 struct BlindRotCore {
     Plan *plan = nullptr;  // owned
-    std::atomic<std::uintptr_t> owner{0};  // one holder at a time (PlanLease), as the plan
-    int depth = 0;
-    hipEvent_t last_done = nullptr;  // cross-stream ordering of successive calls, as run_product
-    bool last_valid = false;
+    PlanGuard guard;       // one holder at a time and cross-stream ordering of successive calls, as the plan
     W *d = nullptr, *e = nullptr, *ping = nullptr;  // chunk * glwe words each
     size_t glwe = 0, ggsw = 0;
     ~BlindRotCore() {
@@ -1277,7 +1073,6 @@ struct BlindRotCore {
             DeviceGuard g(plan->table->device);
             for (W *b : {d, e, ping})
                 if (b) (void)counted_free(b);
-            if (last_done) (void)hipEventDestroy(last_done);
         }
         delete plan;
     }
@@ -1287,8 +1082,12 @@ struct pfhe_blindrot32 : BlindRotCore<pfhe_extprod32_plan, u32> {};
 
 namespace {
 
-template <class H>
-int blindrot_finish_create(H *h) {
+template <class H, class Table, class Rns, class Basis>
+int blindrot_create(const Table *table, const Rns *base, const Basis *basis, size_t glwe_dimension, size_t chunk, H **out) {
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    auto h = std::make_unique<H>();
+    PFHE_TRY(plan_create(table, base, basis, glwe_dimension, chunk, &h->plan));
     const TableSet &t = *h->plan->table;
     h->glwe = (size_t)(h->plan->k + 1) * t.L * t.n;
     h->ggsw = (size_t)(h->plan->k + 1) * h->plan->basis.ell * h->glwe;
@@ -1300,20 +1099,17 @@ int blindrot_finish_create(H *h) {
         PFHE_HIP(counted_malloc(&p, h->plan->chunk * h->glwe * sizeof(W)));
         *b = (W *)p;
     }
-    PFHE_HIP(hipEventCreateWithFlags(&h->last_done, hipEventDisableTiming));
+    PFHE_TRY(h->guard.init(t.device));
+    *out = h.release();
     return PFHE_OK;
 }
-
-// the product of one step: E = coeff_form(D (x) BSK_i) for `cur` ciphertexts
-int blindrot_product(pfhe_blindrot *h, const u64 *d, const u64 *key, u64 *e, u64 cur, hipStream_t s) {
-    return pfhe_extprod_mul_dcrt_ggsw_to_dev(h->plan, (const uint64_t *)d, cur * h->glwe, (const uint64_t *)key, h->ggsw,
-                                             (uint64_t *)e, cur * h->glwe, 1, s);
-}
-int blindrot_product(pfhe_blindrot32 *h, const u32 *d, const u32 *key, u32 *e, u64 cur, hipStream_t s) {
-    return pfhe_extprod32_mul_dcrt_ggsw_to_dev(h->plan, d, cur * h->glwe, key, h->ggsw, e, cur * h->glwe, 1, s);
+template <class H>
+size_t blindrot_scratch_bytes(const H *h) {
+    if (!h || !h->plan) return 0;
+    return plan_scratch_bytes(h->plan) + 3 * h->plan->chunk * h->glwe * sizeof(*h->d);
 }
 
-// Fused small-ring step (u64 only): taken under exactly the condition run_product_impl takes extprod_small_kernel under.
+// Fused small-ring step (u64 only): taken under exactly the condition run_product takes extprod_small_kernel under.
 // Two launches per step, no D or E buffer: digits of X^r * ACC - ACC, then the product whose epilogue adds E to ACC.
 bool blindrot_small_fused(const pfhe_blindrot *h, u64 cur) {
     const pfhe_extprod_plan *p = h->plan;
@@ -1342,7 +1138,7 @@ template <class H, class W>
 int blindrot_rotate_dev(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
                         hipStream_t s) {
     if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h);
+    PFHE_PLAN_LEASE(h->guard, kPlanBusy);
     const TableSet &t = *h->plan->table;
     if (len_acc % h->glwe != 0 || len_bsk % h->ggsw != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->ggsw)) {
         set_last_error("blind rotation: acc must be batch*(k+1)*L*N words, bsk n_steps*(k+1)*ell*(k+1)*L*N and exps "
@@ -1356,49 +1152,41 @@ int blindrot_rotate_dev(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_b
     PFHE_REQUIRE_ALIGNED(bsk);
     DeviceGuard g(t.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const bool tracked = !stream_is_capturing(s);
-    if (tracked && h->last_valid) PFHE_HIP(hipStreamWaitEvent(s, h->last_done, 0));
     const u32 rows = h->plan->k + 1;
-    int rc = PFHE_OK;
-    // chunk after chunk; every step of a chunk runs before the next chunk starts
-    for (u64 done = 0; done < batch && rc == PFHE_OK; done += h->plan->chunk) {
-        const u64 cur = std::min<u64>(h->plan->chunk, batch - done);
-        W *a0 = acc + done * h->glwe;
-        const uint32_t *ex = exps + done * n_steps;
-        if (blindrot_small_fused(h, cur)) {
-            rc = blindrot_small_steps(h, a0, bsk, ex, n_steps, cur, s);
-            continue;
+    return ordered_on(h->guard, s, [&]() -> int {
+        int rc = PFHE_OK;
+        // chunk after chunk; every step of a chunk runs before the next chunk starts
+        for (u64 done = 0; done < batch && rc == PFHE_OK; done += h->plan->chunk) {
+            const u64 cur = std::min<u64>(h->plan->chunk, batch - done);
+            W *a0 = acc + done * h->glwe;
+            const uint32_t *ex = exps + done * n_steps;
+            if (blindrot_small_fused(h, cur)) {
+                rc = blindrot_small_steps(h, a0, bsk, ex, n_steps, cur, s);
+                continue;
+            }
+            // ping-pong between the caller's accumulator and the handle's: every step writes ACC' to the other one, so the
+            // gather of a rotated word never sees a word already updated; an odd step count starts in the handle's buffer
+            // so that the last step ends in the caller's
+            W *src = a0;
+            if (n_steps % 2) {
+                rc = blindrot_glue_dev<W>(t, BlindRotGlue::kFirstCopy, a0, nullptr, h->ping, h->d, ex, (u32)n_steps, rows, cur, s);
+                src = h->ping;
+            } else {
+                rc = blindrot_glue_dev<W>(t, BlindRotGlue::kFirst, a0, nullptr, nullptr, h->d, ex, (u32)n_steps, rows, cur, s);
+            }
+            for (u64 i = 0; i < n_steps && rc == PFHE_OK; ++i) {
+                // the product of one step: E = coeff_form(D (x) BSK_i) for `cur` ciphertexts
+                rc = mul_dcrt_ggsw_to_dev(h->plan, h->d, cur * h->glwe, bsk + i * h->ggsw, h->ggsw, h->e, cur * h->glwe, 1, s);
+                if (rc != PFHE_OK) break;
+                W *dst = src == a0 ? h->ping : a0;
+                rc = i + 1 < n_steps
+                         ? blindrot_glue_dev<W>(t, BlindRotGlue::kStep, src, h->e, dst, h->d, ex + i + 1, (u32)n_steps, rows, cur, s)
+                         : blindrot_glue_dev<W>(t, BlindRotGlue::kLast, src, h->e, dst, nullptr, ex, (u32)n_steps, rows, cur, s);
+                src = dst;
+            }
         }
-        // ping-pong between the caller's accumulator and the handle's: every step writes ACC' to the other one, so the
-        // gather of a rotated word never sees a word already updated; an odd step count starts in the handle's buffer
-        // so that the last step ends in the caller's
-        W *src = a0;
-        if (n_steps % 2) {
-            rc = blindrot_glue_dev<W>(t, BlindRotGlue::kFirstCopy, a0, nullptr, h->ping, h->d, ex, (u32)n_steps, rows, cur, s);
-            src = h->ping;
-        } else {
-            rc = blindrot_glue_dev<W>(t, BlindRotGlue::kFirst, a0, nullptr, nullptr, h->d, ex, (u32)n_steps, rows, cur, s);
-        }
-        for (u64 i = 0; i < n_steps && rc == PFHE_OK; ++i) {
-            rc = blindrot_product(h, h->d, bsk + i * h->ggsw, h->e, cur, s);
-            if (rc != PFHE_OK) break;
-            W *dst = src == a0 ? h->ping : a0;
-            rc = i + 1 < n_steps
-                     ? blindrot_glue_dev<W>(t, BlindRotGlue::kStep, src, h->e, dst, h->d, ex + i + 1, (u32)n_steps, rows, cur, s)
-                     : blindrot_glue_dev<W>(t, BlindRotGlue::kLast, src, h->e, dst, nullptr, ex, (u32)n_steps, rows, cur, s);
-            src = dst;
-        }
-    }
-    if (tracked) {  // also after a failed call: whatever it queued still uses the buffers
-        if (hipEventRecord(h->last_done, s) == hipSuccess) {
-            h->last_valid = true;
-        } else {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s);
-            h->last_valid = false;
-        }
-    }
-    return rc;
+        return rc;
+    });
 }
 
 // host form: every exponent must be below 2N (the reference's debug_assert!(r < 2N)); staged through the pooled context
@@ -1406,7 +1194,7 @@ template <class H, class W, class DevFn>
 int blindrot_rotate_host(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
                          DevFn dev) {
     if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h);
+    PFHE_PLAN_LEASE(h->guard, kPlanBusy);
     if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
     const size_t two_n = 2 * h->plan->table->n;
     for (size_t i = 0; i < len_exps; ++i) {
@@ -1441,21 +1229,12 @@ extern "C" {
 int pfhe_blindrot_create(const pfhe_dcrt *table, const pfhe_rns *base, const pfhe_basis *basis, size_t glwe_dimension,
                          size_t chunk, pfhe_blindrot **out) {
     PFHE_GUARD_BEGIN
-    if (!out) return PFHE_ERR_BAD_ARGUMENT;
-    *out = nullptr;
-    auto h = std::make_unique<pfhe_blindrot>();
-    PFHE_TRY(pfhe_extprod_plan_create(table, base, basis, glwe_dimension, chunk, &h->plan));
-    PFHE_TRY(blindrot_finish_create(h.get()));
-    *out = h.release();
-    return PFHE_OK;
+    return blindrot_create(table, base, basis, glwe_dimension, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_blindrot_destroy(pfhe_blindrot *h) { delete h; }
-int pfhe_blindrot_in_use(const pfhe_blindrot *h) { return h && h->owner.load(std::memory_order_acquire) != 0 ? 1 : 0; }
-size_t pfhe_blindrot_scratch_bytes(const pfhe_blindrot *h) {
-    if (!h || !h->plan) return 0;
-    return pfhe_extprod_plan_scratch_bytes(h->plan) + 3 * h->plan->chunk * h->glwe * sizeof(u64);
-}
+int pfhe_blindrot_in_use(const pfhe_blindrot *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_blindrot_scratch_bytes(const pfhe_blindrot *h) { return blindrot_scratch_bytes(h); }
 int pfhe_blindrot_rotate_dev(pfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const uint64_t *bsk_dev, size_t len_bsk,
                              const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
@@ -1474,21 +1253,12 @@ int pfhe_blindrot_rotate(pfhe_blindrot *h, uint64_t *acc, size_t len_acc, const 
 int pfhe_blindrot32_create(const pfhe_dcrt32 *table, const pfhe_rns32 *base, const pfhe_basis32 *basis,
                            size_t glwe_dimension, size_t chunk, pfhe_blindrot32 **out) {
     PFHE_GUARD_BEGIN
-    if (!out) return PFHE_ERR_BAD_ARGUMENT;
-    *out = nullptr;
-    auto h = std::make_unique<pfhe_blindrot32>();
-    PFHE_TRY(pfhe_extprod32_plan_create(table, base, basis, glwe_dimension, chunk, &h->plan));
-    PFHE_TRY(blindrot_finish_create(h.get()));
-    *out = h.release();
-    return PFHE_OK;
+    return blindrot_create(table, base, basis, glwe_dimension, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_blindrot32_destroy(pfhe_blindrot32 *h) { delete h; }
-int pfhe_blindrot32_in_use(const pfhe_blindrot32 *h) { return h && h->owner.load(std::memory_order_acquire) != 0 ? 1 : 0; }
-size_t pfhe_blindrot32_scratch_bytes(const pfhe_blindrot32 *h) {
-    if (!h || !h->plan) return 0;
-    return pfhe_extprod32_plan_scratch_bytes(h->plan) + 3 * h->plan->chunk * h->glwe * sizeof(u32);
-}
+int pfhe_blindrot32_in_use(const pfhe_blindrot32 *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_blindrot32_scratch_bytes(const pfhe_blindrot32 *h) { return blindrot_scratch_bytes(h); }
 int pfhe_blindrot32_rotate_dev(pfhe_blindrot32 *h, uint32_t *acc_dev, size_t len_acc, const uint32_t *bsk_dev,
                                size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN

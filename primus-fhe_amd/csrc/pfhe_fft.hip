@@ -23,7 +23,6 @@
 //            inverse over plan-owned scratch.
 // Summation order is fixed (rows, then levels); no atomics: results do not depend on batch size or chunking.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -31,6 +30,7 @@
 #include <vector>
 
 #include "pfhe_capi_internal.hpp"
+#include "pfhe_plan_guard.hpp"
 #include "pfhe_staging.hpp"
 
 using namespace pfhe;
@@ -50,11 +50,8 @@ struct pfhe_fft {
 // TfheFftContext<T> + ApproxSignedBasis<T> (power-of-two modulus): the shape of the product and its device scratch.
 template <class W>
 struct TfhePlanCore {
-    const pfhe_fft *fft = nullptr;         // borrowed (must outlive the plan)
-    std::atomic<std::uintptr_t> owner{0};  // one holder at a time, as pfhe_extprod_plan (&mut TfheFftContext)
-    int depth = 0;
-    hipEvent_t last_done = nullptr;  // cross-stream ordering of successive calls
-    bool last_valid = false;
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the plan)
+    PlanGuard guard;                // one holder at a time (&mut TfheFftContext), successive calls ordered across streams
     u32 k = 1, log_basis = 0, ell = 0, drop_bits = 0;
     size_t chunk = 1;
     bool fused = false;
@@ -67,7 +64,6 @@ struct TfhePlanCore {
         DeviceGuard g(fft->device);
         for (double2 *b : {spec, acc, keyh})
             if (b) (void)counted_free(b);
-        if (last_done) (void)hipEventDestroy(last_done);
     }
 };
 struct pfhe_tfhe_plan : TfhePlanCore<u64> {};
@@ -449,41 +445,7 @@ int host_form(const pfhe_fft *f, const In *in, size_t in_bytes, Out *out, size_t
 
 // ---------------- plans ----------------
 
-inline std::uintptr_t thread_token() {
-    static thread_local char token;
-    return reinterpret_cast<std::uintptr_t>(&token);
-}
-template <class P>
-class Lease {
-  public:
-    explicit Lease(P *p) : p_(p) {
-        const std::uintptr_t me = thread_token();
-        std::uintptr_t free_ = 0;
-        if (p->owner.load(std::memory_order_relaxed) == me) {
-            ++p->depth;
-            held_ = true;
-        } else if (p->owner.compare_exchange_strong(free_, me, std::memory_order_acquire)) {
-            p->depth = 1;
-            held_ = true;
-        }
-    }
-    ~Lease() {
-        if (held_ && --p_->depth == 0) p_->owner.store(0, std::memory_order_release);
-    }
-    Lease(const Lease &) = delete;
-    Lease &operator=(const Lease &) = delete;
-    bool held() const { return held_; }
-
-  private:
-    P *p_;
-    bool held_ = false;
-};
-#define PFHE_TFHE_LEASE(plan)                                                                               \
-    Lease<typename std::remove_pointer<decltype(plan)>::type> lease_(plan);                                 \
-    if (!lease_.held()) {                                                                                   \
-        set_last_error("TFHE product plan in use by another thread (one plan per thread, like &mut TfheFftContext)"); \
-        return PFHE_ERR_BUSY;                                                                               \
-    }
+constexpr const char *kPlanBusy = "TFHE product plan in use by another thread (one plan per thread, like &mut TfheFftContext)";
 
 // ApproxSignedBasis::new (basis.rs:47-177) with modulus None: its assert!s become PFHE_ERR_BAD_ARGUMENT (log_basis = BITS
 // overflows the basis there too); decompose_length 0 = the full length BITS / log_basis
@@ -542,7 +504,7 @@ int plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, 
             p->scratch += sizes[i] * sizeof(double2);
         }
     }
-    PFHE_HIP(hipEventCreateWithFlags(&p->last_done, hipEventDisableTiming));
+    PFHE_TRY(p->guard.init(fft->device));
     *out = p.release();
     return PFHE_OK;
 }
@@ -586,7 +548,7 @@ template <class W, class P>
 int product_dev(P *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out,
                 hipStream_t s) {
     if (!p || !p->fft) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_TFHE_LEASE(p);
+    PFHE_PLAN_LEASE(p->guard, kPlanBusy);
     const pfhe_fft &f = *p->fft;
     const size_t rows = p->k + 1, glwe = rows * f.n, key_len = rows * p->ell * rows * f.n;
     if (len_in % glwe != 0 || len_out != len_in || len_key != key_len) {
@@ -609,25 +571,13 @@ int product_dev(P *p, const W *in, size_t len_in, const double *key, size_t len_
     }
     DeviceGuard g(f.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const bool tracked = !stream_is_capturing(s);
-    if (tracked && p->last_valid) PFHE_HIP(hipStreamWaitEvent(s, p->last_done, 0));
-    const int rc = product_impl<W>(p, in, (const double2 *)key, out, batch, s);
-    if (tracked) {  // also after a failed call: whatever it queued still uses the scratch
-        if (hipEventRecord(p->last_done, s) == hipSuccess) {
-            p->last_valid = true;
-        } else {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(s);
-            p->last_valid = false;
-        }
-    }
-    return rc;
+    return ordered_on(p->guard, s, [&] { return product_impl<W>(p, in, (const double2 *)key, out, batch, s); });
 }
 
 template <class W, class P>
 int product_host(P *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out) {
     if (!p || !p->fft) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_TFHE_LEASE(p);
+    PFHE_PLAN_LEASE(p->guard, kPlanBusy);
     if ((!in && len_in) || (!key && len_key) || (!out && len_out)) return PFHE_ERR_BAD_ARGUMENT;
     const pfhe_fft &f = *p->fft;
     const size_t rows = p->k + 1, glwe = rows * f.n, key_len = rows * p->ell * rows * f.n;
@@ -755,7 +705,7 @@ int pfhe_tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t l
 }
 void pfhe_tfhe_plan_destroy(pfhe_tfhe_plan *plan) { delete plan; }
 int pfhe_tfhe_plan_in_use(const pfhe_tfhe_plan *plan) {
-    return plan && plan->owner.load(std::memory_order_acquire) != 0 ? 1 : 0;
+    return plan ? plan->guard.in_use() : 0;
 }
 size_t pfhe_tfhe_plan_scratch_bytes(const pfhe_tfhe_plan *plan) { return plan ? plan->scratch : 0; }
 int pfhe_tfhe_external_product_to_dev(pfhe_tfhe_plan *plan, const uint64_t *input_dev, size_t len_input,
@@ -781,7 +731,7 @@ int pfhe_tfhe32_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t
 }
 void pfhe_tfhe32_plan_destroy(pfhe_tfhe32_plan *plan) { delete plan; }
 int pfhe_tfhe32_plan_in_use(const pfhe_tfhe32_plan *plan) {
-    return plan && plan->owner.load(std::memory_order_acquire) != 0 ? 1 : 0;
+    return plan ? plan->guard.in_use() : 0;
 }
 size_t pfhe_tfhe32_plan_scratch_bytes(const pfhe_tfhe32_plan *plan) { return plan ? plan->scratch : 0; }
 int pfhe_tfhe32_external_product_to_dev(pfhe_tfhe32_plan *plan, const uint32_t *input_dev, size_t len_input,
