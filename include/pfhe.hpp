@@ -41,88 +41,106 @@ inline void check(int status) {
     }
 }
 
-class U64NttTable {
+namespace detail {
+
+// The C functions of one table handle, by name: PRE is the symbol prefix of the handle type H over the word type W.
+#define PFHE_TABLE_TRAITS(NAME, PRE, H, W)                                                   \
+    struct NAME {                                                                            \
+        using Handle = H;                                                                    \
+        using Word = W;                                                                      \
+        static constexpr auto destroy = PRE##destroy;                                        \
+        static constexpr auto poly_length = PRE##poly_length;                                \
+        static constexpr auto transform_slice = PRE##transform_slice;                        \
+        static constexpr auto inverse_transform_slice = PRE##inverse_transform_slice;        \
+        static constexpr auto lazy_transform_slice = PRE##lazy_transform_slice;              \
+        static constexpr auto lazy_inverse_transform_slice = PRE##lazy_inverse_transform_slice; \
+        static constexpr auto transform_monomial = PRE##transform_monomial;                  \
+        static constexpr auto transform_coeff_one_monomial = PRE##transform_coeff_one_monomial; \
+        static constexpr auto transform_coeff_minus_one_monomial = PRE##transform_coeff_minus_one_monomial; \
+        static constexpr auto transform_dev = PRE##transform_dev;                            \
+        static constexpr auto inverse_transform_dev = PRE##inverse_transform_dev;            \
+        static constexpr auto mul_assign_dev = PRE##mul_assign_dev;                          \
+        static constexpr auto add_mul_assign_dev = PRE##add_mul_assign_dev;                  \
+    }
+PFHE_TABLE_TRAITS(NttFns, pfhe_ntt_, pfhe_ntt, uint64_t);
+PFHE_TABLE_TRAITS(DcrtFns, pfhe_dcrt_, pfhe_dcrt, uint64_t);
+PFHE_TABLE_TRAITS(Ntt32Fns, pfhe_ntt32_, pfhe_ntt32, uint32_t);
+PFHE_TABLE_TRAITS(Dcrt32Fns, pfhe_dcrt32_, pfhe_dcrt32, uint32_t);
+#undef PFHE_TABLE_TRAITS
+
+// What the four tables share: ownership of the handle (move only), the host slices, the monomial shortcuts and the
+// device-resident forms.  F names the C functions.
+template <class F>
+class Table {
+  public:
+    using H = typename F::Handle;
+    using W = typename F::Word;
+    ~Table() { F::destroy(h_); }
+    Table(Table &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    Table(const Table &) = delete;
+    Table &operator=(const Table &) = delete;
+
+    size_t poly_length() const { return F::poly_length(h_); }
+    void transform_slice(W *poly, size_t len) const { check(F::transform_slice(h_, poly, len)); }
+    void inverse_transform_slice(W *v, size_t len) const { check(F::inverse_transform_slice(h_, v, len)); }
+    void lazy_transform_slice(W *poly, size_t len) const { check(F::lazy_transform_slice(h_, poly, len)); }
+    void lazy_inverse_transform_slice(W *v, size_t len) const { check(F::lazy_inverse_transform_slice(h_, v, len)); }
+    void transform_monomial(W coeff, size_t degree, W *values, size_t len) const {
+        check(F::transform_monomial(h_, coeff, degree, values, len));
+    }
+    void transform_coeff_one_monomial(size_t degree, W *values, size_t len) const {
+        check(F::transform_coeff_one_monomial(h_, degree, values, len));
+    }
+    void transform_coeff_minus_one_monomial(size_t degree, W *values, size_t len) const {
+        check(F::transform_coeff_minus_one_monomial(h_, degree, values, len));
+    }
+    // device-resident batches (asynchronous on `stream`)
+    void transform_dev(W *poly_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
+        check(F::transform_dev(h_, poly_dev, len, lazy, stream));
+    }
+    void inverse_transform_dev(W *v_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
+        check(F::inverse_transform_dev(h_, v_dev, len, lazy, stream));
+    }
+    // NttPolynomial / DcrtPolynomial::mul_assign, add_mul_assign (crates/primus_poly/src/dcrt/mul.rs:176, mod.rs:105)
+    void mul_assign_dev(W *a, size_t len_a, const W *b, size_t len_b, void *stream = nullptr) const {
+        check(F::mul_assign_dev(h_, a, len_a, b, len_b, stream));
+    }
+    void add_mul_assign_dev(W *acc, const W *a, size_t len_a, const W *b, size_t len_b, void *stream = nullptr) const {
+        check(F::add_mul_assign_dev(h_, acc, a, len_a, b, len_b, stream));
+    }
+    const H *handle() const { return h_; }
+
+  protected:
+    Table() = default;
+    H *h_ = nullptr;
+};
+
+}  // namespace detail
+
+class U64NttTable : public detail::Table<detail::NttFns> {
   public:
     U64NttTable(uint32_t log_n, uint64_t modulus, int device = 0) { check(pfhe_ntt_create(log_n, modulus, device, &h_)); }
-    ~U64NttTable() { pfhe_ntt_destroy(h_); }
-    U64NttTable(U64NttTable &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
-    U64NttTable(const U64NttTable &) = delete;
-    U64NttTable &operator=(const U64NttTable &) = delete;
-
-    size_t poly_length() const { return pfhe_ntt_poly_length(h_); }
     size_t n() const { return poly_length(); }
     uint32_t log_n() const { return pfhe_ntt_log_n(h_); }
     uint64_t modulus() const { return pfhe_ntt_modulus(h_); }
     uint64_t root() const { return pfhe_ntt_root(h_); }
     uint64_t inv_root() const { return pfhe_ntt_inv_root(h_); }
     uint64_t inv_n() const { return pfhe_ntt_inv_n(h_); }
-
-    void transform_slice(uint64_t *poly, size_t len) const { check(pfhe_ntt_transform_slice(h_, poly, len)); }
-    void inverse_transform_slice(uint64_t *v, size_t len) const { check(pfhe_ntt_inverse_transform_slice(h_, v, len)); }
-    void lazy_transform_slice(uint64_t *poly, size_t len) const { check(pfhe_ntt_lazy_transform_slice(h_, poly, len)); }
-    void lazy_inverse_transform_slice(uint64_t *v, size_t len) const { check(pfhe_ntt_lazy_inverse_transform_slice(h_, v, len)); }
-    void transform_monomial(uint64_t coeff, size_t degree, uint64_t *values, size_t len) const {
-        check(pfhe_ntt_transform_monomial(h_, coeff, degree, values, len));
-    }
-    void transform_coeff_one_monomial(size_t degree, uint64_t *values, size_t len) const {
-        check(pfhe_ntt_transform_coeff_one_monomial(h_, degree, values, len));
-    }
-    void transform_coeff_minus_one_monomial(size_t degree, uint64_t *values, size_t len) const {
-        check(pfhe_ntt_transform_coeff_minus_one_monomial(h_, degree, values, len));
-    }
-    // device-resident batches (asynchronous on `stream`)
-    void transform_dev(uint64_t *poly_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_ntt_transform_dev(h_, poly_dev, len, lazy, stream));
-    }
-    void inverse_transform_dev(uint64_t *v_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_ntt_inverse_transform_dev(h_, v_dev, len, lazy, stream));
-    }
-    const pfhe_ntt *handle() const { return h_; }
-
-  private:
-    pfhe_ntt *h_ = nullptr;
 };
 
-class U64DcrtTable {
+class U64DcrtTable : public detail::Table<detail::DcrtFns> {
   public:
     U64DcrtTable(uint32_t log_n, const std::vector<uint64_t> &moduli, int device = 0) {
         check(pfhe_dcrt_create(log_n, moduli.data(), moduli.size(), device, &h_));
     }
-    ~U64DcrtTable() { pfhe_dcrt_destroy(h_); }
-    U64DcrtTable(U64DcrtTable &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
-    U64DcrtTable(const U64DcrtTable &) = delete;
-    U64DcrtTable &operator=(const U64DcrtTable &) = delete;
-
-    size_t poly_length() const { return pfhe_dcrt_poly_length(h_); }
     size_t moduli_count() const { return pfhe_dcrt_moduli_count(h_); }
     size_t crt_poly_length() const { return pfhe_dcrt_crt_poly_length(h_); }
     uint64_t modulus(size_t i) const { return pfhe_dcrt_modulus(h_, i); }
 
-    void transform_slice(uint64_t *poly, size_t len) const { check(pfhe_dcrt_transform_slice(h_, poly, len)); }
-    void inverse_transform_slice(uint64_t *poly, size_t len) const { check(pfhe_dcrt_inverse_transform_slice(h_, poly, len)); }
-    void lazy_transform_slice(uint64_t *poly, size_t len) const { check(pfhe_dcrt_lazy_transform_slice(h_, poly, len)); }
-    void lazy_inverse_transform_slice(uint64_t *poly, size_t len) const { check(pfhe_dcrt_lazy_inverse_transform_slice(h_, poly, len)); }
-    void transform_monomial(uint64_t coeff, size_t degree, uint64_t *values, size_t len) const {
-        check(pfhe_dcrt_transform_monomial(h_, coeff, degree, values, len));
-    }
     // device-pointer form (launches on `stream` only: capturable); minus_one selects -X^degree
     void transform_monomial_dev(uint64_t coeff, size_t degree, uint64_t *values_dev, size_t len, bool minus_one = false,
                                 void *stream = nullptr) const {
         check(pfhe_dcrt_transform_monomial_dev(h_, coeff, degree, values_dev, len, minus_one ? 1 : 0, stream));
-    }
-    void transform_dev(uint64_t *poly_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_dcrt_transform_dev(h_, poly_dev, len, lazy, stream));
-    }
-    void inverse_transform_dev(uint64_t *poly_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_dcrt_inverse_transform_dev(h_, poly_dev, len, lazy, stream));
-    }
-    // DcrtPolynomial::mul_assign / add_mul_assign (crates/primus_poly/src/dcrt/mul.rs:176, mod.rs:105)
-    void mul_assign_dev(uint64_t *a, size_t len_a, const uint64_t *b, size_t len_b, void *stream = nullptr) const {
-        check(pfhe_dcrt_mul_assign_dev(h_, a, len_a, b, len_b, stream));
-    }
-    void add_mul_assign_dev(uint64_t *acc, const uint64_t *a, size_t len_a, const uint64_t *b, size_t len_b,
-                            void *stream = nullptr) const {
-        check(pfhe_dcrt_add_mul_assign_dev(h_, acc, a, len_a, b, len_b, stream));
     }
     // CrtRlwe::mul_dcrt_polynomial_to + into_coeff_form (crates/primus_lattice/src/rlwe/crt.rs:42-65)
     void mul_dcrt_polynomial_dev(uint64_t *crt_poly, size_t len, const uint64_t *dcrt_poly, size_t len_b,
@@ -171,97 +189,34 @@ class U64DcrtTable {
     void inv_to_dev(const uint64_t *a, uint64_t *out, size_t len, void *stream = nullptr) const {
         check(pfhe_dcrt_inv_to_dev(h_, a, out, len, stream));
     }
-    const pfhe_dcrt *handle() const { return h_; }
 
   private:
     static void require_count(size_t got, size_t want) {
         if (got != want) throw Error(PFHE_ERR_BAD_LENGTH, "expected one entry per modulus");
     }
-    pfhe_dcrt *h_ = nullptr;
 };
 
 // primus_ntt::U32NttTable (crates/primus_ntt/src/ntt/prime32/table.rs:37) — q < 2^30, u32 data
-class U32NttTable {
+class U32NttTable : public detail::Table<detail::Ntt32Fns> {
   public:
     U32NttTable(uint32_t log_n, uint32_t modulus, int device = 0) { check(pfhe_ntt32_create(log_n, modulus, device, &h_)); }
-    ~U32NttTable() { pfhe_ntt32_destroy(h_); }
-    U32NttTable(U32NttTable &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
-    U32NttTable(const U32NttTable &) = delete;
-    U32NttTable &operator=(const U32NttTable &) = delete;
-
-    size_t poly_length() const { return pfhe_ntt32_poly_length(h_); }
     size_t n() const { return poly_length(); }
     uint32_t log_n() const { return pfhe_ntt32_log_n(h_); }
     uint32_t modulus() const { return pfhe_ntt32_modulus(h_); }
     uint32_t root() const { return pfhe_ntt32_root(h_); }
     uint32_t inv_root() const { return pfhe_ntt32_inv_root(h_); }
     uint32_t inv_n() const { return pfhe_ntt32_inv_n(h_); }
-
-    void transform_slice(uint32_t *poly, size_t len) const { check(pfhe_ntt32_transform_slice(h_, poly, len)); }
-    void inverse_transform_slice(uint32_t *v, size_t len) const { check(pfhe_ntt32_inverse_transform_slice(h_, v, len)); }
-    void lazy_transform_slice(uint32_t *poly, size_t len) const { check(pfhe_ntt32_lazy_transform_slice(h_, poly, len)); }
-    void lazy_inverse_transform_slice(uint32_t *v, size_t len) const { check(pfhe_ntt32_lazy_inverse_transform_slice(h_, v, len)); }
-    void transform_monomial(uint32_t coeff, size_t degree, uint32_t *values, size_t len) const {
-        check(pfhe_ntt32_transform_monomial(h_, coeff, degree, values, len));
-    }
-    void transform_coeff_one_monomial(size_t degree, uint32_t *values, size_t len) const {
-        check(pfhe_ntt32_transform_coeff_one_monomial(h_, degree, values, len));
-    }
-    void transform_coeff_minus_one_monomial(size_t degree, uint32_t *values, size_t len) const {
-        check(pfhe_ntt32_transform_coeff_minus_one_monomial(h_, degree, values, len));
-    }
-    void transform_dev(uint32_t *poly_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_ntt32_transform_dev(h_, poly_dev, len, lazy, stream));
-    }
-    void inverse_transform_dev(uint32_t *v_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_ntt32_inverse_transform_dev(h_, v_dev, len, lazy, stream));
-    }
-    const pfhe_ntt32 *handle() const { return h_; }
-
-  private:
-    pfhe_ntt32 *h_ = nullptr;
 };
 
 // primus_ntt::U32DcrtTable (crates/primus_ntt/src/dcrt/prime32.rs:11)
-class U32DcrtTable {
+class U32DcrtTable : public detail::Table<detail::Dcrt32Fns> {
   public:
     U32DcrtTable(uint32_t log_n, const std::vector<uint32_t> &moduli, int device = 0) {
         check(pfhe_dcrt32_create(log_n, moduli.data(), moduli.size(), device, &h_));
     }
-    ~U32DcrtTable() { pfhe_dcrt32_destroy(h_); }
-    U32DcrtTable(U32DcrtTable &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
-    U32DcrtTable(const U32DcrtTable &) = delete;
-    U32DcrtTable &operator=(const U32DcrtTable &) = delete;
-
-    size_t poly_length() const { return pfhe_dcrt32_poly_length(h_); }
     size_t moduli_count() const { return pfhe_dcrt32_moduli_count(h_); }
     size_t crt_poly_length() const { return pfhe_dcrt32_crt_poly_length(h_); }
     uint32_t modulus(size_t i) const { return pfhe_dcrt32_modulus(h_, i); }
-
-    void transform_slice(uint32_t *poly, size_t len) const { check(pfhe_dcrt32_transform_slice(h_, poly, len)); }
-    void inverse_transform_slice(uint32_t *poly, size_t len) const { check(pfhe_dcrt32_inverse_transform_slice(h_, poly, len)); }
-    void lazy_transform_slice(uint32_t *poly, size_t len) const { check(pfhe_dcrt32_lazy_transform_slice(h_, poly, len)); }
-    void lazy_inverse_transform_slice(uint32_t *poly, size_t len) const { check(pfhe_dcrt32_lazy_inverse_transform_slice(h_, poly, len)); }
-    void transform_monomial(uint32_t coeff, size_t degree, uint32_t *values, size_t len) const {
-        check(pfhe_dcrt32_transform_monomial(h_, coeff, degree, values, len));
-    }
-    void transform_dev(uint32_t *poly_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_dcrt32_transform_dev(h_, poly_dev, len, lazy, stream));
-    }
-    void inverse_transform_dev(uint32_t *poly_dev, size_t len, bool lazy = false, void *stream = nullptr) const {
-        check(pfhe_dcrt32_inverse_transform_dev(h_, poly_dev, len, lazy, stream));
-    }
-    void mul_assign_dev(uint32_t *a, size_t len_a, const uint32_t *b, size_t len_b, void *stream = nullptr) const {
-        check(pfhe_dcrt32_mul_assign_dev(h_, a, len_a, b, len_b, stream));
-    }
-    void add_mul_assign_dev(uint32_t *acc, const uint32_t *a, size_t len_a, const uint32_t *b, size_t len_b,
-                            void *stream = nullptr) const {
-        check(pfhe_dcrt32_add_mul_assign_dev(h_, acc, a, len_a, b, len_b, stream));
-    }
-    const pfhe_dcrt32 *handle() const { return h_; }
-
-  private:
-    pfhe_dcrt32 *h_ = nullptr;
 };
 
 class RNSBase {

@@ -17,10 +17,16 @@
         return PFHE_ERR_HIP;                             \
     }
 
-struct pfhe_dcrt;
-struct pfhe_dcrt32;
+// The four table handles of pfhe.h: one base, four names.
+struct pfhe_ntt : pfhe::TableHandle {};
+struct pfhe_dcrt : pfhe::TableHandle {};
+struct pfhe_ntt32 : pfhe::TableHandle {};
+struct pfhe_dcrt32 : pfhe::TableHandle {};
+
 namespace pfhe {
 int capi_check_device(int device);
-const TableSet *capi_table_of(const pfhe_dcrt *t);
-const TableSet *capi_table32_of(const pfhe_dcrt32 *t);
+inline const TableSet *capi_table_of(const pfhe_dcrt *t) { return t->t.get(); }
+inline const TableSet *capi_table32_of(const pfhe_dcrt32 *t) { return t->t.get(); }
+// *_transform_pass_name: "u32:" in front of the longest name ntt_pass_name writes
+constexpr size_t kPassNameCap = 4 + 96;
 }  // namespace pfhe

@@ -1,6 +1,7 @@
 // pfhe_staging.cpp — per-device pool of staging contexts for the host-pointer entry points (pfhe_staging.hpp).
 #include <sys/mman.h>
 #include "pfhe_staging.hpp"
+#include "pfhe_handles.hpp"
 
 #include <atomic>
 #include <cerrno>
@@ -567,5 +568,173 @@ int staging_release(int device) {
     for (StageCtx *c : victims) destroy_ctx(c);
     return (int)victims.size();
 }
+
+// Host-pointer form of the transforms (table.rs:541-563 takes `&mut [T]` in place): the slice is staged through a
+// pooled context (pfhe_staging.hpp: no allocation in steady state).  Polynomials are independent, so a long slice in
+// memory the CALLER pinned is cut into pieces of whole units and pipelined over the context's two streams: one carries the
+// copies in, the other waits for each piece, transforms it and copies it back — the copy back of piece i overlaps the
+// copy in of piece i + 1 (the link is full duplex); pageable copies block the calling thread and go as one piece.
+template <class W>
+int transform_host(const TableSet &t, W *host, size_t len, bool inverse, bool lazy) {
+    if (!host && len) return PFHE_ERR_BAD_ARGUMENT;
+    u64 units = 0;
+    PFHE_TRY(check_len(t, len, units));
+    if (len == 0) return PFHE_OK;
+    DeviceGuard g(t.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(t.device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *dv = nullptr;
+    PFHE_TRY(st.alloc(len * sizeof(W), &dv));
+    W *d = static_cast<W *>(dv);
+    const size_t unit = t.n * t.L;
+    const StageKnobs &K = stage_knobs();
+    // The mapped / bounce path and the helper-thread path below exist for the u64 tables only: a u32 slice goes straight to
+    // the piece loop at the end (pfhe_debug_stage_path_count stays 0 for it).
+    constexpr bool kFastPaths = sizeof(W) == sizeof(u64);
+    // A slice of at most one bounce buffer takes no copy engine: the CPU copies it into the pool's pinned buffer (memory
+    // the caller pinned is used as it is), the kernels read and write that buffer over the link themselves (first pass
+    // host -> device scratch, last pass device scratch -> host; single-pass rings in place on the mapped memory), the CPU
+    // copies the result back.  Two kernel launches and one synchronisation instead of copy, two kernels, copy
+    // (tools/perf_host_slice.py); PFHE_STAGE_ZERO_COPY=0 keeps the copy engines.
+    if constexpr (kFastPaths) if (K.zero_copy && len * sizeof(W) <= K.bounce_max && aligned16(host)) {
+        W *mapped = static_cast<W *>(st.map(host, len * sizeof(W)));
+        const bool caller_mapped = mapped != nullptr;
+        void *bounce = nullptr;
+        if (!mapped) {
+            void *bdev = nullptr;
+            bounce = st.bounce(len * sizeof(W), &bdev);
+            if (bounce) {
+                std::memcpy(bounce, host, len * sizeof(W));
+                mapped = static_cast<W *>(bdev);
+            }
+        }
+        if (mapped) {
+            const int rc = ntt_transform_through_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, mapped, d, units * t.L, inverse, lazy,
+                                                     st.stream(), t.tune);
+            if (rc != PFHE_ERR_UNSUPPORTED) {
+                st.touch();
+                stage_path_note(caller_mapped ? kPathMappedCaller : kPathMappedBounce);
+                PFHE_TRY(rc);
+                PFHE_TRY(st.finish());
+                if (bounce) std::memcpy(host, bounce, len * sizeof(W));
+                return PFHE_OK;
+            }
+        }
+    }
+    const bool pinned = st.pin(host, len * sizeof(W));
+    // Long PAGEABLE slices: a pageable copy blocks the thread that issues it, so one thread alone cannot use both
+    // directions of the link.  The context's HELPER THREAD (parked between calls, pfhe_staging.hpp) copies back while this
+    // one copies in: the slice is cut into up to eight pieces of at least 6 MiB; this thread, piece by piece, copies in and
+    // launches the transform on the context's first stream and records an event; the helper waits for each event and copies
+    // that piece back on the second stream.  16 RNS polynomials of 2^16: 0.95 -> 0.79 ms, 64: 3.67 -> 2.54 ms
+    // (tools/perf_host_slice.py).
+    // Two rules keep the two threads apart.  (1) The helper sleeps on a condition variable until a piece is ready — no
+    // spinning beside the copying thread.  (2) Adjacent pieces share the page that holds their common boundary (slices are
+    // 8-byte aligned, not page aligned), and the runtime pins the caller's pages for the duration of a pageable copy: the
+    // helper copies piece k back only once this thread has FINISHED copying piece k + 1 in, so the two threads never have
+    // a page in common in flight (the withdrawn registration of round 4 — r04_experiments.txt item 6 — is the reason to be
+    // strict about who maps the caller's pages when).
+    if constexpr (kFastPaths) if (!pinned && K.helper_thread && units >= 2 && len * sizeof(W) >= ((size_t)8 << 20) &&
+        !st.touches_pinned(host, len * sizeof(W))) {  // (a partly registered slice: copy_in / download stage it)
+        // pieces of at least 6 MiB, at most eight (24 MiB: 2 / 3 / 4 / 6 / 8 pieces 861 / 829 / 808 / 855 / 844 us;
+        // 96 MiB: 3.01 / 2.77 / 2.74 / 2.54 / 2.54 ms; one thread: 0.95 / 3.67 ms)
+        const size_t pieces = std::max<size_t>(2, std::min<size_t>({K.pieces, (size_t)units, len * sizeof(W) / ((size_t)6 << 20)}));
+        std::vector<hipEvent_t> done(pieces);
+        for (hipEvent_t &e : done) PFHE_TRY(st.take_event(&e));
+        std::vector<size_t> off(pieces + 1);
+        for (size_t i = 0; i <= pieces; ++i) off[i] = (size_t)(units * i / pieces) * unit;
+        // shared with the helper's task: must outlive it on EVERY exit path.  `st` was declared before these locals and is
+        // therefore destroyed after them, so its destructor's own wait would come too late for an exception thrown between
+        // helper_start and helper_wait: the Joiner below, declared after everything the task references, aborts and waits first.
+        struct Shared {
+            std::mutex mu;
+            std::condition_variable cv;
+            size_t copied_in = 0;  // pieces whose copy in has returned and whose transform is launched (event recorded)
+            bool all_in = false, abort = false;
+        } sh;
+        const hipStream_t s_in = st.stream(), s_out = st.stream2();
+        st.touch();
+        stage_path_note(kPathHelper);
+        PFHE_TRY(st.helper_start(
+            [&]() -> int {
+                for (size_t i = 0; i < pieces; ++i) {
+                    {
+                        std::unique_lock<std::mutex> lk(sh.mu);
+                        // piece i is launched AND this thread's neighbour piece i + 1 is no longer being copied in
+                        sh.cv.wait(lk, [&] { return sh.abort || sh.all_in || sh.copied_in >= i + 1 + K.helper_lag; });
+                        if (sh.abort) return PFHE_OK;
+                    }
+                    hipError_t e = hipEventSynchronize(done[i]);
+                    if (e == hipSuccess)
+                        e = hipMemcpyAsync(host + off[i], d + off[i], (off[i + 1] - off[i]) * sizeof(W), hipMemcpyDeviceToHost, s_out);
+                    if (e == hipSuccess) e = hipStreamSynchronize(s_out);
+                    if (e != hipSuccess) {
+                        (void)hipGetLastError();
+                        return PFHE_ERR_HIP;
+                    }
+                }
+                return PFHE_OK;
+            },
+            [&]() {
+                std::lock_guard<std::mutex> lk(sh.mu);
+                sh.abort = true;
+                sh.cv.notify_all();
+            }));
+        struct Joiner {
+            HostStage &st;
+            Shared &sh;
+            ~Joiner() {
+                if (!st.helper_busy()) return;
+                {
+                    std::lock_guard<std::mutex> lk(sh.mu);
+                    sh.abort = true;
+                }
+                sh.cv.notify_all();
+                (void)st.helper_wait();
+            }
+        } joiner{st, sh};
+        int rc = PFHE_OK;
+        for (size_t i = 0; i < pieces && rc == PFHE_OK; ++i) {
+            const size_t words = off[i + 1] - off[i];
+            if (hipMemcpyAsync(d + off[i], host + off[i], words * sizeof(W), hipMemcpyHostToDevice, s_in) != hipSuccess) {
+                rc = hip_fail(hipGetLastError(), "staged copy", __FILE__, __LINE__);
+                break;
+            }
+            rc = transform_dev(t, d + off[i], words, inverse, lazy, s_in);
+            if (rc == PFHE_OK && hipEventRecord(done[i], s_in) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipEventRecord", __FILE__, __LINE__);
+            if (rc == PFHE_OK) {
+                std::lock_guard<std::mutex> lk(sh.mu);
+                sh.copied_in = i + 1;
+                sh.all_in = i + 1 == pieces;
+                sh.cv.notify_all();
+            }
+        }
+        if (rc != PFHE_OK) {
+            std::lock_guard<std::mutex> lk(sh.mu);
+            sh.abort = true;
+            sh.cv.notify_all();
+        }
+        const int helper_rc = st.helper_wait();
+        PFHE_TRY(rc);
+        PFHE_TRY(helper_rc);
+        return st.finish();
+    }
+    // otherwise pageable copies go as one piece (they block the calling thread: nothing to pipeline)
+    const size_t per = pinned ? std::max<size_t>(1, K.chunk_bytes / (unit * sizeof(W))) : (size_t)units;
+    const bool pipelined = per < units;
+    const hipStream_t s_in = st.stream(), s_run = pipelined ? st.stream2() : st.stream();
+    for (u64 u0 = 0; u0 < units; u0 += per) {
+        const size_t words = (size_t)std::min<u64>(per, units - u0) * unit, off = (size_t)u0 * unit;
+        PFHE_TRY(st.copy_in(d + off, host + off, words * sizeof(W), s_in));
+        if (pipelined) PFHE_TRY(st.order(s_in, s_run));
+        PFHE_TRY(transform_dev(t, d + off, words, inverse, lazy, s_run));
+        PFHE_TRY(st.download(host + off, d + off, words * sizeof(W), s_run));
+    }
+    return st.finish();
+}
+
+template int transform_host<u64>(const TableSet &, u64 *, size_t, bool, bool);
+template int transform_host<u32>(const TableSet &, u32 *, size_t, bool, bool);
 
 }  // namespace pfhe

@@ -18,21 +18,29 @@ from ._lib import PfheError, check, lib, u64p
 NttError = PfheError  # primus_ntt::NttError variants are carried in PfheError.kind
 
 
-def _host(a: np.ndarray):
-    if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or not a.flags.c_contiguous:
-        raise TypeError("expected a C-contiguous numpy uint64 array")
+def _host(a: np.ndarray, dtype=np.uint64):
+    if not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous:
+        raise TypeError(f"expected a C-contiguous numpy {np.dtype(dtype).name} array")
     return a.ctypes.data_as(C.c_void_p), a.size
 
 
-def _dev(x):
-    """(device pointer, number of 64-bit words) of a torch CUDA tensor or a (ptr, words) pair."""
+def _dev(x, size: int = 8):
+    """(device pointer, number of `size`-byte words) of a torch CUDA tensor or a (ptr, words) pair."""
     if isinstance(x, tuple):
         return C.c_void_p(int(x[0])), int(x[1])
     if hasattr(x, "data_ptr"):
-        if x.element_size() != 8 or not x.is_contiguous() or not x.is_cuda:
-            raise TypeError("expected a contiguous 64-bit CUDA tensor")
+        if x.element_size() != size or not x.is_contiguous() or not x.is_cuda:
+            raise TypeError(f"expected a contiguous {8 * size}-bit CUDA tensor")
         return C.c_void_p(x.data_ptr()), x.numel()
     raise TypeError("expected a torch CUDA tensor or a (device_ptr, words) tuple")
+
+
+def _host32(a: np.ndarray):
+    return _host(a, np.uint32)
+
+
+def _dev32(x):
+    return _dev(x, 4)
 
 
 def _stream(stream):
@@ -47,126 +55,153 @@ def _stream(stream):
     return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
 
 
-class U64NttTable:
-    """primus_ntt::U64NttTable — negacyclic NTT over one prime q < 2^62 (table.rs:41-516)."""
+class _Table:
+    """What the four tables share.  `_pre` is the C symbol prefix, `_dtype` the numpy type of a coefficient."""
 
-    def __init__(self, log_n: int, modulus: int, device: int = 0):
+    _pre = ""
+    _dtype = np.uint64
+
+    def _f(self, name):
+        return getattr(lib(), self._pre + name)
+
+    def _host(self, a):
+        return _host(a, self._dtype)
+
+    def _dev(self, x):
+        return _dev(x, np.dtype(self._dtype).itemsize)
+
+    def _create(self, *args):
         h = C.c_void_p()
-        check(lib().pfhe_ntt_create(log_n, modulus, device, C.byref(h)))
+        check(self._f("create")(*args, C.byref(h)))
         self._h = h
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            lib().pfhe_ntt_destroy(h)
+            try:
+                self._f("destroy")(h)
+            except Exception:
+                pass
             self._h = None
 
-    # getters (table.rs:127-161)
-    def poly_length(self) -> int: return int(lib().pfhe_ntt_poly_length(self._h))
-    def n(self) -> int: return self.poly_length()
-    def log_n(self) -> int: return int(lib().pfhe_ntt_log_n(self._h))
-    def modulus(self) -> int: return int(lib().pfhe_ntt_modulus(self._h))
-    def root(self) -> int: return int(lib().pfhe_ntt_root(self._h))
-    def inv_root(self) -> int: return int(lib().pfhe_ntt_inv_root(self._h))
-    def inv_n(self) -> int: return int(lib().pfhe_ntt_inv_n(self._h))
-    def device(self) -> int: return int(lib().pfhe_ntt_device(self._h))
+    def poly_length(self) -> int: return int(self._f("poly_length")(self._h))
+    def device(self) -> int: return int(self._f("device")(self._h))
 
     # host slices, in place (table.rs:541-563)
-    def transform_slice(self, poly): check(lib().pfhe_ntt_transform_slice(self._h, *_host(poly)))
-    def inverse_transform_slice(self, values): check(lib().pfhe_ntt_inverse_transform_slice(self._h, *_host(values)))
-    def lazy_transform_slice(self, poly): check(lib().pfhe_ntt_lazy_transform_slice(self._h, *_host(poly)))
-    def lazy_inverse_transform_slice(self, values): check(lib().pfhe_ntt_lazy_inverse_transform_slice(self._h, *_host(values)))
-    transform_inplace = transform_slice                  # table.rs:523-530
-    inverse_transform_inplace = inverse_transform_slice  # table.rs:532-539
+    def transform_slice(self, poly): check(self._f("transform_slice")(self._h, *self._host(poly)))
+    def inverse_transform_slice(self, values): check(self._f("inverse_transform_slice")(self._h, *self._host(values)))
+    def lazy_transform_slice(self, poly): check(self._f("lazy_transform_slice")(self._h, *self._host(poly)))
+    def lazy_inverse_transform_slice(self, values): check(self._f("lazy_inverse_transform_slice")(self._h, *self._host(values)))
 
     # monomial shortcuts (table.rs:565-651)
     def transform_monomial(self, coeff: int, degree: int, values):
-        check(lib().pfhe_ntt_transform_monomial(self._h, coeff, degree, *_host(values)))
+        check(self._f("transform_monomial")(self._h, coeff, degree, *self._host(values)))
 
     def transform_coeff_one_monomial(self, degree: int, values):
-        check(lib().pfhe_ntt_transform_coeff_one_monomial(self._h, degree, *_host(values)))
+        check(self._f("transform_coeff_one_monomial")(self._h, degree, *self._host(values)))
 
     def transform_coeff_minus_one_monomial(self, degree: int, values):
-        check(lib().pfhe_ntt_transform_coeff_minus_one_monomial(self._h, degree, *_host(values)))
+        """-X^degree: q_i - 1 in limb i (primus_ntt/src/dcrt/mod.rs:124-134)."""
+        check(self._f("transform_coeff_minus_one_monomial")(self._h, degree, *self._host(values)))
 
     # device path
     def transform_dev(self, poly, lazy: bool = False, stream=None):
-        p, n = _dev(poly)
-        check(lib().pfhe_ntt_transform_dev(self._h, p, n, int(lazy), _stream(stream)))
+        p, n = self._dev(poly)
+        check(self._f("transform_dev")(self._h, p, n, int(lazy), _stream(stream)))
 
     def inverse_transform_dev(self, values, lazy: bool = False, stream=None):
-        p, n = _dev(values)
-        check(lib().pfhe_ntt_inverse_transform_dev(self._h, p, n, int(lazy), _stream(stream)))
-
-    def transform_monomial_dev(self, coeff: int, degree: int, values, stream=None):
-        p, n = _dev(values)
-        check(lib().pfhe_ntt_transform_monomial_dev(self._h, coeff, degree, p, n, _stream(stream)))
+        p, n = self._dev(values)
+        check(self._f("inverse_transform_dev")(self._h, p, n, int(lazy), _stream(stream)))
 
     def mul_assign_dev(self, a, b, stream=None):
-        """NttPolynomial::mul_assign (primus_poly/src/ntt/mul.rs:84-90)."""
-        (pa, na), (pb, nb) = _dev(a), _dev(b)
-        check(lib().pfhe_ntt_mul_assign_dev(self._h, pa, na, pb, nb, _stream(stream)))
+        """NttPolynomial::mul_assign (primus_poly/src/ntt/mul.rs:84-90), DcrtPolynomial::mul_assign
+        (primus_poly/src/dcrt/mul.rs:176-187): a *= b pointwise; b may be one polynomial shared by the batch."""
+        (pa, na), (pb, nb) = self._dev(a), self._dev(b)
+        check(self._f("mul_assign_dev")(self._h, pa, na, pb, nb, _stream(stream)))
 
     def add_mul_assign_dev(self, acc, a, b, stream=None):
-        """NttPolynomial::add_mul_assign (primus_poly/src/ntt/mod.rs:101-112)."""
-        (pc, nc), (pa, na), (pb, nb) = _dev(acc), _dev(a), _dev(b)
+        """NttPolynomial::add_mul_assign (primus_poly/src/ntt/mod.rs:101-112), DcrtPolynomial::add_mul_assign
+        (primus_poly/src/dcrt/mod.rs:105-123)."""
+        (pc, nc), (pa, na), (pb, nb) = self._dev(acc), self._dev(a), self._dev(b)
         if nc != na:
             raise PfheError(32, "acc and a differ in length")
-        check(lib().pfhe_ntt_add_mul_assign_dev(self._h, pc, pa, na, pb, nb, _stream(stream)))
+        check(self._f("add_mul_assign_dev")(self._h, pc, pa, na, pb, nb, _stream(stream)))
+
+
+_U32Common = _Table  # (the name the caller-register probe of tests/conftest.py wraps the slice methods under)
+
+
+class _OnePrime:
+    """The constants of the one prime of an NttTable (table.rs:127-161)."""
+
+    def n(self) -> int: return self.poly_length()
+    def log_n(self) -> int: return int(self._f("log_n")(self._h))
+    def modulus(self) -> int: return int(self._f("modulus")(self._h))
+    def root(self) -> int: return int(self._f("root")(self._h))
+    def inv_root(self) -> int: return int(self._f("inv_root")(self._h))
+    def inv_n(self) -> int: return int(self._f("inv_n")(self._h))
+
+    def transform_monomial_dev(self, coeff: int, degree: int, values, stream=None):
+        p, n = self._dev(values)
+        check(self._f("transform_monomial_dev")(self._h, coeff, degree, p, n, _stream(stream)))
+
+
+class _Limbs:
+    """The shape of a DcrtTable and the constants of its limbs (dcrt/mod.rs:19-135)."""
+
+    def moduli_count(self) -> int: return int(self._f("moduli_count")(self._h))
+    def crt_poly_length(self) -> int: return int(self._f("crt_poly_length")(self._h))
+    def moduli(self): return [int(self._f("modulus")(self._h, i)) for i in range(self.moduli_count())]
+    def roots(self): return [int(self._f("root")(self._h, i)) for i in range(self.moduli_count())]
+
+    def transform_form(self, words: int, inverse: bool = False):
+        """(name, launches): how transform_dev / inverse_transform_dev will run `words` words of data."""
+        buf, k = C.create_string_buffer(112), C.c_int(0)
+        check(self._f("transform_form")(self._h, words, int(inverse), buf, len(buf), C.byref(k)))
+        return buf.value.decode(), int(k.value)
+
+
+class _U64MulTo:
+    """out = a*b (+ c): the u64 tables."""
 
     def mul_to_dev(self, a, b, out, stream=None):
         """NttPolynomial::mul_to (primus_poly/src/ntt/mul.rs:100-107): out = a*b."""
         (pa, na), (pb, nb), (po, no) = _dev(a), _dev(b), _dev(out)
         if no != na:
             raise PfheError(32, "output and multiplicand differ in length")
-        check(lib().pfhe_ntt_mul_to_dev(self._h, pa, na, pb, nb, po, _stream(stream)))
+        check(self._f("mul_to_dev")(self._h, pa, na, pb, nb, po, _stream(stream)))
 
     def mul_add_to_dev(self, a, b, c, out, stream=None):
         """NttPolynomial::mul_add_to (primus_poly/src/ntt/mod.rs:169-187): out = a*b + c."""
         (pa, na), (pb, nb), (pc, nc), (po, no) = _dev(a), _dev(b), _dev(c), _dev(out)
         if no != na or nc != na:
             raise PfheError(32, "operands differ in length")
-        check(lib().pfhe_ntt_mul_add_to_dev(self._h, pa, na, pb, nb, pc, po, _stream(stream)))
+        check(self._f("mul_add_to_dev")(self._h, pa, na, pb, nb, pc, po, _stream(stream)))
 
 
-class U64DcrtTable:
+class U64NttTable(_OnePrime, _U64MulTo, _Table):
+    """primus_ntt::U64NttTable — negacyclic NTT over one prime q < 2^62 (table.rs:41-516)."""
+
+    _pre = "pfhe_ntt_"
+
+    def __init__(self, log_n: int, modulus: int, device: int = 0):
+        self._create(log_n, modulus, device)
+
+    transform_inplace = _Table.transform_slice                  # table.rs:523-530
+    inverse_transform_inplace = _Table.inverse_transform_slice  # table.rs:532-539
+
+
+class U64DcrtTable(_Limbs, _U64MulTo, _Table):
     """primus_ntt::U64DcrtTable — one U64NttTable per RNS limb, modulus-major data (dcrt/prime64.rs)."""
+
+    _pre = "pfhe_dcrt_"
 
     def __init__(self, log_n: int, moduli, device: int = 0):
         arr = np.ascontiguousarray(np.array([int(m) for m in moduli], dtype=np.uint64))
-        h = C.c_void_p()
-        check(lib().pfhe_dcrt_create(log_n, arr.ctypes.data_as(u64p), arr.size, device, C.byref(h)))
-        self._h = h
+        self._create(log_n, arr.ctypes.data_as(u64p), arr.size, device)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            lib().pfhe_dcrt_destroy(h)
-            self._h = None
-
-    def poly_length(self) -> int: return int(lib().pfhe_dcrt_poly_length(self._h))
-    def moduli_count(self) -> int: return int(lib().pfhe_dcrt_moduli_count(self._h))
-    def crt_poly_length(self) -> int: return int(lib().pfhe_dcrt_crt_poly_length(self._h))
-    def device(self) -> int: return int(lib().pfhe_dcrt_device(self._h))
-    def moduli(self): return [int(lib().pfhe_dcrt_modulus(self._h, i)) for i in range(self.moduli_count())]
-    def roots(self): return [int(lib().pfhe_dcrt_root(self._h, i)) for i in range(self.moduli_count())]
-
-    def transform_slice(self, poly): check(lib().pfhe_dcrt_transform_slice(self._h, *_host(poly)))
-    def inverse_transform_slice(self, poly): check(lib().pfhe_dcrt_inverse_transform_slice(self._h, *_host(poly)))
-    def lazy_transform_slice(self, poly): check(lib().pfhe_dcrt_lazy_transform_slice(self._h, *_host(poly)))
-    def lazy_inverse_transform_slice(self, poly): check(lib().pfhe_dcrt_lazy_inverse_transform_slice(self._h, *_host(poly)))
-    transform_inplace = transform_slice
-    inverse_transform_inplace = inverse_transform_slice
-
-    def transform_monomial(self, coeff: int, degree: int, values):
-        check(lib().pfhe_dcrt_transform_monomial(self._h, coeff, degree, *_host(values)))
-
-    def transform_coeff_one_monomial(self, degree: int, values):
-        check(lib().pfhe_dcrt_transform_coeff_one_monomial(self._h, degree, *_host(values)))
-
-    def transform_coeff_minus_one_monomial(self, degree: int, values):
-        """-X^degree: q_i - 1 in limb i (primus_ntt/src/dcrt/mod.rs:124-134)."""
-        check(lib().pfhe_dcrt_transform_coeff_minus_one_monomial(self._h, degree, *_host(values)))
+    transform_inplace = _Table.transform_slice
+    inverse_transform_inplace = _Table.inverse_transform_slice
 
     def transform_monomial_dev(self, coeff: int, degree: int, values, stream=None):
         """DcrtTable::transform_monomial into device memory: launches only, capturable."""
@@ -180,40 +215,6 @@ class U64DcrtTable:
         p, n = _dev(values)
         check(lib().pfhe_dcrt_transform_monomial_dev(self._h, 0, degree, p, n, 1, _stream(stream)))
 
-    def transform_dev(self, poly, lazy: bool = False, stream=None):
-        p, n = _dev(poly)
-        check(lib().pfhe_dcrt_transform_dev(self._h, p, n, int(lazy), _stream(stream)))
-
-    def inverse_transform_dev(self, poly, lazy: bool = False, stream=None):
-        p, n = _dev(poly)
-        check(lib().pfhe_dcrt_inverse_transform_dev(self._h, p, n, int(lazy), _stream(stream)))
-
-    def mul_assign_dev(self, a, b, stream=None):
-        """DcrtPolynomial::mul_assign (primus_poly/src/dcrt/mul.rs:176-187); b may be one shared polynomial."""
-        (pa, na), (pb, nb) = _dev(a), _dev(b)
-        check(lib().pfhe_dcrt_mul_assign_dev(self._h, pa, na, pb, nb, _stream(stream)))
-
-    def add_mul_assign_dev(self, acc, a, b, stream=None):
-        """DcrtPolynomial::add_mul_assign (primus_poly/src/dcrt/mod.rs:105-123)."""
-        (pc, nc), (pa, na), (pb, nb) = _dev(acc), _dev(a), _dev(b)
-        if nc != na:
-            raise PfheError(32, "acc and a differ in length")
-        check(lib().pfhe_dcrt_add_mul_assign_dev(self._h, pc, pa, na, pb, nb, _stream(stream)))
-
-    def mul_to_dev(self, a, b, out, stream=None):
-        """NttPolynomial::mul_to (primus_poly/src/ntt/mul.rs:100-107): out = a*b."""
-        (pa, na), (pb, nb), (po, no) = _dev(a), _dev(b), _dev(out)
-        if no != na:
-            raise PfheError(32, "output and multiplicand differ in length")
-        check(lib().pfhe_dcrt_mul_to_dev(self._h, pa, na, pb, nb, po, _stream(stream)))
-
-    def mul_add_to_dev(self, a, b, c, out, stream=None):
-        """NttPolynomial::mul_add_to (primus_poly/src/ntt/mod.rs:169-187): out = a*b + c."""
-        (pa, na), (pb, nb), (pc, nc), (po, no) = _dev(a), _dev(b), _dev(c), _dev(out)
-        if no != na or nc != na:
-            raise PfheError(32, "operands differ in length")
-        check(lib().pfhe_dcrt_mul_add_to_dev(self._h, pa, na, pb, nb, pc, po, _stream(stream)))
-
     def add_dcrt_glwe_mul_dcrt_polynomial_assign_dev(self, acc, dcrt_glwe, dcrt_poly, glwe_polys: int, stream=None):
         """DcrtGlwe::add_dcrt_glwe_mul_dcrt_polynomial_assign (primus_lattice/src/glwe/dcrt.rs:107-126) over a
         batch: acc[e][c] += dcrt_glwe[e][c] * dcrt_poly[e], c < glwe_polys = k + 1."""
@@ -222,12 +223,6 @@ class U64DcrtTable:
             raise PfheError(32, "accumulator and ciphertext differ in length")
         check(lib().pfhe_dcrt_add_dcrt_glwe_mul_dcrt_polynomial_assign_dev(self._h, pc, pa, na, pb, nb, glwe_polys,
                                                                            _stream(stream)))
-
-    def transform_form(self, words: int, inverse: bool = False):
-        """(name, launches): how transform_dev / inverse_transform_dev will run `words` words of data."""
-        buf, k = C.create_string_buffer(96), C.c_int(0)
-        check(lib().pfhe_dcrt_transform_form(self._h, words, int(inverse), buf, len(buf), C.byref(k)))
-        return buf.value.decode(), int(k.value)
 
     def fill_uniform_dev(self, dst, seed: int, stream=None):
         """Synthetic residues (bench / test input): uniform in [0, q_limb) from SplitMix64(seed)."""
@@ -354,133 +349,23 @@ class U64DcrtTable:
 # u32 tables — primus_ntt::U32NttTable (ntt/prime32/table.rs:37) / U32DcrtTable (dcrt/prime32.rs:11)
 # ---------------------------------------------------------------------------------------------
 
-def _host32(a: np.ndarray):
-    if not isinstance(a, np.ndarray) or a.dtype != np.uint32 or not a.flags.c_contiguous:
-        raise TypeError("expected a C-contiguous numpy uint32 array")
-    return a.ctypes.data_as(C.c_void_p), a.size
-
-
-def _dev32(x):
-    """(device pointer, number of 32-bit words) of a torch CUDA tensor or a (ptr, words) pair."""
-    if isinstance(x, tuple):
-        return C.c_void_p(int(x[0])), int(x[1])
-    if hasattr(x, "data_ptr"):
-        if x.element_size() != 4 or not x.is_contiguous() or not x.is_cuda:
-            raise TypeError("expected a contiguous 32-bit CUDA tensor")
-        return C.c_void_p(x.data_ptr()), x.numel()
-    raise TypeError("expected a torch CUDA tensor or a (device_ptr, words) tuple")
-
-
-class _U32Common:
-    """Methods shared by the two u32 tables; `_pre` is the C symbol prefix."""
-
-    _pre = ""
-
-    def _f(self, name):
-        return getattr(lib(), self._pre + name)
-
-    def transform_slice(self, poly): check(self._f("transform_slice")(self._h, *_host32(poly)))
-    def inverse_transform_slice(self, values): check(self._f("inverse_transform_slice")(self._h, *_host32(values)))
-    def lazy_transform_slice(self, poly): check(self._f("lazy_transform_slice")(self._h, *_host32(poly)))
-    def lazy_inverse_transform_slice(self, values): check(self._f("lazy_inverse_transform_slice")(self._h, *_host32(values)))
-
-    def transform_monomial(self, coeff: int, degree: int, values):
-        check(self._f("transform_monomial")(self._h, coeff, degree, *_host32(values)))
-
-    def transform_coeff_one_monomial(self, degree: int, values):
-        check(self._f("transform_coeff_one_monomial")(self._h, degree, *_host32(values)))
-
-    def transform_coeff_minus_one_monomial(self, degree: int, values):
-        check(self._f("transform_coeff_minus_one_monomial")(self._h, degree, *_host32(values)))
-
-    def transform_dev(self, poly, lazy: bool = False, stream=None):
-        p, n = _dev32(poly)
-        check(self._f("transform_dev")(self._h, p, n, int(lazy), _stream(stream)))
-
-    def inverse_transform_dev(self, values, lazy: bool = False, stream=None):
-        p, n = _dev32(values)
-        check(self._f("inverse_transform_dev")(self._h, p, n, int(lazy), _stream(stream)))
-
-    def mul_assign_dev(self, a, b, stream=None):
-        """a *= b pointwise (b: same length, or one polynomial shared by the batch)."""
-        pa, na = _dev32(a)
-        pb, nb = _dev32(b)
-        check(self._f("mul_assign_dev")(self._h, pa, na, pb, nb, _stream(stream)))
-
-    def add_mul_assign_dev(self, acc, a, b, stream=None):
-        pc, nc = _dev32(acc)
-        pa, na = _dev32(a)
-        pb, nb = _dev32(b)
-        if nc != na:
-            raise PfheError(32, "accumulator and multiplicand differ in length")
-        check(self._f("add_mul_assign_dev")(self._h, pc, pa, na, pb, nb, _stream(stream)))
-
-
-class U32NttTable(_U32Common):
+class U32NttTable(_OnePrime, _Table):
     """primus_ntt::U32NttTable — negacyclic NTT over one prime q < 2^30, u32 data (table.rs:37-470)."""
 
-    _pre = "pfhe_ntt32_"
+    _pre, _dtype = "pfhe_ntt32_", np.uint32
 
     def __init__(self, log_n: int, modulus: int, device: int = 0):
-        h = C.c_void_p()
-        check(lib().pfhe_ntt32_create(log_n, modulus, device, C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().pfhe_ntt32_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    def poly_length(self) -> int: return int(lib().pfhe_ntt32_poly_length(self._h))
-    def n(self) -> int: return self.poly_length()
-    def log_n(self) -> int: return int(lib().pfhe_ntt32_log_n(self._h))
-    def modulus(self) -> int: return int(lib().pfhe_ntt32_modulus(self._h))
-    def root(self) -> int: return int(lib().pfhe_ntt32_root(self._h))
-    def inv_root(self) -> int: return int(lib().pfhe_ntt32_inv_root(self._h))
-    def inv_n(self) -> int: return int(lib().pfhe_ntt32_inv_n(self._h))
-    def device(self) -> int: return int(lib().pfhe_ntt32_device(self._h))
-
-    def transform_monomial_dev(self, coeff: int, degree: int, values, stream=None):
-        p, n = _dev32(values)
-        check(lib().pfhe_ntt32_transform_monomial_dev(self._h, coeff, degree, p, n, _stream(stream)))
+        self._create(log_n, modulus, device)
 
 
-class U32DcrtTable(_U32Common):
+class U32DcrtTable(_Limbs, _Table):
     """primus_ntt::U32DcrtTable — one U32NttTable per RNS limb; unit = L*N words, modulus-major."""
 
-    _pre = "pfhe_dcrt32_"
+    _pre, _dtype = "pfhe_dcrt32_", np.uint32
 
     def __init__(self, log_n: int, moduli, device: int = 0):
         arr = (C.c_uint32 * len(moduli))(*[int(m) for m in moduli])
-        h = C.c_void_p()
-        check(lib().pfhe_dcrt32_create(log_n, arr, len(moduli), device, C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            try:
-                lib().pfhe_dcrt32_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    def poly_length(self) -> int: return int(lib().pfhe_dcrt32_poly_length(self._h))
-    def moduli_count(self) -> int: return int(lib().pfhe_dcrt32_moduli_count(self._h))
-    def transform_form(self, words: int, inverse: bool = False):
-        """(name, launches): how transform_dev / inverse_transform_dev will run `words` u32 words of data."""
-        buf, k = C.create_string_buffer(112), C.c_int(0)
-        check(lib().pfhe_dcrt32_transform_form(self._h, words, int(inverse), buf, len(buf), C.byref(k)))
-        return buf.value.decode(), int(k.value)
-
-    def crt_poly_length(self) -> int: return int(lib().pfhe_dcrt32_crt_poly_length(self._h))
-    def device(self) -> int: return int(lib().pfhe_dcrt32_device(self._h))
-    def moduli(self): return [int(lib().pfhe_dcrt32_modulus(self._h, i)) for i in range(self.moduli_count())]
-    def roots(self): return [int(lib().pfhe_dcrt32_root(self._h, i)) for i in range(self.moduli_count())]
+        self._create(log_n, arr, len(moduli), device)
 
     def fill_uniform_dev(self, dst, seed: int, stream=None):
         """Synthetic residues (bench input): uniform in [0, q_limb) from SplitMix64(seed)."""
