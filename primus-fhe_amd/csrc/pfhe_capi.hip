@@ -534,13 +534,13 @@ int pfhe_dcrt_glwe_mul_dcrt_polynomial_to_dev(const pfhe_dcrt *table, const uint
 }
 
 int pfhe_dcrt_transform_num_passes(const pfhe_dcrt *table) {
-    return table ? ntt_num_passes(table->t->log_n, table->t->ntt_arith, table->t->tune) : 0;
+    return table ? ntt_num_passes(table->t->log_n, table->t->ntt_arith) : 0;
 }
 
 const char *pfhe_dcrt_transform_pass_name(const pfhe_dcrt *table, int inverse, int index) {
     static thread_local char buf[kPassNameCap];
     buf[0] = 0;
-    if (table) ntt_pass_name(table->t->log_n, inverse != 0, index, buf, sizeof buf, table->t->ntt_arith, table->t->tune);
+    if (table) ntt_pass_name(table->t->log_n, inverse != 0, index, buf, sizeof buf, table->t->ntt_arith);
     return buf;
 }
 
@@ -562,7 +562,7 @@ int pfhe_dcrt_transform_pass_dev(const pfhe_dcrt *table, uint64_t *poly_dev, siz
     DeviceGuard g(t.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     return ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, (u64 *)poly_dev, len / t.n, inverse != 0, index,
-                        lazy != 0, (hipStream_t)stream, nullptr, 0, t.tune);
+                        lazy != 0, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 

@@ -104,7 +104,7 @@ int run_product(pfhe_extprod_plan *p, const u64 *crt_polys, u32 rows, const u64 
         }
         const bool fused = gadget_fused_supported(t.log_n, p->k) && p->use_fused &&
                            ((std::min<u64>(batch, p->chunk) * t.L) << (t.log_n - 12)) >= p->fused_min_wgs;
-        const int passes = ntt_num_passes(t.log_n, t.ntt_arith, t.tune);
+        const int passes = ntt_num_passes(t.log_n, t.ntt_arith);
         // One arithmetic for everything in here — the gadget kernels and the plain transform passes around them: the table's
         // transform arithmetic t.ntt_arith (pseudo-Mersenne, Montgomery form for generic primes below 2^61, or the
         // reference's Shoup form).
@@ -132,7 +132,7 @@ int run_product(pfhe_extprod_plan *p, const u64 *crt_polys, u32 rows, const u64 
             } else {
                 PFHE_TRY(gadget_decompose_dev(rns, p->basis_par, t.log_n, crt_polys + done * rows * in_words, dg, cur * rows, s));
                 for (int i = 0; i < passes - 1; ++i)
-                    PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, i, false, s, nullptr, 0, t.tune));
+                    PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, i, false, s));
             }
             PFHE_TRY(stamp());
             // ---- block pass (last pass of the transform) + multiply-accumulate ----
@@ -141,8 +141,7 @@ int run_product(pfhe_extprod_plan *p, const u64 *crt_polys, u32 rows, const u64 
                                                  keys + (keys_shared ? 0 : done * key_words), keys_shared,
                                                  result + done * (p->k + 1) * W, cur, accumulate, s, inv_tail));
             } else {
-                PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, passes - 1, false, s, nullptr, 0,
-                                      t.tune));
+                PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, dg, npolys, false, passes - 1, false, s));
                 PFHE_TRY(gadget_mulacc_dev(t.primes_dev, t.L, t.log_n, p->k, rows, ell, dg,
                                            keys + (keys_shared ? 0 : done * key_words), keys_shared,
                                            result + done * (p->k + 1) * W, cur, accumulate, s));
@@ -704,9 +703,8 @@ int finish_coeff_form(const pfhe_extprod_plan *plan, u64 *result, u64 batch, int
     const TableSet &t = *plan->table;
     if (coeff_passes == 0)
         PFHE_TRY(ntt_inverse_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, result, batch * (plan->k + 1) * t.L, false, s, t.tune));
-    for (int i = coeff_passes; i > 0 && i < ntt_num_passes(t.log_n, t.ntt_arith, t.tune); ++i)
-        PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, result, batch * (plan->k + 1) * t.L, true, i, false, s,
-                              nullptr, 0, t.tune));
+    for (int i = coeff_passes; i > 0 && i < ntt_num_passes(t.log_n, t.ntt_arith); ++i)
+        PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n, t.ntt_arith, result, batch * (plan->k + 1) * t.L, true, i, false, s));
     return PFHE_OK;
 }
 // u32: nothing ran -> the table's inverse; the block pass ran inside the fused kernel -> the strided pass finishes
@@ -716,7 +714,7 @@ int finish_coeff_form(const pfhe_extprod32_plan *plan, u32 *result, u64 batch, i
         PFHE_TRY(ntt32_transform_dev(t.primes_dev, t.L, t.log_n, result, batch * (plan->k + 1) * t.L, true, false, s, t.tune));
     if (coeff_passes == 1)
         PFHE_TRY(ntt_pass_dev(t.primes_dev, t.L, t.log_n - 1, kArithB32, reinterpret_cast<u64 *>(result),
-                              batch * (plan->k + 1) * t.L, true, 1, false, s, nullptr, 0, t.tune));
+                              batch * (plan->k + 1) * t.L, true, 1, false, s));
     return PFHE_OK;
 }
 

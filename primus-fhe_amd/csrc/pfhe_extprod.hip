@@ -40,6 +40,12 @@ constexpr int kMulaccMinWg = 2;  // resident workgroups per CU the 256-thread fo
 // coefficient) live in registers for the whole loop over the terms: with 16 coefficients per thread they are 64 registers
 // on top of the transform's ~106 and only two workgroups (two waves per SIMD) fit a CU; with 8 they are 32 on top of ~80.
 constexpr int kMulacc8MinWaves = 4;
+// The form each policy launches (gadget_block_mulacc_dev).  PmArith, 512 threads x 8 coefficients: 32 accumulator
+// registers, four waves per SIMD (the 256 x 16 form holds 64 and fits two: 48.0 -> 49.0 k products/s when it was replaced).
+// MontArith (generic primes below 2^61, 7 multiplies per butterfly instead of Shoup's 10) takes the 512-thread form too:
+// 38.7 -> 40.0 k products/s for three generic 61-bit primes, same box.  ShoupArith keeps 256 x 16.
+template <class A>
+struct MulaccLogE : std::integral_constant<int, std::is_same<A, ShoupArith>::value ? 4 : 3> {};
 template <class A, int NC, int LOGE = 4>
 __global__ __launch_bounds__(LOGE == 3 ? 512 : 256, LOGE == 3 ? kMulacc8MinWaves : kMulaccMinWg) void gadget_block_mulacc_kernel(const u64 *__restrict__ digits,
                                                                   const u64 *__restrict__ ggsw, u64 ggsw_stride,
@@ -662,9 +668,10 @@ int launch_extprod_small(const int *sdigits, const u64 *ggsw, u64 stride, u64 *r
                          u32 rows, u32 ell, u64 batch, bool accumulate, bool into_coeff, hipStream_t s) {
     const u64 total = batch * L;
     if (total == 0) return PFHE_OK;
-    if (total > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
+    u32 grid = 0;
+    PFHE_TRY(launch_grid(total, &grid));
     constexpr size_t lds_bytes = (size_t)BlockCfg<LOGB>::LDS_WORDS * sizeof(u64);
-    hipLaunchKernelGGL((extprod_small_kernel<A, LOGB, NC, ADD_COEFF>), dim3((u32)total), dim3(BlockCfg<LOGB>::THREADS), lds_bytes, s,
+    hipLaunchKernelGGL((extprod_small_kernel<A, LOGB, NC, ADD_COEFF>), dim3(grid), dim3(BlockCfg<LOGB>::THREADS), lds_bytes, s,
                        sdigits, ggsw, stride, result, primes, L, rows, ell, total, accumulate ? 1u : 0u,
                        into_coeff ? 1u : 0u);
     PFHE_HIP(hipGetLastError());
@@ -693,29 +700,19 @@ int gadget_block_mulacc_dev(const NttPrime *primes, u32 L, u32 log_n, int arith,
     using Cfg = BlockCfg<12>;
     const u64 total_blocks = (batch * L) << (log_n - 12);
     if (total_blocks == 0) return PFHE_OK;
-    if (total_blocks > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
+    u32 grid = 0;
+    PFHE_TRY(launch_grid(total_blocks, &grid));
     const u64 ggsw_words = ((u64)terms * (k + 1) * L) << log_n;
     constexpr size_t lds_bytes = (size_t)Cfg::LDS_WORDS * sizeof(u64);
     const u64 stride = ggsw_shared ? 0ull : ggsw_words;
-    if (arith == kArithPm) {
-        // 512 threads x 8 coefficients: 32 accumulator registers, four waves per SIMD (the 256 x 16 form holds 64 and
-        // fits two: 48.0 -> 49.0 k products/s when it was replaced)
-        hipLaunchKernelGGL((gadget_block_mulacc_kernel<PmArith, 2, 3>), dim3((u32)total_blocks), dim3(512), lds_bytes, s,
-                           digits, ggsw, stride, result, primes, L, log_n, terms, total_blocks, accumulate ? 1u : 0u,
-                           inv_tail ? 1u : 0u);
-    } else if (arith == kArithMont) {
-        // generic primes below 2^61: the Montgomery-form butterflies (7 multiplies) instead of the Shoup ones (10)
-        // (the 512-thread form here too: 38.7 -> 40.0 k products/s for three generic 61-bit primes, same box)
-        hipLaunchKernelGGL((gadget_block_mulacc_kernel<MontArith, 2, 3>), dim3((u32)total_blocks), dim3(512), lds_bytes, s,
-                           digits, ggsw, stride, result, primes, L, log_n, terms, total_blocks, accumulate ? 1u : 0u,
-                           inv_tail ? 1u : 0u);
-    } else {
-        hipLaunchKernelGGL((gadget_block_mulacc_kernel<ShoupArith, 2>), dim3((u32)total_blocks), dim3(256), lds_bytes, s,
-                           digits, ggsw, stride, result, primes, L, log_n, terms, total_blocks, accumulate ? 1u : 0u,
-                           inv_tail ? 1u : 0u);
-    }
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return with_arith(arith, [&](auto a) -> int {
+        using A = typename decltype(a)::type;
+        constexpr int LOGE = MulaccLogE<A>::value;
+        hipLaunchKernelGGL((gadget_block_mulacc_kernel<A, 2, LOGE>), dim3(grid), dim3(LOGE == 3 ? 512 : 256), lds_bytes, s, digits,
+                           ggsw, stride, result, primes, L, log_n, terms, total_blocks, accumulate ? 1u : 0u, inv_tail ? 1u : 0u);
+        PFHE_HIP(hipGetLastError());
+        return PFHE_OK;
+    });
 }
 
 }  // namespace pfhe
@@ -752,14 +749,11 @@ int extprod_small_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u32 k
                       const u64 *ggsw, bool ggsw_shared, u64 *result, u64 batch, bool accumulate, bool into_coeff,
                       hipStream_t s) {
     const u64 stride = ggsw_shared ? 0ull : (((u64)rows * ell * (k + 1) * L) << log_n);
-    if (k == 1) {
-        if (arith == kArithMont)
-            return dispatch_extprod_small<MontArith, 2>(log_n, sdigits, ggsw, stride, result, primes, L, rows, ell, batch, accumulate, into_coeff, s);
-        return arith == kArithPm
-                   ? dispatch_extprod_small<PmArith, 2>(log_n, sdigits, ggsw, stride, result, primes, L, rows, ell, batch, accumulate, into_coeff, s)
-                   : dispatch_extprod_small<ShoupArith, 2>(log_n, sdigits, ggsw, stride, result, primes, L, rows, ell, batch, accumulate, into_coeff, s);
-    }
-    return PFHE_ERR_UNSUPPORTED;
+    if (k != 1) return PFHE_ERR_UNSUPPORTED;
+    return with_arith(arith, [&](auto a) {
+        return dispatch_extprod_small<typename decltype(a)::type, 2>(log_n, sdigits, ggsw, stride, result, primes, L, rows, ell, batch,
+                                                                     accumulate, into_coeff, s);
+    });
 }
 
 // ---- the <u32> product's fused kernels: N = 2^16 (2^15 words = 4 strided stages x blocks of 2^11 words), k = 1 ----
@@ -787,10 +781,11 @@ int gadget_block_mulacc32_dev(const NttPrime *primes, u32 L, u32 log_n, u32 term
     const u32 log_nw = log_n - 1;
     const u64 total_blocks = (batch * L) << (log_nw - 11);
     if (total_blocks == 0) return PFHE_OK;
-    if (total_blocks > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
+    u32 grid = 0;
+    PFHE_TRY(launch_grid(total_blocks, &grid));
     const u64 ggsw_words = ((u64)terms * 2 * L) << log_nw;  // 64-bit words of one GGSW's rows
     constexpr size_t lds_bytes = (size_t)BlockCfg<11, 3>::LDS_WORDS * sizeof(u64);
-    hipLaunchKernelGGL((gadget_block_mulacc32_kernel<2>), dim3((u32)total_blocks), dim3(256), lds_bytes, s,
+    hipLaunchKernelGGL((gadget_block_mulacc32_kernel<2>), dim3(grid), dim3(256), lds_bytes, s,
                        reinterpret_cast<const u64 *>(digits), reinterpret_cast<const u64 *>(ggsw), ggsw_shared ? 0ull : ggsw_words,
                        reinterpret_cast<u64 *>(result), primes, L, log_nw, terms, total_blocks, accumulate ? 1u : 0u,
                        inv_tail ? 1u : 0u);
@@ -814,16 +809,11 @@ int gadget_decompose_strided_dev(const RnsParams &r, const BasisParams &b, const
     if (!gadget_decompose_strided_supported(log_n, r.dev.value_len) || sdigits == nullptr) return PFHE_ERR_UNSUPPORTED;
     if (npolys == 0) return PFHE_OK;
     const int k = make_ntt_plan(log_n).strided[0];
-    if (arith == kArithPm) {
-        return k == 4 ? digits_strided_by_width<PmArith, 4>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s)
-                      : digits_strided_by_width<PmArith, 3>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s);
-    }
-    if (arith == kArithMont) {
-        return k == 4 ? digits_strided_by_width<MontArith, 4>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s)
-                      : digits_strided_by_width<MontArith, 3>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s);
-    }
-    return k == 4 ? digits_strided_by_width<ShoupArith, 4>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s)
-                  : digits_strided_by_width<ShoupArith, 3>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s);
+    return with_arith(arith, [&](auto a) {
+        using A = typename decltype(a)::type;
+        return k == 4 ? digits_strided_by_width<A, 4>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s)
+                      : digits_strided_by_width<A, 3>(r, b, primes, log_n, crt_polys, sdigits, digits, npolys, s);
+    });
 }
 
 // ---- batched blind rotation, fused small-ring step (the handle in pfhe_capi_rns.hip picks this path exactly where
@@ -849,11 +839,10 @@ int blindrot_small_digits_dev(const RnsParams &r, const BasisParams &b, u32 log_
 int blindrot_small_product_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u32 ell, const int *sdigits,
                                const u64 *ggsw, u64 *acc, u64 batch, hipStream_t s) {
     // one shared key (stride 0), coefficient-form output added to ACC in place
-    if (arith == kArithMont)
-        return dispatch_extprod_small<MontArith, 2, true>(log_n, sdigits, ggsw, 0, acc, primes, L, 2, ell, batch, false, true, s);
-    return arith == kArithPm
-               ? dispatch_extprod_small<PmArith, 2, true>(log_n, sdigits, ggsw, 0, acc, primes, L, 2, ell, batch, false, true, s)
-               : dispatch_extprod_small<ShoupArith, 2, true>(log_n, sdigits, ggsw, 0, acc, primes, L, 2, ell, batch, false, true, s);
+    return with_arith(arith, [&](auto a) {
+        return dispatch_extprod_small<typename decltype(a)::type, 2, true>(log_n, sdigits, ggsw, 0, acc, primes, L, 2, ell, batch, false,
+                                                                           true, s);
+    });
 }
 
 }  // namespace pfhe

@@ -771,6 +771,15 @@ __global__ __launch_bounds__(BlockCfg<LOGB>::THREADS) __attribute__((amdgpu_wave
 // ------------------------------------------------------------------------------------------
 // host-side planner / launchers
 // ------------------------------------------------------------------------------------------
+int launch_grid(u64 count, u32 *grid) {
+    if (count > kMaxGrid) {
+        set_last_error("batch too large for one launch");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    *grid = (u32)count;
+    return PFHE_OK;
+}
+
 namespace {
 
 // Large batches take the instantiations with non-temporal stores / staged loads (pfhe_ntt_device.hpp, gstore): measured
@@ -779,41 +788,59 @@ namespace {
 // Cache, keep the plain forms (192 MiB, two passes: 0.181 ms plain, 0.190 ms non-temporal).
 constexpr u64 kNtMinBytes = 256ull << 20;
 
-template <class A, int LOGB, bool INV, bool MUL, bool NT>
-int launch_block_impl(u64 *data, const NttPrime *primes, u32 L, u32 log_n, u64 npolys, bool lazy, hipStream_t s,
-                      const u64 *mul, u64 mul_polys) {
-    using Cfg = BlockCfg<LOGB>;
-    const u64 total_blocks = npolys << (log_n - LOGB);
-    const u64 grid = (total_blocks + Cfg::BPW - 1) / Cfg::BPW;
-    if (grid == 0) return PFHE_OK;
-    if (grid > 0x7fffffffull) {
-        set_last_error("batch too large for one launch");
-        return PFHE_ERR_BAD_LENGTH;
+// A kernel that asks for more than 64 KiB of dynamic LDS has to be told so before its first launch on a device: once per
+// (thread, device, kernel), lock-free; a device index outside the cache sets the attribute on every launch.
+template <auto KERN>
+int allow_dynamic_lds(size_t bytes) {
+    static thread_local bool configured[64] = {};
+    int dev = 0;
+    PFHE_HIP(hipGetDevice(&dev));
+    const bool cached = dev >= 0 && dev < 64;
+    if (!cached || !configured[dev]) {
+        PFHE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)bytes));
+        if (cached) configured[dev] = true;
     }
-    constexpr size_t lds_bytes = (size_t)Cfg::BPW * Cfg::LDS_WORDS * sizeof(u64);
-    void (*kern)(u64 *, const NttPrime *, u32, u32, u64, u32, const u64 *, u64);
-    if constexpr (LOGB >= 13) kern = ntt_block_big_kernel<A, LOGB, INV, MUL, NT>;
-    else if constexpr (LOGB >= 10) kern = ntt_block_kernel<A, LOGB, INV, MUL, NT>;
-    else kern = ntt_block_small_kernel<A, LOGB, INV, MUL, NT>;
-    if (lds_bytes > 64 * 1024) {
-        static thread_local bool configured[64] = {};
-        int dev = 0;
-        PFHE_HIP(hipGetDevice(&dev));
-        const bool cached = dev >= 0 && dev < 64;  // outside the cache: set on every launch
-        if (!cached || !configured[dev]) {
-            PFHE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            if (cached) configured[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((u32)grid), dim3(Cfg::THREADS), lds_bytes, s, data, primes, L, log_n,
-                       total_blocks, lazy ? 1u : 0u, mul, mul_polys);
+    return PFHE_OK;
+}
+
+// every launch of this file: `count` workgroups (none: nothing to do) of kernel KERN on stream s
+template <auto KERN, class... Args>
+int launch(u64 count, u32 threads, size_t lds_bytes, hipStream_t s, Args... args) {
+    if (count == 0) return PFHE_OK;
+    u32 grid = 0;
+    PFHE_TRY(launch_grid(count, &grid));
+    if (lds_bytes > 64 * 1024) PFHE_TRY(allow_dynamic_lds<KERN>(lds_bytes));
+    hipLaunchKernelGGL(KERN, dim3(grid), dim3(threads), lds_bytes, s, args...);
     PFHE_HIP(hipGetLastError());
     return PFHE_OK;
 }
 
+template <class A, int LOGB, bool INV, bool MUL, bool NT>
+constexpr auto block_kernel() {
+    if constexpr (LOGB >= 13) return ntt_block_big_kernel<A, LOGB, INV, MUL, NT>;
+    else if constexpr (LOGB >= 10) return ntt_block_kernel<A, LOGB, INV, MUL, NT>;
+    else return ntt_block_small_kernel<A, LOGB, INV, MUL, NT>;
+}
+
+template <class A, int LOGB, bool INV, bool MUL = false>
+int launch_block(u64 *data, const NttPrime *primes, u32 L, u32 log_n, u64 npolys, bool lazy, hipStream_t s,
+                 const u64 *mul = nullptr, u64 mul_polys = 0) {
+    using Cfg = BlockCfg<LOGB>;
+    const u64 total_blocks = npolys << (log_n - LOGB);
+    const u64 grid = (total_blocks + Cfg::BPW - 1) / Cfg::BPW;
+    constexpr size_t lds_bytes = (size_t)Cfg::BPW * Cfg::LDS_WORDS * sizeof(u64);
+    if constexpr (LOGB >= 11) {
+        if ((npolys << log_n) * sizeof(u64) >= kNtMinBytes)
+            return launch<block_kernel<A, LOGB, INV, MUL, true>()>(grid, Cfg::THREADS, lds_bytes, s, data, primes, L, log_n,
+                                                                  total_blocks, lazy ? 1u : 0u, mul, mul_polys);
+    }
+    return launch<block_kernel<A, LOGB, INV, MUL, false>()>(grid, Cfg::THREADS, lds_bytes, s, data, primes, L, log_n,
+                                                           total_blocks, lazy ? 1u : 0u, mul, mul_polys);
+}
+
 // CUs of the current device (cached per device)
-static int device_cu_count() {
+int device_cu_count() {
     static thread_local int cached[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -825,44 +852,26 @@ static int device_cu_count() {
     return cached[dev];
 }
 
-// persistent single-pass form (ntt_persist_kernel): N = 2^13 / 2^14, at least two polynomials per resident workgroup
-template <class A, int LOGB, bool INV>
-int launch_persist(u64 *data, const NttPrime *primes, u32 L, u64 npolys, bool lazy, hipStream_t s, u64 resident) {
-    using Cfg = BlockCfg<LOGB>;
-    constexpr size_t lds_bytes = (size_t)Cfg::LDS_WORDS * sizeof(u64);
-    void (*kern)(u64 *, const NttPrime *, u32, u64, u32) = ntt_persist_kernel<A, LOGB, INV>;
-    static thread_local bool configured[64] = {};
-    int dev = 0;
-    PFHE_HIP(hipGetDevice(&dev));
-    // (a device index outside the cache sets the attribute on every launch, as polymul_impl does)
-    const bool cached = dev >= 0 && dev < 64;
-    if (!cached || !configured[dev]) {
-        PFHE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds_bytes));
-        if (cached) configured[dev] = true;
-    }
-    // equal shares: every workgroup walks ceil(npolys / grid) polynomials, give or take one
-    const u64 rounds = (npolys + resident - 1) / resident;
-    const u64 grid = (npolys + rounds - 1) / rounds;
-    hipLaunchKernelGGL(kern, dim3((u32)grid), dim3(Cfg::THREADS), lds_bytes, s, data, primes, L, npolys, lazy ? 1u : 0u);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+// Persistent single-pass form of the 64-bit tables (ntt_persist_kernel, ntt_persist_mid_kernel): N = 2^14, from two
+// polynomials per resident workgroup.  (N = 2^13, two workgroups per CU, measures slower in this form: 0.33 vs
+// 0.29-0.32 ms per 8192 polynomials.)
+bool takes_persistent(const NttPlan &plan, int arith, u64 npolys) {
+    return !plan.tiny && plan.n_strided == 0 && plan.block_log == 14 && arith != kArithB32 &&
+           npolys >= 2 * (u64)device_cu_count();
 }
 
-template <class A, int LOGB, bool INV, bool MUL = false>
-int launch_block(u64 *data, const NttPrime *primes, u32 L, u32 log_n, u64 npolys, bool lazy, hipStream_t s,
-                 const u64 *mul = nullptr, u64 mul_polys = 0) {
-    // (N = 2^13, two workgroups per CU, measures slower in this form: 0.33 vs 0.29-0.32 ms per 8192 polynomials)
-    if constexpr (LOGB == 14 && !MUL && !A::kPacked) {
-        const u64 resident = (u64)device_cu_count();
-        if (log_n == LOGB && npolys >= 2 * resident)
-            return launch_persist<A, LOGB, INV>(data, primes, L, npolys, lazy, s, resident);
-    }
-    if constexpr (LOGB >= 11) {
-        if ((npolys << log_n) * sizeof(u64) >= kNtMinBytes)
-            return launch_block_impl<A, LOGB, INV, MUL, true>(data, primes, L, log_n, npolys, lazy, s, mul, mul_polys);
-    }
-    return launch_block_impl<A, LOGB, INV, MUL, false>(data, primes, L, log_n, npolys, lazy, s, mul, mul_polys);
+// its grid, equal shares: every workgroup walks ceil(npolys / grid) polynomials, give or take one
+u64 persistent_grid(u64 npolys) {
+    const u64 resident = (u64)device_cu_count();
+    const u64 rounds = (npolys + resident - 1) / resident;
+    return (npolys + rounds - 1) / rounds;
+}
+
+template <class A, bool INV>
+int launch_persist(u64 *data, const NttPrime *primes, u32 L, u64 npolys, bool lazy, hipStream_t s) {
+    using Cfg = BlockCfg<14>;
+    return launch<ntt_persist_kernel<A, 14, INV>>(persistent_grid(npolys), Cfg::THREADS, (size_t)Cfg::LDS_WORDS * sizeof(u64), s,
+                                                  data, primes, L, npolys, lazy ? 1u : 0u);
 }
 
 template <class A, bool INV, bool MUL = false>
@@ -885,19 +894,11 @@ int launch_strided(u64 *data, const NttPrime *primes, u32 L, u32 log_n, u32 log_
                    hipStream_t s) {
     const u64 total = (npolys << (log_n - K)) >> (VEC == 2 ? 1 : 0);
     const u64 grid = (total + 255) / 256;
-    if (grid == 0) return PFHE_OK;
-    if (grid > 0x7fffffffull) {
-        set_last_error("batch too large for one launch");
-        return PFHE_ERR_BAD_LENGTH;
-    }
     if (K >= 3 && (npolys << log_n) * sizeof(u64) >= kNtMinBytes)
-        hipLaunchKernelGGL((ntt_strided_kernel<A, K, VEC, INV, FINAL, (K >= 3)>), dim3((u32)grid), dim3(256), 0, s, data,
-                           primes, L, log_n, log_s, total, lazy ? 1u : 0u);
-    else
-        hipLaunchKernelGGL((ntt_strided_kernel<A, K, VEC, INV, FINAL>), dim3((u32)grid), dim3(256), 0, s, data, primes,
-                           L, log_n, log_s, total, lazy ? 1u : 0u);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+        return launch<ntt_strided_kernel<A, K, VEC, INV, FINAL, (K >= 3)>>(grid, 256, 0, s, data, primes, L, log_n, log_s,
+                                                                          total, lazy ? 1u : 0u);
+    return launch<ntt_strided_kernel<A, K, VEC, INV, FINAL>>(grid, 256, 0, s, data, primes, L, log_n, log_s, total,
+                                                            lazy ? 1u : 0u);
 }
 
 template <class A, bool INV, bool FINAL>
@@ -916,12 +917,10 @@ int dispatch_strided(int k, u64 *data, const NttPrime *primes, u32 L, u32 log_n,
 
 int launch_tiny(bool inverse, const NttPrime *primes, u32 L, u32 log_n, u64 *data, u64 npolys, bool lazy,
                 hipStream_t s) {
-    if (log_n == 0 || npolys == 0) return PFHE_OK;
-    const dim3 g((u32)((npolys + 255) / 256)), t(256);
-    if (inverse) hipLaunchKernelGGL(ntt_tiny_kernel<true>, g, t, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u);
-    else hipLaunchKernelGGL(ntt_tiny_kernel<false>, g, t, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    if (log_n == 0) return PFHE_OK;
+    const u64 grid = (npolys + 255) / 256;
+    return inverse ? launch<ntt_tiny_kernel<true>>(grid, 256, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u)
+                   : launch<ntt_tiny_kernel<false>>(grid, 256, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u);
 }
 
 // one pass of the plan, in execution order (forward: strided passes then block; inverse: block
@@ -957,6 +956,39 @@ int run_pass(const NttPlan &plan, const NttPrime *primes, u32 L, u32 log_n, u64 
     return dispatch_strided<A, true, false>(k, data, primes, L, log_n, log_s, npolys, false, s);
 }
 
+// pass `index` of `plan`; `persistent`: the batch takes the resident-workgroup kernel for its one pass (takes_persistent)
+int pass_dev(const NttPlan &plan, bool persistent, const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data, u64 npolys,
+             bool inverse, int index, bool lazy, hipStream_t s, const u64 *mul, u64 mul_polys) {
+    if (index < 0 || index >= plan.passes()) return PFHE_ERR_BAD_ARGUMENT;
+    if (plan.tiny) {  // (u32 tables: N <= 16 is served by ntt32_tiny_kernel)
+        if (arith == kArithB32 || mul) return PFHE_ERR_UNSUPPORTED;
+        return launch_tiny(inverse, primes, L, log_n, data, npolys, lazy, s);
+    }
+    if (persistent)
+        return with_arith(arith, [&](auto a) {
+            using A = typename decltype(a)::type;
+            return inverse ? launch_persist<A, true>(data, primes, L, npolys, lazy, s)
+                           : launch_persist<A, false>(data, primes, L, npolys, lazy, s);
+        });
+    return with_arith<true>(arith, [&](auto a) {
+        return run_pass<typename decltype(a)::type>(plan, primes, L, log_n, data, npolys, inverse, index, lazy, s, mul, mul_polys);
+    });
+}
+
+void pass_name(const NttPlan &plan, bool inverse, int index, char *buf, size_t cap) {
+    if (plan.tiny) {
+        std::snprintf(buf, cap, "ntt_tiny_kernel");
+        return;
+    }
+    const int block_at = inverse ? 0 : plan.n_strided;
+    if (index == block_at) {
+        std::snprintf(buf, cap, "ntt_block_kernel<%d,%s>", plan.block_log, inverse ? "inv" : "fwd");
+    } else {
+        const int i = inverse ? plan.n_strided - index : index;
+        std::snprintf(buf, cap, "ntt_strided_kernel<K=%d,%s>", plan.strided[i], inverse ? "inv" : "fwd");
+    }
+}
+
 }  // namespace
 
 static int env_int(const char *name, int lo, int hi) {
@@ -974,14 +1006,13 @@ NttTuning NttTuning::from_env() {
     return t;
 }
 
-
-NttPlan make_ntt_plan(u32 log_n, int arith, const NttTuning &tune) {
+// the plan depends on the ring only (the tuning switches select between FORMS of running it, ntt_form)
+NttPlan make_ntt_plan(u32 log_n, int arith) {
     NttPlan p;
     if (log_n <= 3) {
         p.tiny = true;
         return p;
     }
-    (void)tune;  // the plan depends on the ring only (the tuning switches select between FORMS of running it)
     if (log_n <= kMaxSinglePassLog) {
         p.block_log = (int)log_n;
         return p;
@@ -989,7 +1020,7 @@ NttPlan make_ntt_plan(u32 log_n, int arith, const NttTuning &tune) {
     p.block_log = kTwoPassBlockLog;
     // u32 tables at N = 2^16 (2^15 words): 4 strided stages + blocks of 2^11 words in 128-thread workgroups
     // (8 resident per CU) measured 3.05 ms against 3.24 ms for 3 + 2^12
-    if (arith == 2 /* kArithB32 */ && log_n == 15) p.block_log = 11;
+    if (arith == kArithB32 && log_n == 15) p.block_log = 11;
     int rest = (int)log_n - p.block_log;
     // fewest strided passes with at most 5 stages each, balanced
     int passes = (rest + 4) / 5;
@@ -1001,40 +1032,17 @@ NttPlan make_ntt_plan(u32 log_n, int arith, const NttTuning &tune) {
     return p;
 }
 
-int ntt_num_passes(u32 log_n, int arith, const NttTuning &tune) {
-    const NttPlan plan = make_ntt_plan(log_n, arith, tune);
-    return plan.tiny ? 1 : plan.n_strided + 1;
-}
+int ntt_num_passes(u32 log_n, int arith) { return make_ntt_plan(log_n, arith).passes(); }
 
-void ntt_pass_name(u32 log_n, bool inverse, int index, char *buf, size_t cap, int arith, const NttTuning &tune) {
-    const NttPlan plan = make_ntt_plan(log_n, arith, tune);
-    if (plan.tiny) {
-        std::snprintf(buf, cap, "ntt_tiny_kernel");
-        return;
-    }
-    const int block_at = inverse ? 0 : plan.n_strided;
-    if (index == block_at) {
-        std::snprintf(buf, cap, "ntt_block_kernel<%d,%s>", plan.block_log, inverse ? "inv" : "fwd");
-    } else {
-        const int i = inverse ? plan.n_strided - index : index;
-        std::snprintf(buf, cap, "ntt_strided_kernel<K=%d,%s>", plan.strided[i], inverse ? "inv" : "fwd");
-    }
+void ntt_pass_name(u32 log_n, bool inverse, int index, char *buf, size_t cap, int arith) {
+    pass_name(make_ntt_plan(log_n, arith), inverse, index, buf, cap);
 }
 
 int ntt_pass_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data, u64 npolys, bool inverse, int index,
-                 bool lazy, hipStream_t s, const u64 *mul, u64 mul_polys, const NttTuning &tune) {
-    const NttPlan plan = make_ntt_plan(log_n, arith, tune);
-    if (index < 0 || index >= (plan.tiny ? 1 : plan.n_strided + 1)) return PFHE_ERR_BAD_ARGUMENT;
-    if (arith == kArithB32) {
-        if (plan.tiny) return PFHE_ERR_UNSUPPORTED;  // N <= 16 is served by ntt32_tiny_kernel
-        return run_pass<B32Arith>(plan, primes, L, log_n, data, npolys, inverse, index, lazy, s, mul, mul_polys);
-    }
-    if (plan.tiny) return mul ? PFHE_ERR_UNSUPPORTED : launch_tiny(inverse, primes, L, log_n, data, npolys, lazy, s);
-    if (arith == kArithMont)
-        return run_pass<MontArith>(plan, primes, L, log_n, data, npolys, inverse, index, lazy, s, mul, mul_polys);
-    return arith == kArithPm
-               ? run_pass<PmArith>(plan, primes, L, log_n, data, npolys, inverse, index, lazy, s, mul, mul_polys)
-               : run_pass<ShoupArith>(plan, primes, L, log_n, data, npolys, inverse, index, lazy, s, mul, mul_polys);
+                 bool lazy, hipStream_t s, const u64 *mul, u64 mul_polys) {
+    const NttPlan plan = make_ntt_plan(log_n, arith);
+    return pass_dev(plan, mul == nullptr && takes_persistent(plan, arith, npolys), primes, L, log_n, arith, data, npolys,
+                    inverse, index, lazy, s, mul, mul_polys);
 }
 
 // pipelined form: from 256 MiB of data (2^16-point transforms: 512 limb-polynomials), tiles of 256 MiB = the Infinity
@@ -1043,141 +1051,149 @@ int ntt_pass_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data,
 // 4.72 / 4.64 for 8 tiles with a non-temporal intermediate; 3 GiB: 12 tiles 2.34 ms (8: 2.46); 1.5 GiB: 6 tiles 1.22 ms
 // (12: 1.26); 384 MiB 0.395 -> 0.37 ms against the two plain launches; 96 MiB 0.087 -> 0.096 ms, so smaller batches
 // keep those.
-// (Until round 3 other two-pass rings — N = 2^15, 2^17 — ran their passes tiled on two internal streams; with today's
-// kernels that form measures slower than two full-size launches, 5.08 vs 4.93 ms at 2^15 and 5.13 vs 5.11 ms at 2^17 per
-// 6 GiB, and it is gone: every transform runs on the caller's stream only.)
+// (Other two-pass rings — N = 2^15, 2^17 — measure slower tiled than as two full-size launches, 5.08 vs 4.93 ms at 2^15 and
+// 5.13 vs 5.11 ms at 2^17 per 6 GiB: every transform runs on the caller's stream only.)
 namespace {
 constexpr u64 kPipelinedMinBytes = 256ull << 20;
 constexpr u64 kPipelinedTileBytes = 256ull << 20;
 constexpr int kPipelinedMaxTiles = 64;
+
+// tiles of the pipelined form for this batch, 0 when the batch does not take it
+int pipelined_tiles(const NttPlan &plan, u32 L, u32 log_n, int arith, u64 npolys, bool inverse, bool has_mul,
+                    const NttTuning &tune) {
+    const u64 bytes = (npolys << log_n) * sizeof(u64);
+    const bool b32 = arith == kArithB32;
+    // 64-bit tables: N = 2^16 = 2^4 x 2^12.  u32 tables: 2^15 words = 2^4 x 2^11, the same kernel template with 128-thread
+    // workgroups; 12 288 transforms, same box: INVERSE 2.594 -> 2.462-2.499 ms (6 / 12 tiles), forward 2.512-2.527 ->
+    // 2.472-2.480 ms with the wave-local I/O vectors (120 registers, no scratch).  Both directions take it.
+    const bool shape = log_n == (b32 ? 15u : 16u) && plan.n_strided == 1 && plan.block_log == (b32 ? 11 : 12);
+    if (!(tune.pipelined && shape && (!has_mul || inverse) && npolys % L == 0 &&
+          bytes >= (tune.pipelined_min_mb ? (u64)tune.pipelined_min_mb << 20
+                                           : b32 ? 4 * kPipelinedMinBytes : kPipelinedMinBytes)))
+        return 0;
+    // (u32 tables: tiles of 512 MiB — 6 tiles 2.462 ms, 12 tiles 2.494 ms, 24 tiles 2.586 ms per 3 GiB)
+    const u64 tile_bytes = b32 ? 2 * kPipelinedTileBytes : kPipelinedTileBytes;
+    int pt = tune.pipe_tiles ? tune.pipe_tiles
+                                : (int)std::min<u64>((bytes + tile_bytes / 2) / tile_bytes, (u64)kPipelinedMaxTiles);
+    if (pt < 2) pt = 2;
+    if (pt > kPipelinedMaxTiles) pt = kPipelinedMaxTiles;  // the one cap: PFHE_PIPE_TILES may ask for more
+    if ((u64)pt > npolys / L) pt = (int)(npolys / L);
+    return pt;
+}
+
+// Which form a batch takes: the one decision that transform(), polymul_impl() and the report (ntt_transform_form) share.
+//   kTransform   a plain transform          kInverseMul  the inverse transform of data (*) mul
+//   kPolymul     NTT -> product -> INTT around the middle kernels
+enum class NttOp { kTransform, kInverseMul, kPolymul };
+struct NttForm {
+    enum Kind { kPasses, kPersistent, kPipelined } kind = kPasses;  // kPasses: one launch per pass of the plan
+    int tiles = 0;                                                  // kPipelined: tiles (+ 1 launches; + 2 for kPolymul)
+};
+NttForm ntt_form(const NttPlan &plan, u32 L, u32 log_n, int arith, u64 npolys, bool inverse, NttOp op, const NttTuning &tune) {
+    NttForm f;
+    f.tiles = pipelined_tiles(plan, L, log_n, arith, npolys, inverse, op != NttOp::kTransform, tune);
+    if (f.tiles >= 1) f.kind = NttForm::kPipelined;
+    // (no persistent kernel multiplies in its loads: kInverseMul keeps the block pass)
+    else if (op != NttOp::kInverseMul && takes_persistent(plan, arith, npolys)) f.kind = NttForm::kPersistent;
+    return f;
+}
+
+// Tiles of the pipelined forms: equal shares of whole RNS polynomials (tile weights that ramp up and down again, so that
+// the first and the last launch — one pass's worth of work each — are small, measured no gain).  A per-element
+// multiplicand is tiled like the data; a shared one (one unit of L) is not.
+struct PipeTiles {
+    u64 *data;
+    u64 npolys;
+    const u64 *mul;
+    u64 mul_polys;
+    u32 L, log_n;
+    int block_log, tiles;
+    struct Tile {
+        u64 *ptr = nullptr;
+        u64 blocks = 0;  // blocks of 2^block_log words, = workgroups
+        const u64 *mul = nullptr;
+        u64 mul_polys = 0;
+    };
+    Tile operator[](int k) const {  // out of range: the empty tile
+        Tile t;
+        if (k < 0 || k >= tiles) return t;
+        const u64 units = npolys / L, u0 = units * (u64)k / (u64)tiles, u1 = units * (u64)(k + 1) / (u64)tiles;
+        t.ptr = data + ((u0 * L) << log_n);
+        t.blocks = ((u1 - u0) * L) << (log_n - (u32)block_log);
+        if (mul) {
+            const bool each = mul_polys == npolys;
+            t.mul = each ? mul + ((u0 * L) << log_n) : mul;
+            t.mul_polys = each ? (u1 - u0) * L : mul_polys;
+        }
+        return t;
+    }
+};
 }  // namespace
 
 // the pipelined form of the two-pass transform (ntt_pipe_{fwd,inv}_kernel): tiles + 1 launches on the caller's stream
 template <class A, int LOGB>
 static int transform_pipelined(const NttPrime *primes, u32 L, u64 *data, u64 npolys, bool inverse, bool lazy,
                                hipStream_t s, int tiles, const u64 *mul, u64 mul_polys) {
-    if (tiles > 64) tiles = 64;
-    constexpr u32 log_n = LOGB + 4;
     constexpr size_t lds_bytes = (size_t)BlockCfg<LOGB>::LDS_WORDS * sizeof(u64);
     constexpr u32 threads = BlockCfg<LOGB>::THREADS;
-    const u64 units = npolys / L;
-    // equal tiles of whole RNS polynomials (tile weights that ramp up and down again, so that the first and the last
-    // launch — one pass's worth of work each — are small, measured no gain and are gone)
-    u64 cum[66];
-    for (int k = 0; k <= tiles; ++k) cum[k] = units * (u64)k / (u64)tiles;
+    const PipeTiles split{data, npolys, mul, mul_polys, L, LOGB + 4, LOGB, tiles};
     for (int k = 0; k <= tiles; ++k) {
         // forward: strided pass of tile k, block pass of tile k-1; inverse: block pass of tile k, strided pass of tile k-1
-        const int kb = inverse ? k : k - 1, ks = inverse ? k - 1 : k;
-        u64 *bptr = nullptr, *sptr = nullptr;
-        const u64 *mptr = nullptr;
-        u64 bt = 0, st = 0, mp = 0;
-        if (kb >= 0 && kb < tiles) {
-            const u64 u0 = cum[kb], u1 = cum[kb + 1];
-            bptr = data + ((u0 * L) << log_n);
-            bt = ((u1 - u0) * L) << 4;
-            // a per-element multiplicand is tiled like the data; a shared one (one unit of L) is not
-            if (mul) {
-                mptr = mul_polys == npolys ? mul + ((u0 * L) << log_n) : mul;
-                mp = mul_polys == npolys ? (u1 - u0) * L : mul_polys;
-            }
-        }
-        if (ks >= 0 && ks < tiles) {
-            const u64 u0 = cum[ks], u1 = cum[ks + 1];
-            sptr = data + ((u0 * L) << log_n);
-            st = ((u1 - u0) * L) << 4;
-        }
-        const u64 grid = bt > st ? bt : st;
-        if (grid == 0) continue;
-        if (grid > 0x7fffffffull) {
-            set_last_error("batch too large for one launch");
-            return PFHE_ERR_BAD_LENGTH;
-        }
+        const PipeTiles::Tile b = split[inverse ? k : k - 1], st = split[inverse ? k - 1 : k];
+        const u64 grid = std::max(b.blocks, st.blocks);
         if constexpr (!A::kPacked) {
             if (inverse && mul) {
-                hipLaunchKernelGGL((ntt_pipe_inv_kernel<A, LOGB, true>), dim3((u32)grid), dim3(threads), lds_bytes, s, bptr, bt,
-                                   sptr, st, primes, L, lazy ? 1u : 0u, mptr, mp);
-                PFHE_HIP(hipGetLastError());
+                PFHE_TRY((launch<ntt_pipe_inv_kernel<A, LOGB, true>>(grid, threads, lds_bytes, s, b.ptr, b.blocks, st.ptr, st.blocks,
+                                                                     primes, L, lazy ? 1u : 0u, b.mul, b.mul_polys)));
                 continue;
             }
         }
         if (inverse)
-            hipLaunchKernelGGL((ntt_pipe_inv_kernel<A, LOGB, false>), dim3((u32)grid), dim3(threads), lds_bytes, s, bptr, bt,
-                               sptr, st, primes, L, lazy ? 1u : 0u, mptr, mp);
+            PFHE_TRY((launch<ntt_pipe_inv_kernel<A, LOGB, false>>(grid, threads, lds_bytes, s, b.ptr, b.blocks, st.ptr, st.blocks,
+                                                                  primes, L, lazy ? 1u : 0u, b.mul, b.mul_polys)));
         else
-            hipLaunchKernelGGL((ntt_pipe_fwd_kernel<A, LOGB>), dim3((u32)grid), dim3(threads), lds_bytes, s, bptr, bt, sptr, st,
-                               primes, L, lazy ? 1u : 0u);
-        PFHE_HIP(hipGetLastError());
+            PFHE_TRY((launch<ntt_pipe_fwd_kernel<A, LOGB>>(grid, threads, lds_bytes, s, b.ptr, b.blocks, st.ptr, st.blocks, primes,
+                                                           L, lazy ? 1u : 0u)));
     }
     return PFHE_OK;
 }
 
-// tiles of the pipelined form for this batch, 0 when the batch does not take it
-static int pipelined_tiles(u32 L, u32 log_n, int pm, u64 npolys, bool inverse, bool has_mul, const NttTuning &tune) {
-    const u64 bytes = (npolys << log_n) * sizeof(u64);
-    // 64-bit tables, N = 2^16 = 2^4 x 2^12.  (The u32 tables' 2^15 words = 2^4 x 2^11 fit the same kernel template; measured
-    // 2.858 ms against 2.866-2.874 ms for their two plain launches per 12 288 transforms: not instantiated.)
-    // u32 tables: 2^15 words = 2^4 x 2^11, the same kernel template with 128-thread workgroups.  Round 5, 12 288 transforms,
-    // same box: INVERSE 2.594 -> 2.462-2.499 ms (6 / 12 tiles); forward 2.512-2.527 -> 2.472-2.480 ms once the wave-local
-    // I/O vectors had brought its kernel from 128 registers + 28 bytes of scratch to 120 and none (before that: 2.468 ->
-    // 2.473, not taken).  Both directions take it.
-    const bool shape = (pm != kArithB32 && log_n == 16 && make_ntt_plan(log_n, pm, tune).block_log == 12) ||
-                       (pm == kArithB32 && log_n == 15 &&
-                        make_ntt_plan(log_n, pm, tune).block_log == 11);
-    if (!(tune.pipelined && shape && ntt_num_passes(log_n, pm, tune) == 2 &&
-          (!has_mul || inverse) && npolys % L == 0 &&
-          bytes >= (tune.pipelined_min_mb ? (u64)tune.pipelined_min_mb << 20
-                                           : pm == kArithB32 ? 4 * kPipelinedMinBytes : kPipelinedMinBytes)))
-        return 0;
-    // (u32 tables: tiles of 512 MiB — 6 tiles 2.462 ms, 12 tiles 2.494 ms, 24 tiles 2.586 ms per 3 GiB)
-    const u64 tile_bytes = pm == kArithB32 ? 2 * kPipelinedTileBytes : kPipelinedTileBytes;
-    int pt = tune.pipe_tiles ? tune.pipe_tiles
-                                : (int)std::min<u64>((bytes + tile_bytes / 2) / tile_bytes, (u64)kPipelinedMaxTiles);
-    if (pt < 2) pt = 2;
-    if (pt > kPipelinedMaxTiles) pt = kPipelinedMaxTiles;  // what transform_pipelined runs (its launch count is reported)
-    if ((u64)pt > npolys / L) pt = (int)(npolys / L);
-    return pt;
-}
-
 // how transform() will run a batch: kernel (or form) name and the number of kernel launches
 int ntt_transform_form(u32 L, u32 log_n, int arith, u64 npolys, bool inverse, const NttTuning &tune, char *buf, size_t cap) {
-    const int pt = pipelined_tiles(L, log_n, arith, npolys, inverse, false, tune);
-    if (pt >= 1) {
+    const NttPlan plan = make_ntt_plan(log_n, arith);
+    const NttForm form = ntt_form(plan, L, log_n, arith, npolys, inverse, NttOp::kTransform, tune);
+    if (form.kind == NttForm::kPipelined) {
         std::snprintf(buf, cap, inverse ? "ntt_pipe_inv_kernel" : "ntt_pipe_fwd_kernel");
-        return pt + 1;
+        return form.tiles + 1;
+    }
+    if (form.kind == NttForm::kPersistent) {
+        std::snprintf(buf, cap, "ntt_persist_kernel<14,%s>", inverse ? "inv" : "fwd");
+        return 1;
     }
     // one launch per pass: name them in execution order
-    const NttPlan plan = make_ntt_plan(log_n, arith, tune);
-    const int passes = plan.tiny ? 1 : plan.n_strided + 1;
     size_t at = 0;
     buf[0] = 0;
-    for (int i = 0; i < passes && at + 1 < cap; ++i) {
+    for (int i = 0; i < plan.passes() && at + 1 < cap; ++i) {
         char one[96];
-        ntt_pass_name(log_n, inverse, i, one, sizeof one, arith, tune);
-        if (!plan.tiny && plan.n_strided == 0 && plan.block_log == 14 && arith != kArithB32 &&
-            npolys >= 2 * (u64)device_cu_count())
-            std::snprintf(one, sizeof one, "ntt_persist_kernel<14,%s>", inverse ? "inv" : "fwd");  // launch_block's choice
+        pass_name(plan, inverse, i, one, sizeof one);
         at += (size_t)std::snprintf(buf + at, cap - at, "%s%s", i ? " + " : "", one);
     }
-    return passes;
+    return plan.passes();
 }
 
-static int transform(const NttPrime *primes, u32 L, u32 log_n, int pm, u64 *data, u64 npolys, bool inverse,
+static int transform(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data, u64 npolys, bool inverse,
                      bool lazy, hipStream_t s, const NttTuning &tune, const u64 *mul = nullptr, u64 mul_polys = 0) {
-    const int passes = ntt_num_passes(log_n, pm, tune);
-    {
-        const int pt = pipelined_tiles(L, log_n, pm, npolys, inverse, mul != nullptr, tune);
-        if (pt >= 1 && pm == kArithB32)
-            return transform_pipelined<B32Arith, 11>(primes, L, data, npolys, inverse, lazy, s, pt, mul, mul_polys);
-        if (pt >= 1 && pm == kArithMont)
-            return transform_pipelined<MontArith, 12>(primes, L, data, npolys, inverse, lazy, s, pt, mul, mul_polys);
-        if (pt >= 1)
-            return pm == kArithPm
-                       ? transform_pipelined<PmArith, 12>(primes, L, data, npolys, inverse, lazy, s, pt, mul, mul_polys)
-                       : transform_pipelined<ShoupArith, 12>(primes, L, data, npolys, inverse, lazy, s, pt, mul, mul_polys);
-    }
+    const NttPlan plan = make_ntt_plan(log_n, arith);
+    const NttForm form = ntt_form(plan, L, log_n, arith, npolys, inverse, mul ? NttOp::kInverseMul : NttOp::kTransform, tune);
+    if (form.kind == NttForm::kPipelined)
+        return with_arith<true>(arith, [&](auto a) {
+            using A = typename decltype(a)::type;
+            return transform_pipelined<A, A::kPacked ? 11 : 12>(primes, L, data, npolys, inverse, lazy, s, form.tiles, mul, mul_polys);
+        });
     // one launch per pass on the caller's stream
-    for (int i = 0; i < passes; ++i)
-        PFHE_TRY(ntt_pass_dev(primes, L, log_n, pm, data, npolys, inverse, i, lazy, s, i == 0 ? mul : nullptr, mul_polys, tune));
+    for (int i = 0; i < plan.passes(); ++i)
+        PFHE_TRY(pass_dev(plan, form.kind == NttForm::kPersistent, primes, L, log_n, arith, data, npolys, inverse, i, lazy, s,
+                          i == 0 ? mul : nullptr, mul_polys));
     return PFHE_OK;
 }
 
@@ -1202,7 +1218,7 @@ static int through_dev_two_pass(const NttPlan &plan, const NttPrime *primes, u32
     const u32 log_s = log_n - k;
     const u64 sthreads = (npolys << (log_n - k)) >> (k == 5 ? 0 : 1), sgrid = (sthreads + 255) / 256;  // K = 5: one column per thread
     const u64 blocks = npolys << (log_n - 12);
-    if (sgrid > 0x7fffffffull || blocks > 0x7fffffffull) return PFHE_ERR_UNSUPPORTED;
+    if (sgrid > kMaxGrid || blocks > kMaxGrid) return PFHE_ERR_UNSUPPORTED;
     constexpr size_t lds_bytes = (size_t)BlockCfg<12>::LDS_WORDS * sizeof(u64);
     const auto strided = [&](auto kc, u64 *dst, const u64 *src) {
         constexpr int K = decltype(kc)::value, VEC = K == 5 ? 1 : 2;
@@ -1234,15 +1250,13 @@ static int through_dev_two_pass(const NttPlan &plan, const NttPrime *primes, u32
 int ntt_transform_through_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *io, u64 *scratch, u64 npolys,
                               bool inverse, bool lazy, hipStream_t s, const NttTuning &tune) {
     if (arith == kArithB32) return PFHE_ERR_UNSUPPORTED;
-    const NttPlan plan = make_ntt_plan(log_n, arith, tune);
-    if (plan.tiny || plan.n_strided == 0)
-        return inverse ? ntt_inverse_dev(primes, L, log_n, arith, io, npolys, lazy, s, tune)
-                       : ntt_forward_dev(primes, L, log_n, arith, io, npolys, lazy, s, tune);
+    const NttPlan plan = make_ntt_plan(log_n, arith);
+    if (plan.tiny || plan.n_strided == 0) return transform(primes, L, log_n, arith, io, npolys, inverse, lazy, s, tune);
     if (plan.n_strided != 1 || plan.block_log != 12 || plan.strided[0] < 3 || plan.strided[0] > 5 || scratch == nullptr)
         return PFHE_ERR_UNSUPPORTED;
-    if (arith == kArithMont) return through_dev_two_pass<MontArith>(plan, primes, L, log_n, io, scratch, npolys, inverse, lazy, s);
-    return arith == kArithPm ? through_dev_two_pass<PmArith>(plan, primes, L, log_n, io, scratch, npolys, inverse, lazy, s)
-                             : through_dev_two_pass<ShoupArith>(plan, primes, L, log_n, io, scratch, npolys, inverse, lazy, s);
+    return with_arith(arith, [&](auto a) {
+        return through_dev_two_pass<typename decltype(a)::type>(plan, primes, L, log_n, io, scratch, npolys, inverse, lazy, s);
+    });
 }
 
 int ntt_inverse_mul_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data, u64 npolys, const u64 *mul,
@@ -1252,115 +1266,64 @@ int ntt_inverse_mul_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64
     return transform(primes, L, log_n, arith, data, npolys, true, false, s, tune, mul, mul_polys);
 }
 
+// the middle kernel (block_mid_body) over `np` limb-polynomials of a batch that is `large` or not (kNtMinBytes)
+template <class A, int LOGB>
+static int launch_mid(const NttPrime *primes, u32 L, u32 log_n, u64 *ptr, u64 np, const u64 *mptr, u64 mp, bool large,
+                      hipStream_t s) {
+    using Cfg = BlockCfg<LOGB>;
+    const u64 total_blocks = np << (log_n - LOGB);
+    constexpr size_t lds_bytes = (size_t)Cfg::LDS_WORDS * sizeof(u64);
+    if (!large)
+        return launch<ntt_block_mid_kernel<A, LOGB, false>>(total_blocks, Cfg::THREADS, lds_bytes, s, ptr, primes, L, log_n,
+                                                           total_blocks, mptr, mp);
+    // a per-element multiplicand of a large batch is read once (non-temporal); a shared one stays cacheable
+    if (mp == np)
+        return launch<ntt_block_mid_kernel<A, LOGB, true, true>>(total_blocks, Cfg::THREADS, lds_bytes, s, ptr, primes, L, log_n,
+                                                                total_blocks, mptr, mp);
+    return launch<ntt_block_mid_kernel<A, LOGB, true, false>>(total_blocks, Cfg::THREADS, lds_bytes, s, ptr, primes, L, log_n,
+                                                             total_blocks, mptr, mp);
+}
 
 // NTT -> product -> INTT with the middle kernel (see block_mid_body).  PFHE_ERR_UNSUPPORTED when the shape does not
 // take it (the caller falls back to transform + fused inverse-mul).
 template <class A>
 static int polymul_impl(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data, u64 npolys, const u64 *mul,
                         u64 mul_polys, hipStream_t s, const NttTuning &tune) {
-    const NttPlan plan = make_ntt_plan(log_n, arith, tune);
+    const NttPlan plan = make_ntt_plan(log_n, arith);
     if (plan.tiny || plan.n_strided > 1 || plan.block_log < 10) return PFHE_ERR_UNSUPPORTED;
+    const NttForm form = ntt_form(plan, L, log_n, arith, npolys, true, NttOp::kPolymul, tune);
     const bool large = (npolys << log_n) * sizeof(u64) >= kNtMinBytes;
-    const auto launch_mid = [&](auto logb_c, u64 *ptr, u64 np, const u64 *mptr, u64 mp) -> int {
-        constexpr int LOGB = decltype(logb_c)::value;
-        using Cfg = BlockCfg<LOGB>;
-        const u64 total_blocks = np << (log_n - LOGB);
-        if (total_blocks == 0) return PFHE_OK;
-        if (total_blocks > 0x7fffffffull) {
-            set_last_error("batch too large for one launch");
-            return PFHE_ERR_BAD_LENGTH;
-        }
-        constexpr size_t lds_bytes = (size_t)Cfg::LDS_WORDS * sizeof(u64);
-        // a per-element multiplicand of a large batch is read once (non-temporal); a shared one stays cacheable
-        const int form = !large ? 0 : (mp == np ? 2 : 1);
-        void (*kern)(u64 *, const NttPrime *, u32, u32, u64, const u64 *, u64) =
-            form == 0 ? ntt_block_mid_kernel<A, LOGB, false> : form == 1 ? ntt_block_mid_kernel<A, LOGB, true, false>
-                                                                          : ntt_block_mid_kernel<A, LOGB, true, true>;
-        if (lds_bytes > 64 * 1024) {  // once per device and instantiation
-            static thread_local bool configured[64][3] = {};
-            int dev = 0;
-            PFHE_HIP(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64 || !configured[dev][form]) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute", __FILE__, __LINE__);
-                if (dev >= 0 && dev < 64) configured[dev][form] = true;
-            }
-        }
-        hipLaunchKernelGGL(kern, dim3((u32)total_blocks), dim3(Cfg::THREADS), lds_bytes, s, ptr, primes, L, log_n,
-                           total_blocks, mptr, mp);
-        PFHE_HIP(hipGetLastError());
-        return PFHE_OK;
-    };
-    if (plan.n_strided == 0 && plan.block_log == 14) {
+    if (form.kind == NttForm::kPersistent) {
         // N = 2^14: resident workgroups that prefetch their next polynomial (ntt_persist_mid_kernel)
-        const u64 resident = (u64)device_cu_count();
-        if (npolys >= 2 * resident) {
-            using Cfg = BlockCfg<14>;
-            constexpr size_t lds_bytes = (size_t)Cfg::LDS_WORDS * sizeof(u64);
-            void (*kern)(u64 *, const NttPrime *, u32, u64, const u64 *, u64) = ntt_persist_mid_kernel<A, 14>;
-            static thread_local bool configured[64] = {};
-            int dev = 0;
-            PFHE_HIP(hipGetDevice(&dev));
-            if (dev < 0 || dev >= 64 || !configured[dev]) {
-                PFHE_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)lds_bytes));
-                if (dev >= 0 && dev < 64) configured[dev] = true;
-            }
-            const u64 rounds = (npolys + resident - 1) / resident;
-            const u64 grid = (npolys + rounds - 1) / rounds;
-            hipLaunchKernelGGL(kern, dim3((u32)grid), dim3(Cfg::THREADS), lds_bytes, s, data, primes, L, npolys, mul, mul_polys);
-            PFHE_HIP(hipGetLastError());
-            return PFHE_OK;
-        }
+        using Cfg = BlockCfg<14>;
+        return launch<ntt_persist_mid_kernel<A, 14>>(persistent_grid(npolys), Cfg::THREADS, (size_t)Cfg::LDS_WORDS * sizeof(u64), s,
+                                                     data, primes, L, npolys, mul, mul_polys);
     }
     if (plan.n_strided == 0) {  // single-pass rings: the middle kernel is the whole product
         switch (plan.block_log) {
 #define PFHE_CASE(B) \
-    case B: return launch_mid(std::integral_constant<int, B>{}, data, npolys, mul, mul_polys);
+    case B: return launch_mid<A, B>(primes, L, log_n, data, npolys, mul, mul_polys, large, s);
             PFHE_CASE(10) PFHE_CASE(11) PFHE_CASE(12) PFHE_CASE(13) PFHE_CASE(14)
 #undef PFHE_CASE
         }
         return PFHE_ERR_UNSUPPORTED;
     }
     if (plan.block_log != 12) return PFHE_ERR_UNSUPPORTED;
-    const int pt = pipelined_tiles(L, log_n, arith, npolys, true, true, tune);
-    if (pt >= 1) {
+    if (form.kind == NttForm::kPipelined) {
         constexpr size_t lds_bytes = (size_t)BlockCfg<12>::LDS_WORDS * sizeof(u64);
-        const int tiles = pt > kPipelinedMaxTiles ? kPipelinedMaxTiles : pt;
-        const u64 units = npolys / L;
-        for (int k = 0; k <= tiles + 1; ++k) {
+        const PipeTiles split{data, npolys, mul, mul_polys, L, log_n, 12, form.tiles};
+        for (int k = 0; k <= form.tiles + 1; ++k) {
             // launch k: forward strided pass of tile k, middle kernel on tile k-1, inverse strided pass of tile k-2
-            u64 *ptr[3] = {nullptr, nullptr, nullptr};
-            u64 tot[3] = {0, 0, 0};
-            const u64 *mptr = nullptr;
-            u64 mp = 0;
-            for (int role = 0; role < 3; ++role) {
-                const int kt = k - role;
-                if (kt < 0 || kt >= tiles) continue;
-                const u64 u0 = units * (u64)kt / (u64)tiles, u1 = units * (u64)(kt + 1) / (u64)tiles;
-                ptr[role] = data + ((u0 * L) << log_n);
-                tot[role] = ((u1 - u0) * L) << 4;
-                if (role == 1) {  // a per-element multiplicand is tiled like the data; a shared one (one unit of L) is not
-                    mptr = mul_polys == npolys ? mul + ((u0 * L) << log_n) : mul;
-                    mp = mul_polys == npolys ? (u1 - u0) * L : mul_polys;
-                }
-            }
-            const u64 grid = std::max(tot[0], std::max(tot[1], tot[2]));
-            if (grid == 0) continue;
-            if (grid > 0x7fffffffull) {
-                set_last_error("batch too large for one launch");
-                return PFHE_ERR_BAD_LENGTH;
-            }
-            hipLaunchKernelGGL((ntt_pipe_mid_kernel<A, 12>), dim3((u32)grid), dim3(BlockCfg<12>::THREADS), lds_bytes, s, ptr[1],
-                               tot[1], ptr[0], tot[0], ptr[2], tot[2], primes, L, mptr, mp);
-            PFHE_HIP(hipGetLastError());
+            const PipeTiles::Tile f = split[k], m = split[k - 1], i = split[k - 2];
+            PFHE_TRY((launch<ntt_pipe_mid_kernel<A, 12>>(std::max(f.blocks, std::max(m.blocks, i.blocks)), BlockCfg<12>::THREADS,
+                                                         lds_bytes, s, m.ptr, m.blocks, f.ptr, f.blocks, i.ptr, i.blocks, primes, L,
+                                                         m.mul, m.mul_polys)));
         }
         return PFHE_OK;
     }
-    PFHE_TRY(ntt_pass_dev(primes, L, log_n, arith, data, npolys, false, 0, false, s, nullptr, 0, tune));
-    PFHE_TRY(launch_mid(std::integral_constant<int, 12>{}, data, npolys, mul, mul_polys));
-    return ntt_pass_dev(primes, L, log_n, arith, data, npolys, true, 1, false, s, nullptr, 0, tune);
+    PFHE_TRY(pass_dev(plan, false, primes, L, log_n, arith, data, npolys, false, 0, false, s, nullptr, 0));
+    PFHE_TRY((launch_mid<A, 12>(primes, L, log_n, data, npolys, mul, mul_polys, large, s)));
+    return pass_dev(plan, false, primes, L, log_n, arith, data, npolys, true, 1, false, s, nullptr, 0);
 }
 
 int ntt_polymul_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data, u64 npolys, const u64 *mul,
@@ -1369,9 +1332,9 @@ int ntt_polymul_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *da
         return PFHE_ERR_BAD_ARGUMENT;
     if (arith == kArithB32) return PFHE_ERR_UNSUPPORTED;
     if (npolys == 0) return PFHE_OK;
-    if (arith == kArithMont) return polymul_impl<MontArith>(primes, L, log_n, arith, data, npolys, mul, mul_polys, s, tune);
-    return arith == kArithPm ? polymul_impl<PmArith>(primes, L, log_n, arith, data, npolys, mul, mul_polys, s, tune)
-                             : polymul_impl<ShoupArith>(primes, L, log_n, arith, data, npolys, mul, mul_polys, s, tune);
+    return with_arith(arith, [&](auto a) {
+        return polymul_impl<typename decltype(a)::type>(primes, L, log_n, arith, data, npolys, mul, mul_polys, s, tune);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1431,11 +1394,9 @@ int ntt32_transform_dev(const NttPrime *primes, u32 L, u32 log_n, u32 *data, u64
                         hipStream_t s, const NttTuning &tune) {
     if (log_n == 0 || npolys == 0) return PFHE_OK;  // N = 1: the reference's loops do not execute
     if (log_n <= 4) {
-        const dim3 g((u32)((npolys + 255) / 256)), t(256);
-        if (inverse) hipLaunchKernelGGL(ntt32_tiny_kernel<true>, g, t, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u);
-        else hipLaunchKernelGGL(ntt32_tiny_kernel<false>, g, t, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u);
-        PFHE_HIP(hipGetLastError());
-        return PFHE_OK;
+        const u64 grid = (npolys + 255) / 256;
+        return inverse ? launch<ntt32_tiny_kernel<true>>(grid, 256, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u)
+                       : launch<ntt32_tiny_kernel<false>>(grid, 256, 0, s, data, primes, L, log_n, npolys, lazy ? 1u : 0u);
     }
     return transform(primes, L, log_n - 1, kArithB32, reinterpret_cast<u64 *>(data), npolys, inverse, lazy, s, tune);
 }

@@ -20,6 +20,7 @@ struct NttPlan {
     int n_strided = 0;
     int strided[4] = {0, 0, 0, 0};  // stages per strided pass, in forward order
     int block_log = 0;
+    int passes() const { return tiny ? 1 : n_strided + 1; }  // one launch each
 };
 
 // Tuning switches of the transforms.  The PFHE_* environment variables are read ONCE, when a table handle is
@@ -31,7 +32,7 @@ struct NttTuning {
     int pipelined_min_mb = 0;  // PFHE_PIPELINED_MIN_MB: smallest batch (MiB of data) that takes the pipelined form (0: built-in default)
     static NttTuning from_env();
 };
-NttPlan make_ntt_plan(u32 log_n, int arith = 0, const NttTuning &tune = NttTuning());  // arith: see kArith* below
+NttPlan make_ntt_plan(u32 log_n, int arith = 0);  // the plan depends on the ring only; arith: see kArith* below
 
 // `arith` selects the arithmetic policy: kArithShoup (any q < 2^62), kArithMont (every prime below 2^61: the
 // transforms of generic primes, NttPrime::fwd_m), kArithPm (every prime of the
@@ -67,14 +68,37 @@ int ntt_polymul_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *da
 int ntt32_transform_dev(const NttPrime *primes, u32 L, u32 log_n, u32 *data, u64 npolys, bool inverse, bool lazy,
                         hipStream_t s, const NttTuning &tune = NttTuning());
 
-int ntt_num_passes(u32 log_n, int arith = 0, const NttTuning &tune = NttTuning());
-void ntt_pass_name(u32 log_n, bool inverse, int index, char *buf, size_t cap, int arith = 0,
-                   const NttTuning &tune = NttTuning());
+int ntt_num_passes(u32 log_n, int arith = 0);
+void ntt_pass_name(u32 log_n, bool inverse, int index, char *buf, size_t cap, int arith = 0);
 int ntt_pass_dev(const NttPrime *primes, u32 L, u32 log_n, int arith, u64 *data, u64 npolys, bool inverse,
-                 int index, bool lazy, hipStream_t s, const u64 *mul = nullptr, u64 mul_polys = 0,
-                 const NttTuning &tune = NttTuning());
+                 int index, bool lazy, hipStream_t s, const u64 *mul = nullptr, u64 mul_polys = 0);
+
+// grid of a launch of `count` workgroups; PFHE_ERR_BAD_LENGTH (with the error text) beyond what one launch takes
+constexpr u64 kMaxGrid = 0x7fffffffull;
+int launch_grid(u64 count, u32 *grid);
 
 #if defined(__HIPCC__)
+
+// The one place where a runtime `arith` becomes a policy type: f(ArithTag<A>{}), called as
+//   with_arith(arith, [&](auto a) { using A = typename decltype(a)::type; ... })
+// The 64-bit callers (B32 = false) instantiate the three 64-bit policies only: they reject kArithB32 before they come
+// here, or are reached from 64-bit tables alone.
+struct ShoupArith;
+struct PmArith;
+struct MontArith;
+struct B32Arith;
+template <class A>
+struct ArithTag {
+    using type = A;
+};
+template <bool B32 = false, class F>
+inline int with_arith(int arith, F &&f) {
+    if constexpr (B32) {
+        if (arith == kArithB32) return f(ArithTag<B32Arith>{});
+    }
+    if (arith == kArithMont) return f(ArithTag<MontArith>{});
+    return arith == kArithPm ? f(ArithTag<PmArith>{}) : f(ArithTag<ShoupArith>{});
+}
 
 // Wave-local LDS exchanges without a workgroup barrier, readfirstlane'd twiddle indices and the 64-bit carry masks
 // of the inline asm all assume 64-lane wavefronts.

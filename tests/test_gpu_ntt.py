@@ -853,3 +853,56 @@ def test_fused_polymul_contract_canonical_multiplicand_at_its_extremes(pf, orc, 
                 x = to_dev(data.copy())
                 d.mul_dcrt_polynomial_dev(x, to_dev(m))
                 assert np.array_equal(to_host(x), ref)
+
+
+# One prime per arithmetic policy, each = 1 mod 2^21; the second of a pair = 1 mod 2^23 (for N = 2^22).
+MULTIPASS_PRIMES = {
+    "pm": (2305843009211596801, 2305843009196916737),     # 2^61 - 2097151, 2^61 - 16777215
+    "mont": (936748722539200513, 936748722878939137),     # 60 bits, generic
+    "shoup": (3458764513883455489, None),                 # 62 bits: above Montgomery's 2^61
+}
+MULTIPASS_CASES = [(p, n) for p in ("pm", "mont", "shoup") for n in (18, 19, 20)] + [("pm", 22), ("mont", 22)]
+MULTIPASS_STRIDED = {18: (3, 3), 19: (4, 3), 20: (4, 4), 22: (5, 5)}
+
+
+@pytest.mark.parametrize("policy,log_n", MULTIPASS_CASES)
+def test_two_strided_passes_match_oracle(pf, orc, policy, log_n):
+    """N >= 2^18: two strided passes above blocks of 2^12 (2^18 -> 3+3, 2^19 -> 4+3, 2^20 -> 4+4, 2^22 -> 5+5), the only
+    plans whose pass order, strides and FINAL instantiations differ between the two strided launches.  Device path
+    against the oracle with the assertions of test_forward_inverse_match_oracle; the launch plan asserted literally."""
+    q = MULTIPASS_PRIMES[policy][1 if log_n == 22 else 0]
+    assert max_log(q) >= log_n
+    rng = np.random.default_rng(100 * log_n + len(policy))
+    n = 1 << log_n
+    batch = 2 if log_n == 18 else 1
+    d, o = pf.U64DcrtTable(log_n, [q]), orc.U64NttTable(log_n, q)
+    k0, k1 = MULTIPASS_STRIDED[log_n]
+    assert d.transform_form(batch * n) == (
+        f"ntt_strided_kernel<K={k0},fwd> + ntt_strided_kernel<K={k1},fwd> + ntt_block_kernel<12,fwd>", 3)
+    assert d.transform_form(batch * n, inverse=True) == (
+        f"ntt_block_kernel<12,inv> + ntt_strided_kernel<K={k1},inv> + ntt_strided_kernel<K={k0},inv>", 3)
+    a = rand_mod(rng, q, n * batch)
+    a[:4] = [0, q - 1, 1, q // 2]
+    ref = a.copy(); o.transform_slice(ref)
+    x = to_dev(a)
+    d.transform_dev(x)
+    assert np.array_equal(to_host(x), ref)
+    d.inverse_transform_dev(x)
+    assert np.array_equal(to_host(x), a)
+    lz = to_dev(a); d.transform_dev(lz, lazy=True)
+    lz = to_host(lz)
+    assert lz.max() < 4 * q and np.array_equal(lz % np.uint64(q), ref)
+    lzi = to_dev(ref); d.inverse_transform_dev(lzi, lazy=True)
+    lzi = to_host(lzi)
+    assert lzi.max() < 2 * q and np.array_equal(lzi % np.uint64(q), a)
+    if log_n == 18:
+        # host slices: the zero-copy form covers one strided pass only, so this plan takes the copying one
+        t = pf.U64NttTable(log_n, q)
+        got = a.copy(); t.transform_slice(got)
+        assert np.array_equal(got, ref)
+        t.inverse_transform_slice(got)
+        assert np.array_equal(got, a)
+        lz = a.copy(); t.lazy_transform_slice(lz)
+        assert lz.max() < 4 * q and np.array_equal(lz % np.uint64(q), ref)
+        lzi = ref.copy(); t.lazy_inverse_transform_slice(lzi)
+        assert lzi.max() < 2 * q and np.array_equal(lzi % np.uint64(q), a)

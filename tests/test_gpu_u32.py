@@ -48,6 +48,7 @@ def test_errors(pf):
     (0, 17, 3), (1, 17, 5), (2, 17, 4), (3, Q27, 7), (4, Q27, 3), (5, Q27, 9), (6, Q30[0], 1), (7, Q27, 33),
     (8, Q29, 5), (9, Q27, 2), (10, Q27, 4), (11, Q30[1], 3), (12, Q30[2], 3), (13, Q30[0], 2), (14, Q30[0], 2),
     (15, Q30[1], 2), (16, Q30[0], 3), (17, Q27, 2), (18, Q27, 1),
+    (19, 1012924417, 1), (20, 1012924417, 1),
 ])
 def test_u32_ntt_matches_oracle(pf, orc, log_n, q, batch):
     rng = np.random.default_rng(log_n * 13 + batch)
@@ -231,3 +232,14 @@ def test_u32_pipelined_inverse_equals_plain_passes(pf, orc, batch, tiles, monkey
     h = to_host32(lz[:L * n]).astype(np.uint64)
     qs = np.repeat(np.array(Q30, np.uint64), n)
     assert (h < 2 * qs).all() and np.array_equal(h % qs, to_host32(orig[:L * n]).astype(np.uint64))
+
+
+@pytest.mark.parametrize("log_n,k0,k1", [(19, 3, 3), (20, 4, 3)])
+def test_u32_two_strided_passes_form(pf, log_n, k0, k1):
+    """2^18 and 2^19 words: the first u32 sizes with two strided passes (their words are checked against the oracle by the
+    (19, ...) and (20, ...) rows of test_u32_ntt_matches_oracle)."""
+    d = pf.U32DcrtTable(log_n, [1012924417])
+    assert d.transform_form(1 << log_n) == (
+        f"u32:ntt_strided_kernel<K={k0},fwd> + ntt_strided_kernel<K={k1},fwd> + ntt_block_kernel<12,fwd>", 3)
+    assert d.transform_form(1 << log_n, inverse=True) == (
+        f"u32:ntt_block_kernel<12,inv> + ntt_strided_kernel<K={k1},inv> + ntt_strided_kernel<K={k0},inv>", 3)
