@@ -901,6 +901,58 @@ int pfhe_tfhe32_external_product_to_dev(pfhe_tfhe32_plan *plan, const uint32_t *
 int pfhe_tfhe32_external_product_to(pfhe_tfhe32_plan *plan, const uint32_t *input, size_t len_input, const double *key,
                                     size_t len_key, uint32_t *output, size_t len_output);
 
+/* Batched blind rotation over the TFHE product — the CMUX loop of a programmable bootstrap on torus words.  For every step
+ * i = 0 .. n_steps-1 in order, and every ciphertext e of the batch:
+ *   D     = X^{exps[e*n_steps+i]} * ACC_e - ACC_e    the monic-monomial rotation of CrtGlwe::mul_monic_monomial_assign
+ *                                                    (glwe/crt.rs:76-114) on torus words, sub_element_wise_assign
+ *                                                    (macros/mod.rs:438), wrapping modulo 2^BITS
+ *   E     = external_product_to(D, BSK_i)            tfhe/external_product.rs:36-93, exactly as
+ *                                                    pfhe_tfhe*_external_product_to_dev
+ *   ACC_e = ACC_e + E                                add_element_wise_assign (macros/mod.rs:410), wrapping
+ * acc: batch GLWE ciphertexts ((k+1) x N torus words each), read and written in place; bsk: n_steps Fourier GGSW keys end
+ * to end in the reference's layout ((k+1) x ell x (k+1) x N complex values each; len_bsk counts complex values), shared by
+ * the batch; exps: batch x n_steps uint32, ciphertext-major.  PFHE_ERR_BAD_LENGTH unless both lengths divide evenly and
+ * len_exps == batch * n_steps; n_steps == 0 is a no-op.  Results are deterministic and do not depend on the batch size or
+ * the chunk.
+ * create takes the arguments of pfhe_tfhe_plan_create and checks them in the same order (the basis's assert!s first, then
+ * PFHE_ERR_UNSUPPORTED for k > 64, then the table).  The handle borrows `fft` and owns a product plan; everything is
+ * allocated here, a call only queues work on `stream` (no allocation, no host synchronisation), so one whole rotation can
+ * be captured into a HIP graph.  One holder at a time (PFHE_ERR_BUSY), successive calls on different streams ordered.
+ * k = 1 with N <= 2^11 runs ONE launch per chunk: a workgroup per ciphertext keeps ACC in LDS across all steps and runs
+ * the fused product's own arithmetic per step (PFHE_DISABLE_FUSED_TFHE_BLINDROT, read here, selects the other form).
+ * Every other shape runs the product's launches plus one glue launch per step and owns three buffers of chunk
+ * ciphertexts (chunk 0: the plan's chunk, capped at about 256 MiB of glue buffers). */
+typedef struct pfhe_tfhe_blindrot pfhe_tfhe_blindrot;
+typedef struct pfhe_tfhe32_blindrot pfhe_tfhe32_blindrot;
+int pfhe_tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                              size_t chunk, pfhe_tfhe_blindrot **out);
+void pfhe_tfhe_blindrot_destroy(pfhe_tfhe_blindrot *h);
+int pfhe_tfhe_blindrot_in_use(const pfhe_tfhe_blindrot *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_blindrot_scratch_bytes(const pfhe_tfhe_blindrot *h);
+/* Device form: every exponent is taken modulo 2N on the device. */
+int pfhe_tfhe_blindrot_rotate_dev(pfhe_tfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev,
+                                  size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream);
+/* Host form: PFHE_ERR_BAD_ARGUMENT for any exponent of 2N or more (the reference's debug_assert!(r < 2N)). */
+int pfhe_tfhe_blindrot_rotate(pfhe_tfhe_blindrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                              const uint32_t *exps, size_t len_exps);
+int pfhe_tfhe32_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t chunk, pfhe_tfhe32_blindrot **out);
+void pfhe_tfhe32_blindrot_destroy(pfhe_tfhe32_blindrot *h);
+int pfhe_tfhe32_blindrot_in_use(const pfhe_tfhe32_blindrot *h);
+size_t pfhe_tfhe32_blindrot_scratch_bytes(const pfhe_tfhe32_blindrot *h);
+int pfhe_tfhe32_blindrot_rotate_dev(pfhe_tfhe32_blindrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev,
+                                    size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream);
+int pfhe_tfhe32_blindrot_rotate(pfhe_tfhe32_blindrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                                const uint32_t *exps, size_t len_exps);
+/* X^{exps[e]} * element e for a batch of elements of `polys_per_exp` torus polynomials each (len = elements *
+ * polys_per_exp * N words; exponents taken modulo 2N) — the per-ciphertext X^{-b_e} * TV that starts a bootstrap; the torus
+ * counterpart of pfhe_dcrt_mul_monomial_each_to_dev (CrtGlwe::mul_monic_monomial_assign, glwe/crt.rs:76-114).  out_dev must
+ * not overlap a_dev. */
+int pfhe_tfhe_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint64_t *a_dev, size_t len, const uint32_t *exps_dev,
+                                       size_t polys_per_exp, uint64_t *out_dev, void *stream);
+int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_dev, size_t len, const uint32_t *exps_dev,
+                                         size_t polys_per_exp, uint32_t *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

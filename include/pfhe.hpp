@@ -665,4 +665,73 @@ inline void external_product_to_dev(const uint32_t *input_dev, size_t len_input,
                                               len_output, stream));
 }
 
+// The batched blind rotation over the TFHE product (pfhe_tfhe_blindrot_*): for every step i and ciphertext e,
+// ACC_e += external_product_to(X^{exps[e*n_steps+i]} * ACC_e - ACC_e, BSK_i) on torus words (the rotation of
+// CrtGlwe::mul_monic_monomial_assign, glwe/crt.rs:76-114; external_product_to, tfhe/external_product.rs:36-93).  Takes
+// TfheFftContext's arguments, owns its product plan and glue buffers; one holder at a time.
+class TfheBlindRotate {
+  public:
+    TfheBlindRotate(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length = 0,
+                    size_t chunk = 0) {
+        check(pfhe_tfhe_blindrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfheBlindRotate() { pfhe_tfhe_blindrot_destroy(h_); }
+    TfheBlindRotate(const TfheBlindRotate &) = delete;
+    TfheBlindRotate &operator=(const TfheBlindRotate &) = delete;
+    pfhe_tfhe_blindrot *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_blindrot_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_blindrot_scratch_bytes(h_); }
+    // host slices; every exponent below 2N
+    void rotate(uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps) {
+        check(pfhe_tfhe_blindrot_rotate(h_, acc, len_acc, bsk, len_bsk, exps, len_exps));
+    }
+    // device buffers, queued on `stream` (exponents taken modulo 2N)
+    void rotate_dev(uint64_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk, const uint32_t *exps_dev,
+                    size_t len_exps, void *stream = nullptr) {
+        check(pfhe_tfhe_blindrot_rotate_dev(h_, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream));
+    }
+
+  private:
+    pfhe_tfhe_blindrot *h_ = nullptr;
+};
+
+// the same over the u32 torus
+class TfheBlindRotate32 {
+  public:
+    TfheBlindRotate32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length = 0,
+                      size_t chunk = 0) {
+        check(pfhe_tfhe32_blindrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfheBlindRotate32() { pfhe_tfhe32_blindrot_destroy(h_); }
+    TfheBlindRotate32(const TfheBlindRotate32 &) = delete;
+    TfheBlindRotate32 &operator=(const TfheBlindRotate32 &) = delete;
+    pfhe_tfhe32_blindrot *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_blindrot_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_blindrot_scratch_bytes(h_); }
+    // host slices; every exponent below 2N
+    void rotate(uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps) {
+        check(pfhe_tfhe32_blindrot_rotate(h_, acc, len_acc, bsk, len_bsk, exps, len_exps));
+    }
+    // device buffers, queued on `stream` (exponents taken modulo 2N)
+    void rotate_dev(uint32_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk, const uint32_t *exps_dev,
+                    size_t len_exps, void *stream = nullptr) {
+        check(pfhe_tfhe32_blindrot_rotate_dev(h_, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream));
+    }
+
+  private:
+    pfhe_tfhe32_blindrot *h_ = nullptr;
+};
+
+// X^{exps[e]} * element e for elements of polys_per_exp torus polynomials (the X^{-b_e} * TV that starts a bootstrap)
+inline void mul_monomial_each_to_dev(const FullComplex64FftTable &fft, const uint64_t *a_dev, size_t len,
+                                     const uint32_t *exps_dev, size_t polys_per_exp, uint64_t *out_dev,
+                                     void *stream = nullptr) {
+    check(pfhe_tfhe_mul_monomial_each_to_dev(fft.handle(), a_dev, len, exps_dev, polys_per_exp, out_dev, stream));
+}
+inline void mul_monomial_each_to_dev(const FullComplex64FftTable &fft, const uint32_t *a_dev, size_t len,
+                                     const uint32_t *exps_dev, size_t polys_per_exp, uint32_t *out_dev,
+                                     void *stream = nullptr) {
+    check(pfhe_tfhe32_mul_monomial_each_to_dev(fft.handle(), a_dev, len, exps_dev, polys_per_exp, out_dev, stream));
+}
+
 }  // namespace pfhe

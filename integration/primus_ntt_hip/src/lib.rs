@@ -9,7 +9,8 @@
 //! runs on the GPU unchanged (one host->device->host round trip per `&mut [T]` call), and adds the
 //! batched, device-resident external product as [`HipExternalProduct`].  `FullComplex64FftTable`
 //! (crates/primus_fft/src/complex64/table.rs:47) -> [`HipFftTable`] behind `FftTable`, and the TFHE product in the
-//! Fourier domain as [`HipTfheExternalProduct`] / [`HipTfheExternalProduct32`].
+//! Fourier domain as [`HipTfheExternalProduct`] / [`HipTfheExternalProduct32`], with the blind rotation over it as
+//! [`HipTfheBlindRotate`] / [`HipTfheBlindRotate32`].
 mod ffi;
 
 use core::ffi::{c_int, CStr};
@@ -655,5 +656,63 @@ impl HipTfheExternalProduct32 {
 impl Drop for HipTfheExternalProduct32 {
     fn drop(&mut self) {
         unsafe { ffi::pfhe_tfhe32_plan_destroy(self.plan) }
+    }
+}
+
+/// The batched blind rotation over the TFHE product: for every step i and ciphertext e,
+/// `ACC_e += external_product_to(X^{exps[e*n_steps+i]} * ACC_e - ACC_e, BSK_i)` on u64-torus words, the whole loop on the
+/// device (one launch per chunk for k = 1, N <= 2^11).  Takes [`HipTfheExternalProduct`]'s arguments and owns its plan.
+/// [`HipTfheBlindRotate32`]: the u32 torus.
+pub struct HipTfheBlindRotate {
+    h: *mut ffi::pfhe_tfhe_blindrot,
+}
+impl HipTfheBlindRotate {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize) -> Result<Self, c_int> {
+        let mut h = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe_blindrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, 0, &mut h) } {
+            ffi::PFHE_OK => Ok(Self { h }),
+            e => Err(e),
+        }
+    }
+    /// `acc_dev`: batch x (k+1) x N words, updated in place; `bsk_dev`: n_steps x (k+1) x ell x (k+1) x N complex values
+    /// (`len_bsk` counts them); `exps_dev`: batch x n_steps exponents, taken modulo 2N
+    pub unsafe fn rotate_dev(&mut self, acc_dev: *mut u64, len_acc: usize, bsk_dev: *const f64, len_bsk: usize,
+                             exps_dev: *const u32, len_exps: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe_blindrot_rotate_dev(self.h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheBlindRotate {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe_blindrot_destroy(self.h) }
+    }
+}
+
+pub struct HipTfheBlindRotate32 {
+    h: *mut ffi::pfhe_tfhe32_blindrot,
+}
+impl HipTfheBlindRotate32 {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize) -> Result<Self, c_int> {
+        let mut h = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe32_blindrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, 0, &mut h) } {
+            ffi::PFHE_OK => Ok(Self { h }),
+            e => Err(e),
+        }
+    }
+    /// `acc_dev`: batch x (k+1) x N words, updated in place; `bsk_dev`: n_steps x (k+1) x ell x (k+1) x N complex values
+    /// (`len_bsk` counts them); `exps_dev`: batch x n_steps exponents, taken modulo 2N
+    pub unsafe fn rotate_dev(&mut self, acc_dev: *mut u32, len_acc: usize, bsk_dev: *const f64, len_bsk: usize,
+                             exps_dev: *const u32, len_exps: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe32_blindrot_rotate_dev(self.h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheBlindRotate32 {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe32_blindrot_destroy(self.h) }
     }
 }

@@ -12,8 +12,9 @@ from .lattice import (BlindRotateContext, BlindRotateContext32, blind_rotate, bl
                       add_dcrt_glev_mul_crt_poly_assign_dev, glev_mul_big_uint_poly_to_dev, glev_mul_crt_poly_to_dev,
                       mul_dcrt_ggsw_to, mul_dcrt_ggsw_to_dev, profile_mul_dcrt_ggsw_to_dev)
 from .ntt import NttError, U32DcrtTable, U32NttTable, U64DcrtTable, U64NttTable  # noqa: F401
-from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheFftContext, tfhe_external_product_to,  # noqa: F401
-                   tfhe_external_product_to_dev, write_fourier_form)
+from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateContext, TfheFftContext,  # noqa: F401
+                   tfhe_blind_rotate, tfhe_blind_rotate_dev, tfhe_external_product_to, tfhe_external_product_to_dev,
+                   write_fourier_form)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -23,4 +24,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "add_dcrt_glev_mul_crt_poly_assign_dev", "glev_mul_crt_poly_to_dev", "add_dcrt_glev_mul_big_uint_poly_assign_dev",
            "glev_mul_big_uint_poly_to_dev", "BlindRotateContext", "BlindRotateContext32", "blind_rotate", "blind_rotate_dev",
            "FullComplex64FftTable", "ApproxSignedBasis", "TfheFftContext", "tfhe_external_product_to",
-           "tfhe_external_product_to_dev", "write_fourier_form", "build", "lib", "library_path", "status_string"]
+           "tfhe_external_product_to_dev", "write_fourier_form", "TfheBlindRotateContext", "tfhe_blind_rotate",
+           "tfhe_blind_rotate_dev", "build", "lib", "library_path", "status_string"]

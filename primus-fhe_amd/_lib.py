@@ -187,6 +187,14 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "plan_scratch_bytes", sz, vp)
         sig(tp + "external_product_to_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
         sig(tp + "external_product_to", ci, vp, vp, sz, f64p, sz, vp, sz)
+        br = tp + "blindrot_"                        # batched blind rotation over the TFHE product
+        sig(br + "create", ci, vp, sz, u32, sz, sz, C.POINTER(vp))
+        sig(br + "destroy", None, vp)
+        sig(br + "in_use", ci, vp)
+        sig(br + "scratch_bytes", sz, vp)
+        sig(br + "rotate_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
+        sig(br + "rotate", ci, vp, vp, sz, f64p, sz, vp, sz)
+        sig(tp + "mul_monomial_each_to_dev", ci, vp, vp, sz, vp, sz, vp, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)
     sig("pfhe_dcrt_transform_num_passes", ci, vp)

@@ -22,14 +22,21 @@
 //   general (every other shape): key Hermitian part, digit transforms, one multiply-accumulate kernel and the batched
 //            inverse over plan-owned scratch.
 // Summation order is fixed (rows, then levels); no atomics: results do not depend on batch size or chunking.
+//
+// The blind rotation over the product (pfhe_tfhe{,32}_blindrot_*): per step and ciphertext, ACC += (X^r ACC - ACC) (x) BSK_i.
+//   whole loop (the fused shape): one launch per chunk, a workgroup per ciphertext, ACC in LDS from the first step to the
+//            last, the fused product's own device code per step;
+//   per step  (every other shape, or PFHE_DISABLE_FUSED_TFHE_BLINDROT): the product's launches plus one glue launch.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstdint>
 #include <memory>
 #include <type_traits>
 #include <vector>
 
 #include "pfhe_capi_internal.hpp"
+#include "pfhe_fft_device.hpp"
 #include "pfhe_plan_guard.hpp"
 #include "pfhe_staging.hpp"
 
@@ -69,108 +76,34 @@ struct TfhePlanCore {
 struct pfhe_tfhe_plan : TfhePlanCore<u64> {};
 struct pfhe_tfhe32_plan : TfhePlanCore<u32> {};
 
+// The blind rotation over the TFHE product: owns a product plan and, in the per-step form, three glue buffers of chunk
+// ciphertexts (D, E and the second accumulator of the ping-pong), all allocated at creation.
+template <class P, class W>
+struct TfheBlindRotCore {
+    P *plan = nullptr;  // owned
+    PlanGuard guard;    // one holder at a time and cross-stream ordering of successive calls, as the plan
+    bool whole_loop = false;
+    size_t chunk = 1;
+    W *d = nullptr, *e = nullptr, *ping = nullptr;  // per-step form only: chunk * (k+1) * N words each
+    size_t glwe = 0, key_len = 0, glue_bytes = 0;
+    ~TfheBlindRotCore() {
+        if (!plan) return;
+        {
+            DeviceGuard g(plan->fft->device);
+            for (W *b : {d, e, ping})
+                if (b) (void)counted_free(b);
+        }
+        delete plan;
+    }
+};
+struct pfhe_tfhe_blindrot : TfheBlindRotCore<pfhe_tfhe_plan, u64> {};
+struct pfhe_tfhe32_blindrot : TfheBlindRotCore<pfhe_tfhe32_plan, u32> {};
+
 namespace pfhe {
 namespace {
 
 constexpr u32 kMaxLogN = 14;
-constexpr int kThreads = 256;
-constexpr u32 kFusedMaxLogN = 11;
-constexpr int kFusedPer = (1 << (kFusedMaxLogN - 1)) / kThreads;  // half-spectrum slots per thread in the fused kernel
-
-__device__ __forceinline__ u32 lpad(u32 i) { return i + (i >> 4); }
-__host__ __device__ inline size_t lds_bytes(u32 log_n) {
-    const u32 m = 1u << (log_n - 1);
-    return (size_t)(m + (m >> 4) + 1) * sizeof(double2);
-}
-__device__ __forceinline__ u32 bitrev(u32 i, u32 log_m) { return log_m ? __brev(i) >> (32 - log_m) : 0u; }
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-
-// forward, natural order in, bit-reversed out: spans M/2 .. 1, twiddle e^{-2 pi i j / 2h} after the difference
-__device__ void fft_dif(double2 *x, u32 log_m, u32 log_n, const double2 *__restrict__ tw) {
-    const u32 half = (1u << log_m) >> 1;
-    for (u32 lh = log_m; lh-- > 0;) {
-        const u32 h = 1u << lh;
-        for (u32 b = threadIdx.x; b < half; b += blockDim.x) {
-            const u32 j = b & (h - 1);
-            const u32 i0 = ((b >> lh) << (lh + 1)) + j, i1 = i0 + h;
-            const double2 a = x[lpad(i0)], c = x[lpad(i1)];
-            double2 w = tw[j << (log_n - lh)];
-            w.y = -w.y;
-            x[lpad(i0)] = cadd(a, c);
-            x[lpad(i1)] = cmul(csub(a, c), w);
-        }
-        __syncthreads();
-    }
-}
-
-// inverse (unscaled), bit-reversed in, natural out: spans 1 .. M/2, twiddle e^{+2 pi i j / 2h} before the sum
-__device__ void fft_dit(double2 *x, u32 log_m, u32 log_n, const double2 *__restrict__ tw) {
-    const u32 half = (1u << log_m) >> 1;
-    for (u32 lh = 0; lh < log_m; ++lh) {
-        const u32 h = 1u << lh;
-        for (u32 b = threadIdx.x; b < half; b += blockDim.x) {
-            const u32 j = b & (h - 1);
-            const u32 i0 = ((b >> lh) << (lh + 1)) + j, i1 = i0 + h;
-            const double2 a = x[lpad(i0)], c = cmul(x[lpad(i1)], tw[j << (log_n - lh)]);
-            x[lpad(i0)] = cadd(a, c);
-            x[lpad(i1)] = csub(a, c);
-        }
-        __syncthreads();
-    }
-}
-
-// TorusFftValue::into_f64_centered
-__device__ __forceinline__ double centre(u32 x) { return (double)(int)x; }
-__device__ __forceinline__ double centre(u64 x) { return (double)(long long)x; }
-
-// TorusFftValue::from_f64_wrapping_rounded: round half away from zero, then `as i64 as u32` (saturating at +-2^63) or
-// `as i128 as u64` (saturating at +-2^127, otherwise exact mod 2^64); NaN gives 0
-template <class W>
-__device__ __forceinline__ W to_torus(double v);
-template <>
-__device__ __forceinline__ u32 to_torus<u32>(double v) {
-    const double r = round(v);
-    if (r != r) return 0u;
-    if (r >= 0x1p63) return 0xffffffffu;
-    if (r <= -0x1p63) return 0u;
-    return (u32)(u64)(long long)r;
-}
-template <>
-__device__ __forceinline__ u64 to_torus<u64>(double v) {
-    const double r = round(v);
-    if (r != r) return 0ull;
-    if (fabs(r) < 0x1p63) return (u64)(long long)r;
-    if (r >= 0x1p127) return ~0ull;
-    if (r <= -0x1p127) return 0ull;
-    const u64 bits = (u64)__double_as_longlong(r);  // 2^63 <= |r| < 2^127: r = mant * 2^e, 11 <= e < 75
-    const int e = (int)((bits >> 52) & 0x7ff) - 1075;
-    const u64 mag = e >= 64 ? 0ull : ((bits & 0xfffffffffffffull) | (1ull << 52)) << e;
-    return r < 0 ? 0ull - mag : mag;
-}
-
-// one OnceSignedDecomposer step (common.rs:219-274) on a power-of-two modulus: the digit as its centred f64 value
-template <class W>
-__device__ __forceinline__ double digit_step(W v, u32 shift, u32 log_basis, u32 &carry) {
-    const W B = (W)1 << log_basis;
-    const W temp = ((v >> shift) & (B - 1)) + (W)carry;
-    const W cmask = log_basis == 1 ? (W)2 : (B | (B >> 1));
-    const bool nc = (temp & cmask) != 0;
-    carry = nc ? 1u : 0u;
-    if (!nc) return (double)temp;
-    return temp > B - 1 ? 0.0 : -(double)(B - temp);  // temp + (2^BITS - B), reinterpreted as signed
-}
-template <class W>
-__device__ __forceinline__ u32 init_carry(W v, u32 drop_bits) {
-    return drop_bits ? (u32)((v >> (drop_bits - 1)) & 1) : 0u;
-}
-
-struct Shape {
-    u32 log_n, k, log_basis, ell, drop_bits;
-};
+constexpr int kThreads = kFftThreads;
 
 // ---------------- standalone batched transforms ----------------
 
@@ -283,84 +216,111 @@ __global__ __launch_bounds__(kThreads) void tfhe_mulacc_kernel(const double2 *__
 
 // ---------------- the fused product (k = 1, N <= 2^11) ----------------
 
-// one workgroup per ciphertext.  Thread t owns coefficient pairs (i, i + N/2) and half-spectrum slots i for
-// i = t + 256 u; the accumulators of both output rows stay in its registers.  The key is read in natural order (even
-// entries and their mirrored odd partners), the digit spectrum from LDS at the bit-reversed position.
+// one workgroup per ciphertext; the body is pfhe_fft_device.hpp's fused_accumulate_rows / fused_inverse_rows
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_fused_kernel(const W *__restrict__ in, const double2 *__restrict__ key,
                                                               W *__restrict__ out, const double2 *__restrict__ tw, Shape s) {
     extern __shared__ __attribute__((aligned(16))) double2 lds_p[];
-    const u32 n = 1u << s.log_n, m = n >> 1, log_m = s.log_n - 1;
+    const u32 n = 1u << s.log_n, m = n >> 1;
     const W *x = in + (u64)blockIdx.x * 2 * n;
     W *o = out + (u64)blockIdx.x * 2 * n;
     double2 acc0[kFusedPer], acc1[kFusedPer];
 #pragma unroll
     for (int u = 0; u < kFusedPer; ++u) acc0[u] = acc1[u] = make_double2(0.0, 0.0);
-    for (u32 r = 0; r < 2; ++r) {
-        // the words are re-read at every level (L1 hits) and only the carries stay in registers: bit u of carry0 /
-        // carry1 is the carry of coefficient i / i + N/2 of slot u
-        const W *xr = x + r * n;
-        u32 carry0 = 0, carry1 = 0;
+    fused_accumulate_rows<W>([&](u32 r) { return GlobalRow<W>{x + r * n, m}; }, key, lds_p, tw, s, acc0, acc1);
+    fused_inverse_rows(acc0, acc1, lds_p, tw, s, [&](u32 c, u32 i, double lo, double hi) {
+        o[c * n + i] = to_torus<W>(lo);
+        o[c * n + i + m] = to_torus<W>(hi);
+    });
+}
+
+// ---------------- blind rotation over the product ----------------
+
+// coefficient j of X^r * p - p for a polynomial p of N words (wrapping arithmetic): X^r p [j] = +-p[(j - r) mod N], the
+// wrapped part negated; r >= N (high, rot = r - N) negates the other part
+template <class W>
+__device__ __forceinline__ W rotated_diff(const W *p, u32 j, u32 rot, bool high, u32 mask) {
+    const W v = p[(j - rot) & mask];
+    return (((j < rot) != high) ? (W)0 - v : v) - p[j];
+}
+
+// one input row of D = X^r ACC - ACC, held in registers for all its levels
+template <class W>
+struct RegisterRow {
+    W a[kFusedPer], b[kFusedPer];
+    __device__ __forceinline__ W lo(int u, u32) const { return a[u]; }
+    __device__ __forceinline__ W hi(int u, u32) const { return b[u]; }
+};
+
+// The whole loop of one ciphertext in one workgroup (k = 1, N <= 2^11): ACC (2N words) sits in LDS behind the digit
+// spectrum from the first step to the last.  Per step: D row by row from the LDS-resident ACC into registers, the
+// product's own accumulate and inverse code against step i's key (global memory, natural order), ACC += E in LDS.  Every
+// gather of a step precedes a barrier of fused_accumulate_rows, every update follows them, and fused_inverse_rows
+// ends behind a barrier, so no step reads a word the same step has already updated.
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_blindrot_loop_kernel(W *__restrict__ acc, const double2 *__restrict__ bsk,
+                                                                      const u32 *__restrict__ exps, u32 n_steps,
+                                                                      const double2 *__restrict__ tw, Shape s) {
+    extern __shared__ __attribute__((aligned(16))) double2 lds_l[];
+    const u32 n = 1u << s.log_n, m = n >> 1;
+    W *a = reinterpret_cast<W *>(reinterpret_cast<char *>(lds_l) + lds_bytes(s.log_n));
+    W *g = acc + (u64)blockIdx.x * 2 * n;
+    for (u32 i = threadIdx.x; i < 2 * n; i += blockDim.x) a[i] = g[i];
+    __syncthreads();
+    const u32 *ex = exps + (u64)blockIdx.x * n_steps;
+    const u64 key_len = (u64)4 * s.ell * n;
+    for (u32 step = 0; step < n_steps; ++step) {
+        const u32 r = ex[step] & (2 * n - 1);  // the device form takes every exponent modulo 2N
+        const bool high = r >= n;
+        const u32 rot = high ? r - n : r;
+        const double2 *key = bsk + step * key_len;
+        double2 acc0[kFusedPer], acc1[kFusedPer];
 #pragma unroll
-        for (int u = 0; u < kFusedPer; ++u) {
-            const u32 i = threadIdx.x + u * kThreads;
-            if (i < m) {
-                carry0 |= init_carry(xr[i], s.drop_bits) << u;
-                carry1 |= init_carry(xr[i + m], s.drop_bits) << u;
-            }
-        }
-        for (u32 l = 0; l < s.ell; ++l) {
-            const u32 shift = s.drop_bits + l * s.log_basis;
+        for (int u = 0; u < kFusedPer; ++u) acc0[u] = acc1[u] = make_double2(0.0, 0.0);
+        fused_accumulate_rows<W>([&](u32 row) {
+            RegisterRow<W> d;
 #pragma unroll
             for (int u = 0; u < kFusedPer; ++u) {
                 const u32 i = threadIdx.x + u * kThreads;
-                if (i < m) {
-                    u32 c0 = (carry0 >> u) & 1, c1 = (carry1 >> u) & 1;
-                    const double d0 = digit_step(xr[i], shift, s.log_basis, c0);
-                    const double d1 = digit_step(xr[i + m], shift, s.log_basis, c1);
-                    carry0 = (carry0 & ~(1u << u)) | (c0 << u);
-                    carry1 = (carry1 & ~(1u << u)) | (c1 << u);
-                    lds_p[lpad(i)] = cmul(make_double2(d0, d1), tw[i]);
-                }
+                d.a[u] = i < m ? rotated_diff(a + row * n, i, rot, high, n - 1) : (W)0;
+                d.b[u] = i < m ? rotated_diff(a + row * n, i + m, rot, high, n - 1) : (W)0;
             }
-            __syncthreads();
-            fft_dif(lds_p, log_m, s.log_n, tw);
-            const double2 *k0 = key + (u64)((r * s.ell + l) * 2) * n, *k1 = k0 + n;
-#pragma unroll
-            for (int u = 0; u < kFusedPer; ++u) {
-                const u32 i = threadIdx.x + u * kThreads;
-                if (i < m) {
-                    const double2 d = lds_p[lpad(bitrev(i, log_m))];
-                    const u32 j = (n + 1 - 2 * i) & (n - 1);
-                    const double2 a0 = k0[2 * i], b0 = k0[j], a1 = k1[2 * i], b1 = k1[j];
-                    acc0[u] = cadd(acc0[u], cmul(d, make_double2(0.5 * (a0.x + b0.x), 0.5 * (a0.y - b0.y))));
-                    acc1[u] = cadd(acc1[u], cmul(d, make_double2(0.5 * (a1.x + b1.x), 0.5 * (a1.y - b1.y))));
-                }
-            }
-            __syncthreads();  // the next level overwrites the digit spectrum
-        }
+            return d;
+        }, key, lds_l, tw, s, acc0, acc1);
+        fused_inverse_rows(acc0, acc1, lds_l, tw, s, [&](u32 c, u32 i, double lo, double hi) {
+            a[c * n + i] += to_torus<W>(lo);
+            a[c * n + i + m] += to_torus<W>(hi);
+        });
     }
-    const double scale = 1.0 / (double)m;
-#pragma unroll
-    for (u32 c = 0; c < 2; ++c) {
-#pragma unroll
-        for (int u = 0; u < kFusedPer; ++u) {
-            const u32 i = threadIdx.x + u * kThreads;
-            if (i < m) lds_p[lpad(bitrev(i, log_m))] = c ? acc1[u] : acc0[u];
-        }
-        __syncthreads();
-        fft_dit(lds_p, log_m, s.log_n, tw);
-#pragma unroll
-        for (int u = 0; u < kFusedPer; ++u) {
-            const u32 i = threadIdx.x + u * kThreads;
-            if (i < m) {
-                const double2 t = tw[i];
-                const double2 v = cmul(lds_p[lpad(i)], make_double2(t.x, -t.y));
-                o[c * n + i] = to_torus<W>(v.x * scale);
-                o[c * n + i + m] = to_torus<W>(v.y * scale);
-            }
-        }
-        __syncthreads();  // the second row reuses the buffer
+    for (u32 i = threadIdx.x; i < 2 * n; i += blockDim.x) g[i] = a[i];
+}
+
+// The element-wise glue of the per-step form, one thread per coefficient, as blindrot_glue_kernel on torus words:
+// ACC' = ACC + E (ADD_E; stored when STORE_ACC) and D' = X^r ACC' - ACC' (ROT == kRotSub) or X^r ACC' alone (kRotOnly).
+// The rotated source word is gathered as ACC + E at that index, so ACC' goes to another buffer than it is read from.
+// Coefficient i belongs to polynomial p = i >> log_n of element p / polys_per_exp, which takes exps[element * exp_stride].
+enum TorusRot : int { kRotNone = 0, kRotSub = 1, kRotOnly = 2 };
+
+template <class W, bool ADD_E, bool STORE_ACC, int ROT>
+__global__ __launch_bounds__(kThreads) void tfhe_blindrot_glue_kernel(const W *__restrict__ acc, const W *__restrict__ e_in,
+                                                                      W *__restrict__ acc_out, W *__restrict__ d_out,
+                                                                      const u32 *__restrict__ exps, u32 exp_stride,
+                                                                      u32 polys_per_exp, u32 log_n, u64 total) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const u32 n = 1u << log_n, mask = n - 1;
+    const W a = ADD_E ? (W)(acc[i] + e_in[i]) : acc[i];
+    if constexpr (STORE_ACC) acc_out[i] = a;
+    if constexpr (ROT != kRotNone) {
+        const u64 el = (i >> log_n) / polys_per_exp;
+        const u32 r = exps[el * exp_stride] & (2 * n - 1);
+        const bool high = r >= n;
+        const u32 rot = high ? r - n : r;
+        const u32 j = (u32)(i & mask);
+        const u64 src = (i - j) + ((j - rot) & mask);
+        const W v = ADD_E ? (W)(acc[src] + e_in[src]) : acc[src];
+        const W x = ((j < rot) != high) ? (W)0 - v : v;
+        d_out[i] = ROT == kRotSub ? (W)(x - a) : x;
     }
 }
 
@@ -596,6 +556,204 @@ int product_host(P *p, const W *in, size_t len_in, const double *key, size_t len
     return st.finish();
 }
 
+// ---------------- blind rotation ----------------
+
+constexpr const char *kBlindRotBusy = "TFHE blind-rotation handle in use by another thread (one handle per thread)";
+constexpr const char *kBlindRotLengths = "TFHE blind rotation: acc must be batch*(k+1)*N words, bsk n_steps*(k+1)*ell*(k+1)*N "
+                                         "complex values and exps batch*n_steps exponents";
+constexpr size_t kDefaultGlueBytes = 256ull << 20;
+
+enum class TorusGlue { kFirst, kFirstCopy, kStep, kLast, kMonomial };
+
+template <class W, bool ADD_E, bool STORE_ACC, int ROT>
+int launch_torus_glue(const W *acc, const W *e_in, W *acc_out, W *d_out, const u32 *exps, u32 exp_stride, u32 polys_per_exp,
+                      u32 log_n, u64 total, hipStream_t s) {
+    if (total == 0) return PFHE_OK;
+    const u64 grid = (total + kThreads - 1) / kThreads;
+    if (grid > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
+    hipLaunchKernelGGL((tfhe_blindrot_glue_kernel<W, ADD_E, STORE_ACC, ROT>), dim3((u32)grid), dim3(kThreads), 0, s, acc, e_in,
+                       acc_out, d_out, exps, exp_stride, polys_per_exp, log_n, total);
+    PFHE_HIP(hipGetLastError());
+    return PFHE_OK;
+}
+
+template <class W>
+int torus_glue(const pfhe_fft &f, TorusGlue mode, const W *acc, const W *e_in, W *acc_out, W *d_out, const u32 *exps,
+               u32 exp_stride, u32 polys_per_exp, u64 elements, hipStream_t s) {
+    const u64 total = elements * polys_per_exp * f.n;
+    switch (mode) {
+        case TorusGlue::kFirst:
+            return launch_torus_glue<W, false, false, kRotSub>(acc, nullptr, nullptr, d_out, exps, exp_stride, polys_per_exp,
+                                                               f.log_n, total, s);
+        case TorusGlue::kFirstCopy:
+            return launch_torus_glue<W, false, true, kRotSub>(acc, nullptr, acc_out, d_out, exps, exp_stride, polys_per_exp,
+                                                              f.log_n, total, s);
+        case TorusGlue::kStep:
+            return launch_torus_glue<W, true, true, kRotSub>(acc, e_in, acc_out, d_out, exps, exp_stride, polys_per_exp,
+                                                             f.log_n, total, s);
+        case TorusGlue::kLast:
+            return launch_torus_glue<W, true, true, kRotNone>(acc, e_in, acc_out, nullptr, exps, exp_stride, polys_per_exp,
+                                                              f.log_n, total, s);
+        case TorusGlue::kMonomial:
+            return launch_torus_glue<W, false, false, kRotOnly>(acc, nullptr, nullptr, d_out, exps, exp_stride, polys_per_exp,
+                                                                f.log_n, total, s);
+    }
+    return PFHE_ERR_BAD_ARGUMENT;
+}
+
+// X^{exps[e]} * element e for `polys_per_exp` torus polynomials per element; out must not overlap a (the rotation reads
+// a[(j - r) mod N] while other threads write out[j])
+template <class W>
+int torus_monomial_each(const pfhe_fft *f, const W *a, size_t len, const uint32_t *exps, size_t polys_per_exp, W *out,
+                        hipStream_t s) {
+    if (!f) return PFHE_ERR_BAD_ARGUMENT;
+    const size_t unit = polys_per_exp * f->n;
+    if (polys_per_exp == 0 || polys_per_exp > 0xffffffffull || len % unit != 0) {
+        set_last_error("mul_monomial_each: len must be a whole number of elements of polys_per_exp * N words");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (len == 0) return PFHE_OK;
+    if (!a || !exps || !out) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(a);
+    PFHE_REQUIRE_ALIGNED(out);
+    const uintptr_t a0 = (uintptr_t)a, o0 = (uintptr_t)out, bytes = (uintptr_t)len * sizeof(W);
+    if (a0 < o0 + bytes && o0 < a0 + bytes) {
+        set_last_error("mul_monomial_each_to needs non-overlapping buffers");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    DeviceGuard g(f->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return torus_glue<W>(*f, TorusGlue::kMonomial, a, nullptr, nullptr, out, exps, 1, (u32)polys_per_exp, len / unit, s);
+}
+
+// plan_create's checks in plan_create's order (the handle's plan IS a product plan), then the form: the whole-loop kernel
+// on the product's fused shape unless PFHE_DISABLE_FUSED_TFHE_BLINDROT is set when the handle is created
+template <class H, class P>
+int tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         size_t chunk, H **out) {
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    auto h = std::make_unique<H>();
+    PFHE_TRY(plan_create<P>(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->plan));
+    using W = typename std::remove_pointer<decltype(h->d)>::type;
+    const P &p = *h->plan;
+    h->glwe = (size_t)(p.k + 1) * fft->n;
+    h->key_len = (size_t)(p.k + 1) * p.ell * h->glwe;
+    h->whole_loop = p.fused && std::getenv("PFHE_DISABLE_FUSED_TFHE_BLINDROT") == nullptr;
+    h->chunk = p.chunk;
+    DeviceGuard g(fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    if (!h->whole_loop) {
+        // never above the plan's chunk, so a chunk of the rotation is one chunk of the product
+        if (!chunk) h->chunk = std::min(p.chunk, std::max<size_t>(1, kDefaultGlueBytes / (3 * h->glwe * sizeof(W))));
+        for (W **b : {&h->d, &h->e, &h->ping}) {
+            void *q = nullptr;
+            PFHE_HIP(counted_malloc(&q, h->chunk * h->glwe * sizeof(W)));
+            *b = (W *)q;
+            h->glue_bytes += h->chunk * h->glwe * sizeof(W);
+        }
+    }
+    PFHE_TRY(h->guard.init(fft->device));
+    *out = h.release();
+    return PFHE_OK;
+}
+
+template <class W, class H>
+int tfhe_blindrot_chunk(H *h, W *a0, const double2 *bsk, const uint32_t *ex, u64 n_steps, u64 cur, hipStream_t s) {
+    const pfhe_fft &f = *h->plan->fft;
+    if (h->whole_loop) {
+        const Shape sh{f.log_n, h->plan->k, h->plan->log_basis, h->plan->ell, h->plan->drop_bits};
+        hipLaunchKernelGGL(tfhe_blindrot_loop_kernel<W>, dim3((u32)cur), dim3(kThreads), lds_bytes(f.log_n) + h->glwe * sizeof(W),
+                           s, a0, bsk, ex, (u32)n_steps, f.tw, sh);
+        PFHE_HIP(hipGetLastError());
+        return PFHE_OK;
+    }
+    // ping-pong between the caller's accumulator and the handle's: every step writes ACC' to the other one, so the gather
+    // of a rotated word never sees a word already updated; an odd step count starts in the handle's buffer so that the
+    // last step ends in the caller's
+    const u32 rows = h->plan->k + 1;
+    W *src = a0;
+    if (n_steps % 2) {
+        PFHE_TRY(torus_glue<W>(f, TorusGlue::kFirstCopy, a0, nullptr, h->ping, h->d, ex, (u32)n_steps, rows, cur, s));
+        src = h->ping;
+    } else {
+        PFHE_TRY(torus_glue<W>(f, TorusGlue::kFirst, a0, nullptr, nullptr, h->d, ex, (u32)n_steps, rows, cur, s));
+    }
+    for (u64 i = 0; i < n_steps; ++i) {
+        PFHE_TRY(product_impl<W>(h->plan, h->d, bsk + i * h->key_len, h->e, cur, s));
+        W *dst = src == a0 ? h->ping : a0;
+        PFHE_TRY(i + 1 < n_steps
+                     ? torus_glue<W>(f, TorusGlue::kStep, src, h->e, dst, h->d, ex + i + 1, (u32)n_steps, rows, cur, s)
+                     : torus_glue<W>(f, TorusGlue::kLast, src, h->e, dst, nullptr, ex, (u32)n_steps, rows, cur, s));
+        src = dst;
+    }
+    return PFHE_OK;
+}
+
+template <class W, class H>
+int tfhe_blindrot_dev(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+                      size_t len_exps, hipStream_t s) {
+    if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kBlindRotBusy);
+    if (len_acc % h->glwe != 0 || len_bsk % h->key_len != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->key_len)) {
+        set_last_error(kBlindRotLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    const u64 batch = len_acc / h->glwe, n_steps = len_bsk / h->key_len;
+    if (batch == 0 || n_steps == 0) return PFHE_OK;
+    if (n_steps > 0xffffffffull) return PFHE_ERR_BAD_LENGTH;
+    if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(acc);
+    PFHE_REQUIRE_ALIGNED(bsk);
+    DeviceGuard g(h->plan->fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return ordered_on(h->guard, s, [&]() -> int {
+        // chunk after chunk; every step of a chunk runs before the next chunk starts
+        for (u64 done = 0; done < batch; done += h->chunk) {
+            const u64 cur = std::min<u64>(h->chunk, batch - done);
+            PFHE_TRY(tfhe_blindrot_chunk<W>(h, acc + done * h->glwe, (const double2 *)bsk, exps + done * n_steps, n_steps, cur, s));
+        }
+        return PFHE_OK;
+    });
+}
+
+// host form: every exponent must be below 2N; staged through the pooled context
+template <class W, class H>
+int tfhe_blindrot_host(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+                       size_t len_exps) {
+    if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kBlindRotBusy);
+    if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
+    const pfhe_fft &f = *h->plan->fft;
+    for (size_t i = 0; i < len_exps; ++i) {
+        if (exps[i] >= 2 * f.n) {
+            set_last_error("TFHE blind rotation: every exponent must be below 2N");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
+    }
+    if (len_acc % h->glwe != 0 || len_bsk % h->key_len != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->key_len)) {
+        set_last_error(kBlindRotLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
+    DeviceGuard g(f.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(f.device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *a = nullptr, *k = nullptr, *x = nullptr;
+    PFHE_TRY(st.upload(acc, len_acc * sizeof(W), &a));
+    PFHE_TRY(st.upload(bsk, len_bsk * 2 * sizeof(double), &k));
+    PFHE_TRY(st.upload(exps, len_exps * sizeof(uint32_t), &x));
+    PFHE_TRY(tfhe_blindrot_dev<W>(h, (W *)a, len_acc, (const double *)k, len_bsk, (const uint32_t *)x, len_exps, st.stream()));
+    PFHE_TRY(st.download(acc, a, len_acc * sizeof(W)));
+    return st.finish();
+}
+
+template <class H>
+size_t tfhe_blindrot_scratch(const H *h) {
+    return h && h->plan ? h->plan->scratch + h->glue_bytes : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -745,6 +903,65 @@ int pfhe_tfhe32_external_product_to(pfhe_tfhe32_plan *plan, const uint32_t *inpu
                                     size_t len_key, uint32_t *output, size_t len_output) {
     PFHE_GUARD_BEGIN
     return product_host<u32>(plan, input, len_input, key, len_key, output, len_output);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                              size_t chunk, pfhe_tfhe_blindrot **out) {
+    PFHE_GUARD_BEGIN
+    return tfhe_blindrot_create<pfhe_tfhe_blindrot, pfhe_tfhe_plan>(fft, glwe_dimension, log_basis, decompose_length, chunk,
+                                                                    out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe_blindrot_destroy(pfhe_tfhe_blindrot *h) { delete h; }
+int pfhe_tfhe_blindrot_in_use(const pfhe_tfhe_blindrot *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe_blindrot_scratch_bytes(const pfhe_tfhe_blindrot *h) { return tfhe_blindrot_scratch(h); }
+int pfhe_tfhe_blindrot_rotate_dev(pfhe_tfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev,
+                                  size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
+    PFHE_GUARD_BEGIN
+    return tfhe_blindrot_dev<u64>(h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_blindrot_rotate(pfhe_tfhe_blindrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                              const uint32_t *exps, size_t len_exps) {
+    PFHE_GUARD_BEGIN
+    return tfhe_blindrot_host<u64>(h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint64_t *a_dev, size_t len, const uint32_t *exps_dev,
+                                       size_t polys_per_exp, uint64_t *out_dev, void *stream) {
+    PFHE_GUARD_BEGIN
+    return torus_monomial_each<u64>(fft, (const u64 *)a_dev, len, exps_dev, polys_per_exp, (u64 *)out_dev,
+                                    (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe32_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t chunk, pfhe_tfhe32_blindrot **out) {
+    PFHE_GUARD_BEGIN
+    return tfhe_blindrot_create<pfhe_tfhe32_blindrot, pfhe_tfhe32_plan>(fft, glwe_dimension, log_basis, decompose_length,
+                                                                        chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe32_blindrot_destroy(pfhe_tfhe32_blindrot *h) { delete h; }
+int pfhe_tfhe32_blindrot_in_use(const pfhe_tfhe32_blindrot *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe32_blindrot_scratch_bytes(const pfhe_tfhe32_blindrot *h) { return tfhe_blindrot_scratch(h); }
+int pfhe_tfhe32_blindrot_rotate_dev(pfhe_tfhe32_blindrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev,
+                                    size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
+    PFHE_GUARD_BEGIN
+    return tfhe_blindrot_dev<u32>(h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_blindrot_rotate(pfhe_tfhe32_blindrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                                const uint32_t *exps, size_t len_exps) {
+    PFHE_GUARD_BEGIN
+    return tfhe_blindrot_host<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_dev, size_t len, const uint32_t *exps_dev,
+                                         size_t polys_per_exp, uint32_t *out_dev, void *stream) {
+    PFHE_GUARD_BEGIN
+    return torus_monomial_each<u32>(fft, a_dev, len, exps_dev, polys_per_exp, out_dev, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 

@@ -1,0 +1,211 @@
+// pfhe_fft_device.hpp — device code of the torus FFT and of one fused TFHE external product (pfhe_fft.hip).
+//
+// The half-size transforms in LDS, the torus conversions, the signed digits, and the two halves of the fused product
+// (k = 1, N <= 2^11): fused_accumulate_rows (digits, forward transforms and the multiply-accumulate of both input rows) and
+// fused_inverse_rows (the two folded inverses and the torus wrap).  tfhe_fused_kernel runs them once on words read from
+// global memory; tfhe_blindrot_loop_kernel runs them once per step on an accumulator that stays in LDS.  Both inline the
+// same code, so a step of the loop is the product's arithmetic, operation for operation.
+#pragma once
+
+#include "pfhe_common.hpp"
+
+namespace pfhe {
+
+constexpr int kFftThreads = 256;
+constexpr u32 kFusedMaxLogN = 11;
+constexpr int kFusedPer = (1 << (kFusedMaxLogN - 1)) / kFftThreads;  // half-spectrum slots per thread in the fused kernels
+
+__device__ __forceinline__ u32 lpad(u32 i) { return i + (i >> 4); }
+__host__ __device__ inline size_t lds_bytes(u32 log_n) {
+    const u32 m = 1u << (log_n - 1);
+    return (size_t)(m + (m >> 4) + 1) * sizeof(double2);
+}
+__device__ __forceinline__ u32 bitrev(u32 i, u32 log_m) { return log_m ? __brev(i) >> (32 - log_m) : 0u; }
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
+    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+
+// forward, natural order in, bit-reversed out: spans M/2 .. 1, twiddle e^{-2 pi i j / 2h} after the difference
+static __device__ void fft_dif(double2 *x, u32 log_m, u32 log_n, const double2 *__restrict__ tw) {
+    const u32 half = (1u << log_m) >> 1;
+    for (u32 lh = log_m; lh-- > 0;) {
+        const u32 h = 1u << lh;
+        for (u32 b = threadIdx.x; b < half; b += blockDim.x) {
+            const u32 j = b & (h - 1);
+            const u32 i0 = ((b >> lh) << (lh + 1)) + j, i1 = i0 + h;
+            const double2 a = x[lpad(i0)], c = x[lpad(i1)];
+            double2 w = tw[j << (log_n - lh)];
+            w.y = -w.y;
+            x[lpad(i0)] = cadd(a, c);
+            x[lpad(i1)] = cmul(csub(a, c), w);
+        }
+        __syncthreads();
+    }
+}
+
+// inverse (unscaled), bit-reversed in, natural out: spans 1 .. M/2, twiddle e^{+2 pi i j / 2h} before the sum
+static __device__ void fft_dit(double2 *x, u32 log_m, u32 log_n, const double2 *__restrict__ tw) {
+    const u32 half = (1u << log_m) >> 1;
+    for (u32 lh = 0; lh < log_m; ++lh) {
+        const u32 h = 1u << lh;
+        for (u32 b = threadIdx.x; b < half; b += blockDim.x) {
+            const u32 j = b & (h - 1);
+            const u32 i0 = ((b >> lh) << (lh + 1)) + j, i1 = i0 + h;
+            const double2 a = x[lpad(i0)], c = cmul(x[lpad(i1)], tw[j << (log_n - lh)]);
+            x[lpad(i0)] = cadd(a, c);
+            x[lpad(i1)] = csub(a, c);
+        }
+        __syncthreads();
+    }
+}
+
+// TorusFftValue::into_f64_centered
+__device__ __forceinline__ double centre(u32 x) { return (double)(int)x; }
+__device__ __forceinline__ double centre(u64 x) { return (double)(long long)x; }
+
+// TorusFftValue::from_f64_wrapping_rounded: round half away from zero, then `as i64 as u32` (saturating at +-2^63) or
+// `as i128 as u64` (saturating at +-2^127, otherwise exact mod 2^64); NaN gives 0
+template <class W>
+__device__ __forceinline__ W to_torus(double v);
+template <>
+__device__ __forceinline__ u32 to_torus<u32>(double v) {
+    const double r = round(v);
+    if (r != r) return 0u;
+    if (r >= 0x1p63) return 0xffffffffu;
+    if (r <= -0x1p63) return 0u;
+    return (u32)(u64)(long long)r;
+}
+template <>
+__device__ __forceinline__ u64 to_torus<u64>(double v) {
+    const double r = round(v);
+    if (r != r) return 0ull;
+    if (fabs(r) < 0x1p63) return (u64)(long long)r;
+    if (r >= 0x1p127) return ~0ull;
+    if (r <= -0x1p127) return 0ull;
+    const u64 bits = (u64)__double_as_longlong(r);  // 2^63 <= |r| < 2^127: r = mant * 2^e, 11 <= e < 75
+    const int e = (int)((bits >> 52) & 0x7ff) - 1075;
+    const u64 mag = e >= 64 ? 0ull : ((bits & 0xfffffffffffffull) | (1ull << 52)) << e;
+    return r < 0 ? 0ull - mag : mag;
+}
+
+// one OnceSignedDecomposer step (common.rs:219-274) on a power-of-two modulus: the digit as its centred f64 value
+template <class W>
+__device__ __forceinline__ double digit_step(W v, u32 shift, u32 log_basis, u32 &carry) {
+    const W B = (W)1 << log_basis;
+    const W temp = ((v >> shift) & (B - 1)) + (W)carry;
+    const W cmask = log_basis == 1 ? (W)2 : (B | (B >> 1));
+    const bool nc = (temp & cmask) != 0;
+    carry = nc ? 1u : 0u;
+    if (!nc) return (double)temp;
+    return temp > B - 1 ? 0.0 : -(double)(B - temp);  // temp + (2^BITS - B), reinterpreted as signed
+}
+template <class W>
+__device__ __forceinline__ u32 init_carry(W v, u32 drop_bits) {
+    return drop_bits ? (u32)((v >> (drop_bits - 1)) & 1) : 0u;
+}
+
+struct Shape {
+    u32 log_n, k, log_basis, ell, drop_bits;
+};
+
+// ---------------- the fused product (k = 1, N <= 2^11), one workgroup per ciphertext ----------------
+//
+// Thread t owns coefficient pairs (i, i + N/2) and half-spectrum slots i for i = t + 256 u; the accumulators of both
+// output rows stay in its registers.  The key is read in natural order (even entries and their mirrored odd partners),
+// the digit spectrum from LDS at the bit-reversed position.
+
+// input row r of a ciphertext in global memory: the words are re-read at every level (L1 hits)
+template <class W>
+struct GlobalRow {
+    const W *xr;
+    u32 m;
+    __device__ __forceinline__ W lo(int, u32 i) const { return xr[i]; }
+    __device__ __forceinline__ W hi(int, u32 i) const { return xr[i + m]; }
+};
+
+// both input rows, all levels: rows(r) gives row r, whose lo(u, i) / hi(u, i) are the words of coefficients i and
+// i + N/2 of slot u.  Per level: their signed digits, the forward half transform in lds_p, and acc0 / acc1 += spectrum *
+// Herm(key[r][l][0 / 1]).  Only the carries stay in registers between levels: bit u of carry0 / carry1 is the carry of
+// coefficient i / i + N/2 of slot u.  Ends behind a barrier.
+template <class W, class Rows>
+__device__ __forceinline__ void fused_accumulate_rows(const Rows rows, const double2 *__restrict__ key, double2 *lds_p,
+                                                      const double2 *__restrict__ tw, const Shape s,
+                                                      double2 (&acc0)[kFusedPer], double2 (&acc1)[kFusedPer]) {
+    const u32 n = 1u << s.log_n, m = n >> 1, log_m = s.log_n - 1;
+    for (u32 r = 0; r < 2; ++r) {
+        const auto row = rows(r);
+        u32 carry0 = 0, carry1 = 0;
+#pragma unroll
+        for (int u = 0; u < kFusedPer; ++u) {
+            const u32 i = threadIdx.x + u * kFftThreads;
+            if (i < m) {
+                carry0 |= init_carry(row.lo(u, i), s.drop_bits) << u;
+                carry1 |= init_carry(row.hi(u, i), s.drop_bits) << u;
+            }
+        }
+        for (u32 l = 0; l < s.ell; ++l) {
+            const u32 shift = s.drop_bits + l * s.log_basis;
+#pragma unroll
+            for (int u = 0; u < kFusedPer; ++u) {
+                const u32 i = threadIdx.x + u * kFftThreads;
+                if (i < m) {
+                    u32 c0 = (carry0 >> u) & 1, c1 = (carry1 >> u) & 1;
+                    const double d0 = digit_step(row.lo(u, i), shift, s.log_basis, c0);
+                    const double d1 = digit_step(row.hi(u, i), shift, s.log_basis, c1);
+                    carry0 = (carry0 & ~(1u << u)) | (c0 << u);
+                    carry1 = (carry1 & ~(1u << u)) | (c1 << u);
+                    lds_p[lpad(i)] = cmul(make_double2(d0, d1), tw[i]);
+                }
+            }
+            __syncthreads();
+            fft_dif(lds_p, log_m, s.log_n, tw);
+            const double2 *k0 = key + (u64)((r * s.ell + l) * 2) * n, *k1 = k0 + n;
+#pragma unroll
+            for (int u = 0; u < kFusedPer; ++u) {
+                const u32 i = threadIdx.x + u * kFftThreads;
+                if (i < m) {
+                    const double2 d = lds_p[lpad(bitrev(i, log_m))];
+                    const u32 j = (n + 1 - 2 * i) & (n - 1);
+                    const double2 a0 = k0[2 * i], b0 = k0[j], a1 = k1[2 * i], b1 = k1[j];
+                    acc0[u] = cadd(acc0[u], cmul(d, make_double2(0.5 * (a0.x + b0.x), 0.5 * (a0.y - b0.y))));
+                    acc1[u] = cadd(acc1[u], cmul(d, make_double2(0.5 * (a1.x + b1.x), 0.5 * (a1.y - b1.y))));
+                }
+            }
+            __syncthreads();  // the next level overwrites the digit spectrum
+        }
+    }
+}
+
+// the two folded inverses of acc0 / acc1: sink(c, i, value of coefficient i, value of coefficient i + N/2) for output row
+// c takes the scaled f64 values and wraps them to the torus (to_torus).  Ends behind a barrier.
+template <class Sink>
+__device__ __forceinline__ void fused_inverse_rows(const double2 (&acc0)[kFusedPer], const double2 (&acc1)[kFusedPer],
+                                                   double2 *lds_p, const double2 *__restrict__ tw, const Shape s,
+                                                   const Sink sink) {
+    const u32 n = 1u << s.log_n, m = n >> 1, log_m = s.log_n - 1;
+    const double scale = 1.0 / (double)m;
+#pragma unroll
+    for (u32 c = 0; c < 2; ++c) {
+#pragma unroll
+        for (int u = 0; u < kFusedPer; ++u) {
+            const u32 i = threadIdx.x + u * kFftThreads;
+            if (i < m) lds_p[lpad(bitrev(i, log_m))] = c ? acc1[u] : acc0[u];
+        }
+        __syncthreads();
+        fft_dit(lds_p, log_m, s.log_n, tw);
+#pragma unroll
+        for (int u = 0; u < kFusedPer; ++u) {
+            const u32 i = threadIdx.x + u * kFftThreads;
+            if (i < m) {
+                const double2 t = tw[i];
+                const double2 v = cmul(lds_p[lpad(i)], make_double2(t.x, -t.y));
+                sink(c, i, v.x * scale, v.y * scale);
+            }
+        }
+        __syncthreads();  // the second row reuses the buffer
+    }
+}
+
+}  // namespace pfhe

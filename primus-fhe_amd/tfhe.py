@@ -60,6 +60,16 @@ def _dev_fourier(t):
     return C.cast(C.c_void_p(t.data_ptr()), C.POINTER(C.c_double)), n
 
 
+def _dev_exps(t):
+    """(pointer, count) of a contiguous int32 / uint32 CUDA tensor of exponents, or a (ptr, count) tuple"""
+    if isinstance(t, tuple):
+        return C.c_void_p(int(t[0])), int(t[1])
+    if not hasattr(t, "data_ptr") or not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 \
+            or t.is_floating_point():
+        raise TypeError("expected a contiguous int32 / uint32 CUDA tensor of exponents")
+    return C.c_void_p(t.data_ptr()), t.numel()
+
+
 class FullComplex64FftTable:
     """primus_fft::FullComplex64FftTable — negacyclic torus FFT of N = 2^log_n (1 <= log_n <= 14), u32 and u64 words."""
 
@@ -101,6 +111,17 @@ class FullComplex64FftTable:
         pi, ni = _dev_fourier(inp)
         po, no, w = _dev_words(out)
         check(getattr(lib(), "pfhe_fft_inverse_torus" + w + "_dev")(self._h, pi, ni, po, no, _stream(stream)))
+
+    def mul_monomial_each_to_dev(self, a, exps, out, polys_per_exp: int = 1, stream=None) -> None:
+        """out = X^{exps[e]} * element e for elements of `polys_per_exp` torus polynomials each (exponents modulo 2N): the
+        per-ciphertext X^{-b_e} * TV that starts a bootstrap.  out must not overlap a."""
+        pa, na, wa = _dev_words(a)
+        po, no, wo = _dev_words(out)
+        pe, _ne = _dev_exps(exps)
+        if wa != wo or na != no:
+            raise TypeError("a and out must have the same width and length")
+        check(getattr(lib(), "pfhe_tfhe" + wa + "_mul_monomial_each_to_dev")(self._h, pa, na, pe, polys_per_exp, po,
+                                                                              _stream(stream)))
 
 
 class ApproxSignedBasis:
@@ -184,6 +205,67 @@ def tfhe_external_product_to_dev(inp, key, out, ctx: TfheFftContext, stream=None
     if wi != ctx._w or wo != ctx._w:
         raise TypeError("input / output words must match the basis width")
     check(getattr(lib(), ctx._pre + "external_product_to_dev")(ctx._h, pi, ni, pk, nk, po, no, _stream(stream)))
+
+
+class TfheBlindRotateContext:
+    """Handle of the batched blind rotation over the TFHE product (include/pfhe.h, pfhe_tfhe{,32}_blindrot_*): for every
+    step i and ciphertext e, ACC_e += external_product_to(X^{exps[e*n_steps+i]} * ACC_e - ACC_e, BSK_i) on torus words.
+    Owns a product plan and whatever glue buffers its form needs for `chunk` ciphertexts (0 = the default); one holder at
+    a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1, chunk: int = 0):
+        self._w = "" if basis.bits == 64 else "32"
+        self._pre = "pfhe_tfhe" + self._w + "_blindrot_"
+        h = C.c_void_p()
+        check(getattr(lib(), self._pre + "create")(fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(),
+                                                   chunk, C.byref(h)))
+        self._h = h
+        self.fft, self.basis, self.glwe_dimension = fft, basis, glwe_dimension
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            getattr(lib(), self._pre + "destroy")(h)
+            self._h = None
+
+    def dtype(self):
+        return np.uint64 if self.basis.bits == 64 else np.uint32
+
+    def scratch_bytes(self) -> int:
+        return int(getattr(lib(), self._pre + "scratch_bytes")(self._h))
+
+    def in_use(self) -> bool:
+        return bool(getattr(lib(), self._pre + "in_use")(self._h))
+
+    def glwe_len(self) -> int:
+        return (self.glwe_dimension + 1) * self.fft.poly_length()
+
+    def key_len(self) -> int:
+        """complex values of one Fourier GGSW key (one step of the rotation)"""
+        return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
+
+
+def tfhe_blind_rotate(acc: np.ndarray, bsk: np.ndarray, exps: np.ndarray, ctx: TfheBlindRotateContext) -> None:
+    """Batched blind rotation on host arrays, acc updated in place.  acc: batch GLWE ciphertexts of the context's width;
+    bsk: n_steps Fourier GGSW keys end to end; exps: uint32, batch x n_steps, ciphertext-major, every exponent below 2N."""
+    pa, na, wa = _host_words(acc)
+    pk, nk = _host_fourier(bsk)
+    if wa != ctx._w:
+        raise TypeError("accumulator words must match the basis width")
+    if not isinstance(exps, np.ndarray) or exps.dtype != np.uint32 or not exps.flags.c_contiguous:
+        raise TypeError("expected a C-contiguous numpy uint32 array of exponents")
+    check(getattr(lib(), ctx._pre + "rotate")(ctx._h, pa, na, pk, nk, exps.ctypes.data_as(C.c_void_p), exps.size))
+
+
+def tfhe_blind_rotate_dev(acc, bsk, exps, ctx: TfheBlindRotateContext, stream=None) -> None:
+    """the device form (acc a 32- or 64-bit integer CUDA tensor of the context's width, bsk complex128 or float64, exps
+    int32 / uint32), asynchronous; every exponent is taken modulo 2N on the device"""
+    pa, na, wa = _dev_words(acc)
+    pk, nk = _dev_fourier(bsk)
+    pe, ne = _dev_exps(exps)
+    if wa != ctx._w:
+        raise TypeError("accumulator words must match the basis width")
+    check(getattr(lib(), ctx._pre + "rotate_dev")(ctx._h, pa, na, pk, nk, pe, ne, _stream(stream)))
 
 
 def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) -> None:
