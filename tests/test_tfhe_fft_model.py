@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import tfhe_fft_model as m
+from tfhe_edge_words import edge_words
 
 PATTERN = [0, 1, -1, 2, -2]
 
@@ -87,15 +88,49 @@ def test_basis_digits_recompose():
         assert len(digits) == b.decompose_length
         lo = 0 if lb == 1 else -(1 << (lb - 1))
         assert all(d.min() >= lo and d.max() <= (1 if lb == 1 else (1 << (lb - 1))) for d in digits)
-        # sum d_l B^l 2^drop is x rounded to the kept bits (mod 2^BITS)
-        approx = sum(int(d) << (b.drop_bits + i * lb) for i, dd in enumerate(digits) for d in dd[:1])
-        xi = int(x[0])
-        rounded = ((xi + ((1 << (b.drop_bits - 1)) if b.drop_bits else 0)) >> b.drop_bits) << b.drop_bits
-        assert approx % (1 << bits) == rounded % (1 << bits)
+        # sum d_l B^l 2^drop is x rounded to the kept bits (mod 2^BITS), for every word
+        half = (1 << (b.drop_bits - 1)) if b.drop_bits else 0
+        for j, xi in enumerate(int(v) for v in x):
+            approx = sum(int(dd[j]) << (b.drop_bits + i * lb) for i, dd in enumerate(digits))
+            rounded = ((xi + half) >> b.drop_bits) << b.drop_bits
+            assert approx % (1 << bits) == rounded % (1 << bits), (bits, lb, length, hex(xi))
     with pytest.raises(AssertionError):
         m.ApproxSignedBasis(32, 0)
     with pytest.raises(AssertionError):
         m.ApproxSignedBasis(32, 8, 5)
+
+
+EDGE_BASES = [  # bits, log_basis, reverse_length (None = full), edge words
+    (32, 7, 3, 1373), (32, 10, 2, 197), (32, 8, None, 100), (32, 1, 8, 73), (32, 31, 1, 14),
+    (64, 15, 2, 197), (64, 23, 1, 29), (64, 1, 10, 89), (64, 21, 3, 686),
+]
+
+
+@pytest.mark.parametrize("bits,lb,length,count", EDGE_BASES)
+def test_digits_of_every_edge_word(bits, lb, length, count):
+    """Every edge word (tests/tfhe_edge_words.py) against Python integers: each digit in [-B/2, B/2 - 1] ({0, 1} for
+    log B = 1) and sum d_l 2^(drop + l log B) = ((x + 2^(drop-1)) >> drop) << drop mod 2^BITS (no rounding term when
+    drop = 0).  ell digits of that range represent at most B^ell = 2^(BITS - drop) values, one per residue, so range and
+    recomposition determine the digits: this pins the model without restating its branches."""
+    words = edge_words(bits, lb, length)
+    assert words.dtype == m.UINT[bits] and len(words) == count
+    assert np.array_equal(words, np.unique(words))
+    assert {0, 1, (1 << bits) - 1, 1 << (bits - 1), (1 << (bits - 1)) - 1} <= {int(w) for w in words}
+    b = m.ApproxSignedBasis(bits, lb, length)
+    ell, drop = b.decompose_length, b.drop_bits
+    digits = b.digits(words)
+    assert len(digits) == ell and all(d.shape == words.shape for d in digits)
+    lo, hi = (0, 1) if lb == 1 else (-(1 << (lb - 1)), (1 << (lb - 1)) - 1)
+    half = (1 << (drop - 1)) if drop else 0
+    seen = set()
+    for j, x in enumerate(int(w) for w in words):
+        ds = [int(d[j]) for d in digits]
+        assert all(lo <= d <= hi for d in ds), (hex(x), ds)
+        approx = sum(d << (drop + l * lb) for l, d in enumerate(ds))
+        assert approx % (1 << bits) == (((x + half) >> drop) << drop) % (1 << bits), (hex(x), ds)
+        seen.update(ds)
+    # the list does reach what it is for: both ends of the digit range and, through a carry, a zero digit above B - 1
+    assert {lo, hi, 0} <= seen
 
 
 def test_reference_external_product_smoke():
