@@ -953,6 +953,102 @@ int pfhe_tfhe_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint64_t *a_de
 int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_dev, size_t len, const uint32_t *exps_dev,
                                          size_t polys_per_exp, uint32_t *out_dev, void *stream);
 
+/* ---- the programmable bootstrap around the blind rotation (u64: no suffix, u32: 32) ----
+ * An LWE ciphertext is laid out as the reference's Lwe (primus_lattice/src/lwe/single_message.rs:94-125): a[0..dim) then b,
+ * dim + 1 torus words, b = <a,s> + e + m; a batch is ciphertext after ciphertext.  The three stateless steps below are exact
+ * integer arithmetic modulo 2^BITS; the two without a table take the device first, as pfhe_memset_dev does.
+ *
+ * Modulus switch.  NO reference counterpart: the reference has no modulus switching, and the rule is this project's own.
+ * With shift = BITS - log_n - 1, sw(w) = (((w >> (shift-1)) + 1) >> 1) & (2N-1): round-to-nearest of w * 2N / 2^BITS, ties
+ * up, without overflow; 1 <= log_n <= 14 (PFHE_ERR_BAD_ARGUMENT otherwise).  For every ciphertext e of the batch
+ * (len_lwe = batch*(n+1), n = lwe_dimension): exps[e*n + i] = sw(a_{e,i}) — ciphertext-major, what
+ * pfhe_tfhe*_blindrot_rotate_dev takes (len_exps = batch*n) — and neg_b[e] = (2N - sw(b_e)) & (2N-1) (len_neg_b = batch). */
+int pfhe_tfhe_modswitch_dev(int device, const uint64_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                            uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream);
+int pfhe_tfhe32_modswitch_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                              uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream);
+/* Sample extraction — Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227; index 0: extract_lwe,
+ * :264-288) applied to each of the k mask polynomials of a GLWE ciphertext (A_0..A_{k-1}, B): for index h < N the output LWE
+ * has dimension k*N, out[j*N + i] = A_j[h - i] for i <= h and -A_j[N + h - i] for i > h (wrapping), out[k*N] = B[h]; its key
+ * is the GLWE key polynomials end to end.  len_glwe = batch*(k+1)*N, len_lwe = batch*(k*N+1); 1 <= k <= 64 and index < N
+ * (PFHE_ERR_BAD_ARGUMENT otherwise); the output must not overlap the input.  extract_first_few_lwe / MultiMsgLwe are not
+ * mirrored. */
+int pfhe_tfhe_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
+                                 size_t index, uint64_t *lwe_dev, size_t len_lwe, void *stream);
+int pfhe_tfhe_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe, size_t index,
+                             uint64_t *lwe, size_t len_lwe);
+int pfhe_tfhe32_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe_dev, size_t len_glwe,
+                                   size_t index, uint32_t *lwe_dev, size_t len_lwe, void *stream);
+int pfhe_tfhe32_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe, size_t index,
+                               uint32_t *lwe, size_t len_lwe);
+/* LWE key switch — no single reference function; built from reference pieces: a sequence of Lwe::add_mul_scalar_assign
+ * (lwe/single_message.rs:262-268) under wrapping arithmetic, with the signed digits of ApproxSignedBasis::init_carry_slice
+ * and decompose_iter on the power-of-two modulus (primus_decompose/src/primitive/basis.rs:391-406, primitive/common.rs:226-259;
+ * the digit rule of the TFHE product).  With ell = decompose_length (0 = the full BITS / log_basis) the key is
+ * in_dimension x ell x (out_dimension+1) words: row (i, j) is an LWE ciphertext of s_i * 2^(drop_bits + j*log_basis) under the
+ * output key, levels least significant first.  For every ciphertext e and column c
+ *   out[e][c] = [c == out_dimension] * b_e - sum_{i < in_dimension} sum_{j < ell} d_{e,i,j} * ksk[(i*ell + j)*(out_dimension+1) + c]
+ * modulo 2^BITS, d_{e,i,.} the digits of a_{e,i}.  ApproxSignedBasis::new's assert!s give PFHE_ERR_BAD_ARGUMENT first, as in
+ * pfhe_tfhe_plan_create; then the dimensions (at least 1); then PFHE_ERR_BAD_LENGTH unless len_in = batch*(in_dimension+1),
+ * len_ksk = in_dimension*ell*(out_dimension+1) and len_out = batch*(out_dimension+1).  The output must not overlap an input; it
+ * may be uninitialised, and a call is repeatable (no atomics). */
+int pfhe_tfhe_keyswitch_dev(int device, const uint64_t *lwe_in_dev, size_t len_in, size_t in_dimension, const uint64_t *ksk_dev,
+                            size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length,
+                            uint64_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_keyswitch(int device, const uint64_t *lwe_in, size_t len_in, size_t in_dimension, const uint64_t *ksk,
+                        size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *lwe_out,
+                        size_t len_out);
+int pfhe_tfhe32_keyswitch_dev(int device, const uint32_t *lwe_in_dev, size_t len_in, size_t in_dimension,
+                              const uint32_t *ksk_dev, size_t len_ksk, size_t out_dimension, uint32_t log_basis,
+                              size_t decompose_length, uint32_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe32_keyswitch(int device, const uint32_t *lwe_in, size_t len_in, size_t in_dimension, const uint32_t *ksk,
+                          size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *lwe_out,
+                          size_t len_out);
+/* The bootstrap handle — no reference counterpart as a whole (the reference has no bootstrap); its stages are the calls
+ * above around pfhe_tfhe*_blindrot_rotate_dev.  Per chunk of ciphertexts: modulus switch; ACC_e = X^{neg_b[e]} * TV written
+ * straight into the handle's accumulator (the rotation of pfhe_tfhe*_mul_monomial_each_to_dev, the test vector read in
+ * place); the blind rotation with n_steps = lwe_dimension on the switched exponents; sample extraction at index 0; and, when
+ * with_keyswitch is non-zero, the key switch from k*N to lwe_dimension.  With the phase b - <a,s> and BSK_i encrypting s_i the
+ * accumulator ends as X^{-phase~} * TV, whose coefficient 0 is TV[phase~] for phase~ < N and -TV[phase~ - N] otherwise.
+ *   lwe_in  batch*(n+1) words, n = lwe_dimension;  bsk  n Fourier GGSW keys as pfhe_tfhe*_blindrot_rotate_dev takes them;
+ *   tv      a GLWE ciphertext of (k+1)*N words shared by the batch (a trivially encrypted LUT is (0,...,0,tv)), or
+ *           batch*(k+1)*N words, one per ciphertext;
+ *   ksk     k*N x ks_ell x (n+1) words as pfhe_tfhe*_keyswitch_dev takes them; null with len_ksk 0 without a key switch;
+ *   lwe_out batch*(n+1) words, or batch*(k*N+1) without a key switch; it must not overlap an input.
+ * create runs the blind rotation's create first and returns its statuses in its order (pfhe_tfhe_blindrot_create), then its
+ * own: PFHE_ERR_BAD_ARGUMENT for glwe_dimension 0, lwe_dimension 0 and the key-switch basis's assert!s.  The handle borrows
+ * `fft`, owns a blind-rotation handle and, for `chunk` ciphertexts, the accumulator, the exponents, neg_b and (with a key
+ * switch) the extracted ciphertexts — everything is allocated here.  chunk 0 is the rotation's default, capped at about
+ * 256 MiB of accumulator.  A call only queues work on `stream` (no allocation, no host synchronisation), so one whole
+ * bootstrap can be captured into a HIP graph; a batch larger than the chunk runs chunk by chunk, all stages of a chunk
+ * first.  One holder at a time (PFHE_ERR_BUSY); PFHE_ERR_BAD_LENGTH for any length that does not fit the others. */
+typedef struct pfhe_tfhe_bootstrap_handle pfhe_tfhe_bootstrap_handle;
+typedef struct pfhe_tfhe32_bootstrap_handle pfhe_tfhe32_bootstrap_handle;
+int pfhe_tfhe_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                               size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
+                               size_t chunk, pfhe_tfhe_bootstrap_handle **out);
+void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h);
+int pfhe_tfhe_bootstrap_in_use(const pfhe_tfhe_bootstrap_handle *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h);  /* the rotation handle's scratch included */
+int pfhe_tfhe_bootstrap_dev(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                            size_t len_bsk, const uint64_t *tv_dev, size_t len_tv, const uint64_t *ksk_dev, size_t len_ksk,
+                            uint64_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_bootstrap(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                        const uint64_t *tv, size_t len_tv, const uint64_t *ksk, size_t len_ksk, uint64_t *lwe_out,
+                        size_t len_out);
+int pfhe_tfhe32_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                 size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
+                                 size_t chunk, pfhe_tfhe32_bootstrap_handle **out);
+void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h);
+int pfhe_tfhe32_bootstrap_in_use(const pfhe_tfhe32_bootstrap_handle *h);
+size_t pfhe_tfhe32_bootstrap_scratch_bytes(const pfhe_tfhe32_bootstrap_handle *h);
+int pfhe_tfhe32_bootstrap_dev(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                              size_t len_bsk, const uint32_t *tv_dev, size_t len_tv, const uint32_t *ksk_dev, size_t len_ksk,
+                              uint32_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe32_bootstrap(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                          const uint32_t *tv, size_t len_tv, const uint32_t *ksk, size_t len_ksk, uint32_t *lwe_out,
+                          size_t len_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -734,4 +734,121 @@ inline void mul_monomial_each_to_dev(const FullComplex64FftTable &fft, const uin
     check(pfhe_tfhe32_mul_monomial_each_to_dev(fft.handle(), a_dev, len, exps_dev, polys_per_exp, out_dev, stream));
 }
 
+// The project's own modulus switch (the reference has none): exps[e*n + i] = sw(a_{e,i}), neg_b[e] = (2N - sw(b_e)) mod 2N
+inline void lwe_modulus_switch_dev(int device, const uint64_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                                   uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b,
+                                   void *stream = nullptr) {
+    check(pfhe_tfhe_modswitch_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev, len_neg_b,
+                                  stream));
+}
+// Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial of a GLWE ciphertext
+inline void glwe_sample_extract(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe,
+                                size_t index, uint64_t *lwe, size_t len_lwe) {
+    check(pfhe_tfhe_sample_extract(fft.handle(), glwe_dimension, glwe, len_glwe, index, lwe, len_lwe));
+}
+inline void glwe_sample_extract_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *glwe_dev,
+                                    size_t len_glwe, size_t index, uint64_t *lwe_dev, size_t len_lwe, void *stream = nullptr) {
+    check(pfhe_tfhe_sample_extract_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe, stream));
+}
+// LWE key switch: out = (0, b) - sum_i sum_j d_{i,j} * KSK[i][j] (Lwe::add_mul_scalar_assign, lwe/single_message.rs:262-268,
+// with ApproxSignedBasis's digits); decompose_length 0 = the full BITS / log_basis
+inline void lwe_keyswitch(int device, const uint64_t *lwe_in, size_t len_in, size_t in_dimension, const uint64_t *ksk, size_t len_ksk,
+                          size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *lwe_out, size_t len_out) {
+    check(pfhe_tfhe_keyswitch(device, lwe_in, len_in, in_dimension, ksk, len_ksk, out_dimension, log_basis, decompose_length,
+                              lwe_out, len_out));
+}
+inline void lwe_keyswitch_dev(int device, const uint64_t *lwe_in_dev, size_t len_in, size_t in_dimension, const uint64_t *ksk_dev,
+                              size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length,
+                              uint64_t *lwe_out_dev, size_t len_out, void *stream = nullptr) {
+    check(pfhe_tfhe_keyswitch_dev(device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension, log_basis,
+                                  decompose_length, lwe_out_dev, len_out, stream));
+}
+
+inline void lwe_modulus_switch_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                                   uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b,
+                                   void *stream = nullptr) {
+    check(pfhe_tfhe32_modswitch_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev, len_neg_b,
+                                  stream));
+}
+inline void glwe_sample_extract(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe,
+                                size_t index, uint32_t *lwe, size_t len_lwe) {
+    check(pfhe_tfhe32_sample_extract(fft.handle(), glwe_dimension, glwe, len_glwe, index, lwe, len_lwe));
+}
+inline void glwe_sample_extract_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *glwe_dev,
+                                    size_t len_glwe, size_t index, uint32_t *lwe_dev, size_t len_lwe, void *stream = nullptr) {
+    check(pfhe_tfhe32_sample_extract_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe, stream));
+}
+inline void lwe_keyswitch(int device, const uint32_t *lwe_in, size_t len_in, size_t in_dimension, const uint32_t *ksk, size_t len_ksk,
+                          size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *lwe_out, size_t len_out) {
+    check(pfhe_tfhe32_keyswitch(device, lwe_in, len_in, in_dimension, ksk, len_ksk, out_dimension, log_basis, decompose_length,
+                              lwe_out, len_out));
+}
+inline void lwe_keyswitch_dev(int device, const uint32_t *lwe_in_dev, size_t len_in, size_t in_dimension, const uint32_t *ksk_dev,
+                              size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length,
+                              uint32_t *lwe_out_dev, size_t len_out, void *stream = nullptr) {
+    check(pfhe_tfhe32_keyswitch_dev(device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension, log_basis,
+                                  decompose_length, lwe_out_dev, len_out, stream));
+}
+
+// The batched programmable bootstrap (pfhe_tfhe_bootstrap_*): modulus switch, ACC = X^{-b~} * TV, the blind rotation over
+// lwe_dimension steps, sample extraction at index 0 and, with a key switch, the switch back to lwe_dimension.  Owns a
+// blind-rotation handle and every buffer between the stages; one holder at a time.  TfheBootstrap32: the u32 torus.
+class TfheBootstrap {
+  public:
+    TfheBootstrap(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                    size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, bool with_keyswitch = true,
+                    size_t chunk = 0) {
+        check(pfhe_tfhe_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                         ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_));
+    }
+    ~TfheBootstrap() { pfhe_tfhe_bootstrap_destroy(h_); }
+    TfheBootstrap(const TfheBootstrap &) = delete;
+    TfheBootstrap &operator=(const TfheBootstrap &) = delete;
+    pfhe_tfhe_bootstrap_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_bootstrap_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_bootstrap_scratch_bytes(h_); }
+    void bootstrap(const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const uint64_t *tv, size_t len_tv,
+                   const uint64_t *ksk, size_t len_ksk, uint64_t *lwe_out, size_t len_out) {
+        check(pfhe_tfhe_bootstrap(h_, lwe_in, len_in, bsk, len_bsk, tv, len_tv, ksk, len_ksk, lwe_out, len_out));
+    }
+    void bootstrap_dev(const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk, const uint64_t *tv_dev,
+                       size_t len_tv, const uint64_t *ksk_dev, size_t len_ksk, uint64_t *lwe_out_dev, size_t len_out,
+                       void *stream = nullptr) {
+        check(pfhe_tfhe_bootstrap_dev(h_, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev, len_ksk, lwe_out_dev,
+                                      len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe_bootstrap_handle *h_ = nullptr;
+};
+
+class TfheBootstrap32 {
+  public:
+    TfheBootstrap32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                    size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, bool with_keyswitch = true,
+                    size_t chunk = 0) {
+        check(pfhe_tfhe32_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                         ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_));
+    }
+    ~TfheBootstrap32() { pfhe_tfhe32_bootstrap_destroy(h_); }
+    TfheBootstrap32(const TfheBootstrap32 &) = delete;
+    TfheBootstrap32 &operator=(const TfheBootstrap32 &) = delete;
+    pfhe_tfhe32_bootstrap_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_bootstrap_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_bootstrap_scratch_bytes(h_); }
+    void bootstrap(const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const uint32_t *tv, size_t len_tv,
+                   const uint32_t *ksk, size_t len_ksk, uint32_t *lwe_out, size_t len_out) {
+        check(pfhe_tfhe32_bootstrap(h_, lwe_in, len_in, bsk, len_bsk, tv, len_tv, ksk, len_ksk, lwe_out, len_out));
+    }
+    void bootstrap_dev(const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk, const uint32_t *tv_dev,
+                       size_t len_tv, const uint32_t *ksk_dev, size_t len_ksk, uint32_t *lwe_out_dev, size_t len_out,
+                       void *stream = nullptr) {
+        check(pfhe_tfhe32_bootstrap_dev(h_, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev, len_ksk, lwe_out_dev,
+                                      len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe32_bootstrap_handle *h_ = nullptr;
+};
+
 }  // namespace pfhe

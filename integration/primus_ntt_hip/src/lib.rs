@@ -10,7 +10,8 @@
 //! batched, device-resident external product as [`HipExternalProduct`].  `FullComplex64FftTable`
 //! (crates/primus_fft/src/complex64/table.rs:47) -> [`HipFftTable`] behind `FftTable`, and the TFHE product in the
 //! Fourier domain as [`HipTfheExternalProduct`] / [`HipTfheExternalProduct32`], with the blind rotation over it as
-//! [`HipTfheBlindRotate`] / [`HipTfheBlindRotate32`].
+//! [`HipTfheBlindRotate`] / [`HipTfheBlindRotate32`] and the programmable bootstrap around that as
+//! [`HipTfheBootstrap`] / [`HipTfheBootstrap32`].
 mod ffi;
 
 use core::ffi::{c_int, CStr};
@@ -714,5 +715,138 @@ impl HipTfheBlindRotate32 {
 impl Drop for HipTfheBlindRotate32 {
     fn drop(&mut self) {
         unsafe { ffi::pfhe_tfhe32_blindrot_destroy(self.h) }
+    }
+}
+
+/// The batched programmable bootstrap around [`HipTfheBlindRotate`]: modulus switch, `ACC = X^{-b~} * TV`, the blind
+/// rotation over `lwe_dimension` steps, sample extraction at index 0 and, with a key switch, the switch back to
+/// `lwe_dimension`, all queued on the caller's stream.  Takes [`HipTfheBlindRotate`]'s arguments plus the LWE dimension and
+/// the key-switch basis; owns its rotation handle and every buffer between the stages.
+/// [`HipTfheBootstrap32`]: the u32 torus.
+pub struct HipTfheBootstrap {
+    h: *mut ffi::pfhe_tfhe_bootstrap_handle,
+}
+impl HipTfheBootstrap {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize, lwe_dimension: usize,
+               ks_log_basis: u32, ks_decompose_length: usize, with_keyswitch: bool) -> Result<Self, c_int> {
+        let mut h = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                                       ks_log_basis, ks_decompose_length, with_keyswitch as c_int, 0, &mut h) } {
+            ffi::PFHE_OK => Ok(Self { h }),
+            e => Err(e),
+        }
+    }
+    /// `lwe_in_dev`: batch x (n+1) words; `bsk_dev`: n Fourier GGSW keys (`len_bsk` counts complex values); `tv_dev`: one
+    /// GLWE test vector or one per ciphertext; `ksk_dev`: k*N x ell x (n+1) words, null with `len_ksk` 0 without a key
+    /// switch; `lwe_out_dev`: batch x (n+1) words (batch x (k*N+1) without a key switch), disjoint from every input
+    pub unsafe fn bootstrap_dev(&mut self, lwe_in_dev: *const u64, len_in: usize, bsk_dev: *const f64, len_bsk: usize,
+                                tv_dev: *const u64, len_tv: usize, ksk_dev: *const u64, len_ksk: usize, lwe_out_dev: *mut u64,
+                                len_out: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe_bootstrap_dev(self.h, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev,
+                                                    len_ksk, lwe_out_dev, len_out, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheBootstrap {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe_bootstrap_destroy(self.h) }
+    }
+}
+
+/// The stateless steps of a bootstrap on the u64 torus: the project's own modulus switch (the reference has none), sample
+/// extraction (`Rlwe::extract_lwe_with_index`, rlwe/coeff.rs:194-227, per mask polynomial) and the LWE key switch
+/// (`Lwe::add_mul_scalar_assign`, lwe/single_message.rs:262-268, with `ApproxSignedBasis`'s digits).
+pub unsafe fn tfhe_modswitch_dev(device: c_int, lwe_dev: *const u64, len_lwe: usize, lwe_dimension: usize, log_n: u32,
+                                 exps_dev: *mut u32, len_exps: usize, neg_b_dev: *mut u32, len_neg_b: usize,
+                                 stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_modswitch_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev,
+                                                len_neg_b, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe_sample_extract_dev(fft: &HipFftTable, glwe_dimension: usize, glwe_dev: *const u64, len_glwe: usize,
+                                      index: usize, lwe_dev: *mut u64, len_lwe: usize, stream: *mut core::ffi::c_void)
+                                      -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_sample_extract_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe,
+                                                     stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe_keyswitch_dev(device: c_int, lwe_in_dev: *const u64, len_in: usize, in_dimension: usize,
+                                 ksk_dev: *const u64, len_ksk: usize, out_dimension: usize, log_basis: u32,
+                                 decompose_length: usize, lwe_out_dev: *mut u64, len_out: usize,
+                                 stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_keyswitch_dev(device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension,
+                                                log_basis, decompose_length, lwe_out_dev, len_out, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+
+pub struct HipTfheBootstrap32 {
+    h: *mut ffi::pfhe_tfhe32_bootstrap_handle,
+}
+impl HipTfheBootstrap32 {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize, lwe_dimension: usize,
+               ks_log_basis: u32, ks_decompose_length: usize, with_keyswitch: bool) -> Result<Self, c_int> {
+        let mut h = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe32_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                                       ks_log_basis, ks_decompose_length, with_keyswitch as c_int, 0, &mut h) } {
+            ffi::PFHE_OK => Ok(Self { h }),
+            e => Err(e),
+        }
+    }
+    /// `lwe_in_dev`: batch x (n+1) words; `bsk_dev`: n Fourier GGSW keys (`len_bsk` counts complex values); `tv_dev`: one
+    /// GLWE test vector or one per ciphertext; `ksk_dev`: k*N x ell x (n+1) words, null with `len_ksk` 0 without a key
+    /// switch; `lwe_out_dev`: batch x (n+1) words (batch x (k*N+1) without a key switch), disjoint from every input
+    pub unsafe fn bootstrap_dev(&mut self, lwe_in_dev: *const u32, len_in: usize, bsk_dev: *const f64, len_bsk: usize,
+                                tv_dev: *const u32, len_tv: usize, ksk_dev: *const u32, len_ksk: usize, lwe_out_dev: *mut u32,
+                                len_out: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe32_bootstrap_dev(self.h, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev,
+                                                    len_ksk, lwe_out_dev, len_out, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheBootstrap32 {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe32_bootstrap_destroy(self.h) }
+    }
+}
+
+/// The stateless steps of a bootstrap on the u32 torus: the project's own modulus switch (the reference has none), sample
+/// extraction (`Rlwe::extract_lwe_with_index`, rlwe/coeff.rs:194-227, per mask polynomial) and the LWE key switch
+/// (`Lwe::add_mul_scalar_assign`, lwe/single_message.rs:262-268, with `ApproxSignedBasis`'s digits).
+pub unsafe fn tfhe32_modswitch_dev(device: c_int, lwe_dev: *const u32, len_lwe: usize, lwe_dimension: usize, log_n: u32,
+                                 exps_dev: *mut u32, len_exps: usize, neg_b_dev: *mut u32, len_neg_b: usize,
+                                 stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_modswitch_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev,
+                                                len_neg_b, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe32_sample_extract_dev(fft: &HipFftTable, glwe_dimension: usize, glwe_dev: *const u32, len_glwe: usize,
+                                      index: usize, lwe_dev: *mut u32, len_lwe: usize, stream: *mut core::ffi::c_void)
+                                      -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_sample_extract_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe,
+                                                     stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe32_keyswitch_dev(device: c_int, lwe_in_dev: *const u32, len_in: usize, in_dimension: usize,
+                                 ksk_dev: *const u32, len_ksk: usize, out_dimension: usize, log_basis: u32,
+                                 decompose_length: usize, lwe_out_dev: *mut u32, len_out: usize,
+                                 stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_keyswitch_dev(device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension,
+                                                log_basis, decompose_length, lwe_out_dev, len_out, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
     }
 }

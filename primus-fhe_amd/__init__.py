@@ -12,9 +12,10 @@ from .lattice import (BlindRotateContext, BlindRotateContext32, blind_rotate, bl
                       add_dcrt_glev_mul_crt_poly_assign_dev, glev_mul_big_uint_poly_to_dev, glev_mul_crt_poly_to_dev,
                       mul_dcrt_ggsw_to, mul_dcrt_ggsw_to_dev, profile_mul_dcrt_ggsw_to_dev)
 from .ntt import NttError, U32DcrtTable, U32NttTable, U64DcrtTable, U64NttTable  # noqa: F401
-from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateContext, TfheFftContext,  # noqa: F401
-                   tfhe_blind_rotate, tfhe_blind_rotate_dev, tfhe_external_product_to, tfhe_external_product_to_dev,
-                   write_fourier_form)
+from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateContext, TfheBootstrapContext,  # noqa: F401
+                   TfheFftContext, glwe_sample_extract, glwe_sample_extract_dev, lwe_keyswitch, lwe_keyswitch_dev,
+                   lwe_modulus_switch_dev, tfhe_blind_rotate, tfhe_blind_rotate_dev, tfhe_bootstrap, tfhe_bootstrap_dev,
+                   tfhe_external_product_to, tfhe_external_product_to_dev, write_fourier_form)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -25,4 +26,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "glev_mul_big_uint_poly_to_dev", "BlindRotateContext", "BlindRotateContext32", "blind_rotate", "blind_rotate_dev",
            "FullComplex64FftTable", "ApproxSignedBasis", "TfheFftContext", "tfhe_external_product_to",
            "tfhe_external_product_to_dev", "write_fourier_form", "TfheBlindRotateContext", "tfhe_blind_rotate",
-           "tfhe_blind_rotate_dev", "build", "lib", "library_path", "status_string"]
+           "tfhe_blind_rotate_dev", "lwe_modulus_switch_dev", "glwe_sample_extract", "glwe_sample_extract_dev",
+           "lwe_keyswitch", "lwe_keyswitch_dev", "TfheBootstrapContext", "tfhe_bootstrap", "tfhe_bootstrap_dev", "build", "lib", "library_path", "status_string"]

@@ -195,6 +195,19 @@ def _declare(lib: C.CDLL) -> None:
         sig(br + "rotate_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
         sig(br + "rotate", ci, vp, vp, sz, f64p, sz, vp, sz)
         sig(tp + "mul_monomial_each_to_dev", ci, vp, vp, sz, vp, sz, vp, vp)
+        # the bootstrap around the rotation: modulus switch, sample extraction, key switch and the handle over all of them
+        sig(tp + "modswitch_dev", ci, ci, vp, sz, sz, u32, vp, sz, vp, sz, vp)
+        sig(tp + "sample_extract_dev", ci, vp, sz, vp, sz, sz, vp, sz, vp)
+        sig(tp + "sample_extract", ci, vp, sz, vp, sz, sz, vp, sz)
+        sig(tp + "keyswitch_dev", ci, ci, vp, sz, sz, vp, sz, sz, u32, sz, vp, sz, vp)
+        sig(tp + "keyswitch", ci, ci, vp, sz, sz, vp, sz, sz, u32, sz, vp, sz)
+        bs = tp + "bootstrap"
+        sig(bs + "_create", ci, vp, sz, u32, sz, sz, u32, sz, ci, sz, C.POINTER(vp))
+        sig(bs + "_destroy", None, vp)
+        sig(bs + "_in_use", ci, vp)
+        sig(bs + "_scratch_bytes", sz, vp)
+        sig(bs + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp, sz, vp)
+        sig(bs, ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp, sz)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)
     sig("pfhe_dcrt_transform_num_passes", ci, vp)

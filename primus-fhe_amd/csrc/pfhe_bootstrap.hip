@@ -1,0 +1,696 @@
+// pfhe_bootstrap.hip — the steps of a TFHE programmable bootstrap around the blind rotation, and the handle that runs
+// them in order (include/pfhe.h: pfhe_tfhe{,32}_modswitch_dev, _sample_extract*, _keyswitch*, _bootstrap_*).
+//
+//   modulus switch     LWE words -> exponents modulo 2N.  The reference has no modulus switching; the rule is this
+//                      project's own: sw(w) = (((w >> (shift-1)) + 1) >> 1) & (2N-1), shift = BITS - log_n - 1, i.e.
+//                      round(w 2N / 2^BITS) with ties up, computed without overflow.
+//   accumulator init   ACC_e = X^{neg_b[e]} TV, the rotation of pfhe_tfhe*_mul_monomial_each_to_dev with the test vector
+//                      read in place (one shared by the batch, or one per ciphertext).
+//   blind rotation     the existing handle (pfhe_fft.hip), called as it is.
+//   sample extraction  Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial.
+//   key switch         out = (0, b) - sum_i sum_j d_{i,j} KSK[i][j], a sequence of Lwe::add_mul_scalar_assign
+//                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_step of
+//                      pfhe_fft_device.hpp, the product's own).
+// Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+
+#include "pfhe_fft_device.hpp"
+#include "pfhe_tfhe_handles.hpp"
+
+using namespace pfhe;
+
+namespace pfhe {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr u32 kMaxLogN = 14;
+
+// ---------------- modulus switch ----------------
+
+// one thread per word of the batch: word i of ciphertext e goes to exps[e n + i] (i < n) or, negated, to neg_b[e] (i = n)
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_modswitch_kernel(const W *__restrict__ lwe, u32 *__restrict__ exps,
+                                                                  u32 *__restrict__ neg_b, u32 n, u32 log_n, u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u64 e = t / (n + 1);
+    const u32 i = (u32)(t - e * (n + 1));
+    const u32 shift = 8 * sizeof(W) - log_n - 1, two_n_mask = (2u << log_n) - 1;
+    const u32 v = (u32)(((lwe[t] >> (shift - 1)) + 1) >> 1) & two_n_mask;
+    if (i < n)
+        exps[e * n + i] = v;
+    else
+        neg_b[e] = ((2u << log_n) - v) & two_n_mask;
+}
+
+// ---------------- accumulator init ----------------
+
+// ACC_e = X^{neg_b[e]} TV_e, one thread per accumulator word.  X^r p [j] = +-p[(j - r) mod N], the wrapped part negated;
+// r >= N negates the other part (the rule of tfhe_blindrot_glue_kernel).  tv_stride: words between the test vectors of
+// consecutive ciphertexts, 0 when one is shared by the batch.
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_acc_init_kernel(const W *__restrict__ tv, W *__restrict__ acc,
+                                                                 const u32 *__restrict__ neg_b, u32 rows, u32 log_n,
+                                                                 u64 tv_stride, u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u32 n = 1u << log_n, mask = n - 1;
+    const u64 poly = t >> log_n, e = poly / rows;
+    const u32 row = (u32)(poly - e * rows);
+    const u32 r = neg_b[e] & (2 * n - 1);
+    const bool high = r >= n;
+    const u32 rot = high ? r - n : r;
+    const u32 j = (u32)(t & mask);
+    const W v = tv[e * tv_stride + ((u64)row << log_n) + ((j - rot) & mask)];
+    acc[t] = ((j < rot) != high) ? (W)0 - v : v;
+}
+
+// ---------------- sample extraction ----------------
+
+// one thread per output word: out[jN + i] = A_j[h - i] (i <= h) or -A_j[N + h - i] (i > h), out[kN] = B[h]
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_sample_extract_kernel(const W *__restrict__ glwe, W *__restrict__ lwe, u32 k,
+                                                                       u32 log_n, u32 h, u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u32 n = 1u << log_n;
+    const u64 out_len = ((u64)k << log_n) + 1;
+    const u64 e = t / out_len, c = t - e * out_len;
+    const W *ct = glwe + e * ((u64)(k + 1) << log_n);
+    if (c == out_len - 1) {
+        lwe[t] = ct[((u64)k << log_n) + h];
+        return;
+    }
+    const u32 i = (u32)(c & (n - 1));
+    const W *a = ct + (c - i);
+    lwe[t] = i <= h ? a[h - i] : (W)0 - a[n + h - i];
+}
+
+// ---------------- key switch ----------------
+//
+// A small integer GEMM: M = batch, K = in_dimension * ell, N = out_dimension + 1.  One workgroup owns kKsTileM ciphertexts
+// x kKsTileN output columns; a thread owns kKsRows ciphertexts (its wave's) x kKsCols columns (its lane's, kKsLanes apart)
+// and keeps their sums in registers.  The workgroup walks the mask words in groups of `ki`: first every (ciphertext, mask
+// word) pair of the group gets its ell signed digits from ONE thread, which writes them to LDS as words; then every thread
+// streams the group's key rows, coalesced along the columns and kKsUnroll rows in flight at a time, against the digits of
+// its ciphertexts, which all lanes of a wave read from the same LDS address (a broadcast).  ki * ell <= kKsMaxRows bounds the LDS at kKsMaxRows * kKsTileM words.
+constexpr int kKsLanes = 64, kKsWaves = kThreads / kKsLanes;
+constexpr int kKsRows = 8, kKsCols = 2;
+constexpr int kKsTileM = kKsWaves * kKsRows, kKsTileN = kKsLanes * kKsCols;
+constexpr u32 kKsMaxRows = 64;
+constexpr int kKsUnroll = 4;
+
+struct KsShape {
+    u32 in_dim, out_dim, log_basis, ell, drop_bits, ki;
+};
+
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_keyswitch_kernel(const W *__restrict__ lwe_in, const W *__restrict__ ksk,
+                                                                  W *__restrict__ lwe_out, KsShape s, u64 batch) {
+    __shared__ W dig[kKsMaxRows * kKsTileM];  // [mask word of the group][level][ciphertext of the tile]
+    const u32 lane = threadIdx.x % kKsLanes, wave = threadIdx.x / kKsLanes;
+    const u32 cols = s.out_dim + 1;
+    const u32 c0 = blockIdx.x * kKsTileN + lane;
+    const u64 e0 = (u64)blockIdx.y * kKsTileM;
+    const u64 in_stride = (u64)s.in_dim + 1;
+    W acc[kKsRows][kKsCols];
+#pragma unroll
+    for (int r = 0; r < kKsRows; ++r)
+#pragma unroll
+        for (int c = 0; c < kKsCols; ++c) acc[r][c] = 0;
+
+    // the key columns of this thread; a column past the end reads the last one instead (its sums are never stored), so that
+    // no load of the inner loop sits behind a branch
+    const W *key[kKsCols];
+#pragma unroll
+    for (int c = 0; c < kKsCols; ++c) key[c] = ksk + min(c0 + c * kKsLanes, cols - 1);
+
+    // the pair this thread decomposes in every group: mask word ii of the group, ciphertext ei of the tile
+    const u32 ii = threadIdx.x % s.ki, ei = threadIdx.x / s.ki;
+    for (u32 i0 = 0; i0 < s.in_dim; i0 += s.ki) {
+        if (ei < (u32)kKsTileM) {
+            const bool live = e0 + ei < batch && i0 + ii < s.in_dim;
+            const W v = live ? lwe_in[(e0 + ei) * in_stride + i0 + ii] : (W)0;
+            u32 carry = init_carry(v, s.drop_bits);
+            for (u32 l = 0; l < s.ell; ++l) {
+                const u32 shift = s.drop_bits + l * s.log_basis;
+                const W field = (v >> shift) & (((W)1 << s.log_basis) - 1);
+                const W carry_in = (W)carry;
+                (void)digit_step(v, shift, s.log_basis, carry);  // the rule: it decides the carry out of this level
+                // the digit as a word: field + carry_in - carry_out * B, which is digit_step's value for any log_basis
+                dig[(ii * s.ell + l) * kKsTileM + ei] = field + carry_in - ((W)carry << s.log_basis);
+            }
+        }
+        __syncthreads();
+        const u32 rows = min(s.ki, s.in_dim - i0) * s.ell;
+        const u64 key_row = (u64)i0 * s.ell;
+        u32 row = 0;
+        // kKsUnroll rows at a time: all their key words are requested before the first is used
+        for (; row + kKsUnroll <= rows; row += kKsUnroll) {
+            W kv[kKsUnroll][kKsCols];
+#pragma unroll
+            for (int u = 0; u < kKsUnroll; ++u)
+#pragma unroll
+                for (int c = 0; c < kKsCols; ++c) kv[u][c] = key[c][(key_row + row + u) * cols];
+#pragma unroll
+            for (int u = 0; u < kKsUnroll; ++u)
+#pragma unroll
+                for (int r = 0; r < kKsRows; ++r) {
+                    const W d = dig[(row + u) * kKsTileM + wave * kKsRows + r];
+#pragma unroll
+                    for (int c = 0; c < kKsCols; ++c) acc[r][c] += d * kv[u][c];
+                }
+        }
+        for (; row < rows; ++row) {
+            W kv[kKsCols];
+#pragma unroll
+            for (int c = 0; c < kKsCols; ++c) kv[c] = key[c][(key_row + row) * cols];
+#pragma unroll
+            for (int r = 0; r < kKsRows; ++r) {
+                const W d = dig[row * kKsTileM + wave * kKsRows + r];
+#pragma unroll
+                for (int c = 0; c < kKsCols; ++c) acc[r][c] += d * kv[c];
+            }
+        }
+        __syncthreads();  // the next group overwrites the digits
+    }
+#pragma unroll
+    for (int r = 0; r < kKsRows; ++r) {
+        const u64 e = e0 + wave * kKsRows + r;
+        if (e >= batch) continue;
+#pragma unroll
+        for (int c = 0; c < kKsCols; ++c) {
+            const u32 col = c0 + c * kKsLanes;
+            if (col >= cols) continue;
+            const W b = col == s.out_dim ? lwe_in[e * in_stride + s.in_dim] : (W)0;
+            lwe_out[e * cols + col] = b - acc[r][c];
+        }
+    }
+}
+
+// ---------------- launches (arguments already checked) ----------------
+
+inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+inline int flat_grid(u64 total, u32 &grid) {
+    const u64 g = (total + kThreads - 1) / kThreads;
+    if (g > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
+    grid = (u32)g;
+    return PFHE_OK;
+}
+
+template <class W>
+int launch_modswitch(const W *lwe, u32 n, u32 log_n, u32 *exps, u32 *neg_b, u64 batch, hipStream_t s) {
+    u32 grid = 0;
+    const u64 total = batch * ((u64)n + 1);
+    PFHE_TRY(flat_grid(total, grid));
+    hipLaunchKernelGGL(tfhe_modswitch_kernel<W>, dim3(grid), dim3(kThreads), 0, s, lwe, exps, neg_b, n, log_n, total);
+    PFHE_HIP(hipGetLastError());
+    return PFHE_OK;
+}
+
+template <class W>
+int launch_acc_init(const W *tv, u64 tv_stride, W *acc, const u32 *neg_b, u32 rows, u32 log_n, u64 batch, hipStream_t s) {
+    u32 grid = 0;
+    const u64 total = (batch * rows) << log_n;
+    PFHE_TRY(flat_grid(total, grid));
+    hipLaunchKernelGGL(tfhe_acc_init_kernel<W>, dim3(grid), dim3(kThreads), 0, s, tv, acc, neg_b, rows, log_n, tv_stride, total);
+    PFHE_HIP(hipGetLastError());
+    return PFHE_OK;
+}
+
+template <class W>
+int launch_sample_extract(const W *glwe, W *lwe, u32 k, u32 log_n, u32 h, u64 batch, hipStream_t s) {
+    u32 grid = 0;
+    const u64 total = batch * (((u64)k << log_n) + 1);
+    PFHE_TRY(flat_grid(total, grid));
+    hipLaunchKernelGGL(tfhe_sample_extract_kernel<W>, dim3(grid), dim3(kThreads), 0, s, glwe, lwe, k, log_n, h, total);
+    PFHE_HIP(hipGetLastError());
+    return PFHE_OK;
+}
+
+template <class W>
+int launch_keyswitch(const W *lwe_in, const W *ksk, W *lwe_out, KsShape sh, u64 batch, hipStream_t s) {
+    const u64 gx = ((u64)sh.out_dim + 1 + kKsTileN - 1) / kKsTileN;
+    for (u64 done = 0; done < batch;) {  // grid.y holds 65535 tiles
+        const u64 cur = std::min<u64>(batch - done, (u64)65535 * kKsTileM);
+        hipLaunchKernelGGL(tfhe_keyswitch_kernel<W>, dim3((u32)gx, (u32)((cur + kKsTileM - 1) / kKsTileM)), dim3(kThreads), 0, s,
+                           lwe_in + done * ((u64)sh.in_dim + 1), ksk, lwe_out + done * ((u64)sh.out_dim + 1), sh, cur);
+        PFHE_HIP(hipGetLastError());
+        done += cur;
+    }
+    return PFHE_OK;
+}
+
+// ---------------- the stateless entry points ----------------
+
+template <class W>
+int modswitch_dev(int device, const W *lwe, size_t len_lwe, size_t lwe_dimension, uint32_t log_n, uint32_t *exps,
+                  size_t len_exps, uint32_t *neg_b, size_t len_neg_b, hipStream_t s) {
+    if (log_n == 0 || log_n > kMaxLogN) {
+        set_last_error("modulus switch: log_n must be in 1..14");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    if (lwe_dimension == 0 || lwe_dimension >= 0xffffffffull) {
+        set_last_error("modulus switch: lwe_dimension must be in 1..2^32-2");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    if (len_lwe % (lwe_dimension + 1) != 0 || len_neg_b != len_lwe / (lwe_dimension + 1) ||
+        len_exps != len_neg_b * lwe_dimension) {
+        set_last_error("modulus switch: lwe must be batch*(n+1) words, exps batch*n and neg_b batch exponents");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (len_lwe == 0) return PFHE_OK;
+    if (!lwe || !exps || !neg_b) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_TRY(capi_check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return launch_modswitch<W>(lwe, (u32)lwe_dimension, log_n, exps, neg_b, len_neg_b, s);
+}
+
+constexpr const char *kExtractLengths = "sample extraction: glwe must be batch*(k+1)*N words and lwe batch*(k*N+1)";
+
+template <class W>
+int sample_extract_check(const pfhe_fft *f, size_t k, size_t len_glwe, size_t index, size_t len_lwe) {
+    if (!f) return PFHE_ERR_BAD_ARGUMENT;
+    if (k == 0 || k > 64) {
+        set_last_error("sample extraction: glwe_dimension must be in 1..64");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    if (index >= f->n) {
+        set_last_error("sample extraction: index must be below N");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    if (len_glwe % ((k + 1) * f->n) != 0 || len_lwe != len_glwe / ((k + 1) * f->n) * (k * f->n + 1)) {
+        set_last_error(kExtractLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    return PFHE_OK;
+}
+
+template <class W>
+int sample_extract_dev(const pfhe_fft *f, size_t k, const W *glwe, size_t len_glwe, size_t index, W *lwe, size_t len_lwe,
+                       hipStream_t s) {
+    PFHE_TRY(sample_extract_check<W>(f, k, len_glwe, index, len_lwe));
+    if (len_glwe == 0) return PFHE_OK;
+    if (!glwe || !lwe) return PFHE_ERR_BAD_ARGUMENT;
+    if (overlaps(glwe, len_glwe * sizeof(W), lwe, len_lwe * sizeof(W))) {
+        set_last_error("sample extraction: the output must not overlap the input");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    DeviceGuard g(f->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return launch_sample_extract<W>(glwe, lwe, (u32)k, f->log_n, (u32)index, len_glwe / ((k + 1) * f->n), s);
+}
+
+template <class W>
+int sample_extract_host(const pfhe_fft *f, size_t k, const W *glwe, size_t len_glwe, size_t index, W *lwe, size_t len_lwe) {
+    PFHE_TRY(sample_extract_check<W>(f, k, len_glwe, index, len_lwe));
+    if (len_glwe == 0) return PFHE_OK;
+    if (!glwe || !lwe) return PFHE_ERR_BAD_ARGUMENT;
+    DeviceGuard g(f->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(f->device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *a = nullptr, *o = nullptr;
+    PFHE_TRY(st.upload(glwe, len_glwe * sizeof(W), &a));
+    PFHE_TRY(st.alloc(len_lwe * sizeof(W), &o));
+    PFHE_TRY(sample_extract_dev<W>(f, k, (const W *)a, len_glwe, index, (W *)o, len_lwe, st.stream()));
+    PFHE_TRY(st.download(lwe, o, len_lwe * sizeof(W)));
+    return st.finish();
+}
+
+// ApproxSignedBasis::new's assert!s first, then the dimensions
+template <class W>
+int keyswitch_shape(size_t in_dimension, size_t out_dimension, uint32_t log_basis, size_t decompose_length, KsShape &sh) {
+    u32 ell = 0, drop = 0;
+    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
+    if (in_dimension == 0 || out_dimension == 0 || in_dimension >= 0x7fffffffull || out_dimension >= 0x7fffffffull) {
+        set_last_error("key switch: both dimensions must be in 1..2^31-2");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    sh = KsShape{(u32)in_dimension, (u32)out_dimension, log_basis, ell, drop,
+                 std::max<u32>(1, std::min<u32>(kKsMaxRows / ell, kThreads / kKsTileM))};
+    return PFHE_OK;
+}
+
+// ... then the lengths
+template <class W>
+int keyswitch_check(size_t len_in, size_t in_dimension, size_t len_ksk, size_t out_dimension, uint32_t log_basis,
+                    size_t decompose_length, size_t len_out, KsShape &sh) {
+    PFHE_TRY(keyswitch_shape<W>(in_dimension, out_dimension, log_basis, decompose_length, sh));
+    if (len_in % (in_dimension + 1) != 0 || len_ksk != in_dimension * sh.ell * (out_dimension + 1) ||
+        len_out != len_in / (in_dimension + 1) * (out_dimension + 1)) {
+        set_last_error("key switch: lwe_in must be batch*(in_dimension+1) words, ksk in_dimension*ell*(out_dimension+1) and "
+                       "lwe_out batch*(out_dimension+1)");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    return PFHE_OK;
+}
+
+template <class W>
+int keyswitch_dev(int device, const W *lwe_in, size_t len_in, size_t in_dimension, const W *ksk, size_t len_ksk,
+                  size_t out_dimension, uint32_t log_basis, size_t decompose_length, W *lwe_out, size_t len_out,
+                  hipStream_t s) {
+    KsShape sh{};
+    PFHE_TRY(keyswitch_check<W>(len_in, in_dimension, len_ksk, out_dimension, log_basis, decompose_length, len_out, sh));
+    if (len_in == 0) return PFHE_OK;
+    if (!lwe_in || !ksk || !lwe_out) return PFHE_ERR_BAD_ARGUMENT;
+    if (overlaps(lwe_in, len_in * sizeof(W), lwe_out, len_out * sizeof(W)) ||
+        overlaps(ksk, len_ksk * sizeof(W), lwe_out, len_out * sizeof(W))) {
+        set_last_error("key switch: the output must not overlap an input");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    PFHE_TRY(capi_check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return launch_keyswitch<W>(lwe_in, ksk, lwe_out, sh, len_in / (in_dimension + 1), s);
+}
+
+template <class W>
+int keyswitch_host(int device, const W *lwe_in, size_t len_in, size_t in_dimension, const W *ksk, size_t len_ksk,
+                   size_t out_dimension, uint32_t log_basis, size_t decompose_length, W *lwe_out, size_t len_out) {
+    KsShape sh{};
+    PFHE_TRY(keyswitch_check<W>(len_in, in_dimension, len_ksk, out_dimension, log_basis, decompose_length, len_out, sh));
+    if (len_in == 0) return PFHE_OK;
+    if (!lwe_in || !ksk || !lwe_out) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_TRY(capi_check_device(device));
+    DeviceGuard g(device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *a = nullptr, *k = nullptr, *o = nullptr;
+    PFHE_TRY(st.upload(lwe_in, len_in * sizeof(W), &a));
+    PFHE_TRY(st.upload(ksk, len_ksk * sizeof(W), &k));
+    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
+    PFHE_TRY(launch_keyswitch<W>((const W *)a, (const W *)k, (W *)o, sh, len_in / (in_dimension + 1), st.stream()));
+    PFHE_TRY(st.download(lwe_out, o, len_out * sizeof(W)));
+    return st.finish();
+}
+
+}  // namespace
+}  // namespace pfhe
+
+// ---------------- the bootstrap handle ----------------
+
+// Owns a blind-rotation handle and, for `chunk` ciphertexts, the accumulator, the switched exponents, neg_b and (when a key
+// switch follows) the extracted LWE ciphertexts: all allocated at creation.
+template <class R, class W>
+struct TfheBootstrapCore {
+    R *rot = nullptr;  // owned
+    PlanGuard guard;   // one holder at a time, successive calls on different streams ordered
+    const pfhe_fft *fft = nullptr;
+    u32 k = 1, n = 0;  // GLWE and LWE dimensions
+    bool with_keyswitch = false;
+    KsShape ks{};
+    size_t chunk = 1, key_len = 0, bytes = 0;
+    W *acc = nullptr, *extracted = nullptr;
+    u32 *exps = nullptr, *neg_b = nullptr;
+    ~TfheBootstrapCore() {
+        if (!rot) return;
+        {
+            DeviceGuard g(fft->device);
+            for (void *b : {(void *)acc, (void *)extracted, (void *)exps, (void *)neg_b})
+                if (b) (void)counted_free(b);
+        }
+        delete rot;
+    }
+};
+struct pfhe_tfhe_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe_blindrot, u64> {};
+struct pfhe_tfhe32_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe32_blindrot, u32> {};
+
+namespace {
+
+constexpr const char *kBootstrapBusy = "TFHE bootstrap handle in use by another thread (one handle per thread)";
+constexpr const char *kBootstrapLengths =
+    "TFHE bootstrap: lwe_in must be batch*(n+1) words, bsk n*(k+1)*ell*(k+1)*N complex values, tv (k+1)*N or batch*(k+1)*N "
+    "words, ksk k*N*ks_ell*(n+1) words (0 without a key switch) and lwe_out batch*(n+1) (batch*(k*N+1) without)";
+constexpr size_t kDefaultAccBytes = 256ull << 20;
+
+// the rotation's create first (its statuses, in its order), then what is the bootstrap's own
+template <class H, class W>
+int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                     size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
+                     size_t chunk, H **out) {
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    auto h = std::make_unique<H>();
+    PFHE_TRY(tfhe_blindrot_create_handle(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->rot));
+    h->fft = fft;
+    h->k = (u32)glwe_dimension;
+    h->with_keyswitch = with_keyswitch != 0;
+    const size_t glwe = h->rot->glwe, ext = glwe_dimension * fft->n + 1;
+    if (glwe_dimension == 0 || lwe_dimension == 0 || lwe_dimension >= 0x7fffffffull) {
+        set_last_error("TFHE bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    h->n = (u32)lwe_dimension;
+    h->key_len = h->rot->key_len;
+    if (h->with_keyswitch) PFHE_TRY(keyswitch_shape<W>(ext - 1, lwe_dimension, ks_log_basis, ks_decompose_length, h->ks));
+    // chunk 0: the rotation's default, capped at about 256 MiB of accumulator
+    h->chunk = chunk ? h->rot->chunk : std::min(h->rot->chunk, std::max<size_t>(1, kDefaultAccBytes / (glwe * sizeof(W))));
+    DeviceGuard g(fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    const size_t sizes[] = {h->chunk * glwe * sizeof(W), h->with_keyswitch ? h->chunk * ext * sizeof(W) : 0,
+                            h->chunk * lwe_dimension * sizeof(u32), h->chunk * sizeof(u32)};
+    void **bufs[] = {(void **)&h->acc, (void **)&h->extracted, (void **)&h->exps, (void **)&h->neg_b};
+    for (int i = 0; i < 4; ++i) {
+        if (!sizes[i]) continue;
+        PFHE_HIP(counted_malloc(bufs[i], sizes[i]));
+        h->bytes += sizes[i];
+    }
+    PFHE_TRY(h->guard.init(fft->device));
+    *out = h.release();
+    return PFHE_OK;
+}
+
+template <class W, class H>
+int bootstrap_check(const H *h, size_t len_in, size_t len_bsk, size_t len_tv, size_t len_ksk, size_t len_out, u64 &batch) {
+    const size_t glwe = h->rot->glwe, ext = (size_t)h->k * h->fft->n + 1;
+    const size_t out_words = h->with_keyswitch ? (size_t)h->n + 1 : ext;
+    const size_t ksk_words = h->with_keyswitch ? (ext - 1) * h->ks.ell * ((size_t)h->n + 1) : 0;
+    batch = len_in / ((size_t)h->n + 1);
+    if (len_in % ((size_t)h->n + 1) != 0 || len_bsk != (size_t)h->n * h->key_len || (len_tv != glwe && len_tv != batch * glwe) ||
+        len_ksk != ksk_words || len_out != batch * out_words) {
+        set_last_error(kBootstrapLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    return PFHE_OK;
+}
+
+template <class W, class H>
+int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
+                  const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out, hipStream_t s) {
+    if (!h || !h->rot) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
+    if (!h->with_keyswitch && (ksk || len_ksk)) {
+        set_last_error("TFHE bootstrap: a handle without a key switch takes no key-switch key");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    u64 batch = 0;
+    PFHE_TRY((bootstrap_check<W>(h, len_in, len_bsk, len_tv, len_ksk, len_out, batch)));
+    if (batch == 0) return PFHE_OK;
+    if (!lwe_in || !bsk || !tv || !lwe_out || (h->with_keyswitch && !ksk)) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(bsk);
+    const size_t out_bytes = len_out * sizeof(W);
+    if (overlaps(lwe_in, len_in * sizeof(W), lwe_out, out_bytes) || overlaps(tv, len_tv * sizeof(W), lwe_out, out_bytes) ||
+        overlaps(bsk, len_bsk * 2 * sizeof(double), lwe_out, out_bytes) ||
+        (ksk && overlaps(ksk, len_ksk * sizeof(W), lwe_out, out_bytes))) {
+        set_last_error("TFHE bootstrap: the output must not overlap an input");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    const pfhe_fft &f = *h->fft;
+    DeviceGuard g(f.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    const size_t glwe = h->rot->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
+    const size_t out_words = h->with_keyswitch ? in_words : ext;
+    const u64 tv_stride = len_tv == glwe ? 0 : glwe;
+    return ordered_on(h->guard, s, [&]() -> int {
+        // chunk after chunk; every stage of a chunk is queued before the next chunk starts
+        for (u64 done = 0; done < batch; done += h->chunk) {
+            const u64 cur = std::min<u64>(h->chunk, batch - done);
+            PFHE_TRY(launch_modswitch<W>(lwe_in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, s));
+            PFHE_TRY(launch_acc_init<W>(tv + done * tv_stride, tv_stride, h->acc, h->neg_b, h->k + 1, f.log_n, cur, s));
+            PFHE_TRY(tfhe_blindrot_rotate_handle(h->rot, h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s));
+            W *lwe = h->with_keyswitch ? h->extracted : lwe_out + done * out_words;
+            PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, s));
+            if (h->with_keyswitch) PFHE_TRY(launch_keyswitch<W>(lwe, ksk, lwe_out + done * out_words, h->ks, cur, s));
+        }
+        return PFHE_OK;
+    });
+}
+
+// host form: staged through the pooled context
+template <class W, class H>
+int bootstrap_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
+                   const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out) {
+    if (!h || !h->rot) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
+    if (!h->with_keyswitch && (ksk || len_ksk)) {
+        set_last_error("TFHE bootstrap: a handle without a key switch takes no key-switch key");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    u64 batch = 0;
+    PFHE_TRY((bootstrap_check<W>(h, len_in, len_bsk, len_tv, len_ksk, len_out, batch)));
+    if (batch == 0) return PFHE_OK;
+    if (!lwe_in || !bsk || !tv || !lwe_out || (h->with_keyswitch && !ksk)) return PFHE_ERR_BAD_ARGUMENT;
+    DeviceGuard g(h->fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(h->fft->device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *a = nullptr, *b = nullptr, *t = nullptr, *k = nullptr, *o = nullptr;
+    PFHE_TRY(st.upload(lwe_in, len_in * sizeof(W), &a));
+    PFHE_TRY(st.upload(bsk, len_bsk * 2 * sizeof(double), &b));
+    PFHE_TRY(st.upload(tv, len_tv * sizeof(W), &t));
+    if (h->with_keyswitch) PFHE_TRY(st.upload(ksk, len_ksk * sizeof(W), &k));
+    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
+    PFHE_TRY(bootstrap_dev<W>(h, (const W *)a, len_in, (const double *)b, len_bsk, (const W *)t, len_tv, (const W *)k, len_ksk,
+                              (W *)o, len_out, st.stream()));
+    PFHE_TRY(st.download(lwe_out, o, len_out * sizeof(W)));
+    return st.finish();
+}
+
+template <class H>
+size_t bootstrap_scratch(const H *h) {
+    return h && h->rot && h->rot->plan ? h->rot->plan->scratch + h->rot->glue_bytes + h->bytes : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfhe_tfhe_modswitch_dev(int device, const uint64_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                            uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream) {
+    PFHE_GUARD_BEGIN
+    return modswitch_dev<u64>(device, (const u64 *)lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev,
+                              len_neg_b, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_modswitch_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                              uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream) {
+    PFHE_GUARD_BEGIN
+    return modswitch_dev<u32>(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev, len_neg_b,
+                              (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
+                                 size_t index, uint64_t *lwe_dev, size_t len_lwe, void *stream) {
+    PFHE_GUARD_BEGIN
+    return sample_extract_dev<u64>(fft, glwe_dimension, (const u64 *)glwe_dev, len_glwe, index, (u64 *)lwe_dev, len_lwe,
+                                   (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe, size_t index,
+                             uint64_t *lwe, size_t len_lwe) {
+    PFHE_GUARD_BEGIN
+    return sample_extract_host<u64>(fft, glwe_dimension, (const u64 *)glwe, len_glwe, index, (u64 *)lwe, len_lwe);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe_dev, size_t len_glwe,
+                                   size_t index, uint32_t *lwe_dev, size_t len_lwe, void *stream) {
+    PFHE_GUARD_BEGIN
+    return sample_extract_dev<u32>(fft, glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe, size_t index,
+                               uint32_t *lwe, size_t len_lwe) {
+    PFHE_GUARD_BEGIN
+    return sample_extract_host<u32>(fft, glwe_dimension, glwe, len_glwe, index, lwe, len_lwe);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe_keyswitch_dev(int device, const uint64_t *lwe_in_dev, size_t len_in, size_t in_dimension, const uint64_t *ksk_dev,
+                            size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length,
+                            uint64_t *lwe_out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return keyswitch_dev<u64>(device, (const u64 *)lwe_in_dev, len_in, in_dimension, (const u64 *)ksk_dev, len_ksk,
+                              out_dimension, log_basis, decompose_length, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_keyswitch(int device, const uint64_t *lwe_in, size_t len_in, size_t in_dimension, const uint64_t *ksk,
+                        size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *lwe_out,
+                        size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return keyswitch_host<u64>(device, (const u64 *)lwe_in, len_in, in_dimension, (const u64 *)ksk, len_ksk, out_dimension,
+                               log_basis, decompose_length, (u64 *)lwe_out, len_out);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_keyswitch_dev(int device, const uint32_t *lwe_in_dev, size_t len_in, size_t in_dimension,
+                              const uint32_t *ksk_dev, size_t len_ksk, size_t out_dimension, uint32_t log_basis,
+                              size_t decompose_length, uint32_t *lwe_out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return keyswitch_dev<u32>(device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension, log_basis,
+                              decompose_length, lwe_out_dev, len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_keyswitch(int device, const uint32_t *lwe_in, size_t len_in, size_t in_dimension, const uint32_t *ksk,
+                          size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *lwe_out,
+                          size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return keyswitch_host<u32>(device, lwe_in, len_in, in_dimension, ksk, len_ksk, out_dimension, log_basis, decompose_length,
+                               lwe_out, len_out);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                               size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
+                               size_t chunk, pfhe_tfhe_bootstrap_handle **out) {
+    PFHE_GUARD_BEGIN
+    return bootstrap_create<pfhe_tfhe_bootstrap_handle, u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                                      ks_log_basis, ks_decompose_length, with_keyswitch, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h) { delete h; }
+int pfhe_tfhe_bootstrap_in_use(const pfhe_tfhe_bootstrap_handle *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h) { return bootstrap_scratch(h); }
+int pfhe_tfhe_bootstrap_dev(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                            size_t len_bsk, const uint64_t *tv_dev, size_t len_tv, const uint64_t *ksk_dev, size_t len_ksk,
+                            uint64_t *lwe_out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return bootstrap_dev<u64>(h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)tv_dev, len_tv,
+                              (const u64 *)ksk_dev, len_ksk, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_bootstrap(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                        const uint64_t *tv, size_t len_tv, const uint64_t *ksk, size_t len_ksk, uint64_t *lwe_out,
+                        size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return bootstrap_host<u64>(h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)tv, len_tv, (const u64 *)ksk, len_ksk,
+                               (u64 *)lwe_out, len_out);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe32_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                 size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
+                                 size_t chunk, pfhe_tfhe32_bootstrap_handle **out) {
+    PFHE_GUARD_BEGIN
+    return bootstrap_create<pfhe_tfhe32_bootstrap_handle, u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                                        ks_log_basis, ks_decompose_length, with_keyswitch, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h) { delete h; }
+int pfhe_tfhe32_bootstrap_in_use(const pfhe_tfhe32_bootstrap_handle *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe32_bootstrap_scratch_bytes(const pfhe_tfhe32_bootstrap_handle *h) { return bootstrap_scratch(h); }
+int pfhe_tfhe32_bootstrap_dev(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                              size_t len_bsk, const uint32_t *tv_dev, size_t len_tv, const uint32_t *ksk_dev, size_t len_ksk,
+                              uint32_t *lwe_out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return bootstrap_dev<u32>(h, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev, len_ksk, lwe_out_dev, len_out,
+                              (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_bootstrap(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                          const uint32_t *tv, size_t len_tv, const uint32_t *ksk, size_t len_ksk, uint32_t *lwe_out,
+                          size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return bootstrap_host<u32>(h, lwe_in, len_in, bsk, len_bsk, tv, len_tv, ksk, len_ksk, lwe_out, len_out);
+    PFHE_GUARD_END
+}
+
+}  // extern "C"

@@ -35,69 +35,10 @@
 #include <type_traits>
 #include <vector>
 
-#include "pfhe_capi_internal.hpp"
 #include "pfhe_fft_device.hpp"
-#include "pfhe_plan_guard.hpp"
-#include "pfhe_staging.hpp"
+#include "pfhe_tfhe_handles.hpp"
 
 using namespace pfhe;
-
-struct pfhe_fft {
-    int device = 0;
-    u32 log_n = 0;
-    size_t n = 0;
-    double2 *tw = nullptr;  // device: cis(pi j / N), j < N
-    ~pfhe_fft() {
-        if (!tw) return;
-        DeviceGuard g(device);
-        (void)counted_free(tw);
-    }
-};
-
-// TfheFftContext<T> + ApproxSignedBasis<T> (power-of-two modulus): the shape of the product and its device scratch.
-template <class W>
-struct TfhePlanCore {
-    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the plan)
-    PlanGuard guard;                // one holder at a time (&mut TfheFftContext), successive calls ordered across streams
-    u32 k = 1, log_basis = 0, ell = 0, drop_bits = 0;
-    size_t chunk = 1;
-    bool fused = false;
-    // general form only: digit spectra (chunk x (k+1) x ell x N/2), accumulators (chunk x (k+1) x N/2) and the key's
-    // Hermitian part ((k+1) x ell x (k+1) x N/2), complex f64
-    double2 *spec = nullptr, *acc = nullptr, *keyh = nullptr;
-    size_t scratch = 0;
-    ~TfhePlanCore() {
-        if (!fft) return;
-        DeviceGuard g(fft->device);
-        for (double2 *b : {spec, acc, keyh})
-            if (b) (void)counted_free(b);
-    }
-};
-struct pfhe_tfhe_plan : TfhePlanCore<u64> {};
-struct pfhe_tfhe32_plan : TfhePlanCore<u32> {};
-
-// The blind rotation over the TFHE product: owns a product plan and, in the per-step form, three glue buffers of chunk
-// ciphertexts (D, E and the second accumulator of the ping-pong), all allocated at creation.
-template <class P, class W>
-struct TfheBlindRotCore {
-    P *plan = nullptr;  // owned
-    PlanGuard guard;    // one holder at a time and cross-stream ordering of successive calls, as the plan
-    bool whole_loop = false;
-    size_t chunk = 1;
-    W *d = nullptr, *e = nullptr, *ping = nullptr;  // per-step form only: chunk * (k+1) * N words each
-    size_t glwe = 0, key_len = 0, glue_bytes = 0;
-    ~TfheBlindRotCore() {
-        if (!plan) return;
-        {
-            DeviceGuard g(plan->fft->device);
-            for (W *b : {d, e, ping})
-                if (b) (void)counted_free(b);
-        }
-        delete plan;
-    }
-};
-struct pfhe_tfhe_blindrot : TfheBlindRotCore<pfhe_tfhe_plan, u64> {};
-struct pfhe_tfhe32_blindrot : TfheBlindRotCore<pfhe_tfhe32_plan, u32> {};
 
 namespace pfhe {
 namespace {
@@ -406,23 +347,6 @@ int host_form(const pfhe_fft *f, const In *in, size_t in_bytes, Out *out, size_t
 // ---------------- plans ----------------
 
 constexpr const char *kPlanBusy = "TFHE product plan in use by another thread (one plan per thread, like &mut TfheFftContext)";
-
-// ApproxSignedBasis::new (basis.rs:47-177) with modulus None: its assert!s become PFHE_ERR_BAD_ARGUMENT (log_basis = BITS
-// overflows the basis there too); decompose_length 0 = the full length BITS / log_basis
-int basis_shape(u32 bits, u32 log_basis, size_t length, u32 &ell, u32 &drop) {
-    if (log_basis == 0 || log_basis >= bits) {
-        set_last_error("log_basis must be in 1..BITS-1");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    const u32 full = bits / log_basis;
-    if (length > full) {
-        set_last_error("decompose_length exceeds BITS / log_basis");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    ell = length ? (u32)length : full;
-    drop = bits - ell * log_basis;
-    return PFHE_OK;
-}
 
 constexpr size_t kMaxGlweDimension = 64;
 constexpr size_t kDefaultScratchBytes = 256ull << 20;
@@ -755,6 +679,30 @@ size_t tfhe_blindrot_scratch(const H *h) {
 }
 
 }  // namespace
+
+namespace pfhe {
+
+// what pfhe_tfhe{,32}_blindrot_create / _rotate_dev run, for the bootstrap handle (pfhe_bootstrap.hip)
+int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t chunk, pfhe_tfhe_blindrot **out) {
+    return ::tfhe_blindrot_create<pfhe_tfhe_blindrot, pfhe_tfhe_plan>(fft, glwe_dimension, log_basis, decompose_length, chunk,
+                                                                      out);
+}
+int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t chunk, pfhe_tfhe32_blindrot **out) {
+    return ::tfhe_blindrot_create<pfhe_tfhe32_blindrot, pfhe_tfhe32_plan>(fft, glwe_dimension, log_basis, decompose_length,
+                                                                          chunk, out);
+}
+int tfhe_blindrot_rotate_handle(pfhe_tfhe_blindrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                                const uint32_t *exps, size_t len_exps, hipStream_t s) {
+    return ::tfhe_blindrot_dev<u64>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+}
+int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                                const uint32_t *exps, size_t len_exps, hipStream_t s) {
+    return ::tfhe_blindrot_dev<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+}
+
+}  // namespace pfhe
 
 extern "C" {
 

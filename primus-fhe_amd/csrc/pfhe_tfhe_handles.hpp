@@ -1,0 +1,96 @@
+// pfhe_tfhe_handles.hpp — what the torus-side handles own (pfhe_fft, the TFHE product plan, the blind-rotation handle) and
+// the basis check they share.  Seen by pfhe_fft.hip, which implements them, and by pfhe_bootstrap.hip, whose bootstrap
+// handle is built around a blind-rotation handle.  Host only.
+#pragma once
+
+#include "pfhe_capi_internal.hpp"
+#include "pfhe_plan_guard.hpp"
+#include "pfhe_staging.hpp"
+
+struct pfhe_fft {
+    int device = 0;
+    pfhe::u32 log_n = 0;
+    size_t n = 0;
+    double2 *tw = nullptr;  // device: cis(pi j / N), j < N
+    ~pfhe_fft() {
+        if (!tw) return;
+        pfhe::DeviceGuard g(device);
+        (void)pfhe::counted_free(tw);
+    }
+};
+
+// TfheFftContext<T> + ApproxSignedBasis<T> (power-of-two modulus): the shape of the product and its device scratch.
+template <class W>
+struct TfhePlanCore {
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the plan)
+    pfhe::PlanGuard guard;          // one holder at a time (&mut TfheFftContext), successive calls ordered across streams
+    pfhe::u32 k = 1, log_basis = 0, ell = 0, drop_bits = 0;
+    size_t chunk = 1;
+    bool fused = false;
+    // general form only: digit spectra (chunk x (k+1) x ell x N/2), accumulators (chunk x (k+1) x N/2) and the key's
+    // Hermitian part ((k+1) x ell x (k+1) x N/2), complex f64
+    double2 *spec = nullptr, *acc = nullptr, *keyh = nullptr;
+    size_t scratch = 0;
+    ~TfhePlanCore() {
+        if (!fft) return;
+        pfhe::DeviceGuard g(fft->device);
+        for (double2 *b : {spec, acc, keyh})
+            if (b) (void)pfhe::counted_free(b);
+    }
+};
+struct pfhe_tfhe_plan : TfhePlanCore<pfhe::u64> {};
+struct pfhe_tfhe32_plan : TfhePlanCore<pfhe::u32> {};
+
+// The blind rotation over the TFHE product: owns a product plan and, in the per-step form, three glue buffers of chunk
+// ciphertexts (D, E and the second accumulator of the ping-pong), all allocated at creation.
+template <class P, class W>
+struct TfheBlindRotCore {
+    P *plan = nullptr;     // owned
+    pfhe::PlanGuard guard; // one holder at a time and cross-stream ordering of successive calls, as the plan
+    bool whole_loop = false;
+    size_t chunk = 1;
+    W *d = nullptr, *e = nullptr, *ping = nullptr;  // per-step form only: chunk * (k+1) * N words each
+    size_t glwe = 0, key_len = 0, glue_bytes = 0;
+    ~TfheBlindRotCore() {
+        if (!plan) return;
+        {
+            pfhe::DeviceGuard g(plan->fft->device);
+            for (W *b : {d, e, ping})
+                if (b) (void)pfhe::counted_free(b);
+        }
+        delete plan;
+    }
+};
+struct pfhe_tfhe_blindrot : TfheBlindRotCore<pfhe_tfhe_plan, pfhe::u64> {};
+struct pfhe_tfhe32_blindrot : TfheBlindRotCore<pfhe_tfhe32_plan, pfhe::u32> {};
+
+namespace pfhe {
+
+// ApproxSignedBasis::new (basis.rs:47-177) with modulus None: its assert!s become PFHE_ERR_BAD_ARGUMENT (log_basis = BITS
+// overflows the basis there too); decompose_length 0 = the full length BITS / log_basis
+inline int basis_shape(u32 bits, u32 log_basis, size_t length, u32 &ell, u32 &drop) {
+    if (log_basis == 0 || log_basis >= bits) {
+        set_last_error("log_basis must be in 1..BITS-1");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    const u32 full = bits / log_basis;
+    if (length > full) {
+        set_last_error("decompose_length exceeds BITS / log_basis");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    ell = length ? (u32)length : full;
+    drop = bits - ell * log_basis;
+    return PFHE_OK;
+}
+
+// The blind rotation's own create and device call (pfhe_fft.hip), as pfhe_tfhe{,32}_blindrot_create / _rotate_dev run them.
+int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t chunk, pfhe_tfhe_blindrot **out);
+int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t chunk, pfhe_tfhe32_blindrot **out);
+int tfhe_blindrot_rotate_handle(pfhe_tfhe_blindrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                                const uint32_t *exps, size_t len_exps, hipStream_t s);
+int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                                const uint32_t *exps, size_t len_exps, hipStream_t s);
+
+}  // namespace pfhe

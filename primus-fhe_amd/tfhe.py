@@ -268,6 +268,166 @@ def tfhe_blind_rotate_dev(acc, bsk, exps, ctx: TfheBlindRotateContext, stream=No
     check(getattr(lib(), ctx._pre + "rotate_dev")(ctx._h, pa, na, pk, nk, pe, ne, _stream(stream)))
 
 
+# ---- the programmable bootstrap around the rotation (include/pfhe.h: modswitch, sample_extract, keyswitch, bootstrap) ----
+
+def _dev_index(t, device) -> int:
+    if device is not None:
+        return int(device)
+    return int(t.device.index or 0) if hasattr(t, "device") else 0
+
+
+def lwe_modulus_switch_dev(lwe, lwe_dimension: int, log_n: int, exps, neg_b, device=None, stream=None) -> None:
+    """The project's own modulus switch (the reference has none): for a batch of LWE ciphertexts (a[0..n), b) of 32- or
+    64-bit torus words, exps[e*n + i] = sw(a_{e,i}) and neg_b[e] = (2N - sw(b_e)) mod 2N, with
+    sw(w) = (((w >> (shift-1)) + 1) >> 1) & (2N-1), shift = BITS - log_n - 1 (round to nearest, ties up).  exps is what
+    tfhe_blind_rotate_dev takes; neg_b the exponents of the accumulator's X^{-b} * TV."""
+    pl, nl, w = _dev_words(lwe)
+    pe, ne = _dev_exps(exps)
+    pb, nb = _dev_exps(neg_b)
+    check(getattr(lib(), "pfhe_tfhe" + w + "_modswitch_dev")(_dev_index(lwe, device), pl, nl, lwe_dimension, log_n, pe, ne,
+                                                            pb, nb, _stream(stream)))
+
+
+def glwe_sample_extract(glwe: np.ndarray, lwe: np.ndarray, fft: FullComplex64FftTable, glwe_dimension: int = 1,
+                        index: int = 0) -> None:
+    """Rlwe::extract_lwe_with_index (rlwe/coeff.rs:194-227) per mask polynomial, on host arrays: batch GLWE ciphertexts of
+    (k+1)*N words -> batch LWE ciphertexts of k*N + 1 words under the GLWE key polynomials end to end."""
+    pg, ng, wg = _host_words(glwe)
+    po, no, wo = _host_words(lwe)
+    if wg != wo:
+        raise TypeError("glwe and lwe must have the same word width")
+    check(getattr(lib(), "pfhe_tfhe" + wg + "_sample_extract")(fft._h, glwe_dimension, pg, ng, index, po, no))
+
+
+def glwe_sample_extract_dev(glwe, lwe, fft: FullComplex64FftTable, glwe_dimension: int = 1, index: int = 0,
+                            stream=None) -> None:
+    """the device form; lwe must not overlap glwe"""
+    pg, ng, wg = _dev_words(glwe)
+    po, no, wo = _dev_words(lwe)
+    if wg != wo:
+        raise TypeError("glwe and lwe must have the same word width")
+    check(getattr(lib(), "pfhe_tfhe" + wg + "_sample_extract_dev")(fft._h, glwe_dimension, pg, ng, index, po, no,
+                                                                  _stream(stream)))
+
+
+def _basis_args(basis, width: str):
+    if (basis.bits == 64) != (width == ""):
+        raise TypeError("the basis width must match the torus words")
+    return basis.log_basis(), basis.decompose_length()
+
+
+def lwe_keyswitch(lwe_in: np.ndarray, ksk: np.ndarray, lwe_out: np.ndarray, in_dimension: int, out_dimension: int,
+                  basis: ApproxSignedBasis, device: int = 0) -> None:
+    """LWE key switch on host arrays: out = (0, b) - sum_i sum_j d_{i,j} * KSK[i][j] modulo 2^BITS, d the signed digits of
+    a_i under `basis`; ksk is in_dimension x ell x (out_dimension+1) words, row (i, j) an LWE ciphertext of
+    s_i * 2^(drop_bits + j*log_basis) under the output key, levels least significant first."""
+    pi, ni, wi = _host_words(lwe_in)
+    pk, nk, wk = _host_words(ksk)
+    po, no, wo = _host_words(lwe_out)
+    if not wi == wk == wo:
+        raise TypeError("lwe_in, ksk and lwe_out must have the same word width")
+    lb, ell = _basis_args(basis, wi)
+    check(getattr(lib(), "pfhe_tfhe" + wi + "_keyswitch")(device, pi, ni, in_dimension, pk, nk, out_dimension, lb, ell, po, no))
+
+
+def lwe_keyswitch_dev(lwe_in, ksk, lwe_out, in_dimension: int, out_dimension: int, basis: ApproxSignedBasis, device=None,
+                      stream=None) -> None:
+    """the device form, asynchronous; lwe_out must not overlap an input and may be uninitialised"""
+    pi, ni, wi = _dev_words(lwe_in)
+    pk, nk, wk = _dev_words(ksk)
+    po, no, wo = _dev_words(lwe_out)
+    if not wi == wk == wo:
+        raise TypeError("lwe_in, ksk and lwe_out must have the same word width")
+    lb, ell = _basis_args(basis, wi)
+    check(getattr(lib(), "pfhe_tfhe" + wi + "_keyswitch_dev")(_dev_index(lwe_in, device), pi, ni, in_dimension, pk, nk,
+                                                             out_dimension, lb, ell, po, no, _stream(stream)))
+
+
+class TfheBootstrapContext:
+    """Handle of the batched programmable bootstrap (include/pfhe.h, pfhe_tfhe{,32}_bootstrap_*): modulus switch,
+    ACC = X^{-b~} * TV, the blind rotation over lwe_dimension steps, sample extraction at index 0 and, when ks_basis is
+    given, the key switch back to lwe_dimension.  Owns a blind-rotation handle and every buffer between the stages for
+    `chunk` ciphertexts (0 = the default); one holder at a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int = 1,
+                 ks_basis: ApproxSignedBasis | None = None, chunk: int = 0):
+        self._w = "" if basis.bits == 64 else "32"
+        self._pre = "pfhe_tfhe" + self._w + "_bootstrap"
+        if ks_basis is not None and ks_basis.bits != basis.bits:
+            raise TypeError("both bases must have the width of the torus words")
+        h = C.c_void_p()
+        check(getattr(lib(), self._pre + "_create")(
+            fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(), lwe_dimension,
+            ks_basis.log_basis() if ks_basis else 0, ks_basis.decompose_length() if ks_basis else 0,
+            1 if ks_basis else 0, chunk, C.byref(h)))
+        self._h = h
+        self.fft, self.basis, self.ks_basis = fft, basis, ks_basis
+        self.glwe_dimension, self.lwe_dimension = glwe_dimension, lwe_dimension
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            getattr(lib(), self._pre + "_destroy")(h)
+            self._h = None
+
+    def dtype(self):
+        return np.uint64 if self.basis.bits == 64 else np.uint32
+
+    def scratch_bytes(self) -> int:
+        return int(getattr(lib(), self._pre + "_scratch_bytes")(self._h))
+
+    def in_use(self) -> bool:
+        return bool(getattr(lib(), self._pre + "_in_use")(self._h))
+
+    def glwe_len(self) -> int:
+        return (self.glwe_dimension + 1) * self.fft.poly_length()
+
+    def key_len(self) -> int:
+        """complex values of one Fourier GGSW key (one step of the rotation)"""
+        return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
+
+    def extracted_dimension(self) -> int:
+        return self.glwe_dimension * self.fft.poly_length()
+
+    def ksk_len(self) -> int:
+        """words of the key-switch key (0 without a key switch)"""
+        if self.ks_basis is None:
+            return 0
+        return self.extracted_dimension() * self.ks_basis.decompose_length() * (self.lwe_dimension + 1)
+
+    def out_len(self) -> int:
+        """words of one output ciphertext"""
+        return (self.lwe_dimension if self.ks_basis is not None else self.extracted_dimension()) + 1
+
+
+def tfhe_bootstrap(lwe_in: np.ndarray, bsk: np.ndarray, tv: np.ndarray, ksk, lwe_out: np.ndarray,
+                   ctx: TfheBootstrapContext) -> None:
+    """Batched programmable bootstrap on host arrays.  lwe_in: batch x (n+1) words; bsk: n Fourier GGSW keys end to end;
+    tv: one GLWE test vector ((k+1)*N words) or one per ciphertext; ksk: the key-switch key, None without a key switch;
+    lwe_out: batch x ctx.out_len() words."""
+    pi, ni, wi = _host_words(lwe_in)
+    pk, nk = _host_fourier(bsk)
+    pt, nt, wt = _host_words(tv)
+    po, no, wo = _host_words(lwe_out)
+    ps, ns, ws = _host_words(ksk) if ksk is not None else (None, 0, ctx._w)
+    if not wi == wt == wo == ws == ctx._w:
+        raise TypeError("every word array must have the width of the context's basis")
+    check(getattr(lib(), ctx._pre)(ctx._h, pi, ni, pk, nk, pt, nt, ps, ns, po, no))
+
+
+def tfhe_bootstrap_dev(lwe_in, bsk, tv, ksk, lwe_out, ctx: TfheBootstrapContext, stream=None) -> None:
+    """the device form (32- or 64-bit integer CUDA tensors of the context's width, bsk complex128 or float64),
+    asynchronous; lwe_out must not overlap an input"""
+    pi, ni, wi = _dev_words(lwe_in)
+    pk, nk = _dev_fourier(bsk)
+    pt, nt, wt = _dev_words(tv)
+    po, no, wo = _dev_words(lwe_out)
+    ps, ns, ws = _dev_words(ksk) if ksk is not None else (None, 0, ctx._w)
+    if not wi == wt == wo == ws == ctx._w:
+        raise TypeError("every word tensor must have the width of the context's basis")
+    check(getattr(lib(), ctx._pre + "_dev")(ctx._h, pi, ni, pk, nk, pt, nt, ps, ns, po, no, _stream(stream)))
+
+
 def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) -> None:
     """Glwe / Glev / Ggsw::write_fourier_form (tfhe/convert.rs): the Fourier containers are polynomial after polynomial,
     so each is one batched forward transform.  numpy arrays take the host form, CUDA tensors the device form."""
