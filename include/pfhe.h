@@ -953,6 +953,68 @@ int pfhe_tfhe_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint64_t *a_de
 int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_dev, size_t len, const uint32_t *exps_dev,
                                          size_t polys_per_exp, uint32_t *out_dev, void *stream);
 
+/* Multi-bit blind rotation over the TFHE product — no reference counterpart (the reference has no bootstrap); the LWE mask is
+ * consumed g = grouping_factor elements at a time (1 <= g <= 4), so the serial depth and the transform count of a rotation
+ * fall by g.  ASSUMES BINARY LWE KEYS.  The key `bsk` is groups x 2^g Fourier GGSW keys end to end, each in the layout
+ * pfhe_tfhe*_blindrot_rotate_dev takes; key [t][j] encrypts prod_b (bit b of j ? s_{t*g+b} : 1 - s_{t*g+b}), the indicator
+ * that the key bits of group t equal pattern j.  With n_mask = groups*g, for every ciphertext e and every group t in order:
+ *   r_j   = (sum over the set bits b of j of (exps[e*n_mask + t*g + b] mod 2N)) mod 2N,   j = 0 .. 2^g-1,  r_0 = 0
+ *   K_e,t = sum_j M(r_j) (.) BSK[t][j]      M(r)[k'] = root[(r*(1-2k')) mod 2N], the spectrum of X^r in the table's full
+ *                                           layout; root[i] = tw[i] for i < N, -tw[i-N] otherwise (the table's cis(pi i/N))
+ *   ACC_e = external_product_to(ACC_e, K_e,t)     the product itself (no "+ ACC"), wrapping modulo 2^BITS
+ * The product only sees a key's Hermitian part and M(r) is Hermitian-symmetric, so the arithmetic is DEFINED on
+ * half-spectrum slots: Kh[m] = sum_j M(r_j)[2m] * Herm(BSK[t][j])[2m] with Herm as the product forms it, j ascending, the
+ * j = 0 term added without a multiplication and every complex multiply-add a fixed sequence of fused multiply-adds; the
+ * product's multiply-accumulate, inverse and torus wrap follow as in pfhe_tfhe*_external_product_to_dev.  Every form below
+ * gives the same words, and results do not depend on the batch size or the chunk.
+ * acc: batch GLWE ciphertexts, read and written in place; exps: batch x n_mask uint32, ciphertext-major.
+ * PFHE_ERR_BAD_LENGTH unless len_acc = batch*(k+1)*N, len_bsk = groups*2^g*key_len and len_exps = batch*groups*g;
+ * groups == 0 is a no-op.
+ * create runs pfhe_tfhe_plan_create's checks first, in its order (the basis's assert!s, PFHE_ERR_UNSUPPORTED for k > 64, the
+ * table), then PFHE_ERR_BAD_ARGUMENT for grouping_factor outside 1..4 — all before the device is touched.  The handle
+ * borrows `fft`; everything is allocated here, a call only queues work on `stream` (no allocation, no host
+ * synchronisation), so one whole rotation can be captured into a HIP graph; a batch larger than the chunk runs chunk by
+ * chunk.  One holder at a time (PFHE_ERR_BUSY), successive calls on different streams ordered.
+ * k = 1 with N <= 2^11 runs ONE launch per chunk: a workgroup per ciphertext keeps ACC in LDS across all groups and forms
+ * K_e,t slot by slot inside the fused product's accumulate code (PFHE_DISABLE_FUSED_TFHE_BLINDROT, read here, selects the
+ * other form).  Every other shape runs four launches per group (the Hermitian parts of the group's 2^g keys, the digit
+ * transforms of ACC, the multiply-accumulate with K_e,t formed per ciphertext, the inverses back into ACC) over scratch of
+ * `chunk` ciphertexts (chunk 0: about 256 MiB) plus the Hermitian parts of 2^g keys. */
+typedef struct pfhe_tfhe_mbrot pfhe_tfhe_mbrot;
+typedef struct pfhe_tfhe32_mbrot pfhe_tfhe32_mbrot;
+int pfhe_tfhe_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                           size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out);
+void pfhe_tfhe_mbrot_destroy(pfhe_tfhe_mbrot *h);
+int pfhe_tfhe_mbrot_in_use(const pfhe_tfhe_mbrot *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_mbrot_scratch_bytes(const pfhe_tfhe_mbrot *h);
+/* Device form: every exponent is taken modulo 2N on the device. */
+int pfhe_tfhe_mbrot_rotate_dev(pfhe_tfhe_mbrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
+                               const uint32_t *exps_dev, size_t len_exps, void *stream);
+/* Host form: PFHE_ERR_BAD_ARGUMENT for any exponent of 2N or more, as pfhe_tfhe_blindrot_rotate. */
+int pfhe_tfhe_mbrot_rotate(pfhe_tfhe_mbrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                           const uint32_t *exps, size_t len_exps);
+int pfhe_tfhe32_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                             size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out);
+void pfhe_tfhe32_mbrot_destroy(pfhe_tfhe32_mbrot *h);
+int pfhe_tfhe32_mbrot_in_use(const pfhe_tfhe32_mbrot *h);
+size_t pfhe_tfhe32_mbrot_scratch_bytes(const pfhe_tfhe32_mbrot *h);
+int pfhe_tfhe32_mbrot_rotate_dev(pfhe_tfhe32_mbrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
+                                 const uint32_t *exps_dev, size_t len_exps, void *stream);
+int pfhe_tfhe32_mbrot_rotate(pfhe_tfhe32_mbrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                             const uint32_t *exps, size_t len_exps);
+/* The combined key of ONE ciphertext and ONE group as a key of its own (keys are f64 for both widths): keys_dev holds the
+ * group's 2^g keys (len_keys = 2^g*key_len complex values, key_len = (k+1)*ell*(k+1)*N with ell = decompose_length >= 1),
+ * exps_dev its g exponents (taken modulo 2N), out_dev one key in the reference's full layout: out[2m] = Kh[m],
+ * out[(1-2m) mod N] = conj(Kh[m]).  The product's Hermitian step returns Kh[m] from that bit for bit, so the rotation above
+ * equals, word for word, this call followed by pfhe_tfhe*_external_product_to_dev per ciphertext and group.
+ * In this order: PFHE_ERR_BAD_ARGUMENT for a null table, PFHE_ERR_UNSUPPORTED for glwe_dimension > 64,
+ * PFHE_ERR_BAD_ARGUMENT for decompose_length outside 1..64 or g outside 1..4, PFHE_ERR_BAD_LENGTH for lengths that do not
+ * fit, PFHE_ERR_BAD_ARGUMENT for a null buffer, for keys_dev or out_dev not aligned to 16 bytes (the kernel loads and
+ * stores whole complex values) and for an out_dev that overlaps keys_dev. */
+int pfhe_tfhe_mb_combine_key_dev(const pfhe_fft *fft, size_t glwe_dimension, size_t decompose_length, size_t grouping_factor,
+                                 const double *keys_dev, size_t len_keys, const uint32_t *exps_dev, size_t len_exps,
+                                 double *out_dev, size_t len_out, void *stream);
+
 /* ---- the programmable bootstrap around the blind rotation (u64: no suffix, u32: 32) ----
  * An LWE ciphertext is laid out as the reference's Lwe (primus_lattice/src/lwe/single_message.rs:94-125): a[0..dim) then b,
  * dim + 1 torus words, b = <a,s> + e + m; a batch is ciphertext after ciphertext.  The three stateless steps below are exact
@@ -1027,6 +1089,14 @@ typedef struct pfhe_tfhe32_bootstrap_handle pfhe_tfhe32_bootstrap_handle;
 int pfhe_tfhe_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                                size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
                                size_t chunk, pfhe_tfhe_bootstrap_handle **out);
+/* The same handle over the multi-bit rotation (pfhe_tfhe_mbrot_*): bsk is then the multi-bit key of
+ * (lwe_dimension / grouping_factor) * 2^grouping_factor keys, and every call below works on the handle as before.  The
+ * multi-bit rotation's create runs first (its statuses, in its order); PFHE_ERR_BAD_ARGUMENT in addition when lwe_dimension
+ * is no multiple of grouping_factor.  Handles made by pfhe_tfhe*_bootstrap_create are not affected. */
+int pfhe_tfhe_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                        size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length,
+                                        int with_keyswitch, size_t grouping_factor, size_t chunk,
+                                        pfhe_tfhe_bootstrap_handle **out);
 void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h);
 int pfhe_tfhe_bootstrap_in_use(const pfhe_tfhe_bootstrap_handle *h);  /* 1 while some thread is inside a call on it */
 size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h);  /* the rotation handle's scratch included */
@@ -1039,6 +1109,10 @@ int pfhe_tfhe_bootstrap(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in, s
 int pfhe_tfhe32_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                                  size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
                                  size_t chunk, pfhe_tfhe32_bootstrap_handle **out);
+int pfhe_tfhe32_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
+                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
+                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor, size_t chunk,
+                                          pfhe_tfhe32_bootstrap_handle **out);
 void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h);
 int pfhe_tfhe32_bootstrap_in_use(const pfhe_tfhe32_bootstrap_handle *h);
 size_t pfhe_tfhe32_bootstrap_scratch_bytes(const pfhe_tfhe32_bootstrap_handle *h);

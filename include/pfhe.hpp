@@ -722,6 +722,71 @@ class TfheBlindRotate32 {
     pfhe_tfhe32_blindrot *h_ = nullptr;
 };
 
+// The multi-bit blind rotation (pfhe_tfhe_mbrot_*): the mask is consumed grouping_factor (1..4) elements at a time; for every
+// group t and ciphertext e, ACC_e = external_product_to(ACC_e, sum_j X^{r_j} * BSK[t][j]) with r_j the subset sum of the
+// group's exponents at the set bits of j.  Binary LWE keys; bsk is groups x 2^g Fourier GGSW keys.  Owns the scratch of its
+// form; one holder at a time.  TfheMultiBitBlindRotate32: the u32 torus.
+class TfheMultiBitBlindRotate {
+  public:
+    TfheMultiBitBlindRotate(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                            size_t grouping_factor, size_t chunk = 0) {
+        check(pfhe_tfhe_mbrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &h_));
+    }
+    ~TfheMultiBitBlindRotate() { pfhe_tfhe_mbrot_destroy(h_); }
+    TfheMultiBitBlindRotate(const TfheMultiBitBlindRotate &) = delete;
+    TfheMultiBitBlindRotate &operator=(const TfheMultiBitBlindRotate &) = delete;
+    pfhe_tfhe_mbrot *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_mbrot_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_mbrot_scratch_bytes(h_); }
+    // host slices; every exponent below 2N
+    void rotate(uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps) {
+        check(pfhe_tfhe_mbrot_rotate(h_, acc, len_acc, bsk, len_bsk, exps, len_exps));
+    }
+    // device buffers, queued on `stream` (exponents taken modulo 2N)
+    void rotate_dev(uint64_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk, const uint32_t *exps_dev,
+                    size_t len_exps, void *stream = nullptr) {
+        check(pfhe_tfhe_mbrot_rotate_dev(h_, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream));
+    }
+
+  private:
+    pfhe_tfhe_mbrot *h_ = nullptr;
+};
+
+class TfheMultiBitBlindRotate32 {
+  public:
+    TfheMultiBitBlindRotate32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                              size_t grouping_factor, size_t chunk = 0) {
+        check(pfhe_tfhe32_mbrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &h_));
+    }
+    ~TfheMultiBitBlindRotate32() { pfhe_tfhe32_mbrot_destroy(h_); }
+    TfheMultiBitBlindRotate32(const TfheMultiBitBlindRotate32 &) = delete;
+    TfheMultiBitBlindRotate32 &operator=(const TfheMultiBitBlindRotate32 &) = delete;
+    pfhe_tfhe32_mbrot *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_mbrot_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_mbrot_scratch_bytes(h_); }
+    // host slices; every exponent below 2N
+    void rotate(uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps) {
+        check(pfhe_tfhe32_mbrot_rotate(h_, acc, len_acc, bsk, len_bsk, exps, len_exps));
+    }
+    // device buffers, queued on `stream` (exponents taken modulo 2N)
+    void rotate_dev(uint32_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk, const uint32_t *exps_dev,
+                    size_t len_exps, void *stream = nullptr) {
+        check(pfhe_tfhe32_mbrot_rotate_dev(h_, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream));
+    }
+
+  private:
+    pfhe_tfhe32_mbrot *h_ = nullptr;
+};
+
+// the combined key of one ciphertext and one group as a key in the reference's layout (pfhe_tfhe_mb_combine_key_dev)
+inline void tfhe_multibit_combine_key_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, size_t decompose_length,
+                                          size_t grouping_factor, const double *keys_dev, size_t len_keys,
+                                          const uint32_t *exps_dev, size_t len_exps, double *out_dev, size_t len_out,
+                                          void *stream = nullptr) {
+    check(pfhe_tfhe_mb_combine_key_dev(fft.handle(), glwe_dimension, decompose_length, grouping_factor, keys_dev, len_keys,
+                                       exps_dev, len_exps, out_dev, len_out, stream));
+}
+
 // X^{exps[e]} * element e for elements of polys_per_exp torus polynomials (the X^{-b_e} * TV that starts a bootstrap)
 inline void mul_monomial_each_to_dev(const FullComplex64FftTable &fft, const uint64_t *a_dev, size_t len,
                                      const uint32_t *exps_dev, size_t polys_per_exp, uint64_t *out_dev,
@@ -797,9 +862,14 @@ class TfheBootstrap {
   public:
     TfheBootstrap(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                     size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, bool with_keyswitch = true,
-                    size_t chunk = 0) {
-        check(pfhe_tfhe_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                         ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_));
+                    size_t chunk = 0, size_t grouping_factor = 1) {
+        // grouping_factor 1: the classic rotation; above 1 the multi-bit one, on (lwe_dimension / g) * 2^g keys
+        check(grouping_factor == 1
+                  ? pfhe_tfhe_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                               ks_log_basis, ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_)
+                  : pfhe_tfhe_bootstrap_create_multibit(fft.handle(), glwe_dimension, log_basis, decompose_length,
+                                                        lwe_dimension, ks_log_basis, ks_decompose_length,
+                                                        with_keyswitch ? 1 : 0, grouping_factor, chunk, &h_));
     }
     ~TfheBootstrap() { pfhe_tfhe_bootstrap_destroy(h_); }
     TfheBootstrap(const TfheBootstrap &) = delete;
@@ -826,9 +896,14 @@ class TfheBootstrap32 {
   public:
     TfheBootstrap32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                     size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, bool with_keyswitch = true,
-                    size_t chunk = 0) {
-        check(pfhe_tfhe32_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                         ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_));
+                    size_t chunk = 0, size_t grouping_factor = 1) {
+        // grouping_factor 1: the classic rotation; above 1 the multi-bit one, on (lwe_dimension / g) * 2^g keys
+        check(grouping_factor == 1
+                  ? pfhe_tfhe32_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                               ks_log_basis, ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_)
+                  : pfhe_tfhe32_bootstrap_create_multibit(fft.handle(), glwe_dimension, log_basis, decompose_length,
+                                                        lwe_dimension, ks_log_basis, ks_decompose_length,
+                                                        with_keyswitch ? 1 : 0, grouping_factor, chunk, &h_));
     }
     ~TfheBootstrap32() { pfhe_tfhe32_bootstrap_destroy(h_); }
     TfheBootstrap32(const TfheBootstrap32 &) = delete;

@@ -10,7 +10,8 @@
 //! batched, device-resident external product as [`HipExternalProduct`].  `FullComplex64FftTable`
 //! (crates/primus_fft/src/complex64/table.rs:47) -> [`HipFftTable`] behind `FftTable`, and the TFHE product in the
 //! Fourier domain as [`HipTfheExternalProduct`] / [`HipTfheExternalProduct32`], with the blind rotation over it as
-//! [`HipTfheBlindRotate`] / [`HipTfheBlindRotate32`] and the programmable bootstrap around that as
+//! [`HipTfheBlindRotate`] / [`HipTfheBlindRotate32`], its multi-bit form as [`HipTfheMultiBitBlindRotate`] /
+//! [`HipTfheMultiBitBlindRotate32`], and the programmable bootstrap around that as
 //! [`HipTfheBootstrap`] / [`HipTfheBootstrap32`].
 mod ffi;
 
@@ -715,6 +716,66 @@ impl HipTfheBlindRotate32 {
 impl Drop for HipTfheBlindRotate32 {
     fn drop(&mut self) {
         unsafe { ffi::pfhe_tfhe32_blindrot_destroy(self.h) }
+    }
+}
+
+/// The multi-bit blind rotation over the TFHE product: the mask is consumed `grouping_factor` (1..4) elements at a time, and
+/// for every group t and ciphertext e `ACC_e = external_product_to(ACC_e, sum_j X^{r_j} * BSK[t][j])`, r_j the subset sum of
+/// the group's exponents at the set bits of j.  Binary LWE keys; the key holds groups x 2^g Fourier GGSW keys.
+/// [`HipTfheMultiBitBlindRotate32`]: the u32 torus.
+pub struct HipTfheMultiBitBlindRotate {
+    h: *mut ffi::pfhe_tfhe_mbrot,
+}
+impl HipTfheMultiBitBlindRotate {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize,
+               grouping_factor: usize) -> Result<Self, c_int> {
+        let mut h = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe_mbrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor, 0, &mut h) } {
+            ffi::PFHE_OK => Ok(Self { h }),
+            e => Err(e),
+        }
+    }
+    /// `acc_dev`: batch x (k+1) x N words, updated in place; `bsk_dev`: groups x 2^g keys of (k+1) x ell x (k+1) x N complex
+    /// values (`len_bsk` counts them); `exps_dev`: batch x groups*g exponents, taken modulo 2N
+    pub unsafe fn rotate_dev(&mut self, acc_dev: *mut u64, len_acc: usize, bsk_dev: *const f64, len_bsk: usize,
+                             exps_dev: *const u32, len_exps: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe_mbrot_rotate_dev(self.h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheMultiBitBlindRotate {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe_mbrot_destroy(self.h) }
+    }
+}
+
+pub struct HipTfheMultiBitBlindRotate32 {
+    h: *mut ffi::pfhe_tfhe32_mbrot,
+}
+impl HipTfheMultiBitBlindRotate32 {
+    pub fn new(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize,
+               grouping_factor: usize) -> Result<Self, c_int> {
+        let mut h = core::ptr::null_mut();
+        match unsafe { ffi::pfhe_tfhe32_mbrot_create(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor, 0, &mut h) } {
+            ffi::PFHE_OK => Ok(Self { h }),
+            e => Err(e),
+        }
+    }
+    /// `acc_dev`: batch x (k+1) x N words, updated in place; `bsk_dev`: groups x 2^g keys of (k+1) x ell x (k+1) x N complex
+    /// values (`len_bsk` counts them); `exps_dev`: batch x groups*g exponents, taken modulo 2N
+    pub unsafe fn rotate_dev(&mut self, acc_dev: *mut u32, len_acc: usize, bsk_dev: *const f64, len_bsk: usize,
+                             exps_dev: *const u32, len_exps: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+        match unsafe { ffi::pfhe_tfhe32_mbrot_rotate_dev(self.h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, stream) } {
+            ffi::PFHE_OK => Ok(()),
+            e => Err(e),
+        }
+    }
+}
+impl Drop for HipTfheMultiBitBlindRotate32 {
+    fn drop(&mut self) {
+        unsafe { ffi::pfhe_tfhe32_mbrot_destroy(self.h) }
     }
 }
 

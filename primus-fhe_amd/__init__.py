@@ -13,9 +13,11 @@ from .lattice import (BlindRotateContext, BlindRotateContext32, blind_rotate, bl
                       mul_dcrt_ggsw_to, mul_dcrt_ggsw_to_dev, profile_mul_dcrt_ggsw_to_dev)
 from .ntt import NttError, U32DcrtTable, U32NttTable, U64DcrtTable, U64NttTable  # noqa: F401
 from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateContext, TfheBootstrapContext,  # noqa: F401
-                   TfheFftContext, glwe_sample_extract, glwe_sample_extract_dev, lwe_keyswitch, lwe_keyswitch_dev,
-                   lwe_modulus_switch_dev, tfhe_blind_rotate, tfhe_blind_rotate_dev, tfhe_bootstrap, tfhe_bootstrap_dev,
-                   tfhe_external_product_to, tfhe_external_product_to_dev, write_fourier_form)
+                   TfheFftContext, TfheMultiBitBlindRotateContext, glwe_sample_extract, glwe_sample_extract_dev,
+                   lwe_keyswitch, lwe_keyswitch_dev, lwe_modulus_switch_dev, tfhe_blind_rotate, tfhe_blind_rotate_dev,
+                   tfhe_bootstrap, tfhe_bootstrap_dev, tfhe_external_product_to, tfhe_external_product_to_dev,
+                   tfhe_multibit_blind_rotate, tfhe_multibit_blind_rotate_dev, tfhe_multibit_combine_key_dev,
+                   write_fourier_form)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -27,4 +29,6 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "FullComplex64FftTable", "ApproxSignedBasis", "TfheFftContext", "tfhe_external_product_to",
            "tfhe_external_product_to_dev", "write_fourier_form", "TfheBlindRotateContext", "tfhe_blind_rotate",
            "tfhe_blind_rotate_dev", "lwe_modulus_switch_dev", "glwe_sample_extract", "glwe_sample_extract_dev",
-           "lwe_keyswitch", "lwe_keyswitch_dev", "TfheBootstrapContext", "tfhe_bootstrap", "tfhe_bootstrap_dev", "build", "lib", "library_path", "status_string"]
+           "lwe_keyswitch", "lwe_keyswitch_dev", "TfheBootstrapContext", "tfhe_bootstrap", "tfhe_bootstrap_dev",
+           "TfheMultiBitBlindRotateContext", "tfhe_multibit_blind_rotate", "tfhe_multibit_blind_rotate_dev",
+           "tfhe_multibit_combine_key_dev", "build", "lib", "library_path", "status_string"]

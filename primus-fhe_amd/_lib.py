@@ -195,6 +195,13 @@ def _declare(lib: C.CDLL) -> None:
         sig(br + "rotate_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
         sig(br + "rotate", ci, vp, vp, sz, f64p, sz, vp, sz)
         sig(tp + "mul_monomial_each_to_dev", ci, vp, vp, sz, vp, sz, vp, vp)
+        mb = tp + "mbrot_"                           # multi-bit blind rotation: grouping_factor mask elements per product
+        sig(mb + "create", ci, vp, sz, u32, sz, sz, sz, C.POINTER(vp))
+        sig(mb + "destroy", None, vp)
+        sig(mb + "in_use", ci, vp)
+        sig(mb + "scratch_bytes", sz, vp)
+        sig(mb + "rotate_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
+        sig(mb + "rotate", ci, vp, vp, sz, f64p, sz, vp, sz)
         # the bootstrap around the rotation: modulus switch, sample extraction, key switch and the handle over all of them
         sig(tp + "modswitch_dev", ci, ci, vp, sz, sz, u32, vp, sz, vp, sz, vp)
         sig(tp + "sample_extract_dev", ci, vp, sz, vp, sz, sz, vp, sz, vp)
@@ -203,11 +210,13 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "keyswitch", ci, ci, vp, sz, sz, vp, sz, sz, u32, sz, vp, sz)
         bs = tp + "bootstrap"
         sig(bs + "_create", ci, vp, sz, u32, sz, sz, u32, sz, ci, sz, C.POINTER(vp))
+        sig(bs + "_create_multibit", ci, vp, sz, u32, sz, sz, u32, sz, ci, sz, sz, C.POINTER(vp))
         sig(bs + "_destroy", None, vp)
         sig(bs + "_in_use", ci, vp)
         sig(bs + "_scratch_bytes", sz, vp)
         sig(bs + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp, sz, vp)
         sig(bs, ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp, sz)
+    sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)
     sig("pfhe_dcrt_transform_num_passes", ci, vp)

@@ -6,7 +6,7 @@
 //                      round(w 2N / 2^BITS) with ties up, computed without overflow.
 //   accumulator init   ACC_e = X^{neg_b[e]} TV, the rotation of pfhe_tfhe*_mul_monomial_each_to_dev with the test vector
 //                      read in place (one shared by the batch, or one per ciphertext).
-//   blind rotation     the existing handle (pfhe_fft.hip), called as it is.
+//   blind rotation     the classic or the multi-bit handle (pfhe_fft.hip), called as it is.
 //   sample extraction  Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial.
 //   key switch         out = (0, b) - sum_i sum_j d_{i,j} KSK[i][j], a sequence of Lwe::add_mul_scalar_assign
 //                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_step of
@@ -398,31 +398,33 @@ int keyswitch_host(int device, const W *lwe_in, size_t len_in, size_t in_dimensi
 
 // ---------------- the bootstrap handle ----------------
 
-// Owns a blind-rotation handle and, for `chunk` ciphertexts, the accumulator, the switched exponents, neg_b and (when a key
+// Owns a blind-rotation handle (classic or multi-bit) and, for `chunk` ciphertexts, the accumulator, the switched exponents, neg_b and (when a key
 // switch follows) the extracted LWE ciphertexts: all allocated at creation.
-template <class R, class W>
+template <class R, class M, class W>
 struct TfheBootstrapCore {
-    R *rot = nullptr;  // owned
+    R *rot = nullptr;  // owned: the classic rotation (pfhe_tfhe*_bootstrap_create) ...
+    M *mb = nullptr;   // ... or the multi-bit one (pfhe_tfhe*_bootstrap_create_multibit), never both
     PlanGuard guard;   // one holder at a time, successive calls on different streams ordered
     const pfhe_fft *fft = nullptr;
     u32 k = 1, n = 0;  // GLWE and LWE dimensions
     bool with_keyswitch = false;
     KsShape ks{};
-    size_t chunk = 1, key_len = 0, bytes = 0;
+    size_t chunk = 1, glwe = 0, key_len = 0, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
     W *acc = nullptr, *extracted = nullptr;
     u32 *exps = nullptr, *neg_b = nullptr;
     ~TfheBootstrapCore() {
-        if (!rot) return;
+        if (!rot && !mb) return;
         {
             DeviceGuard g(fft->device);
             for (void *b : {(void *)acc, (void *)extracted, (void *)exps, (void *)neg_b})
                 if (b) (void)counted_free(b);
         }
         delete rot;
+        delete mb;
     }
 };
-struct pfhe_tfhe_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe_blindrot, u64> {};
-struct pfhe_tfhe32_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe32_blindrot, u32> {};
+struct pfhe_tfhe_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe_blindrot, pfhe_tfhe_mbrot, u64> {};
+struct pfhe_tfhe32_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe32_blindrot, pfhe_tfhe32_mbrot, u32> {};
 
 namespace {
 
@@ -432,28 +434,51 @@ constexpr const char *kBootstrapLengths =
     "words, ksk k*N*ks_ell*(n+1) words (0 without a key switch) and lwe_out batch*(n+1) (batch*(k*N+1) without)";
 constexpr size_t kDefaultAccBytes = 256ull << 20;
 
-// the rotation's create first (its statuses, in its order), then what is the bootstrap's own
+// which blind rotation a bootstrap handle owns: the classic one, or the multi-bit one, whose key has (lwe_dimension / g)
+// 2^g keys
+enum class Rotation { Classic, MultiBit };
+
+// the rotation's create first (its statuses, in its order), then what is the bootstrap's own.  grouping_factor counts only
+// for the multi-bit rotation, which refuses any outside 1..4
 template <class H, class W>
 int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                      size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
-                     size_t chunk, H **out) {
+                     Rotation rotation, size_t grouping_factor, size_t chunk, H **out) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
-    PFHE_TRY(tfhe_blindrot_create_handle(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->rot));
+    size_t rot_chunk = 0;
+    const bool multibit = rotation == Rotation::MultiBit;
+    if (multibit) {
+        // everything that is decided before the device: the rotation's own checks in its order, then the divisibility
+        PFHE_TRY(tfhe_mbrot_check_args(8 * sizeof(W), fft, glwe_dimension, log_basis, decompose_length, grouping_factor));
+        if (lwe_dimension % grouping_factor != 0) {
+            set_last_error("TFHE multi-bit bootstrap: lwe_dimension must be a multiple of grouping_factor");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
+        PFHE_TRY(tfhe_mbrot_create_handle(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &h->mb));
+        h->glwe = h->mb->glwe;
+        h->key_len = h->mb->key_len;
+        rot_chunk = h->mb->chunk;
+    } else {
+        PFHE_TRY(tfhe_blindrot_create_handle(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->rot));
+        h->glwe = h->rot->glwe;
+        h->key_len = h->rot->key_len;
+        rot_chunk = h->rot->chunk;
+    }
     h->fft = fft;
     h->k = (u32)glwe_dimension;
     h->with_keyswitch = with_keyswitch != 0;
-    const size_t glwe = h->rot->glwe, ext = glwe_dimension * fft->n + 1;
+    const size_t glwe = h->glwe, ext = glwe_dimension * fft->n + 1;
     if (glwe_dimension == 0 || lwe_dimension == 0 || lwe_dimension >= 0x7fffffffull) {
         set_last_error("TFHE bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2");
         return PFHE_ERR_BAD_ARGUMENT;
     }
     h->n = (u32)lwe_dimension;
-    h->key_len = h->rot->key_len;
+    h->bsk_len = multibit ? ((lwe_dimension / grouping_factor) << grouping_factor) * h->key_len : lwe_dimension * h->key_len;
     if (h->with_keyswitch) PFHE_TRY(keyswitch_shape<W>(ext - 1, lwe_dimension, ks_log_basis, ks_decompose_length, h->ks));
     // chunk 0: the rotation's default, capped at about 256 MiB of accumulator
-    h->chunk = chunk ? h->rot->chunk : std::min(h->rot->chunk, std::max<size_t>(1, kDefaultAccBytes / (glwe * sizeof(W))));
+    h->chunk = chunk ? rot_chunk : std::min(rot_chunk, std::max<size_t>(1, kDefaultAccBytes / (glwe * sizeof(W))));
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     const size_t sizes[] = {h->chunk * glwe * sizeof(W), h->with_keyswitch ? h->chunk * ext * sizeof(W) : 0,
@@ -471,11 +496,11 @@ int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
 
 template <class W, class H>
 int bootstrap_check(const H *h, size_t len_in, size_t len_bsk, size_t len_tv, size_t len_ksk, size_t len_out, u64 &batch) {
-    const size_t glwe = h->rot->glwe, ext = (size_t)h->k * h->fft->n + 1;
+    const size_t glwe = h->glwe, ext = (size_t)h->k * h->fft->n + 1;
     const size_t out_words = h->with_keyswitch ? (size_t)h->n + 1 : ext;
     const size_t ksk_words = h->with_keyswitch ? (ext - 1) * h->ks.ell * ((size_t)h->n + 1) : 0;
     batch = len_in / ((size_t)h->n + 1);
-    if (len_in % ((size_t)h->n + 1) != 0 || len_bsk != (size_t)h->n * h->key_len || (len_tv != glwe && len_tv != batch * glwe) ||
+    if (len_in % ((size_t)h->n + 1) != 0 || len_bsk != h->bsk_len || (len_tv != glwe && len_tv != batch * glwe) ||
         len_ksk != ksk_words || len_out != batch * out_words) {
         set_last_error(kBootstrapLengths);
         return PFHE_ERR_BAD_LENGTH;
@@ -486,7 +511,7 @@ int bootstrap_check(const H *h, size_t len_in, size_t len_bsk, size_t len_tv, si
 template <class W, class H>
 int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
                   const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out, hipStream_t s) {
-    if (!h || !h->rot) return PFHE_ERR_BAD_ARGUMENT;
+    if (!h || (!h->rot && !h->mb)) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
     if (!h->with_keyswitch && (ksk || len_ksk)) {
         set_last_error("TFHE bootstrap: a handle without a key switch takes no key-switch key");
@@ -507,7 +532,7 @@ int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_
     const pfhe_fft &f = *h->fft;
     DeviceGuard g(f.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const size_t glwe = h->rot->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
+    const size_t glwe = h->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
     const size_t out_words = h->with_keyswitch ? in_words : ext;
     const u64 tv_stride = len_tv == glwe ? 0 : glwe;
     return ordered_on(h->guard, s, [&]() -> int {
@@ -516,7 +541,8 @@ int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_
             const u64 cur = std::min<u64>(h->chunk, batch - done);
             PFHE_TRY(launch_modswitch<W>(lwe_in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, s));
             PFHE_TRY(launch_acc_init<W>(tv + done * tv_stride, tv_stride, h->acc, h->neg_b, h->k + 1, f.log_n, cur, s));
-            PFHE_TRY(tfhe_blindrot_rotate_handle(h->rot, h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s));
+            PFHE_TRY(h->mb ? tfhe_mbrot_rotate_handle(h->mb, h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s)
+                           : tfhe_blindrot_rotate_handle(h->rot, h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s));
             W *lwe = h->with_keyswitch ? h->extracted : lwe_out + done * out_words;
             PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, s));
             if (h->with_keyswitch) PFHE_TRY(launch_keyswitch<W>(lwe, ksk, lwe_out + done * out_words, h->ks, cur, s));
@@ -529,7 +555,7 @@ int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_
 template <class W, class H>
 int bootstrap_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
                    const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out) {
-    if (!h || !h->rot) return PFHE_ERR_BAD_ARGUMENT;
+    if (!h || (!h->rot && !h->mb)) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
     if (!h->with_keyswitch && (ksk || len_ksk)) {
         set_last_error("TFHE bootstrap: a handle without a key switch takes no key-switch key");
@@ -557,6 +583,7 @@ int bootstrap_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size
 
 template <class H>
 size_t bootstrap_scratch(const H *h) {
+    if (h && h->mb) return h->mb->scratch + h->bytes;
     return h && h->rot && h->rot->plan ? h->rot->plan->scratch + h->rot->glue_bytes + h->bytes : 0;
 }
 
@@ -643,7 +670,19 @@ int pfhe_tfhe_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint3
                                size_t chunk, pfhe_tfhe_bootstrap_handle **out) {
     PFHE_GUARD_BEGIN
     return bootstrap_create<pfhe_tfhe_bootstrap_handle, u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
-                                                      ks_log_basis, ks_decompose_length, with_keyswitch, chunk, out);
+                                                      ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::Classic, 0,
+                                                      chunk, out);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                        size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length,
+                                        int with_keyswitch, size_t grouping_factor, size_t chunk,
+                                        pfhe_tfhe_bootstrap_handle **out) {
+    PFHE_GUARD_BEGIN
+    if (out) *out = nullptr;
+    return bootstrap_create<pfhe_tfhe_bootstrap_handle, u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                                      ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::MultiBit,
+                                                      grouping_factor, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h) { delete h; }
@@ -671,7 +710,19 @@ int pfhe_tfhe32_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uin
                                  size_t chunk, pfhe_tfhe32_bootstrap_handle **out) {
     PFHE_GUARD_BEGIN
     return bootstrap_create<pfhe_tfhe32_bootstrap_handle, u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
-                                                        ks_log_basis, ks_decompose_length, with_keyswitch, chunk, out);
+                                                        ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::Classic,
+                                                        0, chunk, out);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
+                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
+                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor, size_t chunk,
+                                          pfhe_tfhe32_bootstrap_handle **out) {
+    PFHE_GUARD_BEGIN
+    if (out) *out = nullptr;
+    return bootstrap_create<pfhe_tfhe32_bootstrap_handle, u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                                        ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::MultiBit,
+                                                        grouping_factor, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h) { delete h; }

@@ -27,6 +27,13 @@
 //   whole loop (the fused shape): one launch per chunk, a workgroup per ciphertext, ACC in LDS from the first step to the
 //            last, the fused product's own device code per step;
 //   per step  (every other shape, or PFHE_DISABLE_FUSED_TFHE_BLINDROT): the product's launches plus one glue launch.
+//
+// The multi-bit rotation (pfhe_tfhe{,32}_mbrot_*, pfhe_tfhe_mb_combine_key_dev): per group of g mask elements and ciphertext,
+// ACC = ACC (x) sum_j X^{r_j} BSK[t][j], the per-ciphertext key formed slot by slot in the Fourier domain (mb_combined_slots).
+//   whole loop (the fused shape): one launch per chunk, ACC in LDS across all groups, the key formed inside the accumulate code;
+//   per group  (every other shape, or the same switch): the Hermitian parts of the group's 2^g keys, the digit transforms of
+//            ACC, a multiply-accumulate that forms the key per ciphertext, the inverses back into ACC;
+//   combined key as a call of its own: one ciphertext's key of one group in the reference's layout, for the plain product.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -151,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_mulacc_kernel(const double2 *__
     const double2 *sp = spec + e * rows * ell * m + i;
     const double2 *kh = keyh + (u64)c * m + i;
     double2 a = make_double2(0.0, 0.0);
-    for (u32 rl = 0; rl < rows * ell; ++rl) a = cadd(a, cmul(sp[(u64)rl * m], kh[(u64)rl * rows * m]));
+    for (u32 rl = 0; rl < rows * ell; ++rl) a = cmac_fixed(a, sp[(u64)rl * m], kh[(u64)rl * rows * m]);
     acc[t] = a;
 }
 
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_fused_kernel(const W *__restric
     double2 acc0[kFusedPer], acc1[kFusedPer];
 #pragma unroll
     for (int u = 0; u < kFusedPer; ++u) acc0[u] = acc1[u] = make_double2(0.0, 0.0);
-    fused_accumulate_rows<W>([&](u32 r) { return GlobalRow<W>{x + r * n, m}; }, key, lds_p, tw, s, acc0, acc1);
+    fused_accumulate_rows<W>([&](u32 r) { return GlobalRow<W>{x + r * n, m}; }, ClassicKey{key}, lds_p, tw, s, acc0, acc1);
     fused_inverse_rows(acc0, acc1, lds_p, tw, s, [&](u32 c, u32 i, double lo, double hi) {
         o[c * n + i] = to_torus<W>(lo);
         o[c * n + i + m] = to_torus<W>(hi);
@@ -227,13 +234,101 @@ __global__ __launch_bounds__(kThreads) void tfhe_blindrot_loop_kernel(W *__restr
                 d.b[u] = i < m ? rotated_diff(a + row * n, i + m, rot, high, n - 1) : (W)0;
             }
             return d;
-        }, key, lds_l, tw, s, acc0, acc1);
+        }, ClassicKey{key}, lds_l, tw, s, acc0, acc1);
         fused_inverse_rows(acc0, acc1, lds_l, tw, s, [&](u32 c, u32 i, double lo, double hi) {
             a[c * n + i] += to_torus<W>(lo);
             a[c * n + i + m] += to_torus<W>(hi);
         });
     }
     for (u32 i = threadIdx.x; i < 2 * n; i += blockDim.x) g[i] = a[i];
+}
+
+// ---------------- the multi-bit blind rotation ----------------
+
+// input row r of an accumulator that sits in LDS: read in place at every level, no rotated difference is formed
+template <class W>
+struct LdsRow {
+    const W *xr;
+    u32 m;
+    __device__ __forceinline__ W lo(int, u32 i) const { return xr[i]; }
+    __device__ __forceinline__ W hi(int, u32 i) const { return xr[i + m]; }
+};
+
+// The whole multi-bit loop of one ciphertext in one workgroup (k = 1, N <= 2^11), ACC in LDS behind the digit spectrum as
+// in tfhe_blindrot_loop_kernel.  Per group of g mask elements: ACC = ACC (x) K with K = sum_j X^{r_j} BSK[t][j] formed slot
+// by slot in the accumulate code (MultiBitKey), the sink ASSIGNS to_torus(E) to ACC.  Every read of ACC in a group precedes
+// the barrier that ends fused_accumulate_rows, every write follows it, and fused_inverse_rows ends behind a barrier.
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_mb_blindrot_loop_kernel(W *__restrict__ acc, const double2 *__restrict__ bsk,
+                                                                         const u32 *__restrict__ exps, u32 groups, u32 g,
+                                                                         const double2 *__restrict__ tw, Shape s) {
+    extern __shared__ __attribute__((aligned(16))) double2 lds_m[];
+    const u32 n = 1u << s.log_n, m = n >> 1;
+    W *a = reinterpret_cast<W *>(reinterpret_cast<char *>(lds_m) + lds_bytes(s.log_n));
+    W *gl = acc + (u64)blockIdx.x * 2 * n;
+    for (u32 i = threadIdx.x; i < 2 * n; i += blockDim.x) a[i] = gl[i];
+    __syncthreads();
+    const u32 *ex = exps + (u64)blockIdx.x * groups * g;
+    const u64 key_len = (u64)4 * s.ell * n;
+    for (u32 t = 0; t < groups; ++t) {
+        const MultiBitKey key{bsk + ((u64)t << g) * key_len, key_len, mb_load_exps(ex + t * g, g, n), g};
+        double2 acc0[kFusedPer], acc1[kFusedPer];
+#pragma unroll
+        for (int u = 0; u < kFusedPer; ++u) acc0[u] = acc1[u] = make_double2(0.0, 0.0);
+        fused_accumulate_rows<W>([&](u32 row) { return LdsRow<W>{a + row * n, m}; }, key, lds_m, tw, s, acc0, acc1);
+        fused_inverse_rows(acc0, acc1, lds_m, tw, s, [&](u32 c, u32 i, double lo, double hi) {
+            a[c * n + i] = to_torus<W>(lo);
+            a[c * n + i + m] = to_torus<W>(hi);
+        });
+    }
+    for (u32 i = threadIdx.x; i < 2 * n; i += blockDim.x) gl[i] = a[i];
+}
+
+// tfhe_mulacc_kernel with the key's Hermitian part formed per ciphertext: keyh holds the Hermitian parts of the group's 2^g
+// keys (tfhe_key_herm_kernel's output, key after key), exps points at the group's first exponent of ciphertext 0 and
+// ciphertext e's are exp_stride further on.  acc[e][c][i] = sum over r, l (in that order) of spec[e][r][l][i] * Kh_e[r][l][c][i]
+__global__ __launch_bounds__(kThreads) void tfhe_mb_mulacc_kernel(const double2 *__restrict__ spec,
+                                                                  const double2 *__restrict__ keyh, double2 *__restrict__ acc,
+                                                                  const u32 *__restrict__ exps, u32 exp_stride, u32 g,
+                                                                  const double2 *__restrict__ tw, u32 log_n, u32 k, u32 ell,
+                                                                  u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u32 n = 1u << log_n, m = n >> 1, rows = k + 1;
+    const u32 i = (u32)(t & (m - 1));
+    const u64 ec = t >> (log_n - 1);
+    const u32 c = (u32)(ec % rows);
+    const u64 e = ec / rows;
+    const MbExps x = mb_load_exps(exps + e * exp_stride, g, n);
+    const double2 *sp = spec + e * rows * ell * m + i;
+    const double2 *kh = keyh + (u64)c * m + i;
+    const u64 keyh_len = (u64)rows * ell * rows * m;
+    double2 a = make_double2(0.0, 0.0);
+    for (u32 rl = 0; rl < rows * ell; ++rl) {
+        double2 kc[1];
+        mb_combined_slots<1>([&](u32 j, int) { return kh[j * keyh_len + (u64)rl * rows * m]; }, x, g, i, n, tw, kc);
+        a = cmac_fixed(a, sp[(u64)rl * m], kc[0]);
+    }
+    acc[t] = a;
+}
+
+// The combined key of ONE ciphertext and ONE group as a key of its own, in the reference's full layout: for polynomial p
+// and slot i, out[p][2i] = Kh[i] and out[p][(1 - 2i) mod N] = conj(Kh[i]).  The product's Hermitian step returns Kh[i] from
+// that bit for bit ((x + x) * 0.5 is exact).
+__global__ __launch_bounds__(kThreads) void tfhe_mb_combine_key_kernel(const double2 *__restrict__ keys,
+                                                                       const u32 *__restrict__ exps, double2 *__restrict__ out,
+                                                                       u32 g, const double2 *__restrict__ tw, u32 log_n,
+                                                                       u64 key_len, u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u32 n = 1u << log_n, m = n >> 1;
+    const u64 p = t >> (log_n - 1);
+    const u32 i = (u32)(t & (m - 1));
+    double2 kc[1];
+    mb_combined_slots<1>([&](u32 j, int) { return herm_slot(keys + j * key_len + p * n, i, n); }, mb_load_exps(exps, g, n), g, i,
+                         n, tw, kc);
+    out[p * n + 2 * i] = kc[0];
+    out[p * n + ((n + 1 - 2 * i) & (n - 1))] = make_double2(kc[0].x, -kc[0].y);
 }
 
 // The element-wise glue of the per-step form, one thread per coefficient, as blindrot_glue_kernel on torus words:
@@ -351,6 +446,18 @@ constexpr const char *kPlanBusy = "TFHE product plan in use by another thread (o
 constexpr size_t kMaxGlweDimension = 64;
 constexpr size_t kDefaultScratchBytes = 256ull << 20;
 
+// what a plan checks before the device is touched, in this order: the basis's assert!s, k, the table
+template <class W>
+int plan_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, u32 &ell, u32 &drop) {
+    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
+    if (glwe_dimension > kMaxGlweDimension) {
+        set_last_error("glwe_dimension above 64 is not supported");
+        return PFHE_ERR_UNSUPPORTED;
+    }
+    if (!fft) return PFHE_ERR_BAD_ARGUMENT;
+    return PFHE_OK;
+}
+
 template <class P>
 int plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t chunk,
                 P **out) {
@@ -358,12 +465,7 @@ int plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, 
     *out = nullptr;
     using W = typename std::conditional<std::is_same<P, pfhe_tfhe_plan>::value, u64, u32>::type;
     u32 ell = 0, drop = 0;
-    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
-    if (glwe_dimension > kMaxGlweDimension) {
-        set_last_error("glwe_dimension above 64 is not supported");
-        return PFHE_ERR_UNSUPPORTED;
-    }
-    if (!fft) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_TRY(plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, ell, drop));
     auto p = std::make_unique<P>();
     p->k = (u32)glwe_dimension;
     p->log_basis = log_basis;
@@ -678,6 +780,202 @@ size_t tfhe_blindrot_scratch(const H *h) {
     return h && h->plan ? h->plan->scratch + h->glue_bytes : 0;
 }
 
+// ---------------- multi-bit blind rotation ----------------
+
+constexpr const char *kMbRotBusy = "TFHE multi-bit blind-rotation handle in use by another thread (one handle per thread)";
+constexpr const char *kMbRotLengths = "TFHE multi-bit blind rotation: acc must be batch*(k+1)*N words, bsk groups*2^g keys of "
+                                      "(k+1)*ell*(k+1)*N complex values and exps batch*groups*g exponents";
+constexpr size_t kMaxGrouping = 4;
+
+template <class W>
+int mbrot_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                size_t grouping_factor, u32 &ell, u32 &drop) {
+    PFHE_TRY(plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, ell, drop));
+    if (grouping_factor == 0 || grouping_factor > kMaxGrouping) {
+        set_last_error("grouping_factor must be in 1..4");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    return PFHE_OK;
+}
+
+// plan_create's checks in plan_create's order through plan_check, then the grouping factor, all before the device; the
+// whole-loop kernel on the product's fused shape unless PFHE_DISABLE_FUSED_TFHE_BLINDROT is set when the handle is created
+template <class H, class W>
+int tfhe_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                      size_t grouping_factor, size_t chunk, H **out) {
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    u32 ell = 0, drop = 0;
+    PFHE_TRY(mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, ell, drop));
+    auto h = std::make_unique<H>();
+    h->k = (u32)glwe_dimension;
+    h->log_basis = log_basis;
+    h->ell = ell;
+    h->drop_bits = drop;
+    h->g = (u32)grouping_factor;
+    const size_t m = fft->n / 2, rows = glwe_dimension + 1;
+    h->glwe = rows * fft->n;
+    h->key_len = rows * ell * h->glwe;
+    h->whole_loop = h->k == 1 && fft->log_n <= kFusedMaxLogN && std::getenv("PFHE_DISABLE_FUSED_TFHE_BLINDROT") == nullptr;
+    const size_t per_ct = (rows * ell + rows) * m * sizeof(double2);
+    h->chunk = chunk ? chunk : (h->whole_loop ? 65536 : std::max<size_t>(1, kDefaultScratchBytes / per_ct));
+    h->chunk = std::min<size_t>(h->chunk, h->whole_loop ? 0x7fffffffull : 0x7fffffffull / (rows * ell));
+    DeviceGuard g(fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    h->fft = fft;
+    if (!h->whole_loop) {
+        const size_t sizes[] = {h->chunk * rows * ell * m, h->chunk * rows * m, (rows * ell * rows * m) << h->g};
+        double2 **bufs[] = {&h->spec, &h->acc, &h->keyh};
+        for (int i = 0; i < 3; ++i) {
+            void *b = nullptr;
+            PFHE_HIP(counted_malloc(&b, sizes[i] * sizeof(double2)));
+            *bufs[i] = (double2 *)b;
+            h->scratch += sizes[i] * sizeof(double2);
+        }
+    }
+    PFHE_TRY(h->guard.init(fft->device));
+    *out = h.release();
+    return PFHE_OK;
+}
+
+// the launches of one rotation (arguments already checked)
+template <class W, class H>
+int tfhe_mbrot_impl(H *h, W *acc, const double2 *bsk, const uint32_t *exps, u64 batch, u64 groups, hipStream_t s) {
+    const pfhe_fft &f = *h->fft;
+    const Shape sh{f.log_n, h->k, h->log_basis, h->ell, h->drop_bits};
+    const u32 rows = h->k + 1, m = (u32)(f.n / 2), n_mask = (u32)(groups * h->g);
+    if (h->whole_loop) {
+        for (u64 done = 0; done < batch; done += h->chunk) {
+            const u64 cur = std::min<u64>(h->chunk, batch - done);
+            hipLaunchKernelGGL(tfhe_mb_blindrot_loop_kernel<W>, dim3((u32)cur), dim3(kThreads),
+                               lds_bytes(f.log_n) + h->glwe * sizeof(W), s, acc + done * h->glwe, bsk, exps + done * n_mask,
+                               (u32)groups, h->g, f.tw, sh);
+            PFHE_HIP(hipGetLastError());
+        }
+        return PFHE_OK;
+    }
+    // chunk after chunk; every group of a chunk runs before the next chunk starts.  Per group: the Hermitian parts of its
+    // 2^g keys, the digit spectra of ACC itself, the multiply-accumulate against the per-ciphertext key, the inverses into ACC
+    const u64 kt = ((u64)rows * h->ell * rows * m) << h->g;
+    for (u64 done = 0; done < batch; done += h->chunk) {
+        const u64 cur = std::min<u64>(h->chunk, batch - done);
+        W *a = acc + done * h->glwe;
+        const u64 at = cur * rows * m;
+        for (u64 t = 0; t < groups; ++t) {
+            hipLaunchKernelGGL(tfhe_key_herm_kernel, dim3((u32)((kt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                               bsk + (t << h->g) * h->key_len, h->keyh, f.log_n, kt);
+            PFHE_HIP(hipGetLastError());
+            hipLaunchKernelGGL(tfhe_digit_fwd_kernel<W>, dim3((u32)(cur * rows * h->ell)), dim3(kThreads), lds_bytes(f.log_n), s,
+                               a, h->spec, f.tw, sh);
+            PFHE_HIP(hipGetLastError());
+            hipLaunchKernelGGL(tfhe_mb_mulacc_kernel, dim3((u32)((at + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, h->spec,
+                               h->keyh, h->acc, exps + done * n_mask + t * h->g, n_mask, h->g, f.tw, f.log_n, h->k, h->ell, at);
+            PFHE_HIP(hipGetLastError());
+            hipLaunchKernelGGL((fft_inverse_kernel<W, false>), dim3((u32)(cur * rows)), dim3(kThreads), lds_bytes(f.log_n), s,
+                               h->acc, a, f.tw, f.log_n);
+            PFHE_HIP(hipGetLastError());
+        }
+    }
+    return PFHE_OK;
+}
+
+template <class H>
+bool mbrot_lengths_ok(const H *h, size_t len_acc, size_t len_bsk, size_t len_exps, u64 &batch, u64 &groups) {
+    const size_t group_len = h->key_len << h->g;
+    if (len_acc % h->glwe != 0 || len_bsk % group_len != 0) return false;
+    batch = len_acc / h->glwe;
+    groups = len_bsk / group_len;
+    return len_exps == batch * groups * h->g;
+}
+
+template <class W, class H>
+int tfhe_mbrot_dev(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
+                   hipStream_t s) {
+    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kMbRotBusy);
+    u64 batch = 0, groups = 0;
+    if (!mbrot_lengths_ok(h, len_acc, len_bsk, len_exps, batch, groups)) {
+        set_last_error(kMbRotLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (batch == 0 || groups == 0) return PFHE_OK;
+    if (groups * h->g > 0xffffffffull) return PFHE_ERR_BAD_LENGTH;
+    if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(acc);
+    PFHE_REQUIRE_ALIGNED(bsk);
+    DeviceGuard g(h->fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return ordered_on(h->guard, s, [&] { return tfhe_mbrot_impl<W>(h, acc, (const double2 *)bsk, exps, batch, groups, s); });
+}
+
+// host form: every exponent must be below 2N; staged through the pooled context
+template <class W, class H>
+int tfhe_mbrot_host(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps) {
+    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kMbRotBusy);
+    if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
+    const pfhe_fft &f = *h->fft;
+    for (size_t i = 0; i < len_exps; ++i) {
+        if (exps[i] >= 2 * f.n) {
+            set_last_error("TFHE multi-bit blind rotation: every exponent must be below 2N");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
+    }
+    u64 batch = 0, groups = 0;
+    if (!mbrot_lengths_ok(h, len_acc, len_bsk, len_exps, batch, groups)) {
+        set_last_error(kMbRotLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
+    DeviceGuard g(f.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(f.device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *a = nullptr, *k = nullptr, *x = nullptr;
+    PFHE_TRY(st.upload(acc, len_acc * sizeof(W), &a));
+    PFHE_TRY(st.upload(bsk, len_bsk * 2 * sizeof(double), &k));
+    PFHE_TRY(st.upload(exps, len_exps * sizeof(uint32_t), &x));
+    PFHE_TRY(tfhe_mbrot_dev<W>(h, (W *)a, len_acc, (const double *)k, len_bsk, (const uint32_t *)x, len_exps, st.stream()));
+    PFHE_TRY(st.download(acc, a, len_acc * sizeof(W)));
+    return st.finish();
+}
+
+// the combined key of one ciphertext and one group as a key in the reference's layout
+int mb_combine_key_dev(const pfhe_fft *f, size_t glwe_dimension, size_t decompose_length, size_t grouping_factor,
+                       const double *keys, size_t len_keys, const uint32_t *exps, size_t len_exps, double *out, size_t len_out,
+                       hipStream_t s) {
+    if (!f) return PFHE_ERR_BAD_ARGUMENT;
+    if (glwe_dimension > kMaxGlweDimension) {
+        set_last_error("glwe_dimension above 64 is not supported");
+        return PFHE_ERR_UNSUPPORTED;
+    }
+    if (decompose_length == 0 || decompose_length > 64 || grouping_factor == 0 || grouping_factor > kMaxGrouping) {
+        set_last_error("multi-bit key combination: decompose_length must be in 1..64 and grouping_factor in 1..4");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    const size_t rows = glwe_dimension + 1, key_len = rows * decompose_length * rows * f->n;
+    if (len_keys != key_len << grouping_factor || len_exps != grouping_factor || len_out != key_len) {
+        set_last_error("multi-bit key combination: keys must be 2^g keys of (k+1)*ell*(k+1)*N complex values, exps g exponents "
+                       "and out one key");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (!keys || !exps || !out) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(keys);
+    PFHE_REQUIRE_ALIGNED(out);
+    const uintptr_t k0 = (uintptr_t)keys, o0 = (uintptr_t)out;
+    if (k0 < o0 + len_out * sizeof(double2) && o0 < k0 + len_keys * sizeof(double2)) {
+        set_last_error("multi-bit key combination: the output must not overlap the keys");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    DeviceGuard g(f->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    const u64 total = key_len / 2;
+    hipLaunchKernelGGL(tfhe_mb_combine_key_kernel, dim3((u32)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                       (const double2 *)keys, exps, (double2 *)out, (u32)grouping_factor, f->tw, f->log_n, (u64)key_len, total);
+    PFHE_HIP(hipGetLastError());
+    return PFHE_OK;
+}
+
 }  // namespace
 
 namespace pfhe {
@@ -700,6 +998,30 @@ int tfhe_blindrot_rotate_handle(pfhe_tfhe_blindrot *h, u64 *acc, size_t len_acc,
 int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
                                 const uint32_t *exps, size_t len_exps, hipStream_t s) {
     return ::tfhe_blindrot_dev<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+}
+
+int tfhe_mbrot_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                          size_t grouping_factor) {
+    u32 ell = 0, drop = 0;
+    return bits == 64 ? ::mbrot_check<u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, ell, drop)
+                      : ::mbrot_check<u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, ell, drop);
+}
+int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                             size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out) {
+    return ::tfhe_mbrot_create<pfhe_tfhe_mbrot, u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
+}
+int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                             size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out) {
+    return ::tfhe_mbrot_create<pfhe_tfhe32_mbrot, u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk,
+                                                       out);
+}
+int tfhe_mbrot_rotate_handle(pfhe_tfhe_mbrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                             const uint32_t *exps, size_t len_exps, hipStream_t s) {
+    return ::tfhe_mbrot_dev<u64>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+}
+int tfhe_mbrot_rotate_handle(pfhe_tfhe32_mbrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                             const uint32_t *exps, size_t len_exps, hipStream_t s) {
+    return ::tfhe_mbrot_dev<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
 }
 
 }  // namespace pfhe
@@ -910,6 +1232,58 @@ int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_
                                          size_t polys_per_exp, uint32_t *out_dev, void *stream) {
     PFHE_GUARD_BEGIN
     return torus_monomial_each<u32>(fft, a_dev, len, exps_dev, polys_per_exp, out_dev, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                           size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out) {
+    PFHE_GUARD_BEGIN
+    return tfhe_mbrot_create<pfhe_tfhe_mbrot, u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe_mbrot_destroy(pfhe_tfhe_mbrot *h) { delete h; }
+int pfhe_tfhe_mbrot_in_use(const pfhe_tfhe_mbrot *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe_mbrot_scratch_bytes(const pfhe_tfhe_mbrot *h) { return h ? h->scratch : 0; }
+int pfhe_tfhe_mbrot_rotate_dev(pfhe_tfhe_mbrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
+                               const uint32_t *exps_dev, size_t len_exps, void *stream) {
+    PFHE_GUARD_BEGIN
+    return tfhe_mbrot_dev<u64>(h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_mbrot_rotate(pfhe_tfhe_mbrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                           const uint32_t *exps, size_t len_exps) {
+    PFHE_GUARD_BEGIN
+    return tfhe_mbrot_host<u64>(h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                             size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out) {
+    PFHE_GUARD_BEGIN
+    return tfhe_mbrot_create<pfhe_tfhe32_mbrot, u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk,
+                                                     out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe32_mbrot_destroy(pfhe_tfhe32_mbrot *h) { delete h; }
+int pfhe_tfhe32_mbrot_in_use(const pfhe_tfhe32_mbrot *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe32_mbrot_scratch_bytes(const pfhe_tfhe32_mbrot *h) { return h ? h->scratch : 0; }
+int pfhe_tfhe32_mbrot_rotate_dev(pfhe_tfhe32_mbrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
+                                 const uint32_t *exps_dev, size_t len_exps, void *stream) {
+    PFHE_GUARD_BEGIN
+    return tfhe_mbrot_dev<u32>(h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_mbrot_rotate(pfhe_tfhe32_mbrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                             const uint32_t *exps, size_t len_exps) {
+    PFHE_GUARD_BEGIN
+    return tfhe_mbrot_host<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_mb_combine_key_dev(const pfhe_fft *fft, size_t glwe_dimension, size_t decompose_length, size_t grouping_factor,
+                                 const double *keys_dev, size_t len_keys, const uint32_t *exps_dev, size_t len_exps,
+                                 double *out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return mb_combine_key_dev(fft, glwe_dimension, decompose_length, grouping_factor, keys_dev, len_keys, exps_dev, len_exps,
+                              out_dev, len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 

@@ -4,7 +4,9 @@
 // (k = 1, N <= 2^11): fused_accumulate_rows (digits, forward transforms and the multiply-accumulate of both input rows) and
 // fused_inverse_rows (the two folded inverses and the torus wrap).  tfhe_fused_kernel runs them once on words read from
 // global memory; tfhe_blindrot_loop_kernel runs them once per step on an accumulator that stays in LDS.  Both inline the
-// same code, so a step of the loop is the product's arithmetic, operation for operation.
+// same code, so a step of the loop is the product's arithmetic, operation for operation.  fused_accumulate_rows takes the
+// key's Hermitian part from a key source: ClassicKey (one key in memory) or MultiBitKey (the multi-bit rotation's
+// per-ciphertext combination of 2^g keys, mb_combined_slots, shared with the per-group and combined-key kernels).
 #pragma once
 
 #include "pfhe_common.hpp"
@@ -110,6 +112,85 @@ struct Shape {
     u32 log_n, k, log_basis, ell, drop_bits;
 };
 
+// ---------------- the multi-bit key combination ----------------
+//
+// A group of g mask elements has 2^g keys, key j for the pattern j of the group's key bits.  With r_j the sum of the
+// group's exponents at the set bits of j (modulo 2N), the per-ciphertext key is K = sum_j X^{r_j} K_j; the product sees
+// only its Hermitian part, and the spectrum M(r) of X^r is Hermitian-symmetric, so the arithmetic is DEFINED on
+// half-spectrum slots: Kh[m] = sum_j M(r_j)[2m] Herm(K_j)[2m], M(r)[k'] = root[(r (1 - 2k')) mod 2N], root[i] = tw[i] for
+// i < N and -tw[i - N] otherwise.  j ascending, the j = 0 term added without a multiplication, every multiply-add an
+// explicit fma: the same bits in every kernel that inlines mb_combined_slots.
+
+// Herm(K)[2i] of one key polynomial in the reference's layout, as fused_accumulate_rows' classic source forms it
+__device__ __forceinline__ double2 herm_slot(const double2 *__restrict__ kp, u32 i, u32 n) {
+    const double2 a = kp[2 * i], b = kp[(n + 1 - 2 * i) & (n - 1)];
+    return make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
+}
+
+// the exponents of one group of one ciphertext, each modulo 2N; 0 past the grouping factor
+struct MbExps {
+    u32 e0, e1, e2, e3;
+};
+__device__ __forceinline__ MbExps mb_load_exps(const u32 *__restrict__ ex, u32 g, u32 n) {
+    const u32 mask = 2 * n - 1;
+    return MbExps{ex[0] & mask, g > 1 ? ex[1] & mask : 0u, g > 2 ? ex[2] & mask : 0u, g > 3 ? ex[3] & mask : 0u};
+}
+
+// kh[c] = Kh[i] of C key polynomials that share the slot: herm(j, c) is Herm(K_j)[2i] of polynomial c.  The twiddle index
+// stays in 32 bits: r < 2N <= 2^15 and 4i < 2N, so r 4i < 2^30, and wrapping modulo 2^32 agrees with modulo 2N.
+template <int C, class Herm>
+__device__ __forceinline__ void mb_combined_slots(const Herm herm, const MbExps x, u32 g, u32 i, u32 n,
+                                                  const double2 *__restrict__ tw, double2 (&kh)[C]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) kh[c] = herm(0u, c);
+    for (u32 j = 1; j < (1u << g); ++j) {
+        const u32 r = ((j & 1 ? x.e0 : 0u) + (j & 2 ? x.e1 : 0u) + (j & 4 ? x.e2 : 0u) + (j & 8 ? x.e3 : 0u)) & (2 * n - 1);
+        const u32 idx = (r - r * 4 * i) & (2 * n - 1);
+        double2 w = tw[idx & (n - 1)];
+        if (idx & n) w = make_double2(-w.x, -w.y);
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const double2 h = herm(j, c);
+            kh[c].x = fma(-w.y, h.y, fma(w.x, h.x, kh[c].x));
+            kh[c].y = fma(w.y, h.x, fma(w.x, h.y, kh[c].y));
+        }
+    }
+}
+
+// acc + d * h in ONE fixed sequence of operations, whatever surrounds the call: the two cross products rounded on their own,
+// the other two fused, then the adds.  Every multiply-accumulate of a digit spectrum with a key's Hermitian part goes
+// through here, the classic product's and the multi-bit rotation's alike, so all of them round alike.  Left to contraction
+// the pairing depends on where h comes from (loaded or averaged from memory: this one; out of a chain of fused
+// multiply-adds: the other pairing of the imaginary part), and the forms would differ in the last bit.
+__device__ __forceinline__ double2 cmac_fixed(double2 acc, double2 d, double2 h) {
+#pragma clang fp contract(off)
+    const double x = fma(d.x, h.x, -(d.y * h.y));
+    const double y = fma(d.y, h.x, d.x * h.y);
+    return make_double2(acc.x + x, acc.y + y);
+}
+
+// the multi-bit key source of fused_accumulate_rows: the group's 2^g keys end to end in the reference's layout
+struct MultiBitKey {
+    const double2 *__restrict__ keys;
+    u64 key_len;
+    MbExps x;
+    u32 g;
+    struct Level {
+        const double2 *k0;
+        u64 key_len;
+        MbExps x;
+        u32 g, n;
+        __device__ __forceinline__ void mac(u32 i, const double2 *__restrict__ tw, double2 d, double2 &acc0,
+                                            double2 &acc1) const {
+            double2 kh[2];
+            mb_combined_slots<2>([&](u32 j, int c) { return herm_slot(k0 + j * key_len + (u32)c * n, i, n); }, x, g, i, n, tw, kh);
+            acc0 = cmac_fixed(acc0, d, kh[0]);
+            acc1 = cmac_fixed(acc1, d, kh[1]);
+        }
+    };
+    __device__ __forceinline__ Level level(u32 rl, u32 n) const { return Level{keys + (u64)(rl * 2) * n, key_len, x, g, n}; }
+};
+
 // ---------------- the fused product (k = 1, N <= 2^11), one workgroup per ciphertext ----------------
 //
 // Thread t owns coefficient pairs (i, i + N/2) and half-spectrum slots i for i = t + 256 u; the accumulators of both
@@ -125,12 +206,33 @@ struct GlobalRow {
     __device__ __forceinline__ W hi(int, u32 i) const { return xr[i + m]; }
 };
 
+// Where the Hermitian part of the key comes from.  level(rl, n) fixes the key polynomials of input row r and level l
+// (rl = r ell + l); mac(i, tw, d, acc0, acc1) adds d * Herm(key[r][l][0 / 1])[2i] to the two accumulators.  The classic
+// source reads ONE key in the reference's layout.
+struct ClassicKey {
+    const double2 *__restrict__ key;
+    struct Level {
+        const double2 *k0, *k1;
+        u32 n;
+        __device__ __forceinline__ void mac(u32 i, const double2 *, double2 d, double2 &acc0, double2 &acc1) const {
+            const u32 j = (n + 1 - 2 * i) & (n - 1);
+            const double2 a0 = k0[2 * i], b0 = k0[j], a1 = k1[2 * i], b1 = k1[j];
+            acc0 = cmac_fixed(acc0, d, make_double2(0.5 * (a0.x + b0.x), 0.5 * (a0.y - b0.y)));
+            acc1 = cmac_fixed(acc1, d, make_double2(0.5 * (a1.x + b1.x), 0.5 * (a1.y - b1.y)));
+        }
+    };
+    __device__ __forceinline__ Level level(u32 rl, u32 n) const {
+        const double2 *k0 = key + (u64)(rl * 2) * n;
+        return Level{k0, k0 + n, n};
+    }
+};
+
 // both input rows, all levels: rows(r) gives row r, whose lo(u, i) / hi(u, i) are the words of coefficients i and
 // i + N/2 of slot u.  Per level: their signed digits, the forward half transform in lds_p, and acc0 / acc1 += spectrum *
-// Herm(key[r][l][0 / 1]).  Only the carries stay in registers between levels: bit u of carry0 / carry1 is the carry of
+// Herm(key[r][l][0 / 1]) as the key source gives it.  Only the carries stay in registers between levels: bit u of carry0 / carry1 is the carry of
 // coefficient i / i + N/2 of slot u.  Ends behind a barrier.
-template <class W, class Rows>
-__device__ __forceinline__ void fused_accumulate_rows(const Rows rows, const double2 *__restrict__ key, double2 *lds_p,
+template <class W, class Rows, class Key>
+__device__ __forceinline__ void fused_accumulate_rows(const Rows rows, const Key key, double2 *lds_p,
                                                       const double2 *__restrict__ tw, const Shape s,
                                                       double2 (&acc0)[kFusedPer], double2 (&acc1)[kFusedPer]) {
     const u32 n = 1u << s.log_n, m = n >> 1, log_m = s.log_n - 1;
@@ -161,16 +263,13 @@ __device__ __forceinline__ void fused_accumulate_rows(const Rows rows, const dou
             }
             __syncthreads();
             fft_dif(lds_p, log_m, s.log_n, tw);
-            const double2 *k0 = key + (u64)((r * s.ell + l) * 2) * n, *k1 = k0 + n;
+            const auto kl = key.level(r * s.ell + l, n);
 #pragma unroll
             for (int u = 0; u < kFusedPer; ++u) {
                 const u32 i = threadIdx.x + u * kFftThreads;
                 if (i < m) {
                     const double2 d = lds_p[lpad(bitrev(i, log_m))];
-                    const u32 j = (n + 1 - 2 * i) & (n - 1);
-                    const double2 a0 = k0[2 * i], b0 = k0[j], a1 = k1[2 * i], b1 = k1[j];
-                    acc0[u] = cadd(acc0[u], cmul(d, make_double2(0.5 * (a0.x + b0.x), 0.5 * (a0.y - b0.y))));
-                    acc1[u] = cadd(acc1[u], cmul(d, make_double2(0.5 * (a1.x + b1.x), 0.5 * (a1.y - b1.y))));
+                    kl.mac(i, tw, d, acc0[u], acc1[u]);
                 }
             }
             __syncthreads();  // the next level overwrites the digit spectrum

@@ -1,4 +1,4 @@
-// pfhe_tfhe_handles.hpp — what the torus-side handles own (pfhe_fft, the TFHE product plan, the blind-rotation handle) and
+// pfhe_tfhe_handles.hpp — what the torus-side handles own (pfhe_fft, the TFHE product plan, the two blind-rotation handles) and
 // the basis check they share.  Seen by pfhe_fft.hip, which implements them, and by pfhe_bootstrap.hip, whose bootstrap
 // handle is built around a blind-rotation handle.  Host only.
 #pragma once
@@ -64,6 +64,28 @@ struct TfheBlindRotCore {
 struct pfhe_tfhe_blindrot : TfheBlindRotCore<pfhe_tfhe_plan, pfhe::u64> {};
 struct pfhe_tfhe32_blindrot : TfheBlindRotCore<pfhe_tfhe32_plan, pfhe::u32> {};
 
+// The multi-bit blind rotation: the mask is consumed grouping_factor elements at a time against 2^g keys per group.  Owns,
+// in the per-group form, the digit spectra and accumulators of `chunk` ciphertexts and the Hermitian parts of one group's
+// 2^g keys; nothing in the whole-loop form.  All allocated at creation.
+template <class W>
+struct TfheMultiBitCore {
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
+    pfhe::PlanGuard guard;          // one holder at a time and cross-stream ordering of successive calls, as the plan
+    pfhe::u32 k = 1, log_basis = 0, ell = 0, drop_bits = 0, g = 1;
+    bool whole_loop = false;
+    size_t chunk = 1, glwe = 0, key_len = 0, scratch = 0;
+    // per-group form only: chunk x (k+1) x ell x N/2, chunk x (k+1) x N/2 and 2^g x (k+1) x ell x (k+1) x N/2 complex f64
+    double2 *spec = nullptr, *acc = nullptr, *keyh = nullptr;
+    ~TfheMultiBitCore() {
+        if (!fft) return;
+        pfhe::DeviceGuard dg(fft->device);
+        for (double2 *b : {spec, acc, keyh})
+            if (b) (void)pfhe::counted_free(b);
+    }
+};
+struct pfhe_tfhe_mbrot : TfheMultiBitCore<pfhe::u64> {};
+struct pfhe_tfhe32_mbrot : TfheMultiBitCore<pfhe::u32> {};
+
 namespace pfhe {
 
 // ApproxSignedBasis::new (basis.rs:47-177) with modulus None: its assert!s become PFHE_ERR_BAD_ARGUMENT (log_basis = BITS
@@ -92,5 +114,19 @@ int tfhe_blindrot_rotate_handle(pfhe_tfhe_blindrot *h, u64 *acc, size_t len_acc,
                                 const uint32_t *exps, size_t len_exps, hipStream_t s);
 int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
                                 const uint32_t *exps, size_t len_exps, hipStream_t s);
+
+
+// The multi-bit rotation's create and device call (pfhe_fft.hip), as pfhe_tfhe{,32}_mbrot_create / _rotate_dev run them;
+// tfhe_mbrot_check_args is what the create decides before it touches the device (bits: 32 or 64).
+int tfhe_mbrot_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                          size_t grouping_factor);
+int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                             size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out);
+int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                             size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out);
+int tfhe_mbrot_rotate_handle(pfhe_tfhe_mbrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                             const uint32_t *exps, size_t len_exps, hipStream_t s);
+int tfhe_mbrot_rotate_handle(pfhe_tfhe32_mbrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                             const uint32_t *exps, size_t len_exps, hipStream_t s);
 
 }  // namespace pfhe

@@ -268,6 +268,86 @@ def tfhe_blind_rotate_dev(acc, bsk, exps, ctx: TfheBlindRotateContext, stream=No
     check(getattr(lib(), ctx._pre + "rotate_dev")(ctx._h, pa, na, pk, nk, pe, ne, _stream(stream)))
 
 
+class TfheMultiBitBlindRotateContext:
+    """Handle of the multi-bit blind rotation (include/pfhe.h, pfhe_tfhe{,32}_mbrot_*): the mask is consumed
+    `grouping_factor` (1..4) elements at a time; for every group t and ciphertext e,
+    ACC_e = external_product_to(ACC_e, sum_j X^{r_j} * BSK[t][j]) with r_j the subset sum of the group's exponents at the set
+    bits of j.  Assumes binary LWE keys: key [t][j] encrypts the indicator that the key bits of group t equal pattern j.
+    Owns the scratch of its form for `chunk` ciphertexts (0 = the default); one holder at a time (Busy for a second
+    thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, grouping_factor: int, glwe_dimension: int = 1,
+                 chunk: int = 0):
+        self._w = "" if basis.bits == 64 else "32"
+        self._pre = "pfhe_tfhe" + self._w + "_mbrot_"
+        h = C.c_void_p()
+        check(getattr(lib(), self._pre + "create")(fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(),
+                                                   grouping_factor, chunk, C.byref(h)))
+        self._h = h
+        self.fft, self.basis, self.glwe_dimension, self.grouping_factor = fft, basis, glwe_dimension, grouping_factor
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            getattr(lib(), self._pre + "destroy")(h)
+            self._h = None
+
+    def dtype(self):
+        return np.uint64 if self.basis.bits == 64 else np.uint32
+
+    def scratch_bytes(self) -> int:
+        return int(getattr(lib(), self._pre + "scratch_bytes")(self._h))
+
+    def in_use(self) -> bool:
+        return bool(getattr(lib(), self._pre + "in_use")(self._h))
+
+    def glwe_len(self) -> int:
+        return (self.glwe_dimension + 1) * self.fft.poly_length()
+
+    def key_len(self) -> int:
+        """complex values of one Fourier GGSW key"""
+        return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
+
+    def group_len(self) -> int:
+        """complex values of the 2^g keys of one group"""
+        return self.key_len() << self.grouping_factor
+
+
+def tfhe_multibit_blind_rotate(acc: np.ndarray, bsk: np.ndarray, exps: np.ndarray, ctx: TfheMultiBitBlindRotateContext) -> None:
+    """Multi-bit blind rotation on host arrays, acc updated in place.  acc: batch GLWE ciphertexts of the context's width;
+    bsk: groups x 2^g Fourier GGSW keys end to end; exps: uint32, batch x groups*g, ciphertext-major, every exponent below
+    2N."""
+    pa, na, wa = _host_words(acc)
+    pk, nk = _host_fourier(bsk)
+    if wa != ctx._w:
+        raise TypeError("accumulator words must match the basis width")
+    if not isinstance(exps, np.ndarray) or exps.dtype != np.uint32 or not exps.flags.c_contiguous:
+        raise TypeError("expected a C-contiguous numpy uint32 array of exponents")
+    check(getattr(lib(), ctx._pre + "rotate")(ctx._h, pa, na, pk, nk, exps.ctypes.data_as(C.c_void_p), exps.size))
+
+
+def tfhe_multibit_blind_rotate_dev(acc, bsk, exps, ctx: TfheMultiBitBlindRotateContext, stream=None) -> None:
+    """the device form, asynchronous; every exponent is taken modulo 2N on the device"""
+    pa, na, wa = _dev_words(acc)
+    pk, nk = _dev_fourier(bsk)
+    pe, ne = _dev_exps(exps)
+    if wa != ctx._w:
+        raise TypeError("accumulator words must match the basis width")
+    check(getattr(lib(), ctx._pre + "rotate_dev")(ctx._h, pa, na, pk, nk, pe, ne, _stream(stream)))
+
+
+def tfhe_multibit_combine_key_dev(keys, exps, out, fft: FullComplex64FftTable, decompose_length: int, grouping_factor: int,
+                                  glwe_dimension: int = 1, stream=None) -> None:
+    """The combined key of one ciphertext and one group as a key in the reference's layout: keys the group's 2^g Fourier
+    GGSW keys, exps its g exponents, out one key that tfhe_external_product_to_dev takes; the rotation equals this call
+    followed by the product, word for word."""
+    pk, nk = _dev_fourier(keys)
+    pe, ne = _dev_exps(exps)
+    po, no = _dev_fourier(out)
+    check(lib().pfhe_tfhe_mb_combine_key_dev(fft._h, glwe_dimension, decompose_length, grouping_factor, pk, nk, pe, ne, po, no,
+                                             _stream(stream)))
+
+
 # ---- the programmable bootstrap around the rotation (include/pfhe.h: modswitch, sample_extract, keyswitch, bootstrap) ----
 
 def _dev_index(t, device) -> int:
@@ -345,22 +425,26 @@ def lwe_keyswitch_dev(lwe_in, ksk, lwe_out, in_dimension: int, out_dimension: in
 
 class TfheBootstrapContext:
     """Handle of the batched programmable bootstrap (include/pfhe.h, pfhe_tfhe{,32}_bootstrap_*): modulus switch,
-    ACC = X^{-b~} * TV, the blind rotation over lwe_dimension steps, sample extraction at index 0 and, when ks_basis is
+    ACC = X^{-b~} * TV, the blind rotation over lwe_dimension steps (grouping_factor above 1: the multi-bit rotation over
+    lwe_dimension / grouping_factor groups, on the multi-bit key), sample extraction at index 0 and, when ks_basis is
     given, the key switch back to lwe_dimension.  Owns a blind-rotation handle and every buffer between the stages for
     `chunk` ciphertexts (0 = the default); one holder at a time (Busy for a second thread)."""
 
     def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int = 1,
-                 ks_basis: ApproxSignedBasis | None = None, chunk: int = 0):
+                 ks_basis: ApproxSignedBasis | None = None, chunk: int = 0, grouping_factor: int = 1):
         self._w = "" if basis.bits == 64 else "32"
         self._pre = "pfhe_tfhe" + self._w + "_bootstrap"
         if ks_basis is not None and ks_basis.bits != basis.bits:
             raise TypeError("both bases must have the width of the torus words")
         h = C.c_void_p()
-        check(getattr(lib(), self._pre + "_create")(
-            fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(), lwe_dimension,
-            ks_basis.log_basis() if ks_basis else 0, ks_basis.decompose_length() if ks_basis else 0,
-            1 if ks_basis else 0, chunk, C.byref(h)))
+        args = (fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(), lwe_dimension,
+                ks_basis.log_basis() if ks_basis else 0, ks_basis.decompose_length() if ks_basis else 0, 1 if ks_basis else 0)
+        if grouping_factor == 1:
+            check(getattr(lib(), self._pre + "_create")(*args, chunk, C.byref(h)))
+        else:   # the multi-bit rotation: bsk is (lwe_dimension / g) * 2^g keys
+            check(getattr(lib(), self._pre + "_create_multibit")(*args, grouping_factor, chunk, C.byref(h)))
         self._h = h
+        self.grouping_factor = grouping_factor
         self.fft, self.basis, self.ks_basis = fft, basis, ks_basis
         self.glwe_dimension, self.lwe_dimension = glwe_dimension, lwe_dimension
 
@@ -385,6 +469,11 @@ class TfheBootstrapContext:
     def key_len(self) -> int:
         """complex values of one Fourier GGSW key (one step of the rotation)"""
         return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
+
+    def bsk_len(self) -> int:
+        """complex values of the whole bootstrapping key: lwe_dimension keys, or (lwe_dimension / g) * 2^g multi-bit keys"""
+        g = self.grouping_factor
+        return (self.lwe_dimension if g == 1 else (self.lwe_dimension // g) << g) * self.key_len()
 
     def extracted_dimension(self) -> int:
         return self.glwe_dimension * self.fft.poly_length()
