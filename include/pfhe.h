@@ -1123,6 +1123,79 @@ int pfhe_tfhe32_bootstrap(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_i
                           const uint32_t *tv, size_t len_tv, const uint32_t *ksk, size_t len_ksk, uint32_t *lwe_out,
                           size_t len_out);
 
+/* ---- key generation, encryption and phase for the bootstrap above (u64: no suffix, u32: 32) ----
+ * NO RANDOM NUMBER IS DRAWN HERE.  Every call is deterministic integer arithmetic modulo 2^BITS on buffers the caller has
+ * filled: mask slots hold the uniform words, body slots hold noise + message.  Keys are arrays of torus words, any words
+ * (0/1 for a binary key, all-ones for -1, anything else).  No atomics; a call only queues work on `stream` (no allocation,
+ * no host synchronisation) and can be captured into a HIP graph.  The body calls ACCUMULATE into the body slot: a call is
+ * repeatable only in that sense (a second call adds the product a second time; add followed by subtract restores the input).
+ * Statuses in the house order: argument checks before the device, PFHE_ERR_BAD_LENGTH for lengths that do not divide, then
+ * zero ciphertexts as a no-op, then PFHE_ERR_BAD_ARGUMENT for a null pointer; a key must not overlap what is written.
+ *
+ * LWE body — Lwe::generate_random_zero_sample (primus_lattice/src/lwe/single_message.rs:94-125) without its sampling: for
+ * every ciphertext e of the batch (len_lwe = batch*(dimension+1), len_key = dimension, 1 <= dimension <= 2^31-2),
+ * b_e <- b_e + <a_e, key>, or b_e <- b_e - <a_e, key> when `subtract` is non-zero.  Adding turns (uniform mask, noise +
+ * message) into an encryption; subtracting writes the phase b - <a,s> into the body slot. */
+int pfhe_tfhe_lwe_body_mac_dev(int device, uint64_t *lwe_dev, size_t len_lwe, size_t dimension, const uint64_t *key_dev,
+                               size_t len_key, int subtract, void *stream);
+int pfhe_tfhe_lwe_body_mac(int device, uint64_t *lwe, size_t len_lwe, size_t dimension, const uint64_t *key, size_t len_key,
+                           int subtract);
+int pfhe_tfhe32_lwe_body_mac_dev(int device, uint32_t *lwe_dev, size_t len_lwe, size_t dimension, const uint32_t *key_dev,
+                                 size_t len_key, int subtract, void *stream);
+int pfhe_tfhe32_lwe_body_mac(int device, uint32_t *lwe, size_t len_lwe, size_t dimension, const uint32_t *key, size_t len_key,
+                             int subtract);
+/* GLWE body — Rlwe::generate_random_zero_sample (primus_lattice/src/rlwe/coeff.rs:92-121) without its sampling, for
+ * glwe_dimension k in 1..64 (PFHE_ERR_BAD_ARGUMENT otherwise): for every ciphertext (A_0..A_{k-1}, B) of the batch
+ * (len_glwe = batch*(k+1)*N), B <- B + sum_j A_j * z_j modulo X^N + 1, exact, or B <- B - ... with `subtract`; key is the k
+ * polynomials z_j end to end (len_key = k*N), the layout whose flattening is the key of pfhe_tfhe*_sample_extract's output. */
+int pfhe_tfhe_glwe_body_mac_dev(const pfhe_fft *fft, size_t glwe_dimension, uint64_t *glwe_dev, size_t len_glwe,
+                                const uint64_t *key_dev, size_t len_key, int subtract, void *stream);
+int pfhe_tfhe_glwe_body_mac(const pfhe_fft *fft, size_t glwe_dimension, uint64_t *glwe, size_t len_glwe, const uint64_t *key,
+                            size_t len_key, int subtract);
+int pfhe_tfhe32_glwe_body_mac_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t *glwe_dev, size_t len_glwe,
+                                  const uint32_t *key_dev, size_t len_key, int subtract, void *stream);
+int pfhe_tfhe32_glwe_body_mac(const pfhe_fft *fft, size_t glwe_dimension, uint32_t *glwe, size_t len_glwe, const uint32_t *key,
+                              size_t len_key, int subtract);
+/* The gadget term of a torus-form GGSW — no reference counterpart (the reference's GGSW generation samples inside): for a
+ * batch of GGSWs of (k+1) x ell x (k+1) x N words each (rows (r, l), levels least significant first) and one message word per
+ * GGSW (len_messages = count), m * 2^(drop_bits + l*log_basis) is added to coefficient 0 of component r of row (r, l).
+ * pfhe_tfhe_plan_create's checks run first, in its order (the basis's assert!s, PFHE_ERR_UNSUPPORTED for k > 64, the table),
+ * then PFHE_ERR_BAD_ARGUMENT for k = 0. */
+int pfhe_tfhe_ggsw_add_gadget_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                  uint64_t *ggsw_dev, size_t len_ggsw, const uint64_t *messages_dev, size_t len_messages,
+                                  void *stream);
+int pfhe_tfhe32_ggsw_add_gadget_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                    uint32_t *ggsw_dev, size_t len_ggsw, const uint32_t *messages_dev, size_t len_messages,
+                                    void *stream);
+/* The bootstrapping key — no reference counterpart.  ggsw_torus arrives holding the randomness of `keys` GGSWs (masks uniform,
+ * bodies noise; len_ggsw = keys*(k+1)*ell*(k+1)*N words).  The call runs the GLWE body call (add) on all rows under glwe_key
+ * (k*N words), adds the gadget term of each key's message and runs pfhe_fft_forward_torus*_dev into bsk_out (len_bsk = len_ggsw
+ * complex values): on return ggsw_torus is the torus-form key and bsk_out its write_fourier_form, bit for bit.
+ *   grouping_factor 0      the layout pfhe_tfhe*_blindrot_rotate_dev / _bootstrap_dev take: keys = n, message of key i = s_i;
+ *   grouping_factor 1..4   the layout pfhe_tfhe*_mbrot_rotate_dev takes: keys = (n/g)*2^g, message of key [t][j] =
+ *                          prod_b (bit b of j ? s_{t*g+b} : 1 - s_{t*g+b}) in wrapping words, formed on the device;
+ * s = lwe_key (n = lwe_dimension words).  After the gadget call's checks: PFHE_ERR_BAD_ARGUMENT for grouping_factor > 4, for n
+ * outside 1..2^31-2 and for n % g != 0; then the lengths; then null pointers, ggsw_torus or bsk_out not aligned to 16 bytes,
+ * and outputs that overlap each other or a key. */
+int pfhe_tfhe_bsk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                               size_t grouping_factor, const uint64_t *lwe_key_dev, size_t lwe_dimension,
+                               const uint64_t *glwe_key_dev, size_t len_glwe_key, uint64_t *ggsw_torus_dev, size_t len_ggsw,
+                               double *bsk_out_dev, size_t len_bsk, void *stream);
+int pfhe_tfhe32_bsk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                 size_t grouping_factor, const uint32_t *lwe_key_dev, size_t lwe_dimension,
+                                 const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t *ggsw_torus_dev, size_t len_ggsw,
+                                 double *bsk_out_dev, size_t len_bsk, void *stream);
+/* The key-switch key in the layout pfhe_tfhe*_keyswitch_dev takes — no reference counterpart.  ksk arrives holding the
+ * randomness of in_dimension x ell rows of out_dimension + 1 words (masks uniform, bodies noise); row (i, j) becomes
+ * b <- b + <a, key_out> + key_in[i] * 2^(drop_bits + j*log_basis).  key_in has in_dimension words, key_out out_dimension.
+ * ApproxSignedBasis::new's assert!s first, then the dimensions (1..2^31-2), then len_ksk = in_dimension*ell*(out_dimension+1). */
+int pfhe_tfhe_ksk_generate_dev(int device, const uint64_t *key_in_dev, size_t in_dimension, const uint64_t *key_out_dev,
+                               size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *ksk_dev,
+                               size_t len_ksk, void *stream);
+int pfhe_tfhe32_ksk_generate_dev(int device, const uint32_t *key_in_dev, size_t in_dimension, const uint32_t *key_out_dev,
+                                 size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *ksk_dev,
+                                 size_t len_ksk, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

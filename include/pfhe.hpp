@@ -926,4 +926,85 @@ class TfheBootstrap32 {
     pfhe_tfhe32_bootstrap_handle *h_ = nullptr;
 };
 
+// Key generation, encryption and phase (pfhe_tfhe{,32}_lwe_body_mac*, _glwe_body_mac*, _ggsw_add_gadget_dev, _bsk_generate_dev,
+// _ksk_generate_dev).  No random number is drawn: the buffers arrive holding the caller's randomness (masks uniform, bodies
+// noise + message).  body_mac adds <a,s> (A * z) into the body slot, or subtracts it (the phase); the gadget call adds
+// m * 2^(drop_bits + l*log_basis); the two generators write the keys TfheBootstrap takes (grouping_factor 0: the classic
+// layout, 1..4: the multi-bit one).  uint64_t overloads: the u64 torus; uint32_t: the u32 torus.
+inline void lwe_body_mac(int device, uint64_t *lwe, size_t len_lwe, size_t dimension, const uint64_t *key, size_t len_key,
+                         bool subtract) {
+    check(pfhe_tfhe_lwe_body_mac(device, lwe, len_lwe, dimension, key, len_key, subtract ? 1 : 0));
+}
+inline void lwe_body_mac_dev(int device, uint64_t *lwe_dev, size_t len_lwe, size_t dimension, const uint64_t *key_dev,
+                             size_t len_key, bool subtract, void *stream = nullptr) {
+    check(pfhe_tfhe_lwe_body_mac_dev(device, lwe_dev, len_lwe, dimension, key_dev, len_key, subtract ? 1 : 0, stream));
+}
+inline void glwe_body_mac(const FullComplex64FftTable &fft, size_t glwe_dimension, uint64_t *glwe, size_t len_glwe,
+                          const uint64_t *key, size_t len_key, bool subtract) {
+    check(pfhe_tfhe_glwe_body_mac(fft.handle(), glwe_dimension, glwe, len_glwe, key, len_key, subtract ? 1 : 0));
+}
+inline void glwe_body_mac_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, uint64_t *glwe_dev, size_t len_glwe,
+                              const uint64_t *key_dev, size_t len_key, bool subtract, void *stream = nullptr) {
+    check(pfhe_tfhe_glwe_body_mac_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, key_dev, len_key, subtract ? 1 : 0,
+          stream));
+}
+inline void ggsw_add_gadget_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis,
+                                size_t decompose_length, uint64_t *ggsw_dev, size_t len_ggsw, const uint64_t *messages_dev,
+                                size_t len_messages, void *stream = nullptr) {
+    check(pfhe_tfhe_ggsw_add_gadget_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, ggsw_dev, len_ggsw,
+          messages_dev, len_messages, stream));
+}
+inline void tfhe_generate_bsk_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis,
+                                  size_t decompose_length, size_t grouping_factor, const uint64_t *lwe_key_dev,
+                                  size_t lwe_dimension, const uint64_t *glwe_key_dev, size_t len_glwe_key,
+                                  uint64_t *ggsw_torus_dev, size_t len_ggsw, double *bsk_out_dev, size_t len_bsk,
+                                  void *stream = nullptr) {
+    check(pfhe_tfhe_bsk_generate_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor, lwe_key_dev,
+          lwe_dimension, glwe_key_dev, len_glwe_key, ggsw_torus_dev, len_ggsw, bsk_out_dev, len_bsk, stream));
+}
+inline void tfhe_generate_ksk_dev(int device, const uint64_t *key_in_dev, size_t in_dimension, const uint64_t *key_out_dev,
+                                  size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *ksk_dev,
+                                  size_t len_ksk, void *stream = nullptr) {
+    check(pfhe_tfhe_ksk_generate_dev(device, key_in_dev, in_dimension, key_out_dev, out_dimension, log_basis, decompose_length,
+          ksk_dev, len_ksk, stream));
+}
+
+inline void lwe_body_mac(int device, uint32_t *lwe, size_t len_lwe, size_t dimension, const uint32_t *key, size_t len_key,
+                         bool subtract) {
+    check(pfhe_tfhe32_lwe_body_mac(device, lwe, len_lwe, dimension, key, len_key, subtract ? 1 : 0));
+}
+inline void lwe_body_mac_dev(int device, uint32_t *lwe_dev, size_t len_lwe, size_t dimension, const uint32_t *key_dev,
+                             size_t len_key, bool subtract, void *stream = nullptr) {
+    check(pfhe_tfhe32_lwe_body_mac_dev(device, lwe_dev, len_lwe, dimension, key_dev, len_key, subtract ? 1 : 0, stream));
+}
+inline void glwe_body_mac(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t *glwe, size_t len_glwe,
+                          const uint32_t *key, size_t len_key, bool subtract) {
+    check(pfhe_tfhe32_glwe_body_mac(fft.handle(), glwe_dimension, glwe, len_glwe, key, len_key, subtract ? 1 : 0));
+}
+inline void glwe_body_mac_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t *glwe_dev, size_t len_glwe,
+                              const uint32_t *key_dev, size_t len_key, bool subtract, void *stream = nullptr) {
+    check(pfhe_tfhe32_glwe_body_mac_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, key_dev, len_key, subtract ? 1 : 0,
+          stream));
+}
+inline void ggsw_add_gadget_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis,
+                                size_t decompose_length, uint32_t *ggsw_dev, size_t len_ggsw, const uint32_t *messages_dev,
+                                size_t len_messages, void *stream = nullptr) {
+    check(pfhe_tfhe32_ggsw_add_gadget_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, ggsw_dev, len_ggsw,
+          messages_dev, len_messages, stream));
+}
+inline void tfhe_generate_bsk_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis,
+                                  size_t decompose_length, size_t grouping_factor, const uint32_t *lwe_key_dev,
+                                  size_t lwe_dimension, const uint32_t *glwe_key_dev, size_t len_glwe_key,
+                                  uint32_t *ggsw_torus_dev, size_t len_ggsw, double *bsk_out_dev, size_t len_bsk,
+                                  void *stream = nullptr) {
+    check(pfhe_tfhe32_bsk_generate_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor, lwe_key_dev,
+          lwe_dimension, glwe_key_dev, len_glwe_key, ggsw_torus_dev, len_ggsw, bsk_out_dev, len_bsk, stream));
+}
+inline void tfhe_generate_ksk_dev(int device, const uint32_t *key_in_dev, size_t in_dimension, const uint32_t *key_out_dev,
+                                  size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *ksk_dev,
+                                  size_t len_ksk, void *stream = nullptr) {
+    check(pfhe_tfhe32_ksk_generate_dev(device, key_in_dev, in_dimension, key_out_dev, out_dimension, log_basis, decompose_length,
+          ksk_dev, len_ksk, stream));
+}
+
 }  // namespace pfhe

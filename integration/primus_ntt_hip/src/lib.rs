@@ -911,3 +911,101 @@ pub unsafe fn tfhe32_keyswitch_dev(device: c_int, lwe_in_dev: *const u32, len_in
         e => Err(e),
     }
 }
+
+/// Key generation, encryption and phase for the bootstrap on the u64 torus.  No random number is drawn: the buffers arrive
+/// holding the caller's randomness (masks uniform, bodies noise + message).  The body calls are
+/// `Lwe::generate_random_zero_sample` (lwe/single_message.rs:94-125) and `Rlwe::generate_random_zero_sample`
+/// (rlwe/coeff.rs:92-121) without their sampling, with `subtract` the phase; the gadget term and the two key generators
+/// have no reference counterpart.  `grouping_factor` 0: the classic key layout, 1..4: the multi-bit one.
+pub unsafe fn tfhe_lwe_body_mac_dev(device: c_int, lwe_dev: *mut u64, len_lwe: usize, dimension: usize, key_dev: *const u64,
+                                  len_key: usize, subtract: bool, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_lwe_body_mac_dev(device, lwe_dev, len_lwe, dimension, key_dev, len_key, subtract as c_int, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe_glwe_body_mac_dev(fft: &HipFftTable, glwe_dimension: usize, glwe_dev: *mut u64, len_glwe: usize,
+                                   key_dev: *const u64, len_key: usize, subtract: bool, stream: *mut core::ffi::c_void)
+                                   -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_glwe_body_mac_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, key_dev, len_key,
+                                                 subtract as c_int, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe_ggsw_add_gadget_dev(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize,
+                                     ggsw_dev: *mut u64, len_ggsw: usize, messages_dev: *const u64, len_messages: usize,
+                                     stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_ggsw_add_gadget_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, ggsw_dev, len_ggsw,
+                                                   messages_dev, len_messages, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe_bsk_generate_dev(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize,
+                                  grouping_factor: usize, lwe_key_dev: *const u64, lwe_dimension: usize,
+                                  glwe_key_dev: *const u64, len_glwe_key: usize, ggsw_torus_dev: *mut u64, len_ggsw: usize,
+                                  bsk_out_dev: *mut f64, len_bsk: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_bsk_generate_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor,
+                                                lwe_key_dev, lwe_dimension, glwe_key_dev, len_glwe_key, ggsw_torus_dev, len_ggsw,
+                                                bsk_out_dev, len_bsk, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe_ksk_generate_dev(device: c_int, key_in_dev: *const u64, in_dimension: usize, key_out_dev: *const u64,
+                                  out_dimension: usize, log_basis: u32, decompose_length: usize, ksk_dev: *mut u64,
+                                  len_ksk: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe_ksk_generate_dev(device, key_in_dev, in_dimension, key_out_dev, out_dimension, log_basis,
+                                                decompose_length, ksk_dev, len_ksk, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+
+/// The same calls on the u32 torus.
+pub unsafe fn tfhe32_lwe_body_mac_dev(device: c_int, lwe_dev: *mut u32, len_lwe: usize, dimension: usize, key_dev: *const u32,
+                                  len_key: usize, subtract: bool, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_lwe_body_mac_dev(device, lwe_dev, len_lwe, dimension, key_dev, len_key, subtract as c_int, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe32_glwe_body_mac_dev(fft: &HipFftTable, glwe_dimension: usize, glwe_dev: *mut u32, len_glwe: usize,
+                                   key_dev: *const u32, len_key: usize, subtract: bool, stream: *mut core::ffi::c_void)
+                                   -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_glwe_body_mac_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, key_dev, len_key,
+                                                 subtract as c_int, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe32_ggsw_add_gadget_dev(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize,
+                                     ggsw_dev: *mut u32, len_ggsw: usize, messages_dev: *const u32, len_messages: usize,
+                                     stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_ggsw_add_gadget_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, ggsw_dev, len_ggsw,
+                                                   messages_dev, len_messages, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe32_bsk_generate_dev(fft: &HipFftTable, glwe_dimension: usize, log_basis: u32, decompose_length: usize,
+                                  grouping_factor: usize, lwe_key_dev: *const u32, lwe_dimension: usize,
+                                  glwe_key_dev: *const u32, len_glwe_key: usize, ggsw_torus_dev: *mut u32, len_ggsw: usize,
+                                  bsk_out_dev: *mut f64, len_bsk: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_bsk_generate_dev(fft.handle(), glwe_dimension, log_basis, decompose_length, grouping_factor,
+                                                lwe_key_dev, lwe_dimension, glwe_key_dev, len_glwe_key, ggsw_torus_dev, len_ggsw,
+                                                bsk_out_dev, len_bsk, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}
+pub unsafe fn tfhe32_ksk_generate_dev(device: c_int, key_in_dev: *const u32, in_dimension: usize, key_out_dev: *const u32,
+                                  out_dimension: usize, log_basis: u32, decompose_length: usize, ksk_dev: *mut u32,
+                                  len_ksk: usize, stream: *mut core::ffi::c_void) -> Result<(), c_int> {
+    match unsafe { ffi::pfhe_tfhe32_ksk_generate_dev(device, key_in_dev, in_dimension, key_out_dev, out_dimension, log_basis,
+                                                decompose_length, ksk_dev, len_ksk, stream) } {
+        ffi::PFHE_OK => Ok(()),
+        e => Err(e),
+    }
+}

@@ -17,7 +17,9 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    lwe_keyswitch, lwe_keyswitch_dev, lwe_modulus_switch_dev, tfhe_blind_rotate, tfhe_blind_rotate_dev,
                    tfhe_bootstrap, tfhe_bootstrap_dev, tfhe_external_product_to, tfhe_external_product_to_dev,
                    tfhe_multibit_blind_rotate, tfhe_multibit_blind_rotate_dev, tfhe_multibit_combine_key_dev,
-                   write_fourier_form)
+                   write_fourier_form, TfheKeyShape, ggsw_add_gadget_dev, glwe_encrypt, glwe_encrypt_dev, glwe_phase,
+                   glwe_phase_dev, lwe_encrypt, lwe_encrypt_dev, lwe_phase, lwe_phase_dev, tfhe_generate_bsk_dev,
+                   tfhe_generate_ksk_dev, torus_noise, torus_uniform)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -31,4 +33,6 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "tfhe_blind_rotate_dev", "lwe_modulus_switch_dev", "glwe_sample_extract", "glwe_sample_extract_dev",
            "lwe_keyswitch", "lwe_keyswitch_dev", "TfheBootstrapContext", "tfhe_bootstrap", "tfhe_bootstrap_dev",
            "TfheMultiBitBlindRotateContext", "tfhe_multibit_blind_rotate", "tfhe_multibit_blind_rotate_dev",
-           "tfhe_multibit_combine_key_dev", "build", "lib", "library_path", "status_string"]
+           "tfhe_multibit_combine_key_dev", "lwe_encrypt", "lwe_encrypt_dev", "lwe_phase", "lwe_phase_dev", "glwe_encrypt",
+           "glwe_encrypt_dev", "glwe_phase", "glwe_phase_dev", "ggsw_add_gadget_dev", "TfheKeyShape", "tfhe_generate_bsk_dev",
+           "tfhe_generate_ksk_dev", "torus_uniform", "torus_noise", "build", "lib", "library_path", "status_string"]

@@ -216,6 +216,14 @@ def _declare(lib: C.CDLL) -> None:
         sig(bs + "_scratch_bytes", sz, vp)
         sig(bs + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp, sz, vp)
         sig(bs, ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp, sz)
+        # key generation, encryption and phase: the body calls, the gadget term and the two keys of the bootstrap
+        sig(tp + "lwe_body_mac_dev", ci, ci, vp, sz, sz, vp, sz, ci, vp)
+        sig(tp + "lwe_body_mac", ci, ci, vp, sz, sz, vp, sz, ci)
+        sig(tp + "glwe_body_mac_dev", ci, vp, sz, vp, sz, vp, sz, ci, vp)
+        sig(tp + "glwe_body_mac", ci, vp, sz, vp, sz, vp, sz, ci)
+        sig(tp + "ggsw_add_gadget_dev", ci, vp, sz, u32, sz, vp, sz, vp, sz, vp)
+        sig(tp + "bsk_generate_dev", ci, vp, sz, u32, sz, sz, vp, sz, vp, sz, vp, sz, f64p, sz, vp)
+        sig(tp + "ksk_generate_dev", ci, ci, vp, sz, vp, sz, u32, sz, vp, sz, vp)
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)

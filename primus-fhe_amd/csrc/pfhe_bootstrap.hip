@@ -192,11 +192,6 @@ __global__ __launch_bounds__(kThreads) void tfhe_keyswitch_kernel(const W *__res
 
 // ---------------- launches (arguments already checked) ----------------
 
-inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 inline int flat_grid(u64 total, u32 &grid) {
     const u64 g = (total + kThreads - 1) / kThreads;
     if (g > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;

@@ -1000,6 +1000,12 @@ int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_ac
     return ::tfhe_blindrot_dev<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
 }
 
+int tfhe_plan_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         u32 &ell, u32 &drop) {
+    return bits == 64 ? ::plan_check<u64>(fft, glwe_dimension, log_basis, decompose_length, ell, drop)
+                      : ::plan_check<u32>(fft, glwe_dimension, log_basis, decompose_length, ell, drop);
+}
+
 int tfhe_mbrot_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                           size_t grouping_factor) {
     u32 ell = 0, drop = 0;

@@ -1,6 +1,6 @@
 // pfhe_tfhe_handles.hpp — what the torus-side handles own (pfhe_fft, the TFHE product plan, the two blind-rotation handles) and
 // the basis check they share.  Seen by pfhe_fft.hip, which implements them, and by pfhe_bootstrap.hip, whose bootstrap
-// handle is built around a blind-rotation handle.  Host only.
+// handle is built around a blind-rotation handle, and by pfhe_keygen.hip, which writes the keys they consume.  Host only.
 #pragma once
 
 #include "pfhe_capi_internal.hpp"
@@ -115,6 +115,16 @@ int tfhe_blindrot_rotate_handle(pfhe_tfhe_blindrot *h, u64 *acc, size_t len_acc,
 int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
                                 const uint32_t *exps, size_t len_exps, hipStream_t s);
 
+// true when the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
+inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// What pfhe_tfhe{,32}_plan_create decides before it touches the device, in its order (bits: 32 or 64): the basis's assert!s,
+// glwe_dimension above 64, the table; for pfhe_keygen.hip, whose GGSW calls start with the same checks.
+int tfhe_plan_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         u32 &ell, u32 &drop);
 
 // The multi-bit rotation's create and device call (pfhe_fft.hip), as pfhe_tfhe{,32}_mbrot_create / _rotate_dev run them;
 // tfhe_mbrot_check_args is what the create decides before it touches the device (bits: 32 or 64).

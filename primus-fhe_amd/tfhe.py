@@ -524,3 +524,195 @@ def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) 
         fft.forward_torus_slice(coeff, fourier)
     else:
         fft.forward_torus_dev(coeff, fourier, stream)
+
+
+# ---- key generation, encryption and phase (include/pfhe.h: lwe_body_mac, glwe_body_mac, ggsw_add_gadget, bsk / ksk) ----
+# No call below draws a random number: masks and noise are what the caller put into the buffers (torus_uniform and
+# torus_noise are two ways of doing that).
+
+def _lwe_body(lwe, key, subtract: int, device: int) -> None:
+    pl, nl, wl = _host_words(lwe)
+    pk, nk, wk = _host_words(key)
+    if wl != wk:
+        raise TypeError("ciphertexts and key must have the same word width")
+    check(getattr(lib(), "pfhe_tfhe" + wl + "_lwe_body_mac")(device, pl, nl, nk, pk, nk, subtract))
+
+
+def _lwe_body_dev(lwe, key, subtract: int, device, stream) -> None:
+    pl, nl, wl = _dev_words(lwe)
+    pk, nk, wk = _dev_words(key)
+    if wl != wk:
+        raise TypeError("ciphertexts and key must have the same word width")
+    check(getattr(lib(), "pfhe_tfhe" + wl + "_lwe_body_mac_dev")(_dev_index(lwe, device), pl, nl, nk, pk, nk, subtract,
+                                                               _stream(stream)))
+
+
+def lwe_encrypt(lwe: np.ndarray, key: np.ndarray, device: int = 0) -> None:
+    """Lwe::generate_random_zero_sample (lwe/single_message.rs:94-125) with the caller's randomness, on host arrays and in
+    place: lwe holds batch x (len(key)+1) words, masks uniform and body slots noise + message; b_e += <a_e, key>."""
+    _lwe_body(lwe, key, 0, device)
+
+
+def lwe_encrypt_dev(lwe, key, device=None, stream=None) -> None:
+    """the device form, asynchronous"""
+    _lwe_body_dev(lwe, key, 0, device, stream)
+
+
+def lwe_phase(lwe: np.ndarray, key: np.ndarray, device: int = 0) -> None:
+    """b_e -= <a_e, key> in place: every body slot becomes the phase b - <a,s> = noise + message"""
+    _lwe_body(lwe, key, 1, device)
+
+
+def lwe_phase_dev(lwe, key, device=None, stream=None) -> None:
+    """the device form, asynchronous"""
+    _lwe_body_dev(lwe, key, 1, device, stream)
+
+
+def _glwe_body(glwe, key, fft, glwe_dimension: int, subtract: int) -> None:
+    pg, ng, wg = _host_words(glwe)
+    pk, nk, wk = _host_words(key)
+    if wg != wk:
+        raise TypeError("ciphertexts and key must have the same word width")
+    check(getattr(lib(), "pfhe_tfhe" + wg + "_glwe_body_mac")(fft._h, glwe_dimension, pg, ng, pk, nk, subtract))
+
+
+def _glwe_body_dev(glwe, key, fft, glwe_dimension: int, subtract: int, stream) -> None:
+    pg, ng, wg = _dev_words(glwe)
+    pk, nk, wk = _dev_words(key)
+    if wg != wk:
+        raise TypeError("ciphertexts and key must have the same word width")
+    check(getattr(lib(), "pfhe_tfhe" + wg + "_glwe_body_mac_dev")(fft._h, glwe_dimension, pg, ng, pk, nk, subtract,
+                                                                _stream(stream)))
+
+
+def glwe_encrypt(glwe: np.ndarray, key: np.ndarray, fft: FullComplex64FftTable, glwe_dimension: int = 1) -> None:
+    """Rlwe::generate_random_zero_sample (rlwe/coeff.rs:92-121) with the caller's randomness, on host arrays and in place:
+    glwe holds batch x (k+1) x N words, mask polynomials uniform and body polynomials noise + message; key the k key
+    polynomials end to end; B_e += sum_j A_{e,j} * z_j modulo X^N + 1."""
+    _glwe_body(glwe, key, fft, glwe_dimension, 0)
+
+
+def glwe_encrypt_dev(glwe, key, fft: FullComplex64FftTable, glwe_dimension: int = 1, stream=None) -> None:
+    """the device form, asynchronous"""
+    _glwe_body_dev(glwe, key, fft, glwe_dimension, 0, stream)
+
+
+def glwe_phase(glwe: np.ndarray, key: np.ndarray, fft: FullComplex64FftTable, glwe_dimension: int = 1) -> None:
+    """B_e -= sum_j A_{e,j} * z_j in place: every body polynomial becomes the phase"""
+    _glwe_body(glwe, key, fft, glwe_dimension, 1)
+
+
+def glwe_phase_dev(glwe, key, fft: FullComplex64FftTable, glwe_dimension: int = 1, stream=None) -> None:
+    """the device form, asynchronous"""
+    _glwe_body_dev(glwe, key, fft, glwe_dimension, 1, stream)
+
+
+def ggsw_add_gadget_dev(ggsw, messages, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1,
+                        stream=None) -> None:
+    """Adds m * 2^(drop_bits + l*log_basis) to coefficient 0 of component r of row (r, l) of every torus-form GGSW of the
+    batch ((k+1) x ell x (k+1) x N words each), one message word per GGSW."""
+    pg, ng, wg = _dev_words(ggsw)
+    pm, nm, wm = _dev_words(messages)
+    if wg != wm:
+        raise TypeError("GGSWs and messages must have the same word width")
+    lb, ell = _basis_args(basis, wg)
+    check(getattr(lib(), "pfhe_tfhe" + wg + "_ggsw_add_gadget_dev")(fft._h, glwe_dimension, lb, ell, pg, ng, pm, nm,
+                                                                  _stream(stream)))
+
+
+class TfheKeyShape:
+    """The shape of a bootstrapping key without a handle: what tfhe_generate_bsk_dev reads from a TfheBootstrapContext.
+    grouping_factor 0 is the classic layout (lwe_dimension keys), 1..4 the multi-bit one ((lwe_dimension / g) * 2^g keys)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int = 1,
+                 grouping_factor: int = 0):
+        self.fft, self.basis, self.lwe_dimension = fft, basis, lwe_dimension
+        self.glwe_dimension, self.grouping_factor = glwe_dimension, grouping_factor
+
+    def keys(self) -> int:
+        g = self.grouping_factor
+        return (self.lwe_dimension // g) << g if g else self.lwe_dimension
+
+    def bsk_len(self) -> int:
+        """torus words of the whole key, and complex values of its Fourier form"""
+        rows = self.glwe_dimension + 1
+        return self.keys() * rows * self.basis.decompose_length() * rows * self.fft.poly_length()
+
+
+def _key_shape(ctx_or_shape) -> TfheKeyShape:
+    if isinstance(ctx_or_shape, TfheKeyShape):
+        return ctx_or_shape
+    c = ctx_or_shape    # a TfheBootstrapContext: grouping_factor 1 is its classic rotation
+    return TfheKeyShape(c.fft, c.basis, c.lwe_dimension, c.glwe_dimension, 0 if c.grouping_factor == 1 else c.grouping_factor)
+
+
+def tfhe_generate_bsk_dev(ctx_or_shape, lwe_key, glwe_key, rand, out=None, stream=None):
+    """The bootstrapping key a TfheBootstrapContext (or a TfheKeyShape) takes, generated on the device.  lwe_key: the n key
+    words; glwe_key: the k key polynomials end to end; rand: shape.bsk_len() torus words holding the randomness (masks
+    uniform, bodies noise), which becomes the torus-form key in place; out: as many complex128 values (allocated when
+    None), which becomes its Fourier form, bit for bit what write_fourier_form gives.  Returns out.  Asynchronous."""
+    import torch
+    sh = _key_shape(ctx_or_shape)
+    ps, ns, ws = _dev_words(lwe_key)
+    pz, nz, wz = _dev_words(glwe_key)
+    pr, nr, wr = _dev_words(rand)
+    if not ws == wz == wr:
+        raise TypeError("both keys and the randomness must have the same word width")
+    lb, ell = _basis_args(sh.basis, wr)
+    if out is None:
+        out = torch.empty(nr, dtype=torch.complex128, device=rand.device)
+    po, no = _dev_fourier(out)
+    check(getattr(lib(), "pfhe_tfhe" + wr + "_bsk_generate_dev")(sh.fft._h, sh.glwe_dimension, lb, ell, sh.grouping_factor, ps,
+                                                               ns, pz, nz, pr, nr, po, no, _stream(stream)))
+    return out
+
+
+def tfhe_generate_ksk_dev(key_in, key_out, basis: ApproxSignedBasis, rand, device=None, stream=None) -> None:
+    """The key-switch key lwe_keyswitch_dev takes, from key_in (len(key_in) words) to key_out, generated in place in rand:
+    len(key_in) x ell rows of len(key_out)+1 words holding the randomness (masks uniform, bodies noise); row (i, j) becomes
+    b += <a, key_out> + key_in[i] * 2^(drop_bits + j*log_basis).  Asynchronous."""
+    pi, ni, wi = _dev_words(key_in)
+    po, no, wo = _dev_words(key_out)
+    pr, nr, wr = _dev_words(rand)
+    if not wi == wo == wr:
+        raise TypeError("both keys and the randomness must have the same word width")
+    lb, ell = _basis_args(basis, wr)
+    check(getattr(lib(), "pfhe_tfhe" + wr + "_ksk_generate_dev")(_dev_index(rand, device), pi, ni, po, no, lb, ell, pr, nr,
+                                                               _stream(stream)))
+
+
+def _torus_dtype(bits: int):
+    import torch
+    if bits not in (32, 64):
+        raise PfheError(33, "bits must be 32 or 64")
+    return torch.int32 if bits == 32 else torch.int64
+
+
+def torus_uniform(size, bits: int, device="cuda", generator=None):
+    """`size` uniform torus words of `bits` bits as an int32 / int64 tensor (the words are the two's-complement bit
+    patterns).  NOT CRYPTOGRAPHIC: torch's generator is a statistical one (Philox / Mersenne twister), fit for tests and
+    measurements only; fill the buffers from a cryptographic generator for real keys and ciphertexts."""
+    import torch
+    half = 1 << (bits - 1)
+    dtype = _torus_dtype(bits)
+    if bits == 32:
+        return torch.randint(-half, half, (size,), dtype=torch.int64, device=device, generator=generator).to(dtype)
+    # randint's exclusive upper bound cannot be 2^63: two 32-bit halves instead
+    hi = torch.randint(-(1 << 31), 1 << 31, (size,), dtype=torch.int64, device=device, generator=generator)
+    lo = torch.randint(0, 1 << 32, (size,), dtype=torch.int64, device=device, generator=generator)
+    return (hi << 32) | lo
+
+
+def torus_noise(size, bits: int, device="cuda", std=None, bound=None, generator=None):
+    """`size` noise words as an int32 / int64 tensor: a rounded Gaussian of standard deviation `std` (in units of one torus
+    word, i.e. 2^-BITS of the torus), or integers uniform in [-bound, bound]; exactly one of the two.  NOT CRYPTOGRAPHIC:
+    torch's generator is a statistical one, and the Gaussian is rounded from float64, so its tail ends near 2^53."""
+    import torch
+    dtype = _torus_dtype(bits)
+    if (std is None) == (bound is None):
+        raise TypeError("give exactly one of std and bound")
+    if bound is not None:
+        return torch.randint(-int(bound), int(bound) + 1, (size,), dtype=torch.int64, device=device,
+                             generator=generator).to(dtype)
+    g = torch.empty(size, dtype=torch.float64, device=device).normal_(0.0, float(std), generator=generator)
+    return torch.round(g).to(torch.int64).to(dtype)
