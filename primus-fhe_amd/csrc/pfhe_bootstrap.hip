@@ -6,26 +6,23 @@
 //                      round(w 2N / 2^BITS) with ties up, computed without overflow.
 //   accumulator init   ACC_e = X^{neg_b[e]} TV, the rotation of pfhe_tfhe*_mul_monomial_each_to_dev with the test vector
 //                      read in place (one shared by the batch, or one per ciphertext).
-//   blind rotation     the classic or the multi-bit handle (pfhe_fft.hip), called as it is.
+//   blind rotation     the classic or the multi-bit handle (pfhe_fft.hip) behind TfheRotation, called as it is.
 //   sample extraction  Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial.
 //   key switch         out = (0, b) - sum_i sum_j d_{i,j} KSK[i][j], a sequence of Lwe::add_mul_scalar_assign
 //                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_step of
 //                      pfhe_fft_device.hpp, the product's own).
-// Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.
+// Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
+// host forms go through pfhe_tfhe_host.hpp; the key switch keeps its own 2-D grid.
 #include <algorithm>
 #include <cstdint>
 #include <memory>
 
-#include "pfhe_fft_device.hpp"
 #include "pfhe_tfhe_handles.hpp"
 
 using namespace pfhe;
 
 namespace pfhe {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr u32 kMaxLogN = 14;
 
 // ---------------- modulus switch ----------------
 
@@ -192,41 +189,19 @@ __global__ __launch_bounds__(kThreads) void tfhe_keyswitch_kernel(const W *__res
 
 // ---------------- launches (arguments already checked) ----------------
 
-inline int flat_grid(u64 total, u32 &grid) {
-    const u64 g = (total + kThreads - 1) / kThreads;
-    if (g > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
-    grid = (u32)g;
-    return PFHE_OK;
-}
-
 template <class W>
 int launch_modswitch(const W *lwe, u32 n, u32 log_n, u32 *exps, u32 *neg_b, u64 batch, hipStream_t s) {
-    u32 grid = 0;
-    const u64 total = batch * ((u64)n + 1);
-    PFHE_TRY(flat_grid(total, grid));
-    hipLaunchKernelGGL(tfhe_modswitch_kernel<W>, dim3(grid), dim3(kThreads), 0, s, lwe, exps, neg_b, n, log_n, total);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_flat(tfhe_modswitch_kernel<W>, batch * ((u64)n + 1), s, lwe, exps, neg_b, n, log_n);
 }
 
 template <class W>
 int launch_acc_init(const W *tv, u64 tv_stride, W *acc, const u32 *neg_b, u32 rows, u32 log_n, u64 batch, hipStream_t s) {
-    u32 grid = 0;
-    const u64 total = (batch * rows) << log_n;
-    PFHE_TRY(flat_grid(total, grid));
-    hipLaunchKernelGGL(tfhe_acc_init_kernel<W>, dim3(grid), dim3(kThreads), 0, s, tv, acc, neg_b, rows, log_n, tv_stride, total);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_flat(tfhe_acc_init_kernel<W>, (batch * rows) << log_n, s, tv, acc, neg_b, rows, log_n, tv_stride);
 }
 
 template <class W>
 int launch_sample_extract(const W *glwe, W *lwe, u32 k, u32 log_n, u32 h, u64 batch, hipStream_t s) {
-    u32 grid = 0;
-    const u64 total = batch * (((u64)k << log_n) + 1);
-    PFHE_TRY(flat_grid(total, grid));
-    hipLaunchKernelGGL(tfhe_sample_extract_kernel<W>, dim3(grid), dim3(kThreads), 0, s, glwe, lwe, k, log_n, h, total);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_flat(tfhe_sample_extract_kernel<W>, batch * (((u64)k << log_n) + 1), s, glwe, lwe, k, log_n, h);
 }
 
 template <class W>
@@ -234,9 +209,8 @@ int launch_keyswitch(const W *lwe_in, const W *ksk, W *lwe_out, KsShape sh, u64 
     const u64 gx = ((u64)sh.out_dim + 1 + kKsTileN - 1) / kKsTileN;
     for (u64 done = 0; done < batch;) {  // grid.y holds 65535 tiles
         const u64 cur = std::min<u64>(batch - done, (u64)65535 * kKsTileM);
-        hipLaunchKernelGGL(tfhe_keyswitch_kernel<W>, dim3((u32)gx, (u32)((cur + kKsTileM - 1) / kKsTileM)), dim3(kThreads), 0, s,
-                           lwe_in + done * ((u64)sh.in_dim + 1), ksk, lwe_out + done * ((u64)sh.out_dim + 1), sh, cur);
-        PFHE_HIP(hipGetLastError());
+        PFHE_TRY(launch_grid(tfhe_keyswitch_kernel<W>, dim3((u32)gx, (u32)((cur + kKsTileM - 1) / kKsTileM)), 0, s,
+                             lwe_in + done * ((u64)sh.in_dim + 1), ksk, lwe_out + done * ((u64)sh.out_dim + 1), sh, cur));
         done += cur;
     }
     return PFHE_OK;
@@ -308,16 +282,10 @@ int sample_extract_host(const pfhe_fft *f, size_t k, const W *glwe, size_t len_g
     PFHE_TRY(sample_extract_check<W>(f, k, len_glwe, index, len_lwe));
     if (len_glwe == 0) return PFHE_OK;
     if (!glwe || !lwe) return PFHE_ERR_BAD_ARGUMENT;
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(f->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *o = nullptr;
-    PFHE_TRY(st.upload(glwe, len_glwe * sizeof(W), &a));
-    PFHE_TRY(st.alloc(len_lwe * sizeof(W), &o));
-    PFHE_TRY(sample_extract_dev<W>(f, k, (const W *)a, len_glwe, index, (W *)o, len_lwe, st.stream()));
-    PFHE_TRY(st.download(lwe, o, len_lwe * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(glwe, len_glwe * sizeof(W)), stage_out(lwe, len_lwe * sizeof(W))};
+    return staged_call(f->device, bufs, [&](void *const *d, hipStream_t s) {
+        return sample_extract_dev<W>(f, k, (const W *)d[0], len_glwe, index, (W *)d[1], len_lwe, s);
+    });
 }
 
 // ApproxSignedBasis::new's assert!s first, then the dimensions
@@ -375,17 +343,11 @@ int keyswitch_host(int device, const W *lwe_in, size_t len_in, size_t in_dimensi
     if (len_in == 0) return PFHE_OK;
     if (!lwe_in || !ksk || !lwe_out) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_TRY(capi_check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *o = nullptr;
-    PFHE_TRY(st.upload(lwe_in, len_in * sizeof(W), &a));
-    PFHE_TRY(st.upload(ksk, len_ksk * sizeof(W), &k));
-    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
-    PFHE_TRY(launch_keyswitch<W>((const W *)a, (const W *)k, (W *)o, sh, len_in / (in_dimension + 1), st.stream()));
-    PFHE_TRY(st.download(lwe_out, o, len_out * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(ksk, len_ksk * sizeof(W)),
+                             stage_out(lwe_out, len_out * sizeof(W))};
+    return staged_call(device, bufs, [&](void *const *d, hipStream_t s) {
+        return launch_keyswitch<W>((const W *)d[0], (const W *)d[1], (W *)d[2], sh, len_in / (in_dimension + 1), s);
+    });
 }
 
 }  // namespace
@@ -393,33 +355,31 @@ int keyswitch_host(int device, const W *lwe_in, size_t len_in, size_t in_dimensi
 
 // ---------------- the bootstrap handle ----------------
 
-// Owns a blind-rotation handle (classic or multi-bit) and, for `chunk` ciphertexts, the accumulator, the switched exponents, neg_b and (when a key
-// switch follows) the extracted LWE ciphertexts: all allocated at creation.
-template <class R, class M, class W>
+// Owns a blind rotation (classic or multi-bit, behind TfheRotation) and, for `chunk` ciphertexts, the accumulator, the
+// switched exponents, neg_b and (when a key switch follows) the extracted LWE ciphertexts: all allocated at creation.
+template <class W>
 struct TfheBootstrapCore {
-    R *rot = nullptr;  // owned: the classic rotation (pfhe_tfhe*_bootstrap_create) ...
-    M *mb = nullptr;   // ... or the multi-bit one (pfhe_tfhe*_bootstrap_create_multibit), never both
-    PlanGuard guard;   // one holder at a time, successive calls on different streams ordered
+    TfheRotation<W> *rotation = nullptr;  // owned
+    PlanGuard guard;                      // one holder at a time, successive calls on different streams ordered
     const pfhe_fft *fft = nullptr;
     u32 k = 1, n = 0;  // GLWE and LWE dimensions
     bool with_keyswitch = false;
     KsShape ks{};
-    size_t chunk = 1, glwe = 0, key_len = 0, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
+    size_t chunk = 1, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
     W *acc = nullptr, *extracted = nullptr;
     u32 *exps = nullptr, *neg_b = nullptr;
     ~TfheBootstrapCore() {
-        if (!rot && !mb) return;
+        if (!rotation) return;
         {
             DeviceGuard g(fft->device);
             for (void *b : {(void *)acc, (void *)extracted, (void *)exps, (void *)neg_b})
                 if (b) (void)counted_free(b);
         }
-        delete rot;
-        delete mb;
+        delete rotation;
     }
 };
-struct pfhe_tfhe_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe_blindrot, pfhe_tfhe_mbrot, u64> {};
-struct pfhe_tfhe32_bootstrap_handle : TfheBootstrapCore<pfhe_tfhe32_blindrot, pfhe_tfhe32_mbrot, u32> {};
+struct pfhe_tfhe_bootstrap_handle : TfheBootstrapCore<u64> {};
+struct pfhe_tfhe32_bootstrap_handle : TfheBootstrapCore<u32> {};
 
 namespace {
 
@@ -429,51 +389,40 @@ constexpr const char *kBootstrapLengths =
     "words, ksk k*N*ks_ell*(n+1) words (0 without a key switch) and lwe_out batch*(n+1) (batch*(k*N+1) without)";
 constexpr size_t kDefaultAccBytes = 256ull << 20;
 
-// which blind rotation a bootstrap handle owns: the classic one, or the multi-bit one, whose key has (lwe_dimension / g)
-// 2^g keys
-enum class Rotation { Classic, MultiBit };
-
-// the rotation's create first (its statuses, in its order), then what is the bootstrap's own.  grouping_factor counts only
-// for the multi-bit rotation, which refuses any outside 1..4
-template <class H, class W>
+// The rotation's create first (its statuses, in its order), then what is the bootstrap's own.  With a grouping factor the
+// rotation is the multi-bit one, whose key has (lwe_dimension / g) 2^g keys; everything that decides before the device
+// is then decided first: the rotation's own checks in its order, then the divisibility
+template <class W, class H>
 int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                      size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
-                     Rotation rotation, size_t grouping_factor, size_t chunk, H **out) {
+                     std::optional<size_t> grouping_factor, size_t chunk, H **out) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
-    size_t rot_chunk = 0;
-    const bool multibit = rotation == Rotation::MultiBit;
-    if (multibit) {
-        // everything that is decided before the device: the rotation's own checks in its order, then the divisibility
-        PFHE_TRY(tfhe_mbrot_check_args(8 * sizeof(W), fft, glwe_dimension, log_basis, decompose_length, grouping_factor));
-        if (lwe_dimension % grouping_factor != 0) {
+    if (grouping_factor) {
+        Shape sh{};
+        PFHE_TRY(tfhe_mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, *grouping_factor, sh));
+        if (lwe_dimension % *grouping_factor != 0) {
             set_last_error("TFHE multi-bit bootstrap: lwe_dimension must be a multiple of grouping_factor");
             return PFHE_ERR_BAD_ARGUMENT;
         }
-        PFHE_TRY(tfhe_mbrot_create_handle(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &h->mb));
-        h->glwe = h->mb->glwe;
-        h->key_len = h->mb->key_len;
-        rot_chunk = h->mb->chunk;
-    } else {
-        PFHE_TRY(tfhe_blindrot_create_handle(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->rot));
-        h->glwe = h->rot->glwe;
-        h->key_len = h->rot->key_len;
-        rot_chunk = h->rot->chunk;
     }
+    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &h->rotation));
+    const TfheRotation<W> &rot = *h->rotation;
     h->fft = fft;
     h->k = (u32)glwe_dimension;
     h->with_keyswitch = with_keyswitch != 0;
-    const size_t glwe = h->glwe, ext = glwe_dimension * fft->n + 1;
+    const size_t glwe = rot.glwe, ext = glwe_dimension * fft->n + 1;
     if (glwe_dimension == 0 || lwe_dimension == 0 || lwe_dimension >= 0x7fffffffull) {
         set_last_error("TFHE bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2");
         return PFHE_ERR_BAD_ARGUMENT;
     }
     h->n = (u32)lwe_dimension;
-    h->bsk_len = multibit ? ((lwe_dimension / grouping_factor) << grouping_factor) * h->key_len : lwe_dimension * h->key_len;
+    const size_t keys = grouping_factor ? (lwe_dimension / *grouping_factor) << *grouping_factor : lwe_dimension;
+    h->bsk_len = keys * rot.key_len;
     if (h->with_keyswitch) PFHE_TRY(keyswitch_shape<W>(ext - 1, lwe_dimension, ks_log_basis, ks_decompose_length, h->ks));
     // chunk 0: the rotation's default, capped at about 256 MiB of accumulator
-    h->chunk = chunk ? rot_chunk : std::min(rot_chunk, std::max<size_t>(1, kDefaultAccBytes / (glwe * sizeof(W))));
+    h->chunk = chunk ? rot.chunk : std::min(rot.chunk, std::max<size_t>(1, kDefaultAccBytes / (glwe * sizeof(W))));
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     const size_t sizes[] = {h->chunk * glwe * sizeof(W), h->with_keyswitch ? h->chunk * ext * sizeof(W) : 0,
@@ -491,7 +440,7 @@ int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
 
 template <class W, class H>
 int bootstrap_check(const H *h, size_t len_in, size_t len_bsk, size_t len_tv, size_t len_ksk, size_t len_out, u64 &batch) {
-    const size_t glwe = h->glwe, ext = (size_t)h->k * h->fft->n + 1;
+    const size_t glwe = h->rotation->glwe, ext = (size_t)h->k * h->fft->n + 1;
     const size_t out_words = h->with_keyswitch ? (size_t)h->n + 1 : ext;
     const size_t ksk_words = h->with_keyswitch ? (ext - 1) * h->ks.ell * ((size_t)h->n + 1) : 0;
     batch = len_in / ((size_t)h->n + 1);
@@ -506,7 +455,7 @@ int bootstrap_check(const H *h, size_t len_in, size_t len_bsk, size_t len_tv, si
 template <class W, class H>
 int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
                   const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out, hipStream_t s) {
-    if (!h || (!h->rot && !h->mb)) return PFHE_ERR_BAD_ARGUMENT;
+    if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
     if (!h->with_keyswitch && (ksk || len_ksk)) {
         set_last_error("TFHE bootstrap: a handle without a key switch takes no key-switch key");
@@ -527,7 +476,7 @@ int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_
     const pfhe_fft &f = *h->fft;
     DeviceGuard g(f.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const size_t glwe = h->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
+    const size_t glwe = h->rotation->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
     const size_t out_words = h->with_keyswitch ? in_words : ext;
     const u64 tv_stride = len_tv == glwe ? 0 : glwe;
     return ordered_on(h->guard, s, [&]() -> int {
@@ -536,8 +485,7 @@ int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_
             const u64 cur = std::min<u64>(h->chunk, batch - done);
             PFHE_TRY(launch_modswitch<W>(lwe_in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, s));
             PFHE_TRY(launch_acc_init<W>(tv + done * tv_stride, tv_stride, h->acc, h->neg_b, h->k + 1, f.log_n, cur, s));
-            PFHE_TRY(h->mb ? tfhe_mbrot_rotate_handle(h->mb, h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s)
-                           : tfhe_blindrot_rotate_handle(h->rot, h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s));
+            PFHE_TRY(h->rotation->rotate_dev(h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s));
             W *lwe = h->with_keyswitch ? h->extracted : lwe_out + done * out_words;
             PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, s));
             if (h->with_keyswitch) PFHE_TRY(launch_keyswitch<W>(lwe, ksk, lwe_out + done * out_words, h->ks, cur, s));
@@ -546,11 +494,11 @@ int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_
     });
 }
 
-// host form: staged through the pooled context
+// host form
 template <class W, class H>
 int bootstrap_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
                    const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out) {
-    if (!h || (!h->rot && !h->mb)) return PFHE_ERR_BAD_ARGUMENT;
+    if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
     if (!h->with_keyswitch && (ksk || len_ksk)) {
         set_last_error("TFHE bootstrap: a handle without a key switch takes no key-switch key");
@@ -560,26 +508,19 @@ int bootstrap_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size
     PFHE_TRY((bootstrap_check<W>(h, len_in, len_bsk, len_tv, len_ksk, len_out, batch)));
     if (batch == 0) return PFHE_OK;
     if (!lwe_in || !bsk || !tv || !lwe_out || (h->with_keyswitch && !ksk)) return PFHE_ERR_BAD_ARGUMENT;
-    DeviceGuard g(h->fft->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(h->fft->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *b = nullptr, *t = nullptr, *k = nullptr, *o = nullptr;
-    PFHE_TRY(st.upload(lwe_in, len_in * sizeof(W), &a));
-    PFHE_TRY(st.upload(bsk, len_bsk * 2 * sizeof(double), &b));
-    PFHE_TRY(st.upload(tv, len_tv * sizeof(W), &t));
-    if (h->with_keyswitch) PFHE_TRY(st.upload(ksk, len_ksk * sizeof(W), &k));
-    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
-    PFHE_TRY(bootstrap_dev<W>(h, (const W *)a, len_in, (const double *)b, len_bsk, (const W *)t, len_tv, (const W *)k, len_ksk,
-                              (W *)o, len_out, st.stream()));
-    PFHE_TRY(st.download(lwe_out, o, len_out * sizeof(W)));
-    return st.finish();
+    // without a key switch ksk is empty: it is not staged and the device form gets a null pointer
+    const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
+                             stage_in(tv, len_tv * sizeof(W)), stage_in(ksk, len_ksk * sizeof(W)),
+                             stage_out(lwe_out, len_out * sizeof(W))};
+    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
+        return bootstrap_dev<W>(h, (const W *)d[0], len_in, (const double *)d[1], len_bsk, (const W *)d[2], len_tv,
+                                (const W *)d[3], len_ksk, (W *)d[4], len_out, s);
+    });
 }
 
 template <class H>
 size_t bootstrap_scratch(const H *h) {
-    if (h && h->mb) return h->mb->scratch + h->bytes;
-    return h && h->rot && h->rot->plan ? h->rot->plan->scratch + h->rot->glue_bytes + h->bytes : 0;
+    return h && h->rotation ? h->rotation->scratch_bytes() + h->bytes : 0;
 }
 
 }  // namespace
@@ -664,9 +605,8 @@ int pfhe_tfhe_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint3
                                size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
                                size_t chunk, pfhe_tfhe_bootstrap_handle **out) {
     PFHE_GUARD_BEGIN
-    return bootstrap_create<pfhe_tfhe_bootstrap_handle, u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
-                                                      ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::Classic, 0,
-                                                      chunk, out);
+    return bootstrap_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                 ks_decompose_length, with_keyswitch, std::nullopt, chunk, out);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
@@ -675,9 +615,8 @@ int pfhe_tfhe_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimensi
                                         pfhe_tfhe_bootstrap_handle **out) {
     PFHE_GUARD_BEGIN
     if (out) *out = nullptr;
-    return bootstrap_create<pfhe_tfhe_bootstrap_handle, u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
-                                                      ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::MultiBit,
-                                                      grouping_factor, chunk, out);
+    return bootstrap_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                 ks_decompose_length, with_keyswitch, grouping_factor, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h) { delete h; }
@@ -704,9 +643,8 @@ int pfhe_tfhe32_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uin
                                  size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
                                  size_t chunk, pfhe_tfhe32_bootstrap_handle **out) {
     PFHE_GUARD_BEGIN
-    return bootstrap_create<pfhe_tfhe32_bootstrap_handle, u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
-                                                        ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::Classic,
-                                                        0, chunk, out);
+    return bootstrap_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                 ks_decompose_length, with_keyswitch, std::nullopt, chunk, out);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
@@ -715,9 +653,8 @@ int pfhe_tfhe32_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimen
                                           pfhe_tfhe32_bootstrap_handle **out) {
     PFHE_GUARD_BEGIN
     if (out) *out = nullptr;
-    return bootstrap_create<pfhe_tfhe32_bootstrap_handle, u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension,
-                                                        ks_log_basis, ks_decompose_length, with_keyswitch, Rotation::MultiBit,
-                                                        grouping_factor, chunk, out);
+    return bootstrap_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                 ks_decompose_length, with_keyswitch, grouping_factor, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h) { delete h; }

@@ -50,9 +50,6 @@ using namespace pfhe;
 namespace pfhe {
 namespace {
 
-constexpr u32 kMaxLogN = 14;
-constexpr int kThreads = kFftThreads;
-
 // ---------------- standalone batched transforms ----------------
 
 // forward_torus_slice: count polynomials of N words -> count x N complex (the reference's full layout)
@@ -392,10 +389,7 @@ int forward_dev(const pfhe_fft *f, const W *in, size_t len_in, double *out, size
     if (count > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
     DeviceGuard g(f->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    hipLaunchKernelGGL(fft_forward_kernel<W>, dim3((u32)count), dim3(kThreads), lds_bytes(f->log_n), s, in, (double2 *)out,
-                       f->tw, f->log_n);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_groups(fft_forward_kernel<W>, count, lds_bytes(f->log_n), s, in, (double2 *)out, f->tw, f->log_n);
 }
 
 template <class W>
@@ -413,13 +407,10 @@ int inverse_dev(const pfhe_fft *f, const double *in, size_t len_in, W *out, size
     if (count > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
     DeviceGuard g(f->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    hipLaunchKernelGGL((fft_inverse_kernel<W, true>), dim3((u32)count), dim3(kThreads), lds_bytes(f->log_n), s,
-                       (const double2 *)in, out, f->tw, f->log_n);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_groups(fft_inverse_kernel<W, true>, count, lds_bytes(f->log_n), s, (const double2 *)in, out, f->tw, f->log_n);
 }
 
-// host forms: staged through the pooled context (in, out are host pointers)
+// host forms of the two transforms (in, out are host pointers)
 template <class In, class Out, class DevFn>
 int host_form(const pfhe_fft *f, const In *in, size_t in_bytes, Out *out, size_t out_bytes, size_t len_in, size_t len_out,
               DevFn dev) {
@@ -427,116 +418,79 @@ int host_form(const pfhe_fft *f, const In *in, size_t in_bytes, Out *out, size_t
     if ((!in && in_bytes) || (!out && out_bytes)) return PFHE_ERR_BAD_ARGUMENT;
     if (len_in % f->n != 0 || len_out != len_in) return PFHE_ERR_BAD_LENGTH;
     if (len_in == 0) return PFHE_OK;
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(f->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *b = nullptr;
-    PFHE_TRY(st.upload(in, in_bytes, &a));
-    PFHE_TRY(st.alloc(out_bytes, &b));
-    PFHE_TRY(dev((const In *)a, (Out *)b, st.stream()));
-    PFHE_TRY(st.download(out, b, out_bytes));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(in, in_bytes), stage_out(out, out_bytes)};
+    return staged_call(f->device, bufs, [&](void *const *d, hipStream_t s) { return dev((const In *)d[0], (Out *)d[1], s); });
 }
 
 // ---------------- plans ----------------
 
 constexpr const char *kPlanBusy = "TFHE product plan in use by another thread (one plan per thread, like &mut TfheFftContext)";
 
-constexpr size_t kMaxGlweDimension = 64;
-constexpr size_t kDefaultScratchBytes = 256ull << 20;
+// the shape on which the fused product and the whole-loop rotations run: it follows N and k alone
+inline bool fused_shape(const Shape &sh) { return sh.k == 1 && sh.log_n <= kFusedMaxLogN; }
 
-// what a plan checks before the device is touched, in this order: the basis's assert!s, k, the table
-template <class W>
-int plan_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, u32 &ell, u32 &drop) {
-    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
-    if (glwe_dimension > kMaxGlweDimension) {
-        set_last_error("glwe_dimension above 64 is not supported");
-        return PFHE_ERR_UNSUPPORTED;
-    }
-    if (!fft) return PFHE_ERR_BAD_ARGUMENT;
-    return PFHE_OK;
-}
-
-template <class P>
+// P: a C handle (pfhe_tfhe{,32}_plan) or the core itself (the plan a rotation owns)
+template <class W, class P>
 int plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t chunk,
                 P **out) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    using W = typename std::conditional<std::is_same<P, pfhe_tfhe_plan>::value, u64, u32>::type;
-    u32 ell = 0, drop = 0;
-    PFHE_TRY(plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, ell, drop));
+    Shape sh{};
+    PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, sh));
     auto p = std::make_unique<P>();
-    p->k = (u32)glwe_dimension;
-    p->log_basis = log_basis;
-    p->ell = ell;
-    p->drop_bits = drop;
-    // the form follows N and k alone
-    p->fused = p->k == 1 && fft->log_n <= kFusedMaxLogN;
-    const size_t m = fft->n / 2, rows = glwe_dimension + 1;
-    const size_t per_ct = p->fused ? 0 : (rows * ell + rows) * m * sizeof(double2);
-    p->chunk = chunk ? chunk : (per_ct ? std::max<size_t>(1, kDefaultScratchBytes / per_ct) : 65536);
-    p->chunk = std::min<size_t>(p->chunk, p->fused ? 0x7fffffffull : 0x7fffffffull / (rows * ell));
+    p->shape = sh;
+    p->fused = fused_shape(sh);
+    p->chunk = chunk;
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     p->fft = fft;
-    if (!p->fused) {
-        const size_t sizes[] = {p->chunk * rows * ell * m, p->chunk * rows * m, rows * ell * rows * m};
-        double2 **bufs[] = {&p->spec, &p->acc, &p->keyh};
-        for (int i = 0; i < 3; ++i) {
-            void *b = nullptr;
-            PFHE_HIP(counted_malloc(&b, sizes[i] * sizeof(double2)));
-            *bufs[i] = (double2 *)b;
-            p->scratch += sizes[i] * sizeof(double2);
-        }
-    }
+    PFHE_TRY(p->scratch.create(*fft, sh, 1, !p->fused, p->chunk));
     PFHE_TRY(p->guard.init(fft->device));
     *out = p.release();
     return PFHE_OK;
 }
 
-template <class W, class P>
-int product_impl(P *p, const W *in, const double2 *key, W *out, u64 batch, hipStream_t s) {
+// the launches of the general product on `cur` ciphertexts behind the Hermitian parts in t.keyh: the digit transforms
+// into t.spec, `mulacc` (the multiply-accumulate of the caller's form, which fills t.acc), the inverses into out
+template <class W, class MulAcc>
+int general_product(const pfhe_fft &f, const Shape &sh, const TfheProductScratch &t, const W *in, W *out, u64 cur, hipStream_t s,
+                    MulAcc mulacc) {
+    const u32 rows = sh.k + 1;
+    PFHE_TRY(launch_groups(tfhe_digit_fwd_kernel<W>, cur * rows * sh.ell, lds_bytes(f.log_n), s, in, t.spec, f.tw, sh));
+    PFHE_TRY(mulacc(cur * rows * (f.n / 2)));
+    return launch_groups(fft_inverse_kernel<W, false>, cur * rows, lds_bytes(f.log_n), s, t.acc, out, f.tw, f.log_n);
+}
+
+template <class W>
+int product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *out, u64 batch, hipStream_t s) {
     const pfhe_fft &f = *p->fft;
-    const u32 rows = p->k + 1, m = (u32)(f.n / 2);
-    const Shape sh{f.log_n, p->k, p->log_basis, p->ell, p->drop_bits};
+    const Shape &sh = p->shape;
+    const TfheProductScratch &t = p->scratch;
+    const u32 rows = sh.k + 1;
     const size_t glwe = (size_t)rows * f.n;
-    if (!p->fused) {
-        const u64 kt = (u64)rows * p->ell * rows * m;
-        hipLaunchKernelGGL(tfhe_key_herm_kernel, dim3((u32)((kt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, key,
-                           p->keyh, f.log_n, kt);
-        PFHE_HIP(hipGetLastError());
-    }
+    if (!p->fused) PFHE_TRY(launch_flat(tfhe_key_herm_kernel, (u64)rows * sh.ell * rows * (f.n / 2), s, key, t.keyh, f.log_n));
     for (u64 done = 0; done < batch; done += p->chunk) {
         const u64 cur = std::min<u64>(p->chunk, batch - done);
         const W *x = in + done * glwe;
         W *o = out + done * glwe;
         if (p->fused) {
-            hipLaunchKernelGGL(tfhe_fused_kernel<W>, dim3((u32)cur), dim3(kThreads), lds_bytes(f.log_n), s, x, key, o, f.tw, sh);
-            PFHE_HIP(hipGetLastError());
+            PFHE_TRY(launch_groups(tfhe_fused_kernel<W>, cur, lds_bytes(f.log_n), s, x, key, o, f.tw, sh));
             continue;
         }
-        hipLaunchKernelGGL(tfhe_digit_fwd_kernel<W>, dim3((u32)(cur * rows * p->ell)), dim3(kThreads), lds_bytes(f.log_n), s,
-                           x, p->spec, f.tw, sh);
-        PFHE_HIP(hipGetLastError());
-        const u64 at = cur * rows * m;
-        hipLaunchKernelGGL(tfhe_mulacc_kernel, dim3((u32)((at + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, p->spec,
-                           p->keyh, p->acc, f.log_n, p->k, p->ell, at);
-        PFHE_HIP(hipGetLastError());
-        hipLaunchKernelGGL((fft_inverse_kernel<W, false>), dim3((u32)(cur * rows)), dim3(kThreads), lds_bytes(f.log_n), s,
-                           p->acc, o, f.tw, f.log_n);
-        PFHE_HIP(hipGetLastError());
+        PFHE_TRY(general_product<W>(f, sh, t, x, o, cur, s, [&](u64 at) {
+            return launch_flat(tfhe_mulacc_kernel, at, s, t.spec, t.keyh, t.acc, f.log_n, sh.k, sh.ell);
+        }));
     }
     return PFHE_OK;
 }
 
-template <class W, class P>
-int product_dev(P *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out,
+template <class W>
+int product_dev(TfhePlanCore<W> *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out,
                 hipStream_t s) {
     if (!p || !p->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(p->guard, kPlanBusy);
     const pfhe_fft &f = *p->fft;
-    const size_t rows = p->k + 1, glwe = rows * f.n, key_len = rows * p->ell * rows * f.n;
+    const size_t rows = p->shape.k + 1, glwe = rows * f.n, key_len = rows * p->shape.ell * rows * f.n;
     if (len_in % glwe != 0 || len_out != len_in || len_key != key_len) {
         set_last_error("TFHE external product: input / output must be batch*(k+1)*N words and the key "
                        "(k+1)*ell*(k+1)*N complex values");
@@ -548,10 +502,9 @@ int product_dev(P *p, const W *in, size_t len_in, const double *key, size_t len_
     PFHE_REQUIRE_ALIGNED(in);
     PFHE_REQUIRE_ALIGNED(key);
     PFHE_REQUIRE_ALIGNED(out);
-    const uintptr_t a0 = (uintptr_t)in, o0 = (uintptr_t)out, bytes = (uintptr_t)len_in * sizeof(W);
     // in place is safe: the fused form reads a ciphertext wholly before its workgroup writes it, the general form reads a
     // chunk's input in the digit launch and writes its output in the inverse launch
-    if (a0 < o0 + bytes && o0 < a0 + bytes && a0 != o0) {
+    if (in != out && overlaps(in, len_in * sizeof(W), out, len_out * sizeof(W))) {
         set_last_error("TFHE external product: input and output must be the same buffer or disjoint");
         return PFHE_ERR_BAD_ARGUMENT;
     }
@@ -560,26 +513,20 @@ int product_dev(P *p, const W *in, size_t len_in, const double *key, size_t len_
     return ordered_on(p->guard, s, [&] { return product_impl<W>(p, in, (const double2 *)key, out, batch, s); });
 }
 
-template <class W, class P>
-int product_host(P *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out) {
+template <class W>
+int product_host(TfhePlanCore<W> *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out) {
     if (!p || !p->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(p->guard, kPlanBusy);
     if ((!in && len_in) || (!key && len_key) || (!out && len_out)) return PFHE_ERR_BAD_ARGUMENT;
     const pfhe_fft &f = *p->fft;
-    const size_t rows = p->k + 1, glwe = rows * f.n, key_len = rows * p->ell * rows * f.n;
+    const size_t rows = p->shape.k + 1, glwe = rows * f.n, key_len = rows * p->shape.ell * rows * f.n;
     if (len_in % glwe != 0 || len_out != len_in || len_key != key_len) return PFHE_ERR_BAD_LENGTH;
     if (len_in == 0) return PFHE_OK;
-    DeviceGuard g(f.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(f.device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *o = nullptr;
-    PFHE_TRY(st.upload(in, len_in * sizeof(W), &a));
-    PFHE_TRY(st.upload(key, len_key * 2 * sizeof(double), &k));
-    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
-    PFHE_TRY(product_dev<W>(p, (const W *)a, len_in, (const double *)k, len_key, (W *)o, len_out, st.stream()));
-    PFHE_TRY(st.download(out, o, len_out * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(in, len_in * sizeof(W)), stage_in(key, len_key * sizeof(double2)),
+                             stage_out(out, len_out * sizeof(W))};
+    return staged_call(f.device, bufs, [&](void *const *d, hipStream_t s) {
+        return product_dev<W>(p, (const W *)d[0], len_in, (const double *)d[1], len_key, (W *)d[2], len_out, s);
+    });
 }
 
 // ---------------- blind rotation ----------------
@@ -595,12 +542,8 @@ template <class W, bool ADD_E, bool STORE_ACC, int ROT>
 int launch_torus_glue(const W *acc, const W *e_in, W *acc_out, W *d_out, const u32 *exps, u32 exp_stride, u32 polys_per_exp,
                       u32 log_n, u64 total, hipStream_t s) {
     if (total == 0) return PFHE_OK;
-    const u64 grid = (total + kThreads - 1) / kThreads;
-    if (grid > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
-    hipLaunchKernelGGL((tfhe_blindrot_glue_kernel<W, ADD_E, STORE_ACC, ROT>), dim3((u32)grid), dim3(kThreads), 0, s, acc, e_in,
-                       acc_out, d_out, exps, exp_stride, polys_per_exp, log_n, total);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_flat(tfhe_blindrot_glue_kernel<W, ADD_E, STORE_ACC, ROT>, total, s, acc, e_in, acc_out, d_out, exps, exp_stride,
+                       polys_per_exp, log_n);
 }
 
 template <class W>
@@ -642,8 +585,7 @@ int torus_monomial_each(const pfhe_fft *f, const W *a, size_t len, const uint32_
     if (!a || !exps || !out) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_REQUIRE_ALIGNED(a);
     PFHE_REQUIRE_ALIGNED(out);
-    const uintptr_t a0 = (uintptr_t)a, o0 = (uintptr_t)out, bytes = (uintptr_t)len * sizeof(W);
-    if (a0 < o0 + bytes && o0 < a0 + bytes) {
+    if (overlaps(a, len * sizeof(W), out, len * sizeof(W))) {
         set_last_error("mul_monomial_each_to needs non-overlapping buffers");
         return PFHE_ERR_BAD_ARGUMENT;
     }
@@ -654,17 +596,17 @@ int torus_monomial_each(const pfhe_fft *f, const W *a, size_t len, const uint32_
 
 // plan_create's checks in plan_create's order (the handle's plan IS a product plan), then the form: the whole-loop kernel
 // on the product's fused shape unless PFHE_DISABLE_FUSED_TFHE_BLINDROT is set when the handle is created
-template <class H, class P>
+template <class W, class H>
 int tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                          size_t chunk, H **out) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
-    PFHE_TRY(plan_create<P>(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->plan));
-    using W = typename std::remove_pointer<decltype(h->d)>::type;
-    const P &p = *h->plan;
-    h->glwe = (size_t)(p.k + 1) * fft->n;
-    h->key_len = (size_t)(p.k + 1) * p.ell * h->glwe;
+    PFHE_TRY(plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->plan));
+    const TfhePlanCore<W> &p = *h->plan;
+    h->fft = fft;
+    h->glwe = (size_t)(p.shape.k + 1) * fft->n;
+    h->key_len = (size_t)(p.shape.k + 1) * p.shape.ell * h->glwe;
     h->whole_loop = p.fused && std::getenv("PFHE_DISABLE_FUSED_TFHE_BLINDROT") == nullptr;
     h->chunk = p.chunk;
     DeviceGuard g(fft->device);
@@ -684,20 +626,17 @@ int tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t lo
     return PFHE_OK;
 }
 
-template <class W, class H>
-int tfhe_blindrot_chunk(H *h, W *a0, const double2 *bsk, const uint32_t *ex, u64 n_steps, u64 cur, hipStream_t s) {
-    const pfhe_fft &f = *h->plan->fft;
-    if (h->whole_loop) {
-        const Shape sh{f.log_n, h->plan->k, h->plan->log_basis, h->plan->ell, h->plan->drop_bits};
-        hipLaunchKernelGGL(tfhe_blindrot_loop_kernel<W>, dim3((u32)cur), dim3(kThreads), lds_bytes(f.log_n) + h->glwe * sizeof(W),
-                           s, a0, bsk, ex, (u32)n_steps, f.tw, sh);
-        PFHE_HIP(hipGetLastError());
-        return PFHE_OK;
-    }
+template <class W>
+int tfhe_blindrot_chunk(TfheBlindRotCore<W> *h, W *a0, const double2 *bsk, const uint32_t *ex, u64 n_steps, u64 cur,
+                        hipStream_t s) {
+    const pfhe_fft &f = *h->fft;
+    if (h->whole_loop)
+        return launch_groups(tfhe_blindrot_loop_kernel<W>, cur, lds_bytes(f.log_n) + h->glwe * sizeof(W), s, a0, bsk, ex,
+                             (u32)n_steps, f.tw, h->plan->shape);
     // ping-pong between the caller's accumulator and the handle's: every step writes ACC' to the other one, so the gather
     // of a rotated word never sees a word already updated; an odd step count starts in the handle's buffer so that the
     // last step ends in the caller's
-    const u32 rows = h->plan->k + 1;
+    const u32 rows = h->plan->shape.k + 1;
     W *src = a0;
     if (n_steps % 2) {
         PFHE_TRY(torus_glue<W>(f, TorusGlue::kFirstCopy, a0, nullptr, h->ping, h->d, ex, (u32)n_steps, rows, cur, s));
@@ -716,8 +655,8 @@ int tfhe_blindrot_chunk(H *h, W *a0, const double2 *bsk, const uint32_t *ex, u64
     return PFHE_OK;
 }
 
-template <class W, class H>
-int tfhe_blindrot_dev(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+template <class W>
+int tfhe_blindrot_dev(TfheBlindRotCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
                       size_t len_exps, hipStream_t s) {
     if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBlindRotBusy);
@@ -731,7 +670,7 @@ int tfhe_blindrot_dev(H *h, W *acc, size_t len_acc, const double *bsk, size_t le
     if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_REQUIRE_ALIGNED(acc);
     PFHE_REQUIRE_ALIGNED(bsk);
-    DeviceGuard g(h->plan->fft->device);
+    DeviceGuard g(h->fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     return ordered_on(h->guard, s, [&]() -> int {
         // chunk after chunk; every step of a chunk runs before the next chunk starts
@@ -743,41 +682,24 @@ int tfhe_blindrot_dev(H *h, W *acc, size_t len_acc, const double *bsk, size_t le
     });
 }
 
-// host form: every exponent must be below 2N; staged through the pooled context
-template <class W, class H>
-int tfhe_blindrot_host(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+// host form: every exponent must be below 2N
+template <class W>
+int tfhe_blindrot_host(TfheBlindRotCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
                        size_t len_exps) {
     if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBlindRotBusy);
     if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
-    const pfhe_fft &f = *h->plan->fft;
-    for (size_t i = 0; i < len_exps; ++i) {
-        if (exps[i] >= 2 * f.n) {
-            set_last_error("TFHE blind rotation: every exponent must be below 2N");
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
-    }
+    PFHE_TRY(require_exps_below_2n(exps, len_exps, h->fft->n, "TFHE blind rotation: every exponent must be below 2N"));
     if (len_acc % h->glwe != 0 || len_bsk % h->key_len != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->key_len)) {
         set_last_error(kBlindRotLengths);
         return PFHE_ERR_BAD_LENGTH;
     }
     if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
-    DeviceGuard g(f.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(f.device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *x = nullptr;
-    PFHE_TRY(st.upload(acc, len_acc * sizeof(W), &a));
-    PFHE_TRY(st.upload(bsk, len_bsk * 2 * sizeof(double), &k));
-    PFHE_TRY(st.upload(exps, len_exps * sizeof(uint32_t), &x));
-    PFHE_TRY(tfhe_blindrot_dev<W>(h, (W *)a, len_acc, (const double *)k, len_bsk, (const uint32_t *)x, len_exps, st.stream()));
-    PFHE_TRY(st.download(acc, a, len_acc * sizeof(W)));
-    return st.finish();
-}
-
-template <class H>
-size_t tfhe_blindrot_scratch(const H *h) {
-    return h && h->plan ? h->plan->scratch + h->glue_bytes : 0;
+    const StageBuf bufs[] = {stage_inout(acc, len_acc * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
+                             stage_in(exps, len_exps * sizeof(uint32_t))};
+    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
+        return tfhe_blindrot_dev<W>(h, (W *)d[0], len_acc, (const double *)d[1], len_bsk, (const uint32_t *)d[2], len_exps, s);
+    });
 }
 
 // ---------------- multi-bit blind rotation ----------------
@@ -785,102 +707,64 @@ size_t tfhe_blindrot_scratch(const H *h) {
 constexpr const char *kMbRotBusy = "TFHE multi-bit blind-rotation handle in use by another thread (one handle per thread)";
 constexpr const char *kMbRotLengths = "TFHE multi-bit blind rotation: acc must be batch*(k+1)*N words, bsk groups*2^g keys of "
                                       "(k+1)*ell*(k+1)*N complex values and exps batch*groups*g exponents";
-constexpr size_t kMaxGrouping = 4;
-
-template <class W>
-int mbrot_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                size_t grouping_factor, u32 &ell, u32 &drop) {
-    PFHE_TRY(plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, ell, drop));
-    if (grouping_factor == 0 || grouping_factor > kMaxGrouping) {
-        set_last_error("grouping_factor must be in 1..4");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    return PFHE_OK;
-}
-
-// plan_create's checks in plan_create's order through plan_check, then the grouping factor, all before the device; the
-// whole-loop kernel on the product's fused shape unless PFHE_DISABLE_FUSED_TFHE_BLINDROT is set when the handle is created
-template <class H, class W>
+// the plan's checks in its order, then the grouping factor, all before the device (tfhe_mbrot_check); the whole-loop kernel
+// on the product's fused shape unless PFHE_DISABLE_FUSED_TFHE_BLINDROT is set when the handle is created
+template <class W, class H>
 int tfhe_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                       size_t grouping_factor, size_t chunk, H **out) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
-    u32 ell = 0, drop = 0;
-    PFHE_TRY(mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, ell, drop));
+    Shape sh{};
+    PFHE_TRY(tfhe_mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, sh));
     auto h = std::make_unique<H>();
-    h->k = (u32)glwe_dimension;
-    h->log_basis = log_basis;
-    h->ell = ell;
-    h->drop_bits = drop;
+    h->shape = sh;
     h->g = (u32)grouping_factor;
-    const size_t m = fft->n / 2, rows = glwe_dimension + 1;
-    h->glwe = rows * fft->n;
-    h->key_len = rows * ell * h->glwe;
-    h->whole_loop = h->k == 1 && fft->log_n <= kFusedMaxLogN && std::getenv("PFHE_DISABLE_FUSED_TFHE_BLINDROT") == nullptr;
-    const size_t per_ct = (rows * ell + rows) * m * sizeof(double2);
-    h->chunk = chunk ? chunk : (h->whole_loop ? 65536 : std::max<size_t>(1, kDefaultScratchBytes / per_ct));
-    h->chunk = std::min<size_t>(h->chunk, h->whole_loop ? 0x7fffffffull : 0x7fffffffull / (rows * ell));
+    h->glwe = (glwe_dimension + 1) * fft->n;
+    h->key_len = (glwe_dimension + 1) * sh.ell * h->glwe;
+    h->whole_loop = fused_shape(sh) && std::getenv("PFHE_DISABLE_FUSED_TFHE_BLINDROT") == nullptr;
+    h->chunk = chunk;
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     h->fft = fft;
-    if (!h->whole_loop) {
-        const size_t sizes[] = {h->chunk * rows * ell * m, h->chunk * rows * m, (rows * ell * rows * m) << h->g};
-        double2 **bufs[] = {&h->spec, &h->acc, &h->keyh};
-        for (int i = 0; i < 3; ++i) {
-            void *b = nullptr;
-            PFHE_HIP(counted_malloc(&b, sizes[i] * sizeof(double2)));
-            *bufs[i] = (double2 *)b;
-            h->scratch += sizes[i] * sizeof(double2);
-        }
-    }
+    PFHE_TRY(h->scratch.create(*fft, sh, (size_t)1 << h->g, !h->whole_loop, h->chunk));
     PFHE_TRY(h->guard.init(fft->device));
     *out = h.release();
     return PFHE_OK;
 }
 
 // the launches of one rotation (arguments already checked)
-template <class W, class H>
-int tfhe_mbrot_impl(H *h, W *acc, const double2 *bsk, const uint32_t *exps, u64 batch, u64 groups, hipStream_t s) {
+template <class W>
+int tfhe_mbrot_impl(TfheMultiBitCore<W> *h, W *acc, const double2 *bsk, const uint32_t *exps, u64 batch, u64 groups,
+                    hipStream_t s) {
     const pfhe_fft &f = *h->fft;
-    const Shape sh{f.log_n, h->k, h->log_basis, h->ell, h->drop_bits};
-    const u32 rows = h->k + 1, m = (u32)(f.n / 2), n_mask = (u32)(groups * h->g);
-    if (h->whole_loop) {
-        for (u64 done = 0; done < batch; done += h->chunk) {
-            const u64 cur = std::min<u64>(h->chunk, batch - done);
-            hipLaunchKernelGGL(tfhe_mb_blindrot_loop_kernel<W>, dim3((u32)cur), dim3(kThreads),
-                               lds_bytes(f.log_n) + h->glwe * sizeof(W), s, acc + done * h->glwe, bsk, exps + done * n_mask,
-                               (u32)groups, h->g, f.tw, sh);
-            PFHE_HIP(hipGetLastError());
-        }
-        return PFHE_OK;
-    }
-    // chunk after chunk; every group of a chunk runs before the next chunk starts.  Per group: the Hermitian parts of its
-    // 2^g keys, the digit spectra of ACC itself, the multiply-accumulate against the per-ciphertext key, the inverses into ACC
-    const u64 kt = ((u64)rows * h->ell * rows * m) << h->g;
+    const Shape &sh = h->shape;
+    const TfheProductScratch &t = h->scratch;
+    const u32 rows = sh.k + 1, n_mask = (u32)(groups * h->g);
+    // chunk after chunk; every group of a chunk runs before the next chunk starts.  Per group in the per-group form: the
+    // Hermitian parts of its 2^g keys, then the product of ACC itself against the per-ciphertext key, back into ACC
     for (u64 done = 0; done < batch; done += h->chunk) {
         const u64 cur = std::min<u64>(h->chunk, batch - done);
         W *a = acc + done * h->glwe;
-        const u64 at = cur * rows * m;
-        for (u64 t = 0; t < groups; ++t) {
-            hipLaunchKernelGGL(tfhe_key_herm_kernel, dim3((u32)((kt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                               bsk + (t << h->g) * h->key_len, h->keyh, f.log_n, kt);
-            PFHE_HIP(hipGetLastError());
-            hipLaunchKernelGGL(tfhe_digit_fwd_kernel<W>, dim3((u32)(cur * rows * h->ell)), dim3(kThreads), lds_bytes(f.log_n), s,
-                               a, h->spec, f.tw, sh);
-            PFHE_HIP(hipGetLastError());
-            hipLaunchKernelGGL(tfhe_mb_mulacc_kernel, dim3((u32)((at + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, h->spec,
-                               h->keyh, h->acc, exps + done * n_mask + t * h->g, n_mask, h->g, f.tw, f.log_n, h->k, h->ell, at);
-            PFHE_HIP(hipGetLastError());
-            hipLaunchKernelGGL((fft_inverse_kernel<W, false>), dim3((u32)(cur * rows)), dim3(kThreads), lds_bytes(f.log_n), s,
-                               h->acc, a, f.tw, f.log_n);
-            PFHE_HIP(hipGetLastError());
+        const uint32_t *ex = exps + done * n_mask;
+        if (h->whole_loop) {
+            PFHE_TRY(launch_groups(tfhe_mb_blindrot_loop_kernel<W>, cur, lds_bytes(f.log_n) + h->glwe * sizeof(W), s, a, bsk, ex,
+                                   (u32)groups, h->g, f.tw, sh));
+            continue;
+        }
+        for (u64 g = 0; g < groups; ++g) {
+            PFHE_TRY(launch_flat(tfhe_key_herm_kernel, ((u64)rows * sh.ell * rows * (f.n / 2)) << h->g, s,
+                                 bsk + (g << h->g) * h->key_len, t.keyh, f.log_n));
+            PFHE_TRY(general_product<W>(f, sh, t, a, a, cur, s, [&](u64 at) {
+                return launch_flat(tfhe_mb_mulacc_kernel, at, s, t.spec, t.keyh, t.acc, ex + g * h->g, n_mask, h->g, f.tw,
+                                   f.log_n, sh.k, sh.ell);
+            }));
         }
     }
     return PFHE_OK;
 }
 
-template <class H>
-bool mbrot_lengths_ok(const H *h, size_t len_acc, size_t len_bsk, size_t len_exps, u64 &batch, u64 &groups) {
+template <class W>
+bool mbrot_lengths_ok(const TfheMultiBitCore<W> *h, size_t len_acc, size_t len_bsk, size_t len_exps, u64 &batch, u64 &groups) {
     const size_t group_len = h->key_len << h->g;
     if (len_acc % h->glwe != 0 || len_bsk % group_len != 0) return false;
     batch = len_acc / h->glwe;
@@ -888,9 +772,9 @@ bool mbrot_lengths_ok(const H *h, size_t len_acc, size_t len_bsk, size_t len_exp
     return len_exps == batch * groups * h->g;
 }
 
-template <class W, class H>
-int tfhe_mbrot_dev(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
-                   hipStream_t s) {
+template <class W>
+int tfhe_mbrot_dev(TfheMultiBitCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+                   size_t len_exps, hipStream_t s) {
     if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kMbRotBusy);
     u64 batch = 0, groups = 0;
@@ -908,36 +792,25 @@ int tfhe_mbrot_dev(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_b
     return ordered_on(h->guard, s, [&] { return tfhe_mbrot_impl<W>(h, acc, (const double2 *)bsk, exps, batch, groups, s); });
 }
 
-// host form: every exponent must be below 2N; staged through the pooled context
-template <class W, class H>
-int tfhe_mbrot_host(H *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps) {
+// host form: every exponent must be below 2N
+template <class W>
+int tfhe_mbrot_host(TfheMultiBitCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+                    size_t len_exps) {
     if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kMbRotBusy);
     if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
-    const pfhe_fft &f = *h->fft;
-    for (size_t i = 0; i < len_exps; ++i) {
-        if (exps[i] >= 2 * f.n) {
-            set_last_error("TFHE multi-bit blind rotation: every exponent must be below 2N");
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
-    }
+    PFHE_TRY(require_exps_below_2n(exps, len_exps, h->fft->n, "TFHE multi-bit blind rotation: every exponent must be below 2N"));
     u64 batch = 0, groups = 0;
     if (!mbrot_lengths_ok(h, len_acc, len_bsk, len_exps, batch, groups)) {
         set_last_error(kMbRotLengths);
         return PFHE_ERR_BAD_LENGTH;
     }
     if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
-    DeviceGuard g(f.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(f.device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *x = nullptr;
-    PFHE_TRY(st.upload(acc, len_acc * sizeof(W), &a));
-    PFHE_TRY(st.upload(bsk, len_bsk * 2 * sizeof(double), &k));
-    PFHE_TRY(st.upload(exps, len_exps * sizeof(uint32_t), &x));
-    PFHE_TRY(tfhe_mbrot_dev<W>(h, (W *)a, len_acc, (const double *)k, len_bsk, (const uint32_t *)x, len_exps, st.stream()));
-    PFHE_TRY(st.download(acc, a, len_acc * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_inout(acc, len_acc * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
+                             stage_in(exps, len_exps * sizeof(uint32_t))};
+    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
+        return tfhe_mbrot_dev<W>(h, (W *)d[0], len_acc, (const double *)d[1], len_bsk, (const uint32_t *)d[2], len_exps, s);
+    });
 }
 
 // the combined key of one ciphertext and one group as a key in the reference's layout
@@ -962,73 +835,51 @@ int mb_combine_key_dev(const pfhe_fft *f, size_t glwe_dimension, size_t decompos
     if (!keys || !exps || !out) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_REQUIRE_ALIGNED(keys);
     PFHE_REQUIRE_ALIGNED(out);
-    const uintptr_t k0 = (uintptr_t)keys, o0 = (uintptr_t)out;
-    if (k0 < o0 + len_out * sizeof(double2) && o0 < k0 + len_keys * sizeof(double2)) {
+    if (overlaps(keys, len_keys * sizeof(double2), out, len_out * sizeof(double2))) {
         set_last_error("multi-bit key combination: the output must not overlap the keys");
         return PFHE_ERR_BAD_ARGUMENT;
     }
     DeviceGuard g(f->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const u64 total = key_len / 2;
-    hipLaunchKernelGGL(tfhe_mb_combine_key_kernel, dim3((u32)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       (const double2 *)keys, exps, (double2 *)out, (u32)grouping_factor, f->tw, f->log_n, (u64)key_len, total);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_flat(tfhe_mb_combine_key_kernel, key_len / 2, s, (const double2 *)keys, exps, (double2 *)out,
+                       (u32)grouping_factor, f->tw, f->log_n, (u64)key_len);
 }
 
 }  // namespace
 
+// ---------------- the rotations as the bootstrap handle holds them ----------------
+
+template <class W>
+int TfheBlindRotCore<W>::rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+                                    size_t len_exps, hipStream_t s) {
+    return tfhe_blindrot_dev<W>(this, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+}
+template <class W>
+int TfheMultiBitCore<W>::rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
+                                    size_t len_exps, hipStream_t s) {
+    return tfhe_mbrot_dev<W>(this, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+}
+
 namespace pfhe {
 
-// what pfhe_tfhe{,32}_blindrot_create / _rotate_dev run, for the bootstrap handle (pfhe_bootstrap.hip)
-int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                size_t chunk, pfhe_tfhe_blindrot **out) {
-    return ::tfhe_blindrot_create<pfhe_tfhe_blindrot, pfhe_tfhe_plan>(fft, glwe_dimension, log_basis, decompose_length, chunk,
-                                                                      out);
+template <class W>
+int tfhe_rotation_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         std::optional<size_t> grouping_factor, size_t chunk, TfheRotation<W> **out) {
+    if (grouping_factor) {
+        TfheMultiBitCore<W> *h = nullptr;
+        const int rc = ::tfhe_mbrot_create<W>(fft, glwe_dimension, log_basis, decompose_length, *grouping_factor, chunk, &h);
+        *out = h;
+        return rc;
+    }
+    TfheBlindRotCore<W> *h = nullptr;
+    const int rc = ::tfhe_blindrot_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, &h);
+    *out = h;
+    return rc;
 }
-int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                size_t chunk, pfhe_tfhe32_blindrot **out) {
-    return ::tfhe_blindrot_create<pfhe_tfhe32_blindrot, pfhe_tfhe32_plan>(fft, glwe_dimension, log_basis, decompose_length,
-                                                                          chunk, out);
-}
-int tfhe_blindrot_rotate_handle(pfhe_tfhe_blindrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                                const uint32_t *exps, size_t len_exps, hipStream_t s) {
-    return ::tfhe_blindrot_dev<u64>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
-}
-int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                                const uint32_t *exps, size_t len_exps, hipStream_t s) {
-    return ::tfhe_blindrot_dev<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
-}
-
-int tfhe_plan_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                         u32 &ell, u32 &drop) {
-    return bits == 64 ? ::plan_check<u64>(fft, glwe_dimension, log_basis, decompose_length, ell, drop)
-                      : ::plan_check<u32>(fft, glwe_dimension, log_basis, decompose_length, ell, drop);
-}
-
-int tfhe_mbrot_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                          size_t grouping_factor) {
-    u32 ell = 0, drop = 0;
-    return bits == 64 ? ::mbrot_check<u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, ell, drop)
-                      : ::mbrot_check<u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, ell, drop);
-}
-int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                             size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out) {
-    return ::tfhe_mbrot_create<pfhe_tfhe_mbrot, u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
-}
-int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                             size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out) {
-    return ::tfhe_mbrot_create<pfhe_tfhe32_mbrot, u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk,
-                                                       out);
-}
-int tfhe_mbrot_rotate_handle(pfhe_tfhe_mbrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                             const uint32_t *exps, size_t len_exps, hipStream_t s) {
-    return ::tfhe_mbrot_dev<u64>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
-}
-int tfhe_mbrot_rotate_handle(pfhe_tfhe32_mbrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                             const uint32_t *exps, size_t len_exps, hipStream_t s) {
-    return ::tfhe_mbrot_dev<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
-}
+template int tfhe_rotation_create<u64>(const pfhe_fft *, size_t, uint32_t, size_t, std::optional<size_t>, size_t,
+                                       TfheRotation<u64> **);
+template int tfhe_rotation_create<u32>(const pfhe_fft *, size_t, uint32_t, size_t, std::optional<size_t>, size_t,
+                                       TfheRotation<u32> **);
 
 }  // namespace pfhe
 
@@ -1134,14 +985,14 @@ int pfhe_fft_inverse_torus32_slice(const pfhe_fft *fft, const double *input, siz
 int pfhe_tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                           size_t chunk, pfhe_tfhe_plan **out) {
     PFHE_GUARD_BEGIN
-    return plan_create(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
+    return plan_create<u64>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe_plan_destroy(pfhe_tfhe_plan *plan) { delete plan; }
 int pfhe_tfhe_plan_in_use(const pfhe_tfhe_plan *plan) {
     return plan ? plan->guard.in_use() : 0;
 }
-size_t pfhe_tfhe_plan_scratch_bytes(const pfhe_tfhe_plan *plan) { return plan ? plan->scratch : 0; }
+size_t pfhe_tfhe_plan_scratch_bytes(const pfhe_tfhe_plan *plan) { return plan ? plan->scratch.bytes : 0; }
 int pfhe_tfhe_external_product_to_dev(pfhe_tfhe_plan *plan, const uint64_t *input_dev, size_t len_input,
                                       const double *key_dev, size_t len_key, uint64_t *output_dev, size_t len_output,
                                       void *stream) {
@@ -1160,14 +1011,14 @@ int pfhe_tfhe_external_product_to(pfhe_tfhe_plan *plan, const uint64_t *input, s
 int pfhe_tfhe32_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                             size_t chunk, pfhe_tfhe32_plan **out) {
     PFHE_GUARD_BEGIN
-    return plan_create(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
+    return plan_create<u32>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_plan_destroy(pfhe_tfhe32_plan *plan) { delete plan; }
 int pfhe_tfhe32_plan_in_use(const pfhe_tfhe32_plan *plan) {
     return plan ? plan->guard.in_use() : 0;
 }
-size_t pfhe_tfhe32_plan_scratch_bytes(const pfhe_tfhe32_plan *plan) { return plan ? plan->scratch : 0; }
+size_t pfhe_tfhe32_plan_scratch_bytes(const pfhe_tfhe32_plan *plan) { return plan ? plan->scratch.bytes : 0; }
 int pfhe_tfhe32_external_product_to_dev(pfhe_tfhe32_plan *plan, const uint32_t *input_dev, size_t len_input,
                                         const double *key_dev, size_t len_key, uint32_t *output_dev, size_t len_output,
                                         void *stream) {
@@ -1185,13 +1036,12 @@ int pfhe_tfhe32_external_product_to(pfhe_tfhe32_plan *plan, const uint32_t *inpu
 int pfhe_tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                               size_t chunk, pfhe_tfhe_blindrot **out) {
     PFHE_GUARD_BEGIN
-    return tfhe_blindrot_create<pfhe_tfhe_blindrot, pfhe_tfhe_plan>(fft, glwe_dimension, log_basis, decompose_length, chunk,
-                                                                    out);
+    return tfhe_blindrot_create<u64>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe_blindrot_destroy(pfhe_tfhe_blindrot *h) { delete h; }
 int pfhe_tfhe_blindrot_in_use(const pfhe_tfhe_blindrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_blindrot_scratch_bytes(const pfhe_tfhe_blindrot *h) { return tfhe_blindrot_scratch(h); }
+size_t pfhe_tfhe_blindrot_scratch_bytes(const pfhe_tfhe_blindrot *h) { return h ? h->scratch_bytes() : 0; }
 int pfhe_tfhe_blindrot_rotate_dev(pfhe_tfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev,
                                   size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
@@ -1215,13 +1065,12 @@ int pfhe_tfhe_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint64_t *a_de
 int pfhe_tfhe32_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                                 size_t chunk, pfhe_tfhe32_blindrot **out) {
     PFHE_GUARD_BEGIN
-    return tfhe_blindrot_create<pfhe_tfhe32_blindrot, pfhe_tfhe32_plan>(fft, glwe_dimension, log_basis, decompose_length,
-                                                                        chunk, out);
+    return tfhe_blindrot_create<u32>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_blindrot_destroy(pfhe_tfhe32_blindrot *h) { delete h; }
 int pfhe_tfhe32_blindrot_in_use(const pfhe_tfhe32_blindrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_blindrot_scratch_bytes(const pfhe_tfhe32_blindrot *h) { return tfhe_blindrot_scratch(h); }
+size_t pfhe_tfhe32_blindrot_scratch_bytes(const pfhe_tfhe32_blindrot *h) { return h ? h->scratch_bytes() : 0; }
 int pfhe_tfhe32_blindrot_rotate_dev(pfhe_tfhe32_blindrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev,
                                     size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
@@ -1244,12 +1093,12 @@ int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_
 int pfhe_tfhe_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                            size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out) {
     PFHE_GUARD_BEGIN
-    return tfhe_mbrot_create<pfhe_tfhe_mbrot, u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
+    return tfhe_mbrot_create<u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe_mbrot_destroy(pfhe_tfhe_mbrot *h) { delete h; }
 int pfhe_tfhe_mbrot_in_use(const pfhe_tfhe_mbrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_mbrot_scratch_bytes(const pfhe_tfhe_mbrot *h) { return h ? h->scratch : 0; }
+size_t pfhe_tfhe_mbrot_scratch_bytes(const pfhe_tfhe_mbrot *h) { return h ? h->scratch_bytes() : 0; }
 int pfhe_tfhe_mbrot_rotate_dev(pfhe_tfhe_mbrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
                                const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
@@ -1265,13 +1114,12 @@ int pfhe_tfhe_mbrot_rotate(pfhe_tfhe_mbrot *h, uint64_t *acc, size_t len_acc, co
 int pfhe_tfhe32_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                              size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out) {
     PFHE_GUARD_BEGIN
-    return tfhe_mbrot_create<pfhe_tfhe32_mbrot, u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk,
-                                                     out);
+    return tfhe_mbrot_create<u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_mbrot_destroy(pfhe_tfhe32_mbrot *h) { delete h; }
 int pfhe_tfhe32_mbrot_in_use(const pfhe_tfhe32_mbrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_mbrot_scratch_bytes(const pfhe_tfhe32_mbrot *h) { return h ? h->scratch : 0; }
+size_t pfhe_tfhe32_mbrot_scratch_bytes(const pfhe_tfhe32_mbrot *h) { return h ? h->scratch_bytes() : 0; }
 int pfhe_tfhe32_mbrot_rotate_dev(pfhe_tfhe32_mbrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
                                  const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN

@@ -9,6 +9,7 @@
 //   keys        the three above in a row, then the existing forward transform for the bootstrapping key
 // No random number is drawn here: masks and noise are the caller's.  Every step is exact integer arithmetic modulo 2^BITS;
 // no atomics, no scratch memory.  The body calls ACCUMULATE into the body slot, so running one twice adds the product twice.
+// Launches and host forms go through pfhe_tfhe_host.hpp; the GLWE body keeps its own 2-D grid.
 #include <algorithm>
 #include <cstdint>
 
@@ -19,10 +20,7 @@ using namespace pfhe;
 namespace pfhe {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kWave = 64, kWavesPerBlock = kThreads / kWave;
-constexpr size_t kMaxGlweDimension = 64;
-constexpr size_t kMaxGrouping = 4;
 
 // ---------------- LWE body ----------------
 
@@ -147,20 +145,13 @@ __global__ __launch_bounds__(kThreads) void tfhe_ggsw_add_gadget_kernel(W *__res
 template <class W>
 int launch_lwe_body_mac(W *lwe, const W *key, u32 dim, u64 batch, int subtract, const W *row_key, u32 ell, u32 log_basis,
                         u32 drop, hipStream_t s) {
-    const u64 grid = (batch + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (grid > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
-    hipLaunchKernelGGL(tfhe_lwe_body_mac_kernel<W>, dim3((u32)grid), dim3(kThreads), 0, s, lwe, key, dim, batch, subtract,
-                       row_key, ell, log_basis, drop);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_groups(tfhe_lwe_body_mac_kernel<W>, (batch + kWavesPerBlock - 1) / kWavesPerBlock, 0, s, lwe, key, dim, batch,
+                         subtract, row_key, ell, log_basis, drop);
 }
 
 template <class W, int U>
 int launch_glwe_u(W *glwe, const W *z, GlweMacShape sh, u32 tiles, u64 batch, int subtract, hipStream_t s) {
-    hipLaunchKernelGGL((tfhe_glwe_body_mac_kernel<W, U>), dim3((u32)batch, tiles), dim3(kThreads), sh.window * sizeof(W), s,
-                       glwe, z, sh, subtract);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_grid(tfhe_glwe_body_mac_kernel<W, U>, dim3((u32)batch, tiles), sh.window * sizeof(W), s, glwe, z, sh, subtract);
 }
 
 template <class W>
@@ -185,13 +176,7 @@ int launch_glwe_body_mac(W *glwe, const W *z, u32 k, u32 log_n, u64 batch, int s
 template <class W>
 int launch_gadget(W *ggsw, const W *msgs, u32 k, u32 log_n, u32 ell, u32 log_basis, u32 drop, u32 g, u64 count,
                   hipStream_t s) {
-    const u64 total = count * (k + 1) * ell;
-    const u64 grid = (total + kThreads - 1) / kThreads;
-    if (grid > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
-    hipLaunchKernelGGL(tfhe_ggsw_add_gadget_kernel<W>, dim3((u32)grid), dim3(kThreads), 0, s, ggsw, msgs, k, log_n, ell,
-                       log_basis, drop, g, total);
-    PFHE_HIP(hipGetLastError());
-    return PFHE_OK;
+    return launch_flat(tfhe_ggsw_add_gadget_kernel<W>, count * (k + 1) * ell, s, ggsw, msgs, k, log_n, ell, log_basis, drop, g);
 }
 
 inline int forward_torus(const pfhe_fft *f, const u64 *in, size_t len, double *out, hipStream_t s) {
@@ -238,17 +223,11 @@ int lwe_body_mac_host(int device, W *lwe, size_t len, size_t dimension, const W 
     if (len == 0) return PFHE_OK;
     if (!lwe || !key) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_TRY(capi_check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr;
-    PFHE_TRY(st.upload(lwe, len * sizeof(W), &a));
-    PFHE_TRY(st.upload(key, len_key * sizeof(W), &k));
-    PFHE_TRY(launch_lwe_body_mac<W>((W *)a, (const W *)k, (u32)dimension, len / (dimension + 1), subtract, nullptr, 1, 0, 0,
-                                    st.stream()));
-    PFHE_TRY(st.download(lwe, a, len * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_inout(lwe, len * sizeof(W)), stage_in(key, len_key * sizeof(W))};
+    return staged_call(device, bufs, [&](void *const *d, hipStream_t s) {
+        return launch_lwe_body_mac<W>((W *)d[0], (const W *)d[1], (u32)dimension, len / (dimension + 1), subtract, nullptr, 1, 0,
+                                      0, s);
+    });
 }
 
 template <class W>
@@ -285,22 +264,19 @@ int glwe_body_mac_host(const pfhe_fft *f, size_t k, W *glwe, size_t len, const W
     PFHE_TRY(glwe_body_check<W>(f, k, len, len_key));
     if (len == 0) return PFHE_OK;
     if (!glwe || !key) return PFHE_ERR_BAD_ARGUMENT;
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(f->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *z = nullptr;
-    PFHE_TRY(st.upload(glwe, len * sizeof(W), &a));
-    PFHE_TRY(st.upload(key, len_key * sizeof(W), &z));
-    PFHE_TRY(launch_glwe_body_mac<W>((W *)a, (const W *)z, (u32)k, f->log_n, len / ((k + 1) * f->n), subtract, st.stream()));
-    PFHE_TRY(st.download(glwe, a, len * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_inout(glwe, len * sizeof(W)), stage_in(key, len_key * sizeof(W))};
+    return staged_call(f->device, bufs, [&](void *const *d, hipStream_t s) {
+        return launch_glwe_body_mac<W>((W *)d[0], (const W *)d[1], (u32)k, f->log_n, len / ((k + 1) * f->n), subtract, s);
+    });
 }
 
 // the product plan's checks through the plan's own function, then what a GGSW needs beyond them
 template <class W>
 int ggsw_shape(const pfhe_fft *f, size_t k, uint32_t log_basis, size_t decompose_length, u32 &ell, u32 &drop) {
-    PFHE_TRY(tfhe_plan_check_args(8 * sizeof(W), f, k, log_basis, decompose_length, ell, drop));
+    Shape sh{};
+    PFHE_TRY(tfhe_plan_check<W>(f, k, log_basis, decompose_length, sh));
+    ell = sh.ell;
+    drop = sh.drop_bits;
     if (k == 0) {
         set_last_error("GGSW: glwe_dimension must be at least 1");
         return PFHE_ERR_BAD_ARGUMENT;

@@ -1,11 +1,15 @@
-// pfhe_tfhe_handles.hpp — what the torus-side handles own (pfhe_fft, the TFHE product plan, the two blind-rotation handles) and
-// the basis check they share.  Seen by pfhe_fft.hip, which implements them, and by pfhe_bootstrap.hip, whose bootstrap
-// handle is built around a blind-rotation handle, and by pfhe_keygen.hip, which writes the keys they consume.  Host only.
+// pfhe_tfhe_handles.hpp — what the torus-side handles own: the FFT table, the TFHE product plan, and the two blind
+// rotations behind the one interface the bootstrap handle holds (TfheRotation); and the argument checks their creates
+// share.  pfhe_fft.hip implements them; pfhe_bootstrap.hip sees a rotation only as a TfheRotation; pfhe_keygen.hip, which
+// writes the keys they consume, starts its GGSW calls with the plan's checks.  Host only; the host layer under the entry
+// points of all three is pfhe_tfhe_host.hpp.
 #pragma once
+
+#include <optional>
 
 #include "pfhe_capi_internal.hpp"
 #include "pfhe_plan_guard.hpp"
-#include "pfhe_staging.hpp"
+#include "pfhe_tfhe_host.hpp"
 
 struct pfhe_fft {
     int device = 0;
@@ -19,69 +23,104 @@ struct pfhe_fft {
     }
 };
 
-// TfheFftContext<T> + ApproxSignedBasis<T> (power-of-two modulus): the shape of the product and its device scratch.
-template <class W>
-struct TfhePlanCore {
-    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the plan)
-    pfhe::PlanGuard guard;          // one holder at a time (&mut TfheFftContext), successive calls ordered across streams
-    pfhe::u32 k = 1, log_basis = 0, ell = 0, drop_bits = 0;
-    size_t chunk = 1;
-    bool fused = false;
-    // general form only: digit spectra (chunk x (k+1) x ell x N/2), accumulators (chunk x (k+1) x N/2) and the key's
-    // Hermitian part ((k+1) x ell x (k+1) x N/2), complex f64
+// The device scratch of the general product, shared by the product plan and the per-group multi-bit rotation: digit spectra
+// (chunk x (k+1) x ell x N/2), accumulators (chunk x (k+1) x N/2) and the Hermitian parts of `key_copies` keys
+// ((k+1) x ell x (k+1) x N/2 each), complex f64.  All of it is allocated by create() or none.
+struct TfheProductScratch {
+    static constexpr size_t kDefaultBytes = 256ull << 20;
+    int device = 0;
     double2 *spec = nullptr, *acc = nullptr, *keyh = nullptr;
-    size_t scratch = 0;
-    ~TfhePlanCore() {
-        if (!fft) return;
-        pfhe::DeviceGuard g(fft->device);
+    size_t bytes = 0;
+
+    // Sizes `chunk` (0: the default — what fits kDefaultBytes of spectra and accumulators, or 65536 ciphertexts for a form
+    // that needs no scratch; never more than one launch's grid holds) and, when the form needs it, allocates the three
+    // buffers on the current device, which must be the table's.
+    int create(const pfhe_fft &f, const pfhe::Shape &sh, size_t key_copies, bool needed, size_t &chunk) {
+        const size_t m = f.n / 2, rows = sh.k + 1, digits = rows * sh.ell;
+        if (!chunk) chunk = needed ? std::max<size_t>(1, kDefaultBytes / ((digits + rows) * m * sizeof(double2))) : 65536;
+        chunk = std::min<size_t>(chunk, needed ? 0x7fffffffull / digits : 0x7fffffffull);
+        device = f.device;
+        if (!needed) return PFHE_OK;
+        const size_t sizes[] = {chunk * digits * m, chunk * rows * m, key_copies * digits * rows * m};
+        double2 **bufs[] = {&spec, &acc, &keyh};
+        for (int i = 0; i < 3; ++i) {
+            void *b = nullptr;
+            PFHE_HIP(pfhe::counted_malloc(&b, sizes[i] * sizeof(double2)));
+            *bufs[i] = (double2 *)b;
+            bytes += sizes[i] * sizeof(double2);
+        }
+        return PFHE_OK;
+    }
+    ~TfheProductScratch() {
+        if (!spec) return;
+        pfhe::DeviceGuard g(device);
         for (double2 *b : {spec, acc, keyh})
             if (b) (void)pfhe::counted_free(b);
     }
 };
+
+// TfheFftContext<T> + ApproxSignedBasis<T> (power-of-two modulus): the shape of the product and its device scratch (the
+// general form's; the fused form has none).
+template <class W>
+struct TfhePlanCore {
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the plan)
+    pfhe::PlanGuard guard;          // one holder at a time (&mut TfheFftContext), successive calls ordered across streams
+    pfhe::Shape shape{};
+    size_t chunk = 1;
+    bool fused = false;
+    TfheProductScratch scratch;
+};
 struct pfhe_tfhe_plan : TfhePlanCore<pfhe::u64> {};
 struct pfhe_tfhe32_plan : TfhePlanCore<pfhe::u32> {};
 
+// A blind rotation as the bootstrap handle sees it: the classic one or the multi-bit one.  rotate_dev is the handle's own
+// device call (its lease, checks and stream order), scratch_bytes what its create allocated.
+template <class W>
+struct TfheRotation {
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
+    pfhe::PlanGuard guard;          // one holder at a time and cross-stream ordering of successive calls, as the plan
+    bool whole_loop = false;
+    size_t chunk = 1, glwe = 0, key_len = 0;  // words of a ciphertext, complex values of one Fourier GGSW key
+    virtual ~TfheRotation() = default;
+    virtual int rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
+                           hipStream_t s) = 0;
+    virtual size_t scratch_bytes() const = 0;
+};
+
 // The blind rotation over the TFHE product: owns a product plan and, in the per-step form, three glue buffers of chunk
 // ciphertexts (D, E and the second accumulator of the ping-pong), all allocated at creation.
-template <class P, class W>
-struct TfheBlindRotCore {
-    P *plan = nullptr;     // owned
-    pfhe::PlanGuard guard; // one holder at a time and cross-stream ordering of successive calls, as the plan
-    bool whole_loop = false;
-    size_t chunk = 1;
+template <class W>
+struct TfheBlindRotCore : TfheRotation<W> {
+    TfhePlanCore<W> *plan = nullptr;                // owned
     W *d = nullptr, *e = nullptr, *ping = nullptr;  // per-step form only: chunk * (k+1) * N words each
-    size_t glwe = 0, key_len = 0, glue_bytes = 0;
-    ~TfheBlindRotCore() {
+    size_t glue_bytes = 0;
+    int rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
+                   hipStream_t s) override;
+    size_t scratch_bytes() const override { return plan->scratch.bytes + glue_bytes; }
+    ~TfheBlindRotCore() override {
         if (!plan) return;
         {
-            pfhe::DeviceGuard g(plan->fft->device);
+            pfhe::DeviceGuard g(this->fft->device);
             for (W *b : {d, e, ping})
                 if (b) (void)pfhe::counted_free(b);
         }
         delete plan;
     }
 };
-struct pfhe_tfhe_blindrot : TfheBlindRotCore<pfhe_tfhe_plan, pfhe::u64> {};
-struct pfhe_tfhe32_blindrot : TfheBlindRotCore<pfhe_tfhe32_plan, pfhe::u32> {};
+struct pfhe_tfhe_blindrot : TfheBlindRotCore<pfhe::u64> {};
+struct pfhe_tfhe32_blindrot : TfheBlindRotCore<pfhe::u32> {};
 
 // The multi-bit blind rotation: the mask is consumed grouping_factor elements at a time against 2^g keys per group.  Owns,
-// in the per-group form, the digit spectra and accumulators of `chunk` ciphertexts and the Hermitian parts of one group's
-// 2^g keys; nothing in the whole-loop form.  All allocated at creation.
+// in the per-group form, the product's scratch for `chunk` ciphertexts with the Hermitian parts of one group's 2^g keys;
+// nothing in the whole-loop form.  All allocated at creation.
 template <class W>
-struct TfheMultiBitCore {
-    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
-    pfhe::PlanGuard guard;          // one holder at a time and cross-stream ordering of successive calls, as the plan
-    pfhe::u32 k = 1, log_basis = 0, ell = 0, drop_bits = 0, g = 1;
-    bool whole_loop = false;
-    size_t chunk = 1, glwe = 0, key_len = 0, scratch = 0;
-    // per-group form only: chunk x (k+1) x ell x N/2, chunk x (k+1) x N/2 and 2^g x (k+1) x ell x (k+1) x N/2 complex f64
-    double2 *spec = nullptr, *acc = nullptr, *keyh = nullptr;
-    ~TfheMultiBitCore() {
-        if (!fft) return;
-        pfhe::DeviceGuard dg(fft->device);
-        for (double2 *b : {spec, acc, keyh})
-            if (b) (void)pfhe::counted_free(b);
-    }
+struct TfheMultiBitCore : TfheRotation<W> {
+    pfhe::Shape shape{};
+    pfhe::u32 g = 1;
+    TfheProductScratch scratch;
+    int rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
+                   hipStream_t s) override;
+    size_t scratch_bytes() const override { return scratch.bytes; }
 };
 struct pfhe_tfhe_mbrot : TfheMultiBitCore<pfhe::u64> {};
 struct pfhe_tfhe32_mbrot : TfheMultiBitCore<pfhe::u32> {};
@@ -105,38 +144,37 @@ inline int basis_shape(u32 bits, u32 log_basis, size_t length, u32 &ell, u32 &dr
     return PFHE_OK;
 }
 
-// The blind rotation's own create and device call (pfhe_fft.hip), as pfhe_tfhe{,32}_blindrot_create / _rotate_dev run them.
-int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                size_t chunk, pfhe_tfhe_blindrot **out);
-int tfhe_blindrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                size_t chunk, pfhe_tfhe32_blindrot **out);
-int tfhe_blindrot_rotate_handle(pfhe_tfhe_blindrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                                const uint32_t *exps, size_t len_exps, hipStream_t s);
-int tfhe_blindrot_rotate_handle(pfhe_tfhe32_blindrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                                const uint32_t *exps, size_t len_exps, hipStream_t s);
-
-// true when the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
-inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+// What pfhe_tfhe{,32}_plan_create decides before it touches the device, in its order: the basis's assert!s, glwe_dimension
+// above 64, the table.  The rotations' creates and pfhe_keygen.hip's GGSW calls start with the same checks.
+template <class W>
+int tfhe_plan_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, Shape &sh) {
+    u32 ell = 0, drop = 0;
+    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
+    if (glwe_dimension > kMaxGlweDimension) {
+        set_last_error("glwe_dimension above 64 is not supported");
+        return PFHE_ERR_UNSUPPORTED;
+    }
+    if (!fft) return PFHE_ERR_BAD_ARGUMENT;
+    sh = Shape{fft->log_n, (u32)glwe_dimension, log_basis, ell, drop};
+    return PFHE_OK;
 }
 
-// What pfhe_tfhe{,32}_plan_create decides before it touches the device, in its order (bits: 32 or 64): the basis's assert!s,
-// glwe_dimension above 64, the table; for pfhe_keygen.hip, whose GGSW calls start with the same checks.
-int tfhe_plan_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                         u32 &ell, u32 &drop);
+// ... and the multi-bit rotation's: the plan's checks, then the grouping factor, all before the device
+template <class W>
+int tfhe_mbrot_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                     size_t grouping_factor, Shape &sh) {
+    PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, sh));
+    if (grouping_factor == 0 || grouping_factor > kMaxGrouping) {
+        set_last_error("grouping_factor must be in 1..4");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    return PFHE_OK;
+}
 
-// The multi-bit rotation's create and device call (pfhe_fft.hip), as pfhe_tfhe{,32}_mbrot_create / _rotate_dev run them;
-// tfhe_mbrot_check_args is what the create decides before it touches the device (bits: 32 or 64).
-int tfhe_mbrot_check_args(u32 bits, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                          size_t grouping_factor);
-int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                             size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out);
-int tfhe_mbrot_create_handle(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                             size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out);
-int tfhe_mbrot_rotate_handle(pfhe_tfhe_mbrot *h, u64 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                             const uint32_t *exps, size_t len_exps, hipStream_t s);
-int tfhe_mbrot_rotate_handle(pfhe_tfhe32_mbrot *h, u32 *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                             const uint32_t *exps, size_t len_exps, hipStream_t s);
+// The rotation of a bootstrap handle (pfhe_fft.hip, instantiated for u32 and u64): what pfhe_tfhe{,32}_blindrot_create
+// runs when there is no grouping factor, pfhe_tfhe{,32}_mbrot_create with one.
+template <class W>
+int tfhe_rotation_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         std::optional<size_t> grouping_factor, size_t chunk, TfheRotation<W> **out);
 
 }  // namespace pfhe

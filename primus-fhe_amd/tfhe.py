@@ -70,6 +70,20 @@ def _dev_exps(t):
     return C.c_void_p(t.data_ptr()), t.numel()
 
 
+def _host_exps(exps):
+    """(pointer, count) of the exponents of a host form"""
+    if not isinstance(exps, np.ndarray) or exps.dtype != np.uint32 or not exps.flags.c_contiguous:
+        raise TypeError("expected a C-contiguous numpy uint32 array of exponents")
+    return exps.ctypes.data_as(C.c_void_p), exps.size
+
+
+def _same_width(message: str, *widths) -> str:
+    """the one width suffix of all the word arrays of a call (and of its context), or TypeError(message)"""
+    if len(set(widths)) != 1:
+        raise TypeError(message)
+    return widths[0]
+
+
 class FullComplex64FftTable:
     """primus_fft::FullComplex64FftTable — negacyclic torus FFT of N = 2^log_n (1 <= log_n <= 14), u32 and u64 words."""
 
@@ -150,40 +164,51 @@ class ApproxSignedBasis:
         return self.bits - self._length * self._log_basis
 
 
-class TfheFftContext:
-    """TfheFftContext<T> bundled with its basis and table (context/tfhe.rs): owns the device scratch of the product.  One
-    holder at a time: a call from a second thread while one is inside raises PfheError (Busy)."""
+class _TorusContext:
+    """What the four torus contexts share: the C handle, released with the object, and the sizes that follow from the table,
+    the basis and the GLWE dimension.  Every create starts with (table, glwe_dimension, log_basis, decompose_length) and
+    ends with the handle; `prefix` is what the context's calls start with, `calls` what its create, destroy, in-use and
+    scratch calls are named behind it."""
 
-    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1, chunk: int = 0):
+    def _open(self, fft, basis, glwe_dimension, prefix, args, calls=("create", "destroy", "in_use", "scratch_bytes")):
         self._w = "" if basis.bits == 64 else "32"
-        self._pre = "pfhe_tfhe" + self._w + "_"
+        self._pre = "pfhe_tfhe" + self._w + "_" + prefix
+        self._destroy, self._in_use, self._scratch = calls[1:]
         h = C.c_void_p()
-        check(getattr(lib(), self._pre + "plan_create")(fft._h, glwe_dimension, basis.log_basis(),
-                                                         basis.decompose_length(), chunk, C.byref(h)))
+        check(getattr(lib(), self._pre + calls[0])(fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(), *args,
+                                                   C.byref(h)))
         self._h = h
         self.fft, self.basis, self.glwe_dimension = fft, basis, glwe_dimension
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            getattr(lib(), self._pre + "plan_destroy")(h)
+            getattr(lib(), self._pre + self._destroy)(h)
             self._h = None
 
     def dtype(self):
         return np.uint64 if self.basis.bits == 64 else np.uint32
 
     def scratch_bytes(self) -> int:
-        return int(getattr(lib(), self._pre + "plan_scratch_bytes")(self._h))
+        return int(getattr(lib(), self._pre + self._scratch)(self._h))
 
     def in_use(self) -> bool:
-        return bool(getattr(lib(), self._pre + "plan_in_use")(self._h))
+        return bool(getattr(lib(), self._pre + self._in_use)(self._h))
 
     def glwe_len(self) -> int:
         return (self.glwe_dimension + 1) * self.fft.poly_length()
 
     def key_len(self) -> int:
-        """complex values of one Fourier GGSW key"""
+        """complex values of one Fourier GGSW key (one step of a rotation)"""
         return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
+
+
+class TfheFftContext(_TorusContext):
+    """TfheFftContext<T> bundled with its basis and table (context/tfhe.rs): owns the device scratch of the product.  One
+    holder at a time: a call from a second thread while one is inside raises PfheError (Busy)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1, chunk: int = 0):
+        self._open(fft, basis, glwe_dimension, "", (chunk,), ("plan_create", "plan_destroy", "plan_in_use", "plan_scratch_bytes"))
 
 
 def tfhe_external_product_to(inp: np.ndarray, key: np.ndarray, out: np.ndarray, ctx: TfheFftContext) -> None:
@@ -192,8 +217,7 @@ def tfhe_external_product_to(inp: np.ndarray, key: np.ndarray, out: np.ndarray, 
     pi, ni, wi = _host_words(inp)
     po, no, wo = _host_words(out)
     pk, nk = _host_fourier(key)
-    if wi != ctx._w or wo != ctx._w:
-        raise TypeError("input / output words must match the basis width")
+    _same_width("input / output words must match the basis width", wi, wo, ctx._w)
     check(getattr(lib(), ctx._pre + "external_product_to")(ctx._h, pi, ni, pk, nk, po, no))
 
 
@@ -202,47 +226,18 @@ def tfhe_external_product_to_dev(inp, key, out, ctx: TfheFftContext, stream=None
     pi, ni, wi = _dev_words(inp)
     po, no, wo = _dev_words(out)
     pk, nk = _dev_fourier(key)
-    if wi != ctx._w or wo != ctx._w:
-        raise TypeError("input / output words must match the basis width")
+    _same_width("input / output words must match the basis width", wi, wo, ctx._w)
     check(getattr(lib(), ctx._pre + "external_product_to_dev")(ctx._h, pi, ni, pk, nk, po, no, _stream(stream)))
 
 
-class TfheBlindRotateContext:
+class TfheBlindRotateContext(_TorusContext):
     """Handle of the batched blind rotation over the TFHE product (include/pfhe.h, pfhe_tfhe{,32}_blindrot_*): for every
     step i and ciphertext e, ACC_e += external_product_to(X^{exps[e*n_steps+i]} * ACC_e - ACC_e, BSK_i) on torus words.
     Owns a product plan and whatever glue buffers its form needs for `chunk` ciphertexts (0 = the default); one holder at
     a time (Busy for a second thread)."""
 
     def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1, chunk: int = 0):
-        self._w = "" if basis.bits == 64 else "32"
-        self._pre = "pfhe_tfhe" + self._w + "_blindrot_"
-        h = C.c_void_p()
-        check(getattr(lib(), self._pre + "create")(fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(),
-                                                   chunk, C.byref(h)))
-        self._h = h
-        self.fft, self.basis, self.glwe_dimension = fft, basis, glwe_dimension
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            getattr(lib(), self._pre + "destroy")(h)
-            self._h = None
-
-    def dtype(self):
-        return np.uint64 if self.basis.bits == 64 else np.uint32
-
-    def scratch_bytes(self) -> int:
-        return int(getattr(lib(), self._pre + "scratch_bytes")(self._h))
-
-    def in_use(self) -> bool:
-        return bool(getattr(lib(), self._pre + "in_use")(self._h))
-
-    def glwe_len(self) -> int:
-        return (self.glwe_dimension + 1) * self.fft.poly_length()
-
-    def key_len(self) -> int:
-        """complex values of one Fourier GGSW key (one step of the rotation)"""
-        return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
+        self._open(fft, basis, glwe_dimension, "blindrot_", (chunk,))
 
 
 def tfhe_blind_rotate(acc: np.ndarray, bsk: np.ndarray, exps: np.ndarray, ctx: TfheBlindRotateContext) -> None:
@@ -250,11 +245,9 @@ def tfhe_blind_rotate(acc: np.ndarray, bsk: np.ndarray, exps: np.ndarray, ctx: T
     bsk: n_steps Fourier GGSW keys end to end; exps: uint32, batch x n_steps, ciphertext-major, every exponent below 2N."""
     pa, na, wa = _host_words(acc)
     pk, nk = _host_fourier(bsk)
-    if wa != ctx._w:
-        raise TypeError("accumulator words must match the basis width")
-    if not isinstance(exps, np.ndarray) or exps.dtype != np.uint32 or not exps.flags.c_contiguous:
-        raise TypeError("expected a C-contiguous numpy uint32 array of exponents")
-    check(getattr(lib(), ctx._pre + "rotate")(ctx._h, pa, na, pk, nk, exps.ctypes.data_as(C.c_void_p), exps.size))
+    _same_width("accumulator words must match the basis width", wa, ctx._w)
+    pe, ne = _host_exps(exps)
+    check(getattr(lib(), ctx._pre + "rotate")(ctx._h, pa, na, pk, nk, pe, ne))
 
 
 def tfhe_blind_rotate_dev(acc, bsk, exps, ctx: TfheBlindRotateContext, stream=None) -> None:
@@ -263,12 +256,11 @@ def tfhe_blind_rotate_dev(acc, bsk, exps, ctx: TfheBlindRotateContext, stream=No
     pa, na, wa = _dev_words(acc)
     pk, nk = _dev_fourier(bsk)
     pe, ne = _dev_exps(exps)
-    if wa != ctx._w:
-        raise TypeError("accumulator words must match the basis width")
+    _same_width("accumulator words must match the basis width", wa, ctx._w)
     check(getattr(lib(), ctx._pre + "rotate_dev")(ctx._h, pa, na, pk, nk, pe, ne, _stream(stream)))
 
 
-class TfheMultiBitBlindRotateContext:
+class TfheMultiBitBlindRotateContext(_TorusContext):
     """Handle of the multi-bit blind rotation (include/pfhe.h, pfhe_tfhe{,32}_mbrot_*): the mask is consumed
     `grouping_factor` (1..4) elements at a time; for every group t and ciphertext e,
     ACC_e = external_product_to(ACC_e, sum_j X^{r_j} * BSK[t][j]) with r_j the subset sum of the group's exponents at the set
@@ -278,35 +270,9 @@ class TfheMultiBitBlindRotateContext:
 
     def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, grouping_factor: int, glwe_dimension: int = 1,
                  chunk: int = 0):
-        self._w = "" if basis.bits == 64 else "32"
-        self._pre = "pfhe_tfhe" + self._w + "_mbrot_"
-        h = C.c_void_p()
-        check(getattr(lib(), self._pre + "create")(fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(),
-                                                   grouping_factor, chunk, C.byref(h)))
-        self._h = h
-        self.fft, self.basis, self.glwe_dimension, self.grouping_factor = fft, basis, glwe_dimension, grouping_factor
+        self._open(fft, basis, glwe_dimension, "mbrot_", (grouping_factor, chunk))
+        self.grouping_factor = grouping_factor
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            getattr(lib(), self._pre + "destroy")(h)
-            self._h = None
-
-    def dtype(self):
-        return np.uint64 if self.basis.bits == 64 else np.uint32
-
-    def scratch_bytes(self) -> int:
-        return int(getattr(lib(), self._pre + "scratch_bytes")(self._h))
-
-    def in_use(self) -> bool:
-        return bool(getattr(lib(), self._pre + "in_use")(self._h))
-
-    def glwe_len(self) -> int:
-        return (self.glwe_dimension + 1) * self.fft.poly_length()
-
-    def key_len(self) -> int:
-        """complex values of one Fourier GGSW key"""
-        return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
 
     def group_len(self) -> int:
         """complex values of the 2^g keys of one group"""
@@ -319,11 +285,9 @@ def tfhe_multibit_blind_rotate(acc: np.ndarray, bsk: np.ndarray, exps: np.ndarra
     2N."""
     pa, na, wa = _host_words(acc)
     pk, nk = _host_fourier(bsk)
-    if wa != ctx._w:
-        raise TypeError("accumulator words must match the basis width")
-    if not isinstance(exps, np.ndarray) or exps.dtype != np.uint32 or not exps.flags.c_contiguous:
-        raise TypeError("expected a C-contiguous numpy uint32 array of exponents")
-    check(getattr(lib(), ctx._pre + "rotate")(ctx._h, pa, na, pk, nk, exps.ctypes.data_as(C.c_void_p), exps.size))
+    _same_width("accumulator words must match the basis width", wa, ctx._w)
+    pe, ne = _host_exps(exps)
+    check(getattr(lib(), ctx._pre + "rotate")(ctx._h, pa, na, pk, nk, pe, ne))
 
 
 def tfhe_multibit_blind_rotate_dev(acc, bsk, exps, ctx: TfheMultiBitBlindRotateContext, stream=None) -> None:
@@ -331,8 +295,7 @@ def tfhe_multibit_blind_rotate_dev(acc, bsk, exps, ctx: TfheMultiBitBlindRotateC
     pa, na, wa = _dev_words(acc)
     pk, nk = _dev_fourier(bsk)
     pe, ne = _dev_exps(exps)
-    if wa != ctx._w:
-        raise TypeError("accumulator words must match the basis width")
+    _same_width("accumulator words must match the basis width", wa, ctx._w)
     check(getattr(lib(), ctx._pre + "rotate_dev")(ctx._h, pa, na, pk, nk, pe, ne, _stream(stream)))
 
 
@@ -374,8 +337,7 @@ def glwe_sample_extract(glwe: np.ndarray, lwe: np.ndarray, fft: FullComplex64Fft
     (k+1)*N words -> batch LWE ciphertexts of k*N + 1 words under the GLWE key polynomials end to end."""
     pg, ng, wg = _host_words(glwe)
     po, no, wo = _host_words(lwe)
-    if wg != wo:
-        raise TypeError("glwe and lwe must have the same word width")
+    _same_width("glwe and lwe must have the same word width", wg, wo)
     check(getattr(lib(), "pfhe_tfhe" + wg + "_sample_extract")(fft._h, glwe_dimension, pg, ng, index, po, no))
 
 
@@ -384,8 +346,7 @@ def glwe_sample_extract_dev(glwe, lwe, fft: FullComplex64FftTable, glwe_dimensio
     """the device form; lwe must not overlap glwe"""
     pg, ng, wg = _dev_words(glwe)
     po, no, wo = _dev_words(lwe)
-    if wg != wo:
-        raise TypeError("glwe and lwe must have the same word width")
+    _same_width("glwe and lwe must have the same word width", wg, wo)
     check(getattr(lib(), "pfhe_tfhe" + wg + "_sample_extract_dev")(fft._h, glwe_dimension, pg, ng, index, po, no,
                                                                   _stream(stream)))
 
@@ -404,8 +365,7 @@ def lwe_keyswitch(lwe_in: np.ndarray, ksk: np.ndarray, lwe_out: np.ndarray, in_d
     pi, ni, wi = _host_words(lwe_in)
     pk, nk, wk = _host_words(ksk)
     po, no, wo = _host_words(lwe_out)
-    if not wi == wk == wo:
-        raise TypeError("lwe_in, ksk and lwe_out must have the same word width")
+    _same_width("lwe_in, ksk and lwe_out must have the same word width", wi, wk, wo)
     lb, ell = _basis_args(basis, wi)
     check(getattr(lib(), "pfhe_tfhe" + wi + "_keyswitch")(device, pi, ni, in_dimension, pk, nk, out_dimension, lb, ell, po, no))
 
@@ -416,14 +376,13 @@ def lwe_keyswitch_dev(lwe_in, ksk, lwe_out, in_dimension: int, out_dimension: in
     pi, ni, wi = _dev_words(lwe_in)
     pk, nk, wk = _dev_words(ksk)
     po, no, wo = _dev_words(lwe_out)
-    if not wi == wk == wo:
-        raise TypeError("lwe_in, ksk and lwe_out must have the same word width")
+    _same_width("lwe_in, ksk and lwe_out must have the same word width", wi, wk, wo)
     lb, ell = _basis_args(basis, wi)
     check(getattr(lib(), "pfhe_tfhe" + wi + "_keyswitch_dev")(_dev_index(lwe_in, device), pi, ni, in_dimension, pk, nk,
                                                              out_dimension, lb, ell, po, no, _stream(stream)))
 
 
-class TfheBootstrapContext:
+class TfheBootstrapContext(_TorusContext):
     """Handle of the batched programmable bootstrap (include/pfhe.h, pfhe_tfhe{,32}_bootstrap_*): modulus switch,
     ACC = X^{-b~} * TV, the blind rotation over lwe_dimension steps (grouping_factor above 1: the multi-bit rotation over
     lwe_dimension / grouping_factor groups, on the multi-bit key), sample extraction at index 0 and, when ks_basis is
@@ -432,43 +391,17 @@ class TfheBootstrapContext:
 
     def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int = 1,
                  ks_basis: ApproxSignedBasis | None = None, chunk: int = 0, grouping_factor: int = 1):
-        self._w = "" if basis.bits == 64 else "32"
-        self._pre = "pfhe_tfhe" + self._w + "_bootstrap"
         if ks_basis is not None and ks_basis.bits != basis.bits:
             raise TypeError("both bases must have the width of the torus words")
-        h = C.c_void_p()
-        args = (fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(), lwe_dimension,
-                ks_basis.log_basis() if ks_basis else 0, ks_basis.decompose_length() if ks_basis else 0, 1 if ks_basis else 0)
+        args = (lwe_dimension, ks_basis.log_basis() if ks_basis else 0, ks_basis.decompose_length() if ks_basis else 0,
+                1 if ks_basis else 0)
+        calls = ("_destroy", "_in_use", "_scratch_bytes")
         if grouping_factor == 1:
-            check(getattr(lib(), self._pre + "_create")(*args, chunk, C.byref(h)))
+            self._open(fft, basis, glwe_dimension, "bootstrap", args + (chunk,), ("_create",) + calls)
         else:   # the multi-bit rotation: bsk is (lwe_dimension / g) * 2^g keys
-            check(getattr(lib(), self._pre + "_create_multibit")(*args, grouping_factor, chunk, C.byref(h)))
-        self._h = h
-        self.grouping_factor = grouping_factor
-        self.fft, self.basis, self.ks_basis = fft, basis, ks_basis
-        self.glwe_dimension, self.lwe_dimension = glwe_dimension, lwe_dimension
+            self._open(fft, basis, glwe_dimension, "bootstrap", args + (grouping_factor, chunk), ("_create_multibit",) + calls)
+        self.grouping_factor, self.ks_basis, self.lwe_dimension = grouping_factor, ks_basis, lwe_dimension
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            getattr(lib(), self._pre + "_destroy")(h)
-            self._h = None
-
-    def dtype(self):
-        return np.uint64 if self.basis.bits == 64 else np.uint32
-
-    def scratch_bytes(self) -> int:
-        return int(getattr(lib(), self._pre + "_scratch_bytes")(self._h))
-
-    def in_use(self) -> bool:
-        return bool(getattr(lib(), self._pre + "_in_use")(self._h))
-
-    def glwe_len(self) -> int:
-        return (self.glwe_dimension + 1) * self.fft.poly_length()
-
-    def key_len(self) -> int:
-        """complex values of one Fourier GGSW key (one step of the rotation)"""
-        return (self.glwe_dimension + 1) * self.basis.decompose_length() * self.glwe_len()
 
     def bsk_len(self) -> int:
         """complex values of the whole bootstrapping key: lwe_dimension keys, or (lwe_dimension / g) * 2^g multi-bit keys"""
@@ -499,8 +432,7 @@ def tfhe_bootstrap(lwe_in: np.ndarray, bsk: np.ndarray, tv: np.ndarray, ksk, lwe
     pt, nt, wt = _host_words(tv)
     po, no, wo = _host_words(lwe_out)
     ps, ns, ws = _host_words(ksk) if ksk is not None else (None, 0, ctx._w)
-    if not wi == wt == wo == ws == ctx._w:
-        raise TypeError("every word array must have the width of the context's basis")
+    _same_width("every word array must have the width of the context's basis", wi, wt, wo, ws, ctx._w)
     check(getattr(lib(), ctx._pre)(ctx._h, pi, ni, pk, nk, pt, nt, ps, ns, po, no))
 
 
@@ -512,8 +444,7 @@ def tfhe_bootstrap_dev(lwe_in, bsk, tv, ksk, lwe_out, ctx: TfheBootstrapContext,
     pt, nt, wt = _dev_words(tv)
     po, no, wo = _dev_words(lwe_out)
     ps, ns, ws = _dev_words(ksk) if ksk is not None else (None, 0, ctx._w)
-    if not wi == wt == wo == ws == ctx._w:
-        raise TypeError("every word tensor must have the width of the context's basis")
+    _same_width("every word tensor must have the width of the context's basis", wi, wt, wo, ws, ctx._w)
     check(getattr(lib(), ctx._pre + "_dev")(ctx._h, pi, ni, pk, nk, pt, nt, ps, ns, po, no, _stream(stream)))
 
 
@@ -533,16 +464,14 @@ def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) 
 def _lwe_body(lwe, key, subtract: int, device: int) -> None:
     pl, nl, wl = _host_words(lwe)
     pk, nk, wk = _host_words(key)
-    if wl != wk:
-        raise TypeError("ciphertexts and key must have the same word width")
+    _same_width("ciphertexts and key must have the same word width", wl, wk)
     check(getattr(lib(), "pfhe_tfhe" + wl + "_lwe_body_mac")(device, pl, nl, nk, pk, nk, subtract))
 
 
 def _lwe_body_dev(lwe, key, subtract: int, device, stream) -> None:
     pl, nl, wl = _dev_words(lwe)
     pk, nk, wk = _dev_words(key)
-    if wl != wk:
-        raise TypeError("ciphertexts and key must have the same word width")
+    _same_width("ciphertexts and key must have the same word width", wl, wk)
     check(getattr(lib(), "pfhe_tfhe" + wl + "_lwe_body_mac_dev")(_dev_index(lwe, device), pl, nl, nk, pk, nk, subtract,
                                                                _stream(stream)))
 
@@ -571,16 +500,14 @@ def lwe_phase_dev(lwe, key, device=None, stream=None) -> None:
 def _glwe_body(glwe, key, fft, glwe_dimension: int, subtract: int) -> None:
     pg, ng, wg = _host_words(glwe)
     pk, nk, wk = _host_words(key)
-    if wg != wk:
-        raise TypeError("ciphertexts and key must have the same word width")
+    _same_width("ciphertexts and key must have the same word width", wg, wk)
     check(getattr(lib(), "pfhe_tfhe" + wg + "_glwe_body_mac")(fft._h, glwe_dimension, pg, ng, pk, nk, subtract))
 
 
 def _glwe_body_dev(glwe, key, fft, glwe_dimension: int, subtract: int, stream) -> None:
     pg, ng, wg = _dev_words(glwe)
     pk, nk, wk = _dev_words(key)
-    if wg != wk:
-        raise TypeError("ciphertexts and key must have the same word width")
+    _same_width("ciphertexts and key must have the same word width", wg, wk)
     check(getattr(lib(), "pfhe_tfhe" + wg + "_glwe_body_mac_dev")(fft._h, glwe_dimension, pg, ng, pk, nk, subtract,
                                                                 _stream(stream)))
 
@@ -613,8 +540,7 @@ def ggsw_add_gadget_dev(ggsw, messages, fft: FullComplex64FftTable, basis: Appro
     batch ((k+1) x ell x (k+1) x N words each), one message word per GGSW."""
     pg, ng, wg = _dev_words(ggsw)
     pm, nm, wm = _dev_words(messages)
-    if wg != wm:
-        raise TypeError("GGSWs and messages must have the same word width")
+    _same_width("GGSWs and messages must have the same word width", wg, wm)
     lb, ell = _basis_args(basis, wg)
     check(getattr(lib(), "pfhe_tfhe" + wg + "_ggsw_add_gadget_dev")(fft._h, glwe_dimension, lb, ell, pg, ng, pm, nm,
                                                                   _stream(stream)))
@@ -656,8 +582,7 @@ def tfhe_generate_bsk_dev(ctx_or_shape, lwe_key, glwe_key, rand, out=None, strea
     ps, ns, ws = _dev_words(lwe_key)
     pz, nz, wz = _dev_words(glwe_key)
     pr, nr, wr = _dev_words(rand)
-    if not ws == wz == wr:
-        raise TypeError("both keys and the randomness must have the same word width")
+    _same_width("both keys and the randomness must have the same word width", ws, wz, wr)
     lb, ell = _basis_args(sh.basis, wr)
     if out is None:
         out = torch.empty(nr, dtype=torch.complex128, device=rand.device)
@@ -674,8 +599,7 @@ def tfhe_generate_ksk_dev(key_in, key_out, basis: ApproxSignedBasis, rand, devic
     pi, ni, wi = _dev_words(key_in)
     po, no, wo = _dev_words(key_out)
     pr, nr, wr = _dev_words(rand)
-    if not wi == wo == wr:
-        raise TypeError("both keys and the randomness must have the same word width")
+    _same_width("both keys and the randomness must have the same word width", wi, wo, wr)
     lb, ell = _basis_args(basis, wr)
     check(getattr(lib(), "pfhe_tfhe" + wr + "_ksk_generate_dev")(_dev_index(rand, device), pi, ni, po, no, lb, ell, pr, nr,
                                                                _stream(stream)))
