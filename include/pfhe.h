@@ -1033,8 +1033,8 @@ int pfhe_tfhe32_modswitch_dev(int device, const uint32_t *lwe_dev, size_t len_lw
  * :264-288) applied to each of the k mask polynomials of a GLWE ciphertext (A_0..A_{k-1}, B): for index h < N the output LWE
  * has dimension k*N, out[j*N + i] = A_j[h - i] for i <= h and -A_j[N + h - i] for i > h (wrapping), out[k*N] = B[h]; its key
  * is the GLWE key polynomials end to end.  len_glwe = batch*(k+1)*N, len_lwe = batch*(k*N+1); 1 <= k <= 64 and index < N
- * (PFHE_ERR_BAD_ARGUMENT otherwise); the output must not overlap the input.  extract_first_few_lwe / MultiMsgLwe are not
- * mirrored. */
+ * (PFHE_ERR_BAD_ARGUMENT otherwise); the output must not overlap the input.  extract_first_few_lwe / MultiMsgLwe:
+ * pfhe_tfhe*_sample_extract_first_few and pfhe_tfhe*_multimsg_extract below. */
 int pfhe_tfhe_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
                                  size_t index, uint64_t *lwe_dev, size_t len_lwe, void *stream);
 int pfhe_tfhe_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe, size_t index,
@@ -1195,6 +1195,89 @@ int pfhe_tfhe_ksk_generate_dev(int device, const uint64_t *key_in_dev, size_t in
 int pfhe_tfhe32_ksk_generate_dev(int device, const uint32_t *key_in_dev, size_t in_dimension, const uint32_t *key_out_dev,
                                  size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *ksk_dev,
                                  size_t len_ksk, void *stream);
+
+/* ---- packing: LWE ciphertexts back into a GLWE, and multi-message extraction out of one (u64: no suffix, u32: 32) ----
+ * Exact integer arithmetic modulo 2^BITS on caller-filled buffers, as the key-generation calls above; no atomics, a call
+ * only queues work on `stream` (no allocation, no host synchronisation, no handle), and the table's device is the device.
+ *
+ * Packing key switch — no reference counterpart (the reference has none, as it has no bootstrap).  `count` LWE ciphertexts
+ * of dimension in_dimension become ONE GLWE ciphertext whose message polynomial holds their messages in coefficients
+ * 0 .. count-1 (the other coefficients carry no message).  With ell = decompose_length (0 = the full BITS / log_basis):
+ *   lwe_in    batch x count x (in_dimension+1) words: ciphertext i of group e is a then b, as pfhe_tfhe*_keyswitch takes them;
+ *   pksk      in_dimension x ell x (k+1) x N words: row (j, l) is one GLWE ciphertext (A_1..A_k, B) of
+ *             s_j * 2^(drop_bits + l*log_basis) on coefficient 0 under the output key, levels least significant first;
+ *   glwe_out  batch x (k+1) x N words, one GLWE per group; it may be uninitialised and must not overlap an input.
+ * Modulo 2^BITS and X^N + 1:
+ *   out_e = (0, ..., 0, sum_{i<count} b_{e,i} X^i) - sum_{i<count} X^i * sum_{j<in_dimension} sum_{l<ell} d_l(a_{e,i,j}) * pksk[j][l]
+ * with d_l the signed digits of ApproxSignedBasis exactly as pfhe_tfhe*_keyswitch_dev forms them (init_carry, decompose_iter,
+ * the carry from bit drop_bits-1, the log_basis 1 mask).  With count = 1, sample extraction at index 0 of the result is
+ * pfhe_tfhe*_keyswitch against the key whose rows are the index-0 extractions of the pksk rows, word for word.  A call is
+ * repeatable, and its result depends neither on the batch size nor on how the kernel tiles the work.
+ * Statuses, all before the device is touched: ApproxSignedBasis::new's assert!s (PFHE_ERR_BAD_ARGUMENT) as in
+ * pfhe_tfhe_keyswitch_dev; PFHE_ERR_BAD_ARGUMENT for glwe_dimension 0 or above 64 and in_dimension outside 1..2^31-2, for a
+ * null table, and for count outside 1..N; PFHE_ERR_BAD_LENGTH unless len_in = batch*count*(in_dimension+1),
+ * len_pksk = in_dimension*ell*(k+1)*N and len_out = batch*(k+1)*N; an empty batch is a no-op; then PFHE_ERR_BAD_ARGUMENT for
+ * a null pointer or an output that overlaps an input.  The f64 / FFT route (transform the digit polynomials, multiply into
+ * a Fourier key) is not built: it is approximate, and this call is exact. */
+int pfhe_tfhe_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in_dev, size_t len_in,
+                                 size_t in_dimension, size_t count, const uint64_t *pksk_dev, size_t len_pksk,
+                                 uint32_t log_basis, size_t decompose_length, uint64_t *glwe_out_dev, size_t len_out,
+                                 void *stream);
+int pfhe_tfhe_pack_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
+                             size_t in_dimension, size_t count, const uint64_t *pksk, size_t len_pksk, uint32_t log_basis,
+                             size_t decompose_length, uint64_t *glwe_out, size_t len_out);
+int pfhe_tfhe32_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in_dev, size_t len_in,
+                                   size_t in_dimension, size_t count, const uint32_t *pksk_dev, size_t len_pksk,
+                                   uint32_t log_basis, size_t decompose_length, uint32_t *glwe_out_dev, size_t len_out,
+                                   void *stream);
+int pfhe_tfhe32_pack_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
+                               size_t in_dimension, size_t count, const uint32_t *pksk, size_t len_pksk, uint32_t log_basis,
+                               size_t decompose_length, uint32_t *glwe_out, size_t len_out);
+/* The packing key in the layout pfhe_tfhe*_pack_keyswitch_dev takes — no reference counterpart.  pksk arrives holding the
+ * randomness of in_dimension x ell GLWE rows (mask polynomials uniform, body polynomials noise); row (j, l) becomes
+ *   B <- B + sum_r A_r * z_r + key_in[j] * 2^(drop_bits + l*log_basis)      (the last term on coefficient 0):
+ * the GLWE body call (add) on all rows under glwe_key (k*N words), then the message term.  Deterministic; a second call adds
+ * the body a second time.  Statuses as pfhe_tfhe*_ksk_generate_dev: ApproxSignedBasis::new's assert!s, then the dimensions
+ * (glwe_dimension in 1..64, in_dimension in 1..2^31-2) and the table, then PFHE_ERR_BAD_LENGTH unless len_glwe_key = k*N and
+ * len_pksk = in_dimension*ell*(k+1)*N, then null pointers and a key that overlaps pksk. */
+int pfhe_tfhe_pksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *key_in_dev, size_t in_dimension,
+                                const uint64_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis, size_t decompose_length,
+                                uint64_t *pksk_dev, size_t len_pksk, void *stream);
+int pfhe_tfhe32_pksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *key_in_dev, size_t in_dimension,
+                                  const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
+                                  size_t decompose_length, uint32_t *pksk_dev, size_t len_pksk, void *stream);
+/* Multi-message extraction — Rlwe::extract_first_few_lwe (primus_lattice/src/rlwe/coeff.rs:231-260) applied to each of the k
+ * mask polynomials: a GLWE ciphertext (A_0..A_{k-1}, B) becomes the MultiMsgLwe layout of k*N + count words,
+ *   multi[j*N] = A_j[0], multi[j*N + i] = -A_j[N - i] for 0 < i < N (wrapping), multi[k*N + h] = B[h] for h < count:
+ * the mask of the LWE ciphertext at index 0 once, and the first `count` bodies.  len_glwe = batch*(k+1)*N,
+ * len_multi = batch*(k*N+count).  The table, then 1 <= k <= 64 and 1 <= count <= N (PFHE_ERR_BAD_ARGUMENT), as
+ * pfhe_tfhe_sample_extract checks its table, dimension and index; then the lengths, the empty batch as a no-op, null
+ * pointers, and (device form) an output that overlaps the input. */
+int pfhe_tfhe_sample_extract_first_few_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
+                                           size_t count, uint64_t *multi_dev, size_t len_multi, void *stream);
+int pfhe_tfhe_sample_extract_first_few(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe,
+                                       size_t count, uint64_t *multi, size_t len_multi);
+int pfhe_tfhe32_sample_extract_first_few_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe_dev,
+                                             size_t len_glwe, size_t count, uint32_t *multi_dev, size_t len_multi,
+                                             void *stream);
+int pfhe_tfhe32_sample_extract_first_few(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe,
+                                         size_t count, uint32_t *multi, size_t len_multi);
+/* The expansion of that layout into `count` LWE ciphertexts of k*N + 1 words per group: ciphertext h is
+ * MultiMsgLwe::extract_rlwe_mode(dimension, h) (lwe/multiple_message.rs:250-263) per mask polynomial — the mask rotated
+ * right by h with its first h words negated, and the body b_h:
+ *   lwe[h][j*N + i] = -multi[j*N + N - h + i] for i < h, multi[j*N + i - h] otherwise;  lwe[h][k*N] = multi[k*N + h],
+ * which is pfhe_tfhe*_sample_extract at index h of the GLWE the layout came from, word for word.  len_multi =
+ * batch*(k*N+count), len_lwe = batch*count*(k*N+1); statuses as above.  The reference's extract_all is deliberately NOT
+ * mirrored: as written it builds its first ciphertext without a body slot and then indexes one past the end
+ * (multiple_message.rs:274-281). */
+int pfhe_tfhe_multimsg_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *multi_dev, size_t len_multi,
+                                   size_t count, uint64_t *lwe_dev, size_t len_lwe, void *stream);
+int pfhe_tfhe_multimsg_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *multi, size_t len_multi, size_t count,
+                               uint64_t *lwe, size_t len_lwe);
+int pfhe_tfhe32_multimsg_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *multi_dev, size_t len_multi,
+                                     size_t count, uint32_t *lwe_dev, size_t len_lwe, void *stream);
+int pfhe_tfhe32_multimsg_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *multi, size_t len_multi,
+                                 size_t count, uint32_t *lwe, size_t len_lwe);
 
 #ifdef __cplusplus
 }

@@ -1007,4 +1007,84 @@ inline void tfhe_generate_ksk_dev(int device, const uint32_t *key_in_dev, size_t
           ksk_dev, len_ksk, stream));
 }
 
+// Packing (pfhe_tfhe{,32}_pack_keyswitch*, _pksk_generate_dev, _sample_extract_first_few*, _multimsg_extract*): `count` LWE
+// ciphertexts per group into one GLWE under the packing key (in_dimension x ell GLWE rows, generated in place from the
+// caller's randomness), Rlwe::extract_first_few_lwe per mask polynomial (the MultiMsgLwe layout) and its expansion into
+// `count` LWE ciphertexts (MultiMsgLwe::extract_rlwe_mode at every index).  uint64_t overloads: the u64 torus; uint32_t: u32.
+inline void lwe_pack_keyswitch(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
+                               size_t in_dimension, size_t count, const uint64_t *pksk, size_t len_pksk, uint32_t log_basis,
+                               size_t decompose_length, uint64_t *glwe_out, size_t len_out) {
+    check(pfhe_tfhe_pack_keyswitch(fft.handle(), glwe_dimension, lwe_in, len_in, in_dimension, count, pksk, len_pksk, log_basis,
+          decompose_length, glwe_out, len_out));
+}
+inline void lwe_pack_keyswitch_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *lwe_in_dev, size_t len_in,
+                                   size_t in_dimension, size_t count, const uint64_t *pksk_dev, size_t len_pksk,
+                                   uint32_t log_basis, size_t decompose_length, uint64_t *glwe_out_dev, size_t len_out,
+                                   void *stream = nullptr) {
+    check(pfhe_tfhe_pack_keyswitch_dev(fft.handle(), glwe_dimension, lwe_in_dev, len_in, in_dimension, count, pksk_dev, len_pksk,
+          log_basis, decompose_length, glwe_out_dev, len_out, stream));
+}
+inline void tfhe_generate_pksk_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *key_in_dev,
+                                   size_t in_dimension, const uint64_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
+                                   size_t decompose_length, uint64_t *pksk_dev, size_t len_pksk, void *stream = nullptr) {
+    check(pfhe_tfhe_pksk_generate_dev(fft.handle(), glwe_dimension, key_in_dev, in_dimension, glwe_key_dev, len_glwe_key,
+          log_basis, decompose_length, pksk_dev, len_pksk, stream));
+}
+inline void glwe_sample_extract_first_few(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *glwe,
+                                          size_t len_glwe, size_t count, uint64_t *multi, size_t len_multi) {
+    check(pfhe_tfhe_sample_extract_first_few(fft.handle(), glwe_dimension, glwe, len_glwe, count, multi, len_multi));
+}
+inline void glwe_sample_extract_first_few_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *glwe_dev,
+                                              size_t len_glwe, size_t count, uint64_t *multi_dev, size_t len_multi,
+                                              void *stream = nullptr) {
+    check(pfhe_tfhe_sample_extract_first_few_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, count, multi_dev, len_multi,
+          stream));
+}
+inline void multimsg_lwe_extract(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *multi, size_t len_multi,
+                                 size_t count, uint64_t *lwe, size_t len_lwe) {
+    check(pfhe_tfhe_multimsg_extract(fft.handle(), glwe_dimension, multi, len_multi, count, lwe, len_lwe));
+}
+inline void multimsg_lwe_extract_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *multi_dev,
+                                     size_t len_multi, size_t count, uint64_t *lwe_dev, size_t len_lwe, void *stream = nullptr) {
+    check(pfhe_tfhe_multimsg_extract_dev(fft.handle(), glwe_dimension, multi_dev, len_multi, count, lwe_dev, len_lwe, stream));
+}
+
+inline void lwe_pack_keyswitch(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
+                               size_t in_dimension, size_t count, const uint32_t *pksk, size_t len_pksk, uint32_t log_basis,
+                               size_t decompose_length, uint32_t *glwe_out, size_t len_out) {
+    check(pfhe_tfhe32_pack_keyswitch(fft.handle(), glwe_dimension, lwe_in, len_in, in_dimension, count, pksk, len_pksk, log_basis,
+          decompose_length, glwe_out, len_out));
+}
+inline void lwe_pack_keyswitch_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *lwe_in_dev, size_t len_in,
+                                   size_t in_dimension, size_t count, const uint32_t *pksk_dev, size_t len_pksk,
+                                   uint32_t log_basis, size_t decompose_length, uint32_t *glwe_out_dev, size_t len_out,
+                                   void *stream = nullptr) {
+    check(pfhe_tfhe32_pack_keyswitch_dev(fft.handle(), glwe_dimension, lwe_in_dev, len_in, in_dimension, count, pksk_dev, len_pksk,
+          log_basis, decompose_length, glwe_out_dev, len_out, stream));
+}
+inline void tfhe_generate_pksk_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *key_in_dev,
+                                   size_t in_dimension, const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
+                                   size_t decompose_length, uint32_t *pksk_dev, size_t len_pksk, void *stream = nullptr) {
+    check(pfhe_tfhe32_pksk_generate_dev(fft.handle(), glwe_dimension, key_in_dev, in_dimension, glwe_key_dev, len_glwe_key,
+          log_basis, decompose_length, pksk_dev, len_pksk, stream));
+}
+inline void glwe_sample_extract_first_few(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *glwe,
+                                          size_t len_glwe, size_t count, uint32_t *multi, size_t len_multi) {
+    check(pfhe_tfhe32_sample_extract_first_few(fft.handle(), glwe_dimension, glwe, len_glwe, count, multi, len_multi));
+}
+inline void glwe_sample_extract_first_few_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *glwe_dev,
+                                              size_t len_glwe, size_t count, uint32_t *multi_dev, size_t len_multi,
+                                              void *stream = nullptr) {
+    check(pfhe_tfhe32_sample_extract_first_few_dev(fft.handle(), glwe_dimension, glwe_dev, len_glwe, count, multi_dev, len_multi,
+          stream));
+}
+inline void multimsg_lwe_extract(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *multi, size_t len_multi,
+                                 size_t count, uint32_t *lwe, size_t len_lwe) {
+    check(pfhe_tfhe32_multimsg_extract(fft.handle(), glwe_dimension, multi, len_multi, count, lwe, len_lwe));
+}
+inline void multimsg_lwe_extract_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *multi_dev,
+                                     size_t len_multi, size_t count, uint32_t *lwe_dev, size_t len_lwe, void *stream = nullptr) {
+    check(pfhe_tfhe32_multimsg_extract_dev(fft.handle(), glwe_dimension, multi_dev, len_multi, count, lwe_dev, len_lwe, stream));
+}
+
 }  // namespace pfhe

@@ -19,7 +19,9 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    tfhe_multibit_blind_rotate, tfhe_multibit_blind_rotate_dev, tfhe_multibit_combine_key_dev,
                    write_fourier_form, TfheKeyShape, ggsw_add_gadget_dev, glwe_encrypt, glwe_encrypt_dev, glwe_phase,
                    glwe_phase_dev, lwe_encrypt, lwe_encrypt_dev, lwe_phase, lwe_phase_dev, tfhe_generate_bsk_dev,
-                   tfhe_generate_ksk_dev, torus_noise, torus_uniform)
+                   tfhe_generate_ksk_dev, torus_noise, torus_uniform, lwe_pack_keyswitch, lwe_pack_keyswitch_dev,
+                   tfhe_generate_pksk_dev, glwe_sample_extract_first_few, glwe_sample_extract_first_few_dev,
+                   multimsg_lwe_extract, multimsg_lwe_extract_dev)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -35,4 +37,6 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "TfheMultiBitBlindRotateContext", "tfhe_multibit_blind_rotate", "tfhe_multibit_blind_rotate_dev",
            "tfhe_multibit_combine_key_dev", "lwe_encrypt", "lwe_encrypt_dev", "lwe_phase", "lwe_phase_dev", "glwe_encrypt",
            "glwe_encrypt_dev", "glwe_phase", "glwe_phase_dev", "ggsw_add_gadget_dev", "TfheKeyShape", "tfhe_generate_bsk_dev",
-           "tfhe_generate_ksk_dev", "torus_uniform", "torus_noise", "build", "lib", "library_path", "status_string"]
+           "tfhe_generate_ksk_dev", "torus_uniform", "torus_noise", "lwe_pack_keyswitch",
+           "lwe_pack_keyswitch_dev", "tfhe_generate_pksk_dev", "glwe_sample_extract_first_few",
+           "glwe_sample_extract_first_few_dev", "multimsg_lwe_extract", "multimsg_lwe_extract_dev", "build", "lib", "library_path", "status_string"]

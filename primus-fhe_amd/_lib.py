@@ -224,6 +224,14 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "ggsw_add_gadget_dev", ci, vp, sz, u32, sz, vp, sz, vp, sz, vp)
         sig(tp + "bsk_generate_dev", ci, vp, sz, u32, sz, sz, vp, sz, vp, sz, vp, sz, f64p, sz, vp)
         sig(tp + "ksk_generate_dev", ci, ci, vp, sz, vp, sz, u32, sz, vp, sz, vp)
+        # packing: the LWE-to-GLWE key switch, its key, and the multi-message extraction with its expansion
+        sig(tp + "pack_keyswitch_dev", ci, vp, sz, vp, sz, sz, sz, vp, sz, u32, sz, vp, sz, vp)
+        sig(tp + "pack_keyswitch", ci, vp, sz, vp, sz, sz, sz, vp, sz, u32, sz, vp, sz)
+        sig(tp + "pksk_generate_dev", ci, vp, sz, vp, sz, vp, sz, u32, sz, vp, sz, vp)
+        sig(tp + "sample_extract_first_few_dev", ci, vp, sz, vp, sz, sz, vp, sz, vp)
+        sig(tp + "sample_extract_first_few", ci, vp, sz, vp, sz, sz, vp, sz)
+        sig(tp + "multimsg_extract_dev", ci, vp, sz, vp, sz, sz, vp, sz, vp)
+        sig(tp + "multimsg_extract", ci, vp, sz, vp, sz, sz, vp, sz)
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)

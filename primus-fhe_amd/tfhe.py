@@ -605,6 +605,89 @@ def tfhe_generate_ksk_dev(key_in, key_out, basis: ApproxSignedBasis, rand, devic
                                                                _stream(stream)))
 
 
+# ---- packing: LWE ciphertexts back into a GLWE, and multi-message extraction (include/pfhe.h: pack_keyswitch, pksk_generate,
+# sample_extract_first_few, multimsg_extract) ----
+
+def lwe_pack_keyswitch(lwe_in: np.ndarray, pksk: np.ndarray, glwe_out: np.ndarray, in_dimension: int, count: int,
+                       fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1) -> None:
+    """Packing key switch on host arrays: every group of `count` LWE ciphertexts (in_dimension+1 words each) becomes one GLWE
+    ciphertext whose message polynomial holds their messages in coefficients 0..count-1,
+    out = (0, .., 0, sum_i b_i X^i) - sum_i X^i sum_j sum_l d_l(a_{i,j}) * pksk[j][l] modulo 2^BITS and X^N + 1, d the
+    signed digits of `basis`; pksk is in_dimension x ell x (k+1) x N words, row (j, l) a GLWE ciphertext of
+    s_j * 2^(drop_bits + l*log_basis) under the output key, levels least significant first.  1 <= count <= N."""
+    pi, ni, wi = _host_words(lwe_in)
+    pk, nk, wk = _host_words(pksk)
+    po, no, wo = _host_words(glwe_out)
+    _same_width("lwe_in, pksk and glwe_out must have the same word width", wi, wk, wo)
+    lb, ell = _basis_args(basis, wi)
+    check(getattr(lib(), "pfhe_tfhe" + wi + "_pack_keyswitch")(fft._h, glwe_dimension, pi, ni, in_dimension, count, pk, nk, lb,
+                                                              ell, po, no))
+
+
+def lwe_pack_keyswitch_dev(lwe_in, pksk, glwe_out, in_dimension: int, count: int, fft: FullComplex64FftTable,
+                           basis: ApproxSignedBasis, glwe_dimension: int = 1, stream=None) -> None:
+    """the device form, asynchronous and stateless; glwe_out must not overlap an input and may be uninitialised"""
+    pi, ni, wi = _dev_words(lwe_in)
+    pk, nk, wk = _dev_words(pksk)
+    po, no, wo = _dev_words(glwe_out)
+    _same_width("lwe_in, pksk and glwe_out must have the same word width", wi, wk, wo)
+    lb, ell = _basis_args(basis, wi)
+    check(getattr(lib(), "pfhe_tfhe" + wi + "_pack_keyswitch_dev")(fft._h, glwe_dimension, pi, ni, in_dimension, count, pk, nk,
+                                                                  lb, ell, po, no, _stream(stream)))
+
+
+def tfhe_generate_pksk_dev(key_in, glwe_key, fft: FullComplex64FftTable, basis: ApproxSignedBasis, rand,
+                           glwe_dimension: int = 1, stream=None) -> None:
+    """The packing key lwe_pack_keyswitch_dev takes, from key_in (len(key_in) words) to glwe_key (the k key polynomials end
+    to end), generated in place in rand: len(key_in) x ell GLWE rows of (k+1)*N words holding the randomness (mask
+    polynomials uniform, body polynomials noise); row (j, l) becomes B += sum_r A_r * z_r, and
+    key_in[j] * 2^(drop_bits + l*log_basis) on coefficient 0.  A second call adds the body a second time.  Asynchronous."""
+    pi, ni, wi = _dev_words(key_in)
+    pz, nz, wz = _dev_words(glwe_key)
+    pr, nr, wr = _dev_words(rand)
+    _same_width("both keys and the randomness must have the same word width", wi, wz, wr)
+    lb, ell = _basis_args(basis, wr)
+    check(getattr(lib(), "pfhe_tfhe" + wr + "_pksk_generate_dev")(fft._h, glwe_dimension, pi, ni, pz, nz, lb, ell, pr, nr,
+                                                                _stream(stream)))
+
+
+def _extract_pair(name, src, dst, fft, count, glwe_dimension, dev, stream=None):
+    ps, ns, ws = (_dev_words if dev else _host_words)(src)
+    pd, nd, wd = (_dev_words if dev else _host_words)(dst)
+    _same_width("input and output must have the same word width", ws, wd)
+    tail = (_stream(stream),) if dev else ()
+    check(getattr(lib(), "pfhe_tfhe" + ws + name + ("_dev" if dev else ""))(fft._h, glwe_dimension, ps, ns, count, pd, nd,
+                                                                           *tail))
+
+
+def glwe_sample_extract_first_few(glwe: np.ndarray, out: np.ndarray, fft: FullComplex64FftTable, count: int,
+                                  glwe_dimension: int = 1) -> None:
+    """Rlwe::extract_first_few_lwe (rlwe/coeff.rs:231-260) per mask polynomial, on host arrays: batch GLWE ciphertexts of
+    (k+1)*N words -> batch MultiMsgLwe layouts of k*N + count words, each mask polynomial as [a_0, -a_{N-1}, ..., -a_1],
+    then b_0 .. b_{count-1}."""
+    _extract_pair("_sample_extract_first_few", glwe, out, fft, count, glwe_dimension, False)
+
+
+def glwe_sample_extract_first_few_dev(glwe, out, fft: FullComplex64FftTable, count: int, glwe_dimension: int = 1,
+                                      stream=None) -> None:
+    """the device form; out must not overlap glwe"""
+    _extract_pair("_sample_extract_first_few", glwe, out, fft, count, glwe_dimension, True, stream)
+
+
+def multimsg_lwe_extract(multi: np.ndarray, lwe_out: np.ndarray, fft: FullComplex64FftTable, count: int,
+                         glwe_dimension: int = 1) -> None:
+    """MultiMsgLwe::extract_rlwe_mode (lwe/multiple_message.rs:250-263) for every index h < count, on host arrays: batch
+    layouts of k*N + count words -> batch x count LWE ciphertexts of k*N + 1 words; ciphertext h equals
+    glwe_sample_extract(..., index=h) of the GLWE the layout came from."""
+    _extract_pair("_multimsg_extract", multi, lwe_out, fft, count, glwe_dimension, False)
+
+
+def multimsg_lwe_extract_dev(multi, lwe_out, fft: FullComplex64FftTable, count: int, glwe_dimension: int = 1,
+                             stream=None) -> None:
+    """the device form; lwe_out must not overlap multi"""
+    _extract_pair("_multimsg_extract", multi, lwe_out, fft, count, glwe_dimension, True, stream)
+
+
 def _torus_dtype(bits: int):
     import torch
     if bits not in (32, 64):
