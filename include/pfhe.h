@@ -793,6 +793,11 @@ int pfhe_extprod32_plan_create(const pfhe_dcrt32 *table, const pfhe_rns32 *base,
 void pfhe_extprod32_plan_destroy(pfhe_extprod32_plan *plan);
 int pfhe_extprod32_plan_in_use(const pfhe_extprod32_plan *plan);
 size_t pfhe_extprod32_plan_scratch_bytes(const pfhe_extprod32_plan *plan);
+/* Precondition of every pfhe_extprod32_* product below: all u32 operands are CANONICAL — each word of the GLWE / CRT
+ * polynomials, of the GGSW / GLev key and of an accumulator that a call adds to is below its modulus q_i (< 2^30).  The
+ * kernels sum products of such words lazily in 64 bits and fold once per fifteen terms: fifteen products below 2^60 on a
+ * folded value stay below 2^64 with nothing to spare, so a word of q_i or more can wrap the sum silently (the reference
+ * reduces after every term and would not).  Nothing checks this on the way in. */
 /* CrtGlwe::mul_dcrt_ggsw_to — glwe/crt.rs:200-227 (layouts as pfhe_extprod_mul_dcrt_ggsw_to) */
 int pfhe_extprod32_mul_dcrt_ggsw_to(pfhe_extprod32_plan *plan, const uint32_t *crt_glwe, size_t len_glwe,
                                     const uint32_t *dcrt_ggsw, size_t len_ggsw, uint32_t *result, size_t len_result,

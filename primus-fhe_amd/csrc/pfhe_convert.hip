@@ -8,8 +8,8 @@
 // L_in contiguous 512-byte rows), scales each by (Q/q_i)^-1 mod q_i, and produces every output
 // residue as a modular dot product against the row (Q/q_i) mod p_j.  The reference's coefficient-
 // major scratch array never exists: the scaled residues stay in registers.  Arithmetic follows the
-// reference step by step (128-bit accumulation of the dot product, one BarrettModulus::reduce,
-// barrett/mod.rs:99-139), so results are identical, not merely congruent.
+// reference step by step (128-bit accumulation of the dot product in chunks of 16, BarrettModulus::reduce
+// of each, barrett/mod.rs:99-139), so results are identical, not merely congruent.
 // exact_convert_array is the only floating-point code near this path: f64 quotients temp_i / q_i
 // (IEEE division, correctly rounded on gfx950 as in Rust), summed left to right, (sum + 0.5) as u64.
 #include <memory>
@@ -69,14 +69,27 @@ u32 grid_for(u64 items) {
     return (u32)g;
 }
 
-// reduce_dot_product (compact/slice.rs:380-405): one 128-bit accumulator (overflow discarded like the reference's
-// carrying_add), reduce, reduce_add(., 0).  The reference folds the accumulator every DOT_PRODUCT_INNER_CHUNK = 16 terms;
-// a sum of up to 32 products below 2^124 cannot overflow 128 bits, and the value reduced is the same integer.
+// reduce_dot_product (compact/slice.rs:380-405): a 128-bit accumulator, reduce, reduce_add.  A product of two residues is
+// below 2^124, so kDotChunk = 16 of them (DOT_PRODUCT_INNER_CHUNK, compact/mod.rs:14) stay below 2^128 and 17 need not:
+// 32 moduli just below 2^62 with every scaled residue q_i - 1 sum to more than 2^128 (tests/test_gpu_accumulator_bounds.py,
+// test_converter_at_the_accumulator_bound).  So, like the reference, the accumulator is folded after term 16 into a running
+// residue and restarts from zero; barrett_reduce128 is exact for any 128-bit value.  The fold is a branch on the unrolled
+// loop's constant index in the instantiations with more than 16 scaled residues only: the by-value form and ConvWide<8>,
+// ConvWide<16> compile to the code they had without it (profiles/accbound_a_convert_kernel_identity.txt).
+constexpr int kDotChunk = 16;
 template <class CT>
 __device__ __forceinline__ u64 dot_mod(const CT &C, u32 j, const u64 (&t)[CT::kScaled]) {
+    static_assert(CT::kScaled <= 2 * kDotChunk, "one fold covers at most two chunks");
     u64 lo = 0, hi = 0;
+    [[maybe_unused]] u64 folded = 0;
 #pragma unroll
     for (int i = 0; i < CT::kScaled; ++i) {
+        if constexpr (CT::kScaled > kDotChunk) {
+            if (i == kDotChunk) {
+                folded = barrett_reduce128(lo, hi, C.p_out(j), C.ratio_lo(j), C.ratio_hi(j));
+                lo = hi = 0;
+            }
+        }
         if ((u32)i < C.lin) {
             const u64 m = C.matrix(j, i);
             const u64 pl = t[i] * m, ph = mulhi64(t[i], m);
@@ -84,7 +97,9 @@ __device__ __forceinline__ u64 dot_mod(const CT &C, u32 j, const u64 (&t)[CT::kS
             hi += ph + (lo < pl);
         }
     }
-    return add_mod(barrett_reduce128(lo, hi, C.p_out(j), C.ratio_lo(j), C.ratio_hi(j)), 0, C.p_out(j));
+    const u64 last = barrett_reduce128(lo, hi, C.p_out(j), C.ratio_lo(j), C.ratio_hi(j));
+    if constexpr (CT::kScaled > kDotChunk) return add_mod(last, folded, C.p_out(j));
+    else return add_mod(last, 0, C.p_out(j));
 }
 
 template <class CT, class WT>

@@ -22,7 +22,9 @@ namespace {
 
 // modular multiply-accumulate policies matching the NTT arithmetic policies
 // acc + d*k without folding: a product term is < 1.5 * 2^K (K <= 61), so an accumulator folded below
-// 2^K + 2^(K-9) can take FOUR terms before it must be folded again (1.002 + 4 * 1.5 = 7.002 < 8 = 2^64 / 2^61)
+// 2^K + 2^(K-9) can take FOUR terms before it must be folded again (1.002 + 4 * 1.5 = 7.002 < 8 = 2^64 / 2^61).
+// Pinned with every digit_hat and key word at its maximum, on a fold and with one to three terms pending, for the prime
+// with the largest admissible c too: tests/test_gpu_accumulator_bounds.py [block-pm-*], [small-pm-*].
 __device__ __forceinline__ u64 mac(const PmArith &ar, u64 acc, u64 d, u64 k) {
     return acc + ar.mul_full(d, k);
 }
@@ -139,7 +141,8 @@ __global__ __launch_bounds__(LOGE == 3 ? 512 : 256, LOGE == 3 ? kMulacc8MinWaves
                         acc[c][j].y = ar.reduce_x(acc[c][j].y);
                     }
                 } else {
-                    // the lazy transform leaves digit_hat in [0,4q): Barrett takes any product < q*2^64
+                    // the lazy transform leaves digit_hat in [0,4q): Barrett takes any 64-bit factor (tests/test_modmath_host.py;
+                    // all-(q - 1) digit polynomials and keys: test_gpu_accumulator_bounds.py [block-mont], [block-shoup62])
                     const BarrettMac m{P->q, P->bar_lo, P->bar_hi};
                     acc[c][j].x = mac(m, acc[c][j].x, io[j].x, kv[j].x);
                     acc[c][j].y = mac(m, acc[c][j].y, io[j].y, kv[j].y);
@@ -162,7 +165,8 @@ __global__ __launch_bounds__(LOGE == 3 ? 512 : 256, LOGE == 3 ? kMulacc8MinWaves
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
                 if constexpr (std::is_same<A, PmArith>::value) {
-                    // pending terms < 5.5 * 2^K, old < 2^K: the sum fits 64 bits and is folded below
+                    // pending terms < 5.5 * 2^K, old < 2^K: the sum fits 64 bits and is folded below (three terms pending
+                    // on an accumulator of q - 1: test_gpu_accumulator_bounds.py [block-pm-*], the row call of 7 levels)
                     acc[c][j].x += old[j].x;
                     acc[c][j].y += old[j].y;
                 } else {

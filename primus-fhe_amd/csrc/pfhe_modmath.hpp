@@ -42,9 +42,13 @@ PFHE_HD u64 sub_mod(u64 a, u64 b, u64 q) {
     return min_u64(d, d + q);
 }
 
-// (hi:lo) mod q, canonical, for hi:lo < q * 2^64 (always true for a*b+c with a,b,c < q < 2^62).
-// mu = floor(2^128/q) as (mu_hi:mu_lo).  Quotient estimate = floor((hi:lo)*mu / 2^128) is at
-// most 1 short of the true quotient, so one conditional subtraction finishes.
+// (hi:lo) mod q, canonical, for ANY 128-bit hi:lo and 2 <= q < 2^62.  mu = floor(2^128/q) as (mu_hi:mu_lo).
+// qhat is floor((hi:lo)*mu / 2^128) exactly (the word dropped from lo*mu_lo lies below every carry that is kept), which is
+// the true quotient or one short of it, so lo - qhat*q is the remainder or the remainder + q and one conditional
+// subtraction finishes.  Above q * 2^64 (dot_mod hands in sums up to 2^128 - 1, gadget_mulacc_kernel sums up to 2^127)
+// the quotient no longer fits 64 bits and qhat holds its low word only; that is all the 64-bit product qhat*q needs, since
+// the result is below 2q < 2^64.  Pinned on the host over the whole range — both sides of q * 2^64, multiples of q up to
+// the largest below 2^128, random words — by tests/test_modmath_host.py.
 PFHE_HD u64 barrett_reduce128(u64 lo, u64 hi, u64 q, u64 mu_lo, u64 mu_hi) {
     // carries into the top word only
     u64 a_hi = mulhi64(lo, mu_lo);

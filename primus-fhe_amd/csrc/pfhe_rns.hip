@@ -236,7 +236,10 @@ __global__ __launch_bounds__(kThreads) void gadget_mulacc_kernel(const NttPrime 
         const u64 pl = d * g, ph = mulhi64(d, g);
         lo += pl;
         hi += ph + (lo < pl);
-        if ((ij & 7u) == 7u) {  // 8 products of residues < 2^62 stay below 2^127: fold before the next 8
+        // a folded value < 2^62 and 8 products of residues < 2^62 stay below 2^127 (and the last, partial group plus the
+        // accumulating call's old word do): fold before the next 8.  barrett_reduce128 takes any 128-bit value.  Pinned at
+        // q - 1 everywhere with 0 to 7 terms pending by tests/test_gpu_accumulator_bounds.py [mulacc-*].
+        if ((ij & 7u) == 7u) {
             lo = barrett_reduce128(lo, hi, P->q, P->bar_lo, P->bar_hi);
             hi = 0;
         }
