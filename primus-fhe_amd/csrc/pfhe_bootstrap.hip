@@ -9,8 +9,8 @@
 //   blind rotation     the classic or the multi-bit handle (pfhe_fft.hip) behind TfheRotation, called as it is.
 //   sample extraction  Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial.
 //   key switch         out = (0, b) - sum_i sum_j d_{i,j} KSK[i][j], a sequence of Lwe::add_mul_scalar_assign
-//                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_step of
-//                      pfhe_fft_device.hpp, the product's own).
+//                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_word of
+//                      pfhe_fft_device.hpp, over the product's own digit_step).
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
 // host forms go through pfhe_tfhe_host.hpp; the key switch keeps its own 2-D grid.
 #include <algorithm>
@@ -131,14 +131,8 @@ __global__ __launch_bounds__(kThreads) void tfhe_keyswitch_kernel(const W *__res
             const bool live = e0 + ei < batch && i0 + ii < s.in_dim;
             const W v = live ? lwe_in[(e0 + ei) * in_stride + i0 + ii] : (W)0;
             u32 carry = init_carry(v, s.drop_bits);
-            for (u32 l = 0; l < s.ell; ++l) {
-                const u32 shift = s.drop_bits + l * s.log_basis;
-                const W field = (v >> shift) & (((W)1 << s.log_basis) - 1);
-                const W carry_in = (W)carry;
-                (void)digit_step(v, shift, s.log_basis, carry);  // the rule: it decides the carry out of this level
-                // the digit as a word: field + carry_in - carry_out * B, which is digit_step's value for any log_basis
-                dig[(ii * s.ell + l) * kKsTileM + ei] = field + carry_in - ((W)carry << s.log_basis);
-            }
+            for (u32 l = 0; l < s.ell; ++l)
+                dig[(ii * s.ell + l) * kKsTileM + ei] = digit_word(v, s.drop_bits + l * s.log_basis, s.log_basis, carry);
         }
         __syncthreads();
         const u32 rows = min(s.ki, s.in_dim - i0) * s.ell;
@@ -207,13 +201,11 @@ int launch_sample_extract(const W *glwe, W *lwe, u32 k, u32 log_n, u32 h, u64 ba
 template <class W>
 int launch_keyswitch(const W *lwe_in, const W *ksk, W *lwe_out, KsShape sh, u64 batch, hipStream_t s) {
     const u64 gx = ((u64)sh.out_dim + 1 + kKsTileN - 1) / kKsTileN;
-    for (u64 done = 0; done < batch;) {  // grid.y holds 65535 tiles
-        const u64 cur = std::min<u64>(batch - done, (u64)65535 * kKsTileM);
-        PFHE_TRY(launch_grid(tfhe_keyswitch_kernel<W>, dim3((u32)gx, (u32)((cur + kKsTileM - 1) / kKsTileM)), 0, s,
-                             lwe_in + done * ((u64)sh.in_dim + 1), ksk, lwe_out + done * ((u64)sh.out_dim + 1), sh, cur));
-        done += cur;
-    }
-    return PFHE_OK;
+    return launch_y_slices((batch + kKsTileM - 1) / kKsTileM, [&](u64 first_tile, u32 tiles) {
+        const u64 done = first_tile * kKsTileM, cur = std::min<u64>(batch - done, (u64)tiles * kKsTileM);
+        return launch_grid(tfhe_keyswitch_kernel<W>, dim3((u32)gx, tiles), 0, s, lwe_in + done * ((u64)sh.in_dim + 1), ksk,
+                           lwe_out + done * ((u64)sh.out_dim + 1), sh, cur);
+    });
 }
 
 // ---------------- the stateless entry points ----------------
@@ -235,57 +227,37 @@ int modswitch_dev(int device, const W *lwe, size_t len_lwe, size_t lwe_dimension
         return PFHE_ERR_BAD_LENGTH;
     }
     if (len_lwe == 0) return PFHE_OK;
-    if (!lwe || !exps || !neg_b) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_TRY(capi_check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_modswitch<W>(lwe, (u32)lwe_dimension, log_n, exps, neg_b, len_neg_b, s);
+    // no overlap message: this step refuses none
+    const StageBuf bufs[] = {stage_in(lwe, len_lwe * sizeof(W)), stage_out(exps, len_exps * sizeof(u32)),
+                             stage_out(neg_b, len_neg_b * sizeof(u32))};
+    return stateless_call(
+        device, Form::kDevice, bufs, nullptr, s,
+        [&](void *const *d, hipStream_t st) {
+            return launch_modswitch<W>((const W *)d[0], (u32)lwe_dimension, log_n, (u32 *)d[1], (u32 *)d[2], len_neg_b, st);
+        },
+        [&] { return capi_check_device(device); });
 }
 
-constexpr const char *kExtractLengths = "sample extraction: glwe must be batch*(k+1)*N words and lwe batch*(k*N+1)";
-
 template <class W>
-int sample_extract_check(const pfhe_fft *f, size_t k, size_t len_glwe, size_t index, size_t len_lwe) {
+int sample_extract(Form form, const pfhe_fft *f, size_t k, const W *glwe, size_t len_glwe, size_t index, W *lwe, size_t len_lwe,
+                   hipStream_t s) {
     if (!f) return PFHE_ERR_BAD_ARGUMENT;
-    if (k == 0 || k > 64) {
-        set_last_error("sample extraction: glwe_dimension must be in 1..64");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    PFHE_TRY(require_glwe_dimension(k, "sample extraction: glwe_dimension must be in 1..64"));
     if (index >= f->n) {
         set_last_error("sample extraction: index must be below N");
         return PFHE_ERR_BAD_ARGUMENT;
     }
     if (len_glwe % ((k + 1) * f->n) != 0 || len_lwe != len_glwe / ((k + 1) * f->n) * (k * f->n + 1)) {
-        set_last_error(kExtractLengths);
+        set_last_error("sample extraction: glwe must be batch*(k+1)*N words and lwe batch*(k*N+1)");
         return PFHE_ERR_BAD_LENGTH;
     }
-    return PFHE_OK;
-}
-
-template <class W>
-int sample_extract_dev(const pfhe_fft *f, size_t k, const W *glwe, size_t len_glwe, size_t index, W *lwe, size_t len_lwe,
-                       hipStream_t s) {
-    PFHE_TRY(sample_extract_check<W>(f, k, len_glwe, index, len_lwe));
     if (len_glwe == 0) return PFHE_OK;
-    if (!glwe || !lwe) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(glwe, len_glwe * sizeof(W), lwe, len_lwe * sizeof(W))) {
-        set_last_error("sample extraction: the output must not overlap the input");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_sample_extract<W>(glwe, lwe, (u32)k, f->log_n, (u32)index, len_glwe / ((k + 1) * f->n), s);
-}
-
-template <class W>
-int sample_extract_host(const pfhe_fft *f, size_t k, const W *glwe, size_t len_glwe, size_t index, W *lwe, size_t len_lwe) {
-    PFHE_TRY(sample_extract_check<W>(f, k, len_glwe, index, len_lwe));
-    if (len_glwe == 0) return PFHE_OK;
-    if (!glwe || !lwe) return PFHE_ERR_BAD_ARGUMENT;
     const StageBuf bufs[] = {stage_in(glwe, len_glwe * sizeof(W)), stage_out(lwe, len_lwe * sizeof(W))};
-    return staged_call(f->device, bufs, [&](void *const *d, hipStream_t s) {
-        return sample_extract_dev<W>(f, k, (const W *)d[0], len_glwe, index, (W *)d[1], len_lwe, s);
-    });
+    return stateless_call(f->device, form, bufs, "sample extraction: the output must not overlap the input", s,
+                          [&](void *const *d, hipStream_t st) {
+                              return launch_sample_extract<W>((const W *)d[0], (W *)d[1], (u32)k, f->log_n, (u32)index,
+                                                              len_glwe / ((k + 1) * f->n), st);
+                          });
 }
 
 // ApproxSignedBasis::new's assert!s first, then the dimensions
@@ -293,10 +265,8 @@ template <class W>
 int keyswitch_shape(size_t in_dimension, size_t out_dimension, uint32_t log_basis, size_t decompose_length, KsShape &sh) {
     u32 ell = 0, drop = 0;
     PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
-    if (in_dimension == 0 || out_dimension == 0 || in_dimension >= 0x7fffffffull || out_dimension >= 0x7fffffffull) {
-        set_last_error("key switch: both dimensions must be in 1..2^31-2");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    PFHE_TRY(require_lwe_dimension(in_dimension, "key switch: both dimensions must be in 1..2^31-2"));
+    PFHE_TRY(require_lwe_dimension(out_dimension, "key switch: both dimensions must be in 1..2^31-2"));
     sh = KsShape{(u32)in_dimension, (u32)out_dimension, log_basis, ell, drop,
                  std::max<u32>(1, std::min<u32>(kKsMaxRows / ell, kThreads / kKsTileM))};
     return PFHE_OK;
@@ -317,37 +287,19 @@ int keyswitch_check(size_t len_in, size_t in_dimension, size_t len_ksk, size_t o
 }
 
 template <class W>
-int keyswitch_dev(int device, const W *lwe_in, size_t len_in, size_t in_dimension, const W *ksk, size_t len_ksk,
-                  size_t out_dimension, uint32_t log_basis, size_t decompose_length, W *lwe_out, size_t len_out,
-                  hipStream_t s) {
+int keyswitch(Form form, int device, const W *lwe_in, size_t len_in, size_t in_dimension, const W *ksk, size_t len_ksk,
+              size_t out_dimension, uint32_t log_basis, size_t decompose_length, W *lwe_out, size_t len_out, hipStream_t s) {
     KsShape sh{};
     PFHE_TRY(keyswitch_check<W>(len_in, in_dimension, len_ksk, out_dimension, log_basis, decompose_length, len_out, sh));
     if (len_in == 0) return PFHE_OK;
-    if (!lwe_in || !ksk || !lwe_out) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(lwe_in, len_in * sizeof(W), lwe_out, len_out * sizeof(W)) ||
-        overlaps(ksk, len_ksk * sizeof(W), lwe_out, len_out * sizeof(W))) {
-        set_last_error("key switch: the output must not overlap an input");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    PFHE_TRY(capi_check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_keyswitch<W>(lwe_in, ksk, lwe_out, sh, len_in / (in_dimension + 1), s);
-}
-
-template <class W>
-int keyswitch_host(int device, const W *lwe_in, size_t len_in, size_t in_dimension, const W *ksk, size_t len_ksk,
-                   size_t out_dimension, uint32_t log_basis, size_t decompose_length, W *lwe_out, size_t len_out) {
-    KsShape sh{};
-    PFHE_TRY(keyswitch_check<W>(len_in, in_dimension, len_ksk, out_dimension, log_basis, decompose_length, len_out, sh));
-    if (len_in == 0) return PFHE_OK;
-    if (!lwe_in || !ksk || !lwe_out) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_TRY(capi_check_device(device));
     const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(ksk, len_ksk * sizeof(W)),
                              stage_out(lwe_out, len_out * sizeof(W))};
-    return staged_call(device, bufs, [&](void *const *d, hipStream_t s) {
-        return launch_keyswitch<W>((const W *)d[0], (const W *)d[1], (W *)d[2], sh, len_in / (in_dimension + 1), s);
-    });
+    return stateless_call(
+        device, form, bufs, "key switch: the output must not overlap an input", s,
+        [&](void *const *d, hipStream_t st) {
+            return launch_keyswitch<W>((const W *)d[0], (const W *)d[1], (W *)d[2], sh, len_in / (in_dimension + 1), st);
+        },
+        [&] { return capi_check_device(device); });
 }
 
 }  // namespace
@@ -413,10 +365,9 @@ int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
     h->k = (u32)glwe_dimension;
     h->with_keyswitch = with_keyswitch != 0;
     const size_t glwe = rot.glwe, ext = glwe_dimension * fft->n + 1;
-    if (glwe_dimension == 0 || lwe_dimension == 0 || lwe_dimension >= 0x7fffffffull) {
-        set_last_error("TFHE bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    // a zero glwe_dimension is refused as a zero lwe_dimension is: one message for both
+    PFHE_TRY(require_lwe_dimension(glwe_dimension ? lwe_dimension : 0,
+                                   "TFHE bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2"));
     h->n = (u32)lwe_dimension;
     const size_t keys = grouping_factor ? (lwe_dimension / *grouping_factor) << *grouping_factor : lwe_dimension;
     h->bsk_len = keys * rot.key_len;
@@ -545,26 +496,28 @@ int pfhe_tfhe32_modswitch_dev(int device, const uint32_t *lwe_dev, size_t len_lw
 int pfhe_tfhe_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
                                  size_t index, uint64_t *lwe_dev, size_t len_lwe, void *stream) {
     PFHE_GUARD_BEGIN
-    return sample_extract_dev<u64>(fft, glwe_dimension, (const u64 *)glwe_dev, len_glwe, index, (u64 *)lwe_dev, len_lwe,
-                                   (hipStream_t)stream);
+    return sample_extract<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)glwe_dev, len_glwe, index, (u64 *)lwe_dev,
+                               len_lwe, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe, size_t index,
                              uint64_t *lwe, size_t len_lwe) {
     PFHE_GUARD_BEGIN
-    return sample_extract_host<u64>(fft, glwe_dimension, (const u64 *)glwe, len_glwe, index, (u64 *)lwe, len_lwe);
+    return sample_extract<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)glwe, len_glwe, index, (u64 *)lwe, len_lwe,
+                               nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe_dev, size_t len_glwe,
                                    size_t index, uint32_t *lwe_dev, size_t len_lwe, void *stream) {
     PFHE_GUARD_BEGIN
-    return sample_extract_dev<u32>(fft, glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe, (hipStream_t)stream);
+    return sample_extract<u32>(Form::kDevice, fft, glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe,
+                               (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe, size_t index,
                                uint32_t *lwe, size_t len_lwe) {
     PFHE_GUARD_BEGIN
-    return sample_extract_host<u32>(fft, glwe_dimension, glwe, len_glwe, index, lwe, len_lwe);
+    return sample_extract<u32>(Form::kHost, fft, glwe_dimension, glwe, len_glwe, index, lwe, len_lwe, nullptr);
     PFHE_GUARD_END
 }
 
@@ -572,32 +525,32 @@ int pfhe_tfhe_keyswitch_dev(int device, const uint64_t *lwe_in_dev, size_t len_i
                             size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length,
                             uint64_t *lwe_out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return keyswitch_dev<u64>(device, (const u64 *)lwe_in_dev, len_in, in_dimension, (const u64 *)ksk_dev, len_ksk,
-                              out_dimension, log_basis, decompose_length, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
+    return keyswitch<u64>(Form::kDevice, device, (const u64 *)lwe_in_dev, len_in, in_dimension, (const u64 *)ksk_dev, len_ksk,
+                          out_dimension, log_basis, decompose_length, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_keyswitch(int device, const uint64_t *lwe_in, size_t len_in, size_t in_dimension, const uint64_t *ksk,
                         size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *lwe_out,
                         size_t len_out) {
     PFHE_GUARD_BEGIN
-    return keyswitch_host<u64>(device, (const u64 *)lwe_in, len_in, in_dimension, (const u64 *)ksk, len_ksk, out_dimension,
-                               log_basis, decompose_length, (u64 *)lwe_out, len_out);
+    return keyswitch<u64>(Form::kHost, device, (const u64 *)lwe_in, len_in, in_dimension, (const u64 *)ksk, len_ksk,
+                          out_dimension, log_basis, decompose_length, (u64 *)lwe_out, len_out, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_keyswitch_dev(int device, const uint32_t *lwe_in_dev, size_t len_in, size_t in_dimension,
                               const uint32_t *ksk_dev, size_t len_ksk, size_t out_dimension, uint32_t log_basis,
                               size_t decompose_length, uint32_t *lwe_out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return keyswitch_dev<u32>(device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension, log_basis,
-                              decompose_length, lwe_out_dev, len_out, (hipStream_t)stream);
+    return keyswitch<u32>(Form::kDevice, device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension, log_basis,
+                          decompose_length, lwe_out_dev, len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_keyswitch(int device, const uint32_t *lwe_in, size_t len_in, size_t in_dimension, const uint32_t *ksk,
                           size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *lwe_out,
                           size_t len_out) {
     PFHE_GUARD_BEGIN
-    return keyswitch_host<u32>(device, lwe_in, len_in, in_dimension, ksk, len_ksk, out_dimension, log_basis, decompose_length,
-                               lwe_out, len_out);
+    return keyswitch<u32>(Form::kHost, device, lwe_in, len_in, in_dimension, ksk, len_ksk, out_dimension, log_basis,
+                          decompose_length, lwe_out, len_out, nullptr);
     PFHE_GUARD_END
 }
 

@@ -107,6 +107,16 @@ template <class W>
 __device__ __forceinline__ u32 init_carry(W v, u32 drop_bits) {
     return drop_bits ? (u32)((v >> (drop_bits - 1)) & 1) : 0u;
 }
+// One signed digit of v as a word modulo 2^BITS, for the key switches that multiply digits as integers; levels are walked
+// least significant first, from carry = init_carry(v, drop_bits).  digit_step is the rule and is called for the carry it
+// decides only: the digit as a word is field + carry_in - carry_out * B, which is digit_step's value for any log_basis.
+template <class W>
+__device__ __forceinline__ W digit_word(W v, u32 shift, u32 log_basis, u32 &carry) {
+    const W field = (v >> shift) & (((W)1 << log_basis) - 1);
+    const W carry_in = (W)carry;
+    (void)digit_step(v, shift, log_basis, carry);
+    return field + carry_in - ((W)carry << log_basis);
+}
 
 struct Shape {
     u32 log_n, k, log_basis, ell, drop_bits;

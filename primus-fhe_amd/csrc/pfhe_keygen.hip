@@ -189,85 +189,40 @@ inline int forward_torus(const pfhe_fft *f, const u32 *in, size_t len, double *o
 // ---------------- the entry points ----------------
 
 template <class W>
-int lwe_body_check(size_t len, size_t dimension, size_t len_key) {
-    if (dimension == 0 || dimension >= 0x7fffffffull) {
-        set_last_error("LWE body: dimension must be in 1..2^31-2");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+int lwe_body_mac(Form form, int device, W *lwe, size_t len, size_t dimension, const W *key, size_t len_key, int subtract,
+                 hipStream_t s) {
+    PFHE_TRY(require_lwe_dimension(dimension, "LWE body: dimension must be in 1..2^31-2"));
     if (len_key != dimension || len % (dimension + 1) != 0) {
         set_last_error("LWE body: lwe must be batch*(dimension+1) words and key dimension words");
         return PFHE_ERR_BAD_LENGTH;
     }
-    return PFHE_OK;
-}
-
-template <class W>
-int lwe_body_mac_dev(int device, W *lwe, size_t len, size_t dimension, const W *key, size_t len_key, int subtract,
-                     hipStream_t s) {
-    PFHE_TRY(lwe_body_check<W>(len, dimension, len_key));
     if (len == 0) return PFHE_OK;
-    if (!lwe || !key) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(lwe, len * sizeof(W), key, len_key * sizeof(W))) {
-        set_last_error("LWE body: the key must not overlap the ciphertexts");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    PFHE_TRY(capi_check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_lwe_body_mac<W>(lwe, key, (u32)dimension, len / (dimension + 1), subtract, nullptr, 1, 0, 0, s);
-}
-
-template <class W>
-int lwe_body_mac_host(int device, W *lwe, size_t len, size_t dimension, const W *key, size_t len_key, int subtract) {
-    PFHE_TRY(lwe_body_check<W>(len, dimension, len_key));
-    if (len == 0) return PFHE_OK;
-    if (!lwe || !key) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_TRY(capi_check_device(device));
     const StageBuf bufs[] = {stage_inout(lwe, len * sizeof(W)), stage_in(key, len_key * sizeof(W))};
-    return staged_call(device, bufs, [&](void *const *d, hipStream_t s) {
-        return launch_lwe_body_mac<W>((W *)d[0], (const W *)d[1], (u32)dimension, len / (dimension + 1), subtract, nullptr, 1, 0,
-                                      0, s);
-    });
+    return stateless_call(
+        device, form, bufs, "LWE body: the key must not overlap the ciphertexts", s,
+        [&](void *const *d, hipStream_t st) {
+            return launch_lwe_body_mac<W>((W *)d[0], (const W *)d[1], (u32)dimension, len / (dimension + 1), subtract, nullptr,
+                                          1, 0, 0, st);
+        },
+        [&] { return capi_check_device(device); });
 }
 
 template <class W>
-int glwe_body_check(const pfhe_fft *f, size_t k, size_t len, size_t len_key) {
+int glwe_body_mac(Form form, const pfhe_fft *f, size_t k, W *glwe, size_t len, const W *key, size_t len_key, int subtract,
+                  hipStream_t s) {
     if (!f) return PFHE_ERR_BAD_ARGUMENT;
-    if (k == 0 || k > kMaxGlweDimension) {
-        set_last_error("GLWE body: glwe_dimension must be in 1..64");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    PFHE_TRY(require_glwe_dimension(k, "GLWE body: glwe_dimension must be in 1..64"));
     if (len_key != k * f->n || len % ((k + 1) * f->n) != 0) {
         set_last_error("GLWE body: glwe must be batch*(k+1)*N words and key k*N words");
         return PFHE_ERR_BAD_LENGTH;
     }
-    return PFHE_OK;
-}
-
-template <class W>
-int glwe_body_mac_dev(const pfhe_fft *f, size_t k, W *glwe, size_t len, const W *key, size_t len_key, int subtract,
-                      hipStream_t s) {
-    PFHE_TRY(glwe_body_check<W>(f, k, len, len_key));
     if (len == 0) return PFHE_OK;
-    if (!glwe || !key) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(glwe, len * sizeof(W), key, len_key * sizeof(W))) {
-        set_last_error("GLWE body: the key must not overlap the ciphertexts");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_glwe_body_mac<W>(glwe, key, (u32)k, f->log_n, len / ((k + 1) * f->n), subtract, s);
-}
-
-template <class W>
-int glwe_body_mac_host(const pfhe_fft *f, size_t k, W *glwe, size_t len, const W *key, size_t len_key, int subtract) {
-    PFHE_TRY(glwe_body_check<W>(f, k, len, len_key));
-    if (len == 0) return PFHE_OK;
-    if (!glwe || !key) return PFHE_ERR_BAD_ARGUMENT;
     const StageBuf bufs[] = {stage_inout(glwe, len * sizeof(W)), stage_in(key, len_key * sizeof(W))};
-    return staged_call(f->device, bufs, [&](void *const *d, hipStream_t s) {
-        return launch_glwe_body_mac<W>((W *)d[0], (const W *)d[1], (u32)k, f->log_n, len / ((k + 1) * f->n), subtract, s);
-    });
+    return stateless_call(f->device, form, bufs, "GLWE body: the key must not overlap the ciphertexts", s,
+                          [&](void *const *d, hipStream_t st) {
+                              return launch_glwe_body_mac<W>((W *)d[0], (const W *)d[1], (u32)k, f->log_n,
+                                                             len / ((k + 1) * f->n), subtract, st);
+                          });
 }
 
 // the product plan's checks through the plan's own function, then what a GGSW needs beyond them
@@ -295,14 +250,12 @@ int ggsw_add_gadget_dev(const pfhe_fft *f, size_t k, uint32_t log_basis, size_t 
         return PFHE_ERR_BAD_LENGTH;
     }
     if (len == 0) return PFHE_OK;
-    if (!ggsw || !msgs) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(ggsw, len * sizeof(W), msgs, len_msgs * sizeof(W))) {
-        set_last_error("GGSW gadget: the messages must not overlap the GGSWs");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_gadget<W>(ggsw, msgs, (u32)k, f->log_n, ell, log_basis, drop, 0, len_msgs, s);
+    const StageBuf bufs[] = {stage_inout(ggsw, len * sizeof(W)), stage_in(msgs, len_msgs * sizeof(W))};
+    return stateless_call(f->device, Form::kDevice, bufs, "GGSW gadget: the messages must not overlap the GGSWs", s,
+                          [&](void *const *d, hipStream_t st) {
+                              return launch_gadget<W>((W *)d[0], (const W *)d[1], (u32)k, f->log_n, ell, log_basis, drop, 0,
+                                                      len_msgs, st);
+                          });
 }
 
 template <class W>
@@ -315,10 +268,7 @@ int bsk_generate_dev(const pfhe_fft *f, size_t k, uint32_t log_basis, size_t dec
         set_last_error("bootstrapping key: grouping_factor must be 0 (the classic layout) or in 1..4");
         return PFHE_ERR_BAD_ARGUMENT;
     }
-    if (n == 0 || n >= 0x7fffffffull) {
-        set_last_error("bootstrapping key: lwe_dimension must be in 1..2^31-2");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    PFHE_TRY(require_lwe_dimension(n, "bootstrapping key: lwe_dimension must be in 1..2^31-2"));
     if (grouping && n % grouping != 0) {
         set_last_error("bootstrapping key: lwe_dimension must be a multiple of grouping_factor");
         return PFHE_ERR_BAD_ARGUMENT;
@@ -330,22 +280,20 @@ int bsk_generate_dev(const pfhe_fft *f, size_t k, uint32_t log_basis, size_t dec
                        "many complex values, keys = n or (n/g)*2^g");
         return PFHE_ERR_BAD_LENGTH;
     }
-    if (!lwe_key || !glwe_key || !ggsw || !bsk) return PFHE_ERR_BAD_ARGUMENT;
+    const StageBuf bufs[] = {stage_in(lwe_key, n * sizeof(W)), stage_in(glwe_key, len_glwe_key * sizeof(W)),
+                             stage_inout(ggsw, len_ggsw * sizeof(W)), stage_out(bsk, len_bsk * 2 * sizeof(double))};
+    PFHE_TRY(refuse_null(bufs));  // ahead of the tail's own: the alignment is judged between the null and the overlap test
     PFHE_REQUIRE_ALIGNED(ggsw);
     PFHE_REQUIRE_ALIGNED(bsk);
-    const size_t ggsw_bytes = len_ggsw * sizeof(W), bsk_bytes = len_bsk * 2 * sizeof(double);
-    if (overlaps(ggsw, ggsw_bytes, bsk, bsk_bytes) || overlaps(ggsw, ggsw_bytes, lwe_key, n * sizeof(W)) ||
-        overlaps(ggsw, ggsw_bytes, glwe_key, len_glwe_key * sizeof(W)) || overlaps(bsk, bsk_bytes, lwe_key, n * sizeof(W)) ||
-        overlaps(bsk, bsk_bytes, glwe_key, len_glwe_key * sizeof(W))) {
-        set_last_error("bootstrapping key: the outputs must overlap neither each other nor a key");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    if (keys * rows > 0x7fffffffull || len_ggsw / f->n > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    PFHE_TRY(launch_glwe_body_mac<W>(ggsw, glwe_key, (u32)k, f->log_n, keys * rows, 0, s));
-    PFHE_TRY(launch_gadget<W>(ggsw, lwe_key, (u32)k, f->log_n, ell, log_basis, drop, (u32)grouping, keys, s));
-    return forward_torus(f, ggsw, len_ggsw, bsk, s);
+    return stateless_call(
+        f->device, Form::kDevice, bufs, "bootstrapping key: the outputs must overlap neither each other nor a key", s,
+        [&](void *const *d, hipStream_t st) {
+            PFHE_TRY(launch_glwe_body_mac<W>((W *)d[2], (const W *)d[1], (u32)k, f->log_n, keys * rows, 0, st));
+            PFHE_TRY(launch_gadget<W>((W *)d[2], (const W *)d[0], (u32)k, f->log_n, ell, log_basis, drop, (u32)grouping, keys,
+                                      st));
+            return forward_torus(f, (const W *)d[2], len_ggsw, (double *)d[3], st);
+        },
+        [&] { return keys * rows > 0x7fffffffull || len_ggsw / f->n > 0x7fffffffull ? PFHE_ERR_BAD_LENGTH : PFHE_OK; });
 }
 
 template <class W>
@@ -353,24 +301,21 @@ int ksk_generate_dev(int device, const W *key_in, size_t in_dimension, const W *
                      uint32_t log_basis, size_t decompose_length, W *ksk, size_t len, hipStream_t s) {
     u32 ell = 0, drop = 0;
     PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
-    if (in_dimension == 0 || out_dimension == 0 || in_dimension >= 0x7fffffffull || out_dimension >= 0x7fffffffull) {
-        set_last_error("key-switch key: both dimensions must be in 1..2^31-2");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    PFHE_TRY(require_lwe_dimension(in_dimension, "key-switch key: both dimensions must be in 1..2^31-2"));
+    PFHE_TRY(require_lwe_dimension(out_dimension, "key-switch key: both dimensions must be in 1..2^31-2"));
     if (len != in_dimension * ell * (out_dimension + 1)) {
         set_last_error("key-switch key: ksk must be in_dimension*ell*(out_dimension+1) words");
         return PFHE_ERR_BAD_LENGTH;
     }
-    if (!key_in || !key_out || !ksk) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(ksk, len * sizeof(W), key_in, in_dimension * sizeof(W)) ||
-        overlaps(ksk, len * sizeof(W), key_out, out_dimension * sizeof(W))) {
-        set_last_error("key-switch key: the keys must not overlap ksk");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    PFHE_TRY(capi_check_device(device));
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_lwe_body_mac<W>(ksk, key_out, (u32)out_dimension, (u64)in_dimension * ell, 0, key_in, ell, log_basis, drop, s);
+    const StageBuf bufs[] = {stage_in(key_in, in_dimension * sizeof(W)), stage_in(key_out, out_dimension * sizeof(W)),
+                             stage_inout(ksk, len * sizeof(W))};
+    return stateless_call(
+        device, Form::kDevice, bufs, "key-switch key: the keys must not overlap ksk", s,
+        [&](void *const *d, hipStream_t st) {
+            return launch_lwe_body_mac<W>((W *)d[2], (const W *)d[1], (u32)out_dimension, (u64)in_dimension * ell, 0,
+                                          (const W *)d[0], ell, log_basis, drop, st);
+        },
+        [&] { return capi_check_device(device); });
 }
 
 }  // namespace
@@ -381,52 +326,54 @@ extern "C" {
 int pfhe_tfhe_lwe_body_mac_dev(int device, uint64_t *lwe_dev, size_t len_lwe, size_t dimension, const uint64_t *key_dev,
                                size_t len_key, int subtract, void *stream) {
     PFHE_GUARD_BEGIN
-    return lwe_body_mac_dev<u64>(device, (u64 *)lwe_dev, len_lwe, dimension, (const u64 *)key_dev, len_key, subtract,
-                                 (hipStream_t)stream);
+    return lwe_body_mac<u64>(Form::kDevice, device, (u64 *)lwe_dev, len_lwe, dimension, (const u64 *)key_dev, len_key, subtract,
+                             (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_lwe_body_mac(int device, uint64_t *lwe, size_t len_lwe, size_t dimension, const uint64_t *key, size_t len_key,
                            int subtract) {
     PFHE_GUARD_BEGIN
-    return lwe_body_mac_host<u64>(device, (u64 *)lwe, len_lwe, dimension, (const u64 *)key, len_key, subtract);
+    return lwe_body_mac<u64>(Form::kHost, device, (u64 *)lwe, len_lwe, dimension, (const u64 *)key, len_key, subtract, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_lwe_body_mac_dev(int device, uint32_t *lwe_dev, size_t len_lwe, size_t dimension, const uint32_t *key_dev,
                                  size_t len_key, int subtract, void *stream) {
     PFHE_GUARD_BEGIN
-    return lwe_body_mac_dev<u32>(device, lwe_dev, len_lwe, dimension, key_dev, len_key, subtract, (hipStream_t)stream);
+    return lwe_body_mac<u32>(Form::kDevice, device, lwe_dev, len_lwe, dimension, key_dev, len_key, subtract, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_lwe_body_mac(int device, uint32_t *lwe, size_t len_lwe, size_t dimension, const uint32_t *key, size_t len_key,
                              int subtract) {
     PFHE_GUARD_BEGIN
-    return lwe_body_mac_host<u32>(device, lwe, len_lwe, dimension, key, len_key, subtract);
+    return lwe_body_mac<u32>(Form::kHost, device, lwe, len_lwe, dimension, key, len_key, subtract, nullptr);
     PFHE_GUARD_END
 }
 
 int pfhe_tfhe_glwe_body_mac_dev(const pfhe_fft *fft, size_t glwe_dimension, uint64_t *glwe_dev, size_t len_glwe,
                                 const uint64_t *key_dev, size_t len_key, int subtract, void *stream) {
     PFHE_GUARD_BEGIN
-    return glwe_body_mac_dev<u64>(fft, glwe_dimension, (u64 *)glwe_dev, len_glwe, (const u64 *)key_dev, len_key, subtract,
-                                  (hipStream_t)stream);
+    return glwe_body_mac<u64>(Form::kDevice, fft, glwe_dimension, (u64 *)glwe_dev, len_glwe, (const u64 *)key_dev, len_key,
+                              subtract, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_glwe_body_mac(const pfhe_fft *fft, size_t glwe_dimension, uint64_t *glwe, size_t len_glwe, const uint64_t *key,
                             size_t len_key, int subtract) {
     PFHE_GUARD_BEGIN
-    return glwe_body_mac_host<u64>(fft, glwe_dimension, (u64 *)glwe, len_glwe, (const u64 *)key, len_key, subtract);
+    return glwe_body_mac<u64>(Form::kHost, fft, glwe_dimension, (u64 *)glwe, len_glwe, (const u64 *)key, len_key, subtract,
+                              nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_glwe_body_mac_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t *glwe_dev, size_t len_glwe,
                                   const uint32_t *key_dev, size_t len_key, int subtract, void *stream) {
     PFHE_GUARD_BEGIN
-    return glwe_body_mac_dev<u32>(fft, glwe_dimension, glwe_dev, len_glwe, key_dev, len_key, subtract, (hipStream_t)stream);
+    return glwe_body_mac<u32>(Form::kDevice, fft, glwe_dimension, glwe_dev, len_glwe, key_dev, len_key, subtract,
+                              (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_glwe_body_mac(const pfhe_fft *fft, size_t glwe_dimension, uint32_t *glwe, size_t len_glwe, const uint32_t *key,
                               size_t len_key, int subtract) {
     PFHE_GUARD_BEGIN
-    return glwe_body_mac_host<u32>(fft, glwe_dimension, glwe, len_glwe, key, len_key, subtract);
+    return glwe_body_mac<u32>(Form::kHost, fft, glwe_dimension, glwe, len_glwe, key, len_key, subtract, nullptr);
     PFHE_GUARD_END
 }
 

@@ -4,7 +4,7 @@
 //
 //   packing key switch   out_e = (0, ..., 0, sum_i b_{e,i} X^i) - sum_i X^i sum_j sum_l d_l(a_{e,i,j}) PKSK[j][l] modulo
 //                        2^BITS and X^N + 1, with the digits of ApproxSignedBasis exactly as the LWE key switch forms them
-//                        (init_carry / digit_step of pfhe_fft_device.hpp).  No reference counterpart.
+//                        (init_carry / digit_word of pfhe_fft_device.hpp).  No reference counterpart.
 //   packing key          row (j, l) of the caller's randomness becomes a GLWE encryption of key_in[j] 2^(drop + l log_basis):
 //                        the GLWE body call of pfhe_keygen.hip on all rows, then the message term on coefficient 0.
 //   first few            Rlwe::extract_first_few_lwe (primus_lattice/src/rlwe/coeff.rs:231-260) per mask polynomial: the
@@ -108,13 +108,8 @@ __global__ __launch_bounds__(kThreads) void tfhe_pack_keyswitch_kernel(const W *
                 const u32 jj = p % kcur, ii = p / kcur;
                 const W v = ib + ii < s.count ? lwe[(u64)(ib + ii) * in_stride + j0 + jj] : (W)0;
                 u32 carry = init_carry(v, s.drop_bits);
-                for (u32 l = 0; l < s.ell; ++l) {
-                    const u32 shift = s.drop_bits + l * s.log_basis;
-                    const W field = (v >> shift) & (((W)1 << s.log_basis) - 1);
-                    const W carry_in = (W)carry;
-                    (void)digit_step(v, shift, s.log_basis, carry);  // the rule: it decides the carry out of this level
-                    dig[(jj * s.ell + l) * s.block_j + ii] = field + carry_in - ((W)carry << s.log_basis);
-                }
+                for (u32 l = 0; l < s.ell; ++l)
+                    dig[(jj * s.ell + l) * s.block_j + ii] = digit_word(v, s.drop_bits + l * s.log_basis, s.log_basis, carry);
             }
             for (u32 r = 0; r < rows; r += per_stage) {
 #pragma unroll
@@ -247,17 +242,10 @@ int launch_pack_keyswitch(const W *lwe_in, const W *pksk, W *glwe_out, PackShape
     const u32 n = 1u << sh.log_n;
     const u32 gx = (sh.k + 1) * (n / sh.tile);
     const u64 in_words = (u64)sh.count * ((u64)sh.in_dim + 1), out_words = (u64)(sh.k + 1) << sh.log_n;
-    for (u64 done = 0; done < batch;) {  // grid.y holds 65535 groups
-        const u64 cur = std::min<u64>(batch - done, 65535);
-        if (n >= 4)
-            PFHE_TRY(launch_grid(tfhe_pack_keyswitch_kernel<W, 4>, dim3(gx, (u32)cur), 0, s, lwe_in + done * in_words, pksk,
-                                 glwe_out + done * out_words, sh));
-        else
-            PFHE_TRY(launch_grid(tfhe_pack_keyswitch_kernel<W, 2>, dim3(gx, (u32)cur), 0, s, lwe_in + done * in_words, pksk,
-                                 glwe_out + done * out_words, sh));
-        done += cur;
-    }
-    return PFHE_OK;
+    return launch_y_slices(batch, [&](u64 done, u32 cur) {
+        return launch_grid(n >= 4 ? tfhe_pack_keyswitch_kernel<W, 4> : tfhe_pack_keyswitch_kernel<W, 2>, dim3(gx, cur), 0, s,
+                           lwe_in + done * in_words, pksk, glwe_out + done * out_words, sh);
+    });
 }
 
 template <class W>
@@ -291,10 +279,8 @@ template <class W>
 int pack_dimensions(const char *message, const pfhe_fft *f, size_t k, size_t in_dimension, uint32_t log_basis,
                     size_t decompose_length, u32 &ell, u32 &drop) {
     PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
-    if (k == 0 || k > kMaxGlweDimension || in_dimension == 0 || in_dimension >= 0x7fffffffull) {
-        set_last_error(message);
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    PFHE_TRY(require_glwe_dimension(k, message));
+    PFHE_TRY(require_lwe_dimension(in_dimension, message));
     if (!f) return PFHE_ERR_BAD_ARGUMENT;
     return PFHE_OK;
 }
@@ -319,37 +305,19 @@ int pack_check(const pfhe_fft *f, size_t k, size_t len_in, size_t in_dimension, 
 }
 
 template <class W>
-int pack_keyswitch_dev(const pfhe_fft *f, size_t k, const W *lwe_in, size_t len_in, size_t in_dimension, size_t count,
-                       const W *pksk, size_t len_pksk, uint32_t log_basis, size_t decompose_length, W *glwe_out, size_t len_out,
-                       hipStream_t s) {
+int pack_keyswitch(Form form, const pfhe_fft *f, size_t k, const W *lwe_in, size_t len_in, size_t in_dimension, size_t count,
+                   const W *pksk, size_t len_pksk, uint32_t log_basis, size_t decompose_length, W *glwe_out, size_t len_out,
+                   hipStream_t s) {
     PackShape sh{};
     PFHE_TRY(pack_check<W>(f, k, len_in, in_dimension, count, len_pksk, log_basis, decompose_length, len_out, sh));
     if (len_in == 0) return PFHE_OK;
-    if (!lwe_in || !pksk || !glwe_out) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(lwe_in, len_in * sizeof(W), glwe_out, len_out * sizeof(W)) ||
-        overlaps(pksk, len_pksk * sizeof(W), glwe_out, len_out * sizeof(W))) {
-        set_last_error("packing key switch: the output must not overlap an input");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_pack_keyswitch<W>(lwe_in, pksk, glwe_out, sh, len_in / (count * (in_dimension + 1)), s);
-}
-
-template <class W>
-int pack_keyswitch_host(const pfhe_fft *f, size_t k, const W *lwe_in, size_t len_in, size_t in_dimension, size_t count,
-                        const W *pksk, size_t len_pksk, uint32_t log_basis, size_t decompose_length, W *glwe_out,
-                        size_t len_out) {
-    PackShape sh{};
-    PFHE_TRY(pack_check<W>(f, k, len_in, in_dimension, count, len_pksk, log_basis, decompose_length, len_out, sh));
-    if (len_in == 0) return PFHE_OK;
-    if (!lwe_in || !pksk || !glwe_out) return PFHE_ERR_BAD_ARGUMENT;
     const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(pksk, len_pksk * sizeof(W)),
                              stage_out(glwe_out, len_out * sizeof(W))};
-    return staged_call(f->device, bufs, [&](void *const *d, hipStream_t s) {
-        return launch_pack_keyswitch<W>((const W *)d[0], (const W *)d[1], (W *)d[2], sh, len_in / (count * (in_dimension + 1)),
-                                        s);
-    });
+    return stateless_call(f->device, form, bufs, "packing key switch: the output must not overlap an input", s,
+                          [&](void *const *d, hipStream_t st) {
+                              return launch_pack_keyswitch<W>((const W *)d[0], (const W *)d[1], (W *)d[2], sh,
+                                                              len_in / (count * (in_dimension + 1)), st);
+                          });
 }
 
 template <class W>
@@ -361,29 +329,22 @@ int pksk_generate_dev(const pfhe_fft *f, size_t k, const W *key_in, size_t in_di
         set_last_error("packing key: glwe_key must be k*N words and pksk in_dimension*ell*(k+1)*N");
         return PFHE_ERR_BAD_LENGTH;
     }
-    if (!key_in || !glwe_key || !pksk) return PFHE_ERR_BAD_ARGUMENT;
-    if (overlaps(pksk, len * sizeof(W), key_in, in_dimension * sizeof(W)) ||
-        overlaps(pksk, len * sizeof(W), glwe_key, len_glwe_key * sizeof(W))) {
-        set_last_error("packing key: the keys must not overlap pksk");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    if (in_dimension * ell > 0x7fffffffull) return PFHE_ERR_BAD_LENGTH;
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    PFHE_TRY(glwe_body_add(f, k, pksk, len, glwe_key, len_glwe_key, s));
-    return launch_pksk_message<W>(pksk, key_in, (u32)k, f->log_n, ell, log_basis, drop, (u64)in_dimension * ell, s);
+    const StageBuf bufs[] = {stage_in(key_in, in_dimension * sizeof(W)), stage_in(glwe_key, len_glwe_key * sizeof(W)),
+                             stage_inout(pksk, len * sizeof(W))};
+    return stateless_call(
+        f->device, Form::kDevice, bufs, "packing key: the keys must not overlap pksk", s,
+        [&](void *const *d, hipStream_t st) {
+            PFHE_TRY(glwe_body_add(f, k, (W *)d[2], len, (const W *)d[1], len_glwe_key, st));
+            return launch_pksk_message<W>((W *)d[2], (const W *)d[0], (u32)k, f->log_n, ell, log_basis, drop,
+                                          (u64)in_dimension * ell, st);
+        },
+        [&] { return in_dimension * ell > 0x7fffffffull ? PFHE_ERR_BAD_LENGTH : PFHE_OK; });
 }
-
-constexpr const char *kFirstFewLengths = "multi-message extraction: glwe must be batch*(k+1)*N words and multi batch*(k*N+count)";
-constexpr const char *kExpandLengths = "multi-message expansion: multi must be batch*(k*N+count) words and lwe batch*count*(k*N+1)";
 
 // the table, the dimension and count as pfhe_tfhe_sample_extract checks its table, dimension and index
 inline int multimsg_dimensions(const pfhe_fft *f, size_t k, size_t count) {
     if (!f) return PFHE_ERR_BAD_ARGUMENT;
-    if (k == 0 || k > kMaxGlweDimension) {
-        set_last_error("multi-message extraction: glwe_dimension must be in 1..64");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
+    PFHE_TRY(require_glwe_dimension(k, "multi-message extraction: glwe_dimension must be in 1..64"));
     if (count == 0 || count > f->n) {
         set_last_error("multi-message extraction: count must be in 1..N");
         return PFHE_ERR_BAD_ARGUMENT;
@@ -391,59 +352,40 @@ inline int multimsg_dimensions(const pfhe_fft *f, size_t k, size_t count) {
     return PFHE_OK;
 }
 
-// `dev` decides what is checked of the pointers: the device forms also refuse an output that overlaps the input
 template <class W>
-int first_few(const pfhe_fft *f, size_t k, const W *glwe, size_t len_glwe, size_t count, W *multi, size_t len_multi, bool dev,
+int first_few(Form form, const pfhe_fft *f, size_t k, const W *glwe, size_t len_glwe, size_t count, W *multi, size_t len_multi,
               hipStream_t s) {
     PFHE_TRY(multimsg_dimensions(f, k, count));
     const size_t in_words = (k + 1) * f->n, out_words = k * f->n + count;
     if (len_glwe % in_words != 0 || len_multi != len_glwe / in_words * out_words) {
-        set_last_error(kFirstFewLengths);
+        set_last_error("multi-message extraction: glwe must be batch*(k+1)*N words and multi batch*(k*N+count)");
         return PFHE_ERR_BAD_LENGTH;
     }
     if (len_glwe == 0) return PFHE_OK;
-    if (!glwe || !multi) return PFHE_ERR_BAD_ARGUMENT;
-    const u64 batch = len_glwe / in_words;
-    if (!dev) {
-        const StageBuf bufs[] = {stage_in(glwe, len_glwe * sizeof(W)), stage_out(multi, len_multi * sizeof(W))};
-        return staged_call(f->device, bufs, [&](void *const *d, hipStream_t st) {
-            return launch_extract_first_few<W>((const W *)d[0], (W *)d[1], (u32)k, f->log_n, (u32)count, batch, st);
-        });
-    }
-    if (overlaps(glwe, len_glwe * sizeof(W), multi, len_multi * sizeof(W))) {
-        set_last_error("multi-message extraction: the output must not overlap the input");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_extract_first_few<W>(glwe, multi, (u32)k, f->log_n, (u32)count, batch, s);
+    const StageBuf bufs[] = {stage_in(glwe, len_glwe * sizeof(W)), stage_out(multi, len_multi * sizeof(W))};
+    return stateless_call(f->device, form, bufs, "multi-message extraction: the output must not overlap the input", s,
+                          [&](void *const *d, hipStream_t st) {
+                              return launch_extract_first_few<W>((const W *)d[0], (W *)d[1], (u32)k, f->log_n, (u32)count,
+                                                                 len_glwe / in_words, st);
+                          });
 }
 
 template <class W>
-int multimsg_extract(const pfhe_fft *f, size_t k, const W *multi, size_t len_multi, size_t count, W *lwe, size_t len_lwe,
-                     bool dev, hipStream_t s) {
+int multimsg_extract(Form form, const pfhe_fft *f, size_t k, const W *multi, size_t len_multi, size_t count, W *lwe,
+                     size_t len_lwe, hipStream_t s) {
     PFHE_TRY(multimsg_dimensions(f, k, count));
     const size_t in_words = k * f->n + count, out_words = count * (k * f->n + 1);
     if (len_multi % in_words != 0 || len_lwe != len_multi / in_words * out_words) {
-        set_last_error(kExpandLengths);
+        set_last_error("multi-message expansion: multi must be batch*(k*N+count) words and lwe batch*count*(k*N+1)");
         return PFHE_ERR_BAD_LENGTH;
     }
     if (len_multi == 0) return PFHE_OK;
-    if (!multi || !lwe) return PFHE_ERR_BAD_ARGUMENT;
-    const u64 batch = len_multi / in_words;
-    if (!dev) {
-        const StageBuf bufs[] = {stage_in(multi, len_multi * sizeof(W)), stage_out(lwe, len_lwe * sizeof(W))};
-        return staged_call(f->device, bufs, [&](void *const *d, hipStream_t st) {
-            return launch_multimsg_extract<W>((const W *)d[0], (W *)d[1], (u32)k, f->log_n, (u32)count, batch, st);
-        });
-    }
-    if (overlaps(multi, len_multi * sizeof(W), lwe, len_lwe * sizeof(W))) {
-        set_last_error("multi-message expansion: the output must not overlap the input");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    DeviceGuard g(f->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch_multimsg_extract<W>(multi, lwe, (u32)k, f->log_n, (u32)count, batch, s);
+    const StageBuf bufs[] = {stage_in(multi, len_multi * sizeof(W)), stage_out(lwe, len_lwe * sizeof(W))};
+    return stateless_call(f->device, form, bufs, "multi-message expansion: the output must not overlap the input", s,
+                          [&](void *const *d, hipStream_t st) {
+                              return launch_multimsg_extract<W>((const W *)d[0], (W *)d[1], (u32)k, f->log_n, (u32)count,
+                                                                len_multi / in_words, st);
+                          });
 }
 
 }  // namespace
@@ -456,17 +398,17 @@ int pfhe_tfhe_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, con
                                  uint32_t log_basis, size_t decompose_length, uint64_t *glwe_out_dev, size_t len_out,
                                  void *stream) {
     PFHE_GUARD_BEGIN
-    return pack_keyswitch_dev<u64>(fft, glwe_dimension, (const u64 *)lwe_in_dev, len_in, in_dimension, count,
-                                   (const u64 *)pksk_dev, len_pksk, log_basis, decompose_length, (u64 *)glwe_out_dev, len_out,
-                                   (hipStream_t)stream);
+    return pack_keyswitch<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)lwe_in_dev, len_in, in_dimension, count,
+                               (const u64 *)pksk_dev, len_pksk, log_basis, decompose_length, (u64 *)glwe_out_dev, len_out,
+                               (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_pack_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
                              size_t in_dimension, size_t count, const uint64_t *pksk, size_t len_pksk, uint32_t log_basis,
                              size_t decompose_length, uint64_t *glwe_out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return pack_keyswitch_host<u64>(fft, glwe_dimension, (const u64 *)lwe_in, len_in, in_dimension, count, (const u64 *)pksk,
-                                    len_pksk, log_basis, decompose_length, (u64 *)glwe_out, len_out);
+    return pack_keyswitch<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)lwe_in, len_in, in_dimension, count,
+                               (const u64 *)pksk, len_pksk, log_basis, decompose_length, (u64 *)glwe_out, len_out, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in_dev, size_t len_in,
@@ -474,16 +416,16 @@ int pfhe_tfhe32_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, c
                                    uint32_t log_basis, size_t decompose_length, uint32_t *glwe_out_dev, size_t len_out,
                                    void *stream) {
     PFHE_GUARD_BEGIN
-    return pack_keyswitch_dev<u32>(fft, glwe_dimension, lwe_in_dev, len_in, in_dimension, count, pksk_dev, len_pksk, log_basis,
-                                   decompose_length, glwe_out_dev, len_out, (hipStream_t)stream);
+    return pack_keyswitch<u32>(Form::kDevice, fft, glwe_dimension, lwe_in_dev, len_in, in_dimension, count, pksk_dev, len_pksk,
+                               log_basis, decompose_length, glwe_out_dev, len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_pack_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
                                size_t in_dimension, size_t count, const uint32_t *pksk, size_t len_pksk, uint32_t log_basis,
                                size_t decompose_length, uint32_t *glwe_out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return pack_keyswitch_host<u32>(fft, glwe_dimension, lwe_in, len_in, in_dimension, count, pksk, len_pksk, log_basis,
-                                    decompose_length, glwe_out, len_out);
+    return pack_keyswitch<u32>(Form::kHost, fft, glwe_dimension, lwe_in, len_in, in_dimension, count, pksk, len_pksk, log_basis,
+                               decompose_length, glwe_out, len_out, nullptr);
     PFHE_GUARD_END
 }
 
@@ -507,53 +449,56 @@ int pfhe_tfhe32_pksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, co
 int pfhe_tfhe_sample_extract_first_few_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
                                            size_t count, uint64_t *multi_dev, size_t len_multi, void *stream) {
     PFHE_GUARD_BEGIN
-    return first_few<u64>(fft, glwe_dimension, (const u64 *)glwe_dev, len_glwe, count, (u64 *)multi_dev, len_multi, true,
+    return first_few<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)glwe_dev, len_glwe, count, (u64 *)multi_dev, len_multi,
                           (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_sample_extract_first_few(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe,
                                        size_t count, uint64_t *multi, size_t len_multi) {
     PFHE_GUARD_BEGIN
-    return first_few<u64>(fft, glwe_dimension, (const u64 *)glwe, len_glwe, count, (u64 *)multi, len_multi, false, nullptr);
+    return first_few<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)glwe, len_glwe, count, (u64 *)multi, len_multi, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_sample_extract_first_few_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe_dev,
                                              size_t len_glwe, size_t count, uint32_t *multi_dev, size_t len_multi,
                                              void *stream) {
     PFHE_GUARD_BEGIN
-    return first_few<u32>(fft, glwe_dimension, glwe_dev, len_glwe, count, multi_dev, len_multi, true, (hipStream_t)stream);
+    return first_few<u32>(Form::kDevice, fft, glwe_dimension, glwe_dev, len_glwe, count, multi_dev, len_multi,
+                          (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_sample_extract_first_few(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe,
                                          size_t count, uint32_t *multi, size_t len_multi) {
     PFHE_GUARD_BEGIN
-    return first_few<u32>(fft, glwe_dimension, glwe, len_glwe, count, multi, len_multi, false, nullptr);
+    return first_few<u32>(Form::kHost, fft, glwe_dimension, glwe, len_glwe, count, multi, len_multi, nullptr);
     PFHE_GUARD_END
 }
 
 int pfhe_tfhe_multimsg_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *multi_dev, size_t len_multi,
                                    size_t count, uint64_t *lwe_dev, size_t len_lwe, void *stream) {
     PFHE_GUARD_BEGIN
-    return multimsg_extract<u64>(fft, glwe_dimension, (const u64 *)multi_dev, len_multi, count, (u64 *)lwe_dev, len_lwe, true,
-                                 (hipStream_t)stream);
+    return multimsg_extract<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)multi_dev, len_multi, count, (u64 *)lwe_dev,
+                                 len_lwe, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_multimsg_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *multi, size_t len_multi, size_t count,
                                uint64_t *lwe, size_t len_lwe) {
     PFHE_GUARD_BEGIN
-    return multimsg_extract<u64>(fft, glwe_dimension, (const u64 *)multi, len_multi, count, (u64 *)lwe, len_lwe, false, nullptr);
+    return multimsg_extract<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)multi, len_multi, count, (u64 *)lwe, len_lwe,
+                                 nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_multimsg_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *multi_dev, size_t len_multi,
                                      size_t count, uint32_t *lwe_dev, size_t len_lwe, void *stream) {
     PFHE_GUARD_BEGIN
-    return multimsg_extract<u32>(fft, glwe_dimension, multi_dev, len_multi, count, lwe_dev, len_lwe, true, (hipStream_t)stream);
+    return multimsg_extract<u32>(Form::kDevice, fft, glwe_dimension, multi_dev, len_multi, count, lwe_dev, len_lwe,
+                                 (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_multimsg_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *multi, size_t len_multi,
                                  size_t count, uint32_t *lwe, size_t len_lwe) {
     PFHE_GUARD_BEGIN
-    return multimsg_extract<u32>(fft, glwe_dimension, multi, len_multi, count, lwe, len_lwe, false, nullptr);
+    return multimsg_extract<u32>(Form::kHost, fft, glwe_dimension, multi, len_multi, count, lwe, len_lwe, nullptr);
     PFHE_GUARD_END
 }
 

@@ -319,6 +319,16 @@ def _dev_index(t, device) -> int:
     return int(t.device.index or 0) if hasattr(t, "device") else 0
 
 
+def _stateless(name, dev, arrays, message, args, stream=None) -> None:
+    """One stateless step in its host (dev false) or device form.  `arrays`: numpy arrays or CUDA tensors of one word width w
+    (TypeError(message) otherwise); args(w, (pointer, words) per array) gives the C arguments, and the device form takes
+    the stream after them."""
+    words = [(_dev_words if dev else _host_words)(a) for a in arrays]
+    w = _same_width(message, *(x[2] for x in words))
+    tail = (_stream(stream),) if dev else ()
+    check(getattr(lib(), "pfhe_tfhe" + w + name + ("_dev" if dev else ""))(*args(w, *(x[:2] for x in words)), *tail))
+
+
 def lwe_modulus_switch_dev(lwe, lwe_dimension: int, log_n: int, exps, neg_b, device=None, stream=None) -> None:
     """The project's own modulus switch (the reference has none): for a batch of LWE ciphertexts (a[0..n), b) of 32- or
     64-bit torus words, exps[e*n + i] = sw(a_{e,i}) and neg_b[e] = (2N - sw(b_e)) mod 2N, with
@@ -331,24 +341,22 @@ def lwe_modulus_switch_dev(lwe, lwe_dimension: int, log_n: int, exps, neg_b, dev
                                                             pb, nb, _stream(stream)))
 
 
+def _sample_extract(dev, glwe, lwe, fft, glwe_dimension, index, stream=None) -> None:
+    _stateless("_sample_extract", dev, (glwe, lwe), "glwe and lwe must have the same word width",
+               lambda w, g, o: (fft._h, glwe_dimension, *g, index, *o), stream)
+
+
 def glwe_sample_extract(glwe: np.ndarray, lwe: np.ndarray, fft: FullComplex64FftTable, glwe_dimension: int = 1,
                         index: int = 0) -> None:
     """Rlwe::extract_lwe_with_index (rlwe/coeff.rs:194-227) per mask polynomial, on host arrays: batch GLWE ciphertexts of
     (k+1)*N words -> batch LWE ciphertexts of k*N + 1 words under the GLWE key polynomials end to end."""
-    pg, ng, wg = _host_words(glwe)
-    po, no, wo = _host_words(lwe)
-    _same_width("glwe and lwe must have the same word width", wg, wo)
-    check(getattr(lib(), "pfhe_tfhe" + wg + "_sample_extract")(fft._h, glwe_dimension, pg, ng, index, po, no))
+    _sample_extract(False, glwe, lwe, fft, glwe_dimension, index)
 
 
 def glwe_sample_extract_dev(glwe, lwe, fft: FullComplex64FftTable, glwe_dimension: int = 1, index: int = 0,
                             stream=None) -> None:
     """the device form; lwe must not overlap glwe"""
-    pg, ng, wg = _dev_words(glwe)
-    po, no, wo = _dev_words(lwe)
-    _same_width("glwe and lwe must have the same word width", wg, wo)
-    check(getattr(lib(), "pfhe_tfhe" + wg + "_sample_extract_dev")(fft._h, glwe_dimension, pg, ng, index, po, no,
-                                                                  _stream(stream)))
+    _sample_extract(True, glwe, lwe, fft, glwe_dimension, index, stream)
 
 
 def _basis_args(basis, width: str):
@@ -357,29 +365,24 @@ def _basis_args(basis, width: str):
     return basis.log_basis(), basis.decompose_length()
 
 
+def _keyswitch(dev, lwe_in, ksk, lwe_out, in_dimension, out_dimension, basis, device, stream=None) -> None:
+    _stateless("_keyswitch", dev, (lwe_in, ksk, lwe_out), "lwe_in, ksk and lwe_out must have the same word width",
+               lambda w, i, k, o: (_dev_index(lwe_in, device) if dev else device, *i, in_dimension, *k, out_dimension,
+                                   *_basis_args(basis, w), *o), stream)
+
+
 def lwe_keyswitch(lwe_in: np.ndarray, ksk: np.ndarray, lwe_out: np.ndarray, in_dimension: int, out_dimension: int,
                   basis: ApproxSignedBasis, device: int = 0) -> None:
     """LWE key switch on host arrays: out = (0, b) - sum_i sum_j d_{i,j} * KSK[i][j] modulo 2^BITS, d the signed digits of
     a_i under `basis`; ksk is in_dimension x ell x (out_dimension+1) words, row (i, j) an LWE ciphertext of
     s_i * 2^(drop_bits + j*log_basis) under the output key, levels least significant first."""
-    pi, ni, wi = _host_words(lwe_in)
-    pk, nk, wk = _host_words(ksk)
-    po, no, wo = _host_words(lwe_out)
-    _same_width("lwe_in, ksk and lwe_out must have the same word width", wi, wk, wo)
-    lb, ell = _basis_args(basis, wi)
-    check(getattr(lib(), "pfhe_tfhe" + wi + "_keyswitch")(device, pi, ni, in_dimension, pk, nk, out_dimension, lb, ell, po, no))
+    _keyswitch(False, lwe_in, ksk, lwe_out, in_dimension, out_dimension, basis, device)
 
 
 def lwe_keyswitch_dev(lwe_in, ksk, lwe_out, in_dimension: int, out_dimension: int, basis: ApproxSignedBasis, device=None,
                       stream=None) -> None:
     """the device form, asynchronous; lwe_out must not overlap an input and may be uninitialised"""
-    pi, ni, wi = _dev_words(lwe_in)
-    pk, nk, wk = _dev_words(ksk)
-    po, no, wo = _dev_words(lwe_out)
-    _same_width("lwe_in, ksk and lwe_out must have the same word width", wi, wk, wo)
-    lb, ell = _basis_args(basis, wi)
-    check(getattr(lib(), "pfhe_tfhe" + wi + "_keyswitch_dev")(_dev_index(lwe_in, device), pi, ni, in_dimension, pk, nk,
-                                                             out_dimension, lb, ell, po, no, _stream(stream)))
+    _keyswitch(True, lwe_in, ksk, lwe_out, in_dimension, out_dimension, basis, device, stream)
 
 
 class TfheBootstrapContext(_TorusContext):
@@ -461,77 +464,57 @@ def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) 
 # No call below draws a random number: masks and noise are what the caller put into the buffers (torus_uniform and
 # torus_noise are two ways of doing that).
 
-def _lwe_body(lwe, key, subtract: int, device: int) -> None:
-    pl, nl, wl = _host_words(lwe)
-    pk, nk, wk = _host_words(key)
-    _same_width("ciphertexts and key must have the same word width", wl, wk)
-    check(getattr(lib(), "pfhe_tfhe" + wl + "_lwe_body_mac")(device, pl, nl, nk, pk, nk, subtract))
-
-
-def _lwe_body_dev(lwe, key, subtract: int, device, stream) -> None:
-    pl, nl, wl = _dev_words(lwe)
-    pk, nk, wk = _dev_words(key)
-    _same_width("ciphertexts and key must have the same word width", wl, wk)
-    check(getattr(lib(), "pfhe_tfhe" + wl + "_lwe_body_mac_dev")(_dev_index(lwe, device), pl, nl, nk, pk, nk, subtract,
-                                                               _stream(stream)))
+def _lwe_body(dev, lwe, key, subtract: int, device, stream=None) -> None:
+    _stateless("_lwe_body_mac", dev, (lwe, key), "ciphertexts and key must have the same word width",
+               lambda w, l, k: (_dev_index(lwe, device) if dev else device, *l, k[1], *k, subtract), stream)
 
 
 def lwe_encrypt(lwe: np.ndarray, key: np.ndarray, device: int = 0) -> None:
     """Lwe::generate_random_zero_sample (lwe/single_message.rs:94-125) with the caller's randomness, on host arrays and in
     place: lwe holds batch x (len(key)+1) words, masks uniform and body slots noise + message; b_e += <a_e, key>."""
-    _lwe_body(lwe, key, 0, device)
+    _lwe_body(False, lwe, key, 0, device)
 
 
 def lwe_encrypt_dev(lwe, key, device=None, stream=None) -> None:
     """the device form, asynchronous"""
-    _lwe_body_dev(lwe, key, 0, device, stream)
+    _lwe_body(True, lwe, key, 0, device, stream)
 
 
 def lwe_phase(lwe: np.ndarray, key: np.ndarray, device: int = 0) -> None:
     """b_e -= <a_e, key> in place: every body slot becomes the phase b - <a,s> = noise + message"""
-    _lwe_body(lwe, key, 1, device)
+    _lwe_body(False, lwe, key, 1, device)
 
 
 def lwe_phase_dev(lwe, key, device=None, stream=None) -> None:
     """the device form, asynchronous"""
-    _lwe_body_dev(lwe, key, 1, device, stream)
+    _lwe_body(True, lwe, key, 1, device, stream)
 
 
-def _glwe_body(glwe, key, fft, glwe_dimension: int, subtract: int) -> None:
-    pg, ng, wg = _host_words(glwe)
-    pk, nk, wk = _host_words(key)
-    _same_width("ciphertexts and key must have the same word width", wg, wk)
-    check(getattr(lib(), "pfhe_tfhe" + wg + "_glwe_body_mac")(fft._h, glwe_dimension, pg, ng, pk, nk, subtract))
-
-
-def _glwe_body_dev(glwe, key, fft, glwe_dimension: int, subtract: int, stream) -> None:
-    pg, ng, wg = _dev_words(glwe)
-    pk, nk, wk = _dev_words(key)
-    _same_width("ciphertexts and key must have the same word width", wg, wk)
-    check(getattr(lib(), "pfhe_tfhe" + wg + "_glwe_body_mac_dev")(fft._h, glwe_dimension, pg, ng, pk, nk, subtract,
-                                                                _stream(stream)))
+def _glwe_body(dev, glwe, key, fft, glwe_dimension: int, subtract: int, stream=None) -> None:
+    _stateless("_glwe_body_mac", dev, (glwe, key), "ciphertexts and key must have the same word width",
+               lambda w, g, k: (fft._h, glwe_dimension, *g, *k, subtract), stream)
 
 
 def glwe_encrypt(glwe: np.ndarray, key: np.ndarray, fft: FullComplex64FftTable, glwe_dimension: int = 1) -> None:
     """Rlwe::generate_random_zero_sample (rlwe/coeff.rs:92-121) with the caller's randomness, on host arrays and in place:
     glwe holds batch x (k+1) x N words, mask polynomials uniform and body polynomials noise + message; key the k key
     polynomials end to end; B_e += sum_j A_{e,j} * z_j modulo X^N + 1."""
-    _glwe_body(glwe, key, fft, glwe_dimension, 0)
+    _glwe_body(False, glwe, key, fft, glwe_dimension, 0)
 
 
 def glwe_encrypt_dev(glwe, key, fft: FullComplex64FftTable, glwe_dimension: int = 1, stream=None) -> None:
     """the device form, asynchronous"""
-    _glwe_body_dev(glwe, key, fft, glwe_dimension, 0, stream)
+    _glwe_body(True, glwe, key, fft, glwe_dimension, 0, stream)
 
 
 def glwe_phase(glwe: np.ndarray, key: np.ndarray, fft: FullComplex64FftTable, glwe_dimension: int = 1) -> None:
     """B_e -= sum_j A_{e,j} * z_j in place: every body polynomial becomes the phase"""
-    _glwe_body(glwe, key, fft, glwe_dimension, 1)
+    _glwe_body(False, glwe, key, fft, glwe_dimension, 1)
 
 
 def glwe_phase_dev(glwe, key, fft: FullComplex64FftTable, glwe_dimension: int = 1, stream=None) -> None:
     """the device form, asynchronous"""
-    _glwe_body_dev(glwe, key, fft, glwe_dimension, 1, stream)
+    _glwe_body(True, glwe, key, fft, glwe_dimension, 1, stream)
 
 
 def ggsw_add_gadget_dev(ggsw, messages, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1,
@@ -608,6 +591,11 @@ def tfhe_generate_ksk_dev(key_in, key_out, basis: ApproxSignedBasis, rand, devic
 # ---- packing: LWE ciphertexts back into a GLWE, and multi-message extraction (include/pfhe.h: pack_keyswitch, pksk_generate,
 # sample_extract_first_few, multimsg_extract) ----
 
+def _pack_keyswitch(dev, lwe_in, pksk, glwe_out, in_dimension, count, fft, basis, glwe_dimension, stream=None) -> None:
+    _stateless("_pack_keyswitch", dev, (lwe_in, pksk, glwe_out), "lwe_in, pksk and glwe_out must have the same word width",
+               lambda w, i, k, o: (fft._h, glwe_dimension, *i, in_dimension, count, *k, *_basis_args(basis, w), *o), stream)
+
+
 def lwe_pack_keyswitch(lwe_in: np.ndarray, pksk: np.ndarray, glwe_out: np.ndarray, in_dimension: int, count: int,
                        fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1) -> None:
     """Packing key switch on host arrays: every group of `count` LWE ciphertexts (in_dimension+1 words each) becomes one GLWE
@@ -615,25 +603,13 @@ def lwe_pack_keyswitch(lwe_in: np.ndarray, pksk: np.ndarray, glwe_out: np.ndarra
     out = (0, .., 0, sum_i b_i X^i) - sum_i X^i sum_j sum_l d_l(a_{i,j}) * pksk[j][l] modulo 2^BITS and X^N + 1, d the
     signed digits of `basis`; pksk is in_dimension x ell x (k+1) x N words, row (j, l) a GLWE ciphertext of
     s_j * 2^(drop_bits + l*log_basis) under the output key, levels least significant first.  1 <= count <= N."""
-    pi, ni, wi = _host_words(lwe_in)
-    pk, nk, wk = _host_words(pksk)
-    po, no, wo = _host_words(glwe_out)
-    _same_width("lwe_in, pksk and glwe_out must have the same word width", wi, wk, wo)
-    lb, ell = _basis_args(basis, wi)
-    check(getattr(lib(), "pfhe_tfhe" + wi + "_pack_keyswitch")(fft._h, glwe_dimension, pi, ni, in_dimension, count, pk, nk, lb,
-                                                              ell, po, no))
+    _pack_keyswitch(False, lwe_in, pksk, glwe_out, in_dimension, count, fft, basis, glwe_dimension)
 
 
 def lwe_pack_keyswitch_dev(lwe_in, pksk, glwe_out, in_dimension: int, count: int, fft: FullComplex64FftTable,
                            basis: ApproxSignedBasis, glwe_dimension: int = 1, stream=None) -> None:
     """the device form, asynchronous and stateless; glwe_out must not overlap an input and may be uninitialised"""
-    pi, ni, wi = _dev_words(lwe_in)
-    pk, nk, wk = _dev_words(pksk)
-    po, no, wo = _dev_words(glwe_out)
-    _same_width("lwe_in, pksk and glwe_out must have the same word width", wi, wk, wo)
-    lb, ell = _basis_args(basis, wi)
-    check(getattr(lib(), "pfhe_tfhe" + wi + "_pack_keyswitch_dev")(fft._h, glwe_dimension, pi, ni, in_dimension, count, pk, nk,
-                                                                  lb, ell, po, no, _stream(stream)))
+    _pack_keyswitch(True, lwe_in, pksk, glwe_out, in_dimension, count, fft, basis, glwe_dimension, stream)
 
 
 def tfhe_generate_pksk_dev(key_in, glwe_key, fft: FullComplex64FftTable, basis: ApproxSignedBasis, rand,
@@ -652,12 +628,8 @@ def tfhe_generate_pksk_dev(key_in, glwe_key, fft: FullComplex64FftTable, basis: 
 
 
 def _extract_pair(name, src, dst, fft, count, glwe_dimension, dev, stream=None):
-    ps, ns, ws = (_dev_words if dev else _host_words)(src)
-    pd, nd, wd = (_dev_words if dev else _host_words)(dst)
-    _same_width("input and output must have the same word width", ws, wd)
-    tail = (_stream(stream),) if dev else ()
-    check(getattr(lib(), "pfhe_tfhe" + ws + name + ("_dev" if dev else ""))(fft._h, glwe_dimension, ps, ns, count, pd, nd,
-                                                                           *tail))
+    _stateless(name, dev, (src, dst), "input and output must have the same word width",
+               lambda w, a, b: (fft._h, glwe_dimension, *a, count, *b), stream)
 
 
 def glwe_sample_extract_first_few(glwe: np.ndarray, out: np.ndarray, fft: FullComplex64FftTable, count: int,

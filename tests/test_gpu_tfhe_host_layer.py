@@ -111,7 +111,8 @@ def test_rotation_host_equals_device(p, bits, k, per_step, multibit):
 @pytest.mark.parametrize("bits", [32, 64])
 @pytest.mark.parametrize("k", [1, 2])
 def test_stateless_host_forms_equal_the_device_forms(p, bits, k):
-    """sample extraction, the key switch at (4, 3), the LWE and the GLWE body"""
+    """sample extraction, the key switch at (4, 3), the LWE and the GLWE body, the packing key switch of 3 ciphertexts
+    per GLWE at (4, 3), the first-few extraction and its expansion"""
     rng = np.random.default_rng(bits + 5 * k)
     fft, (_, ks_basis) = p.FullComplex64FftTable(LOG_N), bases(p, bits)
     zeros = lambda size: np.zeros(size, m.UINT[bits])
@@ -136,6 +137,20 @@ def test_stateless_host_forms_equal_the_device_forms(p, bits, k):
         encrypt(host_ct, glwe_key, fft, k)
         encrypt_dev(dev_ct, dev_words(glwe_key, bits), fft, k)
         assert np.array_equal(host_ct, host_words(dev_ct, bits)) and not np.array_equal(host_ct, glwe)
+    count = 3
+    lwe_in, pksk = rand_words(rng, bits, BATCH * count * (LWE + 1)), rand_words(rng, bits, LWE * KS[1] * (k + 1) * N)
+    host_glwe, dev_glwe = zeros(BATCH * (k + 1) * N), dev_words(zeros(BATCH * (k + 1) * N), bits)
+    p.lwe_pack_keyswitch(lwe_in, pksk, host_glwe, LWE, count, fft, ks_basis, k)
+    p.lwe_pack_keyswitch_dev(dev_words(lwe_in, bits), dev_words(pksk, bits), dev_glwe, LWE, count, fft, ks_basis, k)
+    assert np.array_equal(host_glwe, host_words(dev_glwe, bits)) and host_glwe.any()
+    host_multi, dev_multi = zeros(BATCH * (k * N + count)), dev_words(zeros(BATCH * (k * N + count)), bits)
+    p.glwe_sample_extract_first_few(host_glwe, host_multi, fft, count, k)
+    p.glwe_sample_extract_first_few_dev(dev_glwe, dev_multi, fft, count, k)
+    assert np.array_equal(host_multi, host_words(dev_multi, bits)) and host_multi.any()
+    host_each, dev_each = zeros(BATCH * count * (k * N + 1)), dev_words(zeros(BATCH * count * (k * N + 1)), bits)
+    p.multimsg_lwe_extract(host_multi, host_each, fft, count, k)
+    p.multimsg_lwe_extract_dev(dev_multi, dev_each, fft, count, k)
+    assert np.array_equal(host_each, host_words(dev_each, bits)) and host_each.any()
 
 
 @pytest.mark.parametrize("bits", [32, 64])

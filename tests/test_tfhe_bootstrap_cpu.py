@@ -97,6 +97,89 @@ def test_overlapping_key_switch_output_is_refused_before_the_device(pfhe):
     assert lib.pfhe_tfhe32_keyswitch_dev(0, at(0), 5, 4, at(64), 24, 2, 4, 2, at(80), 3, None) == BAD_ARGUMENT
 
 
+NO_DEVICE = 34
+
+
+class TableStandIn(C.Structure):
+    """What the library's table starts with: the device, log N and N.  With device -1 a call that passes every argument
+    check ends in NoDevice, so the order of the refusals before it shows without a GPU; nothing is dereferenced."""
+    _fields_ = [("device", C.c_int), ("log_n", C.c_uint32), ("n", C.c_size_t), ("tw", C.c_void_p)]
+
+
+def last_error(lib):
+    return lib.pfhe_last_error().decode(errors="replace")
+
+
+@pytest.mark.parametrize("w, size", [("", 8), ("32", 4)])
+def test_sample_extraction_refuses_its_arguments_in_order(pfhe, w, size):
+    """the table, the dimension, the index, the lengths, the empty batch, null pointers, overlap (the device form only:
+    the host form refuses none), and only then the device"""
+    lib = pfhe.lib()
+    t = TableStandIn(-1, 3, 8, None)                 # N = 8
+    fft = C.cast(C.pointer(t), C.c_void_p)
+    buf = (C.c_uint64 * 1024)()
+    ptr = C.cast(buf, C.c_void_p)
+    n, k = 8, 2
+    glwe, lwe = 3 * (k + 1) * n, 3 * (k * n + 1)
+    far = C.c_void_p(ptr.value + glwe * size)        # the first byte after the input
+    for form, tail in (("sample_extract_dev", (None,)), ("sample_extract", ())):
+        call = getattr(lib, f"pfhe_tfhe{w}_{form}")
+        assert call(None, 0, None, 5, n, None, 3, *tail) == BAD_ARGUMENT        # the table before anything
+        for kk in (0, 65, 2 ** 40):
+            assert call(fft, kk, None, 5, n, None, 3, *tail) == BAD_ARGUMENT
+            assert last_error(lib) == "sample extraction: glwe_dimension must be in 1..64"
+        for index in (n, 2 ** 40):
+            assert call(fft, k, None, 5, index, None, 3, *tail) == BAD_ARGUMENT
+            assert last_error(lib) == "sample extraction: index must be below N"
+        assert call(fft, k, ptr, glwe + 1, n - 1, far, lwe, *tail) == BAD_LENGTH
+        assert call(fft, k, ptr, glwe, n - 1, far, lwe + 1, *tail) == BAD_LENGTH
+        assert last_error(lib) == "sample extraction: glwe must be batch*(k+1)*N words and lwe batch*(k*N+1)"
+        assert call(fft, k, None, 0, 0, None, 0, *tail) == 0                    # an empty batch: no pointer is looked at
+        assert call(fft, k, None, glwe, 0, far, lwe, *tail) == BAD_ARGUMENT
+        assert call(fft, k, ptr, glwe, 0, None, lwe, *tail) == BAD_ARGUMENT
+        assert call(fft, k, ptr, glwe, 0, far, lwe, *tail) == NO_DEVICE         # the last check
+    dev, host = getattr(lib, f"pfhe_tfhe{w}_sample_extract_dev"), getattr(lib, f"pfhe_tfhe{w}_sample_extract")
+    for out in (ptr, C.c_void_p(far.value - 1), C.c_void_p(ptr.value - lwe * size + 1)):   # the same start, one byte shared
+        assert dev(fft, k, ptr, glwe, 0, out, lwe, None) == BAD_ARGUMENT
+        assert last_error(lib) == "sample extraction: the output must not overlap the input"
+        assert host(fft, k, ptr, glwe, 0, out, lwe) == NO_DEVICE
+    assert dev(fft, k, ptr, glwe, 0, C.c_void_p(ptr.value - lwe * size), lwe, None) == NO_DEVICE    # adjacent below
+
+
+def test_the_stateless_calls_on_a_device_index_look_at_it_last(pfhe):
+    """device -1: the null test and (device forms) the overlap test come before the device is asked about; the host form of
+    the key switch refuses no overlap, the modulus switch refuses none at all, and inputs may overlap each other"""
+    lib = pfhe.lib()
+    buf = (C.c_uint64 * 256)()
+    ptr = C.cast(buf, C.c_void_p)
+    far, out = C.c_void_p(ptr.value + 512), C.c_void_p(ptr.value + 1024)
+    for w in ("", "32"):
+        ms = getattr(lib, f"pfhe_tfhe{w}_modswitch_dev")
+        for log_n in (0, 15):
+            assert ms(-1, ptr, 6, 5, log_n, far, 5, out, 1, None) == BAD_ARGUMENT
+            assert last_error(lib) == "modulus switch: log_n must be in 1..14"
+        for dim in (0, 2 ** 32 - 1):
+            assert ms(-1, ptr, 6, dim, 10, far, 5, out, 1, None) == BAD_ARGUMENT
+            assert last_error(lib) == "modulus switch: lwe_dimension must be in 1..2^32-2"
+        assert ms(-1, None, 6, 5, 10, far, 5, out, 1, None) == BAD_ARGUMENT
+        assert ms(-1, ptr, 6, 5, 10, far, 5, out, 1, None) == NO_DEVICE
+        assert ms(-1, ptr, 6, 5, 10, ptr, 5, ptr, 1, None) == NO_DEVICE
+        dev, host = getattr(lib, f"pfhe_tfhe{w}_keyswitch_dev"), getattr(lib, f"pfhe_tfhe{w}_keyswitch")
+        for fn, tail in ((dev, (None,)), (host, ())):
+            for din, dout in ((2 ** 31 - 1, 2), (4, 2 ** 31 - 1)):
+                assert fn(-1, ptr, 5, din, far, 24, dout, 4, 2, out, 3, *tail) == BAD_ARGUMENT
+                assert last_error(lib) == "key switch: both dimensions must be in 1..2^31-2"
+            assert fn(-1, ptr, 5, 4, far, 23, 2, 4, 2, out, 3, *tail) == BAD_LENGTH
+            assert last_error(lib).startswith("key switch: lwe_in must be batch*(in_dimension+1) words, ksk ")
+            assert fn(-1, ptr, 5, 4, None, 24, 2, 4, 2, out, 3, *tail) == BAD_ARGUMENT
+            assert fn(-1, ptr, 5, 4, far, 24, 2, 4, 2, out, 3, *tail) == NO_DEVICE
+            assert fn(-1, ptr, 5, 4, ptr, 24, 2, 4, 2, out, 3, *tail) == NO_DEVICE     # the inputs overlap each other
+        for a, b in ((ptr, far), (far, ptr)):                                          # the output on lwe_in, then on ksk
+            assert dev(-1, a, 5, 4, b, 24, 2, 4, 2, ptr, 3, None) == BAD_ARGUMENT
+            assert last_error(lib) == "key switch: the output must not overlap an input"
+            assert host(-1, a, 5, 4, b, 24, 2, 4, 2, ptr, 3) == NO_DEVICE
+
+
 def test_create_reports_the_rotations_statuses_first(pfhe):
     import torch
     lib = pfhe.lib()

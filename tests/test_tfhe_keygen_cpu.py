@@ -159,6 +159,135 @@ def test_the_key_switch_key_call_refuses_its_arguments_in_order(pfhe, w, bits):
     assert call(-1, ptr, 8, ptr, 3, 4, 3, far, 96, None) == NO_DEVICE               # device -1, the last check
 
 
+class TableStandIn(C.Structure):
+    """What the library's table starts with: the device, log N and N.  With device -1 a call that passes every argument
+    check ends in NoDevice, so the order of the refusals before it shows without a GPU; nothing is dereferenced."""
+    _fields_ = [("device", C.c_int), ("log_n", C.c_uint32), ("n", C.c_size_t), ("tw", C.c_void_p)]
+
+
+@pytest.fixture(scope="module")
+def table():
+    t = TableStandIn(-1, 3, 8, None)     # N = 8
+    return t, C.cast(C.pointer(t), C.c_void_p)
+
+
+@pytest.mark.parametrize("w", ["", "32"])
+def test_the_lwe_body_forms_differ_only_in_the_overlap_test(pfhe, w):
+    """device -1: the device form refuses the overlap before it asks about the device, the host form refuses none"""
+    lib = pfhe.lib()
+    buf = (C.c_uint64 * 64)()
+    ptr = C.cast(buf, C.c_void_p)
+    dev, host = getattr(lib, f"pfhe_tfhe{w}_lwe_body_mac_dev"), getattr(lib, f"pfhe_tfhe{w}_lwe_body_mac")
+    for key in (ptr, C.c_void_p(ptr.value + 8 * (8 if w == "" else 4) - 1)):       # the same start; the last byte
+        assert dev(-1, ptr, 8, 3, key, 3, 0, None) == BAD_ARGUMENT
+        assert last_error(lib) == "LWE body: the key must not overlap the ciphertexts"
+        assert host(-1, ptr, 8, 3, key, 3, 0) == NO_DEVICE
+    assert dev(-1, ptr, 8, 3, C.c_void_p(ptr.value + 8 * (8 if w == "" else 4)), 3, 0, None) == NO_DEVICE
+
+
+@pytest.mark.parametrize("w, size", [("", 8), ("32", 4)])
+def test_the_glwe_body_call_refuses_its_arguments_in_order(pfhe, table, w, size):
+    """after the table and the dimension: the lengths, the empty batch, null pointers, overlap (the device form only), and
+    only then the device"""
+    lib = pfhe.lib()
+    _, fft = table
+    buf = (C.c_uint64 * 1024)()
+    ptr = C.cast(buf, C.c_void_p)
+    n, k = 8, 2
+    glwe, key = 2 * (k + 1) * n, k * n
+    far = C.c_void_p(ptr.value + glwe * size)        # the first byte after the ciphertexts
+    for form, tail in (("glwe_body_mac_dev", (None,)), ("glwe_body_mac", ())):
+        call = getattr(lib, f"pfhe_tfhe{w}_{form}")
+        assert call(fft, k, ptr, glwe + 1, far, key, 0, *tail) == BAD_LENGTH
+        assert call(fft, k, ptr, glwe, far, key + 1, 0, *tail) == BAD_LENGTH
+        assert last_error(lib) == "GLWE body: glwe must be batch*(k+1)*N words and key k*N words"
+        assert call(fft, k, None, 0, None, key, 1, *tail) == 0                  # an empty batch: no pointer is looked at
+        assert call(fft, k, None, glwe, far, key, 0, *tail) == BAD_ARGUMENT
+        assert call(fft, k, ptr, glwe, None, key, 0, *tail) == BAD_ARGUMENT
+        assert call(fft, k, ptr, glwe, far, key, 0, *tail) == NO_DEVICE         # the last check
+    dev, host = getattr(lib, f"pfhe_tfhe{w}_glwe_body_mac_dev"), getattr(lib, f"pfhe_tfhe{w}_glwe_body_mac")
+    for z in (ptr, C.c_void_p(far.value - 1)):
+        assert dev(fft, k, ptr, glwe, z, key, 0, None) == BAD_ARGUMENT
+        assert last_error(lib) == "GLWE body: the key must not overlap the ciphertexts"
+        assert host(fft, k, ptr, glwe, z, key, 0) == NO_DEVICE
+
+
+@pytest.mark.parametrize("w, size", [("", 8), ("32", 4)])
+def test_the_gadget_call_refuses_its_arguments_in_order(pfhe, table, w, size):
+    """after the plan's checks: the lengths, the empty batch, null pointers, overlap, the device"""
+    lib = pfhe.lib()
+    _, fft = table
+    call = getattr(lib, f"pfhe_tfhe{w}_ggsw_add_gadget_dev")
+    buf = (C.c_uint64 * 1024)()
+    ptr = C.cast(buf, C.c_void_p)
+    n, k, ell = 8, 1, 2
+    one = (k + 1) * ell * (k + 1) * n
+    far = C.c_void_p(ptr.value + 2 * one * size)
+    assert call(fft, k, 4, ell, ptr, 2 * one + 1, far, 2, None) == BAD_LENGTH
+    assert call(fft, k, 4, ell, ptr, 2 * one, far, 3, None) == BAD_LENGTH
+    assert last_error(lib) == "GGSW gadget: ggsw must be count*(k+1)*ell*(k+1)*N words and messages count words"
+    assert call(fft, k, 4, ell, None, 0, None, 0, None) == 0
+    assert call(fft, k, 4, ell, None, 2 * one, far, 2, None) == BAD_ARGUMENT
+    assert call(fft, k, 4, ell, ptr, 2 * one, None, 2, None) == BAD_ARGUMENT
+    for m in (ptr, C.c_void_p(far.value - 1)):
+        assert call(fft, k, 4, ell, ptr, 2 * one, m, 2, None) == BAD_ARGUMENT
+        assert last_error(lib) == "GGSW gadget: the messages must not overlap the GGSWs"
+    assert call(fft, k, 4, ell, ptr, 2 * one, far, 2, None) == NO_DEVICE
+
+
+@pytest.mark.parametrize("w, size", [("", 8), ("32", 4)])
+def test_the_bootstrapping_key_call_refuses_its_arguments_in_order(pfhe, table, w, size):
+    """after the shape: the lengths, null pointers, the alignment of the two outputs, overlap (each output against every
+    other buffer; the keys may share bytes), the size of the launches, and only then the device"""
+    lib = pfhe.lib()
+    _, fft = table
+    bsk = getattr(lib, f"pfhe_tfhe{w}_bsk_generate_dev")
+    buf = (C.c_uint64 * 4096)()
+    base = (C.addressof(buf) + 15) & ~15
+    at = lambda off: C.c_void_p(base + off)
+    n_poly, k, ell, n = 8, 1, 2, 3
+    words = n * (k + 1) * ell * (k + 1) * n_poly      # 192 torus words, as many complex values
+    ggsw, out, s, z = base, base + 4096, base + 8192, base + 8192 + 256
+
+    def call(s, z, ggsw, out, len_z=k * n_poly, len_ggsw=words, len_out=words, n=n):
+        return bsk(fft, k, 4, ell, 0, s and C.c_void_p(s), n, z and C.c_void_p(z), len_z, ggsw and C.c_void_p(ggsw), len_ggsw,
+                   C.cast(C.c_void_p(out), C.POINTER(C.c_double)), len_out, None)
+
+    lengths = "bootstrapping key: glwe_key must be k*N words, ggsw_torus keys*(k+1)*ell*(k+1)*N words and bsk_out as many complex values, keys = n or (n/g)*2^g"
+    for kw in ({"len_z": k * n_poly + 1}, {"len_ggsw": words + 1}, {"len_out": words - 1}):
+        assert call(s, z, ggsw, out, **kw) == BAD_LENGTH and last_error(lib) == lengths
+    for args in ((None, z, ggsw, out), (s, None, ggsw, out), (s, z, None, out), (s, z, ggsw, None)):
+        assert call(*args) == BAD_ARGUMENT
+    assert call(s, z, ggsw, out, len_z=0) == BAD_LENGTH
+    assert call(None, z, ggsw + 8, out + 8) == BAD_ARGUMENT and last_error(lib) == lengths      # null before the alignment
+    assert call(s, z, ggsw + 8, ggsw + 8) == BAD_ARGUMENT and last_error(lib) == "ggsw must be 16-byte aligned"
+    assert call(s, z, ggsw, ggsw + 8) == BAD_ARGUMENT and last_error(lib) == "bsk must be 16-byte aligned"
+    overlap = "bootstrapping key: the outputs must overlap neither each other nor a key"
+    for args in ((s, z, ggsw, ggsw), (s, z, ggsw, ggsw + words * size - 16), (ggsw + 8, z, ggsw, out), (s, ggsw + 8, ggsw, out),
+                 (out + 8, z, ggsw, out), (s, out + words * 16 - 1, ggsw, out)):
+        assert call(*args) == BAD_ARGUMENT and last_error(lib) == overlap, args
+    assert call(s, s, ggsw, out) == NO_DEVICE                                   # the keys may overlap each other
+    assert call(s, z, ggsw, out) == NO_DEVICE                                   # the last check
+    # 2^30 keys of 4 rows are more rows than a launch takes: judged after the overlap and before the device.  The pointers
+    # are never followed
+    big = dict(n=2 ** 30, len_ggsw=2 ** 36, len_out=2 ** 36)
+    assert call(2 ** 46, 2 ** 46 + 2 ** 40, 2 ** 44, 2 ** 45, **big) == BAD_LENGTH
+    assert call(2 ** 46, 2 ** 46 + 2 ** 40, 2 ** 44, 2 ** 44, **big) == BAD_ARGUMENT and last_error(lib) == overlap
+
+
+@pytest.mark.parametrize("w", ["", "32"])
+def test_the_key_switch_key_call_tests_ksk_against_either_key(pfhe, w):
+    lib = pfhe.lib()
+    call = getattr(lib, f"pfhe_tfhe{w}_ksk_generate_dev")
+    buf = (C.c_uint64 * 4096)()
+    ptr = C.cast(buf, C.c_void_p)
+    far, ksk = C.c_void_p(ptr.value + 8192), C.c_void_p(ptr.value + 16384)
+    for key_in, key_out in ((ksk, far), (far, ksk)):
+        assert call(-1, key_in, 8, key_out, 3, 4, 3, ksk, 96, None) == BAD_ARGUMENT
+        assert last_error(lib) == "key-switch key: the keys must not overlap ksk"
+    assert call(-1, ptr, 8, far, 3, 4, 3, ksk, 96, None) == NO_DEVICE
+
+
 def test_no_fallback_without_a_device(pfhe):
     """without a GPU the host forms report NoDevice and leave the buffers as they were: nothing is computed on the CPU"""
     import torch

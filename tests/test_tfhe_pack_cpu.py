@@ -145,6 +145,42 @@ def test_the_packing_key_call_refuses_its_arguments_in_order(pfhe, table, w, bit
 
 
 @pytest.mark.parametrize("w", ["", "32"])
+def test_the_packing_calls_test_every_written_buffer_and_no_other(pfhe, table, w):
+    """the packing key against either key, one at a time, and the size of its launch after the overlap; the host forms
+    refuse no overlap, and inputs may overlap each other"""
+    lib = pfhe.lib()
+    _, fft = table
+    gen = getattr(lib, f"pfhe_tfhe{w}_pksk_generate_dev")
+    buf = (C.c_uint64 * 8192)()
+    ptr = C.cast(buf, C.c_void_p)
+    z, far = C.c_void_p(ptr.value + 1024), C.c_void_p(ptr.value + 8192)
+    n, k, in_dim, ell, count = 8, 1, 4, 3, 3
+    length = in_dim * ell * (k + 1) * n
+    for key_in, glwe_key in ((far, z), (ptr, far)):
+        assert gen(fft, k, key_in, in_dim, glwe_key, k * n, 4, ell, far, length, None) == BAD_ARGUMENT
+        assert last_error(lib) == "packing key: the keys must not overlap pksk"
+    assert gen(fft, k, ptr, in_dim, ptr, k * n, 4, ell, far, length, None) == NO_DEVICE
+    # 2^30 * 3 rows are more than a launch takes: judged after the overlap and before the device; pointers never followed
+    at = lambda a: C.c_void_p(a)
+    big = 2 ** 30 * ell * (k + 1) * n
+    assert gen(fft, k, at(2 ** 40), 2 ** 30, at(2 ** 41), k * n, 4, ell, at(2 ** 44), big, None) == BAD_LENGTH
+    assert gen(fft, k, at(2 ** 44), 2 ** 30, at(2 ** 41), k * n, 4, ell, at(2 ** 44), big, None) == BAD_ARGUMENT
+    len_in, len_key, len_out = 2 * count * (in_dim + 1), in_dim * ell * (k + 1) * n, 2 * (k + 1) * n
+    dev, host = getattr(lib, f"pfhe_tfhe{w}_pack_keyswitch_dev"), getattr(lib, f"pfhe_tfhe{w}_pack_keyswitch")
+    assert dev(fft, k, ptr, len_in, in_dim, count, ptr, len_key, 4, ell, far, len_out, None) == NO_DEVICE
+    for a, b in ((ptr, far), (far, ptr)):
+        assert dev(fft, k, a, len_in, in_dim, count, b, len_key, 4, ell, ptr, len_out, None) == BAD_ARGUMENT
+        assert last_error(lib) == "packing key switch: the output must not overlap an input"
+        assert host(fft, k, a, len_in, in_dim, count, b, len_key, 4, ell, ptr, len_out) == NO_DEVICE
+    glwe, multi, lwe = 2 * (k + 1) * n, 2 * (k * n + count), 2 * count * (k * n + 1)
+    for name, len_a, len_b, text in (("sample_extract_first_few", glwe, multi, "multi-message extraction: the output must not overlap the input"),
+                                     ("multimsg_extract", multi, lwe, "multi-message expansion: the output must not overlap the input")):
+        assert getattr(lib, f"pfhe_tfhe{w}_{name}_dev")(fft, k, ptr, len_a, count, ptr, len_b, None) == BAD_ARGUMENT
+        assert last_error(lib) == text
+        assert getattr(lib, f"pfhe_tfhe{w}_{name}")(fft, k, ptr, len_a, count, ptr, len_b) == NO_DEVICE
+
+
+@pytest.mark.parametrize("w", ["", "32"])
 def test_the_multi_message_calls_refuse_their_arguments_in_order(pfhe, table, w):
     """the table, the dimension, count, the lengths, the empty batch, null pointers, overlap (device forms), the device"""
     lib = pfhe.lib()
