@@ -153,24 +153,18 @@ int monomial(const TableSet &t, W coeff, size_t degree, W *values, size_t len, b
     DeviceGuard g(t.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     const u64 deg = (u64)degree & (2 * (u64)t.n - 1);
-    const auto run = [&](W *out) -> int {
+    const auto run = [&](W *out, hipStream_t st) -> int {
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             const u32 l0 = (u32)gi * kMaxMonomialLimbs, lg = std::min<u32>(kMaxMonomialLimbs, t.L - l0);
-            PFHE_TRY(launch_monomial(out + (size_t)l0 * t.n, t.primes_dev + l0, lg, t.log_n, deg, groups[gi], s));
+            PFHE_TRY(launch_monomial(out + (size_t)l0 * t.n, t.primes_dev + l0, lg, t.log_n, deg, groups[gi], st));
         }
         return PFHE_OK;
     };
     if (!host)  // device output: launches on the caller's stream, nothing else (capturable)
-        return run(values);
+        return run(values, s);
     // host output: the caller's stream is not involved (pooled staging context, no allocation in steady state)
-    HostStage st(t.device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *out_dev = nullptr;
-    PFHE_TRY(st.alloc(len * sizeof(W), &out_dev));
-    s = st.stream();
-    PFHE_TRY(run(static_cast<W *>(out_dev)));
-    PFHE_TRY(st.download(values, out_dev, len * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_out(values, len * sizeof(W))};
+    return staged_call(t.device, bufs, [&](void *const *d, hipStream_t st) { return run(static_cast<W *>(d[0]), st); });
 }
 
 #define PFHE_TABLE_HOST_LAYER(W)                                                                                          \
@@ -308,6 +302,7 @@ int pfhe_fill_uniform_dev(int device, uint64_t *dst, size_t len, const uint64_t 
     if (!dst || !moduli || moduli_count == 0 || poly_len == 0) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_TRY(capi_check_device(device));
     DeviceGuard g(device);
+    // not a staged_call: the list is uploaded and waited for, then the kernel runs on the caller's stream
     HostStage st(device);  // the modulus list travels through a pooled staging context (no allocation per call)
     if (!st.ok()) return PFHE_ERR_HIP;
     void *md = nullptr;

@@ -195,37 +195,6 @@ int rns_moduli_product_impl(const RnsHost *h, W *out, size_t len) {
     return PFHE_OK;
 }
 
-template <class W>
-int rns_compose_dev_impl(const RnsHost *h, const W *in_dev, size_t len_in, W *out_dev, size_t len_out, size_t value_count,
-                         void *stream) {
-    if (!h || ((!in_dev || !out_dev) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len_in != value_count * h->par.dev.L || len_out != value_count * words_per_value<W>(*h)) {
-        set_last_error("compose: multi_residues must hold moduli_count*value_count words and the output "
-                       "value_count*big_uint_value_len words");
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return rns_compose_dev(h->par, (const DevWord<W> *)in_dev, (DevWord<W> *)out_dev, value_count, (hipStream_t)stream);
-}
-
-template <class W>
-int rns_compose_host_impl(const RnsHost *h, const W *in, size_t len_in, W *out, size_t len_out, size_t value_count) {
-    if (!h || ((!in || !out) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len_in != value_count * h->par.dev.L || len_out != value_count * words_per_value<W>(*h)) return PFHE_ERR_BAD_LENGTH;
-    if (value_count == 0) return PFHE_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(h->device);  // pooled staging context: no allocation in steady state
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *i = nullptr, *o = nullptr;
-    PFHE_TRY(st.upload(in, len_in * sizeof(W), &i));
-    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
-    PFHE_TRY(rns_compose_dev(h->par, (const DevWord<W> *)i, (DevWord<W> *)o, value_count, st.stream()));
-    PFHE_TRY(st.download(out, o, len_out * sizeof(W)));
-    return st.finish();
-}
-
 inline int small_modulus_check(const RnsHost &h, u64 small_value_modulus) {
     for (u64 q : h.moduli) {
         if (small_value_modulus >= q || small_value_modulus < 2) {  // base.rs:288-292, :337-341
@@ -236,44 +205,51 @@ inline int small_modulus_check(const RnsHost &h, u64 small_value_modulus) {
     return PFHE_OK;
 }
 
+// The eight steps below are one template each for their host and device forms.  Each refuses in this
+// order: a null handle; a null pointer, when the count is not zero; a bad level or value; a wrong length; what only this
+// step asks; then PFHE_OK for an empty batch, and form_call refuses a device that cannot be made current.  Where the two
+// forms have always differed, a line that names `form` keeps the difference.
+
 template <class W>
-int rns_wrapping_dev_impl(const RnsHost *h, const W *small_dev, size_t value_count, W *multi_dev, size_t len_out,
-                          u64 small_value_modulus, void *stream) {
-    if (!h || ((!small_dev || !multi_dev) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len_out != value_count * h->par.dev.L) return PFHE_ERR_BAD_LENGTH;
-    PFHE_TRY(small_modulus_check(*h, small_value_modulus));
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return rns_wrapping_decompose_dev(h->par, (const DevWord<W> *)small_dev, (DevWord<W> *)multi_dev, value_count,
-                                      small_value_modulus, (hipStream_t)stream);
+int rns_compose(Form form, const RnsHost *h, const W *in, size_t len_in, W *out, size_t len_out, size_t value_count,
+                void *stream) {
+    if (!h || ((!in || !out) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
+    if (len_in != value_count * h->par.dev.L || len_out != value_count * words_per_value<W>(*h)) {
+        set_last_error("compose: multi_residues must hold moduli_count*value_count words and the output "
+                       "value_count*big_uint_value_len words");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (value_count == 0) return PFHE_OK;
+    const StageBuf bufs[] = {stage_in(in, len_in * sizeof(W)), stage_out(out, len_out * sizeof(W))};
+    return form_call(h->device, form, bufs, (hipStream_t)stream, [&](void *const *d, hipStream_t s) {
+        return rns_compose_dev(h->par, (const DevWord<W> *)d[0], (DevWord<W> *)d[1], value_count, s);
+    });
 }
 
 template <class W>
-int rns_wrapping_host_impl(const RnsHost *h, const W *small, size_t value_count, W *multi, size_t len_out,
-                           u64 small_value_modulus) {
+int rns_wrapping(Form form, const RnsHost *h, const W *small, size_t value_count, W *multi, size_t len_out,
+                 u64 small_value_modulus, void *stream) {
     if (!h || ((!small || !multi) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
     if (len_out != value_count * h->par.dev.L) return PFHE_ERR_BAD_LENGTH;
+    if (form == Form::kHost && value_count == 0) return PFHE_OK;  // the device form judges the modulus first
+    PFHE_TRY(small_modulus_check(*h, small_value_modulus));
     if (value_count == 0) return PFHE_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(h->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *i = nullptr, *o = nullptr;
-    PFHE_TRY(st.upload(small, value_count * sizeof(W), &i));
-    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
-    PFHE_TRY(rns_wrapping_dev_impl<W>(h, (const W *)i, value_count, (W *)o, len_out, small_value_modulus, st.stream()));
-    PFHE_TRY(st.download(multi, o, len_out * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(small, value_count * sizeof(W)), stage_out(multi, len_out * sizeof(W))};
+    return form_call(h->device, form, bufs, (hipStream_t)stream, [&](void *const *d, hipStream_t s) {
+        return rns_wrapping_decompose_dev(h->par, (const DevWord<W> *)d[0], (DevWord<W> *)d[1], value_count,
+                                          small_value_modulus, s);
+    });
 }
 
 // `factors`: L ShoupFactor<W> (value, quotient) pairs.  64-bit pairs are used as given; for 32-bit ones the 64-bit
 // quotient the kernels multiply by is derived from the value (the product is the same canonical residue)
 template <class W>
-int rns_add_scaled_dev_impl(const RnsHost *h, const W *small_dev, size_t value_count, W *acc_dev, size_t len_acc,
-                            u64 small_value_modulus, bool centred, const W *factors, void *stream) {
-    if (!h || !factors || ((!small_dev || !acc_dev) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
+int rns_add_scaled(Form form, const RnsHost *h, const W *small, size_t value_count, W *acc, size_t len_acc,
+                   u64 small_value_modulus, bool centred, const W *factors, void *stream) {
+    if (!h || !factors || ((!small || !acc) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
     const u32 L = h->par.dev.L;
     if (len_acc != value_count * L) return PFHE_ERR_BAD_LENGTH;
+    if (form == Form::kHost && value_count == 0) return PFHE_OK;  // the device form judges modulus and factors first
     if (centred) PFHE_TRY(small_modulus_check(*h, small_value_modulus));
     std::vector<u64> pairs(2 * (size_t)L);
     for (u32 i = 0; i < L; ++i) {
@@ -285,61 +261,26 @@ int rns_add_scaled_dev_impl(const RnsHost *h, const W *small_dev, size_t value_c
         pairs[2 * i + 1] = sizeof(W) == 8 ? (u64)factors[2 * i + 1]
                                           : (u64)((((unsigned __int128)factors[2 * i]) << 64) / h->moduli[i]);
     }
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    if (value_count == 0) return PFHE_OK;
     // base.rs:343,371-378: a small modulus of two takes the unsigned branch (a 1 stays +1)
     const bool lift = centred && small_value_modulus != 2;
-    return rns_add_decompose_scaled_dev(h->par, (const DevWord<W> *)small_dev, (DevWord<W> *)acc_dev, value_count,
-                                        small_value_modulus, lift, pairs.data(), (hipStream_t)stream);
+    const StageBuf bufs[] = {stage_in(small, value_count * sizeof(W)), stage_inout(acc, len_acc * sizeof(W))};
+    return form_call(h->device, form, bufs, (hipStream_t)stream, [&](void *const *d, hipStream_t s) {
+        return rns_add_decompose_scaled_dev(h->par, (const DevWord<W> *)d[0], (DevWord<W> *)d[1], value_count,
+                                            small_value_modulus, lift, pairs.data(), s);
+    });
 }
 
 template <class W>
-int rns_add_scaled_host_impl(const RnsHost *h, const W *small, size_t value_count, W *acc, size_t len_acc,
-                             u64 small_value_modulus, bool centred, const W *factors) {
-    if (!h || !factors || ((!small || !acc) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len_acc != value_count * h->par.dev.L) return PFHE_ERR_BAD_LENGTH;
-    if (value_count == 0) return PFHE_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(h->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *i = nullptr, *a = nullptr;
-    PFHE_TRY(st.upload(small, value_count * sizeof(W), &i));
-    PFHE_TRY(st.upload(acc, len_acc * sizeof(W), &a));
-    PFHE_TRY(rns_add_scaled_dev_impl<W>(h, (const W *)i, value_count, (W *)a, len_acc, small_value_modulus, centred, factors,
-                                        st.stream()));
-    PFHE_TRY(st.download(acc, a, len_acc * sizeof(W)));
-    return st.finish();
-}
-
-template <class W>
-int rns_decompose_big_dev_impl(const RnsHost *h, const W *values_dev, size_t len_in, W *multi_dev, size_t len_out,
-                               size_t value_count, void *stream) {
-    if (!h || ((!values_dev || !multi_dev) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len_in != value_count * words_per_value<W>(*h) || len_out != value_count * h->par.dev.L) return PFHE_ERR_BAD_LENGTH;
-    if (value_count == 0) return PFHE_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return rns_decompose_big_dev(h->par, (const DevWord<W> *)values_dev, (DevWord<W> *)multi_dev, value_count,
-                                 (hipStream_t)stream);
-}
-
-template <class W>
-int rns_decompose_big_host_impl(const RnsHost *h, const W *values, size_t len_in, W *multi, size_t len_out,
-                                size_t value_count) {
+int rns_decompose_big(Form form, const RnsHost *h, const W *values, size_t len_in, W *multi, size_t len_out,
+                      size_t value_count, void *stream) {
     if (!h || ((!values || !multi) && value_count)) return PFHE_ERR_BAD_ARGUMENT;
     if (len_in != value_count * words_per_value<W>(*h) || len_out != value_count * h->par.dev.L) return PFHE_ERR_BAD_LENGTH;
     if (value_count == 0) return PFHE_OK;
-    DeviceGuard g(h->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(h->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *i = nullptr, *o = nullptr;
-    PFHE_TRY(st.upload(values, len_in * sizeof(W), &i));
-    PFHE_TRY(st.alloc(len_out * sizeof(W), &o));
-    PFHE_TRY(rns_decompose_big_dev_impl<W>(h, (const W *)i, len_in, (W *)o, len_out, value_count, st.stream()));
-    PFHE_TRY(st.download(multi, o, len_out * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(values, len_in * sizeof(W)), stage_out(multi, len_out * sizeof(W))};
+    return form_call(h->device, form, bufs, (hipStream_t)stream, [&](void *const *d, hipStream_t s) {
+        return rns_decompose_big_dev(h->par, (const DevWord<W> *)d[0], (DevWord<W> *)d[1], value_count, s);
+    });
 }
 
 /* ---- BigUintApproxSignedBasis<W> ---- */
@@ -374,132 +315,81 @@ int basis_scalars_residue_impl(const BasisHost *b, W *out, size_t len) {
 }
 
 template <class W>
-int basis_init_dev_impl(const BasisHost *b, W *values_dev, size_t len, uint8_t *carries_dev, size_t count, void *stream) {
-    if (!b || ((!values_dev || !carries_dev) && count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;  // basis.rs:332
-    DeviceGuard g(b->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return basis_init_value_carry_dev(b->par, (DevWord<W> *)values_dev, carries_dev, count, (hipStream_t)stream);
-}
-
-template <class W>
-int basis_init_host_impl(const BasisHost *b, W *values, size_t len, uint8_t *carries, size_t count) {
+int basis_init(Form form, const BasisHost *b, W *values, size_t len, uint8_t *carries, size_t count, void *stream) {
     if (!b || ((!values || !carries) && count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;
+    if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;  // basis.rs:332
     if (count == 0) return PFHE_OK;
-    DeviceGuard g(b->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(b->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *v = nullptr, *c = nullptr;
-    PFHE_TRY(st.upload(values, len * sizeof(W), &v));
-    PFHE_TRY(st.alloc(count, &c));
-    PFHE_TRY(basis_init_value_carry_dev(b->par, (DevWord<W> *)v, (unsigned char *)c, count, st.stream()));
-    PFHE_TRY(st.download(values, v, len * sizeof(W)));
-    PFHE_TRY(st.download(carries, c, count));
-    return st.finish();
+    const StageBuf bufs[] = {stage_inout(values, len * sizeof(W)), stage_out(carries, count)};
+    return form_call(b->device, form, bufs, (hipStream_t)stream, [&](void *const *d, hipStream_t s) {
+        return basis_init_value_carry_dev(b->par, (DevWord<W> *)d[0], (unsigned char *)d[1], count, s);
+    });
 }
 
+// a copy into `adjusted`, then the in-place step on it
 template <class W>
-int basis_init_to_dev_impl(const BasisHost *b, const W *values_dev, size_t len, W *adjusted_dev, uint8_t *carries_dev,
-                           size_t count, void *stream) {
-    if (!b || ((!values_dev || !adjusted_dev || !carries_dev) && count)) return PFHE_ERR_BAD_ARGUMENT;
+int basis_init_to(Form form, const BasisHost *b, const W *values, size_t len, W *adjusted, uint8_t *carries, size_t count,
+                  void *stream) {
+    if (!b || ((!values || !adjusted || !carries) && count)) return PFHE_ERR_BAD_ARGUMENT;
     if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;  // basis.rs:378-379
     if (count == 0) return PFHE_OK;
-    DeviceGuard g(b->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    if (adjusted_dev != values_dev)
-        PFHE_HIP(hipMemcpyAsync(adjusted_dev, values_dev, len * sizeof(W), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return basis_init_value_carry_dev(b->par, (DevWord<W> *)adjusted_dev, carries_dev, count, (hipStream_t)stream);
+    if (adjusted != values && form == Form::kHost) std::memcpy(adjusted, values, len * sizeof(W));
+    if (adjusted != values && form == Form::kDevice) {
+        DeviceGuard g(b->device);
+        if (!g.ok) return PFHE_ERR_NO_DEVICE;
+        PFHE_HIP(hipMemcpyAsync(adjusted, values, len * sizeof(W), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    return basis_init<W>(form, b, adjusted, len, carries, count, stream);
 }
 
 template <class W>
-int basis_init_to_host_impl(const BasisHost *b, const W *values, size_t len, W *adjusted, uint8_t *carries, size_t count) {
-    if (!b || ((!values || !adjusted || !carries) && count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;
-    if (count == 0) return PFHE_OK;
-    if (adjusted != values) std::memcpy(adjusted, values, len * sizeof(W));
-    return basis_init_host_impl<W>(b, adjusted, len, carries, count);
-}
-
-template <class W>
-int basis_unsigned_dev_impl(const BasisHost *b, size_t level, const W *values_dev, size_t len, W *digits_dev,
-                            uint8_t *carries_dev, size_t count, void *stream) {
-    if (!b || ((!values_dev || !digits_dev || !carries_dev) && count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (level >= b->par.dev.ell) return PFHE_ERR_BAD_ARGUMENT;
-    if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;  // common.rs:316-317
-    DeviceGuard g(b->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return basis_unsigned_decompose_dev(b->par, (u32)level, (const DevWord<W> *)values_dev, (DevWord<W> *)digits_dev,
-                                        carries_dev, count, (hipStream_t)stream);
-}
-
-template <class W>
-int basis_unsigned_host_impl(const BasisHost *b, size_t level, const W *values, size_t len, W *digits, uint8_t *carries,
-                             size_t count) {
+int basis_unsigned(Form form, const BasisHost *b, size_t level, const W *values, size_t len, W *digits, uint8_t *carries,
+                   size_t count, void *stream) {
     if (!b || ((!values || !digits || !carries) && count)) return PFHE_ERR_BAD_ARGUMENT;
     if (level >= b->par.dev.ell) return PFHE_ERR_BAD_ARGUMENT;
-    if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;
+    if (len != count * words_per_value<W>(*b)) return PFHE_ERR_BAD_LENGTH;  // common.rs:316-317
     if (count == 0) return PFHE_OK;
-    DeviceGuard g(b->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(b->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *v = nullptr, *d = nullptr, *c = nullptr;
-    PFHE_TRY(st.upload(values, len * sizeof(W), &v));
-    PFHE_TRY(st.alloc(count * sizeof(W), &d));
-    PFHE_TRY(st.upload(carries, count, &c));
-    PFHE_TRY(basis_unsigned_decompose_dev(b->par, (u32)level, (const DevWord<W> *)v, (DevWord<W> *)d, (unsigned char *)c, count,
-                                          st.stream()));
-    PFHE_TRY(st.download(digits, d, count * sizeof(W)));
-    PFHE_TRY(st.download(carries, c, count));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(values, len * sizeof(W)), stage_out(digits, count * sizeof(W)),
+                             stage_inout(carries, count)};
+    return form_call(b->device, form, bufs, (hipStream_t)stream, [&](void *const *d, hipStream_t s) {
+        return basis_unsigned_decompose_dev(b->par, (u32)level, (const DevWord<W> *)d[0], (DevWord<W> *)d[1],
+                                            (unsigned char *)d[2], count, s);
+    });
 }
 
 template <class W>
-int basis_signed_dev_impl(const BasisHost *b, size_t level, const W *values_dev, size_t len, W *decomposed_dev,
-                          size_t len_out, uint8_t *carries_dev, size_t count, void *stream) {
-    if (!b || ((!values_dev || !decomposed_dev || !carries_dev) && count)) return PFHE_ERR_BAD_ARGUMENT;
+int basis_signed(Form form, const BasisHost *b, size_t level, const W *values, size_t len, W *decomposed, size_t len_out,
+                 uint8_t *carries, size_t count, void *stream) {
+    if (!b || ((!values || !decomposed || !carries) && count)) return PFHE_ERR_BAD_ARGUMENT;
     if (level >= b->par.dev.ell) return PFHE_ERR_BAD_ARGUMENT;
     if (len != count * words_per_value<W>(*b) || len_out != len) return PFHE_ERR_BAD_LENGTH;  // common.rs:296-297
-    if (count && values_dev == decomposed_dev) {
+    if (form == Form::kDevice && count && values == decomposed) {  // the host form stages into separate buffers
         set_last_error("decompose_slice_to needs distinct input and output buffers");
         return PFHE_ERR_BAD_ARGUMENT;
     }
-    DeviceGuard g(b->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return basis_signed_decompose_dev(b->rns, b->par, (u32)level, (const DevWord<W> *)values_dev,
-                                      (DevWord<W> *)decomposed_dev, carries_dev, count, (hipStream_t)stream);
-}
-
-template <class W>
-int basis_signed_host_impl(const BasisHost *b, size_t level, const W *values, size_t len, W *decomposed, size_t len_out,
-                           uint8_t *carries, size_t count) {
-    if (!b || ((!values || !decomposed || !carries) && count)) return PFHE_ERR_BAD_ARGUMENT;
-    if (level >= b->par.dev.ell) return PFHE_ERR_BAD_ARGUMENT;
-    if (len != count * words_per_value<W>(*b) || len_out != len) return PFHE_ERR_BAD_LENGTH;
     if (count == 0) return PFHE_OK;
-    DeviceGuard g(b->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(b->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *v = nullptr, *d = nullptr, *c = nullptr;
-    PFHE_TRY(st.upload(values, len * sizeof(W), &v));
-    PFHE_TRY(st.alloc(len * sizeof(W), &d));
-    PFHE_TRY(st.upload(carries, count, &c));
-    PFHE_TRY(basis_signed_decompose_dev(b->rns, b->par, (u32)level, (const DevWord<W> *)v, (DevWord<W> *)d,
-                                        (unsigned char *)c, count, st.stream()));
-    PFHE_TRY(st.download(decomposed, d, len * sizeof(W)));
-    PFHE_TRY(st.download(carries, c, count));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(values, len * sizeof(W)), stage_out(decomposed, len * sizeof(W)),
+                             stage_inout(carries, count)};
+    return form_call(b->device, form, bufs, (hipStream_t)stream, [&](void *const *d, hipStream_t s) {
+        return basis_signed_decompose_dev(b->rns, b->par, (u32)level, (const DevWord<W> *)d[0], (DevWord<W> *)d[1],
+                                          (unsigned char *)d[2], count, s);
+    });
 }
 
 }  // namespace
 
+// One entry point of the family: guarded against exceptions, then the call.  A step with two forms passes its template
+// Form::kDevice and the caller's stream, or Form::kHost and no stream.
+#define PFHE_RNS_ENTRY(NAME, PARAMS, ...) \
+    int NAME PARAMS {                     \
+        PFHE_GUARD_BEGIN                  \
+        return __VA_ARGS__;               \
+        PFHE_GUARD_END                    \
+    }
+
 // the entry points of one word width: NS = pfhe_rns / pfhe_rns32, BS = pfhe_basis / pfhe_basis32, W = the C word type
 #define H(p) ((p) ? &(p)->h : nullptr)
 #define PFHE_RNS_FAMILY(NS, BS, W)                                                                                         \
-    int NS##_create(const W *moduli, size_t count, int device, NS **out) {                                                \
+    int NS##_create(const W *moduli, size_t count, int device, NS **out) {                                                 \
         PFHE_GUARD_BEGIN                                                                                                   \
         if (!out) return PFHE_ERR_BAD_ARGUMENT;                                                                            \
         *out = nullptr;                                                                                                    \
@@ -513,72 +403,48 @@ int basis_signed_host_impl(const BasisHost *b, size_t level, const W *values, si
     size_t NS##_moduli_count(const NS *r) { return r ? r->h.par.dev.L : 0; }                                               \
     size_t NS##_big_uint_value_len(const NS *r) { return r ? words_per_value<W>(r->h) : 0; }                               \
     int NS##_moduli_product(const NS *r, W *out, size_t len) { return rns_moduli_product_impl<W>(H(r), out, len); }        \
-    int NS##_compose_multiple_values_to_dev(const NS *r, const W *multi_residues_dev, size_t len_in,                      \
-                                            W *big_uint_values_dev, size_t len_out, size_t value_count, void *stream) {   \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_compose_dev_impl<W>(H(r), multi_residues_dev, len_in, big_uint_values_dev, len_out, value_count, stream); \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_compose_multiple_values_to(const NS *r, const W *multi_residues, size_t len_in, W *big_uint_values,          \
-                                        size_t len_out, size_t value_count) {                                              \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_compose_host_impl<W>(H(r), multi_residues, len_in, big_uint_values, len_out, value_count);              \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_wrapping_decompose_small_values_to_dev(const NS *r, const W *small_values_dev, size_t value_count,           \
-                                                    W *multi_residues_dev, size_t len_out, W small_value_modulus,         \
-                                                    void *stream) {                                                        \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_wrapping_dev_impl<W>(H(r), small_values_dev, value_count, multi_residues_dev, len_out,                  \
-                                        small_value_modulus, stream);                                                      \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_wrapping_decompose_small_values_to(const NS *r, const W *small_values, size_t value_count,                   \
-                                                W *multi_residues, size_t len_out, W small_value_modulus) {               \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_wrapping_host_impl<W>(H(r), small_values, value_count, multi_residues, len_out, small_value_modulus);   \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_add_wrapping_decompose_small_values_scaled_dev(const NS *r, const W *small_values_dev, size_t value_count,   \
-                                                            W *acc_dev, size_t len_acc, W small_value_modulus,            \
-                                                            const W *factors, void *stream) {                              \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_add_scaled_dev_impl<W>(H(r), small_values_dev, value_count, acc_dev, len_acc, small_value_modulus,      \
-                                          true, factors, stream);                                                          \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_add_decompose_small_values_scaled_dev(const NS *r, const W *small_values_dev, size_t value_count,            \
-                                                   W *acc_dev, size_t len_acc, const W *factors, void *stream) {           \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_add_scaled_dev_impl<W>(H(r), small_values_dev, value_count, acc_dev, len_acc, 0, false, factors, stream); \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_add_wrapping_decompose_small_values_scaled(const NS *r, const W *small_values, size_t value_count, W *acc,   \
-                                                        size_t len_acc, W small_value_modulus, const W *factors) {         \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_add_scaled_host_impl<W>(H(r), small_values, value_count, acc, len_acc, small_value_modulus, true, factors); \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_add_decompose_small_values_scaled(const NS *r, const W *small_values, size_t value_count, W *acc,            \
-                                               size_t len_acc, const W *factors) {                                         \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_add_scaled_host_impl<W>(H(r), small_values, value_count, acc, len_acc, 0, false, factors);              \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_decompose_big_uint_values_to_dev(const NS *r, const W *big_uint_values_dev, size_t len_in,                   \
-                                              W *multi_residues_dev, size_t len_out, size_t value_count, void *stream) {  \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_decompose_big_dev_impl<W>(H(r), big_uint_values_dev, len_in, multi_residues_dev, len_out, value_count,  \
-                                             stream);                                                                      \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int NS##_decompose_big_uint_values_to(const NS *r, const W *big_uint_values, size_t len_in, W *multi_residues,        \
-                                          size_t len_out, size_t value_count) {                                            \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return rns_decompose_big_host_impl<W>(H(r), big_uint_values, len_in, multi_residues, len_out, value_count);        \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_create(const NS *rns, uint32_t log_basis, size_t reverse_length, BS **out) {                                 \
+    PFHE_RNS_ENTRY(NS##_compose_multiple_values_to_dev, (const NS *r, const W *multi_residues_dev, size_t len_in,          \
+                    W *big_uint_values_dev, size_t len_out, size_t value_count, void *stream),                             \
+                   rns_compose<W>(Form::kDevice, H(r), multi_residues_dev, len_in, big_uint_values_dev, len_out,           \
+                                  value_count, stream))                                                                    \
+    PFHE_RNS_ENTRY(NS##_compose_multiple_values_to, (const NS *r, const W *multi_residues, size_t len_in,                  \
+                    W *big_uint_values, size_t len_out, size_t value_count),                                               \
+                   rns_compose<W>(Form::kHost, H(r), multi_residues, len_in, big_uint_values, len_out, value_count,        \
+                                  nullptr))                                                                                \
+    PFHE_RNS_ENTRY(NS##_wrapping_decompose_small_values_to_dev, (const NS *r, const W *small_values_dev,                   \
+                    size_t value_count, W *multi_residues_dev, size_t len_out, W small_value_modulus, void *stream),       \
+                   rns_wrapping<W>(Form::kDevice, H(r), small_values_dev, value_count, multi_residues_dev, len_out,        \
+                                   small_value_modulus, stream))                                                           \
+    PFHE_RNS_ENTRY(NS##_wrapping_decompose_small_values_to, (const NS *r, const W *small_values, size_t value_count,       \
+                    W *multi_residues, size_t len_out, W small_value_modulus),                                             \
+                   rns_wrapping<W>(Form::kHost, H(r), small_values, value_count, multi_residues, len_out,                  \
+                                   small_value_modulus, nullptr))                                                          \
+    PFHE_RNS_ENTRY(NS##_add_wrapping_decompose_small_values_scaled_dev, (const NS *r, const W *small_values_dev,           \
+                    size_t value_count, W *acc_dev, size_t len_acc, W small_value_modulus, const W *factors,               \
+                    void *stream),                                                                                         \
+                   rns_add_scaled<W>(Form::kDevice, H(r), small_values_dev, value_count, acc_dev, len_acc,                 \
+                                     small_value_modulus, true, factors, stream))                                          \
+    PFHE_RNS_ENTRY(NS##_add_decompose_small_values_scaled_dev, (const NS *r, const W *small_values_dev,                    \
+                    size_t value_count, W *acc_dev, size_t len_acc, const W *factors, void *stream),                       \
+                   rns_add_scaled<W>(Form::kDevice, H(r), small_values_dev, value_count, acc_dev, len_acc, 0, false,       \
+                                     factors, stream))                                                                     \
+    PFHE_RNS_ENTRY(NS##_add_wrapping_decompose_small_values_scaled, (const NS *r, const W *small_values,                   \
+                    size_t value_count, W *acc, size_t len_acc, W small_value_modulus, const W *factors),                  \
+                   rns_add_scaled<W>(Form::kHost, H(r), small_values, value_count, acc, len_acc, small_value_modulus,      \
+                                     true, factors, nullptr))                                                              \
+    PFHE_RNS_ENTRY(NS##_add_decompose_small_values_scaled, (const NS *r, const W *small_values, size_t value_count,        \
+                    W *acc, size_t len_acc, const W *factors),                                                             \
+                   rns_add_scaled<W>(Form::kHost, H(r), small_values, value_count, acc, len_acc, 0, false, factors,        \
+                                     nullptr))                                                                             \
+    PFHE_RNS_ENTRY(NS##_decompose_big_uint_values_to_dev, (const NS *r, const W *big_uint_values_dev, size_t len_in,       \
+                    W *multi_residues_dev, size_t len_out, size_t value_count, void *stream),                              \
+                   rns_decompose_big<W>(Form::kDevice, H(r), big_uint_values_dev, len_in, multi_residues_dev, len_out,     \
+                                        value_count, stream))                                                              \
+    PFHE_RNS_ENTRY(NS##_decompose_big_uint_values_to, (const NS *r, const W *big_uint_values, size_t len_in,               \
+                    W *multi_residues, size_t len_out, size_t value_count),                                                \
+                   rns_decompose_big<W>(Form::kHost, H(r), big_uint_values, len_in, multi_residues, len_out,               \
+                                        value_count, nullptr))                                                             \
+    int BS##_create(const NS *rns, uint32_t log_basis, size_t reverse_length, BS **out) {                                  \
         PFHE_GUARD_BEGIN                                                                                                   \
         if (!out || !rns) return PFHE_ERR_BAD_ARGUMENT;                                                                    \
         *out = nullptr;                                                                                                    \
@@ -595,53 +461,32 @@ int basis_signed_host_impl(const BasisHost *b, size_t level, const W *values, si
     W BS##_basis_value(const BS *b) { return b ? (W)b->h.par.dev.basis : 0; }                                              \
     int BS##_scalars(const BS *b, W *out, size_t len) { return basis_scalars_impl<W>(H(b), out, len); }                    \
     int BS##_scalars_residue(const BS *b, W *out, size_t len) { return basis_scalars_residue_impl<W>(H(b), out, len); }    \
-    int BS##_init_value_carry_slice_inplace_dev(const BS *b, W *values_dev, size_t len, uint8_t *carries_dev,             \
-                                                size_t count, void *stream) {                                              \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_init_dev_impl<W>(H(b), values_dev, len, carries_dev, count, stream);                                  \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_init_value_carry_slice_inplace(const BS *b, W *values, size_t len, uint8_t *carries, size_t count) {         \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_init_host_impl<W>(H(b), values, len, carries, count);                                                 \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_unsigned_decompose_slice_to_dev(const BS *b, size_t level, const W *values_dev, size_t len, W *digits_dev,   \
-                                             uint8_t *carries_dev, size_t count, void *stream) {                           \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_unsigned_dev_impl<W>(H(b), level, values_dev, len, digits_dev, carries_dev, count, stream);           \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_unsigned_decompose_slice_to(const BS *b, size_t level, const W *values, size_t len, W *digits,               \
-                                         uint8_t *carries, size_t count) {                                                 \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_unsigned_host_impl<W>(H(b), level, values, len, digits, carries, count);                              \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_init_value_carry_slice_to_dev(const BS *b, const W *values_dev, size_t len, W *adjusted_dev,                 \
-                                           uint8_t *carries_dev, size_t count, void *stream) {                             \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_init_to_dev_impl<W>(H(b), values_dev, len, adjusted_dev, carries_dev, count, stream);                 \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_init_value_carry_slice_to(const BS *b, const W *values, size_t len, W *adjusted, uint8_t *carries,           \
-                                       size_t count) {                                                                     \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_init_to_host_impl<W>(H(b), values, len, adjusted, carries, count);                                    \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_decompose_slice_to_dev(const BS *b, size_t level, const W *values_dev, size_t len, W *decomposed_dev,        \
-                                    size_t len_out, uint8_t *carries_dev, size_t count, void *stream) {                    \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_signed_dev_impl<W>(H(b), level, values_dev, len, decomposed_dev, len_out, carries_dev, count, stream); \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    int BS##_decompose_slice_to(const BS *b, size_t level, const W *values, size_t len, W *decomposed, size_t len_out,    \
-                                uint8_t *carries, size_t count) {                                                          \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        return basis_signed_host_impl<W>(H(b), level, values, len, decomposed, len_out, carries, count);                   \
-        PFHE_GUARD_END                                                                                                     \
-    }
+    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_inplace_dev, (const BS *b, W *values_dev, size_t len,                       \
+                    uint8_t *carries_dev, size_t count, void *stream),                                                     \
+                   basis_init<W>(Form::kDevice, H(b), values_dev, len, carries_dev, count, stream))                        \
+    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_inplace, (const BS *b, W *values, size_t len, uint8_t *carries,             \
+                    size_t count),                                                                                         \
+                   basis_init<W>(Form::kHost, H(b), values, len, carries, count, nullptr))                                 \
+    PFHE_RNS_ENTRY(BS##_unsigned_decompose_slice_to_dev, (const BS *b, size_t level, const W *values_dev, size_t len,      \
+                    W *digits_dev, uint8_t *carries_dev, size_t count, void *stream),                                      \
+                   basis_unsigned<W>(Form::kDevice, H(b), level, values_dev, len, digits_dev, carries_dev, count,          \
+                                     stream))                                                                              \
+    PFHE_RNS_ENTRY(BS##_unsigned_decompose_slice_to, (const BS *b, size_t level, const W *values, size_t len, W *digits,   \
+                    uint8_t *carries, size_t count),                                                                       \
+                   basis_unsigned<W>(Form::kHost, H(b), level, values, len, digits, carries, count, nullptr))              \
+    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_to_dev, (const BS *b, const W *values_dev, size_t len, W *adjusted_dev,     \
+                    uint8_t *carries_dev, size_t count, void *stream),                                                     \
+                   basis_init_to<W>(Form::kDevice, H(b), values_dev, len, adjusted_dev, carries_dev, count, stream))       \
+    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_to, (const BS *b, const W *values, size_t len, W *adjusted,                 \
+                    uint8_t *carries, size_t count),                                                                       \
+                   basis_init_to<W>(Form::kHost, H(b), values, len, adjusted, carries, count, nullptr))                    \
+    PFHE_RNS_ENTRY(BS##_decompose_slice_to_dev, (const BS *b, size_t level, const W *values_dev, size_t len,               \
+                    W *decomposed_dev, size_t len_out, uint8_t *carries_dev, size_t count, void *stream),                  \
+                   basis_signed<W>(Form::kDevice, H(b), level, values_dev, len, decomposed_dev, len_out, carries_dev,      \
+                                   count, stream))                                                                         \
+    PFHE_RNS_ENTRY(BS##_decompose_slice_to, (const BS *b, size_t level, const W *values, size_t len, W *decomposed,        \
+                    size_t len_out, uint8_t *carries, size_t count),                                                       \
+                   basis_signed<W>(Form::kHost, H(b), level, values, len, decomposed, len_out, carries, count, nullptr))
 
 extern "C" {
 
@@ -830,18 +675,12 @@ int mul_dcrt_ggsw_to(Plan *plan, const W *crt_glwe, size_t len_glwe, const W *dc
     PFHE_TRY(plan_check(plan));
     PFHE_PLAN_LEASE(plan->guard, kPlanBusy);
     if ((!crt_glwe || !dcrt_ggsw || !result) && len_glwe) return PFHE_ERR_BAD_ARGUMENT;
-    DeviceGuard g(plan->table->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(plan->table->device);  // pooled staging context: no allocation in steady state
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *r = nullptr;
-    PFHE_TRY(st.upload(crt_glwe, len_glwe * sizeof(W), &a));
-    PFHE_TRY(st.upload(dcrt_ggsw, len_ggsw * sizeof(W), &k));
-    PFHE_TRY(st.alloc(len_result * sizeof(W), &r));
-    PFHE_TRY(mul_dcrt_ggsw_to_dev(plan, (const W *)a, len_glwe, (const W *)k, len_ggsw, (W *)r, len_result, into_coeff_form,
-                                  st.stream()));
-    PFHE_TRY(st.download(result, r, len_result * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(crt_glwe, len_glwe * sizeof(W)), stage_in(dcrt_ggsw, len_ggsw * sizeof(W)),
+                             stage_out(result, len_result * sizeof(W))};
+    return staged_call(plan->table->device, bufs, [&](void *const *d, hipStream_t s) {
+        return mul_dcrt_ggsw_to_dev(plan, (const W *)d[0], len_glwe, (const W *)d[1], len_ggsw, (W *)d[2], len_result,
+                                    into_coeff_form, s);
+    });
 }
 
 // The GLev rows against `batch` polynomials, accumulating or overwriting (`out_name`: what the length message calls the output).  CRT residues: DcrtGlwe::
@@ -1132,17 +971,23 @@ int blindrot_small_steps(pfhe_blindrot32 *, u32 *, const u32 *, const u32 *, u64
     return PFHE_ERR_UNSUPPORTED;
 }
 
+// the rotation's length test, for both of its forms
+template <class H>
+int blindrot_lengths(const H *h, size_t len_acc, size_t len_bsk, size_t len_exps) {
+    const bool whole = len_acc % h->glwe == 0 && len_bsk % h->ggsw == 0;
+    if (whole && len_exps == (len_acc / h->glwe) * (len_bsk / h->ggsw)) return PFHE_OK;
+    set_last_error("blind rotation: acc must be batch*(k+1)*L*N words, bsk n_steps*(k+1)*ell*(k+1)*L*N and exps "
+                   "batch*n_steps exponents");
+    return PFHE_ERR_BAD_LENGTH;
+}
+
 template <class H, class W>
 int blindrot_rotate_dev(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
                         hipStream_t s) {
     if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kPlanBusy);
     const TableSet &t = *h->plan->table;
-    if (len_acc % h->glwe != 0 || len_bsk % h->ggsw != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->ggsw)) {
-        set_last_error("blind rotation: acc must be batch*(k+1)*L*N words, bsk n_steps*(k+1)*ell*(k+1)*L*N and exps "
-                       "batch*n_steps exponents");
-        return PFHE_ERR_BAD_LENGTH;
-    }
+    PFHE_TRY(blindrot_lengths(h, len_acc, len_bsk, len_exps));
     const u64 batch = len_acc / h->glwe, n_steps = len_bsk / h->ggsw;
     if (batch == 0 || n_steps == 0) return PFHE_OK;
     if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
@@ -1188,36 +1033,20 @@ int blindrot_rotate_dev(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_b
 }
 
 // host form: every exponent must be below 2N (the reference's debug_assert!(r < 2N)); staged through the pooled context
-template <class H, class W, class DevFn>
-int blindrot_rotate_host(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
-                         DevFn dev) {
+template <class H, class W>
+int blindrot_rotate_host(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps) {
     if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kPlanBusy);
     if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
-    const size_t two_n = 2 * h->plan->table->n;
-    for (size_t i = 0; i < len_exps; ++i) {
-        if (exps[i] >= two_n) {
-            set_last_error("blind rotation: every exponent must be below 2N");
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
-    }
-    if (len_acc % h->glwe != 0 || len_bsk % h->ggsw != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->ggsw)) {
-        set_last_error("blind rotation: acc must be batch*(k+1)*L*N words, bsk n_steps*(k+1)*ell*(k+1)*L*N and exps "
-                       "batch*n_steps exponents");
-        return PFHE_ERR_BAD_LENGTH;
-    }
+    PFHE_TRY(require_exps_below_2n(exps, len_exps, h->plan->table->n, "blind rotation: every exponent must be below 2N"));
+    PFHE_TRY(blindrot_lengths(h, len_acc, len_bsk, len_exps));
     if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
-    DeviceGuard g(h->plan->table->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(h->plan->table->device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *a = nullptr, *k = nullptr, *x = nullptr;
-    PFHE_TRY(st.upload(acc, len_acc * sizeof(W), &a));
-    PFHE_TRY(st.upload(bsk, len_bsk * sizeof(W), &k));
-    PFHE_TRY(st.upload(exps, len_exps * sizeof(uint32_t), &x));
-    PFHE_TRY(dev(h, (W *)a, len_acc, (const W *)k, len_bsk, (const uint32_t *)x, len_exps, st.stream()));
-    PFHE_TRY(st.download(acc, a, len_acc * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_inout(acc, len_acc * sizeof(W)), stage_in(bsk, len_bsk * sizeof(W)),
+                             stage_in(exps, len_exps * sizeof(uint32_t))};
+    return staged_call(h->plan->table->device, bufs, [&](void *const *d, hipStream_t s) {
+        return blindrot_rotate_dev<H, W>(h, (W *)d[0], len_acc, (const W *)d[1], len_bsk, (const uint32_t *)d[2], len_exps,
+                                         s);
+    });
 }
 
 }  // namespace
@@ -1243,8 +1072,7 @@ int pfhe_blindrot_rotate_dev(pfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc
 int pfhe_blindrot_rotate(pfhe_blindrot *h, uint64_t *acc, size_t len_acc, const uint64_t *bsk, size_t len_bsk,
                          const uint32_t *exps, size_t len_exps) {
     PFHE_GUARD_BEGIN
-    return blindrot_rotate_host(h, (u64 *)acc, len_acc, (const u64 *)bsk, len_bsk, exps, len_exps,
-                                blindrot_rotate_dev<pfhe_blindrot, u64>);
+    return blindrot_rotate_host(h, (u64 *)acc, len_acc, (const u64 *)bsk, len_bsk, exps, len_exps);
     PFHE_GUARD_END
 }
 
@@ -1267,7 +1095,7 @@ int pfhe_blindrot32_rotate_dev(pfhe_blindrot32 *h, uint32_t *acc_dev, size_t len
 int pfhe_blindrot32_rotate(pfhe_blindrot32 *h, uint32_t *acc, size_t len_acc, const uint32_t *bsk, size_t len_bsk,
                            const uint32_t *exps, size_t len_exps) {
     PFHE_GUARD_BEGIN
-    return blindrot_rotate_host(h, acc, len_acc, bsk, len_bsk, exps, len_exps, blindrot_rotate_dev<pfhe_blindrot32, u32>);
+    return blindrot_rotate_host(h, acc, len_acc, bsk, len_bsk, exps, len_exps);
     PFHE_GUARD_END
 }
 

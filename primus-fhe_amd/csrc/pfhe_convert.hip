@@ -352,16 +352,10 @@ template <class W>
 int conv_host(const ConvCore *c, const W *in, size_t len_in, W *out, size_t len_out, size_t poly_length, bool exact) {
     PFHE_TRY(conv_check(c, in, len_in, out, len_out, poly_length, exact));
     if (poly_length == 0) return PFHE_OK;
-    DeviceGuard g(c->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(c->device);  // pooled staging context: no allocation in steady state
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *din = nullptr, *dout = nullptr;
-    PFHE_TRY(st.upload(in, len_in * sizeof(W), &din));
-    PFHE_TRY(st.alloc(len_out * sizeof(W), &dout));
-    PFHE_TRY(conv_array_dev<W>(c, (const W *)din, len_in, (W *)dout, len_out, poly_length, exact, st.stream()));
-    PFHE_TRY(st.download(out, dout, len_out * sizeof(W)));
-    return st.finish();
+    const StageBuf bufs[] = {stage_in(in, len_in * sizeof(W)), stage_out(out, len_out * sizeof(W))};
+    return staged_call(c->device, bufs, [&](void *const *d, hipStream_t s) {
+        return conv_array_dev<W>(c, (const W *)d[0], len_in, (W *)d[1], len_out, poly_length, exact, s);
+    });
 }
 
 }  // namespace

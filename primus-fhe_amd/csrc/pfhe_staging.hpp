@@ -122,4 +122,78 @@ class HostStage {
 // frees the idle contexts of `device` (-1: every device); returns how many were released
 int staging_release(int device);
 
+// ---------------- host forms on one tail (both sides of the library: DESIGN.md §16) ----------------
+
+// One buffer of a host form: `bytes` at `host` that the device form reads (in), writes (out) or both.  A buffer of no
+// bytes is not staged: its device pointer stays null.
+struct StageBuf {
+    enum Dir { kIn, kOut, kInOut };
+    void *host;
+    size_t bytes;
+    Dir dir;
+};
+inline StageBuf stage_in(const void *host, size_t bytes) { return {const_cast<void *>(host), bytes, StageBuf::kIn}; }
+inline StageBuf stage_out(void *host, size_t bytes) { return {host, bytes, StageBuf::kOut}; }
+inline StageBuf stage_inout(void *host, size_t bytes) { return {host, bytes, StageBuf::kInOut}; }
+
+// The tail of every host form, arguments already checked: `device` made current, a pooled staging context, the ins and
+// in/outs uploaded and the outs allocated in the order given, body(dev, stream) with dev[i] the device copy of bufs[i],
+// the outs and in/outs downloaded, one wait.  PFHE_ERR_NO_DEVICE / PFHE_ERR_HIP when the device or the context cannot be
+// had, otherwise the first status that is not PFHE_OK.
+template <size_t N, class Body>
+int staged_call(int device, const StageBuf (&bufs)[N], Body &&body) {
+    DeviceGuard g(device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    HostStage st(device);
+    if (!st.ok()) return PFHE_ERR_HIP;
+    void *dev[N] = {};
+    for (size_t i = 0; i < N; ++i) {
+        if (!bufs[i].bytes) continue;
+        PFHE_TRY(bufs[i].dir == StageBuf::kOut ? st.alloc(bufs[i].bytes, &dev[i]) : st.upload(bufs[i].host, bufs[i].bytes, &dev[i]));
+    }
+    PFHE_TRY(body(dev, st.stream()));
+    for (size_t i = 0; i < N; ++i)
+        if (bufs[i].bytes && bufs[i].dir != StageBuf::kIn) PFHE_TRY(st.download(bufs[i].host, dev[i], bufs[i].bytes));
+    return st.finish();
+}
+
+// which pointers a step that is one function for both of its forms was handed
+enum class Form { kHost, kDevice };
+
+// The tail of such a step, arguments already checked and the batch not empty.  Host form: staged_call.  Device form:
+// `device` made current, then launch(pointers, s) on the caller's pointers and stream, pointers[i] = bufs[i].host.
+template <size_t N, class Launch>
+int form_call(int device, Form form, const StageBuf (&bufs)[N], hipStream_t s, Launch &&launch) {
+    if (form == Form::kHost) return staged_call(device, bufs, launch);
+    void *dev[N];
+    for (size_t i = 0; i < N; ++i) dev[i] = bufs[i].host;
+    DeviceGuard g(device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return launch(dev, s);
+}
+
+template <size_t N>
+int refuse_null(const StageBuf (&bufs)[N]) {
+    for (const StageBuf &b : bufs)
+        if (b.bytes && !b.host) return PFHE_ERR_BAD_ARGUMENT;
+    return PFHE_OK;
+}
+
+// true when the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
+inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// what the host forms of the rotations ask of their exponents (the device forms take them modulo 2N instead)
+inline int require_exps_below_2n(const uint32_t *exps, size_t len, size_t n, const char *message) {
+    for (size_t i = 0; i < len; ++i) {
+        if (exps[i] >= 2 * n) {
+            set_last_error(message);
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
+    }
+    return PFHE_OK;
+}
+
 }  // namespace pfhe

@@ -1,6 +1,8 @@
 // pfhe_tfhe_host.hpp — the host layer under every torus entry point (pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip,
-// pfhe_pack.hip): the constants and range tests they share, the launch of a torus kernel, the staged run of a launch on
-// host pointers, and the one tail of the stateless steps.  Host only.
+// pfhe_pack.hip): the constants and range tests they share, the launch of a torus kernel, and the one tail of the
+// stateless steps.  Host only.  What is not torus-specific lives in pfhe_staging.hpp, for the RNS side too: StageBuf and
+// stage_in / _out / _inout, staged_call (the staged run of a launch on host pointers), Form and form_call, refuse_null,
+// overlaps, require_exps_below_2n.
 //
 // A handle call (product, rotations, bootstrap) writes its checks in its device form; its host form re-enters that under
 // the handle's lease through staged_call.  A stateless step is ONE function template for both of its forms:
@@ -15,7 +17,7 @@
 //       in as the gate.
 // stateless_call then refuses, in this order: a null buffer; in the device form a written buffer that shares a byte with
 // any other buffer of the call (inputs may overlap each other, and the host form refuses no overlap: it stages); what
-// the gate refuses; a device that cannot be made current.  Nothing is kept between calls.
+// the gate refuses; a device that cannot be made current (form_call).  Nothing is kept between calls.
 #pragma once
 
 #include <algorithm>
@@ -76,98 +78,29 @@ int launch_y_slices(u64 count, Launch &&launch) {
     return PFHE_OK;
 }
 
-// ---------------- host forms ----------------
-
-// One buffer of a host form: `bytes` at `host` that the device form reads (in), writes (out) or both.  A buffer of no
-// bytes is not staged: its device pointer stays null.
-struct StageBuf {
-    enum Dir { kIn, kOut, kInOut };
-    void *host;
-    size_t bytes;
-    Dir dir;
-};
-inline StageBuf stage_in(const void *host, size_t bytes) { return {const_cast<void *>(host), bytes, StageBuf::kIn}; }
-inline StageBuf stage_out(void *host, size_t bytes) { return {host, bytes, StageBuf::kOut}; }
-inline StageBuf stage_inout(void *host, size_t bytes) { return {host, bytes, StageBuf::kInOut}; }
-
-// The tail of every host form, arguments already checked: `device` made current, a pooled staging context, the ins and
-// in/outs uploaded and the outs allocated in the order given, body(dev, stream) with dev[i] the device copy of bufs[i],
-// the outs and in/outs downloaded, one wait.  PFHE_ERR_NO_DEVICE / PFHE_ERR_HIP when the device or the context cannot be
-// had, otherwise the first status that is not PFHE_OK.
-template <size_t N, class Body>
-int staged_call(int device, const StageBuf (&bufs)[N], Body &&body) {
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    HostStage st(device);
-    if (!st.ok()) return PFHE_ERR_HIP;
-    void *dev[N] = {};
-    for (size_t i = 0; i < N; ++i) {
-        if (!bufs[i].bytes) continue;
-        PFHE_TRY(bufs[i].dir == StageBuf::kOut ? st.alloc(bufs[i].bytes, &dev[i]) : st.upload(bufs[i].host, bufs[i].bytes, &dev[i]));
-    }
-    PFHE_TRY(body(dev, st.stream()));
-    for (size_t i = 0; i < N; ++i)
-        if (bufs[i].bytes && bufs[i].dir != StageBuf::kIn) PFHE_TRY(st.download(bufs[i].host, dev[i], bufs[i].bytes));
-    return st.finish();
-}
-
-// what the host forms of the rotations ask of their exponents (the device forms take them modulo 2N instead)
-inline int require_exps_below_2n(const uint32_t *exps, size_t len, size_t n, const char *message) {
-    for (size_t i = 0; i < len; ++i) {
-        if (exps[i] >= 2 * n) {
-            set_last_error(message);
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
-    }
-    return PFHE_OK;
-}
-
-// true when the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte
-inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // ---------------- the stateless steps ----------------
-
-enum class Form { kHost, kDevice };
-
-template <size_t N>
-int refuse_null(const StageBuf (&bufs)[N]) {
-    for (const StageBuf &b : bufs)
-        if (b.bytes && !b.host) return PFHE_ERR_BAD_ARGUMENT;
-    return PFHE_OK;
-}
 
 struct NoGate {
     int operator()() const { return PFHE_OK; }
 };
 
 // The tail of every stateless step, values already checked and the batch not empty (the recipe is at the top of this file).
-// Device form: launch(pointers, s) on the caller's pointers and stream, with pointers[i] = bufs[i].host.  Host form:
-// staged_call.  overlap_message null: the step refuses no overlap.
+// It ends in form_call: the device form launches on the caller's pointers and stream, the host form is staged_call.
+// overlap_message null: the step refuses no overlap.
 template <size_t N, class Launch, class Gate = NoGate>
 int stateless_call(int device, Form form, const StageBuf (&bufs)[N], const char *overlap_message, hipStream_t s,
                    Launch &&launch, Gate &&gate = Gate{}) {
     PFHE_TRY(refuse_null(bufs));
-    if (form == Form::kHost) {
-        PFHE_TRY(gate());
-        return staged_call(device, bufs, launch);
-    }
-    void *dev[N];
-    for (size_t i = 0; i < N; ++i) {
-        dev[i] = bufs[i].host;
-        for (size_t j = 0; overlap_message && bufs[i].dir != StageBuf::kIn && j < N; ++j) {
-            if (j != i && bufs[i].bytes && bufs[j].bytes && overlaps(dev[i], bufs[i].bytes, bufs[j].host, bufs[j].bytes)) {
+    for (size_t i = 0; overlap_message && form == Form::kDevice && i < N; ++i) {
+        for (size_t j = 0; bufs[i].dir != StageBuf::kIn && j < N; ++j) {
+            if (j != i && bufs[i].bytes && bufs[j].bytes && overlaps(bufs[i].host, bufs[i].bytes, bufs[j].host, bufs[j].bytes)) {
                 set_last_error(overlap_message);
                 return PFHE_ERR_BAD_ARGUMENT;
             }
         }
     }
     PFHE_TRY(gate());
-    DeviceGuard g(device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return launch(dev, s);
+    return form_call(device, form, bufs, s, launch);
 }
 
 }  // namespace pfhe
