@@ -1222,8 +1222,8 @@ int pfhe_tfhe32_ksk_generate_dev(int device, const uint32_t *key_in_dev, size_t 
  * pfhe_tfhe_keyswitch_dev; PFHE_ERR_BAD_ARGUMENT for glwe_dimension 0 or above 64 and in_dimension outside 1..2^31-2, for a
  * null table, and for count outside 1..N; PFHE_ERR_BAD_LENGTH unless len_in = batch*count*(in_dimension+1),
  * len_pksk = in_dimension*ell*(k+1)*N and len_out = batch*(k+1)*N; an empty batch is a no-op; then PFHE_ERR_BAD_ARGUMENT for
- * a null pointer or an output that overlaps an input.  The f64 / FFT route (transform the digit polynomials, multiply into
- * a Fourier key) is not built: it is approximate, and this call is exact. */
+ * a null pointer or an output that overlaps an input.  This call is exact and serves every shape; the approximate f64 /
+ * FFT route for full packings is pfhe_tfhe*_pack_keyswitch_fft_dev below. */
 int pfhe_tfhe_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in_dev, size_t len_in,
                                  size_t in_dimension, size_t count, const uint64_t *pksk_dev, size_t len_pksk,
                                  uint32_t log_basis, size_t decompose_length, uint64_t *glwe_out_dev, size_t len_out,
@@ -1283,6 +1283,63 @@ int pfhe_tfhe32_multimsg_extract_dev(const pfhe_fft *fft, size_t glwe_dimension,
                                      size_t count, uint32_t *lwe_dev, size_t len_lwe, void *stream);
 int pfhe_tfhe32_multimsg_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *multi, size_t len_multi,
                                  size_t count, uint32_t *lwe, size_t len_lwe);
+
+/* ---- the packing key switch in the Fourier domain (u64: no suffix, u32: 32) — opt-in, no reference counterpart ----
+ * The same rule as pfhe_tfhe*_pack_keyswitch_dev, computed as ONE external product of in_dimension*ell rows:
+ *   D_{j,l}(X) = sum_{i<count} d_l(a_{e,i,j}) X^i;   ACC_c = sum_j sum_l FFT(D_{j,l}) * Herm(FFT(pksk[j][l][c]));
+ *   out_e = (0, ..., 0, sum_i b_{e,i} X^i) - IFFT(ACC_c)   modulo 2^BITS and X^N + 1,
+ * with the digits exactly as the exact call forms them and the f64 transforms, rounding and torus wrap of
+ * pfhe_tfhe*_external_product_to_dev.  APPROXIMATE as that product is: bit-equal to the exact call while every sum stays
+ * below 2^53 (small keys), otherwise within the f64 transform's error, which u64 full-torus keys make visible.  Cheaper
+ * than the exact call when count approaches N; the exact call stays the default and serves every other shape.
+ * Shapes: 1 <= log N <= 11 and 1 <= glwe_dimension <= 3.
+ *
+ * The plan owns the partial-sum scratch of `chunk` groups (chunk x ceil(in_dimension/4) x (k+1) x N/2 complex values;
+ * chunk 0 = what fits 256 MiB, at most 65535), allocated at creation; a call only queues work on its stream, and a batch
+ * above the chunk runs chunk by chunk.  One holder at a time (PFHE_ERR_BUSY for a second thread); successive calls on
+ * different streams are ordered by the plan.  The mask words are summed in slices of 4, a constant of the build, and the
+ * slices in ascending order: a group's result is bit-identical whatever batch or chunk it sits in, and a call repeatable.
+ * plan_create, all before the device is touched: ApproxSignedBasis::new's assert!s (PFHE_ERR_BAD_ARGUMENT) as
+ * pfhe_tfhe_plan_create; PFHE_ERR_UNSUPPORTED for glwe_dimension above 3, PFHE_ERR_BAD_ARGUMENT for a null table,
+ * PFHE_ERR_UNSUPPORTED for log N above 11; PFHE_ERR_BAD_ARGUMENT for glwe_dimension 0 or in_dimension outside 1..2^31-2. */
+typedef struct pfhe_tfhe_packfft_plan pfhe_tfhe_packfft_plan;
+typedef struct pfhe_tfhe32_packfft_plan pfhe_tfhe32_packfft_plan;
+int pfhe_tfhe_packfft_plan_create(const pfhe_fft *fft, size_t glwe_dimension, size_t in_dimension, uint32_t log_basis,
+                                  size_t decompose_length, size_t chunk, pfhe_tfhe_packfft_plan **out);
+void pfhe_tfhe_packfft_plan_destroy(pfhe_tfhe_packfft_plan *plan);
+int pfhe_tfhe_packfft_plan_in_use(const pfhe_tfhe_packfft_plan *plan);
+size_t pfhe_tfhe_packfft_plan_scratch_bytes(const pfhe_tfhe_packfft_plan *plan);
+int pfhe_tfhe32_packfft_plan_create(const pfhe_fft *fft, size_t glwe_dimension, size_t in_dimension, uint32_t log_basis,
+                                    size_t decompose_length, size_t chunk, pfhe_tfhe32_packfft_plan **out);
+void pfhe_tfhe32_packfft_plan_destroy(pfhe_tfhe32_packfft_plan *plan);
+int pfhe_tfhe32_packfft_plan_in_use(const pfhe_tfhe32_packfft_plan *plan);
+size_t pfhe_tfhe32_packfft_plan_scratch_bytes(const pfhe_tfhe32_packfft_plan *plan);
+/* The Fourier packing key: pksk in exactly the layout pfhe_tfhe*_pksk_generate_dev writes (in_dimension x ell x (k+1) x N
+ * words) becomes the HALF spectrum of every key polynomial in natural order, in_dimension x ell x (k+1) x N/2 complex values
+ * (len_fkey counts complex values): fkey[p][i] = FFT_N(centred(pksk[p]) psi)[2i], which for a real polynomial is its
+ * Hermitian part, so no per-call Hermitian pass is needed and the key is half the bytes of the reference's full layout.
+ * Deterministic.  A null plan (PFHE_ERR_BAD_ARGUMENT), the two lengths (PFHE_ERR_BAD_LENGTH), null pointers, an output
+ * that overlaps the input or is not 16-byte aligned (PFHE_ERR_BAD_ARGUMENT). */
+int pfhe_tfhe_packfft_key_dev(pfhe_tfhe_packfft_plan *plan, const uint64_t *pksk_dev, size_t len_pksk, double *fkey_dev,
+                              size_t len_fkey, void *stream);
+int pfhe_tfhe32_packfft_key_dev(pfhe_tfhe32_packfft_plan *plan, const uint32_t *pksk_dev, size_t len_pksk, double *fkey_dev,
+                                size_t len_fkey, void *stream);
+/* The packing call.  lwe_in and glwe_out have the lengths and layouts of pfhe_tfhe*_pack_keyswitch_dev; fkey is the key
+ * above.  Statuses in the exact call's order, behind a null plan (PFHE_ERR_BAD_ARGUMENT): count outside 1..N
+ * (PFHE_ERR_BAD_ARGUMENT); PFHE_ERR_BAD_LENGTH unless len_in = batch*count*(in_dimension+1),
+ * len_fkey = in_dimension*ell*(k+1)*N/2 and len_out = batch*(k+1)*N; an empty batch is a no-op; then PFHE_ERR_BAD_ARGUMENT
+ * for a null pointer and (device form) an output that overlaps an input.  The host form stages its buffers through the
+ * host layer all torus calls share. */
+int pfhe_tfhe_pack_keyswitch_fft_dev(pfhe_tfhe_packfft_plan *plan, const uint64_t *lwe_in_dev, size_t len_in, size_t count,
+                                     const double *fkey_dev, size_t len_fkey, uint64_t *glwe_out_dev, size_t len_out,
+                                     void *stream);
+int pfhe_tfhe_pack_keyswitch_fft(pfhe_tfhe_packfft_plan *plan, const uint64_t *lwe_in, size_t len_in, size_t count,
+                                 const double *fkey, size_t len_fkey, uint64_t *glwe_out, size_t len_out);
+int pfhe_tfhe32_pack_keyswitch_fft_dev(pfhe_tfhe32_packfft_plan *plan, const uint32_t *lwe_in_dev, size_t len_in, size_t count,
+                                       const double *fkey_dev, size_t len_fkey, uint32_t *glwe_out_dev, size_t len_out,
+                                       void *stream);
+int pfhe_tfhe32_pack_keyswitch_fft(pfhe_tfhe32_packfft_plan *plan, const uint32_t *lwe_in, size_t len_in, size_t count,
+                                   const double *fkey, size_t len_fkey, uint32_t *glwe_out, size_t len_out);
 
 #ifdef __cplusplus
 }

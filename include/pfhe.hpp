@@ -1087,4 +1087,72 @@ inline void multimsg_lwe_extract_dev(const FullComplex64FftTable &fft, size_t gl
     check(pfhe_tfhe32_multimsg_extract_dev(fft.handle(), glwe_dimension, multi_dev, len_multi, count, lwe_dev, len_lwe, stream));
 }
 
+// The packing key switch in the Fourier domain (pfhe_tfhe{,32}_packfft_*, _pack_keyswitch_fft*): lwe_pack_keyswitch's rule
+// as one external product of in_dimension * ell rows against the half-spectrum key of tfhe_pack_key_fourier_dev.  Approximate
+// as the TFHE product is and opt-in: 1 <= log N <= 11, 1 <= glwe_dimension <= 3; the exact call above serves every shape.
+// The context owns the partial sums of `chunk` groups; one holder at a time.
+class TfhePackFftContext {
+  public:
+    TfhePackFftContext(const FullComplex64FftTable &fft, size_t glwe_dimension, size_t in_dimension, uint32_t log_basis,
+                       size_t decompose_length = 0, size_t chunk = 0) {
+        check(pfhe_tfhe_packfft_plan_create(fft.handle(), glwe_dimension, in_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfhePackFftContext() { pfhe_tfhe_packfft_plan_destroy(h_); }
+    TfhePackFftContext(const TfhePackFftContext &) = delete;
+    TfhePackFftContext &operator=(const TfhePackFftContext &) = delete;
+    pfhe_tfhe_packfft_plan *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_packfft_plan_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_packfft_plan_scratch_bytes(h_); }
+
+  private:
+    pfhe_tfhe_packfft_plan *h_ = nullptr;
+};
+
+// the u32 torus
+class TfhePackFftContext32 {
+  public:
+    TfhePackFftContext32(const FullComplex64FftTable &fft, size_t glwe_dimension, size_t in_dimension, uint32_t log_basis,
+                         size_t decompose_length = 0, size_t chunk = 0) {
+        check(pfhe_tfhe32_packfft_plan_create(fft.handle(), glwe_dimension, in_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfhePackFftContext32() { pfhe_tfhe32_packfft_plan_destroy(h_); }
+    TfhePackFftContext32(const TfhePackFftContext32 &) = delete;
+    TfhePackFftContext32 &operator=(const TfhePackFftContext32 &) = delete;
+    pfhe_tfhe32_packfft_plan *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_packfft_plan_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_packfft_plan_scratch_bytes(h_); }
+
+  private:
+    pfhe_tfhe32_packfft_plan *h_ = nullptr;
+};
+
+inline void tfhe_pack_key_fourier_dev(const uint64_t *pksk_dev, size_t len_pksk, double *fkey_dev, size_t len_fkey,
+                                      TfhePackFftContext &context, void *stream = nullptr) {
+    check(pfhe_tfhe_packfft_key_dev(context.handle(), pksk_dev, len_pksk, fkey_dev, len_fkey, stream));
+}
+inline void lwe_pack_keyswitch_fft(const uint64_t *lwe_in, size_t len_in, size_t count, const double *fkey, size_t len_fkey,
+                                   uint64_t *glwe_out, size_t len_out, TfhePackFftContext &context) {
+    check(pfhe_tfhe_pack_keyswitch_fft(context.handle(), lwe_in, len_in, count, fkey, len_fkey, glwe_out, len_out));
+}
+inline void lwe_pack_keyswitch_fft_dev(const uint64_t *lwe_in_dev, size_t len_in, size_t count, const double *fkey_dev,
+                                       size_t len_fkey, uint64_t *glwe_out_dev, size_t len_out, TfhePackFftContext &context,
+                                       void *stream = nullptr) {
+    check(pfhe_tfhe_pack_keyswitch_fft_dev(context.handle(), lwe_in_dev, len_in, count, fkey_dev, len_fkey, glwe_out_dev, len_out,
+          stream));
+}
+inline void tfhe_pack_key_fourier_dev(const uint32_t *pksk_dev, size_t len_pksk, double *fkey_dev, size_t len_fkey,
+                                      TfhePackFftContext32 &context, void *stream = nullptr) {
+    check(pfhe_tfhe32_packfft_key_dev(context.handle(), pksk_dev, len_pksk, fkey_dev, len_fkey, stream));
+}
+inline void lwe_pack_keyswitch_fft(const uint32_t *lwe_in, size_t len_in, size_t count, const double *fkey, size_t len_fkey,
+                                   uint32_t *glwe_out, size_t len_out, TfhePackFftContext32 &context) {
+    check(pfhe_tfhe32_pack_keyswitch_fft(context.handle(), lwe_in, len_in, count, fkey, len_fkey, glwe_out, len_out));
+}
+inline void lwe_pack_keyswitch_fft_dev(const uint32_t *lwe_in_dev, size_t len_in, size_t count, const double *fkey_dev,
+                                       size_t len_fkey, uint32_t *glwe_out_dev, size_t len_out, TfhePackFftContext32 &context,
+                                       void *stream = nullptr) {
+    check(pfhe_tfhe32_pack_keyswitch_fft_dev(context.handle(), lwe_in_dev, len_in, count, fkey_dev, len_fkey, glwe_out_dev, len_out,
+          stream));
+}
+
 }  // namespace pfhe

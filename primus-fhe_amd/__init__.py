@@ -21,7 +21,8 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    glwe_phase_dev, lwe_encrypt, lwe_encrypt_dev, lwe_phase, lwe_phase_dev, tfhe_generate_bsk_dev,
                    tfhe_generate_ksk_dev, torus_noise, torus_uniform, lwe_pack_keyswitch, lwe_pack_keyswitch_dev,
                    tfhe_generate_pksk_dev, glwe_sample_extract_first_few, glwe_sample_extract_first_few_dev,
-                   multimsg_lwe_extract, multimsg_lwe_extract_dev)
+                   multimsg_lwe_extract, multimsg_lwe_extract_dev, TfhePackFftContext, tfhe_pack_key_fourier_dev,
+                   lwe_pack_keyswitch_fft, lwe_pack_keyswitch_fft_dev)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -39,4 +40,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "glwe_encrypt_dev", "glwe_phase", "glwe_phase_dev", "ggsw_add_gadget_dev", "TfheKeyShape", "tfhe_generate_bsk_dev",
            "tfhe_generate_ksk_dev", "torus_uniform", "torus_noise", "lwe_pack_keyswitch",
            "lwe_pack_keyswitch_dev", "tfhe_generate_pksk_dev", "glwe_sample_extract_first_few",
-           "glwe_sample_extract_first_few_dev", "multimsg_lwe_extract", "multimsg_lwe_extract_dev", "build", "lib", "library_path", "status_string"]
+           "glwe_sample_extract_first_few_dev", "multimsg_lwe_extract", "multimsg_lwe_extract_dev",
+           "TfhePackFftContext", "tfhe_pack_key_fourier_dev", "lwe_pack_keyswitch_fft", "lwe_pack_keyswitch_fft_dev", "build", "lib", "library_path", "status_string"]

@@ -232,6 +232,14 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "sample_extract_first_few", ci, vp, sz, vp, sz, sz, vp, sz)
         sig(tp + "multimsg_extract_dev", ci, vp, sz, vp, sz, sz, vp, sz, vp)
         sig(tp + "multimsg_extract", ci, vp, sz, vp, sz, sz, vp, sz)
+        pf = tp + "packfft_"                         # the packing key switch in the Fourier domain: plan, key, call
+        sig(pf + "plan_create", ci, vp, sz, sz, u32, sz, sz, C.POINTER(vp))
+        sig(pf + "plan_destroy", None, vp)
+        sig(pf + "plan_in_use", ci, vp)
+        sig(pf + "plan_scratch_bytes", sz, vp)
+        sig(pf + "key_dev", ci, vp, vp, sz, f64p, sz, vp)
+        sig(tp + "pack_keyswitch_fft_dev", ci, vp, vp, sz, sz, f64p, sz, vp, sz, vp)
+        sig(tp + "pack_keyswitch_fft", ci, vp, vp, sz, sz, f64p, sz, vp, sz)
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)

@@ -1,5 +1,5 @@
 // pfhe_tfhe_host.hpp — the host layer under every torus entry point (pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip,
-// pfhe_pack.hip): the constants and range tests they share, the launch of a torus kernel, and the one tail of the
+// pfhe_pack.hip, pfhe_pack_fft.hip): the constants and range tests they share, the launch of a torus kernel, and the one tail of the
 // stateless steps.  Host only.  What is not torus-specific lives in pfhe_staging.hpp, for the RNS side too: StageBuf and
 // stage_in / _out / _inout, staged_call (the staged run of a launch on host pointers), Form and form_call, refuse_null,
 // overlaps, require_exps_below_2n.

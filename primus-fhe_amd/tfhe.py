@@ -167,16 +167,16 @@ class ApproxSignedBasis:
 class _TorusContext:
     """What the four torus contexts share: the C handle, released with the object, and the sizes that follow from the table,
     the basis and the GLWE dimension.  Every create starts with (table, glwe_dimension, log_basis, decompose_length) and
-    ends with the handle; `prefix` is what the context's calls start with, `calls` what its create, destroy, in-use and
+    ends with the handle (`lead`: what a create takes between the dimension and the basis); `prefix` is what the context's calls start with, `calls` what its create, destroy, in-use and
     scratch calls are named behind it."""
 
-    def _open(self, fft, basis, glwe_dimension, prefix, args, calls=("create", "destroy", "in_use", "scratch_bytes")):
+    def _open(self, fft, basis, glwe_dimension, prefix, args, calls=("create", "destroy", "in_use", "scratch_bytes"), lead=()):
         self._w = "" if basis.bits == 64 else "32"
         self._pre = "pfhe_tfhe" + self._w + "_" + prefix
         self._destroy, self._in_use, self._scratch = calls[1:]
         h = C.c_void_p()
-        check(getattr(lib(), self._pre + calls[0])(fft._h, glwe_dimension, basis.log_basis(), basis.decompose_length(), *args,
-                                                   C.byref(h)))
+        check(getattr(lib(), self._pre + calls[0])(fft._h, glwe_dimension, *lead, basis.log_basis(), basis.decompose_length(),
+                                                   *args, C.byref(h)))
         self._h = h
         self.fft, self.basis, self.glwe_dimension = fft, basis, glwe_dimension
 
@@ -625,6 +625,59 @@ def tfhe_generate_pksk_dev(key_in, glwe_key, fft: FullComplex64FftTable, basis: 
     lb, ell = _basis_args(basis, wr)
     check(getattr(lib(), "pfhe_tfhe" + wr + "_pksk_generate_dev")(fft._h, glwe_dimension, pi, ni, pz, nz, lb, ell, pr, nr,
                                                                 _stream(stream)))
+
+
+class TfhePackFftContext(_TorusContext):
+    """Handle of the packing key switch in the Fourier domain (include/pfhe.h, pfhe_tfhe{,32}_packfft_*): the rule of
+    lwe_pack_keyswitch_dev computed as one external product of in_dimension * ell rows against the half-spectrum key of
+    tfhe_pack_key_fourier_dev.  Approximate as the TFHE product is, cheaper than the exact call when count approaches N, and
+    opt-in: 1 <= log N <= 11 and 1 <= glwe_dimension <= 3 (Unsupported otherwise; the exact call serves every shape).  Owns the
+    partial sums of `chunk` groups (0 = the default); one holder at a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, in_dimension: int, glwe_dimension: int = 1,
+                 chunk: int = 0):
+        self._open(fft, basis, glwe_dimension, "packfft_", (chunk,),
+                   ("plan_create", "plan_destroy", "plan_in_use", "plan_scratch_bytes"), lead=(in_dimension,))
+        self.in_dimension = in_dimension
+
+    @property
+    def fkey_len(self) -> int:
+        """complex values of the Fourier packing key: in_dimension x ell x (k+1) x N/2"""
+        return self.in_dimension * self.basis.decompose_length() * self.glwe_len() // 2
+
+    def pksk_len(self) -> int:
+        """words of the torus packing key it is converted from"""
+        return self.in_dimension * self.basis.decompose_length() * self.glwe_len()
+
+
+def tfhe_pack_key_fourier_dev(pksk, fkey, ctx: TfhePackFftContext, stream=None) -> None:
+    """The Fourier packing key of lwe_pack_keyswitch_fft_dev from the torus key tfhe_generate_pksk_dev wrote: the half
+    spectrum of every key polynomial, ctx.fkey_len complex128 values (or their interleaved float64 view).  Asynchronous."""
+    pk, nk, wk = _dev_words(pksk)
+    pf, nf = _dev_fourier(fkey)
+    _same_width("the packing key must have the width of the context's basis", wk, ctx._w)
+    check(getattr(lib(), ctx._pre + "key_dev")(ctx._h, pk, nk, pf, nf, _stream(stream)))
+
+
+def lwe_pack_keyswitch_fft(lwe_in: np.ndarray, fkey: np.ndarray, glwe_out: np.ndarray, count: int,
+                           ctx: TfhePackFftContext) -> None:
+    """lwe_pack_keyswitch through the Fourier domain, on host arrays: lwe_in and glwe_out as the exact call takes them, fkey
+    the Fourier packing key (complex128, or the interleaved float64 view)."""
+    pi, ni, wi = _host_words(lwe_in)
+    pf, nf = _host_fourier(fkey)
+    po, no, wo = _host_words(glwe_out)
+    _same_width("lwe_in and glwe_out must have the width of the context's basis", wi, wo, ctx._w)
+    check(getattr(lib(), "pfhe_tfhe" + ctx._w + "_pack_keyswitch_fft")(ctx._h, pi, ni, count, pf, nf, po, no))
+
+
+def lwe_pack_keyswitch_fft_dev(lwe_in, fkey, glwe_out, count: int, ctx: TfhePackFftContext, stream=None) -> None:
+    """the device form, asynchronous; glwe_out must not overlap an input and may be uninitialised"""
+    pi, ni, wi = _dev_words(lwe_in)
+    pf, nf = _dev_fourier(fkey)
+    po, no, wo = _dev_words(glwe_out)
+    _same_width("lwe_in and glwe_out must have the width of the context's basis", wi, wo, ctx._w)
+    check(getattr(lib(), "pfhe_tfhe" + ctx._w + "_pack_keyswitch_fft_dev")(ctx._h, pi, ni, count, pf, nf, po, no,
+                                                                          _stream(stream)))
 
 
 def _extract_pair(name, src, dst, fft, count, glwe_dimension, dev, stream=None):
