@@ -1341,6 +1341,115 @@ int pfhe_tfhe32_pack_keyswitch_fft_dev(pfhe_tfhe32_packfft_plan *plan, const uin
 int pfhe_tfhe32_pack_keyswitch_fft(pfhe_tfhe32_packfft_plan *plan, const uint32_t *lwe_in, size_t len_in, size_t count,
                                    const double *fkey, size_t len_fkey, uint32_t *glwe_out, size_t len_out);
 
+/* ---- the circuit bootstrap: an LWE ciphertext of a bit becomes a GGSW ciphertext (u64: no suffix, u32: 32) ----
+ * No reference counterpart; the rules are this project's own.  Conventions as everywhere on the torus side:
+ * the phase is b - <a,s>; ApproxSignedBasis has its levels least significant first, g_l = 2^(drop_bits + l*log_basis); digits
+ * are those of pfhe_tfhe*_keyswitch_dev (init_carry, the carry from bit drop_bits-1, the log_basis 1 mask); a torus-form
+ * GGSW is [(k+1) rows r][ell levels l][(k+1) components][N] words, as pfhe_tfhe*_ggsw_add_gadget_dev takes it.  Under the
+ * phase rule row (r, l) of a GGSW of m is a GLWE ciphertext of f_r(m*g_l), with f_r(x) = -z_r*x for r < k (a polynomial,
+ * z_r the r-th key polynomial) and f_k(x) = x on coefficient 0.
+ *
+ * Private functional key switch — stateless, as pfhe_tfhe*_pack_keyswitch_dev.  With ell = decompose_length (0 = the full
+ * BITS / log_basis):
+ *   lwe_in  batch x levels x (in_dimension+1) words: ciphertext (e, l) is at index e*levels + l, a then b;
+ *   pfksk   (k+1) x (in_dimension+1) x ell GLWE rows of (k+1)*N words: row (u, j, t) encrypts f_u(s'_j * g_t) with
+ *           s' = (s_in, -1): the body word is one more mask word whose key is -1 (it is decomposed with the rest, not
+ *           added in the clear, because f_u of it is secret for u < k);
+ *   out     batch x (k+1) x levels x (k+1)*N words, one GGSW-shaped block per e; it may be uninitialised and must not
+ *           overlap an input.
+ * Modulo 2^BITS, with c_{e,l} = (a, b) of ciphertext (e, l):
+ *   out[e][u][l] = - sum_{j <= in_dimension} sum_{t < ell} d_t(c_{e,l,j}) * pfksk[u][j][t],
+ * so that the phase of out[e][u][l] is f_u of the (rounded) phase of ciphertext (e, l).  Exact wrapping integer
+ * arithmetic; no atomics, no scratch beyond the kernel's own LDS; a call is repeatable and its result depends neither on
+ * the batch size nor on how the kernel tiles the work.  levels = 1 is the plain form: one ciphertext to k+1 GLWE ciphertexts.
+ * Statuses, in this order and all before the device is touched: ApproxSignedBasis::new's assert!s (PFHE_ERR_BAD_ARGUMENT);
+ * PFHE_ERR_BAD_ARGUMENT for glwe_dimension outside 1..64 or in_dimension outside 1..2^31-2; for a null table; for levels
+ * outside 1..64; PFHE_ERR_BAD_LENGTH unless len_in = batch*levels*(in_dimension+1),
+ * len_pfksk = (k+1)*(in_dimension+1)*ell*(k+1)*N and len_out = batch*(k+1)*levels*(k+1)*N; an empty batch is a no-op; then
+ * PFHE_ERR_BAD_ARGUMENT for a null pointer and, in the device form only, for an output that overlaps an input; only then
+ * the device (PFHE_ERR_NO_DEVICE). */
+int pfhe_tfhe_private_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in_dev, size_t len_in,
+                                    size_t in_dimension, size_t levels, const uint64_t *pfksk_dev, size_t len_pfksk,
+                                    uint32_t log_basis, size_t decompose_length, uint64_t *out_dev, size_t len_out,
+                                    void *stream);
+int pfhe_tfhe_private_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
+                                size_t in_dimension, size_t levels, const uint64_t *pfksk, size_t len_pfksk, uint32_t log_basis,
+                                size_t decompose_length, uint64_t *out, size_t len_out);
+int pfhe_tfhe32_private_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in_dev, size_t len_in,
+                                      size_t in_dimension, size_t levels, const uint32_t *pfksk_dev, size_t len_pfksk,
+                                      uint32_t log_basis, size_t decompose_length, uint32_t *out_dev, size_t len_out,
+                                      void *stream);
+int pfhe_tfhe32_private_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
+                                  size_t in_dimension, size_t levels, const uint32_t *pfksk, size_t len_pfksk,
+                                  uint32_t log_basis, size_t decompose_length, uint32_t *out, size_t len_out);
+/* The key of that switch, generated as pfhe_tfhe*_pksk_generate_dev generates the packing key: pfksk arrives holding the
+ * randomness of (k+1) x (in_dimension+1) x ell GLWE rows (mask polynomials uniform, body polynomials noise).  The GLWE body
+ * call (add) runs on all rows under glwe_key (k*N words), then one launch adds the messages, with s'_j = key_in[j] for
+ * j < in_dimension and -1 for j = in_dimension:
+ *   row (k, j, t):          B[0] <- B[0] + s'_j * g_t;
+ *   row (u, j, t), u < k:   B[i] <- B[i] - s'_j * g_t * z_u[i]   for every coefficient i.
+ * No random number is drawn; a second call adds body and messages a second time.  Statuses as
+ * pfhe_tfhe*_pksk_generate_dev: ApproxSignedBasis::new's assert!s, then the dimensions and the table, then
+ * PFHE_ERR_BAD_LENGTH unless len_glwe_key = k*N and len_pfksk = (k+1)*(in_dimension+1)*ell*(k+1)*N, then null pointers and a
+ * key that overlaps pfksk. */
+int pfhe_tfhe_pfksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *key_in_dev, size_t in_dimension,
+                                 const uint64_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis, size_t decompose_length,
+                                 uint64_t *pfksk_dev, size_t len_pfksk, void *stream);
+int pfhe_tfhe32_pfksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *key_in_dev, size_t in_dimension,
+                                   const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
+                                   size_t decompose_length, uint32_t *pfksk_dev, size_t len_pfksk, void *stream);
+/* The circuit bootstrap handle.  An input LWE ciphertext encrypts a bit m as m*2^(BITS-1).  Per chunk of inputs, per input e
+ * and level l of the output basis (cbs_log_basis, cbs_decompose_length: ell_cb levels g_l):
+ *   1. the modulus switch of pfhe_tfhe*_modswitch_dev on (a, b + 2^(BITS-2)): the switched phase sits a quarter turn from
+ *      both sign changes; the exponents of e serve all ell_cb accumulators;
+ *   2. ACC_{e,l} = X^{neg_b[e]} * TV_l, TV_l the trivial GLWE whose body has -g_l/2 on every coefficient, written from
+ *      constants (no test vector in memory);
+ *   3. the blind rotation of pfhe_tfhe*_blindrot_rotate_dev over batch*ell_cb accumulators, through a rotation handle the
+ *      circuit bootstrap owns;
+ *   4. sample extraction at index 0, and g_l/2 added to the extracted body: the phase is then m*g_l plus noise;
+ *   5. the private functional key switch above with levels = ell_cb and in_dimension = k*N into ggsw_out.
+ *   lwe_in    batch*(n+1) words, n = lwe_dimension;  bsk  n Fourier GGSW keys as pfhe_tfhe*_blindrot_rotate_dev takes them;
+ *   pfksk     (k+1)*(k*N+1)*pfks_ell*(k+1)*N words as pfhe_tfhe*_pfksk_generate_dev writes them for key_in = the k GLWE key
+ *             polynomials end to end (the key of an extracted sample);
+ *   ggsw_out  batch x (k+1)*ell_cb*(k+1)*N words: a torus-form GGSW of m per input under the GLWE key, in the output basis;
+ *             pfhe_fft_forward_torus*_dev of it is what pfhe_tfhe*_external_product_to_dev takes with a plan on that basis.
+ *             It must not overlap an input and may be uninitialised.
+ * The handle gives, word for word, what the composition of the public calls named above gives.
+ * create, everything before the device first: the blind rotation's checks in their order (ApproxSignedBasis::new's assert!s,
+ * PFHE_ERR_UNSUPPORTED for glwe_dimension above 64, PFHE_ERR_BAD_ARGUMENT for a null table); then PFHE_ERR_BAD_ARGUMENT for
+ * glwe_dimension 0 or lwe_dimension outside 1..2^31-2, for the assert!s of the output basis and of the key switch's basis,
+ * and for an output basis with drop_bits 0 (g_l/2 must be a word); then the rotation's create.  The handle borrows `fft`,
+ * owns a blind-rotation handle and, for `chunk` inputs (chunk*ell_cb accumulators), the accumulators, the exponents, neg_b
+ * and the extracted ciphertexts — everything is allocated here.  chunk 0: the rotation's default, capped at about 256 MiB
+ * of accumulators.  A call only queues work on `stream` (no allocation, no host synchronisation), so a whole circuit
+ * bootstrap can be captured into a HIP graph; a batch larger than the chunk runs chunk by chunk.  One holder at a time
+ * (PFHE_ERR_BUSY).  A call refuses, in this order: a null handle, a second holder, PFHE_ERR_BAD_LENGTH for any length that
+ * does not fit the others, (the empty batch is a no-op,) null pointers, a bsk not aligned to 16 bytes, an output that
+ * overlaps an input (device form), the device. */
+typedef struct pfhe_tfhe_cbs_handle pfhe_tfhe_cbs_handle;
+typedef struct pfhe_tfhe32_cbs_handle pfhe_tfhe32_cbs_handle;
+int pfhe_tfhe_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+                         size_t pfks_decompose_length, size_t chunk, pfhe_tfhe_cbs_handle **out);
+void pfhe_tfhe_cbs_destroy(pfhe_tfhe_cbs_handle *h);
+int pfhe_tfhe_cbs_in_use(const pfhe_tfhe_cbs_handle *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h);  /* the rotation handle's scratch included */
+int pfhe_tfhe_cbs_dev(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk,
+                      const uint64_t *pfksk_dev, size_t len_pfksk, uint64_t *ggsw_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_cbs(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                  const uint64_t *pfksk, size_t len_pfksk, uint64_t *ggsw_out, size_t len_out);
+int pfhe_tfhe32_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                           size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+                           size_t pfks_decompose_length, size_t chunk, pfhe_tfhe32_cbs_handle **out);
+void pfhe_tfhe32_cbs_destroy(pfhe_tfhe32_cbs_handle *h);
+int pfhe_tfhe32_cbs_in_use(const pfhe_tfhe32_cbs_handle *h);
+size_t pfhe_tfhe32_cbs_scratch_bytes(const pfhe_tfhe32_cbs_handle *h);
+int pfhe_tfhe32_cbs_dev(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                        size_t len_bsk, const uint32_t *pfksk_dev, size_t len_pfksk, uint32_t *ggsw_out_dev, size_t len_out,
+                        void *stream);
+int pfhe_tfhe32_cbs(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                    const uint32_t *pfksk, size_t len_pfksk, uint32_t *ggsw_out, size_t len_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1155,4 +1155,107 @@ inline void lwe_pack_keyswitch_fft_dev(const uint32_t *lwe_in_dev, size_t len_in
           stream));
 }
 
+// The circuit bootstrap (pfhe_tfhe{,32}_private_keyswitch*, _pfksk_generate_dev, _cbs_*): the private functional key switch
+// turns batch x levels LWE ciphertexts into GGSW-shaped blocks whose row (u, l) has the phase f_u of input (e, l), under the
+// key tfhe_generate_pfksk_dev writes in place from the caller's randomness; TfheCircuitBootstrap runs, per input bit and
+// level of the output basis, modulus switch, ACC = X^{-b~} * (-g_l/2), the blind rotation, extraction with g_l/2 added and
+// that key switch, and gives a torus-form GGSW of the bit.  uint64_t overloads: the u64 torus; uint32_t: u32.
+inline void lwe_private_keyswitch(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
+                                  size_t in_dimension, size_t levels, const uint64_t *pfksk, size_t len_pfksk,
+                                  uint32_t log_basis, size_t decompose_length, uint64_t *out, size_t len_out) {
+    check(pfhe_tfhe_private_keyswitch(fft.handle(), glwe_dimension, lwe_in, len_in, in_dimension, levels, pfksk, len_pfksk,
+          log_basis, decompose_length, out, len_out));
+}
+inline void lwe_private_keyswitch_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *lwe_in_dev,
+                                      size_t len_in, size_t in_dimension, size_t levels, const uint64_t *pfksk_dev,
+                                      size_t len_pfksk, uint32_t log_basis, size_t decompose_length, uint64_t *out_dev,
+                                      size_t len_out, void *stream = nullptr) {
+    check(pfhe_tfhe_private_keyswitch_dev(fft.handle(), glwe_dimension, lwe_in_dev, len_in, in_dimension, levels, pfksk_dev,
+          len_pfksk, log_basis, decompose_length, out_dev, len_out, stream));
+}
+inline void tfhe_generate_pfksk_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *key_in_dev,
+                                    size_t in_dimension, const uint64_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
+                                    size_t decompose_length, uint64_t *pfksk_dev, size_t len_pfksk, void *stream = nullptr) {
+    check(pfhe_tfhe_pfksk_generate_dev(fft.handle(), glwe_dimension, key_in_dev, in_dimension, glwe_key_dev, len_glwe_key,
+          log_basis, decompose_length, pfksk_dev, len_pfksk, stream));
+}
+
+inline void lwe_private_keyswitch(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
+                                  size_t in_dimension, size_t levels, const uint32_t *pfksk, size_t len_pfksk,
+                                  uint32_t log_basis, size_t decompose_length, uint32_t *out, size_t len_out) {
+    check(pfhe_tfhe32_private_keyswitch(fft.handle(), glwe_dimension, lwe_in, len_in, in_dimension, levels, pfksk, len_pfksk,
+          log_basis, decompose_length, out, len_out));
+}
+inline void lwe_private_keyswitch_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *lwe_in_dev,
+                                      size_t len_in, size_t in_dimension, size_t levels, const uint32_t *pfksk_dev,
+                                      size_t len_pfksk, uint32_t log_basis, size_t decompose_length, uint32_t *out_dev,
+                                      size_t len_out, void *stream = nullptr) {
+    check(pfhe_tfhe32_private_keyswitch_dev(fft.handle(), glwe_dimension, lwe_in_dev, len_in, in_dimension, levels, pfksk_dev,
+          len_pfksk, log_basis, decompose_length, out_dev, len_out, stream));
+}
+inline void tfhe_generate_pfksk_dev(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *key_in_dev,
+                                    size_t in_dimension, const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
+                                    size_t decompose_length, uint32_t *pfksk_dev, size_t len_pfksk, void *stream = nullptr) {
+    check(pfhe_tfhe32_pfksk_generate_dev(fft.handle(), glwe_dimension, key_in_dev, in_dimension, glwe_key_dev, len_glwe_key,
+          log_basis, decompose_length, pfksk_dev, len_pfksk, stream));
+}
+
+// Owns a blind-rotation handle and every buffer between the stages for `chunk` inputs; one holder at a time.
+// TfheCircuitBootstrap32: the u32 torus.
+class TfheCircuitBootstrap {
+  public:
+    TfheCircuitBootstrap(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+        size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+        size_t pfks_decompose_length, size_t chunk = 0) {
+        check(pfhe_tfhe_cbs_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis,
+                                   cbs_decompose_length, pfks_log_basis, pfks_decompose_length, chunk, &h_));
+    }
+    ~TfheCircuitBootstrap() { pfhe_tfhe_cbs_destroy(h_); }
+    TfheCircuitBootstrap(const TfheCircuitBootstrap &) = delete;
+    TfheCircuitBootstrap &operator=(const TfheCircuitBootstrap &) = delete;
+    pfhe_tfhe_cbs_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_cbs_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_cbs_scratch_bytes(h_); }
+    void circuit_bootstrap(const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const uint64_t *pfksk,
+                           size_t len_pfksk, uint64_t *ggsw_out, size_t len_out) {
+        check(pfhe_tfhe_cbs(h_, lwe_in, len_in, bsk, len_bsk, pfksk, len_pfksk, ggsw_out, len_out));
+    }
+    void circuit_bootstrap_dev(const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk,
+                               const uint64_t *pfksk_dev, size_t len_pfksk, uint64_t *ggsw_out_dev, size_t len_out,
+                               void *stream = nullptr) {
+        check(pfhe_tfhe_cbs_dev(h_, lwe_in_dev, len_in, bsk_dev, len_bsk, pfksk_dev, len_pfksk, ggsw_out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe_cbs_handle *h_ = nullptr;
+};
+
+class TfheCircuitBootstrap32 {
+  public:
+    TfheCircuitBootstrap32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+        size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+        size_t pfks_decompose_length, size_t chunk = 0) {
+        check(pfhe_tfhe32_cbs_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis,
+                                   cbs_decompose_length, pfks_log_basis, pfks_decompose_length, chunk, &h_));
+    }
+    ~TfheCircuitBootstrap32() { pfhe_tfhe32_cbs_destroy(h_); }
+    TfheCircuitBootstrap32(const TfheCircuitBootstrap32 &) = delete;
+    TfheCircuitBootstrap32 &operator=(const TfheCircuitBootstrap32 &) = delete;
+    pfhe_tfhe32_cbs_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_cbs_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_cbs_scratch_bytes(h_); }
+    void circuit_bootstrap(const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const uint32_t *pfksk,
+                           size_t len_pfksk, uint32_t *ggsw_out, size_t len_out) {
+        check(pfhe_tfhe32_cbs(h_, lwe_in, len_in, bsk, len_bsk, pfksk, len_pfksk, ggsw_out, len_out));
+    }
+    void circuit_bootstrap_dev(const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk,
+                               const uint32_t *pfksk_dev, size_t len_pfksk, uint32_t *ggsw_out_dev, size_t len_out,
+                               void *stream = nullptr) {
+        check(pfhe_tfhe32_cbs_dev(h_, lwe_in_dev, len_in, bsk_dev, len_bsk, pfksk_dev, len_pfksk, ggsw_out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe32_cbs_handle *h_ = nullptr;
+};
+
 }  // namespace pfhe

@@ -22,7 +22,9 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    tfhe_generate_ksk_dev, torus_noise, torus_uniform, lwe_pack_keyswitch, lwe_pack_keyswitch_dev,
                    tfhe_generate_pksk_dev, glwe_sample_extract_first_few, glwe_sample_extract_first_few_dev,
                    multimsg_lwe_extract, multimsg_lwe_extract_dev, TfhePackFftContext, tfhe_pack_key_fourier_dev,
-                   lwe_pack_keyswitch_fft, lwe_pack_keyswitch_fft_dev)
+                   lwe_pack_keyswitch_fft, lwe_pack_keyswitch_fft_dev, lwe_private_keyswitch, lwe_private_keyswitch_dev,
+                   tfhe_generate_pfksk_dev, TfheCircuitBootstrapContext, tfhe_circuit_bootstrap,
+                   tfhe_circuit_bootstrap_dev)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -41,4 +43,6 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "tfhe_generate_ksk_dev", "torus_uniform", "torus_noise", "lwe_pack_keyswitch",
            "lwe_pack_keyswitch_dev", "tfhe_generate_pksk_dev", "glwe_sample_extract_first_few",
            "glwe_sample_extract_first_few_dev", "multimsg_lwe_extract", "multimsg_lwe_extract_dev",
-           "TfhePackFftContext", "tfhe_pack_key_fourier_dev", "lwe_pack_keyswitch_fft", "lwe_pack_keyswitch_fft_dev", "build", "lib", "library_path", "status_string"]
+           "TfhePackFftContext", "tfhe_pack_key_fourier_dev", "lwe_pack_keyswitch_fft", "lwe_pack_keyswitch_fft_dev",
+           "lwe_private_keyswitch", "lwe_private_keyswitch_dev", "tfhe_generate_pfksk_dev", "TfheCircuitBootstrapContext",
+           "tfhe_circuit_bootstrap", "tfhe_circuit_bootstrap_dev", "build", "lib", "library_path", "status_string"]

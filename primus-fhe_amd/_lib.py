@@ -240,6 +240,17 @@ def _declare(lib: C.CDLL) -> None:
         sig(pf + "key_dev", ci, vp, vp, sz, f64p, sz, vp)
         sig(tp + "pack_keyswitch_fft_dev", ci, vp, vp, sz, sz, f64p, sz, vp, sz, vp)
         sig(tp + "pack_keyswitch_fft", ci, vp, vp, sz, sz, f64p, sz, vp, sz)
+        # the circuit bootstrap: the private functional key switch, its key, and the handle over the rotation and it
+        sig(tp + "private_keyswitch_dev", ci, vp, sz, vp, sz, sz, sz, vp, sz, u32, sz, vp, sz, vp)
+        sig(tp + "private_keyswitch", ci, vp, sz, vp, sz, sz, sz, vp, sz, u32, sz, vp, sz)
+        sig(tp + "pfksk_generate_dev", ci, vp, sz, vp, sz, vp, sz, u32, sz, vp, sz, vp)
+        cb = tp + "cbs"
+        sig(cb + "_create", ci, vp, sz, u32, sz, sz, u32, sz, u32, sz, sz, C.POINTER(vp))
+        sig(cb + "_destroy", None, vp)
+        sig(cb + "_in_use", ci, vp)
+        sig(cb + "_scratch_bytes", sz, vp)
+        sig(cb + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp)
+        sig(cb, ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz)
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)

@@ -1,0 +1,587 @@
+// pfhe_cbs.hip — from an encrypted bit to a GGSW ciphertext: the private functional key switch, its key, and the circuit
+// bootstrap handle that runs a blind rotation per level in front of it (include/pfhe.h: pfhe_tfhe{,32}_private_keyswitch*,
+// _pfksk_generate_dev, _cbs_*).  No reference counterpart; DESIGN.md §19 states the rules.
+//
+//   private key switch   out[e][u][l] = - sum_{j <= in_dimension} sum_{t < ell} d_t(c_{e,l,j}) PFKSK[u][j][t] modulo 2^BITS,
+//                        c = (a, b): the body word is decomposed as one more mask word (its key is -1).  Row (u, j, t) of the
+//                        key encrypts f_u(s'_j g_t), s' = (s_in, -1), f_u(x) = -z_u x for u < k and x on coefficient 0
+//                        for u = k, so that the phase of out[e][u][l] is f_u of the input's phase: row (u, l) of a GGSW.
+//                        Digits exactly as the LWE key switch forms them (init_carry / digit_word of pfhe_fft_device.hpp).
+//   its key              the GLWE body call of pfhe_keygen.hip on all rows of the caller's randomness, then the messages.
+//   circuit bootstrap    per input e and level l of the output basis: modulus switch of (a, b + 2^(BITS-2)), ACC_{e,l} =
+//                        X^{neg_b[e]} TV_l with TV_l = (0, .., 0, -g_l/2 on every coefficient) written from constants, the
+//                        rotation handle on batch * levels accumulators, extraction at index 0 with g_l/2 added to the body,
+//                        and the private key switch with levels = ell_cb into the caller's GGSWs.
+// Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
+// host forms go through pfhe_tfhe_host.hpp; the private key switch keeps its own 3-D grid.
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+
+#include "pfhe_tfhe_handles.hpp"
+
+using namespace pfhe;
+
+namespace pfhe {
+namespace {
+
+// ---------------- the private functional key switch ----------------
+//
+// A small integer GEMM per key block u: M = batch * levels input ciphertexts, K = (in_dimension + 1) * ell key rows,
+// (k+1) N columns.  The tiling is the LWE key switch's (pfhe_bootstrap.hip): one workgroup owns kPfTileM ciphertexts x
+// kPfTileN columns of ONE key block (grid.z); a thread owns kPfRows ciphertexts (its wave's) x kPfCols columns (its
+// lane's, kPfLanes apart) and keeps their sums in registers.  The workgroup walks the input words, body included, in
+// groups of `ki`: every (ciphertext, word) pair of the group gets its ell signed digits from ONE thread, which writes
+// them to LDS as words; then every thread streams the group's key rows, coalesced along the columns and kPfUnroll rows
+// in flight, against the digits of its ciphertexts, which all lanes of a wave read from the same LDS address (a
+// broadcast).  ki * ell <= kPfMaxRows bounds the LDS at kPfMaxRows * kPfTileM words: 8 KiB for u32, 16 KiB for u64, a
+// constant of the design.  Input row m = e * levels + l is stored to out[e][u][l].
+constexpr int kPfLanes = 64, kPfWaves = kThreads / kPfLanes;
+constexpr int kPfRows = 8, kPfCols = 2;
+constexpr int kPfTileM = kPfWaves * kPfRows, kPfTileN = kPfLanes * kPfCols;
+constexpr u32 kPfMaxRows = 64;
+constexpr int kPfUnroll = 4;
+constexpr size_t kMaxLevels = 64;
+
+struct PfksShape {
+    u32 in_dim, k, log_n, levels, log_basis, ell, drop_bits, ki;
+};
+
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_pfks_kernel(const W *__restrict__ lwe_in, const W *__restrict__ pfksk,
+                                                             W *__restrict__ out, PfksShape s, u64 m0, u64 m_total) {
+    __shared__ W dig[kPfMaxRows * kPfTileM];  // [word of the group][level][ciphertext of the tile]
+    const u32 lane = threadIdx.x % kPfLanes, wave = threadIdx.x / kPfLanes;
+    const u32 cols = (s.k + 1) << s.log_n, words = s.in_dim + 1;
+    const u32 c0 = blockIdx.x * kPfTileN + lane;
+    const u64 r0 = m0 + (u64)blockIdx.y * kPfTileM;
+    const u32 u = blockIdx.z;
+    W acc[kPfRows][kPfCols];
+#pragma unroll
+    for (int r = 0; r < kPfRows; ++r)
+#pragma unroll
+        for (int c = 0; c < kPfCols; ++c) acc[r][c] = 0;
+
+    // the key columns of this thread in block u; a column past the end reads the last one instead (its sums are never
+    // stored), so that no load of the inner loop sits behind a branch
+    const W *key[kPfCols];
+#pragma unroll
+    for (int c = 0; c < kPfCols; ++c) key[c] = pfksk + (u64)u * words * s.ell * cols + min(c0 + c * kPfLanes, cols - 1);
+
+    // the pair this thread decomposes in every group: word ii of the group, ciphertext ei of the tile
+    const u32 ii = threadIdx.x % s.ki, ei = threadIdx.x / s.ki;
+    for (u32 i0 = 0; i0 < words; i0 += s.ki) {
+        if (ei < (u32)kPfTileM) {
+            const bool live = r0 + ei < m_total && i0 + ii < words;
+            const W v = live ? lwe_in[(r0 + ei) * words + i0 + ii] : (W)0;
+            u32 carry = init_carry(v, s.drop_bits);
+            for (u32 l = 0; l < s.ell; ++l)
+                dig[(ii * s.ell + l) * kPfTileM + ei] = digit_word(v, s.drop_bits + l * s.log_basis, s.log_basis, carry);
+        }
+        __syncthreads();
+        const u32 rows = min(s.ki, words - i0) * s.ell;
+        const u64 key_row = (u64)i0 * s.ell;
+        u32 row = 0;
+        // kPfUnroll rows at a time: all their key words are requested before the first is used
+        for (; row + kPfUnroll <= rows; row += kPfUnroll) {
+            W kv[kPfUnroll][kPfCols];
+#pragma unroll
+            for (int q = 0; q < kPfUnroll; ++q)
+#pragma unroll
+                for (int c = 0; c < kPfCols; ++c) kv[q][c] = key[c][(key_row + row + q) * cols];
+#pragma unroll
+            for (int q = 0; q < kPfUnroll; ++q)
+#pragma unroll
+                for (int r = 0; r < kPfRows; ++r) {
+                    const W d = dig[(row + q) * kPfTileM + wave * kPfRows + r];
+#pragma unroll
+                    for (int c = 0; c < kPfCols; ++c) acc[r][c] += d * kv[q][c];
+                }
+        }
+        for (; row < rows; ++row) {
+            W kv[kPfCols];
+#pragma unroll
+            for (int c = 0; c < kPfCols; ++c) kv[c] = key[c][(key_row + row) * cols];
+#pragma unroll
+            for (int r = 0; r < kPfRows; ++r) {
+                const W d = dig[row * kPfTileM + wave * kPfRows + r];
+#pragma unroll
+                for (int c = 0; c < kPfCols; ++c) acc[r][c] += d * kv[c];
+            }
+        }
+        __syncthreads();  // the next group overwrites the digits
+    }
+#pragma unroll
+    for (int r = 0; r < kPfRows; ++r) {
+        const u64 m = r0 + wave * kPfRows + r;
+        if (m >= m_total) continue;
+        const u64 e = m / s.levels, l = m - e * s.levels;
+        W *dst = out + ((e * (s.k + 1) + u) * s.levels + l) * cols;
+#pragma unroll
+        for (int c = 0; c < kPfCols; ++c) {
+            const u32 col = c0 + c * kPfLanes;
+            if (col < cols) dst[col] = (W)0 - acc[r][c];
+        }
+    }
+}
+
+// ---------------- the key's messages ----------------
+
+// Per (j, t): one thread per body coefficient of the k rows (u < k, j, t), which get -s'_j g_t z_u[i], and one for
+// coefficient 0 of row (k, j, t), which gets s'_j g_t; s'_j = key_in[j] for j < in_dim and -1 for the body word
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_pfksk_add_message_kernel(W *__restrict__ pfksk, const W *__restrict__ key_in,
+                                                                          const W *__restrict__ glwe_key, u32 k, u32 log_n,
+                                                                          u32 in_dim, u32 ell, u32 log_basis, u32 drop,
+                                                                          u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u64 per = ((u64)k << log_n) + 1;
+    const u64 pair = t / per, q = t - pair * per;
+    const u64 j = pair / ell;
+    const u32 lvl = (u32)(pair - j * ell);
+    const W msg = (j < in_dim ? key_in[j] : (W)0 - (W)1) << (drop + lvl * log_basis);
+    const u32 u = (u32)(q >> log_n), i = (u32)(q & ((1u << log_n) - 1));  // q = kN: u = k, i = 0
+    W *body = pfksk + (((((u64)u * (in_dim + 1) + j) * ell + lvl) * (k + 1) + k) << log_n);
+    if (u == k)
+        body[0] += msg;
+    else
+        body[i] -= msg * glwe_key[((u64)u << log_n) + i];
+}
+
+// ---------------- the stages of the circuit bootstrap around the rotation ----------------
+
+// The modulus switch of pfhe_bootstrap.hip on (a, b + 2^(BITS-2)), one thread per input word: the exponents of input e are
+// written once per level, exps[(e levels + l) n + i], for the levels accumulators the rotation sees; neg_b[e] once
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_cbs_modswitch_kernel(const W *__restrict__ lwe, u32 *__restrict__ exps,
+                                                                      u32 *__restrict__ neg_b, u32 n, u32 log_n, u32 levels,
+                                                                      u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u64 e = t / (n + 1);
+    const u32 i = (u32)(t - e * (n + 1));
+    const u32 shift = 8 * sizeof(W) - log_n - 1, two_n_mask = (2u << log_n) - 1;
+    const W w = i < n ? lwe[t] : (W)(lwe[t] + ((W)1 << (8 * sizeof(W) - 2)));
+    const u32 v = (u32)(((w >> (shift - 1)) + 1) >> 1) & two_n_mask;
+    if (i < n) {
+        for (u32 l = 0; l < levels; ++l) exps[(e * levels + l) * n + i] = v;
+    } else {
+        neg_b[e] = ((2u << log_n) - v) & two_n_mask;
+    }
+}
+
+// ACC_{e,l} = X^{neg_b[e]} TV_l, one thread per accumulator word: the mask polynomials are 0 and every body coefficient is
+// -+g_l/2, g_l/2 = 2^(half_shift + l log_basis), with the sign of tfhe_acc_init_kernel's rotation
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_cbs_acc_init_kernel(W *__restrict__ acc, const u32 *__restrict__ neg_b, u32 k,
+                                                                     u32 log_n, u32 levels, u32 log_basis, u32 half_shift,
+                                                                     u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u32 n = 1u << log_n;
+    const u64 poly = t >> log_n, a = poly / (k + 1);
+    if (poly - a * (k + 1) != k) {
+        acc[t] = 0;
+        return;
+    }
+    const u64 e = a / levels;
+    const u32 l = (u32)(a - e * levels);
+    const u32 r = neg_b[e] & (2 * n - 1);
+    const bool high = r >= n;
+    const u32 rot = high ? r - n : r;
+    const u32 j = (u32)(t & (n - 1));
+    const W v = (W)0 - ((W)1 << (half_shift + l * log_basis));  // TV_l: -g_l/2
+    acc[t] = ((j < rot) != high) ? (W)0 - v : v;
+}
+
+// sample extraction at index 0 of accumulator (e, l) with g_l/2 added to the body: out[jN] = A_j[0], out[jN + i] =
+// -A_j[N - i], out[kN] = B[0] + g_l/2
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_cbs_extract_kernel(const W *__restrict__ glwe, W *__restrict__ lwe, u32 k,
+                                                                    u32 log_n, u32 levels, u32 log_basis, u32 half_shift,
+                                                                    u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u32 n = 1u << log_n;
+    const u64 out_len = ((u64)k << log_n) + 1;
+    const u64 a = t / out_len, c = t - a * out_len;
+    const W *ct = glwe + a * ((u64)(k + 1) << log_n);
+    if (c == out_len - 1) {
+        lwe[t] = ct[(u64)k << log_n] + ((W)1 << (half_shift + (u32)(a % levels) * log_basis));
+        return;
+    }
+    const u32 i = (u32)(c & (n - 1));
+    lwe[t] = i == 0 ? ct[c] : (W)0 - ct[c - i + (n - i)];
+}
+
+// ---------------- launches (arguments already checked) ----------------
+
+inline u32 pfks_group_words(u32 ell) { return std::max<u32>(1, std::min<u32>(kPfMaxRows / ell, kThreads / kPfTileM)); }
+
+template <class W>
+int launch_pfks(const W *lwe_in, const W *pfksk, W *out, PfksShape sh, u64 rows, hipStream_t s) {
+    const u32 gx = (((sh.k + 1) << sh.log_n) + kPfTileN - 1) / kPfTileN;
+    return launch_y_slices((rows + kPfTileM - 1) / kPfTileM, [&](u64 first_tile, u32 tiles) {
+        return launch_grid(tfhe_pfks_kernel<W>, dim3(gx, tiles, sh.k + 1), 0, s, lwe_in, pfksk, out, sh, first_tile * kPfTileM,
+                           rows);
+    });
+}
+
+inline int glwe_body_add(const pfhe_fft *f, size_t k, u64 *glwe, size_t len, const u64 *key, size_t len_key, hipStream_t s) {
+    return pfhe_tfhe_glwe_body_mac_dev(f, k, (uint64_t *)glwe, len, (const uint64_t *)key, len_key, 0, s);
+}
+inline int glwe_body_add(const pfhe_fft *f, size_t k, u32 *glwe, size_t len, const u32 *key, size_t len_key, hipStream_t s) {
+    return pfhe_tfhe32_glwe_body_mac_dev(f, k, glwe, len, key, len_key, 0, s);
+}
+
+// ---------------- the stateless entry points ----------------
+
+constexpr const char *kPfksDimensions = "private key switch: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2";
+
+// ApproxSignedBasis::new's assert!s, the dimensions, then the table
+template <class W>
+int pfks_dimensions(const char *message, const pfhe_fft *f, size_t k, size_t in_dimension, uint32_t log_basis,
+                    size_t decompose_length, u32 &ell, u32 &drop) {
+    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
+    PFHE_TRY(require_glwe_dimension(k, message));
+    PFHE_TRY(require_lwe_dimension(in_dimension, message));
+    if (!f) return PFHE_ERR_BAD_ARGUMENT;
+    return PFHE_OK;
+}
+
+inline size_t pfksk_words(size_t k, size_t n, size_t in_dimension, size_t ell) {
+    return (k + 1) * (in_dimension + 1) * ell * (k + 1) * n;
+}
+
+template <class W>
+int pfks_check(const pfhe_fft *f, size_t k, size_t len_in, size_t in_dimension, size_t levels, size_t len_pfksk,
+               uint32_t log_basis, size_t decompose_length, size_t len_out, PfksShape &sh) {
+    u32 ell = 0, drop = 0;
+    PFHE_TRY(pfks_dimensions<W>(kPfksDimensions, f, k, in_dimension, log_basis, decompose_length, ell, drop));
+    if (levels == 0 || levels > kMaxLevels) {
+        set_last_error("private key switch: levels must be in 1..64");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    const size_t group = levels * (in_dimension + 1), ggsw = (k + 1) * levels * (k + 1) * f->n;
+    if (len_in % group != 0 || len_pfksk != pfksk_words(k, f->n, in_dimension, ell) || len_out != len_in / group * ggsw) {
+        set_last_error("private key switch: lwe_in must be batch*levels*(in_dimension+1) words, pfksk "
+                       "(k+1)*(in_dimension+1)*ell*(k+1)*N and out batch*(k+1)*levels*(k+1)*N");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    sh = PfksShape{(u32)in_dimension, (u32)k, f->log_n, (u32)levels, log_basis, ell, drop, pfks_group_words(ell)};
+    return PFHE_OK;
+}
+
+template <class W>
+int private_keyswitch(Form form, const pfhe_fft *f, size_t k, const W *lwe_in, size_t len_in, size_t in_dimension, size_t levels,
+                      const W *pfksk, size_t len_pfksk, uint32_t log_basis, size_t decompose_length, W *out, size_t len_out,
+                      hipStream_t s) {
+    PfksShape sh{};
+    PFHE_TRY(pfks_check<W>(f, k, len_in, in_dimension, levels, len_pfksk, log_basis, decompose_length, len_out, sh));
+    if (len_in == 0) return PFHE_OK;
+    const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(pfksk, len_pfksk * sizeof(W)),
+                             stage_out(out, len_out * sizeof(W))};
+    return stateless_call(f->device, form, bufs, "private key switch: the output must not overlap an input", s,
+                          [&](void *const *d, hipStream_t st) {
+                              return launch_pfks<W>((const W *)d[0], (const W *)d[1], (W *)d[2], sh, len_in / (in_dimension + 1),
+                                                    st);
+                          });
+}
+
+template <class W>
+int pfksk_generate_dev(const pfhe_fft *f, size_t k, const W *key_in, size_t in_dimension, const W *glwe_key, size_t len_glwe_key,
+                       uint32_t log_basis, size_t decompose_length, W *pfksk, size_t len, hipStream_t s) {
+    u32 ell = 0, drop = 0;
+    PFHE_TRY(pfks_dimensions<W>("private key-switch key: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2", f, k,
+                                in_dimension, log_basis, decompose_length, ell, drop));
+    if (len_glwe_key != k * f->n || len != pfksk_words(k, f->n, in_dimension, ell)) {
+        set_last_error("private key-switch key: glwe_key must be k*N words and pfksk (k+1)*(in_dimension+1)*ell*(k+1)*N");
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    const StageBuf bufs[] = {stage_in(key_in, in_dimension * sizeof(W)), stage_in(glwe_key, len_glwe_key * sizeof(W)),
+                             stage_inout(pfksk, len * sizeof(W))};
+    const u64 pairs = ((u64)in_dimension + 1) * ell;
+    return stateless_call(
+        f->device, Form::kDevice, bufs, "private key-switch key: the keys must not overlap pfksk", s,
+        [&](void *const *d, hipStream_t st) {
+            PFHE_TRY(glwe_body_add(f, k, (W *)d[2], len, (const W *)d[1], len_glwe_key, st));
+            return launch_flat(tfhe_pfksk_add_message_kernel<W>, pairs * (k * f->n + 1), st, (W *)d[2], (const W *)d[0],
+                               (const W *)d[1], (u32)k, f->log_n, (u32)in_dimension, ell, log_basis, drop);
+        },
+        [&] { return pairs * (k + 1) > 0x7fffffffull ? PFHE_ERR_BAD_LENGTH : PFHE_OK; });
+}
+
+}  // namespace
+}  // namespace pfhe
+
+// ---------------- the circuit bootstrap handle ----------------
+
+// Owns a blind rotation (the classic one, behind TfheRotation) and, for `chunk` inputs, chunk * ell_cb accumulators, their
+// switched exponents, neg_b and the extracted LWE ciphertexts: all allocated at creation.
+template <class W>
+struct TfheCbsCore {
+    TfheRotation<W> *rotation = nullptr;  // owned
+    PlanGuard guard;                      // one holder at a time, successive calls on different streams ordered
+    const pfhe_fft *fft = nullptr;
+    u32 k = 1, n = 0;                      // GLWE and LWE dimensions
+    u32 cb_log_basis = 0, cb_ell = 0, cb_drop = 0;
+    PfksShape pf{};
+    size_t chunk = 1, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
+    W *acc = nullptr, *extracted = nullptr;
+    u32 *exps = nullptr, *neg_b = nullptr;
+    ~TfheCbsCore() {
+        if (!rotation) return;
+        {
+            DeviceGuard g(fft->device);
+            for (void *b : {(void *)acc, (void *)extracted, (void *)exps, (void *)neg_b})
+                if (b) (void)counted_free(b);
+        }
+        delete rotation;
+    }
+};
+struct pfhe_tfhe_cbs_handle : TfheCbsCore<u64> {};
+struct pfhe_tfhe32_cbs_handle : TfheCbsCore<u32> {};
+
+namespace {
+
+constexpr const char *kCbsBusy = "TFHE circuit bootstrap handle in use by another thread (one handle per thread)";
+constexpr const char *kCbsLengths =
+    "TFHE circuit bootstrap: lwe_in must be batch*(n+1) words, bsk n*(k+1)*ell*(k+1)*N complex values, pfksk "
+    "(k+1)*(k*N+1)*pfks_ell*(k+1)*N words and ggsw_out batch*(k+1)*cbs_ell*(k+1)*N";
+constexpr size_t kCbsDefaultAccBytes = 256ull << 20;
+
+// Everything that decides before the device first: the rotation's own checks in its order, then what is the circuit
+// bootstrap's own (the dimensions, the two bases' assert!s, drop_bits of the output basis); then the rotation's create
+template <class W, class H>
+int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t lwe_dimension,
+               uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis, size_t pfks_decompose_length,
+               size_t chunk, H **out) {
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    Shape rot_shape{};
+    PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, rot_shape));
+    // a zero glwe_dimension is refused as a zero lwe_dimension is: one message for both
+    PFHE_TRY(require_lwe_dimension(glwe_dimension ? lwe_dimension : 0,
+                                   "TFHE circuit bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2"));
+    auto h = std::make_unique<H>();
+    PFHE_TRY(basis_shape(8 * sizeof(W), cbs_log_basis, cbs_decompose_length, h->cb_ell, h->cb_drop));
+    u32 pf_ell = 0, pf_drop = 0;
+    PFHE_TRY(basis_shape(8 * sizeof(W), pfks_log_basis, pfks_decompose_length, pf_ell, pf_drop));
+    if (h->cb_drop == 0) {
+        set_last_error("TFHE circuit bootstrap: the output basis must drop at least one bit (g_l / 2 must be a word)");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    // chunk inputs are chunk * ell_cb accumulators of the rotation; 0 stays the rotation's default
+    if (chunk > 0x7fffffffull / h->cb_ell) return PFHE_ERR_BAD_LENGTH;
+    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, std::nullopt, chunk * h->cb_ell,
+                                     &h->rotation));
+    const TfheRotation<W> &rot = *h->rotation;
+    h->fft = fft;
+    h->k = (u32)glwe_dimension;
+    h->n = (u32)lwe_dimension;
+    h->cb_log_basis = cbs_log_basis;
+    const size_t glwe = rot.glwe, ext = glwe_dimension * fft->n + 1, levels = h->cb_ell;
+    h->pf = PfksShape{(u32)(ext - 1), h->k, fft->log_n, h->cb_ell, pfks_log_basis, pf_ell, pf_drop, pfks_group_words(pf_ell)};
+    h->bsk_len = lwe_dimension * rot.key_len;
+    // chunk 0: what the rotation's default holds, capped at about 256 MiB of accumulators
+    h->chunk = chunk ? chunk
+                     : std::max<size_t>(1, std::min(rot.chunk, kCbsDefaultAccBytes / (glwe * sizeof(W))) / levels);
+    DeviceGuard g(fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    const size_t accs = h->chunk * levels;
+    const size_t sizes[] = {accs * glwe * sizeof(W), accs * ext * sizeof(W), accs * lwe_dimension * sizeof(u32),
+                            h->chunk * sizeof(u32)};
+    void **bufs[] = {(void **)&h->acc, (void **)&h->extracted, (void **)&h->exps, (void **)&h->neg_b};
+    for (int i = 0; i < 4; ++i) {
+        PFHE_HIP(counted_malloc(bufs[i], sizes[i]));
+        h->bytes += sizes[i];
+    }
+    PFHE_TRY(h->guard.init(fft->device));
+    *out = h.release();
+    return PFHE_OK;
+}
+
+template <class W, class H>
+int cbs_check(const H *h, size_t len_in, size_t len_bsk, size_t len_pfksk, size_t len_out, u64 &batch) {
+    const size_t n = h->fft->n, k = h->k, in_words = (size_t)h->n + 1;
+    batch = len_in / in_words;
+    if (len_in % in_words != 0 || len_bsk != h->bsk_len || len_pfksk != pfksk_words(k, n, k * n, h->pf.ell) ||
+        len_out != batch * (k + 1) * h->cb_ell * (k + 1) * n) {
+        set_last_error(kCbsLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    return PFHE_OK;
+}
+
+template <class W, class H>
+int cbs_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *pfksk, size_t len_pfksk,
+            W *ggsw_out, size_t len_out, hipStream_t s) {
+    if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kCbsBusy);
+    u64 batch = 0;
+    PFHE_TRY((cbs_check<W>(h, len_in, len_bsk, len_pfksk, len_out, batch)));
+    if (batch == 0) return PFHE_OK;
+    if (!lwe_in || !bsk || !pfksk || !ggsw_out) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(bsk);
+    const size_t out_bytes = len_out * sizeof(W);
+    if (overlaps(lwe_in, len_in * sizeof(W), ggsw_out, out_bytes) || overlaps(bsk, len_bsk * 2 * sizeof(double), ggsw_out, out_bytes) ||
+        overlaps(pfksk, len_pfksk * sizeof(W), ggsw_out, out_bytes)) {
+        set_last_error("TFHE circuit bootstrap: the output must not overlap an input");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    const pfhe_fft &f = *h->fft;
+    DeviceGuard g(f.device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    const size_t glwe = h->rotation->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
+    const u32 levels = h->cb_ell, half_shift = h->cb_drop - 1;
+    const size_t ggsw = (size_t)(h->k + 1) * levels * glwe;
+    return ordered_on(h->guard, s, [&]() -> int {
+        // chunk after chunk; every stage of a chunk is queued before the next chunk starts
+        for (u64 done = 0; done < batch; done += h->chunk) {
+            const u64 cur = std::min<u64>(h->chunk, batch - done), accs = cur * levels;
+            PFHE_TRY(launch_flat(tfhe_cbs_modswitch_kernel<W>, cur * in_words, s, lwe_in + done * in_words, h->exps, h->neg_b,
+                                 h->n, f.log_n, levels));
+            PFHE_TRY(launch_flat(tfhe_cbs_acc_init_kernel<W>, accs * glwe, s, h->acc, (const u32 *)h->neg_b, h->k, f.log_n, levels,
+                                 h->cb_log_basis, half_shift));
+            PFHE_TRY(h->rotation->rotate_dev(h->acc, accs * glwe, bsk, len_bsk, h->exps, accs * h->n, s));
+            PFHE_TRY(launch_flat(tfhe_cbs_extract_kernel<W>, accs * ext, s, (const W *)h->acc, h->extracted, h->k, f.log_n, levels,
+                                 h->cb_log_basis, half_shift));
+            PFHE_TRY(launch_pfks<W>(h->extracted, pfksk, ggsw_out + done * ggsw, h->pf, accs, s));
+        }
+        return PFHE_OK;
+    });
+}
+
+// host form
+template <class W, class H>
+int cbs_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *pfksk, size_t len_pfksk,
+             W *ggsw_out, size_t len_out) {
+    if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kCbsBusy);
+    u64 batch = 0;
+    PFHE_TRY((cbs_check<W>(h, len_in, len_bsk, len_pfksk, len_out, batch)));
+    if (batch == 0) return PFHE_OK;
+    if (!lwe_in || !bsk || !pfksk || !ggsw_out) return PFHE_ERR_BAD_ARGUMENT;
+    const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
+                             stage_in(pfksk, len_pfksk * sizeof(W)), stage_out(ggsw_out, len_out * sizeof(W))};
+    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
+        return cbs_dev<W>(h, (const W *)d[0], len_in, (const double *)d[1], len_bsk, (const W *)d[2], len_pfksk, (W *)d[3],
+                          len_out, s);
+    });
+}
+
+template <class H>
+size_t cbs_scratch(const H *h) {
+    return h && h->rotation ? h->rotation->scratch_bytes() + h->bytes : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfhe_tfhe_private_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in_dev, size_t len_in,
+                                    size_t in_dimension, size_t levels, const uint64_t *pfksk_dev, size_t len_pfksk,
+                                    uint32_t log_basis, size_t decompose_length, uint64_t *out_dev, size_t len_out,
+                                    void *stream) {
+    PFHE_GUARD_BEGIN
+    return private_keyswitch<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)lwe_in_dev, len_in, in_dimension, levels,
+                                  (const u64 *)pfksk_dev, len_pfksk, log_basis, decompose_length, (u64 *)out_dev, len_out,
+                                  (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_private_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
+                                size_t in_dimension, size_t levels, const uint64_t *pfksk, size_t len_pfksk, uint32_t log_basis,
+                                size_t decompose_length, uint64_t *out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return private_keyswitch<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)lwe_in, len_in, in_dimension, levels,
+                                  (const u64 *)pfksk, len_pfksk, log_basis, decompose_length, (u64 *)out, len_out, nullptr);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_private_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in_dev, size_t len_in,
+                                      size_t in_dimension, size_t levels, const uint32_t *pfksk_dev, size_t len_pfksk,
+                                      uint32_t log_basis, size_t decompose_length, uint32_t *out_dev, size_t len_out,
+                                      void *stream) {
+    PFHE_GUARD_BEGIN
+    return private_keyswitch<u32>(Form::kDevice, fft, glwe_dimension, lwe_in_dev, len_in, in_dimension, levels, pfksk_dev,
+                                  len_pfksk, log_basis, decompose_length, out_dev, len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_private_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
+                                  size_t in_dimension, size_t levels, const uint32_t *pfksk, size_t len_pfksk,
+                                  uint32_t log_basis, size_t decompose_length, uint32_t *out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return private_keyswitch<u32>(Form::kHost, fft, glwe_dimension, lwe_in, len_in, in_dimension, levels, pfksk, len_pfksk,
+                                  log_basis, decompose_length, out, len_out, nullptr);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe_pfksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *key_in_dev, size_t in_dimension,
+                                 const uint64_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis, size_t decompose_length,
+                                 uint64_t *pfksk_dev, size_t len_pfksk, void *stream) {
+    PFHE_GUARD_BEGIN
+    return pfksk_generate_dev<u64>(fft, glwe_dimension, (const u64 *)key_in_dev, in_dimension, (const u64 *)glwe_key_dev,
+                                   len_glwe_key, log_basis, decompose_length, (u64 *)pfksk_dev, len_pfksk, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_pfksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *key_in_dev, size_t in_dimension,
+                                   const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
+                                   size_t decompose_length, uint32_t *pfksk_dev, size_t len_pfksk, void *stream) {
+    PFHE_GUARD_BEGIN
+    return pfksk_generate_dev<u32>(fft, glwe_dimension, key_in_dev, in_dimension, glwe_key_dev, len_glwe_key, log_basis,
+                                   decompose_length, pfksk_dev, len_pfksk, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+                         size_t pfks_decompose_length, size_t chunk, pfhe_tfhe_cbs_handle **out) {
+    PFHE_GUARD_BEGIN
+    return cbs_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
+                           pfks_log_basis, pfks_decompose_length, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe_cbs_destroy(pfhe_tfhe_cbs_handle *h) { delete h; }
+int pfhe_tfhe_cbs_in_use(const pfhe_tfhe_cbs_handle *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h) { return cbs_scratch(h); }
+int pfhe_tfhe_cbs_dev(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk,
+                      const uint64_t *pfksk_dev, size_t len_pfksk, uint64_t *ggsw_out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return cbs_dev<u64>(h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)pfksk_dev, len_pfksk,
+                        (u64 *)ggsw_out_dev, len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_cbs(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                  const uint64_t *pfksk, size_t len_pfksk, uint64_t *ggsw_out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return cbs_host<u64>(h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)pfksk, len_pfksk, (u64 *)ggsw_out, len_out);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe32_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                           size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+                           size_t pfks_decompose_length, size_t chunk, pfhe_tfhe32_cbs_handle **out) {
+    PFHE_GUARD_BEGIN
+    return cbs_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
+                           pfks_log_basis, pfks_decompose_length, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe32_cbs_destroy(pfhe_tfhe32_cbs_handle *h) { delete h; }
+int pfhe_tfhe32_cbs_in_use(const pfhe_tfhe32_cbs_handle *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe32_cbs_scratch_bytes(const pfhe_tfhe32_cbs_handle *h) { return cbs_scratch(h); }
+int pfhe_tfhe32_cbs_dev(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                        size_t len_bsk, const uint32_t *pfksk_dev, size_t len_pfksk, uint32_t *ggsw_out_dev, size_t len_out,
+                        void *stream) {
+    PFHE_GUARD_BEGIN
+    return cbs_dev<u32>(h, lwe_in_dev, len_in, bsk_dev, len_bsk, pfksk_dev, len_pfksk, ggsw_out_dev, len_out,
+                        (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_cbs(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                    const uint32_t *pfksk, size_t len_pfksk, uint32_t *ggsw_out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return cbs_host<u32>(h, lwe_in, len_in, bsk, len_bsk, pfksk, len_pfksk, ggsw_out, len_out);
+    PFHE_GUARD_END
+}
+
+}  // extern "C"

@@ -713,6 +713,106 @@ def multimsg_lwe_extract_dev(multi, lwe_out, fft: FullComplex64FftTable, count: 
     _extract_pair("_multimsg_extract", multi, lwe_out, fft, count, glwe_dimension, True, stream)
 
 
+# ---- the circuit bootstrap: an encrypted bit becomes a GGSW (include/pfhe.h: private_keyswitch, pfksk_generate, cbs) ----
+
+def _private_keyswitch(dev, lwe_in, pfksk, out, in_dimension, levels, fft, basis, glwe_dimension, stream=None) -> None:
+    _stateless("_private_keyswitch", dev, (lwe_in, pfksk, out), "lwe_in, pfksk and out must have the same word width",
+               lambda w, i, k, o: (fft._h, glwe_dimension, *i, in_dimension, levels, *k, *_basis_args(basis, w), *o), stream)
+
+
+def lwe_private_keyswitch(lwe_in: np.ndarray, pfksk: np.ndarray, out: np.ndarray, in_dimension: int, levels: int,
+                          fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1) -> None:
+    """Private functional key switch on host arrays: batch x levels LWE ciphertexts (in_dimension+1 words, ciphertext (e, l)
+    at e*levels + l) become batch GGSW-shaped blocks of (k+1) x levels x (k+1)*N words,
+    out[e][u][l] = - sum_{j <= in_dimension} sum_t d_t(c_{e,l,j}) * pfksk[u][j][t] modulo 2^BITS, c = (a, b) with the body
+    decomposed as one more mask word and d the signed digits of `basis`; pfksk is (k+1) x (in_dimension+1) x ell GLWE rows,
+    row (u, j, t) an encryption of f_u(s'_j * 2^(drop_bits + t*log_basis)), s' = (s_in, -1), f_u(x) = -z_u*x for u < k and
+    x on coefficient 0 for u = k: the phase of out[e][u][l] is f_u of the phase of input (e, l).  1 <= levels <= 64."""
+    _private_keyswitch(False, lwe_in, pfksk, out, in_dimension, levels, fft, basis, glwe_dimension)
+
+
+def lwe_private_keyswitch_dev(lwe_in, pfksk, out, in_dimension: int, levels: int, fft: FullComplex64FftTable,
+                              basis: ApproxSignedBasis, glwe_dimension: int = 1, stream=None) -> None:
+    """the device form, asynchronous and stateless; out must not overlap an input and may be uninitialised"""
+    _private_keyswitch(True, lwe_in, pfksk, out, in_dimension, levels, fft, basis, glwe_dimension, stream)
+
+
+def tfhe_generate_pfksk_dev(key_in, glwe_key, fft: FullComplex64FftTable, basis: ApproxSignedBasis, rand,
+                            glwe_dimension: int = 1, stream=None) -> None:
+    """The key lwe_private_keyswitch_dev takes, from key_in (len(key_in) words) to glwe_key (the k key polynomials end to
+    end), generated in place in rand: (k+1) x (len(key_in)+1) x ell GLWE rows of (k+1)*N words holding the randomness (mask
+    polynomials uniform, body polynomials noise).  Every row becomes B += sum_r A_r * z_r; then, with s' = (key_in, -1) and
+    g_t = 2^(drop_bits + t*log_basis), row (k, j, t) gets s'_j*g_t on coefficient 0 of the body and row (u, j, t), u < k,
+    gets -s'_j*g_t*z_u[i] on every body coefficient i.  A second call adds both a second time.  Asynchronous."""
+    pi, ni, wi = _dev_words(key_in)
+    pz, nz, wz = _dev_words(glwe_key)
+    pr, nr, wr = _dev_words(rand)
+    _same_width("both keys and the randomness must have the same word width", wi, wz, wr)
+    lb, ell = _basis_args(basis, wr)
+    check(getattr(lib(), "pfhe_tfhe" + wr + "_pfksk_generate_dev")(fft._h, glwe_dimension, pi, ni, pz, nz, lb, ell, pr, nr,
+                                                                 _stream(stream)))
+
+
+class TfheCircuitBootstrapContext(_TorusContext):
+    """Handle of the batched circuit bootstrap (include/pfhe.h, pfhe_tfhe{,32}_cbs_*): an LWE ciphertext of a bit m encoded
+    as m*2^(BITS-1) becomes a torus-form GGSW of m under the GLWE key, in `cbs_basis`.  Per input and level l of cbs_basis:
+    the modulus switch of (a, b + 2^(BITS-2)), ACC = X^{-b~} * (0, .., 0, -g_l/2 on every coefficient), the blind rotation
+    over lwe_dimension steps under `basis`, sample extraction at index 0 with g_l/2 added to the body, and the private
+    functional key switch under `pfks_basis` with levels = cbs_basis.decompose_length().  cbs_basis must drop at least
+    one bit.  Owns a blind-rotation handle and every buffer between the stages for `chunk` inputs (0 = the default); one
+    holder at a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int,
+                 cbs_basis: ApproxSignedBasis, pfks_basis: ApproxSignedBasis, chunk: int = 0):
+        if cbs_basis.bits != basis.bits or pfks_basis.bits != basis.bits:
+            raise TypeError("every basis must have the width of the torus words")
+        args = (lwe_dimension, cbs_basis.log_basis(), cbs_basis.decompose_length(), pfks_basis.log_basis(),
+                pfks_basis.decompose_length(), chunk)
+        self._open(fft, basis, glwe_dimension, "cbs", args, ("_create", "_destroy", "_in_use", "_scratch_bytes"))
+        self.lwe_dimension, self.cbs_basis, self.pfks_basis = lwe_dimension, cbs_basis, pfks_basis
+
+    def bsk_len(self) -> int:
+        """complex values of the bootstrapping key: lwe_dimension Fourier GGSW keys"""
+        return self.lwe_dimension * self.key_len()
+
+    def extracted_dimension(self) -> int:
+        return self.glwe_dimension * self.fft.poly_length()
+
+    def pfksk_len(self) -> int:
+        """words of the private key-switch key"""
+        return (self.glwe_dimension + 1) * (self.extracted_dimension() + 1) * self.pfks_basis.decompose_length() \
+            * self.glwe_len()
+
+    def ggsw_len(self) -> int:
+        """words of one output GGSW: (k+1) x ell_cb x (k+1) x N"""
+        return (self.glwe_dimension + 1) * self.cbs_basis.decompose_length() * self.glwe_len()
+
+
+def tfhe_circuit_bootstrap(lwe_in: np.ndarray, bsk: np.ndarray, pfksk: np.ndarray, ggsw_out: np.ndarray,
+                           ctx: TfheCircuitBootstrapContext) -> None:
+    """Batched circuit bootstrap on host arrays.  lwe_in: batch x (n+1) words; bsk: n Fourier GGSW keys end to end; pfksk:
+    ctx.pfksk_len() words as tfhe_generate_pfksk_dev writes them for key_in = the GLWE key polynomials end to end;
+    ggsw_out: batch x ctx.ggsw_len() words."""
+    pi, ni, wi = _host_words(lwe_in)
+    pk, nk = _host_fourier(bsk)
+    pp, np_, wp = _host_words(pfksk)
+    po, no, wo = _host_words(ggsw_out)
+    _same_width("every word array must have the width of the context's basis", wi, wp, wo, ctx._w)
+    check(getattr(lib(), ctx._pre)(ctx._h, pi, ni, pk, nk, pp, np_, po, no))
+
+
+def tfhe_circuit_bootstrap_dev(lwe_in, bsk, pfksk, ggsw_out, ctx: TfheCircuitBootstrapContext, stream=None) -> None:
+    """the device form (32- or 64-bit integer CUDA tensors of the context's width, bsk complex128 or float64),
+    asynchronous; ggsw_out must not overlap an input and may be uninitialised.  write_fourier_form of ggsw_out is what
+    tfhe_external_product_to_dev takes with a TfheFftContext on cbs_basis."""
+    pi, ni, wi = _dev_words(lwe_in)
+    pk, nk = _dev_fourier(bsk)
+    pp, np_, wp = _dev_words(pfksk)
+    po, no, wo = _dev_words(ggsw_out)
+    _same_width("every word tensor must have the width of the context's basis", wi, wp, wo, ctx._w)
+    check(getattr(lib(), ctx._pre + "_dev")(ctx._h, pi, ni, pk, nk, pp, np_, po, no, _stream(stream)))
+
+
 def _torus_dtype(bits: int):
     import torch
     if bits not in (32, 64):
