@@ -1450,6 +1450,71 @@ int pfhe_tfhe32_cbs_dev(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in_dev, s
 int pfhe_tfhe32_cbs(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
                     const uint32_t *pfksk, size_t len_pfksk, uint32_t *ggsw_out, size_t len_out);
 
+/* ---- the batched CMUX with a selector per group, and the CMUX tree (u64: no suffix, u32: 32) ----
+ * No reference counterpart; the rules are this project's own, built on the arithmetic of
+ * pfhe_tfhe*_external_product_to_dev, which they leave bit for bit what it is.  A selector is a Fourier GGSW key in the
+ * layout that call takes: (k+1)*ell*(k+1)*N complex values, e.g. pfhe_fft_forward_torus*_dev of a GGSW that
+ * pfhe_tfhe*_cbs_dev wrote, under a handle on that output basis.
+ *
+ * Rule 1, the CMUX.  d0, d1, out: count GLWE ciphertexts of (k+1)*N words; keys: count / per_key keys end to end;
+ * per_key >= 1 and count % per_key == 0.  Modulo 2^BITS:
+ *   out[i] = d0[i] + external_product_to(d1[i] - d0[i], keys[i / per_key]),
+ * so a key of the bit m selects d_m.  The words equal, one for one, those of a wrapping subtraction,
+ * pfhe_tfhe*_external_product_to_dev on each group of per_key differences with the group's key, and a wrapping addition.
+ * Nothing is atomic: the words depend neither on the batch, nor on the chunk, nor on how per_key tiles the launches.  out
+ * may be exactly d0 or exactly d1; any other overlap of out with an input is refused in the device form.
+ *
+ * Rule 2, the tree of depth d.  table: 2^d GLWE ciphertexts shared by the batch, or batch*2^d of them, input-major (which
+ * one follows from len_table; any other length is refused); selectors: batch x d keys, the key of input e and bit j at
+ * index e*d + j (the order in which pfhe_tfhe*_cbs_dev on LWE inputs ordered e*d + j, then the forward transform, gives
+ * them); out: batch ciphertexts.  Level j = 0..d-1 halves the nodes, bit 0 the least significant bit of the leaf index:
+ *   node_{j+1}[e][i] = node_j[e][2i] + external_product_to(node_j[e][2i+1] - node_j[e][2i], selectors[e*d + j]),
+ *   node_0[e] = table (shared or input e's),  out[e] = node_d[e][0],
+ * so out[e] is leaf sum_j m_{e,j} 2^j.  The tree equals, word for word, d calls of rule 1 with per_key = 2^(d-1-j) and a key
+ * stride of d.
+ *
+ * create, everything before the device first: the product plan's checks in their order (ApproxSignedBasis::new's assert!s,
+ * PFHE_ERR_UNSUPPORTED for glwe_dimension above 64, PFHE_ERR_BAD_ARGUMENT for a null table), then PFHE_ERR_BAD_ARGUMENT for
+ * a depth outside 1..16.  The handle borrows `fft` and allocates everything here, for `chunk` inputs: two node buffers of
+ * chunk*2^(d-1) and chunk*2^(d-2) ciphertexts (the last level writes into out; depth 1 needs none) and, off the fused shape
+ * (k = 1, N <= 2^11), a product plan with its scratch and two buffers of chunk*2^(d-1) ciphertexts.  chunk 0: inputs such
+ * that these stay near 256 MiB, at least 1.  A call only queues work on `stream` (no allocation, no host
+ * synchronisation), so it can be captured into a HIP graph; a batch larger than the chunk runs chunk by chunk, all levels
+ * of a chunk first; rule 1 runs at most chunk*2^(d-1) ciphertexts per launch.  One holder at a time (PFHE_ERR_BUSY).  A
+ * call refuses, in the order of pfhe_tfhe*_external_product_to_dev: a null handle, a second holder, PFHE_ERR_BAD_LENGTH
+ * for any length that does not fit the others (per_key 0 included), (the empty batch is a no-op,) null pointers, a pointer
+ * not aligned to 16 bytes, an overlap (device form), the device. */
+typedef struct pfhe_tfhe_cmux_tree_handle pfhe_tfhe_cmux_tree_handle;
+typedef struct pfhe_tfhe32_cmux_tree_handle pfhe_tfhe32_cmux_tree_handle;
+int pfhe_tfhe_cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                               size_t depth, size_t chunk, pfhe_tfhe_cmux_tree_handle **out);
+void pfhe_tfhe_cmux_tree_destroy(pfhe_tfhe_cmux_tree_handle *h);
+int pfhe_tfhe_cmux_tree_in_use(const pfhe_tfhe_cmux_tree_handle *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_cmux_tree_scratch_bytes(const pfhe_tfhe_cmux_tree_handle *h);  /* the owned plan's scratch included */
+int pfhe_tfhe_cmux_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0_dev, size_t len_d0, const uint64_t *d1_dev, size_t len_d1,
+                       const double *keys_dev, size_t len_keys, size_t per_key, uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_cmux(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0, size_t len_d0, const uint64_t *d1, size_t len_d1,
+                   const double *keys, size_t len_keys, size_t per_key, uint64_t *out, size_t len_out);
+int pfhe_tfhe_cmux_tree_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table_dev, size_t len_table,
+                            const double *selectors_dev, size_t len_selectors, uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_cmux_tree(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table, size_t len_table, const double *selectors,
+                        size_t len_selectors, uint64_t *out, size_t len_out);
+int pfhe_tfhe32_cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                 size_t depth, size_t chunk, pfhe_tfhe32_cmux_tree_handle **out);
+void pfhe_tfhe32_cmux_tree_destroy(pfhe_tfhe32_cmux_tree_handle *h);
+int pfhe_tfhe32_cmux_tree_in_use(const pfhe_tfhe32_cmux_tree_handle *h);
+size_t pfhe_tfhe32_cmux_tree_scratch_bytes(const pfhe_tfhe32_cmux_tree_handle *h);
+int pfhe_tfhe32_cmux_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0_dev, size_t len_d0, const uint32_t *d1_dev,
+                         size_t len_d1, const double *keys_dev, size_t len_keys, size_t per_key, uint32_t *out_dev,
+                         size_t len_out, void *stream);
+int pfhe_tfhe32_cmux(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0, size_t len_d0, const uint32_t *d1, size_t len_d1,
+                     const double *keys, size_t len_keys, size_t per_key, uint32_t *out, size_t len_out);
+int pfhe_tfhe32_cmux_tree_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table_dev, size_t len_table,
+                              const double *selectors_dev, size_t len_selectors, uint32_t *out_dev, size_t len_out,
+                              void *stream);
+int pfhe_tfhe32_cmux_tree(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
+                          size_t len_selectors, uint32_t *out, size_t len_out);
+
 #ifdef __cplusplus
 }
 #endif

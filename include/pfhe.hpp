@@ -1258,4 +1258,74 @@ class TfheCircuitBootstrap32 {
     pfhe_tfhe32_cbs_handle *h_ = nullptr;
 };
 
+// The batched CMUX with a Fourier GGSW selector per group of per_key ciphertexts (out[i] = d0[i] +
+// external_product_to(d1[i] - d0[i], keys[i / per_key]); out may be d0 or d1) and the tree that selects one of 2^depth GLWE
+// ciphertexts by depth selectors per input (pfhe_tfhe{,32}_cmux_tree_*, _cmux, _cmux_dev).  Owns the node buffers of `chunk`
+// inputs and, off the fused shape, a product plan; one holder at a time.  TfheCmuxTree32: the u32 torus.
+class TfheCmuxTree {
+  public:
+    TfheCmuxTree(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                 size_t depth, size_t chunk = 0) {
+        check(pfhe_tfhe_cmux_tree_create(fft.handle(), glwe_dimension, log_basis, decompose_length, depth, chunk, &h_));
+    }
+    ~TfheCmuxTree() { pfhe_tfhe_cmux_tree_destroy(h_); }
+    TfheCmuxTree(const TfheCmuxTree &) = delete;
+    TfheCmuxTree &operator=(const TfheCmuxTree &) = delete;
+    pfhe_tfhe_cmux_tree_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_cmux_tree_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_cmux_tree_scratch_bytes(h_); }
+    void cmux(const uint64_t *d0, size_t len_d0, const uint64_t *d1, size_t len_d1, const double *keys, size_t len_keys,
+              size_t per_key, uint64_t *out, size_t len_out) {
+        check(pfhe_tfhe_cmux(h_, d0, len_d0, d1, len_d1, keys, len_keys, per_key, out, len_out));
+    }
+    void cmux_dev(const uint64_t *d0_dev, size_t len_d0, const uint64_t *d1_dev, size_t len_d1, const double *keys_dev,
+                  size_t len_keys, size_t per_key, uint64_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe_cmux_dev(h_, d0_dev, len_d0, d1_dev, len_d1, keys_dev, len_keys, per_key, out_dev, len_out, stream));
+    }
+    void cmux_tree(const uint64_t *table, size_t len_table, const double *selectors, size_t len_selectors, uint64_t *out,
+                   size_t len_out) {
+        check(pfhe_tfhe_cmux_tree(h_, table, len_table, selectors, len_selectors, out, len_out));
+    }
+    void cmux_tree_dev(const uint64_t *table_dev, size_t len_table, const double *selectors_dev, size_t len_selectors,
+                       uint64_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe_cmux_tree_dev(h_, table_dev, len_table, selectors_dev, len_selectors, out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe_cmux_tree_handle *h_ = nullptr;
+};
+
+class TfheCmuxTree32 {
+  public:
+    TfheCmuxTree32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                   size_t depth, size_t chunk = 0) {
+        check(pfhe_tfhe32_cmux_tree_create(fft.handle(), glwe_dimension, log_basis, decompose_length, depth, chunk, &h_));
+    }
+    ~TfheCmuxTree32() { pfhe_tfhe32_cmux_tree_destroy(h_); }
+    TfheCmuxTree32(const TfheCmuxTree32 &) = delete;
+    TfheCmuxTree32 &operator=(const TfheCmuxTree32 &) = delete;
+    pfhe_tfhe32_cmux_tree_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_cmux_tree_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_cmux_tree_scratch_bytes(h_); }
+    void cmux(const uint32_t *d0, size_t len_d0, const uint32_t *d1, size_t len_d1, const double *keys, size_t len_keys,
+              size_t per_key, uint32_t *out, size_t len_out) {
+        check(pfhe_tfhe32_cmux(h_, d0, len_d0, d1, len_d1, keys, len_keys, per_key, out, len_out));
+    }
+    void cmux_dev(const uint32_t *d0_dev, size_t len_d0, const uint32_t *d1_dev, size_t len_d1, const double *keys_dev,
+                  size_t len_keys, size_t per_key, uint32_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe32_cmux_dev(h_, d0_dev, len_d0, d1_dev, len_d1, keys_dev, len_keys, per_key, out_dev, len_out, stream));
+    }
+    void cmux_tree(const uint32_t *table, size_t len_table, const double *selectors, size_t len_selectors, uint32_t *out,
+                   size_t len_out) {
+        check(pfhe_tfhe32_cmux_tree(h_, table, len_table, selectors, len_selectors, out, len_out));
+    }
+    void cmux_tree_dev(const uint32_t *table_dev, size_t len_table, const double *selectors_dev, size_t len_selectors,
+                       uint32_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe32_cmux_tree_dev(h_, table_dev, len_table, selectors_dev, len_selectors, out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe32_cmux_tree_handle *h_ = nullptr;
+};
+
 }  // namespace pfhe

@@ -24,7 +24,8 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    multimsg_lwe_extract, multimsg_lwe_extract_dev, TfhePackFftContext, tfhe_pack_key_fourier_dev,
                    lwe_pack_keyswitch_fft, lwe_pack_keyswitch_fft_dev, lwe_private_keyswitch, lwe_private_keyswitch_dev,
                    tfhe_generate_pfksk_dev, TfheCircuitBootstrapContext, tfhe_circuit_bootstrap,
-                   tfhe_circuit_bootstrap_dev)
+                   tfhe_circuit_bootstrap_dev, TfheCmuxTreeContext, tfhe_cmux, tfhe_cmux_dev, tfhe_cmux_tree,
+                   tfhe_cmux_tree_dev)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -45,4 +46,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "glwe_sample_extract_first_few_dev", "multimsg_lwe_extract", "multimsg_lwe_extract_dev",
            "TfhePackFftContext", "tfhe_pack_key_fourier_dev", "lwe_pack_keyswitch_fft", "lwe_pack_keyswitch_fft_dev",
            "lwe_private_keyswitch", "lwe_private_keyswitch_dev", "tfhe_generate_pfksk_dev", "TfheCircuitBootstrapContext",
-           "tfhe_circuit_bootstrap", "tfhe_circuit_bootstrap_dev", "build", "lib", "library_path", "status_string"]
+           "tfhe_circuit_bootstrap", "tfhe_circuit_bootstrap_dev", "TfheCmuxTreeContext", "tfhe_cmux", "tfhe_cmux_dev",
+           "tfhe_cmux_tree", "tfhe_cmux_tree_dev", "build", "lib", "library_path", "status_string"]

@@ -251,6 +251,16 @@ def _declare(lib: C.CDLL) -> None:
         sig(cb + "_scratch_bytes", sz, vp)
         sig(cb + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz, vp)
         sig(cb, ci, vp, vp, sz, f64p, sz, vp, sz, vp, sz)
+        # the CMUX with a selector per group and the CMUX tree, both calls of one handle
+        ct = tp + "cmux_tree"
+        sig(ct + "_create", ci, vp, sz, u32, sz, sz, sz, C.POINTER(vp))
+        sig(ct + "_destroy", None, vp)
+        sig(ct + "_in_use", ci, vp)
+        sig(ct + "_scratch_bytes", sz, vp)
+        sig(tp + "cmux_dev", ci, vp, vp, sz, vp, sz, f64p, sz, sz, vp, sz, vp)
+        sig(tp + "cmux", ci, vp, vp, sz, vp, sz, f64p, sz, sz, vp, sz)
+        sig(ct + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
+        sig(ct, ci, vp, vp, sz, f64p, sz, vp, sz)
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)

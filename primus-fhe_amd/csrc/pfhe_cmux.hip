@@ -1,0 +1,437 @@
+// pfhe_cmux.hip — the batched CMUX with a Fourier GGSW selector per group of ciphertexts, and the tree of CMUXes that
+// selects one of 2^d GLWE ciphertexts by d encrypted bits (include/pfhe.h: pfhe_tfhe{,32}_cmux_tree_*, _cmux, _cmux_dev).
+// No reference counterpart; DESIGN.md §20 states the rules.  Both are built on the arithmetic of external_product_to
+// (pfhe_fft.hip), which stays what it is.
+//
+//   rule 1, the CMUX     out[i] = d0[i] + external_product_to(d1[i] - d0[i], keys[i / per_key]) modulo 2^BITS
+//   rule 2, the tree     level j = 0..d-1 of input e: node_{j+1}[e][i] = CMUX(node_j[e][2i], node_j[e][2i+1]; selectors[e d + j]),
+//                        node_0[e] the table (one for the batch, or one per input), out[e] = node_d[e][0]: d calls of
+//                        rule 1 with per_key = 2^(d-1-j) and a key stride of d.
+//   fused   (k = 1, N <= 2^11): tfhe_cmux_kernel, one launch per level and chunk, a workgroup per node: the difference in
+//            registers, the product's own accumulate and inverse code against the node's key, d0 added in the sink;
+//   general (every other shape): one difference launch, the product's own launch sequence once per key group through the
+//            public product call on a plan the handle owns, one add launch.  batch * d product sequences per tree: the
+//            slow form.
+// Nothing is atomic and the summation order is the product's: the words depend neither on the batch, nor on the chunk,
+// nor on how per_key tiles the launches.  Launches and host forms go through pfhe_tfhe_host.hpp.
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+
+#include "pfhe_tfhe_handles.hpp"
+
+using namespace pfhe;
+
+namespace pfhe {
+namespace {
+
+// Where a launch finds its nodes.  Node b of the launch (blockIdx.x) reads d0 / d1 at index (b mod period) * stride words
+// (period 0: b itself; a period is the shared table of the tree's first level) and writes out at b * (k+1) N.  Its key is
+// keys + ((first_node + b) / per_key) * key_stride: first_node is the global index of the launch's first node, so a chunk
+// boundary inside a key group still picks the group's key.
+struct CmuxNodes {
+    u64 stride, first_node, per_key, key_stride;
+    u32 period;
+    __device__ __forceinline__ u64 source(u64 b) const { return (period ? b % period : b) * stride; }
+    __device__ __forceinline__ u64 key(u64 b) const { return ((first_node + b) / per_key) * key_stride; }
+};
+
+// one input row of D = d1 - d0, formed once and held in registers for all its levels
+template <class W>
+struct DiffRow {
+    W a[kFusedPer], b[kFusedPer];
+    __device__ __forceinline__ W lo(int u, u32) const { return a[u]; }
+    __device__ __forceinline__ W hi(int u, u32) const { return b[u]; }
+};
+
+// One workgroup per CMUX node (k = 1, N <= 2^11); the body is pfhe_fft_device.hpp's fused_accumulate_rows /
+// fused_inverse_rows, so the product inside is the fused product's arithmetic, operation for operation.  Every read of
+// d0 / d1 by the row source precedes a barrier of fused_accumulate_rows, every store of the sink follows the barrier that
+// ends it, and the sink reads d0 at the index it then writes, in the same thread: out may be exactly d0 or exactly d1.
+// (No __restrict__ on the three for that reason.)
+template <class W>
+__global__ __launch_bounds__(kThreads) void tfhe_cmux_kernel(const W *d0, const W *d1, const double2 *__restrict__ keys,
+                                                             W *out, const double2 *__restrict__ tw, Shape s, CmuxNodes nodes) {
+    extern __shared__ __attribute__((aligned(16))) double2 lds_c[];
+    const u32 n = 1u << s.log_n, m = n >> 1;
+    const u64 src = nodes.source(blockIdx.x);
+    const W *x0 = d0 + src, *x1 = d1 + src;
+    W *o = out + (u64)blockIdx.x * 2 * n;
+    double2 acc0[kFusedPer], acc1[kFusedPer];
+#pragma unroll
+    for (int u = 0; u < kFusedPer; ++u) acc0[u] = acc1[u] = make_double2(0.0, 0.0);
+    fused_accumulate_rows<W>([&](u32 row) {
+        DiffRow<W> d;
+#pragma unroll
+        for (int u = 0; u < kFusedPer; ++u) {
+            const u32 i = threadIdx.x + u * kThreads;
+            d.a[u] = i < m ? (W)(x1[row * n + i] - x0[row * n + i]) : (W)0;
+            d.b[u] = i < m ? (W)(x1[row * n + i + m] - x0[row * n + i + m]) : (W)0;
+        }
+        return d;
+    }, ClassicKey{keys + nodes.key(blockIdx.x)}, lds_c, tw, s, acc0, acc1);
+    fused_inverse_rows(acc0, acc1, lds_c, tw, s, [&](u32 c, u32 i, double lo, double hi) {
+        o[c * n + i] = x0[c * n + i] + to_torus<W>(lo);
+        o[c * n + i + m] = x0[c * n + i + m] + to_torus<W>(hi);
+    });
+}
+
+// The element-wise ends of the general form, one thread per word of `glwe` words per node: ADD false, out = d1 - d0 (the
+// handle's D buffer); ADD true, out = d0 + e (d1 is then the handle's E buffer, read at the node's own index).  A thread
+// reads and writes one index, so the add may store over d0 or d1.
+template <class W, bool ADD>
+__global__ __launch_bounds__(kThreads) void tfhe_cmux_glue_kernel(const W *d0, const W *d1, W *out, u64 glwe, CmuxNodes nodes,
+                                                                  u64 total) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const u64 b = t / glwe, j = t - b * glwe;
+    const W a = d0[nodes.source(b) + j];
+    out[t] = ADD ? (W)(a + d1[t]) : (W)(d1[nodes.source(b) + j] - a);
+}
+
+}  // namespace
+}  // namespace pfhe
+
+// ---------------- the handle ----------------
+
+template <class W>
+struct CmuxProductCalls;
+template <>
+struct CmuxProductCalls<u64> {
+    using Plan = pfhe_tfhe_plan;
+    static int create(const pfhe_fft *f, size_t k, uint32_t lb, size_t ell, size_t chunk, Plan **out) {
+        return pfhe_tfhe_plan_create(f, k, lb, ell, chunk, out);
+    }
+    static int product(Plan *p, const u64 *in, size_t len, const double *key, size_t len_key, u64 *out, hipStream_t s) {
+        return pfhe_tfhe_external_product_to_dev(p, (const uint64_t *)in, len, key, len_key, (uint64_t *)out, len, s);
+    }
+};
+template <>
+struct CmuxProductCalls<u32> {
+    using Plan = pfhe_tfhe32_plan;
+    static int create(const pfhe_fft *f, size_t k, uint32_t lb, size_t ell, size_t chunk, Plan **out) {
+        return pfhe_tfhe32_plan_create(f, k, lb, ell, chunk, out);
+    }
+    static int product(Plan *p, const u32 *in, size_t len, const double *key, size_t len_key, u32 *out, hipStream_t s) {
+        return pfhe_tfhe32_external_product_to_dev(p, in, len, key, len_key, out, len, s);
+    }
+};
+
+// Owns, for `chunk` inputs of a tree of depth d: the two ping-pong node buffers (chunk * 2^(d-1) and chunk * 2^(d-2)
+// ciphertexts; the last level writes into the caller's output) and, in the general form, a product plan and the D and E
+// buffers of chunk * 2^(d-1) ciphertexts.  All allocated at creation.
+template <class W>
+struct TfheCmuxTreeCore {
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
+    PlanGuard guard;                // one holder at a time, successive calls on different streams ordered
+    Shape shape{};
+    u32 depth = 1;
+    bool fused = false;
+    size_t chunk = 1, glwe = 0, key_len = 0, bytes = 0;
+    typename CmuxProductCalls<W>::Plan *plan = nullptr;  // owned, general form only
+    W *node[2] = {nullptr, nullptr}, *d = nullptr, *e = nullptr;
+    size_t launch_nodes() const { return chunk << (depth - 1); }
+    ~TfheCmuxTreeCore() {
+        if (!fft) return;
+        {
+            DeviceGuard g(fft->device);
+            for (W *b : {node[0], node[1], d, e})
+                if (b) (void)counted_free(b);
+        }
+        delete plan;
+    }
+};
+struct pfhe_tfhe_cmux_tree_handle : TfheCmuxTreeCore<u64> {};
+struct pfhe_tfhe32_cmux_tree_handle : TfheCmuxTreeCore<u32> {};
+
+namespace {
+
+constexpr const char *kCmuxBusy = "TFHE CMUX-tree handle in use by another thread (one handle per thread)";
+constexpr const char *kCmuxLengths = "TFHE CMUX: d0, d1 and out must be count*(k+1)*N words, count a multiple of per_key, and "
+                                     "keys (count/per_key)*(k+1)*ell*(k+1)*N complex values";
+constexpr const char *kTreeLengths = "TFHE CMUX tree: out must be batch*(k+1)*N words, selectors batch*depth keys of "
+                                     "(k+1)*ell*(k+1)*N complex values and table 2^depth or batch*2^depth ciphertexts";
+constexpr size_t kCmuxDefaultBytes = 256ull << 20;
+constexpr size_t kMaxDepth = 16;
+
+// the product plan's checks in their order, then the depth, all before the device; then every allocation
+template <class W, class H>
+int cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t depth,
+                     size_t chunk, H **out) {
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    Shape sh{};
+    PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, sh));
+    if (depth == 0 || depth > kMaxDepth) {
+        set_last_error("TFHE CMUX tree: depth must be in 1..16");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    auto h = std::make_unique<H>();
+    h->shape = sh;
+    h->depth = (u32)depth;
+    h->fused = sh.k == 1 && sh.log_n <= kFusedMaxLogN;
+    h->glwe = (glwe_dimension + 1) * fft->n;
+    h->key_len = (glwe_dimension + 1) * sh.ell * h->glwe;
+    // ciphertexts per input: the two node buffers (one ciphertext stands for them at depth 1), and D and E in the general form
+    const size_t half = (size_t)1 << (depth - 1), nodes = depth > 1 ? half + half / 2 : 0;
+    const size_t per_input = std::max<size_t>(1, nodes) + (h->fused ? 0 : 2 * half);
+    h->chunk = chunk ? chunk : std::max<size_t>(1, kCmuxDefaultBytes / (per_input * h->glwe * sizeof(W)));
+    if (h->chunk > (0x7fffffffull >> (depth - 1))) {
+        if (chunk) return PFHE_ERR_BAD_LENGTH;
+        h->chunk = 0x7fffffffull >> (depth - 1);  // a launch's grid holds chunk * 2^(depth-1) nodes
+    }
+    DeviceGuard g(fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    h->fft = fft;
+    const size_t ct = h->glwe * sizeof(W);
+    const size_t sizes[] = {depth > 1 ? h->chunk * half * ct : 0, depth > 2 ? h->chunk * (half / 2) * ct : 0,
+                            h->fused ? 0 : h->chunk * half * ct, h->fused ? 0 : h->chunk * half * ct};
+    W **bufs[] = {&h->node[0], &h->node[1], &h->d, &h->e};
+    for (int i = 0; i < 4; ++i) {
+        if (!sizes[i]) continue;
+        void *b = nullptr;
+        PFHE_HIP(counted_malloc(&b, sizes[i]));
+        *bufs[i] = (W *)b;
+        h->bytes += sizes[i];
+    }
+    if (!h->fused) PFHE_TRY(CmuxProductCalls<W>::create(fft, glwe_dimension, log_basis, decompose_length, 0, &h->plan));
+    PFHE_TRY(h->guard.init(fft->device));
+    *out = h.release();
+    return PFHE_OK;
+}
+
+// Rule 1 on `count` nodes whose sources `at` describes (stride, period, per_key, key_stride; first_node is set here), at most
+// launch_nodes() of them per launch; out is count ciphertexts.  Arguments are checked, the device is current.
+template <class W>
+int cmux_nodes(TfheCmuxTreeCore<W> *h, const W *d0, const W *d1, const double2 *keys, W *out, u64 count, CmuxNodes at,
+               hipStream_t s) {
+    const pfhe_fft &f = *h->fft;
+    for (u64 done = 0; done < count; done += h->launch_nodes()) {
+        const u64 cur = std::min<u64>(h->launch_nodes(), count - done);
+        // a period divides every launch's first node (the tree's chunks are whole inputs), so a launch starts at source 0
+        const u64 off = at.period ? 0 : done * at.stride;
+        W *o = out + done * h->glwe;
+        at.first_node = done;
+        if (h->fused) {
+            PFHE_TRY(launch_groups(tfhe_cmux_kernel<W>, cur, lds_bytes(f.log_n), s, d0 + off, d1 + off, keys, o, f.tw, h->shape, at));
+            continue;
+        }
+        PFHE_TRY(launch_flat(tfhe_cmux_glue_kernel<W, false>, cur * h->glwe, s, d0 + off, d1 + off, h->d, (u64)h->glwe, at));
+        for (u64 b = 0; b < cur;) {  // the product's own launches, once per key group that the launch meets
+            const u64 group = (done + b) / at.per_key;
+            const u64 run = std::min<u64>(cur - b, (group + 1) * at.per_key - (done + b));
+            PFHE_TRY(CmuxProductCalls<W>::product(h->plan, h->d + b * h->glwe, run * h->glwe,
+                                                  (const double *)(keys + group * at.key_stride), h->key_len, h->e + b * h->glwe, s));
+            b += run;
+        }
+        PFHE_TRY(launch_flat(tfhe_cmux_glue_kernel<W, true>, cur * h->glwe, s, d0 + off, (const W *)h->e, o, (u64)h->glwe, at));
+    }
+    return PFHE_OK;
+}
+
+template <class W>
+int cmux_dev(TfheCmuxTreeCore<W> *h, const W *d0, size_t len_d0, const W *d1, size_t len_d1, const double *keys, size_t len_keys,
+             size_t per_key, W *out, size_t len_out, hipStream_t s) {
+    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
+    const u64 count = len_d0 / h->glwe;
+    if (per_key == 0 || len_d0 % h->glwe != 0 || len_d1 != len_d0 || len_out != len_d0 || count % per_key != 0 ||
+        len_keys != count / per_key * h->key_len) {
+        set_last_error(kCmuxLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (count == 0) return PFHE_OK;
+    if (!d0 || !d1 || !keys || !out) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(d0);
+    PFHE_REQUIRE_ALIGNED(d1);
+    PFHE_REQUIRE_ALIGNED(keys);
+    PFHE_REQUIRE_ALIGNED(out);
+    // in place is safe (tfhe_cmux_kernel; the general form reads both inputs in the difference launch and adds index by index)
+    const size_t bytes = len_out * sizeof(W);
+    if ((out != d0 && overlaps(d0, bytes, out, bytes)) || (out != d1 && overlaps(d1, bytes, out, bytes)) ||
+        overlaps(keys, len_keys * sizeof(double2), out, bytes)) {
+        set_last_error("TFHE CMUX: out must be exactly d0, exactly d1, or disjoint from both, and disjoint from the keys");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    DeviceGuard g(h->fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    return ordered_on(h->guard, s, [&] {
+        return cmux_nodes<W>(h, d0, d1, (const double2 *)keys, out, count, CmuxNodes{h->glwe, 0, per_key, h->key_len, 0}, s);
+    });
+}
+
+template <class W>
+int cmux_host(TfheCmuxTreeCore<W> *h, const W *d0, size_t len_d0, const W *d1, size_t len_d1, const double *keys, size_t len_keys,
+              size_t per_key, W *out, size_t len_out) {
+    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
+    if ((!d0 && len_d0) || (!d1 && len_d1) || (!keys && len_keys) || (!out && len_out)) return PFHE_ERR_BAD_ARGUMENT;
+    if (per_key == 0 || len_d0 % h->glwe != 0 || len_d1 != len_d0 || len_out != len_d0 || (len_d0 / h->glwe) % per_key != 0 ||
+        len_keys != len_d0 / h->glwe / per_key * h->key_len) {
+        set_last_error(kCmuxLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (len_d0 == 0) return PFHE_OK;
+    const StageBuf bufs[] = {stage_in(d0, len_d0 * sizeof(W)), stage_in(d1, len_d1 * sizeof(W)),
+                             stage_in(keys, len_keys * sizeof(double2)), stage_out(out, len_out * sizeof(W))};
+    return staged_call(h->fft->device, bufs, [&](void *const *p, hipStream_t s) {
+        return cmux_dev<W>(h, (const W *)p[0], len_d0, (const W *)p[1], len_d1, (const double *)p[2], len_keys, per_key, (W *)p[3],
+                           len_out, s);
+    });
+}
+
+// batch from the output; the table is shared when it holds 2^d ciphertexts (at batch 1 the two readings coincide)
+template <class W>
+bool tree_lengths_ok(const TfheCmuxTreeCore<W> *h, size_t len_table, size_t len_selectors, size_t len_out, u64 &batch,
+                     bool &shared) {
+    if (len_out % h->glwe != 0) return false;
+    batch = len_out / h->glwe;
+    const size_t leaves = h->glwe << h->depth;
+    shared = len_table == leaves;
+    return len_selectors == batch * h->depth * h->key_len && (shared || len_table == batch * leaves);
+}
+
+template <class W>
+int cmux_tree_dev(TfheCmuxTreeCore<W> *h, const W *table, size_t len_table, const double *selectors, size_t len_selectors, W *out,
+                  size_t len_out, hipStream_t s) {
+    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
+    u64 batch = 0;
+    bool shared = false;
+    if (!tree_lengths_ok(h, len_table, len_selectors, len_out, batch, shared)) {
+        set_last_error(kTreeLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (batch == 0) return PFHE_OK;
+    if (!table || !selectors || !out) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_REQUIRE_ALIGNED(table);
+    PFHE_REQUIRE_ALIGNED(selectors);
+    PFHE_REQUIRE_ALIGNED(out);
+    if (overlaps(table, len_table * sizeof(W), out, len_out * sizeof(W)) ||
+        overlaps(selectors, len_selectors * sizeof(double2), out, len_out * sizeof(W))) {
+        set_last_error("TFHE CMUX tree: the output must not overlap an input");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    DeviceGuard g(h->fft->device);
+    if (!g.ok) return PFHE_ERR_NO_DEVICE;
+    const u32 d = h->depth;
+    const size_t glwe = h->glwe;
+    return ordered_on(h->guard, s, [&]() -> int {
+        // chunk after chunk; every level of a chunk is queued before the next chunk starts
+        for (u64 done = 0; done < batch; done += h->chunk) {
+            const u64 cur = std::min<u64>(h->chunk, batch - done);
+            const double2 *keys = (const double2 *)selectors + done * d * h->key_len;
+            const W *src = shared ? table : table + (done << d) * glwe;
+            for (u32 j = 0; j < d; ++j) {
+                const u64 per_input = 1ull << (d - 1 - j);
+                W *dst = j + 1 == d ? out + done * glwe : h->node[j & 1];
+                const CmuxNodes at{2 * glwe, 0, per_input, (u64)d * h->key_len, j == 0 && shared ? (u32)per_input : 0u};
+                PFHE_TRY(cmux_nodes<W>(h, src, src + glwe, keys + j * h->key_len, dst, cur * per_input, at, s));
+                src = dst;
+            }
+        }
+        return PFHE_OK;
+    });
+}
+
+template <class W>
+int cmux_tree_host(TfheCmuxTreeCore<W> *h, const W *table, size_t len_table, const double *selectors, size_t len_selectors, W *out,
+                   size_t len_out) {
+    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
+    PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
+    if ((!table && len_table) || (!selectors && len_selectors) || (!out && len_out)) return PFHE_ERR_BAD_ARGUMENT;
+    u64 batch = 0;
+    bool shared = false;
+    if (!tree_lengths_ok(h, len_table, len_selectors, len_out, batch, shared)) {
+        set_last_error(kTreeLengths);
+        return PFHE_ERR_BAD_LENGTH;
+    }
+    if (batch == 0) return PFHE_OK;
+    const StageBuf bufs[] = {stage_in(table, len_table * sizeof(W)), stage_in(selectors, len_selectors * sizeof(double2)),
+                             stage_out(out, len_out * sizeof(W))};
+    return staged_call(h->fft->device, bufs, [&](void *const *p, hipStream_t s) {
+        return cmux_tree_dev<W>(h, (const W *)p[0], len_table, (const double *)p[1], len_selectors, (W *)p[2], len_out, s);
+    });
+}
+
+template <class H>
+size_t cmux_scratch(const H *h) {
+    return h && h->fft ? h->bytes + (h->plan ? h->plan->scratch.bytes : 0) : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pfhe_tfhe_cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                               size_t depth, size_t chunk, pfhe_tfhe_cmux_tree_handle **out) {
+    PFHE_GUARD_BEGIN
+    return cmux_tree_create<u64>(fft, glwe_dimension, log_basis, decompose_length, depth, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe_cmux_tree_destroy(pfhe_tfhe_cmux_tree_handle *h) { delete h; }
+int pfhe_tfhe_cmux_tree_in_use(const pfhe_tfhe_cmux_tree_handle *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe_cmux_tree_scratch_bytes(const pfhe_tfhe_cmux_tree_handle *h) { return cmux_scratch(h); }
+int pfhe_tfhe_cmux_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0_dev, size_t len_d0, const uint64_t *d1_dev, size_t len_d1,
+                       const double *keys_dev, size_t len_keys, size_t per_key, uint64_t *out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return cmux_dev<u64>(h, (const u64 *)d0_dev, len_d0, (const u64 *)d1_dev, len_d1, keys_dev, len_keys, per_key, (u64 *)out_dev,
+                         len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_cmux(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0, size_t len_d0, const uint64_t *d1, size_t len_d1, const double *keys,
+                   size_t len_keys, size_t per_key, uint64_t *out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return cmux_host<u64>(h, (const u64 *)d0, len_d0, (const u64 *)d1, len_d1, keys, len_keys, per_key, (u64 *)out, len_out);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_cmux_tree_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table_dev, size_t len_table, const double *selectors_dev,
+                            size_t len_selectors, uint64_t *out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return cmux_tree_dev<u64>(h, (const u64 *)table_dev, len_table, selectors_dev, len_selectors, (u64 *)out_dev, len_out,
+                              (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe_cmux_tree(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table, size_t len_table, const double *selectors,
+                        size_t len_selectors, uint64_t *out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return cmux_tree_host<u64>(h, (const u64 *)table, len_table, selectors, len_selectors, (u64 *)out, len_out);
+    PFHE_GUARD_END
+}
+
+int pfhe_tfhe32_cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                 size_t depth, size_t chunk, pfhe_tfhe32_cmux_tree_handle **out) {
+    PFHE_GUARD_BEGIN
+    return cmux_tree_create<u32>(fft, glwe_dimension, log_basis, decompose_length, depth, chunk, out);
+    PFHE_GUARD_END
+}
+void pfhe_tfhe32_cmux_tree_destroy(pfhe_tfhe32_cmux_tree_handle *h) { delete h; }
+int pfhe_tfhe32_cmux_tree_in_use(const pfhe_tfhe32_cmux_tree_handle *h) { return h ? h->guard.in_use() : 0; }
+size_t pfhe_tfhe32_cmux_tree_scratch_bytes(const pfhe_tfhe32_cmux_tree_handle *h) { return cmux_scratch(h); }
+int pfhe_tfhe32_cmux_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0_dev, size_t len_d0, const uint32_t *d1_dev, size_t len_d1,
+                         const double *keys_dev, size_t len_keys, size_t per_key, uint32_t *out_dev, size_t len_out,
+                         void *stream) {
+    PFHE_GUARD_BEGIN
+    return cmux_dev<u32>(h, d0_dev, len_d0, d1_dev, len_d1, keys_dev, len_keys, per_key, out_dev, len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_cmux(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0, size_t len_d0, const uint32_t *d1, size_t len_d1,
+                     const double *keys, size_t len_keys, size_t per_key, uint32_t *out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return cmux_host<u32>(h, d0, len_d0, d1, len_d1, keys, len_keys, per_key, out, len_out);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_cmux_tree_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table_dev, size_t len_table, const double *selectors_dev,
+                              size_t len_selectors, uint32_t *out_dev, size_t len_out, void *stream) {
+    PFHE_GUARD_BEGIN
+    return cmux_tree_dev<u32>(h, table_dev, len_table, selectors_dev, len_selectors, out_dev, len_out, (hipStream_t)stream);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_cmux_tree(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
+                          size_t len_selectors, uint32_t *out, size_t len_out) {
+    PFHE_GUARD_BEGIN
+    return cmux_tree_host<u32>(h, table, len_table, selectors, len_selectors, out, len_out);
+    PFHE_GUARD_END
+}
+
+}  // extern "C"

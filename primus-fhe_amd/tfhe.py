@@ -813,6 +813,63 @@ def tfhe_circuit_bootstrap_dev(lwe_in, bsk, pfksk, ggsw_out, ctx: TfheCircuitBoo
     check(getattr(lib(), ctx._pre + "_dev")(ctx._h, pi, ni, pk, nk, pp, np_, po, no, _stream(stream)))
 
 
+# ---- the CMUX with a selector per group, and the CMUX tree (include/pfhe.h: cmux_tree_*, cmux, cmux_dev) ----
+
+class TfheCmuxTreeContext(_TorusContext):
+    """Handle of the batched CMUX and of the CMUX tree (include/pfhe.h, pfhe_tfhe{,32}_cmux_tree_*): a tree of `depth`
+    (1..16) levels selects one of 2^depth GLWE ciphertexts by depth Fourier GGSW selectors per input, the vertical packing
+    of a look-up table; tfhe_cmux(_dev) is one level with a key per group as a call of its own.  `basis` is the selectors'
+    (the circuit bootstrap's cbs_basis when they come from there).  Owns the node buffers of `chunk` inputs (0 = the
+    default) and, off the fused shape, a product plan; one holder at a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int, depth: int, chunk: int = 0):
+        self._open(fft, basis, glwe_dimension, "cmux_tree", (depth, chunk), ("_create", "_destroy", "_in_use", "_scratch_bytes"))
+        self.depth = depth
+
+
+def _cmux(words, fourier, d0, d1, keys, out, per_key, ctx, name, tail):
+    p0, n0, w0 = words(d0)
+    p1, n1, w1 = words(d1)
+    po, no, wo = words(out)
+    pk, nk = fourier(keys)
+    _same_width("d0, d1 and out must have the width of the context's basis", w0, w1, wo, ctx._w)
+    check(getattr(lib(), "pfhe_tfhe" + ctx._w + name)(ctx._h, p0, n0, p1, n1, pk, nk, per_key, po, no, *tail))
+
+
+def tfhe_cmux(d0: np.ndarray, d1: np.ndarray, keys: np.ndarray, out: np.ndarray, ctx: TfheCmuxTreeContext,
+              per_key: int = 1) -> None:
+    """Batched CMUX on host arrays: out[i] = d0[i] + external_product_to(d1[i] - d0[i], keys[i // per_key]) modulo 2^BITS
+    for count GLWE ciphertexts and count / per_key Fourier GGSW keys end to end (ctx.key_len() complex values each): a key
+    of the bit m selects d_m.  Word for word the subtraction, tfhe_external_product_to per key group and the addition."""
+    _cmux(_host_words, _host_fourier, d0, d1, keys, out, per_key, ctx, "_cmux", ())
+
+
+def tfhe_cmux_dev(d0, d1, keys, out, ctx: TfheCmuxTreeContext, per_key: int = 1, stream=None) -> None:
+    """the device form, asynchronous; out may be exactly d0 or exactly d1, any other overlap with an input is refused"""
+    _cmux(_dev_words, _dev_fourier, d0, d1, keys, out, per_key, ctx, "_cmux_dev", (_stream(stream),))
+
+
+def _cmux_tree(words, fourier, table, selectors, out, ctx, name, tail):
+    pt, nt, wt = words(table)
+    po, no, wo = words(out)
+    ps, ns = fourier(selectors)
+    _same_width("table and out must have the width of the context's basis", wt, wo, ctx._w)
+    check(getattr(lib(), ctx._pre + name)(ctx._h, pt, nt, ps, ns, po, no, *tail))
+
+
+def tfhe_cmux_tree(table: np.ndarray, selectors: np.ndarray, out: np.ndarray, ctx: TfheCmuxTreeContext) -> None:
+    """The CMUX tree on host arrays.  table: 2^depth GLWE ciphertexts shared by the batch, or batch * 2^depth, input-major;
+    selectors: batch x depth Fourier GGSW keys, the key of input e and bit j at e*depth + j (what
+    tfhe_circuit_bootstrap_dev on inputs in that order, then write_fourier_form, gives); out: batch ciphertexts, out[e] the
+    leaf sum_j m_{e,j} 2^j of e's table.  Word for word depth calls of tfhe_cmux with per_key = 2^(depth-1-j)."""
+    _cmux_tree(_host_words, _host_fourier, table, selectors, out, ctx, "", ())
+
+
+def tfhe_cmux_tree_dev(table, selectors, out, ctx: TfheCmuxTreeContext, stream=None) -> None:
+    """the device form, asynchronous; out must not overlap an input and may be uninitialised"""
+    _cmux_tree(_dev_words, _dev_fourier, table, selectors, out, ctx, "_dev", (_stream(stream),))
+
+
 def _torus_dtype(bits: int):
     import torch
     if bits not in (32, 64):
