@@ -12,7 +12,8 @@
 //                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_word of
 //                      pfhe_fft_device.hpp, over the product's own digit_step).
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
-// host forms go through pfhe_tfhe_host.hpp; the key switch keeps its own 2-D grid.
+// the two forms of every call (stateless_call, handle_call) go through pfhe_tfhe_host.hpp; the key switch keeps its own
+// 2-D grid.
 #include <algorithm>
 #include <cstdint>
 #include <memory>
@@ -403,9 +404,10 @@ int bootstrap_check(const H *h, size_t len_in, size_t len_bsk, size_t len_tv, si
     return PFHE_OK;
 }
 
+// Both forms refuse alike up to the null test; the device form then looks at its pointers.
 template <class W, class H>
-int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
-                  const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out, hipStream_t s) {
+int bootstrap(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
+              const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out, hipStream_t s) {
     if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
     if (!h->with_keyswitch && (ksk || len_ksk)) {
@@ -416,56 +418,38 @@ int bootstrap_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_
     PFHE_TRY((bootstrap_check<W>(h, len_in, len_bsk, len_tv, len_ksk, len_out, batch)));
     if (batch == 0) return PFHE_OK;
     if (!lwe_in || !bsk || !tv || !lwe_out || (h->with_keyswitch && !ksk)) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(bsk);
-    const size_t out_bytes = len_out * sizeof(W);
-    if (overlaps(lwe_in, len_in * sizeof(W), lwe_out, out_bytes) || overlaps(tv, len_tv * sizeof(W), lwe_out, out_bytes) ||
-        overlaps(bsk, len_bsk * 2 * sizeof(double), lwe_out, out_bytes) ||
-        (ksk && overlaps(ksk, len_ksk * sizeof(W), lwe_out, out_bytes))) {
-        set_last_error("TFHE bootstrap: the output must not overlap an input");
-        return PFHE_ERR_BAD_ARGUMENT;
+    if (form == Form::kDevice) {
+        PFHE_REQUIRE_ALIGNED(bsk);
+        const size_t out_bytes = len_out * sizeof(W);
+        if (overlaps(lwe_in, len_in * sizeof(W), lwe_out, out_bytes) || overlaps(tv, len_tv * sizeof(W), lwe_out, out_bytes) ||
+            overlaps(bsk, len_bsk * 2 * sizeof(double), lwe_out, out_bytes) ||
+            (ksk && overlaps(ksk, len_ksk * sizeof(W), lwe_out, out_bytes))) {
+            set_last_error("TFHE bootstrap: the output must not overlap an input");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
     }
     const pfhe_fft &f = *h->fft;
-    DeviceGuard g(f.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
     const size_t glwe = h->rotation->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
     const size_t out_words = h->with_keyswitch ? in_words : ext;
     const u64 tv_stride = len_tv == glwe ? 0 : glwe;
-    return ordered_on(h->guard, s, [&]() -> int {
-        // chunk after chunk; every stage of a chunk is queued before the next chunk starts
-        for (u64 done = 0; done < batch; done += h->chunk) {
-            const u64 cur = std::min<u64>(h->chunk, batch - done);
-            PFHE_TRY(launch_modswitch<W>(lwe_in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, s));
-            PFHE_TRY(launch_acc_init<W>(tv + done * tv_stride, tv_stride, h->acc, h->neg_b, h->k + 1, f.log_n, cur, s));
-            PFHE_TRY(h->rotation->rotate_dev(h->acc, cur * glwe, bsk, len_bsk, h->exps, cur * h->n, s));
-            W *lwe = h->with_keyswitch ? h->extracted : lwe_out + done * out_words;
-            PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, s));
-            if (h->with_keyswitch) PFHE_TRY(launch_keyswitch<W>(lwe, ksk, lwe_out + done * out_words, h->ks, cur, s));
-        }
-        return PFHE_OK;
-    });
-}
-
-// host form
-template <class W, class H>
-int bootstrap_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *tv, size_t len_tv,
-                   const W *ksk, size_t len_ksk, W *lwe_out, size_t len_out) {
-    if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h->guard, kBootstrapBusy);
-    if (!h->with_keyswitch && (ksk || len_ksk)) {
-        set_last_error("TFHE bootstrap: a handle without a key switch takes no key-switch key");
-        return PFHE_ERR_BAD_ARGUMENT;
-    }
-    u64 batch = 0;
-    PFHE_TRY((bootstrap_check<W>(h, len_in, len_bsk, len_tv, len_ksk, len_out, batch)));
-    if (batch == 0) return PFHE_OK;
-    if (!lwe_in || !bsk || !tv || !lwe_out || (h->with_keyswitch && !ksk)) return PFHE_ERR_BAD_ARGUMENT;
-    // without a key switch ksk is empty: it is not staged and the device form gets a null pointer
+    // without a key switch ksk is empty: the host form does not stage it and the launches get a null pointer
     const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
                              stage_in(tv, len_tv * sizeof(W)), stage_in(ksk, len_ksk * sizeof(W)),
                              stage_out(lwe_out, len_out * sizeof(W))};
-    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
-        return bootstrap_dev<W>(h, (const W *)d[0], len_in, (const double *)d[1], len_bsk, (const W *)d[2], len_tv,
-                                (const W *)d[3], len_ksk, (W *)d[4], len_out, s);
+    return handle_call(h->guard, f.device, form, bufs, s, [&](void *const *d, hipStream_t st) -> int {
+        const W *in = (const W *)d[0], *vec = (const W *)d[2], *key = (const W *)d[3];
+        W *out = (W *)d[4];
+        // chunk after chunk; every stage of a chunk is queued before the next chunk starts
+        for (u64 done = 0; done < batch; done += h->chunk) {
+            const u64 cur = std::min<u64>(h->chunk, batch - done);
+            PFHE_TRY(launch_modswitch<W>(in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, st));
+            PFHE_TRY(launch_acc_init<W>(vec + done * tv_stride, tv_stride, h->acc, h->neg_b, h->k + 1, f.log_n, cur, st));
+            PFHE_TRY(h->rotation->rotate_dev(h->acc, cur * glwe, (const double *)d[1], len_bsk, h->exps, cur * h->n, st));
+            W *lwe = h->with_keyswitch ? h->extracted : out + done * out_words;
+            PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, st));
+            if (h->with_keyswitch) PFHE_TRY(launch_keyswitch<W>(lwe, key, out + done * out_words, h->ks, cur, st));
+        }
+        return PFHE_OK;
     });
 }
 
@@ -579,16 +563,16 @@ int pfhe_tfhe_bootstrap_dev(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_i
                             size_t len_bsk, const uint64_t *tv_dev, size_t len_tv, const uint64_t *ksk_dev, size_t len_ksk,
                             uint64_t *lwe_out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return bootstrap_dev<u64>(h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)tv_dev, len_tv,
-                              (const u64 *)ksk_dev, len_ksk, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
+    return bootstrap<u64>(Form::kDevice, h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)tv_dev, len_tv,
+                          (const u64 *)ksk_dev, len_ksk, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_bootstrap(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
                         const uint64_t *tv, size_t len_tv, const uint64_t *ksk, size_t len_ksk, uint64_t *lwe_out,
                         size_t len_out) {
     PFHE_GUARD_BEGIN
-    return bootstrap_host<u64>(h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)tv, len_tv, (const u64 *)ksk, len_ksk,
-                               (u64 *)lwe_out, len_out);
+    return bootstrap<u64>(Form::kHost, h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)tv, len_tv,
+                          (const u64 *)ksk, len_ksk, (u64 *)lwe_out, len_out, nullptr);
     PFHE_GUARD_END
 }
 
@@ -617,15 +601,15 @@ int pfhe_tfhe32_bootstrap_dev(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *l
                               size_t len_bsk, const uint32_t *tv_dev, size_t len_tv, const uint32_t *ksk_dev, size_t len_ksk,
                               uint32_t *lwe_out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return bootstrap_dev<u32>(h, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev, len_ksk, lwe_out_dev, len_out,
-                              (hipStream_t)stream);
+    return bootstrap<u32>(Form::kDevice, h, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev, len_ksk, lwe_out_dev,
+                          len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_bootstrap(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
                           const uint32_t *tv, size_t len_tv, const uint32_t *ksk, size_t len_ksk, uint32_t *lwe_out,
                           size_t len_out) {
     PFHE_GUARD_BEGIN
-    return bootstrap_host<u32>(h, lwe_in, len_in, bsk, len_bsk, tv, len_tv, ksk, len_ksk, lwe_out, len_out);
+    return bootstrap<u32>(Form::kHost, h, lwe_in, len_in, bsk, len_bsk, tv, len_tv, ksk, len_ksk, lwe_out, len_out, nullptr);
     PFHE_GUARD_END
 }
 

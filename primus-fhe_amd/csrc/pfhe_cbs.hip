@@ -13,7 +13,8 @@
 //                        rotation handle on batch * levels accumulators, extraction at index 0 with g_l/2 added to the body,
 //                        and the private key switch with levels = ell_cb into the caller's GGSWs.
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
-// host forms go through pfhe_tfhe_host.hpp; the private key switch keeps its own 3-D grid.
+// the two forms of every call (stateless_call, handle_call) go through pfhe_tfhe_host.hpp; the private key switch keeps
+// its own 3-D grid.
 #include <algorithm>
 #include <cstdint>
 #include <memory>
@@ -414,60 +415,46 @@ int cbs_check(const H *h, size_t len_in, size_t len_bsk, size_t len_pfksk, size_
     return PFHE_OK;
 }
 
+// Both forms refuse alike up to the null test; the device form then looks at its pointers.
 template <class W, class H>
-int cbs_dev(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *pfksk, size_t len_pfksk,
-            W *ggsw_out, size_t len_out, hipStream_t s) {
+int cbs(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *pfksk, size_t len_pfksk,
+        W *ggsw_out, size_t len_out, hipStream_t s) {
     if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kCbsBusy);
     u64 batch = 0;
     PFHE_TRY((cbs_check<W>(h, len_in, len_bsk, len_pfksk, len_out, batch)));
     if (batch == 0) return PFHE_OK;
     if (!lwe_in || !bsk || !pfksk || !ggsw_out) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(bsk);
-    const size_t out_bytes = len_out * sizeof(W);
-    if (overlaps(lwe_in, len_in * sizeof(W), ggsw_out, out_bytes) || overlaps(bsk, len_bsk * 2 * sizeof(double), ggsw_out, out_bytes) ||
-        overlaps(pfksk, len_pfksk * sizeof(W), ggsw_out, out_bytes)) {
-        set_last_error("TFHE circuit bootstrap: the output must not overlap an input");
-        return PFHE_ERR_BAD_ARGUMENT;
+    if (form == Form::kDevice) {
+        PFHE_REQUIRE_ALIGNED(bsk);
+        const size_t out_bytes = len_out * sizeof(W);
+        if (overlaps(lwe_in, len_in * sizeof(W), ggsw_out, out_bytes) ||
+            overlaps(bsk, len_bsk * 2 * sizeof(double), ggsw_out, out_bytes) ||
+            overlaps(pfksk, len_pfksk * sizeof(W), ggsw_out, out_bytes)) {
+            set_last_error("TFHE circuit bootstrap: the output must not overlap an input");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
     }
     const pfhe_fft &f = *h->fft;
-    DeviceGuard g(f.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
     const size_t glwe = h->rotation->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
     const u32 levels = h->cb_ell, half_shift = h->cb_drop - 1;
     const size_t ggsw = (size_t)(h->k + 1) * levels * glwe;
-    return ordered_on(h->guard, s, [&]() -> int {
+    const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
+                             stage_in(pfksk, len_pfksk * sizeof(W)), stage_out(ggsw_out, len_out * sizeof(W))};
+    return handle_call(h->guard, f.device, form, bufs, s, [&](void *const *d, hipStream_t st) -> int {
         // chunk after chunk; every stage of a chunk is queued before the next chunk starts
         for (u64 done = 0; done < batch; done += h->chunk) {
             const u64 cur = std::min<u64>(h->chunk, batch - done), accs = cur * levels;
-            PFHE_TRY(launch_flat(tfhe_cbs_modswitch_kernel<W>, cur * in_words, s, lwe_in + done * in_words, h->exps, h->neg_b,
-                                 h->n, f.log_n, levels));
-            PFHE_TRY(launch_flat(tfhe_cbs_acc_init_kernel<W>, accs * glwe, s, h->acc, (const u32 *)h->neg_b, h->k, f.log_n, levels,
+            PFHE_TRY(launch_flat(tfhe_cbs_modswitch_kernel<W>, cur * in_words, st, (const W *)d[0] + done * in_words, h->exps,
+                                 h->neg_b, h->n, f.log_n, levels));
+            PFHE_TRY(launch_flat(tfhe_cbs_acc_init_kernel<W>, accs * glwe, st, h->acc, (const u32 *)h->neg_b, h->k, f.log_n, levels,
                                  h->cb_log_basis, half_shift));
-            PFHE_TRY(h->rotation->rotate_dev(h->acc, accs * glwe, bsk, len_bsk, h->exps, accs * h->n, s));
-            PFHE_TRY(launch_flat(tfhe_cbs_extract_kernel<W>, accs * ext, s, (const W *)h->acc, h->extracted, h->k, f.log_n, levels,
+            PFHE_TRY(h->rotation->rotate_dev(h->acc, accs * glwe, (const double *)d[1], len_bsk, h->exps, accs * h->n, st));
+            PFHE_TRY(launch_flat(tfhe_cbs_extract_kernel<W>, accs * ext, st, (const W *)h->acc, h->extracted, h->k, f.log_n, levels,
                                  h->cb_log_basis, half_shift));
-            PFHE_TRY(launch_pfks<W>(h->extracted, pfksk, ggsw_out + done * ggsw, h->pf, accs, s));
+            PFHE_TRY(launch_pfks<W>(h->extracted, (const W *)d[2], (W *)d[3] + done * ggsw, h->pf, accs, st));
         }
         return PFHE_OK;
-    });
-}
-
-// host form
-template <class W, class H>
-int cbs_host(H *h, const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *pfksk, size_t len_pfksk,
-             W *ggsw_out, size_t len_out) {
-    if (!h || !h->rotation) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h->guard, kCbsBusy);
-    u64 batch = 0;
-    PFHE_TRY((cbs_check<W>(h, len_in, len_bsk, len_pfksk, len_out, batch)));
-    if (batch == 0) return PFHE_OK;
-    if (!lwe_in || !bsk || !pfksk || !ggsw_out) return PFHE_ERR_BAD_ARGUMENT;
-    const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
-                             stage_in(pfksk, len_pfksk * sizeof(W)), stage_out(ggsw_out, len_out * sizeof(W))};
-    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
-        return cbs_dev<W>(h, (const W *)d[0], len_in, (const double *)d[1], len_bsk, (const W *)d[2], len_pfksk, (W *)d[3],
-                          len_out, s);
     });
 }
 
@@ -547,14 +534,15 @@ size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h) { return cbs_s
 int pfhe_tfhe_cbs_dev(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk,
                       const uint64_t *pfksk_dev, size_t len_pfksk, uint64_t *ggsw_out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return cbs_dev<u64>(h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)pfksk_dev, len_pfksk,
-                        (u64 *)ggsw_out_dev, len_out, (hipStream_t)stream);
+    return cbs<u64>(Form::kDevice, h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)pfksk_dev, len_pfksk,
+                    (u64 *)ggsw_out_dev, len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_cbs(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
                   const uint64_t *pfksk, size_t len_pfksk, uint64_t *ggsw_out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return cbs_host<u64>(h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)pfksk, len_pfksk, (u64 *)ggsw_out, len_out);
+    return cbs<u64>(Form::kHost, h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)pfksk, len_pfksk, (u64 *)ggsw_out,
+                    len_out, nullptr);
     PFHE_GUARD_END
 }
 
@@ -573,14 +561,14 @@ int pfhe_tfhe32_cbs_dev(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in_dev, s
                         size_t len_bsk, const uint32_t *pfksk_dev, size_t len_pfksk, uint32_t *ggsw_out_dev, size_t len_out,
                         void *stream) {
     PFHE_GUARD_BEGIN
-    return cbs_dev<u32>(h, lwe_in_dev, len_in, bsk_dev, len_bsk, pfksk_dev, len_pfksk, ggsw_out_dev, len_out,
-                        (hipStream_t)stream);
+    return cbs<u32>(Form::kDevice, h, lwe_in_dev, len_in, bsk_dev, len_bsk, pfksk_dev, len_pfksk, ggsw_out_dev, len_out,
+                    (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_cbs(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
                     const uint32_t *pfksk, size_t len_pfksk, uint32_t *ggsw_out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return cbs_host<u32>(h, lwe_in, len_in, bsk, len_bsk, pfksk, len_pfksk, ggsw_out, len_out);
+    return cbs<u32>(Form::kHost, h, lwe_in, len_in, bsk, len_bsk, pfksk, len_pfksk, ggsw_out, len_out, nullptr);
     PFHE_GUARD_END
 }
 

@@ -9,11 +9,12 @@
 //                        rule 1 with per_key = 2^(d-1-j) and a key stride of d.
 //   fused   (k = 1, N <= 2^11): tfhe_cmux_kernel, one launch per level and chunk, a workgroup per node: the difference in
 //            registers, the product's own accumulate and inverse code against the node's key, d0 added in the sink;
-//   general (every other shape): one difference launch, the product's own launch sequence once per key group through the
-//            public product call on a plan the handle owns, one add launch.  batch * d product sequences per tree: the
-//            slow form.
+//   general (every other shape): one difference launch, the product's own launch sequence (tfhe_product_impl) once per key
+//            group on a plan the handle owns, one add launch, all under the handle's own stream order.  batch * d product
+//            sequences per tree: the slow form.
 // Nothing is atomic and the summation order is the product's: the words depend neither on the batch, nor on the chunk,
-// nor on how per_key tiles the launches.  Launches and host forms go through pfhe_tfhe_host.hpp.
+// nor on how per_key tiles the launches.  Launches and the two forms of both calls (handle_call) go through
+// pfhe_tfhe_host.hpp.
 #include <algorithm>
 #include <cstdint>
 #include <memory>
@@ -94,29 +95,6 @@ __global__ __launch_bounds__(kThreads) void tfhe_cmux_glue_kernel(const W *d0, c
 
 // ---------------- the handle ----------------
 
-template <class W>
-struct CmuxProductCalls;
-template <>
-struct CmuxProductCalls<u64> {
-    using Plan = pfhe_tfhe_plan;
-    static int create(const pfhe_fft *f, size_t k, uint32_t lb, size_t ell, size_t chunk, Plan **out) {
-        return pfhe_tfhe_plan_create(f, k, lb, ell, chunk, out);
-    }
-    static int product(Plan *p, const u64 *in, size_t len, const double *key, size_t len_key, u64 *out, hipStream_t s) {
-        return pfhe_tfhe_external_product_to_dev(p, (const uint64_t *)in, len, key, len_key, (uint64_t *)out, len, s);
-    }
-};
-template <>
-struct CmuxProductCalls<u32> {
-    using Plan = pfhe_tfhe32_plan;
-    static int create(const pfhe_fft *f, size_t k, uint32_t lb, size_t ell, size_t chunk, Plan **out) {
-        return pfhe_tfhe32_plan_create(f, k, lb, ell, chunk, out);
-    }
-    static int product(Plan *p, const u32 *in, size_t len, const double *key, size_t len_key, u32 *out, hipStream_t s) {
-        return pfhe_tfhe32_external_product_to_dev(p, in, len, key, len_key, out, len, s);
-    }
-};
-
 // Owns, for `chunk` inputs of a tree of depth d: the two ping-pong node buffers (chunk * 2^(d-1) and chunk * 2^(d-2)
 // ciphertexts; the last level writes into the caller's output) and, in the general form, a product plan and the D and E
 // buffers of chunk * 2^(d-1) ciphertexts.  All allocated at creation.
@@ -128,7 +106,7 @@ struct TfheCmuxTreeCore {
     u32 depth = 1;
     bool fused = false;
     size_t chunk = 1, glwe = 0, key_len = 0, bytes = 0;
-    typename CmuxProductCalls<W>::Plan *plan = nullptr;  // owned, general form only
+    TfhePlanCore<W> *plan = nullptr;  // owned, general form only; its launches run under this handle's guard
     W *node[2] = {nullptr, nullptr}, *d = nullptr, *e = nullptr;
     size_t launch_nodes() const { return chunk << (depth - 1); }
     ~TfheCmuxTreeCore() {
@@ -194,7 +172,7 @@ int cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
         *bufs[i] = (W *)b;
         h->bytes += sizes[i];
     }
-    if (!h->fused) PFHE_TRY(CmuxProductCalls<W>::create(fft, glwe_dimension, log_basis, decompose_length, 0, &h->plan));
+    if (!h->fused) PFHE_TRY(tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, 0, &h->plan));
     PFHE_TRY(h->guard.init(fft->device));
     *out = h.release();
     return PFHE_OK;
@@ -220,8 +198,7 @@ int cmux_nodes(TfheCmuxTreeCore<W> *h, const W *d0, const W *d1, const double2 *
         for (u64 b = 0; b < cur;) {  // the product's own launches, once per key group that the launch meets
             const u64 group = (done + b) / at.per_key;
             const u64 run = std::min<u64>(cur - b, (group + 1) * at.per_key - (done + b));
-            PFHE_TRY(CmuxProductCalls<W>::product(h->plan, h->d + b * h->glwe, run * h->glwe,
-                                                  (const double *)(keys + group * at.key_stride), h->key_len, h->e + b * h->glwe, s));
+            PFHE_TRY(tfhe_product_impl<W>(h->plan, h->d + b * h->glwe, keys + group * at.key_stride, h->e + b * h->glwe, run, s));
             b += run;
         }
         PFHE_TRY(launch_flat(tfhe_cmux_glue_kernel<W, true>, cur * h->glwe, s, d0 + off, (const W *)h->e, o, (u64)h->glwe, at));
@@ -229,11 +206,14 @@ int cmux_nodes(TfheCmuxTreeCore<W> *h, const W *d0, const W *d1, const double2 *
     return PFHE_OK;
 }
 
+// The host form refuses a null pointer before the lengths; the device form's pointer tests follow the empty batch.
 template <class W>
-int cmux_dev(TfheCmuxTreeCore<W> *h, const W *d0, size_t len_d0, const W *d1, size_t len_d1, const double *keys, size_t len_keys,
-             size_t per_key, W *out, size_t len_out, hipStream_t s) {
+int cmux(Form form, TfheCmuxTreeCore<W> *h, const W *d0, size_t len_d0, const W *d1, size_t len_d1, const double *keys,
+         size_t len_keys, size_t per_key, W *out, size_t len_out, hipStream_t s) {
     if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
+    if (form == Form::kHost && ((!d0 && len_d0) || (!d1 && len_d1) || (!keys && len_keys) || (!out && len_out)))
+        return PFHE_ERR_BAD_ARGUMENT;
     const u64 count = len_d0 / h->glwe;
     if (per_key == 0 || len_d0 % h->glwe != 0 || len_d1 != len_d0 || len_out != len_d0 || count % per_key != 0 ||
         len_keys != count / per_key * h->key_len) {
@@ -241,42 +221,26 @@ int cmux_dev(TfheCmuxTreeCore<W> *h, const W *d0, size_t len_d0, const W *d1, si
         return PFHE_ERR_BAD_LENGTH;
     }
     if (count == 0) return PFHE_OK;
-    if (!d0 || !d1 || !keys || !out) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(d0);
-    PFHE_REQUIRE_ALIGNED(d1);
-    PFHE_REQUIRE_ALIGNED(keys);
-    PFHE_REQUIRE_ALIGNED(out);
-    // in place is safe (tfhe_cmux_kernel; the general form reads both inputs in the difference launch and adds index by index)
-    const size_t bytes = len_out * sizeof(W);
-    if ((out != d0 && overlaps(d0, bytes, out, bytes)) || (out != d1 && overlaps(d1, bytes, out, bytes)) ||
-        overlaps(keys, len_keys * sizeof(double2), out, bytes)) {
-        set_last_error("TFHE CMUX: out must be exactly d0, exactly d1, or disjoint from both, and disjoint from the keys");
-        return PFHE_ERR_BAD_ARGUMENT;
+    if (form == Form::kDevice) {
+        if (!d0 || !d1 || !keys || !out) return PFHE_ERR_BAD_ARGUMENT;
+        PFHE_REQUIRE_ALIGNED(d0);
+        PFHE_REQUIRE_ALIGNED(d1);
+        PFHE_REQUIRE_ALIGNED(keys);
+        PFHE_REQUIRE_ALIGNED(out);
+        // in place is safe (tfhe_cmux_kernel; the general form reads both inputs in the difference launch and adds index by
+        // index)
+        const size_t bytes = len_out * sizeof(W);
+        if ((out != d0 && overlaps(d0, bytes, out, bytes)) || (out != d1 && overlaps(d1, bytes, out, bytes)) ||
+            overlaps(keys, len_keys * sizeof(double2), out, bytes)) {
+            set_last_error("TFHE CMUX: out must be exactly d0, exactly d1, or disjoint from both, and disjoint from the keys");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
     }
-    DeviceGuard g(h->fft->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return ordered_on(h->guard, s, [&] {
-        return cmux_nodes<W>(h, d0, d1, (const double2 *)keys, out, count, CmuxNodes{h->glwe, 0, per_key, h->key_len, 0}, s);
-    });
-}
-
-template <class W>
-int cmux_host(TfheCmuxTreeCore<W> *h, const W *d0, size_t len_d0, const W *d1, size_t len_d1, const double *keys, size_t len_keys,
-              size_t per_key, W *out, size_t len_out) {
-    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
-    if ((!d0 && len_d0) || (!d1 && len_d1) || (!keys && len_keys) || (!out && len_out)) return PFHE_ERR_BAD_ARGUMENT;
-    if (per_key == 0 || len_d0 % h->glwe != 0 || len_d1 != len_d0 || len_out != len_d0 || (len_d0 / h->glwe) % per_key != 0 ||
-        len_keys != len_d0 / h->glwe / per_key * h->key_len) {
-        set_last_error(kCmuxLengths);
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    if (len_d0 == 0) return PFHE_OK;
     const StageBuf bufs[] = {stage_in(d0, len_d0 * sizeof(W)), stage_in(d1, len_d1 * sizeof(W)),
                              stage_in(keys, len_keys * sizeof(double2)), stage_out(out, len_out * sizeof(W))};
-    return staged_call(h->fft->device, bufs, [&](void *const *p, hipStream_t s) {
-        return cmux_dev<W>(h, (const W *)p[0], len_d0, (const W *)p[1], len_d1, (const double *)p[2], len_keys, per_key, (W *)p[3],
-                           len_out, s);
+    return handle_call(h->guard, h->fft->device, form, bufs, s, [&](void *const *p, hipStream_t st) {
+        return cmux_nodes<W>(h, (const W *)p[0], (const W *)p[1], (const double2 *)p[2], (W *)p[3], count,
+                             CmuxNodes{h->glwe, 0, per_key, h->key_len, 0}, st);
     });
 }
 
@@ -291,11 +255,14 @@ bool tree_lengths_ok(const TfheCmuxTreeCore<W> *h, size_t len_table, size_t len_
     return len_selectors == batch * h->depth * h->key_len && (shared || len_table == batch * leaves);
 }
 
+// the refusals of the CMUX, in its order
 template <class W>
-int cmux_tree_dev(TfheCmuxTreeCore<W> *h, const W *table, size_t len_table, const double *selectors, size_t len_selectors, W *out,
-                  size_t len_out, hipStream_t s) {
+int cmux_tree(Form form, TfheCmuxTreeCore<W> *h, const W *table, size_t len_table, const double *selectors, size_t len_selectors,
+              W *out, size_t len_out, hipStream_t s) {
     if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
+    if (form == Form::kHost && ((!table && len_table) || (!selectors && len_selectors) || (!out && len_out)))
+        return PFHE_ERR_BAD_ARGUMENT;
     u64 batch = 0;
     bool shared = false;
     if (!tree_lengths_ok(h, len_table, len_selectors, len_out, batch, shared)) {
@@ -303,54 +270,37 @@ int cmux_tree_dev(TfheCmuxTreeCore<W> *h, const W *table, size_t len_table, cons
         return PFHE_ERR_BAD_LENGTH;
     }
     if (batch == 0) return PFHE_OK;
-    if (!table || !selectors || !out) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(table);
-    PFHE_REQUIRE_ALIGNED(selectors);
-    PFHE_REQUIRE_ALIGNED(out);
-    if (overlaps(table, len_table * sizeof(W), out, len_out * sizeof(W)) ||
-        overlaps(selectors, len_selectors * sizeof(double2), out, len_out * sizeof(W))) {
-        set_last_error("TFHE CMUX tree: the output must not overlap an input");
-        return PFHE_ERR_BAD_ARGUMENT;
+    if (form == Form::kDevice) {
+        if (!table || !selectors || !out) return PFHE_ERR_BAD_ARGUMENT;
+        PFHE_REQUIRE_ALIGNED(table);
+        PFHE_REQUIRE_ALIGNED(selectors);
+        PFHE_REQUIRE_ALIGNED(out);
+        if (overlaps(table, len_table * sizeof(W), out, len_out * sizeof(W)) ||
+            overlaps(selectors, len_selectors * sizeof(double2), out, len_out * sizeof(W))) {
+            set_last_error("TFHE CMUX tree: the output must not overlap an input");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
     }
-    DeviceGuard g(h->fft->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
     const u32 d = h->depth;
     const size_t glwe = h->glwe;
-    return ordered_on(h->guard, s, [&]() -> int {
+    const StageBuf bufs[] = {stage_in(table, len_table * sizeof(W)), stage_in(selectors, len_selectors * sizeof(double2)),
+                             stage_out(out, len_out * sizeof(W))};
+    return handle_call(h->guard, h->fft->device, form, bufs, s, [&](void *const *p, hipStream_t st) -> int {
+        const W *leaves = (const W *)p[0];
         // chunk after chunk; every level of a chunk is queued before the next chunk starts
         for (u64 done = 0; done < batch; done += h->chunk) {
             const u64 cur = std::min<u64>(h->chunk, batch - done);
-            const double2 *keys = (const double2 *)selectors + done * d * h->key_len;
-            const W *src = shared ? table : table + (done << d) * glwe;
+            const double2 *keys = (const double2 *)p[1] + done * d * h->key_len;
+            const W *src = shared ? leaves : leaves + (done << d) * glwe;
             for (u32 j = 0; j < d; ++j) {
                 const u64 per_input = 1ull << (d - 1 - j);
-                W *dst = j + 1 == d ? out + done * glwe : h->node[j & 1];
+                W *dst = j + 1 == d ? (W *)p[2] + done * glwe : h->node[j & 1];
                 const CmuxNodes at{2 * glwe, 0, per_input, (u64)d * h->key_len, j == 0 && shared ? (u32)per_input : 0u};
-                PFHE_TRY(cmux_nodes<W>(h, src, src + glwe, keys + j * h->key_len, dst, cur * per_input, at, s));
+                PFHE_TRY(cmux_nodes<W>(h, src, src + glwe, keys + j * h->key_len, dst, cur * per_input, at, st));
                 src = dst;
             }
         }
         return PFHE_OK;
-    });
-}
-
-template <class W>
-int cmux_tree_host(TfheCmuxTreeCore<W> *h, const W *table, size_t len_table, const double *selectors, size_t len_selectors, W *out,
-                   size_t len_out) {
-    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h->guard, kCmuxBusy);
-    if ((!table && len_table) || (!selectors && len_selectors) || (!out && len_out)) return PFHE_ERR_BAD_ARGUMENT;
-    u64 batch = 0;
-    bool shared = false;
-    if (!tree_lengths_ok(h, len_table, len_selectors, len_out, batch, shared)) {
-        set_last_error(kTreeLengths);
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    if (batch == 0) return PFHE_OK;
-    const StageBuf bufs[] = {stage_in(table, len_table * sizeof(W)), stage_in(selectors, len_selectors * sizeof(double2)),
-                             stage_out(out, len_out * sizeof(W))};
-    return staged_call(h->fft->device, bufs, [&](void *const *p, hipStream_t s) {
-        return cmux_tree_dev<W>(h, (const W *)p[0], len_table, (const double *)p[1], len_selectors, (W *)p[2], len_out, s);
     });
 }
 
@@ -375,27 +325,28 @@ size_t pfhe_tfhe_cmux_tree_scratch_bytes(const pfhe_tfhe_cmux_tree_handle *h) { 
 int pfhe_tfhe_cmux_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0_dev, size_t len_d0, const uint64_t *d1_dev, size_t len_d1,
                        const double *keys_dev, size_t len_keys, size_t per_key, uint64_t *out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return cmux_dev<u64>(h, (const u64 *)d0_dev, len_d0, (const u64 *)d1_dev, len_d1, keys_dev, len_keys, per_key, (u64 *)out_dev,
-                         len_out, (hipStream_t)stream);
+    return cmux<u64>(Form::kDevice, h, (const u64 *)d0_dev, len_d0, (const u64 *)d1_dev, len_d1, keys_dev, len_keys, per_key,
+                     (u64 *)out_dev, len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_cmux(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0, size_t len_d0, const uint64_t *d1, size_t len_d1, const double *keys,
                    size_t len_keys, size_t per_key, uint64_t *out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return cmux_host<u64>(h, (const u64 *)d0, len_d0, (const u64 *)d1, len_d1, keys, len_keys, per_key, (u64 *)out, len_out);
+    return cmux<u64>(Form::kHost, h, (const u64 *)d0, len_d0, (const u64 *)d1, len_d1, keys, len_keys, per_key, (u64 *)out, len_out,
+                     nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_cmux_tree_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table_dev, size_t len_table, const double *selectors_dev,
                             size_t len_selectors, uint64_t *out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return cmux_tree_dev<u64>(h, (const u64 *)table_dev, len_table, selectors_dev, len_selectors, (u64 *)out_dev, len_out,
-                              (hipStream_t)stream);
+    return cmux_tree<u64>(Form::kDevice, h, (const u64 *)table_dev, len_table, selectors_dev, len_selectors, (u64 *)out_dev,
+                          len_out, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_cmux_tree(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table, size_t len_table, const double *selectors,
                         size_t len_selectors, uint64_t *out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return cmux_tree_host<u64>(h, (const u64 *)table, len_table, selectors, len_selectors, (u64 *)out, len_out);
+    return cmux_tree<u64>(Form::kHost, h, (const u64 *)table, len_table, selectors, len_selectors, (u64 *)out, len_out, nullptr);
     PFHE_GUARD_END
 }
 
@@ -412,25 +363,27 @@ int pfhe_tfhe32_cmux_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0_dev
                          const double *keys_dev, size_t len_keys, size_t per_key, uint32_t *out_dev, size_t len_out,
                          void *stream) {
     PFHE_GUARD_BEGIN
-    return cmux_dev<u32>(h, d0_dev, len_d0, d1_dev, len_d1, keys_dev, len_keys, per_key, out_dev, len_out, (hipStream_t)stream);
+    return cmux<u32>(Form::kDevice, h, d0_dev, len_d0, d1_dev, len_d1, keys_dev, len_keys, per_key, out_dev, len_out,
+                     (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_cmux(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0, size_t len_d0, const uint32_t *d1, size_t len_d1,
                      const double *keys, size_t len_keys, size_t per_key, uint32_t *out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return cmux_host<u32>(h, d0, len_d0, d1, len_d1, keys, len_keys, per_key, out, len_out);
+    return cmux<u32>(Form::kHost, h, d0, len_d0, d1, len_d1, keys, len_keys, per_key, out, len_out, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_cmux_tree_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table_dev, size_t len_table, const double *selectors_dev,
                               size_t len_selectors, uint32_t *out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
-    return cmux_tree_dev<u32>(h, table_dev, len_table, selectors_dev, len_selectors, out_dev, len_out, (hipStream_t)stream);
+    return cmux_tree<u32>(Form::kDevice, h, table_dev, len_table, selectors_dev, len_selectors, out_dev, len_out,
+                          (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_cmux_tree(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
                           size_t len_selectors, uint32_t *out, size_t len_out) {
     PFHE_GUARD_BEGIN
-    return cmux_tree_host<u32>(h, table, len_table, selectors, len_selectors, out, len_out);
+    return cmux_tree<u32>(Form::kHost, h, table, len_table, selectors, len_selectors, out, len_out, nullptr);
     PFHE_GUARD_END
 }
 

@@ -429,10 +429,27 @@ constexpr const char *kPlanBusy = "TFHE product plan in use by another thread (o
 // the shape on which the fused product and the whole-loop rotations run: it follows N and k alone
 inline bool fused_shape(const Shape &sh) { return sh.k == 1 && sh.log_n <= kFusedMaxLogN; }
 
-// P: a C handle (pfhe_tfhe{,32}_plan) or the core itself (the plan a rotation owns)
+// the launches of the general product on `cur` ciphertexts behind the Hermitian parts in t.keyh: the digit transforms
+// into t.spec, `mulacc` (the multiply-accumulate of the caller's form, which fills t.acc), the inverses into out
+template <class W, class MulAcc>
+int general_product(const pfhe_fft &f, const Shape &sh, const TfheProductScratch &t, const W *in, W *out, u64 cur, hipStream_t s,
+                    MulAcc mulacc) {
+    const u32 rows = sh.k + 1;
+    PFHE_TRY(launch_groups(tfhe_digit_fwd_kernel<W>, cur * rows * sh.ell, lds_bytes(f.log_n), s, in, t.spec, f.tw, sh));
+    PFHE_TRY(mulacc(cur * rows * (f.n / 2)));
+    return launch_groups(fft_inverse_kernel<W, false>, cur * rows, lds_bytes(f.log_n), s, t.acc, out, f.tw, f.log_n);
+}
+
+}  // namespace
+
+// What the CMUX handle (pfhe_cmux.hip) shares with the handles of this file: the create of a plan and the product's launches
+// (declared in pfhe_tfhe_handles.hpp, instantiated at the end of this file)
+namespace pfhe {
+
+// P: a C handle (pfhe_tfhe{,32}_plan) or the core itself (the plan a rotation or a CMUX handle owns)
 template <class W, class P>
-int plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t chunk,
-                P **out) {
+int tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t chunk,
+                     P **out) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     Shape sh{};
@@ -450,19 +467,8 @@ int plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, 
     return PFHE_OK;
 }
 
-// the launches of the general product on `cur` ciphertexts behind the Hermitian parts in t.keyh: the digit transforms
-// into t.spec, `mulacc` (the multiply-accumulate of the caller's form, which fills t.acc), the inverses into out
-template <class W, class MulAcc>
-int general_product(const pfhe_fft &f, const Shape &sh, const TfheProductScratch &t, const W *in, W *out, u64 cur, hipStream_t s,
-                    MulAcc mulacc) {
-    const u32 rows = sh.k + 1;
-    PFHE_TRY(launch_groups(tfhe_digit_fwd_kernel<W>, cur * rows * sh.ell, lds_bytes(f.log_n), s, in, t.spec, f.tw, sh));
-    PFHE_TRY(mulacc(cur * rows * (f.n / 2)));
-    return launch_groups(fft_inverse_kernel<W, false>, cur * rows, lds_bytes(f.log_n), s, t.acc, out, f.tw, f.log_n);
-}
-
 template <class W>
-int product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *out, u64 batch, hipStream_t s) {
+int tfhe_product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *out, u64 batch, hipStream_t s) {
     const pfhe_fft &f = *p->fft;
     const Shape &sh = p->shape;
     const TfheProductScratch &t = p->scratch;
@@ -484,48 +490,44 @@ int product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *out, u6
     return PFHE_OK;
 }
 
+}  // namespace pfhe
+
+namespace {
+
+// The host form refuses a null pointer before the lengths, and a wrong length without a message; the device form's
+// pointer tests follow the empty batch.
 template <class W>
-int product_dev(TfhePlanCore<W> *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out,
-                hipStream_t s) {
+int product(Form form, TfhePlanCore<W> *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out,
+            size_t len_out, hipStream_t s) {
     if (!p || !p->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(p->guard, kPlanBusy);
+    if (form == Form::kHost && ((!in && len_in) || (!key && len_key) || (!out && len_out))) return PFHE_ERR_BAD_ARGUMENT;
     const pfhe_fft &f = *p->fft;
     const size_t rows = p->shape.k + 1, glwe = rows * f.n, key_len = rows * p->shape.ell * rows * f.n;
     if (len_in % glwe != 0 || len_out != len_in || len_key != key_len) {
-        set_last_error("TFHE external product: input / output must be batch*(k+1)*N words and the key "
-                       "(k+1)*ell*(k+1)*N complex values");
+        if (form == Form::kDevice)
+            set_last_error("TFHE external product: input / output must be batch*(k+1)*N words and the key "
+                           "(k+1)*ell*(k+1)*N complex values");
         return PFHE_ERR_BAD_LENGTH;
     }
     const u64 batch = len_in / glwe;
     if (batch == 0) return PFHE_OK;
-    if (!in || !key || !out) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(in);
-    PFHE_REQUIRE_ALIGNED(key);
-    PFHE_REQUIRE_ALIGNED(out);
-    // in place is safe: the fused form reads a ciphertext wholly before its workgroup writes it, the general form reads a
-    // chunk's input in the digit launch and writes its output in the inverse launch
-    if (in != out && overlaps(in, len_in * sizeof(W), out, len_out * sizeof(W))) {
-        set_last_error("TFHE external product: input and output must be the same buffer or disjoint");
-        return PFHE_ERR_BAD_ARGUMENT;
+    if (form == Form::kDevice) {
+        if (!in || !key || !out) return PFHE_ERR_BAD_ARGUMENT;
+        PFHE_REQUIRE_ALIGNED(in);
+        PFHE_REQUIRE_ALIGNED(key);
+        PFHE_REQUIRE_ALIGNED(out);
+        // in place is safe: the fused form reads a ciphertext wholly before its workgroup writes it, the general form reads
+        // a chunk's input in the digit launch and writes its output in the inverse launch
+        if (in != out && overlaps(in, len_in * sizeof(W), out, len_out * sizeof(W))) {
+            set_last_error("TFHE external product: input and output must be the same buffer or disjoint");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
     }
-    DeviceGuard g(f.device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return ordered_on(p->guard, s, [&] { return product_impl<W>(p, in, (const double2 *)key, out, batch, s); });
-}
-
-template <class W>
-int product_host(TfhePlanCore<W> *p, const W *in, size_t len_in, const double *key, size_t len_key, W *out, size_t len_out) {
-    if (!p || !p->fft) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(p->guard, kPlanBusy);
-    if ((!in && len_in) || (!key && len_key) || (!out && len_out)) return PFHE_ERR_BAD_ARGUMENT;
-    const pfhe_fft &f = *p->fft;
-    const size_t rows = p->shape.k + 1, glwe = rows * f.n, key_len = rows * p->shape.ell * rows * f.n;
-    if (len_in % glwe != 0 || len_out != len_in || len_key != key_len) return PFHE_ERR_BAD_LENGTH;
-    if (len_in == 0) return PFHE_OK;
     const StageBuf bufs[] = {stage_in(in, len_in * sizeof(W)), stage_in(key, len_key * sizeof(double2)),
                              stage_out(out, len_out * sizeof(W))};
-    return staged_call(f.device, bufs, [&](void *const *d, hipStream_t s) {
-        return product_dev<W>(p, (const W *)d[0], len_in, (const double *)d[1], len_key, (W *)d[2], len_out, s);
+    return handle_call(p->guard, f.device, form, bufs, s, [&](void *const *d, hipStream_t st) {
+        return tfhe_product_impl<W>(p, (const W *)d[0], (const double2 *)d[1], (W *)d[2], batch, st);
     });
 }
 
@@ -594,15 +596,15 @@ int torus_monomial_each(const pfhe_fft *f, const W *a, size_t len, const uint32_
     return torus_glue<W>(*f, TorusGlue::kMonomial, a, nullptr, nullptr, out, exps, 1, (u32)polys_per_exp, len / unit, s);
 }
 
-// plan_create's checks in plan_create's order (the handle's plan IS a product plan), then the form: the whole-loop kernel
-// on the product's fused shape unless PFHE_DISABLE_FUSED_TFHE_BLINDROT is set when the handle is created
+// tfhe_plan_create's checks in its order (the handle's plan IS a product plan), then the form: the whole-loop kernel on
+// the product's fused shape unless PFHE_DISABLE_FUSED_TFHE_BLINDROT is set when the handle is created
 template <class W, class H>
 int tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                          size_t chunk, H **out) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
-    PFHE_TRY(plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->plan));
+    PFHE_TRY(tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->plan));
     const TfhePlanCore<W> &p = *h->plan;
     h->fft = fft;
     h->glwe = (size_t)(p.shape.k + 1) * fft->n;
@@ -645,7 +647,7 @@ int tfhe_blindrot_chunk(TfheBlindRotCore<W> *h, W *a0, const double2 *bsk, const
         PFHE_TRY(torus_glue<W>(f, TorusGlue::kFirst, a0, nullptr, nullptr, h->d, ex, (u32)n_steps, rows, cur, s));
     }
     for (u64 i = 0; i < n_steps; ++i) {
-        PFHE_TRY(product_impl<W>(h->plan, h->d, bsk + i * h->key_len, h->e, cur, s));
+        PFHE_TRY(tfhe_product_impl<W>(h->plan, h->d, bsk + i * h->key_len, h->e, cur, s));
         W *dst = src == a0 ? h->ping : a0;
         PFHE_TRY(i + 1 < n_steps
                      ? torus_glue<W>(f, TorusGlue::kStep, src, h->e, dst, h->d, ex + i + 1, (u32)n_steps, rows, cur, s)
@@ -655,11 +657,17 @@ int tfhe_blindrot_chunk(TfheBlindRotCore<W> *h, W *a0, const double2 *bsk, const
     return PFHE_OK;
 }
 
+// The host form refuses a null pointer and an exponent of 2N or more before the lengths (the device form takes the
+// exponents modulo 2N); the device form's pointer tests follow the empty batch and the cap on the steps.
 template <class W>
-int tfhe_blindrot_dev(TfheBlindRotCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
-                      size_t len_exps, hipStream_t s) {
+int tfhe_blindrot(Form form, TfheBlindRotCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+                  const uint32_t *exps, size_t len_exps, hipStream_t s) {
     if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kBlindRotBusy);
+    if (form == Form::kHost) {
+        if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
+        PFHE_TRY(require_exps_below_2n(exps, len_exps, h->fft->n, "TFHE blind rotation: every exponent must be below 2N"));
+    }
     if (len_acc % h->glwe != 0 || len_bsk % h->key_len != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->key_len)) {
         set_last_error(kBlindRotLengths);
         return PFHE_ERR_BAD_LENGTH;
@@ -667,38 +675,21 @@ int tfhe_blindrot_dev(TfheBlindRotCore<W> *h, W *acc, size_t len_acc, const doub
     const u64 batch = len_acc / h->glwe, n_steps = len_bsk / h->key_len;
     if (batch == 0 || n_steps == 0) return PFHE_OK;
     if (n_steps > 0xffffffffull) return PFHE_ERR_BAD_LENGTH;
-    if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(acc);
-    PFHE_REQUIRE_ALIGNED(bsk);
-    DeviceGuard g(h->fft->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return ordered_on(h->guard, s, [&]() -> int {
+    if (form == Form::kDevice) {
+        if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
+        PFHE_REQUIRE_ALIGNED(acc);
+        PFHE_REQUIRE_ALIGNED(bsk);
+    }
+    const StageBuf bufs[] = {stage_inout(acc, len_acc * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
+                             stage_in(exps, len_exps * sizeof(uint32_t))};
+    return handle_call(h->guard, h->fft->device, form, bufs, s, [&](void *const *d, hipStream_t st) -> int {
         // chunk after chunk; every step of a chunk runs before the next chunk starts
         for (u64 done = 0; done < batch; done += h->chunk) {
             const u64 cur = std::min<u64>(h->chunk, batch - done);
-            PFHE_TRY(tfhe_blindrot_chunk<W>(h, acc + done * h->glwe, (const double2 *)bsk, exps + done * n_steps, n_steps, cur, s));
+            PFHE_TRY(tfhe_blindrot_chunk<W>(h, (W *)d[0] + done * h->glwe, (const double2 *)d[1],
+                                            (const uint32_t *)d[2] + done * n_steps, n_steps, cur, st));
         }
         return PFHE_OK;
-    });
-}
-
-// host form: every exponent must be below 2N
-template <class W>
-int tfhe_blindrot_host(TfheBlindRotCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
-                       size_t len_exps) {
-    if (!h || !h->plan) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h->guard, kBlindRotBusy);
-    if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_TRY(require_exps_below_2n(exps, len_exps, h->fft->n, "TFHE blind rotation: every exponent must be below 2N"));
-    if (len_acc % h->glwe != 0 || len_bsk % h->key_len != 0 || len_exps != (len_acc / h->glwe) * (len_bsk / h->key_len)) {
-        set_last_error(kBlindRotLengths);
-        return PFHE_ERR_BAD_LENGTH;
-    }
-    if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
-    const StageBuf bufs[] = {stage_inout(acc, len_acc * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
-                             stage_in(exps, len_exps * sizeof(uint32_t))};
-    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
-        return tfhe_blindrot_dev<W>(h, (W *)d[0], len_acc, (const double *)d[1], len_bsk, (const uint32_t *)d[2], len_exps, s);
     });
 }
 
@@ -772,11 +763,16 @@ bool mbrot_lengths_ok(const TfheMultiBitCore<W> *h, size_t len_acc, size_t len_b
     return len_exps == batch * groups * h->g;
 }
 
+// the refusals of the classic rotation, in its order
 template <class W>
-int tfhe_mbrot_dev(TfheMultiBitCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
-                   size_t len_exps, hipStream_t s) {
+int tfhe_mbrot(Form form, TfheMultiBitCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk,
+               const uint32_t *exps, size_t len_exps, hipStream_t s) {
     if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
     PFHE_PLAN_LEASE(h->guard, kMbRotBusy);
+    if (form == Form::kHost) {
+        if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
+        PFHE_TRY(require_exps_below_2n(exps, len_exps, h->fft->n, "TFHE multi-bit blind rotation: every exponent must be below 2N"));
+    }
     u64 batch = 0, groups = 0;
     if (!mbrot_lengths_ok(h, len_acc, len_bsk, len_exps, batch, groups)) {
         set_last_error(kMbRotLengths);
@@ -784,32 +780,15 @@ int tfhe_mbrot_dev(TfheMultiBitCore<W> *h, W *acc, size_t len_acc, const double 
     }
     if (batch == 0 || groups == 0) return PFHE_OK;
     if (groups * h->g > 0xffffffffull) return PFHE_ERR_BAD_LENGTH;
-    if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_REQUIRE_ALIGNED(acc);
-    PFHE_REQUIRE_ALIGNED(bsk);
-    DeviceGuard g(h->fft->device);
-    if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    return ordered_on(h->guard, s, [&] { return tfhe_mbrot_impl<W>(h, acc, (const double2 *)bsk, exps, batch, groups, s); });
-}
-
-// host form: every exponent must be below 2N
-template <class W>
-int tfhe_mbrot_host(TfheMultiBitCore<W> *h, W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
-                    size_t len_exps) {
-    if (!h || !h->fft) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_PLAN_LEASE(h->guard, kMbRotBusy);
-    if ((!acc && len_acc) || (!bsk && len_bsk) || (!exps && len_exps)) return PFHE_ERR_BAD_ARGUMENT;
-    PFHE_TRY(require_exps_below_2n(exps, len_exps, h->fft->n, "TFHE multi-bit blind rotation: every exponent must be below 2N"));
-    u64 batch = 0, groups = 0;
-    if (!mbrot_lengths_ok(h, len_acc, len_bsk, len_exps, batch, groups)) {
-        set_last_error(kMbRotLengths);
-        return PFHE_ERR_BAD_LENGTH;
+    if (form == Form::kDevice) {
+        if (!acc || !bsk || !exps) return PFHE_ERR_BAD_ARGUMENT;
+        PFHE_REQUIRE_ALIGNED(acc);
+        PFHE_REQUIRE_ALIGNED(bsk);
     }
-    if (len_acc == 0 || len_bsk == 0) return PFHE_OK;
     const StageBuf bufs[] = {stage_inout(acc, len_acc * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
                              stage_in(exps, len_exps * sizeof(uint32_t))};
-    return staged_call(h->fft->device, bufs, [&](void *const *d, hipStream_t s) {
-        return tfhe_mbrot_dev<W>(h, (W *)d[0], len_acc, (const double *)d[1], len_bsk, (const uint32_t *)d[2], len_exps, s);
+    return handle_call(h->guard, h->fft->device, form, bufs, s, [&](void *const *d, hipStream_t st) {
+        return tfhe_mbrot_impl<W>(h, (W *)d[0], (const double2 *)d[1], (const uint32_t *)d[2], batch, groups, st);
     });
 }
 
@@ -852,12 +831,12 @@ int mb_combine_key_dev(const pfhe_fft *f, size_t glwe_dimension, size_t decompos
 template <class W>
 int TfheBlindRotCore<W>::rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
                                     size_t len_exps, hipStream_t s) {
-    return tfhe_blindrot_dev<W>(this, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+    return tfhe_blindrot<W>(Form::kDevice, this, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
 }
 template <class W>
 int TfheMultiBitCore<W>::rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps,
                                     size_t len_exps, hipStream_t s) {
-    return tfhe_mbrot_dev<W>(this, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
+    return tfhe_mbrot<W>(Form::kDevice, this, acc, len_acc, bsk, len_bsk, exps, len_exps, s);
 }
 
 namespace pfhe {
@@ -880,6 +859,12 @@ template int tfhe_rotation_create<u64>(const pfhe_fft *, size_t, uint32_t, size_
                                        TfheRotation<u64> **);
 template int tfhe_rotation_create<u32>(const pfhe_fft *, size_t, uint32_t, size_t, std::optional<size_t>, size_t,
                                        TfheRotation<u32> **);
+
+// ... and what pfhe_cmux.hip takes of the product: the create of the plan it owns and the launches
+template int tfhe_plan_create<u64>(const pfhe_fft *, size_t, uint32_t, size_t, size_t, TfhePlanCore<u64> **);
+template int tfhe_plan_create<u32>(const pfhe_fft *, size_t, uint32_t, size_t, size_t, TfhePlanCore<u32> **);
+template int tfhe_product_impl<u64>(TfhePlanCore<u64> *, const u64 *, const double2 *, u64 *, u64, hipStream_t);
+template int tfhe_product_impl<u32>(TfhePlanCore<u32> *, const u32 *, const double2 *, u32 *, u64, hipStream_t);
 
 }  // namespace pfhe
 
@@ -985,7 +970,7 @@ int pfhe_fft_inverse_torus32_slice(const pfhe_fft *fft, const double *input, siz
 int pfhe_tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                           size_t chunk, pfhe_tfhe_plan **out) {
     PFHE_GUARD_BEGIN
-    return plan_create<u64>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
+    return tfhe_plan_create<u64>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe_plan_destroy(pfhe_tfhe_plan *plan) { delete plan; }
@@ -997,21 +982,21 @@ int pfhe_tfhe_external_product_to_dev(pfhe_tfhe_plan *plan, const uint64_t *inpu
                                       const double *key_dev, size_t len_key, uint64_t *output_dev, size_t len_output,
                                       void *stream) {
     PFHE_GUARD_BEGIN
-    return product_dev<u64>(plan, (const u64 *)input_dev, len_input, key_dev, len_key, (u64 *)output_dev, len_output,
+    return product<u64>(Form::kDevice, plan, (const u64 *)input_dev, len_input, key_dev, len_key, (u64 *)output_dev, len_output,
                             (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_external_product_to(pfhe_tfhe_plan *plan, const uint64_t *input, size_t len_input, const double *key,
                                   size_t len_key, uint64_t *output, size_t len_output) {
     PFHE_GUARD_BEGIN
-    return product_host<u64>(plan, (const u64 *)input, len_input, key, len_key, (u64 *)output, len_output);
+    return product<u64>(Form::kHost, plan, (const u64 *)input, len_input, key, len_key, (u64 *)output, len_output, nullptr);
     PFHE_GUARD_END
 }
 
 int pfhe_tfhe32_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                             size_t chunk, pfhe_tfhe32_plan **out) {
     PFHE_GUARD_BEGIN
-    return plan_create<u32>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
+    return tfhe_plan_create<u32>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_plan_destroy(pfhe_tfhe32_plan *plan) { delete plan; }
@@ -1023,13 +1008,13 @@ int pfhe_tfhe32_external_product_to_dev(pfhe_tfhe32_plan *plan, const uint32_t *
                                         const double *key_dev, size_t len_key, uint32_t *output_dev, size_t len_output,
                                         void *stream) {
     PFHE_GUARD_BEGIN
-    return product_dev<u32>(plan, input_dev, len_input, key_dev, len_key, output_dev, len_output, (hipStream_t)stream);
+    return product<u32>(Form::kDevice, plan, input_dev, len_input, key_dev, len_key, output_dev, len_output, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_external_product_to(pfhe_tfhe32_plan *plan, const uint32_t *input, size_t len_input, const double *key,
                                     size_t len_key, uint32_t *output, size_t len_output) {
     PFHE_GUARD_BEGIN
-    return product_host<u32>(plan, input, len_input, key, len_key, output, len_output);
+    return product<u32>(Form::kHost, plan, input, len_input, key, len_key, output, len_output, nullptr);
     PFHE_GUARD_END
 }
 
@@ -1045,13 +1030,13 @@ size_t pfhe_tfhe_blindrot_scratch_bytes(const pfhe_tfhe_blindrot *h) { return h 
 int pfhe_tfhe_blindrot_rotate_dev(pfhe_tfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev,
                                   size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
-    return tfhe_blindrot_dev<u64>(h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    return tfhe_blindrot<u64>(Form::kDevice, h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_blindrot_rotate(pfhe_tfhe_blindrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
                               const uint32_t *exps, size_t len_exps) {
     PFHE_GUARD_BEGIN
-    return tfhe_blindrot_host<u64>(h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps);
+    return tfhe_blindrot<u64>(Form::kHost, h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint64_t *a_dev, size_t len, const uint32_t *exps_dev,
@@ -1074,13 +1059,13 @@ size_t pfhe_tfhe32_blindrot_scratch_bytes(const pfhe_tfhe32_blindrot *h) { retur
 int pfhe_tfhe32_blindrot_rotate_dev(pfhe_tfhe32_blindrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev,
                                     size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
-    return tfhe_blindrot_dev<u32>(h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    return tfhe_blindrot<u32>(Form::kDevice, h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_blindrot_rotate(pfhe_tfhe32_blindrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
                                 const uint32_t *exps, size_t len_exps) {
     PFHE_GUARD_BEGIN
-    return tfhe_blindrot_host<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps);
+    return tfhe_blindrot<u32>(Form::kHost, h, acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_dev, size_t len, const uint32_t *exps_dev,
@@ -1102,13 +1087,13 @@ size_t pfhe_tfhe_mbrot_scratch_bytes(const pfhe_tfhe_mbrot *h) { return h ? h->s
 int pfhe_tfhe_mbrot_rotate_dev(pfhe_tfhe_mbrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
                                const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
-    return tfhe_mbrot_dev<u64>(h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    return tfhe_mbrot<u64>(Form::kDevice, h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_mbrot_rotate(pfhe_tfhe_mbrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
                            const uint32_t *exps, size_t len_exps) {
     PFHE_GUARD_BEGIN
-    return tfhe_mbrot_host<u64>(h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps);
+    return tfhe_mbrot<u64>(Form::kHost, h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
@@ -1123,13 +1108,13 @@ size_t pfhe_tfhe32_mbrot_scratch_bytes(const pfhe_tfhe32_mbrot *h) { return h ? 
 int pfhe_tfhe32_mbrot_rotate_dev(pfhe_tfhe32_mbrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
                                  const uint32_t *exps_dev, size_t len_exps, void *stream) {
     PFHE_GUARD_BEGIN
-    return tfhe_mbrot_dev<u32>(h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
+    return tfhe_mbrot<u32>(Form::kDevice, h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
     PFHE_GUARD_END
 }
 int pfhe_tfhe32_mbrot_rotate(pfhe_tfhe32_mbrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
                              const uint32_t *exps, size_t len_exps) {
     PFHE_GUARD_BEGIN
-    return tfhe_mbrot_host<u32>(h, acc, len_acc, bsk, len_bsk, exps, len_exps);
+    return tfhe_mbrot<u32>(Form::kHost, h, acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
     PFHE_GUARD_END
 }
 int pfhe_tfhe_mb_combine_key_dev(const pfhe_fft *fft, size_t glwe_dimension, size_t decompose_length, size_t grouping_factor,

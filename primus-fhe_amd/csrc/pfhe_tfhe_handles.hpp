@@ -1,8 +1,9 @@
 // pfhe_tfhe_handles.hpp — what the torus-side handles own: the FFT table, the TFHE product plan, and the two blind
 // rotations behind the one interface the bootstrap handle holds (TfheRotation); and the argument checks their creates
-// share.  pfhe_fft.hip implements them; pfhe_bootstrap.hip sees a rotation only as a TfheRotation; pfhe_keygen.hip, which
-// writes the keys they consume, starts its GGSW calls with the plan's checks.  Host only; the host layer under the entry
-// points of all three is pfhe_tfhe_host.hpp.
+// share.  pfhe_fft.hip implements them; pfhe_bootstrap.hip and pfhe_cbs.hip see a rotation only as a TfheRotation;
+// pfhe_cmux.hip owns a product plan and queues the product's launches itself; pfhe_keygen.hip, which writes the keys they
+// consume, starts its GGSW calls with the plan's checks.  Host only; the host layer under the entry points of all of them
+// is pfhe_tfhe_host.hpp.
 #pragma once
 
 #include <optional>
@@ -176,5 +177,14 @@ int tfhe_mbrot_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
 template <class W>
 int tfhe_rotation_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                          std::optional<size_t> grouping_factor, size_t chunk, TfheRotation<W> **out);
+
+// The product plan a handle owns (pfhe_fft.hip, instantiated for P = TfhePlanCore<W>, u32 and u64): what
+// pfhe_tfhe{,32}_plan_create runs, and the product's launches on `batch` ciphertexts, arguments already checked and the
+// device current.  The owner calls the launches inside its own ordered_on; the plan's own guard stays unused.
+template <class W, class P>
+int tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t chunk,
+                     P **out);
+template <class W>
+int tfhe_product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *out, u64 batch, hipStream_t s);
 
 }  // namespace pfhe

@@ -1,11 +1,24 @@
 // pfhe_tfhe_host.hpp — the host layer under every torus entry point (pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip,
-// pfhe_pack.hip, pfhe_pack_fft.hip): the constants and range tests they share, the launch of a torus kernel, and the one tail of the
-// stateless steps.  Host only.  What is not torus-specific lives in pfhe_staging.hpp, for the RNS side too: StageBuf and
-// stage_in / _out / _inout, staged_call (the staged run of a launch on host pointers), Form and form_call, refuse_null,
-// overlaps, require_exps_below_2n.
+// pfhe_pack.hip, pfhe_pack_fft.hip, pfhe_cbs.hip, pfhe_cmux.hip): the constants and range tests they share, the launch of a
+// torus kernel, and the two tails: stateless_call of the stateless steps, handle_call of the calls on a handle.  Host only.
+// What is not torus-specific lives in pfhe_staging.hpp, for the RNS side too: StageBuf and stage_in / _out / _inout,
+// staged_call (the staged run of a launch on host pointers), Form and form_call, refuse_null, overlaps,
+// require_exps_below_2n; the lease and the stream order of a handle live in pfhe_plan_guard.hpp.
 //
-// A handle call (product, rotations, bootstrap) writes its checks in its device form; its host form re-enters that under
-// the handle's lease through staged_call.  A stateless step is ONE function template for both of its forms:
+// A handle call (product, rotations, bootstrap, circuit bootstrap, CMUX and its tree) is ONE function template for both
+// of its forms:
+//    1. it takes the Form (the extern "C" wrappers pass Form::kHost with a null stream, or Form::kDevice);
+//    2. it refuses a null handle and takes the handle's lease (PFHE_PLAN_LEASE), once;
+//    3. it runs its own checks inline, in its own order; where the two forms refuse differently (a null pointer before or
+//       after the lengths, the exponents below 2N, alignment and overlap of device pointers) the line names `form`;
+//    4. it returns PFHE_OK for an empty batch;
+//    5. it lists its buffers as StageBufs and hands them to handle_call with the handle's guard, the table's device, the
+//       stream and a callback (pointers, stream) that queues every launch of the call.
+// handle_call is form_call with the launch under ordered_on: a device that cannot be made current is refused, the host form
+// stages, and the launches run behind the handle's last call on whichever stream they are given.  DESIGN.md §16 lists
+// every call's refusals in order.
+//
+// A stateless step is ONE function template for both of its forms:
 //    1. it takes the Form (the extern "C" wrappers pass Form::kHost or Form::kDevice; a device-only step has none);
 //    2. it runs its own argument checks in the order it wants them refused (require_lwe_dimension / _glwe_dimension
 //       for the ranges), every one of them on values, none on a pointer;
@@ -23,6 +36,7 @@
 #include <algorithm>
 
 #include "pfhe_fft_device.hpp"
+#include "pfhe_plan_guard.hpp"
 #include "pfhe_staging.hpp"
 
 namespace pfhe {
@@ -101,6 +115,18 @@ int stateless_call(int device, Form form, const StageBuf (&bufs)[N], const char 
     }
     PFHE_TRY(gate());
     return form_call(device, form, bufs, s, launch);
+}
+
+// ---------------- the calls on a handle ----------------
+
+// The tail of every handle call, the lease taken, every argument checked and the batch not empty (the recipe is at the top
+// of this file): form_call whose launch runs under ordered_on(guard, ...) on the stream form_call hands it, the caller's in
+// the device form and the staging context's in the host form.
+template <size_t N, class Launch>
+int handle_call(PlanGuard &guard, int device, Form form, const StageBuf (&bufs)[N], hipStream_t s, Launch &&launch) {
+    return form_call(device, form, bufs, s, [&](void *const *d, hipStream_t st) {
+        return ordered_on(guard, st, [&] { return launch(d, st); });
+    });
 }
 
 }  // namespace pfhe

@@ -1,5 +1,5 @@
-"""What the torus entry points (csrc/pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip) share on the host side, pinned where
-the other torus tests leave it open: every host form against its device form word for word, the status and the
+"""What the torus entry points (csrc/pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip, pfhe_cbs.hip, pfhe_cmux.hip) share on
+the host side, pinned where the other torus tests leave it open: every host form against its device form word for word, the status and the
 pfhe_last_error() text of every refusal that is decided before a launch (and their order), a zero batch, and what each
 handle kind allocates.  All at N = 8 with batch 3 on handles of chunk 2, so every chunk loop runs a full and a short chunk."""
 import ctypes as C
@@ -174,6 +174,37 @@ def test_bootstrap_host_equals_device(p, bits, k, grouping):
             assert np.array_equal(host_out, host_words(dev_out, bits)) and host_out.any(), (with_ks, tvs)
 
 
+def handle_cases(p, rng, bits, k):
+    """(name, host call, device call, input arrays, words of the output) of the circuit bootstrap, the CMUX and the CMUX tree
+    on chunk-2 handles.  The CMUX handle of depth 2 launches 4 nodes at a time: 6 nodes with per_key = 3 put the second
+    key group across the launch boundary; the tree runs with a table per input and with one for the batch."""
+    fft, (basis, ks_basis) = p.FullComplex64FftTable(LOG_N), bases(p, bits)
+    cbs = p.TfheCircuitBootstrapContext(fft, basis, LWE, k, basis, ks_basis, chunk=CHUNK)
+    yield ("cbs", lambda *a: p.tfhe_circuit_bootstrap(*a, cbs), lambda *a: p.tfhe_circuit_bootstrap_dev(*a, cbs),
+           (rand_words(rng, bits, BATCH * (LWE + 1)), fourier(rng, cbs.bsk_len(), bits), rand_words(rng, bits, cbs.pfksk_len())),
+           BATCH * cbs.ggsw_len())
+    tree = p.TfheCmuxTreeContext(fft, basis, k, 2, chunk=CHUNK)
+    glwe, key, count, per_key = tree.glwe_len(), tree.key_len(), 6, 3
+    yield ("cmux", lambda *a: p.tfhe_cmux(*a, tree, per_key), lambda *a: p.tfhe_cmux_dev(*a, tree, per_key),
+           (rand_words(rng, bits, count * glwe), rand_words(rng, bits, count * glwe), fourier(rng, count // per_key * key, bits)),
+           count * glwe)
+    for tables in (BATCH, 1):
+        yield ("cmux_tree, %d table(s)" % tables, lambda *a: p.tfhe_cmux_tree(*a, tree), lambda *a: p.tfhe_cmux_tree_dev(*a, tree),
+               (rand_words(rng, bits, tables * 4 * glwe), fourier(rng, BATCH * 2 * key, bits)), BATCH * glwe)
+
+
+@pytest.mark.parametrize("bits", [32, 64])
+@pytest.mark.parametrize("k", [1, 2])                          # the fused and the general form
+def test_handle_host_equals_device(p, bits, k):
+    rng = np.random.default_rng(bits + 11 * k)
+    for name, host_call, dev_call, inputs, out_words in handle_cases(p, rng, bits, k):
+        host_out = np.zeros(out_words, m.UINT[bits])
+        dev_out = dev_words(host_out, bits)
+        host_call(*inputs, host_out)
+        dev_call(*[dev_complex(x) if x.dtype == np.complex128 else dev_words(x, bits) for x in inputs], dev_out)
+        assert np.array_equal(host_out, host_words(dev_out, bits)) and host_out.any(), name
+
+
 # ---------------- what each handle kind allocates ----------------
 #
 # scratch_bytes() and the allocations of a create (as many frees in the destroy), per width, at N = 8 (N/2 = 4 complex
@@ -247,6 +278,12 @@ BOOT_LEN = ("TFHE bootstrap: lwe_in must be batch*(n+1) words, bsk n*(k+1)*ell*(
             "without)")
 BSK_LEN = ("bootstrapping key: glwe_key must be k*N words, ggsw_torus keys*(k+1)*ell*(k+1)*N words and bsk_out as many "
            "complex values, keys = n or (n/g)*2^g")
+CBS_LEN = ("TFHE circuit bootstrap: lwe_in must be batch*(n+1) words, bsk n*(k+1)*ell*(k+1)*N complex values, pfksk "
+           "(k+1)*(k*N+1)*pfks_ell*(k+1)*N words and ggsw_out batch*(k+1)*cbs_ell*(k+1)*N")
+CMUX_LEN = ("TFHE CMUX: d0, d1 and out must be count*(k+1)*N words, count a multiple of per_key, and keys "
+            "(count/per_key)*(k+1)*ell*(k+1)*N complex values")
+TREE_LEN = ("TFHE CMUX tree: out must be batch*(k+1)*N words, selectors batch*depth keys of (k+1)*ell*(k+1)*N complex values "
+            "and table 2^depth or batch*2^depth ciphertexts")
 
 
 class Bufs:
@@ -282,7 +319,9 @@ def entry_points(p, bits):
     rot = p.TfheBlindRotateContext(fft, basis, 1, chunk=CHUNK)
     mb = p.TfheMultiBitBlindRotateContext(fft, basis, G, 1, chunk=CHUNK)
     boot = p.TfheBootstrapContext(fft, basis, LWE, 1, ks_basis, chunk=CHUNK)
-    keep = (fft, plan, rot, mb, boot)
+    cbs = p.TfheCircuitBootstrapContext(fft, basis, LWE, 1, basis, ks_basis, chunk=CHUNK)
+    tree = p.TfheCmuxTreeContext(fft, basis, 1, 2, chunk=CHUNK)
+    keep = (fft, plan, rot, mb, boot, cbs, tree)
     f, t = fft._h, "pfhe_tfhe" + w + "_"
     words = lambda count: (count, W)
     out = []
@@ -374,6 +413,27 @@ def entry_points(p, bits):
                    b.len["ksk"], None],
         lengths="key-switch key: ksk must be in_dimension*ell*(out_dimension+1) words", null_first=False,
         overlap=("ksk", "key_in", "key-switch key: the keys must not overlap ksk"))
+    sizes = {"in": words(BATCH * (LWE + 1)), "bsk": (cbs.bsk_len(), 16), "pfksk": words(cbs.pfksk_len()),
+             "out": words(BATCH * cbs.ggsw_len())}
+    circuit = lambda b: [cbs._h, b.ptr["in"], b.len["in"], b.ptr["bsk"], b.len["bsk"], b.ptr["pfksk"], b.len["pfksk"],
+                         b.ptr["out"], b.len["out"]]
+    add(cbs._pre + "_dev", True, sizes, lambda b: circuit(b) + [None], lengths=CBS_LEN, null_first=False,
+        overlap=("out", "in", "TFHE circuit bootstrap: the output must not overlap an input"), zero=("in", "out"), out="out")
+    add(cbs._pre, False, sizes, circuit, lengths=CBS_LEN, null_first=False, zero=("in", "out"), out="out")
+    sizes = {"d0": words(BATCH * glwe), "d1": words(BATCH * glwe), "keys": (BATCH * key, 16), "out": words(BATCH * glwe)}
+    cmux = lambda b: [tree._h, b.ptr["d0"], b.len["d0"], b.ptr["d1"], b.len["d1"], b.ptr["keys"], b.len["keys"], 1, b.ptr["out"],
+                      b.len["out"]]
+    add(t + "cmux_dev", True, sizes, lambda b: cmux(b) + [None], lengths=CMUX_LEN, null_first=False,
+        overlap=("out", "d0", "TFHE CMUX: out must be exactly d0, exactly d1, or disjoint from both, and disjoint from the keys"),
+        zero=("d0", "d1", "keys", "out"), out="out")
+    add(t + "cmux", False, sizes, cmux, lengths=CMUX_LEN, null_first=True, zero=("d0", "d1", "keys", "out"), out="out")
+    sizes = {"table": words(4 * glwe), "selectors": (BATCH * 2 * key, 16), "out": words(BATCH * glwe)}
+    select = lambda b: [tree._h, b.ptr["table"], b.len["table"], b.ptr["selectors"], b.len["selectors"], b.ptr["out"],
+                        b.len["out"]]
+    add(tree._pre + "_dev", True, sizes, lambda b: select(b) + [None], lengths=TREE_LEN, null_first=False,
+        overlap=("out", "table", "TFHE CMUX tree: the output must not overlap an input"), zero=("table", "selectors", "out"),
+        out="out")
+    add(tree._pre, False, sizes, select, lengths=TREE_LEN, null_first=True, zero=("table", "selectors", "out"), out="out")
     return out
 
 
@@ -439,4 +499,4 @@ def test_refusals_before_a_launch(p, bits):
             torch.cuda.synchronize()
             assert (status, message) == (0, SENTINEL) and b.untouched(expect["out"]), name
         seen += 1
-    assert seen == (26 if bits == 64 else 25)
+    assert seen == (32 if bits == 64 else 31)
