@@ -1515,6 +1515,97 @@ int pfhe_tfhe32_cmux_tree_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *t
 int pfhe_tfhe32_cmux_tree(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
                           size_t len_selectors, uint32_t *out, size_t len_out);
 
+/* ---- GLWE key switch, Galois automorphism and homomorphic trace; their keys; the LWE embedding ----
+ *
+ * All 22 entry points below are the project's own rules, DESIGN.md section 21: the reference has no counterpart.  They are
+ * stated over the arithmetic of pfhe_tfhe*_external_product_to_dev, which they leave bit for bit what it is.  Phase is
+ * B - sum_j A_j z_j; a GLWE ciphertext is A_0..A_{k-1}, B of N words each; levels are least significant first,
+ * g_l = 2^(drop_bits + l*log_basis).  For odd t in 1..2N-1, sigma_t is p(X) -> p(X^t) mod X^N + 1, exact on words:
+ * sigma_t(p)[i] = p[u] for u < N and -p[u - N] otherwise, u = i * t^-1 mod 2N.
+ *
+ * Rule 1, the automorphism with its key switch (t = 1: a plain GLWE key switch).  key: one Fourier key of k*ell rows, row
+ * (j, l) k+1 polynomials of N complex values in the reference's layout, i.e. the first k*ell rows of what
+ * pfhe_tfhe*_external_product_to_dev takes (pfhe_tfhe*_gksk_generate_dev writes such keys).  Modulo 2^BITS:
+ *   out[e] = (0, .., 0, sigma_t(B_e)) - to_torus(sum_{j<k} sum_{l<ell} d_l(sigma_t(A_{e,j})) * key[j][l]).
+ * The words equal, one for one, the exact permutation sigma_t of every polynomial, pfhe_tfhe*_external_product_to_dev
+ * against the key padded with ell all-zero body rows, and the wrapping subtraction of that from (0, .., 0, sigma_t(B)).
+ * Nothing is atomic: the words depend neither on the batch nor on the chunk.  out may not overlap in (the operation is a
+ * gather; refused in the device form).  t even or outside 1..2N-1: PFHE_ERR_BAD_ARGUMENT.
+ *
+ * Rule 2, the trace of `steps` = m steps, 1 <= m <= log N (anything else: PFHE_ERR_BAD_ARGUMENT).  keys: m keys of rule 1
+ * end to end, key s-1 for t_s = 2^(log N - s + 1) + 1 (t_1 = N + 1):
+ *   ACC_0 = in[e],  ACC_s = ACC_{s-1} + automorphism(ACC_{s-1}, keys[s-1], t_s)  (s = 1..m),  out[e] = ACC_m,
+ * word for word m calls of rule 1 with a wrapping addition after each.  The phase of out is 2^m times the phase of in at
+ * the coefficients that are multiples of 2^m and (up to key-switch noise) 0 at every other one; m = log N leaves N times
+ * coefficient 0.  Dividing the message by 2^m beforehand is the caller's business.  out may be exactly in.
+ *
+ * Rule 3, the keys (device only, queues work only).  exponents: `count` odd values in 1..2N-1, read on the HOST during the
+ * call.  gksk_torus: count x k*ell x (k+1)*N words holding the caller's randomness (mask polynomials uniform, body
+ * polynomials noise); row (j, l) of key x becomes B += sum_c A_c (*) key_out_c (pfhe_tfhe*_glwe_body_mac_dev) and
+ * B += g_l * sigma_{t_x}(key_in_j); gksk_out: as many complex values, the forward transform of the torus form
+ * (pfhe_fft_forward_torus*_dev).  exponents {1}: the key of a plain key switch from key_in to key_out; the t_s of rule 2
+ * with key_in == key_out: the trace's keys.  Refused in order: the product plan's checks, glwe_dimension 0, a null or bad
+ * exponent, the lengths, (nothing to do,) null pointers, alignment, overlap, the device.
+ *
+ * Rule 4, the embedding of LWE ciphertexts (a[0..kN), b) into GLWE ciphertexts: A_j[0] = a[jN], A_j[N - i] = -a[jN + i]
+ * for i >= 1, B = (b, 0, .., 0); exact, stateless, one thread per output word.  pfhe_tfhe*_sample_extract at index 0
+ * returns the LWE ciphertext word for word; followed by the full trace it is the LWE-to-GLWE conversion.
+ *
+ * create, everything before the device first: the product plan's checks in their order (ApproxSignedBasis::new's assert!s,
+ * PFHE_ERR_UNSUPPORTED for glwe_dimension above 64, PFHE_ERR_BAD_ARGUMENT for a null table), then PFHE_ERR_BAD_ARGUMENT for
+ * glwe_dimension 0.  The handle borrows `fft` and allocates everything here, for `chunk` ciphertexts (0: a default):
+ * nothing on the fused shape (k = 1, N <= 2^11: one launch per chunk for all steps), otherwise the product's scratch and
+ * three word buffers of k, 1 and k+1 polynomials per ciphertext.  A call only queues work on `stream` (no allocation, no
+ * host synchronisation), so it can be captured into a HIP graph; a batch larger than the chunk runs chunk by chunk, all
+ * steps of a chunk first.  One holder at a time (PFHE_ERR_BUSY).  A call refuses: a null handle, a second holder, t or
+ * steps out of range, then in the order of pfhe_tfhe*_external_product_to_dev: PFHE_ERR_BAD_LENGTH for any length that does
+ * not fit the others, (the empty batch is a no-op,) null pointers, a pointer not aligned to 16 bytes, an overlap (device
+ * form), the device. */
+typedef struct pfhe_tfhe_glwe_trace_handle pfhe_tfhe_glwe_trace_handle;
+typedef struct pfhe_tfhe32_glwe_trace_handle pfhe_tfhe32_glwe_trace_handle;
+int pfhe_tfhe_glwe_trace_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t chunk, pfhe_tfhe_glwe_trace_handle **out);
+void pfhe_tfhe_glwe_trace_destroy(pfhe_tfhe_glwe_trace_handle *h);
+int pfhe_tfhe_glwe_trace_in_use(const pfhe_tfhe_glwe_trace_handle *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_glwe_trace_scratch_bytes(const pfhe_tfhe_glwe_trace_handle *h);
+int pfhe_tfhe_glwe_automorphism_dev(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in_dev, size_t len_in, const double *key_dev,
+                                    size_t len_key, uint32_t t, uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_glwe_automorphism(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in, size_t len_in, const double *key, size_t len_key,
+                                uint32_t t, uint64_t *out, size_t len_out);
+int pfhe_tfhe_glwe_trace_dev(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in_dev, size_t len_in, const double *keys_dev,
+                             size_t len_keys, size_t steps, uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_glwe_trace(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in, size_t len_in, const double *keys, size_t len_keys,
+                         size_t steps, uint64_t *out, size_t len_out);
+int pfhe_tfhe_gksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                const uint64_t *key_in_dev, size_t len_key_in, const uint64_t *key_out_dev, size_t len_key_out,
+                                const uint32_t *exponents, size_t count, uint64_t *gksk_torus_dev, size_t len_gksk,
+                                double *gksk_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_lwe_embed_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_dev, size_t len_lwe,
+                            uint64_t *glwe_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_lwe_embed(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe, size_t len_lwe, uint64_t *glwe_out,
+                        size_t len_out);
+int pfhe_tfhe32_glwe_trace_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                  size_t chunk, pfhe_tfhe32_glwe_trace_handle **out);
+void pfhe_tfhe32_glwe_trace_destroy(pfhe_tfhe32_glwe_trace_handle *h);
+int pfhe_tfhe32_glwe_trace_in_use(const pfhe_tfhe32_glwe_trace_handle *h);
+size_t pfhe_tfhe32_glwe_trace_scratch_bytes(const pfhe_tfhe32_glwe_trace_handle *h);
+int pfhe_tfhe32_glwe_automorphism_dev(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in_dev, size_t len_in, const double *key_dev,
+                                      size_t len_key, uint32_t t, uint32_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe32_glwe_automorphism(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in, size_t len_in, const double *key,
+                                  size_t len_key, uint32_t t, uint32_t *out, size_t len_out);
+int pfhe_tfhe32_glwe_trace_dev(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in_dev, size_t len_in, const double *keys_dev,
+                               size_t len_keys, size_t steps, uint32_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe32_glwe_trace(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in, size_t len_in, const double *keys, size_t len_keys,
+                           size_t steps, uint32_t *out, size_t len_out);
+int pfhe_tfhe32_gksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                  const uint32_t *key_in_dev, size_t len_key_in, const uint32_t *key_out_dev, size_t len_key_out,
+                                  const uint32_t *exponents, size_t count, uint32_t *gksk_torus_dev, size_t len_gksk,
+                                  double *gksk_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe32_lwe_embed_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_dev, size_t len_lwe,
+                              uint32_t *glwe_out_dev, size_t len_out, void *stream);
+int pfhe_tfhe32_lwe_embed(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe, size_t len_lwe, uint32_t *glwe_out,
+                          size_t len_out);
+
 #ifdef __cplusplus
 }
 #endif

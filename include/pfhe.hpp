@@ -1328,4 +1328,76 @@ class TfheCmuxTree32 {
     pfhe_tfhe32_cmux_tree_handle *h_ = nullptr;
 };
 
+// The GLWE automorphism X -> X^t with its key switch (out = (0, .., 0, sigma_t(B)) - sum_j sum_l d_l(sigma_t(A_j)) key[j][l],
+// key the k*ell mask rows of a Fourier GGSW; t = 1 is a plain key switch; out may not overlap in) and the homomorphic trace
+// of `steps` steps built from it (ACC += automorphism(ACC, keys[s-1], 2^(log N - s + 1) + 1); out may be in; the factor
+// 2^steps stays in the result) (pfhe_tfhe{,32}_glwe_trace_*, _glwe_automorphism*).  Owns, off the fused shape, the buffers
+// of `chunk` ciphertexts; one holder at a time.  The keys come from pfhe_tfhe*_gksk_generate_dev, the embedding of an LWE
+// ciphertext from pfhe_tfhe*_lwe_embed*, both stateless.  TfheGlweTrace32: the u32 torus.
+class TfheGlweTrace {
+  public:
+    TfheGlweTrace(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                  size_t chunk = 0) {
+        check(pfhe_tfhe_glwe_trace_create(fft.handle(), glwe_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfheGlweTrace() { pfhe_tfhe_glwe_trace_destroy(h_); }
+    TfheGlweTrace(const TfheGlweTrace &) = delete;
+    TfheGlweTrace &operator=(const TfheGlweTrace &) = delete;
+    pfhe_tfhe_glwe_trace_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_glwe_trace_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_glwe_trace_scratch_bytes(h_); }
+    void automorphism(const uint64_t *in, size_t len_in, const double *key, size_t len_key, uint32_t t, uint64_t *out,
+                      size_t len_out) {
+        check(pfhe_tfhe_glwe_automorphism(h_, in, len_in, key, len_key, t, out, len_out));
+    }
+    void automorphism_dev(const uint64_t *in_dev, size_t len_in, const double *key_dev, size_t len_key, uint32_t t,
+                          uint64_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe_glwe_automorphism_dev(h_, in_dev, len_in, key_dev, len_key, t, out_dev, len_out, stream));
+    }
+    void trace(const uint64_t *in, size_t len_in, const double *keys, size_t len_keys, size_t steps, uint64_t *out,
+               size_t len_out) {
+        check(pfhe_tfhe_glwe_trace(h_, in, len_in, keys, len_keys, steps, out, len_out));
+    }
+    void trace_dev(const uint64_t *in_dev, size_t len_in, const double *keys_dev, size_t len_keys, size_t steps,
+                   uint64_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe_glwe_trace_dev(h_, in_dev, len_in, keys_dev, len_keys, steps, out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe_glwe_trace_handle *h_ = nullptr;
+};
+
+class TfheGlweTrace32 {
+  public:
+    TfheGlweTrace32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                    size_t chunk = 0) {
+        check(pfhe_tfhe32_glwe_trace_create(fft.handle(), glwe_dimension, log_basis, decompose_length, chunk, &h_));
+    }
+    ~TfheGlweTrace32() { pfhe_tfhe32_glwe_trace_destroy(h_); }
+    TfheGlweTrace32(const TfheGlweTrace32 &) = delete;
+    TfheGlweTrace32 &operator=(const TfheGlweTrace32 &) = delete;
+    pfhe_tfhe32_glwe_trace_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_glwe_trace_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_glwe_trace_scratch_bytes(h_); }
+    void automorphism(const uint32_t *in, size_t len_in, const double *key, size_t len_key, uint32_t t, uint32_t *out,
+                      size_t len_out) {
+        check(pfhe_tfhe32_glwe_automorphism(h_, in, len_in, key, len_key, t, out, len_out));
+    }
+    void automorphism_dev(const uint32_t *in_dev, size_t len_in, const double *key_dev, size_t len_key, uint32_t t,
+                          uint32_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe32_glwe_automorphism_dev(h_, in_dev, len_in, key_dev, len_key, t, out_dev, len_out, stream));
+    }
+    void trace(const uint32_t *in, size_t len_in, const double *keys, size_t len_keys, size_t steps, uint32_t *out,
+               size_t len_out) {
+        check(pfhe_tfhe32_glwe_trace(h_, in, len_in, keys, len_keys, steps, out, len_out));
+    }
+    void trace_dev(const uint32_t *in_dev, size_t len_in, const double *keys_dev, size_t len_keys, size_t steps,
+                   uint32_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe32_glwe_trace_dev(h_, in_dev, len_in, keys_dev, len_keys, steps, out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe32_glwe_trace_handle *h_ = nullptr;
+};
+
 }  // namespace pfhe

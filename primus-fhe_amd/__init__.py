@@ -25,7 +25,9 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    lwe_pack_keyswitch_fft, lwe_pack_keyswitch_fft_dev, lwe_private_keyswitch, lwe_private_keyswitch_dev,
                    tfhe_generate_pfksk_dev, TfheCircuitBootstrapContext, tfhe_circuit_bootstrap,
                    tfhe_circuit_bootstrap_dev, TfheCmuxTreeContext, tfhe_cmux, tfhe_cmux_dev, tfhe_cmux_tree,
-                   tfhe_cmux_tree_dev)
+                   tfhe_cmux_tree_dev, TfheGlweTraceContext, glwe_automorphism, glwe_automorphism_dev, glwe_keyswitch,
+                   glwe_keyswitch_dev, glwe_trace, glwe_trace_dev, tfhe_generate_gksk_dev, lwe_embed_glwe,
+                   lwe_embed_glwe_dev)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -47,4 +49,6 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "TfhePackFftContext", "tfhe_pack_key_fourier_dev", "lwe_pack_keyswitch_fft", "lwe_pack_keyswitch_fft_dev",
            "lwe_private_keyswitch", "lwe_private_keyswitch_dev", "tfhe_generate_pfksk_dev", "TfheCircuitBootstrapContext",
            "tfhe_circuit_bootstrap", "tfhe_circuit_bootstrap_dev", "TfheCmuxTreeContext", "tfhe_cmux", "tfhe_cmux_dev",
-           "tfhe_cmux_tree", "tfhe_cmux_tree_dev", "build", "lib", "library_path", "status_string"]
+           "tfhe_cmux_tree", "tfhe_cmux_tree_dev", "TfheGlweTraceContext", "glwe_automorphism", "glwe_automorphism_dev",
+           "glwe_keyswitch", "glwe_keyswitch_dev", "glwe_trace", "glwe_trace_dev", "tfhe_generate_gksk_dev", "lwe_embed_glwe",
+           "lwe_embed_glwe_dev", "build", "lib", "library_path", "status_string"]

@@ -261,6 +261,19 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "cmux", ci, vp, vp, sz, vp, sz, f64p, sz, sz, vp, sz)
         sig(ct + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
         sig(ct, ci, vp, vp, sz, f64p, sz, vp, sz)
+        # the GLWE automorphism / key switch and the trace, both calls of one handle; their keys; the LWE embedding
+        gt = tp + "glwe_trace"
+        sig(gt + "_create", ci, vp, sz, u32, sz, sz, C.POINTER(vp))
+        sig(gt + "_destroy", None, vp)
+        sig(gt + "_in_use", ci, vp)
+        sig(gt + "_scratch_bytes", sz, vp)
+        sig(tp + "glwe_automorphism_dev", ci, vp, vp, sz, f64p, sz, u32, vp, sz, vp)
+        sig(tp + "glwe_automorphism", ci, vp, vp, sz, f64p, sz, u32, vp, sz)
+        sig(gt + "_dev", ci, vp, vp, sz, f64p, sz, sz, vp, sz, vp)
+        sig(gt, ci, vp, vp, sz, f64p, sz, sz, vp, sz)
+        sig(tp + "gksk_generate_dev", ci, vp, sz, u32, sz, vp, sz, vp, sz, vp, sz, vp, sz, f64p, sz, vp)
+        sig(tp + "lwe_embed_dev", ci, vp, sz, vp, sz, vp, sz, vp)
+        sig(tp + "lwe_embed", ci, vp, sz, vp, sz, vp, sz)
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)

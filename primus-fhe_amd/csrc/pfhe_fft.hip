@@ -866,6 +866,24 @@ template int tfhe_plan_create<u32>(const pfhe_fft *, size_t, uint32_t, size_t, s
 template int tfhe_product_impl<u64>(TfhePlanCore<u64> *, const u64 *, const double2 *, u64 *, u64, hipStream_t);
 template int tfhe_product_impl<u32>(TfhePlanCore<u32> *, const u32 *, const double2 *, u32 *, u64, hipStream_t);
 
+// ... and what the general form of pfhe_trace.hip takes: three launches of the general product as they are, on a key of
+// k ell rows and on k digit rows per ciphertext
+int tfhe_key_herm_launch(const pfhe_fft &f, const double2 *key, double2 *keyh, u64 polys, hipStream_t s) {
+    return launch_flat(tfhe_key_herm_kernel, polys * (f.n / 2), s, key, keyh, f.log_n);
+}
+template <class W>
+int tfhe_digit_fwd_launch(const pfhe_fft &f, const Shape &sh, const W *in, double2 *spec, u64 polys, hipStream_t s) {
+    return launch_groups(tfhe_digit_fwd_kernel<W>, polys * sh.ell, lds_bytes(f.log_n), s, in, spec, f.tw, sh);
+}
+template <class W>
+int tfhe_half_inverse_launch(const pfhe_fft &f, const double2 *acc, W *out, u64 polys, hipStream_t s) {
+    return launch_groups(fft_inverse_kernel<W, false>, polys, lds_bytes(f.log_n), s, acc, out, f.tw, f.log_n);
+}
+template int tfhe_digit_fwd_launch<u64>(const pfhe_fft &, const Shape &, const u64 *, double2 *, u64, hipStream_t);
+template int tfhe_digit_fwd_launch<u32>(const pfhe_fft &, const Shape &, const u32 *, double2 *, u64, hipStream_t);
+template int tfhe_half_inverse_launch<u64>(const pfhe_fft &, const double2 *, u64 *, u64, hipStream_t);
+template int tfhe_half_inverse_launch<u32>(const pfhe_fft &, const double2 *, u32 *, u64, hipStream_t);
+
 }  // namespace pfhe
 
 extern "C" {

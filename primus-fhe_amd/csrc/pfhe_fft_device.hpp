@@ -3,8 +3,9 @@
 // The half-size transforms in LDS, the torus conversions, the signed digits, and the two halves of the fused product
 // (k = 1, N <= 2^11): fused_accumulate_rows (digits, forward transforms and the multiply-accumulate of both input rows) and
 // fused_inverse_rows (the two folded inverses and the torus wrap).  tfhe_fused_kernel runs them once on words read from
-// global memory; tfhe_blindrot_loop_kernel runs them once per step on an accumulator that stays in LDS.  Both inline the
-// same code, so a step of the loop is the product's arithmetic, operation for operation.  fused_accumulate_rows takes the
+// global memory; tfhe_blindrot_loop_kernel runs them once per step on an accumulator that stays in LDS; so does
+// tfhe_trace_loop_kernel (pfhe_trace.hip), on the mask row alone.  All inline the same code, so a step of a loop is the
+// product's arithmetic, operation for operation.  fused_accumulate_rows takes the
 // key's Hermitian part from a key source: ClassicKey (one key in memory) or MultiBitKey (the multi-bit rotation's
 // per-ciphertext combination of 2^g keys, mb_combined_slots, shared with the per-group and combined-key kernels).
 #pragma once
@@ -240,13 +241,14 @@ struct ClassicKey {
 // both input rows, all levels: rows(r) gives row r, whose lo(u, i) / hi(u, i) are the words of coefficients i and
 // i + N/2 of slot u.  Per level: their signed digits, the forward half transform in lds_p, and acc0 / acc1 += spectrum *
 // Herm(key[r][l][0 / 1]) as the key source gives it.  Only the carries stay in registers between levels: bit u of carry0 / carry1 is the carry of
-// coefficient i / i + N/2 of slot u.  Ends behind a barrier.
-template <class W, class Rows, class Key>
+// coefficient i / i + N/2 of slot u.  Ends behind a barrier.  ROWS = 1 walks the mask row alone, against a key of ell
+// rows (the key switch of pfhe_trace.hip): the same code, one trip of the outer loop.
+template <class W, u32 ROWS = 2, class Rows, class Key>
 __device__ __forceinline__ void fused_accumulate_rows(const Rows rows, const Key key, double2 *lds_p,
                                                       const double2 *__restrict__ tw, const Shape s,
                                                       double2 (&acc0)[kFusedPer], double2 (&acc1)[kFusedPer]) {
     const u32 n = 1u << s.log_n, m = n >> 1, log_m = s.log_n - 1;
-    for (u32 r = 0; r < 2; ++r) {
+    for (u32 r = 0; r < ROWS; ++r) {
         const auto row = rows(r);
         u32 carry0 = 0, carry1 = 0;
 #pragma unroll

@@ -187,4 +187,14 @@ int tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
 template <class W>
 int tfhe_product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *out, u64 batch, hipStream_t s);
 
+// Three launches of the general product for a caller that decomposes fewer rows than k+1 (pfhe_trace.hip: the k mask
+// rows): the Hermitian parts of `polys` key polynomials, the digit transforms of `polys` torus polynomials (polys * ell
+// workgroups, spectra in natural order polynomial after polynomial, level after level), and the half-spectrum inverses of
+// `polys` accumulators.  pfhe_fft.hip; the device is current.
+int tfhe_key_herm_launch(const pfhe_fft &f, const double2 *key, double2 *keyh, u64 polys, hipStream_t s);
+template <class W>
+int tfhe_digit_fwd_launch(const pfhe_fft &f, const Shape &sh, const W *in, double2 *spec, u64 polys, hipStream_t s);
+template <class W>
+int tfhe_half_inverse_launch(const pfhe_fft &f, const double2 *acc, W *out, u64 polys, hipStream_t s);
+
 }  // namespace pfhe

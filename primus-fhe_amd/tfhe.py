@@ -870,6 +870,130 @@ def tfhe_cmux_tree_dev(table, selectors, out, ctx: TfheCmuxTreeContext, stream=N
     _cmux_tree(_dev_words, _dev_fourier, table, selectors, out, ctx, "_dev", (_stream(stream),))
 
 
+# ---- GLWE key switch, automorphism and trace; their keys; the LWE embedding (include/pfhe.h: glwe_trace_*, glwe_automorphism,
+# gksk_generate_dev, lwe_embed) ----
+
+class TfheGlweTraceContext(_TorusContext):
+    """Handle of the GLWE automorphism X -> X^t with its key switch and of the homomorphic trace built from it
+    (include/pfhe.h, pfhe_tfhe{,32}_glwe_trace_*).  Created and checked as TfheFftContext; owns, off the fused shape
+    (k = 1, N <= 2^11), the buffers of `chunk` ciphertexts (0 = the default); one holder at a time (Busy for a second
+    thread).  A key has k*ell rows, the mask rows of a Fourier GGSW: key_len() complex values."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1, chunk: int = 0):
+        self._open(fft, basis, glwe_dimension, "glwe_trace", (chunk,), ("_create", "_destroy", "_in_use", "_scratch_bytes"))
+
+    def key_len(self) -> int:
+        """complex values (and torus words) of one key: k * ell rows of a GLWE ciphertext each"""
+        return self.glwe_dimension * self.basis.decompose_length() * self.glwe_len()
+
+    def trace_exponents(self, steps: int | None = None) -> list:
+        """the exponents t_s = 2^(log N - s + 1) + 1, s = 1..steps (default log N), whose keys glwe_trace takes in this order"""
+        log_n = self.fft.log_n
+        steps = log_n if steps is None else steps
+        if not 1 <= steps <= log_n:
+            raise PfheError(33, "steps must be in 1..log N")
+        return [(1 << (log_n - s + 1)) + 1 for s in range(1, steps + 1)]
+
+
+def _glwe_automorphism(words, fourier, inp, key, out, t, ctx, name, tail):
+    pi, ni, wi = words(inp)
+    po, no, wo = words(out)
+    pk, nk = fourier(key)
+    _same_width("inp and out must have the width of the context's basis", wi, wo, ctx._w)
+    check(getattr(lib(), "pfhe_tfhe" + ctx._w + name)(ctx._h, pi, ni, pk, nk, t, po, no, *tail))
+
+
+def glwe_automorphism(inp: np.ndarray, key: np.ndarray, out: np.ndarray, t: int, ctx: TfheGlweTraceContext) -> None:
+    """The automorphism X -> X^t (t odd, 1..2N-1) with its key switch, on host arrays:
+    out[e] = (0, .., 0, sigma_t(B_e)) - to_torus(sum_j sum_l d_l(sigma_t(A_{e,j})) * key[j][l]) modulo 2^BITS for a batch of
+    GLWE ciphertexts and one key of ctx.key_len() complex values (tfhe_generate_gksk_dev).  Word for word the exact
+    permutation sigma_t, tfhe_external_product_to against the key padded with ell zero body rows, and the subtraction."""
+    _glwe_automorphism(_host_words, _host_fourier, inp, key, out, t, ctx, "_glwe_automorphism", ())
+
+
+def glwe_automorphism_dev(inp, key, out, t: int, ctx: TfheGlweTraceContext, stream=None) -> None:
+    """the device form, asynchronous; out must not overlap inp (the operation is a gather)"""
+    _glwe_automorphism(_dev_words, _dev_fourier, inp, key, out, t, ctx, "_glwe_automorphism_dev", (_stream(stream),))
+
+
+def glwe_keyswitch(inp: np.ndarray, key: np.ndarray, out: np.ndarray, ctx: TfheGlweTraceContext) -> None:
+    """GLWE key switch on host arrays: glwe_automorphism with t = 1, key from tfhe_generate_gksk_dev(.., exponents=[1])"""
+    glwe_automorphism(inp, key, out, 1, ctx)
+
+
+def glwe_keyswitch_dev(inp, key, out, ctx: TfheGlweTraceContext, stream=None) -> None:
+    """the device form, asynchronous; out must not overlap inp"""
+    glwe_automorphism_dev(inp, key, out, 1, ctx, stream)
+
+
+def _glwe_trace(words, fourier, inp, keys, out, ctx, steps, name, tail):
+    pi, ni, wi = words(inp)
+    po, no, wo = words(out)
+    pk, nk = fourier(keys)
+    _same_width("inp and out must have the width of the context's basis", wi, wo, ctx._w)
+    m = ctx.fft.log_n if steps is None else steps
+    check(getattr(lib(), ctx._pre + name)(ctx._h, pi, ni, pk, nk, m, po, no, *tail))
+
+
+def glwe_trace(inp: np.ndarray, keys: np.ndarray, out: np.ndarray, ctx: TfheGlweTraceContext, steps: int | None = None) -> None:
+    """The homomorphic trace of `steps` = m steps (1..log N, default log N) on host arrays: ACC_0 = inp[e],
+    ACC_s = ACC_{s-1} + automorphism(ACC_{s-1}, keys[s-1], t_s), out[e] = ACC_m, with t_s = ctx.trace_exponents(m)[s-1] and
+    keys the m keys end to end; word for word m calls of glwe_automorphism with a wrapping addition after each.  The phase
+    of out is 2^m times the phase of inp at the coefficients that are multiples of 2^m and (up to the key switches' noise)
+    zero elsewhere; m = log N leaves N times coefficient 0 alone.  The factor 2^m is NOT removed here: scaling the message
+    by 1 / 2^m beforehand is the caller's business."""
+    _glwe_trace(_host_words, _host_fourier, inp, keys, out, ctx, steps, "", ())
+
+
+def glwe_trace_dev(inp, keys, out, ctx: TfheGlweTraceContext, steps: int | None = None, stream=None) -> None:
+    """the device form, asynchronous; out may be exactly inp, any other overlap is refused.  The factor 2^m stays in
+    the result, as in glwe_trace."""
+    _glwe_trace(_dev_words, _dev_fourier, inp, keys, out, ctx, steps, "_dev", (_stream(stream),))
+
+
+def tfhe_generate_gksk_dev(key_in, key_out, fft: FullComplex64FftTable, basis: ApproxSignedBasis, rand, exponents,
+                           glwe_dimension: int = 1, out=None, stream=None):
+    """The keys glwe_automorphism_dev / glwe_trace_dev take, generated on the device: for every odd exponent t_x of
+    `exponents`, a key that switches sigma_{t_x} of a ciphertext under key_in to key_out (both the k key polynomials end to
+    end).  rand: len(exponents) x k*ell x (k+1)*N torus words holding the randomness (mask polynomials uniform, body
+    polynomials noise), which becomes the torus-form keys in place: row (j, l) of key x gets B += sum_c A_c * key_out_c and
+    B += sigma_{t_x}(key_in_j) * 2^(drop_bits + l*log_basis); out: as many complex128 values (allocated when None), the
+    Fourier form, bit for bit what write_fourier_form gives.  exponents=[1] is a plain GLWE key switch key;
+    ctx.trace_exponents(m) with key_in == key_out the trace's keys.  Returns out.  Asynchronous."""
+    import torch
+    pi, ni, wi = _dev_words(key_in)
+    pz, nz, wz = _dev_words(key_out)
+    pr, nr, wr = _dev_words(rand)
+    _same_width("both keys and the randomness must have the same word width", wi, wz, wr)
+    lb, ell = _basis_args(basis, wr)
+    ex = np.ascontiguousarray(list(exponents), dtype=np.uint32)
+    if out is None:
+        out = torch.empty(nr, dtype=torch.complex128, device=rand.device)
+    po, no = _dev_fourier(out)
+    check(getattr(lib(), "pfhe_tfhe" + wr + "_gksk_generate_dev")(fft._h, glwe_dimension, lb, ell, pi, ni, pz, nz,
+                                                                ex.ctypes.data_as(C.c_void_p), ex.size, pr, nr, po, no,
+                                                                _stream(stream)))
+    return out
+
+
+def _lwe_embed(dev, lwe, glwe_out, fft, glwe_dimension, stream=None) -> None:
+    _stateless("_lwe_embed", dev, (lwe, glwe_out), "lwe and glwe_out must have the same word width",
+               lambda w, l, g: (fft._h, glwe_dimension, *l, *g), stream)
+
+
+def lwe_embed_glwe(lwe: np.ndarray, glwe_out: np.ndarray, fft: FullComplex64FftTable, glwe_dimension: int = 1) -> None:
+    """Embeds LWE ciphertexts (a[0..kN), b) under the GLWE key polynomials end to end into GLWE ciphertexts whose phase has
+    the LWE phase on coefficient 0 (and no meaning elsewhere), on host arrays: A_j[0] = a[jN], A_j[N - i] = -a[jN + i],
+    B = (b, 0, .., 0).  Exact; glwe_sample_extract at index 0 gives the LWE ciphertext back word for word; followed by
+    the full glwe_trace it is the LWE-to-GLWE conversion (times N)."""
+    _lwe_embed(False, lwe, glwe_out, fft, glwe_dimension)
+
+
+def lwe_embed_glwe_dev(lwe, glwe_out, fft: FullComplex64FftTable, glwe_dimension: int = 1, stream=None) -> None:
+    """the device form, asynchronous and stateless; glwe_out must not overlap lwe and may be uninitialised"""
+    _lwe_embed(True, lwe, glwe_out, fft, glwe_dimension, stream)
+
+
 def _torus_dtype(bits: int):
     import torch
     if bits not in (32, 64):
