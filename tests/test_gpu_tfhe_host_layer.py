@@ -1,4 +1,5 @@
-"""What the torus entry points (csrc/pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip, pfhe_cbs.hip, pfhe_cmux.hip) share on
+"""What the torus entry points (csrc/pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip, pfhe_cbs.hip, pfhe_cmux.hip; for the
+allocations also pfhe_trace.hip and pfhe_pack_fft.hip) share on
 the host side, pinned where the other torus tests leave it open: every host form against its device form word for word, the status and the
 pfhe_last_error() text of every refusal that is decided before a launch (and their order), a zero batch, and what each
 handle kind allocates.  All at N = 8 with batch 3 on handles of chunk 2, so every chunk loop runs a full and a short chunk."""
@@ -216,6 +217,28 @@ def test_handle_host_equals_device(p, bits, k):
 #   bootstrap                the rotation's plus acc chunk*(k+1)*N*W, extracted chunk*(k*N+1)*W (with a key switch only),
 #                            exps chunk*4*4 = 32 and neg_b chunk*4 = 8: k = 1: 240 / 440 (168 / 296 without), k = 2: 368 / 696
 #   the fused product and the whole-loop rotations own nothing
+# The handles of DESIGN.md §18-21, from the buffer lists in their header comments (csrc/pfhe_pack_fft.hip, pfhe_cbs.hip,
+# pfhe_cmux.hip, pfhe_trace.hip), not from the numbers the code gives:
+#   circuit bootstrap        output basis = the product's (two levels), so chunk 2 is 4 accumulators, and the rotation it
+#                            owns is created for a chunk of 4.  Its own four buffers: acc 4*(k+1)*N*W, extracted
+#                            4*(k*N+1)*W, exps 4*4*4 = 64, neg_b 2*4 = 8.
+#                            k = 1 (whole loop, nothing more): 64 W + 36 W + 72 = 472 / 872.
+#                            k = 2: 96 W + 68 W + 72 = 728 / 1384, plus the per-step rotation at chunk 4: the product's
+#                            spec 4*3*2*4*16 = 1536, acc 4*3*4*16 = 768, keyh 1152 = 3456 and three glue buffers of
+#                            4*24 W = 1152 / 2304: 5336 / 7144 in 4 + 6 buffers
+#   CMUX tree                node buffers of chunk*2^(d-1) and chunk*2^(d-2) ciphertexts (depth 1 none, depth 2 one); the
+#                            general form adds D and E of chunk*2^(d-1) ciphertexts and a product plan of the DEFAULT chunk
+#                            (§11: what fits 256 MiB at (k+1)(ell+1) N/2 = 3*3*4 complex values = 576 bytes a
+#                            ciphertext, floor(2^28 / 576) = 466033 of them, and the Hermitian parts of one key, 1152):
+#                            PLAN = 466033 * 576 + 1152 = 268436160 in three buffers.
+#                            fused (k = 1, 16 words a ciphertext): depth 1 nothing; depth 3: (8 + 4)*16 W = 768 / 1536, two
+#                            general (k = 2, 24 words): depth 1: D, E of 2 ciphertexts, 96 W = 384 / 768, + PLAN, 2 + 3;
+#                            depth 3: (8 + 4 + 8 + 8)*24 W = 2688 / 5376, + PLAN, 4 + 3
+#   trace                    fused: nothing.  general, k = 2: the product's scratch at chunk 2 (the "plan general" row: 2304)
+#                            and D 2*2*8 W, the gathered bodies 2*8 W, E 2*24 W = 96 W = 384 / 768: six buffers
+#   packing plan             the partial half spectra, chunk x ceil(in_dimension / 4) x (k+1) x N/2 complex values: 5 mask
+#                            words are 2 slices, 2*2*2*4*16 = 512, one buffer
+CMUX_PLAN = 466033 * 576 + 1152
 HANDLES = {
     "plan fused": (lambda p, f, b, ks: p.TfheFftContext(f, b, 1, chunk=CHUNK), False, {32: (0, 0), 64: (0, 0)}),
     "plan general": (lambda p, f, b, ks: p.TfheFftContext(f, b, 2, chunk=CHUNK), False, {32: (2304, 3), 64: (2304, 3)}),
@@ -241,6 +264,22 @@ HANDLES = {
         {32: (240, 4), 64: (440, 4)}),
     "bootstrap per group": (lambda p, f, b, ks: p.TfheBootstrapContext(f, b, LWE, 2, ks, chunk=CHUNK, grouping_factor=G), False,
                             {32: (5760 + 368, 7), 64: (5760 + 696, 7)}),
+    "circuit bootstrap over the whole loop": (
+        lambda p, f, b, ks: p.TfheCircuitBootstrapContext(f, b, LWE, 1, b, ks, chunk=CHUNK), False, {32: (472, 4), 64: (872, 4)}),
+    "circuit bootstrap per step": (
+        lambda p, f, b, ks: p.TfheCircuitBootstrapContext(f, b, LWE, 2, b, ks, chunk=CHUNK), False,
+        {32: (3456 + 1152 + 728, 10), 64: (3456 + 2304 + 1384, 10)}),
+    "cmux tree fused, depth 1": (lambda p, f, b, ks: p.TfheCmuxTreeContext(f, b, 1, 1, chunk=CHUNK), False, {32: (0, 0), 64: (0, 0)}),
+    "cmux tree fused, depth 3": (lambda p, f, b, ks: p.TfheCmuxTreeContext(f, b, 1, 3, chunk=CHUNK), False,
+                                 {32: (768, 2), 64: (1536, 2)}),
+    "cmux tree general, depth 1": (lambda p, f, b, ks: p.TfheCmuxTreeContext(f, b, 2, 1, chunk=CHUNK), False,
+                                   {32: (384 + CMUX_PLAN, 5), 64: (768 + CMUX_PLAN, 5)}),
+    "cmux tree general, depth 3": (lambda p, f, b, ks: p.TfheCmuxTreeContext(f, b, 2, 3, chunk=CHUNK), False,
+                                   {32: (2688 + CMUX_PLAN, 7), 64: (5376 + CMUX_PLAN, 7)}),
+    "trace fused": (lambda p, f, b, ks: p.TfheGlweTraceContext(f, b, 1, chunk=CHUNK), False, {32: (0, 0), 64: (0, 0)}),
+    "trace general": (lambda p, f, b, ks: p.TfheGlweTraceContext(f, b, 2, chunk=CHUNK), False,
+                      {32: (2304 + 384, 6), 64: (2304 + 768, 6)}),
+    "packing plan": (lambda p, f, b, ks: p.TfhePackFftContext(f, ks, 5, 1, CHUNK), False, {32: (512, 1), 64: (512, 1)}),
 }
 
 
