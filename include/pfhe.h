@@ -1034,6 +1034,19 @@ int pfhe_tfhe_modswitch_dev(int device, const uint64_t *lwe_dev, size_t len_lwe,
                             uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream);
 int pfhe_tfhe32_modswitch_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
                               uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream);
+/* The strided modulus switch, what a many-LUT rotation takes.  NO reference counterpart.  With
+ * v = log_stride, 0 <= v <= log_n:  sw_v(w) = ((((w >> (BITS - log_n - 2 + v)) + 1) >> 1) << v) & (2N-1), i.e. w * 2N / 2^v /
+ * 2^BITS rounded to nearest, ties up, times 2^v: every value is a multiple of 2^v, and a word that rounds up to 2N wraps to
+ * 0.  exps[e*n + i] = sw_v(a_{e,i}), neg_b[e] = (2N - sw_v(b_e)) & (2N-1); lengths as pfhe_tfhe*_modswitch_dev, whose words
+ * sw_0 gives one for one.  Refusals in that call's order, PFHE_ERR_BAD_ARGUMENT for log_stride > log_n right behind log_n's:
+ * log_n, log_stride, lwe_dimension, PFHE_ERR_BAD_LENGTH for the lengths, (the empty batch is a no-op,) null pointers, the
+ * device. */
+int pfhe_tfhe_modswitch_stride_dev(int device, const uint64_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                                   uint32_t log_stride, uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev,
+                                   size_t len_neg_b, void *stream);
+int pfhe_tfhe32_modswitch_stride_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
+                                     uint32_t log_stride, uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev,
+                                     size_t len_neg_b, void *stream);
 /* Sample extraction — Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227; index 0: extract_lwe,
  * :264-288) applied to each of the k mask polynomials of a GLWE ciphertext (A_0..A_{k-1}, B): for index h < N the output LWE
  * has dimension k*N, out[j*N + i] = A_j[h - i] for i <= h and -A_j[N + h - i] for i > h (wrapping), out[k*N] = B[h]; its key
@@ -1102,6 +1115,20 @@ int pfhe_tfhe_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimensi
                                         size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length,
                                         int with_keyswitch, size_t grouping_factor, size_t chunk,
                                         pfhe_tfhe_bootstrap_handle **out);
+/* The many-LUT bootstrap on the same handle: ONE rotation per input evaluates 2^log_luts look-ups.  Per
+ * chunk: pfhe_tfhe*_modswitch_stride_dev with v = log_luts; the accumulator init as above; the rotation (the classic one for
+ * grouping_factor 0 or 1, the multi-bit one above that, on its key); sample extraction of ACC_e at EVERY index i < 2^v, each
+ * what pfhe_tfhe*_sample_extract_dev gives at index i; with a key switch, the key switch of all of them.  lwe_out holds
+ * batch*2^v ciphertexts, output (e, i) at index e*2^v + i; every other length is as before, and every call below works on
+ * the handle.  The words equal, one for one, that composition of public calls; log_luts 0 gives the words of a handle of
+ * the two creates above.  The rotated phase is a multiple of 2^v, so with TV[c] = tv_{c mod 2^v}[c - (c mod 2^v)] output i
+ * is the ordinary bootstrap of test vector tv_i at the stride-rounded phase.  create, before the device: the rotation's
+ * checks in its order (with a grouping factor above 1 its range and PFHE_ERR_BAD_ARGUMENT when lwe_dimension is no multiple
+ * of it, as pfhe_tfhe*_bootstrap_create_multibit), then PFHE_ERR_BAD_ARGUMENT for log_luts > log N; then as the creates above. */
+int pfhe_tfhe_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                        size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length,
+                                        int with_keyswitch, size_t grouping_factor /* 0 or 1: classic */, uint32_t log_luts,
+                                        size_t chunk, pfhe_tfhe_bootstrap_handle **out);
 void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h);
 int pfhe_tfhe_bootstrap_in_use(const pfhe_tfhe_bootstrap_handle *h);  /* 1 while some thread is inside a call on it */
 size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h);  /* the rotation handle's scratch included */
@@ -1118,6 +1145,10 @@ int pfhe_tfhe32_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimen
                                           size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
                                           size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor, size_t chunk,
                                           pfhe_tfhe32_bootstrap_handle **out);
+int pfhe_tfhe32_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
+                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
+                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor,
+                                          uint32_t log_luts, size_t chunk, pfhe_tfhe32_bootstrap_handle **out);
 void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h);
 int pfhe_tfhe32_bootstrap_in_use(const pfhe_tfhe32_bootstrap_handle *h);
 size_t pfhe_tfhe32_bootstrap_scratch_bytes(const pfhe_tfhe32_bootstrap_handle *h);
@@ -1431,6 +1462,31 @@ typedef struct pfhe_tfhe32_cbs_handle pfhe_tfhe32_cbs_handle;
 int pfhe_tfhe_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                          size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
                          size_t pfks_decompose_length, size_t chunk, pfhe_tfhe_cbs_handle **out);
+/* The same handle with options; with both off it is pfhe_tfhe*_cbs_create, word for word, and every call
+ * below works on it.
+ *   grouping_factor g > 1 (0 or 1: classic): the owned rotation is the multi-bit one and bsk the multi-bit key of
+ *     (lwe_dimension / g) * 2^g keys that pfhe_tfhe*_bsk_generate_dev writes; the other stages are unchanged.
+ *   shared_rotation non-zero: ONE rotation per input serves all ell_cb levels.  With v = ceil(log2 ell_cb), per chunk:
+ *     1. pfhe_tfhe*_modswitch_stride_dev with v on (a, b + 2^(BITS-2)); exponents and neg_b of an input are written once;
+ *     2. ACC_e = X^{neg_b[e]} * TV, TV the trivial GLWE whose body coefficient c is -g_{c mod 2^v}/2 when c mod 2^v < ell_cb
+ *        and 0 otherwise, written from constants;
+ *     3. the rotation over the chunk's accumulators, one per input;
+ *     4. sample extraction of ACC_e at index l for every l < ell_cb, with g_l/2 added to the body, into row e*ell_cb + l;
+ *     5. the private functional key switch, as before.
+ *     The words equal, one for one, that composition of public calls (pfhe_tfhe*_mul_monomial_each_to_dev on TV in memory
+ *     for step 2); with ell_cb = 1 they are the existing handle's.  The handle then owns chunk accumulators, chunk*n
+ *     exponents and chunk*ell_cb extracted ciphertexts, and the rotation is created for chunk accumulators; chunk 0 is the
+ *     rotation's default capped at about 256 MiB of accumulators.  The switch rounds every word to a multiple of 2^v, so
+ *     the worst-case margin of the switched phase is 2^(v-1)*(n+1) plus the input's own error, in units of 2^BITS/2N,
+ *     against N/2; outside it the output is right only statistically.  Nothing is refused on that account.
+ * create, everything before the device first, in the order of pfhe_tfhe*_cbs_create with the options' refusals in their
+ * places: the rotation's checks (for g > 1 with PFHE_ERR_BAD_ARGUMENT for g above 4 last), PFHE_ERR_BAD_ARGUMENT when
+ * lwe_dimension is no multiple of g, the dimensions, the two other bases, drop_bits of the output basis, and
+ * PFHE_ERR_BAD_ARGUMENT for ell_cb > N with a shared rotation; then the rotation's create. */
+int pfhe_tfhe_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                              size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,
+                              uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t grouping_factor /* 0 or 1: classic */,
+                              int shared_rotation, size_t chunk, pfhe_tfhe_cbs_handle **out);
 void pfhe_tfhe_cbs_destroy(pfhe_tfhe_cbs_handle *h);
 int pfhe_tfhe_cbs_in_use(const pfhe_tfhe_cbs_handle *h);  /* 1 while some thread is inside a call on it */
 size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h);  /* the rotation handle's scratch included */
@@ -1441,6 +1497,10 @@ int pfhe_tfhe_cbs(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in, size_t len_in
 int pfhe_tfhe32_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                            size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
                            size_t pfks_decompose_length, size_t chunk, pfhe_tfhe32_cbs_handle **out);
+int pfhe_tfhe32_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,
+                                uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t grouping_factor,
+                                int shared_rotation, size_t chunk, pfhe_tfhe32_cbs_handle **out);
 void pfhe_tfhe32_cbs_destroy(pfhe_tfhe32_cbs_handle *h);
 int pfhe_tfhe32_cbs_in_use(const pfhe_tfhe32_cbs_handle *h);
 size_t pfhe_tfhe32_cbs_scratch_bytes(const pfhe_tfhe32_cbs_handle *h);

@@ -806,6 +806,13 @@ inline void lwe_modulus_switch_dev(int device, const uint64_t *lwe_dev, size_t l
     check(pfhe_tfhe_modswitch_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev, len_neg_b,
                                   stream));
 }
+// ... to multiples of 2^log_stride (log_stride <= log_n), what a many-LUT rotation takes; log_stride 0 is the call above
+inline void lwe_modulus_switch_strided_dev(int device, const uint64_t *lwe_dev, size_t len_lwe, size_t lwe_dimension,
+                                           uint32_t log_n, uint32_t log_stride, uint32_t *exps_dev, size_t len_exps,
+                                           uint32_t *neg_b_dev, size_t len_neg_b, void *stream = nullptr) {
+    check(pfhe_tfhe_modswitch_stride_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, log_stride, exps_dev, len_exps,
+                                         neg_b_dev, len_neg_b, stream));
+}
 // Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial of a GLWE ciphertext
 inline void glwe_sample_extract(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe,
                                 size_t index, uint64_t *lwe, size_t len_lwe) {
@@ -835,6 +842,12 @@ inline void lwe_modulus_switch_dev(int device, const uint32_t *lwe_dev, size_t l
     check(pfhe_tfhe32_modswitch_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev, len_neg_b,
                                   stream));
 }
+inline void lwe_modulus_switch_strided_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension,
+                                           uint32_t log_n, uint32_t log_stride, uint32_t *exps_dev, size_t len_exps,
+                                           uint32_t *neg_b_dev, size_t len_neg_b, void *stream = nullptr) {
+    check(pfhe_tfhe32_modswitch_stride_dev(device, lwe_dev, len_lwe, lwe_dimension, log_n, log_stride, exps_dev, len_exps,
+                                           neg_b_dev, len_neg_b, stream));
+}
 inline void glwe_sample_extract(const FullComplex64FftTable &fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe,
                                 size_t index, uint32_t *lwe, size_t len_lwe) {
     check(pfhe_tfhe32_sample_extract(fft.handle(), glwe_dimension, glwe, len_glwe, index, lwe, len_lwe));
@@ -862,9 +875,14 @@ class TfheBootstrap {
   public:
     TfheBootstrap(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                     size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, bool with_keyswitch = true,
-                    size_t chunk = 0, size_t grouping_factor = 1) {
-        // grouping_factor 1: the classic rotation; above 1 the multi-bit one, on (lwe_dimension / g) * 2^g keys
-        check(grouping_factor == 1
+                    size_t chunk = 0, size_t grouping_factor = 1, uint32_t log_luts = 0) {
+        // grouping_factor 1: the classic rotation; above 1 the multi-bit one, on (lwe_dimension / g) * 2^g keys.  log_luts
+        // above 0: the many-LUT bootstrap, 2^log_luts outputs per input (output (e, i) at e * 2^log_luts + i)
+        check(log_luts != 0
+                  ? pfhe_tfhe_bootstrap_create_many_lut(fft.handle(), glwe_dimension, log_basis, decompose_length,
+                                                        lwe_dimension, ks_log_basis, ks_decompose_length,
+                                                        with_keyswitch ? 1 : 0, grouping_factor, log_luts, chunk, &h_)
+              : grouping_factor == 1
                   ? pfhe_tfhe_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension,
                                                ks_log_basis, ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_)
                   : pfhe_tfhe_bootstrap_create_multibit(fft.handle(), glwe_dimension, log_basis, decompose_length,
@@ -896,9 +914,14 @@ class TfheBootstrap32 {
   public:
     TfheBootstrap32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                     size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, bool with_keyswitch = true,
-                    size_t chunk = 0, size_t grouping_factor = 1) {
-        // grouping_factor 1: the classic rotation; above 1 the multi-bit one, on (lwe_dimension / g) * 2^g keys
-        check(grouping_factor == 1
+                    size_t chunk = 0, size_t grouping_factor = 1, uint32_t log_luts = 0) {
+        // grouping_factor 1: the classic rotation; above 1 the multi-bit one, on (lwe_dimension / g) * 2^g keys.  log_luts
+        // above 0: the many-LUT bootstrap, 2^log_luts outputs per input (output (e, i) at e * 2^log_luts + i)
+        check(log_luts != 0
+                  ? pfhe_tfhe32_bootstrap_create_many_lut(fft.handle(), glwe_dimension, log_basis, decompose_length,
+                                                          lwe_dimension, ks_log_basis, ks_decompose_length,
+                                                          with_keyswitch ? 1 : 0, grouping_factor, log_luts, chunk, &h_)
+              : grouping_factor == 1
                   ? pfhe_tfhe32_bootstrap_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension,
                                                ks_log_basis, ks_decompose_length, with_keyswitch ? 1 : 0, chunk, &h_)
                   : pfhe_tfhe32_bootstrap_create_multibit(fft.handle(), glwe_dimension, log_basis, decompose_length,
@@ -1210,6 +1233,15 @@ class TfheCircuitBootstrap {
         check(pfhe_tfhe_cbs_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis,
                                    cbs_decompose_length, pfks_log_basis, pfks_decompose_length, chunk, &h_));
     }
+    // with options (pfhe_tfhe_cbs_create_with): grouping_factor above 1 runs the multi-bit rotation on its key;
+    // shared_rotation runs one rotation per input for all levels of the output basis (many-LUT)
+    TfheCircuitBootstrap(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+        size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+        size_t pfks_decompose_length, size_t chunk, size_t grouping_factor, bool shared_rotation) {
+        check(pfhe_tfhe_cbs_create_with(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis,
+                                        cbs_decompose_length, pfks_log_basis, pfks_decompose_length, grouping_factor,
+                                        shared_rotation ? 1 : 0, chunk, &h_));
+    }
     ~TfheCircuitBootstrap() { pfhe_tfhe_cbs_destroy(h_); }
     TfheCircuitBootstrap(const TfheCircuitBootstrap &) = delete;
     TfheCircuitBootstrap &operator=(const TfheCircuitBootstrap &) = delete;
@@ -1237,6 +1269,13 @@ class TfheCircuitBootstrap32 {
         size_t pfks_decompose_length, size_t chunk = 0) {
         check(pfhe_tfhe32_cbs_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis,
                                    cbs_decompose_length, pfks_log_basis, pfks_decompose_length, chunk, &h_));
+    }
+    TfheCircuitBootstrap32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+        size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
+        size_t pfks_decompose_length, size_t chunk, size_t grouping_factor, bool shared_rotation) {
+        check(pfhe_tfhe32_cbs_create_with(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension,
+                                          cbs_log_basis, cbs_decompose_length, pfks_log_basis, pfks_decompose_length,
+                                          grouping_factor, shared_rotation ? 1 : 0, chunk, &h_));
     }
     ~TfheCircuitBootstrap32() { pfhe_tfhe32_cbs_destroy(h_); }
     TfheCircuitBootstrap32(const TfheCircuitBootstrap32 &) = delete;

@@ -14,7 +14,8 @@ from .lattice import (BlindRotateContext, BlindRotateContext32, blind_rotate, bl
 from .ntt import NttError, U32DcrtTable, U32NttTable, U64DcrtTable, U64NttTable  # noqa: F401
 from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateContext, TfheBootstrapContext,  # noqa: F401
                    TfheFftContext, TfheMultiBitBlindRotateContext, glwe_sample_extract, glwe_sample_extract_dev,
-                   lwe_keyswitch, lwe_keyswitch_dev, lwe_modulus_switch_dev, tfhe_blind_rotate, tfhe_blind_rotate_dev,
+                   lwe_keyswitch, lwe_keyswitch_dev, lwe_modulus_switch_dev, lwe_modulus_switch_strided_dev,
+                   tfhe_many_lut_test_vector, tfhe_blind_rotate, tfhe_blind_rotate_dev,
                    tfhe_bootstrap, tfhe_bootstrap_dev, tfhe_external_product_to, tfhe_external_product_to_dev,
                    tfhe_multibit_blind_rotate, tfhe_multibit_blind_rotate_dev, tfhe_multibit_combine_key_dev,
                    write_fourier_form, TfheKeyShape, ggsw_add_gadget_dev, glwe_encrypt, glwe_encrypt_dev, glwe_phase,
@@ -38,7 +39,7 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "glev_mul_big_uint_poly_to_dev", "BlindRotateContext", "BlindRotateContext32", "blind_rotate", "blind_rotate_dev",
            "FullComplex64FftTable", "ApproxSignedBasis", "TfheFftContext", "tfhe_external_product_to",
            "tfhe_external_product_to_dev", "write_fourier_form", "TfheBlindRotateContext", "tfhe_blind_rotate",
-           "tfhe_blind_rotate_dev", "lwe_modulus_switch_dev", "glwe_sample_extract", "glwe_sample_extract_dev",
+           "tfhe_blind_rotate_dev", "lwe_modulus_switch_dev", "lwe_modulus_switch_strided_dev", "tfhe_many_lut_test_vector", "glwe_sample_extract", "glwe_sample_extract_dev",
            "lwe_keyswitch", "lwe_keyswitch_dev", "TfheBootstrapContext", "tfhe_bootstrap", "tfhe_bootstrap_dev",
            "TfheMultiBitBlindRotateContext", "tfhe_multibit_blind_rotate", "tfhe_multibit_blind_rotate_dev",
            "tfhe_multibit_combine_key_dev", "lwe_encrypt", "lwe_encrypt_dev", "lwe_phase", "lwe_phase_dev", "glwe_encrypt",

@@ -211,6 +211,8 @@ def _declare(lib: C.CDLL) -> None:
         bs = tp + "bootstrap"
         sig(bs + "_create", ci, vp, sz, u32, sz, sz, u32, sz, ci, sz, C.POINTER(vp))
         sig(bs + "_create_multibit", ci, vp, sz, u32, sz, sz, u32, sz, ci, sz, sz, C.POINTER(vp))
+        sig(bs + "_create_many_lut", ci, vp, sz, u32, sz, sz, u32, sz, ci, sz, u32, sz, C.POINTER(vp))
+        sig(tp + "modswitch_stride_dev", ci, ci, vp, sz, sz, u32, u32, vp, sz, vp, sz, vp)
         sig(bs + "_destroy", None, vp)
         sig(bs + "_in_use", ci, vp)
         sig(bs + "_scratch_bytes", sz, vp)
@@ -246,6 +248,7 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "pfksk_generate_dev", ci, vp, sz, vp, sz, vp, sz, u32, sz, vp, sz, vp)
         cb = tp + "cbs"
         sig(cb + "_create", ci, vp, sz, u32, sz, sz, u32, sz, u32, sz, sz, C.POINTER(vp))
+        sig(cb + "_create_with", ci, vp, sz, u32, sz, sz, u32, sz, u32, sz, sz, ci, sz, C.POINTER(vp))
         sig(cb + "_destroy", None, vp)
         sig(cb + "_in_use", ci, vp)
         sig(cb + "_scratch_bytes", sz, vp)

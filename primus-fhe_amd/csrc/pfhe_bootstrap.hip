@@ -11,6 +11,8 @@
 //   key switch         out = (0, b) - sum_i sum_j d_{i,j} KSK[i][j], a sequence of Lwe::add_mul_scalar_assign
 //                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_word of
 //                      pfhe_fft_device.hpp, over the product's own digit_step).
+//   many-LUT           (pfhe_tfhe{,32}_bootstrap_create_many_lut) the strided switch and the extraction at every
+//                      index below 2^log_luts of pfhe_manylut.hip in place of the first and the fourth step.
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
 // the two forms of every call (stateless_call, handle_call) go through pfhe_tfhe_host.hpp; the key switch keeps its own
 // 2-D grid.
@@ -316,6 +318,7 @@ struct TfheBootstrapCore {
     PlanGuard guard;                      // one holder at a time, successive calls on different streams ordered
     const pfhe_fft *fft = nullptr;
     u32 k = 1, n = 0;  // GLWE and LWE dimensions
+    u32 log_luts = 0;  // many-LUT: 2^log_luts outputs per input, extracted at indices 0..2^log_luts-1 of one accumulator
     bool with_keyswitch = false;
     KsShape ks{};
     size_t chunk = 1, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
@@ -344,14 +347,20 @@ constexpr size_t kDefaultAccBytes = 256ull << 20;
 
 // The rotation's create first (its statuses, in its order), then what is the bootstrap's own.  With a grouping factor the
 // rotation is the multi-bit one, whose key has (lwe_dimension / g) 2^g keys; everything that decides before the device
-// is then decided first: the rotation's own checks in its order, then the divisibility
+// is then decided first: the rotation's own checks in its order, then the divisibility.  many_lut (create_many_lut): the
+// classic rotation's checks run here too, and log_luts above log N is refused right behind the rotation's, before the device
 template <class W, class H>
 int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
                      size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
-                     std::optional<size_t> grouping_factor, size_t chunk, H **out) {
+                     std::optional<size_t> grouping_factor, size_t chunk, H **out, bool many_lut = false,
+                     uint32_t log_luts = 0) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
+    if (many_lut && !grouping_factor) {
+        Shape sh{};
+        PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, sh));
+    }
     if (grouping_factor) {
         Shape sh{};
         PFHE_TRY(tfhe_mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, *grouping_factor, sh));
@@ -360,6 +369,11 @@ int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
             return PFHE_ERR_BAD_ARGUMENT;
         }
     }
+    if (many_lut && log_luts > fft->log_n) {
+        set_last_error("TFHE many-LUT bootstrap: log_luts must be at most log N");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    h->log_luts = log_luts;
     PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &h->rotation));
     const TfheRotation<W> &rot = *h->rotation;
     h->fft = fft;
@@ -377,7 +391,7 @@ int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
     h->chunk = chunk ? rot.chunk : std::min(rot.chunk, std::max<size_t>(1, kDefaultAccBytes / (glwe * sizeof(W))));
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const size_t sizes[] = {h->chunk * glwe * sizeof(W), h->with_keyswitch ? h->chunk * ext * sizeof(W) : 0,
+    const size_t sizes[] = {h->chunk * glwe * sizeof(W), h->with_keyswitch ? (h->chunk << log_luts) * ext * sizeof(W) : 0,
                             h->chunk * lwe_dimension * sizeof(u32), h->chunk * sizeof(u32)};
     void **bufs[] = {(void **)&h->acc, (void **)&h->extracted, (void **)&h->exps, (void **)&h->neg_b};
     for (int i = 0; i < 4; ++i) {
@@ -397,7 +411,7 @@ int bootstrap_check(const H *h, size_t len_in, size_t len_bsk, size_t len_tv, si
     const size_t ksk_words = h->with_keyswitch ? (ext - 1) * h->ks.ell * ((size_t)h->n + 1) : 0;
     batch = len_in / ((size_t)h->n + 1);
     if (len_in % ((size_t)h->n + 1) != 0 || len_bsk != h->bsk_len || (len_tv != glwe && len_tv != batch * glwe) ||
-        len_ksk != ksk_words || len_out != batch * out_words) {
+        len_ksk != ksk_words || len_out != (batch << h->log_luts) * out_words) {
         set_last_error(kBootstrapLengths);
         return PFHE_ERR_BAD_LENGTH;
     }
@@ -430,7 +444,7 @@ int bootstrap(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk
     }
     const pfhe_fft &f = *h->fft;
     const size_t glwe = h->rotation->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
-    const size_t out_words = h->with_keyswitch ? in_words : ext;
+    const size_t out_words = (h->with_keyswitch ? in_words : ext) << h->log_luts;  // of one input's 2^log_luts outputs
     const u64 tv_stride = len_tv == glwe ? 0 : glwe;
     // without a key switch ksk is empty: the host form does not stage it and the launches get a null pointer
     const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
@@ -442,12 +456,20 @@ int bootstrap(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk
         // chunk after chunk; every stage of a chunk is queued before the next chunk starts
         for (u64 done = 0; done < batch; done += h->chunk) {
             const u64 cur = std::min<u64>(h->chunk, batch - done);
-            PFHE_TRY(launch_modswitch<W>(in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, st));
+            if (h->log_luts)
+                PFHE_TRY(launch_modswitch_stride<W>(in + done * in_words, h->n, f.log_n, h->log_luts, (W)0, h->exps, h->neg_b, cur,
+                                                    st));
+            else
+                PFHE_TRY(launch_modswitch<W>(in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, st));
             PFHE_TRY(launch_acc_init<W>(vec + done * tv_stride, tv_stride, h->acc, h->neg_b, h->k + 1, f.log_n, cur, st));
             PFHE_TRY(h->rotation->rotate_dev(h->acc, cur * glwe, (const double *)d[1], len_bsk, h->exps, cur * h->n, st));
             W *lwe = h->with_keyswitch ? h->extracted : out + done * out_words;
-            PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, st));
-            if (h->with_keyswitch) PFHE_TRY(launch_keyswitch<W>(lwe, key, out + done * out_words, h->ks, cur, st));
+            if (h->log_luts)
+                PFHE_TRY(launch_multi_extract<W>(h->acc, lwe, h->k, f.log_n, 1u << h->log_luts, false, 0, 0, cur, st));
+            else
+                PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, st));
+            if (h->with_keyswitch)
+                PFHE_TRY(launch_keyswitch<W>(lwe, key, out + done * out_words, h->ks, cur << h->log_luts, st));
         }
         return PFHE_OK;
     });
@@ -556,6 +578,18 @@ int pfhe_tfhe_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimensi
                                  ks_decompose_length, with_keyswitch, grouping_factor, chunk, out);
     PFHE_GUARD_END
 }
+int pfhe_tfhe_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
+                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
+                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor,
+                                          uint32_t log_luts, size_t chunk, pfhe_tfhe_bootstrap_handle **out) {
+    PFHE_GUARD_BEGIN
+    if (out) *out = nullptr;
+    return bootstrap_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                 ks_decompose_length, with_keyswitch,
+                                 grouping_factor > 1 ? std::optional<size_t>(grouping_factor) : std::nullopt, chunk, out, true,
+                                 log_luts);
+    PFHE_GUARD_END
+}
 void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h) { delete h; }
 int pfhe_tfhe_bootstrap_in_use(const pfhe_tfhe_bootstrap_handle *h) { return h ? h->guard.in_use() : 0; }
 size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h) { return bootstrap_scratch(h); }
@@ -592,6 +626,18 @@ int pfhe_tfhe32_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimen
     if (out) *out = nullptr;
     return bootstrap_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
                                  ks_decompose_length, with_keyswitch, grouping_factor, chunk, out);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
+                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
+                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor,
+                                          uint32_t log_luts, size_t chunk, pfhe_tfhe32_bootstrap_handle **out) {
+    PFHE_GUARD_BEGIN
+    if (out) *out = nullptr;
+    return bootstrap_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                 ks_decompose_length, with_keyswitch,
+                                 grouping_factor > 1 ? std::optional<size_t>(grouping_factor) : std::nullopt, chunk, out, true,
+                                 log_luts);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h) { delete h; }

@@ -12,6 +12,9 @@
 //                        X^{neg_b[e]} TV_l with TV_l = (0, .., 0, -g_l/2 on every coefficient) written from constants, the
 //                        rotation handle on batch * levels accumulators, extraction at index 0 with g_l/2 added to the body,
 //                        and the private key switch with levels = ell_cb into the caller's GGSWs.
+//   ... with options     (pfhe_tfhe{,32}_cbs_create_with) the rotation is the multi-bit one, and / or ONE rotation
+//                        per input serves all levels: the strided switch, the patterned accumulator and the multi-index
+//                        extraction of pfhe_manylut.hip in place of the three kernels below, which stay as they are.
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
 // the two forms of every call (stateless_call, handle_call) go through pfhe_tfhe_host.hpp; the private key switch keeps
 // its own 3-D grid.
@@ -318,8 +321,9 @@ int pfksk_generate_dev(const pfhe_fft *f, size_t k, const W *key_in, size_t in_d
 
 // ---------------- the circuit bootstrap handle ----------------
 
-// Owns a blind rotation (the classic one, behind TfheRotation) and, for `chunk` inputs, chunk * ell_cb accumulators, their
-// switched exponents, neg_b and the extracted LWE ciphertexts: all allocated at creation.
+// Owns a blind rotation (classic or multi-bit, behind TfheRotation) and, for `chunk` inputs, chunk * ell_cb accumulators (chunk
+// with a shared rotation), their switched exponents, neg_b and the chunk * ell_cb extracted LWE ciphertexts: all allocated at
+// creation.
 template <class W>
 struct TfheCbsCore {
     TfheRotation<W> *rotation = nullptr;  // owned
@@ -327,6 +331,8 @@ struct TfheCbsCore {
     const pfhe_fft *fft = nullptr;
     u32 k = 1, n = 0;                      // GLWE and LWE dimensions
     u32 cb_log_basis = 0, cb_ell = 0, cb_drop = 0;
+    bool shared = false;  // one rotation per input serves all ell_cb levels (many-LUT): chunk accumulators, not chunk * ell_cb
+    u32 log_stride = 0;   // shared: ceil(log2 ell_cb), the stride bits of the modulus switch
     PfksShape pf{};
     size_t chunk = 1, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
     W *acc = nullptr, *extracted = nullptr;
@@ -353,15 +359,26 @@ constexpr const char *kCbsLengths =
 constexpr size_t kCbsDefaultAccBytes = 256ull << 20;
 
 // Everything that decides before the device first: the rotation's own checks in its order, then what is the circuit
-// bootstrap's own (the dimensions, the two bases' assert!s, drop_bits of the output basis); then the rotation's create
+// bootstrap's own (the dimensions, the two bases' assert!s, drop_bits of the output basis); then the rotation's create.
+// cbs_create_with adds: grouping_factor above 1 makes the rotation the multi-bit one (its range with the rotation's checks,
+// then the divisibility, as bootstrap_create refuses them); shared_rotation refuses ell_cb above N last of all
 template <class W, class H>
 int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t lwe_dimension,
                uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis, size_t pfks_decompose_length,
-               size_t chunk, H **out) {
+               size_t chunk, H **out, size_t grouping_factor = 1, bool shared = false) {
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     Shape rot_shape{};
-    PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, rot_shape));
+    const std::optional<size_t> grouping = grouping_factor > 1 ? std::optional<size_t>(grouping_factor) : std::nullopt;
+    if (grouping) {
+        PFHE_TRY(tfhe_mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, *grouping, rot_shape));
+        if (lwe_dimension % *grouping != 0) {
+            set_last_error("TFHE circuit bootstrap: lwe_dimension must be a multiple of grouping_factor");
+            return PFHE_ERR_BAD_ARGUMENT;
+        }
+    } else {
+        PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, rot_shape));
+    }
     // a zero glwe_dimension is refused as a zero lwe_dimension is: one message for both
     PFHE_TRY(require_lwe_dimension(glwe_dimension ? lwe_dimension : 0,
                                    "TFHE circuit bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2"));
@@ -373,9 +390,16 @@ int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, s
         set_last_error("TFHE circuit bootstrap: the output basis must drop at least one bit (g_l / 2 must be a word)");
         return PFHE_ERR_BAD_ARGUMENT;
     }
-    // chunk inputs are chunk * ell_cb accumulators of the rotation; 0 stays the rotation's default
+    if (shared && h->cb_ell > fft->n) {
+        set_last_error("TFHE circuit bootstrap: a shared rotation serves at most N levels of the output basis");
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    h->shared = shared;
+    while (shared && (1u << h->log_stride) < h->cb_ell) ++h->log_stride;
+    // chunk inputs are chunk * ell_cb accumulators of the rotation, or chunk with a shared one; 0 stays the rotation's default
+    const size_t per_input = shared ? 1 : h->cb_ell;
     if (chunk > 0x7fffffffull / h->cb_ell) return PFHE_ERR_BAD_LENGTH;
-    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, std::nullopt, chunk * h->cb_ell,
+    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping, chunk * per_input,
                                      &h->rotation));
     const TfheRotation<W> &rot = *h->rotation;
     h->fft = fft;
@@ -384,14 +408,14 @@ int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, s
     h->cb_log_basis = cbs_log_basis;
     const size_t glwe = rot.glwe, ext = glwe_dimension * fft->n + 1, levels = h->cb_ell;
     h->pf = PfksShape{(u32)(ext - 1), h->k, fft->log_n, h->cb_ell, pfks_log_basis, pf_ell, pf_drop, pfks_group_words(pf_ell)};
-    h->bsk_len = lwe_dimension * rot.key_len;
+    h->bsk_len = (grouping ? (lwe_dimension / *grouping) << *grouping : lwe_dimension) * rot.key_len;
     // chunk 0: what the rotation's default holds, capped at about 256 MiB of accumulators
     h->chunk = chunk ? chunk
-                     : std::max<size_t>(1, std::min(rot.chunk, kCbsDefaultAccBytes / (glwe * sizeof(W))) / levels);
+                     : std::max<size_t>(1, std::min(rot.chunk, kCbsDefaultAccBytes / (glwe * sizeof(W))) / per_input);
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const size_t accs = h->chunk * levels;
-    const size_t sizes[] = {accs * glwe * sizeof(W), accs * ext * sizeof(W), accs * lwe_dimension * sizeof(u32),
+    const size_t accs = h->chunk * per_input, rows = h->chunk * levels;
+    const size_t sizes[] = {accs * glwe * sizeof(W), rows * ext * sizeof(W), accs * lwe_dimension * sizeof(u32),
                             h->chunk * sizeof(u32)};
     void **bufs[] = {(void **)&h->acc, (void **)&h->extracted, (void **)&h->exps, (void **)&h->neg_b};
     for (int i = 0; i < 4; ++i) {
@@ -442,17 +466,31 @@ int cbs(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk, size
     const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
                              stage_in(pfksk, len_pfksk * sizeof(W)), stage_out(ggsw_out, len_out * sizeof(W))};
     return handle_call(h->guard, f.device, form, bufs, s, [&](void *const *d, hipStream_t st) -> int {
-        // chunk after chunk; every stage of a chunk is queued before the next chunk starts
+        // chunk after chunk; every stage of a chunk is queued before the next chunk starts.  accs: the accumulators of the
+        // chunk, one per input with a shared rotation (the switch to multiples of 2^log_stride, the patterned test vector,
+        // level l read off coefficient l), one per input and level without
+        const W *in = (const W *)d[0];
         for (u64 done = 0; done < batch; done += h->chunk) {
-            const u64 cur = std::min<u64>(h->chunk, batch - done), accs = cur * levels;
-            PFHE_TRY(launch_flat(tfhe_cbs_modswitch_kernel<W>, cur * in_words, st, (const W *)d[0] + done * in_words, h->exps,
-                                 h->neg_b, h->n, f.log_n, levels));
-            PFHE_TRY(launch_flat(tfhe_cbs_acc_init_kernel<W>, accs * glwe, st, h->acc, (const u32 *)h->neg_b, h->k, f.log_n, levels,
-                                 h->cb_log_basis, half_shift));
+            const u64 cur = std::min<u64>(h->chunk, batch - done), accs = h->shared ? cur : cur * levels;
+            if (h->shared) {
+                PFHE_TRY(launch_modswitch_stride<W>(in + done * in_words, h->n, f.log_n, h->log_stride, (W)1 << (8 * sizeof(W) - 2),
+                                                    h->exps, h->neg_b, cur, st));
+                PFHE_TRY(launch_pattern_acc_init<W>(h->acc, h->neg_b, h->k, f.log_n, h->log_stride, levels, h->cb_log_basis,
+                                                    half_shift, cur, st));
+            } else {
+                PFHE_TRY(launch_flat(tfhe_cbs_modswitch_kernel<W>, cur * in_words, st, in + done * in_words, h->exps, h->neg_b, h->n,
+                                     f.log_n, levels));
+                PFHE_TRY(launch_flat(tfhe_cbs_acc_init_kernel<W>, accs * glwe, st, h->acc, (const u32 *)h->neg_b, h->k, f.log_n,
+                                     levels, h->cb_log_basis, half_shift));
+            }
             PFHE_TRY(h->rotation->rotate_dev(h->acc, accs * glwe, (const double *)d[1], len_bsk, h->exps, accs * h->n, st));
-            PFHE_TRY(launch_flat(tfhe_cbs_extract_kernel<W>, accs * ext, st, (const W *)h->acc, h->extracted, h->k, f.log_n, levels,
-                                 h->cb_log_basis, half_shift));
-            PFHE_TRY(launch_pfks<W>(h->extracted, (const W *)d[2], (W *)d[3] + done * ggsw, h->pf, accs, st));
+            if (h->shared)
+                PFHE_TRY(launch_multi_extract<W>(h->acc, h->extracted, h->k, f.log_n, levels, true, h->cb_log_basis, half_shift, cur,
+                                                 st));
+            else
+                PFHE_TRY(launch_flat(tfhe_cbs_extract_kernel<W>, accs * ext, st, (const W *)h->acc, h->extracted, h->k, f.log_n,
+                                     levels, h->cb_log_basis, half_shift));
+            PFHE_TRY(launch_pfks<W>(h->extracted, (const W *)d[2], (W *)d[3] + done * ggsw, h->pf, cur * levels, st));
         }
         return PFHE_OK;
     });
@@ -528,6 +566,15 @@ int pfhe_tfhe_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t lo
                            pfks_log_basis, pfks_decompose_length, chunk, out);
     PFHE_GUARD_END
 }
+int pfhe_tfhe_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                              size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,
+                              uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t grouping_factor, int shared_rotation,
+                              size_t chunk, pfhe_tfhe_cbs_handle **out) {
+    PFHE_GUARD_BEGIN
+    return cbs_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
+                           pfks_log_basis, pfks_decompose_length, chunk, out, grouping_factor, shared_rotation != 0);
+    PFHE_GUARD_END
+}
 void pfhe_tfhe_cbs_destroy(pfhe_tfhe_cbs_handle *h) { delete h; }
 int pfhe_tfhe_cbs_in_use(const pfhe_tfhe_cbs_handle *h) { return h ? h->guard.in_use() : 0; }
 size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h) { return cbs_scratch(h); }
@@ -552,6 +599,15 @@ int pfhe_tfhe32_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t 
     PFHE_GUARD_BEGIN
     return cbs_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
                            pfks_log_basis, pfks_decompose_length, chunk, out);
+    PFHE_GUARD_END
+}
+int pfhe_tfhe32_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                                size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,
+                                uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t grouping_factor,
+                                int shared_rotation, size_t chunk, pfhe_tfhe32_cbs_handle **out) {
+    PFHE_GUARD_BEGIN
+    return cbs_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
+                           pfks_log_basis, pfks_decompose_length, chunk, out, grouping_factor, shared_rotation != 0);
     PFHE_GUARD_END
 }
 void pfhe_tfhe32_cbs_destroy(pfhe_tfhe32_cbs_handle *h) { delete h; }

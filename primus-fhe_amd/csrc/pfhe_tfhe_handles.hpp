@@ -197,4 +197,18 @@ int tfhe_digit_fwd_launch(const pfhe_fft &f, const Shape &sh, const W *in, doubl
 template <class W>
 int tfhe_half_inverse_launch(const pfhe_fft &f, const double2 *acc, W *out, u64 polys, hipStream_t s);
 
+// The many-LUT steps around a rotation (pfhe_manylut.hip, instantiated for u32 and u64), arguments already checked and the
+// device current: the modulus switch to multiples of 2^log_stride (body_offset is added to the body word first), the
+// accumulator X^{neg_b[e]} TV of the shared circuit bootstrap written from constants, and sample extraction at every index
+// below `count` of every accumulator into row e * count + h (add_half: plus 2^(half_shift + h log_basis) on the body).
+template <class W>
+int launch_modswitch_stride(const W *lwe, u32 n, u32 log_n, u32 log_stride, W body_offset, u32 *exps, u32 *neg_b, u64 batch,
+                            hipStream_t s);
+template <class W>
+int launch_pattern_acc_init(W *acc, const u32 *neg_b, u32 k, u32 log_n, u32 log_stride, u32 levels, u32 log_basis,
+                            u32 half_shift, u64 batch, hipStream_t s);
+template <class W>
+int launch_multi_extract(const W *glwe, W *lwe, u32 k, u32 log_n, u32 count, bool add_half, u32 log_basis, u32 half_shift,
+                         u64 batch, hipStream_t s);
+
 }  // namespace pfhe

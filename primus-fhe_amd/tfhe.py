@@ -341,6 +341,35 @@ def lwe_modulus_switch_dev(lwe, lwe_dimension: int, log_n: int, exps, neg_b, dev
                                                             pb, nb, _stream(stream)))
 
 
+def lwe_modulus_switch_strided_dev(lwe, lwe_dimension: int, log_n: int, log_stride: int, exps, neg_b, device=None,
+                                   stream=None) -> None:
+    """The modulus switch to multiples of 2^log_stride (0 <= log_stride <= log_n), what a many-LUT rotation takes:
+    exps[e*n + i] = sw_v(a_{e,i}) and neg_b[e] = (2N - sw_v(b_e)) mod 2N with
+    sw_v(w) = ((((w >> (BITS - log_n - 2 + v)) + 1) >> 1) << v) & (2N-1): w * 2N / 2^v / 2^BITS rounded to nearest, ties up,
+    times 2^v; a word that rounds up to 2N wraps to 0.  log_stride 0 is lwe_modulus_switch_dev, word for word."""
+    pl, nl, w = _dev_words(lwe)
+    pe, ne = _dev_exps(exps)
+    pb, nb = _dev_exps(neg_b)
+    check(getattr(lib(), "pfhe_tfhe" + w + "_modswitch_stride_dev")(_dev_index(lwe, device), pl, nl, lwe_dimension, log_n,
+                                                                   log_stride, pe, ne, pb, nb, _stream(stream)))
+
+
+def tfhe_many_lut_test_vector(tvs):
+    """The test vector of a many-LUT bootstrap from 2^v ordinary ones: tvs is a (2^v, ..., N) torch tensor (or a sequence of
+    2^v tensors of one shape) of test vectors, polynomial coefficients last, and TV[c] = tvs[c mod 2^v][c - (c mod 2^v)]
+    for every polynomial.  The strided switch makes the rotated phase p a multiple of 2^v, so coefficient i < 2^v of
+    ACC = X^{-p} * TV is TV[p + i] = tvs[i][p] for p < N and -TV[p - N + i] = -tvs[i][p - N] otherwise: output i of the
+    bootstrap is what an ordinary bootstrap with tvs[i] gives at the stride-rounded phase, with one sign for all i."""
+    import torch
+    t = torch.stack(list(tvs)) if not hasattr(tvs, "shape") else tvs
+    luts, n = t.shape[0], t.shape[-1]
+    if luts == 0 or luts & (luts - 1) or n % luts:
+        raise ValueError("expected 2^v test vectors of N coefficients, 2^v dividing N")
+    c = torch.arange(n, device=t.device)
+    low = c % luts
+    return t[low, ..., c - low].movedim(0, -1).contiguous()
+
+
 def _sample_extract(dev, glwe, lwe, fft, glwe_dimension, index, stream=None) -> None:
     _stateless("_sample_extract", dev, (glwe, lwe), "glwe and lwe must have the same word width",
                lambda w, g, o: (fft._h, glwe_dimension, *g, index, *o), stream)
@@ -389,21 +418,28 @@ class TfheBootstrapContext(_TorusContext):
     """Handle of the batched programmable bootstrap (include/pfhe.h, pfhe_tfhe{,32}_bootstrap_*): modulus switch,
     ACC = X^{-b~} * TV, the blind rotation over lwe_dimension steps (grouping_factor above 1: the multi-bit rotation over
     lwe_dimension / grouping_factor groups, on the multi-bit key), sample extraction at index 0 and, when ks_basis is
-    given, the key switch back to lwe_dimension.  Owns a blind-rotation handle and every buffer between the stages for
-    `chunk` ciphertexts (0 = the default); one holder at a time (Busy for a second thread)."""
+    given, the key switch back to lwe_dimension.  log_luts = v above 0 (at most log N) is the many-LUT bootstrap: the
+    modulus switch is lwe_modulus_switch_strided_dev with v, the accumulator is extracted at every index i < 2^v, and
+    lwe_out holds batch * 2^v ciphertexts, output (e, i) at e * 2^v + i; tfhe_many_lut_test_vector builds its test vector.
+    Owns a blind-rotation handle and every buffer between the stages for `chunk` ciphertexts (0 = the default); one holder
+    at a time (Busy for a second thread)."""
 
     def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int = 1,
-                 ks_basis: ApproxSignedBasis | None = None, chunk: int = 0, grouping_factor: int = 1):
+                 ks_basis: ApproxSignedBasis | None = None, chunk: int = 0, grouping_factor: int = 1, log_luts: int = 0):
         if ks_basis is not None and ks_basis.bits != basis.bits:
             raise TypeError("both bases must have the width of the torus words")
         args = (lwe_dimension, ks_basis.log_basis() if ks_basis else 0, ks_basis.decompose_length() if ks_basis else 0,
                 1 if ks_basis else 0)
         calls = ("_destroy", "_in_use", "_scratch_bytes")
-        if grouping_factor == 1:
+        if log_luts:    # many-LUT: the switch to multiples of 2^log_luts and 2^log_luts outputs per input
+            self._open(fft, basis, glwe_dimension, "bootstrap", args + (grouping_factor, log_luts, chunk),
+                       ("_create_many_lut",) + calls)
+        elif grouping_factor == 1:
             self._open(fft, basis, glwe_dimension, "bootstrap", args + (chunk,), ("_create",) + calls)
         else:   # the multi-bit rotation: bsk is (lwe_dimension / g) * 2^g keys
             self._open(fft, basis, glwe_dimension, "bootstrap", args + (grouping_factor, chunk), ("_create_multibit",) + calls)
         self.grouping_factor, self.ks_basis, self.lwe_dimension = grouping_factor, ks_basis, lwe_dimension
+        self.log_luts = log_luts
 
 
     def bsk_len(self) -> int:
@@ -759,21 +795,33 @@ class TfheCircuitBootstrapContext(_TorusContext):
     the modulus switch of (a, b + 2^(BITS-2)), ACC = X^{-b~} * (0, .., 0, -g_l/2 on every coefficient), the blind rotation
     over lwe_dimension steps under `basis`, sample extraction at index 0 with g_l/2 added to the body, and the private
     functional key switch under `pfks_basis` with levels = cbs_basis.decompose_length().  cbs_basis must drop at least
-    one bit.  Owns a blind-rotation handle and every buffer between the stages for `chunk` inputs (0 = the default); one
-    holder at a time (Busy for a second thread)."""
+    one bit.  grouping_factor above 1 runs the multi-bit rotation on the multi-bit key of tfhe_generate_bsk_dev.
+    shared_rotation runs ONE rotation per input for all levels (many-LUT): with v = ceil(log2 ell_cb) the switch is
+    lwe_modulus_switch_strided_dev with v, the test vector's body coefficient c is -g_{c mod 2^v}/2 (0 where the basis has no
+    such level), and level l is extracted at index l; ell_cb must be at most N.  The switch then rounds every word to a
+    multiple of 2^v: its worst-case margin shrinks by that factor.  Owns a blind-rotation handle and every
+    buffer between the stages for `chunk` inputs (0 = the default); one holder at a time (Busy for a second thread)."""
 
     def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int,
-                 cbs_basis: ApproxSignedBasis, pfks_basis: ApproxSignedBasis, chunk: int = 0):
+                 cbs_basis: ApproxSignedBasis, pfks_basis: ApproxSignedBasis, chunk: int = 0, grouping_factor: int = 1,
+                 shared_rotation: bool = False):
         if cbs_basis.bits != basis.bits or pfks_basis.bits != basis.bits:
             raise TypeError("every basis must have the width of the torus words")
         args = (lwe_dimension, cbs_basis.log_basis(), cbs_basis.decompose_length(), pfks_basis.log_basis(),
-                pfks_basis.decompose_length(), chunk)
-        self._open(fft, basis, glwe_dimension, "cbs", args, ("_create", "_destroy", "_in_use", "_scratch_bytes"))
+                pfks_basis.decompose_length())
+        calls = ("_destroy", "_in_use", "_scratch_bytes")
+        if grouping_factor == 1 and not shared_rotation:
+            self._open(fft, basis, glwe_dimension, "cbs", args + (chunk,), ("_create",) + calls)
+        else:
+            self._open(fft, basis, glwe_dimension, "cbs", args + (grouping_factor, 1 if shared_rotation else 0, chunk),
+                       ("_create_with",) + calls)
         self.lwe_dimension, self.cbs_basis, self.pfks_basis = lwe_dimension, cbs_basis, pfks_basis
+        self.grouping_factor, self.shared_rotation = grouping_factor, bool(shared_rotation)
 
     def bsk_len(self) -> int:
-        """complex values of the bootstrapping key: lwe_dimension Fourier GGSW keys"""
-        return self.lwe_dimension * self.key_len()
+        """complex values of the bootstrapping key: lwe_dimension Fourier GGSW keys, or (lwe_dimension / g) * 2^g multi-bit keys"""
+        g = self.grouping_factor
+        return (self.lwe_dimension if g == 1 else (self.lwe_dimension // g) << g) * self.key_len()
 
     def extracted_dimension(self) -> int:
         return self.glwe_dimension * self.fft.poly_length()
