@@ -313,26 +313,10 @@ int keyswitch(Form form, int device, const W *lwe_in, size_t len_in, size_t in_d
 // Owns a blind rotation (classic or multi-bit, behind TfheRotation) and, for `chunk` ciphertexts, the accumulator, the
 // switched exponents, neg_b and (when a key switch follows) the extracted LWE ciphertexts: all allocated at creation.
 template <class W>
-struct TfheBootstrapCore {
-    TfheRotation<W> *rotation = nullptr;  // owned
-    PlanGuard guard;                      // one holder at a time, successive calls on different streams ordered
-    const pfhe_fft *fft = nullptr;
-    u32 k = 1, n = 0;  // GLWE and LWE dimensions
+struct TfheBootstrapCore : TfheBootstrapBase<W> {
     u32 log_luts = 0;  // many-LUT: 2^log_luts outputs per input, extracted at indices 0..2^log_luts-1 of one accumulator
     bool with_keyswitch = false;
     KsShape ks{};
-    size_t chunk = 1, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
-    W *acc = nullptr, *extracted = nullptr;
-    u32 *exps = nullptr, *neg_b = nullptr;
-    ~TfheBootstrapCore() {
-        if (!rotation) return;
-        {
-            DeviceGuard g(fft->device);
-            for (void *b : {(void *)acc, (void *)extracted, (void *)exps, (void *)neg_b})
-                if (b) (void)counted_free(b);
-        }
-        delete rotation;
-    }
 };
 struct pfhe_tfhe_bootstrap_handle : TfheBootstrapCore<u64> {};
 struct pfhe_tfhe32_bootstrap_handle : TfheBootstrapCore<u32> {};
@@ -357,24 +341,19 @@ int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
-    if (many_lut && !grouping_factor) {
+    if (many_lut || grouping_factor) {  // the plain create leaves every check to the rotation's create
         Shape sh{};
-        PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, sh));
-    }
-    if (grouping_factor) {
-        Shape sh{};
-        PFHE_TRY(tfhe_mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, *grouping_factor, sh));
-        if (lwe_dimension % *grouping_factor != 0) {
-            set_last_error("TFHE multi-bit bootstrap: lwe_dimension must be a multiple of grouping_factor");
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
+        PFHE_TRY(tfhe_bootstrap_check<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, lwe_dimension,
+                                         "TFHE multi-bit bootstrap: lwe_dimension must be a multiple of grouping_factor", sh));
     }
     if (many_lut && log_luts > fft->log_n) {
         set_last_error("TFHE many-LUT bootstrap: log_luts must be at most log N");
         return PFHE_ERR_BAD_ARGUMENT;
     }
     h->log_luts = log_luts;
-    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &h->rotation));
+    TfheRotation<W> *rotation = nullptr;
+    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, &rotation));
+    h->rotation.reset(rotation);
     const TfheRotation<W> &rot = *h->rotation;
     h->fft = fft;
     h->k = (u32)glwe_dimension;
@@ -384,21 +363,17 @@ int bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
     PFHE_TRY(require_lwe_dimension(glwe_dimension ? lwe_dimension : 0,
                                    "TFHE bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2"));
     h->n = (u32)lwe_dimension;
-    const size_t keys = grouping_factor ? (lwe_dimension / *grouping_factor) << *grouping_factor : lwe_dimension;
-    h->bsk_len = keys * rot.key_len;
+    h->bsk_len = tfhe_bootstrap_keys(grouping_factor, lwe_dimension) * rot.key_len;
     if (h->with_keyswitch) PFHE_TRY(keyswitch_shape<W>(ext - 1, lwe_dimension, ks_log_basis, ks_decompose_length, h->ks));
     // chunk 0: the rotation's default, capped at about 256 MiB of accumulator
     h->chunk = chunk ? rot.chunk : std::min(rot.chunk, std::max<size_t>(1, kDefaultAccBytes / (glwe * sizeof(W))));
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    const size_t sizes[] = {h->chunk * glwe * sizeof(W), h->with_keyswitch ? (h->chunk << log_luts) * ext * sizeof(W) : 0,
-                            h->chunk * lwe_dimension * sizeof(u32), h->chunk * sizeof(u32)};
-    void **bufs[] = {(void **)&h->acc, (void **)&h->extracted, (void **)&h->exps, (void **)&h->neg_b};
-    for (int i = 0; i < 4; ++i) {
-        if (!sizes[i]) continue;
-        PFHE_HIP(counted_malloc(bufs[i], sizes[i]));
-        h->bytes += sizes[i];
-    }
+    h->bufs.bind(fft->device);
+    PFHE_TRY(h->bufs.add(h->acc, h->chunk * glwe));
+    PFHE_TRY(h->bufs.add(h->extracted, h->with_keyswitch ? (h->chunk << log_luts) * ext : 0));
+    PFHE_TRY(h->bufs.add(h->exps, h->chunk * lwe_dimension));
+    PFHE_TRY(h->bufs.add(h->neg_b, h->chunk));
     PFHE_TRY(h->guard.init(fft->device));
     *out = h.release();
     return PFHE_OK;
@@ -473,11 +448,6 @@ int bootstrap(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk
         }
         return PFHE_OK;
     });
-}
-
-template <class H>
-size_t bootstrap_scratch(const H *h) {
-    return h && h->rotation ? h->rotation->scratch_bytes() + h->bytes : 0;
 }
 
 }  // namespace
@@ -592,7 +562,7 @@ int pfhe_tfhe_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimensi
 }
 void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h) { delete h; }
 int pfhe_tfhe_bootstrap_in_use(const pfhe_tfhe_bootstrap_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h) { return bootstrap_scratch(h); }
+size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h) { return tfhe_bootstrap_scratch(h); }
 int pfhe_tfhe_bootstrap_dev(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
                             size_t len_bsk, const uint64_t *tv_dev, size_t len_tv, const uint64_t *ksk_dev, size_t len_ksk,
                             uint64_t *lwe_out_dev, size_t len_out, void *stream) {
@@ -642,7 +612,7 @@ int pfhe_tfhe32_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimen
 }
 void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h) { delete h; }
 int pfhe_tfhe32_bootstrap_in_use(const pfhe_tfhe32_bootstrap_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_bootstrap_scratch_bytes(const pfhe_tfhe32_bootstrap_handle *h) { return bootstrap_scratch(h); }
+size_t pfhe_tfhe32_bootstrap_scratch_bytes(const pfhe_tfhe32_bootstrap_handle *h) { return tfhe_bootstrap_scratch(h); }
 int pfhe_tfhe32_bootstrap_dev(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
                               size_t len_bsk, const uint32_t *tv_dev, size_t len_tv, const uint32_t *ksk_dev, size_t len_ksk,
                               uint32_t *lwe_out_dev, size_t len_out, void *stream) {

@@ -42,17 +42,11 @@ struct ExtprodPlanCore {
     // decomposition, between the decomposition and the transform / multiply-accumulate, and after it, per chunk
     std::vector<hipEvent_t> *prof = nullptr;
     W *digits = nullptr;
-    size_t digits_words = 0;
     // compact signed digits of one chunk (chunk * (k+1) * ell * N words of sdigit_bytes), or null.  u64: int32 when
     // log_basis <= 31, else int64; u32: balanced int32 digits, for N = 2^16, k = 1 (the fused kernels)
     void *sdigits = nullptr;
     size_t sdigit_bytes = 0;
-    ~ExtprodPlanCore() {
-        if (!table) return;
-        DeviceGuard g(table->device);
-        if (digits) (void)counted_free(digits);
-        if (sdigits) (void)counted_free(sdigits);
-    }
+    DeviceBuffers bufs;
 };
 struct pfhe_extprod_plan : ExtprodPlanCore<u64> {};
 struct pfhe_extprod32_plan : ExtprodPlanCore<u32> {};
@@ -617,17 +611,15 @@ int plan_create(const Table *table, const Rns *rns, const Basis *basis, size_t g
         chunk = std::max<size_t>(128, std::min<size_t>(65536, budget / per_ct));
     }
     p->chunk = chunk;
-    p->digits_words = p->chunk * (p->k + 1) * p->basis.ell * t->L * t->n;
+    const size_t digits_words = p->chunk * (p->k + 1) * p->basis.ell * t->L * t->n;
     DeviceGuard g(t->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     // read here, once, and kept in the plan (nothing on the launch path calls getenv)
     p->use_fused = std::getenv("PFHE_DISABLE_FUSED_EXTPROD") == nullptr;
-    void *d = nullptr;
-    PFHE_HIP(counted_malloc(&d, p->digits_words * sizeof(W)));
-    p->digits = (W *)d;
+    p->bufs.bind(t->device);
+    PFHE_TRY(p->bufs.add(p->digits, digits_words));
     p->sdigit_bytes = sdigit_bytes_for(*p);
-    if (p->sdigit_bytes)
-        PFHE_HIP(counted_malloc(&p->sdigits, p->chunk * (p->k + 1) * p->basis.ell * t->n * p->sdigit_bytes));
+    PFHE_TRY(p->bufs.add(p->sdigits, p->chunk * (p->k + 1) * p->basis.ell * t->n * p->sdigit_bytes));
     PFHE_TRY(p->guard.init(t->device));
     *out = p.release();
     return PFHE_OK;
@@ -635,9 +627,7 @@ int plan_create(const Table *table, const Rns *rns, const Basis *basis, size_t g
 
 template <class Plan>
 size_t plan_scratch_bytes(const Plan *p) {
-    if (!p) return 0;
-    return p->digits_words * sizeof(typename Plan::Word) +
-           (p->sdigits ? p->chunk * (p->k + 1) * p->basis.ell * p->table->n * p->sdigit_bytes : 0);
+    return p ? p->bufs.bytes() : 0;
 }
 
 template <class Plan, class W>
@@ -900,19 +890,11 @@ int pfhe_extprod32_glev_mul_big_uint_poly_to_dev(pfhe_extprod32_plan *plan, cons
 // nothing and synchronises with nothing, so one whole rotation can be captured into a HIP graph.
 template <class Plan, class W>
 struct BlindRotCore {
-    Plan *plan = nullptr;  // owned
-    PlanGuard guard;       // one holder at a time and cross-stream ordering of successive calls, as the plan
+    PlanGuard guard;             // one holder at a time and cross-stream ordering of successive calls, as the plan
+    std::unique_ptr<Plan> plan;  // owned
     W *d = nullptr, *e = nullptr, *ping = nullptr;  // chunk * glwe words each
     size_t glwe = 0, ggsw = 0;
-    ~BlindRotCore() {
-        if (!plan) return;
-        {
-            DeviceGuard g(plan->table->device);
-            for (W *b : {d, e, ping})
-                if (b) (void)counted_free(b);
-        }
-        delete plan;
-    }
+    DeviceBuffers bufs;  // after the plan: the glue buffers are freed first, then the plan, then the guard's event
 };
 struct pfhe_blindrot : BlindRotCore<pfhe_extprod_plan, u64> {};
 struct pfhe_blindrot32 : BlindRotCore<pfhe_extprod32_plan, u32> {};
@@ -924,18 +906,16 @@ int blindrot_create(const Table *table, const Rns *base, const Basis *basis, siz
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
-    PFHE_TRY(plan_create(table, base, basis, glwe_dimension, chunk, &h->plan));
+    decltype(h->plan.get()) plan = nullptr;
+    PFHE_TRY(plan_create(table, base, basis, glwe_dimension, chunk, &plan));
+    h->plan.reset(plan);
     const TableSet &t = *h->plan->table;
     h->glwe = (size_t)(h->plan->k + 1) * t.L * t.n;
     h->ggsw = (size_t)(h->plan->k + 1) * h->plan->basis.ell * h->glwe;
     DeviceGuard g(t.device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    using W = typename std::remove_pointer<decltype(h->d)>::type;
-    for (W **b : {&h->d, &h->e, &h->ping}) {
-        void *p = nullptr;
-        PFHE_HIP(counted_malloc(&p, h->plan->chunk * h->glwe * sizeof(W)));
-        *b = (W *)p;
-    }
+    h->bufs.bind(t.device);
+    for (auto **b : {&h->d, &h->e, &h->ping}) PFHE_TRY(h->bufs.add(*b, h->plan->chunk * h->glwe));
     PFHE_TRY(h->guard.init(t.device));
     *out = h.release();
     return PFHE_OK;
@@ -943,20 +923,20 @@ int blindrot_create(const Table *table, const Rns *base, const Basis *basis, siz
 template <class H>
 size_t blindrot_scratch_bytes(const H *h) {
     if (!h || !h->plan) return 0;
-    return plan_scratch_bytes(h->plan) + 3 * h->plan->chunk * h->glwe * sizeof(*h->d);
+    return h->plan->bufs.bytes() + h->bufs.bytes();
 }
 
 // Fused small-ring step (u64 only): taken under exactly the condition run_product takes extprod_small_kernel under.
 // Two launches per step, no D or E buffer: digits of X^r * ACC - ACC, then the product whose epilogue adds E to ACC.
 bool blindrot_small_fused(const pfhe_blindrot *h, u64 cur) {
-    const pfhe_extprod_plan *p = h->plan;
+    const pfhe_extprod_plan *p = h->plan.get();
     const TableSet &t = *p->table;
     return p->sdigits != nullptr && extprod_small_supported(t.log_n, p->k, p->rns.dev.value_len, p->basis.log_basis) &&
            cur * t.L >= 1024 && p->use_fused;
 }
 bool blindrot_small_fused(const pfhe_blindrot32 *, u64) { return false; }
 int blindrot_small_steps(pfhe_blindrot *h, u64 *acc, const u64 *bsk, const u32 *exps, u64 n_steps, u64 cur, hipStream_t s) {
-    const pfhe_extprod_plan *p = h->plan;
+    const pfhe_extprod_plan *p = h->plan.get();
     const TableSet &t = *p->table;
     RnsParams rns = p->rns;
     rns.dev.big_input = rns.wide_tab.big_input = 0u;
@@ -1019,7 +999,7 @@ int blindrot_rotate_dev(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_b
             }
             for (u64 i = 0; i < n_steps && rc == PFHE_OK; ++i) {
                 // the product of one step: E = coeff_form(D (x) BSK_i) for `cur` ciphertexts
-                rc = mul_dcrt_ggsw_to_dev(h->plan, h->d, cur * h->glwe, bsk + i * h->ggsw, h->ggsw, h->e, cur * h->glwe, 1, s);
+                rc = mul_dcrt_ggsw_to_dev(h->plan.get(), h->d, cur * h->glwe, bsk + i * h->ggsw, h->ggsw, h->e, cur * h->glwe, 1, s);
                 if (rc != PFHE_OK) break;
                 W *dst = src == a0 ? h->ping : a0;
                 rc = i + 1 < n_steps

@@ -325,27 +325,11 @@ int pfksk_generate_dev(const pfhe_fft *f, size_t k, const W *key_in, size_t in_d
 // with a shared rotation), their switched exponents, neg_b and the chunk * ell_cb extracted LWE ciphertexts: all allocated at
 // creation.
 template <class W>
-struct TfheCbsCore {
-    TfheRotation<W> *rotation = nullptr;  // owned
-    PlanGuard guard;                      // one holder at a time, successive calls on different streams ordered
-    const pfhe_fft *fft = nullptr;
-    u32 k = 1, n = 0;                      // GLWE and LWE dimensions
+struct TfheCbsCore : TfheBootstrapBase<W> {
     u32 cb_log_basis = 0, cb_ell = 0, cb_drop = 0;
     bool shared = false;  // one rotation per input serves all ell_cb levels (many-LUT): chunk accumulators, not chunk * ell_cb
     u32 log_stride = 0;   // shared: ceil(log2 ell_cb), the stride bits of the modulus switch
     PfksShape pf{};
-    size_t chunk = 1, bsk_len = 0, bytes = 0;  // bsk_len: complex values of the whole key
-    W *acc = nullptr, *extracted = nullptr;
-    u32 *exps = nullptr, *neg_b = nullptr;
-    ~TfheCbsCore() {
-        if (!rotation) return;
-        {
-            DeviceGuard g(fft->device);
-            for (void *b : {(void *)acc, (void *)extracted, (void *)exps, (void *)neg_b})
-                if (b) (void)counted_free(b);
-        }
-        delete rotation;
-    }
 };
 struct pfhe_tfhe_cbs_handle : TfheCbsCore<u64> {};
 struct pfhe_tfhe32_cbs_handle : TfheCbsCore<u32> {};
@@ -370,15 +354,8 @@ int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, s
     *out = nullptr;
     Shape rot_shape{};
     const std::optional<size_t> grouping = grouping_factor > 1 ? std::optional<size_t>(grouping_factor) : std::nullopt;
-    if (grouping) {
-        PFHE_TRY(tfhe_mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, *grouping, rot_shape));
-        if (lwe_dimension % *grouping != 0) {
-            set_last_error("TFHE circuit bootstrap: lwe_dimension must be a multiple of grouping_factor");
-            return PFHE_ERR_BAD_ARGUMENT;
-        }
-    } else {
-        PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, rot_shape));
-    }
+    PFHE_TRY(tfhe_bootstrap_check<W>(fft, glwe_dimension, log_basis, decompose_length, grouping, lwe_dimension,
+                                     "TFHE circuit bootstrap: lwe_dimension must be a multiple of grouping_factor", rot_shape));
     // a zero glwe_dimension is refused as a zero lwe_dimension is: one message for both
     PFHE_TRY(require_lwe_dimension(glwe_dimension ? lwe_dimension : 0,
                                    "TFHE circuit bootstrap: glwe_dimension must be at least 1 and lwe_dimension in 1..2^31-2"));
@@ -399,8 +376,9 @@ int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, s
     // chunk inputs are chunk * ell_cb accumulators of the rotation, or chunk with a shared one; 0 stays the rotation's default
     const size_t per_input = shared ? 1 : h->cb_ell;
     if (chunk > 0x7fffffffull / h->cb_ell) return PFHE_ERR_BAD_LENGTH;
-    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping, chunk * per_input,
-                                     &h->rotation));
+    TfheRotation<W> *rotation = nullptr;
+    PFHE_TRY(tfhe_rotation_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping, chunk * per_input, &rotation));
+    h->rotation.reset(rotation);
     const TfheRotation<W> &rot = *h->rotation;
     h->fft = fft;
     h->k = (u32)glwe_dimension;
@@ -408,20 +386,18 @@ int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, s
     h->cb_log_basis = cbs_log_basis;
     const size_t glwe = rot.glwe, ext = glwe_dimension * fft->n + 1, levels = h->cb_ell;
     h->pf = PfksShape{(u32)(ext - 1), h->k, fft->log_n, h->cb_ell, pfks_log_basis, pf_ell, pf_drop, pfks_group_words(pf_ell)};
-    h->bsk_len = (grouping ? (lwe_dimension / *grouping) << *grouping : lwe_dimension) * rot.key_len;
+    h->bsk_len = tfhe_bootstrap_keys(grouping, lwe_dimension) * rot.key_len;
     // chunk 0: what the rotation's default holds, capped at about 256 MiB of accumulators
     h->chunk = chunk ? chunk
                      : std::max<size_t>(1, std::min(rot.chunk, kCbsDefaultAccBytes / (glwe * sizeof(W))) / per_input);
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     const size_t accs = h->chunk * per_input, rows = h->chunk * levels;
-    const size_t sizes[] = {accs * glwe * sizeof(W), rows * ext * sizeof(W), accs * lwe_dimension * sizeof(u32),
-                            h->chunk * sizeof(u32)};
-    void **bufs[] = {(void **)&h->acc, (void **)&h->extracted, (void **)&h->exps, (void **)&h->neg_b};
-    for (int i = 0; i < 4; ++i) {
-        PFHE_HIP(counted_malloc(bufs[i], sizes[i]));
-        h->bytes += sizes[i];
-    }
+    h->bufs.bind(fft->device);
+    PFHE_TRY(h->bufs.add(h->acc, accs * glwe));
+    PFHE_TRY(h->bufs.add(h->extracted, rows * ext));
+    PFHE_TRY(h->bufs.add(h->exps, accs * lwe_dimension));
+    PFHE_TRY(h->bufs.add(h->neg_b, h->chunk));
     PFHE_TRY(h->guard.init(fft->device));
     *out = h.release();
     return PFHE_OK;
@@ -494,11 +470,6 @@ int cbs(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk, size
         }
         return PFHE_OK;
     });
-}
-
-template <class H>
-size_t cbs_scratch(const H *h) {
-    return h && h->rotation ? h->rotation->scratch_bytes() + h->bytes : 0;
 }
 
 }  // namespace
@@ -577,7 +548,7 @@ int pfhe_tfhe_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint32
 }
 void pfhe_tfhe_cbs_destroy(pfhe_tfhe_cbs_handle *h) { delete h; }
 int pfhe_tfhe_cbs_in_use(const pfhe_tfhe_cbs_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h) { return cbs_scratch(h); }
+size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h) { return tfhe_bootstrap_scratch(h); }
 int pfhe_tfhe_cbs_dev(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk,
                       const uint64_t *pfksk_dev, size_t len_pfksk, uint64_t *ggsw_out_dev, size_t len_out, void *stream) {
     PFHE_GUARD_BEGIN
@@ -612,7 +583,7 @@ int pfhe_tfhe32_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint
 }
 void pfhe_tfhe32_cbs_destroy(pfhe_tfhe32_cbs_handle *h) { delete h; }
 int pfhe_tfhe32_cbs_in_use(const pfhe_tfhe32_cbs_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_cbs_scratch_bytes(const pfhe_tfhe32_cbs_handle *h) { return cbs_scratch(h); }
+size_t pfhe_tfhe32_cbs_scratch_bytes(const pfhe_tfhe32_cbs_handle *h) { return tfhe_bootstrap_scratch(h); }
 int pfhe_tfhe32_cbs_dev(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
                         size_t len_bsk, const uint32_t *pfksk_dev, size_t len_pfksk, uint32_t *ggsw_out_dev, size_t len_out,
                         void *stream) {

@@ -105,19 +105,11 @@ struct TfheCmuxTreeCore {
     Shape shape{};
     u32 depth = 1;
     bool fused = false;
-    size_t chunk = 1, glwe = 0, key_len = 0, bytes = 0;
-    TfhePlanCore<W> *plan = nullptr;  // owned, general form only; its launches run under this handle's guard
+    size_t chunk = 1, glwe = 0, key_len = 0;
+    std::unique_ptr<TfhePlanCore<W>> plan;  // owned, general form only; its launches run under this handle's guard
     W *node[2] = {nullptr, nullptr}, *d = nullptr, *e = nullptr;
+    DeviceBuffers bufs;  // after the plan: the four buffers are freed first, then the plan
     size_t launch_nodes() const { return chunk << (depth - 1); }
-    ~TfheCmuxTreeCore() {
-        if (!fft) return;
-        {
-            DeviceGuard g(fft->device);
-            for (W *b : {node[0], node[1], d, e})
-                if (b) (void)counted_free(b);
-        }
-        delete plan;
-    }
 };
 struct pfhe_tfhe_cmux_tree_handle : TfheCmuxTreeCore<u64> {};
 struct pfhe_tfhe32_cmux_tree_handle : TfheCmuxTreeCore<u32> {};
@@ -161,18 +153,17 @@ int cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
     h->fft = fft;
-    const size_t ct = h->glwe * sizeof(W);
-    const size_t sizes[] = {depth > 1 ? h->chunk * half * ct : 0, depth > 2 ? h->chunk * (half / 2) * ct : 0,
-                            h->fused ? 0 : h->chunk * half * ct, h->fused ? 0 : h->chunk * half * ct};
-    W **bufs[] = {&h->node[0], &h->node[1], &h->d, &h->e};
-    for (int i = 0; i < 4; ++i) {
-        if (!sizes[i]) continue;
-        void *b = nullptr;
-        PFHE_HIP(counted_malloc(&b, sizes[i]));
-        *bufs[i] = (W *)b;
-        h->bytes += sizes[i];
+    const size_t level = h->chunk * half * h->glwe;  // words of the widest level's nodes
+    h->bufs.bind(fft->device);
+    PFHE_TRY(h->bufs.add(h->node[0], depth > 1 ? level : 0));
+    PFHE_TRY(h->bufs.add(h->node[1], depth > 2 ? level / 2 : 0));
+    PFHE_TRY(h->bufs.add(h->d, h->fused ? 0 : level));
+    PFHE_TRY(h->bufs.add(h->e, h->fused ? 0 : level));
+    if (!h->fused) {
+        TfhePlanCore<W> *plan = nullptr;
+        PFHE_TRY(tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, 0, &plan));
+        h->plan.reset(plan);
     }
-    if (!h->fused) PFHE_TRY(tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, 0, &h->plan));
     PFHE_TRY(h->guard.init(fft->device));
     *out = h.release();
     return PFHE_OK;
@@ -198,7 +189,7 @@ int cmux_nodes(TfheCmuxTreeCore<W> *h, const W *d0, const W *d1, const double2 *
         for (u64 b = 0; b < cur;) {  // the product's own launches, once per key group that the launch meets
             const u64 group = (done + b) / at.per_key;
             const u64 run = std::min<u64>(cur - b, (group + 1) * at.per_key - (done + b));
-            PFHE_TRY(tfhe_product_impl<W>(h->plan, h->d + b * h->glwe, keys + group * at.key_stride, h->e + b * h->glwe, run, s));
+            PFHE_TRY(tfhe_product_impl<W>(h->plan.get(), h->d + b * h->glwe, keys + group * at.key_stride, h->e + b * h->glwe, run, s));
             b += run;
         }
         PFHE_TRY(launch_flat(tfhe_cmux_glue_kernel<W, true>, cur * h->glwe, s, d0 + off, (const W *)h->e, o, (u64)h->glwe, at));
@@ -306,7 +297,7 @@ int cmux_tree(Form form, TfheCmuxTreeCore<W> *h, const W *table, size_t len_tabl
 
 template <class H>
 size_t cmux_scratch(const H *h) {
-    return h && h->fft ? h->bytes + (h->plan ? h->plan->scratch.bytes : 0) : 0;
+    return h && h->fft ? h->bufs.bytes() + (h->plan ? h->plan->scratch.bytes() : 0) : 0;
 }
 
 }  // namespace

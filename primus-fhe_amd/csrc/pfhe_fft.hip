@@ -604,7 +604,9 @@ int tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t lo
     if (!out) return PFHE_ERR_BAD_ARGUMENT;
     *out = nullptr;
     auto h = std::make_unique<H>();
-    PFHE_TRY(tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, &h->plan));
+    TfhePlanCore<W> *plan = nullptr;
+    PFHE_TRY(tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, &plan));
+    h->plan.reset(plan);
     const TfhePlanCore<W> &p = *h->plan;
     h->fft = fft;
     h->glwe = (size_t)(p.shape.k + 1) * fft->n;
@@ -616,12 +618,8 @@ int tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t lo
     if (!h->whole_loop) {
         // never above the plan's chunk, so a chunk of the rotation is one chunk of the product
         if (!chunk) h->chunk = std::min(p.chunk, std::max<size_t>(1, kDefaultGlueBytes / (3 * h->glwe * sizeof(W))));
-        for (W **b : {&h->d, &h->e, &h->ping}) {
-            void *q = nullptr;
-            PFHE_HIP(counted_malloc(&q, h->chunk * h->glwe * sizeof(W)));
-            *b = (W *)q;
-            h->glue_bytes += h->chunk * h->glwe * sizeof(W);
-        }
+        h->bufs.bind(fft->device);
+        for (W **b : {&h->d, &h->e, &h->ping}) PFHE_TRY(h->bufs.add(*b, h->chunk * h->glwe));
     }
     PFHE_TRY(h->guard.init(fft->device));
     *out = h.release();
@@ -647,7 +645,7 @@ int tfhe_blindrot_chunk(TfheBlindRotCore<W> *h, W *a0, const double2 *bsk, const
         PFHE_TRY(torus_glue<W>(f, TorusGlue::kFirst, a0, nullptr, nullptr, h->d, ex, (u32)n_steps, rows, cur, s));
     }
     for (u64 i = 0; i < n_steps; ++i) {
-        PFHE_TRY(tfhe_product_impl<W>(h->plan, h->d, bsk + i * h->key_len, h->e, cur, s));
+        PFHE_TRY(tfhe_product_impl<W>(h->plan.get(), h->d, bsk + i * h->key_len, h->e, cur, s));
         W *dst = src == a0 ? h->ping : a0;
         PFHE_TRY(i + 1 < n_steps
                      ? torus_glue<W>(f, TorusGlue::kStep, src, h->e, dst, h->d, ex + i + 1, (u32)n_steps, rows, cur, s)
@@ -909,9 +907,8 @@ int pfhe_fft_create(uint32_t log_n, int device, pfhe_fft **out) {
     }
     DeviceGuard g(device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
-    void *d = nullptr;
-    PFHE_HIP(counted_malloc(&d, f->n * sizeof(double2)));
-    f->tw = (double2 *)d;
+    f->bufs.bind(device);
+    PFHE_TRY(f->bufs.add(f->tw, f->n));
     PFHE_HIP(hipMemcpy(f->tw, tw.data(), f->n * sizeof(double2), hipMemcpyHostToDevice));
     PFHE_TRY(set_lds_attributes<u64>(lds_bytes(log_n)));
     PFHE_TRY(set_lds_attributes<u32>(lds_bytes(log_n)));
@@ -995,7 +992,7 @@ void pfhe_tfhe_plan_destroy(pfhe_tfhe_plan *plan) { delete plan; }
 int pfhe_tfhe_plan_in_use(const pfhe_tfhe_plan *plan) {
     return plan ? plan->guard.in_use() : 0;
 }
-size_t pfhe_tfhe_plan_scratch_bytes(const pfhe_tfhe_plan *plan) { return plan ? plan->scratch.bytes : 0; }
+size_t pfhe_tfhe_plan_scratch_bytes(const pfhe_tfhe_plan *plan) { return plan ? plan->scratch.bytes() : 0; }
 int pfhe_tfhe_external_product_to_dev(pfhe_tfhe_plan *plan, const uint64_t *input_dev, size_t len_input,
                                       const double *key_dev, size_t len_key, uint64_t *output_dev, size_t len_output,
                                       void *stream) {
@@ -1021,7 +1018,7 @@ void pfhe_tfhe32_plan_destroy(pfhe_tfhe32_plan *plan) { delete plan; }
 int pfhe_tfhe32_plan_in_use(const pfhe_tfhe32_plan *plan) {
     return plan ? plan->guard.in_use() : 0;
 }
-size_t pfhe_tfhe32_plan_scratch_bytes(const pfhe_tfhe32_plan *plan) { return plan ? plan->scratch.bytes : 0; }
+size_t pfhe_tfhe32_plan_scratch_bytes(const pfhe_tfhe32_plan *plan) { return plan ? plan->scratch.bytes() : 0; }
 int pfhe_tfhe32_external_product_to_dev(pfhe_tfhe32_plan *plan, const uint32_t *input_dev, size_t len_input,
                                         const double *key_dev, size_t len_key, uint32_t *output_dev, size_t len_output,
                                         void *stream) {

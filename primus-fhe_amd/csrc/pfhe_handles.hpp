@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "pfhe_common.hpp"
+#include "pfhe_device_buffers.hpp"
 #include "pfhe_ntt_device.hpp"
 #include "pfhe_pointwise.hpp"
 
@@ -23,8 +24,7 @@ struct TableSet {
     const NttPrime *primes_dev = nullptr;  // the same array on the device
     const u64 *moduli_dev = nullptr;
     std::vector<u64> roots, inv_roots;
-    std::vector<void *> allocations;
-    ~TableSet();
+    DeviceBuffers bufs;                    // every device table above
 };
 
 // The four table handles of the C ABI (pfhe_ntt, pfhe_dcrt, pfhe_ntt32, pfhe_dcrt32: pfhe_capi_internal.hpp) are empty

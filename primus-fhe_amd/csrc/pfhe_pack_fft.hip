@@ -199,13 +199,9 @@ struct TfhePackFftCore {
     const pfhe_fft *fft = nullptr;  // borrowed (must outlive the plan)
     pfhe::PlanGuard guard;          // one holder at a time, successive calls ordered across streams
     pfhe::Shape shape{};
-    size_t in_dim = 0, slices = 0, chunk = 1, bytes = 0;
+    size_t in_dim = 0, slices = 0, chunk = 1;
     double2 *partial = nullptr;
-    ~TfhePackFftCore() {
-        if (!partial) return;
-        pfhe::DeviceGuard g(fft->device);
-        (void)pfhe::counted_free(partial);
-    }
+    pfhe::DeviceBuffers bufs;
 };
 struct pfhe_tfhe_packfft_plan : TfhePackFftCore<pfhe::u64> {};
 struct pfhe_tfhe32_packfft_plan : TfhePackFftCore<pfhe::u32> {};
@@ -241,8 +237,8 @@ int packfft_plan_create(const pfhe_fft *fft, size_t k, size_t in_dimension, uint
     p->shape = Shape{fft->log_n, (u32)k, log_basis, ell, drop};
     p->in_dim = in_dimension;
     p->slices = (in_dimension + kPackFftSlice - 1) / kPackFftSlice;
-    const size_t per_group = p->slices * (k + 1) * (fft->n / 2) * sizeof(double2);
-    p->chunk = chunk ? chunk : std::max<size_t>(1, kPackFftDefaultBytes / per_group);
+    const size_t per_group = p->slices * (k + 1) * (fft->n / 2);  // complex values
+    p->chunk = chunk ? chunk : std::max<size_t>(1, kPackFftDefaultBytes / (per_group * sizeof(double2)));
     p->chunk = std::min(p->chunk, kPackFftMaxChunk);
     DeviceGuard g(fft->device);
     if (!g.ok) return PFHE_ERR_NO_DEVICE;
@@ -253,10 +249,8 @@ int packfft_plan_create(const pfhe_fft *fft, size_t k, size_t in_dimension, uint
         for (const void *kern : {accumulate_kernel<W, 2>(), accumulate_kernel<W, 3>(), accumulate_kernel<W, 4>()})
             PFHE_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    void *b = nullptr;
-    PFHE_HIP(counted_malloc(&b, p->chunk * per_group));
-    p->partial = (double2 *)b;
-    p->bytes = p->chunk * per_group;
+    p->bufs.bind(fft->device);
+    PFHE_TRY(p->bufs.add(p->partial, p->chunk * per_group));
     PFHE_TRY(p->guard.init(fft->device));
     *out = p.release();
     return PFHE_OK;
@@ -358,7 +352,7 @@ int pfhe_tfhe_packfft_plan_create(const pfhe_fft *fft, size_t glwe_dimension, si
 }
 void pfhe_tfhe_packfft_plan_destroy(pfhe_tfhe_packfft_plan *plan) { delete plan; }
 int pfhe_tfhe_packfft_plan_in_use(const pfhe_tfhe_packfft_plan *plan) { return plan ? plan->guard.in_use() : 0; }
-size_t pfhe_tfhe_packfft_plan_scratch_bytes(const pfhe_tfhe_packfft_plan *plan) { return plan ? plan->bytes : 0; }
+size_t pfhe_tfhe_packfft_plan_scratch_bytes(const pfhe_tfhe_packfft_plan *plan) { return plan ? plan->bufs.bytes() : 0; }
 int pfhe_tfhe_packfft_key_dev(pfhe_tfhe_packfft_plan *plan, const uint64_t *pksk_dev, size_t len_pksk, double *fkey_dev,
                               size_t len_fkey, void *stream) {
     PFHE_GUARD_BEGIN
@@ -389,7 +383,7 @@ int pfhe_tfhe32_packfft_plan_create(const pfhe_fft *fft, size_t glwe_dimension, 
 }
 void pfhe_tfhe32_packfft_plan_destroy(pfhe_tfhe32_packfft_plan *plan) { delete plan; }
 int pfhe_tfhe32_packfft_plan_in_use(const pfhe_tfhe32_packfft_plan *plan) { return plan ? plan->guard.in_use() : 0; }
-size_t pfhe_tfhe32_packfft_plan_scratch_bytes(const pfhe_tfhe32_packfft_plan *plan) { return plan ? plan->bytes : 0; }
+size_t pfhe_tfhe32_packfft_plan_scratch_bytes(const pfhe_tfhe32_packfft_plan *plan) { return plan ? plan->bufs.bytes() : 0; }
 int pfhe_tfhe32_packfft_key_dev(pfhe_tfhe32_packfft_plan *plan, const uint32_t *pksk_dev, size_t len_pksk, double *fkey_dev,
                                 size_t len_fkey, void *stream) {
     PFHE_GUARD_BEGIN

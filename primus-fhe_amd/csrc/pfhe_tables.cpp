@@ -12,9 +12,13 @@
 
 namespace pfhe {
 
-TableSet::~TableSet() {
-    DeviceGuard g(device);
-    for (void *p : allocations) (void)counted_free(p);
+// One device table: as many elements as `v` holds, allocated into the table's own typed pointer and filled from `v`.
+template <class V, class T>
+static int upload(TableSet &ts, const V &v, T *&dst) {
+    PFHE_TRY(ts.bufs.add(dst, v.size()));
+    static_assert(sizeof(typename V::value_type) == sizeof(T), "the table's element is the vector's");
+    PFHE_HIP(hipMemcpy((void *)dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return PFHE_OK;
 }
 
 // The twiddles of the closing register pass, re-ordered so that the 64 lanes of a wave load 64 consecutive entries
@@ -81,7 +85,6 @@ int make_table_set(u32 log_n, const u64 *moduli, size_t count, int device, std::
     ts->L = (u32)count;
     ts->primes.resize(count);
     ts->tune = NttTuning::from_env();
-    const size_t bytes = ts->n * sizeof(ulonglong2);
     bool all_pm = std::getenv("PFHE_DISABLE_PM") == nullptr;  // tuning switch: force the generic path
     bool all_mont = std::getenv("PFHE_DISABLE_MONT") == nullptr;  // tuning switch: generic primes keep the Shoup transforms
     for (size_t i = 0; i < count; ++i) {
@@ -91,20 +94,12 @@ int make_table_set(u32 log_n, const u64 *moduli, size_t count, int device, std::
         if (!mont_shape(host[i].q)) all_mont = false;
     }
     const bool use_mont = !all_pm && all_mont && log_n >= 4;
-    const auto upload = [&](const void *src, size_t nbytes, const void **dst) -> int {
-        void *d = nullptr;
-        PFHE_HIP(counted_malloc(&d, nbytes));
-        ts->allocations.push_back(d);
-        PFHE_HIP(hipMemcpy(d, src, nbytes, hipMemcpyHostToDevice));
-        *dst = d;
-        return PFHE_OK;
-    };
+    ts->bufs.bind(device);
     for (size_t i = 0; i < count; ++i) {
-        const void *fwd = nullptr, *inv = nullptr;
-        PFHE_TRY(upload(host[i].fwd.data(), bytes, &fwd));
-        PFHE_TRY(upload(host[i].inv.data(), bytes, &inv));
         NttPrime &P = ts->primes[i];
         std::memset(&P, 0, sizeof P);
+        PFHE_TRY(upload(*ts, host[i].fwd, P.fwd));
+        PFHE_TRY(upload(*ts, host[i].inv, P.inv));
         P.q = host[i].q;
         P.two_q = host[i].q << 1;
         P.q3 = 3 * host[i].q;
@@ -114,8 +109,6 @@ int make_table_set(u32 log_n, const u64 *moduli, size_t count, int device, std::
         P.inv_n_w_p = (u64)(((unsigned __int128)host[i].inv_n_w << 64) / host[i].q);
         P.bar_lo = host[i].bar_lo;
         P.bar_hi = host[i].bar_hi;
-        P.fwd = static_cast<const ulonglong2 *>(fwd);
-        P.inv = static_cast<const ulonglong2 *>(inv);
         u32 pk = 0;
         u64 pc = 0;
         P.pm_k = pm_shape(P.q, pk, pc) ? pk : 0;
@@ -129,11 +122,8 @@ int make_table_set(u32 log_n, const u64 *moduli, size_t count, int device, std::
                 fw[k] = ulonglong2{host[i].fwd[k].x, shifted(host[i].fwd[k].x)};
                 iw[k] = ulonglong2{host[i].inv[k].x, shifted(host[i].inv[k].x)};
             }
-            const void *fwp = nullptr, *iwp = nullptr;
-            PFHE_TRY(upload(fw.data(), bytes, &fwp));
-            PFHE_TRY(upload(iw.data(), bytes, &iwp));
-            P.fwd_p = static_cast<const ulonglong2 *>(fwp);
-            P.inv_p = static_cast<const ulonglong2 *>(iwp);
+            PFHE_TRY(upload(*ts, fw, P.fwd_p));
+            PFHE_TRY(upload(*ts, iw, P.inv_p));
             P.inv_n_2 = shifted(P.inv_n);
             P.inv_n_w_2 = shifted(P.inv_n_w);
             if (all_pm && log_n >= 4) last_order(ts->n, fw, iw, fl, il);
@@ -152,15 +142,10 @@ int make_table_set(u32 log_n, const u64 *moduli, size_t count, int device, std::
                 im[k] = mform(host[i].inv[k].x);
             }
             last_order(ts->n, fm, im, flm, ilm);
-            const void *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr;
-            PFHE_TRY(upload(fm.data(), bytes, &a));
-            PFHE_TRY(upload(im.data(), bytes, &b));
-            PFHE_TRY(upload(flm.data(), flm.size() * sizeof(ulonglong2), &c));
-            PFHE_TRY(upload(ilm.data(), ilm.size() * sizeof(ulonglong2), &d));
-            P.fwd_m = static_cast<const ulonglong2 *>(a);
-            P.inv_m = static_cast<const ulonglong2 *>(b);
-            P.fwd_last_m = static_cast<const ulonglong2 *>(c);
-            P.inv_last_m = static_cast<const ulonglong2 *>(d);
+            PFHE_TRY(upload(*ts, fm, P.fwd_m));
+            PFHE_TRY(upload(*ts, im, P.inv_m));
+            PFHE_TRY(upload(*ts, flm, P.fwd_last_m));
+            PFHE_TRY(upload(*ts, ilm, P.inv_last_m));
             const ulonglong2 nm = mform(P.inv_n), nwm = mform(P.inv_n_w);
             P.inv_n_m = nm.x, P.inv_n_m2 = nm.y, P.inv_n_w_m = nwm.x, P.inv_n_w_m2 = nwm.y;
             u32 inv = 1;  // Newton: q^-1 mod 2^32
@@ -170,28 +155,16 @@ int make_table_set(u32 log_n, const u64 *moduli, size_t count, int device, std::
             P.mont_qf = ((1ull << 63) / q) * q;
         }
         if (!fl.empty()) {
-            const void *flp = nullptr, *ilp = nullptr;
-            PFHE_TRY(upload(fl.data(), fl.size() * sizeof(ulonglong2), &flp));
-            PFHE_TRY(upload(il.data(), il.size() * sizeof(ulonglong2), &ilp));
-            P.fwd_last = static_cast<const ulonglong2 *>(flp);
-            P.inv_last = static_cast<const ulonglong2 *>(ilp);
+            PFHE_TRY(upload(*ts, fl, P.fwd_last));
+            PFHE_TRY(upload(*ts, il, P.inv_last));
         }
         ts->roots.push_back(host[i].root);
         ts->inv_roots.push_back(host[i].inv_root);
     }
     ts->pm = all_pm;
     ts->ntt_arith = all_pm ? kArithPm : (use_mont ? kArithMont : kArithShoup);
-    void *pd = nullptr;
-    PFHE_HIP(counted_malloc(&pd, count * sizeof(NttPrime)));
-    ts->allocations.push_back(pd);
-    PFHE_HIP(hipMemcpy(pd, ts->primes.data(), count * sizeof(NttPrime), hipMemcpyHostToDevice));
-    ts->primes_dev = static_cast<const NttPrime *>(pd);
-    void *md = nullptr;
-    PFHE_HIP(counted_malloc(&md, count * sizeof(u64)));
-    ts->allocations.push_back(md);
-    std::vector<u64> mods(moduli, moduli + count);
-    PFHE_HIP(hipMemcpy(md, mods.data(), count * sizeof(u64), hipMemcpyHostToDevice));
-    ts->moduli_dev = static_cast<const u64 *>(md);
+    PFHE_TRY(upload(*ts, ts->primes, ts->primes_dev));
+    PFHE_TRY(upload(*ts, std::vector<u64>(moduli, moduli + count), ts->moduli_dev));
     out = std::move(ts);
     return PFHE_OK;
 }
@@ -224,6 +197,7 @@ int make_table_set32(u32 log_n, const u32 *moduli, size_t count, int device, std
     ts->tune = NttTuning::from_env();  // u32 tables read the tuning switches at creation too
     ts->primes.resize(count);
     const size_t n = ts->n;
+    ts->bufs.bind(device);
     for (size_t i = 0; i < count; ++i) {
         const u64 q = host[i].q;
         NttPrime &P = ts->primes[i];
@@ -235,14 +209,6 @@ int make_table_set32(u32 log_n, const u32 *moduli, size_t count, int device, std
         P.inv_n_w = host[i].inv_n_w;
         P.inv_n_w_p = (host[i].inv_n_w << 32) / q;
         P.bar_lo = (u64)(((unsigned __int128)1 << 64) / q);
-        const auto upload = [&](const std::vector<u64> &v, const u64 **dst) -> int {
-            void *d = nullptr;
-            PFHE_HIP(counted_malloc(&d, v.size() * sizeof(u64)));
-            ts->allocations.push_back(d);
-            PFHE_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(u64), hipMemcpyHostToDevice));
-            *dst = static_cast<const u64 *>(d);
-            return PFHE_OK;
-        };
         const auto pack_of = [&](const std::vector<ulonglong2> &src, bool negate) {
             std::vector<u64> v(n);
             for (size_t k = 0; k < n; ++k)
@@ -252,24 +218,20 @@ int make_table_set32(u32 log_n, const u32 *moduli, size_t count, int device, std
         // forward, inverse, forward with the twiddle negated (B32Arith::mul1_neg)
         const std::vector<u64> pf = pack_of(host[i].fwd, false), pi = pack_of(host[i].inv, false), pn = pack_of(host[i].fwd, true);
         const u64 *dinv = nullptr;
-        PFHE_TRY(upload(pf, &P.fwd_w));
-        PFHE_TRY(upload(pi, &dinv));
+        PFHE_TRY(upload(*ts, pf, P.fwd_w));
+        PFHE_TRY(upload(*ts, pi, dinv));
         P.inv_w = dinv + n / 2;  // the word kernels index the inverse table in units of words: biased by N/2 entries
-        PFHE_TRY(upload(pn, &P.fwd_wn));
+        PFHE_TRY(upload(*ts, pn, P.fwd_wn));
         if (n / 2 >= 16) {
             std::vector<u64> fl, il;
             last_order32(n / 2, pn, pi, fl, il);
-            PFHE_TRY(upload(fl, &P.fwd_last_w));
-            PFHE_TRY(upload(il, &P.inv_last_w));
+            PFHE_TRY(upload(*ts, fl, P.fwd_last_w));
+            PFHE_TRY(upload(*ts, il, P.inv_last_w));
         }
         ts->roots.push_back(host[i].root);
         ts->inv_roots.push_back(host[i].inv_root);
     }
-    void *pd = nullptr;
-    PFHE_HIP(counted_malloc(&pd, count * sizeof(NttPrime)));
-    ts->allocations.push_back(pd);
-    PFHE_HIP(hipMemcpy(pd, ts->primes.data(), count * sizeof(NttPrime), hipMemcpyHostToDevice));
-    ts->primes_dev = static_cast<const NttPrime *>(pd);
+    PFHE_TRY(upload(*ts, ts->primes, ts->primes_dev));
     out = std::move(ts);
     return PFHE_OK;
 }

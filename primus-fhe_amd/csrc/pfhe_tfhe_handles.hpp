@@ -6,9 +6,11 @@
 // is pfhe_tfhe_host.hpp.
 #pragma once
 
+#include <memory>
 #include <optional>
 
 #include "pfhe_capi_internal.hpp"
+#include "pfhe_device_buffers.hpp"
 #include "pfhe_plan_guard.hpp"
 #include "pfhe_tfhe_host.hpp"
 
@@ -17,11 +19,7 @@ struct pfhe_fft {
     pfhe::u32 log_n = 0;
     size_t n = 0;
     double2 *tw = nullptr;  // device: cis(pi j / N), j < N
-    ~pfhe_fft() {
-        if (!tw) return;
-        pfhe::DeviceGuard g(device);
-        (void)pfhe::counted_free(tw);
-    }
+    pfhe::DeviceBuffers bufs;
 };
 
 // The device scratch of the general product, shared by the product plan and the per-group multi-bit rotation: digit spectra
@@ -29,9 +27,9 @@ struct pfhe_fft {
 // ((k+1) x ell x (k+1) x N/2 each), complex f64.  All of it is allocated by create() or none.
 struct TfheProductScratch {
     static constexpr size_t kDefaultBytes = 256ull << 20;
-    int device = 0;
     double2 *spec = nullptr, *acc = nullptr, *keyh = nullptr;
-    size_t bytes = 0;
+    pfhe::DeviceBuffers bufs;
+    size_t bytes() const { return bufs.bytes(); }
 
     // Sizes `chunk` (0: the default — what fits kDefaultBytes of spectra and accumulators, or 65536 ciphertexts for a form
     // that needs no scratch; never more than one launch's grid holds) and, when the form needs it, allocates the three
@@ -40,23 +38,11 @@ struct TfheProductScratch {
         const size_t m = f.n / 2, rows = sh.k + 1, digits = rows * sh.ell;
         if (!chunk) chunk = needed ? std::max<size_t>(1, kDefaultBytes / ((digits + rows) * m * sizeof(double2))) : 65536;
         chunk = std::min<size_t>(chunk, needed ? 0x7fffffffull / digits : 0x7fffffffull);
-        device = f.device;
         if (!needed) return PFHE_OK;
-        const size_t sizes[] = {chunk * digits * m, chunk * rows * m, key_copies * digits * rows * m};
-        double2 **bufs[] = {&spec, &acc, &keyh};
-        for (int i = 0; i < 3; ++i) {
-            void *b = nullptr;
-            PFHE_HIP(pfhe::counted_malloc(&b, sizes[i] * sizeof(double2)));
-            *bufs[i] = (double2 *)b;
-            bytes += sizes[i] * sizeof(double2);
-        }
-        return PFHE_OK;
-    }
-    ~TfheProductScratch() {
-        if (!spec) return;
-        pfhe::DeviceGuard g(device);
-        for (double2 *b : {spec, acc, keyh})
-            if (b) (void)pfhe::counted_free(b);
+        bufs.bind(f.device);
+        PFHE_TRY(bufs.add(spec, chunk * digits * m));
+        PFHE_TRY(bufs.add(acc, chunk * rows * m));
+        return bufs.add(keyh, key_copies * digits * rows * m);
     }
 };
 
@@ -92,21 +78,12 @@ struct TfheRotation {
 // ciphertexts (D, E and the second accumulator of the ping-pong), all allocated at creation.
 template <class W>
 struct TfheBlindRotCore : TfheRotation<W> {
-    TfhePlanCore<W> *plan = nullptr;                // owned
+    std::unique_ptr<TfhePlanCore<W>> plan;          // owned
     W *d = nullptr, *e = nullptr, *ping = nullptr;  // per-step form only: chunk * (k+1) * N words each
-    size_t glue_bytes = 0;
+    pfhe::DeviceBuffers bufs;                       // after the plan: the glue buffers are freed first, then the plan
     int rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
                    hipStream_t s) override;
-    size_t scratch_bytes() const override { return plan->scratch.bytes + glue_bytes; }
-    ~TfheBlindRotCore() override {
-        if (!plan) return;
-        {
-            pfhe::DeviceGuard g(this->fft->device);
-            for (W *b : {d, e, ping})
-                if (b) (void)pfhe::counted_free(b);
-        }
-        delete plan;
-    }
+    size_t scratch_bytes() const override { return plan->scratch.bytes() + bufs.bytes(); }
 };
 struct pfhe_tfhe_blindrot : TfheBlindRotCore<pfhe::u64> {};
 struct pfhe_tfhe32_blindrot : TfheBlindRotCore<pfhe::u32> {};
@@ -121,10 +98,26 @@ struct TfheMultiBitCore : TfheRotation<W> {
     TfheProductScratch scratch;
     int rotate_dev(W *acc, size_t len_acc, const double *bsk, size_t len_bsk, const uint32_t *exps, size_t len_exps,
                    hipStream_t s) override;
-    size_t scratch_bytes() const override { return scratch.bytes; }
+    size_t scratch_bytes() const override { return scratch.bytes(); }
 };
 struct pfhe_tfhe_mbrot : TfheMultiBitCore<pfhe::u64> {};
 struct pfhe_tfhe32_mbrot : TfheMultiBitCore<pfhe::u32> {};
+
+// What the bootstrap handle (pfhe_bootstrap.hip) and the circuit bootstrap handle (pfhe_cbs.hip) share: a blind rotation
+// they own (classic or multi-bit, behind TfheRotation) and, sized by their creates for `chunk` inputs, the accumulators,
+// the extracted LWE ciphertexts, the switched exponents and neg_b, all allocated at creation.  Destroyed in the order
+// buffers, rotation, guard.
+template <class W>
+struct TfheBootstrapBase {
+    pfhe::PlanGuard guard;                      // one holder at a time, successive calls on different streams ordered
+    std::unique_ptr<TfheRotation<W>> rotation;  // owned
+    const pfhe_fft *fft = nullptr;
+    pfhe::u32 k = 1, n = 0;          // GLWE and LWE dimensions
+    size_t chunk = 1, bsk_len = 0;   // bsk_len: complex values of the whole key
+    W *acc = nullptr, *extracted = nullptr;
+    pfhe::u32 *exps = nullptr, *neg_b = nullptr;
+    pfhe::DeviceBuffers bufs;
+};
 
 namespace pfhe {
 
@@ -170,6 +163,31 @@ int tfhe_mbrot_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
         return PFHE_ERR_BAD_ARGUMENT;
     }
     return PFHE_OK;
+}
+
+// The "classic or multi-bit" head of the two bootstrap creates, all before the device: with a grouping factor the multi-bit
+// rotation's checks and then the divisibility, refused with the caller's own message; without one the plan's checks
+template <class W>
+int tfhe_bootstrap_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         std::optional<size_t> grouping_factor, size_t lwe_dimension, const char *not_a_multiple, Shape &sh) {
+    if (!grouping_factor) return tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, sh);
+    PFHE_TRY(tfhe_mbrot_check<W>(fft, glwe_dimension, log_basis, decompose_length, *grouping_factor, sh));
+    if (lwe_dimension % *grouping_factor != 0) {
+        set_last_error(not_a_multiple);
+        return PFHE_ERR_BAD_ARGUMENT;
+    }
+    return PFHE_OK;
+}
+
+// keys of a bootstrapping key: lwe_dimension, or (lwe_dimension / g) 2^g multi-bit ones
+inline size_t tfhe_bootstrap_keys(std::optional<size_t> grouping_factor, size_t lwe_dimension) {
+    return grouping_factor ? (lwe_dimension / *grouping_factor) << *grouping_factor : lwe_dimension;
+}
+
+// *_scratch_bytes of both: the rotation's plus the handle's own buffers
+template <class W>
+size_t tfhe_bootstrap_scratch(const TfheBootstrapBase<W> *h) {
+    return h && h->rotation ? h->rotation->scratch_bytes() + h->bufs.bytes() : 0;
 }
 
 // The rotation of a bootstrap handle (pfhe_fft.hip, instantiated for u32 and u64): what pfhe_tfhe{,32}_blindrot_create

@@ -3,7 +3,8 @@
 // torus kernel, and the two tails: stateless_call of the stateless steps, handle_call of the calls on a handle.  Host only.
 // What is not torus-specific lives in pfhe_staging.hpp, for the RNS side too: StageBuf and stage_in / _out / _inout,
 // staged_call (the staged run of a launch on host pointers), Form and form_call, refuse_null, overlaps,
-// require_exps_below_2n; the lease and the stream order of a handle live in pfhe_plan_guard.hpp.
+// require_exps_below_2n; the lease and the stream order of a handle live in pfhe_plan_guard.hpp, and the owner of the
+// device buffers a handle allocates at create in pfhe_device_buffers.hpp (the create-side recipe: DESIGN.md §16).
 //
 // A handle call (product, rotations, bootstrap, circuit bootstrap, CMUX and its tree, automorphism and trace) is ONE function template for both
 // of its forms:

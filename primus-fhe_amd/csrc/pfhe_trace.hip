@@ -218,15 +218,10 @@ struct TfheTraceCore {
     PlanGuard guard;                // one holder at a time, successive calls on different streams ordered
     Shape shape{};
     bool fused = false;
-    size_t chunk = 1, glwe = 0, key_len = 0, bytes = 0;
+    size_t chunk = 1, glwe = 0, key_len = 0;
     TfheProductScratch scratch;
     W *d = nullptr, *body = nullptr, *e = nullptr;
-    ~TfheTraceCore() {
-        if (!fft) return;
-        DeviceGuard g(fft->device);
-        for (W *b : {d, body, e})
-            if (b) (void)counted_free(b);
-    }
+    DeviceBuffers bufs;  // after the scratch: the word buffers are freed first
 };
 struct pfhe_tfhe_glwe_trace_handle : TfheTraceCore<u64> {};
 struct pfhe_tfhe32_glwe_trace_handle : TfheTraceCore<u32> {};
@@ -261,14 +256,10 @@ int trace_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
     h->fft = fft;
     PFHE_TRY(h->scratch.create(*fft, sh, 1, !h->fused, h->chunk));  // also caps the chunk at what a launch's grid holds
     if (!h->fused) {
-        const size_t sizes[] = {h->chunk * sh.k * fft->n, h->chunk * fft->n, h->chunk * h->glwe};
-        W **bufs[] = {&h->d, &h->body, &h->e};
-        for (int i = 0; i < 3; ++i) {
-            void *b = nullptr;
-            PFHE_HIP(counted_malloc(&b, sizes[i] * sizeof(W)));
-            *bufs[i] = (W *)b;
-            h->bytes += sizes[i] * sizeof(W);
-        }
+        h->bufs.bind(fft->device);
+        PFHE_TRY(h->bufs.add(h->d, h->chunk * sh.k * fft->n));
+        PFHE_TRY(h->bufs.add(h->body, h->chunk * fft->n));
+        PFHE_TRY(h->bufs.add(h->e, h->chunk * h->glwe));
     }
     PFHE_TRY(h->guard.init(fft->device));
     *out = h.release();
@@ -450,7 +441,7 @@ int lwe_embed(Form form, const pfhe_fft *f, size_t k, const W *lwe, size_t len_l
 
 template <class H>
 size_t trace_scratch(const H *h) {
-    return h && h->fft ? h->bytes + h->scratch.bytes : 0;
+    return h && h->fft ? h->bufs.bytes() + h->scratch.bytes() : 0;
 }
 
 }  // namespace

@@ -216,6 +216,9 @@ def test_handle_host_equals_device(p, bits, k):
 #                            k = 2: 768 + 384 + 4*1152 = 5760
 #   bootstrap                the rotation's plus acc chunk*(k+1)*N*W, extracted chunk*(k*N+1)*W (with a key switch only),
 #                            exps chunk*4*4 = 32 and neg_b chunk*4 = 8: k = 1: 240 / 440 (168 / 296 without), k = 2: 368 / 696
+#   many-LUT bootstrap       log_luts = 1: two outputs per input, so extracted holds (chunk*2)*(k*N+1) words; the rest as the
+#                            bootstrap's.  k = 1 with a key switch: acc 2*16 W, extracted 4*9 W, exps 32, neg_b 8:
+#                            68 W + 40 = 312 / 584, four buffers
 #   the fused product and the whole-loop rotations own nothing
 # The handles of DESIGN.md §18-21, from the buffer lists in their header comments (csrc/pfhe_pack_fft.hip, pfhe_cbs.hip,
 # pfhe_cmux.hip, pfhe_trace.hip), not from the numbers the code gives:
@@ -226,6 +229,8 @@ def test_handle_host_equals_device(p, bits, k):
 #                            k = 2: 96 W + 68 W + 72 = 728 / 1384, plus the per-step rotation at chunk 4: the product's
 #                            spec 4*3*2*4*16 = 1536, acc 4*3*4*16 = 768, keyh 1152 = 3456 and three glue buffers of
 #                            4*24 W = 1152 / 2304: 5336 / 7144 in 4 + 6 buffers
+#                            shared rotation, k = 1: one accumulator per input, so the rotation is created for a chunk of 2;
+#                            acc 2*16 W, extracted still 4*9 W, exps 2*4*4 = 32, neg_b 8: 68 W + 40 = 312 / 584 in four
 #   CMUX tree                node buffers of chunk*2^(d-1) and chunk*2^(d-2) ciphertexts (depth 1 none, depth 2 one); the
 #                            general form adds D and E of chunk*2^(d-1) ciphertexts and a product plan of the DEFAULT chunk
 #                            (§11: what fits 256 MiB at (k+1)(ell+1) N/2 = 3*3*4 complex values = 576 bytes a
@@ -264,6 +269,11 @@ HANDLES = {
         {32: (240, 4), 64: (440, 4)}),
     "bootstrap per group": (lambda p, f, b, ks: p.TfheBootstrapContext(f, b, LWE, 2, ks, chunk=CHUNK, grouping_factor=G), False,
                             {32: (5760 + 368, 7), 64: (5760 + 696, 7)}),
+    "bootstrap many-LUT": (lambda p, f, b, ks: p.TfheBootstrapContext(f, b, LWE, 1, ks, chunk=CHUNK, log_luts=1), False,
+                           {32: (312, 4), 64: (584, 4)}),
+    "circuit bootstrap, shared rotation": (
+        lambda p, f, b, ks: p.TfheCircuitBootstrapContext(f, b, LWE, 1, b, ks, chunk=CHUNK, shared_rotation=True), False,
+        {32: (312, 4), 64: (584, 4)}),
     "circuit bootstrap over the whole loop": (
         lambda p, f, b, ks: p.TfheCircuitBootstrapContext(f, b, LWE, 1, b, ks, chunk=CHUNK), False, {32: (472, 4), 64: (872, 4)}),
     "circuit bootstrap per step": (
