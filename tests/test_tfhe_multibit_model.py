@@ -1,14 +1,18 @@
 """The numpy model of the multi-bit blind rotation (tests/tfhe_multibit_model.py) against what it has to mean: M(r) is the
 transform of the monomial, indicator keys rotate a message by X^{sum a_i s_i}, the combined key of g = 1 is
 K_0 + X^a K_1, and on full-torus keys the model's own error against the exact integer step is printed per shape (the
-quantity the GPU tests' error rule is relative to)."""
+quantity the GPU tests' error rule is relative to).  Then the exact regime: for every exact case of
+tests/test_gpu_tfhe_multibit_edges.py (the tables of tests/tfhe_multibit_cases.py) the 2^g rule holds and the f64 model
+equals the integer model word for word on that file's own inputs."""
 import itertools
 
 import numpy as np
 import pytest
 
 import tfhe_blindrot_model as bm
+import tfhe_bootstrap_model as bs
 import tfhe_fft_model as m
+import tfhe_multibit_cases as cases
 import tfhe_multibit_model as mbm
 
 
@@ -83,3 +87,104 @@ def test_model_error_against_the_exact_group_on_full_torus_keys(bits, log_n, k, 
     print(f"bits {bits} N 2^{log_n} k {k} logB {lb} ell {ell} g {g}: model_err {err:.3g} (single product {single_err:.3g})")
     budget = (1 << g) * n * (k + 1) * ell * 2.0 ** (bits - 1) * 2.0 ** (lb - 1) * 2.0 ** -53 * 4 * log_n
     assert err <= max(1.0, budget)
+
+
+# ---------------- the exact regime of tests/test_gpu_tfhe_multibit_edges.py ----------------
+#
+# The GPU file asks for every word of the integer model.  That can only be asked where f64 holds every accumulator: under
+# the 2^g rule of tests/tfhe_multibit_cases.py.  Here the rule is asserted for every exact case of that file, and the f64
+# model (the key combined in the Fourier domain, as the device combines it) is shown to give the integer model's words on
+# that file's own inputs.  Necessary, not sufficient: the device rounds in another order.
+
+def assert_step_is_exact(acc, keys, exps, g, mb, log_n, k):
+    """every ciphertext of acc through every group: step (f64) == exact_group (integers), the integer result carried on;
+    returns the integer result and, per group, whether any ciphertext entered it with a non-zero digit"""
+    W = (k + 1) << log_n
+    exps = np.asarray(exps).reshape(acc.size // W, -1)
+    groups = exps.shape[1] // g
+    fourier = [mbm.fourier(keys[t << g:(t + 1) << g], log_n, mb.bits) for t in range(groups)]
+    out, live = [], [False] * groups
+    for e in range(acc.size // W):
+        a = acc[e * W:(e + 1) * W]
+        for t in range(groups):
+            live[t] = live[t] or bool(np.stack(mb.digits(a)).any())
+            x = exps[e, t * g:(t + 1) * g]
+            exact = mbm.exact_group(a, keys[t << g:(t + 1) << g], x, mb, log_n, k)
+            assert np.array_equal(mbm.step(a, fourier[t], x, mb, log_n, k), exact), (e, t, x.tolist())
+            a = exact
+        out.append(a)
+    return np.concatenate(out), live
+
+
+def test_exact_rotate_loop_is_exact_group_over_the_groups_with_exponents_modulo_2n():
+    bits, log_n, k, g = 32, 3, 1, 2
+    n = 1 << log_n
+    mb = m.ApproxSignedBasis(bits, 7, 3)
+    rng = np.random.default_rng(5)
+    keys = [rng.integers(-1024, 1025, 2 * 3 * 2 * n).astype(np.uint32) for _ in range(3 << g)]
+    acc = rng.integers(0, 2 ** bits, 2 * n, dtype=np.uint64).astype(np.uint32)
+    exps = rng.integers(0, 2 * n, 3 * g).astype(np.uint32)
+    want = acc
+    for t in range(3):
+        want = mbm.exact_group(want, keys[t << g:(t + 1) << g], exps[t * g:(t + 1) * g], mb, log_n, k)
+    assert np.array_equal(mbm.exact_rotate_loop(acc, keys, exps, g, mb, log_n, k), want)
+    big = (exps.astype(np.uint64) + 2 * n * np.array([1, 3, 5, 2 ** 27 - 1, 7, 2], np.uint64)).astype(np.uint32)
+    assert big.min() >= 2 * n
+    assert np.array_equal(mbm.exact_rotate_loop(acc, keys, big, g, mb, log_n, k), want)
+    assert not np.array_equal(want, acc)
+
+
+@pytest.mark.parametrize("bits,log_n,k,lb,ell,g,gmax", cases.EDGE_GROUP)
+def test_edge_group_cases_stay_in_the_exact_regime(bits, log_n, k, lb, ell, g, gmax):
+    assert cases.rule_lhs(bits, log_n, k, lb, ell, g, gmax) <= 2 ** 40
+    c = cases.edge_group_case(bits, log_n, k, lb, ell, g, gmax)
+    cases.assert_patterns_reach(c["exps"], 1 << log_n, g)
+    assert all(np.abs(key.view(m.SINT[bits]).astype(np.int64)).max() <= gmax for key in c["keys"])
+    assert gmax <= cases.largest_gmax(bits, log_n, k, lb, ell, g)
+    out, _ = assert_step_is_exact(c["acc"], c["keys"], c["exps"], g, c["mb"], log_n, k)
+    W = (k + 1) << log_n
+    for e in c["quiet"]:                                   # the product of the quiet ciphertexts is zero
+        assert not out[e * W:(e + 1) * W].any()
+        assert c["acc"][e * W:(e + 1) * W].any() or c["mb"].drop_bits == 0
+
+
+@pytest.mark.parametrize("bits,log_n,k,lb,ell,g", cases.SMALL_CASES)
+def test_small_n_cases_stay_in_the_exact_regime(bits, log_n, k, lb, ell, g):
+    c = cases.small_n_case(bits, log_n, k, lb, ell, g)
+    assert 2 ** 39 < cases.rule_lhs(bits, log_n, k, lb, ell, g, c["gmax"]) <= 2 ** 40
+    cases.assert_patterns_reach(c["exps"], 1 << log_n, g)
+    out, live = assert_step_is_exact(c["acc"], c["keys"], c["exps"], g, c["mb"], log_n, k)
+    print(f"groups entered with a non-zero digit: {live}")
+    assert live[0] and (all(live) or bits == 64)           # u64 beyond the first group: tfhe_multibit_cases.largest_gmax
+    W = (k + 1) << log_n
+    want = np.concatenate([mbm.exact_rotate_loop(c["acc"][e * W:(e + 1) * W], c["keys"], c["exps"][e], g, c["mb"], log_n, k)
+                           for e in range(cases.SMALL_BATCH)])
+    assert np.array_equal(out, want)
+
+
+@pytest.mark.parametrize("bits,log_n,k,lb,ell,g", cases.HANDLE_CASES)
+def test_handle_cases_stay_in_the_exact_regime(bits, log_n, k, lb, ell, g):
+    """the rotation's inputs as the handle forms them (ACC = X^{neg_b} TV, the switched mask), with the shared test vector;
+    and bootstrap(rotate=...) is sample extraction of exactly these accumulators"""
+    c = cases.handle_case(bits, log_n, k, lb, ell, g)
+    assert 2 ** 39 < cases.rule_lhs(bits, log_n, k, lb, ell, g, c["gmax"]) <= 2 ** 40
+    assert c["n"] % g == 0 and 4 <= c["n"] < 4 + g
+    exps, neg_b = cases.assert_handle_inputs_sit_on_the_branch_points(c, bits, log_n)
+    tv = c["tvs"]["shared"]
+    acc = np.concatenate([bm.rotate(tv, int(r), 1 << log_n) for r in neg_b])
+    out, live = assert_step_is_exact(acc, c["keys"], exps, g, c["mb"], log_n, k)
+    assert all(live) and out.any()                         # every group multiplies something: tfhe_multibit_cases.HANDLE_CASES
+    if log_n <= 6:
+        want = bs.bootstrap(c["lwe"], c["keys"], tv, None, c["mb"], c["ks_mb"], log_n, k, c["n"], rotate=cases.multibit_rotate(g))
+        assert np.array_equal(want, bs.sample_extract(out, log_n, k, 0))
+
+
+def test_bootstrap_model_default_rotation_is_unchanged():
+    bits, log_n, k, n = 32, 3, 1, 4
+    mb, ks_mb = m.ApproxSignedBasis(bits, 7, 3), m.ApproxSignedBasis(bits, 4, 3)
+    rng = np.random.default_rng(6)
+    keys = [rng.integers(-1024, 1025, 2 * 3 * 2 << log_n).astype(np.uint32) for _ in range(n)]
+    lwe = rng.integers(0, 2 ** bits, 3 * (n + 1), dtype=np.uint64).astype(np.uint32)
+    tv = rng.integers(0, 2 ** bits, 2 << log_n, dtype=np.uint64).astype(np.uint32)
+    assert np.array_equal(bs.bootstrap(lwe, keys, tv, None, mb, ks_mb, log_n, k, n),
+                          bs.bootstrap(lwe, keys, tv, None, mb, ks_mb, log_n, k, n, rotate=bm.exact_rotate))

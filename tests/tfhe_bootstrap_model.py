@@ -115,9 +115,12 @@ def noise_free_ksk(s_in: np.ndarray, s_out: np.ndarray, basis: m.ApproxSignedBas
 
 # ---------------- the whole bootstrap ----------------
 
-def bootstrap(lwe_in, keys_coeff, tv, ksk, basis: m.ApproxSignedBasis, ks_basis, log_n: int, k: int, n: int) -> np.ndarray:
+def bootstrap(lwe_in, keys_coeff, tv, ksk, basis: m.ApproxSignedBasis, ks_basis, log_n: int, k: int, n: int,
+              rotate=bm.exact_rotate) -> np.ndarray:
     """modulus switch, ACC = X^{neg_b} TV, exact_rotate over the n coefficient-domain keys, extraction at index 0 and,
-    when ksk is not None, the key switch from k N to n.  tv: (k+1) N words shared by the batch, or one per ciphertext."""
+    when ksk is not None, the key switch from k N to n.  tv: (k+1) N words shared by the batch, or one per ciphertext.
+    rotate(acc_e, keys_coeff, exps_e, basis, log_n, k) is the rotation of one ciphertext: another one (a closure over
+    tfhe_multibit_model.exact_rotate_loop and its grouping factor) models the handle over the multi-bit rotation."""
     bits, big_n = basis.bits, 1 << log_n
     glwe = (k + 1) * big_n
     exps, neg_b = modulus_switch(lwe_in, n, bits, log_n)
@@ -125,7 +128,7 @@ def bootstrap(lwe_in, keys_coeff, tv, ksk, basis: m.ApproxSignedBasis, ks_basis,
     accs = []
     for e in range(exps.shape[0]):
         t = tv if tv.size == glwe else tv[e * glwe:(e + 1) * glwe]
-        accs.append(bm.exact_rotate(bm.rotate(t, int(neg_b[e]), big_n), keys_coeff, exps[e], basis, log_n, k))
+        accs.append(rotate(bm.rotate(t, int(neg_b[e]), big_n), keys_coeff, exps[e], basis, log_n, k))
     lwe = sample_extract(np.concatenate(accs), log_n, k, 0)
     return lwe if ksk is None else keyswitch(lwe, ksk, k * big_n, n, ks_basis)
 

@@ -85,6 +85,16 @@ def exact_group(acc_e: np.ndarray, keys_coeff, exps_group, basis: m.ApproxSigned
     return m.schoolbook(acc_e, exact_key(keys_coeff, exps_group, log_n), basis, log_n, k).astype(acc_e.dtype)
 
 
+def exact_rotate_loop(acc_e: np.ndarray, keys_coeff, exps_e, g: int, basis: m.ApproxSignedBasis, log_n: int, k: int) -> np.ndarray:
+    """the whole loop for ONE ciphertext in integers: exact_group over the groups.  keys_coeff: groups * 2^g coefficient-domain
+    keys, group after group; exps_e: groups * g exponents, each taken modulo 2N (device-form words of 2N and more allowed)"""
+    assert len(exps_e) % g == 0 and len(keys_coeff) == (len(exps_e) // g) << g
+    acc = np.asarray(acc_e).copy()
+    for t in range(len(exps_e) // g):
+        acc = exact_group(acc, keys_coeff[t << g:(t + 1) << g], exps_e[t * g:(t + 1) * g], basis, log_n, k)
+    return acc
+
+
 def indicator_keys(basis: m.ApproxSignedBasis, log_n: int, k: int, key_bits) -> list:
     """the 2^g trivially encrypted keys of one group: key j is G when the group's key bits equal pattern j, 0 otherwise"""
     g = len(key_bits)
