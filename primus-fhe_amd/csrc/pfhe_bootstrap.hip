@@ -1,9 +1,8 @@
 // pfhe_bootstrap.hip — the steps of a TFHE programmable bootstrap around the blind rotation, and the handle that runs
 // them in order (include/pfhe.h: pfhe_tfhe{,32}_modswitch_dev, _sample_extract*, _keyswitch*, _bootstrap_*).
 //
-//   modulus switch     LWE words -> exponents modulo 2N.  The reference has no modulus switching; the rule is this
-//                      project's own: sw(w) = (((w >> (shift-1)) + 1) >> 1) & (2N-1), shift = BITS - log_n - 1, i.e.
-//                      round(w 2N / 2^BITS) with ties up, computed without overflow.
+//   modulus switch     LWE words -> exponents modulo 2N: switch_rounded at stride 0, round(w 2N / 2^BITS) with ties up,
+//                      reduced modulo 2N.
 //   accumulator init   ACC_e = X^{neg_b[e]} TV, the rotation of pfhe_tfhe*_mul_monomial_each_to_dev with the test vector
 //                      read in place (one shared by the batch, or one per ciphertext).
 //   blind rotation     the classic or the multi-bit handle (pfhe_fft.hip) behind TfheRotation, called as it is.
@@ -15,11 +14,12 @@
 //                      index below 2^log_luts of pfhe_manylut.hip in place of the first and the fourth step.
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
 // the two forms of every call (stateless_call, handle_call) go through pfhe_tfhe_host.hpp; the key switch keeps its own
-// 2-D grid.
+// 2-D grid.  The rules of the exact steps and the key switch's tile are pfhe_tfhe_exact_device.hpp's.
 #include <algorithm>
 #include <cstdint>
 #include <memory>
 
+#include "pfhe_tfhe_exact_device.hpp"
 #include "pfhe_tfhe_handles.hpp"
 
 using namespace pfhe;
@@ -37,8 +37,8 @@ __global__ __launch_bounds__(kThreads) void tfhe_modswitch_kernel(const W *__res
     if (t >= total) return;
     const u64 e = t / (n + 1);
     const u32 i = (u32)(t - e * (n + 1));
-    const u32 shift = 8 * sizeof(W) - log_n - 1, two_n_mask = (2u << log_n) - 1;
-    const u32 v = (u32)(((lwe[t] >> (shift - 1)) + 1) >> 1) & two_n_mask;
+    const u32 two_n_mask = (2u << log_n) - 1;
+    const u32 v = switch_rounded<W>(lwe[t], log_n, 0) & two_n_mask;
     if (i < n)
         exps[e * n + i] = v;
     else
@@ -47,8 +47,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_modswitch_kernel(const W *__res
 
 // ---------------- accumulator init ----------------
 
-// ACC_e = X^{neg_b[e]} TV_e, one thread per accumulator word.  X^r p [j] = +-p[(j - r) mod N], the wrapped part negated;
-// r >= N negates the other part (the rule of tfhe_blindrot_glue_kernel).  tv_stride: words between the test vectors of
+// ACC_e = X^{neg_b[e]} TV_e (MonomialShift), one thread per accumulator word.  tv_stride: words between the test vectors of
 // consecutive ciphertexts, 0 when one is shared by the batch.
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_acc_init_kernel(const W *__restrict__ tv, W *__restrict__ acc,
@@ -56,20 +55,16 @@ __global__ __launch_bounds__(kThreads) void tfhe_acc_init_kernel(const W *__rest
                                                                  u64 tv_stride, u64 total) {
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
-    const u32 n = 1u << log_n, mask = n - 1;
+    const u32 n = 1u << log_n, j = (u32)(t & (n - 1));
     const u64 poly = t >> log_n, e = poly / rows;
     const u32 row = (u32)(poly - e * rows);
-    const u32 r = neg_b[e] & (2 * n - 1);
-    const bool high = r >= n;
-    const u32 rot = high ? r - n : r;
-    const u32 j = (u32)(t & mask);
-    const W v = tv[e * tv_stride + ((u64)row << log_n) + ((j - rot) & mask)];
-    acc[t] = ((j < rot) != high) ? (W)0 - v : v;
+    const MonomialShift x(neg_b[e], n);
+    acc[t] = x.apply(j, tv[e * tv_stride + ((u64)row << log_n) + x.source(j)]);
 }
 
 // ---------------- sample extraction ----------------
 
-// one thread per output word: out[jN + i] = A_j[h - i] (i <= h) or -A_j[N + h - i] (i > h), out[kN] = B[h]
+// one thread per output word: out[jN + i] = extract_word(A_j, h, N, i), out[kN] = B[h]
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_sample_extract_kernel(const W *__restrict__ glwe, W *__restrict__ lwe, u32 k,
                                                                        u32 log_n, u32 h, u64 total) {
@@ -84,23 +79,13 @@ __global__ __launch_bounds__(kThreads) void tfhe_sample_extract_kernel(const W *
         return;
     }
     const u32 i = (u32)(c & (n - 1));
-    const W *a = ct + (c - i);
-    lwe[t] = i <= h ? a[h - i] : (W)0 - a[n + h - i];
+    lwe[t] = extract_word(ct + (c - i), h, n, i);
 }
 
 // ---------------- key switch ----------------
 //
-// A small integer GEMM: M = batch, K = in_dimension * ell, N = out_dimension + 1.  One workgroup owns kKsTileM ciphertexts
-// x kKsTileN output columns; a thread owns kKsRows ciphertexts (its wave's) x kKsCols columns (its lane's, kKsLanes apart)
-// and keeps their sums in registers.  The workgroup walks the mask words in groups of `ki`: first every (ciphertext, mask
-// word) pair of the group gets its ell signed digits from ONE thread, which writes them to LDS as words; then every thread
-// streams the group's key rows, coalesced along the columns and kKsUnroll rows in flight at a time, against the digits of
-// its ciphertexts, which all lanes of a wave read from the same LDS address (a broadcast).  ki * ell <= kKsMaxRows bounds the LDS at kKsMaxRows * kKsTileM words.
-constexpr int kKsLanes = 64, kKsWaves = kThreads / kKsLanes;
-constexpr int kKsRows = 8, kKsCols = 2;
-constexpr int kKsTileM = kKsWaves * kKsRows, kKsTileN = kKsLanes * kKsCols;
-constexpr u32 kKsMaxRows = 64;
-constexpr int kKsUnroll = 4;
+// The key-switch tile of pfhe_tfhe_exact_device.hpp with M = batch, K = in_dimension * ell, out_dimension + 1 columns: the
+// workgroup walks the mask words, and the body goes into the last column behind the sums.
 
 struct KsShape {
     u32 in_dim, out_dim, log_basis, ell, drop_bits, ki;
@@ -109,67 +94,19 @@ struct KsShape {
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_keyswitch_kernel(const W *__restrict__ lwe_in, const W *__restrict__ ksk,
                                                                   W *__restrict__ lwe_out, KsShape s, u64 batch) {
-    __shared__ W dig[kKsMaxRows * kKsTileM];  // [mask word of the group][level][ciphertext of the tile]
+    __shared__ W dig[kKsMaxRows * kKsTileM];
     const u32 lane = threadIdx.x % kKsLanes, wave = threadIdx.x / kKsLanes;
     const u32 cols = s.out_dim + 1;
     const u32 c0 = blockIdx.x * kKsTileN + lane;
     const u64 e0 = (u64)blockIdx.y * kKsTileM;
     const u64 in_stride = (u64)s.in_dim + 1;
-    W acc[kKsRows][kKsCols];
-#pragma unroll
-    for (int r = 0; r < kKsRows; ++r)
-#pragma unroll
-        for (int c = 0; c < kKsCols; ++c) acc[r][c] = 0;
-
+    W acc[kKsRows][kKsCols] = {};
     // the key columns of this thread; a column past the end reads the last one instead (its sums are never stored), so that
     // no load of the inner loop sits behind a branch
     const W *key[kKsCols];
 #pragma unroll
     for (int c = 0; c < kKsCols; ++c) key[c] = ksk + min(c0 + c * kKsLanes, cols - 1);
-
-    // the pair this thread decomposes in every group: mask word ii of the group, ciphertext ei of the tile
-    const u32 ii = threadIdx.x % s.ki, ei = threadIdx.x / s.ki;
-    for (u32 i0 = 0; i0 < s.in_dim; i0 += s.ki) {
-        if (ei < (u32)kKsTileM) {
-            const bool live = e0 + ei < batch && i0 + ii < s.in_dim;
-            const W v = live ? lwe_in[(e0 + ei) * in_stride + i0 + ii] : (W)0;
-            u32 carry = init_carry(v, s.drop_bits);
-            for (u32 l = 0; l < s.ell; ++l)
-                dig[(ii * s.ell + l) * kKsTileM + ei] = digit_word(v, s.drop_bits + l * s.log_basis, s.log_basis, carry);
-        }
-        __syncthreads();
-        const u32 rows = min(s.ki, s.in_dim - i0) * s.ell;
-        const u64 key_row = (u64)i0 * s.ell;
-        u32 row = 0;
-        // kKsUnroll rows at a time: all their key words are requested before the first is used
-        for (; row + kKsUnroll <= rows; row += kKsUnroll) {
-            W kv[kKsUnroll][kKsCols];
-#pragma unroll
-            for (int u = 0; u < kKsUnroll; ++u)
-#pragma unroll
-                for (int c = 0; c < kKsCols; ++c) kv[u][c] = key[c][(key_row + row + u) * cols];
-#pragma unroll
-            for (int u = 0; u < kKsUnroll; ++u)
-#pragma unroll
-                for (int r = 0; r < kKsRows; ++r) {
-                    const W d = dig[(row + u) * kKsTileM + wave * kKsRows + r];
-#pragma unroll
-                    for (int c = 0; c < kKsCols; ++c) acc[r][c] += d * kv[u][c];
-                }
-        }
-        for (; row < rows; ++row) {
-            W kv[kKsCols];
-#pragma unroll
-            for (int c = 0; c < kKsCols; ++c) kv[c] = key[c][(key_row + row) * cols];
-#pragma unroll
-            for (int r = 0; r < kKsRows; ++r) {
-                const W d = dig[row * kKsTileM + wave * kKsRows + r];
-#pragma unroll
-                for (int c = 0; c < kKsCols; ++c) acc[r][c] += d * kv[c];
-            }
-        }
-        __syncthreads();  // the next group overwrites the digits
-    }
+    ks_tile_sums(dig, lwe_in, in_stride, s.in_dim, e0, batch, key, cols, s.log_basis, s.ell, s.drop_bits, s.ki, acc);
 #pragma unroll
     for (int r = 0; r < kKsRows; ++r) {
         const u64 e = e0 + wave * kKsRows + r;
@@ -271,7 +208,7 @@ int keyswitch_shape(size_t in_dimension, size_t out_dimension, uint32_t log_basi
     PFHE_TRY(require_lwe_dimension(in_dimension, "key switch: both dimensions must be in 1..2^31-2"));
     PFHE_TRY(require_lwe_dimension(out_dimension, "key switch: both dimensions must be in 1..2^31-2"));
     sh = KsShape{(u32)in_dimension, (u32)out_dimension, log_basis, ell, drop,
-                 std::max<u32>(1, std::min<u32>(kKsMaxRows / ell, kThreads / kKsTileM))};
+                 ks_group_words(ell)};
     return PFHE_OK;
 }
 

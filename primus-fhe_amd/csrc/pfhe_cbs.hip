@@ -22,6 +22,7 @@
 #include <cstdint>
 #include <memory>
 
+#include "pfhe_tfhe_exact_device.hpp"
 #include "pfhe_tfhe_handles.hpp"
 
 using namespace pfhe;
@@ -31,20 +32,9 @@ namespace {
 
 // ---------------- the private functional key switch ----------------
 //
-// A small integer GEMM per key block u: M = batch * levels input ciphertexts, K = (in_dimension + 1) * ell key rows,
-// (k+1) N columns.  The tiling is the LWE key switch's (pfhe_bootstrap.hip): one workgroup owns kPfTileM ciphertexts x
-// kPfTileN columns of ONE key block (grid.z); a thread owns kPfRows ciphertexts (its wave's) x kPfCols columns (its
-// lane's, kPfLanes apart) and keeps their sums in registers.  The workgroup walks the input words, body included, in
-// groups of `ki`: every (ciphertext, word) pair of the group gets its ell signed digits from ONE thread, which writes
-// them to LDS as words; then every thread streams the group's key rows, coalesced along the columns and kPfUnroll rows
-// in flight, against the digits of its ciphertexts, which all lanes of a wave read from the same LDS address (a
-// broadcast).  ki * ell <= kPfMaxRows bounds the LDS at kPfMaxRows * kPfTileM words: 8 KiB for u32, 16 KiB for u64, a
-// constant of the design.  Input row m = e * levels + l is stored to out[e][u][l].
-constexpr int kPfLanes = 64, kPfWaves = kThreads / kPfLanes;
-constexpr int kPfRows = 8, kPfCols = 2;
-constexpr int kPfTileM = kPfWaves * kPfRows, kPfTileN = kPfLanes * kPfCols;
-constexpr u32 kPfMaxRows = 64;
-constexpr int kPfUnroll = 4;
+// The key-switch tile of pfhe_tfhe_exact_device.hpp per key block u (grid.z): M = batch * levels input ciphertexts, K =
+// (in_dimension + 1) * ell key rows, (k+1) N columns.  The workgroup walks the input words, body included.  Input row m =
+// e * levels + l is stored to out[e][u][l].
 constexpr size_t kMaxLevels = 64;
 
 struct PfksShape {
@@ -54,76 +44,28 @@ struct PfksShape {
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_pfks_kernel(const W *__restrict__ lwe_in, const W *__restrict__ pfksk,
                                                              W *__restrict__ out, PfksShape s, u64 m0, u64 m_total) {
-    __shared__ W dig[kPfMaxRows * kPfTileM];  // [word of the group][level][ciphertext of the tile]
-    const u32 lane = threadIdx.x % kPfLanes, wave = threadIdx.x / kPfLanes;
+    __shared__ W dig[kKsMaxRows * kKsTileM];
+    const u32 lane = threadIdx.x % kKsLanes, wave = threadIdx.x / kKsLanes;
     const u32 cols = (s.k + 1) << s.log_n, words = s.in_dim + 1;
-    const u32 c0 = blockIdx.x * kPfTileN + lane;
-    const u64 r0 = m0 + (u64)blockIdx.y * kPfTileM;
+    const u32 c0 = blockIdx.x * kKsTileN + lane;
+    const u64 r0 = m0 + (u64)blockIdx.y * kKsTileM;
     const u32 u = blockIdx.z;
-    W acc[kPfRows][kPfCols];
-#pragma unroll
-    for (int r = 0; r < kPfRows; ++r)
-#pragma unroll
-        for (int c = 0; c < kPfCols; ++c) acc[r][c] = 0;
-
+    W acc[kKsRows][kKsCols] = {};
     // the key columns of this thread in block u; a column past the end reads the last one instead (its sums are never
     // stored), so that no load of the inner loop sits behind a branch
-    const W *key[kPfCols];
+    const W *key[kKsCols];
 #pragma unroll
-    for (int c = 0; c < kPfCols; ++c) key[c] = pfksk + (u64)u * words * s.ell * cols + min(c0 + c * kPfLanes, cols - 1);
-
-    // the pair this thread decomposes in every group: word ii of the group, ciphertext ei of the tile
-    const u32 ii = threadIdx.x % s.ki, ei = threadIdx.x / s.ki;
-    for (u32 i0 = 0; i0 < words; i0 += s.ki) {
-        if (ei < (u32)kPfTileM) {
-            const bool live = r0 + ei < m_total && i0 + ii < words;
-            const W v = live ? lwe_in[(r0 + ei) * words + i0 + ii] : (W)0;
-            u32 carry = init_carry(v, s.drop_bits);
-            for (u32 l = 0; l < s.ell; ++l)
-                dig[(ii * s.ell + l) * kPfTileM + ei] = digit_word(v, s.drop_bits + l * s.log_basis, s.log_basis, carry);
-        }
-        __syncthreads();
-        const u32 rows = min(s.ki, words - i0) * s.ell;
-        const u64 key_row = (u64)i0 * s.ell;
-        u32 row = 0;
-        // kPfUnroll rows at a time: all their key words are requested before the first is used
-        for (; row + kPfUnroll <= rows; row += kPfUnroll) {
-            W kv[kPfUnroll][kPfCols];
+    for (int c = 0; c < kKsCols; ++c) key[c] = pfksk + (u64)u * words * s.ell * cols + min(c0 + c * kKsLanes, cols - 1);
+    ks_tile_sums(dig, lwe_in, (u64)words, words, r0, m_total, key, cols, s.log_basis, s.ell, s.drop_bits, s.ki, acc);
 #pragma unroll
-            for (int q = 0; q < kPfUnroll; ++q)
-#pragma unroll
-                for (int c = 0; c < kPfCols; ++c) kv[q][c] = key[c][(key_row + row + q) * cols];
-#pragma unroll
-            for (int q = 0; q < kPfUnroll; ++q)
-#pragma unroll
-                for (int r = 0; r < kPfRows; ++r) {
-                    const W d = dig[(row + q) * kPfTileM + wave * kPfRows + r];
-#pragma unroll
-                    for (int c = 0; c < kPfCols; ++c) acc[r][c] += d * kv[q][c];
-                }
-        }
-        for (; row < rows; ++row) {
-            W kv[kPfCols];
-#pragma unroll
-            for (int c = 0; c < kPfCols; ++c) kv[c] = key[c][(key_row + row) * cols];
-#pragma unroll
-            for (int r = 0; r < kPfRows; ++r) {
-                const W d = dig[row * kPfTileM + wave * kPfRows + r];
-#pragma unroll
-                for (int c = 0; c < kPfCols; ++c) acc[r][c] += d * kv[c];
-            }
-        }
-        __syncthreads();  // the next group overwrites the digits
-    }
-#pragma unroll
-    for (int r = 0; r < kPfRows; ++r) {
-        const u64 m = r0 + wave * kPfRows + r;
+    for (int r = 0; r < kKsRows; ++r) {
+        const u64 m = r0 + wave * kKsRows + r;
         if (m >= m_total) continue;
         const u64 e = m / s.levels, l = m - e * s.levels;
         W *dst = out + ((e * (s.k + 1) + u) * s.levels + l) * cols;
 #pragma unroll
-        for (int c = 0; c < kPfCols; ++c) {
-            const u32 col = c0 + c * kPfLanes;
+        for (int c = 0; c < kKsCols; ++c) {
+            const u32 col = c0 + c * kKsLanes;
             if (col < cols) dst[col] = (W)0 - acc[r][c];
         }
     }
@@ -155,8 +97,8 @@ __global__ __launch_bounds__(kThreads) void tfhe_pfksk_add_message_kernel(W *__r
 
 // ---------------- the stages of the circuit bootstrap around the rotation ----------------
 
-// The modulus switch of pfhe_bootstrap.hip on (a, b + 2^(BITS-2)), one thread per input word: the exponents of input e are
-// written once per level, exps[(e levels + l) n + i], for the levels accumulators the rotation sees; neg_b[e] once
+// The plain modulus switch (switch_rounded at stride 0) on (a, b + 2^(BITS-2)), one thread per input word: the exponents of
+// input e are written once per level, exps[(e levels + l) n + i], for the levels accumulators the rotation sees; neg_b[e] once
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_cbs_modswitch_kernel(const W *__restrict__ lwe, u32 *__restrict__ exps,
                                                                       u32 *__restrict__ neg_b, u32 n, u32 log_n, u32 levels,
@@ -165,9 +107,9 @@ __global__ __launch_bounds__(kThreads) void tfhe_cbs_modswitch_kernel(const W *_
     if (t >= total) return;
     const u64 e = t / (n + 1);
     const u32 i = (u32)(t - e * (n + 1));
-    const u32 shift = 8 * sizeof(W) - log_n - 1, two_n_mask = (2u << log_n) - 1;
+    const u32 two_n_mask = (2u << log_n) - 1;
     const W w = i < n ? lwe[t] : (W)(lwe[t] + ((W)1 << (8 * sizeof(W) - 2)));
-    const u32 v = (u32)(((w >> (shift - 1)) + 1) >> 1) & two_n_mask;
+    const u32 v = switch_rounded<W>(w, log_n, 0) & two_n_mask;
     if (i < n) {
         for (u32 l = 0; l < levels; ++l) exps[(e * levels + l) * n + i] = v;
     } else {
@@ -176,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_cbs_modswitch_kernel(const W *_
 }
 
 // ACC_{e,l} = X^{neg_b[e]} TV_l, one thread per accumulator word: the mask polynomials are 0 and every body coefficient is
-// -+g_l/2, g_l/2 = 2^(half_shift + l log_basis), with the sign of tfhe_acc_init_kernel's rotation
+// -+g_l/2, g_l/2 = 2^(half_shift + l log_basis), with MonomialShift's sign
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_cbs_acc_init_kernel(W *__restrict__ acc, const u32 *__restrict__ neg_b, u32 k,
                                                                      u32 log_n, u32 levels, u32 log_basis, u32 half_shift,
@@ -191,12 +133,9 @@ __global__ __launch_bounds__(kThreads) void tfhe_cbs_acc_init_kernel(W *__restri
     }
     const u64 e = a / levels;
     const u32 l = (u32)(a - e * levels);
-    const u32 r = neg_b[e] & (2 * n - 1);
-    const bool high = r >= n;
-    const u32 rot = high ? r - n : r;
-    const u32 j = (u32)(t & (n - 1));
-    const W v = (W)0 - ((W)1 << (half_shift + l * log_basis));  // TV_l: -g_l/2
-    acc[t] = ((j < rot) != high) ? (W)0 - v : v;
+    const MonomialShift x(neg_b[e], n);
+    const W half = (W)1 << (half_shift + l * log_basis);  // TV_l is -g_l/2 on every coefficient: X^r TV_l = -(X^r g_l/2)
+    acc[t] = (W)0 - x.apply((u32)(t & (n - 1)), half);
 }
 
 // sample extraction at index 0 of accumulator (e, l) with g_l/2 added to the body: out[jN] = A_j[0], out[jN + i] =
@@ -221,38 +160,18 @@ __global__ __launch_bounds__(kThreads) void tfhe_cbs_extract_kernel(const W *__r
 
 // ---------------- launches (arguments already checked) ----------------
 
-inline u32 pfks_group_words(u32 ell) { return std::max<u32>(1, std::min<u32>(kPfMaxRows / ell, kThreads / kPfTileM)); }
-
 template <class W>
 int launch_pfks(const W *lwe_in, const W *pfksk, W *out, PfksShape sh, u64 rows, hipStream_t s) {
-    const u32 gx = (((sh.k + 1) << sh.log_n) + kPfTileN - 1) / kPfTileN;
-    return launch_y_slices((rows + kPfTileM - 1) / kPfTileM, [&](u64 first_tile, u32 tiles) {
-        return launch_grid(tfhe_pfks_kernel<W>, dim3(gx, tiles, sh.k + 1), 0, s, lwe_in, pfksk, out, sh, first_tile * kPfTileM,
+    const u32 gx = (((sh.k + 1) << sh.log_n) + kKsTileN - 1) / kKsTileN;
+    return launch_y_slices((rows + kKsTileM - 1) / kKsTileM, [&](u64 first_tile, u32 tiles) {
+        return launch_grid(tfhe_pfks_kernel<W>, dim3(gx, tiles, sh.k + 1), 0, s, lwe_in, pfksk, out, sh, first_tile * kKsTileM,
                            rows);
     });
-}
-
-inline int glwe_body_add(const pfhe_fft *f, size_t k, u64 *glwe, size_t len, const u64 *key, size_t len_key, hipStream_t s) {
-    return pfhe_tfhe_glwe_body_mac_dev(f, k, (uint64_t *)glwe, len, (const uint64_t *)key, len_key, 0, s);
-}
-inline int glwe_body_add(const pfhe_fft *f, size_t k, u32 *glwe, size_t len, const u32 *key, size_t len_key, hipStream_t s) {
-    return pfhe_tfhe32_glwe_body_mac_dev(f, k, glwe, len, key, len_key, 0, s);
 }
 
 // ---------------- the stateless entry points ----------------
 
 constexpr const char *kPfksDimensions = "private key switch: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2";
-
-// ApproxSignedBasis::new's assert!s, the dimensions, then the table
-template <class W>
-int pfks_dimensions(const char *message, const pfhe_fft *f, size_t k, size_t in_dimension, uint32_t log_basis,
-                    size_t decompose_length, u32 &ell, u32 &drop) {
-    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
-    PFHE_TRY(require_glwe_dimension(k, message));
-    PFHE_TRY(require_lwe_dimension(in_dimension, message));
-    if (!f) return PFHE_ERR_BAD_ARGUMENT;
-    return PFHE_OK;
-}
 
 inline size_t pfksk_words(size_t k, size_t n, size_t in_dimension, size_t ell) {
     return (k + 1) * (in_dimension + 1) * ell * (k + 1) * n;
@@ -262,7 +181,7 @@ template <class W>
 int pfks_check(const pfhe_fft *f, size_t k, size_t len_in, size_t in_dimension, size_t levels, size_t len_pfksk,
                uint32_t log_basis, size_t decompose_length, size_t len_out, PfksShape &sh) {
     u32 ell = 0, drop = 0;
-    PFHE_TRY(pfks_dimensions<W>(kPfksDimensions, f, k, in_dimension, log_basis, decompose_length, ell, drop));
+    PFHE_TRY(tfhe_keyswitch_dimensions<W>(kPfksDimensions, f, k, in_dimension, log_basis, decompose_length, ell, drop));
     if (levels == 0 || levels > kMaxLevels) {
         set_last_error("private key switch: levels must be in 1..64");
         return PFHE_ERR_BAD_ARGUMENT;
@@ -273,7 +192,7 @@ int pfks_check(const pfhe_fft *f, size_t k, size_t len_in, size_t in_dimension, 
                        "(k+1)*(in_dimension+1)*ell*(k+1)*N and out batch*(k+1)*levels*(k+1)*N");
         return PFHE_ERR_BAD_LENGTH;
     }
-    sh = PfksShape{(u32)in_dimension, (u32)k, f->log_n, (u32)levels, log_basis, ell, drop, pfks_group_words(ell)};
+    sh = PfksShape{(u32)in_dimension, (u32)k, f->log_n, (u32)levels, log_basis, ell, drop, ks_group_words(ell)};
     return PFHE_OK;
 }
 
@@ -297,7 +216,7 @@ template <class W>
 int pfksk_generate_dev(const pfhe_fft *f, size_t k, const W *key_in, size_t in_dimension, const W *glwe_key, size_t len_glwe_key,
                        uint32_t log_basis, size_t decompose_length, W *pfksk, size_t len, hipStream_t s) {
     u32 ell = 0, drop = 0;
-    PFHE_TRY(pfks_dimensions<W>("private key-switch key: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2", f, k,
+    PFHE_TRY(tfhe_keyswitch_dimensions<W>("private key-switch key: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2", f, k,
                                 in_dimension, log_basis, decompose_length, ell, drop));
     if (len_glwe_key != k * f->n || len != pfksk_words(k, f->n, in_dimension, ell)) {
         set_last_error("private key-switch key: glwe_key must be k*N words and pfksk (k+1)*(in_dimension+1)*ell*(k+1)*N");
@@ -385,7 +304,7 @@ int cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, s
     h->n = (u32)lwe_dimension;
     h->cb_log_basis = cbs_log_basis;
     const size_t glwe = rot.glwe, ext = glwe_dimension * fft->n + 1, levels = h->cb_ell;
-    h->pf = PfksShape{(u32)(ext - 1), h->k, fft->log_n, h->cb_ell, pfks_log_basis, pf_ell, pf_drop, pfks_group_words(pf_ell)};
+    h->pf = PfksShape{(u32)(ext - 1), h->k, fft->log_n, h->cb_ell, pfks_log_basis, pf_ell, pf_drop, ks_group_words(pf_ell)};
     h->bsk_len = tfhe_bootstrap_keys(grouping, lwe_dimension) * rot.key_len;
     // chunk 0: what the rotation's default holds, capped at about 256 MiB of accumulators
     h->chunk = chunk ? chunk

@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "pfhe_fft_device.hpp"
+#include "pfhe_tfhe_exact_device.hpp"
 #include "pfhe_tfhe_handles.hpp"
 
 using namespace pfhe;
@@ -181,12 +182,10 @@ __global__ __launch_bounds__(kThreads) void tfhe_fused_kernel(const W *__restric
 
 // ---------------- blind rotation over the product ----------------
 
-// coefficient j of X^r * p - p for a polynomial p of N words (wrapping arithmetic): X^r p [j] = +-p[(j - r) mod N], the
-// wrapped part negated; r >= N (high, rot = r - N) negates the other part
+// coefficient j of X^r * p - p for a polynomial p of N words (wrapping arithmetic)
 template <class W>
-__device__ __forceinline__ W rotated_diff(const W *p, u32 j, u32 rot, bool high, u32 mask) {
-    const W v = p[(j - rot) & mask];
-    return (((j < rot) != high) ? (W)0 - v : v) - p[j];
+__device__ __forceinline__ W rotated_diff(const W *p, u32 j, const MonomialShift &x) {
+    return x.apply(j, p[x.source(j)]) - p[j];
 }
 
 // one input row of D = X^r ACC - ACC, held in registers for all its levels
@@ -215,9 +214,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_blindrot_loop_kernel(W *__restr
     const u32 *ex = exps + (u64)blockIdx.x * n_steps;
     const u64 key_len = (u64)4 * s.ell * n;
     for (u32 step = 0; step < n_steps; ++step) {
-        const u32 r = ex[step] & (2 * n - 1);  // the device form takes every exponent modulo 2N
-        const bool high = r >= n;
-        const u32 rot = high ? r - n : r;
+        const MonomialShift x(ex[step], n);  // the device form takes every exponent modulo 2N
         const double2 *key = bsk + step * key_len;
         double2 acc0[kFusedPer], acc1[kFusedPer];
 #pragma unroll
@@ -227,8 +224,8 @@ __global__ __launch_bounds__(kThreads) void tfhe_blindrot_loop_kernel(W *__restr
 #pragma unroll
             for (int u = 0; u < kFusedPer; ++u) {
                 const u32 i = threadIdx.x + u * kThreads;
-                d.a[u] = i < m ? rotated_diff(a + row * n, i, rot, high, n - 1) : (W)0;
-                d.b[u] = i < m ? rotated_diff(a + row * n, i + m, rot, high, n - 1) : (W)0;
+                d.a[u] = i < m ? rotated_diff(a + row * n, i, x) : (W)0;
+                d.b[u] = i < m ? rotated_diff(a + row * n, i + m, x) : (W)0;
             }
             return d;
         }, ClassicKey{key}, lds_l, tw, s, acc0, acc1);
@@ -346,13 +343,10 @@ __global__ __launch_bounds__(kThreads) void tfhe_blindrot_glue_kernel(const W *_
     if constexpr (STORE_ACC) acc_out[i] = a;
     if constexpr (ROT != kRotNone) {
         const u64 el = (i >> log_n) / polys_per_exp;
-        const u32 r = exps[el * exp_stride] & (2 * n - 1);
-        const bool high = r >= n;
-        const u32 rot = high ? r - n : r;
+        const MonomialShift shift(exps[el * exp_stride], n);
         const u32 j = (u32)(i & mask);
-        const u64 src = (i - j) + ((j - rot) & mask);
-        const W v = ADD_E ? (W)(acc[src] + e_in[src]) : acc[src];
-        const W x = ((j < rot) != high) ? (W)0 - v : v;
+        const u64 src = (i - j) + shift.source(j);
+        const W x = shift.apply(j, ADD_E ? (W)(acc[src] + e_in[src]) : acc[src]);
         d_out[i] = ROT == kRotSub ? (W)(x - a) : x;
     }
 }

@@ -3,30 +3,25 @@
 // (pfhe_bootstrap.hip, log_luts) and the circuit bootstrap handle (pfhe_cbs.hip, shared_rotation) queue them through the
 // launches declared in pfhe_tfhe_handles.hpp.  Each generalises a kernel of one of those files, which stays as it is:
 //
-//   strided modulus switch    sw_v(w) = ((((w >> (BITS - log_n - 2 + v)) + 1) >> 1) << v) & (2N-1): round(w 2N / 2^v / 2^BITS)
-//                             with ties up, times 2^v.  v = 0 is tfhe_modswitch_kernel's rule; with body_offset = 2^(BITS-2)
-//                             it is tfhe_cbs_modswitch_kernel's, the exponents of an input written once.
+//   strided modulus switch    switch_rounded (pfhe_tfhe_exact_device.hpp) at stride 2^v, reduced modulo 2N: round(w 2N /
+//                             2^v / 2^BITS) with ties up, times 2^v.  v = 0 is what tfhe_modswitch_kernel writes; with
+//                             body_offset = 2^(BITS-2) it is what tfhe_cbs_modswitch_kernel writes, the exponents of an
+//                             input written once.
 //   patterned accumulator     ACC_e = X^{neg_b[e]} TV, TV the trivial GLWE whose body coefficient c is -g_{c mod 2^v}/2 for
-//                             c mod 2^v < levels and 0 otherwise, written from constants with the rotation sign of
-//                             tfhe_cbs_acc_init_kernel (v = 0, levels = 1: that kernel's words).
+//                             c mod 2^v < levels and 0 otherwise, written from constants with MonomialShift's sign as
+//                             tfhe_cbs_acc_init_kernel does (v = 0, levels = 1: that kernel's words).
 //   multi-index extraction    tfhe_sample_extract_kernel at every index h < count of every accumulator, row e count + h,
 //                             with g_h/2 added to the body when the circuit bootstrap asks for it.
 // Exact integer arithmetic modulo 2^BITS; one thread per word written, no LDS, no atomics, no scratch memory.
 #include <cstdint>
 
+#include "pfhe_tfhe_exact_device.hpp"
 #include "pfhe_tfhe_handles.hpp"
 
 using namespace pfhe;
 
 namespace pfhe {
 namespace {
-
-// sw_v of one word: every value is a multiple of 2^v below 2N, and a word that rounds up to 2N wraps to 0
-template <class W>
-__device__ __forceinline__ u32 switch_strided(W w, u32 log_n, u32 log_stride) {
-    const u32 drop = 8 * sizeof(W) - log_n - 2 + log_stride;  // at most BITS - 2: log_stride <= log_n
-    return ((u32)(((w >> drop) + 1) >> 1) << log_stride) & ((2u << log_n) - 1);
-}
 
 // one thread per word of the batch: word i of ciphertext e goes to exps[e n + i] (i < n) or, with body_offset added before
 // the switch and negated after it, to neg_b[e] (i = n)
@@ -39,9 +34,10 @@ __global__ __launch_bounds__(kThreads) void tfhe_modswitch_stride_kernel(const W
     const u64 e = t / (n + 1);
     const u32 i = (u32)(t - e * (n + 1));
     if (i < n)
-        exps[e * n + i] = switch_strided<W>(lwe[t], log_n, log_stride);
+        exps[e * n + i] = switch_rounded<W>(lwe[t], log_n, log_stride) & ((2u << log_n) - 1);
     else
-        neg_b[e] = ((2u << log_n) - switch_strided<W>((W)(lwe[t] + body_offset), log_n, log_stride)) & ((2u << log_n) - 1);
+        neg_b[e] = ((2u << log_n) - (switch_rounded<W>((W)(lwe[t] + body_offset), log_n, log_stride) & ((2u << log_n) - 1))) &
+                   ((2u << log_n) - 1);
 }
 
 // ACC_e = X^{neg_b[e]} TV, one thread per accumulator word: the mask polynomials are 0; body coefficient j holds
@@ -59,17 +55,15 @@ __global__ __launch_bounds__(kThreads) void tfhe_pattern_acc_init_kernel(W *__re
         acc[t] = 0;
         return;
     }
-    const u32 r = neg_b[e] & (2 * n - 1);
-    const bool high = r >= n;
-    const u32 rot = high ? r - n : r;
+    const MonomialShift x(neg_b[e], n);
     const u32 j = (u32)(t & (n - 1));
-    const u32 level = (j - rot) & ((1u << log_stride) - 1);
+    const u32 level = (j - x.rot) & ((1u << log_stride) - 1);
     const W v = level < levels ? (W)0 - ((W)1 << (half_shift + level * log_basis)) : (W)0;
-    acc[t] = ((j < rot) != high) ? (W)0 - v : v;
+    acc[t] = x.apply(j, v);
 }
 
-// one thread per output word: row a = e count + h is accumulator e extracted at index h, out[jN + i] = A_j[h - i] (i <= h)
-// or -A_j[N + h - i] (i > h), out[kN] = B[h], plus 2^(half_shift + h log_basis) when add_half is set
+// one thread per output word: row a = e count + h is accumulator e extracted at index h, out[jN + i] =
+// extract_word(A_j, h, N, i), out[kN] = B[h], plus 2^(half_shift + h log_basis) when add_half is set
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_multi_extract_kernel(const W *__restrict__ glwe, W *__restrict__ lwe, u32 k,
                                                                       u32 log_n, u32 count, u32 add_half, u32 log_basis,
@@ -88,8 +82,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_multi_extract_kernel(const W *_
         return;
     }
     const u32 i = (u32)(c & (n - 1));
-    const W *poly = ct + (c - i);
-    lwe[t] = i <= h ? poly[h - i] : (W)0 - poly[n + h - i];
+    lwe[t] = extract_word(ct + (c - i), h, n, i);
 }
 
 }  // namespace

@@ -265,31 +265,14 @@ int launch_multimsg_extract(const W *multi, W *lwe, u32 k, u32 log_n, u32 count,
                        count);
 }
 
-inline int glwe_body_add(const pfhe_fft *f, size_t k, u64 *glwe, size_t len, const u64 *key, size_t len_key, hipStream_t s) {
-    return pfhe_tfhe_glwe_body_mac_dev(f, k, (uint64_t *)glwe, len, (const uint64_t *)key, len_key, 0, s);
-}
-inline int glwe_body_add(const pfhe_fft *f, size_t k, u32 *glwe, size_t len, const u32 *key, size_t len_key, hipStream_t s) {
-    return pfhe_tfhe32_glwe_body_mac_dev(f, k, glwe, len, key, len_key, 0, s);
-}
-
 // ---------------- the entry points ----------------
 
-// ApproxSignedBasis::new's assert!s, the dimensions, the table, then count (which needs the table's N)
-template <class W>
-int pack_dimensions(const char *message, const pfhe_fft *f, size_t k, size_t in_dimension, uint32_t log_basis,
-                    size_t decompose_length, u32 &ell, u32 &drop) {
-    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
-    PFHE_TRY(require_glwe_dimension(k, message));
-    PFHE_TRY(require_lwe_dimension(in_dimension, message));
-    if (!f) return PFHE_ERR_BAD_ARGUMENT;
-    return PFHE_OK;
-}
-
+// tfhe_keyswitch_dimensions' refusals, then count (which needs the table's N)
 template <class W>
 int pack_check(const pfhe_fft *f, size_t k, size_t len_in, size_t in_dimension, size_t count, size_t len_pksk,
                uint32_t log_basis, size_t decompose_length, size_t len_out, PackShape &sh) {
     u32 ell = 0, drop = 0;
-    PFHE_TRY(pack_dimensions<W>("packing key switch: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2", f, k, in_dimension, log_basis, decompose_length, ell, drop));
+    PFHE_TRY(tfhe_keyswitch_dimensions<W>("packing key switch: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2", f, k, in_dimension, log_basis, decompose_length, ell, drop));
     if (count == 0 || count > f->n) {
         set_last_error("packing key switch: count must be in 1..N");
         return PFHE_ERR_BAD_ARGUMENT;
@@ -324,7 +307,7 @@ template <class W>
 int pksk_generate_dev(const pfhe_fft *f, size_t k, const W *key_in, size_t in_dimension, const W *glwe_key, size_t len_glwe_key,
                       uint32_t log_basis, size_t decompose_length, W *pksk, size_t len, hipStream_t s) {
     u32 ell = 0, drop = 0;
-    PFHE_TRY(pack_dimensions<W>("packing key: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2", f, k, in_dimension, log_basis, decompose_length, ell, drop));
+    PFHE_TRY(tfhe_keyswitch_dimensions<W>("packing key: glwe_dimension must be in 1..64 and in_dimension in 1..2^31-2", f, k, in_dimension, log_basis, decompose_length, ell, drop));
     if (len_glwe_key != k * f->n || len != in_dimension * ell * (k + 1) * f->n) {
         set_last_error("packing key: glwe_key must be k*N words and pksk in_dimension*ell*(k+1)*N");
         return PFHE_ERR_BAD_LENGTH;

@@ -179,6 +179,26 @@ int tfhe_bootstrap_check(const pfhe_fft *fft, size_t glwe_dimension, uint32_t lo
     return PFHE_OK;
 }
 
+// What the key switches into a GLWE and their keys decide first (packing and private key switch, pfhe_pack.hip and
+// pfhe_cbs.hip): ApproxSignedBasis::new's assert!s, the two dimensions refused with the caller's own message, then the table
+template <class W>
+int tfhe_keyswitch_dimensions(const char *message, const pfhe_fft *f, size_t k, size_t in_dimension, uint32_t log_basis,
+                              size_t decompose_length, u32 &ell, u32 &drop) {
+    PFHE_TRY(basis_shape(8 * sizeof(W), log_basis, decompose_length, ell, drop));
+    PFHE_TRY(require_glwe_dimension(k, message));
+    PFHE_TRY(require_lwe_dimension(in_dimension, message));
+    if (!f) return PFHE_ERR_BAD_ARGUMENT;
+    return PFHE_OK;
+}
+
+// B += sum_r A_r z_r on every GLWE row of a key under generation (pfhe_keygen.hip's body call, adding), for either word
+inline int glwe_body_add(const pfhe_fft *f, size_t k, u64 *glwe, size_t len, const u64 *key, size_t len_key, hipStream_t s) {
+    return pfhe_tfhe_glwe_body_mac_dev(f, k, (uint64_t *)glwe, len, (const uint64_t *)key, len_key, 0, s);
+}
+inline int glwe_body_add(const pfhe_fft *f, size_t k, u32 *glwe, size_t len, const u32 *key, size_t len_key, hipStream_t s) {
+    return pfhe_tfhe32_glwe_body_mac_dev(f, k, glwe, len, key, len_key, 0, s);
+}
+
 // keys of a bootstrapping key: lwe_dimension, or (lwe_dimension / g) 2^g multi-bit ones
 inline size_t tfhe_bootstrap_keys(std::optional<size_t> grouping_factor, size_t lwe_dimension) {
     return grouping_factor ? (lwe_dimension / *grouping_factor) << *grouping_factor : lwe_dimension;

@@ -366,12 +366,6 @@ int trace(Form form, TfheTraceCore<W> *h, const W *in, size_t len_in, const doub
 
 // ---------------- the stateless calls ----------------
 
-inline int glwe_body_add(const pfhe_fft *f, size_t k, u64 *glwe, size_t len, const u64 *key, size_t len_key, hipStream_t s) {
-    return pfhe_tfhe_glwe_body_mac_dev(f, k, (uint64_t *)glwe, len, (const uint64_t *)key, len_key, 0, s);
-}
-inline int glwe_body_add(const pfhe_fft *f, size_t k, u32 *glwe, size_t len, const u32 *key, size_t len_key, hipStream_t s) {
-    return pfhe_tfhe32_glwe_body_mac_dev(f, k, glwe, len, key, len_key, 0, s);
-}
 inline int forward_torus(const pfhe_fft *f, const u64 *in, size_t len, double *out, hipStream_t s) {
     return pfhe_fft_forward_torus_dev(f, (const uint64_t *)in, len, out, len, s);
 }

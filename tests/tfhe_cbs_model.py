@@ -20,6 +20,7 @@ import tfhe_blindrot_model as bm
 import tfhe_bootstrap_model as bs
 import tfhe_fft_model as m
 import tfhe_keygen_model as kg
+import tfhe_ks_shapes as ks
 
 
 # ---------------- rule 1: the private functional key switch ----------------
@@ -219,11 +220,10 @@ def noisy_case(bits, log_n, k, n, lb, ell, noise, pf_lb, pf_ell, cb_lb, cb_ell, 
 
 # ---------------- the shapes at which the key switch's tiling takes its other paths ----------------
 
-PF_MAX_ROWS = 64        # key rows of one group, the LDS bound
-PF_MAX_WORDS = 8        # input words of one group: 256 threads / 32 ciphertexts of a tile
-PF_UNROLL = 4           # key rows in flight
-PF_TILE_ROWS = 32       # input ciphertexts (batch x levels) of one workgroup
-PF_TILE_COLS = 128      # output columns of one workgroup, two per lane 64 apart
+# The tile is the LWE key switch's (tests/tfhe_ks_shapes.py), walked over in_dim + 1 words: the body is decomposed too.
+PF_UNROLL = ks.KS_UNROLL            # key rows in flight
+PF_TILE_ROWS = ks.KS_TILE_BATCH     # input ciphertexts (batch x levels) of one workgroup
+PF_TILE_COLS = ks.KS_TILE_COLS      # output columns of one workgroup, two per lane 64 apart
 
 # bits, in_dim, log_n, k, log_basis, ell, levels, batch                 what it reaches
 PFKS_EDGE_SHAPES = [
@@ -238,12 +238,9 @@ PFKS_EDGE_SHAPES = [
 ]
 
 
-def group_words(ell: int) -> int:
-    """ki: input words per group"""
-    return max(1, min(PF_MAX_ROWS // ell, PF_MAX_WORDS))
+group_words = ks.group_words           # ki: input words per group
 
 
 def group_rows(in_dim: int, ell: int):
     """key rows of every group, in the order the kernel walks them; the body is word in_dim"""
-    ki = group_words(ell)
-    return [min(ki, in_dim + 1 - i0) * ell for i0 in range(0, in_dim + 1, ki)]
+    return ks.group_rows(in_dim + 1, ell)

@@ -4,6 +4,9 @@ tests/test_gpu_tfhe_bootstrap_edges.py (which runs them).  Nothing here imports 
 
 The kernel walks the mask words in groups of ki (ki * ell <= 64, at most 8 mask words per group).  A group of
 g mask words has g * ell key rows; the kernel takes them four at a time and finishes the rest one by one.
+
+The private key switch (csrc/pfhe_cbs.hip, tfhe_pfks_kernel) runs the same tile over in_dim + 1 words, the body included:
+tests/tfhe_cbs_model.py takes the constants and both functions from here and keeps its own table of shapes.
 """
 
 KS_MAX_ROWS = 64        # key rows of one group, the LDS bound
