@@ -1666,6 +1666,75 @@ int pfhe_tfhe32_lwe_embed_dev(const pfhe_fft *fft, size_t glwe_dimension, const 
 int pfhe_tfhe32_lwe_embed(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe, size_t len_lwe, uint32_t *glwe_out,
                           size_t len_out);
 
+/* ---- a look-up table on encrypted bits: CMUX tree, rotation by encrypted bits, sample extraction (u64: no suffix, u32: 32) ----
+ * The reference has neither; the rules are this project's own, built on the arithmetic of
+ * pfhe_tfhe*_external_product_to_dev and on the CMUX above, which they leave bit for bit what they are.  A handle has a
+ * tree depth t (0..16), r rotation bits (0..log N), a stride 2^s (r + s <= log N) and o >= 1 outputs; p = t + r >= 1 bits
+ * per input, bit 0 the least significant.  A selector is a Fourier GGSW key in the layout the product takes,
+ * (k+1)*ell*(k+1)*N complex values.  Bits 0..r-1 drive the rotation, bits r..p-1 the tree.
+ *
+ * Rule 1, the rotation by encrypted bits.  inp, out: count = batch*o GLWE ciphertexts of (k+1)*N words, accumulator a
+ * belonging to input a / o; keys: batch*keys_per_input keys end to end, first_key + r <= keys_per_input.  Modulo 2^BITS:
+ *   acc_0 = inp[a],
+ *   acc_{j+1} = acc_j + external_product_to(X^{2N - 2^(j+s)} acc_j - acc_j, keys[(a / o)*keys_per_input + first_key + j]),
+ *   out[a] = acc_r      (= X^{-x 2^s} inp[a] for key bits x = sum_j m_j 2^j).
+ * Per step the words equal, one for one, those of pfhe_tfhe*_mul_monomial_each_to_dev with exponent 2N - 2^(j+s) and then
+ * pfhe_tfhe*_cmux_dev(d0 = acc, d1 = the rotated one, the step's keys, per_key = o).  out may be exactly inp; any other
+ * overlap is refused in the device form.  r = 0 is a copy.
+ *
+ * Rule 2, the table.  table: o*2^t GLWE ciphertexts shared by the batch, or batch*o*2^t of them (which one follows from
+ * len_table); leaf (output u, index i) of an input at u*2^t + i.  selectors: batch x p keys, the key of input e and bit j
+ * at e*p + j (the order in which pfhe_tfhe*_cbs_dev, then the forward transform, leaves them).  Stage A (t > 0): the tree
+ * of the CMUX section on the nodes (e, u, i) with bit r + j at level j: t calls of its rule 1 with per_key = o*2^(t-1-j) and
+ * a key stride of p keys.  Stage B: rule 1 with keys_per_input = p, first_key = 0 on the batch*o results (t = 0: on the
+ * table).  Stage C: with extract = 0, out is the batch*o GLWE ciphertexts; with extract = c in 1..N, batch*o*c LWE
+ * ciphertexts of k*N + 1 words, row (e*o + u)*c + i what pfhe_tfhe*_sample_extract_dev writes at index i.  So output (e, u)
+ * at index 0 is entry x = sum_j m_{e,j} 2^j of table u when that entry sits in leaf x >> r at body coefficient
+ * (x mod 2^r)*2^s.
+ *
+ * create, everything before the device first and in this order: a null out pointer; the product plan's checks in their order
+ * (ApproxSignedBasis::new's assert!s, PFHE_ERR_UNSUPPORTED for glwe_dimension above 64, PFHE_ERR_BAD_ARGUMENT for a null
+ * table); PFHE_ERR_BAD_ARGUMENT for tree_depth above 16, for rot_bits + log_stride above log N, for tree_depth + rot_bits = 0,
+ * for outputs = 0; PFHE_ERR_BAD_LENGTH for a chunk whose widest launch (chunk*o*2^(t-1) nodes) a grid does not hold.  The
+ * handle borrows `fft` and allocates everything here, for `chunk` inputs (0: inputs such that the buffers stay near
+ * 256 MiB, at least 1).  A call only queues work on `stream` (no allocation, no host synchronisation), so it can be
+ * captured into a HIP graph; a batch larger than the chunk runs chunk by chunk, all stages of a chunk first.  One holder at
+ * a time (PFHE_ERR_BUSY).  A call refuses, in the CMUX tree's order: a null handle, a second holder, (rule 2: extract above
+ * N,) null pointers (host form), PFHE_ERR_BAD_LENGTH for any length that does not fit the others, (the empty batch is a
+ * no-op,) null pointers, a pointer not aligned to 16 bytes, an overlap (device form), the device. */
+typedef struct pfhe_tfhe_lut_handle pfhe_tfhe_lut_handle;
+typedef struct pfhe_tfhe32_lut_handle pfhe_tfhe32_lut_handle;
+int pfhe_tfhe_lut_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         size_t tree_depth, size_t rot_bits, size_t log_stride, size_t outputs, size_t chunk,
+                         pfhe_tfhe_lut_handle **out);
+void pfhe_tfhe_lut_destroy(pfhe_tfhe_lut_handle *h);
+int pfhe_tfhe_lut_in_use(const pfhe_tfhe_lut_handle *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_tfhe_lut_scratch_bytes(const pfhe_tfhe_lut_handle *h);  /* the owned CMUX buffers and plan included */
+int pfhe_tfhe_rotate_by_bits_dev(pfhe_tfhe_lut_handle *h, const uint64_t *inp_dev, size_t len_inp, const double *keys_dev,
+                                 size_t len_keys, size_t keys_per_input, size_t first_key, uint64_t *out_dev, size_t len_out,
+                                 void *stream);
+int pfhe_tfhe_rotate_by_bits(pfhe_tfhe_lut_handle *h, const uint64_t *inp, size_t len_inp, const double *keys, size_t len_keys,
+                             size_t keys_per_input, size_t first_key, uint64_t *out, size_t len_out);
+int pfhe_tfhe_lut_eval_dev(pfhe_tfhe_lut_handle *h, const uint64_t *table_dev, size_t len_table, const double *selectors_dev,
+                           size_t len_selectors, size_t extract, uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe_lut_eval(pfhe_tfhe_lut_handle *h, const uint64_t *table, size_t len_table, const double *selectors,
+                       size_t len_selectors, size_t extract, uint64_t *out, size_t len_out);
+int pfhe_tfhe32_lut_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                           size_t tree_depth, size_t rot_bits, size_t log_stride, size_t outputs, size_t chunk,
+                           pfhe_tfhe32_lut_handle **out);
+void pfhe_tfhe32_lut_destroy(pfhe_tfhe32_lut_handle *h);
+int pfhe_tfhe32_lut_in_use(const pfhe_tfhe32_lut_handle *h);
+size_t pfhe_tfhe32_lut_scratch_bytes(const pfhe_tfhe32_lut_handle *h);
+int pfhe_tfhe32_rotate_by_bits_dev(pfhe_tfhe32_lut_handle *h, const uint32_t *inp_dev, size_t len_inp, const double *keys_dev,
+                                   size_t len_keys, size_t keys_per_input, size_t first_key, uint32_t *out_dev, size_t len_out,
+                                   void *stream);
+int pfhe_tfhe32_rotate_by_bits(pfhe_tfhe32_lut_handle *h, const uint32_t *inp, size_t len_inp, const double *keys,
+                               size_t len_keys, size_t keys_per_input, size_t first_key, uint32_t *out, size_t len_out);
+int pfhe_tfhe32_lut_eval_dev(pfhe_tfhe32_lut_handle *h, const uint32_t *table_dev, size_t len_table, const double *selectors_dev,
+                             size_t len_selectors, size_t extract, uint32_t *out_dev, size_t len_out, void *stream);
+int pfhe_tfhe32_lut_eval(pfhe_tfhe32_lut_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
+                         size_t len_selectors, size_t extract, uint32_t *out, size_t len_out);
+
 #ifdef __cplusplus
 }
 #endif

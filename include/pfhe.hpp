@@ -1439,4 +1439,78 @@ class TfheGlweTrace32 {
     pfhe_tfhe32_glwe_trace_handle *h_ = nullptr;
 };
 
+// A look-up table of 2^(tree_depth + rot_bits) entries on encrypted bits: a CMUX tree over the high bits, the rotation by
+// the low bits (acc += external_product_to(X^{2N - 2^(j+log_stride)} acc - acc, the input's key of bit j); out may be inp)
+// and sample extraction at the indices below `extract` (pfhe_tfhe{,32}_lut_*, _rotate_by_bits*, _lut_eval*).  Owns the
+// buffers of `chunk` inputs of `outputs` look-ups each; one holder at a time.  TfheLut32: the u32 torus.
+class TfheLut {
+  public:
+    TfheLut(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+            size_t tree_depth, size_t rot_bits, size_t outputs = 1, size_t log_stride = 0, size_t chunk = 0) {
+        check(pfhe_tfhe_lut_create(fft.handle(), glwe_dimension, log_basis, decompose_length, tree_depth, rot_bits, log_stride,
+                                    outputs, chunk, &h_));
+    }
+    ~TfheLut() { pfhe_tfhe_lut_destroy(h_); }
+    TfheLut(const TfheLut &) = delete;
+    TfheLut &operator=(const TfheLut &) = delete;
+    pfhe_tfhe_lut_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe_lut_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe_lut_scratch_bytes(h_); }
+    void rotate_by_bits(const uint64_t *inp, size_t len_inp, const double *keys, size_t len_keys, size_t keys_per_input,
+                        size_t first_key, uint64_t *out, size_t len_out) {
+        check(pfhe_tfhe_rotate_by_bits(h_, inp, len_inp, keys, len_keys, keys_per_input, first_key, out, len_out));
+    }
+    void rotate_by_bits_dev(const uint64_t *inp_dev, size_t len_inp, const double *keys_dev, size_t len_keys,
+                            size_t keys_per_input, size_t first_key, uint64_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe_rotate_by_bits_dev(h_, inp_dev, len_inp, keys_dev, len_keys, keys_per_input, first_key, out_dev, len_out,
+                                            stream));
+    }
+    void lut_eval(const uint64_t *table, size_t len_table, const double *selectors, size_t len_selectors, size_t extract,
+                  uint64_t *out, size_t len_out) {
+        check(pfhe_tfhe_lut_eval(h_, table, len_table, selectors, len_selectors, extract, out, len_out));
+    }
+    void lut_eval_dev(const uint64_t *table_dev, size_t len_table, const double *selectors_dev, size_t len_selectors,
+                      size_t extract, uint64_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe_lut_eval_dev(h_, table_dev, len_table, selectors_dev, len_selectors, extract, out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe_lut_handle *h_ = nullptr;
+};
+
+class TfheLut32 {
+  public:
+    TfheLut32(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+              size_t tree_depth, size_t rot_bits, size_t outputs = 1, size_t log_stride = 0, size_t chunk = 0) {
+        check(pfhe_tfhe32_lut_create(fft.handle(), glwe_dimension, log_basis, decompose_length, tree_depth, rot_bits, log_stride,
+                                      outputs, chunk, &h_));
+    }
+    ~TfheLut32() { pfhe_tfhe32_lut_destroy(h_); }
+    TfheLut32(const TfheLut32 &) = delete;
+    TfheLut32 &operator=(const TfheLut32 &) = delete;
+    pfhe_tfhe32_lut_handle *handle() const { return h_; }
+    bool in_use() const { return pfhe_tfhe32_lut_in_use(h_) != 0; }
+    size_t scratch_bytes() const { return pfhe_tfhe32_lut_scratch_bytes(h_); }
+    void rotate_by_bits(const uint32_t *inp, size_t len_inp, const double *keys, size_t len_keys, size_t keys_per_input,
+                        size_t first_key, uint32_t *out, size_t len_out) {
+        check(pfhe_tfhe32_rotate_by_bits(h_, inp, len_inp, keys, len_keys, keys_per_input, first_key, out, len_out));
+    }
+    void rotate_by_bits_dev(const uint32_t *inp_dev, size_t len_inp, const double *keys_dev, size_t len_keys,
+                            size_t keys_per_input, size_t first_key, uint32_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe32_rotate_by_bits_dev(h_, inp_dev, len_inp, keys_dev, len_keys, keys_per_input, first_key, out_dev, len_out,
+                                              stream));
+    }
+    void lut_eval(const uint32_t *table, size_t len_table, const double *selectors, size_t len_selectors, size_t extract,
+                  uint32_t *out, size_t len_out) {
+        check(pfhe_tfhe32_lut_eval(h_, table, len_table, selectors, len_selectors, extract, out, len_out));
+    }
+    void lut_eval_dev(const uint32_t *table_dev, size_t len_table, const double *selectors_dev, size_t len_selectors,
+                      size_t extract, uint32_t *out_dev, size_t len_out, void *stream = nullptr) {
+        check(pfhe_tfhe32_lut_eval_dev(h_, table_dev, len_table, selectors_dev, len_selectors, extract, out_dev, len_out, stream));
+    }
+
+  private:
+    pfhe_tfhe32_lut_handle *h_ = nullptr;
+};
+
 }  // namespace pfhe

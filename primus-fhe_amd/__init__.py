@@ -28,7 +28,8 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    tfhe_circuit_bootstrap_dev, TfheCmuxTreeContext, tfhe_cmux, tfhe_cmux_dev, tfhe_cmux_tree,
                    tfhe_cmux_tree_dev, TfheGlweTraceContext, glwe_automorphism, glwe_automorphism_dev, glwe_keyswitch,
                    glwe_keyswitch_dev, glwe_trace, glwe_trace_dev, tfhe_generate_gksk_dev, lwe_embed_glwe,
-                   lwe_embed_glwe_dev)
+                   lwe_embed_glwe_dev, TfheLutContext, tfhe_rotate_by_bits, tfhe_rotate_by_bits_dev, tfhe_lut_eval,
+                   tfhe_lut_eval_dev, tfhe_lut_table)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -52,4 +53,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "tfhe_circuit_bootstrap", "tfhe_circuit_bootstrap_dev", "TfheCmuxTreeContext", "tfhe_cmux", "tfhe_cmux_dev",
            "tfhe_cmux_tree", "tfhe_cmux_tree_dev", "TfheGlweTraceContext", "glwe_automorphism", "glwe_automorphism_dev",
            "glwe_keyswitch", "glwe_keyswitch_dev", "glwe_trace", "glwe_trace_dev", "tfhe_generate_gksk_dev", "lwe_embed_glwe",
-           "lwe_embed_glwe_dev", "build", "lib", "library_path", "status_string"]
+           "lwe_embed_glwe_dev", "TfheLutContext", "tfhe_rotate_by_bits", "tfhe_rotate_by_bits_dev", "tfhe_lut_eval",
+           "tfhe_lut_eval_dev", "tfhe_lut_table", "build", "lib", "library_path", "status_string"]

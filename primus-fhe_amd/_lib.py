@@ -264,6 +264,16 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "cmux", ci, vp, vp, sz, vp, sz, f64p, sz, sz, vp, sz)
         sig(ct + "_dev", ci, vp, vp, sz, f64p, sz, vp, sz, vp)
         sig(ct, ci, vp, vp, sz, f64p, sz, vp, sz)
+        # the look-up table on encrypted bits: the rotation by bits and the table evaluation, both calls of one handle
+        lu = tp + "lut"
+        sig(lu + "_create", ci, vp, sz, u32, sz, sz, sz, sz, sz, sz, C.POINTER(vp))
+        sig(lu + "_destroy", None, vp)
+        sig(lu + "_in_use", ci, vp)
+        sig(lu + "_scratch_bytes", sz, vp)
+        sig(tp + "rotate_by_bits_dev", ci, vp, vp, sz, f64p, sz, sz, sz, vp, sz, vp)
+        sig(tp + "rotate_by_bits", ci, vp, vp, sz, f64p, sz, sz, sz, vp, sz)
+        sig(lu + "_eval_dev", ci, vp, vp, sz, f64p, sz, sz, vp, sz, vp)
+        sig(lu + "_eval", ci, vp, vp, sz, f64p, sz, sz, vp, sz)
         # the GLWE automorphism / key switch and the trace, both calls of one handle; their keys; the LWE embedding
         gt = tp + "glwe_trace"
         sig(gt + "_create", ci, vp, sz, u32, sz, sz, C.POINTER(vp))

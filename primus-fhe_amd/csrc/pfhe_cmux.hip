@@ -14,7 +14,8 @@
 //            sequences per tree: the slow form.
 // Nothing is atomic and the summation order is the product's: the words depend neither on the batch, nor on the chunk,
 // nor on how per_key tiles the launches.  Launches and the two forms of both calls (handle_call) go through
-// pfhe_tfhe_host.hpp.
+// pfhe_tfhe_host.hpp.  The look-up handle (pfhe_lut.hip) owns a TfheCmuxTreeCore of its own and runs rule 1 on it through
+// tfhe_cmux_core_create / tfhe_cmux_launch at the end of this file.
 #include <algorithm>
 #include <cstdint>
 #include <memory>
@@ -95,22 +96,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_cmux_glue_kernel(const W *d0, c
 
 // ---------------- the handle ----------------
 
-// Owns, for `chunk` inputs of a tree of depth d: the two ping-pong node buffers (chunk * 2^(d-1) and chunk * 2^(d-2)
-// ciphertexts; the last level writes into the caller's output) and, in the general form, a product plan and the D and E
-// buffers of chunk * 2^(d-1) ciphertexts.  All allocated at creation.
-template <class W>
-struct TfheCmuxTreeCore {
-    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
-    PlanGuard guard;                // one holder at a time, successive calls on different streams ordered
-    Shape shape{};
-    u32 depth = 1;
-    bool fused = false;
-    size_t chunk = 1, glwe = 0, key_len = 0;
-    std::unique_ptr<TfhePlanCore<W>> plan;  // owned, general form only; its launches run under this handle's guard
-    W *node[2] = {nullptr, nullptr}, *d = nullptr, *e = nullptr;
-    DeviceBuffers bufs;  // after the plan: the four buffers are freed first, then the plan
-    size_t launch_nodes() const { return chunk << (depth - 1); }
-};
+// TfheCmuxTreeCore (pfhe_tfhe_handles.hpp) is what a handle owns; the look-up handle (pfhe_lut.hip) owns one too.
 struct pfhe_tfhe_cmux_tree_handle : TfheCmuxTreeCore<u64> {};
 struct pfhe_tfhe32_cmux_tree_handle : TfheCmuxTreeCore<u32> {};
 
@@ -125,18 +111,15 @@ constexpr size_t kCmuxDefaultBytes = 256ull << 20;
 constexpr size_t kMaxDepth = 16;
 
 // the product plan's checks in their order, then the depth, all before the device; then every allocation
-template <class W, class H>
-int cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t depth,
-                     size_t chunk, H **out) {
-    if (!out) return PFHE_ERR_BAD_ARGUMENT;
-    *out = nullptr;
+template <class W>
+int cmux_core_init(TfheCmuxTreeCore<W> *h, const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
+                   size_t decompose_length, size_t depth, size_t chunk) {
     Shape sh{};
     PFHE_TRY(tfhe_plan_check<W>(fft, glwe_dimension, log_basis, decompose_length, sh));
     if (depth == 0 || depth > kMaxDepth) {
         set_last_error("TFHE CMUX tree: depth must be in 1..16");
         return PFHE_ERR_BAD_ARGUMENT;
     }
-    auto h = std::make_unique<H>();
     h->shape = sh;
     h->depth = (u32)depth;
     h->fused = sh.k == 1 && sh.log_n <= kFusedMaxLogN;
@@ -164,7 +147,16 @@ int cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
         PFHE_TRY(tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, 0, &plan));
         h->plan.reset(plan);
     }
-    PFHE_TRY(h->guard.init(fft->device));
+    return h->guard.init(fft->device);
+}
+
+template <class W, class H>
+int cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t depth,
+                     size_t chunk, H **out) {
+    if (!out) return PFHE_ERR_BAD_ARGUMENT;
+    *out = nullptr;
+    auto h = std::make_unique<H>();
+    PFHE_TRY(cmux_core_init<W>(h.get(), fft, glwe_dimension, log_basis, decompose_length, depth, chunk));
     *out = h.release();
     return PFHE_OK;
 }
@@ -301,6 +293,31 @@ size_t cmux_scratch(const H *h) {
 }
 
 }  // namespace
+
+// ---------------- what the look-up handle (pfhe_lut.hip) runs of this file, declared in pfhe_tfhe_handles.hpp ----------------
+
+namespace pfhe {
+
+template <class W>
+int tfhe_cmux_core_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t depth,
+                          size_t chunk, TfheCmuxTreeCore<W> **out) {
+    return cmux_tree_create<W>(fft, glwe_dimension, log_basis, decompose_length, depth, chunk, out);
+}
+
+template <class W>
+int tfhe_cmux_launch(TfheCmuxTreeCore<W> *h, const W *d0, const W *d1, const double2 *keys, W *out, u64 count,
+                     const CmuxSources &at, hipStream_t s) {
+    return cmux_nodes<W>(h, d0, d1, keys, out, count, CmuxNodes{at.stride, 0, at.per_key, at.key_stride, at.period}, s);
+}
+
+template int tfhe_cmux_core_create<u32>(const pfhe_fft *, size_t, uint32_t, size_t, size_t, size_t, TfheCmuxTreeCore<u32> **);
+template int tfhe_cmux_core_create<u64>(const pfhe_fft *, size_t, uint32_t, size_t, size_t, size_t, TfheCmuxTreeCore<u64> **);
+template int tfhe_cmux_launch<u32>(TfheCmuxTreeCore<u32> *, const u32 *, const u32 *, const double2 *, u32 *, u64,
+                                   const CmuxSources &, hipStream_t);
+template int tfhe_cmux_launch<u64>(TfheCmuxTreeCore<u64> *, const u64 *, const u64 *, const double2 *, u64 *, u64,
+                                   const CmuxSources &, hipStream_t);
+
+}  // namespace pfhe
 
 extern "C" {
 

@@ -1,9 +1,9 @@
 // pfhe_tfhe_handles.hpp — what the torus-side handles own: the FFT table, the TFHE product plan, and the two blind
 // rotations behind the one interface the bootstrap handle holds (TfheRotation); and the argument checks their creates
 // share.  pfhe_fft.hip implements them; pfhe_bootstrap.hip and pfhe_cbs.hip see a rotation only as a TfheRotation;
-// pfhe_cmux.hip owns a product plan and queues the product's launches itself; pfhe_keygen.hip, which writes the keys they
-// consume, starts its GGSW calls with the plan's checks.  Host only; the host layer under the entry points of all of them
-// is pfhe_tfhe_host.hpp.
+// pfhe_cmux.hip owns a product plan and queues the product's launches itself, and pfhe_lut.hip runs the CMUX's launches on a
+// core it owns; pfhe_keygen.hip, which writes the keys they consume, starts its GGSW calls with the plan's checks.  Host
+// only; the host layer under the entry points of all of them is pfhe_tfhe_host.hpp.
 #pragma once
 
 #include <memory>
@@ -117,6 +117,24 @@ struct TfheBootstrapBase {
     W *acc = nullptr, *extracted = nullptr;
     pfhe::u32 *exps = nullptr, *neg_b = nullptr;
     pfhe::DeviceBuffers bufs;
+};
+
+// The CMUX tree handle (pfhe_cmux.hip), which the look-up handle (pfhe_lut.hip) owns one of as well.  Owns, for `chunk`
+// inputs of a tree of depth d: the two ping-pong node buffers (chunk * 2^(d-1) and chunk * 2^(d-2)
+// ciphertexts; the last level writes into the caller's output) and, in the general form, a product plan and the D and E
+// buffers of chunk * 2^(d-1) ciphertexts.  All allocated at creation.
+template <class W>
+struct TfheCmuxTreeCore {
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
+    pfhe::PlanGuard guard;          // one holder at a time, successive calls on different streams ordered
+    pfhe::Shape shape{};
+    pfhe::u32 depth = 1;
+    bool fused = false;
+    size_t chunk = 1, glwe = 0, key_len = 0;
+    std::unique_ptr<TfhePlanCore<W>> plan;  // owned, general form only; its launches run under this handle's guard
+    W *node[2] = {nullptr, nullptr}, *d = nullptr, *e = nullptr;
+    pfhe::DeviceBuffers bufs;  // after the plan: the four buffers are freed first, then the plan
+    size_t launch_nodes() const { return chunk << (depth - 1); }
 };
 
 namespace pfhe {
@@ -248,5 +266,22 @@ int launch_pattern_acc_init(W *acc, const u32 *neg_b, u32 k, u32 log_n, u32 log_
 template <class W>
 int launch_multi_extract(const W *glwe, W *lwe, u32 k, u32 log_n, u32 count, bool add_half, u32 log_basis, u32 half_shift,
                          u64 batch, hipStream_t s);
+
+// The CMUX of a handle that owns a TfheCmuxTreeCore without being one (pfhe_cmux.hip, instantiated for u32 and u64): what
+// pfhe_tfhe{,32}_cmux_tree_create runs, its checks and allocations for `chunk` inputs of a tree of `depth` levels, and rule 1
+//  on `count` nodes, arguments already checked and the device current: tfhe_cmux_kernel on the fused shape,
+// the general form's launches otherwise, at most launch_nodes() nodes per launch.  Node b reads d0 / d1 at
+// (period ? b mod period : b) * stride words, takes keys + (b / per_key) * key_stride and writes out at b * (k+1) N.  The
+// owner calls it inside its own ordered_on; the core's own guard stays unused.
+struct CmuxSources {
+    u64 stride, per_key, key_stride;
+    u32 period;
+};
+template <class W>
+int tfhe_cmux_core_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t depth,
+                          size_t chunk, TfheCmuxTreeCore<W> **out);
+template <class W>
+int tfhe_cmux_launch(TfheCmuxTreeCore<W> *h, const W *d0, const W *d1, const double2 *keys, W *out, u64 count,
+                     const CmuxSources &at, hipStream_t s);
 
 }  // namespace pfhe

@@ -1,12 +1,12 @@
 // pfhe_tfhe_host.hpp — the host layer under every torus entry point (pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip,
-// pfhe_pack.hip, pfhe_pack_fft.hip, pfhe_cbs.hip, pfhe_manylut.hip, pfhe_cmux.hip, pfhe_trace.hip): the constants and range tests they share, the launch of a
+// pfhe_pack.hip, pfhe_pack_fft.hip, pfhe_cbs.hip, pfhe_manylut.hip, pfhe_cmux.hip, pfhe_trace.hip, pfhe_lut.hip): the constants and range tests they share, the launch of a
 // torus kernel, and the two tails: stateless_call of the stateless steps, handle_call of the calls on a handle.  Host only.
 // What is not torus-specific lives in pfhe_staging.hpp, for the RNS side too: StageBuf and stage_in / _out / _inout,
 // staged_call (the staged run of a launch on host pointers), Form and form_call, refuse_null, overlaps,
 // require_exps_below_2n; the lease and the stream order of a handle live in pfhe_plan_guard.hpp, and the owner of the
 // device buffers a handle allocates at create in pfhe_device_buffers.hpp (the create-side recipe: DESIGN.md §16).
 //
-// A handle call (product, rotations, bootstrap, circuit bootstrap, CMUX and its tree, automorphism and trace) is ONE function template for both
+// A handle call (product, rotations, bootstrap, circuit bootstrap, CMUX and its tree, automorphism and trace, the look-up and its rotation by bits) is ONE function template for both
 // of its forms:
 //    1. it takes the Form (the extern "C" wrappers pass Form::kHost with a null stream, or Form::kDevice);
 //    2. it refuses a null handle and takes the handle's lease (PFHE_PLAN_LEASE), once;

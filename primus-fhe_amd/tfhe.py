@@ -918,6 +918,100 @@ def tfhe_cmux_tree_dev(table, selectors, out, ctx: TfheCmuxTreeContext, stream=N
     _cmux_tree(_dev_words, _dev_fourier, table, selectors, out, ctx, "_dev", (_stream(stream),))
 
 
+# ---- a look-up table on encrypted bits: tree, rotation by bits, extraction (include/pfhe.h: lut_*, rotate_by_bits, lut_eval) ----
+
+class TfheLutContext(_TorusContext):
+    """Handle of the look-up table on encrypted bits (include/pfhe.h, pfhe_tfhe{,32}_lut_*): a CMUX tree of
+    `tree_depth` t (0..16) levels over the high bits, a rotation by the `rot_bits` r (0..log N) low bits at stride
+    2^`log_stride` (r + s <= log N), and sample extraction, for `outputs` o >= 1 tables per input; p = t + r >= 1 bits per
+    input.  `basis` is the selectors' (the circuit bootstrap's cbs_basis when they come from there).  Owns the buffers of
+    `chunk` inputs (0 = the default); one holder at a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int, tree_depth: int,
+                 rot_bits: int, outputs: int = 1, log_stride: int = 0, chunk: int = 0):
+        self._open(fft, basis, glwe_dimension, "lut", (tree_depth, rot_bits, log_stride, outputs, chunk),
+                   ("_create", "_destroy", "_in_use", "_scratch_bytes"))
+        self.tree_depth, self.rot_bits, self.log_stride, self.outputs = tree_depth, rot_bits, log_stride, outputs
+
+    def bits(self) -> int:
+        """p = tree_depth + rot_bits, the selectors per input"""
+        return self.tree_depth + self.rot_bits
+
+
+def _rotate_by_bits(words, fourier, inp, keys, out, ctx, keys_per_input, first_key, name, tail):
+    pi, ni, wi = words(inp)
+    po, no, wo = words(out)
+    pk, nk = fourier(keys)
+    _same_width("inp and out must have the width of the context's basis", wi, wo, ctx._w)
+    kpi = ctx.rot_bits if keys_per_input is None else keys_per_input
+    check(getattr(lib(), "pfhe_tfhe" + ctx._w + name)(ctx._h, pi, ni, pk, nk, kpi, first_key, po, no, *tail))
+
+
+def tfhe_rotate_by_bits(inp: np.ndarray, keys: np.ndarray, out: np.ndarray, ctx: TfheLutContext,
+                        keys_per_input: int | None = None, first_key: int = 0) -> None:
+    """The rotation by encrypted bits on host arrays.  inp, out: count = batch * outputs GLWE ciphertexts, accumulator a of
+    input a // outputs; keys: batch * keys_per_input Fourier GGSW keys (default rot_bits per input), of which input e uses
+    keys[e * keys_per_input + first_key + j] for bit j < rot_bits:
+    acc += external_product_to(X^{2N - 2^(j + log_stride)} acc - acc, that key), so out[a] = X^{-x 2^log_stride} inp[a] for
+    key bits x = sum_j m_j 2^j.  Word for word, per step, mul_monomial_each_to_dev and tfhe_cmux_dev with per_key = outputs."""
+    _rotate_by_bits(_host_words, _host_fourier, inp, keys, out, ctx, keys_per_input, first_key, "_rotate_by_bits", ())
+
+
+def tfhe_rotate_by_bits_dev(inp, keys, out, ctx: TfheLutContext, keys_per_input: int | None = None, first_key: int = 0,
+                            stream=None) -> None:
+    """the device form, asynchronous; out may be exactly inp, any other overlap is refused"""
+    _rotate_by_bits(_dev_words, _dev_fourier, inp, keys, out, ctx, keys_per_input, first_key, "_rotate_by_bits_dev",
+                    (_stream(stream),))
+
+
+def _lut_eval(words, fourier, table, selectors, out, ctx, extract, name, tail):
+    pt, nt, wt = words(table)
+    po, no, wo = words(out)
+    ps, ns = fourier(selectors)
+    _same_width("table and out must have the width of the context's basis", wt, wo, ctx._w)
+    check(getattr(lib(), ctx._pre + name)(ctx._h, pt, nt, ps, ns, extract, po, no, *tail))
+
+
+def tfhe_lut_eval(table: np.ndarray, selectors: np.ndarray, out: np.ndarray, ctx: TfheLutContext, extract: int = 0) -> None:
+    """A look-up table of 2^p entries on p encrypted bits, on host arrays.  table: outputs * 2^tree_depth GLWE ciphertexts
+    shared by the batch, or batch times as many, leaf (output u, index i) at u * 2^tree_depth + i (tfhe_lut_table builds
+    them); selectors: batch x p Fourier GGSW keys, the key of input e and bit j at e*p + j (what tfhe_circuit_bootstrap_dev,
+    then write_fourier_form, gives); bits 0..rot_bits-1 rotate, the others walk the tree.  out: batch * outputs GLWE
+    ciphertexts (extract = 0), or batch * outputs * extract LWE ciphertexts of k*N + 1 words, row (e * outputs + u) * extract
+    + i what glwe_sample_extract writes at index i: index 0 of output (e, u) is entry sum_j m_{e,j} 2^j of table u."""
+    _lut_eval(_host_words, _host_fourier, table, selectors, out, ctx, extract, "_eval", ())
+
+
+def tfhe_lut_eval_dev(table, selectors, out, ctx: TfheLutContext, extract: int = 0, stream=None) -> None:
+    """the device form, asynchronous; out must not overlap an input and may be uninitialised"""
+    _lut_eval(_dev_words, _dev_fourier, table, selectors, out, ctx, extract, "_eval_dev", (_stream(stream),))
+
+
+def tfhe_lut_table(values, log_n: int, k: int, tree_depth: int, rot_bits: int, log_stride: int = 0):
+    """The trivial GLWE leaves of tfhe_lut_eval from clear entries.  values: a torch or numpy integer array of shape
+    (outputs, 2^p) or (outputs, 2^p, words), words <= 2^log_stride, the torus words of entry x of every output.  Returns an
+    array of the same kind and dtype of shape (outputs, 2^tree_depth, k+1, N): masks zero, word w of entry x at body
+    coefficient (x mod 2^rot_bits) * 2^log_stride + w of leaf x >> rot_bits, every other coefficient zero."""
+    n, p = 1 << log_n, tree_depth + rot_bits
+    if values.ndim == 2:
+        values = values[:, :, None]
+    if values.ndim != 3 or values.shape[1] != 1 << p or not 1 <= values.shape[2] <= 1 << log_stride \
+            or rot_bits + log_stride > log_n:
+        raise ValueError("expected values of shape (outputs, 2^(tree_depth + rot_bits)[, words <= 2^log_stride]) and "
+                         "rot_bits + log_stride <= log_n")
+    outputs, words = values.shape[0], values.shape[2]
+    shape = (outputs, 1 << tree_depth, k + 1, n)
+    if isinstance(values, np.ndarray):
+        leaves = np.zeros(shape, dtype=values.dtype)
+    else:
+        import torch
+        leaves = torch.zeros(shape, dtype=values.dtype, device=values.device)
+    body = leaves[:, :, k, :(1 << rot_bits) << log_stride].reshape(outputs, 1 << tree_depth, 1 << rot_bits, 1 << log_stride)
+    body[..., :words] = values.reshape(outputs, 1 << tree_depth, 1 << rot_bits, words)
+    leaves[:, :, k, :(1 << rot_bits) << log_stride] = body.reshape(outputs, 1 << tree_depth, -1)
+    return leaves
+
+
 # ---- GLWE key switch, automorphism and trace; their keys; the LWE embedding (include/pfhe.h: glwe_trace_*, glwe_automorphism,
 # gksk_generate_dev, lwe_embed) ----
 
