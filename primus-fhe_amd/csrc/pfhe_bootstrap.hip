@@ -389,181 +389,74 @@ int bootstrap(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk
 
 }  // namespace
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_BOOTSTRAP_FAMILY(P, CW, W)                                                                                 \
+    PFHE_ENTRY(P##_modswitch_dev, (int device, const CW *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n, \
+                uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream),              \
+               modswitch_dev<W>(device, (const W *)lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps,          \
+                                neg_b_dev, len_neg_b, (hipStream_t)stream))                                             \
+    PFHE_ENTRY(P##_sample_extract_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *glwe_dev,                 \
+                size_t len_glwe, size_t index, CW *lwe_dev, size_t len_lwe, void *stream),                              \
+               sample_extract<W>(Form::kDevice, fft, glwe_dimension, (const W *)glwe_dev, len_glwe, index,              \
+                                 (W *)lwe_dev, len_lwe, (hipStream_t)stream))                                           \
+    PFHE_ENTRY(P##_sample_extract, (const pfhe_fft *fft, size_t glwe_dimension, const CW *glwe, size_t len_glwe,        \
+                size_t index, CW *lwe, size_t len_lwe),                                                                 \
+               sample_extract<W>(Form::kHost, fft, glwe_dimension, (const W *)glwe, len_glwe, index, (W *)lwe, len_lwe, \
+                                 nullptr))                                                                              \
+    PFHE_ENTRY(P##_keyswitch_dev, (int device, const CW *lwe_in_dev, size_t len_in, size_t in_dimension,                \
+                const CW *ksk_dev, size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length,   \
+                CW *lwe_out_dev, size_t len_out, void *stream),                                                         \
+               keyswitch<W>(Form::kDevice, device, (const W *)lwe_in_dev, len_in, in_dimension, (const W *)ksk_dev,     \
+                            len_ksk, out_dimension, log_basis, decompose_length, (W *)lwe_out_dev, len_out,             \
+                            (hipStream_t)stream))                                                                       \
+    PFHE_ENTRY(P##_keyswitch, (int device, const CW *lwe_in, size_t len_in, size_t in_dimension, const CW *ksk,         \
+                size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, CW *lwe_out,         \
+                size_t len_out),                                                                                        \
+               keyswitch<W>(Form::kHost, device, (const W *)lwe_in, len_in, in_dimension, (const W *)ksk, len_ksk,      \
+                            out_dimension, log_basis, decompose_length, (W *)lwe_out, len_out, nullptr))                \
+    PFHE_ENTRY(P##_bootstrap_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                   \
+                size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length,       \
+                int with_keyswitch, size_t chunk, P##_bootstrap_handle **out),                                          \
+               bootstrap_create<W>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,       \
+                                   ks_decompose_length, with_keyswitch, std::nullopt, chunk, out))                      \
+    int P##_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                   \
+                                      size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,             \
+                                      size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor,           \
+                                      size_t chunk, P##_bootstrap_handle **out) {                                       \
+        PFHE_GUARD_BEGIN                                                                                                \
+        if (out) *out = nullptr;                                                                                        \
+        return bootstrap_create<W>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,       \
+                                   ks_decompose_length, with_keyswitch, grouping_factor, chunk, out);                   \
+        PFHE_GUARD_END                                                                                                  \
+    }                                                                                                                   \
+    int P##_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                   \
+                                      size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,             \
+                                      size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor,           \
+                                      uint32_t log_luts, size_t chunk, P##_bootstrap_handle **out) {                    \
+        PFHE_GUARD_BEGIN                                                                                                \
+        if (out) *out = nullptr;                                                                                        \
+        return bootstrap_create<W>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,       \
+                                   ks_decompose_length, with_keyswitch,                                                 \
+                                   grouping_factor > 1 ? std::optional<size_t>(grouping_factor) : std::nullopt, chunk,  \
+                                   out, true, log_luts);                                                                \
+        PFHE_GUARD_END                                                                                                  \
+    }                                                                                                                   \
+    PFHE_HANDLE_TRIO(P##_bootstrap, P##_bootstrap_handle, tfhe_bootstrap_scratch(h))                                    \
+    PFHE_ENTRY(P##_bootstrap_dev, (P##_bootstrap_handle *h, const CW *lwe_in_dev, size_t len_in, const double *bsk_dev, \
+                size_t len_bsk, const CW *tv_dev, size_t len_tv, const CW *ksk_dev, size_t len_ksk, CW *lwe_out_dev,    \
+                size_t len_out, void *stream),                                                                          \
+               bootstrap<W>(Form::kDevice, h, (const W *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const W *)tv_dev,       \
+                            len_tv, (const W *)ksk_dev, len_ksk, (W *)lwe_out_dev, len_out, (hipStream_t)stream))       \
+    PFHE_ENTRY(P##_bootstrap, (P##_bootstrap_handle *h, const CW *lwe_in, size_t len_in, const double *bsk,             \
+                size_t len_bsk, const CW *tv, size_t len_tv, const CW *ksk, size_t len_ksk, CW *lwe_out,                \
+                size_t len_out),                                                                                        \
+               bootstrap<W>(Form::kHost, h, (const W *)lwe_in, len_in, bsk, len_bsk, (const W *)tv, len_tv,             \
+                            (const W *)ksk, len_ksk, (W *)lwe_out, len_out, nullptr))
+
 extern "C" {
 
-int pfhe_tfhe_modswitch_dev(int device, const uint64_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
-                            uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream) {
-    PFHE_GUARD_BEGIN
-    return modswitch_dev<u64>(device, (const u64 *)lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev,
-                              len_neg_b, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_modswitch_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
-                              uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev, size_t len_neg_b, void *stream) {
-    PFHE_GUARD_BEGIN
-    return modswitch_dev<u32>(device, lwe_dev, len_lwe, lwe_dimension, log_n, exps_dev, len_exps, neg_b_dev, len_neg_b,
-                              (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
-                                 size_t index, uint64_t *lwe_dev, size_t len_lwe, void *stream) {
-    PFHE_GUARD_BEGIN
-    return sample_extract<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)glwe_dev, len_glwe, index, (u64 *)lwe_dev,
-                               len_lwe, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe, size_t index,
-                             uint64_t *lwe, size_t len_lwe) {
-    PFHE_GUARD_BEGIN
-    return sample_extract<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)glwe, len_glwe, index, (u64 *)lwe, len_lwe,
-                               nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_sample_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe_dev, size_t len_glwe,
-                                   size_t index, uint32_t *lwe_dev, size_t len_lwe, void *stream) {
-    PFHE_GUARD_BEGIN
-    return sample_extract<u32>(Form::kDevice, fft, glwe_dimension, glwe_dev, len_glwe, index, lwe_dev, len_lwe,
-                               (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_sample_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe, size_t index,
-                               uint32_t *lwe, size_t len_lwe) {
-    PFHE_GUARD_BEGIN
-    return sample_extract<u32>(Form::kHost, fft, glwe_dimension, glwe, len_glwe, index, lwe, len_lwe, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_keyswitch_dev(int device, const uint64_t *lwe_in_dev, size_t len_in, size_t in_dimension, const uint64_t *ksk_dev,
-                            size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length,
-                            uint64_t *lwe_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return keyswitch<u64>(Form::kDevice, device, (const u64 *)lwe_in_dev, len_in, in_dimension, (const u64 *)ksk_dev, len_ksk,
-                          out_dimension, log_basis, decompose_length, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_keyswitch(int device, const uint64_t *lwe_in, size_t len_in, size_t in_dimension, const uint64_t *ksk,
-                        size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *lwe_out,
-                        size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return keyswitch<u64>(Form::kHost, device, (const u64 *)lwe_in, len_in, in_dimension, (const u64 *)ksk, len_ksk,
-                          out_dimension, log_basis, decompose_length, (u64 *)lwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_keyswitch_dev(int device, const uint32_t *lwe_in_dev, size_t len_in, size_t in_dimension,
-                              const uint32_t *ksk_dev, size_t len_ksk, size_t out_dimension, uint32_t log_basis,
-                              size_t decompose_length, uint32_t *lwe_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return keyswitch<u32>(Form::kDevice, device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension, log_basis,
-                          decompose_length, lwe_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_keyswitch(int device, const uint32_t *lwe_in, size_t len_in, size_t in_dimension, const uint32_t *ksk,
-                          size_t len_ksk, size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *lwe_out,
-                          size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return keyswitch<u32>(Form::kHost, device, lwe_in, len_in, in_dimension, ksk, len_ksk, out_dimension, log_basis,
-                          decompose_length, lwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                               size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
-                               size_t chunk, pfhe_tfhe_bootstrap_handle **out) {
-    PFHE_GUARD_BEGIN
-    return bootstrap_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                 ks_decompose_length, with_keyswitch, std::nullopt, chunk, out);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                        size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length,
-                                        int with_keyswitch, size_t grouping_factor, size_t chunk,
-                                        pfhe_tfhe_bootstrap_handle **out) {
-    PFHE_GUARD_BEGIN
-    if (out) *out = nullptr;
-    return bootstrap_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                 ks_decompose_length, with_keyswitch, grouping_factor, chunk, out);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
-                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
-                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor,
-                                          uint32_t log_luts, size_t chunk, pfhe_tfhe_bootstrap_handle **out) {
-    PFHE_GUARD_BEGIN
-    if (out) *out = nullptr;
-    return bootstrap_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                 ks_decompose_length, with_keyswitch,
-                                 grouping_factor > 1 ? std::optional<size_t>(grouping_factor) : std::nullopt, chunk, out, true,
-                                 log_luts);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_bootstrap_destroy(pfhe_tfhe_bootstrap_handle *h) { delete h; }
-int pfhe_tfhe_bootstrap_in_use(const pfhe_tfhe_bootstrap_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_bootstrap_scratch_bytes(const pfhe_tfhe_bootstrap_handle *h) { return tfhe_bootstrap_scratch(h); }
-int pfhe_tfhe_bootstrap_dev(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
-                            size_t len_bsk, const uint64_t *tv_dev, size_t len_tv, const uint64_t *ksk_dev, size_t len_ksk,
-                            uint64_t *lwe_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return bootstrap<u64>(Form::kDevice, h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)tv_dev, len_tv,
-                          (const u64 *)ksk_dev, len_ksk, (u64 *)lwe_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_bootstrap(pfhe_tfhe_bootstrap_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
-                        const uint64_t *tv, size_t len_tv, const uint64_t *ksk, size_t len_ksk, uint64_t *lwe_out,
-                        size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return bootstrap<u64>(Form::kHost, h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)tv, len_tv,
-                          (const u64 *)ksk, len_ksk, (u64 *)lwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_bootstrap_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                 size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, int with_keyswitch,
-                                 size_t chunk, pfhe_tfhe32_bootstrap_handle **out) {
-    PFHE_GUARD_BEGIN
-    return bootstrap_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                 ks_decompose_length, with_keyswitch, std::nullopt, chunk, out);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_bootstrap_create_multibit(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
-                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
-                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor, size_t chunk,
-                                          pfhe_tfhe32_bootstrap_handle **out) {
-    PFHE_GUARD_BEGIN
-    if (out) *out = nullptr;
-    return bootstrap_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                 ks_decompose_length, with_keyswitch, grouping_factor, chunk, out);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_bootstrap_create_many_lut(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
-                                          size_t decompose_length, size_t lwe_dimension, uint32_t ks_log_basis,
-                                          size_t ks_decompose_length, int with_keyswitch, size_t grouping_factor,
-                                          uint32_t log_luts, size_t chunk, pfhe_tfhe32_bootstrap_handle **out) {
-    PFHE_GUARD_BEGIN
-    if (out) *out = nullptr;
-    return bootstrap_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
-                                 ks_decompose_length, with_keyswitch,
-                                 grouping_factor > 1 ? std::optional<size_t>(grouping_factor) : std::nullopt, chunk, out, true,
-                                 log_luts);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_bootstrap_destroy(pfhe_tfhe32_bootstrap_handle *h) { delete h; }
-int pfhe_tfhe32_bootstrap_in_use(const pfhe_tfhe32_bootstrap_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_bootstrap_scratch_bytes(const pfhe_tfhe32_bootstrap_handle *h) { return tfhe_bootstrap_scratch(h); }
-int pfhe_tfhe32_bootstrap_dev(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
-                              size_t len_bsk, const uint32_t *tv_dev, size_t len_tv, const uint32_t *ksk_dev, size_t len_ksk,
-                              uint32_t *lwe_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return bootstrap<u32>(Form::kDevice, h, lwe_in_dev, len_in, bsk_dev, len_bsk, tv_dev, len_tv, ksk_dev, len_ksk, lwe_out_dev,
-                          len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_bootstrap(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
-                          const uint32_t *tv, size_t len_tv, const uint32_t *ksk, size_t len_ksk, uint32_t *lwe_out,
-                          size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return bootstrap<u32>(Form::kHost, h, lwe_in, len_in, bsk, len_bsk, tv, len_tv, ksk, len_ksk, lwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
+PFHE_BOOTSTRAP_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_BOOTSTRAP_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_BOOTSTRAP_FAMILY
 
 }  // extern "C"

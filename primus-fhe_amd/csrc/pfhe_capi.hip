@@ -340,14 +340,8 @@ int pfhe_dcrt32_create(uint32_t log_n, const uint32_t *moduli, size_t moduli_cou
     PFHE_GUARD_END
 }
 
-// One entry point: guarded against exceptions, refuses a null table, then the call.
-#define PFHE_TABLE_ENTRY(NAME, PARAMS, ...)        \
-    int NAME PARAMS {                              \
-        PFHE_GUARD_BEGIN                           \
-        if (!table) return PFHE_ERR_BAD_ARGUMENT;  \
-        return __VA_ARGS__;                        \
-        PFHE_GUARD_END                             \
-    }
+// An entry point of a table: PFHE_ENTRY that refuses a null `table` before the call.
+#define PFHE_ENTRY_TABLE(NAME, PARAMS, ...) PFHE_ENTRY(NAME, PARAMS, table ? (__VA_ARGS__) : PFHE_ERR_BAD_ARGUMENT)
 
 // What the four handles share.  H: the handle type, whose name is also the symbol prefix; W / CW: the word type as the
 // host layer and as pfhe.h spell it.
@@ -355,28 +349,28 @@ int pfhe_dcrt32_create(uint32_t log_n, const uint32_t *moduli, size_t moduli_cou
     void H##_destroy(H *table) { delete table; }                                                                         \
     size_t H##_poly_length(const H *t) { return t ? t->t->n : 0; }                                                       \
     int H##_device(const H *t) { return t ? t->t->device : -1; }                                                         \
-    PFHE_TABLE_ENTRY(H##_transform_slice, (const H *table, CW *p, size_t len),                                           \
+    PFHE_ENTRY_TABLE(H##_transform_slice, (const H *table, CW *p, size_t len),                                           \
                      transform_host(*table->t, (W *)p, len, false, false))                                               \
-    PFHE_TABLE_ENTRY(H##_inverse_transform_slice, (const H *table, CW *p, size_t len),                                   \
+    PFHE_ENTRY_TABLE(H##_inverse_transform_slice, (const H *table, CW *p, size_t len),                                   \
                      transform_host(*table->t, (W *)p, len, true, false))                                                \
-    PFHE_TABLE_ENTRY(H##_lazy_transform_slice, (const H *table, CW *p, size_t len),                                      \
+    PFHE_ENTRY_TABLE(H##_lazy_transform_slice, (const H *table, CW *p, size_t len),                                      \
                      transform_host(*table->t, (W *)p, len, false, true))                                                \
-    PFHE_TABLE_ENTRY(H##_lazy_inverse_transform_slice, (const H *table, CW *p, size_t len),                              \
+    PFHE_ENTRY_TABLE(H##_lazy_inverse_transform_slice, (const H *table, CW *p, size_t len),                              \
                      transform_host(*table->t, (W *)p, len, true, true))                                                 \
-    PFHE_TABLE_ENTRY(H##_transform_monomial, (const H *table, CW coeff, size_t degree, CW *values, size_t len),          \
+    PFHE_ENTRY_TABLE(H##_transform_monomial, (const H *table, CW coeff, size_t degree, CW *values, size_t len),          \
                      monomial<W>(*table->t, coeff, degree, (W *)values, len, true, nullptr))                             \
-    PFHE_TABLE_ENTRY(H##_transform_coeff_one_monomial, (const H *table, size_t degree, CW *values, size_t len),          \
+    PFHE_ENTRY_TABLE(H##_transform_coeff_one_monomial, (const H *table, size_t degree, CW *values, size_t len),          \
                      monomial<W>(*table->t, 1, degree, (W *)values, len, true, nullptr))                                 \
-    PFHE_TABLE_ENTRY(H##_transform_coeff_minus_one_monomial, (const H *table, size_t degree, CW *values, size_t len),    \
+    PFHE_ENTRY_TABLE(H##_transform_coeff_minus_one_monomial, (const H *table, size_t degree, CW *values, size_t len),    \
                      monomial<W>(*table->t, 0, degree, (W *)values, len, true, nullptr, /*minus_one=*/true))             \
-    PFHE_TABLE_ENTRY(H##_transform_dev, (const H *table, CW *poly_dev, size_t len, int lazy, void *stream),              \
+    PFHE_ENTRY_TABLE(H##_transform_dev, (const H *table, CW *poly_dev, size_t len, int lazy, void *stream),              \
                      transform_dev(*table->t, (W *)poly_dev, len, false, lazy != 0, (hipStream_t)stream))                \
-    PFHE_TABLE_ENTRY(H##_inverse_transform_dev, (const H *table, CW *values_dev, size_t len, int lazy, void *stream),    \
+    PFHE_ENTRY_TABLE(H##_inverse_transform_dev, (const H *table, CW *values_dev, size_t len, int lazy, void *stream),    \
                      transform_dev(*table->t, (W *)values_dev, len, true, lazy != 0, (hipStream_t)stream))               \
-    PFHE_TABLE_ENTRY(H##_mul_assign_dev,                                                                                 \
+    PFHE_ENTRY_TABLE(H##_mul_assign_dev,                                                                                 \
                      (const H *table, CW *a_dev, size_t len_a, const CW *b_dev, size_t len_b, void *stream),             \
                      pointwise<W>(*table->t, 0, (W *)a_dev, nullptr, len_a, (const W *)b_dev, len_b, (hipStream_t)stream)) \
-    PFHE_TABLE_ENTRY(H##_add_mul_assign_dev,                                                                             \
+    PFHE_ENTRY_TABLE(H##_add_mul_assign_dev,                                                                             \
                      (const H *table, CW *acc_dev, const CW *a_dev, size_t len_a, const CW *b_dev, size_t len_b,         \
                       void *stream),                                                                                     \
                      pointwise<W>(*table->t, 1, (W *)acc_dev, (const W *)a_dev, len_a, (const W *)b_dev, len_b,          \
@@ -397,12 +391,12 @@ int pfhe_dcrt32_create(uint32_t log_n, const uint32_t *moduli, size_t moduli_cou
 
 // out = a*b (+ c): the u64 tables only
 #define PFHE_TABLE_MUL_TO(H)                                                                                              \
-    PFHE_TABLE_ENTRY(H##_mul_to_dev,                                                                                      \
+    PFHE_ENTRY_TABLE(H##_mul_to_dev,                                                                                      \
                      (const H *table, const uint64_t *a_dev, size_t len_a, const uint64_t *b_dev, size_t len_b,           \
                       uint64_t *out_dev, void *stream),                                                                   \
                      pointwise_to(*table->t, (u64 *)out_dev, (const u64 *)a_dev, len_a, (const u64 *)b_dev, len_b,        \
                                   nullptr, false, (hipStream_t)stream))                                                   \
-    PFHE_TABLE_ENTRY(H##_mul_add_to_dev,                                                                                  \
+    PFHE_ENTRY_TABLE(H##_mul_add_to_dev,                                                                                  \
                      (const H *table, const uint64_t *a_dev, size_t len_a, const uint64_t *b_dev, size_t len_b,           \
                       const uint64_t *c_dev, uint64_t *out_dev, void *stream),                                            \
                      pointwise_to(*table->t, (u64 *)out_dev, (const u64 *)a_dev, len_a, (const u64 *)b_dev, len_b,        \
@@ -427,10 +421,10 @@ uint64_t pfhe_dcrt_inv_n(const pfhe_dcrt *t, size_t i) { return (t && i < t->t->
 
 /* ---------------------------- entry points one table has ---------------------------- */
 
-PFHE_TABLE_ENTRY(pfhe_ntt_transform_monomial_dev,
+PFHE_ENTRY_TABLE(pfhe_ntt_transform_monomial_dev,
                  (const pfhe_ntt *table, uint64_t coeff, size_t degree, uint64_t *values_dev, size_t len, void *stream),
                  monomial<u64>(*table->t, coeff, degree, (u64 *)values_dev, len, false, (hipStream_t)stream))
-PFHE_TABLE_ENTRY(pfhe_ntt32_transform_monomial_dev,
+PFHE_ENTRY_TABLE(pfhe_ntt32_transform_monomial_dev,
                  (const pfhe_ntt32 *table, uint32_t coeff, size_t degree, uint32_t *values_dev, size_t len, void *stream),
                  monomial<u32>(*table->t, coeff, degree, values_dev, len, false, (hipStream_t)stream))
 
@@ -443,7 +437,7 @@ int pfhe_dcrt_transform_monomial_dev(const pfhe_dcrt *table, uint64_t coeff, siz
                          minus_one != 0);
     PFHE_GUARD_END
 }
-#undef PFHE_TABLE_ENTRY
+#undef PFHE_ENTRY_TABLE
 
 static int butterfly_api(const pfhe_dcrt *table, bool factor, uint64_t *a_dev, const uint64_t *rhs_dev, size_t len,
                          const uint64_t *w_dev, size_t len_w, uint64_t *result_dev, void *stream) {

@@ -1,5 +1,7 @@
 // pfhe_capi_rns.hip — extern "C" boundary for RNSBase, BigUintApproxSignedBasis and the RNS gadget
-// external product (include/pfhe.h, second half).
+// external product (include/pfhe.h, second half).  Every entry point of both widths comes out of one of three families,
+// each expanded for u64 and u32: PFHE_RNS_FAMILY, PFHE_EXTPROD_FAMILY, PFHE_BLINDROT_FAMILY; the profile entry and the
+// test hold of the u64 plan are written out.
 #include <cstdint>
 #include <cstdlib>
 #include <memory>
@@ -371,121 +373,114 @@ int basis_signed(Form form, const BasisHost *b, size_t level, const W *values, s
 
 }  // namespace
 
-// One entry point of the family: guarded against exceptions, then the call.  A step with two forms passes its template
-// Form::kDevice and the caller's stream, or Form::kHost and no stream.
-#define PFHE_RNS_ENTRY(NAME, PARAMS, ...) \
-    int NAME PARAMS {                     \
-        PFHE_GUARD_BEGIN                  \
-        return __VA_ARGS__;               \
-        PFHE_GUARD_END                    \
-    }
-
 // the entry points of one word width: NS = pfhe_rns / pfhe_rns32, BS = pfhe_basis / pfhe_basis32, W = the C word type
 #define H(p) ((p) ? &(p)->h : nullptr)
-#define PFHE_RNS_FAMILY(NS, BS, W)                                                                                         \
-    int NS##_create(const W *moduli, size_t count, int device, NS **out) {                                                 \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        if (!out) return PFHE_ERR_BAD_ARGUMENT;                                                                            \
-        *out = nullptr;                                                                                                    \
-        auto r = std::make_unique<NS>();                                                                                   \
-        PFHE_TRY(rns_create_impl<W>(moduli, count, device, r->h));                                                         \
-        *out = r.release();                                                                                                \
-        return PFHE_OK;                                                                                                    \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    void NS##_destroy(NS *r) { delete r; }                                                                                 \
-    size_t NS##_moduli_count(const NS *r) { return r ? r->h.par.dev.L : 0; }                                               \
-    size_t NS##_big_uint_value_len(const NS *r) { return r ? words_per_value<W>(r->h) : 0; }                               \
-    int NS##_moduli_product(const NS *r, W *out, size_t len) { return rns_moduli_product_impl<W>(H(r), out, len); }        \
-    PFHE_RNS_ENTRY(NS##_compose_multiple_values_to_dev, (const NS *r, const W *multi_residues_dev, size_t len_in,          \
-                    W *big_uint_values_dev, size_t len_out, size_t value_count, void *stream),                             \
-                   rns_compose<W>(Form::kDevice, H(r), multi_residues_dev, len_in, big_uint_values_dev, len_out,           \
-                                  value_count, stream))                                                                    \
-    PFHE_RNS_ENTRY(NS##_compose_multiple_values_to, (const NS *r, const W *multi_residues, size_t len_in,                  \
-                    W *big_uint_values, size_t len_out, size_t value_count),                                               \
-                   rns_compose<W>(Form::kHost, H(r), multi_residues, len_in, big_uint_values, len_out, value_count,        \
-                                  nullptr))                                                                                \
-    PFHE_RNS_ENTRY(NS##_wrapping_decompose_small_values_to_dev, (const NS *r, const W *small_values_dev,                   \
-                    size_t value_count, W *multi_residues_dev, size_t len_out, W small_value_modulus, void *stream),       \
-                   rns_wrapping<W>(Form::kDevice, H(r), small_values_dev, value_count, multi_residues_dev, len_out,        \
-                                   small_value_modulus, stream))                                                           \
-    PFHE_RNS_ENTRY(NS##_wrapping_decompose_small_values_to, (const NS *r, const W *small_values, size_t value_count,       \
-                    W *multi_residues, size_t len_out, W small_value_modulus),                                             \
-                   rns_wrapping<W>(Form::kHost, H(r), small_values, value_count, multi_residues, len_out,                  \
-                                   small_value_modulus, nullptr))                                                          \
-    PFHE_RNS_ENTRY(NS##_add_wrapping_decompose_small_values_scaled_dev, (const NS *r, const W *small_values_dev,           \
-                    size_t value_count, W *acc_dev, size_t len_acc, W small_value_modulus, const W *factors,               \
-                    void *stream),                                                                                         \
-                   rns_add_scaled<W>(Form::kDevice, H(r), small_values_dev, value_count, acc_dev, len_acc,                 \
-                                     small_value_modulus, true, factors, stream))                                          \
-    PFHE_RNS_ENTRY(NS##_add_decompose_small_values_scaled_dev, (const NS *r, const W *small_values_dev,                    \
-                    size_t value_count, W *acc_dev, size_t len_acc, const W *factors, void *stream),                       \
-                   rns_add_scaled<W>(Form::kDevice, H(r), small_values_dev, value_count, acc_dev, len_acc, 0, false,       \
-                                     factors, stream))                                                                     \
-    PFHE_RNS_ENTRY(NS##_add_wrapping_decompose_small_values_scaled, (const NS *r, const W *small_values,                   \
-                    size_t value_count, W *acc, size_t len_acc, W small_value_modulus, const W *factors),                  \
-                   rns_add_scaled<W>(Form::kHost, H(r), small_values, value_count, acc, len_acc, small_value_modulus,      \
-                                     true, factors, nullptr))                                                              \
-    PFHE_RNS_ENTRY(NS##_add_decompose_small_values_scaled, (const NS *r, const W *small_values, size_t value_count,        \
-                    W *acc, size_t len_acc, const W *factors),                                                             \
-                   rns_add_scaled<W>(Form::kHost, H(r), small_values, value_count, acc, len_acc, 0, false, factors,        \
-                                     nullptr))                                                                             \
-    PFHE_RNS_ENTRY(NS##_decompose_big_uint_values_to_dev, (const NS *r, const W *big_uint_values_dev, size_t len_in,       \
-                    W *multi_residues_dev, size_t len_out, size_t value_count, void *stream),                              \
-                   rns_decompose_big<W>(Form::kDevice, H(r), big_uint_values_dev, len_in, multi_residues_dev, len_out,     \
-                                        value_count, stream))                                                              \
-    PFHE_RNS_ENTRY(NS##_decompose_big_uint_values_to, (const NS *r, const W *big_uint_values, size_t len_in,               \
-                    W *multi_residues, size_t len_out, size_t value_count),                                                \
-                   rns_decompose_big<W>(Form::kHost, H(r), big_uint_values, len_in, multi_residues, len_out,               \
-                                        value_count, nullptr))                                                             \
-    int BS##_create(const NS *rns, uint32_t log_basis, size_t reverse_length, BS **out) {                                  \
-        PFHE_GUARD_BEGIN                                                                                                   \
-        if (!out || !rns) return PFHE_ERR_BAD_ARGUMENT;                                                                    \
-        *out = nullptr;                                                                                                    \
-        auto b = std::make_unique<BS>();                                                                                   \
-        PFHE_TRY(basis_create_impl(H(rns), log_basis, reverse_length, b->h));                                              \
-        *out = b.release();                                                                                                \
-        return PFHE_OK;                                                                                                    \
-        PFHE_GUARD_END                                                                                                     \
-    }                                                                                                                      \
-    void BS##_destroy(BS *b) { delete b; }                                                                                 \
-    size_t BS##_decompose_length(const BS *b) { return b ? b->h.par.dev.ell : 0; }                                         \
-    uint32_t BS##_log_basis(const BS *b) { return b ? b->h.par.dev.log_basis : 0; }                                        \
-    uint32_t BS##_drop_bits(const BS *b) { return b ? b->h.par.dev.drop_bits : 0; }                                        \
-    W BS##_basis_value(const BS *b) { return b ? (W)b->h.par.dev.basis : 0; }                                              \
-    int BS##_scalars(const BS *b, W *out, size_t len) { return basis_scalars_impl<W>(H(b), out, len); }                    \
-    int BS##_scalars_residue(const BS *b, W *out, size_t len) { return basis_scalars_residue_impl<W>(H(b), out, len); }    \
-    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_inplace_dev, (const BS *b, W *values_dev, size_t len,                       \
-                    uint8_t *carries_dev, size_t count, void *stream),                                                     \
-                   basis_init<W>(Form::kDevice, H(b), values_dev, len, carries_dev, count, stream))                        \
-    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_inplace, (const BS *b, W *values, size_t len, uint8_t *carries,             \
-                    size_t count),                                                                                         \
-                   basis_init<W>(Form::kHost, H(b), values, len, carries, count, nullptr))                                 \
-    PFHE_RNS_ENTRY(BS##_unsigned_decompose_slice_to_dev, (const BS *b, size_t level, const W *values_dev, size_t len,      \
-                    W *digits_dev, uint8_t *carries_dev, size_t count, void *stream),                                      \
-                   basis_unsigned<W>(Form::kDevice, H(b), level, values_dev, len, digits_dev, carries_dev, count,          \
-                                     stream))                                                                              \
-    PFHE_RNS_ENTRY(BS##_unsigned_decompose_slice_to, (const BS *b, size_t level, const W *values, size_t len, W *digits,   \
-                    uint8_t *carries, size_t count),                                                                       \
-                   basis_unsigned<W>(Form::kHost, H(b), level, values, len, digits, carries, count, nullptr))              \
-    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_to_dev, (const BS *b, const W *values_dev, size_t len, W *adjusted_dev,     \
-                    uint8_t *carries_dev, size_t count, void *stream),                                                     \
-                   basis_init_to<W>(Form::kDevice, H(b), values_dev, len, adjusted_dev, carries_dev, count, stream))       \
-    PFHE_RNS_ENTRY(BS##_init_value_carry_slice_to, (const BS *b, const W *values, size_t len, W *adjusted,                 \
-                    uint8_t *carries, size_t count),                                                                       \
-                   basis_init_to<W>(Form::kHost, H(b), values, len, adjusted, carries, count, nullptr))                    \
-    PFHE_RNS_ENTRY(BS##_decompose_slice_to_dev, (const BS *b, size_t level, const W *values_dev, size_t len,               \
-                    W *decomposed_dev, size_t len_out, uint8_t *carries_dev, size_t count, void *stream),                  \
-                   basis_signed<W>(Form::kDevice, H(b), level, values_dev, len, decomposed_dev, len_out, carries_dev,      \
-                                   count, stream))                                                                         \
-    PFHE_RNS_ENTRY(BS##_decompose_slice_to, (const BS *b, size_t level, const W *values, size_t len, W *decomposed,        \
-                    size_t len_out, uint8_t *carries, size_t count),                                                       \
-                   basis_signed<W>(Form::kHost, H(b), level, values, len, decomposed, len_out, carries, count, nullptr))
+#define PFHE_RNS_FAMILY(NS, BS, W)                                                                                      \
+    int NS##_create(const W *moduli, size_t count, int device, NS **out) {                                              \
+        PFHE_GUARD_BEGIN                                                                                                \
+        if (!out) return PFHE_ERR_BAD_ARGUMENT;                                                                         \
+        *out = nullptr;                                                                                                 \
+        auto r = std::make_unique<NS>();                                                                                \
+        PFHE_TRY(rns_create_impl<W>(moduli, count, device, r->h));                                                      \
+        *out = r.release();                                                                                             \
+        return PFHE_OK;                                                                                                 \
+        PFHE_GUARD_END                                                                                                  \
+    }                                                                                                                   \
+    void NS##_destroy(NS *r) { delete r; }                                                                              \
+    size_t NS##_moduli_count(const NS *r) { return r ? r->h.par.dev.L : 0; }                                            \
+    size_t NS##_big_uint_value_len(const NS *r) { return r ? words_per_value<W>(r->h) : 0; }                            \
+    int NS##_moduli_product(const NS *r, W *out, size_t len) { return rns_moduli_product_impl<W>(H(r), out, len); }     \
+    PFHE_ENTRY(NS##_compose_multiple_values_to_dev, (const NS *r, const W *multi_residues_dev, size_t len_in,           \
+                W *big_uint_values_dev, size_t len_out, size_t value_count, void *stream),                              \
+               rns_compose<W>(Form::kDevice, H(r), multi_residues_dev, len_in, big_uint_values_dev, len_out,            \
+                              value_count, stream))                                                                     \
+    PFHE_ENTRY(NS##_compose_multiple_values_to, (const NS *r, const W *multi_residues, size_t len_in,                   \
+                W *big_uint_values, size_t len_out, size_t value_count),                                                \
+               rns_compose<W>(Form::kHost, H(r), multi_residues, len_in, big_uint_values, len_out, value_count,         \
+                              nullptr))                                                                                 \
+    PFHE_ENTRY(NS##_wrapping_decompose_small_values_to_dev, (const NS *r, const W *small_values_dev,                    \
+                size_t value_count, W *multi_residues_dev, size_t len_out, W small_value_modulus, void *stream),        \
+               rns_wrapping<W>(Form::kDevice, H(r), small_values_dev, value_count, multi_residues_dev, len_out,         \
+                               small_value_modulus, stream))                                                            \
+    PFHE_ENTRY(NS##_wrapping_decompose_small_values_to, (const NS *r, const W *small_values, size_t value_count,        \
+                W *multi_residues, size_t len_out, W small_value_modulus),                                              \
+               rns_wrapping<W>(Form::kHost, H(r), small_values, value_count, multi_residues, len_out,                   \
+                               small_value_modulus, nullptr))                                                           \
+    PFHE_ENTRY(NS##_add_wrapping_decompose_small_values_scaled_dev, (const NS *r, const W *small_values_dev,            \
+                size_t value_count, W *acc_dev, size_t len_acc, W small_value_modulus, const W *factors,                \
+                void *stream),                                                                                          \
+               rns_add_scaled<W>(Form::kDevice, H(r), small_values_dev, value_count, acc_dev, len_acc,                  \
+                                 small_value_modulus, true, factors, stream))                                           \
+    PFHE_ENTRY(NS##_add_decompose_small_values_scaled_dev, (const NS *r, const W *small_values_dev,                     \
+                size_t value_count, W *acc_dev, size_t len_acc, const W *factors, void *stream),                        \
+               rns_add_scaled<W>(Form::kDevice, H(r), small_values_dev, value_count, acc_dev, len_acc, 0, false,        \
+                                 factors, stream))                                                                      \
+    PFHE_ENTRY(NS##_add_wrapping_decompose_small_values_scaled, (const NS *r, const W *small_values,                    \
+                size_t value_count, W *acc, size_t len_acc, W small_value_modulus, const W *factors),                   \
+               rns_add_scaled<W>(Form::kHost, H(r), small_values, value_count, acc, len_acc, small_value_modulus,       \
+                                 true, factors, nullptr))                                                               \
+    PFHE_ENTRY(NS##_add_decompose_small_values_scaled, (const NS *r, const W *small_values, size_t value_count,         \
+                W *acc, size_t len_acc, const W *factors),                                                              \
+               rns_add_scaled<W>(Form::kHost, H(r), small_values, value_count, acc, len_acc, 0, false, factors,         \
+                                 nullptr))                                                                              \
+    PFHE_ENTRY(NS##_decompose_big_uint_values_to_dev, (const NS *r, const W *big_uint_values_dev, size_t len_in,        \
+                W *multi_residues_dev, size_t len_out, size_t value_count, void *stream),                               \
+               rns_decompose_big<W>(Form::kDevice, H(r), big_uint_values_dev, len_in, multi_residues_dev, len_out,      \
+                                    value_count, stream))                                                               \
+    PFHE_ENTRY(NS##_decompose_big_uint_values_to, (const NS *r, const W *big_uint_values, size_t len_in,                \
+                W *multi_residues, size_t len_out, size_t value_count),                                                 \
+               rns_decompose_big<W>(Form::kHost, H(r), big_uint_values, len_in, multi_residues, len_out,                \
+                                    value_count, nullptr))                                                              \
+    int BS##_create(const NS *rns, uint32_t log_basis, size_t reverse_length, BS **out) {                               \
+        PFHE_GUARD_BEGIN                                                                                                \
+        if (!out || !rns) return PFHE_ERR_BAD_ARGUMENT;                                                                 \
+        *out = nullptr;                                                                                                 \
+        auto b = std::make_unique<BS>();                                                                                \
+        PFHE_TRY(basis_create_impl(H(rns), log_basis, reverse_length, b->h));                                           \
+        *out = b.release();                                                                                             \
+        return PFHE_OK;                                                                                                 \
+        PFHE_GUARD_END                                                                                                  \
+    }                                                                                                                   \
+    void BS##_destroy(BS *b) { delete b; }                                                                              \
+    size_t BS##_decompose_length(const BS *b) { return b ? b->h.par.dev.ell : 0; }                                      \
+    uint32_t BS##_log_basis(const BS *b) { return b ? b->h.par.dev.log_basis : 0; }                                     \
+    uint32_t BS##_drop_bits(const BS *b) { return b ? b->h.par.dev.drop_bits : 0; }                                     \
+    W BS##_basis_value(const BS *b) { return b ? (W)b->h.par.dev.basis : 0; }                                           \
+    int BS##_scalars(const BS *b, W *out, size_t len) { return basis_scalars_impl<W>(H(b), out, len); }                 \
+    int BS##_scalars_residue(const BS *b, W *out, size_t len) { return basis_scalars_residue_impl<W>(H(b), out, len); } \
+    PFHE_ENTRY(BS##_init_value_carry_slice_inplace_dev, (const BS *b, W *values_dev, size_t len,                        \
+                uint8_t *carries_dev, size_t count, void *stream),                                                      \
+               basis_init<W>(Form::kDevice, H(b), values_dev, len, carries_dev, count, stream))                         \
+    PFHE_ENTRY(BS##_init_value_carry_slice_inplace, (const BS *b, W *values, size_t len, uint8_t *carries,              \
+                size_t count),                                                                                          \
+               basis_init<W>(Form::kHost, H(b), values, len, carries, count, nullptr))                                  \
+    PFHE_ENTRY(BS##_unsigned_decompose_slice_to_dev, (const BS *b, size_t level, const W *values_dev, size_t len,       \
+                W *digits_dev, uint8_t *carries_dev, size_t count, void *stream),                                       \
+               basis_unsigned<W>(Form::kDevice, H(b), level, values_dev, len, digits_dev, carries_dev, count,           \
+                                 stream))                                                                               \
+    PFHE_ENTRY(BS##_unsigned_decompose_slice_to, (const BS *b, size_t level, const W *values, size_t len, W *digits,    \
+                uint8_t *carries, size_t count),                                                                        \
+               basis_unsigned<W>(Form::kHost, H(b), level, values, len, digits, carries, count, nullptr))               \
+    PFHE_ENTRY(BS##_init_value_carry_slice_to_dev, (const BS *b, const W *values_dev, size_t len, W *adjusted_dev,      \
+                uint8_t *carries_dev, size_t count, void *stream),                                                      \
+               basis_init_to<W>(Form::kDevice, H(b), values_dev, len, adjusted_dev, carries_dev, count, stream))        \
+    PFHE_ENTRY(BS##_init_value_carry_slice_to, (const BS *b, const W *values, size_t len, W *adjusted,                  \
+                uint8_t *carries, size_t count),                                                                        \
+               basis_init_to<W>(Form::kHost, H(b), values, len, adjusted, carries, count, nullptr))                     \
+    PFHE_ENTRY(BS##_decompose_slice_to_dev, (const BS *b, size_t level, const W *values_dev, size_t len,                \
+                W *decomposed_dev, size_t len_out, uint8_t *carries_dev, size_t count, void *stream),                   \
+               basis_signed<W>(Form::kDevice, H(b), level, values_dev, len, decomposed_dev, len_out, carries_dev,       \
+                               count, stream))                                                                          \
+    PFHE_ENTRY(BS##_decompose_slice_to, (const BS *b, size_t level, const W *values, size_t len, W *decomposed,         \
+                size_t len_out, uint8_t *carries, size_t count),                                                        \
+               basis_signed<W>(Form::kHost, H(b), level, values, len, decomposed, len_out, carries, count, nullptr))
 
 extern "C" {
 
 PFHE_RNS_FAMILY(pfhe_rns, pfhe_basis, uint64_t)
 PFHE_RNS_FAMILY(pfhe_rns32, pfhe_basis32, uint32_t)
+#undef PFHE_RNS_FAMILY
+#undef H
 
 }  // extern "C"
 
@@ -705,16 +700,50 @@ int glev_common(Plan *plan, W *out_dev, size_t len_out, const W *dcrt_glev_dev, 
 
 }  // namespace
 
+// The external product's entry points of one word width.  P: pfhe_extprod / pfhe_extprod32; TB, NS, BS: the width's table,
+// RNS-base and basis handles; CW / W: the word as pfhe.h and as the library spell it.
+// Kept on purpose: what the length message of a glev call names its output.  u64 says "acc" in the accumulating CRT call
+// and "result" in the overwriting one, u32 "acc/result" in both; the two big-integer calls say "acc/result" at either width.
+#define PFHE_EXTPROD_FAMILY(P, TB, NS, BS, CW, W)                                                                      \
+    PFHE_ENTRY(P##_plan_create, (const TB *table, const NS *rns, const BS *basis, size_t glwe_dimension, size_t chunk, \
+                P##_plan **out),                                                                                       \
+               plan_create(table, rns, basis, glwe_dimension, chunk, out))                                             \
+    PFHE_HANDLE_TRIO(P##_plan, P##_plan, plan_scratch_bytes(h))                                                        \
+    PFHE_ENTRY(P##_mul_dcrt_ggsw_to_dev, (P##_plan *plan, const CW *crt_glwe_dev, size_t len_glwe,                     \
+                const CW *dcrt_ggsw_dev, size_t len_ggsw, CW *result_dev, size_t len_result, int into_coeff_form,      \
+                void *stream),                                                                                         \
+               mul_dcrt_ggsw_to_dev(plan, (const W *)crt_glwe_dev, len_glwe, (const W *)dcrt_ggsw_dev, len_ggsw,       \
+                                    (W *)result_dev, len_result, into_coeff_form, (hipStream_t)stream))                \
+    PFHE_ENTRY(P##_mul_dcrt_ggsw_to, (P##_plan *plan, const CW *crt_glwe, size_t len_glwe, const CW *dcrt_ggsw,        \
+                size_t len_ggsw, CW *result, size_t len_result, int into_coeff_form),                                  \
+               mul_dcrt_ggsw_to(plan, (const W *)crt_glwe, len_glwe, (const W *)dcrt_ggsw, len_ggsw, (W *)result,      \
+                                len_result, into_coeff_form))                                                          \
+    PFHE_ENTRY(P##_add_dcrt_glev_mul_crt_poly_assign_dev, (P##_plan *plan, CW *acc_dev, size_t len_acc,                \
+                const CW *dcrt_glev_dev, size_t len_glev, const CW *crt_poly_dev, size_t len_poly, void *stream),      \
+               glev_common(plan, (W *)acc_dev, len_acc, (const W *)dcrt_glev_dev, len_glev, (const W *)crt_poly_dev,   \
+                           len_poly, true, false, sizeof(W) == 8 ? "acc" : "acc/result", stream))                      \
+    PFHE_ENTRY(P##_glev_mul_crt_poly_to_dev, (P##_plan *plan, const CW *dcrt_glev_dev, size_t len_glev,                \
+                const CW *crt_poly_dev, size_t len_poly, CW *result_dev, size_t len_result, void *stream),             \
+               glev_common(plan, (W *)result_dev, len_result, (const W *)dcrt_glev_dev, len_glev,                      \
+                           (const W *)crt_poly_dev, len_poly, false, false, sizeof(W) == 8 ? "result" : "acc/result",  \
+                           stream))                                                                                    \
+    PFHE_ENTRY(P##_add_dcrt_glev_mul_big_uint_poly_assign_dev, (P##_plan *plan, CW *acc_dev, size_t len_acc,           \
+                const CW *dcrt_glev_dev, size_t len_glev, const CW *big_uint_poly_dev, size_t len_poly, void *stream), \
+               glev_common(plan, (W *)acc_dev, len_acc, (const W *)dcrt_glev_dev, len_glev,                            \
+                           (const W *)big_uint_poly_dev, len_poly, true, true, "acc/result", stream))                  \
+    PFHE_ENTRY(P##_glev_mul_big_uint_poly_to_dev, (P##_plan *plan, const CW *dcrt_glev_dev, size_t len_glev,           \
+                const CW *big_uint_poly_dev, size_t len_poly, CW *result_dev, size_t len_result, void *stream),        \
+               glev_common(plan, (W *)result_dev, len_result, (const W *)dcrt_glev_dev, len_glev,                      \
+                           (const W *)big_uint_poly_dev, len_poly, false, true, "acc/result", stream))
+
 extern "C" {
 
-int pfhe_extprod_plan_create(const pfhe_dcrt *table, const pfhe_rns *rns, const pfhe_basis *basis,
-                             size_t glwe_dimension, size_t chunk, pfhe_extprod_plan **out) {
-    PFHE_GUARD_BEGIN
-    return plan_create(table, rns, basis, glwe_dimension, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_extprod_plan_destroy(pfhe_extprod_plan *p) { delete p; }
-int pfhe_extprod_plan_in_use(const pfhe_extprod_plan *p) { return p ? p->guard.in_use() : 0; }
+PFHE_EXTPROD_FAMILY(pfhe_extprod, pfhe_dcrt, pfhe_rns, pfhe_basis, uint64_t, u64)
+PFHE_EXTPROD_FAMILY(pfhe_extprod32, pfhe_dcrt32, pfhe_rns32, pfhe_basis32, uint32_t, u32)
+#undef PFHE_EXTPROD_FAMILY
+
+/* ------------------------------ what only the u64 plan has ------------------------------ */
+
 // test aid: hold != 0 takes the plan for the calling thread as an entry point would (PFHE_ERR_BUSY if another thread has
 // it) and keeps it until the same thread calls with hold == 0
 int pfhe_extprod_plan_debug_hold(pfhe_extprod_plan *p, int hold) {
@@ -724,17 +753,6 @@ int pfhe_extprod_plan_debug_hold(pfhe_extprod_plan *p, int hold) {
     p->guard.release();
     return PFHE_OK;
 }
-size_t pfhe_extprod_plan_scratch_bytes(const pfhe_extprod_plan *p) { return plan_scratch_bytes(p); }
-
-int pfhe_extprod_mul_dcrt_ggsw_to_dev(pfhe_extprod_plan *plan, const uint64_t *crt_glwe_dev, size_t len_glwe,
-                                      const uint64_t *dcrt_ggsw_dev, size_t len_ggsw, uint64_t *result_dev,
-                                      size_t len_result, int into_coeff_form, void *stream) {
-    PFHE_GUARD_BEGIN
-    return mul_dcrt_ggsw_to_dev(plan, (const u64 *)crt_glwe_dev, len_glwe, (const u64 *)dcrt_ggsw_dev, len_ggsw,
-                                (u64 *)result_dev, len_result, into_coeff_form, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
 int pfhe_extprod_profile_dev(pfhe_extprod_plan *plan, const uint64_t *crt_glwe_dev, size_t len_glwe,
                              const uint64_t *dcrt_ggsw_dev, size_t len_ggsw, uint64_t *result_dev, size_t len_result,
                              double *ms_out, size_t *launches_out, void *stream) {
@@ -762,118 +780,6 @@ int pfhe_extprod_profile_dev(pfhe_extprod_plan *plan, const uint64_t *crt_glwe_d
     for (hipEvent_t x : ev) (void)hipEventDestroy(x);
     if (e != hipSuccess) return hip_fail(e, "external-product profile", __FILE__, __LINE__);
     return rc;
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod_add_dcrt_glev_mul_crt_poly_assign_dev(pfhe_extprod_plan *plan, uint64_t *acc_dev, size_t len_acc,
-                                                       const uint64_t *dcrt_glev_dev, size_t len_glev,
-                                                       const uint64_t *crt_poly_dev, size_t len_poly, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, (u64 *)acc_dev, len_acc, (const u64 *)dcrt_glev_dev, len_glev, (const u64 *)crt_poly_dev,
-                       len_poly, true, false, "acc", stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod_glev_mul_crt_poly_to_dev(pfhe_extprod_plan *plan, const uint64_t *dcrt_glev_dev, size_t len_glev,
-                                          const uint64_t *crt_poly_dev, size_t len_poly, uint64_t *result_dev,
-                                          size_t len_result, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, (u64 *)result_dev, len_result, (const u64 *)dcrt_glev_dev, len_glev,
-                       (const u64 *)crt_poly_dev, len_poly, false, false, "result", stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod_add_dcrt_glev_mul_big_uint_poly_assign_dev(pfhe_extprod_plan *plan, uint64_t *acc_dev, size_t len_acc,
-                                                            const uint64_t *dcrt_glev_dev, size_t len_glev,
-                                                            const uint64_t *big_uint_poly_dev, size_t len_poly,
-                                                            void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, (u64 *)acc_dev, len_acc, (const u64 *)dcrt_glev_dev, len_glev,
-                       (const u64 *)big_uint_poly_dev, len_poly, true, true, "acc/result", stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod_glev_mul_big_uint_poly_to_dev(pfhe_extprod_plan *plan, const uint64_t *dcrt_glev_dev, size_t len_glev,
-                                               const uint64_t *big_uint_poly_dev, size_t len_poly, uint64_t *result_dev,
-                                               size_t len_result, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, (u64 *)result_dev, len_result, (const u64 *)dcrt_glev_dev, len_glev,
-                       (const u64 *)big_uint_poly_dev, len_poly, false, true, "acc/result", stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod_mul_dcrt_ggsw_to(pfhe_extprod_plan *plan, const uint64_t *crt_glwe, size_t len_glwe,
-                                  const uint64_t *dcrt_ggsw, size_t len_ggsw, uint64_t *result, size_t len_result,
-                                  int into_coeff_form) {
-    PFHE_GUARD_BEGIN
-    return mul_dcrt_ggsw_to(plan, (const u64 *)crt_glwe, len_glwe, (const u64 *)dcrt_ggsw, len_ggsw, (u64 *)result,
-                            len_result, into_coeff_form);
-    PFHE_GUARD_END
-}
-
-/* ------------------------------ external product over U32DcrtTable ------------------------------ */
-
-int pfhe_extprod32_plan_create(const pfhe_dcrt32 *table, const pfhe_rns32 *rns, const pfhe_basis32 *basis,
-                               size_t glwe_dimension, size_t chunk, pfhe_extprod32_plan **out) {
-    PFHE_GUARD_BEGIN
-    return plan_create(table, rns, basis, glwe_dimension, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_extprod32_plan_destroy(pfhe_extprod32_plan *p) { delete p; }
-int pfhe_extprod32_plan_in_use(const pfhe_extprod32_plan *p) { return p ? p->guard.in_use() : 0; }
-size_t pfhe_extprod32_plan_scratch_bytes(const pfhe_extprod32_plan *p) { return plan_scratch_bytes(p); }
-
-int pfhe_extprod32_mul_dcrt_ggsw_to_dev(pfhe_extprod32_plan *plan, const uint32_t *crt_glwe_dev, size_t len_glwe,
-                                        const uint32_t *dcrt_ggsw_dev, size_t len_ggsw, uint32_t *result_dev,
-                                        size_t len_result, int into_coeff_form, void *stream) {
-    PFHE_GUARD_BEGIN
-    return mul_dcrt_ggsw_to_dev(plan, crt_glwe_dev, len_glwe, dcrt_ggsw_dev, len_ggsw, result_dev, len_result,
-                                into_coeff_form, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod32_mul_dcrt_ggsw_to(pfhe_extprod32_plan *plan, const uint32_t *crt_glwe, size_t len_glwe,
-                                    const uint32_t *dcrt_ggsw, size_t len_ggsw, uint32_t *result, size_t len_result,
-                                    int into_coeff_form) {
-    PFHE_GUARD_BEGIN
-    return mul_dcrt_ggsw_to(plan, crt_glwe, len_glwe, dcrt_ggsw, len_ggsw, result, len_result, into_coeff_form);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod32_add_dcrt_glev_mul_crt_poly_assign_dev(pfhe_extprod32_plan *plan, uint32_t *acc_dev, size_t len_acc,
-                                                         const uint32_t *dcrt_glev_dev, size_t len_glev,
-                                                         const uint32_t *crt_poly_dev, size_t len_poly, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, acc_dev, len_acc, dcrt_glev_dev, len_glev, crt_poly_dev, len_poly, true, false, "acc/result",
-                       stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod32_glev_mul_crt_poly_to_dev(pfhe_extprod32_plan *plan, const uint32_t *dcrt_glev_dev, size_t len_glev,
-                                            const uint32_t *crt_poly_dev, size_t len_poly, uint32_t *result_dev,
-                                            size_t len_result, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, result_dev, len_result, dcrt_glev_dev, len_glev, crt_poly_dev, len_poly, false, false,
-                       "acc/result", stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod32_add_dcrt_glev_mul_big_uint_poly_assign_dev(pfhe_extprod32_plan *plan, uint32_t *acc_dev, size_t len_acc,
-                                                              const uint32_t *dcrt_glev_dev, size_t len_glev,
-                                                              const uint32_t *big_uint_poly_dev, size_t len_poly,
-                                                              void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, acc_dev, len_acc, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, true, true,
-                       "acc/result", stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_extprod32_glev_mul_big_uint_poly_to_dev(pfhe_extprod32_plan *plan, const uint32_t *dcrt_glev_dev, size_t len_glev,
-                                                 const uint32_t *big_uint_poly_dev, size_t len_poly, uint32_t *result_dev,
-                                                 size_t len_result, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glev_common(plan, result_dev, len_result, dcrt_glev_dev, len_glev, big_uint_poly_dev, len_poly, false, true,
-                       "acc/result", stream);
     PFHE_GUARD_END
 }
 
@@ -1031,52 +937,25 @@ int blindrot_rotate_host(H *h, W *acc, size_t len_acc, const W *bsk, size_t len_
 
 }  // namespace
 
+// The rotation's entry points of one word width.  P: pfhe_blindrot / pfhe_blindrot32, also the handle type; the rest as
+// PFHE_EXTPROD_FAMILY.
+#define PFHE_BLINDROT_FAMILY(P, TB, NS, BS, CW, W)                                                                  \
+    PFHE_ENTRY(P##_create, (const TB *table, const NS *base, const BS *basis, size_t glwe_dimension, size_t chunk,  \
+                P **out),                                                                                           \
+               blindrot_create(table, base, basis, glwe_dimension, chunk, out))                                     \
+    PFHE_HANDLE_TRIO(P, P, blindrot_scratch_bytes(h))                                                               \
+    PFHE_ENTRY(P##_rotate_dev, (P *h, CW *acc_dev, size_t len_acc, const CW *bsk_dev, size_t len_bsk,               \
+                const uint32_t *exps_dev, size_t len_exps, void *stream),                                           \
+               blindrot_rotate_dev<P, W>(h, (W *)acc_dev, len_acc, (const W *)bsk_dev, len_bsk, exps_dev, len_exps, \
+                                         (hipStream_t)stream))                                                      \
+    PFHE_ENTRY(P##_rotate, (P *h, CW *acc, size_t len_acc, const CW *bsk, size_t len_bsk, const uint32_t *exps,     \
+                size_t len_exps),                                                                                   \
+               blindrot_rotate_host(h, (W *)acc, len_acc, (const W *)bsk, len_bsk, exps, len_exps))
+
 extern "C" {
 
-int pfhe_blindrot_create(const pfhe_dcrt *table, const pfhe_rns *base, const pfhe_basis *basis, size_t glwe_dimension,
-                         size_t chunk, pfhe_blindrot **out) {
-    PFHE_GUARD_BEGIN
-    return blindrot_create(table, base, basis, glwe_dimension, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_blindrot_destroy(pfhe_blindrot *h) { delete h; }
-int pfhe_blindrot_in_use(const pfhe_blindrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_blindrot_scratch_bytes(const pfhe_blindrot *h) { return blindrot_scratch_bytes(h); }
-int pfhe_blindrot_rotate_dev(pfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const uint64_t *bsk_dev, size_t len_bsk,
-                             const uint32_t *exps_dev, size_t len_exps, void *stream) {
-    PFHE_GUARD_BEGIN
-    return blindrot_rotate_dev<pfhe_blindrot, u64>(h, (u64 *)acc_dev, len_acc, (const u64 *)bsk_dev, len_bsk, exps_dev,
-                                                   len_exps, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_blindrot_rotate(pfhe_blindrot *h, uint64_t *acc, size_t len_acc, const uint64_t *bsk, size_t len_bsk,
-                         const uint32_t *exps, size_t len_exps) {
-    PFHE_GUARD_BEGIN
-    return blindrot_rotate_host(h, (u64 *)acc, len_acc, (const u64 *)bsk, len_bsk, exps, len_exps);
-    PFHE_GUARD_END
-}
-
-int pfhe_blindrot32_create(const pfhe_dcrt32 *table, const pfhe_rns32 *base, const pfhe_basis32 *basis,
-                           size_t glwe_dimension, size_t chunk, pfhe_blindrot32 **out) {
-    PFHE_GUARD_BEGIN
-    return blindrot_create(table, base, basis, glwe_dimension, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_blindrot32_destroy(pfhe_blindrot32 *h) { delete h; }
-int pfhe_blindrot32_in_use(const pfhe_blindrot32 *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_blindrot32_scratch_bytes(const pfhe_blindrot32 *h) { return blindrot_scratch_bytes(h); }
-int pfhe_blindrot32_rotate_dev(pfhe_blindrot32 *h, uint32_t *acc_dev, size_t len_acc, const uint32_t *bsk_dev,
-                               size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
-    PFHE_GUARD_BEGIN
-    return blindrot_rotate_dev<pfhe_blindrot32, u32>(h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps,
-                                                     (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_blindrot32_rotate(pfhe_blindrot32 *h, uint32_t *acc, size_t len_acc, const uint32_t *bsk, size_t len_bsk,
-                           const uint32_t *exps, size_t len_exps) {
-    PFHE_GUARD_BEGIN
-    return blindrot_rotate_host(h, acc, len_acc, bsk, len_bsk, exps, len_exps);
-    PFHE_GUARD_END
-}
+PFHE_BLINDROT_FAMILY(pfhe_blindrot, pfhe_dcrt, pfhe_rns, pfhe_basis, uint64_t, u64)
+PFHE_BLINDROT_FAMILY(pfhe_blindrot32, pfhe_dcrt32, pfhe_rns32, pfhe_basis32, uint32_t, u32)
+#undef PFHE_BLINDROT_FAMILY
 
 }  // extern "C"

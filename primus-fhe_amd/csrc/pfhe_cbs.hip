@@ -393,129 +393,52 @@ int cbs(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk, size
 
 }  // namespace
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_CBS_FAMILY(P, CW, W)                                                                                       \
+    PFHE_ENTRY(P##_private_keyswitch_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *lwe_in_dev,            \
+                size_t len_in, size_t in_dimension, size_t levels, const CW *pfksk_dev, size_t len_pfksk,               \
+                uint32_t log_basis, size_t decompose_length, CW *out_dev, size_t len_out, void *stream),                \
+               private_keyswitch<W>(Form::kDevice, fft, glwe_dimension, (const W *)lwe_in_dev, len_in, in_dimension,    \
+                                    levels, (const W *)pfksk_dev, len_pfksk, log_basis, decompose_length, (W *)out_dev, \
+                                    len_out, (hipStream_t)stream))                                                      \
+    PFHE_ENTRY(P##_private_keyswitch, (const pfhe_fft *fft, size_t glwe_dimension, const CW *lwe_in, size_t len_in,     \
+                size_t in_dimension, size_t levels, const CW *pfksk, size_t len_pfksk, uint32_t log_basis,              \
+                size_t decompose_length, CW *out, size_t len_out),                                                      \
+               private_keyswitch<W>(Form::kHost, fft, glwe_dimension, (const W *)lwe_in, len_in, in_dimension, levels,  \
+                                    (const W *)pfksk, len_pfksk, log_basis, decompose_length, (W *)out, len_out,        \
+                                    nullptr))                                                                           \
+    PFHE_ENTRY(P##_pfksk_generate_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *key_in_dev,               \
+                size_t in_dimension, const CW *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,                   \
+                size_t decompose_length, CW *pfksk_dev, size_t len_pfksk, void *stream),                                \
+               pfksk_generate_dev<W>(fft, glwe_dimension, (const W *)key_in_dev, in_dimension,                          \
+                                     (const W *)glwe_key_dev, len_glwe_key, log_basis, decompose_length,                \
+                                     (W *)pfksk_dev, len_pfksk, (hipStream_t)stream))                                   \
+    PFHE_ENTRY(P##_cbs_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                         \
+                size_t decompose_length, size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,     \
+                uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t chunk, P##_cbs_handle **out),             \
+               cbs_create<W>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis,            \
+                             cbs_decompose_length, pfks_log_basis, pfks_decompose_length, chunk, out))                  \
+    PFHE_ENTRY(P##_cbs_create_with, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                    \
+                size_t decompose_length, size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,     \
+                uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t grouping_factor, int shared_rotation,     \
+                size_t chunk, P##_cbs_handle **out),                                                                    \
+               cbs_create<W>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis,            \
+                             cbs_decompose_length, pfks_log_basis, pfks_decompose_length, chunk, out, grouping_factor,  \
+                             shared_rotation != 0))                                                                     \
+    PFHE_HANDLE_TRIO(P##_cbs, P##_cbs_handle, tfhe_bootstrap_scratch(h))                                                \
+    PFHE_ENTRY(P##_cbs_dev, (P##_cbs_handle *h, const CW *lwe_in_dev, size_t len_in, const double *bsk_dev,             \
+                size_t len_bsk, const CW *pfksk_dev, size_t len_pfksk, CW *ggsw_out_dev, size_t len_out, void *stream), \
+               cbs<W>(Form::kDevice, h, (const W *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const W *)pfksk_dev,          \
+                      len_pfksk, (W *)ggsw_out_dev, len_out, (hipStream_t)stream))                                      \
+    PFHE_ENTRY(P##_cbs, (P##_cbs_handle *h, const CW *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,         \
+                const CW *pfksk, size_t len_pfksk, CW *ggsw_out, size_t len_out),                                       \
+               cbs<W>(Form::kHost, h, (const W *)lwe_in, len_in, bsk, len_bsk, (const W *)pfksk, len_pfksk,             \
+                      (W *)ggsw_out, len_out, nullptr))
+
 extern "C" {
 
-int pfhe_tfhe_private_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in_dev, size_t len_in,
-                                    size_t in_dimension, size_t levels, const uint64_t *pfksk_dev, size_t len_pfksk,
-                                    uint32_t log_basis, size_t decompose_length, uint64_t *out_dev, size_t len_out,
-                                    void *stream) {
-    PFHE_GUARD_BEGIN
-    return private_keyswitch<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)lwe_in_dev, len_in, in_dimension, levels,
-                                  (const u64 *)pfksk_dev, len_pfksk, log_basis, decompose_length, (u64 *)out_dev, len_out,
-                                  (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_private_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
-                                size_t in_dimension, size_t levels, const uint64_t *pfksk, size_t len_pfksk, uint32_t log_basis,
-                                size_t decompose_length, uint64_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return private_keyswitch<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)lwe_in, len_in, in_dimension, levels,
-                                  (const u64 *)pfksk, len_pfksk, log_basis, decompose_length, (u64 *)out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_private_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in_dev, size_t len_in,
-                                      size_t in_dimension, size_t levels, const uint32_t *pfksk_dev, size_t len_pfksk,
-                                      uint32_t log_basis, size_t decompose_length, uint32_t *out_dev, size_t len_out,
-                                      void *stream) {
-    PFHE_GUARD_BEGIN
-    return private_keyswitch<u32>(Form::kDevice, fft, glwe_dimension, lwe_in_dev, len_in, in_dimension, levels, pfksk_dev,
-                                  len_pfksk, log_basis, decompose_length, out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_private_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
-                                  size_t in_dimension, size_t levels, const uint32_t *pfksk, size_t len_pfksk,
-                                  uint32_t log_basis, size_t decompose_length, uint32_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return private_keyswitch<u32>(Form::kHost, fft, glwe_dimension, lwe_in, len_in, in_dimension, levels, pfksk, len_pfksk,
-                                  log_basis, decompose_length, out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_pfksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *key_in_dev, size_t in_dimension,
-                                 const uint64_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis, size_t decompose_length,
-                                 uint64_t *pfksk_dev, size_t len_pfksk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return pfksk_generate_dev<u64>(fft, glwe_dimension, (const u64 *)key_in_dev, in_dimension, (const u64 *)glwe_key_dev,
-                                   len_glwe_key, log_basis, decompose_length, (u64 *)pfksk_dev, len_pfksk, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_pfksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *key_in_dev, size_t in_dimension,
-                                   const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
-                                   size_t decompose_length, uint32_t *pfksk_dev, size_t len_pfksk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return pfksk_generate_dev<u32>(fft, glwe_dimension, key_in_dev, in_dimension, glwe_key_dev, len_glwe_key, log_basis,
-                                   decompose_length, pfksk_dev, len_pfksk, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                         size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
-                         size_t pfks_decompose_length, size_t chunk, pfhe_tfhe_cbs_handle **out) {
-    PFHE_GUARD_BEGIN
-    return cbs_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
-                           pfks_log_basis, pfks_decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                              size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,
-                              uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t grouping_factor, int shared_rotation,
-                              size_t chunk, pfhe_tfhe_cbs_handle **out) {
-    PFHE_GUARD_BEGIN
-    return cbs_create<u64>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
-                           pfks_log_basis, pfks_decompose_length, chunk, out, grouping_factor, shared_rotation != 0);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_cbs_destroy(pfhe_tfhe_cbs_handle *h) { delete h; }
-int pfhe_tfhe_cbs_in_use(const pfhe_tfhe_cbs_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_cbs_scratch_bytes(const pfhe_tfhe_cbs_handle *h) { return tfhe_bootstrap_scratch(h); }
-int pfhe_tfhe_cbs_dev(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk,
-                      const uint64_t *pfksk_dev, size_t len_pfksk, uint64_t *ggsw_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return cbs<u64>(Form::kDevice, h, (const u64 *)lwe_in_dev, len_in, bsk_dev, len_bsk, (const u64 *)pfksk_dev, len_pfksk,
-                    (u64 *)ggsw_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_cbs(pfhe_tfhe_cbs_handle *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
-                  const uint64_t *pfksk, size_t len_pfksk, uint64_t *ggsw_out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return cbs<u64>(Form::kHost, h, (const u64 *)lwe_in, len_in, bsk, len_bsk, (const u64 *)pfksk, len_pfksk, (u64 *)ggsw_out,
-                    len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_cbs_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                           size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length, uint32_t pfks_log_basis,
-                           size_t pfks_decompose_length, size_t chunk, pfhe_tfhe32_cbs_handle **out) {
-    PFHE_GUARD_BEGIN
-    return cbs_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
-                           pfks_log_basis, pfks_decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_cbs_create_with(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                size_t lwe_dimension, uint32_t cbs_log_basis, size_t cbs_decompose_length,
-                                uint32_t pfks_log_basis, size_t pfks_decompose_length, size_t grouping_factor,
-                                int shared_rotation, size_t chunk, pfhe_tfhe32_cbs_handle **out) {
-    PFHE_GUARD_BEGIN
-    return cbs_create<u32>(fft, glwe_dimension, log_basis, decompose_length, lwe_dimension, cbs_log_basis, cbs_decompose_length,
-                           pfks_log_basis, pfks_decompose_length, chunk, out, grouping_factor, shared_rotation != 0);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_cbs_destroy(pfhe_tfhe32_cbs_handle *h) { delete h; }
-int pfhe_tfhe32_cbs_in_use(const pfhe_tfhe32_cbs_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_cbs_scratch_bytes(const pfhe_tfhe32_cbs_handle *h) { return tfhe_bootstrap_scratch(h); }
-int pfhe_tfhe32_cbs_dev(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
-                        size_t len_bsk, const uint32_t *pfksk_dev, size_t len_pfksk, uint32_t *ggsw_out_dev, size_t len_out,
-                        void *stream) {
-    PFHE_GUARD_BEGIN
-    return cbs<u32>(Form::kDevice, h, lwe_in_dev, len_in, bsk_dev, len_bsk, pfksk_dev, len_pfksk, ggsw_out_dev, len_out,
-                    (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_cbs(pfhe_tfhe32_cbs_handle *h, const uint32_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
-                    const uint32_t *pfksk, size_t len_pfksk, uint32_t *ggsw_out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return cbs<u32>(Form::kHost, h, lwe_in, len_in, bsk, len_bsk, pfksk, len_pfksk, ggsw_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
+PFHE_CBS_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_CBS_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_CBS_FAMILY
 
 }  // extern "C"

@@ -319,80 +319,34 @@ template int tfhe_cmux_launch<u64>(TfheCmuxTreeCore<u64> *, const u64 *, const u
 
 }  // namespace pfhe
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_CMUX_FAMILY(P, CW, W)                                                                                    \
+    PFHE_ENTRY(P##_cmux_tree_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                 \
+                size_t decompose_length, size_t depth, size_t chunk, P##_cmux_tree_handle **out),                     \
+               cmux_tree_create<W>(fft, glwe_dimension, log_basis, decompose_length, depth, chunk, out))              \
+    PFHE_HANDLE_TRIO(P##_cmux_tree, P##_cmux_tree_handle, cmux_scratch(h))                                            \
+    PFHE_ENTRY(P##_cmux_dev, (P##_cmux_tree_handle *h, const CW *d0_dev, size_t len_d0, const CW *d1_dev,             \
+                size_t len_d1, const double *keys_dev, size_t len_keys, size_t per_key, CW *out_dev, size_t len_out,  \
+                void *stream),                                                                                        \
+               cmux<W>(Form::kDevice, h, (const W *)d0_dev, len_d0, (const W *)d1_dev, len_d1, keys_dev, len_keys,    \
+                       per_key, (W *)out_dev, len_out, (hipStream_t)stream))                                          \
+    PFHE_ENTRY(P##_cmux, (P##_cmux_tree_handle *h, const CW *d0, size_t len_d0, const CW *d1, size_t len_d1,          \
+                const double *keys, size_t len_keys, size_t per_key, CW *out, size_t len_out),                        \
+               cmux<W>(Form::kHost, h, (const W *)d0, len_d0, (const W *)d1, len_d1, keys, len_keys, per_key,         \
+                       (W *)out, len_out, nullptr))                                                                   \
+    PFHE_ENTRY(P##_cmux_tree_dev, (P##_cmux_tree_handle *h, const CW *table_dev, size_t len_table,                    \
+                const double *selectors_dev, size_t len_selectors, CW *out_dev, size_t len_out, void *stream),        \
+               cmux_tree<W>(Form::kDevice, h, (const W *)table_dev, len_table, selectors_dev, len_selectors,          \
+                            (W *)out_dev, len_out, (hipStream_t)stream))                                              \
+    PFHE_ENTRY(P##_cmux_tree, (P##_cmux_tree_handle *h, const CW *table, size_t len_table, const double *selectors,   \
+                size_t len_selectors, CW *out, size_t len_out),                                                       \
+               cmux_tree<W>(Form::kHost, h, (const W *)table, len_table, selectors, len_selectors, (W *)out, len_out, \
+                            nullptr))
+
 extern "C" {
 
-int pfhe_tfhe_cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                               size_t depth, size_t chunk, pfhe_tfhe_cmux_tree_handle **out) {
-    PFHE_GUARD_BEGIN
-    return cmux_tree_create<u64>(fft, glwe_dimension, log_basis, decompose_length, depth, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_cmux_tree_destroy(pfhe_tfhe_cmux_tree_handle *h) { delete h; }
-int pfhe_tfhe_cmux_tree_in_use(const pfhe_tfhe_cmux_tree_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_cmux_tree_scratch_bytes(const pfhe_tfhe_cmux_tree_handle *h) { return cmux_scratch(h); }
-int pfhe_tfhe_cmux_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0_dev, size_t len_d0, const uint64_t *d1_dev, size_t len_d1,
-                       const double *keys_dev, size_t len_keys, size_t per_key, uint64_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return cmux<u64>(Form::kDevice, h, (const u64 *)d0_dev, len_d0, (const u64 *)d1_dev, len_d1, keys_dev, len_keys, per_key,
-                     (u64 *)out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_cmux(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *d0, size_t len_d0, const uint64_t *d1, size_t len_d1, const double *keys,
-                   size_t len_keys, size_t per_key, uint64_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return cmux<u64>(Form::kHost, h, (const u64 *)d0, len_d0, (const u64 *)d1, len_d1, keys, len_keys, per_key, (u64 *)out, len_out,
-                     nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_cmux_tree_dev(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table_dev, size_t len_table, const double *selectors_dev,
-                            size_t len_selectors, uint64_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return cmux_tree<u64>(Form::kDevice, h, (const u64 *)table_dev, len_table, selectors_dev, len_selectors, (u64 *)out_dev,
-                          len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_cmux_tree(pfhe_tfhe_cmux_tree_handle *h, const uint64_t *table, size_t len_table, const double *selectors,
-                        size_t len_selectors, uint64_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return cmux_tree<u64>(Form::kHost, h, (const u64 *)table, len_table, selectors, len_selectors, (u64 *)out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_cmux_tree_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                 size_t depth, size_t chunk, pfhe_tfhe32_cmux_tree_handle **out) {
-    PFHE_GUARD_BEGIN
-    return cmux_tree_create<u32>(fft, glwe_dimension, log_basis, decompose_length, depth, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_cmux_tree_destroy(pfhe_tfhe32_cmux_tree_handle *h) { delete h; }
-int pfhe_tfhe32_cmux_tree_in_use(const pfhe_tfhe32_cmux_tree_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_cmux_tree_scratch_bytes(const pfhe_tfhe32_cmux_tree_handle *h) { return cmux_scratch(h); }
-int pfhe_tfhe32_cmux_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0_dev, size_t len_d0, const uint32_t *d1_dev, size_t len_d1,
-                         const double *keys_dev, size_t len_keys, size_t per_key, uint32_t *out_dev, size_t len_out,
-                         void *stream) {
-    PFHE_GUARD_BEGIN
-    return cmux<u32>(Form::kDevice, h, d0_dev, len_d0, d1_dev, len_d1, keys_dev, len_keys, per_key, out_dev, len_out,
-                     (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_cmux(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *d0, size_t len_d0, const uint32_t *d1, size_t len_d1,
-                     const double *keys, size_t len_keys, size_t per_key, uint32_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return cmux<u32>(Form::kHost, h, d0, len_d0, d1, len_d1, keys, len_keys, per_key, out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_cmux_tree_dev(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table_dev, size_t len_table, const double *selectors_dev,
-                              size_t len_selectors, uint32_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return cmux_tree<u32>(Form::kDevice, h, table_dev, len_table, selectors_dev, len_selectors, out_dev, len_out,
-                          (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_cmux_tree(pfhe_tfhe32_cmux_tree_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
-                          size_t len_selectors, uint32_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return cmux_tree<u32>(Form::kHost, h, table, len_table, selectors, len_selectors, out, len_out, nullptr);
-    PFHE_GUARD_END
-}
+PFHE_CMUX_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_CMUX_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_CMUX_FAMILY
 
 }  // extern "C"

@@ -361,56 +361,42 @@ int conv_host(const ConvCore *c, const W *in, size_t len_in, W *out, size_t len_
 }  // namespace
 
 // the C entry points of one word type: CV = pfhe_conv / pfhe_conv32, NS = pfhe_rns / pfhe_rns32
-#define PFHE_CONV_FAMILY(CV, NS, W)                                                                                       \
-    int CV##_create(const NS *input_base, const NS *output_base, CV **out) {                                              \
-        PFHE_GUARD_BEGIN                                                                                                  \
-        if (!input_base || !output_base || !out) return PFHE_ERR_BAD_ARGUMENT;                                            \
-        *out = nullptr;                                                                                                   \
-        auto c = std::make_unique<CV>();                                                                                  \
-        PFHE_TRY(conv_create(input_base->h, output_base->h, &c->c));                                                      \
-        *out = c.release();                                                                                               \
-        return PFHE_OK;                                                                                                   \
-        PFHE_GUARD_END                                                                                                    \
-    }                                                                                                                     \
-    void CV##_destroy(CV *c) { delete c; }                                                                                \
-    size_t CV##_input_moduli_count(const CV *c) { return c ? c->c.lin : 0; }                                              \
-    size_t CV##_output_moduli_count(const CV *c) { return c ? c->c.lout : 0; }                                            \
+#define PFHE_CONV_FAMILY(CV, NS, W)                                                                                        \
+    int CV##_create(const NS *input_base, const NS *output_base, CV **out) {                                               \
+        PFHE_GUARD_BEGIN                                                                                                   \
+        if (!input_base || !output_base || !out) return PFHE_ERR_BAD_ARGUMENT;                                             \
+        *out = nullptr;                                                                                                    \
+        auto c = std::make_unique<CV>();                                                                                   \
+        PFHE_TRY(conv_create(input_base->h, output_base->h, &c->c));                                                       \
+        *out = c.release();                                                                                                \
+        return PFHE_OK;                                                                                                    \
+        PFHE_GUARD_END                                                                                                     \
+    }                                                                                                                      \
+    void CV##_destroy(CV *c) { delete c; }                                                                                 \
+    size_t CV##_input_moduli_count(const CV *c) { return c ? c->c.lin : 0; }                                               \
+    size_t CV##_output_moduli_count(const CV *c) { return c ? c->c.lout : 0; }                                             \
     int CV##_base_change_matrix(const CV *c, W *out, size_t len) { return conv_matrix<W>(c ? &c->c : nullptr, out, len); } \
-    int CV##_fast_convert_array_dev(const CV *c, const W *crt_poly_in_dev, size_t len_in, W *crt_poly_out_dev,            \
-                                    size_t len_out, size_t poly_length, void *stream) {                                   \
-        PFHE_GUARD_BEGIN                                                                                                  \
-        return conv_array_dev<W>(c ? &c->c : nullptr, crt_poly_in_dev, len_in, crt_poly_out_dev, len_out, poly_length,    \
-                                 false, stream);                                                                          \
-        PFHE_GUARD_END                                                                                                    \
-    }                                                                                                                     \
-    int CV##_fast_convert_array_to_pairs_dev(const CV *c, const W *crt_poly_in_dev, size_t len_in, W *pairs_out_dev,      \
-                                             size_t len_out, size_t poly_length, void *stream) {                          \
-        PFHE_GUARD_BEGIN                                                                                                  \
-        return conv_pairs_dev<W>(c ? &c->c : nullptr, crt_poly_in_dev, len_in, pairs_out_dev, len_out, poly_length,       \
-                                 stream);                                                                                 \
-        PFHE_GUARD_END                                                                                                    \
-    }                                                                                                                     \
-    int CV##_exact_convert_array_dev(const CV *c, const W *crt_poly_in_dev, size_t len_in, W *crt_poly_out_dev,           \
-                                     size_t len_out, size_t poly_length, void *stream) {                                  \
-        PFHE_GUARD_BEGIN                                                                                                  \
-        return conv_array_dev<W>(c ? &c->c : nullptr, crt_poly_in_dev, len_in, crt_poly_out_dev, len_out, poly_length,    \
-                                 true, stream);                                                                           \
-        PFHE_GUARD_END                                                                                                    \
-    }                                                                                                                     \
-    int CV##_fast_convert_array(const CV *c, const W *crt_poly_in, size_t len_in, W *crt_poly_out, size_t len_out,        \
-                                size_t poly_length) {                                                                     \
-        PFHE_GUARD_BEGIN                                                                                                  \
-        return conv_host<W>(c ? &c->c : nullptr, crt_poly_in, len_in, crt_poly_out, len_out, poly_length, false);         \
-        PFHE_GUARD_END                                                                                                    \
-    }                                                                                                                     \
-    int CV##_exact_convert_array(const CV *c, const W *crt_poly_in, size_t len_in, W *crt_poly_out, size_t len_out,       \
-                                 size_t poly_length) {                                                                    \
-        PFHE_GUARD_BEGIN                                                                                                  \
-        return conv_host<W>(c ? &c->c : nullptr, crt_poly_in, len_in, crt_poly_out, len_out, poly_length, true);          \
-        PFHE_GUARD_END                                                                                                    \
-    }
+    PFHE_ENTRY(CV##_fast_convert_array_dev, (const CV *c, const W *crt_poly_in_dev, size_t len_in, W *crt_poly_out_dev,    \
+                size_t len_out, size_t poly_length, void *stream),                                                         \
+               conv_array_dev<W>(c ? &c->c : nullptr, crt_poly_in_dev, len_in, crt_poly_out_dev, len_out, poly_length,     \
+                                 false, stream))                                                                           \
+    PFHE_ENTRY(CV##_fast_convert_array_to_pairs_dev, (const CV *c, const W *crt_poly_in_dev, size_t len_in,                \
+                W *pairs_out_dev, size_t len_out, size_t poly_length, void *stream),                                       \
+               conv_pairs_dev<W>(c ? &c->c : nullptr, crt_poly_in_dev, len_in, pairs_out_dev, len_out, poly_length,        \
+                                 stream))                                                                                  \
+    PFHE_ENTRY(CV##_exact_convert_array_dev, (const CV *c, const W *crt_poly_in_dev, size_t len_in, W *crt_poly_out_dev,   \
+                size_t len_out, size_t poly_length, void *stream),                                                         \
+               conv_array_dev<W>(c ? &c->c : nullptr, crt_poly_in_dev, len_in, crt_poly_out_dev, len_out, poly_length,     \
+                                 true, stream))                                                                            \
+    PFHE_ENTRY(CV##_fast_convert_array, (const CV *c, const W *crt_poly_in, size_t len_in, W *crt_poly_out,                \
+                size_t len_out, size_t poly_length),                                                                       \
+               conv_host<W>(c ? &c->c : nullptr, crt_poly_in, len_in, crt_poly_out, len_out, poly_length, false))          \
+    PFHE_ENTRY(CV##_exact_convert_array, (const CV *c, const W *crt_poly_in, size_t len_in, W *crt_poly_out,               \
+                size_t len_out, size_t poly_length),                                                                       \
+               conv_host<W>(c ? &c->c : nullptr, crt_poly_in, len_in, crt_poly_out, len_out, poly_length, true))
 
 extern "C" {
 PFHE_CONV_FAMILY(pfhe_conv, pfhe_rns, uint64_t)
 PFHE_CONV_FAMILY(pfhe_conv32, pfhe_rns32, uint32_t)
+#undef PFHE_CONV_FAMILY
 }  // extern "C"

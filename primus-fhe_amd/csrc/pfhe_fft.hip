@@ -878,7 +878,73 @@ template int tfhe_half_inverse_launch<u32>(const pfhe_fft &, const double2 *, u3
 
 }  // namespace pfhe
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; T: what the transforms' names call the width (torus /
+// torus32); CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_FFT_FAMILY(P, T, CW, W)                                                                                  \
+    PFHE_ENTRY(pfhe_fft_forward_##T##_dev, (const pfhe_fft *fft, const CW *input_dev, size_t len_input,               \
+                double *output_dev, size_t len_output, void *stream),                                                 \
+               forward_dev<W>(fft, (const W *)input_dev, len_input, output_dev, len_output, (hipStream_t)stream))     \
+    PFHE_ENTRY(pfhe_fft_inverse_##T##_dev, (const pfhe_fft *fft, const double *input_dev, size_t len_input,           \
+                CW *output_dev, size_t len_output, void *stream),                                                     \
+               inverse_dev<W>(fft, input_dev, len_input, (W *)output_dev, len_output, (hipStream_t)stream))           \
+    PFHE_ENTRY(pfhe_fft_forward_##T##_slice, (const pfhe_fft *fft, const CW *input, size_t len_input, double *output, \
+                size_t len_output),                                                                                   \
+               host_form(fft, input, len_input * sizeof(W), output, len_output * 16, len_input, len_output,           \
+                         [&](const CW *a, double *b, hipStream_t s) {                                                 \
+                             return forward_dev<W>(fft, (const W *)a, len_input, b, len_output, s);                   \
+                         }))                                                                                          \
+    PFHE_ENTRY(pfhe_fft_inverse_##T##_slice, (const pfhe_fft *fft, const double *input, size_t len_input, CW *output, \
+                size_t len_output),                                                                                   \
+               host_form(fft, input, len_input * 16, output, len_output * sizeof(W), len_input, len_output,           \
+                         [&](const double *a, CW *b, hipStream_t s) {                                                 \
+                             return inverse_dev<W>(fft, a, len_input, (W *)b, len_output, s);                         \
+                         }))                                                                                          \
+    PFHE_ENTRY(P##_plan_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                      \
+                size_t decompose_length, size_t chunk, P##_plan **out),                                               \
+               tfhe_plan_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, out))                     \
+    PFHE_HANDLE_TRIO(P##_plan, P##_plan, h->scratch.bytes())                                                          \
+    PFHE_ENTRY(P##_external_product_to_dev, (P##_plan *plan, const CW *input_dev, size_t len_input,                   \
+                const double *key_dev, size_t len_key, CW *output_dev, size_t len_output, void *stream),              \
+               product<W>(Form::kDevice, plan, (const W *)input_dev, len_input, key_dev, len_key, (W *)output_dev,    \
+                          len_output, (hipStream_t)stream))                                                           \
+    PFHE_ENTRY(P##_external_product_to, (P##_plan *plan, const CW *input, size_t len_input, const double *key,        \
+                size_t len_key, CW *output, size_t len_output),                                                       \
+               product<W>(Form::kHost, plan, (const W *)input, len_input, key, len_key, (W *)output, len_output,      \
+                          nullptr))                                                                                   \
+    PFHE_ENTRY(P##_blindrot_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                  \
+                size_t decompose_length, size_t chunk, P##_blindrot **out),                                           \
+               tfhe_blindrot_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, out))                 \
+    PFHE_HANDLE_TRIO(P##_blindrot, P##_blindrot, h->scratch_bytes())                                                  \
+    PFHE_ENTRY(P##_blindrot_rotate_dev, (P##_blindrot *h, CW *acc_dev, size_t len_acc, const double *bsk_dev,         \
+                size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream),                             \
+               tfhe_blindrot<W>(Form::kDevice, h, (W *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps,        \
+                                (hipStream_t)stream))                                                                 \
+    PFHE_ENTRY(P##_blindrot_rotate, (P##_blindrot *h, CW *acc, size_t len_acc, const double *bsk, size_t len_bsk,     \
+                const uint32_t *exps, size_t len_exps),                                                               \
+               tfhe_blindrot<W>(Form::kHost, h, (W *)acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr))            \
+    PFHE_ENTRY(P##_mul_monomial_each_to_dev, (const pfhe_fft *fft, const CW *a_dev, size_t len,                       \
+                const uint32_t *exps_dev, size_t polys_per_exp, CW *out_dev, void *stream),                           \
+               torus_monomial_each<W>(fft, (const W *)a_dev, len, exps_dev, polys_per_exp, (W *)out_dev,              \
+                                      (hipStream_t)stream))                                                           \
+    PFHE_ENTRY(P##_mbrot_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                     \
+                size_t decompose_length, size_t grouping_factor, size_t chunk, P##_mbrot **out),                      \
+               tfhe_mbrot_create<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out))   \
+    PFHE_HANDLE_TRIO(P##_mbrot, P##_mbrot, h->scratch_bytes())                                                        \
+    PFHE_ENTRY(P##_mbrot_rotate_dev, (P##_mbrot *h, CW *acc_dev, size_t len_acc, const double *bsk_dev,               \
+                size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream),                             \
+               tfhe_mbrot<W>(Form::kDevice, h, (W *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps,           \
+                             (hipStream_t)stream))                                                                    \
+    PFHE_ENTRY(P##_mbrot_rotate, (P##_mbrot *h, CW *acc, size_t len_acc, const double *bsk, size_t len_bsk,           \
+                const uint32_t *exps, size_t len_exps),                                                               \
+               tfhe_mbrot<W>(Form::kHost, h, (W *)acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr))
+
 extern "C" {
+
+PFHE_FFT_FAMILY(pfhe_tfhe, torus, uint64_t, u64)
+PFHE_FFT_FAMILY(pfhe_tfhe32, torus32, uint32_t, u32)
+#undef PFHE_FFT_FAMILY
+
+/* ------------------------------ entry points without a word width ------------------------------ */
 
 int pfhe_fft_create(uint32_t log_n, int device, pfhe_fft **out) {
     PFHE_GUARD_BEGIN
@@ -914,218 +980,6 @@ void pfhe_fft_destroy(pfhe_fft *fft) { delete fft; }
 size_t pfhe_fft_poly_length(const pfhe_fft *fft) { return fft ? fft->n : 0; }
 size_t pfhe_fft_fourier_length(const pfhe_fft *fft) { return fft ? fft->n : 0; }
 
-int pfhe_fft_forward_torus_dev(const pfhe_fft *fft, const uint64_t *input_dev, size_t len_input, double *output_dev,
-                               size_t len_output, void *stream) {
-    PFHE_GUARD_BEGIN
-    return forward_dev<u64>(fft, (const u64 *)input_dev, len_input, output_dev, len_output, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_fft_forward_torus32_dev(const pfhe_fft *fft, const uint32_t *input_dev, size_t len_input, double *output_dev,
-                                 size_t len_output, void *stream) {
-    PFHE_GUARD_BEGIN
-    return forward_dev<u32>(fft, input_dev, len_input, output_dev, len_output, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_fft_inverse_torus_dev(const pfhe_fft *fft, const double *input_dev, size_t len_input, uint64_t *output_dev,
-                               size_t len_output, void *stream) {
-    PFHE_GUARD_BEGIN
-    return inverse_dev<u64>(fft, input_dev, len_input, (u64 *)output_dev, len_output, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_fft_inverse_torus32_dev(const pfhe_fft *fft, const double *input_dev, size_t len_input, uint32_t *output_dev,
-                                 size_t len_output, void *stream) {
-    PFHE_GUARD_BEGIN
-    return inverse_dev<u32>(fft, input_dev, len_input, output_dev, len_output, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_fft_forward_torus_slice(const pfhe_fft *fft, const uint64_t *input, size_t len_input, double *output,
-                                 size_t len_output) {
-    PFHE_GUARD_BEGIN
-    return host_form(fft, input, len_input * 8, output, len_output * 16, len_input, len_output,
-                     [&](const uint64_t *a, double *b, hipStream_t s) {
-                         return forward_dev<u64>(fft, (const u64 *)a, len_input, b, len_output, s);
-                     });
-    PFHE_GUARD_END
-}
-int pfhe_fft_forward_torus32_slice(const pfhe_fft *fft, const uint32_t *input, size_t len_input, double *output,
-                                   size_t len_output) {
-    PFHE_GUARD_BEGIN
-    return host_form(fft, input, len_input * 4, output, len_output * 16, len_input, len_output,
-                     [&](const uint32_t *a, double *b, hipStream_t s) {
-                         return forward_dev<u32>(fft, a, len_input, b, len_output, s);
-                     });
-    PFHE_GUARD_END
-}
-int pfhe_fft_inverse_torus_slice(const pfhe_fft *fft, const double *input, size_t len_input, uint64_t *output,
-                                 size_t len_output) {
-    PFHE_GUARD_BEGIN
-    return host_form(fft, input, len_input * 16, output, len_output * 8, len_input, len_output,
-                     [&](const double *a, uint64_t *b, hipStream_t s) {
-                         return inverse_dev<u64>(fft, a, len_input, (u64 *)b, len_output, s);
-                     });
-    PFHE_GUARD_END
-}
-int pfhe_fft_inverse_torus32_slice(const pfhe_fft *fft, const double *input, size_t len_input, uint32_t *output,
-                                   size_t len_output) {
-    PFHE_GUARD_BEGIN
-    return host_form(fft, input, len_input * 16, output, len_output * 4, len_input, len_output,
-                     [&](const double *a, uint32_t *b, hipStream_t s) {
-                         return inverse_dev<u32>(fft, a, len_input, b, len_output, s);
-                     });
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                          size_t chunk, pfhe_tfhe_plan **out) {
-    PFHE_GUARD_BEGIN
-    return tfhe_plan_create<u64>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_plan_destroy(pfhe_tfhe_plan *plan) { delete plan; }
-int pfhe_tfhe_plan_in_use(const pfhe_tfhe_plan *plan) {
-    return plan ? plan->guard.in_use() : 0;
-}
-size_t pfhe_tfhe_plan_scratch_bytes(const pfhe_tfhe_plan *plan) { return plan ? plan->scratch.bytes() : 0; }
-int pfhe_tfhe_external_product_to_dev(pfhe_tfhe_plan *plan, const uint64_t *input_dev, size_t len_input,
-                                      const double *key_dev, size_t len_key, uint64_t *output_dev, size_t len_output,
-                                      void *stream) {
-    PFHE_GUARD_BEGIN
-    return product<u64>(Form::kDevice, plan, (const u64 *)input_dev, len_input, key_dev, len_key, (u64 *)output_dev, len_output,
-                            (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_external_product_to(pfhe_tfhe_plan *plan, const uint64_t *input, size_t len_input, const double *key,
-                                  size_t len_key, uint64_t *output, size_t len_output) {
-    PFHE_GUARD_BEGIN
-    return product<u64>(Form::kHost, plan, (const u64 *)input, len_input, key, len_key, (u64 *)output, len_output, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                            size_t chunk, pfhe_tfhe32_plan **out) {
-    PFHE_GUARD_BEGIN
-    return tfhe_plan_create<u32>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_plan_destroy(pfhe_tfhe32_plan *plan) { delete plan; }
-int pfhe_tfhe32_plan_in_use(const pfhe_tfhe32_plan *plan) {
-    return plan ? plan->guard.in_use() : 0;
-}
-size_t pfhe_tfhe32_plan_scratch_bytes(const pfhe_tfhe32_plan *plan) { return plan ? plan->scratch.bytes() : 0; }
-int pfhe_tfhe32_external_product_to_dev(pfhe_tfhe32_plan *plan, const uint32_t *input_dev, size_t len_input,
-                                        const double *key_dev, size_t len_key, uint32_t *output_dev, size_t len_output,
-                                        void *stream) {
-    PFHE_GUARD_BEGIN
-    return product<u32>(Form::kDevice, plan, input_dev, len_input, key_dev, len_key, output_dev, len_output, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_external_product_to(pfhe_tfhe32_plan *plan, const uint32_t *input, size_t len_input, const double *key,
-                                    size_t len_key, uint32_t *output, size_t len_output) {
-    PFHE_GUARD_BEGIN
-    return product<u32>(Form::kHost, plan, input, len_input, key, len_key, output, len_output, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                              size_t chunk, pfhe_tfhe_blindrot **out) {
-    PFHE_GUARD_BEGIN
-    return tfhe_blindrot_create<u64>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_blindrot_destroy(pfhe_tfhe_blindrot *h) { delete h; }
-int pfhe_tfhe_blindrot_in_use(const pfhe_tfhe_blindrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_blindrot_scratch_bytes(const pfhe_tfhe_blindrot *h) { return h ? h->scratch_bytes() : 0; }
-int pfhe_tfhe_blindrot_rotate_dev(pfhe_tfhe_blindrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev,
-                                  size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
-    PFHE_GUARD_BEGIN
-    return tfhe_blindrot<u64>(Form::kDevice, h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_blindrot_rotate(pfhe_tfhe_blindrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                              const uint32_t *exps, size_t len_exps) {
-    PFHE_GUARD_BEGIN
-    return tfhe_blindrot<u64>(Form::kHost, h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint64_t *a_dev, size_t len, const uint32_t *exps_dev,
-                                       size_t polys_per_exp, uint64_t *out_dev, void *stream) {
-    PFHE_GUARD_BEGIN
-    return torus_monomial_each<u64>(fft, (const u64 *)a_dev, len, exps_dev, polys_per_exp, (u64 *)out_dev,
-                                    (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_blindrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                size_t chunk, pfhe_tfhe32_blindrot **out) {
-    PFHE_GUARD_BEGIN
-    return tfhe_blindrot_create<u32>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_blindrot_destroy(pfhe_tfhe32_blindrot *h) { delete h; }
-int pfhe_tfhe32_blindrot_in_use(const pfhe_tfhe32_blindrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_blindrot_scratch_bytes(const pfhe_tfhe32_blindrot *h) { return h ? h->scratch_bytes() : 0; }
-int pfhe_tfhe32_blindrot_rotate_dev(pfhe_tfhe32_blindrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev,
-                                    size_t len_bsk, const uint32_t *exps_dev, size_t len_exps, void *stream) {
-    PFHE_GUARD_BEGIN
-    return tfhe_blindrot<u32>(Form::kDevice, h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_blindrot_rotate(pfhe_tfhe32_blindrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                                const uint32_t *exps, size_t len_exps) {
-    PFHE_GUARD_BEGIN
-    return tfhe_blindrot<u32>(Form::kHost, h, acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_mul_monomial_each_to_dev(const pfhe_fft *fft, const uint32_t *a_dev, size_t len, const uint32_t *exps_dev,
-                                         size_t polys_per_exp, uint32_t *out_dev, void *stream) {
-    PFHE_GUARD_BEGIN
-    return torus_monomial_each<u32>(fft, a_dev, len, exps_dev, polys_per_exp, out_dev, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                           size_t grouping_factor, size_t chunk, pfhe_tfhe_mbrot **out) {
-    PFHE_GUARD_BEGIN
-    return tfhe_mbrot_create<u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_mbrot_destroy(pfhe_tfhe_mbrot *h) { delete h; }
-int pfhe_tfhe_mbrot_in_use(const pfhe_tfhe_mbrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_mbrot_scratch_bytes(const pfhe_tfhe_mbrot *h) { return h ? h->scratch_bytes() : 0; }
-int pfhe_tfhe_mbrot_rotate_dev(pfhe_tfhe_mbrot *h, uint64_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
-                               const uint32_t *exps_dev, size_t len_exps, void *stream) {
-    PFHE_GUARD_BEGIN
-    return tfhe_mbrot<u64>(Form::kDevice, h, (u64 *)acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_mbrot_rotate(pfhe_tfhe_mbrot *h, uint64_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                           const uint32_t *exps, size_t len_exps) {
-    PFHE_GUARD_BEGIN
-    return tfhe_mbrot<u64>(Form::kHost, h, (u64 *)acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_mbrot_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                             size_t grouping_factor, size_t chunk, pfhe_tfhe32_mbrot **out) {
-    PFHE_GUARD_BEGIN
-    return tfhe_mbrot_create<u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_mbrot_destroy(pfhe_tfhe32_mbrot *h) { delete h; }
-int pfhe_tfhe32_mbrot_in_use(const pfhe_tfhe32_mbrot *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_mbrot_scratch_bytes(const pfhe_tfhe32_mbrot *h) { return h ? h->scratch_bytes() : 0; }
-int pfhe_tfhe32_mbrot_rotate_dev(pfhe_tfhe32_mbrot *h, uint32_t *acc_dev, size_t len_acc, const double *bsk_dev, size_t len_bsk,
-                                 const uint32_t *exps_dev, size_t len_exps, void *stream) {
-    PFHE_GUARD_BEGIN
-    return tfhe_mbrot<u32>(Form::kDevice, h, acc_dev, len_acc, bsk_dev, len_bsk, exps_dev, len_exps, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_mbrot_rotate(pfhe_tfhe32_mbrot *h, uint32_t *acc, size_t len_acc, const double *bsk, size_t len_bsk,
-                             const uint32_t *exps, size_t len_exps) {
-    PFHE_GUARD_BEGIN
-    return tfhe_mbrot<u32>(Form::kHost, h, acc, len_acc, bsk, len_bsk, exps, len_exps, nullptr);
-    PFHE_GUARD_END
-}
 int pfhe_tfhe_mb_combine_key_dev(const pfhe_fft *fft, size_t glwe_dimension, size_t decompose_length, size_t grouping_factor,
                                  const double *keys_dev, size_t len_keys, const uint32_t *exps_dev, size_t len_exps,
                                  double *out_dev, size_t len_out, void *stream) {

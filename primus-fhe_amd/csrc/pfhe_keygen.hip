@@ -321,115 +321,46 @@ int ksk_generate_dev(int device, const W *key_in, size_t in_dimension, const W *
 }  // namespace
 }  // namespace pfhe
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_KEYGEN_FAMILY(P, CW, W)                                                                                    \
+    PFHE_ENTRY(P##_lwe_body_mac_dev, (int device, CW *lwe_dev, size_t len_lwe, size_t dimension, const CW *key_dev,     \
+                size_t len_key, int subtract, void *stream),                                                            \
+               lwe_body_mac<W>(Form::kDevice, device, (W *)lwe_dev, len_lwe, dimension, (const W *)key_dev, len_key,    \
+                               subtract, (hipStream_t)stream))                                                          \
+    PFHE_ENTRY(P##_lwe_body_mac, (int device, CW *lwe, size_t len_lwe, size_t dimension, const CW *key, size_t len_key, \
+                int subtract),                                                                                          \
+               lwe_body_mac<W>(Form::kHost, device, (W *)lwe, len_lwe, dimension, (const W *)key, len_key, subtract,    \
+                               nullptr))                                                                                \
+    PFHE_ENTRY(P##_glwe_body_mac_dev, (const pfhe_fft *fft, size_t glwe_dimension, CW *glwe_dev, size_t len_glwe,       \
+                const CW *key_dev, size_t len_key, int subtract, void *stream),                                         \
+               glwe_body_mac<W>(Form::kDevice, fft, glwe_dimension, (W *)glwe_dev, len_glwe, (const W *)key_dev,        \
+                                len_key, subtract, (hipStream_t)stream))                                                \
+    PFHE_ENTRY(P##_glwe_body_mac, (const pfhe_fft *fft, size_t glwe_dimension, CW *glwe, size_t len_glwe,               \
+                const CW *key, size_t len_key, int subtract),                                                           \
+               glwe_body_mac<W>(Form::kHost, fft, glwe_dimension, (W *)glwe, len_glwe, (const W *)key, len_key,         \
+                                subtract, nullptr))                                                                     \
+    PFHE_ENTRY(P##_ggsw_add_gadget_dev, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                \
+                size_t decompose_length, CW *ggsw_dev, size_t len_ggsw, const CW *messages_dev, size_t len_messages,    \
+                void *stream),                                                                                          \
+               ggsw_add_gadget_dev<W>(fft, glwe_dimension, log_basis, decompose_length, (W *)ggsw_dev, len_ggsw,        \
+                                      (const W *)messages_dev, len_messages, (hipStream_t)stream))                      \
+    PFHE_ENTRY(P##_bsk_generate_dev, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                   \
+                size_t decompose_length, size_t grouping_factor, const CW *lwe_key_dev, size_t lwe_dimension,           \
+                const CW *glwe_key_dev, size_t len_glwe_key, CW *ggsw_torus_dev, size_t len_ggsw, double *bsk_out_dev,  \
+                size_t len_bsk, void *stream),                                                                          \
+               bsk_generate_dev<W>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor,                   \
+                                   (const W *)lwe_key_dev, lwe_dimension, (const W *)glwe_key_dev, len_glwe_key,        \
+                                   (W *)ggsw_torus_dev, len_ggsw, bsk_out_dev, len_bsk, (hipStream_t)stream))           \
+    PFHE_ENTRY(P##_ksk_generate_dev, (int device, const CW *key_in_dev, size_t in_dimension, const CW *key_out_dev,     \
+                size_t out_dimension, uint32_t log_basis, size_t decompose_length, CW *ksk_dev, size_t len_ksk,         \
+                void *stream),                                                                                          \
+               ksk_generate_dev<W>(device, (const W *)key_in_dev, in_dimension, (const W *)key_out_dev, out_dimension,  \
+                                   log_basis, decompose_length, (W *)ksk_dev, len_ksk, (hipStream_t)stream))
+
 extern "C" {
 
-int pfhe_tfhe_lwe_body_mac_dev(int device, uint64_t *lwe_dev, size_t len_lwe, size_t dimension, const uint64_t *key_dev,
-                               size_t len_key, int subtract, void *stream) {
-    PFHE_GUARD_BEGIN
-    return lwe_body_mac<u64>(Form::kDevice, device, (u64 *)lwe_dev, len_lwe, dimension, (const u64 *)key_dev, len_key, subtract,
-                             (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_lwe_body_mac(int device, uint64_t *lwe, size_t len_lwe, size_t dimension, const uint64_t *key, size_t len_key,
-                           int subtract) {
-    PFHE_GUARD_BEGIN
-    return lwe_body_mac<u64>(Form::kHost, device, (u64 *)lwe, len_lwe, dimension, (const u64 *)key, len_key, subtract, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_lwe_body_mac_dev(int device, uint32_t *lwe_dev, size_t len_lwe, size_t dimension, const uint32_t *key_dev,
-                                 size_t len_key, int subtract, void *stream) {
-    PFHE_GUARD_BEGIN
-    return lwe_body_mac<u32>(Form::kDevice, device, lwe_dev, len_lwe, dimension, key_dev, len_key, subtract, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_lwe_body_mac(int device, uint32_t *lwe, size_t len_lwe, size_t dimension, const uint32_t *key, size_t len_key,
-                             int subtract) {
-    PFHE_GUARD_BEGIN
-    return lwe_body_mac<u32>(Form::kHost, device, lwe, len_lwe, dimension, key, len_key, subtract, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_glwe_body_mac_dev(const pfhe_fft *fft, size_t glwe_dimension, uint64_t *glwe_dev, size_t len_glwe,
-                                const uint64_t *key_dev, size_t len_key, int subtract, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glwe_body_mac<u64>(Form::kDevice, fft, glwe_dimension, (u64 *)glwe_dev, len_glwe, (const u64 *)key_dev, len_key,
-                              subtract, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_glwe_body_mac(const pfhe_fft *fft, size_t glwe_dimension, uint64_t *glwe, size_t len_glwe, const uint64_t *key,
-                            size_t len_key, int subtract) {
-    PFHE_GUARD_BEGIN
-    return glwe_body_mac<u64>(Form::kHost, fft, glwe_dimension, (u64 *)glwe, len_glwe, (const u64 *)key, len_key, subtract,
-                              nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_glwe_body_mac_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t *glwe_dev, size_t len_glwe,
-                                  const uint32_t *key_dev, size_t len_key, int subtract, void *stream) {
-    PFHE_GUARD_BEGIN
-    return glwe_body_mac<u32>(Form::kDevice, fft, glwe_dimension, glwe_dev, len_glwe, key_dev, len_key, subtract,
-                              (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_glwe_body_mac(const pfhe_fft *fft, size_t glwe_dimension, uint32_t *glwe, size_t len_glwe, const uint32_t *key,
-                              size_t len_key, int subtract) {
-    PFHE_GUARD_BEGIN
-    return glwe_body_mac<u32>(Form::kHost, fft, glwe_dimension, glwe, len_glwe, key, len_key, subtract, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_ggsw_add_gadget_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                  uint64_t *ggsw_dev, size_t len_ggsw, const uint64_t *messages_dev, size_t len_messages,
-                                  void *stream) {
-    PFHE_GUARD_BEGIN
-    return ggsw_add_gadget_dev<u64>(fft, glwe_dimension, log_basis, decompose_length, (u64 *)ggsw_dev, len_ggsw,
-                                    (const u64 *)messages_dev, len_messages, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_ggsw_add_gadget_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                    uint32_t *ggsw_dev, size_t len_ggsw, const uint32_t *messages_dev, size_t len_messages,
-                                    void *stream) {
-    PFHE_GUARD_BEGIN
-    return ggsw_add_gadget_dev<u32>(fft, glwe_dimension, log_basis, decompose_length, ggsw_dev, len_ggsw, messages_dev,
-                                    len_messages, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_bsk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                               size_t grouping_factor, const uint64_t *lwe_key_dev, size_t lwe_dimension,
-                               const uint64_t *glwe_key_dev, size_t len_glwe_key, uint64_t *ggsw_torus_dev, size_t len_ggsw,
-                               double *bsk_out_dev, size_t len_bsk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return bsk_generate_dev<u64>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, (const u64 *)lwe_key_dev,
-                                 lwe_dimension, (const u64 *)glwe_key_dev, len_glwe_key, (u64 *)ggsw_torus_dev, len_ggsw,
-                                 bsk_out_dev, len_bsk, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_bsk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                 size_t grouping_factor, const uint32_t *lwe_key_dev, size_t lwe_dimension,
-                                 const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t *ggsw_torus_dev, size_t len_ggsw,
-                                 double *bsk_out_dev, size_t len_bsk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return bsk_generate_dev<u32>(fft, glwe_dimension, log_basis, decompose_length, grouping_factor, lwe_key_dev, lwe_dimension,
-                                 glwe_key_dev, len_glwe_key, ggsw_torus_dev, len_ggsw, bsk_out_dev, len_bsk,
-                                 (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_ksk_generate_dev(int device, const uint64_t *key_in_dev, size_t in_dimension, const uint64_t *key_out_dev,
-                               size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint64_t *ksk_dev,
-                               size_t len_ksk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return ksk_generate_dev<u64>(device, (const u64 *)key_in_dev, in_dimension, (const u64 *)key_out_dev, out_dimension,
-                                 log_basis, decompose_length, (u64 *)ksk_dev, len_ksk, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_ksk_generate_dev(int device, const uint32_t *key_in_dev, size_t in_dimension, const uint32_t *key_out_dev,
-                                 size_t out_dimension, uint32_t log_basis, size_t decompose_length, uint32_t *ksk_dev,
-                                 size_t len_ksk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return ksk_generate_dev<u32>(device, key_in_dev, in_dimension, key_out_dev, out_dimension, log_basis, decompose_length,
-                                 ksk_dev, len_ksk, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
+PFHE_KEYGEN_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_KEYGEN_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_KEYGEN_FAMILY
 
 }  // extern "C"

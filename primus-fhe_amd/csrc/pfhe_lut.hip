@@ -384,84 +384,36 @@ size_t lut_scratch(const H *h) {
 
 }  // namespace
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_LUT_FAMILY(P, CW, W)                                                                                         \
+    PFHE_ENTRY(P##_lut_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                           \
+                size_t decompose_length, size_t tree_depth, size_t rot_bits, size_t log_stride, size_t outputs,           \
+                size_t chunk, P##_lut_handle **out),                                                                      \
+               lut_create<W>(fft, glwe_dimension, log_basis, decompose_length, tree_depth, rot_bits, log_stride, outputs, \
+                             chunk, out))                                                                                 \
+    PFHE_HANDLE_TRIO(P##_lut, P##_lut_handle, lut_scratch(h))                                                             \
+    PFHE_ENTRY(P##_rotate_by_bits_dev, (P##_lut_handle *h, const CW *inp_dev, size_t len_inp, const double *keys_dev,     \
+                size_t len_keys, size_t keys_per_input, size_t first_key, CW *out_dev, size_t len_out, void *stream),     \
+               rotate_by_bits<W>(Form::kDevice, h, (const W *)inp_dev, len_inp, keys_dev, len_keys, keys_per_input,       \
+                                 first_key, (W *)out_dev, len_out, (hipStream_t)stream))                                  \
+    PFHE_ENTRY(P##_rotate_by_bits, (P##_lut_handle *h, const CW *inp, size_t len_inp, const double *keys,                 \
+                size_t len_keys, size_t keys_per_input, size_t first_key, CW *out, size_t len_out),                       \
+               rotate_by_bits<W>(Form::kHost, h, (const W *)inp, len_inp, keys, len_keys, keys_per_input, first_key,      \
+                                 (W *)out, len_out, nullptr))                                                             \
+    PFHE_ENTRY(P##_lut_eval_dev, (P##_lut_handle *h, const CW *table_dev, size_t len_table,                               \
+                const double *selectors_dev, size_t len_selectors, size_t extract, CW *out_dev, size_t len_out,           \
+                void *stream),                                                                                            \
+               lut_eval<W>(Form::kDevice, h, (const W *)table_dev, len_table, selectors_dev, len_selectors, extract,      \
+                           (W *)out_dev, len_out, (hipStream_t)stream))                                                   \
+    PFHE_ENTRY(P##_lut_eval, (P##_lut_handle *h, const CW *table, size_t len_table, const double *selectors,              \
+                size_t len_selectors, size_t extract, CW *out, size_t len_out),                                           \
+               lut_eval<W>(Form::kHost, h, (const W *)table, len_table, selectors, len_selectors, extract, (W *)out,      \
+                           len_out, nullptr))
+
 extern "C" {
 
-int pfhe_tfhe_lut_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                         size_t tree_depth, size_t rot_bits, size_t log_stride, size_t outputs, size_t chunk,
-                         pfhe_tfhe_lut_handle **out) {
-    PFHE_GUARD_BEGIN
-    return lut_create<u64>(fft, glwe_dimension, log_basis, decompose_length, tree_depth, rot_bits, log_stride, outputs, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_lut_destroy(pfhe_tfhe_lut_handle *h) { delete h; }
-int pfhe_tfhe_lut_in_use(const pfhe_tfhe_lut_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_lut_scratch_bytes(const pfhe_tfhe_lut_handle *h) { return lut_scratch(h); }
-int pfhe_tfhe_rotate_by_bits_dev(pfhe_tfhe_lut_handle *h, const uint64_t *inp_dev, size_t len_inp, const double *keys_dev,
-                                 size_t len_keys, size_t keys_per_input, size_t first_key, uint64_t *out_dev, size_t len_out,
-                                 void *stream) {
-    PFHE_GUARD_BEGIN
-    return rotate_by_bits<u64>(Form::kDevice, h, (const u64 *)inp_dev, len_inp, keys_dev, len_keys, keys_per_input, first_key,
-                               (u64 *)out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_rotate_by_bits(pfhe_tfhe_lut_handle *h, const uint64_t *inp, size_t len_inp, const double *keys, size_t len_keys,
-                             size_t keys_per_input, size_t first_key, uint64_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return rotate_by_bits<u64>(Form::kHost, h, (const u64 *)inp, len_inp, keys, len_keys, keys_per_input, first_key, (u64 *)out,
-                               len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_lut_eval_dev(pfhe_tfhe_lut_handle *h, const uint64_t *table_dev, size_t len_table, const double *selectors_dev,
-                           size_t len_selectors, size_t extract, uint64_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return lut_eval<u64>(Form::kDevice, h, (const u64 *)table_dev, len_table, selectors_dev, len_selectors, extract,
-                         (u64 *)out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_lut_eval(pfhe_tfhe_lut_handle *h, const uint64_t *table, size_t len_table, const double *selectors,
-                       size_t len_selectors, size_t extract, uint64_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return lut_eval<u64>(Form::kHost, h, (const u64 *)table, len_table, selectors, len_selectors, extract, (u64 *)out, len_out,
-                         nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_lut_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                           size_t tree_depth, size_t rot_bits, size_t log_stride, size_t outputs, size_t chunk,
-                           pfhe_tfhe32_lut_handle **out) {
-    PFHE_GUARD_BEGIN
-    return lut_create<u32>(fft, glwe_dimension, log_basis, decompose_length, tree_depth, rot_bits, log_stride, outputs, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_lut_destroy(pfhe_tfhe32_lut_handle *h) { delete h; }
-int pfhe_tfhe32_lut_in_use(const pfhe_tfhe32_lut_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_lut_scratch_bytes(const pfhe_tfhe32_lut_handle *h) { return lut_scratch(h); }
-int pfhe_tfhe32_rotate_by_bits_dev(pfhe_tfhe32_lut_handle *h, const uint32_t *inp_dev, size_t len_inp, const double *keys_dev,
-                                   size_t len_keys, size_t keys_per_input, size_t first_key, uint32_t *out_dev, size_t len_out,
-                                   void *stream) {
-    PFHE_GUARD_BEGIN
-    return rotate_by_bits<u32>(Form::kDevice, h, inp_dev, len_inp, keys_dev, len_keys, keys_per_input, first_key, out_dev,
-                               len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_rotate_by_bits(pfhe_tfhe32_lut_handle *h, const uint32_t *inp, size_t len_inp, const double *keys, size_t len_keys,
-                               size_t keys_per_input, size_t first_key, uint32_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return rotate_by_bits<u32>(Form::kHost, h, inp, len_inp, keys, len_keys, keys_per_input, first_key, out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_lut_eval_dev(pfhe_tfhe32_lut_handle *h, const uint32_t *table_dev, size_t len_table, const double *selectors_dev,
-                             size_t len_selectors, size_t extract, uint32_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return lut_eval<u32>(Form::kDevice, h, table_dev, len_table, selectors_dev, len_selectors, extract, out_dev, len_out,
-                         (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_lut_eval(pfhe_tfhe32_lut_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
-                         size_t len_selectors, size_t extract, uint32_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return lut_eval<u32>(Form::kHost, h, table, len_table, selectors, len_selectors, extract, out, len_out, nullptr);
-    PFHE_GUARD_END
-}
+PFHE_LUT_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_LUT_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_LUT_FAMILY
 
 }  // extern "C"

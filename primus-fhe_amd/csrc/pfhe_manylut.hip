@@ -156,23 +156,18 @@ int modswitch_stride_dev(int device, const W *lwe, size_t len_lwe, size_t lwe_di
 }  // namespace
 }  // namespace pfhe
 
+// The entry point of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_MANYLUT_FAMILY(P, CW, W)                                                                                   \
+    PFHE_ENTRY(P##_modswitch_stride_dev, (int device, const CW *lwe_dev, size_t len_lwe, size_t lwe_dimension,          \
+                uint32_t log_n, uint32_t log_stride, uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev,          \
+                size_t len_neg_b, void *stream),                                                                        \
+               modswitch_stride_dev<W>(device, (const W *)lwe_dev, len_lwe, lwe_dimension, log_n, log_stride, exps_dev, \
+                                       len_exps, neg_b_dev, len_neg_b, (hipStream_t)stream))
+
 extern "C" {
 
-int pfhe_tfhe_modswitch_stride_dev(int device, const uint64_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
-                                   uint32_t log_stride, uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev,
-                                   size_t len_neg_b, void *stream) {
-    PFHE_GUARD_BEGIN
-    return modswitch_stride_dev<u64>(device, (const u64 *)lwe_dev, len_lwe, lwe_dimension, log_n, log_stride, exps_dev, len_exps,
-                                     neg_b_dev, len_neg_b, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_modswitch_stride_dev(int device, const uint32_t *lwe_dev, size_t len_lwe, size_t lwe_dimension, uint32_t log_n,
-                                     uint32_t log_stride, uint32_t *exps_dev, size_t len_exps, uint32_t *neg_b_dev,
-                                     size_t len_neg_b, void *stream) {
-    PFHE_GUARD_BEGIN
-    return modswitch_stride_dev<u32>(device, lwe_dev, len_lwe, lwe_dimension, log_n, log_stride, exps_dev, len_exps, neg_b_dev,
-                                     len_neg_b, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
+PFHE_MANYLUT_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_MANYLUT_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_MANYLUT_FAMILY
 
 }  // extern "C"

@@ -374,115 +374,47 @@ int multimsg_extract(Form form, const pfhe_fft *f, size_t k, const W *multi, siz
 }  // namespace
 }  // namespace pfhe
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_PACK_FAMILY(P, CW, W)                                                                                       \
+    PFHE_ENTRY(P##_pack_keyswitch_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *lwe_in_dev, size_t len_in, \
+                size_t in_dimension, size_t count, const CW *pksk_dev, size_t len_pksk, uint32_t log_basis,              \
+                size_t decompose_length, CW *glwe_out_dev, size_t len_out, void *stream),                                \
+               pack_keyswitch<W>(Form::kDevice, fft, glwe_dimension, (const W *)lwe_in_dev, len_in, in_dimension, count, \
+                                 (const W *)pksk_dev, len_pksk, log_basis, decompose_length, (W *)glwe_out_dev, len_out, \
+                                 (hipStream_t)stream))                                                                   \
+    PFHE_ENTRY(P##_pack_keyswitch, (const pfhe_fft *fft, size_t glwe_dimension, const CW *lwe_in, size_t len_in,         \
+                size_t in_dimension, size_t count, const CW *pksk, size_t len_pksk, uint32_t log_basis,                  \
+                size_t decompose_length, CW *glwe_out, size_t len_out),                                                  \
+               pack_keyswitch<W>(Form::kHost, fft, glwe_dimension, (const W *)lwe_in, len_in, in_dimension, count,       \
+                                 (const W *)pksk, len_pksk, log_basis, decompose_length, (W *)glwe_out, len_out,         \
+                                 nullptr))                                                                               \
+    PFHE_ENTRY(P##_pksk_generate_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *key_in_dev,                 \
+                size_t in_dimension, const CW *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,                    \
+                size_t decompose_length, CW *pksk_dev, size_t len_pksk, void *stream),                                   \
+               pksk_generate_dev<W>(fft, glwe_dimension, (const W *)key_in_dev, in_dimension, (const W *)glwe_key_dev,   \
+                                    len_glwe_key, log_basis, decompose_length, (W *)pksk_dev, len_pksk,                  \
+                                    (hipStream_t)stream))                                                                \
+    PFHE_ENTRY(P##_sample_extract_first_few_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *glwe_dev,        \
+                size_t len_glwe, size_t count, CW *multi_dev, size_t len_multi, void *stream),                           \
+               first_few<W>(Form::kDevice, fft, glwe_dimension, (const W *)glwe_dev, len_glwe, count, (W *)multi_dev,    \
+                            len_multi, (hipStream_t)stream))                                                             \
+    PFHE_ENTRY(P##_sample_extract_first_few, (const pfhe_fft *fft, size_t glwe_dimension, const CW *glwe,                \
+                size_t len_glwe, size_t count, CW *multi, size_t len_multi),                                             \
+               first_few<W>(Form::kHost, fft, glwe_dimension, (const W *)glwe, len_glwe, count, (W *)multi, len_multi,   \
+                            nullptr))                                                                                    \
+    PFHE_ENTRY(P##_multimsg_extract_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *multi_dev,               \
+                size_t len_multi, size_t count, CW *lwe_dev, size_t len_lwe, void *stream),                              \
+               multimsg_extract<W>(Form::kDevice, fft, glwe_dimension, (const W *)multi_dev, len_multi, count,           \
+                                   (W *)lwe_dev, len_lwe, (hipStream_t)stream))                                          \
+    PFHE_ENTRY(P##_multimsg_extract, (const pfhe_fft *fft, size_t glwe_dimension, const CW *multi, size_t len_multi,     \
+                size_t count, CW *lwe, size_t len_lwe),                                                                  \
+               multimsg_extract<W>(Form::kHost, fft, glwe_dimension, (const W *)multi, len_multi, count, (W *)lwe,       \
+                                   len_lwe, nullptr))
+
 extern "C" {
 
-int pfhe_tfhe_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in_dev, size_t len_in,
-                                 size_t in_dimension, size_t count, const uint64_t *pksk_dev, size_t len_pksk,
-                                 uint32_t log_basis, size_t decompose_length, uint64_t *glwe_out_dev, size_t len_out,
-                                 void *stream) {
-    PFHE_GUARD_BEGIN
-    return pack_keyswitch<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)lwe_in_dev, len_in, in_dimension, count,
-                               (const u64 *)pksk_dev, len_pksk, log_basis, decompose_length, (u64 *)glwe_out_dev, len_out,
-                               (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_pack_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_in, size_t len_in,
-                             size_t in_dimension, size_t count, const uint64_t *pksk, size_t len_pksk, uint32_t log_basis,
-                             size_t decompose_length, uint64_t *glwe_out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return pack_keyswitch<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)lwe_in, len_in, in_dimension, count,
-                               (const u64 *)pksk, len_pksk, log_basis, decompose_length, (u64 *)glwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_pack_keyswitch_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in_dev, size_t len_in,
-                                   size_t in_dimension, size_t count, const uint32_t *pksk_dev, size_t len_pksk,
-                                   uint32_t log_basis, size_t decompose_length, uint32_t *glwe_out_dev, size_t len_out,
-                                   void *stream) {
-    PFHE_GUARD_BEGIN
-    return pack_keyswitch<u32>(Form::kDevice, fft, glwe_dimension, lwe_in_dev, len_in, in_dimension, count, pksk_dev, len_pksk,
-                               log_basis, decompose_length, glwe_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_pack_keyswitch(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_in, size_t len_in,
-                               size_t in_dimension, size_t count, const uint32_t *pksk, size_t len_pksk, uint32_t log_basis,
-                               size_t decompose_length, uint32_t *glwe_out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return pack_keyswitch<u32>(Form::kHost, fft, glwe_dimension, lwe_in, len_in, in_dimension, count, pksk, len_pksk, log_basis,
-                               decompose_length, glwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_pksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *key_in_dev, size_t in_dimension,
-                                const uint64_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis, size_t decompose_length,
-                                uint64_t *pksk_dev, size_t len_pksk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return pksk_generate_dev<u64>(fft, glwe_dimension, (const u64 *)key_in_dev, in_dimension, (const u64 *)glwe_key_dev,
-                                  len_glwe_key, log_basis, decompose_length, (u64 *)pksk_dev, len_pksk, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_pksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *key_in_dev, size_t in_dimension,
-                                  const uint32_t *glwe_key_dev, size_t len_glwe_key, uint32_t log_basis,
-                                  size_t decompose_length, uint32_t *pksk_dev, size_t len_pksk, void *stream) {
-    PFHE_GUARD_BEGIN
-    return pksk_generate_dev<u32>(fft, glwe_dimension, key_in_dev, in_dimension, glwe_key_dev, len_glwe_key, log_basis,
-                                  decompose_length, pksk_dev, len_pksk, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_sample_extract_first_few_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe_dev, size_t len_glwe,
-                                           size_t count, uint64_t *multi_dev, size_t len_multi, void *stream) {
-    PFHE_GUARD_BEGIN
-    return first_few<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)glwe_dev, len_glwe, count, (u64 *)multi_dev, len_multi,
-                          (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_sample_extract_first_few(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *glwe, size_t len_glwe,
-                                       size_t count, uint64_t *multi, size_t len_multi) {
-    PFHE_GUARD_BEGIN
-    return first_few<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)glwe, len_glwe, count, (u64 *)multi, len_multi, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_sample_extract_first_few_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe_dev,
-                                             size_t len_glwe, size_t count, uint32_t *multi_dev, size_t len_multi,
-                                             void *stream) {
-    PFHE_GUARD_BEGIN
-    return first_few<u32>(Form::kDevice, fft, glwe_dimension, glwe_dev, len_glwe, count, multi_dev, len_multi,
-                          (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_sample_extract_first_few(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *glwe, size_t len_glwe,
-                                         size_t count, uint32_t *multi, size_t len_multi) {
-    PFHE_GUARD_BEGIN
-    return first_few<u32>(Form::kHost, fft, glwe_dimension, glwe, len_glwe, count, multi, len_multi, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe_multimsg_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *multi_dev, size_t len_multi,
-                                   size_t count, uint64_t *lwe_dev, size_t len_lwe, void *stream) {
-    PFHE_GUARD_BEGIN
-    return multimsg_extract<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)multi_dev, len_multi, count, (u64 *)lwe_dev,
-                                 len_lwe, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_multimsg_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *multi, size_t len_multi, size_t count,
-                               uint64_t *lwe, size_t len_lwe) {
-    PFHE_GUARD_BEGIN
-    return multimsg_extract<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)multi, len_multi, count, (u64 *)lwe, len_lwe,
-                                 nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_multimsg_extract_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *multi_dev, size_t len_multi,
-                                     size_t count, uint32_t *lwe_dev, size_t len_lwe, void *stream) {
-    PFHE_GUARD_BEGIN
-    return multimsg_extract<u32>(Form::kDevice, fft, glwe_dimension, multi_dev, len_multi, count, lwe_dev, len_lwe,
-                                 (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_multimsg_extract(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *multi, size_t len_multi,
-                                 size_t count, uint32_t *lwe, size_t len_lwe) {
-    PFHE_GUARD_BEGIN
-    return multimsg_extract<u32>(Form::kHost, fft, glwe_dimension, multi, len_multi, count, lwe, len_lwe, nullptr);
-    PFHE_GUARD_END
-}
+PFHE_PACK_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_PACK_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_PACK_FAMILY
 
 }  // extern "C"

@@ -342,67 +342,28 @@ int packfft_keyswitch(Form form, TfhePackFftCore<W> *p, const W *lwe_in, size_t 
 
 }  // namespace
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_PACKFFT_FAMILY(P, CW, W)                                                                                  \
+    PFHE_ENTRY(P##_packfft_plan_create, (const pfhe_fft *fft, size_t glwe_dimension, size_t in_dimension,              \
+                uint32_t log_basis, size_t decompose_length, size_t chunk, P##_packfft_plan **out),                    \
+               packfft_plan_create<W>(fft, glwe_dimension, in_dimension, log_basis, decompose_length, chunk, out))     \
+    PFHE_HANDLE_TRIO(P##_packfft_plan, P##_packfft_plan, h->bufs.bytes())                                              \
+    PFHE_ENTRY(P##_packfft_key_dev, (P##_packfft_plan *plan, const CW *pksk_dev, size_t len_pksk, double *fkey_dev,    \
+                size_t len_fkey, void *stream),                                                                        \
+               packfft_key_dev<W>(plan, (const W *)pksk_dev, len_pksk, fkey_dev, len_fkey, (hipStream_t)stream))       \
+    PFHE_ENTRY(P##_pack_keyswitch_fft_dev, (P##_packfft_plan *plan, const CW *lwe_in_dev, size_t len_in, size_t count, \
+                const double *fkey_dev, size_t len_fkey, CW *glwe_out_dev, size_t len_out, void *stream),              \
+               packfft_keyswitch<W>(Form::kDevice, plan, (const W *)lwe_in_dev, len_in, count, fkey_dev, len_fkey,     \
+                                    (W *)glwe_out_dev, len_out, (hipStream_t)stream))                                  \
+    PFHE_ENTRY(P##_pack_keyswitch_fft, (P##_packfft_plan *plan, const CW *lwe_in, size_t len_in, size_t count,         \
+                const double *fkey, size_t len_fkey, CW *glwe_out, size_t len_out),                                    \
+               packfft_keyswitch<W>(Form::kHost, plan, (const W *)lwe_in, len_in, count, fkey, len_fkey,               \
+                                    (W *)glwe_out, len_out, nullptr))
+
 extern "C" {
 
-int pfhe_tfhe_packfft_plan_create(const pfhe_fft *fft, size_t glwe_dimension, size_t in_dimension, uint32_t log_basis,
-                                  size_t decompose_length, size_t chunk, pfhe_tfhe_packfft_plan **out) {
-    PFHE_GUARD_BEGIN
-    return packfft_plan_create<u64>(fft, glwe_dimension, in_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_packfft_plan_destroy(pfhe_tfhe_packfft_plan *plan) { delete plan; }
-int pfhe_tfhe_packfft_plan_in_use(const pfhe_tfhe_packfft_plan *plan) { return plan ? plan->guard.in_use() : 0; }
-size_t pfhe_tfhe_packfft_plan_scratch_bytes(const pfhe_tfhe_packfft_plan *plan) { return plan ? plan->bufs.bytes() : 0; }
-int pfhe_tfhe_packfft_key_dev(pfhe_tfhe_packfft_plan *plan, const uint64_t *pksk_dev, size_t len_pksk, double *fkey_dev,
-                              size_t len_fkey, void *stream) {
-    PFHE_GUARD_BEGIN
-    return packfft_key_dev<u64>(plan, (const u64 *)pksk_dev, len_pksk, fkey_dev, len_fkey, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_pack_keyswitch_fft_dev(pfhe_tfhe_packfft_plan *plan, const uint64_t *lwe_in_dev, size_t len_in, size_t count,
-                                     const double *fkey_dev, size_t len_fkey, uint64_t *glwe_out_dev, size_t len_out,
-                                     void *stream) {
-    PFHE_GUARD_BEGIN
-    return packfft_keyswitch<u64>(Form::kDevice, plan, (const u64 *)lwe_in_dev, len_in, count, fkey_dev, len_fkey,
-                                  (u64 *)glwe_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_pack_keyswitch_fft(pfhe_tfhe_packfft_plan *plan, const uint64_t *lwe_in, size_t len_in, size_t count,
-                                 const double *fkey, size_t len_fkey, uint64_t *glwe_out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return packfft_keyswitch<u64>(Form::kHost, plan, (const u64 *)lwe_in, len_in, count, fkey, len_fkey, (u64 *)glwe_out,
-                                  len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_packfft_plan_create(const pfhe_fft *fft, size_t glwe_dimension, size_t in_dimension, uint32_t log_basis,
-                                    size_t decompose_length, size_t chunk, pfhe_tfhe32_packfft_plan **out) {
-    PFHE_GUARD_BEGIN
-    return packfft_plan_create<u32>(fft, glwe_dimension, in_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_packfft_plan_destroy(pfhe_tfhe32_packfft_plan *plan) { delete plan; }
-int pfhe_tfhe32_packfft_plan_in_use(const pfhe_tfhe32_packfft_plan *plan) { return plan ? plan->guard.in_use() : 0; }
-size_t pfhe_tfhe32_packfft_plan_scratch_bytes(const pfhe_tfhe32_packfft_plan *plan) { return plan ? plan->bufs.bytes() : 0; }
-int pfhe_tfhe32_packfft_key_dev(pfhe_tfhe32_packfft_plan *plan, const uint32_t *pksk_dev, size_t len_pksk, double *fkey_dev,
-                                size_t len_fkey, void *stream) {
-    PFHE_GUARD_BEGIN
-    return packfft_key_dev<u32>(plan, pksk_dev, len_pksk, fkey_dev, len_fkey, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_pack_keyswitch_fft_dev(pfhe_tfhe32_packfft_plan *plan, const uint32_t *lwe_in_dev, size_t len_in, size_t count,
-                                       const double *fkey_dev, size_t len_fkey, uint32_t *glwe_out_dev, size_t len_out,
-                                       void *stream) {
-    PFHE_GUARD_BEGIN
-    return packfft_keyswitch<u32>(Form::kDevice, plan, lwe_in_dev, len_in, count, fkey_dev, len_fkey, glwe_out_dev, len_out,
-                                  (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_pack_keyswitch_fft(pfhe_tfhe32_packfft_plan *plan, const uint32_t *lwe_in, size_t len_in, size_t count,
-                                   const double *fkey, size_t len_fkey, uint32_t *glwe_out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return packfft_keyswitch<u32>(Form::kHost, plan, lwe_in, len_in, count, fkey, len_fkey, glwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
+PFHE_PACKFFT_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_PACKFFT_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_PACKFFT_FAMILY
 
 }  // extern "C"

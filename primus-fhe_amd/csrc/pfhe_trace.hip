@@ -440,121 +440,45 @@ size_t trace_scratch(const H *h) {
 
 }  // namespace
 
+// The entry points of one word width.  P: pfhe_tfhe / pfhe_tfhe32; CW / W: the word as pfhe.h and as the library spell it.
+#define PFHE_TRACE_FAMILY(P, CW, W)                                                                                      \
+    PFHE_ENTRY(P##_glwe_trace_create, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                   \
+                size_t decompose_length, size_t chunk, P##_glwe_trace_handle **out),                                     \
+               trace_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, out))                            \
+    PFHE_HANDLE_TRIO(P##_glwe_trace, P##_glwe_trace_handle, trace_scratch(h))                                            \
+    PFHE_ENTRY(P##_glwe_automorphism_dev, (P##_glwe_trace_handle *h, const CW *in_dev, size_t len_in,                    \
+                const double *key_dev, size_t len_key, uint32_t t, CW *out_dev, size_t len_out, void *stream),           \
+               automorphism<W>(Form::kDevice, h, (const W *)in_dev, len_in, key_dev, len_key, t, (W *)out_dev, len_out,  \
+                               (hipStream_t)stream))                                                                     \
+    PFHE_ENTRY(P##_glwe_automorphism, (P##_glwe_trace_handle *h, const CW *in, size_t len_in, const double *key,         \
+                size_t len_key, uint32_t t, CW *out, size_t len_out),                                                    \
+               automorphism<W>(Form::kHost, h, (const W *)in, len_in, key, len_key, t, (W *)out, len_out, nullptr))      \
+    PFHE_ENTRY(P##_glwe_trace_dev, (P##_glwe_trace_handle *h, const CW *in_dev, size_t len_in, const double *keys_dev,   \
+                size_t len_keys, size_t steps, CW *out_dev, size_t len_out, void *stream),                               \
+               trace<W>(Form::kDevice, h, (const W *)in_dev, len_in, keys_dev, len_keys, steps, (W *)out_dev, len_out,   \
+                        (hipStream_t)stream))                                                                            \
+    PFHE_ENTRY(P##_glwe_trace, (P##_glwe_trace_handle *h, const CW *in, size_t len_in, const double *keys,               \
+                size_t len_keys, size_t steps, CW *out, size_t len_out),                                                 \
+               trace<W>(Form::kHost, h, (const W *)in, len_in, keys, len_keys, steps, (W *)out, len_out, nullptr))       \
+    PFHE_ENTRY(P##_gksk_generate_dev, (const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,                   \
+                size_t decompose_length, const CW *key_in_dev, size_t len_key_in, const CW *key_out_dev,                 \
+                size_t len_key_out, const uint32_t *exponents, size_t count, CW *gksk_torus_dev, size_t len_gksk,        \
+                double *gksk_out_dev, size_t len_out, void *stream),                                                     \
+               gksk_generate_dev<W>(fft, glwe_dimension, log_basis, decompose_length, (const W *)key_in_dev, len_key_in, \
+                                    (const W *)key_out_dev, len_key_out, exponents, count, (W *)gksk_torus_dev,          \
+                                    len_gksk, gksk_out_dev, len_out, (hipStream_t)stream))                               \
+    PFHE_ENTRY(P##_lwe_embed_dev, (const pfhe_fft *fft, size_t glwe_dimension, const CW *lwe_dev, size_t len_lwe,        \
+                CW *glwe_out_dev, size_t len_out, void *stream),                                                         \
+               lwe_embed<W>(Form::kDevice, fft, glwe_dimension, (const W *)lwe_dev, len_lwe, (W *)glwe_out_dev, len_out, \
+                            (hipStream_t)stream))                                                                        \
+    PFHE_ENTRY(P##_lwe_embed, (const pfhe_fft *fft, size_t glwe_dimension, const CW *lwe, size_t len_lwe,                \
+                CW *glwe_out, size_t len_out),                                                                           \
+               lwe_embed<W>(Form::kHost, fft, glwe_dimension, (const W *)lwe, len_lwe, (W *)glwe_out, len_out, nullptr))
+
 extern "C" {
 
-int pfhe_tfhe_glwe_trace_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                size_t chunk, pfhe_tfhe_glwe_trace_handle **out) {
-    PFHE_GUARD_BEGIN
-    return trace_create<u64>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe_glwe_trace_destroy(pfhe_tfhe_glwe_trace_handle *h) { delete h; }
-int pfhe_tfhe_glwe_trace_in_use(const pfhe_tfhe_glwe_trace_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe_glwe_trace_scratch_bytes(const pfhe_tfhe_glwe_trace_handle *h) { return trace_scratch(h); }
-int pfhe_tfhe_glwe_automorphism_dev(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in_dev, size_t len_in, const double *key_dev,
-                                    size_t len_key, uint32_t t, uint64_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return automorphism<u64>(Form::kDevice, h, (const u64 *)in_dev, len_in, key_dev, len_key, t, (u64 *)out_dev, len_out,
-                             (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_glwe_automorphism(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in, size_t len_in, const double *key, size_t len_key,
-                                uint32_t t, uint64_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return automorphism<u64>(Form::kHost, h, (const u64 *)in, len_in, key, len_key, t, (u64 *)out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_glwe_trace_dev(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in_dev, size_t len_in, const double *keys_dev,
-                             size_t len_keys, size_t steps, uint64_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return trace<u64>(Form::kDevice, h, (const u64 *)in_dev, len_in, keys_dev, len_keys, steps, (u64 *)out_dev, len_out,
-                      (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_glwe_trace(pfhe_tfhe_glwe_trace_handle *h, const uint64_t *in, size_t len_in, const double *keys, size_t len_keys,
-                         size_t steps, uint64_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return trace<u64>(Form::kHost, h, (const u64 *)in, len_in, keys, len_keys, steps, (u64 *)out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_gksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                const uint64_t *key_in_dev, size_t len_key_in, const uint64_t *key_out_dev, size_t len_key_out,
-                                const uint32_t *exponents, size_t count, uint64_t *gksk_torus_dev, size_t len_gksk,
-                                double *gksk_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return gksk_generate_dev<u64>(fft, glwe_dimension, log_basis, decompose_length, (const u64 *)key_in_dev, len_key_in,
-                                  (const u64 *)key_out_dev, len_key_out, exponents, count, (u64 *)gksk_torus_dev, len_gksk,
-                                  gksk_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_lwe_embed_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe_dev, size_t len_lwe,
-                            uint64_t *glwe_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return lwe_embed<u64>(Form::kDevice, fft, glwe_dimension, (const u64 *)lwe_dev, len_lwe, (u64 *)glwe_out_dev, len_out,
-                          (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe_lwe_embed(const pfhe_fft *fft, size_t glwe_dimension, const uint64_t *lwe, size_t len_lwe, uint64_t *glwe_out,
-                        size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return lwe_embed<u64>(Form::kHost, fft, glwe_dimension, (const u64 *)lwe, len_lwe, (u64 *)glwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-
-int pfhe_tfhe32_glwe_trace_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                  size_t chunk, pfhe_tfhe32_glwe_trace_handle **out) {
-    PFHE_GUARD_BEGIN
-    return trace_create<u32>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
-    PFHE_GUARD_END
-}
-void pfhe_tfhe32_glwe_trace_destroy(pfhe_tfhe32_glwe_trace_handle *h) { delete h; }
-int pfhe_tfhe32_glwe_trace_in_use(const pfhe_tfhe32_glwe_trace_handle *h) { return h ? h->guard.in_use() : 0; }
-size_t pfhe_tfhe32_glwe_trace_scratch_bytes(const pfhe_tfhe32_glwe_trace_handle *h) { return trace_scratch(h); }
-int pfhe_tfhe32_glwe_automorphism_dev(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in_dev, size_t len_in, const double *key_dev,
-                                      size_t len_key, uint32_t t, uint32_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return automorphism<u32>(Form::kDevice, h, in_dev, len_in, key_dev, len_key, t, out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_glwe_automorphism(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in, size_t len_in, const double *key,
-                                  size_t len_key, uint32_t t, uint32_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return automorphism<u32>(Form::kHost, h, in, len_in, key, len_key, t, out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_glwe_trace_dev(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in_dev, size_t len_in, const double *keys_dev,
-                               size_t len_keys, size_t steps, uint32_t *out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return trace<u32>(Form::kDevice, h, in_dev, len_in, keys_dev, len_keys, steps, out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_glwe_trace(pfhe_tfhe32_glwe_trace_handle *h, const uint32_t *in, size_t len_in, const double *keys, size_t len_keys,
-                           size_t steps, uint32_t *out, size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return trace<u32>(Form::kHost, h, in, len_in, keys, len_keys, steps, out, len_out, nullptr);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_gksk_generate_dev(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
-                                  const uint32_t *key_in_dev, size_t len_key_in, const uint32_t *key_out_dev, size_t len_key_out,
-                                  const uint32_t *exponents, size_t count, uint32_t *gksk_torus_dev, size_t len_gksk,
-                                  double *gksk_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return gksk_generate_dev<u32>(fft, glwe_dimension, log_basis, decompose_length, key_in_dev, len_key_in, key_out_dev,
-                                  len_key_out, exponents, count, gksk_torus_dev, len_gksk, gksk_out_dev, len_out,
-                                  (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_lwe_embed_dev(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe_dev, size_t len_lwe,
-                              uint32_t *glwe_out_dev, size_t len_out, void *stream) {
-    PFHE_GUARD_BEGIN
-    return lwe_embed<u32>(Form::kDevice, fft, glwe_dimension, lwe_dev, len_lwe, glwe_out_dev, len_out, (hipStream_t)stream);
-    PFHE_GUARD_END
-}
-int pfhe_tfhe32_lwe_embed(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe, size_t len_lwe, uint32_t *glwe_out,
-                          size_t len_out) {
-    PFHE_GUARD_BEGIN
-    return lwe_embed<u32>(Form::kHost, fft, glwe_dimension, lwe, len_lwe, glwe_out, len_out, nullptr);
-    PFHE_GUARD_END
-}
+PFHE_TRACE_FAMILY(pfhe_tfhe, uint64_t, u64)
+PFHE_TRACE_FAMILY(pfhe_tfhe32, uint32_t, u32)
+#undef PFHE_TRACE_FAMILY
 
 }  // extern "C"

@@ -174,6 +174,76 @@ def test_library_exports_exactly_the_declared_symbols(header):
     assert exported == set(header), {"not exported": sorted(set(header) - exported), "not declared": sorted(exported - set(header))}
 
 
+WIDTH_PAIRS = ((r"pfhe_tfhe_", "pfhe_tfhe32_"), (r"pfhe_extprod_", "pfhe_extprod32_"), (r"pfhe_blindrot_", "pfhe_blindrot32_"),
+               (r"pfhe_fft_(forward|inverse)_torus_", r"pfhe_fft_\1_torus32_"))
+SINGLE_WIDTH = {"pfhe_extprod_plan_debug_hold", "pfhe_extprod_profile_dev", "pfhe_tfhe_mb_combine_key_dev"}
+
+
+def header_signatures(text: str):
+    """{name: (return type, [parameter types])} with the types as pfhe.h spells them (one space between tokens, none
+    before a `*`), where header_prototypes keeps only their width classes"""
+    body = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = re.sub(r"^\s*#.*$", "", body, flags=re.M).replace('extern "C" {', "")
+
+    def norm(t):
+        return re.sub(r"\s*\*\s*", " *", " ".join(t.split())).strip()
+
+    out = {}
+    for m in re.finditer(r"([A-Za-z_][\w\s\*]*?)\b(pfhe_\w+)\s*\(([^;{}]*)\)\s*;", body):
+        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if ret.startswith("typedef"):
+            continue
+        params = [] if args in ("", "void") else [norm(re.match(r"(.*?)(\w+)$", a.strip()).group(1)) for a in args.split(",")]
+        out[name] = (norm(ret), params)
+    return out
+
+
+def test_every_width_pair_has_one_signature_up_to_the_word():
+    """The torus and RNS-product entry points are defined once, in a family macro expanded per word width, while pfhe.h
+    stays hand-written: the u32 prototype of each pair must be the u64 one with uint64_t -> uint32_t and every handle
+    type -> its 32 name, only SINGLE_WIDTH may lack a twin, and no `32` name may lack its u64 master."""
+    text = open(HEADER).read()
+    sigs = header_signatures(text)
+    assert set(sigs) == set(header_prototypes(text))
+    handles = set(re.findall(r"typedef struct (pfhe_\w+) \1;", text))
+
+    def twin_name(name):
+        for pat, rep in WIDTH_PAIRS:
+            if re.match(pat, name):
+                return re.sub("^" + pat, rep, name)
+        return None
+
+    def twin_type(t):
+        def handle32(m):
+            h = m.group(0)
+            if h == "pfhe_fft":                  # the transform tables have no width
+                return h
+            for pat, rep in WIDTH_PAIRS[:3]:     # pfhe_tfhe_plan -> pfhe_tfhe32_plan, ...
+                if re.match(pat, h):
+                    return re.sub("^" + pat, rep, h)
+            return h + "32"                      # pfhe_dcrt -> pfhe_dcrt32, pfhe_rns, pfhe_basis
+        return re.sub(r"\bpfhe_\w+", handle32, t.replace("uint64_t", "uint32_t"))
+
+    pairs, singles = 0, set()
+    for name, (ret, params) in sigs.items():
+        other = twin_name(name)
+        if other is None:
+            continue
+        if other not in sigs:
+            singles.add(name)
+            continue
+        pairs += 1
+        assert (twin_type(ret), [twin_type(p) for p in params]) == sigs[other], (name, sigs[name], other, sigs[other])
+        for p in params + sigs[other][1]:        # every handle type a pair names is one pfhe.h declares
+            for h in re.findall(r"\bpfhe_\w+", p):
+                assert h in handles, (name, h)
+    assert singles == SINGLE_WIDTH, sorted(singles ^ SINGLE_WIDTH)
+    assert pairs == 111
+    masters = {twin_name(n) for n in sigs if twin_name(n)}
+    orphans = {n for n in sigs if re.match(r"pfhe_(tfhe|extprod|blindrot)32_|pfhe_fft_(forward|inverse)_torus32_", n)} - masters
+    assert not orphans, sorted(orphans)
+
+
 def impl_methods(text: str, trait: str):
     """{implementing type: set of fn names} for every `impl <trait> for X { ... }` block of lib.rs"""
     out = {}
