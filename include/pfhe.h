@@ -1735,6 +1735,66 @@ int pfhe_tfhe32_lut_eval_dev(pfhe_tfhe32_lut_handle *h, const uint32_t *table_de
 int pfhe_tfhe32_lut_eval(pfhe_tfhe32_lut_handle *h, const uint32_t *table, size_t len_table, const double *selectors,
                          size_t len_selectors, size_t extract, uint32_t *out, size_t len_out);
 
+/* ---- bit extraction: an LWE ciphertext of a multi-bit message into one LWE ciphertext per bit (u64: no suffix, u32: 32) ----
+ * The reference has none; the rule is this project's own, built from the rules of the LWE key switch, the
+ * modulus switch, the accumulator of the circuit bootstrap and the classic blind rotation, which it leaves bit for bit what
+ * they are.  It closes the loop of the look-up above: its outputs are what pfhe_tfhe*_cbs_dev takes, in the order in which
+ * pfhe_tfhe*_lut_eval_dev expects the selectors.  The family has a prefix of its own, pfhe_bitext_ / pfhe_bitext32_ (as
+ * pfhe_blindrot_ / pfhe_blindrot32_ on the RNS side), and the handle types are pfhe_bitext / pfhe_bitext32; the u32 prototype
+ * of every pair is the u64 one with uint64_t -> uint32_t and the handle type -> its 32 name.
+ *
+ * lwe_in: batch ciphertexts of k*N + 1 words under the extracted GLWE key (what pfhe_tfhe*_sample_extract_dev and
+ * pfhe_tfhe*_lut_eval_dev with extract >= 1 write), phase b - <a,s> = m*2^delta_log + e.  bits_out: batch*bits ciphertexts of
+ * n + 1 words under the LWE key, bit i of input e (bit 0 the least significant) at index e*bits + i, phase
+ * m_i*2^(BITS-1) plus noise.  bsk: the n Fourier GGSW keys of pfhe_tfhe*_bootstrap_dev; ksk: the k*N*ks_ell*(n+1) words of
+ * pfhe_tfhe*_generate_ksk_dev from the extracted key to the LWE key.  1 <= delta_log, 1 <= bits, delta_log + bits <= BITS;
+ * message bits at or above delta_log + bits are shifted out.  With c_0 = lwe_in, for i = 0 .. bits-1, modulo 2^BITS:
+ *   bits_out[e*bits + i] = keyswitch(c_i << (BITS - 1 - delta_log - i))     every word shifted as a wrapping word, then the
+ *                                                                           rule of pfhe_tfhe*_keyswitch_dev word for word;
+ *   unless i = bits-1:  (exps, neg_b) = pfhe_tfhe*_modswitch_dev of that output with 2^(BITS-2) added to its body,
+ *                       ACC = X^{neg_b} TV_i, TV_i = (0, .., 0, -2^(delta_log+i-1) on every coefficient),
+ *                       ACC rotated by pfhe_tfhe*_blind_rotate_dev over the n keys,
+ *                       c_{i+1} = c_i - (pfhe_tfhe*_sample_extract_dev of ACC at index 0, 2^(delta_log+i-1) added to its body).
+ * The words equal, one for one, those of that composition of public calls.  lwe_in is read only.
+ *
+ * create, everything before the device first and in this order: a null out pointer; the product plan's checks in their order
+ * (ApproxSignedBasis::new's assert!s, PFHE_ERR_UNSUPPORTED for glwe_dimension above 64, PFHE_ERR_BAD_ARGUMENT for a null
+ * table); PFHE_ERR_BAD_ARGUMENT for glwe_dimension 0 or lwe_dimension outside 1..2^31-2; the key-switch basis's assert!s;
+ * then the classic rotation's create.  The handle borrows `fft` and allocates everything here, for `chunk` inputs (0: the
+ * rotation's default, capped at about 256 MiB of accumulators).  A call only queues work on `stream` (no allocation, no
+ * host synchronisation), so it can be captured into a HIP graph; a batch larger than the chunk runs chunk by chunk, all
+ * bits of a chunk first.  One holder at a time (PFHE_ERR_BUSY).  A call refuses, in this order: a null handle, a second
+ * holder, PFHE_ERR_BAD_ARGUMENT for delta_log = 0, bits = 0 or delta_log + bits above BITS, null pointers (host form),
+ * PFHE_ERR_BAD_LENGTH for lwe_in no multiple of k*N + 1, bits_out other than batch*bits*(n+1), bsk other than n keys or ksk
+ * other than k*N*ks_ell*(n+1) words, (the empty batch is a no-op,) null pointers, a pointer not aligned to 16 bytes, an
+ * output that overlaps an input (device form), the device. */
+typedef struct pfhe_bitext pfhe_bitext;
+typedef struct pfhe_bitext32 pfhe_bitext32;
+int pfhe_bitext_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                            size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, size_t chunk,
+                            pfhe_bitext **out);
+void pfhe_bitext_destroy(pfhe_bitext *h);
+int pfhe_bitext_in_use(const pfhe_bitext *h);  /* 1 while some thread is inside a call on it */
+size_t pfhe_bitext_scratch_bytes(const pfhe_bitext *h);  /* the owned rotation's included */
+int pfhe_bitext_extract_bits_dev(pfhe_bitext *h, const uint64_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                               size_t len_bsk, const uint64_t *ksk_dev, size_t len_ksk, uint32_t delta_log, uint32_t bits,
+                               uint64_t *bits_out_dev, size_t len_out, void *stream);
+int pfhe_bitext_extract_bits(pfhe_bitext *h, const uint64_t *lwe_in, size_t len_in, const double *bsk, size_t len_bsk,
+                           const uint64_t *ksk, size_t len_ksk, uint32_t delta_log, uint32_t bits, uint64_t *bits_out,
+                           size_t len_out);
+int pfhe_bitext32_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                              size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, size_t chunk,
+                              pfhe_bitext32 **out);
+void pfhe_bitext32_destroy(pfhe_bitext32 *h);
+int pfhe_bitext32_in_use(const pfhe_bitext32 *h);
+size_t pfhe_bitext32_scratch_bytes(const pfhe_bitext32 *h);
+int pfhe_bitext32_extract_bits_dev(pfhe_bitext32 *h, const uint32_t *lwe_in_dev, size_t len_in, const double *bsk_dev,
+                                 size_t len_bsk, const uint32_t *ksk_dev, size_t len_ksk, uint32_t delta_log, uint32_t bits,
+                                 uint32_t *bits_out_dev, size_t len_out, void *stream);
+int pfhe_bitext32_extract_bits(pfhe_bitext32 *h, const uint32_t *lwe_in, size_t len_in, const double *bsk,
+                             size_t len_bsk, const uint32_t *ksk, size_t len_ksk, uint32_t delta_log, uint32_t bits,
+                             uint32_t *bits_out, size_t len_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,6 +293,8 @@ struct Fns;
         using TfheCmuxTree = PFHE_TFHE_PLAN(S, cmux_tree_handle, cmux_tree);                                   \
         using TfheGlweTrace = PFHE_TFHE_PLAN(S, glwe_trace_handle, glwe_trace);                                \
         using TfheLut = PFHE_TFHE_PLAN(S, lut_handle, lut);                                                    \
+        using TfheBitext = Plan<pfhe_bitext##S, pfhe_bitext##S##_destroy, pfhe_bitext##S##_in_use,             \
+                                pfhe_bitext##S##_scratch_bytes>;                                       \
         PFHE_FN(rns, S, create);                                                                               \
         PFHE_FN(rns, S, moduli_count);                                                                         \
         PFHE_FN(rns, S, big_uint_value_len);                                                                   \
@@ -388,6 +390,9 @@ struct Fns;
         PFHE_FN(tfhe, S, rotate_by_bits_dev);                                                                  \
         PFHE_FN(tfhe, S, lut_eval);                                                                            \
         PFHE_FN(tfhe, S, lut_eval_dev);                                                                        \
+        PFHE_FN(bitext, S, create);                                                                            \
+        PFHE_FN(bitext, S, extract_bits);                                                                      \
+        PFHE_FN(bitext, S, extract_bits_dev);                                                                  \
     }
 PFHE_WORD_TRAITS(uint64_t, , U64DcrtTable);
 PFHE_WORD_TRAITS(uint32_t, 32, U32DcrtTable);
@@ -1085,5 +1090,34 @@ class TfheLutT : public detail::Fns<W>::TfheLut {
 };
 using TfheLut = TfheLutT<uint64_t>;
 using TfheLut32 = TfheLutT<uint32_t>;
+
+// Bit extraction: batch LWE ciphertexts of k*N + 1 words with phase m*2^delta_log + e become batch*bits LWE ciphertexts of
+// lwe_dimension + 1 words, bit i of input e at e*bits + i with phase m_i*2^(BITS-1) plus noise: per bit the key switch of the
+// running ciphertext shifted left and, unless it is the last, a blind rotation that clears the bit
+// (pfhe_bitext{,32}_*).  Owns a classic rotation and the buffers of `chunk` inputs; one holder at a
+// time.
+template <class W>
+class TfheBitExtractT : public detail::Fns<W>::TfheBitext {
+    using F = detail::Fns<W>;
+
+  public:
+    TfheBitExtractT(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                    size_t lwe_dimension, uint32_t ks_log_basis, size_t ks_decompose_length, size_t chunk = 0) {
+        check(F::bitext_create(fft.handle(), glwe_dimension, log_basis, decompose_length, lwe_dimension, ks_log_basis,
+                                    ks_decompose_length, chunk, &this->h_));
+    }
+    void extract_bits(const W *lwe_in, size_t len_in, const double *bsk, size_t len_bsk, const W *ksk, size_t len_ksk,
+                      uint32_t delta_log, uint32_t bits, W *bits_out, size_t len_out) {
+        check(F::bitext_extract_bits(this->h_, lwe_in, len_in, bsk, len_bsk, ksk, len_ksk, delta_log, bits, bits_out, len_out));
+    }
+    void extract_bits_dev(const W *lwe_in_dev, size_t len_in, const double *bsk_dev, size_t len_bsk, const W *ksk_dev,
+                          size_t len_ksk, uint32_t delta_log, uint32_t bits, W *bits_out_dev, size_t len_out,
+                          void *stream = nullptr) {
+        check(F::bitext_extract_bits_dev(this->h_, lwe_in_dev, len_in, bsk_dev, len_bsk, ksk_dev, len_ksk, delta_log, bits,
+                                       bits_out_dev, len_out, stream));
+    }
+};
+using TfheBitExtract = TfheBitExtractT<uint64_t>;
+using TfheBitExtract32 = TfheBitExtractT<uint32_t>;
 
 }  // namespace pfhe

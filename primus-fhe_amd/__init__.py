@@ -29,7 +29,8 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    tfhe_cmux_tree_dev, TfheGlweTraceContext, glwe_automorphism, glwe_automorphism_dev, glwe_keyswitch,
                    glwe_keyswitch_dev, glwe_trace, glwe_trace_dev, tfhe_generate_gksk_dev, lwe_embed_glwe,
                    lwe_embed_glwe_dev, TfheLutContext, tfhe_rotate_by_bits, tfhe_rotate_by_bits_dev, tfhe_lut_eval,
-                   tfhe_lut_eval_dev, tfhe_lut_table)
+                   tfhe_lut_eval_dev, tfhe_lut_table, TfheBitExtractContext, tfhe_extract_bits, tfhe_extract_bits_dev,
+                   tfhe_lut_on_integer_dev)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -54,4 +55,5 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "tfhe_cmux_tree", "tfhe_cmux_tree_dev", "TfheGlweTraceContext", "glwe_automorphism", "glwe_automorphism_dev",
            "glwe_keyswitch", "glwe_keyswitch_dev", "glwe_trace", "glwe_trace_dev", "tfhe_generate_gksk_dev", "lwe_embed_glwe",
            "lwe_embed_glwe_dev", "TfheLutContext", "tfhe_rotate_by_bits", "tfhe_rotate_by_bits_dev", "tfhe_lut_eval",
-           "tfhe_lut_eval_dev", "tfhe_lut_table", "build", "lib", "library_path", "status_string"]
+           "tfhe_lut_eval_dev", "tfhe_lut_table", "TfheBitExtractContext", "tfhe_extract_bits", "tfhe_extract_bits_dev",
+           "tfhe_lut_on_integer_dev", "build", "lib", "library_path", "status_string"]

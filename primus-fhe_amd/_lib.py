@@ -274,6 +274,14 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "rotate_by_bits", ci, vp, vp, sz, f64p, sz, sz, sz, vp, sz)
         sig(lu + "_eval_dev", ci, vp, vp, sz, f64p, sz, sz, vp, sz, vp)
         sig(lu + "_eval", ci, vp, vp, sz, f64p, sz, sz, vp, sz)
+        # bit extraction of a multi-bit LWE message into bit ciphertexts
+        be = "pfhe_bitext" + ("32" if tp.endswith("32_") else "")     # a prefix of its own, pfhe_bitext_ / pfhe_bitext32_
+        sig(be + "_create", ci, vp, sz, u32, sz, sz, u32, sz, sz, C.POINTER(vp))
+        sig(be + "_destroy", None, vp)
+        sig(be + "_in_use", ci, vp)
+        sig(be + "_scratch_bytes", sz, vp)
+        sig(be + "_extract_bits_dev", ci, vp, vp, sz, f64p, sz, vp, sz, u32, u32, vp, sz, vp)
+        sig(be + "_extract_bits", ci, vp, vp, sz, f64p, sz, vp, sz, u32, u32, vp, sz)
         # the GLWE automorphism / key switch and the trace, both calls of one handle; their keys; the LWE embedding
         gt = tp + "glwe_trace"
         sig(gt + "_create", ci, vp, sz, u32, sz, sz, C.POINTER(vp))

@@ -8,7 +8,8 @@
 //   extract_word     a mask word of sample extraction at index h: pfhe_bootstrap.hip and pfhe_manylut.hip.  The two kernels
 //                    that extract at index 0 alone (tfhe_cbs_extract_kernel, tfhe_extract_first_few_kernel) keep their own
 //                    two-case form, a[0] or -a[N - i]: with h = 0 passed here they compile to other instructions.
-//   ks_tile_sums     the group loop of tfhe_keyswitch_kernel (pfhe_bootstrap.hip) and tfhe_pfks_kernel (pfhe_cbs.hip).
+//   ks_tile_sums     the group loop of tfhe_keyswitch_kernel (pfhe_bootstrap.hip), tfhe_pfks_kernel (pfhe_cbs.hip) and
+//                    tfhe_bitext_keyswitch_kernel (pfhe_bitext.hip).
 // Every function is inlined into its kernels, which stay separate kernels with their own names, grids and arguments.  The
 // forms (what is a member, the order of parameters, what is left to the caller) are the ones with which every kernel but
 // the two key switches compiles to the instructions it had with the rule written out
@@ -79,18 +80,19 @@ inline u32 ks_group_words(u32 ell) { return std::max<u32>(1, std::min<u32>(kKsMa
 // acc[r][c] += sum over the `words` first words j of input row r0 + wave kKsRows + r (row m starts at in + m stride; rows
 // from `total` on count as 0) and the levels l of d_l(word j) * key[c][(j ell + l) cols].  dig: kKsMaxRows * kKsTileM words
 // of LDS, [word of the group][level][ciphertext of the tile].  The LWE key switch passes stride = words + 1 (the body is not
-// decomposed), the private one stride = words (it is).
+// decomposed), the private one stride = words (it is).  shift: every word is shifted left by it, as a wrapping word, before
+// its digits are taken (pfhe_bitext.hip; 0 everywhere else, where the shift folds away).
 template <class W>
 __device__ __forceinline__ void ks_tile_sums(W *dig, const W *__restrict__ in, u64 stride, u32 words, u64 r0, u64 total,
                                              const W *const (&key)[kKsCols], u32 cols, u32 log_basis, u32 ell, u32 drop_bits,
-                                             u32 ki, W (&acc)[kKsRows][kKsCols]) {
+                                             u32 ki, W (&acc)[kKsRows][kKsCols], u32 shift = 0) {
     const u32 wave = threadIdx.x / kKsLanes;
     // the pair this thread decomposes in every group: word ii of the group, ciphertext ei of the tile
     const u32 ii = threadIdx.x % ki, ei = threadIdx.x / ki;
     for (u32 i0 = 0; i0 < words; i0 += ki) {
         if (ei < (u32)kKsTileM) {
             const bool live = r0 + ei < total && i0 + ii < words;
-            const W v = live ? in[(r0 + ei) * stride + i0 + ii] : (W)0;
+            const W v = live ? (W)(in[(r0 + ei) * stride + i0 + ii] << shift) : (W)0;
             u32 carry = init_carry(v, drop_bits);
             for (u32 l = 0; l < ell; ++l)
                 dig[(ii * ell + l) * kKsTileM + ei] = digit_word(v, drop_bits + l * log_basis, log_basis, carry);

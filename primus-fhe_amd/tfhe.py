@@ -170,9 +170,11 @@ class _TorusContext:
     ends with the handle (`lead`: what a create takes between the dimension and the basis); `prefix` is what the context's calls start with, `calls` what its create, destroy, in-use and
     scratch calls are named behind it."""
 
-    def _open(self, fft, basis, glwe_dimension, prefix, args, calls=("create", "destroy", "in_use", "scratch_bytes"), lead=()):
+    def _open(self, fft, basis, glwe_dimension, prefix, args, calls=("create", "destroy", "in_use", "scratch_bytes"), lead=(),
+              family=None):
         self._w = "" if basis.bits == 64 else "32"
-        self._pre = "pfhe_tfhe" + self._w + "_" + prefix
+        # family: a handle whose entry points have a prefix of their own, family + width, instead of pfhe_tfhe{,32}_<prefix>
+        self._pre = family + self._w if family else "pfhe_tfhe" + self._w + "_" + prefix
         self._destroy, self._in_use, self._scratch = calls[1:]
         h = C.c_void_p()
         check(getattr(lib(), self._pre + calls[0])(fft._h, glwe_dimension, *lead, basis.log_basis(), basis.decompose_length(),
@@ -1010,6 +1012,90 @@ def tfhe_lut_table(values, log_n: int, k: int, tree_depth: int, rot_bits: int, l
     body[..., :words] = values.reshape(outputs, 1 << tree_depth, 1 << rot_bits, words)
     leaves[:, :, k, :(1 << rot_bits) << log_stride] = body.reshape(outputs, 1 << tree_depth, -1)
     return leaves
+
+
+# ---- bit extraction of a multi-bit LWE message, and the look-up on an encrypted integer (include/pfhe.h: pfhe_bitext{,32}_*) ----
+
+class TfheBitExtractContext(_TorusContext):
+    """Handle of the batched bit extraction (include/pfhe.h, pfhe_bitext{,32}_*): an LWE ciphertext of
+    k*N + 1 words under the extracted GLWE key with phase m*2^delta_log + e becomes `bits` LWE ciphertexts of
+    lwe_dimension + 1 words under the LWE key, bit i encoded as m_i*2^(BITS-1): what tfhe_circuit_bootstrap_dev takes.
+    Per bit: the key switch under `ks_basis` of the running ciphertext shifted left, and unless it is the last bit a
+    blind rotation under `basis` that clears the bit from the running ciphertext.  Owns a blind-rotation handle and every
+    buffer between the stages for `chunk` inputs (0 = the default); one holder at a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, lwe_dimension: int, glwe_dimension: int = 1,
+                 ks_basis: ApproxSignedBasis | None = None, chunk: int = 0):
+        if ks_basis is None:
+            raise ValueError("bit extraction needs ks_basis: every bit leaves through the key switch")
+        if ks_basis.bits != basis.bits:
+            raise TypeError("ks_basis must have the width of the torus words")
+        self._open(fft, basis, glwe_dimension, "bitext",
+                   (lwe_dimension, ks_basis.log_basis(), ks_basis.decompose_length(), chunk),
+                   ("_create", "_destroy", "_in_use", "_scratch_bytes"), family="pfhe_bitext")
+        self.lwe_dimension, self.ks_basis = lwe_dimension, ks_basis
+
+    def bsk_len(self) -> int:
+        """complex values of the bootstrapping key: lwe_dimension Fourier GGSW keys"""
+        return self.lwe_dimension * self.key_len()
+
+    def extracted_dimension(self) -> int:
+        return self.glwe_dimension * self.fft.poly_length()
+
+    def ksk_len(self) -> int:
+        """words of the key-switch key from the extracted key to the LWE key"""
+        return self.extracted_dimension() * self.ks_basis.decompose_length() * (self.lwe_dimension + 1)
+
+
+def _extract_bits(words, fourier, lwe_in, bsk, ksk, bits_out, ctx, delta_log, bits, name, tail):
+    pi, ni, wi = words(lwe_in)
+    pk, nk = fourier(bsk)
+    ps, ns, ws = words(ksk)
+    po, no, wo = words(bits_out)
+    _same_width("every word array must have the width of the context's basis", wi, ws, wo, ctx._w)
+    check(getattr(lib(), ctx._pre + name)(ctx._h, pi, ni, pk, nk, ps, ns, delta_log, bits, po, no, *tail))
+
+
+def tfhe_extract_bits(lwe_in: np.ndarray, bsk: np.ndarray, ksk: np.ndarray, bits_out: np.ndarray,
+                      ctx: TfheBitExtractContext, delta_log: int, bits: int) -> None:
+    """Batched bit extraction on host arrays.  lwe_in: batch x (k*N + 1) words, phase m*2^delta_log + e; bsk: n Fourier
+    GGSW keys end to end; ksk: ctx.ksk_len() words as tfhe_generate_ksk_dev writes them; bits_out: batch x bits x (n+1)
+    words, bit i (0 the least significant) of input e at row e*bits + i with phase m_i*2^(BITS-1) plus noise.
+    1 <= delta_log, 1 <= bits, delta_log + bits <= BITS; higher message bits are shifted out."""
+    _extract_bits(_host_words, _host_fourier, lwe_in, bsk, ksk, bits_out, ctx, delta_log, bits, "_extract_bits", ())
+
+
+def tfhe_extract_bits_dev(lwe_in, bsk, ksk, bits_out, ctx: TfheBitExtractContext, delta_log: int, bits: int,
+                          stream=None) -> None:
+    """the device form (32- or 64-bit integer CUDA tensors of the context's width, bsk complex128 or float64),
+    asynchronous; bits_out must not overlap an input and may be uninitialised; lwe_in is read only"""
+    _extract_bits(_dev_words, _dev_fourier, lwe_in, bsk, ksk, bits_out, ctx, delta_log, bits, "_extract_bits_dev",
+                  (_stream(stream),))
+
+
+def tfhe_lut_on_integer_dev(lwe_in, bsk, ksk, pfksk, table, out, bitext_ctx: TfheBitExtractContext,
+                            cbs_ctx: TfheCircuitBootstrapContext, lut_ctx: TfheLutContext, delta_log: int, extract: int = 1,
+                            stream=None) -> None:
+    """A look-up table on an encrypted integer without a padding bit, as a chain of three public calls: tfhe_extract_bits_dev
+    with bits = lut_ctx.bits(), tfhe_circuit_bootstrap_dev + write_fourier_form on the batch*bits bit ciphertexts, and
+    tfhe_lut_eval_dev with those selectors.  lwe_in: batch x (k*N + 1) words with phase m*2^delta_log + e; out: what
+    tfhe_lut_eval_dev writes for `extract` (with extract >= 1 its rows are inputs of the next such call).  lut_ctx's basis
+    is cbs_ctx.cbs_basis.  Plain Python, not a handle: every call allocates its intermediates with torch (the bit
+    ciphertexts, the torus GGSWs and their Fourier form) on lwe_in's device; allocation and the current-stream semantics
+    of torch apply, so pass the stream torch is on, or None on the default stream."""
+    import torch
+    p = lut_ctx.bits()
+    ext = bitext_ctx.extracted_dimension() + 1
+    if lwe_in.numel() % ext != 0:
+        raise ValueError("lwe_in must be batch x (k*N + 1) words")
+    batch = lwe_in.numel() // ext
+    bit_cts = torch.empty(batch * p * (bitext_ctx.lwe_dimension + 1), dtype=lwe_in.dtype, device=lwe_in.device)
+    ggsw = torch.empty(batch * p * cbs_ctx.ggsw_len(), dtype=lwe_in.dtype, device=lwe_in.device)
+    selectors = torch.empty(ggsw.numel(), dtype=torch.complex128, device=lwe_in.device)
+    tfhe_extract_bits_dev(lwe_in, bsk, ksk, bit_cts, bitext_ctx, delta_log, p, stream)
+    tfhe_circuit_bootstrap_dev(bit_cts, bsk, pfksk, ggsw, cbs_ctx, stream)
+    write_fourier_form(ggsw, selectors, cbs_ctx.fft, stream)
+    tfhe_lut_eval_dev(table, selectors, out, lut_ctx, extract, stream)
 
 
 # ---- GLWE key switch, automorphism and trace; their keys; the LWE embedding (include/pfhe.h: glwe_trace_*, glwe_automorphism,
