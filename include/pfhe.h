@@ -1795,6 +1795,56 @@ int pfhe_bitext32_extract_bits(pfhe_bitext32 *h, const uint32_t *lwe_in, size_t 
                              size_t len_bsk, const uint32_t *ksk, size_t len_ksk, uint32_t delta_log, uint32_t bits,
                              uint32_t *bits_out, size_t len_out);
 
+/* ---- linear layer: clear integer weights on batches of LWE ciphertexts (u64: no suffix, u32: 32) ----
+ * The leveled step between two bootstraps: out_features chains of Lwe::add_mul_scalar_assign
+ * (primus_lattice/src/lwe/single_message.rs:262-268) per input vector, one chain per output, summed over the inputs of a
+ * neuron.  The family has a prefix of its own, pfhe_lwe_ / pfhe_lwe32_; the u32 prototype of every pair is
+ * the u64 one with uint64_t -> uint32_t.
+ *
+ * With row = dimension + 1 words per ciphertext (a then b): lwe_in is batch*in_features*row words, vector e, ciphertext i;
+ * weights is out_features*in_features scalars, row-major, shared by the batch; bias is out_features words, already encoded
+ * as torus words and added to the body, or null with len_bias 0; lwe_out is batch*out_features*row words, may be
+ * uninitialised and must not overlap an input.  Modulo 2^BITS:
+ *   out[e][o][c] = sum_{i < in_features} W[o][i] * in[e][i][c]  +  [c = dimension] * bias[o]
+ * A sum modulo 2^BITS does not depend on its order, so the words depend on no tiling, batch size or path.  The rule is
+ * word-wise: a GLWE row of (k+1)*N words passed as dimension = (k+1)*N - 1 with a null bias is served as well.
+ *   linear      W[o][i] is a word of the ciphertext's width, the reference's `scalar: T`, a negative weight in two's complement;
+ *   linear_i8   W[o][i] is an int8_t; the result is, by definition, linear's on the sign-extended weights (computed on the
+ *               matrix cores, byte plane by byte plane; no cap on in_features).
+ * Statuses, in this order and all before the device is touched: PFHE_ERR_BAD_ARGUMENT for dimension, in_features or
+ * out_features outside 1..2^31-2; PFHE_ERR_BAD_LENGTH unless len_in is a multiple of in_features*row, len_weights =
+ * out_features*in_features, len_bias is 0 or out_features and len_out = batch*out_features*row; (an empty batch is a no-op;)
+ * PFHE_ERR_BAD_ARGUMENT for a null pointer (a bias of len_bias words included), for a bias pointer with len_bias 0 and for
+ * an output that overlaps an input (device form); PFHE_ERR_BAD_LENGTH for more than 2^31-1 workgroups in a row, the batch
+ * being folded into one grid dimension with the column tiles: batch*ceil(row/128) for linear, batch*ceil(row/64) for
+ * linear_i8 (a status of this implementation, beyond the reference's rule); the device.
+ * A call only queues work on `stream`: no allocation, no atomics, no scratch, repeatable, and it can be captured into a
+ * HIP graph. */
+int pfhe_lwe_linear_dev(int device, const uint64_t *lwe_in_dev, size_t len_in, size_t dimension, const uint64_t *weights_dev,
+                        size_t len_weights, size_t in_features, size_t out_features, const uint64_t *bias_dev, size_t len_bias,
+                        uint64_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_lwe_linear(int device, const uint64_t *lwe_in, size_t len_in, size_t dimension, const uint64_t *weights,
+                    size_t len_weights, size_t in_features, size_t out_features, const uint64_t *bias, size_t len_bias,
+                    uint64_t *lwe_out, size_t len_out);
+int pfhe_lwe_linear_i8_dev(int device, const uint64_t *lwe_in_dev, size_t len_in, size_t dimension, const int8_t *weights_dev,
+                           size_t len_weights, size_t in_features, size_t out_features, const uint64_t *bias_dev,
+                           size_t len_bias, uint64_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_lwe_linear_i8(int device, const uint64_t *lwe_in, size_t len_in, size_t dimension, const int8_t *weights,
+                       size_t len_weights, size_t in_features, size_t out_features, const uint64_t *bias, size_t len_bias,
+                       uint64_t *lwe_out, size_t len_out);
+int pfhe_lwe32_linear_dev(int device, const uint32_t *lwe_in_dev, size_t len_in, size_t dimension, const uint32_t *weights_dev,
+                          size_t len_weights, size_t in_features, size_t out_features, const uint32_t *bias_dev, size_t len_bias,
+                          uint32_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_lwe32_linear(int device, const uint32_t *lwe_in, size_t len_in, size_t dimension, const uint32_t *weights,
+                      size_t len_weights, size_t in_features, size_t out_features, const uint32_t *bias, size_t len_bias,
+                      uint32_t *lwe_out, size_t len_out);
+int pfhe_lwe32_linear_i8_dev(int device, const uint32_t *lwe_in_dev, size_t len_in, size_t dimension, const int8_t *weights_dev,
+                             size_t len_weights, size_t in_features, size_t out_features, const uint32_t *bias_dev,
+                             size_t len_bias, uint32_t *lwe_out_dev, size_t len_out, void *stream);
+int pfhe_lwe32_linear_i8(int device, const uint32_t *lwe_in, size_t len_in, size_t dimension, const int8_t *weights,
+                         size_t len_weights, size_t in_features, size_t out_features, const uint32_t *bias, size_t len_bias,
+                         uint32_t *lwe_out, size_t len_out);
+
 #ifdef __cplusplus
 }
 #endif

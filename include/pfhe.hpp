@@ -393,6 +393,10 @@ struct Fns;
         PFHE_FN(bitext, S, create);                                                                            \
         PFHE_FN(bitext, S, extract_bits);                                                                      \
         PFHE_FN(bitext, S, extract_bits_dev);                                                                  \
+        PFHE_FN(lwe, S, linear);                                                                               \
+        PFHE_FN(lwe, S, linear_dev);                                                                           \
+        PFHE_FN(lwe, S, linear_i8);                                                                            \
+        PFHE_FN(lwe, S, linear_i8_dev);                                                                        \
     }
 PFHE_WORD_TRAITS(uint64_t, , U64DcrtTable);
 PFHE_WORD_TRAITS(uint32_t, 32, U32DcrtTable);
@@ -743,6 +747,39 @@ void lwe_keyswitch_dev(int device, const W *lwe_in_dev, size_t len_in, size_t in
                        detail::same<W> *lwe_out_dev, size_t len_out, void *stream = nullptr) {
     check(detail::Fns<W>::tfhe_keyswitch_dev(device, lwe_in_dev, len_in, in_dimension, ksk_dev, len_ksk, out_dimension,
                                              log_basis, decompose_length, lwe_out_dev, len_out, stream));
+}
+
+// The linear layer with clear weights (pfhe_lwe{,32}_linear*): out[e][o] = sum_i W[o][i] * in[e][i] + (0, bias[o]), out_features
+// chains of Lwe::add_mul_scalar_assign (lwe/single_message.rs:262-268) per input vector.  The weights' type picks the entry:
+// words of the ciphertext's width (the reference's `scalar: T`), or int8_t, which gives the words of the sign-extended weights.
+// bias: out_features torus words, or null with len_bias 0.
+template <class W>
+void lwe_linear(int device, const W *lwe_in, size_t len_in, size_t dimension, const detail::same<W> *weights, size_t len_weights,
+                size_t in_features, size_t out_features, const detail::same<W> *bias, size_t len_bias, detail::same<W> *lwe_out,
+                size_t len_out) {
+    check(detail::Fns<W>::lwe_linear(device, lwe_in, len_in, dimension, weights, len_weights, in_features, out_features, bias,
+                                     len_bias, lwe_out, len_out));
+}
+template <class W>
+void lwe_linear(int device, const W *lwe_in, size_t len_in, size_t dimension, const int8_t *weights, size_t len_weights,
+                size_t in_features, size_t out_features, const detail::same<W> *bias, size_t len_bias, detail::same<W> *lwe_out,
+                size_t len_out) {
+    check(detail::Fns<W>::lwe_linear_i8(device, lwe_in, len_in, dimension, weights, len_weights, in_features, out_features, bias,
+                                        len_bias, lwe_out, len_out));
+}
+template <class W>
+void lwe_linear_dev(int device, const W *lwe_in_dev, size_t len_in, size_t dimension, const detail::same<W> *weights_dev,
+                    size_t len_weights, size_t in_features, size_t out_features, const detail::same<W> *bias_dev, size_t len_bias,
+                    detail::same<W> *lwe_out_dev, size_t len_out, void *stream = nullptr) {
+    check(detail::Fns<W>::lwe_linear_dev(device, lwe_in_dev, len_in, dimension, weights_dev, len_weights, in_features,
+                                         out_features, bias_dev, len_bias, lwe_out_dev, len_out, stream));
+}
+template <class W>
+void lwe_linear_dev(int device, const W *lwe_in_dev, size_t len_in, size_t dimension, const int8_t *weights_dev,
+                    size_t len_weights, size_t in_features, size_t out_features, const detail::same<W> *bias_dev, size_t len_bias,
+                    detail::same<W> *lwe_out_dev, size_t len_out, void *stream = nullptr) {
+    check(detail::Fns<W>::lwe_linear_i8_dev(device, lwe_in_dev, len_in, dimension, weights_dev, len_weights, in_features,
+                                            out_features, bias_dev, len_bias, lwe_out_dev, len_out, stream));
 }
 
 // The batched programmable bootstrap (pfhe_tfhe_bootstrap_*): modulus switch, ACC = X^{-b~} * TV, the blind rotation over

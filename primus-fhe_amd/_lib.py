@@ -282,6 +282,11 @@ def _declare(lib: C.CDLL) -> None:
         sig(be + "_scratch_bytes", sz, vp)
         sig(be + "_extract_bits_dev", ci, vp, vp, sz, f64p, sz, vp, sz, u32, u32, vp, sz, vp)
         sig(be + "_extract_bits", ci, vp, vp, sz, f64p, sz, vp, sz, u32, u32, vp, sz)
+        # the linear layer with clear weights: word weights and int8 weights (a byte pointer), each in two forms
+        ll = "pfhe_lwe" + ("32" if tp.endswith("32_") else "") + "_linear"  # a prefix of its own, pfhe_lwe_ / pfhe_lwe32_
+        for entry in (ll, ll + "_i8"):
+            sig(entry + "_dev", ci, ci, vp, sz, sz, vp, sz, sz, sz, vp, sz, vp, sz, vp)
+            sig(entry, ci, ci, vp, sz, sz, vp, sz, sz, sz, vp, sz, vp, sz)
         # the GLWE automorphism / key switch and the trace, both calls of one handle; their keys; the LWE embedding
         gt = tp + "glwe_trace"
         sig(gt + "_create", ci, vp, sz, u32, sz, sz, C.POINTER(vp))

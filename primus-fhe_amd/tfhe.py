@@ -416,6 +416,60 @@ def lwe_keyswitch_dev(lwe_in, ksk, lwe_out, in_dimension: int, out_dimension: in
     _keyswitch(True, lwe_in, ksk, lwe_out, in_dimension, out_dimension, basis, device, stream)
 
 
+# ---- the linear layer with clear weights (include/pfhe.h: pfhe_lwe{,32}_linear*) ----
+
+def _linear_weights(dev, weights, w: str):
+    """(pointer, count, entry suffix) of the weights: dtype int8 takes the i8 entry, the word's dtype (for a tensor, the
+    integer dtype of the word's size) the word entry; anything else is a ValueError before the library is called"""
+    if dev:
+        import torch
+        if not hasattr(weights, "data_ptr") or not weights.is_cuda or not weights.is_contiguous():
+            raise TypeError("expected a contiguous CUDA tensor of weights")
+        if weights.dtype == torch.int8:
+            return C.c_void_p(weights.data_ptr()), weights.numel(), "_i8"
+        if weights.is_floating_point() or weights.is_complex() or weights.dtype == torch.bool \
+                or weights.element_size() != (4 if w == "32" else 8):
+            raise ValueError("weights must be int8 or of the ciphertext words' dtype")
+        return C.c_void_p(weights.data_ptr()), weights.numel(), ""
+    if not isinstance(weights, np.ndarray) or not weights.flags.c_contiguous:
+        raise TypeError("expected a C-contiguous numpy array of weights")
+    if weights.dtype == np.int8:
+        return weights.ctypes.data_as(C.c_void_p), weights.size, "_i8"
+    if _WORD.get(weights.dtype) != w:
+        raise ValueError("weights must be int8 or of the ciphertext words' dtype")
+    return weights.ctypes.data_as(C.c_void_p), weights.size, ""
+
+
+def _linear(dev, lwe_in, weights, bias, lwe_out, dimension, in_features, out_features, device, stream=None) -> None:
+    words = _dev_words if dev else _host_words
+    pi, ni, wi = words(lwe_in)
+    po, no, wo = words(lwe_out)
+    pb, nb, wb = words(bias) if bias is not None else (None, 0, wi)
+    w = _same_width("lwe_in, bias and lwe_out must have the same word width", wi, wo, wb)
+    pw, nw, entry = _linear_weights(dev, weights, w)
+    tail = (_stream(stream),) if dev else ()
+    check(getattr(lib(), "pfhe_lwe" + w + "_linear" + entry + ("_dev" if dev else ""))(
+        _dev_index(lwe_in, device) if dev else device, pi, ni, dimension, pw, nw, in_features, out_features, pb, nb, po, no,
+        *tail))
+
+
+def lwe_linear(lwe_in: np.ndarray, weights: np.ndarray, bias, lwe_out: np.ndarray, dimension: int, in_features: int,
+               out_features: int, device: int = 0) -> None:
+    """A linear layer with clear integer weights on host arrays, modulo 2^BITS: lwe_in is batch x in_features ciphertexts of
+    dimension + 1 words, weights out_features x in_features (row-major, shared by the batch), bias out_features torus words
+    added to the bodies or None, and out[e][o] = sum_i weights[o][i] * in[e][i] + (0, bias[o]): out_features chains of
+    Lwe::add_mul_scalar_assign (lwe/single_message.rs:262-268) per input vector.  Weights of dtype int8 run on the matrix
+    cores and give the words of the sign-extended weights; weights of the words' dtype are the reference's scalars, a
+    negative weight in two's complement.  Any other dtype is a ValueError."""
+    _linear(False, lwe_in, weights, bias, lwe_out, dimension, in_features, out_features, device)
+
+
+def lwe_linear_dev(lwe_in, weights, bias, lwe_out, dimension: int, in_features: int, out_features: int, device=None,
+                   stream=None) -> None:
+    """the device form, asynchronous; lwe_out must not overlap an input and may be uninitialised"""
+    _linear(True, lwe_in, weights, bias, lwe_out, dimension, in_features, out_features, device, stream)
+
+
 class TfheBootstrapContext(_TorusContext):
     """Handle of the batched programmable bootstrap (include/pfhe.h, pfhe_tfhe{,32}_bootstrap_*): modulus switch,
     ACC = X^{-b~} * TV, the blind rotation over lwe_dimension steps (grouping_factor above 1: the multi-bit rotation over
@@ -487,6 +541,26 @@ def tfhe_bootstrap_dev(lwe_in, bsk, tv, ksk, lwe_out, ctx: TfheBootstrapContext,
     ps, ns, ws = _dev_words(ksk) if ksk is not None else (None, 0, ctx._w)
     _same_width("every word tensor must have the width of the context's basis", wi, wt, wo, ws, ctx._w)
     check(getattr(lib(), ctx._pre + "_dev")(ctx._h, pi, ni, pk, nk, pt, nt, ps, ns, po, no, _stream(stream)))
+
+
+def tfhe_dense_layer_dev(lwe_in, weights, bias, bsk, tv, ksk, lwe_out, ctx: TfheBootstrapContext, in_features: int,
+                         out_features: int, stream=None) -> None:
+    """A dense layer of encrypted inference as two public calls: lwe_linear_dev (the weighted sums of every input vector,
+    with the bias) and tfhe_bootstrap_dev on the batch * out_features sums (the activation, as the test vector tv: one, or
+    one per output ciphertext).  ctx is a bootstrap context with its key switch, so lwe_out (batch x out_features
+    ciphertexts of lwe_dimension + 1 words) feeds the next layer.  Plain Python, not a handle: every call allocates the
+    intermediate sums with torch on lwe_in's device; allocation and the current-stream semantics of torch apply, so pass the
+    stream torch is on, or None on the default stream."""
+    import torch
+    if ctx.ks_basis is None:
+        raise ValueError("a dense layer needs a bootstrap context with its key switch")
+    row = ctx.lwe_dimension + 1
+    if lwe_in.numel() % (in_features * row) != 0:
+        raise ValueError("lwe_in must be batch x in_features x (lwe_dimension + 1) words")
+    batch = lwe_in.numel() // (in_features * row)
+    sums = torch.empty(batch * out_features * row, dtype=lwe_in.dtype, device=lwe_in.device)
+    lwe_linear_dev(lwe_in, weights, bias, sums, ctx.lwe_dimension, in_features, out_features, stream=stream)
+    tfhe_bootstrap_dev(sums, bsk, tv, ksk, lwe_out, ctx, stream)
 
 
 def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) -> None:
