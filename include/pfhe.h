@@ -1161,7 +1161,8 @@ int pfhe_tfhe32_bootstrap(pfhe_tfhe32_bootstrap_handle *h, const uint32_t *lwe_i
 
 /* ---- key generation, encryption and phase for the bootstrap above (u64: no suffix, u32: 32) ----
  * NO RANDOM NUMBER IS DRAWN HERE.  Every call is deterministic integer arithmetic modulo 2^BITS on buffers the caller has
- * filled: mask slots hold the uniform words, body slots hold noise + message.  Keys are arrays of torus words, any words
+ * filled: mask slots hold the uniform words, body slots hold noise + message (pfhe_rand{,32}_fill_rows_dev, at the end of
+ * this file, fills them on the device from a ChaCha20 stream).  Keys are arrays of torus words, any words
  * (0/1 for a binary key, all-ones for -1, anything else).  No atomics; a call only queues work on `stream` (no allocation,
  * no host synchronisation) and can be captured into a HIP graph.  The body calls ACCUMULATE into the body slot: a call is
  * repeatable only in that sense (a second call adds the product a second time; add followed by subtract restores the input).
@@ -1844,6 +1845,104 @@ int pfhe_lwe32_linear_i8_dev(int device, const uint32_t *lwe_in_dev, size_t len_
 int pfhe_lwe32_linear_i8(int device, const uint32_t *lwe_in, size_t len_in, size_t dimension, const int8_t *weights,
                          size_t len_weights, size_t in_features, size_t out_features, const uint32_t *bias, size_t len_bias,
                          uint32_t *lwe_out, size_t len_out);
+
+/* ---- random layer: a device ChaCha20 stream, exact samplers, seeded LWE ciphertexts (u64: no suffix, u32: 32) ----
+ * The randomness every encryption call and key generator above takes as a caller-filled buffer (masks uniform, bodies
+ * noise), drawn on the device from a position-addressed stream.  The reference's layer is primus_distr,
+ * which samples from a stateful `rand::Rng + CryptoRng`; a call here has NO state: output i of a sampler is a closed form
+ * of (key, nonce, i), so any call can produce any sub-range and a mask can be re-made from its seed instead of being stored.
+ * The families have prefixes of their own, pfhe_csprng_ and pfhe_rand_ / pfhe_rand32_; the u32 prototype of every pair is
+ * the u64 one with uint64_t -> uint32_t (keys and nonces are uint32_t words at both widths, indices size_t).
+ *
+ * The stream: ChaCha20, the 20-round block function of RFC 8439, with a 64-bit block counter in state words 12 (low) and
+ * 13 (high) and a 64-bit nonce in words 14 (low) and 15 (high).  `key` points at eight uint32_t words (state words 4..11)
+ * and `nonce` at two (words 14, 15), both in HOST memory: a key travels to the kernels as a kernel argument and is never
+ * written to device global memory, printed or put into an error message.  u32 stream word j is little-endian word j mod 16
+ * of block j div 16; u64 stream word j is u32 words 2j (low half) and 2j+1 (high half).  The layout is RFC 8439 §2.3.2's
+ * and `openssl enc -chacha20`'s (whose 16-byte IV is state words 12..15), both tested; it should also be
+ * rand_chacha::ChaCha20Rng's (set_stream = the nonce, set_word_pos = the u32 word index, next_u64 low word first), which is
+ * UNVERIFIED: no Rust toolchain was at hand.  The library gathers no entropy: the caller supplies every key.
+ *
+ * Samplers, exact integer rules on u32 / u64 torus words; `offset` is the absolute index of the first output:
+ *   keystream  u32 stream words [word_offset, word_offset + n_words) (no primus_distr counterpart: RngCore::next_u32)
+ *   uniform    output i = stream word i of the output's width (primus_distr has no power-of-two case: its uniform is
+ *              rand's Uniform<T> modulo q, which rejects; sample_uniform_values_to, primus_distr/src/common.rs:87-96)
+ *   binary     output i = bit i mod 32 of u32 stream word i div 32: sample_binary_values_to
+ *              (primus_distr/src/common.rs:22-42) on the same word stream
+ *   ternary    output i = [0, 0, 1, -1][(w >> 2 (i mod 16)) & 3], w = u32 stream word i div 16, -1 the all-ones word:
+ *              sample_ternary_values_to (common.rs:56-76)
+ *   tuniform   output i takes u64 stream word i at BOTH widths; r = its low bound_log2 + 2 bits; the value is
+ *              (r >> 1) + (r & 1) - 2^bound_log2 modulo 2^BITS: support [-2^b, 2^b], the two ends with probability
+ *              2^-(b+2), every other value 2^-(b+1), variance (2^(2b+1) + 1) / 6; 0 <= bound_log2 <= BITS - 2 (no
+ *              primus_distr counterpart: its noise is the discrete Gaussian, which is out of scope here)
+ * Rows: fill_rows writes rows of mask_len + body_len words; for absolute row R = first_row + r (rows = len_out /
+ * (mask_len + body_len)) mask word j is uniform output R*mask_len + j of the mask stream, and body word j gets tuniform
+ * output R*body_len + j of the noise stream, stored when add = 0 and added otherwise (so messages can be placed first).
+ * One launch.  LWE rows are (n, 1), GLWE rows (k*N, N), and the `rand` argument of pfhe_tfhe*_bsk_generate_dev,
+ * _ksk_generate_dev, _pksk_generate_dev, _pfksk_generate_dev and _gksk_generate_dev is rows of one of the two (no
+ * primus_distr counterpart: the reference draws inside generate_random_zero_sample).
+ * Seeded ciphertexts: lwe_encrypt_seeded computes bodies[r] += <mask(R), lwe_key> + noise(R) with mask(R) the row's mask
+ * above at mask_len = dimension and noise(R) tuniform output R: the body slot of fill_rows(add) followed by
+ * pfhe_tfhe*_lwe_body_mac, word for word, while the mask stays in registers; the key is any words.  seeded_expand writes the
+ * full rows, masks from the stream and bodies copied; it takes no noise seed: it is what the receiving side runs (neither
+ * has a primus_distr or primus_lattice counterpart).
+ * Statuses, in this order and all before the device is touched: PFHE_ERR_BAD_ARGUMENT for a null key or nonce, for
+ * (mask_key, mask_nonce) equal to (noise_key, noise_nonce) in the calls that take both (a seeded ciphertext publishes its
+ * mask seed, which must never give the noise), for bound_log2 > BITS - 2 and for mask_len, body_len or dimension outside
+ * 1..2^31-2; PFHE_ERR_BAD_LENGTH for a length that is not a whole number of rows (len_out, len_bodies; both must give the
+ * same rows) and for a last output index above 2^64 - 2^20; (no outputs: a no-op;) PFHE_ERR_BAD_ARGUMENT for a null buffer and, in
+ * the device forms, for an output that overlaps an input; PFHE_ERR_BAD_LENGTH for more than 2^31-1 workgroups; the device.
+ * A call only queues work on `stream`: no allocation, no atomics, no scratch, repeatable, capturable into a HIP graph. */
+int pfhe_csprng_keystream_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t word_offset, uint32_t *out_dev,
+                              size_t n_words, void *stream);
+int pfhe_rand_uniform_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint64_t *out_dev, size_t n,
+                          void *stream);
+int pfhe_rand_binary_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint64_t *out_dev, size_t n,
+                         void *stream);
+int pfhe_rand_ternary_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint64_t *out_dev, size_t n,
+                          void *stream);
+int pfhe_rand_tuniform_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint32_t bound_log2,
+                           uint64_t *out_dev, size_t n, void *stream);
+int pfhe_rand_fill_rows_dev(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, const uint32_t *noise_key,
+                            const uint32_t *noise_nonce, size_t first_row, size_t mask_len, size_t body_len,
+                            uint32_t bound_log2, int add, uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_rand_lwe_encrypt_seeded_dev(int device, const uint32_t *mask_key, const uint32_t *mask_nonce,
+                                     const uint32_t *noise_key, const uint32_t *noise_nonce, size_t first_row,
+                                     const uint64_t *lwe_key_dev, size_t dimension, uint32_t bound_log2, uint64_t *bodies_dev,
+                                     size_t rows, void *stream);
+int pfhe_rand_lwe_encrypt_seeded(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, const uint32_t *noise_key,
+                                 const uint32_t *noise_nonce, size_t first_row, const uint64_t *lwe_key, size_t dimension,
+                                 uint32_t bound_log2, uint64_t *bodies, size_t rows);
+int pfhe_rand_seeded_expand_dev(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, size_t first_row,
+                                size_t mask_len, size_t body_len, const uint64_t *bodies_dev, size_t len_bodies,
+                                uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_rand_seeded_expand(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, size_t first_row,
+                            size_t mask_len, size_t body_len, const uint64_t *bodies, size_t len_bodies, uint64_t *out,
+                            size_t len_out);
+int pfhe_rand32_uniform_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint32_t *out_dev, size_t n,
+                            void *stream);
+int pfhe_rand32_binary_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint32_t *out_dev, size_t n,
+                           void *stream);
+int pfhe_rand32_ternary_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint32_t *out_dev, size_t n,
+                            void *stream);
+int pfhe_rand32_tuniform_dev(int device, const uint32_t *key, const uint32_t *nonce, size_t offset, uint32_t bound_log2,
+                             uint32_t *out_dev, size_t n, void *stream);
+int pfhe_rand32_fill_rows_dev(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, const uint32_t *noise_key,
+                              const uint32_t *noise_nonce, size_t first_row, size_t mask_len, size_t body_len,
+                              uint32_t bound_log2, int add, uint32_t *out_dev, size_t len_out, void *stream);
+int pfhe_rand32_lwe_encrypt_seeded_dev(int device, const uint32_t *mask_key, const uint32_t *mask_nonce,
+                                       const uint32_t *noise_key, const uint32_t *noise_nonce, size_t first_row,
+                                       const uint32_t *lwe_key_dev, size_t dimension, uint32_t bound_log2, uint32_t *bodies_dev,
+                                       size_t rows, void *stream);
+int pfhe_rand32_lwe_encrypt_seeded(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, const uint32_t *noise_key,
+                                   const uint32_t *noise_nonce, size_t first_row, const uint32_t *lwe_key, size_t dimension,
+                                   uint32_t bound_log2, uint32_t *bodies, size_t rows);
+int pfhe_rand32_seeded_expand_dev(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, size_t first_row,
+                                  size_t mask_len, size_t body_len, const uint32_t *bodies_dev, size_t len_bodies,
+                                  uint32_t *out_dev, size_t len_out, void *stream);
+int pfhe_rand32_seeded_expand(int device, const uint32_t *mask_key, const uint32_t *mask_nonce, size_t first_row,
+                              size_t mask_len, size_t body_len, const uint32_t *bodies, size_t len_bodies, uint32_t *out,
+                              size_t len_out);
 
 #ifdef __cplusplus
 }

@@ -397,6 +397,15 @@ struct Fns;
         PFHE_FN(lwe, S, linear_dev);                                                                           \
         PFHE_FN(lwe, S, linear_i8);                                                                            \
         PFHE_FN(lwe, S, linear_i8_dev);                                                                        \
+        PFHE_FN(rand, S, uniform_dev);                                                                         \
+        PFHE_FN(rand, S, binary_dev);                                                                          \
+        PFHE_FN(rand, S, ternary_dev);                                                                         \
+        PFHE_FN(rand, S, tuniform_dev);                                                                        \
+        PFHE_FN(rand, S, fill_rows_dev);                                                                       \
+        PFHE_FN(rand, S, lwe_encrypt_seeded);                                                                  \
+        PFHE_FN(rand, S, lwe_encrypt_seeded_dev);                                                              \
+        PFHE_FN(rand, S, seeded_expand);                                                                       \
+        PFHE_FN(rand, S, seeded_expand_dev);                                                                   \
     }
 PFHE_WORD_TRAITS(uint64_t, , U64DcrtTable);
 PFHE_WORD_TRAITS(uint32_t, 32, U32DcrtTable);
@@ -780,6 +789,83 @@ void lwe_linear_dev(int device, const W *lwe_in_dev, size_t len_in, size_t dimen
                     detail::same<W> *lwe_out_dev, size_t len_out, void *stream = nullptr) {
     check(detail::Fns<W>::lwe_linear_i8_dev(device, lwe_in_dev, len_in, dimension, weights_dev, len_weights, in_features,
                                             out_features, bias_dev, len_bias, lwe_out_dev, len_out, stream));
+}
+
+// The random layer (pfhe_csprng_keystream_dev, pfhe_rand{,32}_*): a position-addressed ChaCha20 stream on the device, exact
+// samplers over it, whole ciphertext rows, and seeded LWE ciphertexts.  A RandSeed is the identity of one stream: eight key
+// words (RFC 8439's key, little-endian words) and a 64-bit nonce.  It lives in host memory and reaches the kernels as a
+// kernel argument; the library gathers no entropy, so the key is the caller's.  Output i of a sampler is a closed form of
+// (seed, i): no state, any sub-range from any call.  A mask seed may be published; a noise seed is a secret and must differ
+// from it (refused otherwise).  primus_distr's samplers draw from a stateful rand::Rng instead: binary and ternary give
+// sample_binary_values_to / sample_ternary_values_to (primus_distr/src/common.rs:22-76) on the same word stream, the others
+// have no counterpart there.
+struct RandSeed {
+    uint32_t key[8];
+    uint32_t nonce[2];  // state words 14 (low) and 15 (high)
+    RandSeed(const uint32_t (&key_words)[8], uint64_t nonce64) : nonce{(uint32_t)nonce64, (uint32_t)(nonce64 >> 32)} {
+        for (int i = 0; i < 8; ++i) key[i] = key_words[i];
+    }
+};
+// u32 stream words [word_offset, word_offset + n_words); a template like the rest of this header, so that a unit that does not
+// call it does not reference the entry point: the stream's words are uint32_t and W is nothing else
+template <class W = uint32_t>
+void csprng_keystream_dev(int device, const RandSeed &seed, size_t word_offset, detail::same<W> *out_dev, size_t n_words,
+                          void *stream = nullptr) {
+    static_assert(std::is_same<W, uint32_t>::value, "the keystream is written as uint32_t words");
+    check(pfhe_csprng_keystream_dev(device, seed.key, seed.nonce, word_offset, out_dev, n_words, stream));
+}
+// outputs [offset, offset + n) of a sampler: uniform words, bits, {0, 0, 1, -1} by two bits, TUniform(bound_log2)
+template <class W>
+void torus_uniform_dev(int device, const RandSeed &seed, size_t offset, W *out_dev, size_t n, void *stream = nullptr) {
+    check(detail::Fns<W>::rand_uniform_dev(device, seed.key, seed.nonce, offset, out_dev, n, stream));
+}
+template <class W>
+void torus_binary_dev(int device, const RandSeed &seed, size_t offset, W *out_dev, size_t n, void *stream = nullptr) {
+    check(detail::Fns<W>::rand_binary_dev(device, seed.key, seed.nonce, offset, out_dev, n, stream));
+}
+template <class W>
+void torus_ternary_dev(int device, const RandSeed &seed, size_t offset, W *out_dev, size_t n, void *stream = nullptr) {
+    check(detail::Fns<W>::rand_ternary_dev(device, seed.key, seed.nonce, offset, out_dev, n, stream));
+}
+template <class W>
+void torus_tuniform_dev(int device, const RandSeed &seed, size_t offset, uint32_t bound_log2, W *out_dev, size_t n,
+                        void *stream = nullptr) {
+    check(detail::Fns<W>::rand_tuniform_dev(device, seed.key, seed.nonce, offset, bound_log2, out_dev, n, stream));
+}
+// rows of mask_len uniform words and body_len TUniform words (stored, or added when `add`), absolute rows from first_row on:
+// the `rand` argument of every key generator and the buffers lwe_body_mac / glwe_body_mac take
+template <class W>
+void fill_rows_dev(int device, const RandSeed &mask_seed, const RandSeed &noise_seed, size_t first_row, size_t mask_len,
+                   size_t body_len, uint32_t bound_log2, bool add, W *out_dev, size_t len_out, void *stream = nullptr) {
+    check(detail::Fns<W>::rand_fill_rows_dev(device, mask_seed.key, mask_seed.nonce, noise_seed.key, noise_seed.nonce, first_row,
+                                             mask_len, body_len, bound_log2, add ? 1 : 0, out_dev, len_out, stream));
+}
+// bodies[r] += <mask(first_row + r), lwe_key> + noise(first_row + r): the mask never leaves registers
+template <class W>
+void lwe_encrypt_seeded(int device, const RandSeed &mask_seed, const RandSeed &noise_seed, size_t first_row, const W *lwe_key,
+                        size_t dimension, uint32_t bound_log2, detail::same<W> *bodies, size_t rows) {
+    check(detail::Fns<W>::rand_lwe_encrypt_seeded(device, mask_seed.key, mask_seed.nonce, noise_seed.key, noise_seed.nonce,
+                                                  first_row, lwe_key, dimension, bound_log2, bodies, rows));
+}
+template <class W>
+void lwe_encrypt_seeded_dev(int device, const RandSeed &mask_seed, const RandSeed &noise_seed, size_t first_row,
+                            const W *lwe_key_dev, size_t dimension, uint32_t bound_log2, detail::same<W> *bodies_dev, size_t rows,
+                            void *stream = nullptr) {
+    check(detail::Fns<W>::rand_lwe_encrypt_seeded_dev(device, mask_seed.key, mask_seed.nonce, noise_seed.key, noise_seed.nonce,
+                                                      first_row, lwe_key_dev, dimension, bound_log2, bodies_dev, rows, stream));
+}
+// the full rows of seeded ciphertexts: masks from the stream, bodies copied; what the receiving side runs
+template <class W>
+void seeded_expand(int device, const RandSeed &mask_seed, size_t first_row, size_t mask_len, size_t body_len, const W *bodies,
+                   size_t len_bodies, detail::same<W> *out, size_t len_out) {
+    check(detail::Fns<W>::rand_seeded_expand(device, mask_seed.key, mask_seed.nonce, first_row, mask_len, body_len, bodies,
+                                             len_bodies, out, len_out));
+}
+template <class W>
+void seeded_expand_dev(int device, const RandSeed &mask_seed, size_t first_row, size_t mask_len, size_t body_len,
+                       const W *bodies_dev, size_t len_bodies, detail::same<W> *out_dev, size_t len_out, void *stream = nullptr) {
+    check(detail::Fns<W>::rand_seeded_expand_dev(device, mask_seed.key, mask_seed.nonce, first_row, mask_len, body_len, bodies_dev,
+                                                 len_bodies, out_dev, len_out, stream));
 }
 
 // The batched programmable bootstrap (pfhe_tfhe_bootstrap_*): modulus switch, ACC = X^{-b~} * TV, the blind rotation over

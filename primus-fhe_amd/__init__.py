@@ -30,7 +30,10 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    glwe_keyswitch_dev, glwe_trace, glwe_trace_dev, tfhe_generate_gksk_dev, lwe_embed_glwe,
                    lwe_embed_glwe_dev, TfheLutContext, tfhe_rotate_by_bits, tfhe_rotate_by_bits_dev, tfhe_lut_eval,
                    tfhe_lut_eval_dev, tfhe_lut_table, TfheBitExtractContext, tfhe_extract_bits, tfhe_extract_bits_dev,
-                   tfhe_lut_on_integer_dev, lwe_linear, lwe_linear_dev, tfhe_dense_layer_dev)
+                   tfhe_lut_on_integer_dev, lwe_linear, lwe_linear_dev, tfhe_dense_layer_dev, RandSeed, csprng_keystream_dev,
+                   torus_uniform_dev, torus_binary_dev, torus_ternary_dev, torus_tuniform_dev, tfhe_fill_rows_dev,
+                   lwe_encrypt_seeded, lwe_encrypt_seeded_dev, seeded_expand, seeded_expand_dev,
+                   tfhe_generate_ksk_seeded_dev)
 from .rns import (BaseConverter, BaseConverter32, BigUintApproxSignedBasis, BigUintApproxSignedBasis32, RNSBase, RNSBase32,  # noqa: F401
                   RNSError)
 
@@ -56,4 +59,7 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "glwe_keyswitch", "glwe_keyswitch_dev", "glwe_trace", "glwe_trace_dev", "tfhe_generate_gksk_dev", "lwe_embed_glwe",
            "lwe_embed_glwe_dev", "TfheLutContext", "tfhe_rotate_by_bits", "tfhe_rotate_by_bits_dev", "tfhe_lut_eval",
            "tfhe_lut_eval_dev", "tfhe_lut_table", "TfheBitExtractContext", "tfhe_extract_bits", "tfhe_extract_bits_dev",
-           "tfhe_lut_on_integer_dev", "lwe_linear", "lwe_linear_dev", "tfhe_dense_layer_dev", "build", "lib", "library_path", "status_string"]
+           "tfhe_lut_on_integer_dev", "lwe_linear", "lwe_linear_dev", "tfhe_dense_layer_dev", "RandSeed",
+           "csprng_keystream_dev", "torus_uniform_dev", "torus_binary_dev", "torus_ternary_dev", "torus_tuniform_dev",
+           "tfhe_fill_rows_dev", "lwe_encrypt_seeded", "lwe_encrypt_seeded_dev", "seeded_expand", "seeded_expand_dev",
+           "tfhe_generate_ksk_seeded_dev", "build", "lib", "library_path", "status_string"]

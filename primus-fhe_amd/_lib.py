@@ -287,6 +287,16 @@ def _declare(lib: C.CDLL) -> None:
         for entry in (ll, ll + "_i8"):
             sig(entry + "_dev", ci, ci, vp, sz, sz, vp, sz, sz, sz, vp, sz, vp, sz, vp)
             sig(entry, ci, ci, vp, sz, sz, vp, sz, sz, sz, vp, sz, vp, sz)
+        # the random layer: samplers over the ChaCha20 stream, rows, seeded ciphertexts; keys and nonces are host pointers
+        rd = "pfhe_rand" + ("32" if tp.endswith("32_") else "") + "_"   # a prefix of its own, pfhe_rand_ / pfhe_rand32_
+        for sampler in ("uniform", "binary", "ternary"):
+            sig(rd + sampler + "_dev", ci, ci, vp, vp, sz, vp, sz, vp)
+        sig(rd + "tuniform_dev", ci, ci, vp, vp, sz, u32, vp, sz, vp)
+        sig(rd + "fill_rows_dev", ci, ci, vp, vp, vp, vp, sz, sz, sz, u32, ci, vp, sz, vp)
+        sig(rd + "lwe_encrypt_seeded_dev", ci, ci, vp, vp, vp, vp, sz, vp, sz, u32, vp, sz, vp)
+        sig(rd + "lwe_encrypt_seeded", ci, ci, vp, vp, vp, vp, sz, vp, sz, u32, vp, sz)
+        sig(rd + "seeded_expand_dev", ci, ci, vp, vp, sz, sz, sz, vp, sz, vp, sz, vp)
+        sig(rd + "seeded_expand", ci, ci, vp, vp, sz, sz, sz, vp, sz, vp, sz)
         # the GLWE automorphism / key switch and the trace, both calls of one handle; their keys; the LWE embedding
         gt = tp + "glwe_trace"
         sig(gt + "_create", ci, vp, sz, u32, sz, sz, C.POINTER(vp))
@@ -300,6 +310,7 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "gksk_generate_dev", ci, vp, sz, u32, sz, vp, sz, vp, sz, vp, sz, vp, sz, f64p, sz, vp)
         sig(tp + "lwe_embed_dev", ci, vp, sz, vp, sz, vp, sz, vp)
         sig(tp + "lwe_embed", ci, vp, sz, vp, sz, vp, sz)
+    sig("pfhe_csprng_keystream_dev", ci, ci, vp, vp, sz, vp, sz, vp)   # raw u32 words of the ChaCha20 stream: no width
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)
     sig("pfhe_extprod_profile_dev", ci, vp, vp, sz, vp, sz, vp, sz, C.POINTER(C.c_double), C.POINTER(sz), vp)

@@ -573,8 +573,8 @@ def write_fourier_form(coeff, fourier, fft: FullComplex64FftTable, stream=None) 
 
 
 # ---- key generation, encryption and phase (include/pfhe.h: lwe_body_mac, glwe_body_mac, ggsw_add_gadget, bsk / ksk) ----
-# No call below draws a random number: masks and noise are what the caller put into the buffers (torus_uniform and
-# torus_noise are two ways of doing that).
+# No call below draws a random number: masks and noise are what the caller put into the buffers (tfhe_fill_rows_dev, at the
+# end of this file, fills them from a ChaCha20 stream; torus_uniform and torus_noise are statistical fillers for tests).
 
 def _lwe_body(dev, lwe, key, subtract: int, device, stream=None) -> None:
     _stateless("_lwe_body_mac", dev, (lwe, key), "ciphertexts and key must have the same word width",
@@ -1331,3 +1331,174 @@ def torus_noise(size, bits: int, device="cuda", std=None, bound=None, generator=
                              generator=generator).to(dtype)
     g = torch.empty(size, dtype=torch.float64, device=device).normal_(0.0, float(std), generator=generator)
     return torch.round(g).to(torch.int64).to(dtype)
+
+
+# ---- the random layer: a ChaCha20 stream on the device, samplers, rows, seeded ciphertexts (include/pfhe.h: pfhe_csprng_*,
+# pfhe_rand{,32}_*) ----
+
+class RandSeed:
+    """The identity of one ChaCha20 stream: a 32-byte key and a 64-bit nonce (the key's bytes are the state words 4..11
+    little-endian, as in RFC 8439; the nonce is state words 14 and 15).  Every output of every sampler is a closed form of
+    (key, nonce, index), so the same seed gives the same words in any call, of any length, on any launch.
+
+    The library gathers NO entropy of its own: `key` is the caller's, and fresh() takes it from os.urandom.  A mask seed
+    may be published (a seeded ciphertext carries it); a noise seed is a secret and must differ from the mask seed in key
+    or nonce.  Neither repr() nor an error message shows a key."""
+
+    def __init__(self, key: bytes, nonce: int = 0):
+        if not isinstance(key, (bytes, bytearray)) or len(key) != 32:
+            raise ValueError("the key must be 32 bytes")
+        if not 0 <= int(nonce) < 1 << 64:
+            raise ValueError("the nonce must be in 0..2^64-1")
+        self.nonce = int(nonce)
+        self._key = (C.c_uint32 * 8)(*(int.from_bytes(key[4 * i:4 * i + 4], "little") for i in range(8)))
+        self._nonce = (C.c_uint32 * 2)(self.nonce & 0xffffffff, self.nonce >> 32)
+
+    @classmethod
+    def fresh(cls, nonce: int = 0) -> "RandSeed":
+        """a seed whose key is 32 bytes of os.urandom: the operating system's entropy, not the library's"""
+        import os
+        return cls(os.urandom(32), nonce)
+
+    def with_nonce(self, nonce: int) -> "RandSeed":
+        """the same key under another nonce: an independent stream"""
+        return RandSeed(b"".join(int(w).to_bytes(4, "little") for w in self._key), nonce)
+
+    def __repr__(self) -> str:
+        return "RandSeed(key=<32 bytes>, nonce=%d)" % self.nonce
+
+    def _args(self):
+        return C.cast(self._key, C.c_void_p), C.cast(self._nonce, C.c_void_p)
+
+
+def _seed_args(*seeds):
+    for s in seeds:
+        if not isinstance(s, RandSeed):
+            raise TypeError("expected a RandSeed")
+    return tuple(a for s in seeds for a in s._args())
+
+
+def csprng_keystream_dev(seed: RandSeed, word_offset: int, out, device=None, stream=None) -> None:
+    """u32 words [word_offset, word_offset + out.numel()) of the seed's ChaCha20 stream into a 32-bit integer CUDA tensor:
+    word j is little-endian word j mod 16 of block j div 16.  Asynchronous."""
+    po, no, w = _dev_words(out)
+    if w != "32":
+        raise TypeError("the keystream is written as 32-bit words")
+    check(lib().pfhe_csprng_keystream_dev(_dev_index(out, device), *_seed_args(seed), word_offset, po, no, _stream(stream)))
+
+
+def _sampler(name, seed, offset, out, device, stream, *lead) -> None:
+    po, no, w = _dev_words(out)
+    check(getattr(lib(), "pfhe_rand" + w + "_" + name + "_dev")(_dev_index(out, device), *_seed_args(seed), offset, *lead, po,
+                                                             no, _stream(stream)))
+
+
+def torus_uniform_dev(seed: RandSeed, offset: int, out, device=None, stream=None) -> None:
+    """out[i] = stream word offset + i of the tensor's width (32- or 64-bit integer CUDA tensor; a u64 stream word is u32
+    words 2j, low half, and 2j + 1): uniform torus words from a cryptographic stream.  Asynchronous."""
+    _sampler("uniform", seed, offset, out, device, stream)
+
+
+def torus_binary_dev(seed: RandSeed, offset: int, out, device=None, stream=None) -> None:
+    """out[i] = bit (offset + i) mod 32 of u32 stream word (offset + i) div 32, as a torus word 0 or 1: the values of
+    sample_binary_values_to (primus_distr/src/common.rs:22-42) on the same word stream.  Asynchronous."""
+    _sampler("binary", seed, offset, out, device, stream)
+
+
+def torus_ternary_dev(seed: RandSeed, offset: int, out, device=None, stream=None) -> None:
+    """out[i] = [0, 0, 1, -1][(w >> 2 (j mod 16)) & 3] with j = offset + i and w u32 stream word j div 16, -1 the all-ones
+    word: sample_ternary_values_to (common.rs:56-76).  Asynchronous."""
+    _sampler("ternary", seed, offset, out, device, stream)
+
+
+def torus_tuniform_dev(seed: RandSeed, offset: int, bound_log2: int, out, device=None, stream=None) -> None:
+    """Bounded noise TUniform(b), b = bound_log2 in 0..BITS-2: out[i] takes u64 stream word offset + i at both widths, r its
+    low b + 2 bits, and is (r >> 1) + (r & 1) - 2^b modulo 2^BITS: support [-2^b, 2^b], the two ends with probability
+    2^-(b+2), every other value 2^-(b+1), variance (2^(2b+1) + 1) / 6.  Asynchronous."""
+    _sampler("tuniform", seed, offset, out, device, stream, bound_log2)
+
+
+def tfhe_fill_rows_dev(mask_seed: RandSeed, noise_seed: RandSeed, first_row: int, mask_len: int, body_len: int,
+                       bound_log2: int, out, add: bool = False, device=None, stream=None) -> None:
+    """The randomness of whole ciphertext rows in one launch: out holds rows x (mask_len + body_len) words; for absolute row
+    R = first_row + r, mask word j is uniform output R*mask_len + j of the mask stream and body word j gets TUniform(bound_log2)
+    output R*body_len + j of the noise stream, stored, or added when `add` (so that messages can be placed first).  LWE rows
+    are (n, 1), GLWE rows (k*N, N); the `rand` argument of tfhe_generate_bsk_dev, _ksk_dev, _pksk_dev, _pfksk_dev and
+    _gksk_dev is rows of one of the two.  Rows [a, a + b) written alone are that slice of rows [0, R).  The two seeds must
+    differ.  Asynchronous."""
+    po, no, w = _dev_words(out)
+    check(getattr(lib(), "pfhe_rand" + w + "_fill_rows_dev")(_dev_index(out, device), *_seed_args(mask_seed, noise_seed),
+                                                           first_row, mask_len, body_len, bound_log2, int(bool(add)), po, no,
+                                                           _stream(stream)))
+
+
+def _encrypt_seeded(dev, mask_seed, noise_seed, first_row, key, bound_log2, bodies, device, stream=None) -> None:
+    words = _dev_words if dev else _host_words
+    pk, nk, wk = words(key)
+    pb, nb, wb = words(bodies)
+    w = _same_width("key and bodies must have the same word width", wk, wb)
+    tail = (_stream(stream),) if dev else ()
+    check(getattr(lib(), "pfhe_rand" + w + "_lwe_encrypt_seeded" + ("_dev" if dev else ""))(
+        _dev_index(bodies, device) if dev else device, *_seed_args(mask_seed, noise_seed), first_row, pk, nk, bound_log2, pb,
+        nb, *tail))
+
+
+def lwe_encrypt_seeded(mask_seed: RandSeed, noise_seed: RandSeed, first_row: int, key: np.ndarray, bound_log2: int,
+                       bodies: np.ndarray, device: int = 0) -> None:
+    """Seeded LWE encryption on host arrays, in place: bodies[r] += <mask(R), key> + noise(R) for R = first_row + r, where
+    mask(R) is uniform outputs [R*n, (R+1)*n) of the mask stream (n = len(key)) and noise(R) TUniform(bound_log2) output R of
+    the noise stream.  bodies holds the encoded messages on entry and the ciphertext bodies on exit: with (mask_seed,
+    first_row) they ARE the ciphertexts, one word each instead of n + 1.  The mask is generated in registers and never
+    stored; the result is word for word tfhe_fill_rows_dev(add=True) followed by lwe_encrypt_dev.  The key is any words."""
+    _encrypt_seeded(False, mask_seed, noise_seed, first_row, key, bound_log2, bodies, device)
+
+
+def lwe_encrypt_seeded_dev(mask_seed: RandSeed, noise_seed: RandSeed, first_row: int, key, bound_log2: int, bodies,
+                           device=None, stream=None) -> None:
+    """the device form, asynchronous; the key must not overlap the bodies"""
+    _encrypt_seeded(True, mask_seed, noise_seed, first_row, key, bound_log2, bodies, device, stream)
+
+
+def _seeded_expand(dev, mask_seed, first_row, mask_len, body_len, bodies, out, device, stream=None) -> None:
+    words = _dev_words if dev else _host_words
+    pb, nb, wb = words(bodies)
+    po, no, wo = words(out)
+    w = _same_width("bodies and out must have the same word width", wb, wo)
+    tail = (_stream(stream),) if dev else ()
+    check(getattr(lib(), "pfhe_rand" + w + "_seeded_expand" + ("_dev" if dev else ""))(
+        _dev_index(out, device) if dev else device, *_seed_args(mask_seed), first_row, mask_len, body_len, pb, nb, po, no,
+        *tail))
+
+
+def seeded_expand(mask_seed: RandSeed, first_row: int, mask_len: int, body_len: int, bodies: np.ndarray, out: np.ndarray,
+                  device: int = 0) -> None:
+    """What the receiving side of seeded ciphertexts runs, on host arrays: out becomes rows x (mask_len + body_len) words,
+    the masks from the mask stream (as tfhe_fill_rows_dev writes them) and the bodies copied from `bodies` (rows x body_len
+    words).  It takes no noise seed."""
+    _seeded_expand(False, mask_seed, first_row, mask_len, body_len, bodies, out, device)
+
+
+def seeded_expand_dev(mask_seed: RandSeed, first_row: int, mask_len: int, body_len: int, bodies, out, device=None,
+                      stream=None) -> None:
+    """the device form, asynchronous; out must not overlap bodies and may be uninitialised"""
+    _seeded_expand(True, mask_seed, first_row, mask_len, body_len, bodies, out, device, stream)
+
+
+def tfhe_generate_ksk_seeded_dev(mask_seed: RandSeed, noise_seed: RandSeed, key_in, key_out, basis: ApproxSignedBasis,
+                                 bound_log2: int, first_row: int = 0, device=None, stream=None):
+    """The key-switch key lwe_keyswitch_dev takes, in seeded form: len(key_in) * ell words instead of len(key_in) * ell *
+    (len(key_out) + 1).  Row (i, j) is absolute row first_row + i*ell + j of the two streams; its body starts as the message
+    key_in[i] * 2^(drop_bits + j*log_basis) (placed by torch) and lwe_encrypt_seeded_dev adds <mask, key_out> + noise.
+    seeded_expand_dev(mask_seed, first_row, len(key_out), 1, bodies, ksk) then gives exactly what tfhe_generate_ksk_dev makes
+    of tfhe_fill_rows_dev's buffer.  Returns the bodies (allocates them).  Asynchronous on `stream`'s device; torch places the
+    messages on its current stream."""
+    import torch
+    _, _, wi = _dev_words(key_in)
+    _, _, wo = _dev_words(key_out)
+    _basis_args(basis, _same_width("both keys must have the same word width", wi, wo))
+    bits, half = basis.bits, 1 << (basis.bits - 1)
+    factors = [1 << (basis.drop_bits() + j * basis.log_basis()) for j in range(basis.decompose_length())]
+    gadget = torch.tensor([f - (1 << bits) if f >= half else f for f in factors], dtype=key_in.dtype, device=key_in.device)
+    bodies = (key_in.reshape(-1, 1) * gadget.reshape(1, -1)).reshape(-1).contiguous()   # wrapping products modulo 2^BITS
+    lwe_encrypt_seeded_dev(mask_seed, noise_seed, first_row, key_out, bound_log2, bodies, device, stream)
+    return bodies
