@@ -1,7 +1,8 @@
 """The model of the random layer (tests/csprng_model.py) held against what it restates: the RFC 8439 §2.3.2 block, a keystream
 written by openssl (tests/golden/chacha20_keystream.json, one case crossing block counter 2^32), the reference's binary and
-ternary loops restated literally over the model's next_u32, and the stated probabilities of TUniform by exhaustive
-enumeration.  No GPU, no library."""
+ternary loops restated literally over the model's next_u32, the stated probabilities of TUniform by exhaustive
+enumeration, and the array forms at far positions (a sampler's own counter carry, a counter with bits in both words, the last
+legal index) against the block function and the sampler's rule on single outputs.  No GPU, no library."""
 import json
 import os
 from collections import Counter
@@ -148,6 +149,74 @@ def test_tuniform_at_the_largest_bound(bits):
     assert cm.tuniform_value(1, b, bits) == (1 << bits) - (1 << b) + 1
     with pytest.raises(AssertionError):
         cm.tuniform_value(0, b + 1, bits)
+
+
+# ---- far positions: what tests/test_gpu_csprng_edges.py trusts the model at ----
+
+NONCE = 0xfedcba9876543210
+CAP = (1 << 64) - (1 << 20)                      # the largest output index a call may end at
+BOTH = 0x89abcdef01234567                        # a block counter with bits set in both state words
+PER = {("uniform", 32): 16, ("uniform", 64): 8, ("tuniform", 32): 8, ("tuniform", 64): 8, ("binary", 32): 512,
+       ("binary", 64): 512, ("ternary", 32): 256, ("ternary", 64): 256}
+
+
+def u32_word(j):
+    """u32 stream word j from block() alone"""
+    return cm.block(KEY, NONCE, j // 16)[j % 16]
+
+
+def output_by_the_rule(name, i, bits, b):
+    """output i of a sampler from block() and §26's rule, in Python integers; no array code of the model is used"""
+    if name == "binary":
+        return (u32_word(i // 32) >> (i % 32)) & 1
+    if name == "ternary":
+        return [0, 0, 1, (1 << bits) - 1][(u32_word(i // 16) >> (2 * (i % 16))) & 3]
+    if name == "uniform" and bits == 32:
+        return u32_word(i)
+    word = u32_word(2 * i) | u32_word(2 * i + 1) << 32
+    if name == "uniform":
+        return word
+    r = word & ((1 << (b + 2)) - 1)
+    return ((r >> 1) + (r & 1) - (1 << b)) % (1 << bits)
+
+
+@pytest.mark.parametrize("bits", [32, 64])
+@pytest.mark.parametrize("name", ["uniform", "binary", "ternary", "tuniform"])
+def test_single_outputs_at_far_positions_follow_from_the_block_function(bits, name):
+    """the array forms at the sampler's own counter carry, at a counter with bits in both words and at the last legal index
+    are block() and the sampler's rule on one output each; Python integers carry the offsets and blocks() wraps the counter"""
+    per = PER[name, bits]
+    carry = ((1 << 32) - 1) * per + per - 3
+    both = (BOTH % ((CAP - 8) // per)) * per + 5
+    assert (both // per) >> 32 > 1 << 16 and ((both // per) & cm.MASK32) > 1 << 16
+    for b in ((0, bits - 2) if name == "tuniform" else (None,)):
+        sample = (lambda off, n: cm.tuniform(KEY, NONCE, off, b, n, bits)) if name == "tuniform" else \
+                 (lambda off, n: getattr(cm, name)(KEY, NONCE, off, n, bits))
+        for offset, n in ((carry, 7), (both, 3), (CAP - 3, 3)):
+            got = sample(offset, n)
+            assert got.dtype == (np.uint32 if bits == 32 else np.uint64) and got.size == n
+            assert [int(v) for v in got] == [output_by_the_rule(name, offset + j, bits, b) for j in range(n)], (offset, b)
+        assert carry // per == (1 << 32) - 1 and (carry + 6) // per == 1 << 32          # the seven outputs cross the carry
+        # the last legal index, written out: output 2^64 - 2^20 - 1 sits in block (2^64 - 2^20 - 1) div per
+        last = (1 << 64) - (1 << 20) - 1
+        assert int(sample(last, 1)[0]) == output_by_the_rule(name, last, bits, b)
+    if name == "uniform" and bits == 32:
+        blk = cm.block(KEY, NONCE, (1 << 60) - (1 << 16) - 1)
+        assert int(cm.uniform(KEY, NONCE, (1 << 64) - (1 << 20) - 1, 1, 32)[0]) == blk[15]
+        assert u32_word(carry + 3) == cm.block(KEY, NONCE, 1 << 32)[0] != cm.block(KEY, NONCE, 0)[0]
+
+
+@pytest.mark.parametrize("bits", [32, 64])
+def test_fill_rows_at_a_far_first_row_is_two_flat_ranges(bits):
+    mk, nk = KEY, bytes(range(1, 33))
+    for mask_len, body_len, first in ((7, 3, (1 << 40) + 12345), (630, 1, (1 << 35) - 2), (128, 64, CAP // 128 - 5)):
+        rows = 5
+        got = cm.fill_rows(mk, 3, nk, 4, first, mask_len, body_len, bits - 2, rows, bits)
+        assert got.shape == (rows, mask_len + body_len)
+        assert np.array_equal(got[:, :mask_len].reshape(-1), cm.uniform(mk, 3, first * mask_len, rows * mask_len, bits))
+        assert np.array_equal(got[:, mask_len:].reshape(-1),
+                              cm.tuniform(nk, 4, first * body_len, bits - 2, rows * body_len, bits))
+        assert np.array_equal(cm.fill_rows(mk, 3, nk, 4, first + 1, mask_len, body_len, bits - 2, 3, bits), got[1:4])
 
 
 def test_fill_rows_is_two_flat_ranges():
