@@ -473,6 +473,7 @@ __global__ __launch_bounds__(BlockCfg<LOGB>::THREADS) __attribute__((amdgpu_wave
 // (strided first); inverse: A = tile k, B = tile k-1 (block first).  Both tiles start at a multiple of L polynomials,
 // so block i and chunk i belong to the same limb (16 blocks and 16 chunks per limb-polynomial).
 // ------------------------------------------------------------------------------------------
+// (The forward kernels of PmArith and MontArith tables take the PARKED form of this pair instead, ntt_pipe_parked_body below.)
 // Register budgets: both directions run at four waves per SIMD without spilling — the forward instantiations in 124
 // registers (5.00-5.01 against 5.06 ms per 12 288 transforms at three waves), the inverse ones in 128 once the strided
 // chunk's loads are issued in front of the block pass's LAST register pass (block_pass_body; issued after the staging
@@ -535,11 +536,120 @@ __device__ __forceinline__ void ntt_pipe_body(
     }
 }
 
+// The forward form with the chunk in registers (four workgroups per CU): the policies the parked form below does not serve.
 template <class A, int LOGB>
-__global__ __launch_bounds__(BlockCfg<LOGB>::THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ntt_pipe_fwd_kernel(
+__global__ __launch_bounds__(BlockCfg<LOGB>::THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ntt_pipe_fwd_regs_kernel(
     u64 *__restrict__ blk_data, u64 blk_total, u64 *__restrict__ str_data, u64 str_total,
     const NttPrime *__restrict__ primes, u32 L, u32 lazy) {
     ntt_pipe_body<A, LOGB, false, false>(blk_data, blk_total, str_data, str_total, primes, L, lazy, nullptr, 0);
+}
+
+// ------------------------------------------------------------------------------------------
+// The PARKED forward form: five workgroups per CU instead of four (PipeParked, pfhe_ntt_device.hpp).  The same pairs, the
+// same butterflies in the same order; what changes is where the words wait.
+//   * the block's two exchanges run in halves through 18 432 bytes (parked_exchange_8_4 across the workgroup,
+//     parked_exchange_4_0 inside each wave);
+//   * once every wave has read its second exchange (one workgroup barrier) the image is dead, and each wave fetches rows
+//     0-14 of ITS 64 columns of the chunk into a private 7680-byte region of it by LDS-DMA — seven 16-byte loads of two
+//     rows each (lanes 0-31 one row, lanes 32-63 the next) and two 4-byte loads for row 14; row 15 is an ordinary load
+//     into two VGPRs.  They are in flight during the block's last register pass;
+//   * the wave then waits for its own loads (nobody else reads them: no barrier), reads the fifteen rows back — lane l
+//     its own column, [row][lane], conflict-free — and only then stages the block's output through the same region,
+//     32 lanes' worth at a time, into 1 KiB store instructions;
+//   * four strided stages and sixteen stores as before.
+// ------------------------------------------------------------------------------------------
+template <class A>
+__device__ __forceinline__ void ntt_pipe_parked_body(u64 *__restrict__ blk_data, u64 blk_total, u64 *__restrict__ str_data,
+                                                     u64 str_total, const NttPrime *__restrict__ primes, u32 L, u32 lazy) {
+    constexpr int LOGB = 12, K = 4;
+    static_assert(!A::kPacked && BlockCfg<LOGB>::THREADS == 256, "four waves of sixteen 64-bit coefficients");
+    constexpr u32 log_n = LOGB + K, n = 1u << log_n;
+    extern __shared__ __attribute__((aligned(16))) u64 lds_raw[];
+    const u64 chunk = blockIdx.x;
+    const bool has_str = chunk < str_total, has_blk = chunk < blk_total;
+    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    u64 *__restrict__ park = lds_raw + wave * PipeParked::kWaveWords;
+    u64 *__restrict__ cp = str_data + (chunk >> 4) * n + (chunk & 15) * 256u;  // the chunk: row 0, column 0
+    u64 row15 = 0;
+    const auto issue = [&]() {
+        if (!has_str) return;
+        const u32 t = opaque_tid(), lane = t & 63u;
+        const u32 dst = __builtin_amdgcn_readfirstlane((u32)(size_t)(__attribute__((address_space(3))) u64 *)park);
+        const u64 *g = cp + ((u64)(lane >> 5) << LOGB) + wave * 64u + 2u * (lane & 31u);
+#pragma unroll
+        for (u32 j = 0; j < 7; ++j) glds16_nt(g + ((u64)(2 * j) << LOGB), dst + j * 1024u);
+        const char *g14 = reinterpret_cast<const char *>(cp + (14ull << LOGB) + wave * 64u) + 4u * lane;
+        glds4_nt(g14, dst + 14u * 512u);
+        glds4_nt(g14 + 256, dst + 14u * 512u + 256u);
+        row15 = __builtin_nontemporal_load(cp + (15ull << LOGB) + t);
+    };
+    u64 x[16];
+    if (has_blk) {
+        const A ar(primes + (u32)((chunk >> 4) % L));
+        const u32 eblk = (u32)(chunk & 15) << LOGB;
+        const u64 *__restrict__ g = blk_data + (chunk << LOGB) + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) x[k] = __builtin_nontemporal_load(g + ((u32)k << (LOGB - 4)));
+        u32 lt = threadIdx.x;
+        fwd_regpass<A, 8, 3, 0, true>(ar, x, n + eblk + layout<8>(lt, 0), n);
+        asm volatile("" : "+v"(lt));  // (fwd_chain: each pass's addresses are computed where they are used)
+        parked_exchange_8_4(x, lds_raw, lt, wave);
+        fwd_regpass<A, 4, 3, 0, true>(ar, x, n + eblk + layout<4>(lt, 0), n);
+        asm volatile("" : "+v"(lt));
+        parked_exchange_4_0(x, lds_raw + PipeParked::slice(wave), lt & 63u);
+        __syncthreads();  // every wave has read its last exchange: the image is dead
+        issue();
+        fwd_regpass<A, 0, 3, 0, true>(ar, x, n + eblk + layout<0>(lt, 0), n);
+        block_forward_finish<A>(ar, x, n, eblk, lt, lazy != 0);
+    } else {
+        issue();  // (the first launch: nothing has used the LDS)
+    }
+    u64 sx[1 << K][1];
+    if (has_str) {
+        // this wave's own loads, with no store pending yet: the block's stores below are never waited for
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(row15) : : "memory");
+        const u64 *__restrict__ pk = park + (opaque_tid() & 63u);
+#pragma unroll
+        for (int k = 0; k < PipeParked::kRows; ++k) sx[k][0] = pk[k * 64];
+        sx[15][0] = row15;
+    }
+    if (has_blk) {
+        const u32 lane = opaque_tid() & 63u;
+        const GVec2Ptr gw = (GVec2Ptr)(void *)(blk_data + (chunk << LOGB) + wave * 1024u) + lane;
+        u64 *__restrict__ wr = park + lds_phi((lane & 31u) << 4);
+        const u64 *__restrict__ rd = park + lds_phi(2 * lane);
+#pragma unroll
+        for (u32 h = 0; h < 2; ++h) {
+            wave_sync_lds();  // the reads of the parked rows / of the first half are older than these writes
+            if ((lane >> 5) == h) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) wr[k] = x[k];
+            }
+            wave_sync_lds();
+            u64x2 io[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) io[j] = *reinterpret_cast<const u64x2 *>(rd + lds_voff<LOGB>(j));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) __builtin_nontemporal_store(io[j], gw + 256u * h + 64u * j);
+        }
+    }
+    if (has_str) {
+        const A ar(primes + (u32)((chunk >> 4) % L));
+        strided_forward_regs<A, K, 1, true>(ar, sx, n, 0u, LOGB);
+        u64 *__restrict__ sp = cp + opaque_tid();
+#pragma unroll
+        for (int k = 0; k < (1 << K); ++k) gstore<kPipeIntermediateNt>(sp + ((u64)k << LOGB), sx[k][0]);
+    }
+}
+
+// (the attributes take no template arguments: one kernel per register budget)
+template <class A> constexpr bool kPipeFwdParked = std::is_same<A, PmArith>::value || std::is_same<A, MontArith>::value;
+template <class A, int LOGB>
+__global__ __launch_bounds__(BlockCfg<LOGB>::THREADS) __attribute__((amdgpu_waves_per_eu(5, 5), amdgpu_num_vgpr(96))) void ntt_pipe_fwd_kernel(
+    u64 *__restrict__ blk_data, u64 blk_total, u64 *__restrict__ str_data, u64 str_total,
+    const NttPrime *__restrict__ primes, u32 L, u32 lazy) {
+    static_assert(LOGB == 12 && kPipeFwdParked<A>, "the parked form: blocks of 2^12 words");
+    ntt_pipe_parked_body<A>(blk_data, blk_total, str_data, str_total, primes, L, lazy);
 }
 template <class A, int LOGB, bool MUL>
 __global__ __launch_bounds__(BlockCfg<LOGB>::THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ntt_pipe_inv_kernel(
@@ -1151,9 +1261,13 @@ static int transform_pipelined(const NttPrime *primes, u32 L, u64 *data, u64 npo
         if (inverse)
             PFHE_TRY((launch<ntt_pipe_inv_kernel<A, LOGB, false>>(grid, threads, lds_bytes, s, b.ptr, b.blocks, st.ptr, st.blocks,
                                                                   primes, L, lazy ? 1u : 0u, b.mul, b.mul_polys)));
+        else if constexpr (kPipeFwdParked<A>)
+            // (PipeParked static_asserts kLdsBytes <= 31 744, what a fifth workgroup per CU leaves; the kernel has no static LDS)
+            PFHE_TRY((launch<ntt_pipe_fwd_kernel<A, LOGB>>(grid, threads, (size_t)PipeParked::kLdsBytes, s, b.ptr, b.blocks, st.ptr,
+                                                           st.blocks, primes, L, lazy ? 1u : 0u)));
         else
-            PFHE_TRY((launch<ntt_pipe_fwd_kernel<A, LOGB>>(grid, threads, lds_bytes, s, b.ptr, b.blocks, st.ptr, st.blocks, primes,
-                                                           L, lazy ? 1u : 0u)));
+            PFHE_TRY((launch<ntt_pipe_fwd_regs_kernel<A, LOGB>>(grid, threads, lds_bytes, s, b.ptr, b.blocks, st.ptr, st.blocks,
+                                                                primes, L, lazy ? 1u : 0u)));
     }
     return PFHE_OK;
 }

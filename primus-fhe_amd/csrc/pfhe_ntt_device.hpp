@@ -969,25 +969,11 @@ __device__ __forceinline__ void fwd_chain(const A &ar, u64 (&x)[1 << LOGE], u64 
     }
 }
 
-// forward compute core: x holds layout<LOGB-LOGE> on entry and layout<0> (canonical unless lazy) on exit
-// LEAD = false: the caller filled x by lds_get_layout<LOGB-LOGE> from this LDS region (so the first exchange, too,
-// only overwrites slots its own thread read last) and needs no barrier in front of it.
-// RAW (only with lazy): the output feeds a product with a second data word on chip (PmArith::mul_full, Barrett) instead of
-// leaving the kernel, so the reference's [0,4q) contract of lazy outputs does not apply.  Wide policies then fold at EVEN
-// distances — the last stage, distance 1, folds its x input — and return x' = X + T, y' = X + 3q - T < 4U + 2^31 as they
-// are: below 2^63 + 2^32, which mul_full takes (its partial sums need y1 <= 2^31), and the finishing fold of every
-// coefficient (4 instructions each) is gone.  The stage in front of the core must have folded (inputs below 4U + 2^31):
-// true for canonical / [0,4q) inputs and behind a strided pass, whose last stage folds.  Montgomery tables skip their
-// closing reduction the same way (values below 2^63 + 3q; the Barrett product takes any 64-bit word).
-template <class A, int LOGB, bool LEAD = true, int LOGE = 4, class Late = NoLateHook, bool RAW = false>
-__device__ __forceinline__ void block_forward_core(const A &ar, u64 (&x)[1 << LOGE], u64 *__restrict__ lds, u32 n,
-                                                   u32 eblk, u32 lt, bool lazy, Late before_last = Late()) {
-    constexpr int POS0 = LOGB - LOGE, E = 1 << LOGE;
-    constexpr bool UNI = BlockCfg<LOGB, LOGE>::TPB >= 64;  // a wave never straddles two blocks
-    constexpr bool EVEN = RAW && A::kWide;
-    fwd_regpass<A, POS0, LOGE - 1, 0, UNI, LOGE, EVEN>(ar, x, n + eblk + layout<POS0, LOGE>(lt, 0), n);
-    fwd_chain<A, LOGB, POS0, LEAD, LOGE, Late, EVEN>(ar, x, lds, n, eblk, lt, before_last);
-    if constexpr (RAW && (A::kWide || A::kMont)) return;
+// the end of a forward block pass, x in layout <0>: the packed policies' distance-1 stage, then the reduction the caller
+// asked for (canonical unless lazy)
+template <class A, int LOGE = 4>
+__device__ __forceinline__ void block_forward_finish(const A &ar, u64 (&x)[1 << LOGE], u32 n, u32 eblk, u32 lt, bool lazy) {
+    constexpr int E = 1 << LOGE;
     if constexpr (A::kPacked) {  // distance-1 stage between the halves of each word
         if constexpr (LOGE == 4) {  // lane-ordered twiddles: slot 15 + k of group (eblk >> 4) + lt
             const u32 off0 = 15u * (n >> 4) + (eblk >> 4) + lt;
@@ -1013,6 +999,28 @@ __device__ __forceinline__ void block_forward_core(const A &ar, u64 (&x)[1 << LO
 #pragma unroll
         for (int k = 0; k < E; ++k) x[k] = ar.reduce_4q(x[k]);
     }
+}
+
+// forward compute core: x holds layout<LOGB-LOGE> on entry and layout<0> (canonical unless lazy) on exit
+// LEAD = false: the caller filled x by lds_get_layout<LOGB-LOGE> from this LDS region (so the first exchange, too,
+// only overwrites slots its own thread read last) and needs no barrier in front of it.
+// RAW (only with lazy): the output feeds a product with a second data word on chip (PmArith::mul_full, Barrett) instead of
+// leaving the kernel, so the reference's [0,4q) contract of lazy outputs does not apply.  Wide policies then fold at EVEN
+// distances — the last stage, distance 1, folds its x input — and return x' = X + T, y' = X + 3q - T < 4U + 2^31 as they
+// are: below 2^63 + 2^32, which mul_full takes (its partial sums need y1 <= 2^31), and the finishing fold of every
+// coefficient (4 instructions each) is gone.  The stage in front of the core must have folded (inputs below 4U + 2^31):
+// true for canonical / [0,4q) inputs and behind a strided pass, whose last stage folds.  Montgomery tables skip their
+// closing reduction the same way (values below 2^63 + 3q; the Barrett product takes any 64-bit word).
+template <class A, int LOGB, bool LEAD = true, int LOGE = 4, class Late = NoLateHook, bool RAW = false>
+__device__ __forceinline__ void block_forward_core(const A &ar, u64 (&x)[1 << LOGE], u64 *__restrict__ lds, u32 n,
+                                                   u32 eblk, u32 lt, bool lazy, Late before_last = Late()) {
+    constexpr int POS0 = LOGB - LOGE;
+    constexpr bool UNI = BlockCfg<LOGB, LOGE>::TPB >= 64;  // a wave never straddles two blocks
+    constexpr bool EVEN = RAW && A::kWide;
+    fwd_regpass<A, POS0, LOGE - 1, 0, UNI, LOGE, EVEN>(ar, x, n + eblk + layout<POS0, LOGE>(lt, 0), n);
+    fwd_chain<A, LOGB, POS0, LEAD, LOGE, Late, EVEN>(ar, x, lds, n, eblk, lt, before_last);
+    if constexpr (RAW && (A::kWide || A::kMont)) return;
+    block_forward_finish<A, LOGE>(ar, x, n, eblk, lt, lazy);
 }
 
 // before_last runs in front of the last register pass (uniform twiddles: the pass with the fewest live registers)
@@ -1167,6 +1175,114 @@ __device__ __forceinline__ void lds_get_vectors(u64x2 (&v)[1 << (LOGE - 1)], con
     } else {
 #pragma unroll
         for (int j = 0; j < NV; ++j) v[j] = *reinterpret_cast<const u64x2 *>(lds + lds_phi(2 * (lt + TPB * j)));
+    }
+}
+
+// ---- the parked form of the pipelined forward kernel (pfhe_ntt.hip, ntt_pipe_parked_body): five workgroups per CU.
+// LDS is granted in 1280-byte granules, so a fifth resident workgroup leaves each 31 744 bytes: the padded image of a whole
+// 2^12 block (36 864) does not fit, the padded image of HALF a block (18 432) does, and so do fifteen of the sixteen rows of
+// the strided chunk (15 x 256 x 8 = 30 720), which the kernel parks there by LDS-DMA instead of holding them in 30 VGPRs.
+struct PipeParked {
+    static constexpr int kRows = 15;                                 // parked rows; the sixteenth stays in two VGPRs
+    static constexpr u32 kHalfWords = BlockCfg<11>::LDS_WORDS;       // padded image of 2^11 words (the half-exchanges)
+    static constexpr u32 kSliceWords = BlockCfg<9>::LDS_WORDS;       // padded image of 2^9 words (a wave's wave-local halves)
+    static constexpr u32 kWaveWords = kRows * 64;                    // a wave's parked region, [row][lane]
+    static constexpr u32 kLdsBytes = 4 * kWaveWords * (u32)sizeof(u64);  // dynamic LDS of the launch
+    static constexpr u32 kLdsPerWgAtFive = 31744;
+    // word offset of wave w's slice for the second (wave-local) exchange and the output staging of its halves: waves 2 and 3
+    // inside the half-image rows they alone read in the first exchange, waves 0 and 1 behind the half-image
+    __device__ static __forceinline__ u32 slice(u32 wave) {
+        return wave < 2 ? kHalfWords + kSliceWords * wave : (wave - 2) * (kHalfWords / 2);
+    }
+    static_assert(kHalfWords + 2 * kSliceWords <= kLdsBytes / sizeof(u64), "the slices of waves 0 and 1 lie inside the allocation");
+    static_assert(kSliceWords <= kWaveWords, "the output staging of half a wave fits the wave's parked region");
+    static_assert(kLdsBytes <= kLdsPerWgAtFive, "five workgroups per CU");
+};
+
+// LDS-DMA: every lane's 16 (4) bytes at gsrc land at lds_dst + lane * 16 (4) — no destination registers, no ds_write.  Inline
+// asm: the compiler neither counts these loads nor waits for them; the issuing wave does (s_waitcnt vmcnt) before it reads
+// the bytes back.  M0 (the LDS base) is saved and restored inside the statement.
+__device__ __forceinline__ void glds16_nt(const void *gsrc, u32 lds_dst) {
+    u32 keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(lds_dst)
+                 : "memory");
+}
+__device__ __forceinline__ void glds4_nt(const void *gsrc, u32 lds_dst) {
+    u32 keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off nt\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(gsrc), "s"(lds_dst)
+                 : "memory");
+}
+
+__device__ __forceinline__ void wave_sync_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// layout <8> -> <4> of a 2^12 block (256 threads x 16) through the image of HALF a block.  Register k of the writer is
+// element (k << 8) + lt, which the reader lt' with lt' >> 4 == k takes: the top bit of k selects the reading half of the
+// workgroup.  All threads write registers 0-7, waves 0 and 1 read their sixteen words; then registers 8-15 for waves 2
+// and 3.  The early readers keep eight new words aside until their own registers 8-15 have been written.
+__device__ __forceinline__ void parked_exchange_8_4(u64 (&x)[16], u64 *__restrict__ img, u32 lt, u32 wave) {
+    u64 *__restrict__ wr = img + lds_phi(lt);
+    const u64 *__restrict__ rd = img + lds_phi(layout<4>(lt & 127u, 0));
+    const bool early = wave < 2;
+    u64 t[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wr[lds_koff<8>(k)] = x[k];
+    __syncthreads();
+    if (early) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            x[k] = rd[lds_koff<4>(k)];
+            t[k] = rd[lds_koff<4>(k + 8)];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wr[lds_koff<8>(k)] = x[k + 8];
+    __syncthreads();
+    if (early) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k + 8] = t[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) x[k] = rd[lds_koff<4>(k)];
+    }
+}
+
+// layout <4> -> <0> inside one wave (1024 words: element ((l >> 4) << 8) | (k << 4) | (l & 15) of lane l goes to lane
+// e >> 4) through a wave-private padded image of 512 words: the top bit of k is bit 3 of the reading lane.  Words with
+// bit 7 clear first, read by the lanes with bit 3 clear; then the others.  The image index drops bit 7 of the element.
+__device__ __forceinline__ void parked_exchange_4_0(u64 (&x)[16], u64 *__restrict__ img, u32 lane) {
+    u64 *__restrict__ wr = img + lds_phi(((lane >> 4) << 7) | (lane & 15u));
+    const u64 *__restrict__ rd = img + lds_phi(((lane >> 4) << 7) | ((lane & 7u) << 4));
+    const bool early = (lane & 8u) == 0;
+    u64 t[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wr[lds_koff<4>(k)] = x[k];
+    wave_sync_lds();
+    if (early) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            x[k] = rd[k];
+            t[k] = rd[k + 8];
+        }
+    }
+    wave_sync_lds();
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wr[lds_koff<4>(k)] = x[k + 8];
+    wave_sync_lds();
+    if (early) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k + 8] = t[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) x[k] = rd[k];
     }
 }
 
