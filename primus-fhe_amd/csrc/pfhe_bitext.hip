@@ -9,9 +9,10 @@
 //                        stores an output word also stores its modulus switch (switch_rounded at stride 0, the body with
 //                        2^(BITS-2) added and negated): the quarter turn of DESIGN.md §19 costs no launch.
 //   accumulator          ACC_e = X^{neg_b[e]} TV_i, TV_i = (0, .., 0, -2^(delta+i-1) on every coefficient), written from
-//                        constants by pfhe_manylut.hip's patterned kernel at one level (launch_pattern_acc_init).
+//                        constants by pfhe_tfhe_stages.hip's kernel at one level (launch_const_acc_init).
 //   blind rotation       the classic handle behind TfheRotation, called as it is.
-//   extract and subtract c_{i+1} = c_i - (extraction of ACC_e at index 0, with 2^(delta+i-1) added to the body): bit i cleared.
+//   extract and subtract c_{i+1} = c_i - (extraction of ACC_e at index 0, with 2^(delta+i-1) added to the body): bit i cleared
+//                        (launch_extract with a source, pfhe_tfhe_stages.hip's extraction kernel in its subtracting form).
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
 // the two forms of the call (handle_call) go through pfhe_tfhe_host.hpp; the key switch keeps its own 2-D grid.
 #include <algorithm>
@@ -33,10 +34,6 @@ namespace {
 // an input are neighbours in the caller's output).  exps != null: output word (e, col) also goes through switch_rounded to
 // exps[e n + col], the body (col = n) with 2^(BITS-2) added and negated to neg_b[e]; every word has one thread.
 
-struct BitextKsShape {
-    u32 in_dim, out_dim, log_basis, ell, drop_bits, ki;
-};
-
 // Two things about the form, both measured on the u64 kernel, whose row loop the compiler schedules by what surrounds it
 // (DESIGN.md §24).  The body is shifted behind the select, not in front of it: with `col == n ? body << shift : 0` the loop
 // takes 110 registers (four waves per SIMD) instead of tfhe_keyswitch_kernel's 92 (five).  And the modulus switch is a
@@ -45,7 +42,7 @@ struct BitextKsShape {
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_bitext_keyswitch_kernel(
     const W *__restrict__ lwe_in, const W *__restrict__ ksk, W *__restrict__ lwe_out, u32 *__restrict__ exps,
-    u32 *__restrict__ neg_b, BitextKsShape s, u32 shift, u32 log_n, u64 out_stride, u64 batch) {
+    u32 *__restrict__ neg_b, KsShape s, u32 shift, u32 log_n, u64 out_stride, u64 batch) {
     __shared__ W dig[kKsMaxRows * kKsTileM];
     const u32 lane = threadIdx.x % kKsLanes, wave = threadIdx.x / kKsLanes;
     const u32 cols = s.out_dim + 1;
@@ -91,32 +88,11 @@ __global__ __launch_bounds__(kThreads) void tfhe_bitext_keyswitch_kernel(
     }
 }
 
-// ---------------- extraction at index 0, subtracted from the running ciphertext ----------------
-
-// one thread per word of the batch: dst[e][j N + i] = src[e][j N + i] - extract_word(A_j, 0, N, i) and dst[e][k N] =
-// src[e][k N] - (B[0] + half).  dst may be exactly src: a thread reads and writes one word of them.
-template <class W>
-__global__ __launch_bounds__(kThreads) void tfhe_bitext_extract_sub_kernel(const W *__restrict__ glwe, const W *src, W *dst,
-                                                                           u32 k, u32 log_n, W half, u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u32 n = 1u << log_n;
-    const u64 len = ((u64)k << log_n) + 1;
-    const u64 e = t / len, c = t - e * len;
-    const W *ct = glwe + e * ((u64)(k + 1) << log_n);
-    if (c == len - 1) {
-        dst[t] = src[t] - (W)(ct[(u64)k << log_n] + half);
-        return;
-    }
-    const u32 i = (u32)(c & (n - 1));
-    dst[t] = src[t] - extract_word(ct + (c - i), 0u, n, i);
-}
-
 // ---------------- launches (arguments already checked) ----------------
 
 // exps / neg_b null: the last bit, whose output nobody switches
 template <class W>
-int launch_bitext_keyswitch(const W *lwe_in, const W *ksk, W *lwe_out, u32 *exps, u32 *neg_b, BitextKsShape sh, u32 shift,
+int launch_bitext_keyswitch(const W *lwe_in, const W *ksk, W *lwe_out, u32 *exps, u32 *neg_b, KsShape sh, u32 shift,
                             u32 log_n, u64 out_stride, u64 batch, hipStream_t s) {
     const u64 gx = ((u64)sh.out_dim + 1 + kKsTileN - 1) / kKsTileN;
     return launch_y_slices((batch + kKsTileM - 1) / kKsTileM, [&](u64 first_tile, u32 tiles) {
@@ -136,7 +112,7 @@ int launch_bitext_keyswitch(const W *lwe_in, const W *ksk, W *lwe_out, u32 *exps
 // neg_b and the running ciphertexts of k N + 1 words (TfheBootstrapBase's `extracted`): all allocated at creation.
 template <class W>
 struct TfheBitextCore : TfheBootstrapBase<W> {
-    BitextKsShape ks{};
+    KsShape ks{};
 };
 struct pfhe_bitext : TfheBitextCore<u64> {};
 struct pfhe_bitext32 : TfheBitextCore<u32> {};
@@ -172,7 +148,7 @@ int bitext_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis
     h->k = (u32)glwe_dimension;
     h->n = (u32)lwe_dimension;
     const size_t glwe = rot.glwe, ext = glwe_dimension * fft->n + 1;
-    h->ks = BitextKsShape{(u32)(ext - 1), h->n, ks_log_basis, ks_ell, ks_drop, ks_group_words(ks_ell)};
+    h->ks = KsShape{(u32)(ext - 1), h->n, ks_log_basis, ks_ell, ks_drop, ks_group_words(ks_ell)};
     h->bsk_len = lwe_dimension * rot.key_len;
     // chunk 0: the rotation's default, capped at about 256 MiB of accumulators
     h->chunk = chunk ? rot.chunk : std::min(rot.chunk, std::max<size_t>(1, kBitextDefaultAccBytes / (glwe * sizeof(W))));
@@ -243,10 +219,10 @@ int extract_bits(Form form, H *h, const W *lwe_in, size_t len_in, const double *
                                                     out_stride, cur, st));
                 if (last) break;
                 const u32 half_shift = delta_log + i - 1;
-                PFHE_TRY(launch_pattern_acc_init<W>(h->acc, h->neg_b, h->k, f.log_n, 0, 1, 0, half_shift, cur, st));
+                PFHE_TRY(launch_const_acc_init<W>(h->acc, h->neg_b, h->k, f.log_n, 1, 0, 1, 0, half_shift, cur, st));
                 PFHE_TRY(h->rotation->rotate_dev(h->acc, cur * glwe, (const double *)d[1], len_bsk, h->exps, cur * h->n, st));
-                PFHE_TRY(launch_flat(tfhe_bitext_extract_sub_kernel<W>, cur * ext, st, (const W *)h->acc, run, h->extracted, h->k,
-                                     f.log_n, (W)((W)1 << half_shift)));
+                PFHE_TRY(launch_extract<W>(h->acc, run, h->extracted, h->k, f.log_n, ExtractRule{1, 0, 1, 1, 0, half_shift}, cur,
+                                           st));
                 run = h->extracted;
             }
         }

@@ -1,17 +1,18 @@
 // pfhe_bootstrap.hip — the steps of a TFHE programmable bootstrap around the blind rotation, and the handle that runs
 // them in order (include/pfhe.h: pfhe_tfhe{,32}_modswitch_dev, _sample_extract*, _keyswitch*, _bootstrap_*).
 //
-//   modulus switch     LWE words -> exponents modulo 2N: switch_rounded at stride 0, round(w 2N / 2^BITS) with ties up,
-//                      reduced modulo 2N.
+//   modulus switch     LWE words -> exponents modulo 2N: switch_rounded at stride 2^log_luts (0 without many-LUT),
+//                      round(w 2N / 2^BITS) with ties up, reduced modulo 2N.
 //   accumulator init   ACC_e = X^{neg_b[e]} TV, the rotation of pfhe_tfhe*_mul_monomial_each_to_dev with the test vector
 //                      read in place (one shared by the batch, or one per ciphertext).
 //   blind rotation     the classic or the multi-bit handle (pfhe_fft.hip) behind TfheRotation, called as it is.
-//   sample extraction  Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial.
+//   sample extraction  Rlwe::extract_lwe_with_index (primus_lattice/src/rlwe/coeff.rs:194-227) per mask polynomial, at
+//                      every index below 2^log_luts (pfhe_tfhe{,32}_bootstrap_create_many_lut; index 0 without).
 //   key switch         out = (0, b) - sum_i sum_j d_{i,j} KSK[i][j], a sequence of Lwe::add_mul_scalar_assign
 //                      (lwe/single_message.rs:262-268) with the digits of ApproxSignedBasis (init_carry / digit_word of
 //                      pfhe_fft_device.hpp, over the product's own digit_step).
-//   many-LUT           (pfhe_tfhe{,32}_bootstrap_create_many_lut) the strided switch and the extraction at every
-//                      index below 2^log_luts of pfhe_manylut.hip in place of the first and the fourth step.
+// The switch, the accumulator and the extraction are the stage kernels of pfhe_tfhe_stages.hip, queued through the launches
+// of pfhe_tfhe_handles.hpp; the key switch's kernel is this file's.
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
 // the two forms of every call (stateless_call, handle_call) go through pfhe_tfhe_host.hpp; the key switch keeps its own
 // 2-D grid.  The rules of the exact steps and the key switch's tile are pfhe_tfhe_exact_device.hpp's.
@@ -27,69 +28,10 @@ using namespace pfhe;
 namespace pfhe {
 namespace {
 
-// ---------------- modulus switch ----------------
-
-// one thread per word of the batch: word i of ciphertext e goes to exps[e n + i] (i < n) or, negated, to neg_b[e] (i = n)
-template <class W>
-__global__ __launch_bounds__(kThreads) void tfhe_modswitch_kernel(const W *__restrict__ lwe, u32 *__restrict__ exps,
-                                                                  u32 *__restrict__ neg_b, u32 n, u32 log_n, u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u64 e = t / (n + 1);
-    const u32 i = (u32)(t - e * (n + 1));
-    const u32 two_n_mask = (2u << log_n) - 1;
-    const u32 v = switch_rounded<W>(lwe[t], log_n, 0) & two_n_mask;
-    if (i < n)
-        exps[e * n + i] = v;
-    else
-        neg_b[e] = ((2u << log_n) - v) & two_n_mask;
-}
-
-// ---------------- accumulator init ----------------
-
-// ACC_e = X^{neg_b[e]} TV_e (MonomialShift), one thread per accumulator word.  tv_stride: words between the test vectors of
-// consecutive ciphertexts, 0 when one is shared by the batch.
-template <class W>
-__global__ __launch_bounds__(kThreads) void tfhe_acc_init_kernel(const W *__restrict__ tv, W *__restrict__ acc,
-                                                                 const u32 *__restrict__ neg_b, u32 rows, u32 log_n,
-                                                                 u64 tv_stride, u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u32 n = 1u << log_n, j = (u32)(t & (n - 1));
-    const u64 poly = t >> log_n, e = poly / rows;
-    const u32 row = (u32)(poly - e * rows);
-    const MonomialShift x(neg_b[e], n);
-    acc[t] = x.apply(j, tv[e * tv_stride + ((u64)row << log_n) + x.source(j)]);
-}
-
-// ---------------- sample extraction ----------------
-
-// one thread per output word: out[jN + i] = extract_word(A_j, h, N, i), out[kN] = B[h]
-template <class W>
-__global__ __launch_bounds__(kThreads) void tfhe_sample_extract_kernel(const W *__restrict__ glwe, W *__restrict__ lwe, u32 k,
-                                                                       u32 log_n, u32 h, u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u32 n = 1u << log_n;
-    const u64 out_len = ((u64)k << log_n) + 1;
-    const u64 e = t / out_len, c = t - e * out_len;
-    const W *ct = glwe + e * ((u64)(k + 1) << log_n);
-    if (c == out_len - 1) {
-        lwe[t] = ct[((u64)k << log_n) + h];
-        return;
-    }
-    const u32 i = (u32)(c & (n - 1));
-    lwe[t] = extract_word(ct + (c - i), h, n, i);
-}
-
 // ---------------- key switch ----------------
 //
 // The key-switch tile of pfhe_tfhe_exact_device.hpp with M = batch, K = in_dimension * ell, out_dimension + 1 columns: the
 // workgroup walks the mask words, and the body goes into the last column behind the sums.
-
-struct KsShape {
-    u32 in_dim, out_dim, log_basis, ell, drop_bits, ki;
-};
 
 template <class W>
 __global__ __launch_bounds__(kThreads) void tfhe_keyswitch_kernel(const W *__restrict__ lwe_in, const W *__restrict__ ksk,
@@ -122,21 +64,6 @@ __global__ __launch_bounds__(kThreads) void tfhe_keyswitch_kernel(const W *__res
 }
 
 // ---------------- launches (arguments already checked) ----------------
-
-template <class W>
-int launch_modswitch(const W *lwe, u32 n, u32 log_n, u32 *exps, u32 *neg_b, u64 batch, hipStream_t s) {
-    return launch_flat(tfhe_modswitch_kernel<W>, batch * ((u64)n + 1), s, lwe, exps, neg_b, n, log_n);
-}
-
-template <class W>
-int launch_acc_init(const W *tv, u64 tv_stride, W *acc, const u32 *neg_b, u32 rows, u32 log_n, u64 batch, hipStream_t s) {
-    return launch_flat(tfhe_acc_init_kernel<W>, (batch * rows) << log_n, s, tv, acc, neg_b, rows, log_n, tv_stride);
-}
-
-template <class W>
-int launch_sample_extract(const W *glwe, W *lwe, u32 k, u32 log_n, u32 h, u64 batch, hipStream_t s) {
-    return launch_flat(tfhe_sample_extract_kernel<W>, batch * (((u64)k << log_n) + 1), s, glwe, lwe, k, log_n, h);
-}
 
 template <class W>
 int launch_keyswitch(const W *lwe_in, const W *ksk, W *lwe_out, KsShape sh, u64 batch, hipStream_t s) {
@@ -173,7 +100,8 @@ int modswitch_dev(int device, const W *lwe, size_t len_lwe, size_t lwe_dimension
     return stateless_call(
         device, Form::kDevice, bufs, nullptr, s,
         [&](void *const *d, hipStream_t st) {
-            return launch_modswitch<W>((const W *)d[0], (u32)lwe_dimension, log_n, (u32 *)d[1], (u32 *)d[2], len_neg_b, st);
+            return launch_modswitch<W>((const W *)d[0], (u32)lwe_dimension, log_n, 0, (W)0, 1, (u32 *)d[1], (u32 *)d[2],
+                                       len_neg_b, st);
         },
         [&] { return capi_check_device(device); });
 }
@@ -195,8 +123,8 @@ int sample_extract(Form form, const pfhe_fft *f, size_t k, const W *glwe, size_t
     const StageBuf bufs[] = {stage_in(glwe, len_glwe * sizeof(W)), stage_out(lwe, len_lwe * sizeof(W))};
     return stateless_call(f->device, form, bufs, "sample extraction: the output must not overlap the input", s,
                           [&](void *const *d, hipStream_t st) {
-                              return launch_sample_extract<W>((const W *)d[0], (W *)d[1], (u32)k, f->log_n, (u32)index,
-                                                              len_glwe / ((k + 1) * f->n), st);
+                              return launch_extract<W>((const W *)d[0], nullptr, (W *)d[1], (u32)k, f->log_n,
+                                                       ExtractRule{1, (u32)index, 1, 0, 0, 0}, len_glwe / ((k + 1) * f->n), st);
                           });
 }
 
@@ -365,21 +293,15 @@ int bootstrap(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk
     return handle_call(h->guard, f.device, form, bufs, s, [&](void *const *d, hipStream_t st) -> int {
         const W *in = (const W *)d[0], *vec = (const W *)d[2], *key = (const W *)d[3];
         W *out = (W *)d[4];
+        const u32 luts = 1u << h->log_luts;  // outputs per input: indices 0..luts-1 of its one accumulator
         // chunk after chunk; every stage of a chunk is queued before the next chunk starts
         for (u64 done = 0; done < batch; done += h->chunk) {
             const u64 cur = std::min<u64>(h->chunk, batch - done);
-            if (h->log_luts)
-                PFHE_TRY(launch_modswitch_stride<W>(in + done * in_words, h->n, f.log_n, h->log_luts, (W)0, h->exps, h->neg_b, cur,
-                                                    st));
-            else
-                PFHE_TRY(launch_modswitch<W>(in + done * in_words, h->n, f.log_n, h->exps, h->neg_b, cur, st));
+            PFHE_TRY(launch_modswitch<W>(in + done * in_words, h->n, f.log_n, h->log_luts, (W)0, 1, h->exps, h->neg_b, cur, st));
             PFHE_TRY(launch_acc_init<W>(vec + done * tv_stride, tv_stride, h->acc, h->neg_b, h->k + 1, f.log_n, cur, st));
             PFHE_TRY(h->rotation->rotate_dev(h->acc, cur * glwe, (const double *)d[1], len_bsk, h->exps, cur * h->n, st));
             W *lwe = h->with_keyswitch ? h->extracted : out + done * out_words;
-            if (h->log_luts)
-                PFHE_TRY(launch_multi_extract<W>(h->acc, lwe, h->k, f.log_n, 1u << h->log_luts, false, 0, 0, cur, st));
-            else
-                PFHE_TRY(launch_sample_extract<W>(h->acc, lwe, h->k, f.log_n, 0, cur, st));
+            PFHE_TRY(launch_extract<W>(h->acc, nullptr, lwe, h->k, f.log_n, ExtractRule{luts, 0, luts, 0, 0, 0}, cur * luts, st));
             if (h->with_keyswitch)
                 PFHE_TRY(launch_keyswitch<W>(lwe, key, out + done * out_words, h->ks, cur << h->log_luts, st));
         }

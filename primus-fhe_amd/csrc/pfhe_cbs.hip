@@ -13,8 +13,10 @@
 //                        rotation handle on batch * levels accumulators, extraction at index 0 with g_l/2 added to the body,
 //                        and the private key switch with levels = ell_cb into the caller's GGSWs.
 //   ... with options     (pfhe_tfhe{,32}_cbs_create_with) the rotation is the multi-bit one, and / or ONE rotation
-//                        per input serves all levels: the strided switch, the patterned accumulator and the multi-index
-//                        extraction of pfhe_manylut.hip in place of the three kernels below, which stay as they are.
+//                        per input serves all levels: the switch to multiples of 2^ceil(log2 ell_cb), TV with -g_l/2 on the
+//                        coefficients l mod 2^ceil(log2 ell_cb), extraction of level l at index l.
+// The switch, the accumulator and the extraction are the stage kernels of pfhe_tfhe_stages.hip, queued through the launches
+// of pfhe_tfhe_handles.hpp with one set of arguments per form; the private key switch and its key are this file's.
 // Every step is exact integer arithmetic modulo 2^BITS except the rotation; no atomics, no scratch memory.  Launches and
 // the two forms of every call (stateless_call, handle_call) go through pfhe_tfhe_host.hpp; the private key switch keeps
 // its own 3-D grid.
@@ -93,69 +95,6 @@ __global__ __launch_bounds__(kThreads) void tfhe_pfksk_add_message_kernel(W *__r
         body[0] += msg;
     else
         body[i] -= msg * glwe_key[((u64)u << log_n) + i];
-}
-
-// ---------------- the stages of the circuit bootstrap around the rotation ----------------
-
-// The plain modulus switch (switch_rounded at stride 0) on (a, b + 2^(BITS-2)), one thread per input word: the exponents of
-// input e are written once per level, exps[(e levels + l) n + i], for the levels accumulators the rotation sees; neg_b[e] once
-template <class W>
-__global__ __launch_bounds__(kThreads) void tfhe_cbs_modswitch_kernel(const W *__restrict__ lwe, u32 *__restrict__ exps,
-                                                                      u32 *__restrict__ neg_b, u32 n, u32 log_n, u32 levels,
-                                                                      u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u64 e = t / (n + 1);
-    const u32 i = (u32)(t - e * (n + 1));
-    const u32 two_n_mask = (2u << log_n) - 1;
-    const W w = i < n ? lwe[t] : (W)(lwe[t] + ((W)1 << (8 * sizeof(W) - 2)));
-    const u32 v = switch_rounded<W>(w, log_n, 0) & two_n_mask;
-    if (i < n) {
-        for (u32 l = 0; l < levels; ++l) exps[(e * levels + l) * n + i] = v;
-    } else {
-        neg_b[e] = ((2u << log_n) - v) & two_n_mask;
-    }
-}
-
-// ACC_{e,l} = X^{neg_b[e]} TV_l, one thread per accumulator word: the mask polynomials are 0 and every body coefficient is
-// -+g_l/2, g_l/2 = 2^(half_shift + l log_basis), with MonomialShift's sign
-template <class W>
-__global__ __launch_bounds__(kThreads) void tfhe_cbs_acc_init_kernel(W *__restrict__ acc, const u32 *__restrict__ neg_b, u32 k,
-                                                                     u32 log_n, u32 levels, u32 log_basis, u32 half_shift,
-                                                                     u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u32 n = 1u << log_n;
-    const u64 poly = t >> log_n, a = poly / (k + 1);
-    if (poly - a * (k + 1) != k) {
-        acc[t] = 0;
-        return;
-    }
-    const u64 e = a / levels;
-    const u32 l = (u32)(a - e * levels);
-    const MonomialShift x(neg_b[e], n);
-    const W half = (W)1 << (half_shift + l * log_basis);  // TV_l is -g_l/2 on every coefficient: X^r TV_l = -(X^r g_l/2)
-    acc[t] = (W)0 - x.apply((u32)(t & (n - 1)), half);
-}
-
-// sample extraction at index 0 of accumulator (e, l) with g_l/2 added to the body: out[jN] = A_j[0], out[jN + i] =
-// -A_j[N - i], out[kN] = B[0] + g_l/2
-template <class W>
-__global__ __launch_bounds__(kThreads) void tfhe_cbs_extract_kernel(const W *__restrict__ glwe, W *__restrict__ lwe, u32 k,
-                                                                    u32 log_n, u32 levels, u32 log_basis, u32 half_shift,
-                                                                    u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u32 n = 1u << log_n;
-    const u64 out_len = ((u64)k << log_n) + 1;
-    const u64 a = t / out_len, c = t - a * out_len;
-    const W *ct = glwe + a * ((u64)(k + 1) << log_n);
-    if (c == out_len - 1) {
-        lwe[t] = ct[(u64)k << log_n] + ((W)1 << (half_shift + (u32)(a % levels) * log_basis));
-        return;
-    }
-    const u32 i = (u32)(c & (n - 1));
-    lwe[t] = i == 0 ? ct[c] : (W)0 - ct[c - i + (n - i)];
 }
 
 // ---------------- launches (arguments already checked) ----------------
@@ -355,36 +294,27 @@ int cbs(Form form, H *h, const W *lwe_in, size_t len_in, const double *bsk, size
         }
     }
     const pfhe_fft &f = *h->fft;
-    const size_t glwe = h->rotation->glwe, ext = (size_t)h->k * f.n + 1, in_words = (size_t)h->n + 1;
+    const size_t glwe = h->rotation->glwe, in_words = (size_t)h->n + 1;
     const u32 levels = h->cb_ell, half_shift = h->cb_drop - 1;
     const size_t ggsw = (size_t)(h->k + 1) * levels * glwe;
     const StageBuf bufs[] = {stage_in(lwe_in, len_in * sizeof(W)), stage_in(bsk, len_bsk * sizeof(double2)),
                              stage_in(pfksk, len_pfksk * sizeof(W)), stage_out(ggsw_out, len_out * sizeof(W))};
     return handle_call(h->guard, f.device, form, bufs, s, [&](void *const *d, hipStream_t st) -> int {
-        // chunk after chunk; every stage of a chunk is queued before the next chunk starts.  accs: the accumulators of the
-        // chunk, one per input with a shared rotation (the switch to multiples of 2^log_stride, the patterned test vector,
-        // level l read off coefficient l), one per input and level without
+        // chunk after chunk; every stage of a chunk is queued before the next chunk starts.  An input has per_input
+        // accumulators, each of which gives per_acc of its `levels` rows: one accumulator with a shared rotation (the switch to
+        // multiples of 2^log_stride, the patterned test vector, level l read off coefficient l), one per level without
+        // (log_stride 0, every coefficient of TV_l alike, index 0)
         const W *in = (const W *)d[0];
+        const u32 per_input = h->shared ? 1 : levels, per_acc = h->shared ? levels : 1;
         for (u64 done = 0; done < batch; done += h->chunk) {
-            const u64 cur = std::min<u64>(h->chunk, batch - done), accs = h->shared ? cur : cur * levels;
-            if (h->shared) {
-                PFHE_TRY(launch_modswitch_stride<W>(in + done * in_words, h->n, f.log_n, h->log_stride, (W)1 << (8 * sizeof(W) - 2),
-                                                    h->exps, h->neg_b, cur, st));
-                PFHE_TRY(launch_pattern_acc_init<W>(h->acc, h->neg_b, h->k, f.log_n, h->log_stride, levels, h->cb_log_basis,
-                                                    half_shift, cur, st));
-            } else {
-                PFHE_TRY(launch_flat(tfhe_cbs_modswitch_kernel<W>, cur * in_words, st, in + done * in_words, h->exps, h->neg_b, h->n,
-                                     f.log_n, levels));
-                PFHE_TRY(launch_flat(tfhe_cbs_acc_init_kernel<W>, accs * glwe, st, h->acc, (const u32 *)h->neg_b, h->k, f.log_n,
-                                     levels, h->cb_log_basis, half_shift));
-            }
+            const u64 cur = std::min<u64>(h->chunk, batch - done), accs = cur * per_input;
+            PFHE_TRY(launch_modswitch<W>(in + done * in_words, h->n, f.log_n, h->log_stride, (W)1 << (8 * sizeof(W) - 2), per_input,
+                                         h->exps, h->neg_b, cur, st));
+            PFHE_TRY(launch_const_acc_init<W>(h->acc, h->neg_b, h->k, f.log_n, per_input, h->log_stride, levels, h->cb_log_basis,
+                                              half_shift, accs, st));
             PFHE_TRY(h->rotation->rotate_dev(h->acc, accs * glwe, (const double *)d[1], len_bsk, h->exps, accs * h->n, st));
-            if (h->shared)
-                PFHE_TRY(launch_multi_extract<W>(h->acc, h->extracted, h->k, f.log_n, levels, true, h->cb_log_basis, half_shift, cur,
-                                                 st));
-            else
-                PFHE_TRY(launch_flat(tfhe_cbs_extract_kernel<W>, accs * ext, st, (const W *)h->acc, h->extracted, h->k, f.log_n,
-                                     levels, h->cb_log_basis, half_shift));
+            PFHE_TRY(launch_extract<W>(h->acc, nullptr, h->extracted, h->k, f.log_n,
+                                       ExtractRule{per_acc, 0, levels, 1, h->cb_log_basis, half_shift}, cur * levels, st));
             PFHE_TRY(launch_pfks<W>(h->extracted, (const W *)d[2], (W *)d[3] + done * ggsw, h->pf, cur * levels, st));
         }
         return PFHE_OK;

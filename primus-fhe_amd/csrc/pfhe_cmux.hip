@@ -38,14 +38,6 @@ struct CmuxNodes {
     __device__ __forceinline__ u64 key(u64 b) const { return ((first_node + b) / per_key) * key_stride; }
 };
 
-// one input row of D = d1 - d0, formed once and held in registers for all its levels
-template <class W>
-struct DiffRow {
-    W a[kFusedPer], b[kFusedPer];
-    __device__ __forceinline__ W lo(int u, u32) const { return a[u]; }
-    __device__ __forceinline__ W hi(int u, u32) const { return b[u]; }
-};
-
 // One workgroup per CMUX node (k = 1, N <= 2^11); the body is pfhe_fft_device.hpp's fused_accumulate_rows /
 // fused_inverse_rows, so the product inside is the fused product's arithmetic, operation for operation.  Every read of
 // d0 / d1 by the row source precedes a barrier of fused_accumulate_rows, every store of the sink follows the barrier that
@@ -63,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_cmux_kernel(const W *d0, const 
 #pragma unroll
     for (int u = 0; u < kFusedPer; ++u) acc0[u] = acc1[u] = make_double2(0.0, 0.0);
     fused_accumulate_rows<W>([&](u32 row) {
-        DiffRow<W> d;
+        RegisterRow<W> d;  // D = d1 - d0, formed once and held in registers for all its levels
 #pragma unroll
         for (int u = 0; u < kFusedPer; ++u) {
             const u32 i = threadIdx.x + u * kThreads;

@@ -142,21 +142,22 @@ __global__ __launch_bounds__(kThreads) void tfhe_digit_fwd_kernel(const W *__res
     for (u32 i = threadIdx.x; i < m; i += blockDim.x) out[i] = lds_d[lpad(bitrev(i, log_m))];
 }
 
-// acc[e][c][i] = sum over r, l (in that order) of spec[e][r][l][i] * keyh[r][l][c][i]
+// acc[e][c][i] = sum over r < in_rows, l (in that order) of spec[e][r][l][i] * keyh[r][l][c][i], c <= k.  The product
+// decomposes all k+1 rows of its input; the trace (pfhe_trace.hip) the k mask rows alone, against a key of k ell rows.
 __global__ __launch_bounds__(kThreads) void tfhe_mulacc_kernel(const double2 *__restrict__ spec,
                                                                const double2 *__restrict__ keyh, double2 *__restrict__ acc,
-                                                               u32 log_n, u32 k, u32 ell, u64 total) {
+                                                               u32 log_n, u32 k, u32 ell, u32 in_rows, u64 total) {
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
-    const u32 m = 1u << (log_n - 1), rows = k + 1;
+    const u32 m = 1u << (log_n - 1), cols = k + 1;
     const u32 i = (u32)(t & (m - 1));
     const u64 ec = t >> (log_n - 1);
-    const u32 c = (u32)(ec % rows);
-    const u64 e = ec / rows;
-    const double2 *sp = spec + e * rows * ell * m + i;
+    const u32 c = (u32)(ec % cols);
+    const u64 e = ec / cols;
+    const double2 *sp = spec + e * in_rows * ell * m + i;
     const double2 *kh = keyh + (u64)c * m + i;
     double2 a = make_double2(0.0, 0.0);
-    for (u32 rl = 0; rl < rows * ell; ++rl) a = cmac_fixed(a, sp[(u64)rl * m], kh[(u64)rl * rows * m]);
+    for (u32 rl = 0; rl < in_rows * ell; ++rl) a = cmac_fixed(a, sp[(u64)rl * m], kh[(u64)rl * cols * m]);
     acc[t] = a;
 }
 
@@ -181,20 +182,6 @@ __global__ __launch_bounds__(kThreads) void tfhe_fused_kernel(const W *__restric
 }
 
 // ---------------- blind rotation over the product ----------------
-
-// coefficient j of X^r * p - p for a polynomial p of N words (wrapping arithmetic)
-template <class W>
-__device__ __forceinline__ W rotated_diff(const W *p, u32 j, const MonomialShift &x) {
-    return x.apply(j, p[x.source(j)]) - p[j];
-}
-
-// one input row of D = X^r ACC - ACC, held in registers for all its levels
-template <class W>
-struct RegisterRow {
-    W a[kFusedPer], b[kFusedPer];
-    __device__ __forceinline__ W lo(int u, u32) const { return a[u]; }
-    __device__ __forceinline__ W hi(int u, u32) const { return b[u]; }
-};
 
 // The whole loop of one ciphertext in one workgroup (k = 1, N <= 2^11): ACC (2N words) sits in LDS behind the digit
 // spectrum from the first step to the last.  Per step: D row by row from the LDS-resident ACC into registers, the
@@ -477,8 +464,8 @@ int tfhe_product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *ou
             PFHE_TRY(launch_groups(tfhe_fused_kernel<W>, cur, lds_bytes(f.log_n), s, x, key, o, f.tw, sh));
             continue;
         }
-        PFHE_TRY(general_product<W>(f, sh, t, x, o, cur, s, [&](u64 at) {
-            return launch_flat(tfhe_mulacc_kernel, at, s, t.spec, t.keyh, t.acc, f.log_n, sh.k, sh.ell);
+        PFHE_TRY(general_product<W>(f, sh, t, x, o, cur, s, [&](u64) {
+            return tfhe_mulacc_launch(f, t.spec, t.keyh, t.acc, sh.k, sh.ell, sh.k + 1, cur, s);
         }));
     }
     return PFHE_OK;
@@ -862,6 +849,10 @@ template int tfhe_product_impl<u32>(TfhePlanCore<u32> *, const u32 *, const doub
 // k ell rows and on k digit rows per ciphertext
 int tfhe_key_herm_launch(const pfhe_fft &f, const double2 *key, double2 *keyh, u64 polys, hipStream_t s) {
     return launch_flat(tfhe_key_herm_kernel, polys * (f.n / 2), s, key, keyh, f.log_n);
+}
+int tfhe_mulacc_launch(const pfhe_fft &f, const double2 *spec, const double2 *keyh, double2 *acc, u32 k, u32 ell, u32 in_rows,
+                       u64 batch, hipStream_t s) {
+    return launch_flat(tfhe_mulacc_kernel, batch * (k + 1) * (f.n / 2), s, spec, keyh, acc, f.log_n, k, ell, in_rows);
 }
 template <class W>
 int tfhe_digit_fwd_launch(const pfhe_fft &f, const Shape &sh, const W *in, double2 *spec, u64 polys, hipStream_t s) {

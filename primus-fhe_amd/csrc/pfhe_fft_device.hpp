@@ -3,11 +3,13 @@
 // The half-size transforms in LDS, the torus conversions, the signed digits, and the two halves of the fused product
 // (k = 1, N <= 2^11): fused_accumulate_rows (digits, forward transforms and the multiply-accumulate of both input rows) and
 // fused_inverse_rows (the two folded inverses and the torus wrap).  tfhe_fused_kernel runs them once on words read from
-// global memory; tfhe_blindrot_loop_kernel runs them once per step on an accumulator that stays in LDS; so does
-// tfhe_trace_loop_kernel (pfhe_trace.hip), on the mask row alone.  All inline the same code, so a step of a loop is the
-// product's arithmetic, operation for operation.  fused_accumulate_rows takes the
-// key's Hermitian part from a key source: ClassicKey (one key in memory) or MultiBitKey (the multi-bit rotation's
-// per-ciphertext combination of 2^g keys, mb_combined_slots, shared with the per-group and combined-key kernels).
+// global memory; tfhe_blindrot_loop_kernel and tfhe_bitrot_loop_kernel (pfhe_lut.hip) run them once per step on an
+// accumulator that stays in LDS; so does tfhe_trace_loop_kernel (pfhe_trace.hip), on the mask row alone.  All inline the
+// same code, so a step of a loop is the product's arithmetic, operation for operation.  RegisterRow (at the end of this
+// file, with MonomialShift and rotated_diff) is the row of every form that holds its input row in registers.
+// fused_accumulate_rows takes the key's Hermitian part from a key source: ClassicKey (one key in memory) or MultiBitKey
+// (the multi-bit rotation's per-ciphertext combination of 2^g keys, mb_combined_slots, shared with the per-group and
+// combined-key kernels).
 #pragma once
 
 #include "pfhe_common.hpp"
@@ -318,5 +320,41 @@ __device__ __forceinline__ void fused_inverse_rows(const double2 (&acc0)[kFusedP
         __syncthreads();  // the second row reuses the buffer
     }
 }
+
+// ---------------- the rows of a rotation step, held in registers ----------------
+
+// X^r p for a polynomial p of N words, r taken modulo 2N: coefficient j is +-p[(j - r) mod N], the wrapped part negated;
+// r >= N (high, rot = r - N) negates the other part
+struct MonomialShift {
+    u32 n, rot;
+    bool high;
+    __device__ __forceinline__ MonomialShift(u32 r, u32 n) : n(n) {
+        r &= 2 * n - 1;
+        high = r >= n;
+        rot = high ? r - n : r;
+    }
+    // the index of the word that coefficient j takes ...
+    __device__ __forceinline__ u32 source(u32 j) const { return (j - rot) & (n - 1); }
+    // ... and that word, v, with coefficient j's sign
+    template <class W>
+    __device__ __forceinline__ W apply(u32 j, W v) const {
+        return ((j < rot) != high) ? (W)0 - v : v;
+    }
+};
+
+// coefficient j of X^r * p - p for a polynomial p of N words (wrapping arithmetic)
+template <class W>
+__device__ __forceinline__ W rotated_diff(const W *p, u32 j, const MonomialShift &x) {
+    return x.apply(j, p[x.source(j)]) - p[j];
+}
+
+// one input row formed once and held in registers for all its levels: slot u holds coefficients i and i + N/2, i = thread +
+// 256 u.  A row of X^r ACC - ACC here, of d1 - d0 in pfhe_cmux.hip, of sigma_t(ACC) in pfhe_trace.hip.
+template <class W>
+struct RegisterRow {
+    W a[kFusedPer], b[kFusedPer];
+    __device__ __forceinline__ W lo(int u, u32) const { return a[u]; }
+    __device__ __forceinline__ W hi(int u, u32) const { return b[u]; }
+};
 
 }  // namespace pfhe

@@ -8,7 +8,7 @@
 //                         words of mul_monomial_each_to_dev, then the CMUX with d0 = acc, d1 = the rotated one, per_key = o.
 //   rule 2, the table     stage A, the tree of §20 on the nodes (input, output, leaf) with bit r + j at level j; stage B, rule 1
 //                         on its batch * o results (on the table itself at tree depth 0); stage C, sample extraction at the
-//                         indices below `extract` (launch_multi_extract on the stored ciphertexts), or none.
+//                         indices below `extract` (launch_extract on the stored ciphertexts), or none.
 //   fused   (k = 1, N <= 2^11): tfhe_bitrot_loop_kernel, ONE launch per chunk for all r steps, a workgroup per accumulator,
 //            ACC in LDS from the first step to the last; the tree's levels are tfhe_cmux_kernel launches (tfhe_cmux_launch).
 //   general (every other shape): per step tfhe_bitrot_monomial_kernel into an owned buffer, then the CMUX's general form in
@@ -37,20 +37,6 @@ struct BitRot {
     __device__ __forceinline__ u64 key(u64 b) const { return ((first_acc + b) / per_input) * key_stride; }
     // the exponent of step j, 2N - 2^(j + s): X^{-2^(j+s)}
     __device__ __host__ __forceinline__ u32 exponent(u32 j, u32 n) const { return 2 * n - (1u << (j + log_stride)); }
-};
-
-// coefficient j of X^e p - p for a polynomial p of N words (wrapping arithmetic), the rotation loop's rule
-template <class W>
-__device__ __forceinline__ W rotated_diff(const W *p, u32 j, const MonomialShift &x) {
-    return x.apply(j, p[x.source(j)]) - p[j];
-}
-
-// one input row of D = X^e ACC - ACC, held in registers for all its levels
-template <class W>
-struct RegisterRow {
-    W a[kFusedPer], b[kFusedPer];
-    __device__ __forceinline__ W lo(int u, u32) const { return a[u]; }
-    __device__ __forceinline__ W hi(int u, u32) const { return b[u]; }
 };
 
 // All r steps of one accumulator in one workgroup (k = 1, N <= 2^11): ACC (2N words) sits in LDS behind the digit spectrum
@@ -368,8 +354,9 @@ int lut_eval(Form form, TfheLutCore<W> *h, const W *table, size_t len_table, con
                 PFHE_TRY(rotate_accs<W>(h, gather ? leaves : src, (const double2 *)ptr[1], res, done * o, cur * o, p,
                                         gather ? (u32)o : 0u, st));
             if (extract)  // stage C
-                PFHE_TRY(launch_multi_extract<W>(res, (W *)ptr[2] + done * o * extract * (((u64)k << h->shape.log_n) + 1), k,
-                                                 h->shape.log_n, (u32)extract, false, 0, 0, cur * o, st));
+                PFHE_TRY(launch_extract<W>(res, nullptr, (W *)ptr[2] + done * o * extract * (((u64)k << h->shape.log_n) + 1), k,
+                                           h->shape.log_n, ExtractRule{(u32)extract, 0, (u32)extract, 0, 0, 0}, cur * o * extract,
+                                           st));
         }
         return PFHE_OK;
     });

@@ -1,19 +1,21 @@
 // pfhe_tfhe_exact_device.hpp — the exact (integer, modulo 2^BITS) device code the torus-side stages share: the rules of the
 // stages around a blind rotation, one definition each, and the tile of the two key-switch GEMMs.
 //
-//   MonomialShift    X^r p on N words, the negacyclic rule: pfhe_bootstrap.hip, pfhe_cbs.hip and pfhe_manylut.hip
-//                    (accumulator init), pfhe_fft.hip (the rotated difference of the loop kernel and of the glue kernel).
-//   switch_rounded   the modulus switch to multiples of 2^v, which its callers reduce modulo 2N; v = 0 is the plain switch
-//                    (pfhe_bootstrap.hip, pfhe_cbs.hip), v > 0 the many-LUT one (pfhe_manylut.hip).
-//   extract_word     a mask word of sample extraction at index h: pfhe_bootstrap.hip and pfhe_manylut.hip.  The two kernels
-//                    that extract at index 0 alone (tfhe_cbs_extract_kernel, tfhe_extract_first_few_kernel) keep their own
-//                    two-case form, a[0] or -a[N - i]: with h = 0 passed here they compile to other instructions.
+//   switch_rounded   the modulus switch to multiples of 2^v, which its callers reduce modulo 2N; v = 0 is the plain switch:
+//                    tfhe_modswitch_kernel (pfhe_tfhe_stages.hip) and the switch that tfhe_bitext_keyswitch_kernel
+//                    (pfhe_bitext.hip) does on the words it has just stored.
+//   extract_word     a mask word of sample extraction at index h: tfhe_extract_kernel (pfhe_tfhe_stages.hip), every form of
+//                    it.  tfhe_extract_first_few_kernel (pfhe_pack.hip), which writes another layout, keeps its own two-case
+//                    form for index 0, a[0] or -a[N - i].
+//   KsShape          the LWE key switch as its two kernels take it: tfhe_keyswitch_kernel (pfhe_bootstrap.hip) and
+//                    tfhe_bitext_keyswitch_kernel (pfhe_bitext.hip).
 //   ks_tile_sums     the group loop of tfhe_keyswitch_kernel (pfhe_bootstrap.hip), tfhe_pfks_kernel (pfhe_cbs.hip) and
 //                    tfhe_bitext_keyswitch_kernel (pfhe_bitext.hip).
-// Every function is inlined into its kernels, which stay separate kernels with their own names, grids and arguments.  The
-// forms (what is a member, the order of parameters, what is left to the caller) are the ones with which every kernel but
-// the two key switches compiles to the instructions it had with the rule written out
-// (profiles/tfhe_exact_a_kernel_identity.txt).
+// MonomialShift, the negacyclic rule X^r p of the accumulator kernels (pfhe_tfhe_stages.hip) and of the rotated differences
+// (pfhe_fft.hip, pfhe_lut.hip), sits in pfhe_fft_device.hpp beside rotated_diff, which needs it; it is included from there.
+// Every function is inlined into its kernels.  The forms (what is a member, the order of parameters, what is left to the
+// caller) are the ones with which the kernels that were not merged compile to the instructions they had with the rule
+// written out (profiles/tfhe_exact_a_kernel_identity.txt, profiles/tfhe_stages_a_kernel_identity.txt).
 #pragma once
 
 #include <algorithm>
@@ -23,25 +25,6 @@
 namespace pfhe {
 
 // ---------------- the stage rules ----------------
-
-// X^r p for a polynomial p of N words, r taken modulo 2N: coefficient j is +-p[(j - r) mod N], the wrapped part negated;
-// r >= N (high, rot = r - N) negates the other part
-struct MonomialShift {
-    u32 n, rot;
-    bool high;
-    __device__ __forceinline__ MonomialShift(u32 r, u32 n) : n(n) {
-        r &= 2 * n - 1;
-        high = r >= n;
-        rot = high ? r - n : r;
-    }
-    // the index of the word that coefficient j takes ...
-    __device__ __forceinline__ u32 source(u32 j) const { return (j - rot) & (n - 1); }
-    // ... and that word, v, with coefficient j's sign
-    template <class W>
-    __device__ __forceinline__ W apply(u32 j, W v) const {
-        return ((j < rot) != high) ? (W)0 - v : v;
-    }
-};
 
 // The modulus switch of one word before its reduction modulo 2N: round(w 2N / 2^v / 2^BITS) with ties up, times 2^v, computed
 // without overflow; sw_v(w) = switch_rounded(w, log_n, v) & (2N-1), a multiple of 2^v below 2N (a word that rounds up to 2N
@@ -73,6 +56,12 @@ constexpr int kKsRows = 8, kKsCols = 2;
 constexpr int kKsTileM = kKsWaves * kKsRows, kKsTileN = kKsLanes * kKsCols;
 constexpr u32 kKsMaxRows = 64;
 constexpr int kKsUnroll = 4;
+
+// The LWE key switch as its kernels take it (tfhe_keyswitch_kernel, tfhe_bitext_keyswitch_kernel): the two dimensions, the
+// basis, and ki
+struct KsShape {
+    u32 in_dim, out_dim, log_basis, ell, drop_bits, ki;
+};
 
 // ki: input words of one group
 inline u32 ks_group_words(u32 ell) { return std::max<u32>(1, std::min<u32>(kKsMaxRows / ell, kFftThreads / kKsTileM)); }

@@ -243,29 +243,44 @@ int tfhe_plan_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_ba
 template <class W>
 int tfhe_product_impl(TfhePlanCore<W> *p, const W *in, const double2 *key, W *out, u64 batch, hipStream_t s);
 
-// Three launches of the general product for a caller that decomposes fewer rows than k+1 (pfhe_trace.hip: the k mask
+// The four launches of the general product for a caller that decomposes fewer rows than k+1 (pfhe_trace.hip: the k mask
 // rows): the Hermitian parts of `polys` key polynomials, the digit transforms of `polys` torus polynomials (polys * ell
-// workgroups, spectra in natural order polynomial after polynomial, level after level), and the half-spectrum inverses of
-// `polys` accumulators.  pfhe_fft.hip; the device is current.
+// workgroups, spectra in natural order polynomial after polynomial, level after level), the multiply-accumulate of `batch`
+// ciphertexts' in_rows * ell digit spectra into their k+1 accumulators, and the half-spectrum inverses of `polys`
+// accumulators.  pfhe_fft.hip; the device is current.
 int tfhe_key_herm_launch(const pfhe_fft &f, const double2 *key, double2 *keyh, u64 polys, hipStream_t s);
+int tfhe_mulacc_launch(const pfhe_fft &f, const double2 *spec, const double2 *keyh, double2 *acc, u32 k, u32 ell, u32 in_rows,
+                       u64 batch, hipStream_t s);
 template <class W>
 int tfhe_digit_fwd_launch(const pfhe_fft &f, const Shape &sh, const W *in, double2 *spec, u64 polys, hipStream_t s);
 template <class W>
 int tfhe_half_inverse_launch(const pfhe_fft &f, const double2 *acc, W *out, u64 polys, hipStream_t s);
 
-// The many-LUT steps around a rotation (pfhe_manylut.hip, instantiated for u32 and u64), arguments already checked and the
-// device current: the modulus switch to multiples of 2^log_stride (body_offset is added to the body word first), the
-// accumulator X^{neg_b[e]} TV of the shared circuit bootstrap written from constants, and sample extraction at every index
-// below `count` of every accumulator into row e * count + h (add_half: plus 2^(half_shift + h log_basis) on the body).
+// The exact stages around a rotation, one kernel each (pfhe_tfhe_stages.hip, instantiated for u32 and u64), arguments
+// already checked and the device current.
+//   launch_modswitch       the modulus switch to multiples of 2^log_stride (body_offset is added to the body word first);
+//                          input e's exponents go to exps[(e copies + c) n ..] for every c < copies, its body to neg_b[e].
+//   launch_acc_init        ACC_e = X^{neg_b[e]} TV_e on the caller's test vector(s), tv_stride words apart (0: one for all).
+//   launch_const_acc_init  `accs` accumulators X^{neg_b[a / per_input]} TV written from constants: body coefficient c of TV
+//                          is -2^(half_shift + level log_basis) at level = a mod per_input + c mod 2^log_stride, 0 from
+//                          `levels` on.
+//   launch_extract         `rows` output rows of k N + 1 words by the rule below; src null: the rows go to dst; src given:
+//                          dst = src - rows, and dst may be exactly src.
+// Row a of an extraction reads accumulator a / per_acc at index first_index + a mod per_acc (below N); add_half: plus
+// 2^(half_shift + (a mod level_period) log_basis) on the body.
+struct ExtractRule {
+    u32 per_acc, first_index, level_period, add_half, log_basis, half_shift;
+};
 template <class W>
-int launch_modswitch_stride(const W *lwe, u32 n, u32 log_n, u32 log_stride, W body_offset, u32 *exps, u32 *neg_b, u64 batch,
-                            hipStream_t s);
+int launch_modswitch(const W *lwe, u32 n, u32 log_n, u32 log_stride, W body_offset, u32 copies, u32 *exps, u32 *neg_b,
+                     u64 batch, hipStream_t s);
 template <class W>
-int launch_pattern_acc_init(W *acc, const u32 *neg_b, u32 k, u32 log_n, u32 log_stride, u32 levels, u32 log_basis,
-                            u32 half_shift, u64 batch, hipStream_t s);
+int launch_acc_init(const W *tv, u64 tv_stride, W *acc, const u32 *neg_b, u32 rows, u32 log_n, u64 batch, hipStream_t s);
 template <class W>
-int launch_multi_extract(const W *glwe, W *lwe, u32 k, u32 log_n, u32 count, bool add_half, u32 log_basis, u32 half_shift,
-                         u64 batch, hipStream_t s);
+int launch_const_acc_init(W *acc, const u32 *neg_b, u32 k, u32 log_n, u32 per_input, u32 log_stride, u32 levels, u32 log_basis,
+                          u32 half_shift, u64 accs, hipStream_t s);
+template <class W>
+int launch_extract(const W *glwe, const W *src, W *dst, u32 k, u32 log_n, const ExtractRule &rule, u64 rows, hipStream_t s);
 
 // The CMUX of a handle that owns a TfheCmuxTreeCore without being one (pfhe_cmux.hip, instantiated for u32 and u64): what
 // pfhe_tfhe{,32}_cmux_tree_create runs, its checks and allocations for `chunk` inputs of a tree of `depth` levels, and rule 1

@@ -1,5 +1,5 @@
 // pfhe_tfhe_host.hpp — the host layer under every torus entry point (pfhe_fft.hip, pfhe_bootstrap.hip, pfhe_keygen.hip,
-// pfhe_pack.hip, pfhe_pack_fft.hip, pfhe_cbs.hip, pfhe_manylut.hip, pfhe_cmux.hip, pfhe_trace.hip, pfhe_lut.hip, pfhe_bitext.hip, pfhe_linear.hip, pfhe_csprng.hip): the constants and range tests they share, the launch of a
+// pfhe_pack.hip, pfhe_pack_fft.hip, pfhe_cbs.hip, pfhe_tfhe_stages.hip, pfhe_cmux.hip, pfhe_trace.hip, pfhe_lut.hip, pfhe_bitext.hip, pfhe_linear.hip, pfhe_csprng.hip): the constants and range tests they share, the launch of a
 // torus kernel, and the two tails: stateless_call of the stateless steps, handle_call of the calls on a handle.  Host only.
 // What is not torus-specific lives in pfhe_staging.hpp, for the RNS side too: StageBuf and stage_in / _out / _inout,
 // staged_call (the staged run of a launch on host pointers), Form and form_call, refuse_null, overlaps,

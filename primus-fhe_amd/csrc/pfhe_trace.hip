@@ -53,14 +53,6 @@ __device__ __forceinline__ W sigma_word(const W *p, u32 i, u32 t_inv, u32 n) {
     return (u & n) ? (W)0 - v : v;
 }
 
-// one row of sigma_t(ACC), gathered once and held in registers for all its levels (RegisterRow's shape)
-template <class W>
-struct GatheredRow {
-    W a[kFusedPer], b[kFusedPer];
-    __device__ __forceinline__ W lo(int u, u32) const { return a[u]; }
-    __device__ __forceinline__ W hi(int u, u32) const { return b[u]; }
-};
-
 // All steps of one ciphertext in one workgroup (k = 1, N <= 2^11): ACC (2N words) sits in LDS behind the digit spectrum
 // from the first step to the last, as in tfhe_blindrot_loop_kernel.  Per step: sigma_t(A) and sigma_t(B) gathered from
 // the LDS-resident ACC into registers, a barrier, B = [B +] sigma_t(B) at the thread's own slots (which frees those
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(kThreads) void tfhe_trace_loop_kernel(const W *in, 
     for (u32 step = 0; step < steps.count; ++step) {
         const u32 t_inv = odd_inverse(steps.t[step], 2 * n - 1);
         double2 acc0[kFusedPer], acc1[kFusedPer];
-        GatheredRow<W> mask;
+        RegisterRow<W> mask;
         W body_lo[kFusedPer], body_hi[kFusedPer];
 #pragma unroll
         for (int u = 0; u < kFusedPer; ++u) {
@@ -134,25 +126,6 @@ __global__ __launch_bounds__(kThreads) void tfhe_trace_gather_kernel(const W *__
         d[((e * k + c) << log_n) + i] = v;
     else
         body[(e << log_n) + i] = v;
-}
-
-// acc[e][c][i] = sum over the k ell mask rows rl (in that order) of spec[e][rl][i] * keyh[rl][c][i]: tfhe_mulacc_kernel's
-// sum without the ell body rows
-__global__ __launch_bounds__(kThreads) void tfhe_trace_mulacc_kernel(const double2 *__restrict__ spec,
-                                                                     const double2 *__restrict__ keyh, double2 *__restrict__ acc,
-                                                                     u32 log_n, u32 k, u32 ell, u64 total) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= total) return;
-    const u32 m = 1u << (log_n - 1), cols = k + 1;
-    const u32 i = (u32)(t & (m - 1));
-    const u64 ec = t >> (log_n - 1);
-    const u32 c = (u32)(ec % cols);
-    const u64 e = ec / cols;
-    const double2 *sp = spec + e * k * ell * m + i;
-    const double2 *kh = keyh + (u64)c * m + i;
-    double2 a = make_double2(0.0, 0.0);
-    for (u32 rl = 0; rl < k * ell; ++rl) a = cmac_fixed(a, sp[(u64)rl * m], kh[(u64)rl * cols * m]);
-    acc[t] = a;
 }
 
 // One thread per word: dst = [src +] (0, .., 0, body) - e, the bracketed term when the step accumulates.  A thread reads
@@ -291,7 +264,7 @@ int trace_steps(TfheTraceCore<W> *h, const W *in, const double2 *keys, W *out, u
                                  f.log_n, k));
             PFHE_TRY(tfhe_key_herm_launch(f, key, t.keyh, (u64)k * sh.ell * (k + 1), s));
             PFHE_TRY(tfhe_digit_fwd_launch<W>(f, sh, h->d, t.spec, cur * k, s));
-            PFHE_TRY(launch_flat(tfhe_trace_mulacc_kernel, cur * (k + 1) * (f.n / 2), s, t.spec, t.keyh, t.acc, f.log_n, k, sh.ell));
+            PFHE_TRY(tfhe_mulacc_launch(f, t.spec, t.keyh, t.acc, k, sh.ell, k, cur, s));
             PFHE_TRY(tfhe_half_inverse_launch<W>(f, t.acc, h->e, cur * (k + 1), s));
             PFHE_TRY(launch_flat(tfhe_trace_sub_kernel<W>, words, s, src, (const W *)h->body, (const W *)h->e, o, steps.accumulate,
                                  f.log_n, k));

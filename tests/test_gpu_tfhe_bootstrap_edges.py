@@ -1,5 +1,6 @@
-"""GPU parity of the bootstrap's own stages (csrc/pfhe_bootstrap.hip) where the random data and comfortable shapes of
-tests/test_gpu_tfhe_bootstrap.py do not reach:
+"""GPU parity of the bootstrap's own stages (the key switch of csrc/pfhe_bootstrap.hip; tfhe_modswitch_kernel,
+tfhe_acc_init_kernel and tfhe_extract_kernel of csrc/pfhe_tfhe_stages.hip, which every handle around a blind rotation now
+shares) where the random data and comfortable shapes of tests/test_gpu_tfhe_bootstrap.py do not reach:
 
   - the key switch at the shapes of tests/tfhe_ks_shapes.py (groups whose key rows are no multiple of four, every group
     size, a short last group, a mask shorter than a group, 128 / 129 / 256 / 257 columns, 31 / 32 / 33 ciphertexts), on
@@ -23,7 +24,8 @@ out of bounds):
   - tfhe_acc_init_kernel with `high = r > n` and the rotation still reduced for r >= n (X^N TV comes out as +TV): all 21
     handle cases fail, each at exactly the ciphertexts with neg_b = N, while every test of test_gpu_tfhe_bootstrap.py
     still passes.  (`high = r > n` ALONE changes nothing: at r = N it gives rot = N, the index (j - N) mod N = j and j < rot
-    for every j, which is the same -TV[j] by the other branch; all 21 cases pass with it, as they must.)
+    for every j, which is the same -TV[j] by the other branch; all 21 cases pass with it, as they must.)  The rule is
+    MonomialShift's, one copy for this kernel and for tfhe_const_acc_init_kernel (tests/test_gpu_tfhe_cbs_edges.py).
   - ordered_on without its hipStreamWaitEvent: the bootstrap handle's case and the per-step rotation's fail in the first
     round (ciphertexts of the long call that the short one overtook); the whole-loop rotation's case passes, as it shares
     no buffer between calls.  This is a race: a failure under the change was seen, not proven to be certain.

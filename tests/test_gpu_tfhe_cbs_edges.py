@@ -1,5 +1,6 @@
-"""GPU parity of the circuit bootstrap's own stages (csrc/pfhe_cbs.hip: tfhe_cbs_modswitch_kernel, tfhe_cbs_acc_init_kernel,
-tfhe_cbs_extract_kernel) where the random data and comfortable shapes of tests/test_gpu_tfhe_cbs.py do not reach, and the
+"""GPU parity of the circuit bootstrap's stages (csrc/pfhe_tfhe_stages.hip: tfhe_modswitch_kernel with the exponents
+written once per level, tfhe_const_acc_init_kernel, tfhe_extract_kernel; one kernel per stage for every handle around a
+blind rotation) where the random data and comfortable shapes of tests/test_gpu_tfhe_cbs.py do not reach, and the
 stream order of the four handles that own device buffers between calls and had no test of it:
 
   - the handle at N = 2 .. 512 with k up to 3, with inputs whose switched exponents, AFTER the handle's own offset of
@@ -20,14 +21,15 @@ the per-step rotation it would select is reached through k = 2 and k = 3.
 
 What the file was seen to catch on an MI355X, each change built into a copy of the library (none of them moves an access
 out of bounds):
-  1. tfhe_cbs_acc_init_kernel with `high = r > n` and the rotation still reduced for r >= n (X^N TV_l comes out as +TV_l,
-     the change tests/test_gpu_tfhe_bootstrap_edges.py records for the bootstrap's copy): 20 of the 22 handle cases fail,
+  1. the accumulator written from constants (tfhe_const_acc_init_kernel now, then the circuit bootstrap's own copy) with
+     `high = r > n` and the rotation still reduced for r >= n (X^N TV_l comes out as +TV_l, the change
+     tests/test_gpu_tfhe_bootstrap_edges.py records for tfhe_acc_init_kernel): 20 of the 22 handle cases fail,
      each at exactly the GGSW rows of the inputs with neg_b = N.  The two cases with the output basis of drop_bits 1 pass:
      there +-g_0/2 = +-1 on the extracted body is below what the key switch's basis (5, 4) keeps, so they cannot see the
      sign (they do see change 2).  Of tests/test_gpu_tfhe_cbs.py, 1 of 34 fails (test_exact_regime_equals_the_integer_model
      [64-5-2-15-2], whose random data happens to hold a neg_b of N); 33 pass.
-  2. tfhe_cbs_extract_kernel taking its level as a / levels instead of a % levels: all 22 handle cases fail.
-     tests/test_gpu_tfhe_cbs.py sees this one too: 17 of 34 fail.
+  2. the extraction (then the circuit bootstrap's own copy) taking its level as a / levels instead of a % levels: all 22
+     handle cases fail.  tests/test_gpu_tfhe_cbs.py sees this one too: 17 of 34 fail.
   3. ordered_on without its hipStreamWaitEvent: all six stream cases of a form that owns buffers fail (circuit
      bootstrap, CMUX tree fused and general, trace general u32 and u64, packing plan), in 4 runs of 4, in round 0 or 1, at
      ciphertexts of the long call that the short one overtook or at the short call's; the fused trace passes, as it shares
@@ -40,6 +42,17 @@ out of bounds):
      whole file: the circuit bootstrap's; the stream cases alone: the fused tree's), while a loop of the fused tree's case
      on its own failed in 17 of 21 repetitions.  Supposed, not shown: the runtime served that pair from one hardware queue,
      which orders the two streams by itself.  Hence a fresh pair of streams in every round (one_stream_after_another).
+  4. The index arithmetic of the merged stage kernels, one run each of the 22 handle cases (levels 3, or 1 with the output
+     basis of drop_bits 1 at u32; batch 7 to 9; chunk 3 and the default), the unmodified library failing none:
+     (a) tfhe_extract_kernel's level as a / level_period instead of a % level_period (change 2 on the merged kernel): all 22
+         fail;
+     (b) tfhe_const_acc_init_kernel's input as a % per_input instead of a / per_input (the level base kept right): 21 of
+         22 fail; u32-N8-k1-cbs(31, 1) passes, the one-level basis whose +-g_0/2 = +-1 the key switch's basis drops (change 1);
+     (c) tfhe_modswitch_kernel's copies written at (e + c batch) n instead of (e copies + c) n: 12 of 22 fail: the 10 u32
+         cases with 3 levels, u64-N8-k1-cbs(21, 3) and u64-N8-k1-pfks(16, None).  The 8 u64 cases of the shape table, u64-N512
+         and the one-level u32 case pass; supposed, not examined: the change hands an accumulator another input's mask
+         exponents, and the crafted batches are mostly zero there, so a swap of equal rows is not seen.
+     Each is seen by existing cases, so none was added.
 Wall time on an MI355X: 4.7 s for the 29 tests of this file, 1.6 s of it the first import; the slowest case 0.63 s (the
 circuit bootstrap's stream case), the two N = 512 handle cases 0.5 s each (the integer model), every other below 0.12 s.
 """

@@ -26,9 +26,15 @@ def test_bitext_kernels_use_no_scratch_spill_nothing_and_keep_the_key_switchs_wa
     rows = kernel_resources.report(os.path.join(CSRC, "pfhe_bitext.hip"))
     by_name = {r["pretty"]: r for r in rows}
     words = {"unsigned int": 4, "unsigned long long": 8}
-    want = ["%s<%s>" % (kern, w) for kern in ("tfhe_bitext_keyswitch_kernel", "tfhe_bitext_extract_sub_kernel") for w in words]
+    want = ["tfhe_bitext_keyswitch_kernel<%s>" % w for w in words]
     assert sorted(by_name) == sorted(want), sorted(by_name)
+    # extract-and-subtract is the subtracting form of the extraction kernel of pfhe_tfhe_stages.hip
+    stages = {r["pretty"]: r for r in kernel_resources.report(os.path.join(CSRC, "pfhe_tfhe_stages.hip"))}
+    subtracting = ["tfhe_extract_kernel<%s, true>" % w for w in words]
+    by_name.update({name: stages[name] for name in subtracting})
+    want += subtracting
     recorded = open(os.path.join(ROOT, "profiles", "tfhe_bitext_a_kernel_resources.txt")).read()
+    recorded += open(os.path.join(ROOT, "profiles", "tfhe_stages_a_kernel_resources.txt")).read()
     for name in want:
         r = by_name[name]
         assert r.get("ScratchSize", 0) == 0 and r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, r
@@ -39,7 +45,7 @@ def test_bitext_kernels_use_no_scratch_spill_nothing_and_keep_the_key_switchs_wa
         ks = by_name["tfhe_bitext_keyswitch_kernel<%s>" % w]
         assert ks.get("Occupancy", 0) >= plain["tfhe_keyswitch_kernel<%s>" % w]["Occupancy"] > 0, (ks, w)
         assert ks.get("LDS Size", 0) == K_KS_MAX_ROWS * K_KS_TILE_M * size, ks
-        assert by_name["tfhe_bitext_extract_sub_kernel<%s>" % w].get("LDS Size", 0) == 0
+        assert by_name["tfhe_extract_kernel<%s, true>" % w].get("LDS Size", 0) == 0
     header = open(os.path.join(CSRC, "pfhe_tfhe_exact_device.hpp")).read()
     assert "constexpr u32 kKsMaxRows = %d;" % K_KS_MAX_ROWS in header and "kKsRows = 8" in header
 

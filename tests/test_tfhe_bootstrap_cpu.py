@@ -20,10 +20,12 @@ BAD_ARGUMENT, BAD_LENGTH, UNSUPPORTED = 33, 32, 36
 
 def test_bootstrap_kernels_are_reported_and_use_no_scratch():
     import kernel_resources
-    rows = kernel_resources.report(os.path.join(ROOT, "primus-fhe_amd", "csrc", "pfhe_bootstrap.hip"))
+    # the key switch is the file's own kernel; the switch, the accumulator and the extraction are csrc/pfhe_tfhe_stages.hip's
+    csrc = os.path.join(ROOT, "primus-fhe_amd", "csrc")
+    rows = kernel_resources.report(os.path.join(csrc, "pfhe_bootstrap.hip")) + kernel_resources.report(os.path.join(csrc, "pfhe_tfhe_stages.hip"))
     by_name = {r["pretty"]: r for r in rows}
-    must = [f"{kern}<{w}>" for kern in ("tfhe_modswitch_kernel", "tfhe_acc_init_kernel", "tfhe_sample_extract_kernel",
-                                       "tfhe_keyswitch_kernel") for w in ("unsigned int", "unsigned long long")]
+    must = [kern % w for kern in ("tfhe_modswitch_kernel<%s>", "tfhe_acc_init_kernel<%s>", "tfhe_extract_kernel<%s, false>",
+                                  "tfhe_keyswitch_kernel<%s>") for w in ("unsigned int", "unsigned long long")]
     for name in must:
         assert name in by_name, (name, sorted(by_name))
         assert by_name[name].get("ScratchSize", 0) == 0 and by_name[name].get("VGPRs Spill", 0) == 0, by_name[name]

@@ -21,12 +21,17 @@ BAD_LENGTH, BAD_ARGUMENT, NO_DEVICE, UNSUPPORTED = 32, 33, 34, 36
 
 def test_cbs_kernels_use_no_scratch_and_spill_nothing():
     import kernel_resources
-    rows = kernel_resources.report(os.path.join(ROOT, "primus-fhe_amd", "csrc", "pfhe_cbs.hip"))
-    by_name = {r["pretty"]: r for r in rows}
+    csrc = os.path.join(ROOT, "primus-fhe_amd", "csrc")
+    by_name = {r["pretty"]: r for r in kernel_resources.report(os.path.join(csrc, "pfhe_cbs.hip"))}
     words = ("unsigned int", "unsigned long long")
-    want = ["%s<%s>" % (kern, w) for kern in ("tfhe_pfks_kernel", "tfhe_pfksk_add_message_kernel", "tfhe_cbs_modswitch_kernel",
-                                              "tfhe_cbs_acc_init_kernel", "tfhe_cbs_extract_kernel") for w in words]
+    want = [kern % w for kern in ("tfhe_pfks_kernel<%s>", "tfhe_pfksk_add_message_kernel<%s>") for w in words]
     assert sorted(by_name) == sorted(want), sorted(by_name)
+    # the switch, the accumulator from constants and the extraction are the stage kernels of csrc/pfhe_tfhe_stages.hip
+    stages = {r["pretty"]: r for r in kernel_resources.report(os.path.join(csrc, "pfhe_tfhe_stages.hip"))}
+    staged = [kern % w for kern in ("tfhe_modswitch_kernel<%s>", "tfhe_const_acc_init_kernel<%s>",
+                                    "tfhe_extract_kernel<%s, false>") for w in words]
+    by_name.update({name: stages[name] for name in staged})
+    want += staged
     for name in want:
         assert by_name[name].get("ScratchSize", 0) == 0 and by_name[name].get("VGPRs Spill", 0) == 0, by_name[name]
         assert by_name[name].get("SGPRs Spill", 0) == 0, by_name[name]

@@ -1,8 +1,9 @@
 """CPU-side checks of the many-LUT entries (pfhe_tfhe{,32}_modswitch_stride_dev, _bootstrap_create_many_lut,
 _cbs_create_with): the entry points are in the ctypes table, declared in include/pfhe.h and mirrored in include/pfhe.hpp, the
 Python names are exported, every refusal of the two creates and of the strided switch arrives before the device is touched
-and in the stated order, and the compiler's resource report shows the three new kernels for both word types with no scratch
-memory, no spilled register and no LDS, as profiles/tfhe_cbs_b_kernel_resources.txt records them."""
+and in the stated order, and the compiler's resource report shows the stage kernels that do the many-LUT steps
+(csrc/pfhe_tfhe_stages.hip: one kernel per stage for every form) for both word types with no scratch memory, no spilled
+register and no LDS, as profiles/tfhe_stages_a_kernel_resources.txt records them."""
 import ctypes as C
 import os
 import sys
@@ -16,16 +17,19 @@ CALLS = ("modswitch_stride_dev", "bootstrap_create_many_lut", "cbs_create_with")
 NAMES = [pre + g for pre in ("pfhe_tfhe_", "pfhe_tfhe32_") for g in CALLS]
 PUBLIC = ("lwe_modulus_switch_strided_dev", "tfhe_many_lut_test_vector")
 BAD_LENGTH, BAD_ARGUMENT, NO_DEVICE, UNSUPPORTED = 32, 33, 34, 36
-KERNELS = ("tfhe_modswitch_stride_kernel", "tfhe_pattern_acc_init_kernel", "tfhe_multi_extract_kernel")
+# the strided switch, the patterned accumulator and the multi-index extraction are arguments of these; with them in the file,
+# the caller's-test-vector accumulator and the subtracting form of the extraction
+KERNELS = ("tfhe_modswitch_kernel<%s>", "tfhe_const_acc_init_kernel<%s>", "tfhe_extract_kernel<%s, false>",
+           "tfhe_acc_init_kernel<%s>", "tfhe_extract_kernel<%s, true>")
 
 
 def test_many_lut_kernels_use_no_scratch_no_lds_and_spill_nothing():
     import kernel_resources
-    rows = kernel_resources.report(os.path.join(ROOT, "primus-fhe_amd", "csrc", "pfhe_manylut.hip"))
+    rows = kernel_resources.report(os.path.join(ROOT, "primus-fhe_amd", "csrc", "pfhe_tfhe_stages.hip"))
     by_name = {r["pretty"]: r for r in rows}
-    want = ["%s<%s>" % (kern, w) for kern in KERNELS for w in ("unsigned int", "unsigned long long")]
+    want = [kern % w for kern in KERNELS for w in ("unsigned int", "unsigned long long")]
     assert sorted(by_name) == sorted(want), sorted(by_name)
-    recorded = open(os.path.join(ROOT, "profiles", "tfhe_cbs_b_kernel_resources.txt")).read()
+    recorded = open(os.path.join(ROOT, "profiles", "tfhe_stages_a_kernel_resources.txt")).read()
     for name in want:
         r = by_name[name]
         assert r.get("ScratchSize", 0) == 0 and r.get("VGPRs Spill", 0) == 0 and r.get("SGPRs Spill", 0) == 0, r
