@@ -1667,6 +1667,80 @@ int pfhe_tfhe32_lwe_embed_dev(const pfhe_fft *fft, size_t glwe_dimension, const 
 int pfhe_tfhe32_lwe_embed(const pfhe_fft *fft, size_t glwe_dimension, const uint32_t *lwe, size_t len_lwe, uint32_t *glwe_out,
                           size_t len_out);
 
+/* ---- ring packing of LWE ciphertexts by automorphisms: the merge and the pack (u64: no suffix, u32: 32) ----
+ * The reference has neither; the rules are this project's own (Chen, Dai, Kim, Song, "Efficient homomorphic
+ * conversion between (ring) LWE ciphertexts", ACNS 2021, Alg. 3-4), built on rule 1, the trace, their keys and the embedding
+ * of the section above, which they leave bit for bit what they are.  Conventions are that section's.  `keys` is the FULL
+ * trace's key array: log N keys end to end, keys[s-1] the key of t_s = 2^(log N - s + 1) + 1 (pfhe_tfhe*_gksk_generate_dev
+ * with key_in == key_out), whatever the count: no new key, no new format.  The family has a prefix of its own,
+ * pfhe_ringpack_ / pfhe_ringpack32_ (as pfhe_bitext_ / pfhe_bitext32_), and the handle types are pfhe_ringpack /
+ * pfhe_ringpack32; the u32 prototype of each call is the u64 one with uint64_t -> uint32_t and the handle's 32 name.
+ *
+ * Rule A, the merge at `level` l, 1 <= l <= log N (anything else: PFHE_ERR_BAD_ARGUMENT), with s = N / 2^l, t = 2^l + 1 and
+ * key the key of t.  Modulo 2^BITS:
+ *   D = even[e] - X^s odd[e],  S = even[e] + X^s odd[e],  out[e] = S + automorphism(D, key, t).
+ * The words equal, one for one, pfhe_tfhe*_mul_monomial_each_to_dev, a wrapping subtraction and addition,
+ * pfhe_tfhe*_glwe_automorphism_dev and a wrapping addition.  sigma_t fixes X^j for j a multiple of 2s and negates it for j
+ * an odd multiple of s, so out = (even + sigma_t(even)) + X^s (odd + sigma_t(odd)): what either child holds at a multiple
+ * of 2s is doubled, what it holds at an odd multiple of s cancels.  out may be exactly even (a node reads both children
+ * wholly before it writes); any other overlap, and any overlap with odd or key, is refused in the device form.
+ *
+ * Rule B, the pack of `count` LWE ciphertexts per output, 1 <= count <= max_count (anything else: PFHE_ERR_BAD_ARGUMENT),
+ * m = ceil(log2 count).  lwe: batch*count ciphertexts of k*N + 1 words, group e ciphertexts e*count .. e*count + count - 1:
+ *   node_0[i] = embedding of lwe[e*count + i] (rule 4 above) for i < count, the all-zero ciphertext for count <= i < 2^m,
+ *   node_l[r] = merge(node_{l-1}[r], node_{l-1}[r + 2^(m-l)], keys[log N - l], level l),  l = 1..m, r < 2^(m-l),
+ *   glwe_out[e] = trace(node_m[0], keys[0 .. log N - m), steps = log N - m)     (node_m[0] itself when m = log N),
+ * word for word that composition of the public calls, for every shape, batch, chunk and count.  The phase of glwe_out[e] is
+ * N times the phase of ciphertext i at coefficient i * N / 2^m and (up to key-switch noise) 0 at every other one: the stride
+ * is N / 2^m, where pfhe_tfhe*_pack_keyswitch fills coefficients 0..count-1.  The factor N is NOT removed, as the trace's
+ * 2^m is not: the message has to sit log N bits lower in the inputs than it is wanted in the output.  That is the price
+ * against the packing key switch, whose key is about 50 times larger.  len_keys is log N * k*ell*(k+1)*N for every count
+ * (PFHE_ERR_BAD_LENGTH otherwise); glwe_out may overlap neither lwe nor keys.
+ *
+ * create, everything before the device first: the product plan's checks in their order, PFHE_ERR_BAD_ARGUMENT for
+ * glwe_dimension 0, then for max_count 0 or above N.  The handle borrows `fft` and allocates everything here, for `chunk`
+ * OUTPUT ciphertexts (0: a default near 256 MiB): the node buffer of chunk * max(1, 2^(M-1)) GLWE ciphertexts,
+ * M = ceil(log2 max_count), and off the fused shape (k = 1, N <= 2^11) the general form's buffers for as many.  On the fused
+ * shape a pack is one launch per level and chunk (the LWE leaves are read through the embedding's index rule and never
+ * stored; the root runs its trailing trace steps in the same launch), otherwise per level a prepare launch and the
+ * trace's general step.  A call only queues work on `stream` (no allocation, no host synchronisation), so it can be
+ * captured into a HIP graph; a batch larger than the chunk runs chunk by chunk.  One holder at a time (PFHE_ERR_BUSY).  A
+ * call refuses: a null handle, a second holder, level or count out of range, then in the order of
+ * pfhe_tfhe*_glwe_trace_dev: PFHE_ERR_BAD_LENGTH for any length that does not fit the others, (the empty batch is a
+ * no-op,) null pointers, a pointer not aligned to 16 bytes, an overlap (device form), the device. */
+typedef struct pfhe_ringpack pfhe_ringpack;
+typedef struct pfhe_ringpack32 pfhe_ringpack32;
+int pfhe_ringpack_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                         size_t max_count, size_t chunk, pfhe_ringpack **out);
+void pfhe_ringpack_destroy(pfhe_ringpack *h);
+int pfhe_ringpack_in_use(const pfhe_ringpack *h);
+size_t pfhe_ringpack_scratch_bytes(const pfhe_ringpack *h);
+/* rule A: out[e] = S + automorphism(D, key, 2^level + 1), D = even[e] - X^s odd[e], S = even[e] + X^s odd[e], s = N / 2^level */
+int pfhe_ringpack_merge_dev(pfhe_ringpack *h, const uint64_t *even_dev, size_t len_even, const uint64_t *odd_dev,
+                            size_t len_odd, const double *key_dev, size_t len_key, uint32_t level, uint64_t *out_dev, size_t len_out, void *stream);
+int pfhe_ringpack_merge(pfhe_ringpack *h, const uint64_t *even, size_t len_even, const uint64_t *odd, size_t len_odd,
+                        const double *key, size_t len_key, uint32_t level, uint64_t *out, size_t len_out);
+/* rule B: glwe_out[e] = the pack of LWE ciphertexts e*count .. e*count + count - 1: N phi_i at coefficient i N / 2^m */
+int pfhe_ringpack_pack_dev(pfhe_ringpack *h, const uint64_t *lwe_dev, size_t len_lwe, const double *keys_dev,
+                           size_t len_keys, size_t count, uint64_t *glwe_out_dev, size_t len_out, void *stream);
+int pfhe_ringpack_pack(pfhe_ringpack *h, const uint64_t *lwe, size_t len_lwe, const double *keys, size_t len_keys,
+                       size_t count, uint64_t *glwe_out, size_t len_out);
+int pfhe_ringpack32_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                           size_t max_count, size_t chunk, pfhe_ringpack32 **out);
+void pfhe_ringpack32_destroy(pfhe_ringpack32 *h);
+int pfhe_ringpack32_in_use(const pfhe_ringpack32 *h);
+size_t pfhe_ringpack32_scratch_bytes(const pfhe_ringpack32 *h);
+/* rule A: out[e] = S + automorphism(D, key, 2^level + 1), D = even[e] - X^s odd[e], S = even[e] + X^s odd[e], s = N / 2^level */
+int pfhe_ringpack32_merge_dev(pfhe_ringpack32 *h, const uint32_t *even_dev, size_t len_even, const uint32_t *odd_dev,
+                              size_t len_odd, const double *key_dev, size_t len_key, uint32_t level, uint32_t *out_dev, size_t len_out, void *stream);
+int pfhe_ringpack32_merge(pfhe_ringpack32 *h, const uint32_t *even, size_t len_even, const uint32_t *odd, size_t len_odd,
+                          const double *key, size_t len_key, uint32_t level, uint32_t *out, size_t len_out);
+/* rule B: glwe_out[e] = the pack of LWE ciphertexts e*count .. e*count + count - 1: N phi_i at coefficient i N / 2^m */
+int pfhe_ringpack32_pack_dev(pfhe_ringpack32 *h, const uint32_t *lwe_dev, size_t len_lwe, const double *keys_dev,
+                             size_t len_keys, size_t count, uint32_t *glwe_out_dev, size_t len_out, void *stream);
+int pfhe_ringpack32_pack(pfhe_ringpack32 *h, const uint32_t *lwe, size_t len_lwe, const double *keys, size_t len_keys,
+                         size_t count, uint32_t *glwe_out, size_t len_out);
+
 /* ---- a look-up table on encrypted bits: CMUX tree, rotation by encrypted bits, sample extraction (u64: no suffix, u32: 32) ----
  * The reference has neither; the rules are this project's own, built on the arithmetic of
  * pfhe_tfhe*_external_product_to_dev and on the CMUX above, which they leave bit for bit what they are.  A handle has a

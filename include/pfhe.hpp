@@ -292,6 +292,8 @@ struct Fns;
         using TfheCbs = PFHE_TFHE_PLAN(S, cbs_handle, cbs);                                                    \
         using TfheCmuxTree = PFHE_TFHE_PLAN(S, cmux_tree_handle, cmux_tree);                                   \
         using TfheGlweTrace = PFHE_TFHE_PLAN(S, glwe_trace_handle, glwe_trace);                                \
+        using TfheRingPack = Plan<pfhe_ringpack##S, pfhe_ringpack##S##_destroy, pfhe_ringpack##S##_in_use,     \
+                                  pfhe_ringpack##S##_scratch_bytes>;                                   \
         using TfheLut = PFHE_TFHE_PLAN(S, lut_handle, lut);                                                    \
         using TfheBitext = Plan<pfhe_bitext##S, pfhe_bitext##S##_destroy, pfhe_bitext##S##_in_use,             \
                                 pfhe_bitext##S##_scratch_bytes>;                                       \
@@ -385,6 +387,11 @@ struct Fns;
         PFHE_FN(tfhe, S, glwe_automorphism_dev);                                                               \
         PFHE_FN(tfhe, S, glwe_trace);                                                                          \
         PFHE_FN(tfhe, S, glwe_trace_dev);                                                                      \
+        PFHE_FN(ringpack, S, create);                                                                  \
+        PFHE_FN(ringpack, S, merge);                                                                   \
+        PFHE_FN(ringpack, S, merge_dev);                                                               \
+        PFHE_FN(ringpack, S, pack);                                                                    \
+        PFHE_FN(ringpack, S, pack_dev);                                                                \
         PFHE_FN(tfhe, S, lut_create);                                                                          \
         PFHE_FN(tfhe, S, rotate_by_bits);                                                                      \
         PFHE_FN(tfhe, S, rotate_by_bits_dev);                                                                  \
@@ -1177,6 +1184,52 @@ class TfheGlweTraceT : public detail::Fns<W>::TfheGlweTrace {
 };
 using TfheGlweTrace = TfheGlweTraceT<uint64_t>;
 using TfheGlweTrace32 = TfheGlweTraceT<uint32_t>;
+
+// Ring packing of LWE ciphertexts by automorphisms (pfhe_ringpack{,32}_*): the
+// merge at level l (out = S + automorphism(D, key, 2^l + 1), D = even - X^s odd, S = even + X^s odd, s = N / 2^l; out may be
+// even) and the pack of `count` <= max_count LWE ciphertexts per output built from it, the embedding and the trailing trace
+// steps, on ALL log N keys of the full trace: N times the phase of ciphertext i arrives at coefficient slot(i, count) =
+// i N / 2^ceil(log2 count).  The factor N stays in the result: the message has to sit log N bits lower in the inputs, the
+// price against the packing key switch and its far larger key.  Owns the node buffer of `chunk` outputs (and off the fused
+// shape the general form's buffers); one holder at a time.
+template <class W>
+class TfheRingPackT : public detail::Fns<W>::TfheRingPack {
+    using F = detail::Fns<W>;
+    size_t n_ = 0;
+
+  public:
+    // max_count 0: the default, N
+    TfheRingPackT(const FullComplex64FftTable &fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length,
+                  size_t max_count = 0, size_t chunk = 0)
+        : n_(fft.poly_length()) {
+        check(F::ringpack_create(fft.handle(), glwe_dimension, log_basis, decompose_length, max_count ? max_count : n_, chunk,
+                                       &this->h_));
+    }
+    // the coefficient that holds N times the phase of input i of `count`
+    size_t slot(size_t i, size_t count) const {
+        size_t stride = n_;
+        for (size_t c = 1; c < count; c <<= 1) stride >>= 1;
+        return i * stride;
+    }
+    void merge(const W *even, size_t len_even, const W *odd, size_t len_odd, const double *key, size_t len_key, uint32_t level,
+               W *out, size_t len_out) {
+        check(F::ringpack_merge(this->h_, even, len_even, odd, len_odd, key, len_key, level, out, len_out));
+    }
+    void merge_dev(const W *even_dev, size_t len_even, const W *odd_dev, size_t len_odd, const double *key_dev, size_t len_key,
+                   uint32_t level, W *out_dev, size_t len_out, void *stream = nullptr) {
+        check(F::ringpack_merge_dev(this->h_, even_dev, len_even, odd_dev, len_odd, key_dev, len_key, level, out_dev, len_out,
+                                          stream));
+    }
+    void pack(const W *lwe, size_t len_lwe, const double *keys, size_t len_keys, size_t count, W *glwe_out, size_t len_out) {
+        check(F::ringpack_pack(this->h_, lwe, len_lwe, keys, len_keys, count, glwe_out, len_out));
+    }
+    void pack_dev(const W *lwe_dev, size_t len_lwe, const double *keys_dev, size_t len_keys, size_t count, W *glwe_out_dev,
+                  size_t len_out, void *stream = nullptr) {
+        check(F::ringpack_pack_dev(this->h_, lwe_dev, len_lwe, keys_dev, len_keys, count, glwe_out_dev, len_out, stream));
+    }
+};
+using TfheRingPack = TfheRingPackT<uint64_t>;
+using TfheRingPack32 = TfheRingPackT<uint32_t>;
 
 // A look-up table of 2^(tree_depth + rot_bits) entries on encrypted bits: a CMUX tree over the high bits, the rotation by
 // the low bits (acc += external_product_to(X^{2N - 2^(j+log_stride)} acc - acc, the input's key of bit j); out may be inp)

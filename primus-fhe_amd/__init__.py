@@ -27,7 +27,8 @@ from .tfhe import (ApproxSignedBasis, FullComplex64FftTable, TfheBlindRotateCont
                    tfhe_generate_pfksk_dev, TfheCircuitBootstrapContext, tfhe_circuit_bootstrap,
                    tfhe_circuit_bootstrap_dev, TfheCmuxTreeContext, tfhe_cmux, tfhe_cmux_dev, tfhe_cmux_tree,
                    tfhe_cmux_tree_dev, TfheGlweTraceContext, glwe_automorphism, glwe_automorphism_dev, glwe_keyswitch,
-                   glwe_keyswitch_dev, glwe_trace, glwe_trace_dev, tfhe_generate_gksk_dev, lwe_embed_glwe,
+                   glwe_keyswitch_dev, glwe_trace, glwe_trace_dev, TfheRingPackContext, glwe_ring_merge,
+                   glwe_ring_merge_dev, lwe_ring_pack, lwe_ring_pack_dev, tfhe_generate_gksk_dev, lwe_embed_glwe,
                    lwe_embed_glwe_dev, TfheLutContext, tfhe_rotate_by_bits, tfhe_rotate_by_bits_dev, tfhe_lut_eval,
                    tfhe_lut_eval_dev, tfhe_lut_table, TfheBitExtractContext, tfhe_extract_bits, tfhe_extract_bits_dev,
                    tfhe_lut_on_integer_dev, lwe_linear, lwe_linear_dev, tfhe_dense_layer_dev, RandSeed, csprng_keystream_dev,
@@ -56,7 +57,8 @@ __all__ = ["PfheError", "NttError", "RNSError", "U64NttTable", "U64DcrtTable", "
            "lwe_private_keyswitch", "lwe_private_keyswitch_dev", "tfhe_generate_pfksk_dev", "TfheCircuitBootstrapContext",
            "tfhe_circuit_bootstrap", "tfhe_circuit_bootstrap_dev", "TfheCmuxTreeContext", "tfhe_cmux", "tfhe_cmux_dev",
            "tfhe_cmux_tree", "tfhe_cmux_tree_dev", "TfheGlweTraceContext", "glwe_automorphism", "glwe_automorphism_dev",
-           "glwe_keyswitch", "glwe_keyswitch_dev", "glwe_trace", "glwe_trace_dev", "tfhe_generate_gksk_dev", "lwe_embed_glwe",
+           "glwe_keyswitch", "glwe_keyswitch_dev", "glwe_trace", "glwe_trace_dev", "TfheRingPackContext", "glwe_ring_merge",
+           "glwe_ring_merge_dev", "lwe_ring_pack", "lwe_ring_pack_dev", "tfhe_generate_gksk_dev", "lwe_embed_glwe",
            "lwe_embed_glwe_dev", "TfheLutContext", "tfhe_rotate_by_bits", "tfhe_rotate_by_bits_dev", "tfhe_lut_eval",
            "tfhe_lut_eval_dev", "tfhe_lut_table", "TfheBitExtractContext", "tfhe_extract_bits", "tfhe_extract_bits_dev",
            "tfhe_lut_on_integer_dev", "lwe_linear", "lwe_linear_dev", "tfhe_dense_layer_dev", "RandSeed",

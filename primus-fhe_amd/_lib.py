@@ -310,6 +310,16 @@ def _declare(lib: C.CDLL) -> None:
         sig(tp + "gksk_generate_dev", ci, vp, sz, u32, sz, vp, sz, vp, sz, vp, sz, vp, sz, f64p, sz, vp)
         sig(tp + "lwe_embed_dev", ci, vp, sz, vp, sz, vp, sz, vp)
         sig(tp + "lwe_embed", ci, vp, sz, vp, sz, vp, sz)
+        # ring packing by automorphisms: the merge and the pack, both calls of one handle
+        rp = "pfhe_ringpack" + ("32" if tp.endswith("32_") else "")   # a prefix of its own, pfhe_ringpack_ / pfhe_ringpack32_
+        sig(rp + "_create", ci, vp, sz, u32, sz, sz, sz, C.POINTER(vp))
+        sig(rp + "_destroy", None, vp)
+        sig(rp + "_in_use", ci, vp)
+        sig(rp + "_scratch_bytes", sz, vp)
+        sig(rp + "_merge_dev", ci, vp, vp, sz, vp, sz, f64p, sz, u32, vp, sz, vp)
+        sig(rp + "_merge", ci, vp, vp, sz, vp, sz, f64p, sz, u32, vp, sz)
+        sig(rp + "_pack_dev", ci, vp, vp, sz, f64p, sz, sz, vp, sz, vp)
+        sig(rp + "_pack", ci, vp, vp, sz, f64p, sz, sz, vp, sz)
     sig("pfhe_csprng_keystream_dev", ci, ci, vp, vp, sz, vp, sz, vp)   # raw u32 words of the ChaCha20 stream: no width
     sig("pfhe_tfhe_mb_combine_key_dev", ci, vp, sz, sz, sz, f64p, sz, vp, sz, f64p, sz, vp)
     sig("pfhe_extprod_plan_debug_hold", ci, vp, ci)

@@ -137,6 +137,22 @@ struct TfheCmuxTreeCore {
     size_t launch_nodes() const { return chunk << (depth - 1); }
 };
 
+// The GLWE trace handle (pfhe_trace.hip), which the ring-packing handle (pfhe_ring_pack.hip) owns one of off the fused
+// shape.  Owns, in the general form, for `chunk` ciphertexts: the product's scratch (digit spectra, accumulators, the
+// Hermitian parts of one key) and three word buffers: D (k polynomials per ciphertext), the gathered bodies (one) and E
+// (k+1).  Nothing in the fused form.  All allocated at creation.
+template <class W>
+struct TfheTraceCore {
+    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
+    pfhe::PlanGuard guard;          // one holder at a time, successive calls on different streams ordered
+    pfhe::Shape shape{};
+    bool fused = false;
+    size_t chunk = 1, glwe = 0, key_len = 0;
+    TfheProductScratch scratch;
+    W *d = nullptr, *body = nullptr, *e = nullptr;
+    pfhe::DeviceBuffers bufs;  // after the scratch: the word buffers are freed first
+};
+
 namespace pfhe {
 
 // ApproxSignedBasis::new (basis.rs:47-177) with modulus None: its assert!s become PFHE_ERR_BAD_ARGUMENT (log_basis = BITS
@@ -298,5 +314,21 @@ int tfhe_cmux_core_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t l
 template <class W>
 int tfhe_cmux_launch(TfheCmuxTreeCore<W> *h, const W *d0, const W *d1, const double2 *keys, W *out, u64 count,
                      const CmuxSources &at, hipStream_t s);
+
+// The trace of a handle that owns a TfheTraceCore without being one (pfhe_trace.hip, instantiated for u32 and u64): what
+// pfhe_tfhe{,32}_glwe_trace_create runs; one step of the general form on `cur` ciphertexts (at most the core's chunk):
+// dst = [src +] (0, .., 0, sigma_t(gathered_B)) - to_torus(product of sigma_t(gathered_A) with the key), the bracketed term
+// when the step accumulates, and dst may be exactly src; and `steps` on `batch` ciphertexts in either form.  Arguments
+// already checked and the device current; the owner calls them inside its own ordered_on, the core's own guard stays unused.
+struct TraceSteps;  // pfhe_trace_device.hpp
+template <class W>
+int tfhe_trace_core_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t chunk,
+                           TfheTraceCore<W> **out);
+template <class W>
+int tfhe_trace_general_step(TfheTraceCore<W> *h, const W *gathered, const W *src, W *dst, const double2 *key, u32 t,
+                            u32 accumulate, u64 cur, hipStream_t s);
+template <class W>
+int tfhe_trace_steps(TfheTraceCore<W> *h, const W *in, const double2 *keys, W *out, u64 batch, const TraceSteps &steps,
+                     hipStream_t s);
 
 }  // namespace pfhe

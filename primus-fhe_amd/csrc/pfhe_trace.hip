@@ -24,34 +24,12 @@
 #include <memory>
 
 #include "pfhe_tfhe_handles.hpp"
+#include "pfhe_trace_device.hpp"
 
 using namespace pfhe;
 
 namespace pfhe {
 namespace {
-
-// the exponents of one launch sequence, as the kernels take them: step s applies sigma_{t[s]}; accumulate says whether a
-// step adds its result to ACC (the trace) or replaces it (rule 1)
-struct TraceSteps {
-    u32 count, accumulate;
-    u32 t[kMaxLogN];
-};
-
-// t^-1 modulo 2N (mask = 2N - 1) for odd t: t is its own inverse modulo 8, and each Newton step doubles the bits
-__host__ __device__ inline u32 odd_inverse(u32 t, u32 mask) {
-    u32 x = t;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) x *= 2u - t * x;
-    return x & mask;
-}
-
-// sigma_t(p)[i] of a polynomial of n words, t_inv = t^-1 mod 2n
-template <class W>
-__device__ __forceinline__ W sigma_word(const W *p, u32 i, u32 t_inv, u32 n) {
-    const u32 u = (i * t_inv) & (2 * n - 1);
-    const W v = p[u & (n - 1)];
-    return (u & n) ? (W)0 - v : v;
-}
 
 // All steps of one ciphertext in one workgroup (k = 1, N <= 2^11): ACC (2N words) sits in LDS behind the digit spectrum
 // from the first step to the last, as in tfhe_blindrot_loop_kernel.  Per step: sigma_t(A) and sigma_t(B) gathered from
@@ -182,20 +160,6 @@ __global__ __launch_bounds__(kThreads) void tfhe_lwe_embed_kernel(const W *__res
 
 // ---------------- the handle ----------------
 
-// Owns, in the general form, for `chunk` ciphertexts: the product's scratch (digit spectra, accumulators, the Hermitian
-// parts of one key) and three word buffers: D (k polynomials per ciphertext), the gathered bodies (one) and E (k+1).
-// Nothing in the fused form.  All allocated at creation.
-template <class W>
-struct TfheTraceCore {
-    const pfhe_fft *fft = nullptr;  // borrowed (must outlive the handle)
-    PlanGuard guard;                // one holder at a time, successive calls on different streams ordered
-    Shape shape{};
-    bool fused = false;
-    size_t chunk = 1, glwe = 0, key_len = 0;
-    TfheProductScratch scratch;
-    W *d = nullptr, *body = nullptr, *e = nullptr;
-    DeviceBuffers bufs;  // after the scratch: the word buffers are freed first
-};
 struct pfhe_tfhe_glwe_trace_handle : TfheTraceCore<u64> {};
 struct pfhe_tfhe32_glwe_trace_handle : TfheTraceCore<u32> {};
 
@@ -239,39 +203,69 @@ int trace_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis,
     return PFHE_OK;
 }
 
-// `steps` on `batch` ciphertexts, chunk after chunk, every step of a chunk queued before the next chunk starts.  keys: the
-// steps' keys end to end.  Arguments are checked, the device is current.
+}  // namespace
+
+namespace pfhe {
+
+// one step of the general form: a gather launch, the product's Hermitian-part, digit, multiply-accumulate and inverse
+// launches on the k mask rows, and one subtract launch
 template <class W>
-int trace_steps(TfheTraceCore<W> *h, const W *in, const double2 *keys, W *out, u64 batch, const TraceSteps &steps, hipStream_t s) {
+int tfhe_trace_general_step(TfheTraceCore<W> *h, const W *gathered, const W *src, W *dst, const double2 *key, u32 t,
+                            u32 accumulate, u64 cur, hipStream_t s) {
     const pfhe_fft &f = *h->fft;
     const Shape &sh = h->shape;
     const u32 k = sh.k;
+    const u64 words = cur * h->glwe;
+    const TfheProductScratch &p = h->scratch;
+    PFHE_TRY(launch_flat(tfhe_trace_gather_kernel<W>, words, s, gathered, h->d, h->body, odd_inverse(t, 2 * (u32)f.n - 1), f.log_n, k));
+    PFHE_TRY(tfhe_key_herm_launch(f, key, p.keyh, (u64)k * sh.ell * (k + 1), s));
+    PFHE_TRY(tfhe_digit_fwd_launch<W>(f, sh, h->d, p.spec, cur * k, s));
+    PFHE_TRY(tfhe_mulacc_launch(f, p.spec, p.keyh, p.acc, k, sh.ell, k, cur, s));
+    PFHE_TRY(tfhe_half_inverse_launch<W>(f, p.acc, h->e, cur * (k + 1), s));
+    return launch_flat(tfhe_trace_sub_kernel<W>, words, s, src, (const W *)h->body, (const W *)h->e, dst, accumulate, f.log_n, k);
+}
+
+// `steps` on `batch` ciphertexts, chunk after chunk, every step of a chunk queued before the next chunk starts.  keys: the
+// steps' keys end to end.  Arguments are checked, the device is current.
+template <class W>
+int tfhe_trace_steps(TfheTraceCore<W> *h, const W *in, const double2 *keys, W *out, u64 batch, const TraceSteps &steps,
+                     hipStream_t s) {
+    const pfhe_fft &f = *h->fft;
     for (u64 done = 0; done < batch; done += h->chunk) {
         const u64 cur = std::min<u64>(h->chunk, batch - done);
         const W *x = in + done * h->glwe;
         W *o = out + done * h->glwe;
         if (h->fused) {
             PFHE_TRY(launch_groups(tfhe_trace_loop_kernel<W>, cur, lds_bytes(f.log_n) + 2 * f.n * sizeof(W), s, x, keys, o, steps, f.tw,
-                                   sh));
+                                   h->shape));
             continue;
         }
-        const u64 words = cur * h->glwe;
         for (u32 st = 0; st < steps.count; ++st) {
             const W *src = st ? o : x;  // the first step reads the input, the rest the chunk's own output
-            const double2 *key = keys + (u64)st * h->key_len;
-            const TfheProductScratch &t = h->scratch;
-            PFHE_TRY(launch_flat(tfhe_trace_gather_kernel<W>, words, s, src, h->d, h->body, odd_inverse(steps.t[st], 2 * (u32)f.n - 1),
-                                 f.log_n, k));
-            PFHE_TRY(tfhe_key_herm_launch(f, key, t.keyh, (u64)k * sh.ell * (k + 1), s));
-            PFHE_TRY(tfhe_digit_fwd_launch<W>(f, sh, h->d, t.spec, cur * k, s));
-            PFHE_TRY(tfhe_mulacc_launch(f, t.spec, t.keyh, t.acc, k, sh.ell, k, cur, s));
-            PFHE_TRY(tfhe_half_inverse_launch<W>(f, t.acc, h->e, cur * (k + 1), s));
-            PFHE_TRY(launch_flat(tfhe_trace_sub_kernel<W>, words, s, src, (const W *)h->body, (const W *)h->e, o, steps.accumulate,
-                                 f.log_n, k));
+            PFHE_TRY(tfhe_trace_general_step<W>(h, src, src, o, keys + (u64)st * h->key_len, steps.t[st], steps.accumulate, cur, s));
         }
     }
     return PFHE_OK;
 }
+
+template <class W>
+int tfhe_trace_core_create(const pfhe_fft *fft, size_t glwe_dimension, uint32_t log_basis, size_t decompose_length, size_t chunk,
+                           TfheTraceCore<W> **out) {
+    return trace_create<W>(fft, glwe_dimension, log_basis, decompose_length, chunk, out);
+}
+
+#define PFHE_TRACE_CORE(W)                                                                                                       \
+    template int tfhe_trace_core_create<W>(const pfhe_fft *, size_t, uint32_t, size_t, size_t, TfheTraceCore<W> **);             \
+    template int tfhe_trace_general_step<W>(TfheTraceCore<W> *, const W *, const W *, W *, const double2 *, u32, u32, u64,       \
+                                            hipStream_t);                                                                        \
+    template int tfhe_trace_steps<W>(TfheTraceCore<W> *, const W *, const double2 *, W *, u64, const TraceSteps &, hipStream_t);
+PFHE_TRACE_CORE(u32)
+PFHE_TRACE_CORE(u64)
+#undef PFHE_TRACE_CORE
+
+}  // namespace pfhe
+
+namespace {
 
 // What both calls of the handle share behind the lease and their own value check: steps.accumulate is the trace, whose out
 // may be exactly in.  The host form refuses a null pointer before the lengths; the device form's pointer tests follow the
@@ -303,7 +297,7 @@ int trace_call(Form form, TfheTraceCore<W> *h, const W *in, size_t len_in, const
     const StageBuf bufs[] = {stage_in(in, len_in * sizeof(W)), stage_in(keys, len_keys * sizeof(double2)),
                              stage_out(out, len_out * sizeof(W))};
     return handle_call(h->guard, h->fft->device, form, bufs, s, [&](void *const *p, hipStream_t st) {
-        return trace_steps<W>(h, (const W *)p[0], (const double2 *)p[1], (W *)p[2], batch, steps, st);
+        return tfhe_trace_steps<W>(h, (const W *)p[0], (const double2 *)p[1], (W *)p[2], batch, steps, st);
     });
 }
 

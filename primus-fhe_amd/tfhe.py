@@ -1296,6 +1296,96 @@ def lwe_embed_glwe_dev(lwe, glwe_out, fft: FullComplex64FftTable, glwe_dimension
     _lwe_embed(True, lwe, glwe_out, fft, glwe_dimension, stream)
 
 
+# ---- ring packing of LWE ciphertexts by automorphisms (include/pfhe.h: pfhe_ringpack{,32}_*) ----
+
+class TfheRingPackContext(_TorusContext):
+    """Handle of ring packing (include/pfhe.h, pfhe_ringpack{,32}_*): up to `max_count` (default N)
+    LWE ciphertexts under the GLWE key polynomials end to end become ONE GLWE ciphertext, by pairwise merges with one
+    automorphism each and the remaining trace steps, on the key set glwe_trace takes.  Created and checked as
+    TfheGlweTraceContext, then max_count in 1..N; owns the node buffer of chunk * max(1, 2^(M-1)) ciphertexts,
+    M = ceil(log2 max_count), and off the fused shape (k = 1, N <= 2^11) the general form's buffers; `chunk` counts
+    output ciphertexts (0 = the default); one holder at a time (Busy for a second thread)."""
+
+    def __init__(self, fft: FullComplex64FftTable, basis: ApproxSignedBasis, glwe_dimension: int = 1,
+                 max_count: int | None = None, chunk: int = 0):
+        self.max_count = fft.poly_length() if max_count is None else max_count
+        self._open(fft, basis, glwe_dimension, "ringpack", (self.max_count, chunk),
+                   ("_create", "_destroy", "_in_use", "_scratch_bytes"), family="pfhe_ringpack")
+
+    def key_len(self) -> int:
+        """complex values (and torus words) of one key: k * ell rows of a GLWE ciphertext each"""
+        return self.glwe_dimension * self.basis.decompose_length() * self.glwe_len()
+
+    def lwe_len(self) -> int:
+        return self.glwe_dimension * self.fft.poly_length() + 1
+
+    def trace_exponents(self) -> list:
+        """the exponents t_s = 2^(log N - s + 1) + 1, s = 1..log N, whose keys lwe_ring_pack takes in this order: all of
+        them, whatever the count (tfhe_generate_gksk_dev with key_in == key_out)"""
+        log_n = self.fft.log_n
+        return [(1 << (log_n - s + 1)) + 1 for s in range(1, log_n + 1)]
+
+    def slot(self, i: int, count: int) -> int:
+        """the coefficient of the packed phase that holds N times the phase of LWE ciphertext i of `count`: i * N / 2^m,
+        m = ceil(log2 count)"""
+        if not 0 <= i < count <= self.max_count:
+            raise PfheError(33, "need 0 <= i < count <= max_count")
+        return i * (self.fft.poly_length() >> (count - 1).bit_length())
+
+
+def _glwe_ring_merge(words, fourier, even, odd, key, out, level, ctx, name, tail):
+    pe, ne, we = words(even)
+    pd, nd, wd = words(odd)
+    po, no, wo = words(out)
+    pk, nk = fourier(key)
+    _same_width("even, odd and out must have the width of the context's basis", we, wd, wo, ctx._w)
+    check(getattr(lib(), ctx._pre + name)(ctx._h, pe, ne, pd, nd, pk, nk, level, po, no, *tail))
+
+
+def glwe_ring_merge(even: np.ndarray, odd: np.ndarray, key: np.ndarray, out: np.ndarray, level: int,
+                    ctx: TfheRingPackContext) -> None:
+    """The merge of ring packing at `level` l in 1..log N, on host arrays, with s = N / 2^l and t = 2^l + 1:
+    D = even[e] - X^s odd[e], S = even[e] + X^s odd[e], out[e] = S + automorphism(D, key, t) modulo 2^BITS, for a batch of
+    pairs and one key of ctx.key_len() complex values (the key of t).  Word for word tfhe_mul_monomial_each_to_dev, a
+    wrapping subtraction and addition, glwe_automorphism and a wrapping addition.  Where the phases of both inputs are
+    fixed by sigma_t up to a sign at the multiples of 2 s (what the previous level leaves), the phase of out is twice the
+    phase of even at the even multiples of s and twice the phase of odd, moved by s, at the odd ones."""
+    _glwe_ring_merge(_host_words, _host_fourier, even, odd, key, out, level, ctx, "_merge", ())
+
+
+def glwe_ring_merge_dev(even, odd, key, out, level: int, ctx: TfheRingPackContext, stream=None) -> None:
+    """the device form, asynchronous; out may be exactly even, any other overlap (and any with odd or key) is refused"""
+    _glwe_ring_merge(_dev_words, _dev_fourier, even, odd, key, out, level, ctx, "_merge_dev", (_stream(stream),))
+
+
+def _lwe_ring_pack(words, fourier, lwe_in, keys, glwe_out, count, ctx, name, tail):
+    pi, ni, wi = words(lwe_in)
+    po, no, wo = words(glwe_out)
+    pk, nk = fourier(keys)
+    _same_width("lwe_in and glwe_out must have the width of the context's basis", wi, wo, ctx._w)
+    check(getattr(lib(), ctx._pre + name)(ctx._h, pi, ni, pk, nk, count, po, no, *tail))
+
+
+def lwe_ring_pack(lwe_in: np.ndarray, keys: np.ndarray, glwe_out: np.ndarray, count: int, ctx: TfheRingPackContext) -> None:
+    """Ring packing on host arrays: lwe_in holds batch * count LWE ciphertexts of k*N + 1 words (group e is ciphertexts
+    e*count .. e*count + count - 1), keys the log N keys of ctx.trace_exponents() end to end (ALL of them, whatever the
+    count), glwe_out batch GLWE ciphertexts.  With m = ceil(log2 count): node_0[i] = lwe_embed_glwe(lwe_in[e*count + i])
+    (all zero for count <= i < 2^m), node_l[r] = glwe_ring_merge(node_{l-1}[r], node_{l-1}[r + 2^(m-l)], keys[log N - l],
+    level l) for l = 1..m, glwe_out[e] = glwe_trace(node_m[0], keys[0 .. log N - m), steps = log N - m); word for word
+    that composition.  The phase of glwe_out[e] is N times the phase of ciphertext i at coefficient ctx.slot(i, count) =
+    i * N / 2^m and (up to the key switches' noise) zero elsewhere: the stride is N / 2^m, where lwe_pack_keyswitch fills
+    coefficients 0..count-1.  The factor N is NOT removed, as the trace's 2^m is not: the message has to sit log N bits
+    lower in the inputs than it is wanted in the output, which is the price against the packing key switch (whose key is
+    about 50 times larger)."""
+    _lwe_ring_pack(_host_words, _host_fourier, lwe_in, keys, glwe_out, count, ctx, "_pack", ())
+
+
+def lwe_ring_pack_dev(lwe_in, keys, glwe_out, count: int, ctx: TfheRingPackContext, stream=None) -> None:
+    """the device form, asynchronous; glwe_out must overlap neither lwe_in nor keys.  The factor N stays in the result and
+    the message has to sit log N bits lower, as in lwe_ring_pack."""
+    _lwe_ring_pack(_dev_words, _dev_fourier, lwe_in, keys, glwe_out, count, ctx, "_pack_dev", (_stream(stream),))
+
+
 def _torus_dtype(bits: int):
     import torch
     if bits not in (32, 64):
